@@ -47,6 +47,8 @@ Contract (driver):  python bench.py --gpus N --steps K --warmup W     -> one JSO
     on one host core: 20 fixed iterations on the 256^3 cube of BASELINE config 2, its
     wall time reported next to it (`wall_s`); `cpu_baseline_all_cores`: the same sample through the CPU restatement
     under OpenMP on every host core the process may use (thread count in `cores`) -- context, as BASELINE.md section 3 allows.
+  * --dump-outputs DIR (single GPU): X and R as the last timed step left them, float64 .npy files (dump_outputs), so two
+    builds can be compared output for output on the same inputs.
 """
 from __future__ import annotations
 
@@ -82,6 +84,29 @@ def bar_rhs(N, k0=0, k1=None):
     if kb > ka:
         b[ka - k0:kb - k0, N // 4 - 1:3 * N // 4, lo - 1:hi] = mu0 * 1e6
     return b.reshape(-1)
+
+
+DUMP_ROWS = 1 << 21      # rows of X and R kept by --dump-outputs on larger systems: 3 x 16 MiB of float64, under 64 MB
+DUMP_SEED = 20251015
+
+
+def dump_outputs(path, s):
+    """--dump-outputs DIR: what the timed iterations left in the handle, as a caller of ec3d_iterate reads it back with
+    ec3d_download -- the iterate X and the residual R -- written as float64 .npy files.  Systems of more than DUMP_ROWS
+    rows keep the rows of a fixed, seeded sample (index.npy, the same for every run of the same arguments); norms.npy
+    holds ||X|| and ||R|| of the whole vectors."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    x, r = s.download("X"), s.download("R")
+    n = len(x)
+    if n > DUMP_ROWS:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_ROWS))
+    else:
+        idx = np.arange(n)
+    np.save(os.path.join(path, "x.npy"), x[idx])
+    np.save(os.path.join(path, "r.npy"), r[idx])
+    np.save(os.path.join(path, "index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(path, "norms.npy"), np.array([np.linalg.norm(x), np.linalg.norm(r)]))
 
 
 def av_system(refine):
@@ -541,7 +566,15 @@ def main():
                          "it; inlib: the in-library form in this one process")
     ap.add_argument("--no-in-library", action="store_true", help="N > 1: skip the in-library form's sub-record")
     ap.add_argument("--child-timeout", type=int, default=420, help="N > 1: seconds a child form may take")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="single-GPU form: after the timed steps write what they computed (X and R, float64; a seeded "
+                         "sample of rows on large systems) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.gpus > 1 or args.devices is not None or args.force_dist or args.role is not None
+                              or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        ap.error("--dump-outputs runs with the single-GPU form (--gpus 1)")
     if args.rehearse:
         args.force_dist = True
     under_launcher = "WORLD_SIZE" in os.environ and "RANK" in os.environ
@@ -710,6 +743,8 @@ def main():
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         elapsed = t1 - t0
+        if args.dump_outputs:      # before the instrumented pass below moves the iterate on
+            dump_outputs(args.dump_outputs, s)
         # instrumented pass of the same iterations (at most 50 of them: six hipEvents each), library stream
         kernel_ms = s.iterate(W + K + 1, min(K, 50), per_kernel=True)
         spmv_ms = s.time_kernel("spmv", 20)

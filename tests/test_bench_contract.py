@@ -99,3 +99,44 @@ def test_headline_line_carries_the_av_and_256_sub_records():
         assert set(s["kernels"]) == {"k1", "k2", "k3", "k4", "k5"}        # below 32 Mi rows: five launches
         dom = s["dominant"]
         assert dom["frac"] == pytest.approx(dom["achieved"] / 8000.0) and 0.3 < dom["frac"] < 1.2
+
+
+def test_steps_and_dump_outputs_are_checked_before_any_gpu_call(tmp_path):
+    r = _run(["--steps", "0", "--warmup", "1"])
+    assert r.returncode != 0 and "--steps must be at least 1" in r.stderr
+    r = _run(["--gpus", "2", "--devices", "0,0", "--steps", "2", "--dump-outputs", str(tmp_path / "d")])
+    assert r.returncode != 0 and "--dump-outputs runs with the single-GPU form" in r.stderr
+    assert not (tmp_path / "d").exists()
+
+
+@pytest.mark.gpu
+def test_dump_outputs_are_what_the_timed_steps_computed(tmp_path):
+    """--dump-outputs DIR: X and R after exactly --warmup + --steps iterations, float64, the same bits from run to run; R
+    is the residual of that X (b - A X to rounding) and one step more gives another X."""
+    import numpy as np
+    from bench import bar_rhs
+    import eddy_currents_3d_amd as E
+    out = {}
+    for tag, steps in (("a", 5), ("b", 5), ("c", 6)):
+        d = tmp_path / tag
+        r = _run(["--grid", "64", "--steps", str(steps), "--warmup", "2", "--no-cpu-baseline", "--no-spmv-dia",
+                  "--dump-outputs", str(d)])
+        assert r.returncode == 0, r.stdout + r.stderr
+        line = json.loads([l for l in r.stdout.splitlines() if l.strip()][0])
+        assert line["steps"] == steps and line["ms_per_step"] > 0
+        out[tag] = {k: np.load(d / f"{k}.npy") for k in ("x", "r", "index", "norms")}
+        assert sum((d / f"{k}.npy").stat().st_size for k in out[tag]) <= 64 << 20
+    n = 64 ** 3
+    a = out["a"]
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert a["x"].shape == (n,) and np.array_equal(a["index"], np.arange(n, dtype=np.float64))
+    for k in a:
+        assert np.array_equal(a[k], out["b"][k]), k
+    assert not np.array_equal(a["x"], out["c"]["x"])
+    assert a["norms"] == pytest.approx([np.linalg.norm(a["x"]), np.linalg.norm(a["r"])], rel=1e-12)
+    b = bar_rhs(64)
+    with E.EC3DSolver(device=0) as s:
+        s.assemble_poisson(64, 64, 64)
+        true_r = b - s.spmv(a["x"])
+    assert np.linalg.norm(true_r - a["r"]) <= 1e-8 * np.linalg.norm(b)
+    assert np.linalg.norm(a["r"]) < 0.9 * np.linalg.norm(b)       # the iterations did move X

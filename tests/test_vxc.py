@@ -6,7 +6,7 @@ import os
 import numpy as np
 import pytest
 
-from conftest import load_golden
+from conftest import GOLDEN, load_golden
 from eddy_currents_3d_amd import vxc
 
 
@@ -64,13 +64,12 @@ def test_refine_keeps_physical_size():
     assert t["ncells0"] == 24 * int((m.vox == 1).sum())
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src"), reason="reference inputs not present")
 @pytest.mark.parametrize("stem", ["compare_to_Elmer", "ec_src_move_hole", "LIM"])
 def test_shipped_inputs_ingest(stem):
-    """The three shipped ZLIB files decode to the grids the reference reports and to
-    the unknown counts captured from the reference run (g4 fixtures)."""
+    """The three shipped ZLIB files (stored unchanged as tests/golden/g4_<stem>.vxc) decode to the grids the
+    reference reports and to the unknown counts captured from the reference run (g4 fixtures)."""
     g = load_golden("g4_" + stem)
-    m = vxc.read_vxc(f"/root/reference/src/{stem}.vxc")
+    m = vxc.read_vxc(os.path.join(GOLDEN, f"g4_{stem}.vxc"))
     assert m.compression == "ZLIB"
     assert np.array_equal(m.vox, g["vox"])
     t = vxc.domain_tables(m)
