@@ -476,9 +476,8 @@ __global__ __launch_bounds__(256) void k_assemble_sav(GridPar g, const int8_t *_
 static int64_t round_up64(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 
 // dictionary for natively assembled operators: 27 position classes, one per domain, one all-zero
-static int build_device_table(ec3d_ctx *c, GridPar &g, const double *d_valPHYS, int nsub_glob)
+static int build_device_table(ec3d_ctx *c, DevMatrix &A, GridPar &g, const double *d_valPHYS, int nsub_glob)
 {
-    DevMatrix &A = c->A;
     const int ncls = 27 + nsub_glob + 1;
     if (ncls > 256) return 0;
     g.zero_cls = ncls - 1;
@@ -518,7 +517,7 @@ int ec3d_assemble_poisson_device(ec3d_ctx *c, int32_t sdx, int32_t sdy, int32_t 
     EC3D_HIP(hipMalloc(&A.tval, 8));
     const int64_t nblk = (g.nCells + 255) / 256;
     if (c->use_dict) {
-        if (build_device_table(c, g, nullptr, 0) <= 0) return 100;
+        if (build_device_table(c, A, g, nullptr, 0) <= 0) return 100;
         if (!A.cls) { // what the kernel stores through: checked on the host, an error code instead of a fault
             ec3d_set_error("ec3d_assemble_poisson: no class array");
             return 100;
@@ -548,6 +547,29 @@ int ec3d_assemble_poisson_device(ec3d_ctx *c, int32_t sdx, int32_t sdy, int32_t 
     c->sdx = sdx; c->sdy = sdy; c->sdz = sdz;
     c->halo = (k0 == 0 && k1 == sdz) ? 0 : g.kdz;
     return ec3d_prepare_vectors(c);
+}
+
+int ec3d_assemble_poisson_level(ec3d_ctx *c, DevMatrix &A, int32_t sdx, int32_t sdy, int32_t sdz, const double *BND,
+                                const double *delta)
+{
+    GridPar g;
+    memset(&g, 0, sizeof g);
+    int rc = fill_gridpar(g, sdx, sdy, sdz, BND, delta, 1.0);
+    if (rc) return rc;
+    A = DevMatrix();
+    A.n = g.nCells;
+    A.n_pad = g.n_pad = round_up64(A.n, EC3D_TILE);
+    set_offsets(A, g);
+    if (build_device_table(c, A, g, nullptr, 0) <= 0 || !A.cls) {
+        ec3d_set_error("ec3d_set_preconditioner: no class array for a coarse level");
+        return 100;
+    }
+    const int64_t nblk = (g.nCells + 255) / 256;
+    k_assemble_poisson<<<(unsigned)nblk, 256, 0, c->stream>>>(g, nullptr, A.cls);
+    EC3D_HIP(hipGetLastError());
+    EC3D_HIP(hipStreamSynchronize(c->stream));
+    A.nnz = 7 * g.nCells - 2 * ((int64_t)sdy * sdz + (int64_t)sdx * sdz) - 2 * (int64_t)sdx * sdy;
+    return 0;
 }
 
 int ec3d_assemble_device(ec3d_ctx *c, int32_t sdx, int32_t sdy, int32_t sdz, int32_t e0, int32_t e1, int32_t k0,
@@ -633,7 +655,7 @@ int ec3d_assemble_device(ec3d_ctx *c, int32_t sdx, int32_t sdy, int32_t sdz, int
     EC3D_HIP(hipMemcpyAsync(d_val, valPHYS, (size_t)nsub_glob * 5 * 8, hipMemcpyHostToDevice, c->stream));
     EC3D_HIP(hipMemsetAsync(d_err, 0, sizeof(int), c->stream));
     EC3D_HIP(hipMemsetAsync(d_nnz, 0, sizeof(unsigned long long), c->stream));
-    if (!bb && build_device_table(c, g, d_val, nsub_glob) <= 0) return 100;
+    if (!bb && build_device_table(c, c->A, g, d_val, nsub_glob) <= 0) return 100;
     const int64_t nblk = (g.nCells + 255) / 256;
     k_assemble_av<<<(unsigned)nblk, 256, 0, c->stream>>>(g, d_geo, d_geoC, d_uidx, d_val, A.bands, A.cls, A.tail_id,
                                                          A.tile_flag, A.chunk_ptr, A.tcol, A.tval, d_flags, d_err,

@@ -261,6 +261,8 @@ void ec3d_free_matrix(ec3d_ctx *c)
     c->slab_xd = 0;
     ec3d_free_rhs(c);
     ec3d_free_output(c);
+    ec3d_mg_free(c);
+    c->poisson_full = false;
     c->have_matrix = false;
     if (c->vplace_len > 0 && c->own_vectors && c->vec_base) { // keep the placement the search chose for the next matrix of this size
         if (c->parked_vec) (void)hipFree(c->parked_vec);
@@ -1664,7 +1666,13 @@ extern "C" int ec3d_assemble_poisson(ec3d_handle c, int32_t sdx, int32_t sdy, in
                                      const double *delta)
 {
     EC3D_HIP(hipSetDevice(c->device));
-    return ec3d_assemble_poisson_device(c, sdx, sdy, sdz, 0, sdz, BND, delta);
+    const int rc = ec3d_assemble_poisson_device(c, sdx, sdy, sdz, 0, sdz, BND, delta);
+    if (rc == 0) { // what a multigrid hierarchy rediscretises (ec3d_set_preconditioner)
+        c->poisson_full = true;
+        std::copy(BND, BND + 6, c->poisson_bnd);
+        std::copy(delta, delta + 3, c->poisson_delta);
+    }
+    return rc;
 }
 
 extern "C" int ec3d_assemble_poisson_slab(ec3d_handle c, int32_t sdx, int32_t sdy, int32_t sdz, int32_t k0,

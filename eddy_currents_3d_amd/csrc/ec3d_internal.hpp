@@ -274,6 +274,8 @@ struct DevMatrix {
     MatView view() const;
 };
 
+struct ec3d_mg; // multigrid hierarchy (ec3d_mg.hip)
+
 struct ec3d_ctx {
     int device = 0;
     hipStream_t stream = nullptr;         // the stream every launch goes to
@@ -427,6 +429,12 @@ struct ec3d_ctx {
     int out_next = 0;
     bool out_busy = false;
     unsigned out_started = 0;  // bit i: slot i has had an ec3d_vtk_fields_begin (its event is worth waiting for)
+    // the matrix came from ec3d_assemble_poisson on the whole grid (what the multigrid hierarchy rediscretises), with
+    // this BND and spacing; in_multi: the handle is a slab of ec3d_multi (no preconditioner there)
+    bool poisson_full = false;
+    double poisson_bnd[6] = {0, 0, 0, 0, 0, 0}, poisson_delta[3] = {0, 0, 0};
+    bool in_multi = false;
+    ec3d_mg *mg = nullptr; // ec3d_set_preconditioner(EC3D_PRECOND_MG): solves run the preconditioned iteration
 };
 
 // partial-sum slots inside ctx->partials (each nblk doubles)
@@ -609,6 +617,13 @@ int ec3d_assemble_sav_device(ec3d_ctx *c, int32_t sdx, int32_t sdy, int32_t sdz,
                              int32_t nsub_glob, const double *BND, const double *delta, double dt);
 int ec3d_assemble_poisson_device(ec3d_ctx *c, int32_t sdx, int32_t sdy, int32_t sdz, int32_t k0, int32_t k1,
                                  const double *BND, const double *delta);
+// the same assembly (dictionary form) into a matrix of its own: a coarse level of the multigrid hierarchy
+int ec3d_assemble_poisson_level(ec3d_ctx *c, DevMatrix &A, int32_t sdx, int32_t sdy, int32_t sdz, const double *BND,
+                                const double *delta);
+// ec3d_mg.hip
+void ec3d_mg_free(ec3d_ctx *c);
+int ec3d_mg_chunk(const ec3d_ctx *c);             // iterations per poll of the preconditioned loop
+void ec3d_mg_launch_iteration(ec3d_ctx *c, int it); // one preconditioned iteration (after ec3d_launch_begin)
 // ec3d_format.cpp / ec3d_context.hip: dictionary compression of the bands
 int ec3d_build_dictionary_host(HostMatrix &M);
 // ec3d_output.hip

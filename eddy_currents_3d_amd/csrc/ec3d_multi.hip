@@ -644,6 +644,7 @@ int slab_reset(ec3d_multi *m, Slab &s)
     MHIP(hipSetDevice(s.device));
     if (!s.c) {
         int rc = ec3d_create(&s.c, s.device);
+        if (rc == 0) s.c->in_multi = true;
         if (rc) return rc;
         MHIP(hipStreamCreateWithFlags(&s.side, hipStreamNonBlocking));
         for (int v = 0; v < NHALO; ++v)

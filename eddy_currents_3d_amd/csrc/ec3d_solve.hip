@@ -270,13 +270,16 @@ static int solve_core(ec3d_ctx *c, double tol, int32_t itmax, int32_t *iter, dou
 
     // iterations per poll: about 0.4 ms of device work, so an exit is noticed within ~1 ms
     const double est_us = (double)c->A.n_pad * 264.0 / 4.0e6 + 12.0;
-    const int chunk = (int)std::min<double>(32.0, std::max<double>(1.0, 400.0 / est_us));
+    const int chunk = c->mg ? ec3d_mg_chunk(c) : (int)std::min<double>(32.0, std::max<double>(1.0, 400.0 / est_us));
     int64_t launched = 0;
     int ci = 0;
     bool stopped = false;
     while (launched < total && !stopped) {
         const int64_t m = std::min<int64_t>(chunk, total - launched);
-        for (int64_t i = 0; i < m; ++i) ec3d_launch_iteration(c, A, (int)(++launched));
+        for (int64_t i = 0; i < m; ++i) {
+            if (c->mg) ec3d_mg_launch_iteration(c, (int)(++launched)); // ec3d_set_preconditioner (ec3d_mg.hip)
+            else ec3d_launch_iteration(c, A, (int)(++launched));
+        }
         EC3D_HIP(hipGetLastError());
         EC3D_ASYNC_CHECK(c);
         EC3D_HIP(hipMemcpyAsync(&c->state_pinned[ci & 1], c->state, sizeof(SolverState), hipMemcpyDeviceToHost,

@@ -19,9 +19,11 @@ module ec3d_hip
               ec3d_multi_solve, ec3d_multi_upload, ec3d_multi_download, ec3d_multi_solve_resident, &
               ec3d_multi_rhs_step, ec3d_multi_post_update, ec3d_multi_vtk_fields, ec3d_multi_true_residual, &
               ec3d_multi_vtk_fields_begin, ec3d_multi_vtk_fields_wait, ec3d_rccl_unique_id, ec3d_multi_create_rank, &
-              ec3d_multi_plan
+              ec3d_multi_plan, ec3d_set_preconditioner, ec3d_get_preconditioner, ec3d_precond_apply, &
+              EC3D_PRECOND_NONE, EC3D_PRECOND_MG
 
     integer(c_int), parameter :: EC3D_VEC_X = 0, EC3D_VEC_B = 1   ! Uaf, Jaf
+    integer(c_int), parameter :: EC3D_PRECOND_NONE = 0, EC3D_PRECOND_MG = 1   ! ec3d_set_preconditioner
 
     interface
         integer(c_int) function ec3d_create(h, device) bind(C, name="ec3d_create")
@@ -148,6 +150,29 @@ module ec3d_hip
             type(c_ptr), value :: h
             real(c_double), intent(in) :: x(*)
             real(c_double), intent(out) :: y(*)
+        end function
+        ! multigrid preconditioner of a matrix from ec3d_assemble_poisson (include/ec3d_hip.h); zeros = defaults
+        integer(c_int) function ec3d_set_preconditioner(h, kind, pre, post, coarse_sweeps) &
+                bind(C, name="ec3d_set_preconditioner")
+            import :: c_ptr, c_int, c_int32_t
+            type(c_ptr), value :: h
+            integer(c_int), value :: kind
+            integer(c_int32_t), value :: pre, post, coarse_sweeps
+        end function
+        ! dims(3*levels): sdx, sdy, sdz of every level, finest first
+        integer(c_int) function ec3d_get_preconditioner(h, kind, levels, dims) bind(C, name="ec3d_get_preconditioner")
+            import :: c_ptr, c_int, c_int32_t
+            type(c_ptr), value :: h
+            integer(c_int), intent(out) :: kind
+            integer(c_int32_t), intent(out) :: levels
+            integer(c_int32_t), intent(out) :: dims(*)
+        end function
+        ! z = M r, one V-cycle (parity probe)
+        integer(c_int) function ec3d_precond_apply(h, r, z) bind(C, name="ec3d_precond_apply")
+            import :: c_ptr, c_int, c_double
+            type(c_ptr), value :: h
+            real(c_double), intent(in) :: r(*)
+            real(c_double), intent(out) :: z(*)
         end function
         ! cel_bndX/Y/Z, cel_bndUx/y/z (src/EC3D.f90:758-760, :938-940): which = 0..5
         integer(c_int) function ec3d_get_cel_bnd(h, which, count, list) bind(C, name="ec3d_get_cel_bnd")

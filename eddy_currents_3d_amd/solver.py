@@ -68,7 +68,10 @@ EXPORTS = ["sprsbcgstabwr_", "ec3d_invalidate", "ec3d_create", "ec3d_destroy", "
            "ec3d_multi_upload", "ec3d_multi_download", "ec3d_multi_solve", "ec3d_multi_solve_resident",
            "ec3d_multi_rhs_step", "ec3d_multi_post_update", "ec3d_multi_vtk_fields", "ec3d_multi_vtk_fields_begin",
            "ec3d_multi_vtk_fields_wait", "ec3d_multi_iterate_begin",
-           "ec3d_multi_iterate", "ec3d_multi_synchronize", "ec3d_true_residual", "ec3d_multi_true_residual", "ec3d_get_visit_order", "ec3d_probe_csr_multi", "ec3d_multi_spmv", "ec3d_multi_api_calls", "ec3d_multi_plan", "ec3d_multi_halo_rows", "ec3d_rccl_unique_id", "ec3d_multi_create_rank", "ec3d_format_real8_gfortran", "ec3d_multi_iterate_timed", "ec3d_multi_rccl_info"]
+           "ec3d_multi_iterate", "ec3d_multi_synchronize", "ec3d_true_residual", "ec3d_multi_true_residual", "ec3d_get_visit_order", "ec3d_probe_csr_multi", "ec3d_multi_spmv", "ec3d_multi_api_calls", "ec3d_multi_plan", "ec3d_multi_halo_rows", "ec3d_rccl_unique_id", "ec3d_multi_create_rank", "ec3d_format_real8_gfortran", "ec3d_multi_iterate_timed", "ec3d_multi_rccl_info",
+           "ec3d_set_preconditioner", "ec3d_get_preconditioner", "ec3d_precond_apply"]
+PRECOND = dict(none=0, mg=1)   # EC3D_PRECOND_* of include/ec3d_hip.h
+PRECOND_E_MATRIX, PRECOND_E_COARSE = 20, 21   # ec3d_set_preconditioner's refusals
 
 _f64 = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
 _i32 = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
@@ -143,6 +146,9 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.ec3d_device_vector.argtypes = [hp, C.c_int, C.POINTER(hp), C.POINTER(C.c_int64)]
     L.ec3d_solve_resident.argtypes = [hp, C.c_double, C.c_int32, C.POINTER(C.c_int32), hp, C.c_int32]
     L.ec3d_spmv.argtypes = [hp, _f64, _f64]
+    L.ec3d_set_preconditioner.argtypes = [hp, C.c_int, C.c_int32, C.c_int32, C.c_int32]
+    L.ec3d_get_preconditioner.argtypes = [hp, C.POINTER(C.c_int), C.POINTER(C.c_int32), hp]
+    L.ec3d_precond_apply.argtypes = [hp, _f64, _f64]
     L.ec3d_export_csr.argtypes = [hp, C.POINTER(C.c_int32), C.POINTER(C.c_int64), hp, hp, hp]
     L.ec3d_get_cel_bnd.argtypes = [hp, C.c_int, C.POINTER(C.c_int32), hp]
     L.ec3d_get_reduction_geometry.argtypes = [hp, C.c_int, C.POINTER(Geom)]
@@ -234,7 +240,9 @@ def load_library(path: str | None = None) -> C.CDLL:
 
 def _chk(L, rc, what):
     if rc != 0:
-        raise EC3DError(f"{what} failed ({rc}): {L.ec3d_last_error().decode()}")
+        e = EC3DError(f"{what} failed ({rc}): {L.ec3d_last_error().decode()}")
+        e.status = rc
+        raise e
 
 
 def probe_csr(valA, irow, jcol):
@@ -515,6 +523,31 @@ class EC3DSolver:
         y = np.empty(self.n)
         _chk(self.L, self.L.ec3d_spmv(self.h, np.ascontiguousarray(x, np.float64), y), "ec3d_spmv")
         return y
+
+    # ---- preconditioner (a matrix from assemble_poisson only) ------------------------------
+    def set_preconditioner(self, kind: str = "mg", pre: int = 2, post: int = 2, coarse_sweeps: int = 0):
+        """"mg": solves run the right-preconditioned iteration with one multigrid V-cycle as M; "none": the
+        reference's iteration.  Zeros select the library's defaults.  Refusal: EC3DError with .status
+        PRECOND_E_MATRIX or PRECOND_E_COARSE, the handle unchanged."""
+        _chk(self.L, self.L.ec3d_set_preconditioner(self.h, PRECOND[kind], pre, post, coarse_sweeps),
+             "ec3d_set_preconditioner")
+
+    def preconditioner(self):
+        """(kind, [(sdx, sdy, sdz) per level, finest first])"""
+        kind, levels = C.c_int(0), C.c_int32(0)
+        _chk(self.L, self.L.ec3d_get_preconditioner(self.h, C.byref(kind), C.byref(levels), None),
+             "ec3d_get_preconditioner")
+        dims = np.zeros(3 * max(levels.value, 1), np.int32)
+        _chk(self.L, self.L.ec3d_get_preconditioner(self.h, C.byref(kind), C.byref(levels), dims.ctypes.data),
+             "ec3d_get_preconditioner")
+        name = {v: k for k, v in PRECOND.items()}[kind.value]
+        return name, [tuple(int(a) for a in dims[3 * l:3 * l + 3]) for l in range(levels.value)]
+
+    def precond_apply(self, r):
+        """z = M r (one V-cycle) on host vectors."""
+        z = np.empty(self.n)
+        _chk(self.L, self.L.ec3d_precond_apply(self.h, np.ascontiguousarray(r, np.float64), z), "ec3d_precond_apply")
+        return z
 
     # ---- measurement ----------------------------------------------------------------------
     def time_kernel(self, name: str, reps: int = 20) -> float:

@@ -155,6 +155,27 @@ int ec3d_set_structured(ec3d_handle h, int on);
 /* device row of every unknown of the reference's numbering (n entries); identity unless structured */
 int ec3d_get_row_map(ec3d_handle h, int32_t *ref_to_dev);
 
+/* Preconditioner of ec3d_solve / ec3d_solve_resident.  EC3D_PRECOND_NONE (default): the reference's
+ * iteration, unchanged.  EC3D_PRECOND_MG: right-preconditioned BiCGSTAB with restart whose preconditioner M is
+ * one geometric multigrid V-cycle (red-black Gauss-Seidel, `pre` + `post` sweeps per level, mean restriction,
+ * piecewise-constant prolongation, `coarse_sweeps` symmetric sweeps on the coarsest level in one workgroup):
+ *   p^ = M p; v = A p^; alpha = rho/(r0.v); s = r - alpha v; [exit on ||s||/||b||]
+ *   s^ = M s; t = A s^; omega = (t.s)/(t.t); x += alpha p^ + omega s^; r = s - omega t; [exit on ||r||/||b||]
+ * Iteration count, itmax exit, ||b|| = 0 return and restart rule are src/solvers.f90:24-50's; resid_hist keeps
+ * ||S||, ||R|| of the recurrence (R = b - A x).  Only for a matrix from ec3d_assemble_poisson on a handle of its
+ * own: every coarser level reruns that assembly at half the cells and twice the spacing on each axis that is
+ * even and >= 8 (same BND), until no axis halves or a level has <= 4096 rows.  Zeros select the defaults
+ * (pre = post = 2, coarse_sweeps = 16).  The hierarchy is built at once and freed by ec3d_destroy, by a new
+ * matrix or by EC3D_PRECOND_NONE.  Refused, with the handle left as it was: EC3D_PRECOND_E_MATRIX (A-V, CSR,
+ * a slab, a handle of ec3d_multi), EC3D_PRECOND_E_COARSE (the coarsest level has > 4096 rows). */
+enum { EC3D_PRECOND_NONE = 0, EC3D_PRECOND_MG = 1 };
+enum { EC3D_PRECOND_E_MATRIX = 20, EC3D_PRECOND_E_COARSE = 21 };
+int ec3d_set_preconditioner(ec3d_handle h, int kind, int32_t pre, int32_t post, int32_t coarse_sweeps);
+/* kind, number of levels, and (dims != NULL) sdx, sdy, sdz of every level, finest first (3*levels entries) */
+int ec3d_get_preconditioner(ec3d_handle h, int *kind, int32_t *levels, int32_t *dims /* 3*levels */);
+/* z = M r, one V-cycle on host vectors (H2D, apply, D2H).  Parity probe, like ec3d_spmv. */
+int ec3d_precond_apply(ec3d_handle h, const double *r, double *z);
+
 /* ------------------------------------------------------------------------------------------
  * 2b. Multi-rank building blocks (z-slab decomposition, one process per GPU).
  *     No reference counterpart: the reference is serial.  The host

@@ -1,0 +1,83 @@
+"""Time-to-solution of the bar-RHS Poisson solve (BASELINE config 2) with and without the multigrid preconditioner.
+
+    python tools/mg_time_to_solution.py [--sizes 256 512] [--tol 1e-8] [--fixed 200]
+
+One JSON line per size: wall time of ec3d_solve_resident to `tol` with MG (after one untimed solve) and its outer
+iterations; the same without a preconditioner -- a full solve where --fixed is 0 or the size is <= 256, otherwise a
+fixed `--fixed` iterations (tol 1e-300) scaled by the reference's iteration count (tests/golden/g5_cube*.npz `iter`,
+or BASELINE.md section 2b's projection of 7 500 at 512^3), which the line says; and us per V-cycle, from
+ec3d_precond_apply minus ec3d_spmv (both move the same two host vectors; the split by level comes from a
+rocprofv3 --kernel-trace --stats run of this tool, profiles/mg_*.txt)."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+REF_ITERS = {64: 603, 128: 1439, 256: 4097, 512: 7500}
+
+
+def timed(fn, reps=1):
+    fn()
+    t = time.perf_counter()
+    for _ in range(reps):
+        out = fn()
+    return (time.perf_counter() - t) / reps, out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", type=int, nargs="+", default=[256, 512])
+    ap.add_argument("--tol", type=float, default=1e-8)
+    ap.add_argument("--fixed", type=int, default=200)
+    a = ap.parse_args()
+    import eddy_currents_3d_amd as E
+    from bench import bar_rhs
+    for N in a.sizes:
+        out = dict(N=N, tol=a.tol)
+        b = bar_rhs(N)
+        x0 = np.zeros(N ** 3)
+        with E.EC3DSolver() as s:
+            s.assemble_poisson(N, N, N)
+
+            def solve(tol=a.tol, itmax=100000):
+                s.upload("B", b)
+                s.upload("X", x0)
+                s.synchronize()
+                t = time.perf_counter()
+                it, _ = s.solve_resident(tol, itmax)
+                return time.perf_counter() - t, it
+
+            s.set_preconditioner("mg")
+            out["levels"] = s.preconditioner()[1]
+            solve()
+            out["mg_s"], out["mg_iter"] = solve()
+            out["mg_true_residual"] = s.true_residual()[0]
+            r = np.random.Generator(np.random.PCG64(1)).standard_normal(N ** 3)
+            t_apply, _ = timed(lambda: s.precond_apply(r), 3)
+            t_spmv, _ = timed(lambda: s.spmv(r), 3)
+            out["us_per_vcycle"] = round(1e6 * (t_apply - t_spmv), 1)
+            out["mg_us_per_outer_iteration"] = round(1e6 * out["mg_s"] / max(out["mg_iter"], 1), 1)
+            s.set_preconditioner("none")
+            if a.fixed and N > 256:
+                solve(1e-300, a.fixed - 1)
+                t, it = solve(1e-300, a.fixed - 1)
+                out["none_fixed_iters"], out["none_fixed_s"] = it, t
+                out["none_iter"] = REF_ITERS.get(N)
+                out["none_s"] = t / it * out["none_iter"]
+                out["none_note"] = f"{it} fixed iterations scaled to the reference's {out['none_iter']}"
+            else:
+                out["none_s"], out["none_iter"] = solve()
+        out["speedup"] = round(out["none_s"] / out["mg_s"], 1)
+        print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
