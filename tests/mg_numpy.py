@@ -15,6 +15,13 @@ Colour of cell (i, j, k) is (i + j + k) & 1 (0-based), red = 0.  One V-cycle fro
   b_{l+1} = mean of the children's b - A w; V-cycle on level l + 1;
   x = w + P x_{l+1}; post sweeps of (black, red);
   coarsest level: coarse_sweeps sweeps of (red, black, black, red) from x = 0.
+
+`bnd` is what oracle.poisson_csr takes: a scalar for all six faces, or six values in the Fortran order of BND(3, 2),
+BND(d, 1) for d = x, y, z and then BND(d, 2) (the operator uses BND(d, 2) on the first cell of axis d and BND(d, 1) on
+the last; solver.assemble_poisson flattens a (3, 2) array column-major to that order).  Every level gets the same BND.
+
+pbicgstab_gpuorder restates the outer iteration (ec3d_mg_launch_iteration) with the kernels' summation order, so a
+device solve is expected to equal it bit for bit as well.
 """
 from __future__ import annotations
 
@@ -57,7 +64,7 @@ def bands_of(sdx, sdy, sdz, delta, bnd=-0.95):
 
 
 class Level:
-    def __init__(self, dims, delta, bnd=-0.95):
+    def __init__(self, dims, delta, bnd=-0.95):  # bnd: scalar or six faces, as oracle.poisson_csr
         self.dims = dims
         self.sdx, self.sdy, self.sdz = dims
         self.n = self.sdx * self.sdy * self.sdz
@@ -207,3 +214,133 @@ def pbicgstab(mg, b, x0=None, tol=1e-8, itmax=200):
             r0 = r.copy()
             p = r.copy()
             rr0 = r @ r0
+
+
+# ---- GPU-order twin of the outer iteration ------------------------------------------------------------------------
+MG_DOT_BLOCKS = 2048  # EC3D_MG_DOT_BLOCKS
+EXIT_NONE, EXIT_S, EXIT_R = 0, 1, 2  # SolverState::stop_kind: 0 for the itmax exit and ||b|| = 0
+
+
+def _block_sums(v):
+    """block_sum of every 256-value row of v: a 64-lane __shfl_down tree per wave (o = 32 ... 1), then the four wave
+    sums added in order from 0.0."""
+    w = v.reshape(-1, 4, 64)
+    o = 32
+    while o >= 1:
+        w = w[..., :o] + w[..., o:2 * o]
+        o //= 2
+    s = np.zeros(w.shape[0])
+    for q in range(4):
+        s = s + w[:, q, 0]
+    return s
+
+
+def mg_partials(prod):
+    """The per-workgroup partials of one reducing MG kernel (k_mg_spmv_dot, k_mg_s, k_mg_xr) over the row products
+    `prod`: nb = min(2048, ceil(n / 256)) workgroups of 256 threads, thread t of workgroup k adding rows
+    k*256 + t + m*nb*256 in increasing m from 0.0, then block_sum."""
+    n = len(prod)
+    nb = min(MG_DOT_BLOCKS, max(1, -(-n // 256)))
+    T = nb * 256
+    M = -(-n // T)
+    P = np.zeros(M * T)
+    P[:n] = prod
+    P = P.reshape(M, T)
+    acc = np.zeros(T)
+    for m in range(M):
+        acc = acc + P[m]
+    return _block_sums(acc)
+
+
+def mg_scalar_sum(part):
+    """k_mg_scalar: thread t adds part[t], part[t + 256], ... from 0.0, then block_sum."""
+    nr = -(-len(part) // 256)
+    P = np.zeros(nr * 256)
+    P[:len(part)] = part
+    P = P.reshape(nr, 256)
+    acc = np.zeros(256)
+    for m in range(nr):
+        acc = acc + P[m]
+    return float(_block_sums(acc)[0])
+
+
+def mg_dot(a, b):
+    """a.b as one MG reducing kernel and k_mg_scalar sum it (products a[r] * b[r])."""
+    return mg_scalar_sum(mg_partials(a * b))
+
+
+class Identity:
+    """M = I on the operator of `level`: with it, pbicgstab_gpuorder is the reference's iteration."""
+
+    def __init__(self, level):
+        self.levels = [level]
+
+    def apply(self, r):
+        return np.array(r, np.float64, copy=True)
+
+
+def pbicgstab_gpuorder(mg, b, x0, tol, itmax, setup_geom=None, hist_cap=0):
+    """ec3d_mg_launch_iteration restated operation by operation, every sum in the kernels' order.
+
+    Setup as the device's (the solve without a preconditioner's): R = b - A x0, R0 = P = R, ||b|| and R.R summed by
+    the SpMV kernels' geometry setup_geom (oracle.geoms_of(solver)[1]; None: in the MG kernels' order, for a twin
+    without a device).  The row sums of A x are Level.spmv's (oracle_spmv_csr's up to the sign of a zero).
+
+    Returns (x, it, hist_s, hist_r, restarts, exit_kind): hist_* of length hist_cap, NaN where not reached;
+    exit_kind EXIT_S (||S|| / ||b|| < tol: x += alpha p^ only), EXIT_R, or EXIT_NONE (itmax + 1 iterations ran, or
+    ||b|| = 0: x returned unchanged with it = 0)."""
+    A = mg.levels[0].spmv
+    b = np.asarray(b, np.float64)
+    x = np.array(x0, np.float64, copy=True)
+    hs = np.full(hist_cap, np.nan)
+    hr = np.full(hist_cap, np.nan)
+    if setup_geom is None:
+        sdot = mg_dot
+    else:
+        from oracle import oracle as O
+        def sdot(u, v):
+            return O.dot_gpuorder(setup_geom, u, v)
+    R = b - A(x)
+    R0 = R.copy()
+    p = R.copy()
+    bnorm = np.sqrt(sdot(b, b))                       # k_setup
+    if bnorm == 0.0:
+        return x, 0, hs, hr, 0, EXIT_NONE
+    rr0 = sdot(R, R0)                                 # st->rr0[1]
+    it = 0
+    restarts = 0
+    while True:
+        if it > itmax:
+            return x, it, hs, hr, restarts, EXIT_NONE
+        it += 1
+        ph = mg.apply(p)
+        v = A(ph)                                     # k_mg_spmv_dot #1: R0.v
+        alpha = rr0 / mg_dot(R0, v)                   # MG_ALPHA
+        s = R - alpha * v                             # k_mg_s: S.S
+        sn = np.sqrt(mg_dot(s, s))                    # MG_SEXIT
+        if it - 1 < hist_cap:
+            hs[it - 1] = sn
+        if sn / bnorm < tol:
+            x = x + alpha * ph                        # k_mg_xr, the ||S|| exit's branch
+            return x, it, hs, hr, restarts, EXIT_S
+        sh = mg.apply(s)
+        t = A(sh)                                     # k_mg_spmv_dot #2: S.t, t.t
+        omega = mg_dot(s, t) / mg_dot(t, t)           # MG_OMEGA
+        x = x + alpha * ph + omega * sh               # k_mg_xr: R.R, R.R0
+        R = s - omega * t
+        rr = mg_dot(R, R)
+        rr0_new = mg_dot(R, R0)
+        rn = np.sqrt(rr)                              # MG_REXIT
+        if it - 1 < hist_cap:
+            hr[it - 1] = rn
+        if rn / bnorm < tol:
+            return x, it, hs, hr, restarts, EXIT_R
+        beta = (alpha / omega) * rr0_new / rr0
+        if abs(rr0_new) / bnorm < tol:                # k_mg_p: the restart R0 = R, P = R
+            restarts += 1
+            p = R.copy()
+            R0 = R.copy()
+            rr0 = rr                                  # R0 == R: the next rr0 is R.R
+        else:
+            p = R + beta * (p - omega * v)
+            rr0 = rr0_new

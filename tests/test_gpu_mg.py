@@ -3,8 +3,10 @@
 * precond_apply (one V-cycle) == the numpy restatement tests/mg_numpy.py BIT FOR BIT: no reduction enters a V-cycle
   and every elementwise operation is restated in the kernels' order, with fused multiply-add off on both sides;
 * the level operators are the oracle's poisson_csr at the level's dims and spacing: the restatement builds its levels
-  from oracle.poisson_csr, so the bitwise equality above on a 4-level semi-coarsened hierarchy with anisotropic
-  spacing (96x80x72) and on unit vectors at a small size holds only if every device level has the same coefficients;
+  from oracle.poisson_csr, so the bitwise equality above on a 4-level hierarchy (96x80x72: every axis halves at every
+  level, so the spacing stays isotropic), on a semi-coarsened one (48x40x33: z keeps its cells and spacing) and on
+  unit vectors at a small size holds only if every device level has the same coefficients (distinct spacings per axis
+  and distinct BND faces: tests/test_gpu_mg_twin.py);
 * solves to 1e-8 with the bar RHS at 64^3, 128^3, 256^3 in <= 20 outer iterations, the true residual below tol, and at
   256^3 x at g5_cube256's probes within 10 tol of the reference's converged x (4 097 reference iterations);
 * warm start and a forced restart converge; switching back to EC3D_PRECOND_NONE gives a fresh handle's result bit

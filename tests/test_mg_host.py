@@ -1,7 +1,10 @@
 """Multigrid preconditioner, host side (no GPU): the numpy restatement of the V-cycle (tests/mg_numpy.py) converges
-in a grid-independent number of outer iterations, the hierarchy rule gives the documented level dims, and the built
-library exports the C ABI of the feature (include/ec3d_hip.h, ec3d_set_preconditioner)."""
+in a grid-independent number of outer iterations, its GPU-order twin of the outer iteration (pbicgstab_gpuorder) is
+the same iteration as pbicgstab and, with M = I, as the reference's (oracle.bicgstab_wr: exits, restarts, itmax), the
+hierarchy rule gives the documented level dims, and the built library exports the C ABI of the feature
+(include/ec3d_hip.h, ec3d_set_preconditioner)."""
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -26,6 +29,20 @@ def test_restatement_converges_in_few_outer_iterations(oracle, N):
     ((96, 80, 72), [(96, 80, 72), (48, 40, 36), (24, 20, 18), (12, 10, 9)], True),
     ((48, 40, 33), [(48, 40, 33), (24, 20, 33), (12, 10, 33)], True),
     ((67, 67, 67), [(67, 67, 67)], False),
+    ((40, 24, 16), [(40, 24, 16), (20, 12, 8)], True),
+    ((33, 32, 32), [(33, 32, 32), (33, 16, 16), (33, 8, 8)], True),
+    ((32, 33, 32), [(32, 33, 32), (16, 33, 16), (8, 33, 8)], True),
+    ((32, 32, 33), [(32, 32, 33), (16, 16, 33), (8, 8, 33)], True),
+    ((9, 9, 128), [(9, 9, 128), (9, 9, 64), (9, 9, 32)], True),
+    ((128, 9, 9), [(128, 9, 9), (64, 9, 9), (32, 9, 9)], True),
+    ((9, 128, 9), [(9, 128, 9), (9, 64, 9), (9, 32, 9)], True),
+    ((256, 8, 8), [(256, 8, 8), (128, 4, 4)], True),
+    ((512, 4, 4), [(512, 4, 4), (256, 4, 4)], True),
+    ((16, 16, 16), [(16, 16, 16)], True),
+    ((7, 9, 11), [(7, 9, 11)], True),
+    ((3, 3, 3), [(3, 3, 3)], True),
+    ((17, 17, 15), [(17, 17, 15)], False),
+    ((384, 384, 256), [(384, 384, 256), (192, 192, 128), (96, 96, 64), (48, 48, 32), (24, 24, 16), (12, 12, 8)], True),
 ])
 def test_hierarchy_rule(dims, levels, ok):
     got, deltas, good = M.hierarchy_dims(*dims, delta=(1.0, 2.0, 4.0))
@@ -34,6 +51,138 @@ def test_hierarchy_rule(dims, levels, ok):
         for l in range(1, len(got)):
             f = got[l - 1][a] // got[l][a]
             assert deltas[l][a] == deltas[l - 1][a] * f
+
+
+@pytest.mark.parametrize("N", [32, 64])
+def test_gpuorder_twin_is_the_same_iteration(oracle, N):
+    """pbicgstab_gpuorder (sums in the kernels' order) against pbicgstab (numpy's): the same iteration count and exit,
+    the histories within rounding."""
+    mg = M.MG(N, N, N)
+    b = oracle.bar_rhs(N)
+    x, it = M.pbicgstab(mg, b, tol=1e-8)
+    xt, itt, hs, hr, restarts, kind = M.pbicgstab_gpuorder(mg, b, np.zeros(N ** 3), 1e-8, 200, hist_cap=64)
+    assert itt == it and kind in (M.EXIT_S, M.EXIT_R)
+    assert np.isnan(hs[itt:]).all() and np.isnan(hr[itt:]).all()
+    assert np.isnan(hr[itt - 1]) == (kind == M.EXIT_S)
+    assert np.abs(xt - x).max() <= 1e-12 * np.abs(x).max()
+    # the histories of pbicgstab, recomputed from its own iteration: 1e-12 relative while the norms are within 1e-3 of
+    # the first; below that the two summation orders' rounding is amplified (up to 1.2e-11 measured at 1e-8)
+    hs_ref, hr_ref = _pbicgstab_history(mg, b, itt)
+    for h, ref in ((hs[:itt], hs_ref), (hr[:itt], hr_ref)):
+        k = ~np.isnan(h)
+        rel = np.abs(h[k] - ref[k]) / ref[k]
+        big = ref[k] >= 1e-3 * ref[0]
+        assert (rel[big] <= 1e-12).all() and (rel <= 1e-10).all(), rel
+
+
+def _pbicgstab_history(mg, b, iters):
+    """||S||, ||R|| of the first `iters` iterations of pbicgstab's arithmetic (no exit taken)."""
+    A = mg.spmv
+    r = b - A(np.zeros_like(b))
+    r0, p = r.copy(), r.copy()
+    rr0 = r @ r0
+    hs, hr = np.empty(iters), np.empty(iters)
+    for i in range(iters):
+        ph = mg.apply(p)
+        v = A(ph)
+        alpha = rr0 / (r0 @ v)
+        s = r - alpha * v
+        hs[i] = np.linalg.norm(s)
+        sh = mg.apply(s)
+        t = A(sh)
+        omega = (t @ s) / (t @ t)
+        r = s - omega * t
+        hr[i] = np.linalg.norm(r)
+        rr0_new = r @ r0
+        p = r + (alpha / omega) * rr0_new / rr0 * (p - omega * v)
+        rr0 = rr0_new
+    return hs, hr
+
+
+def _reference_exit(it, itmax, hr):
+    if it > itmax:
+        return M.EXIT_NONE
+    return M.EXIT_S if np.isnan(hr[it - 1]) else M.EXIT_R
+
+
+@pytest.mark.parametrize("scale, tol, itmax, exit_kind", [
+    (1.0, 1e-2, 500, M.EXIT_R),        # the ||R|| exit after restarts
+    (1e3, 1e-2, 500, M.EXIT_S),        # the ||S|| exit (the restart test scales with ||b||: none fires)
+    (1.0, 1e-30, 5, M.EXIT_NONE),      # itmax + 1 iterations
+    (1.0, 1e-30, 0, M.EXIT_NONE),
+    (1.0, 1e-30, -1, M.EXIT_NONE),     # no iteration
+])
+def test_twin_with_identity_is_the_reference_iteration(oracle, scale, tol, itmax, exit_kind):
+    """With M = I the twin's iteration is src/solvers.f90:3-50: oracle.bicgstab_wr takes the same exit after the same
+    number of iterations, with the same histories to rounding (the sums differ only in their order).  Cases whose
+    path is stable under a change of summation order (unpreconditioned BiCGSTAB with many restarts is not)."""
+    dims = (12, 10, 9)
+    L = M.Level(dims, (0.00333, 0.00333, 0.00333))
+    I = M.Identity(L)
+    valA, irow, jcol = oracle.poisson_csr(*dims)
+    b = scale * np.random.Generator(np.random.PCG64(31)).standard_normal(L.n)
+    x0 = np.zeros(L.n)
+    cap = 600
+    xr, itr, hsr, hrr = oracle.bicgstab_wr(valA, irow, jcol, b, x0, tol, itmax, hist_cap=cap)
+    xt, itt, hst, hrt, restarts, kind = M.pbicgstab_gpuorder(I, b, x0, tol, itmax, hist_cap=cap)
+    print(f"tol {tol:.0e} itmax {itmax}: it {itt} (reference {itr}), exit {kind}, restarts {restarts}")
+    assert itt == itr
+    assert kind == exit_kind == _reference_exit(itr, itmax, hrr)
+    assert np.array_equal(np.isnan(hst), np.isnan(hsr)) and np.array_equal(np.isnan(hrt), np.isnan(hrr))
+    for h, ref in ((hst, hsr), (hrt, hrr)):
+        k = ~np.isnan(ref)
+        assert np.allclose(h[k], ref[k], rtol=1e-10, atol=0)
+    assert np.abs(xt - xr).max() <= 1e-10 * max(np.abs(xr).max(), 1e-300)
+    if itmax < 500:
+        assert itt == itmax + 1
+    if itmax == -1:
+        assert np.array_equal(xt, x0)
+    if exit_kind == M.EXIT_R:
+        assert restarts >= 1   # the rule of src/solvers.f90:47-49 fired in this case
+
+
+def test_twin_with_zero_rhs_returns_x0(oracle):
+    dims = (12, 10, 9)
+    mg = M.MG(*dims)
+    x0 = np.random.Generator(np.random.PCG64(2)).standard_normal(mg.levels[0].n)
+    x, it, hs, hr, restarts, kind = M.pbicgstab_gpuorder(mg, np.zeros_like(x0), x0, 1e-8, 100, hist_cap=4)
+    assert it == 0 and restarts == 0 and kind == M.EXIT_NONE and np.array_equal(x, x0)
+    assert np.isnan(hs).all() and np.isnan(hr).all()
+
+
+def test_mg_dot_order():
+    """mg_partials against a plain loop in the kernels' order on a small case (n = 3 * 256 + 5: four workgroups, the
+    last with 5 rows), and mg_dot within rounding of the exact sum on a case with 2048 workgroups and a second
+    grid-stride pass."""
+    rng = np.random.Generator(np.random.PCG64(4))
+    a = rng.standard_normal(3 * 256 + 5)
+    nb = 4
+    part = []
+    for k in range(nb):
+        lanes = []
+        for t in range(256):
+            d = 0.0
+            r = k * 256 + t
+            while r < len(a):
+                d = d + a[r] * a[r]
+                r += nb * 256
+            lanes.append(d)
+        waves = []
+        for w in range(4):
+            v = lanes[64 * w:64 * w + 64]
+            o = 32
+            while o >= 1:
+                v = [v[l] + v[l + o] for l in range(o)]
+                o //= 2
+            waves.append(v[0])
+        s = 0.0
+        for w in waves:
+            s = s + w
+        part.append(s)
+    assert np.array_equal(M.mg_partials(a * a), np.array(part))
+    a = rng.standard_normal(2048 * 256 + 1000)
+    exact = math.fsum(a * a)
+    assert abs(M.mg_dot(a, a) - exact) <= 1e-12 * exact
 
 
 def test_library_exports_the_preconditioner():
