@@ -17,6 +17,9 @@
 // runs in place; the prolongation reads w and writes x (another buffer), because its black rows read red neighbours
 // the same launch corrects.
 //
+// EC3D_PRECOND_BLOCK_MG (the structured A-V form) shares the outer iteration's vector kernels;
+// its own kernels (k_avmg_*) are below, behind the single-component ones.
+//
 // A row of a level is read from the level's own device format: class byte + coefficient table in LDS (dictionary form,
 // what every coarse level uses) or the seven band streams (ec3d_set_format(h, 0)).  Bands in offset order
 // (-z, -y, -x, diag, +x, +y, +z); a neighbour beyond the box contributes nothing (its coefficient is 0 there anyway).
@@ -56,9 +59,44 @@ struct MgScalars {
     int pad_;
 };
 
+// A level of the block multigrid of the structured A-V form (EC3D_PRECOND_BLOCK_MG).  One operator serves the three
+// A blocks, whose vectors lie vs doubles apart.  Level 0 reads block 0's class bytes of the handle's matrix, with the
+// plane pitch of the structured form (kdz) and its zero-class padding rows; coarse levels are 7 plain band streams.
+struct AvOp {
+    int sdx, sdy, sdz;
+    int64_t kdz;          // rows between two planes
+    int64_t n;            // rows of one block (level 0: planes * pitch, padding rows included)
+    int64_t vs;           // doubles between the three blocks' vectors
+    const uint8_t *cls;   // class form: coefficient q of row r = table[cls[r] * 16 + q], q < 7, for classes in
+    const double *table;  //   [cls0, cls0 + ncls); any other class is a row without coefficients
+    int cls0, ncls;
+    const double *bands;  // band form (cls == nullptr): bands[q * n_pad + r]
+    int64_t n_pad;
+};
+
+struct AvLevel {
+    AvOp op;
+    int f[3] = {1, 1, 1};     // aggregate width towards the next level per axis (1 or 2)
+    double *bands = nullptr;  // coarse levels: owned
+    double *x = nullptr, *w = nullptr, *b = nullptr; // coarse levels: inside ec3d_mg::vec_base, 3 blocks each
+};
+
 struct ec3d_mg {
+    int kind = EC3D_PRECOND_MG;
     int pre = 2, post = 2, coarse = 16;
     std::vector<MgLevel> lev;
+    std::vector<AvLevel> av;    // EC3D_PRECOND_BLOCK_MG: the A blocks' hierarchy
+    AvOp uop{};                 // ... and the U block's rows (class form, no hierarchy)
+    int32_t *ulist = nullptr;   // U-block rows that hold an unknown: the red ones, then the black ones
+    int64_t nu_red = 0, nu_black = 0;
+    // Projection of the U right-hand side onto the range of the U block (one null vector per conducting component):
+    // ucomp[e] = component of ulist[e]; plist = the U rows ordered by component, pw their weights; chunks = [lo, hi)
+    // of each chunk of plist (within one component), cco = first chunk of each component; upart / umean / inv_w
+    int32_t *ucomp = nullptr, *plist = nullptr, *chunks = nullptr, *cco = nullptr; // inside uidx
+    double *pw = nullptr, *inv_w = nullptr, *upart = nullptr, *umean = nullptr;    // inside ubuf
+    int32_t *uidx = nullptr;
+    double *ubuf = nullptr;
+    int ncomp = 0, nchunk = 0;
     double *vec_base = nullptr; // coarse x, w, b per level, then the fine w, p^, s^
     double *w0 = nullptr, *ph = nullptr, *sh = nullptr;
     double *part = nullptr;     // 2 * EC3D_MG_DOT_BLOCKS
@@ -106,15 +144,15 @@ template <bool DICT> __device__ __forceinline__ void row_coefs(const MgOp &A, co
 struct Pos {
     int i, j, k;
 };
-__device__ __forceinline__ Pos pos_of(const MgOp &A, int64_t r)
+template <class OP> __device__ __forceinline__ Pos pos_of(const OP &A, int64_t r)
 {
     const unsigned ur = (unsigned)r, sx = (unsigned)A.sdx;
     const unsigned ij = ur % (unsigned)A.kdz;
     return Pos{(int)(ij % sx), (int)(ij / sx), (int)(ur / (unsigned)A.kdz)};
 }
 // x at the six neighbours in offset order (-z, -y, -x, +x, +y, +z); 0 beyond the box
-template <class LD>
-__device__ __forceinline__ void neighbours(const MgOp &A, const Pos &p, int64_t r, LD ld, double (&v)[6])
+template <class OP, class LD>
+__device__ __forceinline__ void neighbours(const OP &A, const Pos &p, int64_t r, LD ld, double (&v)[6])
 {
     v[0] = p.k > 0 ? ld(r - A.kdz) : 0.0;
     v[1] = p.j > 0 ? ld(r - A.sdx) : 0.0;
@@ -503,6 +541,383 @@ void launch_vcycle(ec3d_mg *m, Gate g, const double *r, double *z, hipStream_t s
     }
 }
 
+// ---- block multigrid of the structured A-V form (EC3D_PRECOND_BLOCK_MG) ----------------------
+// The kernels below restate k_mg_smooth / k_mg_restrict / k_mg_prolong / k_mg_coarse for the A blocks with three
+// right-hand sides per launch (the blocks' vectors vs apart: one read of a row's coefficients serves all three), rows
+// without a diagonal (level 0's padding rows) producing 0, and aggregates of ceil-halving (an odd axis ends in an
+// aggregate of one cell).  tests/avmg_numpy.py restates them operation by operation.
+#define EC3D_AVMG_MAXCLS 64 // classes of one block the smoothers' table holds (the native structured form: 36 A, 27 U)
+
+__device__ __forceinline__ void av_load_table(const AvOp &A, double *tbl)
+{
+    if (!A.cls) return;
+    for (int q = threadIdx.x; q < A.ncls * 7; q += blockDim.x) tbl[q] = A.table[(size_t)(A.cls0 + q / 7) * 16 + q % 7];
+    __syncthreads();
+}
+template <bool DICT> __device__ __forceinline__ void av_coefs(const AvOp &A, const double *tbl, int64_t r, double (&c)[7])
+{
+    if constexpr (DICT) {
+        const unsigned k = (unsigned)((int)A.cls[r] - A.cls0);
+        if (k >= (unsigned)A.ncls) {
+#pragma unroll
+            for (int q = 0; q < 7; ++q) c[q] = 0.0;
+            return;
+        }
+        const double *t = tbl + 7 * k;
+#pragma unroll
+        for (int q = 0; q < 7; ++q) c[q] = t[q];
+    } else {
+#pragma unroll
+        for (int q = 0; q < 7; ++q) c[q] = A.bands[(size_t)q * A.n_pad + r];
+    }
+}
+template <bool DICT> __device__ __forceinline__ double av_diag(const AvOp &A, const double *tbl, int64_t r)
+{
+    if constexpr (DICT) {
+        const unsigned k = (unsigned)((int)A.cls[r] - A.cls0);
+        return k < (unsigned)A.ncls ? tbl[7 * k + 3] : 0.0;
+    } else {
+        return A.bands[(size_t)3 * A.n_pad + r];
+    }
+}
+
+// Half-sweep of one colour on the three blocks, in place (k_mg_smooth).  Level 0, bytes per cell: class 1 + 3 x (b 8 +
+// x 8 read + x 8 written) = 73 B; init: 1 + 3 x 16 = 49 B.
+template <bool DICT>
+__global__ __launch_bounds__(256) void k_avmg_smooth(AvOp A, Gate g, int colour, int init, double *__restrict__ x,
+                                                     const double *__restrict__ b)
+{
+    __shared__ double tbl[EC3D_AVMG_MAXCLS * 7];
+    if (gated_off(g)) return;
+    if (DICT) av_load_table(A, tbl);
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= A.n) return;
+    const Pos p = pos_of(A, r);
+    if (((p.i + p.j + p.k) & 1) != colour) {
+        if (init)
+            for (int d = 0; d < 3; ++d) x[d * A.vs + r] = 0.0;
+        return;
+    }
+    double c[7];
+    av_coefs<DICT>(A, tbl, r, c);
+    const bool live = c[3] != 0.0 && p.j < A.sdy;
+    for (int d = 0; d < 3; ++d) {
+        const int64_t o = d * A.vs;
+        double val = 0.0;
+        if (live && init) {
+            val = b[o + r] / c[3];
+        } else if (live) {
+            double v[6];
+            neighbours(A, p, r, [&](int64_t q) { return x[o + q]; }, v);
+            val = gs_value(c, v, b[o + r]);
+        }
+        x[o + r] = val;
+    }
+}
+
+// Residual + mean restriction over the aggregate's actual children (k_mg_restrict), three blocks.
+template <bool DICT>
+__global__ __launch_bounds__(256) void k_avmg_restrict(AvOp A, AvOp C, int fx, int fy, int fz, Gate g,
+                                                       const double *__restrict__ w, const double *__restrict__ b,
+                                                       double *__restrict__ bc)
+{
+    __shared__ double tbl[EC3D_AVMG_MAXCLS * 7];
+    if (gated_off(g)) return;
+    if (DICT) av_load_table(A, tbl);
+    const int64_t rc = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (rc >= C.n) return;
+    const Pos pc = pos_of(C, rc);
+    double s[3] = {0.0, 0.0, 0.0};
+    int cnt = 0;
+    for (int dk = 0; dk < fz && pc.k * fz + dk < A.sdz; ++dk)
+        for (int dj = 0; dj < fy && pc.j * fy + dj < A.sdy; ++dj)
+            for (int di = 0; di < fx && pc.i * fx + di < A.sdx; ++di) {
+                const Pos p{pc.i * fx + di, pc.j * fy + dj, pc.k * fz + dk};
+                const int64_t r = (int64_t)p.k * A.kdz + (int64_t)p.j * A.sdx + p.i;
+                double c[7];
+                av_coefs<DICT>(A, tbl, r, c);
+                ++cnt;
+                for (int d = 0; d < 3; ++d) {
+                    const int64_t o = d * A.vs;
+                    double v[6];
+                    neighbours(A, p, r, [&](int64_t q) { return w[o + q]; }, v);
+                    double t = b[o + r];
+                    t = t - c[0] * v[0];
+                    t = t - c[1] * v[1];
+                    t = t - c[2] * v[2];
+                    t = t - c[3] * w[o + r];
+                    t = t - c[4] * v[3];
+                    t = t - c[5] * v[4];
+                    t = t - c[6] * v[5];
+                    s[d] = s[d] + t;
+                }
+            }
+    const double mean = 1.0 / (double)cnt;
+    for (int d = 0; d < 3; ++d) bc[d * C.vs + rc] = s[d] * mean;
+}
+
+// Prolongation + correction fused with the first post half-sweep (black), three blocks (k_mg_prolong).  A row without
+// a diagonal is 0, as the corrected value its neighbours read.
+template <bool DICT>
+__global__ __launch_bounds__(256) void k_avmg_prolong(AvOp A, AvOp C, int fx, int fy, int fz, Gate g,
+                                                      const double *__restrict__ w, const double *__restrict__ xc,
+                                                      const double *__restrict__ b, double *__restrict__ x)
+{
+    __shared__ double tbl[EC3D_AVMG_MAXCLS * 7];
+    if (gated_off(g)) return;
+    if (DICT) av_load_table(A, tbl);
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= A.n) return;
+    const Pos p = pos_of(A, r);
+    double c[7];
+    av_coefs<DICT>(A, tbl, r, c);
+    const bool live = c[3] != 0.0 && p.j < A.sdy;
+    const auto parent = [&](const Pos &q) {
+        return (int64_t)(q.k / fz) * C.kdz + (int64_t)(q.j / fy) * C.sdx + q.i / fx;
+    };
+    const bool red = ((p.i + p.j + p.k) & 1) == 0;
+    for (int d = 0; d < 3; ++d) {
+        const int64_t o = d * A.vs, oc = d * C.vs;
+        double val = 0.0;
+        if (live && red) {
+            val = w[o + r] + xc[oc + parent(p)];
+        } else if (live) {
+            const auto corrected = [&](int64_t q) {
+                if (av_diag<DICT>(A, tbl, q) == 0.0) return 0.0;
+                return w[o + q] + xc[oc + parent(pos_of(A, q))];
+            };
+            double v[6];
+            neighbours(A, p, r, corrected, v);
+            val = gs_value(c, v, b[o + r]);
+        }
+        x[o + r] = val;
+    }
+}
+
+// Coarsest level (k_mg_coarse): workgroup d solves block d; x of the level's cells in LDS, indexed by cell (level 0's
+// rows are pitched: cell (i, j, k) is row k kdz + j sdx + i).
+template <bool DICT>
+__global__ __launch_bounds__(EC3D_MG_COARSE_THREADS) void k_avmg_coarse(AvOp A, Gate g, int sweeps,
+                                                                        const double *__restrict__ b,
+                                                                        double *__restrict__ x)
+{
+    constexpr int RPT = EC3D_MG_COARSE_ROWS / EC3D_MG_COARSE_THREADS;
+    __shared__ double xs[EC3D_MG_COARSE_ROWS];
+    __shared__ double tbl[EC3D_AVMG_MAXCLS * 7];
+    if (gated_off(g)) return;
+    if (DICT) av_load_table(A, tbl);
+    AvOp Ac = A; // the same grid in cell numbering
+    Ac.kdz = (int64_t)A.sdx * A.sdy;
+    const int64_t ncell = Ac.kdz * A.sdz, o = (int64_t)blockIdx.x * A.vs;
+    double br[RPT];
+    Pos pr[RPT];
+    int colr[RPT];
+#pragma unroll
+    for (int q = 0; q < RPT; ++q) {
+        const int64_t e = threadIdx.x + (int64_t)q * EC3D_MG_COARSE_THREADS;
+        colr[q] = -1;
+        if (e < ncell) {
+            pr[q] = pos_of(Ac, e);
+            colr[q] = (pr[q].i + pr[q].j + pr[q].k) & 1;
+            br[q] = b[o + (int64_t)pr[q].k * A.kdz + (int64_t)pr[q].j * A.sdx + pr[q].i];
+            xs[e] = 0.0;
+        }
+    }
+    __syncthreads();
+    for (int s = 0; s < sweeps; ++s)
+        for (int h = 0; h < 4; ++h) {
+            const int colour = (h == 0 || h == 3) ? 0 : 1;
+#pragma unroll
+            for (int q = 0; q < RPT; ++q) {
+                if (colr[q] != colour) continue;
+                const int64_t e = threadIdx.x + (int64_t)q * EC3D_MG_COARSE_THREADS;
+                double c[7], v[6];
+                av_coefs<DICT>(A, tbl, (int64_t)pr[q].k * A.kdz + (int64_t)pr[q].j * A.sdx + pr[q].i, c);
+                if (c[3] == 0.0) continue; // stays 0
+                neighbours(Ac, pr[q], e, [&](int64_t t) { return xs[t]; }, v);
+                xs[e] = gs_value(c, v, br[q]);
+            }
+            __syncthreads();
+        }
+#pragma unroll
+    for (int q = 0; q < RPT; ++q) {
+        const int64_t e = threadIdx.x + (int64_t)q * EC3D_MG_COARSE_THREADS;
+        if (e < ncell) x[o + (int64_t)pr[q].k * A.kdz + (int64_t)pr[q].j * A.sdx + pr[q].i] = xs[e];
+    }
+}
+
+// Galerkin coarse operator of piecewise-constant aggregation: coarse band q = the sum of the children's couplings that
+// cross the aggregate's face on that side (to a cell inside the box), the diagonal = the children's diagonals plus their
+// couplings inside the aggregate; children k outermost, i innermost, within a child the diagonal first and then the
+// couplings in offset order; times `scale` = 1 / (2 * nominal children).  One thread per coarse cell.
+template <bool DICT>
+__global__ __launch_bounds__(256) void k_avmg_galerkin(AvOp F, AvOp C, int fx, int fy, int fz, double scale,
+                                                       double *__restrict__ bands)
+{
+    __shared__ double tbl[EC3D_AVMG_MAXCLS * 7];
+    if (DICT) av_load_table(F, tbl);
+    const int64_t rc = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (rc >= C.n) return;
+    const Pos pc = pos_of(C, rc);
+    double D = 0.0, B[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    const int ext[3] = {F.sdx, F.sdy, F.sdz}, f[3] = {fx, fy, fz}, agg[3] = {pc.i, pc.j, pc.k};
+    // offset order: axis and direction of band q (q = 3, the diagonal, is skipped)
+    const int qax[7] = {2, 1, 0, -1, 0, 1, 2}, qdir[7] = {-1, -1, -1, 0, 1, 1, 1};
+    for (int dk = 0; dk < fz && pc.k * fz + dk < F.sdz; ++dk)
+        for (int dj = 0; dj < fy && pc.j * fy + dj < F.sdy; ++dj)
+            for (int di = 0; di < fx && pc.i * fx + di < F.sdx; ++di) {
+                const int pos[3] = {pc.i * fx + di, pc.j * fy + dj, pc.k * fz + dk};
+                const int64_t r = (int64_t)pos[2] * F.kdz + (int64_t)pos[1] * F.sdx + pos[0];
+                double c[7];
+                av_coefs<DICT>(F, tbl, r, c);
+                D = D + c[3];
+#pragma unroll
+                for (int q = 0; q < 7; ++q) {
+                    if (q == 3) continue;
+                    const int a = qax[q], nb = pos[a] + qdir[q];
+                    if (nb < 0 || nb >= ext[a]) continue;
+                    if (nb / f[a] == agg[a]) D = D + c[q];
+                    else B[q] = B[q] + c[q];
+                }
+            }
+#pragma unroll
+    for (int q = 0; q < 7; ++q) bands[(size_t)q * C.n_pad + rc] = (q == 3 ? D : B[q]) * scale;
+}
+
+// Gauss-Seidel half-sweep of the U block over a list of its unknowns' rows (one colour); init: from zero, x = b / d.
+// The right-hand side of a row is b - umean[its component] (the projection below).
+__global__ __launch_bounds__(256) void k_avmg_usweep(AvOp U, Gate g, const int32_t *__restrict__ list,
+                                                     const int32_t *__restrict__ comp, const double *__restrict__ umean,
+                                                     int64_t count, int init, double *__restrict__ x,
+                                                     const double *__restrict__ b)
+{
+    __shared__ double tbl[EC3D_AVMG_MAXCLS * 7];
+    if (gated_off(g)) return;
+    av_load_table(U, tbl);
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= count) return;
+    const int64_t r = list[e];
+    double c[7];
+    av_coefs<true>(U, tbl, r, c);
+    const double bb = b[r] - umean[comp[e]];
+    double val = 0.0;
+    if (c[3] != 0.0 && init) {
+        val = bb / c[3];
+    } else if (c[3] != 0.0) {
+        double v[6];
+        neighbours(U, pos_of(U, r), r, [&](int64_t q) { return x[q]; }, v);
+        val = gs_value(c, v, bb);
+    }
+    x[r] = val;
+}
+
+// The U block of the A-V system is singular: a constant on one conducting component (A = 0) is a null vector of the
+// whole operator, and the U rows' left null vector is w = the product over the axes of 1/2 where the cell misses a
+// neighbour along that axis, 1 elsewhere (the one-sided rows carry the factor 2; exact where a missing neighbour is
+// on one side only, an approximation otherwise -- M stays a fixed linear operator either way).  Gauss-Seidel on a right-hand side
+// with a component along that null direction does not converge, and the outer iteration stalls; so the U sweeps see
+// b - (w.b / w.1) on each component, which lies in the U block's range.  The weighted sums run in a fixed order:
+// chunks of EC3D_AVMG_UCHUNK entries of one component (thread t adds entries t, t + 256, ..., then the workgroup
+// tree), then per component the chunks' partials as k_mg_scalar sums them.
+#define EC3D_AVMG_UCHUNK 4096
+__global__ __launch_bounds__(256) void k_avmg_upart(Gate g, const int32_t *__restrict__ plist,
+                                                    const double *__restrict__ pw, const int32_t *__restrict__ chunks,
+                                                    const double *__restrict__ b, double *__restrict__ upart)
+{
+    __shared__ double lds[8];
+    if (gated_off(g)) return;
+    const int lo = chunks[2 * blockIdx.x], hi = chunks[2 * blockIdx.x + 1];
+    double a = 0.0;
+    for (int e = lo + (int)threadIdx.x; e < hi; e += (int)blockDim.x) a = a + pw[e] * b[plist[e]];
+    a = block_sum(a, lds);
+    if (threadIdx.x == 0) upart[blockIdx.x] = a;
+}
+__global__ __launch_bounds__(256) void k_avmg_umean(Gate g, const int32_t *__restrict__ cco,
+                                                    const double *__restrict__ upart, const double *__restrict__ inv_w,
+                                                    double *__restrict__ umean)
+{
+    __shared__ double lds[8];
+    if (gated_off(g)) return;
+    const int lo = cco[blockIdx.x], hi = cco[blockIdx.x + 1];
+    double a = 0.0;
+    for (int q = lo + (int)threadIdx.x; q < hi; q += (int)blockDim.x) a += upart[q];
+    a = block_sum(a, lds);
+    if (threadIdx.x == 0) umean[blockIdx.x] = a * inv_w[blockIdx.x];
+}
+
+// partials of a.y (slot 0) and, with two, y.y (slot 1), the products summed as k_mg_spmv_dot sums them
+__global__ __launch_bounds__(256) void k_avmg_dot(int64_t n, Gate g, const double *__restrict__ a,
+                                                  const double *__restrict__ y, int two, double *__restrict__ part)
+{
+    __shared__ double lds[8];
+    if (gated_off(g)) return;
+    double d0 = 0.0, d1 = 0.0;
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x) {
+        const double s = y[r];
+        d0 = d0 + a[r] * s;
+        d1 = d1 + s * s;
+    }
+    d0 = block_sum(d0, lds);
+    if (threadIdx.x == 0) part[blockIdx.x] = d0;
+    if (two) {
+        d1 = block_sum(d1, lds);
+        if (threadIdx.x == 0) part[gridDim.x + blockIdx.x] = d1;
+    }
+}
+
+// z = M r of the block multigrid (enqueued): one V-cycle on each A block, the U block's sweeps.  r, z: device vectors
+// of the structured form (4 blocks of nCd rows).
+void launch_avcycle(ec3d_mg *m, Gate g, const double *r, double *z, hipStream_t s)
+{
+    const int L = (int)m->av.size();
+    for (int l = 0; l + 1 < L; ++l) {
+        AvLevel &F = m->av[(size_t)l];
+        const AvOp &A = F.op;
+        const bool dict = l == 0;
+        const double *B = l == 0 ? r : F.b;
+        double *W = l == 0 ? m->w0 : F.w;
+        for (int sw = 0; sw < m->pre; ++sw) {
+            MG_LAUNCH(k_avmg_smooth, blocks_of(A.n), 256, A, g, 0, sw == 0, W, B);
+            MG_LAUNCH(k_avmg_smooth, blocks_of(A.n), 256, A, g, 1, 0, W, B);
+        }
+        const AvLevel &C = m->av[(size_t)l + 1];
+        MG_LAUNCH(k_avmg_restrict, blocks_of(C.op.n), 256, A, C.op, F.f[0], F.f[1], F.f[2], g, W, B, C.b);
+    }
+    {
+        AvLevel &K = m->av[(size_t)L - 1];
+        const bool dict = L == 1;
+        MG_LAUNCH(k_avmg_coarse, 3, EC3D_MG_COARSE_THREADS, K.op, g, m->coarse, L == 1 ? r : K.b, L == 1 ? z : K.x);
+    }
+    for (int l = L - 2; l >= 0; --l) {
+        AvLevel &F = m->av[(size_t)l];
+        const AvOp &A = F.op;
+        const bool dict = l == 0;
+        const double *B = l == 0 ? r : F.b;
+        double *W = l == 0 ? m->w0 : F.w;
+        double *X = l == 0 ? z : F.x;
+        const AvLevel &C = m->av[(size_t)l + 1];
+        MG_LAUNCH(k_avmg_prolong, blocks_of(A.n), 256, A, C.op, F.f[0], F.f[1], F.f[2], g, W, C.x, B, X);
+        MG_LAUNCH(k_avmg_smooth, blocks_of(A.n), 256, A, g, 0, 0, X, B);
+        for (int sw = 1; sw < m->post; ++sw) {
+            MG_LAUNCH(k_avmg_smooth, blocks_of(A.n), 256, A, g, 1, 0, X, B);
+            MG_LAUNCH(k_avmg_smooth, blocks_of(A.n), 256, A, g, 0, 0, X, B);
+        }
+    }
+    const int64_t ub = 3 * m->av[0].op.vs; // the U block
+    if (m->ncomp) {
+        k_avmg_upart<<<(unsigned)m->nchunk, 256, 0, s>>>(g, m->plist, m->pw, m->chunks, r + ub, m->upart);
+        k_avmg_umean<<<(unsigned)m->ncomp, 256, 0, s>>>(g, m->cco, m->upart, m->inv_w, m->umean);
+    }
+    for (int sw = 0; sw < m->pre + m->post; ++sw) {
+        if (m->nu_red)
+            k_avmg_usweep<<<blocks_of(m->nu_red), 256, 0, s>>>(m->uop, g, m->ulist, m->ucomp, m->umean, m->nu_red,
+                                                                sw == 0, z + ub, r + ub);
+        if (m->nu_black)
+            k_avmg_usweep<<<blocks_of(m->nu_black), 256, 0, s>>>(m->uop, g, m->ulist + m->nu_red, m->ucomp + m->nu_red,
+                                                                  m->umean, m->nu_black, 0, z + ub, r + ub);
+    }
+}
+
 void free_level_matrix(DevMatrix &A)
 {
     if (A.bands) (void)hipFree(A.bands);
@@ -520,6 +935,11 @@ void free_mg(ec3d_mg *m)
 {
     if (!m) return;
     for (size_t l = 1; l < m->lev.size(); ++l) free_level_matrix(m->lev[l].A);
+    for (AvLevel &L : m->av)
+        if (L.bands) (void)hipFree(L.bands);
+    if (m->ulist) (void)hipFree(m->ulist);
+    if (m->uidx) (void)hipFree(m->uidx);
+    if (m->ubuf) (void)hipFree(m->ubuf);
     if (m->vec_base) (void)hipFree(m->vec_base);
     if (m->part) (void)hipFree(m->part);
     if (m->scal) (void)hipFree(m->scal);
@@ -549,6 +969,275 @@ static bool mg_dims(int sdx, int sdy, int sdz, std::vector<std::array<int, 3>> &
     }
 }
 
+// ---- block multigrid of the structured A-V form: set-up --------------------------------------------------------------
+// Level dims: every axis whose extent is > 1 is ceil-halved, until a level has <= 4096 cells (always reached).
+static std::vector<std::array<int, 3>> avmg_dims(int sdx, int sdy, int sdz)
+{
+    std::vector<std::array<int, 3>> dims(1, {sdx, sdy, sdz});
+    while ((int64_t)dims.back()[0] * dims.back()[1] * dims.back()[2] > EC3D_MG_COARSE_ROWS) {
+        std::array<int, 3> e = dims.back();
+        for (int a = 0; a < 3; ++a)
+            if (e[a] > 1) e[a] = (e[a] + 1) / 2;
+        dims.push_back(e);
+    }
+    return dims;
+}
+
+static int set_block_mg(ec3d_ctx *c, int32_t pre, int32_t post, int32_t coarse_sweeps)
+{
+    const DevMatrix &A = c->A;
+    if (!A.sav || c->in_multi || c->halo > 0 || c->nranks > 1 || c->dist) {
+        ec3d_set_error("ec3d_set_preconditioner: the block multigrid preconditioner needs the structured A-V form "
+                       "(ec3d_assemble) on a handle of its own (not Poisson, bands + tail, a slab or a handle of "
+                       "ec3d_multi)");
+        return EC3D_PRECOND_E_MATRIX;
+    }
+    const int sdx = (int)A.sav_step[1], pitch = (int)A.sav_step[2];
+    const int sdy = (int)(c->plane / sdx), sdz = (int)(A.sav_nC / pitch);
+    const int64_t nCd = A.sav_nC;
+    const int a_hi = A.sav_u0, u_lo = A.sav_u0, u_hi = A.sav_zero; // A rows: classes [0, u0); U rows: [u0, zero)
+    if (a_hi > EC3D_AVMG_MAXCLS || u_hi - u_lo > EC3D_AVMG_MAXCLS) {
+        ec3d_set_error("ec3d_set_preconditioner: more classes than the block smoothers' table holds");
+        return EC3D_PRECOND_E_MATRIX;
+    }
+    // the three A blocks must have the same 7 band coefficients in every row (src/EC3D.f90: valY = valX, valZ = valX)
+    std::vector<uint8_t> cls((size_t)(4 * nCd));
+    std::vector<double> tab((size_t)A.ncls * 16);
+    EC3D_HIP(hipMemcpyAsync(cls.data(), A.cls, cls.size(), hipMemcpyDeviceToHost, c->stream));
+    EC3D_HIP(hipMemcpyAsync(tab.data(), A.table, tab.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    EC3D_HIP(hipStreamSynchronize(c->stream));
+    const auto bands_of = [&](int k, int lo, int hi, double (&b)[7]) { // what the smoothers read for class k
+        const bool in = k >= lo && k < hi;
+        for (int q = 0; q < 7; ++q) b[q] = in ? tab[(size_t)k * 16 + q] : 0.0;
+        if (in) return true;
+        for (int q = 0; q < 7; ++q) // a class outside the range is only allowed without band coefficients
+            if (tab[(size_t)k * 16 + q] != 0.0) return false;
+        return true;
+    };
+    std::vector<int32_t> ured, ublack;
+    for (int64_t r = 0; r < nCd; ++r) {
+        double b0[7], b1[7], b2[7], bu[7];
+        if (!bands_of(cls[(size_t)r], 0, a_hi, b0) || !bands_of(cls[(size_t)(nCd + r)], 0, a_hi, b1) ||
+            !bands_of(cls[(size_t)(2 * nCd + r)], 0, a_hi, b2) || memcmp(b0, b1, sizeof b0) || memcmp(b0, b2, sizeof b0)) {
+            ec3d_set_error("ec3d_set_preconditioner: the band coefficients of the Ax, Ay, Az rows of device cell " +
+                           std::to_string(r) + " differ: one hierarchy cannot serve the three blocks");
+            return EC3D_PRECOND_E_MATRIX;
+        }
+        const int ku = cls[(size_t)(3 * nCd + r)];
+        if (!bands_of(ku, u_lo, u_hi, bu)) {
+            ec3d_set_error("ec3d_set_preconditioner: a U row outside the U classes has band coefficients");
+            return EC3D_PRECOND_E_MATRIX;
+        }
+        if (ku >= u_lo && ku < u_hi) {
+            const int64_t ij = r % pitch;
+            const int i = (int)(ij % sdx), j = (int)(ij / sdx), k = (int)(r / pitch);
+            (((i + j + k) & 1) ? ublack : ured).push_back((int32_t)r);
+        }
+    }
+    // the U block's conducting components (U rows joined across a face) in order of their first row, and the weights
+    // of the U rows' left null vector (k_avmg_upart)
+    std::vector<int32_t> comp_of((size_t)nCd, -1), plist, chunks, cco, ucomp;
+    std::vector<double> pw, inv_w;
+    {
+        std::vector<char> is_u((size_t)nCd, 0);
+        for (int32_t r : ured) is_u[(size_t)r] = 1;
+        for (int32_t r : ublack) is_u[(size_t)r] = 1;
+        std::vector<int32_t> stack;
+        int nc = 0;
+        for (int64_t r0 = 0; r0 < nCd; ++r0) {
+            if (!is_u[(size_t)r0] || comp_of[(size_t)r0] >= 0) continue;
+            comp_of[(size_t)r0] = nc;
+            stack.assign(1, (int32_t)r0);
+            while (!stack.empty()) {
+                const int64_t r = stack.back();
+                stack.pop_back();
+                const int64_t ij = r % pitch;
+                const int i = (int)(ij % sdx), j = (int)(ij / sdx), k = (int)(r / pitch);
+                const int64_t nb[6] = {k > 0 ? r - pitch : -1, j > 0 ? r - sdx : -1, i > 0 ? r - 1 : -1,
+                                       i + 1 < sdx ? r + 1 : -1, j + 1 < sdy ? r + sdx : -1,
+                                       k + 1 < sdz ? r + pitch : -1};
+                for (int64_t q : nb)
+                    if (q >= 0 && is_u[(size_t)q] && comp_of[(size_t)q] < 0) {
+                        comp_of[(size_t)q] = nc;
+                        stack.push_back((int32_t)q);
+                    }
+            }
+            ++nc;
+        }
+        std::vector<std::vector<int32_t>> rows((size_t)nc);
+        for (int64_t r = 0; r < nCd; ++r)
+            if (comp_of[(size_t)r] >= 0) rows[(size_t)comp_of[(size_t)r]].push_back((int32_t)r);
+        for (int cc = 0; cc < nc; ++cc) {
+            cco.push_back((int32_t)(chunks.size() / 2));
+            const int32_t lo = (int32_t)plist.size();
+            double wsum = 0.0;
+            for (int32_t r : rows[(size_t)cc]) {
+                const double *t = &tab[(size_t)cls[(size_t)(3 * nCd + r)] * 16];
+                double w = 1.0;
+                for (int d = 0; d < 3; ++d)
+                    if (t[2 - d] == 0.0 || t[4 + d] == 0.0) w *= 0.5;
+                plist.push_back(r);
+                pw.push_back(w);
+                wsum += w;
+            }
+            const int32_t hi = (int32_t)plist.size();
+            for (int32_t e = lo; e < hi; e += EC3D_AVMG_UCHUNK) {
+                chunks.push_back(e);
+                chunks.push_back(std::min<int32_t>(hi, e + EC3D_AVMG_UCHUNK));
+            }
+            inv_w.push_back(1.0 / wsum);
+        }
+        cco.push_back((int32_t)(chunks.size() / 2));
+        for (int32_t r : ured) ucomp.push_back(comp_of[(size_t)r]);
+        for (int32_t r : ublack) ucomp.push_back(comp_of[(size_t)r]);
+    }
+    const std::vector<std::array<int, 3>> dims = avmg_dims(sdx, sdy, sdz);
+    const int L = (int)dims.size();
+    // build the new hierarchy completely before the old one is replaced: a failure leaves the handle as it was
+    ec3d_mg *m = new ec3d_mg;
+    m->kind = EC3D_PRECOND_BLOCK_MG;
+    m->pre = pre ? pre : 2;
+    m->post = post ? post : 2;
+    m->coarse = coarse_sweeps ? coarse_sweeps : 16;
+    m->av.resize((size_t)L);
+    const auto fail = [&](int code) {
+        free_mg(m);
+        return code;
+    };
+    const auto oom = [&](const char *what) {
+        (void)hipGetLastError();
+        ec3d_set_error(std::string("ec3d_set_preconditioner: ") + what);
+        return fail(100);
+    };
+    AvOp &A0 = m->av[0].op;
+    A0 = AvOp{};
+    A0.sdx = sdx; A0.sdy = sdy; A0.sdz = sdz;
+    A0.kdz = pitch;
+    A0.n = nCd;
+    A0.vs = nCd;
+    A0.cls = A.cls; // block 0's classes serve all three blocks (checked above)
+    A0.table = A.table;
+    A0.cls0 = 0;
+    A0.ncls = a_hi;
+    m->uop = A0;
+    m->uop.cls = A.cls + 3 * nCd;
+    m->uop.cls0 = u_lo;
+    m->uop.ncls = u_hi - u_lo;
+    int64_t coarse_len = 0;
+    for (int l = 1; l < L; ++l) {
+        AvLevel &P = m->av[(size_t)l - 1], &Q = m->av[(size_t)l];
+        for (int a = 0; a < 3; ++a) P.f[a] = dims[(size_t)l - 1][a] > 1 ? 2 : 1;
+        AvOp &o = Q.op;
+        o = AvOp{};
+        o.sdx = dims[(size_t)l][0]; o.sdy = dims[(size_t)l][1]; o.sdz = dims[(size_t)l][2];
+        o.kdz = (int64_t)o.sdx * o.sdy;
+        o.n = o.kdz * o.sdz;
+        o.n_pad = (o.n + 63) / 64 * 64;
+        o.vs = o.n_pad;
+        if (hipMalloc(&Q.bands, (size_t)7 * o.n_pad * sizeof(double)) != hipSuccess)
+            return oom("out of device memory for the hierarchy");
+        o.bands = Q.bands;
+        coarse_len += 9 * o.n_pad;
+    }
+    // p^ and s^ are read by the format's SpMV, which may read the zero halo around a vector (ec3d_prepare_vectors)
+    const int64_t nf = c->ghost + (A.n_pad + 63) / 64 * 64 + c->ghost;
+    const int64_t total = coarse_len + 3 * nCd + 2 * nf;
+    if (hipMalloc(&m->vec_base, (size_t)total * sizeof(double)) != hipSuccess ||
+        hipMalloc(&m->part, 2 * EC3D_MG_DOT_BLOCKS * sizeof(double)) != hipSuccess ||
+        hipMalloc(&m->scal, sizeof(MgScalars)) != hipSuccess ||
+        hipMalloc(&m->ulist, std::max<size_t>(1, ured.size() + ublack.size()) * sizeof(int32_t)) != hipSuccess)
+        return oom("out of device memory for the hierarchy");
+    m->nu_red = (int64_t)ured.size();
+    m->nu_black = (int64_t)ublack.size();
+    if (hipMemsetAsync(m->vec_base, 0, (size_t)total * sizeof(double), c->stream) != hipSuccess ||
+        hipMemsetAsync(m->scal, 0, sizeof(MgScalars), c->stream) != hipSuccess ||
+        (m->nu_red && hipMemcpyAsync(m->ulist, ured.data(), ured.size() * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess) ||
+        (m->nu_black && hipMemcpyAsync(m->ulist + m->nu_red, ublack.data(), ublack.size() * 4, hipMemcpyHostToDevice,
+                                       c->stream) != hipSuccess))
+        return oom("building the hierarchy failed");
+    m->ncomp = (int)inv_w.size();
+    m->nchunk = (int)(chunks.size() / 2);
+    {
+        const size_t nu = plist.size(), ni = 2 * nu + chunks.size() + cco.size(), nd = nu + 2 * inv_w.size() + chunks.size() / 2;
+        if (hipMalloc(&m->uidx, std::max<size_t>(1, ni) * sizeof(int32_t)) != hipSuccess ||
+            hipMalloc(&m->ubuf, std::max<size_t>(1, nd) * sizeof(double)) != hipSuccess)
+            return oom("out of device memory for the hierarchy");
+        m->ucomp = m->uidx;
+        m->plist = m->ucomp + nu;
+        m->chunks = m->plist + nu;
+        m->cco = m->chunks + chunks.size();
+        m->pw = m->ubuf;
+        m->inv_w = m->pw + nu;
+        m->umean = m->inv_w + inv_w.size();
+        m->upart = m->umean + inv_w.size();
+        std::vector<int32_t> hi;
+        hi.insert(hi.end(), ucomp.begin(), ucomp.end());
+        hi.insert(hi.end(), plist.begin(), plist.end());
+        hi.insert(hi.end(), chunks.begin(), chunks.end());
+        hi.insert(hi.end(), cco.begin(), cco.end());
+        std::vector<double> hd;
+        hd.insert(hd.end(), pw.begin(), pw.end());
+        hd.insert(hd.end(), inv_w.begin(), inv_w.end());
+        hd.resize(nd, 0.0);
+        if (hipMemcpy(m->uidx, hi.data(), hi.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(m->ubuf, hd.data(), hd.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+            return oom("building the hierarchy failed");
+    }
+    double *q = m->vec_base;
+    for (int l = 1; l < L; ++l) {
+        AvLevel &Q = m->av[(size_t)l];
+        const int64_t len = 3 * Q.op.n_pad;
+        Q.x = q; Q.w = q + len; Q.b = q + 2 * len;
+        q += 3 * len;
+    }
+    m->w0 = q; m->ph = q + 3 * nCd + c->ghost; m->sh = q + 3 * nCd + nf + c->ghost;
+    // the Galerkin levels, finest first, on the device
+    for (int l = 1; l < L; ++l) {
+        const AvLevel &P = m->av[(size_t)l - 1];
+        AvLevel &Q = m->av[(size_t)l];
+        const double scale = 1.0 / (2.0 * P.f[0] * P.f[1] * P.f[2]);
+        hipStream_t s = c->stream;
+        const bool dict = l == 1;
+        MG_LAUNCH(k_avmg_galerkin, blocks_of(Q.op.n), 256, P.op, Q.op, P.f[0], P.f[1], P.f[2], scale, Q.bands);
+    }
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
+        ec3d_set_error("ec3d_set_preconditioner: building the hierarchy failed");
+        return fail(100);
+    }
+    ec3d_mg_free(c);
+    c->mg = m;
+    return 0;
+}
+
+// One iteration of the right-preconditioned BiCGSTAB with restart on the structured A-V form: ec3d_mg_launch_iteration's
+// algorithm, with M the block multigrid, v = A p^ and t = A s^ by the format's own SpMV (ec3d_launch_spmv), then their
+// dot partials (k_avmg_dot: the summation order of k_mg_spmv_dot).  The SpMV launches are not gated: past an exit
+// nothing reads what they write.
+static void avmg_launch_iteration(ec3d_ctx *c, int it)
+{
+    ec3d_mg *m = c->mg;
+    double **v = c->vec;
+    hipStream_t s = c->stream;
+    const MatView V = c->A.view();
+    const int64_t n = c->A.n;
+    const unsigned nb = dot_blocks(n);
+    const Gate g0{c->state, it, 0}, g1{c->state, it, 1};
+    launch_avcycle(m, g0, v[EC3D_VEC_P], m->ph, s);
+    ec3d_launch_spmv(V, c->sweep_s, m->ph, v[EC3D_VEC_AP], s);
+    k_avmg_dot<<<nb, 256, 0, s>>>(n, g0, v[EC3D_VEC_R0], v[EC3D_VEC_AP], 0, m->part);
+    k_mg_scalar<<<1, 256, 0, s>>>(MG_ALPHA, g0, c->state, m->scal, m->part, (int)nb, c->hist, c->hist_cap);
+    k_mg_s<<<nb, 256, 0, s>>>(n, g0, c->state, v[EC3D_VEC_R], v[EC3D_VEC_AP], v[EC3D_VEC_S], m->part);
+    k_mg_scalar<<<1, 256, 0, s>>>(MG_SEXIT, g0, c->state, m->scal, m->part, (int)nb, c->hist, c->hist_cap);
+    launch_avcycle(m, g1, v[EC3D_VEC_S], m->sh, s);
+    ec3d_launch_spmv(V, c->sweep_s, m->sh, v[EC3D_VEC_AS], s);
+    k_avmg_dot<<<nb, 256, 0, s>>>(n, g1, v[EC3D_VEC_S], v[EC3D_VEC_AS], 1, m->part);
+    k_mg_scalar<<<1, 256, 0, s>>>(MG_OMEGA, g1, c->state, m->scal, m->part, (int)nb, c->hist, c->hist_cap);
+    k_mg_xr<<<nb, 256, 0, s>>>(n, it, c->state, v[EC3D_VEC_X], m->ph, m->sh, v[EC3D_VEC_S], v[EC3D_VEC_AS],
+                               v[EC3D_VEC_R0], v[EC3D_VEC_R], m->part);
+    k_mg_scalar<<<1, 256, 0, s>>>(MG_REXIT, g1, c->state, m->scal, m->part, (int)nb, c->hist, c->hist_cap);
+    k_mg_p<<<nb, 256, 0, s>>>(n, g1, c->state, m->scal, v[EC3D_VEC_R], v[EC3D_VEC_AP], v[EC3D_VEC_P], v[EC3D_VEC_R0]);
+}
+
 void ec3d_mg_free(ec3d_ctx *c)
 {
     free_mg(c->mg);
@@ -567,12 +1256,13 @@ extern "C" int ec3d_set_preconditioner(ec3d_handle c, int kind, int32_t pre, int
         ec3d_mg_free(c);
         return 0;
     }
-    if (kind != EC3D_PRECOND_MG || pre < 0 || post < 0 || coarse_sweeps < 0) {
+    if ((kind != EC3D_PRECOND_MG && kind != EC3D_PRECOND_BLOCK_MG) || pre < 0 || post < 0 || coarse_sweeps < 0) {
         ec3d_set_error("ec3d_set_preconditioner: unknown kind or negative sweep count");
         return 2;
     }
     int rc = ec3d_need_matrix(c, "ec3d_set_preconditioner");
     if (rc) return rc;
+    if (kind == EC3D_PRECOND_BLOCK_MG) return set_block_mg(c, pre, post, coarse_sweeps);
     if (!c->poisson_full || c->in_multi || c->halo > 0 || c->nranks > 1 || c->dist) {
         ec3d_set_error("ec3d_set_preconditioner: the multigrid preconditioner needs a matrix from ec3d_assemble_poisson "
                        "on a handle of its own (not A-V, CSR, a slab or a handle of ec3d_multi)");
@@ -654,7 +1344,17 @@ extern "C" int ec3d_get_preconditioner(ec3d_handle c, int *kind, int32_t *levels
         return 2;
     }
     const ec3d_mg *m = c->mg;
-    if (kind) *kind = m ? EC3D_PRECOND_MG : EC3D_PRECOND_NONE;
+    if (kind) *kind = m ? m->kind : EC3D_PRECOND_NONE;
+    if (m && m->kind == EC3D_PRECOND_BLOCK_MG) {
+        if (levels) *levels = (int32_t)m->av.size();
+        if (dims)
+            for (size_t l = 0; l < m->av.size(); ++l) {
+                dims[3 * l] = m->av[l].op.sdx;
+                dims[3 * l + 1] = m->av[l].op.sdy;
+                dims[3 * l + 2] = m->av[l].op.sdz;
+            }
+        return 0;
+    }
     if (levels) *levels = m ? (int32_t)m->lev.size() : 0;
     if (dims && m)
         for (size_t l = 0; l < m->lev.size(); ++l) {
@@ -675,7 +1375,8 @@ extern "C" int ec3d_precond_apply(ec3d_handle c, const double *r, double *z)
     }
     ec3d_mg *m = c->mg;
     if ((rc = ec3d_vec_h2d(c, m->ph, r))) return rc;
-    launch_vcycle(m, Gate{nullptr, 0, 0}, m->ph, m->sh, c->stream);
+    if (m->kind == EC3D_PRECOND_BLOCK_MG) launch_avcycle(m, Gate{nullptr, 0, 0}, m->ph, m->sh, c->stream);
+    else launch_vcycle(m, Gate{nullptr, 0, 0}, m->ph, m->sh, c->stream);
     EC3D_HIP(hipGetLastError());
     if ((rc = ec3d_vec_d2h(c, z, m->sh))) return rc;
     EC3D_HIP(hipStreamSynchronize(c->stream));
@@ -685,6 +1386,13 @@ extern "C" int ec3d_precond_apply(ec3d_handle c, const double *r, double *z)
 // iterations per poll of solve_core: about 1 ms of device work (a V-cycle is ~210 B per fine row, two per iteration)
 int ec3d_mg_chunk(const ec3d_ctx *c)
 {
+    if (c->mg->kind == EC3D_PRECOND_BLOCK_MG) {
+        // per A cell and iteration: two applications of M (three V-cycles of ~210 B each) ~1260 B, two SpMVs of the
+        // four blocks and the vector kernels ~800 B; the launches of a level cost ~60 us per application on small grids
+        const double cells = (double)c->mg->av[0].op.n;
+        const double est_us = cells * 2100.0 / 4.0e6 + 120.0 * (double)c->mg->av.size();
+        return (int)std::min<double>(16.0, std::max<double>(1.0, 1000.0 / est_us));
+    }
     const double est_us = (double)c->A.n_pad * 600.0 / 4.0e6 + 60.0 * (double)c->mg->lev.size();
     return (int)std::min<double>(16.0, std::max<double>(1.0, 1000.0 / est_us));
 }
@@ -698,6 +1406,10 @@ int ec3d_mg_chunk(const ec3d_ctx *c)
 void ec3d_mg_launch_iteration(ec3d_ctx *c, int it)
 {
     ec3d_mg *m = c->mg;
+    if (m->kind == EC3D_PRECOND_BLOCK_MG) {
+        avmg_launch_iteration(c, it);
+        return;
+    }
     double **v = c->vec;
     hipStream_t s = c->stream;
     const MgOp &A = m->lev[0].op;

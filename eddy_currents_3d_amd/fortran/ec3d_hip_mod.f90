@@ -20,10 +20,11 @@ module ec3d_hip
               ec3d_multi_rhs_step, ec3d_multi_post_update, ec3d_multi_vtk_fields, ec3d_multi_true_residual, &
               ec3d_multi_vtk_fields_begin, ec3d_multi_vtk_fields_wait, ec3d_rccl_unique_id, ec3d_multi_create_rank, &
               ec3d_multi_plan, ec3d_set_preconditioner, ec3d_get_preconditioner, ec3d_precond_apply, &
-              EC3D_PRECOND_NONE, EC3D_PRECOND_MG
+              EC3D_PRECOND_NONE, EC3D_PRECOND_MG, EC3D_PRECOND_BLOCK_MG
 
     integer(c_int), parameter :: EC3D_VEC_X = 0, EC3D_VEC_B = 1   ! Uaf, Jaf
     integer(c_int), parameter :: EC3D_PRECOND_NONE = 0, EC3D_PRECOND_MG = 1   ! ec3d_set_preconditioner
+    integer(c_int), parameter :: EC3D_PRECOND_BLOCK_MG = 2   ! ... of the structured A-V form (ec3d_assemble)
 
     interface
         integer(c_int) function ec3d_create(h, device) bind(C, name="ec3d_create")

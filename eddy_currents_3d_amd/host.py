@@ -338,7 +338,8 @@ class _SourcesAhead:
 
 
 def run(model: vxc.VxcModel, solver, steps: int | None = None, out_dir: str | None = None, on_step=None,
-        on_rhs=None, on_solved=None, write_output=None, overlap_output: bool = True, on_fields=None, on_written=None):
+        on_rhs=None, on_solved=None, write_output=None, overlap_output: bool = True, on_fields=None, on_written=None,
+        precond: str | None = None):
     """The reference's run of ``model`` on ``solver`` (an EC3DSolver): assemble, then step until T >= stop (or
     ``steps`` steps).  Returns a list of per-step dicts (T, iter).  ``out_dir``: write ``field_N.vtk`` there at
     the reference's output cadence.  Hooks, all ``(k, solver, info)``: ``on_rhs`` when Jaf (B) of step k is
@@ -354,11 +355,14 @@ def run(model: vxc.VxcModel, solver, steps: int | None = None, out_dir: str | No
     the pinned buffer (valid during the call; calls for different N may overlap and arrive out of order).  Without overlap the fields are fetched synchronously after the post-update,
     ``on_fields`` is called in the loop and ``info["fields"]`` holds them when they are not written.
     ``on_written(N, paths)``: after output step N's files are complete (a run of hundreds of 500 MB files may want
-    to move them away)."""
+    to move them away).  ``precond`` (e.g. "block-mg"): solver.set_preconditioner(precond) right after the assembly;
+    None leaves the handle's preconditioner as it is."""
     t = vxc.domain_tables(model)
     if t["dt"] is None or t["time"] is None:
         raise ValueError("the model has no 'tran stop=... step=...' line")
     solver.assemble(t["geoPHYS"], t["geoPHYS_C"], t["valPHYS"], t["BND"], t["delta"], t["dt"])
+    if precond is not None:
+        solver.set_preconditioner(precond)
     n = solver.n
     solver.upload("X", np.zeros(n))
     solver.upload("B", np.zeros(n))

@@ -25,6 +25,9 @@ def main(argv=None):
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--refine", type=int, nargs=3, metavar=("FX", "FY", "FZ"), default=None,
                     help="split every cell FX x FY x FZ times first (same physical size, finer grid)")
+    ap.add_argument("--precond", choices=("none", "block-mg"), default="none",
+                    help="preconditioner of the time step's solve: none (the reference's BiCGSTAB, default) or block-mg "
+                         "(right-preconditioned BiCGSTAB, block multigrid M; one GPU only)")
     a = ap.parse_args(argv)
 
     from . import EC3DSolver, host, vxc
@@ -43,6 +46,8 @@ def main(argv=None):
               + (f"  -> field_{info['output']}.vtk" if "output" in info and out_dir else ""), flush=True)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if world > 1 and a.precond != "none":
+        ap.error(f"--precond {a.precond} runs on one GPU only; the multi-rank z-slab path has no preconditioner")
     if world > 1:   # one process per GPU: z-slabs, halo exchange and reductions over RCCL
         import torch
         import torch.distributed as dist
@@ -59,7 +64,8 @@ def main(argv=None):
         n = 3 * model.vox.size + t["ncells0"]
     else:
         with EC3DSolver(device=a.device) as s:
-            log = host.run(model, s, steps=a.steps, out_dir=out_dir, on_step=on_step)
+            log = host.run(model, s, steps=a.steps, out_dir=out_dir, on_step=on_step,
+                           precond=None if a.precond == "none" else a.precond)
             n = s.n
     wall = time.perf_counter() - t0
     its = sum(i["iter"] for i in log)

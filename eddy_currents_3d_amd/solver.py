@@ -70,7 +70,7 @@ EXPORTS = ["sprsbcgstabwr_", "ec3d_invalidate", "ec3d_create", "ec3d_destroy", "
            "ec3d_multi_vtk_fields_wait", "ec3d_multi_iterate_begin",
            "ec3d_multi_iterate", "ec3d_multi_synchronize", "ec3d_true_residual", "ec3d_multi_true_residual", "ec3d_get_visit_order", "ec3d_probe_csr_multi", "ec3d_multi_spmv", "ec3d_multi_api_calls", "ec3d_multi_plan", "ec3d_multi_halo_rows", "ec3d_rccl_unique_id", "ec3d_multi_create_rank", "ec3d_format_real8_gfortran", "ec3d_multi_iterate_timed", "ec3d_multi_rccl_info",
            "ec3d_set_preconditioner", "ec3d_get_preconditioner", "ec3d_precond_apply"]
-PRECOND = dict(none=0, mg=1)   # EC3D_PRECOND_* of include/ec3d_hip.h
+PRECOND = {"none": 0, "mg": 1, "block-mg": 2}   # EC3D_PRECOND_* of include/ec3d_hip.h
 PRECOND_E_MATRIX, PRECOND_E_COARSE = 20, 21   # ec3d_set_preconditioner's refusals
 
 _f64 = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
@@ -524,10 +524,11 @@ class EC3DSolver:
         _chk(self.L, self.L.ec3d_spmv(self.h, np.ascontiguousarray(x, np.float64), y), "ec3d_spmv")
         return y
 
-    # ---- preconditioner (a matrix from assemble_poisson only) ------------------------------
+    # ---- preconditioner ("mg": a matrix from assemble_poisson; "block-mg": the structured A-V form) -----------
     def set_preconditioner(self, kind: str = "mg", pre: int = 2, post: int = 2, coarse_sweeps: int = 0):
-        """"mg": solves run the right-preconditioned iteration with one multigrid V-cycle as M; "none": the
-        reference's iteration.  Zeros select the library's defaults.  Refusal: EC3DError with .status
+        """"mg": solves run the right-preconditioned iteration with one multigrid V-cycle as M; "block-mg": the same
+        iteration on the A-V system of assemble, M one Galerkin V-cycle per A block and Gauss-Seidel sweeps on U;
+        "none": the reference's iteration.  Zeros select the library's defaults.  Refusal: EC3DError with .status
         PRECOND_E_MATRIX or PRECOND_E_COARSE, the handle unchanged."""
         _chk(self.L, self.L.ec3d_set_preconditioner(self.h, PRECOND[kind], pre, post, coarse_sweeps),
              "ec3d_set_preconditioner")
@@ -544,7 +545,7 @@ class EC3DSolver:
         return name, [tuple(int(a) for a in dims[3 * l:3 * l + 3]) for l in range(levels.value)]
 
     def precond_apply(self, r):
-        """z = M r (one V-cycle) on host vectors."""
+        """z = M r on host vectors (the reference's numbering)."""
         z = np.empty(self.n)
         _chk(self.L, self.L.ec3d_precond_apply(self.h, np.ascontiguousarray(r, np.float64), z), "ec3d_precond_apply")
         return z

@@ -168,7 +168,19 @@ int ec3d_get_row_map(ec3d_handle h, int32_t *ref_to_dev);
  * (pre = post = 2, coarse_sweeps = 16).  The hierarchy is built at once and freed by ec3d_destroy, by a new
  * matrix or by EC3D_PRECOND_NONE.  Refused, with the handle left as it was: EC3D_PRECOND_E_MATRIX (A-V, CSR,
  * a slab, a handle of ec3d_multi), EC3D_PRECOND_E_COARSE (the coarsest level has > 4096 rows). */
-enum { EC3D_PRECOND_NONE = 0, EC3D_PRECOND_MG = 1 };
+/* EC3D_PRECOND_BLOCK_MG: the same outer iteration on the structured A-V form (ec3d_assemble with the structured
+ * form on, an undivided single-GPU handle), v = A p^ and t = A s^ by the full operator.  M is block diagonal over
+ * [Ax | Ay | Az | U]; the A-U couplings are left out of M.  The three A blocks have the same band coefficients in every
+ * cell (checked; else EC3D_PRECOND_E_MATRIX), so one hierarchy serves them: level 0 is the handle's matrix, every
+ * coarser level the Galerkin product of piecewise-constant aggregation (2 cells along every axis whose extent is > 1,
+ * ceil-halving; scaled by 1 / (2 * nominal children)), built on the device until a level has <= 4096 cells; one
+ * V-cycle per block as for EC3D_PRECOND_MG, with the mean over the aggregate's actual cells.  The U block gets
+ * pre + post red-black Gauss-Seidel sweeps from zero on its unknowns, its right-hand side first projected onto the
+ * U block's range (each conducting component's weighted mean taken out).  Rows without a diagonal give 0.  Same defaults
+ * (2 / 2 / 16).  Refused with EC3D_PRECOND_E_MATRIX, the handle unchanged: Poisson, bands + tail (CSR, or
+ * ec3d_set_structured(h, 0)), a slab, a handle of ec3d_multi.  ec3d_get_preconditioner reports the A blocks'
+ * levels; ec3d_precond_apply applies M on host vectors in the reference's numbering. */
+enum { EC3D_PRECOND_NONE = 0, EC3D_PRECOND_MG = 1, EC3D_PRECOND_BLOCK_MG = 2 };
 enum { EC3D_PRECOND_E_MATRIX = 20, EC3D_PRECOND_E_COARSE = 21 };
 int ec3d_set_preconditioner(ec3d_handle h, int kind, int32_t pre, int32_t post, int32_t coarse_sweeps);
 /* kind, number of levels, and (dims != NULL) sdx, sdy, sdz of every level, finest first (3*levels entries) */
