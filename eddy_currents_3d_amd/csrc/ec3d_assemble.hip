@@ -30,7 +30,9 @@ struct GridPar {
     double bnd[6];   // BND(d,s) column-major: [s*3+d]
     double dt;
     int nsub_glob;
-    int cond_dom;      // structured form: THE conducting domain (it allows one), 1 when there is none
+    int ndom_c;        // structured form: conducting domains (>= 1: with none, domain 1 fills the 9 classes)
+    uint8_t cond_ord[128];            // structured form: domain id -> its ordinal among the conducting domains
+    uint8_t cond_dom_of[EC3D_SAV_MAXDOM]; // and back: ordinal -> domain id
     int64_t ncells0;
 };
 
@@ -326,21 +328,23 @@ void set_offsets(DevMatrix &A, const GridPar &g)
 // ---------------------------------------------------------------------------------------------
 // Structured A-V form (MatView::sav): classes instead of entries.
 //   class 0..26                      A row, position type bt, no coupling
-//   27 + ((dom-1)*3 + d)*3 + pat-1   A_d row of an interior conducting cell of domain dom;
+//   27 + (ord*3 + d)*3 + pat-1       A_d row of an interior conducting cell of the ord-th conducting domain
+//                                    (0-based, in U-id order: GridPar::cond_ord / cond_dom_of);
 //                                    pat 1 central, 2 one-sided low (U(+1) missing), 3 one-sided high
 //   u0 + stx + 3 sty + 9 stz         U row; st = 0 both neighbours, 1 minus one missing, 2 plus one missing
 //   zero                             no coefficients (inactive U slot, padding)
 struct SavIds {
     int a0, u0, zero, ncls;
 };
-// 27 box-position classes of a plain A row, 9 of a conducting A row (component x stencil pattern; the
-// structured form has ONE conducting domain, so the count does not grow with the number of air domains the
-// reference splits a large grid into, src/vxc2data.f90:316-333), 27 U-row patterns, the all-zero class: 64
-__host__ __device__ inline SavIds sav_ids()
+// 27 box-position classes of a plain A row, 9 per CONDUCTING domain of a conducting A row (component x stencil
+// pattern; air domains never count, so the count does not grow with the number of air domains the reference
+// splits a large grid into, src/vxc2data.f90:316-333), 27 U-row patterns (they hold no material value), the
+// all-zero class: 55 + 9 D, 64 with one conducting domain (or none), 253 with EC3D_SAV_MAXDOM = 22
+__host__ __device__ inline SavIds sav_ids(int ndom_c)
 {
     SavIds s;
     s.a0 = 27;
-    s.u0 = 27 + 9;
+    s.u0 = 27 + 9 * ndom_c;
     s.zero = s.u0 + 27;
     s.ncls = s.zero + 1;
     return s;
@@ -348,7 +352,7 @@ __host__ __device__ inline SavIds sav_ids()
 
 __global__ void k_build_table_sav(GridPar g, const double *__restrict__ valPHYS, double *table)
 {
-    const SavIds id = sav_ids();
+    const SavIds id = sav_ids(g.ndom_c);
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= id.ncls) return;
     double t[16];
@@ -362,7 +366,7 @@ __global__ void k_build_table_sav(GridPar g, const double *__restrict__ valPHYS,
         a_row_bands(g, p[0], p[1], p[2], c, on_box);
         for (int b = 0; b < 7; ++b) t[b] = c[b];
     } else if (q < id.u0) {
-        const int e = q - 27, pat = e % 3 + 1, d = e / 3, dom = g.cond_dom;
+        const int e = q - 27, pat = e % 3 + 1, d = (e / 3) % 3, dom = g.cond_dom_of[e / 9];
         a_row_bands(g, 2, 2, 2, c, on_box);
         conductor_terms(g, valPHYS, dom, c);
         for (int b = 0; b < 7; ++b) t[b] = c[b];
@@ -411,7 +415,7 @@ __global__ __launch_bounds__(256) void k_assemble_sav(GridPar g, const int8_t *_
                                                       uint8_t *tile_flag, uint8_t *flags, int *err,
                                                       unsigned long long *nnz)
 {
-    const SavIds id = sav_ids();
+    const SavIds id = sav_ids(g.ndom_c);
     const int64_t nn0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (nn0 >= g.nCells) return;
     const int kl = (int)(nn0 / g.kdz); // plane within the planes held
@@ -437,6 +441,7 @@ __global__ __launch_bounds__(256) void k_assemble_sav(GridPar g, const int8_t *_
     if (on_box) { atomicMax(err, 3); return; }
     const int64_t step[3] = {1, g.sdx, g.kdz};
     const int pos[3] = {i, j, k}, sd[3] = {g.sdx, g.sdy, g.sdz};
+    const int a_dom = id.a0 + 9 * g.cond_ord[geo[nn0]]; // this cell's conducting domain's 9 classes
     int pu = 0, mul = 1;
     for (int d = 0; d < 3; ++d, mul *= 3) {
         const int32_t um = geoC[nn0 - step[d]], up = geoC[nn0 + step[d]];
@@ -455,7 +460,7 @@ __global__ __launch_bounds__(256) void k_assemble_sav(GridPar g, const int8_t *_
         if (pat != 1) fl |= (uint8_t)(1u << d);
         cnt += pat == 1 ? 2 : 3;
         const int64_t row = (int64_t)d * g.nCd + pc;
-        cls[row] = (uint8_t)(id.a0 + d * 3 + pat - 1);
+        cls[row] = (uint8_t)(a_dom + d * 3 + pat - 1);
         tile_flag[row / EC3D_TILE] = 1;
         // U row: which neighbours are missing
         if (um == 0 && up == 0) { atomicMax(err, 1); return; } // the reference meets a zero column here
@@ -730,12 +735,17 @@ int ec3d_assemble_sav_device(ec3d_ctx *c, int32_t sdx, int32_t sdy, int32_t sdz,
     const int32_t np = e1 - e0;           // planes held (a z-slab: owned planes + halo planes)
     g.nCells = g.kdz * np;
     const bool slab = !(e0 == 0 && e1 == sdz);
-    const SavIds id = sav_ids();
     if (sdx < 5 || sdy < 5 || sdz < 5) return -1;
-    // conducting cells in scan order; one conducting domain only (U numbering = scan order)
+    // Conducting cells in scan order.  The reference numbers U COLUMNS domain-major (src/vxc2data.f90:624-636) but
+    // its U ROWS in scan order (countU, src/EC3D.f90:521, :955), and the structured form holds a cell's U row and U
+    // unknown in the same slot.  So it is the reference's system, symmetrically permuted, exactly when the two orders
+    // agree: every domain's cells follow the previous domain's in scan order (always so for one domain).  Otherwise,
+    // and for more than EC3D_SAV_MAXDOM conducting domains or several of them on a slab, bands + tail.
     std::vector<int32_t> uidx((size_t)g.nCells, -1);
     int64_t nc0 = 0;
-    int dom_seen = 0;
+    int ndom = 0;
+    memset(g.cond_ord, 0, sizeof g.cond_ord);
+    memset(g.cond_dom_of, 0, sizeof g.cond_dom_of);
     for (int64_t q = 0; q < g.nCells; ++q)
         if (geoPHYS_C[q] != 0) {
             const int dom = geoPHYS[q];
@@ -743,12 +753,19 @@ int ec3d_assemble_sav_device(ec3d_ctx *c, int32_t sdx, int32_t sdy, int32_t sdz,
                 ec3d_set_error("ec3d_assemble: geoPHYS domain id out of range");
                 return 2;
             }
-            if (dom_seen && dom != dom_seen) return -1; // several conducting domains: bands + tail
-            dom_seen = dom;
+            if (ndom == 0 || dom != g.cond_dom_of[ndom - 1]) { // a new domain: its U ids follow the last one's
+                for (int o = 0; o < ndom; ++o)
+                    if (g.cond_dom_of[o] == dom) return -1; // a domain resumes: not scan-order numbering
+                if (ndom == EC3D_SAV_MAXDOM || (slab && ndom == 1)) return -1;
+                g.cond_ord[dom] = (uint8_t)ndom;
+                g.cond_dom_of[ndom++] = (uint8_t)dom;
+            }
             if (geoPHYS_C[q] != 3 * g.nCells + nc0 + 1) return -1; // not scan-order numbering
             uidx[(size_t)q] = (int32_t)nc0++;
         }
-    g.cond_dom = dom_seen ? dom_seen : 1;
+    if (ndom == 0) g.cond_dom_of[0] = 1; // no conductor: the 9 coupled classes are filled from domain 1, unused
+    g.ndom_c = std::max(ndom, 1);
+    const SavIds id = sav_ids(g.ndom_c);
     // plane pitch: whole tiles per xy plane whenever that costs < 1/16 in rows
     // (EC3D_PITCH=0: never, 2: always -- the tests use it to cover the pitched layout on small grids)
     g.pitch = g.kdz;

@@ -13,6 +13,7 @@
 
 #define EC3D_THREADS 256
 #define EC3D_TILE 512 /* rows per tile: every thread owns 2 consecutive rows (one 16-B access) */
+#define EC3D_SAV_MAXDOM 22 /* conducting domains the structured form holds: 55 + 9 D classes fit a byte */
 #define EC3D_MAXB 16  /* DIA bands */
 #define EC3D_CHUNK 64 /* sliced-ELL slice height = one wavefront */
 #define EC3D_OUT_SLOTS 3 /* pinned host buffers of the overlapped field output (ec3d_vtk_fields_begin) */
@@ -394,6 +395,8 @@ struct ec3d_ctx {
     // per-step RHS build / post-update on the device (src/EC3D.f90:370-404, :412-433)
     int64_t n_cond = 0;            // conducting cells (U unknowns), scan order
     int n_cond_domains = 0;
+    int64_t nu_siz_max = 0;        // max over conducting domains of the domain's cell count (PHYS_C%siznod)
+    int u_rhs = 0;                 // EC3D_U_RHS_*: which U rows the RHS step gives their A-part (ec3d_set_u_rhs)
     int32_t *cond_cell = nullptr;  // [n_cond] 0-based DEVICE cell index (dev_cell)
     double *cond_a = nullptr;      // [n_cond] 2*C/dt of the cell's domain (PHYS_C%valdom)
     int32_t *bnd_list = nullptr;   // the six cel_bnd* lists, 0-based unknown ids, concatenated

@@ -2793,8 +2793,9 @@ static inline SweepZ sweep_z(const Sweep &sw)
     z.il_seg = sw.il_seg;
     return z;
 }
-// dynamic LDS: the class table (a full 256-class table of the structured form would be 32 KiB and cap the CU
-// at 4 workgroups; real problems have 64 classes = 8 KiB) and, for the z-marching structured kernels, the
+// dynamic LDS: the class table (55 + 9 D classes of the structured form with D conducting domains: 64 classes =
+// 8 KiB for one domain, 253 = 31.6 KiB at D = 22, which with the staging slots caps the CU at 3 workgroups -- a cost
+// not measured) and, for the z-marching structured kernels, the
 // staging slots behind it (16 KiB): 24.6 KiB per workgroup, six of them fit a CU's 160 KiB
 static inline size_t tbl_bytes(const MatView &A, int F, bool zm, bool patch, bool il = false)
 {

@@ -546,7 +546,8 @@ void launch_vcycle(ec3d_mg *m, Gate g, const double *r, double *z, hipStream_t s
 // right-hand sides per launch (the blocks' vectors vs apart: one read of a row's coefficients serves all three), rows
 // without a diagonal (level 0's padding rows) producing 0, and aggregates of ceil-halving (an odd axis ends in an
 // aggregate of one cell).  tests/avmg_numpy.py restates them operation by operation.
-#define EC3D_AVMG_MAXCLS 64 // classes of one block the smoothers' table holds (the native structured form: 36 A, 27 U)
+#define EC3D_AVMG_MAXCLS 64 // classes of one block the smoothers' table holds (the native structured form: 27 + 9 D A
+                            // classes with D conducting domains, so D <= 4; 27 U)
 
 __device__ __forceinline__ void av_load_table(const AvOp &A, double *tbl)
 {
@@ -997,7 +998,8 @@ static int set_block_mg(ec3d_ctx *c, int32_t pre, int32_t post, int32_t coarse_s
     const int64_t nCd = A.sav_nC;
     const int a_hi = A.sav_u0, u_lo = A.sav_u0, u_hi = A.sav_zero; // A rows: classes [0, u0); U rows: [u0, zero)
     if (a_hi > EC3D_AVMG_MAXCLS || u_hi - u_lo > EC3D_AVMG_MAXCLS) {
-        ec3d_set_error("ec3d_set_preconditioner: more classes than the block smoothers' table holds");
+        ec3d_set_error("ec3d_set_preconditioner: more classes than the block smoothers' table holds (at most 4 "
+                       "conducting domains)");
         return EC3D_PRECOND_E_MATRIX;
     }
     // the three A blocks must have the same 7 band coefficients in every row (src/EC3D.f90: valY = valX, valZ = valX)

@@ -4,7 +4,8 @@
 // x (Uaf) stay resident in HBM from step to step and only the coil cells' source values cross PCIe:
 //   src/EC3D.f90:277-296  moving sources: keep only the inertial part of Jaf (A entries of conductor cells)
 //   src/EC3D.f90:298-367  Jaf(m) = a at the source cells                      (values computed by the host)
-//   src/EC3D.f90:374-393  Jaf = a*Uaf + Jaf at conductor cells; U-row RHS = sum over the row's A columns
+//   src/EC3D.f90:374-393  Jaf = a*Uaf + Jaf at conductor cells; U-row RHS = sum over the row's A columns, for the
+//                         rows 3*nCells + n, n <= max_m siznod(m) only (EC3D_U_RHS_REFERENCE; see k_rhs_inertial)
 //   src/EC3D.f90:396-402  zero Jaf at the six cel_bnd* lists
 //   src/EC3D.f90:412-433  after the solve: Jaf = a*Uaf - Jaf at conductor cells; zero Jaf, Uaf at cel_bndX/Y/Z
 // Same expression order as the reference, no contraction: bit-identical given the same inputs.
@@ -35,9 +36,13 @@ __global__ void k_scatter_sources(int64_t ns, const int32_t *idx, const double *
     if (q < ns) b[idx[q]] = val[q];
 }
 
-// :374-393  one thread per conducting cell
+// :374-393  one thread per conducting cell, m = the cell's scan-order ordinal = its U row's offset.  The reference
+// loops n = 1..siznod(m) over each domain m and sets the U row 3*nCells + n, so with several conducting domains
+// only the rows n <= max_m siznod(m) get their sum and the rest keep Jaf's initial 0 (nothing else writes a U row
+// of Jaf).  nu_rhs is that bound (EC3D_U_RHS_REFERENCE) or n_cond (EC3D_U_RHS_ALL); with one domain both are n_cond.
 __global__ void k_rhs_inertial(MatView A, const int32_t *cond_cell, const double *cond_a, int64_t nc,
-                               int64_t nCells, const double *__restrict__ x, double *__restrict__ b)
+                               int64_t nu_rhs, int64_t nCells, const double *__restrict__ x,
+                               double *__restrict__ b)
 {
     const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (m >= nc) return;
@@ -56,7 +61,7 @@ __global__ void k_rhs_inertial(MatView A, const int32_t *cond_cell, const double
                 const double v = t[7 + 3 * d + j];
                 if (v != 0.0) s = s + v * x[d * nCells + L + (j - 1) * A.sav_step[d]];
             }
-        b[row] = s;
+        b[row] = m < nu_rhs ? s : 0.0;
         return;
     }
     // :385-392  U row m restricted to its A columns (stored ascending, A columns first)
@@ -69,7 +74,7 @@ __global__ void k_rhs_inertial(MatView A, const int32_t *cond_cell, const double
             if (col < 3 * nCells && A.tval[e] != 0.0) s = s + A.tval[e] * x[col];
         }
     }
-    b[row] = s;
+    b[row] = m < nu_rhs ? s : 0.0;
 }
 
 // :412-425
@@ -108,7 +113,7 @@ void ec3d_free_rhs(ec3d_ctx *c)
     if (c->src_val) (void)hipFree(c->src_val);
     c->cond_cell = nullptr; c->cond_a = nullptr; c->bnd_list = nullptr; c->rhs_tmp = nullptr;
     c->src_idx = nullptr; c->src_val = nullptr;
-    c->n_cond = 0; c->n_cond_domains = 0; c->src_cap = 0;
+    c->n_cond = 0; c->n_cond_domains = 0; c->nu_siz_max = 0; c->src_cap = 0;
     for (auto &o : c->bnd_off) o = 0;
 }
 
@@ -119,15 +124,16 @@ int ec3d_setup_rhs(ec3d_ctx *c, int64_t nCells, const int8_t *geoPHYS, const int
     const int64_t nCd = c->nCd ? c->nCd : nCells; // device rows per component block
     std::vector<int32_t> cell;
     std::vector<double> a;
-    std::vector<char> seen((size_t)nsub_glob + 1, 0);
+    std::vector<int64_t> siznod((size_t)nsub_glob + 1, 0);
     for (int64_t q = 0; q < nCells; ++q)
         if (geoPHYS_C[q] != 0) {
             const int dom = geoPHYS[q];
             cell.push_back((int32_t)c->dev_cell(q));
             a.push_back(2.0 * valPHYS[1 * (int64_t)nsub_glob + dom - 1] / dt); // PHYS_C%valdom, vxc2data.f90:461
-            if (!seen[(size_t)dom]) { seen[(size_t)dom] = 1; ++c->n_cond_domains; }
+            if (siznod[(size_t)dom]++ == 0) ++c->n_cond_domains;
         }
     c->n_cond = (int64_t)cell.size();
+    for (int64_t n : siznod) c->nu_siz_max = std::max(c->nu_siz_max, n); // PHYS_C%siznod, vxc2data.f90:639-650
     std::vector<int32_t> lists;
     for (int w = 0; w < 6; ++w) {
         c->bnd_off[w] = (int64_t)lists.size();
@@ -160,10 +166,11 @@ static int need_grid(ec3d_ctx *c, const char *who)
         ec3d_set_error(std::string(who) + ": needs a matrix assembled with ec3d_assemble / ec3d_assemble_slab");
         return 3;
     }
-    if (c->n_cond_domains > 1) {
-        ec3d_set_error(std::string(who) + ": more than one conducting domain: the reference's own RHS loop "
-                                          "(src/EC3D.f90:385-392) indexes U rows per domain and is only "
-                                          "consistent for one; not reproduced");
+    const bool slab = c->in_multi || c->n_cells != (int64_t)c->sdx * c->sdy * c->sdz;
+    if (c->n_cond_domains > 1 && slab) {
+        ec3d_set_error(std::string(who) + ": more than one conducting domain on a z-slab: the reference's U-row "
+                                          "RHS bound (src/EC3D.f90:385-392, max siznod over the domains) is a "
+                                          "global count; only undivided handles (ec3d_assemble) reproduce it");
         return 5;
     }
     EC3D_HIP(hipSetDevice(c->device));
@@ -234,7 +241,8 @@ extern "C" int ec3d_rhs_step(ec3d_handle c, int32_t moving, int32_t nsrc, const 
         EC3D_HIP(hipStreamSynchronize(s)); // idx/val are stack-owned
     }
     if (nc) { // :370-404
-        k_rhs_inertial<<<blocks(nc), 256, 0, s>>>(c->A.view(), c->cond_cell, c->cond_a, nc, nCd, x, b);
+        const int64_t nu_rhs = c->u_rhs == EC3D_U_RHS_ALL ? nc : std::min(nc, c->nu_siz_max);
+        k_rhs_inertial<<<blocks(nc), 256, 0, s>>>(c->A.view(), c->cond_cell, c->cond_a, nc, nu_rhs, nCd, x, b);
         const int64_t cnt = c->bnd_off[6];
         if (cnt) k_zero_list<<<blocks(cnt), 256, 0, s>>>(c->bnd_list, cnt, b, nullptr);
     }
@@ -254,5 +262,17 @@ extern "C" int ec3d_post_update(ec3d_handle c)
     const int64_t cnt = c->bnd_off[3]; // cel_bndX, Y, Z only (:426-432)
     if (cnt) k_zero_list<<<blocks(cnt), 256, 0, c->stream>>>(c->bnd_list, cnt, b, x);
     EC3D_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int ec3d_set_u_rhs(ec3d_handle c, int32_t rule)
+{
+    if (!c) return 2;
+    if (rule != EC3D_U_RHS_REFERENCE && rule != EC3D_U_RHS_ALL) {
+        ec3d_set_error("ec3d_set_u_rhs: unknown rule " + std::to_string(rule) +
+                       " (EC3D_U_RHS_REFERENCE = 0, EC3D_U_RHS_ALL = 1)");
+        return 2;
+    }
+    c->u_rhs = rule;
     return 0;
 }

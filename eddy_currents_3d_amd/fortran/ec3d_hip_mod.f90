@@ -20,11 +20,13 @@ module ec3d_hip
               ec3d_multi_rhs_step, ec3d_multi_post_update, ec3d_multi_vtk_fields, ec3d_multi_true_residual, &
               ec3d_multi_vtk_fields_begin, ec3d_multi_vtk_fields_wait, ec3d_rccl_unique_id, ec3d_multi_create_rank, &
               ec3d_multi_plan, ec3d_set_preconditioner, ec3d_get_preconditioner, ec3d_precond_apply, &
-              EC3D_PRECOND_NONE, EC3D_PRECOND_MG, EC3D_PRECOND_BLOCK_MG
+              EC3D_PRECOND_NONE, EC3D_PRECOND_MG, EC3D_PRECOND_BLOCK_MG, &
+              ec3d_set_u_rhs, EC3D_U_RHS_REFERENCE, EC3D_U_RHS_ALL
 
     integer(c_int), parameter :: EC3D_VEC_X = 0, EC3D_VEC_B = 1   ! Uaf, Jaf
     integer(c_int), parameter :: EC3D_PRECOND_NONE = 0, EC3D_PRECOND_MG = 1   ! ec3d_set_preconditioner
     integer(c_int), parameter :: EC3D_PRECOND_BLOCK_MG = 2   ! ... of the structured A-V form (ec3d_assemble)
+    integer(c_int), parameter :: EC3D_U_RHS_REFERENCE = 0, EC3D_U_RHS_ALL = 1   ! ec3d_set_u_rhs
 
     interface
         integer(c_int) function ec3d_create(h, device) bind(C, name="ec3d_create")
@@ -174,6 +176,12 @@ module ec3d_hip
             type(c_ptr), value :: h
             real(c_double), intent(in) :: r(*)
             real(c_double), intent(out) :: z(*)
+        end function
+        ! U rows ec3d_rhs_step gives their right-hand side with several conducting domains (include/ec3d_hip.h)
+        integer(c_int) function ec3d_set_u_rhs(h, rule) bind(C, name="ec3d_set_u_rhs")
+            import :: c_ptr, c_int, c_int32_t
+            type(c_ptr), value :: h
+            integer(c_int32_t), value :: rule
         end function
         ! cel_bndX/Y/Z, cel_bndUx/y/z (src/EC3D.f90:758-760, :938-940): which = 0..5
         integer(c_int) function ec3d_get_cel_bnd(h, which, count, list) bind(C, name="ec3d_get_cel_bnd")

@@ -339,7 +339,7 @@ class _SourcesAhead:
 
 def run(model: vxc.VxcModel, solver, steps: int | None = None, out_dir: str | None = None, on_step=None,
         on_rhs=None, on_solved=None, write_output=None, overlap_output: bool = True, on_fields=None, on_written=None,
-        precond: str | None = None):
+        precond: str | None = None, u_rhs: str | None = None):
     """The reference's run of ``model`` on ``solver`` (an EC3DSolver): assemble, then step until T >= stop (or
     ``steps`` steps).  Returns a list of per-step dicts (T, iter).  ``out_dir``: write ``field_N.vtk`` there at
     the reference's output cadence.  Hooks, all ``(k, solver, info)``: ``on_rhs`` when Jaf (B) of step k is
@@ -356,10 +356,14 @@ def run(model: vxc.VxcModel, solver, steps: int | None = None, out_dir: str | No
     ``on_fields`` is called in the loop and ``info["fields"]`` holds them when they are not written.
     ``on_written(N, paths)``: after output step N's files are complete (a run of hundreds of 500 MB files may want
     to move them away).  ``precond`` (e.g. "block-mg"): solver.set_preconditioner(precond) right after the assembly;
-    None leaves the handle's preconditioner as it is."""
+    None leaves the handle's preconditioner as it is.  ``u_rhs`` ("reference" or "all"): solver.set_u_rhs(u_rhs)
+    before the assembly -- which U rows get their right-hand side with several conducting domains; None leaves the
+    handle's rule (default "reference", src/EC3D.f90:374-392) as it is."""
     t = vxc.domain_tables(model)
     if t["dt"] is None or t["time"] is None:
         raise ValueError("the model has no 'tran stop=... step=...' line")
+    if u_rhs is not None:
+        solver.set_u_rhs(u_rhs)
     solver.assemble(t["geoPHYS"], t["geoPHYS_C"], t["valPHYS"], t["BND"], t["delta"], t["dt"])
     if precond is not None:
         solver.set_preconditioner(precond)

@@ -28,6 +28,10 @@ def main(argv=None):
     ap.add_argument("--precond", choices=("none", "block-mg"), default="none",
                     help="preconditioner of the time step's solve: none (the reference's BiCGSTAB, default) or block-mg "
                          "(right-preconditioned BiCGSTAB, block multigrid M; one GPU only)")
+    ap.add_argument("--u-rhs", choices=("reference", "all"), default="reference",
+                    help="U rows that get their right-hand side when the model has several conducting domains: "
+                         "reference (rows up to the largest domain's cell count, as the reference does; default) or "
+                         "all (every U row: the consistent form, a departure from the reference; one GPU only)")
     a = ap.parse_args(argv)
 
     from . import EC3DSolver, host, vxc
@@ -48,6 +52,8 @@ def main(argv=None):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1 and a.precond != "none":
         ap.error(f"--precond {a.precond} runs on one GPU only; the multi-rank z-slab path has no preconditioner")
+    if world > 1 and a.u_rhs != "reference":
+        ap.error(f"--u-rhs {a.u_rhs} runs on one GPU only; z-slabs take one conducting domain")
     if world > 1:   # one process per GPU: z-slabs, halo exchange and reductions over RCCL
         import torch
         import torch.distributed as dist
@@ -65,7 +71,7 @@ def main(argv=None):
     else:
         with EC3DSolver(device=a.device) as s:
             log = host.run(model, s, steps=a.steps, out_dir=out_dir, on_step=on_step,
-                           precond=None if a.precond == "none" else a.precond)
+                           precond=None if a.precond == "none" else a.precond, u_rhs=a.u_rhs)
             n = s.n
     wall = time.perf_counter() - t0
     its = sum(i["iter"] for i in log)

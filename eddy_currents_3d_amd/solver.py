@@ -69,7 +69,8 @@ EXPORTS = ["sprsbcgstabwr_", "ec3d_invalidate", "ec3d_create", "ec3d_destroy", "
            "ec3d_multi_rhs_step", "ec3d_multi_post_update", "ec3d_multi_vtk_fields", "ec3d_multi_vtk_fields_begin",
            "ec3d_multi_vtk_fields_wait", "ec3d_multi_iterate_begin",
            "ec3d_multi_iterate", "ec3d_multi_synchronize", "ec3d_true_residual", "ec3d_multi_true_residual", "ec3d_get_visit_order", "ec3d_probe_csr_multi", "ec3d_multi_spmv", "ec3d_multi_api_calls", "ec3d_multi_plan", "ec3d_multi_halo_rows", "ec3d_rccl_unique_id", "ec3d_multi_create_rank", "ec3d_format_real8_gfortran", "ec3d_multi_iterate_timed", "ec3d_multi_rccl_info",
-           "ec3d_set_preconditioner", "ec3d_get_preconditioner", "ec3d_precond_apply"]
+           "ec3d_set_preconditioner", "ec3d_get_preconditioner", "ec3d_precond_apply", "ec3d_set_u_rhs"]
+U_RHS = {"reference": 0, "all": 1}   # EC3D_U_RHS_* of include/ec3d_hip.h
 PRECOND = {"none": 0, "mg": 1, "block-mg": 2}   # EC3D_PRECOND_* of include/ec3d_hip.h
 PRECOND_E_MATRIX, PRECOND_E_COARSE = 20, 21   # ec3d_set_preconditioner's refusals
 
@@ -149,6 +150,7 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.ec3d_set_preconditioner.argtypes = [hp, C.c_int, C.c_int32, C.c_int32, C.c_int32]
     L.ec3d_get_preconditioner.argtypes = [hp, C.POINTER(C.c_int), C.POINTER(C.c_int32), hp]
     L.ec3d_precond_apply.argtypes = [hp, _f64, _f64]
+    L.ec3d_set_u_rhs.argtypes = [hp, C.c_int32]
     L.ec3d_export_csr.argtypes = [hp, C.POINTER(C.c_int32), C.POINTER(C.c_int64), hp, hp, hp]
     L.ec3d_get_cel_bnd.argtypes = [hp, C.c_int, C.POINTER(C.c_int32), hp]
     L.ec3d_get_reduction_geometry.argtypes = [hp, C.c_int, C.POINTER(Geom)]
@@ -523,6 +525,14 @@ class EC3DSolver:
         y = np.empty(self.n)
         _chk(self.L, self.L.ec3d_spmv(self.h, np.ascontiguousarray(x, np.float64), y), "ec3d_spmv")
         return y
+
+    def set_u_rhs(self, rule: str = "reference"):
+        """Which U rows rhs_step gives their right-hand side with several conducting domains: "reference" (default)
+        only the rows n <= max siznod, as src/EC3D.f90:374-392 does; "all" every U row, the consistent form and a
+        departure from the reference.  Identical with one domain.  Kept across assemblies."""
+        if rule not in U_RHS:
+            raise ValueError(f"u_rhs must be one of {sorted(U_RHS)}, not {rule!r}")
+        _chk(self.L, self.L.ec3d_set_u_rhs(self.h, U_RHS[rule]), "ec3d_set_u_rhs")
 
     # ---- preconditioner ("mg": a matrix from assemble_poisson; "block-mg": the structured A-V form) -----------
     def set_preconditioner(self, kind: str = "mg", pre: int = 2, post: int = 2, coarse_sweeps: int = 0):

@@ -96,10 +96,21 @@ int ec3d_solve_resident(ec3d_handle h, double tolerance, int32_t itmax, int32_t 
  *   of Jaf (:277-296); then Jaf(src_index(q)) = src_value(q), q in order (1-based unknown ids; the
  *   host evaluates the source functions and the coil motion, :245-340); then Jaf = a*Uaf + Jaf on the
  *   conductor cells, the U-row right-hand sides (:385-392) and the zero-fills at cel_bnd* (:396-402).
- * ec3d_post_update  replaces :412-433 after the solve. */
+ * ec3d_post_update  replaces :412-433 after the solve.
+ * Any number of conducting domains on a handle of ec3d_assemble (each cell uses its own domain's 2C/dt); several of
+ * them on a slab (ec3d_assemble_slab, ec3d_multi_*) return 5. */
 int ec3d_rhs_step(ec3d_handle h, int32_t moving, int32_t nsrc, const int32_t *src_index,
                   const double *src_value);
 int ec3d_post_update(ec3d_handle h);
+
+/* Which U rows ec3d_rhs_step gives their right-hand side s = (the row's A part) . Uaf.  The reference loops over the
+ * conducting domains m and sets Jaf(3*nCells + n) = s for n = 1..siznod(m) (src/EC3D.f90:374-392), so with several
+ * domains only the U rows n <= max_m siznod(m) get theirs and every later U row keeps 0: EC3D_U_RHS_REFERENCE, the
+ * default.  EC3D_U_RHS_ALL gives every U row its s, the physically consistent right-hand side and a DEPARTURE from
+ * the reference.  With one conducting domain the two are the same.  The rule belongs to the handle and outlives new
+ * matrices.  An unknown rule returns 2 and leaves the handle unchanged. */
+enum { EC3D_U_RHS_REFERENCE = 0, EC3D_U_RHS_ALL = 1 };
+int ec3d_set_u_rhs(ec3d_handle h, int32_t rule);
 
 /* The four float32 point vectors of the reference's field_N.vtk (writeVtk_field, src/utilites.f90:222-289)
  * from the resident Uaf (X) and Jaf (B): Field_A, Vector_field_eddy (NULL allowed when there is no
@@ -146,13 +157,20 @@ int ec3d_get_cel_bnd(ec3d_handle h, int which, int32_t *count, int32_t *list);
  * multiplied in the same order either way.  Call before ec3d_set_matrix_csr / ec3d_assemble*. */
 int ec3d_set_format(ec3d_handle h, int dictionary);
 /* 1 (default): ec3d_assemble, ec3d_assemble_slab and ec3d_set_matrix_csr store the A-V system in its
- * structured form when they can (dictionary format on, <= 256 coefficient classes, conducting cells of
- * one domain numbered in scan order): U is embedded in the grid (device vectors hold 4 blocks of
- * planes*pitch rows, pitch >= sdx*sdy), every A<->U coupling is a fixed-offset stencil slot with a
- * class-coded coefficient, and there is no sliced-ELL tail.  Host vectors keep the reference's
- * numbering (3*nCells + Ncells0); the library permutes on upload/download.  0: bands + tail. */
+ * structured form when they can (dictionary format on, <= 256 coefficient classes, U ids in scan order):
+ * U is embedded in the grid (device vectors hold 4 blocks of planes*pitch rows, pitch >= sdx*sdy), every
+ * A<->U coupling is a fixed-offset stencil slot with a class-coded coefficient, and there is no sliced-ELL
+ * tail.  ec3d_assemble takes up to 22 conducting domains (55 + 9 D classes) as long as geoPHYS_C's
+ * domain-major U numbering (src/vxc2data.f90:624-636) equals scan order, i.e. every domain's cells follow the
+ * previous domain's in scan order: the reference's U ROWS are in scan order (src/EC3D.f90:521), and only then is
+ * its system a symmetric permutation of the structured one.  ec3d_assemble_slab and ec3d_set_matrix_csr take one
+ * conducting domain.  Otherwise bands + tail, which holds the reference's rows and columns as they are.  Host
+ * vectors keep the reference's numbering (3*nCells + Ncells0); the library permutes on upload/download.
+ * 0: bands + tail. */
 int ec3d_set_structured(ec3d_handle h, int on);
-/* device row of every unknown of the reference's numbering (n entries); identity unless structured */
+/* device row of every unknown of the reference's numbering (n entries); identity unless structured.  Structured:
+ * A rows go to their (pitched) cell, the U unknown 3*nCells + m (0-based m) to the U block row of the m-th conducting
+ * cell in scan order, which is the cell whose geoPHYS_C is 3*nCells + m + 1; the map increases within each block. */
 int ec3d_get_row_map(ec3d_handle h, int32_t *ref_to_dev);
 
 /* Preconditioner of ec3d_solve / ec3d_solve_resident.  EC3D_PRECOND_NONE (default): the reference's
@@ -178,7 +196,8 @@ int ec3d_get_row_map(ec3d_handle h, int32_t *ref_to_dev);
  * pre + post red-black Gauss-Seidel sweeps from zero on its unknowns, its right-hand side first projected onto the
  * U block's range (each conducting component's weighted mean taken out).  Rows without a diagonal give 0.  Same defaults
  * (2 / 2 / 16).  Refused with EC3D_PRECOND_E_MATRIX, the handle unchanged: Poisson, bands + tail (CSR, or
- * ec3d_set_structured(h, 0)), a slab, a handle of ec3d_multi.  ec3d_get_preconditioner reports the A blocks'
+ * ec3d_set_structured(h, 0)), a slab, a handle of ec3d_multi, more than 4 conducting domains (the smoothers' class
+ * table holds 64 classes, the structured form has 27 + 9 D A-row classes).  ec3d_get_preconditioner reports the A blocks'
  * levels; ec3d_precond_apply applies M on host vectors in the reference's numbering. */
 enum { EC3D_PRECOND_NONE = 0, EC3D_PRECOND_MG = 1, EC3D_PRECOND_BLOCK_MG = 2 };
 enum { EC3D_PRECOND_E_MATRIX = 20, EC3D_PRECOND_E_COARSE = 21 };
