@@ -1133,7 +1133,7 @@ static int place_vectors(ec3d_ctx *c, int cand, bool force)
         EC3D_HIP(hipMemsetAsync(c->vec[EC3D_VEC_B], 0x3f, (size_t)c->A.n * sizeof(double), c->stream)); // 4.8e-4 in every row
         int rc = ec3d_launch_begin(c, V, -1.0); // tol < 0: no exit, no restart
         if (rc) return rc;
-        c->xd_last = 2 * D;
+        (void)ec3d_run_open(c, 1, 2 * D);
         for (int it = 1; it <= D; ++it) ec3d_launch_iteration(c, V, it);
         EC3D_HIP(hipEventRecord(e0, c->stream));
         for (int it = D + 1; it <= 2 * D; ++it) ec3d_launch_iteration(c, V, it);
@@ -1224,7 +1224,7 @@ static int place_vectors(ec3d_ctx *c, int cand, bool force)
         EC3D_HIP(hipMemcpyAsync(c->state, &init, sizeof init, hipMemcpyHostToDevice, c->stream));
     }
     EC3D_HIP(hipStreamSynchronize(c->stream));
-    c->it_next = 1;
+    ec3d_run_reset(c);
     c->vplace_len = len;
     c->vplace_ms = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
     return 0;
@@ -1271,7 +1271,7 @@ int ec3d_spare_pair(ec3d_ctx *c)
     c->xasync_cap = c->xasync_forced = false;
     c->xinline = false;
     c->xdefer = 1;
-    c->pcur = c->apcur = c->scur = 1;
+    ec3d_run_reset(c);
     // X every D-th iteration: from the size where both fusions run by themselves (everything streams from HBM there, every
     // kernel at 5.6-5.9 TB/s of what it moves, so bytes are the only lever: K4 moves 50 B per row on average instead of
     // 56; 512^3: K4 1278 -> 1185 us, profiles/r04_deferred_x_512.log).  EC3D_XDEFER=1 keeps the classic K4, 2 .. 4 force
@@ -2011,9 +2011,9 @@ extern "C" int ec3d_get_row_map(ec3d_handle c, int32_t *ref_to_dev)
 // P and AP alternate between two buffers while K5 runs inside K1 (ec3d_fused51): the pair the last launch wrote
 static double *cur_vec(ec3d_ctx *c, int which)
 {
-    if ((ec3d_fused51(c) || ec3d_xdefer(c) > 1) && which == EC3D_VEC_P) return c->pbuf[c->pcur];
-    if (ec3d_fused51(c) && which == EC3D_VEC_AP) return c->apbuf[c->apcur];
-    if (ec3d_xdefer(c) > 1 && which == EC3D_VEC_S) return c->sbuf[c->scur];
+    if ((ec3d_fused51(c) || ec3d_xdefer(c) > 1) && which == EC3D_VEC_P) return c->pbuf[c->run.pcur];
+    if (ec3d_fused51(c) && which == EC3D_VEC_AP) return c->apbuf[c->run.apcur];
+    if (ec3d_xdefer(c) > 1 && which == EC3D_VEC_S) return c->sbuf[c->run.scur];
     return c->vec[which];
 }
 

@@ -174,11 +174,11 @@ extern "C" int ec3d_dist_step(ec3d_handle c, int32_t stage, int32_t it, double t
     auto fin_k3 = [&](bool split) {
         const RedSrc k3 = ec3d_part_of(c, EC3D_BY_SPMV, split);
         const unsigned m3 = 1u << P_D2 | 1u << P_D3 | (ec3d_fused23(c) ? 1u << P_SS : 0u);
-        if (c->ss_parts > 0 && !ec3d_fused23(c))
-            ec3d_launch_finalize2(RedSrc{c->partials, c->ss_parts, 1, c->sweep.pstride, nullptr}, 1u << P_SS, k3, m3, c->lsum, c->stream);
+        if (c->run.ss_parts > 0 && !ec3d_fused23(c))
+            ec3d_launch_finalize2(RedSrc{c->partials, c->run.ss_parts, 1, c->sweep.pstride, nullptr}, 1u << P_SS, k3, m3, c->lsum, c->stream);
         else
             ec3d_launch_finalize(k3, c->lsum, m3, c->stream);
-        c->ss_parts = 0;
+        c->run.ss_parts = 0;
     };
     auto need_split = [&]() {
         if (!c->can_overlap) ec3d_set_error("ec3d_dist_step: this slab cannot split K1/K3 (see ec3d_can_overlap)");
@@ -187,14 +187,7 @@ extern "C" int ec3d_dist_step(ec3d_handle c, int32_t stage, int32_t it, double t
     switch (stage) {
     case EC3D_STAGE_RESID:
         c->hist_cap = 0;
-        c->pcur = c->apcur = c->scur = 1; // (as ec3d_launch_begin: P = R goes to vec[P] = pbuf[1])
-        c->ap_valid_for = 0;
-        c->p_off = 0;
-        c->it_next = 1;
-        c->xd_base = 1;
-        c->xd_last = INT_MAX;
-        c->ss_parts = 0;
-        ec3d_xgroups_reset(c);
+        ec3d_run_reset(c);
         ec3d_launch_residual(A, c->sweep_s, v[EC3D_VEC_X], v[EC3D_VEC_B], v[EC3D_VEC_R], v[EC3D_VEC_R0],
                              v[EC3D_VEC_P], c->partials, c->stream);
         fin(EC3D_BY_SPMV, 1u << P_BB | 1u << P_RR_INIT);
@@ -204,14 +197,14 @@ extern "C" int ec3d_dist_step(ec3d_handle c, int32_t stage, int32_t it, double t
     // iteration does not exist yet (iteration 1, or a call that does not continue the last one), stage 2 nothing, stage 3
     // K2-in-K3 (sums S.S, AS.S, AS.AS), stage 4 K4 in SpMV form, stage 5 K5-in-K1, which sums AP.R0 of the NEXT iteration.
     case EC3D_STAGE_K1:
-        if (ec3d_fused51(c) && it != 1 && c->ap_valid_for == it) break;
+        if (ec3d_fused51(c) && it != 1 && c->run.ap_valid_for == it) break;
         ec3d_launch_stage(c, A, it, 1);
         fin(EC3D_BY_SPMV, 1u << P_D1);
         break;
     case EC3D_STAGE_K2:
         if (ec3d_fused23(c)) break;
         ec3d_launch_stage(c, A, it, 2);
-        c->ss_parts = ec3d_part_of(c, EC3D_BY_K2, false).count;
+        c->run.ss_parts = ec3d_part_of(c, EC3D_BY_K2, false).count;
         break;
     case EC3D_STAGE_K3:
         ec3d_launch_stage(c, A, it, 3);
@@ -251,8 +244,8 @@ extern "C" int ec3d_dist_step(ec3d_handle c, int32_t stage, int32_t it, double t
         const bool bnd = stage == EC3D_STAGE_K2_BND;
         ec3d_launch_k2(bnd ? c->sweep_vb : c->sweep_vi, ec3d_src_of(c, EC3D_BY_SPMV), c->state, it, v[EC3D_VEC_R], v[EC3D_VEC_AP],
                        ec3d_vec_at(c, EC3D_VEC_S, it), c->partials, c->stream);
-        c->scur = ec3d_xdefer(c) > 1 ? it % c->sdepth : 1;
-        if (!bnd) c->ss_parts = c->sweep_vb.nblk + c->sweep_vi.nblk; // (both launches' partials, folded by K3's collapse launch)
+        ec3d_after_s(c, it);
+        if (!bnd) c->run.ss_parts = c->sweep_vb.nblk + c->sweep_vi.nblk; // (both launches' partials, folded by K3's collapse launch)
         break;
     }
     case EC3D_STAGE_K5_BND:
@@ -261,12 +254,11 @@ extern "C" int ec3d_dist_step(ec3d_handle c, int32_t stage, int32_t it, double t
             ec3d_set_error("ec3d_dist_step: call ec3d_dist_set_boundary_rows first");
             return 3;
         }
-        // (deferred X update: the new P goes to the next buffer of the ring, as in ec3d_launch_stage)
+        // (deferred X update: the new P goes to the next buffer of the ring)
         ec3d_launch_k5(stage == EC3D_STAGE_K5_BND ? c->sweep_vb : c->sweep_vi, ec3d_src_of(c, EC3D_BY_K4), c->state, it,
                        v[EC3D_VEC_R], v[EC3D_VEC_AP], ec3d_vec_at(c, EC3D_VEC_P, it), ec3d_vec_at(c, EC3D_VEC_P, it + 1),
                        v[EC3D_VEC_R0], c->hist, c->hist_cap, c->stream);
-        if (ec3d_xdefer(c) > 1) c->pcur = ((it + 1 + c->p_off) % c->pdepth + c->pdepth) % c->pdepth;
-        c->it_next = it + 1;
+        ec3d_after_p(c, it);
         break;
     case EC3D_STAGE_K4F_BND:
     case EC3D_STAGE_K4F_INT:
@@ -298,7 +290,7 @@ int ec3d_dist_launches(const ec3d_ctx *c, int stage, int it)
 {
     const int fin = 1; // the collapse launch behind a producer of sums
     switch (stage) {
-    case EC3D_STAGE_K1: return (ec3d_fused51(c) && it != 1 && c->ap_valid_for == it) ? 0 : 1 + fin;
+    case EC3D_STAGE_K1: return (ec3d_fused51(c) && it != 1 && c->run.ap_valid_for == it) ? 0 : 1 + fin;
     case EC3D_STAGE_K2: return ec3d_fused23(c) ? 0 : 1; // (its S.S partials are folded by K3's collapse launch)
     case EC3D_STAGE_K5: return ec3d_fused51(c) ? 1 + fin : 1;
     case EC3D_STAGE_SETUP: case EC3D_STAGE_K1_INT: case EC3D_STAGE_K3_INT: case EC3D_STAGE_K2_BND: case EC3D_STAGE_K2_INT:

@@ -277,6 +277,24 @@ struct DevMatrix {
 
 struct ec3d_mg; // multigrid hierarchy (ec3d_mg.hip)
 
+// The host's cursor of a run of iterations.  The device state is addressed by the iteration number (rr0[it & 1], AP in
+// apbuf[it & 1], P and S in their rings), so the host keeps in step with it here and nowhere else: ec3d_run_reset starts
+// a run, ec3d_run_open says which iterations a call launches, ec3d_after_s / ec3d_after_p advance it behind a launch
+// (ec3d_solve.hip); a default-constructed cursor IS the state of a run that has just begun.
+struct IterCursor {
+    int p_off = 0;         // P(it) lives in pbuf[(it + p_off) % pdepth] (0: iterations are numbered from the last ec3d_run_reset)
+    int it_next = 1;       // the iteration the next launch has to be: ec3d_iterate / ec3d_multi_iterate must continue where the last call ended
+    int xd_base = 1;       // the iteration the groups of D are counted from (1 in a solve; ec3d_iterate: its first_iter)
+    int xd_last = INT_MAX; // the last iteration the present call is going to launch: it applies whatever is pending
+    int pcur = 1;          // which P buffer holds the CURRENT P (what ec3d_download and ec3d_device_vector hand out)
+    int apcur = 1, scur = 1; // the same for AP and S (a run begins with P = R in vec[P] = pbuf[1])
+    int ap_valid_for = 0;  // K5-in-K1: the iteration whose AP = A P the last K51 launch already produced (0: none)
+    int ss_parts = 0;      // z-slab: workgroup partials of S.S that K2 left for K3's collapse launch to fold (0: none pending)
+    int xg_n = 0;          // groups of X updates launched since the last ec3d_run_reset
+    int xg_done_upto = 0;  // the last iteration whose X update an enqueued k_x_group covers
+    void forget_ap() { ap_valid_for = 0; } // the next stage 1 launches K1 on its own (ec3d_time_kernel)
+};
+
 struct ec3d_ctx {
     int device = 0;
     hipStream_t stream = nullptr;         // the stream every launch goes to
@@ -303,11 +321,7 @@ struct ec3d_ctx {
     // Sweep::halo_store); the X update deferred over slab_xd iterations (0: not on this slab)
     bool slab_fused = false;
     int slab_xd = 0;
-    // P(it) lives in pbuf[(it + p_off) % pdepth] (0: iterations are numbered from the last ec3d_launch_begin)
-    int p_off = 0;
-    // The iteration the next launch has to be: the device state is addressed by the iteration number (rr0[it & 1], AP in
-    // apbuf[it & 1], P and S in their rings), so ec3d_iterate / ec3d_multi_iterate must continue where the last call ended
-    int it_next = 1;
+    IterCursor run; // where the iterations of this handle stand (host side)
     // K5-in-K1 reads the previous iteration's P and AP while it writes the new ones (neighbouring workgroups read the
     // old values of cells this one owns), so both vectors alternate between two buffers: P(it) lives in
     // pbuf[it & 1], AP(it) in apbuf[it & 1]; index 1 is vec[EC3D_VEC_P] / vec[EC3D_VEC_AP], index 0 the spare pair
@@ -335,15 +349,7 @@ struct ec3d_ctx {
     // launchers): noted there, turned into an error code by whoever checks the stage's launches (EC3D_ASYNC_CHECK)
     hipError_t async_err = hipSuccess;
     const char *async_what = nullptr;
-    int ss_parts = 0;      // z-slab: workgroup partials of S.S that K2 left for K3's collapse launch to fold (0: none pending)
-    int xg_n = 0;          // groups launched since the last ec3d_launch_begin
-    int xg_done_upto = 0;  // the last iteration whose X update an enqueued k_x_group covers
     int xdefer = 1;        // D: iterations between two X updates on this handle (1: every iteration, the classic K4)
-    int xd_base = 1;       // the iteration the groups of D are counted from (1 in a solve; ec3d_iterate: its first_iter)
-    int xd_last = 0x7fffffff; // the last iteration the present call is going to launch: it applies whatever is pending
-    int pcur = 1;          // which P buffer holds the CURRENT P (what ec3d_download and ec3d_device_vector hand out)
-    int apcur = 1, scur = 1; // the same for AP and S
-    int ap_valid_for = 0;  // K5-in-K1: the iteration whose AP = A P the last K51 launch already produced (0: none)
     // K2/K5 as boundary + interior launches (ec3d_dist_set_boundary_rows): tile lists on the device
     Sweep sweep_vb{}, sweep_vi{};
     int32_t *vb_list = nullptr, *vi_list = nullptr;
@@ -561,12 +567,25 @@ inline bool ec3d_xasync(const ec3d_ctx *c)
     if (!c->xasync_cap) return false;
     return (c->dist || c->halo != 0) ? c->slab_xasync : c->xasync_forced;
 }
-// where vector `vec` (EC3D_VEC_P / _AP / _S; anything else: the plain work vector) of iteration `it` lives on this handle
-double *ec3d_vec_at(const ec3d_ctx *c, int vec, int it);
+// the buffer of its ring (of AP's pair) that holds P / S / AP of iteration `it`; any `it`, negative ones too
+inline int ec3d_ring_slot(int it, int depth) { return (it % depth + depth) % depth; }
+inline int ec3d_p_slot(const ec3d_ctx *c, int it) { return ec3d_ring_slot(it + c->run.p_off, c->pdepth); }
+inline int ec3d_s_slot(const ec3d_ctx *c, int it) { return ec3d_ring_slot(it, c->sdepth); }
+inline int ec3d_ap_slot(int it) { return it & 1; }
+// where vector `vec` (EC3D_VEC_P / _AP / _S; anything else: the plain work vector) of iteration `it` lives: the slot worked
+// out from `me`'s cursor and plan, the pointer taken from `owner`'s tables (another slab of the job, ec3d_multi.hip)
+double *ec3d_vec_at(const ec3d_ctx *me, const ec3d_ctx *owner, int vec, int it);
+inline double *ec3d_vec_at(const ec3d_ctx *c, int vec, int it) { return ec3d_vec_at(c, c, vec, it); }
 int ec3d_flush_x(ec3d_ctx *c, int stop_iter); // the pending X updates after an exit at stop_iter (enqueued)
 bool ec3d_dist_can_split_planes(const ec3d_ctx *c);
 void ec3d_launch_x_group_of(ec3d_ctx *c, int first, int count, bool join);
-void ec3d_xgroups_reset(ec3d_ctx *c);
+// a new run of iterations on this handle: the cursor as a fresh handle has it (every caller, every field)
+void ec3d_run_reset(ec3d_ctx *c);
+// this call launches iterations first .. last.  who: the iterate entry point that has to continue the handle's iterations
+// (0, or 6 + error text when first is not the next one); nullptr: no such check
+int ec3d_run_open(ec3d_ctx *c, int first, int64_t last, const char *who = nullptr);
+void ec3d_after_s(ec3d_ctx *c, int it); // behind K2 / K2-in-K3 of iteration it
+void ec3d_after_p(ec3d_ctx *c, int it); // behind K5 / K5-in-K1 of iteration it
 void ec3d_launch_iteration(ec3d_ctx *c, const MatView &A, int it);
 int ec3d_launch_begin(ec3d_ctx *c, const MatView &A, double tol);
 int ec3d_single_rank_only(ec3d_ctx *c, const char *who);

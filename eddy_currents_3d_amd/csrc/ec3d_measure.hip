@@ -22,7 +22,7 @@ extern "C" int ec3d_time_iterations(ec3d_handle c, int32_t iters, double *ms_tot
     c->hist_cap = 0;
     if ((rc = ec3d_launch_begin(c, A, -1.0))) return rc; // tol < 0: no exit, no restart
     EC3D_HIP(hipEventRecord(c->t0, c->stream));
-    c->xd_last = iters;
+    (void)ec3d_run_open(c, 1, iters);
     for (int it = 1; it <= iters; ++it) ec3d_launch_iteration(c, A, it);
     EC3D_HIP(hipEventRecord(c->t1, c->stream));
     EC3D_HIP(hipGetLastError());
@@ -66,7 +66,7 @@ extern "C" int ec3d_get_x_groups(ec3d_handle c, int32_t *second_stream, int32_t 
     int rc = ec3d_need_matrix(c, "ec3d_get_x_groups");
     if (rc) return rc;
     if (second_stream) *second_stream = !ec3d_xasync(c) ? 0 : (c->xinline && !c->dist && c->halo == 0) ? 2 : 1;
-    if (groups_launched) *groups_launched = c->xg_n;
+    if (groups_launched) *groups_launched = c->run.xg_n;
     return 0;
 }
 
@@ -84,18 +84,8 @@ extern "C" int ec3d_iterate(ec3d_handle c, int32_t first_iter, int32_t count, do
     if (rc) return rc;
     if ((rc = ec3d_single_rank_only(c, "ec3d_iterate"))) return rc;
     const MatView A = c->A.view();
-    // deferred X update: groups counted from this call's first iteration, its last one applies what is pending --
-    // every call leaves X complete
-    // The device state is addressed by the iteration number -- rr0[it & 1], AP in apbuf[it & 1], P and S in their rings --
-    // so a call has to continue where the last one ended (ec3d_iterate_begin starts again from 1): iterate(1, n) twice
-    // would read an older P and the other rr0.
-    if (first_iter != c->it_next) {
-        ec3d_set_error("ec3d_iterate: first_iter = " + std::to_string(first_iter) + " does not continue the iterations of this "
-                       "handle (next: " + std::to_string(c->it_next) + "; ec3d_iterate_begin starts again from 1)");
-        return 6;
-    }
-    c->xd_base = first_iter;
-    c->xd_last = first_iter + count - 1;
+    // (deferred X update: every call leaves X complete)
+    if ((rc = ec3d_run_open(c, first_iter, (int64_t)first_iter + count - 1, "ec3d_iterate"))) return rc;
     if (!kernel_ms) {
         for (int it = first_iter; it < first_iter + count; ++it) ec3d_launch_iteration(c, A, it);
         EC3D_HIP(hipGetLastError());
@@ -145,16 +135,16 @@ extern "C" int ec3d_time_kernel(ec3d_handle c, int kernel, int32_t reps, double 
         return 5;
     }
     if ((rc = ec3d_launch_begin(c, A, -1.0))) return rc;
-    c->xd_last = 1;
+    (void)ec3d_run_open(c, 1, 1);
     ec3d_launch_iteration(c, A, 1); // populate every partial slot and the scalars
-    c->xd_base = c->xd_last = 2;     // (the single stages below: the classic K4, nothing pending)
+    (void)ec3d_run_open(c, 2, 2);   // (the single stages below: the classic K4, nothing pending)
     auto one = [&]() {
         if (kernel == EC3D_K_SPMV)
             ec3d_launch_spmv(A, c->sweep_s, v[EC3D_VEC_P], v[EC3D_VEC_AP], s);
         else {
             // K5-in-K1 handles: EC3D_K1 times the plain K1 of iteration 2 (on the AP buffer the fused launch filled),
             // EC3D_K5 the fused K5 + K1 launch
-            if (kernel == EC3D_K1) c->ap_valid_for = 0;
+            if (kernel == EC3D_K1) c->run.forget_ap();
             ec3d_launch_stage(c, A, 2, kernel);
         }
     };

@@ -344,23 +344,14 @@ int cross_wait(hipStream_t stream, hipEvent_t ev)
     return 0;
 }
 
-// Vector `vec` of iteration `it` in slab `owner`'s memory.  The ring position is worked out from MY handle's state
-// (every rank of a job runs the same plan with the same depths, and my state is current when I get here), the pointer
-// taken from the owner's tables, which do not change while a job runs: another rank's thread may be iterations ahead or
-// behind with its own host-side bookkeeping.
 constexpr int kFacts = 15;         // doubles every rank tells the others at set-up (finish_setup)
 constexpr int kPlainVec = INT_MIN; // `it` of a caller that means the plain work vector (uploads, probes, the time loop's X)
+// Vector `vec` of iteration `it` in slab `owner`'s memory: the ring position from MY handle's cursor, the pointer from
+// the owner's tables, which do not change while a job runs -- another rank's thread may be iterations ahead or behind
+// with its own host-side bookkeeping (ec3d_vec_at)
 double *vec_of(const ec3d_ctx *me, const ec3d_ctx *owner, int vec, int it)
 {
-    if (it == kPlainVec) return owner->vec[vec];
-    const bool f51 = ec3d_fused51(me);
-    const int D = ec3d_xdefer(me), pd = me->pdepth;
-    switch (vec) {
-    case EC3D_VEC_P: return (f51 || D > 1) ? owner->pbuf[((it + me->p_off) % pd + pd) % pd] : owner->vec[EC3D_VEC_P];
-    case EC3D_VEC_AP: return f51 ? owner->apbuf[it & 1] : owner->vec[EC3D_VEC_AP];
-    case EC3D_VEC_S: return D > 1 ? owner->sbuf[((it % me->sdepth) + me->sdepth) % me->sdepth] : owner->vec[EC3D_VEC_S];
-    default: return owner->vec[vec];
-    }
+    return it == kPlainVec ? owner->vec[vec] : ec3d_vec_at(me, owner, vec, it);
 }
 
 int halo_start(ec3d_multi *m, Slab &s, int v, int it = kPlainVec)
@@ -555,7 +546,7 @@ int run_plan(ec3d_multi *m, Slab &s, const std::vector<Op> &plan, int it, double
         case OP_HALO_WAIT: if ((rc = timed_sync(tm, s, T_HALO_WAIT, [&] { return halo_wait(s, op.arg); }))) return rc; break;
         case OP_GATHER: if ((rc = timed_sync(tm, s, T_GATHER, [&] { return gather(m, s); }))) return rc; break;
         case OP_SKIP_IF_AP: // AP = A P of this iteration came out of the last K5-in-K1: no lone K1, no sum, no exchange
-            if (it != 1 && s.c->ap_valid_for == it) oi += (size_t)op.arg;
+            if (it != 1 && s.c->run.ap_valid_for == it) oi += (size_t)op.arg;
             break;
         default: {
             int st = op.arg;
@@ -1054,7 +1045,7 @@ int slab_solve(ec3d_multi *m, Slab &s, double tol, int32_t itmax, int32_t *iter_
     const int64_t total = std::max<int64_t>(0, (int64_t)itmax + 1); // src/solvers.f90:25-29
     int rc = run_plan(m, s, begin_plan(s), 0, tol, nullptr);
     if (rc) return rc;
-    c->xd_last = (int)std::min<int64_t>(total, INT_MAX); // the itmax exit: the last iteration applies the pending X updates
+    (void)ec3d_run_open(c, 1, total); // the itmax exit: the last iteration applies the pending X updates
     // every rank must look at the flag after the same iterations, so the chunk is a property of the job
     // (finish_setup: from the largest slab), not of this slab
     const int chunk = m->chunk;
@@ -1753,17 +1744,10 @@ int multi_iterate(ec3d_multi *m, int32_t first_iter, int32_t count, int timed_ra
 {
     int rc = need(m, "ec3d_multi_iterate");
     if (rc) return rc;
-    if (first_iter != m->slab[0]->c->it_next) { // (as ec3d_iterate: the device state is addressed by the iteration number)
-        ec3d_set_error("ec3d_multi_iterate: first_iter = " + std::to_string(first_iter) + " does not continue the iterations "
-                       "of this handle (next: " + std::to_string(m->slab[0]->c->it_next) + "; ec3d_multi_iterate_begin "
-                       "starts again from 1)");
-        return 6;
-    }
-    for (auto &sp : m->slab) { // as ec3d_iterate: the groups of the deferred X update are counted from this call's first
-        ec3d_ctx *c = sp->c;   // iteration, its last one applies what is pending
-        c->xd_base = first_iter;
-        c->xd_last = first_iter + count - 1;
-    }
+    // as ec3d_iterate; slab 0's cursor speaks for the job (the other slabs' threads keep theirs in step with it)
+    for (size_t r = 0; r < m->slab.size(); ++r)
+        if ((rc = ec3d_run_open(m->slab[r]->c, first_iter, (int64_t)first_iter + count - 1, r == 0 ? "ec3d_multi_iterate" : nullptr)))
+            return rc;
     return run_all(m, [&](int r) -> int {
         Slab &s = *m->slab[(size_t)r];
         StageTimer tm;

@@ -42,17 +42,44 @@ RedSrc ec3d_part_of(const ec3d_ctx *c, int producer, bool split)
 
 // Where vector `vec` of iteration `it` lives: P in the ring pbuf (K5-in-K1 alternates two buffers, the deferred X update
 // keeps D), AP in apbuf (K5-in-K1), S in sbuf (deferred X update); otherwise the plain work vector.  The multi-rank
-// drivers address the halo exchange of an iteration's vector through the same function (ec3d_multi.hip).
-double *ec3d_vec_at(const ec3d_ctx *c, int vec, int it)
+// drivers address the halo exchange of an iteration's vector through the same function (ec3d_multi.hip): the ring
+// position is worked out from MY handle's state (every rank of a job runs the same plan with the same depths, and my
+// state is current when I get here), the pointer taken from the owner's tables, which do not change while a job runs:
+// another rank's thread may be iterations ahead or behind with its own host-side bookkeeping.
+double *ec3d_vec_at(const ec3d_ctx *me, const ec3d_ctx *owner, int vec, int it)
+{
+    const bool f51 = ec3d_fused51(me);
+    const int D = ec3d_xdefer(me);
+    switch (vec) {
+    case EC3D_VEC_P: return (f51 || D > 1) ? owner->pbuf[ec3d_p_slot(me, it)] : owner->vec[EC3D_VEC_P];
+    case EC3D_VEC_AP: return f51 ? owner->apbuf[ec3d_ap_slot(it)] : owner->vec[EC3D_VEC_AP];
+    case EC3D_VEC_S: return D > 1 ? owner->sbuf[ec3d_s_slot(me, it)] : owner->vec[EC3D_VEC_S];
+    default: return owner->vec[vec];
+    }
+}
+
+// P and S of the `count` iterations that end with `last`, oldest first: what a launch that applies pending X updates is
+// handed.  Entries at or past the count repeat the newest one (count = 0: iteration `last`'s own, whose S a K4 that
+// leaves X alone still reads as entry 0): no kernel dereferences them, any valid pointer will do.
+static void pending_bufs(const ec3d_ctx *c, int last, int count, const double **pp, const double **sp)
+{
+    const int n = std::max(count, 1);
+    for (int j = 0; j < EC3D_XD_MAX; ++j) {
+        const int itj = last - (n - 1) + std::min(j, n - 1);
+        pp[j] = ec3d_vec_at(c, EC3D_VEC_P, itj);
+        sp[j] = ec3d_vec_at(c, EC3D_VEC_S, itj);
+    }
+}
+
+// the cursor behind K2 / K2-in-K3 and behind K5 / K5-in-K1 of iteration it (ec3d_dist_step's split K2 / K5 launches too)
+void ec3d_after_s(ec3d_ctx *c, int it) { c->run.scur = ec3d_xdefer(c) > 1 ? ec3d_s_slot(c, it) : 1; }
+void ec3d_after_p(ec3d_ctx *c, int it)
 {
     const bool f51 = ec3d_fused51(c);
-    const int D = ec3d_xdefer(c), pd = c->pdepth;
-    switch (vec) {
-    case EC3D_VEC_P: return (f51 || D > 1) ? c->pbuf[((it + c->p_off) % pd + pd) % pd] : c->vec[EC3D_VEC_P];
-    case EC3D_VEC_AP: return f51 ? c->apbuf[it & 1] : c->vec[EC3D_VEC_AP];
-    case EC3D_VEC_S: return D > 1 ? c->sbuf[((it % c->sdepth) + c->sdepth) % c->sdepth] : c->vec[EC3D_VEC_S];
-    default: return c->vec[vec];
-    }
+    if (f51 || ec3d_xdefer(c) > 1) c->run.pcur = ec3d_p_slot(c, it + 1); // (else K5 updates P in place)
+    if (f51) c->run.apcur = ec3d_ap_slot(it + 1);
+    if (f51) c->run.ap_valid_for = it + 1;
+    c->run.it_next = it + 1;
 }
 
 // the five launches of one iteration; `k` selects one of them (1..5) or all (0).
@@ -61,7 +88,7 @@ double *ec3d_vec_at(const ec3d_ctx *c, int vec, int it)
 //   stage 2: empty, stage 3: K23 (S = R - alpha*AP inside AS = A S)
 //   stage 4: K4 -- as an SpMV kernel that computes A S again (ec3d_k4s: K23 then does not store AS), or the vector kernel
 //   stage 5: K51 (the exits and the P update of K5, then the NEXT iteration's K1 on the new P)
-// P(it) and AP(it) then live in pbuf[it % pdepth] / apbuf[it & 1] (ec3d_ctx).
+// P(it) and AP(it) then live in pbuf[ec3d_p_slot(it)] / apbuf[ec3d_ap_slot(it)] (ec3d_ctx).
 // With the X update deferred (ec3d_xdefer = D > 1; three launches or five) P(it) and S(it) live in rings of D buffers, K4
 // leaves X alone except in the last iteration of a group of D (counted from xd_base) or of the call (xd_last), where it
 // applies what is pending; an exit in between is completed by ec3d_flush_x.
@@ -72,83 +99,82 @@ void ec3d_launch_stage(ec3d_ctx *c, const MatView &A, int it, int k, int part)
     hipStream_t s = c->stream;
     const bool fused = ec3d_fused23(c); // K2 inside K3 (2-D tiles, single rank): stage 2 is empty, stage 3 is K23
     const bool f51 = ec3d_fused51(c);
-    const int D = ec3d_xdefer(c), pd = c->pdepth;
-    const bool ring = D > 1; // P(it) in the ring also on the five-launch iteration (K5 then writes the next buffer)
+    const int D = ec3d_xdefer(c);
     double *P = ec3d_vec_at(c, EC3D_VEC_P, it), *AP = ec3d_vec_at(c, EC3D_VEC_AP, it);
     double *S = ec3d_vec_at(c, EC3D_VEC_S, it);
-    const auto pidx = [&](int i) { return ((i + c->p_off) % pd + pd) % pd; };
     // fused: AP(it) was produced by the previous iteration's K51 -- unless this call does not continue that
     // iteration (iteration 1, ec3d_iterate from another first_iter, ec3d_time_kernel): then K1 runs on its own
-    if ((k == 0 || k == 1) && (!f51 || it == 1 || c->ap_valid_for != it))
+    if ((k == 0 || k == 1) && (!f51 || it == 1 || c->run.ap_valid_for != it))
         ec3d_launch_k1(A, ss, c->state, it, P, v[EC3D_VEC_R0], AP, c->partials, s);
     if ((k == 0 || k == 2) && !fused) {
         ec3d_launch_k2(c->sweep_k2, ec3d_src_of(c, EC3D_BY_SPMV), c->state, it, v[EC3D_VEC_R], AP, S, c->partials, s);
-        c->scur = D > 1 ? it % c->sdepth : 1;
+        ec3d_after_s(c, it);
     }
     if ((k == 0 || k == 3) && fused) {
         ec3d_launch_k23(A, ss, ec3d_src_of(c, EC3D_BY_SPMV), c->state, it, v[EC3D_VEC_R], AP, S,
                         ec3d_k4s(c) ? nullptr : v[EC3D_VEC_AS], c->partials, s); // (K4 in SpMV form computes A S again)
-        c->scur = D > 1 ? it % c->sdepth : 1;
+        ec3d_after_s(c, it);
     }
     if ((k == 0 || k == 3) && !fused)
         ec3d_launch_k3(A, ss, c->state, it, S, v[EC3D_VEC_AS], c->partials, s);
     if (k == 0 || k == 4) {
         // position of this iteration in its group of D, and how many updates an applying launch finds pending
-        const int xm = D > 1 ? (it - c->xd_base) % D : 0;
+        const int xm = D > 1 ? (it - c->run.xd_base) % D : 0;
         // (ec3d_xasync: no K4 touches X; alpha / omega of iteration it wait in entry it % 2D, and the group's own launch --
         // below, behind the K4 of its last iteration -- applies them)
         const bool xa = ec3d_xasync(c);
-        const bool group_end = D > 1 && (xm == D - 1 || it >= c->xd_last);
+        const bool group_end = D > 1 && (xm == D - 1 || it >= c->run.xd_last);
         const bool apply = !xa && (D <= 1 || group_end);
         const int xe = xa ? it % (2 * D) : xm; // the entry this K4 leaves its alpha / omega in
-        if (ec3d_k4s(c)) {
-            const double *pp[EC3D_XD_MAX] = {nullptr}, *sp[EC3D_XD_MAX] = {nullptr};
-            const int ne = apply ? xm + 1 : 0;
-            for (int j = 0; j < ne; ++j) { // iterations it - xm .. it, oldest first
-                pp[j] = c->pbuf[pidx(it - xm + j)];
-                sp[j] = D > 1 ? c->sbuf[(it - xm + j) % c->sdepth] : S;
-            }
-            if (ne == 0) sp[0] = S;
-            ec3d_launch_k4s(A, ss, ec3d_src_of(c, EC3D_BY_K2), ec3d_src_of(c, EC3D_BY_SPMV), c->state, it, ne, xe, pp, sp,
-                            v[EC3D_VEC_R0], v[EC3D_VEC_X], v[EC3D_VEC_R], c->partials, c->hist, c->hist_cap, s);
-        } else if (D <= 1 || (apply && xm == 0)) {
+        if (!ec3d_k4s(c) && (D <= 1 || (apply && xm == 0))) {
             ec3d_launch_k4(sw, ec3d_src_of(c, EC3D_BY_K2), ec3d_src_of(c, EC3D_BY_SPMV), c->state, it, P, S, v[EC3D_VEC_AS],
                            v[EC3D_VEC_R0], v[EC3D_VEC_X], v[EC3D_VEC_R], c->partials, c->hist, c->hist_cap, s);
         } else {
-            const double *pp[EC3D_XD_MAX] = {nullptr}, *sp[EC3D_XD_MAX] = {nullptr};
-            const int ne = apply ? xm + 1 : 0;
-            for (int j = 0; j < ne; ++j) { // iterations it - xm .. it, oldest first
-                pp[j] = c->pbuf[pidx(it - xm + j)];
-                sp[j] = c->sbuf[(it - xm + j) % c->sdepth];
-            }
-            if (ne == 0) sp[0] = S;
-            ec3d_launch_k4d(sw, ec3d_src_of(c, EC3D_BY_K2), ec3d_src_of(c, EC3D_BY_SPMV), c->state, it, ne, xe, pp, sp,
-                            v[EC3D_VEC_AS], v[EC3D_VEC_R0], v[EC3D_VEC_X], v[EC3D_VEC_R], c->partials, c->hist, c->hist_cap,
-                            s);
+            const double *pp[EC3D_XD_MAX], *sp[EC3D_XD_MAX];
+            const int ne = apply ? xm + 1 : 0; // iterations it - xm .. it
+            pending_bufs(c, it, ne, pp, sp);
+            if (ec3d_k4s(c))
+                ec3d_launch_k4s(A, ss, ec3d_src_of(c, EC3D_BY_K2), ec3d_src_of(c, EC3D_BY_SPMV), c->state, it, ne, xe, pp, sp,
+                                v[EC3D_VEC_R0], v[EC3D_VEC_X], v[EC3D_VEC_R], c->partials, c->hist, c->hist_cap, s);
+            else
+                ec3d_launch_k4d(sw, ec3d_src_of(c, EC3D_BY_K2), ec3d_src_of(c, EC3D_BY_SPMV), c->state, it, ne, xe, pp, sp,
+                                v[EC3D_VEC_AS], v[EC3D_VEC_R0], v[EC3D_VEC_X], v[EC3D_VEC_R], c->partials, c->hist,
+                                c->hist_cap, s);
         }
-        if (xa && group_end && part != 1) ec3d_launch_x_group_of(c, it - xm, xm + 1, it >= c->xd_last);
+        if (xa && group_end && part != 1) ec3d_launch_x_group_of(c, it - xm, xm + 1, it >= c->run.xd_last);
     }
-    if ((k == 0 || k == 5) && part != 1) c->it_next = it + 1;
-    if ((k == 0 || k == 5) && !f51) {
+    if ((k == 0 || k == 5) && !f51)
         ec3d_launch_k5(c->sweep_k5, ec3d_src_of(c, EC3D_BY_K4), c->state, it, v[EC3D_VEC_R], AP, P,
-                       ring ? c->pbuf[pidx(it + 1)] : P, v[EC3D_VEC_R0], c->hist, c->hist_cap, s);
-        if (ring) c->pcur = pidx(it + 1);
-    }
-    if ((k == 0 || k == 5) && f51) {
-        ec3d_launch_k51(A, ss, ec3d_src_of(c, EC3D_BY_K4), c->state, it, v[EC3D_VEC_R], P, AP, c->pbuf[pidx(it + 1)],
-                        c->apbuf[(it + 1) & 1], v[EC3D_VEC_R0], c->partials, c->hist, c->hist_cap, s);
-        c->ap_valid_for = it + 1;
-        c->pcur = pidx(it + 1);
-        c->apcur = (it + 1) & 1;
-    }
+                       ec3d_vec_at(c, EC3D_VEC_P, it + 1), v[EC3D_VEC_R0], c->hist, c->hist_cap, s);
+    if ((k == 0 || k == 5) && f51)
+        ec3d_launch_k51(A, ss, ec3d_src_of(c, EC3D_BY_K4), c->state, it, v[EC3D_VEC_R], P, AP, ec3d_vec_at(c, EC3D_VEC_P, it + 1),
+                        ec3d_vec_at(c, EC3D_VEC_AP, it + 1), v[EC3D_VEC_R0], c->partials, c->hist, c->hist_cap, s);
+    // (a slab's boundary launch, part 1, is followed by the interior launch of the same stage: that one advances)
+    if ((k == 0 || k == 5) && part != 1) ec3d_after_p(c, it);
 }
 
-// a new run of iterations on this handle: whatever the second stream still holds belongs to the last one and is waited for
-void ec3d_xgroups_reset(ec3d_ctx *c)
+// A new run of iterations on this handle.  Whatever the second stream still holds belongs to the last run and is waited
+// for; then every field of the cursor is what a fresh handle has.
+void ec3d_run_reset(ec3d_ctx *c)
 {
-    if (c->xstream && c->xg_n > 0) (void)hipStreamWaitEvent(c->stream, c->ev_xdone[(c->xg_n - 1) & 1], 0);
-    c->xg_n = 0;
-    c->xg_done_upto = 0;
+    if (c->xstream && c->run.xg_n > 0) (void)hipStreamWaitEvent(c->stream, c->ev_xdone[(c->run.xg_n - 1) & 1], 0);
+    c->run = IterCursor{};
+}
+
+int ec3d_run_open(ec3d_ctx *c, int first, int64_t last, const char *who)
+{
+    // The device state is addressed by the iteration number -- rr0[it & 1], AP in apbuf[it & 1], P and S in their rings --
+    // so an iterate call has to continue where the last one ended (its _begin starts again from 1): iterate(1, n) twice
+    // would read an older P and the other rr0.
+    if (who && first != c->run.it_next) {
+        ec3d_set_error(std::string(who) + ": first_iter = " + std::to_string(first) + " does not continue the iterations of "
+                       "this handle (next: " + std::to_string(c->run.it_next) + "; " + who + "_begin starts again from 1)");
+        return 6;
+    }
+    // deferred X update: the groups of D are counted from the call's first iteration, its last one applies what is pending
+    c->run.xd_base = first;
+    c->run.xd_last = (int)std::min<int64_t>(last, INT_MAX);
+    return 0;
 }
 
 // ec3d_xasync: the X updates of iterations first .. first + count - 1 as a launch of their own on the second stream,
@@ -158,18 +184,14 @@ void ec3d_xgroups_reset(ec3d_ctx *c)
 // call: whoever synchronises the main stream then has X).
 void ec3d_launch_x_group_of(ec3d_ctx *c, int first, int count, bool join)
 {
-    const int D = ec3d_xdefer(c), d2 = 2 * D, pd = c->pdepth;
+    const int d2 = 2 * ec3d_xdefer(c), n = c->run.xg_n;
     const double *pp[EC3D_XD_MAX], *sp[EC3D_XD_MAX];
-    for (int j = 0; j < EC3D_XD_MAX; ++j) { // entries past the count are never dereferenced: any valid pointer
-        const int itj = first + std::min(j, count - 1);
-        pp[j] = c->pbuf[((itj + c->p_off) % pd + pd) % pd];
-        sp[j] = c->sbuf[itj % c->sdepth];
-    }
+    pending_bufs(c, first + count - 1, count, pp, sp);
+    c->run.xg_n = n + 1;
+    c->run.xg_done_upto = first + count - 1;
     if (c->xinline) { // on the iteration's own stream, the vector kernels' grid: ordered by the stream itself
         // (256 ... 768 workgroups instead: the iteration within 0.3 % of the full grid's, profiles/r06_x_groups_own_launch.log)
         ec3d_launch_x_group(c->sweep, c->state, pp, sp, first, count, d2, c->vec[EC3D_VEC_X], 0, c->stream);
-        ++c->xg_n;
-        c->xg_done_upto = first + count - 1;
         return;
     }
     // 128 workgroups (half a workgroup per CU): beside the iteration's kernels the launch takes a small share of the
@@ -178,13 +200,11 @@ void ec3d_launch_x_group_of(ec3d_ctx *c, int first, int count, bool join)
     // (profiles/r05_x_groups_on_a_second_stream.log).  EC3D_XASYNC_WGS overrides (0: the vector kernels' grid).
     const int wgs = getenv("EC3D_XASYNC_WGS") ? atoi(getenv("EC3D_XASYNC_WGS")) : 128;
     EC3D_NOTE(c, hipEventRecord(c->ev_xready, c->stream));
-    if (c->xg_n > 0) EC3D_NOTE(c, hipStreamWaitEvent(c->stream, c->ev_xdone[(c->xg_n - 1) & 1], 0));
+    if (n > 0) EC3D_NOTE(c, hipStreamWaitEvent(c->stream, c->ev_xdone[(n - 1) & 1], 0));
     EC3D_NOTE(c, hipStreamWaitEvent(c->xstream, c->ev_xready, 0));
     ec3d_launch_x_group(c->sweep, c->state, pp, sp, first, count, d2, c->vec[EC3D_VEC_X], wgs, c->xstream);
-    EC3D_NOTE(c, hipEventRecord(c->ev_xdone[c->xg_n & 1], c->xstream));
-    if (join) EC3D_NOTE(c, hipStreamWaitEvent(c->stream, c->ev_xdone[c->xg_n & 1], 0));
-    ++c->xg_n;
-    c->xg_done_upto = first + count - 1;
+    EC3D_NOTE(c, hipEventRecord(c->ev_xdone[n & 1], c->xstream));
+    if (join) EC3D_NOTE(c, hipStreamWaitEvent(c->stream, c->ev_xdone[n & 1], 0));
 }
 
 // The X updates an exit at iteration stop_iter left pending (deferred X update): enqueued behind everything else.
@@ -194,20 +214,15 @@ int ec3d_flush_x(ec3d_ctx *c, int stop_iter)
     if (ec3d_xasync(c)) {
         // the groups already enqueued end themselves at the exit (k_x_group); the group the exit lies in may not have
         // been enqueued yet (the host stopped before its last iteration): now, cut at the exit by the kernel itself
-        if (stop_iter > c->xg_done_upto) ec3d_launch_x_group_of(c, c->xg_done_upto + 1, D, true);
-        else if (c->xg_n > 0 && !c->xinline) EC3D_HIP(hipStreamWaitEvent(c->stream, c->ev_xdone[(c->xg_n - 1) & 1], 0));
+        if (stop_iter > c->run.xg_done_upto) ec3d_launch_x_group_of(c, c->run.xg_done_upto + 1, D, true);
+        else if (c->run.xg_n > 0 && !c->xinline) EC3D_HIP(hipStreamWaitEvent(c->stream, c->ev_xdone[(c->run.xg_n - 1) & 1], 0));
         EC3D_HIP(hipGetLastError());
         EC3D_ASYNC_CHECK(c);
         return 0;
     }
-    if ((D <= 1 && !ec3d_k4s(c)) || stop_iter < c->xd_base) return 0;
-    const int xm = (stop_iter - c->xd_base) % D;
+    if ((D <= 1 && !ec3d_k4s(c)) || stop_iter < c->run.xd_base) return 0;
     const double *pp[EC3D_XD_MAX], *sp[EC3D_XD_MAX];
-    for (int j = 0; j < EC3D_XD_MAX; ++j) { // entries past the pending count are never dereferenced: any valid pointer
-        const int itj = stop_iter - xm + std::min(j, xm);
-        pp[j] = c->pbuf[((itj + c->p_off) % c->pdepth + c->pdepth) % c->pdepth];
-        sp[j] = D > 1 ? c->sbuf[itj % c->sdepth] : c->vec[EC3D_VEC_S];
-    }
+    pending_bufs(c, stop_iter, (stop_iter - c->run.xd_base) % D + 1, pp, sp);
     ec3d_launch_x_flush(c->sweep, c->state, pp, sp, c->vec[EC3D_VEC_X], c->stream);
     EC3D_HIP(hipGetLastError());
     return 0;
@@ -221,13 +236,7 @@ int ec3d_launch_begin(ec3d_ctx *c, const MatView &A, double tol)
     ec3d_launch_residual(A, c->sweep_s, v[EC3D_VEC_X], v[EC3D_VEC_B], v[EC3D_VEC_R], v[EC3D_VEC_R0], v[EC3D_VEC_P],
                          c->partials, c->stream);
     ec3d_launch_setup(c->state, ec3d_src_of(c, EC3D_BY_SPMV), tol, c->stream);
-    c->pcur = c->apcur = c->scur = 1; // P = R went to vec[P] = pbuf[1]
-    c->ap_valid_for = 0;
-    c->p_off = 0;
-    c->it_next = 1;
-    c->xd_base = 1;
-    c->xd_last = INT_MAX;
-    ec3d_xgroups_reset(c);
+    ec3d_run_reset(c);
     EC3D_HIP(hipGetLastError());
     return 0;
 }
@@ -266,7 +275,7 @@ static int solve_core(ec3d_ctx *c, double tol, int32_t itmax, int32_t *iter, dou
     int rc = ensure_hist(c, hist_host ? std::min<int64_t>(hist_cap, total) : 0);
     if (rc) return rc;
     if ((rc = ec3d_launch_begin(c, A, tol))) return rc;
-    c->xd_last = (int)std::min<int64_t>(total, INT_MAX); // the itmax exit: the last iteration applies what is pending
+    (void)ec3d_run_open(c, 1, total); // the itmax exit: the last iteration applies what is pending
 
     // iterations per poll: about 0.4 ms of device work, so an exit is noticed within ~1 ms
     const double est_us = (double)c->A.n_pad * 264.0 / 4.0e6 + 12.0;
