@@ -169,8 +169,9 @@ __global__ __launch_bounds__(256) void k_assemble_av(GridPar g, const int8_t *__
     double c[7];
     bool on_box;
     a_row_bands(g, i, j, k, c, on_box);
-    unsigned long long cnt = 0;
-    for (int b = 0; b < 7; ++b) cnt += 3ull * (c[b] != 0.0 || b == 3);
+    // nonzeros of the plain A row as the reference stores them: 7 minus one per box face the cell touches (a
+    // boundary value of 0 leaves a stored zero)
+    unsigned long long cnt = 3ull * (7 - (i == 1 || i == g.sdx) - (j == 1 || j == g.sdy) - (k == 1 || k == g.sdz));
     const int32_t u0 = geoC[nn0];
     const int ndom = geo[nn0];
     uint8_t fl = 0;

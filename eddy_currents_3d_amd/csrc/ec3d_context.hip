@@ -1732,8 +1732,14 @@ static int sav_to_csr(ec3d_ctx *c, std::vector<int32_t> &irow, std::vector<int32
             const int64_t q = c->dev_cell(qr);
             const int cc = cls[(size_t)(d * nCd + q)];
             const double *t = &tab[(size_t)cc * 16];
-            for (int b = 0; b < 7; ++b)
+            // a box-position class (tx + 3 ty + 9 tz) keeps every neighbour inside the box, also with coefficient 0.0
+            // (a boundary value of 0: the reference stores that zero, src/EC3D.f90:528-646)
+            const int tp[3] = {cc % 3, (cc / 3) % 3, cc / 9};
+            for (int b = 0; b < 7; ++b) {
+                const bool inside = cc < 27 && b != 3 && tp[b < 3 ? 2 - b : b - 4] != (b < 3 ? 0 : 2);
                 if (t[b] != 0.0) put(d * nC + c->ref_cell(q + A.off[b]) + 1, t[b]);
+                else if (inside) { jcol.push_back((int32_t)(d * nC + c->ref_cell(q + A.off[b]) + 1)); valA.push_back(t[b]); }
+            }
             if (cc >= A.sav_a0 && cc < A.sav_u0)
                 for (int m = -2; m <= 2; ++m) {
                     const double v = t[7 + m + 2];
@@ -1769,7 +1775,9 @@ extern "C" int ec3d_export_csr(ec3d_handle c, int32_t *n, int64_t *nnz, int32_t 
     } else {
         HostMatrix M;
         if ((rc = ec3d_download_matrix(c, M))) return rc;
-        ec3d_host_matrix_to_csr(M, ir, jc, va);
+        // the A-V operator of ec3d_assemble / ec3d_assemble_slab: entries are where the reference stores them
+        const CsrGrid grid = {c->sdx, c->sdy, c->sdz, c->n_cells, c->slab_e0, c->slab_k0, c->slab_k1};
+        ec3d_host_matrix_to_csr(M, ir, jc, va, c->n_cells > 0 ? &grid : nullptr);
     }
     *n = (int32_t)c->n_ref;
     *nnz = (int64_t)jc.size();

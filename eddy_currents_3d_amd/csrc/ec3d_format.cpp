@@ -163,18 +163,28 @@ int ec3d_build_dictionary_host(HostMatrix &M)
 }
 
 // inverse, for parity checks of the device assembly.  Band slots holding exactly 0.0 and tail
-// padding (value 0.0) are not emitted, so explicit zeros of a source CSR do not round-trip.
+// padding (value 0.0) are not emitted, so explicit zeros of a source CSR do not round-trip.  With `grid` (a natively
+// assembled A-V operator) the A rows of owned planes emit every neighbour inside the box, zero or not.
 void ec3d_host_matrix_to_csr(const HostMatrix &M, std::vector<int32_t> &irow, std::vector<int32_t> &jcol,
-                             std::vector<double> &valA)
+                             std::vector<double> &valA, const CsrGrid *grid)
 {
     irow.assign((size_t)M.n + 1, 0);
     jcol.clear();
     valA.clear();
     irow[0] = 1;
     for (int64_t r = 0; r < M.n; ++r) {
+        bool inside[7] = {false, false, false, false, false, false, false}; // bands -z, -y, -x, diag, +x, +y, +z
+        if (grid && M.nb == 7 && r < 3 * grid->cells) {
+            const int64_t q = r % grid->cells, i = q % grid->sdx, j = (q / grid->sdx) % grid->sdy,
+                          k = grid->e0 + q / (grid->sdx * grid->sdy);
+            if (k >= grid->k0 && k < grid->k1) {
+                inside[0] = k > 0; inside[1] = j > 0; inside[2] = i > 0; inside[3] = true;
+                inside[4] = i + 1 < grid->sdx; inside[5] = j + 1 < grid->sdy; inside[6] = k + 1 < grid->sdz;
+            }
+        }
         for (int b = 0; b < M.nb; ++b) {
             const double v = M.bands[(size_t)b * M.n_pad + r];
-            if (v != 0.0) {
+            if (v != 0.0 || (b < 7 && inside[b])) {
                 jcol.push_back((int32_t)(r + M.off[b] + 1));
                 valA.push_back(v);
             }

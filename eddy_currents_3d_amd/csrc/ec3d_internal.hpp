@@ -502,8 +502,14 @@ template <class T> struct DevTmp {
 // ec3d_format.cpp
 int ec3d_csr_to_host_matrix(int64_t n, const double *valA, const int32_t *irow, const int32_t *jcol,
                             HostMatrix &M);
+// native assembly's grid for ec3d_host_matrix_to_csr: an A row keeps the entry of every neighbour inside the box, even
+// where its coefficient is 0.0 (a boundary value of 0: the reference stores that zero, src/EC3D.f90:528-646)
+struct CsrGrid {
+    int64_t sdx, sdy, sdz, cells; // global grid; cells held per component
+    int64_t e0, k0, k1;           // first plane held; owned planes [k0, k1)
+};
 void ec3d_host_matrix_to_csr(const HostMatrix &M, std::vector<int32_t> &irow, std::vector<int32_t> &jcol,
-                             std::vector<double> &valA);
+                             std::vector<double> &valA, const CsrGrid *grid = nullptr);
 
 // ec3d_sav_csr.cpp: 0, or -1 when the matrix does not have the structure
 int ec3d_csr_to_sav_host(int64_t n, const double *valA, const int32_t *irow, const int32_t *jcol, SavHost &S);

@@ -1,7 +1,10 @@
 """GPU parity tests: the HIP path (through the C ABI of libec3d_hip.so) against the oracle and the
 fixtures captured from the unmodified reference.  Run on the MI355X box with ``-m gpu``.
 
-Bars (written here, as DESIGN.md §6 states them):
+Geometries beyond the captured plates (six distinct boundary values, several moving domains, concave conductors next to
+the box faces, every refusal path) are in tests/test_gpu_generated_av.py, held to the same bars.
+
+Bars (written here, as DESIGN.md §5 states them):
   * SpMV, assembly: bit-identical to the oracle / the reference's CSR.
   * Solve vs the oracle's "GPU order" twin (same algorithm, dot products summed in the kernels'
     order): bit-identical x, iter and residual history.

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Write tests/golden/g8*_*.npz: models with SEVERAL conducting domains, captured from the unmodified reference.
+"""Write tests/golden/g8*_*.npz and g9*_*.npz: models with SEVERAL conducting domains, and models with six distinct
+boundary values, captured from the unmodified reference.
 
 TEST INFRASTRUCTURE ONLY, like oracle/make_goldens.py, whose helpers it uses: needs the reference sources and
 oracle/_ref/EC3D_capture (``make -C oracle ref``).  Each fixture holds the inputs (vox, palette names, lattice,
@@ -16,7 +17,21 @@ the last step.
   g8d  g3's geometry with its plate split by a z-plane into two domains of the same material.  4 steps.  Its U
        rows past max siznod are the top plane's, which cel_bndUz zeroes anyway: both rules give the same b.
 
-    python tools/make_multidomain_goldens.py [g8a g8b g8c g8d]
+The g9 pair leaves the ground every earlier fixture stands on (BND = -0.95 on all six faces, box-shaped conductors):
+a ``boundary`` record with six distinct values, one of them 0 (the reference then stores explicit zeros) and two
+positive, on the anisotropic lattice (1, 1.25, 0.75).
+
+  g9a  two blocks touching along z, domain 1 below (U ids in scan order: the structured form applies), different
+       conductivities, each with its own Vex / Vey / Vez of mixed sign.  Static coil, 3 steps.
+  g9b  one conducting domain, L-shaped in the x-y plane (a concave step) with a 1 x 1 through hole along z, one cell
+       from the box on the low-x and on the high-y side, z planes [5, 11) of 16.  dist.slab_bounds cuts 16 planes at 8
+       for two slabs and at 6 and 11 for three: the cut at 11 coincides with the conductor's top face (the one-sided z
+       stencil of the plane below reads the second halo plane), the cut at 6 lies one plane above its bottom face, and
+       8 cuts it in the middle.  Moving coil (Vsx, and Vsy a FUNC), 3 steps, tol = 5m.  The reference stalls easily on
+       this shape (at tol = 1m, with the coil one plane lower, or with the conductor one plane thicker it takes the
+       itmax exit on the second or third step); this placement converges in 24, 14 and 13 iterations.
+
+    python tools/make_multidomain_goldens.py [g8a g8b g8c g8d g8ck g9a g9b]
 """
 from __future__ import annotations
 
@@ -35,14 +50,22 @@ SRC = ["f1 func Fp=a*cos(p2*f*t) a='183/(dx*2*dz)' p2='2*pi' f=50 t=t",
        "f2 func Fm=a*cos(p2*f*t) a='-183/(dx*2*dz)' p2='2*pi' f=50 t=t"]
 
 
-def _case(stem, vox, conductors, coil_extra, steps, tol, itmax, lattice="0.004", extra=()):
-    """conductors: [(palette name, C expression, (vex, vey, vez))], palette ids 1..D; coil ids D+1..D+4."""
+def _case(stem, vox, conductors, coil_extra, steps, tol, itmax, lattice="0.004", extra=(), adj=("1", "1", "1"),
+          bnd=None):
+    """conductors: [(palette name, C expression, (vex, vey, vez))], palette ids 1..D; coil ids D+1..D+4.
+    bnd: ((BXM, BXP), (BYM, BYP), (BZM, BZP)) of a ``boundary`` record; None: the reference's default, -0.95."""
     D = len(conductors)
     names = [f"{nm} D=1 C='{c}'" + ("" if not any(v) else " Vex={} Vey={} Vez={}".format(*v))
              for nm, c, v in conductors]
     names += G.coil_names(coil_extra) + [f"param tran stop={steps}m step=1m",
                                          f"p2 solver tol={tol} itmax={itmax} dir={stem[:3]}"] + SRC + list(extra)
-    calls, log = G.run_reference(vox=vox, names=names, lattice_dim=lattice, max_calls=steps, all_matrices=True)
+    BND = np.full((3, 2), -0.95)
+    if bnd is not None:
+        BND = np.array(bnd, np.float64)
+        names.append("bnd boundary " + " ".join(f"B{ax}{side}={BND[d, s]:g}" for d, ax in enumerate("XYZ")
+                                                for s, side in enumerate("MP")))
+    calls, log = G.run_reference(vox=vox, names=names, lattice_dim=lattice, adj=adj, max_calls=steps,
+                                 all_matrices=True)
     assert len(calls) == steps, (stem, len(calls))
     for c in calls[1:]:   # one assembly for the whole run: every call's CSR is the first one's
         assert np.array_equal(c["irow"], calls[0]["irow"]) and np.array_equal(c["jcol"], calls[0]["jcol"])
@@ -57,9 +80,10 @@ def _case(stem, vox, conductors, coil_extra, steps, tol, itmax, lattice="0.004",
     calls[0]["vtk"] = {last: calls[0]["vtk"][last]}
     d = G.pack_calls(calls)
     d["vtk_last"] = np.array(last)
-    G.save(stem, vox=vox, names=np.array(names), lattice_dim=np.array(lattice), adj=np.ones(3),
-           geoPHYS=geo, geoPHYS_C=geoC, delta=np.full(3, float(lattice)), dt=np.float64(1e-3),
-           BND=np.full((3, 2), -0.95), valPHYS=valPHYS, **d)
+    fadj = np.array([float(a) for a in adj])
+    G.save(stem, vox=vox, names=np.array(names), lattice_dim=np.array(lattice), adj=fadj,
+           geoPHYS=geo, geoPHYS_C=geoC, delta=float(lattice) * fadj, dt=np.float64(1e-3),
+           BND=BND, valPHYS=valPHYS, **d)
     print(stem, "iterations", [c["iter"] for c in calls])
 
 
@@ -117,7 +141,30 @@ def g8ck():
     print("g8ck iterations", c["iter"])
 
 
-CASES = dict(g8a=g8a, g8b=g8b, g8c=g8c, g8d=g8d, g8ck=g8ck)
+BND9 = ((-0.95, 0.5), (-1.0, 1.5), (0.0, -0.25))   # six distinct values: one 0, two positive
+ADJ9 = ("1", "1.25", "0.75")
+
+
+def g9a():
+    vox = np.zeros((14, 16, 20), np.uint8)
+    vox[3:6, 4:12, 4:16] = 1            # domain 1 below
+    vox[6:9, 4:12, 4:16] = 2            # domain 2 on top of it: U ids in scan order
+    G.put_coil(vox, (3, 4, 5, 6), 10, 12, 3, 13, 3, 17)
+    _case("g9a_two_moving_mixed_bnd_20x16x14", vox, [("alu", ALU, (1.5, -0.7, 0.3)), ("cu", CU, (-0.9, 0.4, -1.1))],
+          "", 3, "5m", 10000, adj=ADJ9, bnd=BND9)
+
+
+def g9b():
+    vox = np.zeros((16, 16, 17), np.uint8)
+    vox[5:11, 2:15, 1:14] = 1           # 13 x 13 x 6, one cell from the low-x and from the high-y face
+    vox[5:11, 2:8, 8:14] = 0            # the quadrant high-x / low-y cut away: an L with a concave step
+    vox[5:11, 11, 4] = 0                # through hole along z in the corner of the L, 1 x 1, walls 3 cells
+    G.put_coil(vox, (2, 3, 4, 5), 13, 15, 4, 12, 3, 11)
+    _case("g9b_L_hole_near_faces_17x16x16", vox, [("plast", ALU, (0, 0, 0))], " Vsx=2.0 Vsy=Vmy", 3, "5m", 10000,
+          extra=["m2 func Vmy=a*p2*f*cos(p2*f*t) a='-dY*3' p2='2*pi' f=100 t=t"], adj=ADJ9, bnd=BND9)
+
+
+CASES = dict(g8a=g8a, g8b=g8b, g8c=g8c, g8d=g8d, g8ck=g8ck, g9a=g9a, g9b=g9b)
 
 if __name__ == "__main__":
     for name in sys.argv[1:] or CASES:
