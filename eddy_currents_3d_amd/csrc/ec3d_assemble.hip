@@ -488,10 +488,10 @@ static int build_device_table(ec3d_ctx *c, DevMatrix &A, GridPar &g, const doubl
     if (ncls > 256) return 0;
     g.zero_cls = ncls - 1;
     A.ncls = ncls;
-    EC3D_HIP(hipMalloc(&A.table, (size_t)ncls * 7 * sizeof(double)));
+    EC3D_HIP(A.table.alloc((size_t)ncls * 7));
     k_build_table<<<(ncls + 63) / 64, 64, 0, c->stream>>>(g, d_valPHYS, A.table, ncls);
     EC3D_HIP(hipGetLastError());
-    EC3D_HIP(hipMalloc(&A.cls, (size_t)A.n_pad));
+    EC3D_HIP(A.cls.alloc((size_t)A.n_pad));
     EC3D_HIP(hipMemsetAsync(A.cls, g.zero_cls, (size_t)A.n_pad, c->stream));
     A.bytes += (int64_t)A.n_pad + ncls * 56;
     return ncls;
@@ -511,16 +511,17 @@ int ec3d_assemble_poisson_device(ec3d_ctx *c, int32_t sdx, int32_t sdy, int32_t 
         return 2;
     }
     ec3d_free_matrix(c);
+    MatrixBuild build(c);
     DevMatrix &A = c->A;
     A.n = g.nCells;
     A.n_pad = g.n_pad = round_up64(A.n, EC3D_TILE);
     set_offsets(A, g);
     // unused tail arrays still need valid pointers
-    EC3D_HIP(hipMalloc(&A.tail_id, 8));
-    EC3D_HIP(hipMalloc(&A.tile_flag, 8));
-    EC3D_HIP(hipMalloc(&A.chunk_ptr, 8));
-    EC3D_HIP(hipMalloc(&A.tcol, 8));
-    EC3D_HIP(hipMalloc(&A.tval, 8));
+    EC3D_HIP(A.tail_id.alloc(2));
+    EC3D_HIP(A.tile_flag.alloc(8));
+    EC3D_HIP(A.chunk_ptr.alloc(1));
+    EC3D_HIP(A.tcol.alloc(2));
+    EC3D_HIP(A.tval.alloc(1));
     const int64_t nblk = (g.nCells + 255) / 256;
     if (c->use_dict) {
         if (build_device_table(c, A, g, nullptr, 0) <= 0) return 100;
@@ -532,7 +533,7 @@ int ec3d_assemble_poisson_device(ec3d_ctx *c, int32_t sdx, int32_t sdy, int32_t 
     } else {
         const size_t bb = (size_t)7 * A.n_pad * sizeof(double);
         {
-            const int rcb = ec3d_alloc_bands(c, &A.bands, bb); // the placement a probe chose for this size, if any
+            const int rcb = ec3d_alloc_bands(c, A.bands, bb); // the placement a probe chose for this size, if any
             if (rcb) return rcb;
         }
         if (!A.bands) { // (ec3d_alloc_bands checks too: a NULL stream base would be a store at row * 8 from address zero)
@@ -552,7 +553,7 @@ int ec3d_assemble_poisson_device(ec3d_ctx *c, int32_t sdx, int32_t sdy, int32_t 
     c->have_matrix = true;
     c->sdx = sdx; c->sdy = sdy; c->sdz = sdz;
     c->halo = (k0 == 0 && k1 == sdz) ? 0 : g.kdz;
-    return ec3d_prepare_vectors(c);
+    return build.done(ec3d_prepare_vectors(c));
 }
 
 int ec3d_assemble_poisson_level(ec3d_ctx *c, DevMatrix &A, int32_t sdx, int32_t sdy, int32_t sdz, const double *BND,
@@ -610,6 +611,7 @@ int ec3d_assemble_device(ec3d_ctx *c, int32_t sdx, int32_t sdy, int32_t sdz, int
         return 2;
     }
     ec3d_free_matrix(c);
+    MatrixBuild build(c);
     DevMatrix &A = c->A;
     A.n = n;
     A.n_pad = g.n_pad = round_up64(n, EC3D_TILE);
@@ -626,28 +628,28 @@ int ec3d_assemble_device(ec3d_ctx *c, int32_t sdx, int32_t sdy, int32_t sdz, int
     const size_t bb = c->use_dict && nsub_glob + 28 <= 256 ? 0 : (size_t)7 * A.n_pad * sizeof(double);
     const size_t te = (size_t)std::max<int64_t>(A.tail_entries, 1);
     if (bb) {
-        EC3D_HIP(hipMalloc(&A.bands, bb));
+        EC3D_HIP(A.bands.alloc((size_t)7 * A.n_pad));
         EC3D_HIP(hipMemsetAsync(A.bands, 0, bb, c->stream));
     }
-    EC3D_HIP(hipMalloc(&A.tail_id, (size_t)A.n_pad * 4));
+    EC3D_HIP(A.tail_id.alloc((size_t)A.n_pad));
     EC3D_HIP(hipMemsetAsync(A.tail_id, 0xFF, (size_t)A.n_pad * 4, c->stream));
-    EC3D_HIP(hipMalloc(&A.tile_flag, (size_t)(A.n_pad / EC3D_TILE) + 4)); // + 4: read by dwords (sav_tile_coupled)
+    EC3D_HIP(A.tile_flag.alloc((size_t)(A.n_pad / EC3D_TILE) + 4)); // + 4: read by dwords (sav_tile_coupled)
     EC3D_HIP(hipMemsetAsync(A.tile_flag, 0, (size_t)(A.n_pad / EC3D_TILE) + 4, c->stream));
-    EC3D_HIP(hipMalloc(&A.chunk_ptr, cp.size() * 8));
+    EC3D_HIP(A.chunk_ptr.alloc(cp.size()));
     EC3D_HIP(hipMemcpyAsync(A.chunk_ptr, cp.data(), cp.size() * 8, hipMemcpyHostToDevice, c->stream));
-    EC3D_HIP(hipMalloc(&A.tcol, te * 4));
+    EC3D_HIP(A.tcol.alloc(te));
     EC3D_HIP(hipMemsetAsync(A.tcol, 0, te * 4, c->stream));
-    EC3D_HIP(hipMalloc(&A.tval, te * 8));
+    EC3D_HIP(A.tval.alloc(te));
     EC3D_HIP(hipMemsetAsync(A.tval, 0, te * 8, c->stream));
     A.bytes = (int64_t)(bb + (size_t)A.n_pad * 4 + A.n_pad / EC3D_TILE + cp.size() * 8 + te * 12);
 
     // inputs
-    DevTmp<int8_t> d_geo;
-    DevTmp<int32_t> d_geoC, d_uidx;
-    DevTmp<double> d_val;
-    DevTmp<uint8_t> d_flags;
-    DevTmp<int> d_err;
-    DevTmp<unsigned long long> d_nnz;
+    DevBuf<int8_t> d_geo;
+    DevBuf<int32_t> d_geoC, d_uidx;
+    DevBuf<double> d_val;
+    DevBuf<uint8_t> d_flags;
+    DevBuf<int> d_err;
+    DevBuf<unsigned long long> d_nnz;
     EC3D_HIP(d_geo.alloc((size_t)g.nCells));
     EC3D_HIP(d_geoC.alloc((size_t)g.nCells));
     EC3D_HIP(d_uidx.alloc((size_t)g.nCells));
@@ -675,7 +677,6 @@ int ec3d_assemble_device(ec3d_ctx *c, int32_t sdx, int32_t sdy, int32_t sdz, int
     EC3D_HIP(hipMemcpyAsync(flags.data(), d_flags, flags.size(), hipMemcpyDeviceToHost, c->stream));
     EC3D_HIP(hipStreamSynchronize(c->stream));
     if (err) {
-        ec3d_free_matrix(c);
         ec3d_set_error(err == 3 ? "ec3d_assemble: conductor touches the box boundary or is thinner than 3 cells "
                                   "(the reference indexes out of range here)"
                       : err == 2 ? "ec3d_assemble: node Fi double (src/EC3D.f90:924-936)"
@@ -715,6 +716,7 @@ int ec3d_assemble_device(ec3d_ctx *c, int32_t sdx, int32_t sdy, int32_t sdz, int
     c->n_cells = g.nCells;
     c->slab_e0 = e0; c->slab_k0 = k0; c->slab_k1 = k1;
     if ((rc = ec3d_prepare_vectors(c))) return rc;
+    build.done(0);
     // per-step RHS tables; in a slab they cover the held planes in local numbering (halo rows included:
     // what is computed there is overwritten by the next halo exchange or never read)
     return ec3d_setup_rhs(c, g.nCells, geoPHYS, geoPHYS_C, valPHYS, nsub_glob, dt);
@@ -781,6 +783,7 @@ int ec3d_assemble_sav_device(ec3d_ctx *c, int32_t sdx, int32_t sdy, int32_t sdz,
     if (n_dev > (int64_t)INT32_MAX - EC3D_TILE) return -1;
     g.ncells0 = nc0;
     ec3d_free_matrix(c);
+    MatrixBuild build(c);
     DevMatrix &A = c->A;
     A.n = n_dev;
     A.n_pad = g.n_pad = round_up64(n_dev, EC3D_TILE);
@@ -796,23 +799,23 @@ int ec3d_assemble_sav_device(ec3d_ctx *c, int32_t sdx, int32_t sdy, int32_t sdz,
     c->plane = g.kdz; c->pitch = g.pitch; c->nCd = g.nCd;
     A.ncls = id.ncls;
     c->n_ref = 3 * g.nCells + nc0;
-    EC3D_HIP(hipMalloc(&A.tail_id, 8));
-    EC3D_HIP(hipMalloc(&A.chunk_ptr, 8));
-    EC3D_HIP(hipMalloc(&A.tcol, 8));
-    EC3D_HIP(hipMalloc(&A.tval, 8));
-    EC3D_HIP(hipMalloc(&A.cls, (size_t)A.n_pad));
+    EC3D_HIP(A.tail_id.alloc(2));
+    EC3D_HIP(A.chunk_ptr.alloc(1));
+    EC3D_HIP(A.tcol.alloc(2));
+    EC3D_HIP(A.tval.alloc(1));
+    EC3D_HIP(A.cls.alloc((size_t)A.n_pad));
     EC3D_HIP(hipMemsetAsync(A.cls, id.zero, (size_t)A.n_pad, c->stream));
-    EC3D_HIP(hipMalloc(&A.tile_flag, (size_t)(A.n_pad / EC3D_TILE) + 4)); // + 4: read by dwords (sav_tile_coupled)
+    EC3D_HIP(A.tile_flag.alloc((size_t)(A.n_pad / EC3D_TILE) + 4)); // + 4: read by dwords (sav_tile_coupled)
     EC3D_HIP(hipMemsetAsync(A.tile_flag, 0, (size_t)(A.n_pad / EC3D_TILE) + 4, c->stream));
-    EC3D_HIP(hipMalloc(&A.table, (size_t)id.ncls * 16 * sizeof(double)));
+    EC3D_HIP(A.table.alloc((size_t)id.ncls * 16));
     A.bytes = A.n_pad + A.n_pad / EC3D_TILE + id.ncls * 128;
 
-    DevTmp<int8_t> d_geo;
-    DevTmp<int32_t> d_geoC;
-    DevTmp<double> d_val;
-    DevTmp<uint8_t> d_flags;
-    DevTmp<int> d_err;
-    DevTmp<unsigned long long> d_nnz;
+    DevBuf<int8_t> d_geo;
+    DevBuf<int32_t> d_geoC;
+    DevBuf<double> d_val;
+    DevBuf<uint8_t> d_flags;
+    DevBuf<int> d_err;
+    DevBuf<unsigned long long> d_nnz;
     EC3D_HIP(d_geo.alloc((size_t)g.nCells));
     EC3D_HIP(d_geoC.alloc((size_t)g.nCells));
     EC3D_HIP(d_val.alloc((size_t)nsub_glob * 5));
@@ -836,7 +839,6 @@ int ec3d_assemble_sav_device(ec3d_ctx *c, int32_t sdx, int32_t sdy, int32_t sdz,
     EC3D_HIP(hipMemcpyAsync(flags.data(), d_flags, flags.size(), hipMemcpyDeviceToHost, c->stream));
     EC3D_HIP(hipStreamSynchronize(c->stream));
     if (err) {
-        ec3d_free_matrix(c);
         ec3d_set_error(err == 3 ? "ec3d_assemble: conductor touches the box boundary or is thinner than 3 cells "
                                   "(the reference indexes out of range here)"
                                 : "ec3d_assemble: non-positive column (src/EC3D.f90:717-720, :945-948)");
@@ -853,7 +855,7 @@ int ec3d_assemble_sav_device(ec3d_ctx *c, int32_t sdx, int32_t sdy, int32_t sdz,
             if (tf[(size_t)t]) ul.push_back((int32_t)t);
         A.ntiles_front = first_u;
         A.ulist_n = (int)ul.size();
-        EC3D_HIP(hipMalloc(&A.ulist, std::max<size_t>(ul.size(), 1) * 4));
+        EC3D_HIP(A.ulist.alloc(std::max<size_t>(ul.size(), 1)));
         if (!ul.empty()) EC3D_HIP(hipMemcpy(A.ulist, ul.data(), ul.size() * 4, hipMemcpyHostToDevice));
     }
     for (auto &l : c->cel_bnd) l.clear();
@@ -877,7 +879,8 @@ int ec3d_assemble_sav_device(ec3d_ctx *c, int32_t sdx, int32_t sdy, int32_t sdz,
         }
         c->halo = g.pitch;
     }
-    if (nc0) EC3D_HIP(hipMalloc(&c->io_tmp, (size_t)nc0 * sizeof(double)));
+    if (nc0) EC3D_HIP(c->io_tmp.alloc((size_t)nc0));
     if ((rc = ec3d_prepare_vectors(c))) return rc;
+    build.done(0);
     return ec3d_setup_rhs(c, g.nCells, geoPHYS, geoPHYS_C, valPHYS, nsub_glob, dt);
 }

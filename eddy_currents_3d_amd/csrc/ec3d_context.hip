@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <chrono>
+#include <memory>
 #include <mutex>
 
 static thread_local std::string g_err;
@@ -174,11 +175,11 @@ extern "C" int ec3d_create(ec3d_handle *h, int device)
         return 102;
     }
     EC3D_HIP(hipSetDevice(device));
-    ec3d_ctx *c = new ec3d_ctx();
+    std::unique_ptr<ec3d_ctx> c(new ec3d_ctx()); // (a failure below returns what it has taken so far)
     c->device = device;
-    EC3D_HIP(hipStreamCreateWithFlags(&c->own_stream_obj, hipStreamNonBlocking));
+    EC3D_HIP(c->own_stream_obj.create(hipStreamNonBlocking));
     c->stream = c->own_stream_obj;
-    EC3D_HIP(hipMalloc(&c->state, sizeof(SolverState)));
+    EC3D_HIP(c->state.alloc(1));
     {   // a state nobody has set up yet reads "running, nothing pending": a stage driven from outside before any set-up stage
         // (ec3d_stage; tests/test_gpu_formats_dist.py drives K1 alone) otherwise meets whatever the allocation held before --
         // an exit word of 0 makes every stage return at once
@@ -186,28 +187,25 @@ extern "C" int ec3d_create(ec3d_handle *h, int device)
         init.stop_iter = INT_MAX;
         EC3D_HIP(hipMemcpy(c->state, &init, sizeof init, hipMemcpyHostToDevice));
     }
-    EC3D_HIP(hipHostMalloc(&c->state_pinned, 2 * sizeof(SolverState), hipHostMallocDefault));
-    for (int i = 0; i < 2; ++i) EC3D_HIP(hipEventCreateWithFlags(&c->ev[i], hipEventDisableTiming));
-    EC3D_HIP(hipEventCreate(&c->t0));
-    EC3D_HIP(hipEventCreate(&c->t1));
+    EC3D_HIP(c->state_pinned.alloc(2));
+    for (int i = 0; i < 2; ++i) EC3D_HIP(c->ev[i].create(hipEventDisableTiming));
+    EC3D_HIP(c->t0.create());
+    EC3D_HIP(c->t1.create());
     if (const char *e = getenv("EC3D_NBLK")) c->nblk_request = atoi(e);
     if (const char *e = getenv("EC3D_DICT")) c->use_dict = atoi(e) != 0;
     if (const char *e = getenv("EC3D_NT")) c->nt_request = atoi(e);
     if (const char *e = getenv("EC3D_SAV")) c->use_sav = atoi(e) != 0;
-    *h = c;
+    *h = c.release();
     return 0;
 }
 
 static void free_vectors(ec3d_ctx *c)
 {
-    if (c->vec_base && c->own_vectors) (void)hipFree(c->vec_base);
-    c->own_vectors = true;
-    if (c->partials) (void)hipFree(c->partials);
-    if (c->pp_base) (void)hipFree(c->pp_base);
-    c->pp_base = nullptr;
+    c->vec_own.reset(); // (adopted vectors are the caller's: there is nothing here to release then)
+    c->partials.reset();
+    c->pp_base.reset();
     c->pp_len = 0;
     c->vec_base = nullptr;
-    c->partials = nullptr;
     for (auto &v : c->vec) v = nullptr;
 }
 
@@ -215,37 +213,19 @@ void ec3d_free_matrix(ec3d_ctx *c)
 {
     DevMatrix &A = c->A;
     if (A.bands && c->bands_placed) { // keep the placement the probe chose for the next matrix of this size
-        if (c->placed_bands && c->placed_bands != A.bands) (void)hipFree(c->placed_bands);
-        c->placed_bands = A.bands;
         c->placed_bytes = (size_t)A.nb * A.n_pad * sizeof(double);
-    } else if (A.bands) {
-        (void)hipFree(A.bands);
+        c->placed_bands = std::move(A.bands);
     }
     c->bands_placed = false;
-    if (A.tail_id) (void)hipFree(A.tail_id);
-    if (A.tile_flag) (void)hipFree(A.tile_flag);
-    if (A.chunk_ptr) (void)hipFree(A.chunk_ptr);
-    if (A.tcol) (void)hipFree(A.tcol);
-    if (A.tval) (void)hipFree(A.tval);
-    if (A.ulist) (void)hipFree(A.ulist);
-    if (A.rp_flag) (void)hipFree(A.rp_flag);
-    if (A.cls) (void)hipFree(A.cls);
-    if (A.table) (void)hipFree(A.table);
     A = DevMatrix();
-    if (c->io_tmp) (void)hipFree(c->io_tmp);
-    c->io_tmp = nullptr;
-    if (c->vb_list) (void)hipFree(c->vb_list);
-    if (c->vi_list) (void)hipFree(c->vi_list);
-    c->vb_list = c->vi_list = nullptr;
-    if (c->il_umask) (void)hipFree(c->il_umask);
-    c->il_umask = nullptr;
-    if (c->il_seg) (void)hipFree(c->il_seg);
-    c->il_seg = nullptr;
-    if (c->us_list) (void)hipFree(c->us_list);
-    c->us_list = nullptr;
-    if (c->ii_list) (void)hipFree(c->ii_list);
-    if (c->ib_list) (void)hipFree(c->ib_list);
-    c->ii_list = c->ib_list = nullptr;
+    c->io_tmp.reset();
+    c->vb_list.reset();
+    c->vi_list.reset();
+    c->il_umask.reset();
+    c->il_seg.reset();
+    c->us_list.reset();
+    c->ii_list.reset();
+    c->ib_list.reset();
     c->us_host.clear();
     c->can_vsplit = false;
     c->n_ref = 0;
@@ -264,15 +244,10 @@ void ec3d_free_matrix(ec3d_ctx *c)
     ec3d_mg_free(c);
     c->poisson_full = false;
     c->have_matrix = false;
-    if (c->vplace_len > 0 && c->own_vectors && c->vec_base) { // keep the placement the search chose for the next matrix of this size
-        if (c->parked_vec) (void)hipFree(c->parked_vec);
-        if (c->parked_pp) (void)hipFree(c->parked_pp);
-        c->parked_vec = c->vec_base;
-        c->parked_pp = c->pp_base;
+    if (c->vplace_len > 0 && c->vec_own) { // keep the placement the search chose for the next matrix of this size
+        c->parked_vec = std::move(c->vec_own);
+        c->parked_pp = std::move(c->pp_base);
         c->parked_pp_len = c->pp_len;
-        c->vec_base = nullptr;
-        c->pp_base = nullptr;
-        c->pp_len = 0;
     }
     free_vectors(c);
     for (auto &l : c->cel_bnd) l.clear();
@@ -280,6 +255,8 @@ void ec3d_free_matrix(ec3d_ctx *c)
     c->n_cells = 0;
     c->slab_e0 = c->slab_k0 = c->slab_k1 = 0;
 }
+
+ec3d_ctx::~ec3d_ctx() { ec3d_mg_free(this); }
 
 extern "C" int ec3d_destroy(ec3d_handle c)
 {
@@ -291,29 +268,8 @@ extern "C" int ec3d_destroy(ec3d_handle c)
         (void)hipDeviceSynchronize();
     else
         (void)hipStreamSynchronize(c->stream);
-    c->stream = c->own_stream_obj;
-    if (c->xstream) {
-        (void)hipStreamSynchronize(c->xstream);
-        (void)hipStreamDestroy(c->xstream);
-        if (c->ev_xready) (void)hipEventDestroy(c->ev_xready);
-        for (int i = 0; i < 2; ++i)
-            if (c->ev_xdone[i]) (void)hipEventDestroy(c->ev_xdone[i]);
-        c->xstream = nullptr;
-    }
-    ec3d_free_matrix(c);
-    if (c->placed_bands) (void)hipFree(c->placed_bands);
-    c->placed_bands = nullptr;
-    if (c->parked_vec) (void)hipFree(c->parked_vec);
-    if (c->parked_pp) (void)hipFree(c->parked_pp);
-    c->parked_vec = c->parked_pp = nullptr;
-    if (c->hist) (void)hipFree(c->hist);
-    if (c->state) (void)hipFree(c->state);
-    if (c->state_pinned) (void)hipHostFree(c->state_pinned);
-    for (int i = 0; i < 2; ++i)
-        if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
-    if (c->t0) (void)hipEventDestroy(c->t0);
-    if (c->t1) (void)hipEventDestroy(c->t1);
-    if (c->own_stream_obj) (void)hipStreamDestroy(c->own_stream_obj);
+    if (c->xstream) (void)hipStreamSynchronize(c->xstream);
+    if (c->out_stream) (void)hipStreamSynchronize(c->out_stream); // (copies into the pinned buffers may still be under way)
     delete c;
     return 0;
 }
@@ -352,8 +308,7 @@ static int build_patch_tables(ec3d_ctx *c, int px, int py)
 {
     DevMatrix &A = c->A;
     if (A.rp_px == px && A.rp_py == py && A.rp_flag) return 0;
-    if (A.rp_flag) (void)hipFree(A.rp_flag);
-    A.rp_flag = nullptr;
+    A.rp_flag.reset();
     const int64_t sdx = A.sav_step[1], pitch = A.sav_step[2], planes = A.sav_nC / pitch, sdy = c->plane / sdx;
     const int64_t npx = sdx / px, npy = (sdy + py - 1) / py, tpp = npx * npy;
     std::vector<uint8_t> cls((size_t)A.n_pad);
@@ -379,7 +334,7 @@ static int build_patch_tables(ec3d_ctx *c, int px, int py)
             if (P < 3 * planes) flag[(size_t)(P * tpp + q)] = 1;
             else A.rp_ulist_host.push_back((int32_t)(P * tpp + q));
         }
-    EC3D_HIP(hipMalloc(&A.rp_flag, flag.size()));
+    EC3D_HIP(A.rp_flag.alloc(flag.size()));
     EC3D_HIP(hipMemcpy(A.rp_flag, flag.data(), flag.size(), hipMemcpyHostToDevice));
     A.rp_px = px;
     A.rp_py = py;
@@ -585,10 +540,8 @@ static int choose_sweep(ec3d_ctx *c)
             // stated size (256^3, 53.2 M unknowns, HBM-bound; profiles/r06_av256_*): the separate U list re-read ten
             // tile-sized operands per U tile from HBM -- K1 / K3 fetched 31.0 / 22.7 B per row for 25 / 17 algorithmic.
             // EC3D_SAV_IL=0 never, 2 on every such grid (tests: the small fixtures).
-            if (c->il_umask) (void)hipFree(c->il_umask);
-            if (c->il_seg) (void)hipFree(c->il_seg);
-            c->il_umask = nullptr;
-            c->il_seg = nullptr;
+            c->il_umask.reset();
+            c->il_seg.reset();
             c->il_umask_host.clear();
             c->il_seg_host.clear();
             {
@@ -668,9 +621,9 @@ static int choose_sweep(ec3d_ctx *c)
                         for (int x = 0; x < 8; ++x)
                             for (size_t j = 0; j < perx[(size_t)x].size() / 3; ++j)
                                 for (int q = 0; q < 3; ++q) seg[(j * 8 + (size_t)x) * 4 + (size_t)q] = perx[(size_t)x][j * 3 + (size_t)q];
-                        EC3D_HIP(hipMalloc(&c->il_umask, std::max<size_t>(um.size(), 1) * 4 + 4));
+                        EC3D_HIP(c->il_umask.alloc(std::max<size_t>(um.size(), 1) + 1));
                         EC3D_HIP(hipMemcpy(c->il_umask, um.data(), um.size() * 4, hipMemcpyHostToDevice));
-                        EC3D_HIP(hipMalloc(&c->il_seg, std::max<size_t>(seg.size(), 4) * 4));
+                        EC3D_HIP(c->il_seg.alloc(std::max<size_t>(seg.size(), 4)));
                         EC3D_HIP(hipMemcpy(c->il_seg, seg.data(), seg.size() * 4, hipMemcpyHostToDevice));
                         c->il_umask_host = um;
                         c->il_seg_host = seg;
@@ -746,8 +699,7 @@ static int choose_sweep(ec3d_ctx *c)
     // shares, one per XCD label; a share is taken plane by plane, consecutive tiles by consecutive workgroups of that
     // XCD at the same time, so in-plane and plane-to-plane neighbours meet in that XCD's L2.  Holes (-1) end a
     // workgroup's list.  The vector kernels keep the plain list (they read nothing twice).
-    if (c->us_list) (void)hipFree(c->us_list);
-    c->us_list = nullptr;
+    c->us_list.reset();
     c->us_host.clear();
     {
         const int local = 1;
@@ -772,14 +724,14 @@ static int choose_sweep(ec3d_ctx *c)
             for (int x = 0; x < 8; ++x)
                 for (size_t i = 0; i < share[x].size(); ++i)
                     perm[(size_t)(((int64_t)i / Gx) * G + ((int64_t)i % Gx) * 8 + x)] = share[x][i];
-            EC3D_HIP(hipMalloc(&c->us_list, perm.size() * 4));
+            EC3D_HIP(c->us_list.alloc(perm.size()));
             EC3D_HIP(hipMemcpy(c->us_list, perm.data(), perm.size() * 4, hipMemcpyHostToDevice));
             ss.ulist = c->us_list;
             ss.ulist_n = (int)perm.size();
             c->us_host = perm;
         } else if (rp) { // (a grid of fewer than 8 workgroups: the list as it is)
             if (!src.empty()) {
-                EC3D_HIP(hipMalloc(&c->us_list, src.size() * 4));
+                EC3D_HIP(c->us_list.alloc(src.size()));
                 EC3D_HIP(hipMemcpy(c->us_list, src.data(), src.size() * 4, hipMemcpyHostToDevice));
             }
             ss.ulist = c->us_list;
@@ -818,9 +770,8 @@ static int choose_sweep(ec3d_ctx *c)
     // the XCD-local order of the whole list).  Boundary launch: no front sweep at all -- the tiles of the four outer planes
     // of the three A blocks and the U tiles there, as ONE list (a listed tile starts its march afresh, which is what a
     // tile of a lone plane needs anyway).  Every owned tile is visited by exactly one of the two (ec3d_get_visit_order 3 / 4).
-    if (c->ib_list) (void)hipFree(c->ib_list);
-    if (c->ii_list) (void)hipFree(c->ii_list);
-    c->ib_list = c->ii_list = nullptr;
+    c->ib_list.reset();
+    c->ii_list.reset();
     if (A.sav && c->halo > 0 && sw.win_nt > 0 && ss.zm_tpp > 0 && ss.rp_px == 0 && c->A.ulist &&
         (int)c->A.ulist_host.size() == c->A.ulist_n) {
         const int64_t tpp = ss.zm_tpp, npo = sw.win_nt / tpp, H = 2, blk = sw.win_blk, p0 = sw.win_t0 / tpp;
@@ -863,7 +814,7 @@ static int choose_sweep(ec3d_ctx *c)
                     for (int x = 0; x < 8; ++x)
                         for (size_t i = 0; i < share[x].size(); ++i)
                             perm[(size_t)(((int64_t)i / Gx) * G + ((int64_t)i % Gx) * 8 + x)] = share[x][i];
-                    EC3D_HIP(hipMalloc(&c->ii_list, perm.size() * 4));
+                    EC3D_HIP(c->ii_list.alloc(perm.size()));
                     EC3D_HIP(hipMemcpy(c->ii_list, perm.data(), perm.size() * 4, hipMemcpyHostToDevice));
                 }
                 si.ulist = c->ii_list;
@@ -874,7 +825,7 @@ static int choose_sweep(ec3d_ctx *c)
                     for (int64_t pl : {(int64_t)0, (int64_t)1, npo - 2, npo - 1})
                         for (int64_t q = 0; q < tpp; ++q) bl.push_back((int32_t)(d * blk + (p0 + pl) * tpp + q));
                 bl.insert(bl.end(), ub.begin(), ub.end());
-                EC3D_HIP(hipMalloc(&c->ib_list, bl.size() * 4));
+                EC3D_HIP(c->ib_list.alloc(bl.size()));
                 EC3D_HIP(hipMemcpy(c->ib_list, bl.data(), bl.size() * 4, hipMemcpyHostToDevice));
                 sb.ntiles = 0; // (no front sweep: ec3d_tile_of / walk_zm find no plane whose tile exists)
                 sb.win_nt = 0;
@@ -933,19 +884,17 @@ static int choose_sweep(ec3d_ctx *c)
 // after EC3D_PLACE candidates (default 8; 0 or 1: off) -- about 15 ms each at 512^3.  Only from 32 Mi rows (below that
 // the streams partly live in the Infinity Cache and the spread is gone) and only while the device has room for a
 // second copy.  Results do not depend on it.
-int ec3d_alloc_bands(ec3d_ctx *c, double **bands, size_t bytes)
+int ec3d_alloc_bands(ec3d_ctx *c, DevBuf<double> &bands, size_t bytes)
 {
     if (c->placed_bands && c->placed_bytes == bytes) { // the placement found for this size earlier: no new probe
-        *bands = c->placed_bands;
-        c->placed_bands = nullptr;
+        bands = std::move(c->placed_bands);
         c->bands_placed = true;
         return 0;
     }
-    if (c->placed_bands) (void)hipFree(c->placed_bands); // another size now: the kept copy is of no use
-    c->placed_bands = nullptr;
+    c->placed_bands.reset(); // another size now: the kept copy is of no use
     c->bands_placed = false;
-    EC3D_HIP(hipMalloc(bands, bytes));
-    if (!*bands && bytes) { // (never seen; the r03j aborts were stores at row * 8 from a NULL stream base)
+    EC3D_HIP(bands.alloc(bytes / sizeof(double)));
+    if (!bands && bytes) { // (never seen; the r03j aborts were stores at row * 8 from a NULL stream base)
         ec3d_set_error("ec3d_alloc_bands: the allocation of the band streams returned no memory");
         return 100;
     }
@@ -967,9 +916,9 @@ static int place_bands(ec3d_ctx *c)
     const double budget_ms = 400.0; // the whole search: a candidate costs a 7.5 GB device copy and three launches (~15 ms at 512^3)
     const size_t bb = (size_t)A.nb * A.n_pad * sizeof(double);
     const bool verbose = getenv("EC3D_PLACE_VERBOSE") != nullptr;
-    hipEvent_t e0, e1;
-    EC3D_HIP(hipEventCreate(&e0));
-    EC3D_HIP(hipEventCreate(&e1));
+    Event e0, e1;
+    EC3D_HIP(e0.create());
+    EC3D_HIP(e1.create());
     auto time_it = [&](float &ms) -> int {
         const MatView V = A.view();
         ec3d_launch_spmv(V, c->sweep_s, c->vec[EC3D_VEC_P], c->vec[EC3D_VEC_AP], c->stream); // warm
@@ -989,17 +938,16 @@ static int place_bands(ec3d_ctx *c)
         if (std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count() > budget_ms) break;
         size_t fr = 0, tot = 0;
         if (hipMemGetInfo(&fr, &tot) != hipSuccess || fr < bb + ((size_t)1 << 30)) break;
-        double *other = nullptr;
-        if (hipMalloc(&other, bb) != hipSuccess) {
+        DevBuf<double> other; // (released at the end of this round, whichever copy it then holds)
+        if (other.alloc(bb / sizeof(double)) != hipSuccess) {
             (void)hipGetLastError();
             break;
         }
         if (hipMemcpyAsync(other, A.bands, bb, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) {
-            (void)hipFree(other);
             rc = 100;
             break;
         }
-        std::swap(other, A.bands); // A.bands: the new copy; other: the best so far
+        other.swap(A.bands); // A.bands: the new copy; other: the best so far
         float ms = 0.f;
         rc = time_it(ms);
         if (verbose) fprintf(stderr, "libec3d_hip: band placement %d: %.1f us per SpMV\n", k, 500.0 * ms);
@@ -1009,12 +957,9 @@ static int place_bands(ec3d_ctx *c)
             best = ms;
             c->place_kept = k;
         } else {
-            std::swap(other, A.bands);
+            other.swap(A.bands);
         }
-        (void)hipFree(other);
     }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     c->bands_placed = rc == 0;
     // AP held A*0 = 0 before and after
     return rc;
@@ -1027,27 +972,20 @@ int ec3d_prepare_vectors(ec3d_ctx *c)
 {
     // vectors and rings of a handle whose placement a search has chosen (place_vectors) are kept for the next matrix of the
     // same size: parked by ec3d_free_matrix (or set aside here), taken back below if the lengths agree
-    double *kept_vec = c->parked_vec, *kept_pp = c->parked_pp;
+    DevBuf<double> kept_vec = std::move(c->parked_vec), kept_pp = std::move(c->parked_pp);
     int64_t kept_pp_len = c->parked_pp_len;
-    c->parked_vec = c->parked_pp = nullptr;
     c->parked_pp_len = 0;
-    if (!kept_vec && c->vplace_len > 0 && c->own_vectors && c->vec_base) {
-        kept_vec = c->vec_base;
-        kept_pp = c->pp_base;
+    if (!kept_vec && c->vplace_len > 0 && c->vec_own) {
+        kept_vec = std::move(c->vec_own);
+        kept_pp = std::move(c->pp_base);
         kept_pp_len = c->pp_len;
-        c->vec_base = nullptr;
-        c->pp_base = nullptr;
-        c->pp_len = 0;
     }
     free_vectors(c);
     // a parked copy of plain band streams (ec3d_free_matrix keeps the placement a probe chose) that the NEW matrix did not
     // take back -- it has no plain bands, or bands of another size -- is of no use any more: 7.5 GB at 512^3 that would
     // otherwise stay allocated until ec3d_destroy and could push ec3d_spare_pair into its fallbacks
-    if (c->placed_bands) {
-        (void)hipFree(c->placed_bands);
-        c->placed_bands = nullptr;
-        c->placed_bytes = 0;
-    }
+    c->placed_bands.reset();
+    c->placed_bytes = 0;
     c->A.ulist_host.resize((size_t)c->A.ulist_n);
     if (c->A.ulist_n)
         EC3D_HIP(hipMemcpy(c->A.ulist_host.data(), c->A.ulist, (size_t)c->A.ulist_n * 4, hipMemcpyDeviceToHost));
@@ -1059,18 +997,19 @@ int ec3d_prepare_vectors(ec3d_ctx *c)
     c->ghost = round_up(maxoff + 2, galign);
     const int64_t len = c->ghost + c->A.n_pad + c->ghost;
     if (kept_vec && c->vplace_len == len) {
-        c->vec_base = kept_vec;
+        c->vec_own = std::move(kept_vec);
         if (kept_pp) { // (ec3d_spare_pair keeps rings of the length it wants and replaces any other)
-            c->pp_base = kept_pp;
+            c->pp_base = std::move(kept_pp);
             c->pp_len = kept_pp_len;
             EC3D_HIP(hipMemsetAsync(c->pp_base, 0, (size_t)c->pp_len * sizeof(double), c->stream));
         }
-    } else {
-        if (kept_vec) (void)hipFree(kept_vec);
-        if (kept_pp) (void)hipFree(kept_pp);
+    } else { // a kept set of another length goes BEFORE the new vectors are allocated
+        kept_vec.reset();
+        kept_pp.reset();
         c->vplace_len = 0;
-        EC3D_HIP(hipMalloc(&c->vec_base, (size_t)len * EC3D_NVEC * sizeof(double)));
+        EC3D_HIP(c->vec_own.alloc((size_t)len * EC3D_NVEC));
     }
+    c->vec_base = c->vec_own;
     EC3D_HIP(hipMemsetAsync(c->vec_base, 0, (size_t)len * EC3D_NVEC * sizeof(double), c->stream));
     for (int v = 0; v < EC3D_NVEC; ++v) c->vec[v] = c->vec_base + (size_t)v * len + c->ghost;
     if (c->n_ref == 0) c->n_ref = c->A.n;
@@ -1078,7 +1017,7 @@ int ec3d_prepare_vectors(ec3d_ctx *c)
         int rc = choose_sweep(c);
         if (rc) return rc;
     }
-    EC3D_HIP(hipMalloc(&c->partials, (size_t)P_NSLOT * c->sweep.pstride * sizeof(double)));
+    EC3D_HIP(c->partials.alloc((size_t)P_NSLOT * c->sweep.pstride));
     EC3D_HIP(hipMemsetAsync(c->partials, 0, (size_t)P_NSLOT * c->sweep.pstride * sizeof(double), c->stream));
     EC3D_HIP(hipStreamSynchronize(c->stream));
     {
@@ -1113,7 +1052,7 @@ static int place_vectors(ec3d_ctx *c, int cand, bool force)
     c->vplace_us.clear();
     c->vplace_kept = -1;
     c->vplace_ms = 0.f;
-    if (cand < 2 || !c->own_vectors || c->halo > 0 || c->dist || c->nranks > 1 || !c->vec_base) return 0;
+    if (cand < 2 || !c->own_vectors() || c->halo > 0 || c->dist || c->nranks > 1 || !c->vec_base) return 0;
     // by itself only where it has been seen to matter: the three-launch iteration (2-D tiles from 32 Mi rows, 1 GiB per
     // vector at 512^3).  The five-launch iteration of the structured A-V system at 53 M rows ran at 1437 ... 1447 us on every
     // one of twelve allocations (profiles/r06_vector_placement.log): nothing to choose there.
@@ -1125,9 +1064,9 @@ static int place_vectors(ec3d_ctx *c, int cand, bool force)
     c->hist_cap = 0; // (no residual history from these iterations)
     const size_t vec_bytes = (size_t)len * EC3D_NVEC * sizeof(double), pp_bytes = (size_t)c->pp_len * sizeof(double);
     const int D = std::max(1, ec3d_xdefer(c));
-    hipEvent_t e0, e1;
-    EC3D_HIP(hipEventCreate(&e0));
-    EC3D_HIP(hipEventCreate(&e1));
+    Event e0, e1;
+    EC3D_HIP(e0.create());
+    EC3D_HIP(e1.create());
     auto time_it = [&](float &ms) -> int { // on whatever c->vec / the rings point at; leaves them dirty
         EC3D_HIP(hipMemsetAsync(c->vec[EC3D_VEC_X], 0, (size_t)c->A.n_pad * sizeof(double), c->stream));
         EC3D_HIP(hipMemsetAsync(c->vec[EC3D_VEC_B], 0x3f, (size_t)c->A.n * sizeof(double), c->stream)); // 4.8e-4 in every row
@@ -1144,10 +1083,14 @@ static int place_vectors(ec3d_ctx *c, int cand, bool force)
         ms /= (float)D;
         return 0;
     };
-    auto repoint = [&](double *vb, double *pb) -> int {
-        c->vec_base = vb;
-        for (int v = 0; v < EC3D_NVEC; ++v) c->vec[v] = vb + (size_t)v * len + c->ghost;
-        c->pp_base = pb;
+    struct VecSet { DevBuf<double> vec, pp; }; // the work vectors and the rings of one candidate
+    auto trade = [&](VecSet &o) { // the handle owns o's set, o the one the handle had; the pointers stay behind
+        o.vec.swap(c->vec_own);
+        o.pp.swap(c->pp_base);
+    };
+    auto repoint = [&]() -> int { // the handle works on the set it owns
+        c->vec_base = c->vec_own;
+        for (int v = 0; v < EC3D_NVEC; ++v) c->vec[v] = c->vec_base + (size_t)v * len + c->ghost;
         return ec3d_spare_pair(c); // pp_len is what it wants: the ring pointers follow pp_base
     };
     float best = 0.f;
@@ -1158,38 +1101,42 @@ static int place_vectors(ec3d_ctx *c, int cand, bool force)
     c->vplace_us.push_back(1e3f * best);
     c->vplace_kept = 0;
     if (verbose) fprintf(stderr, "libec3d_hip: vector placement 0: %.1f us per iteration\n", 1e3 * best);
-    double *best_v = c->vec_base, *best_p = c->pp_base;
     // Candidates that lose are held until the search is over and freed together: hipMalloc, 0.5 ms as a rule, took 1.4-2 s when
     // it came behind the frees of earlier candidates (the fifth of 15 GiB at 512^3, the second of 30 / 51 GiB at 640^3 / 768^3:
     // profiles/r06_vector_placement.log) -- so what the search holds at once is capped: 96 GiB besides the first set.
-    std::vector<std::pair<double *, double *>> losers;
+    // Between two rounds the handle owns the best set so far; it is pointed at it again once, when the search is over.
+    std::vector<VecSet> losers;
     for (int k = 1; k < cand && !rc && best > 0.965f * worst; ++k) {
         if (std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count() > budget_ms) break;
         size_t fr = 0, tot = 0;
         if (hipMemGetInfo(&fr, &tot) != hipSuccess || fr < vec_bytes + pp_bytes + ((size_t)8 << 30)) break;
         if (!force && (size_t)k * (vec_bytes + pp_bytes) > ((size_t)96 << 30)) break;
-        double *nv = nullptr, *np = nullptr;
+        VecSet s;
         const auto t_alloc = std::chrono::steady_clock::now();
-        if (hipMalloc(&nv, vec_bytes) != hipSuccess) {
+        if (s.vec.alloc(vec_bytes / sizeof(double)) != hipSuccess) {
             (void)hipGetLastError();
             break;
         }
-        if (pp_bytes && hipMalloc(&np, pp_bytes) != hipSuccess) {
+        if (pp_bytes && s.pp.alloc(pp_bytes / sizeof(double)) != hipSuccess) {
             (void)hipGetLastError();
-            (void)hipFree(nv);
             break;
         }
-        if (hipMemsetAsync(nv, 0, vec_bytes, c->stream) != hipSuccess ||
-            (np && hipMemsetAsync(np, 0, pp_bytes, c->stream) != hipSuccess)) {
+        if (hipMemsetAsync(s.vec, 0, vec_bytes, c->stream) != hipSuccess ||
+            (s.pp && hipMemsetAsync(s.pp, 0, pp_bytes, c->stream) != hipSuccess)) {
             rc = 100;
         }
-        if (!rc) rc = repoint(nv, np);
+        const bool on_candidate = !rc; // the handle works on the candidate, s holds the best so far
+        if (on_candidate) {
+            trade(s);
+            rc = repoint();
+        }
         const double alloc_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_alloc).count();
         float ms = 0.f;
         if (!rc) rc = time_it(ms);
         if (rc) { // back to the best so far; the candidate goes
-            (void)repoint(best_v, best_p);
-            losers.emplace_back(nv, np);
+            if (on_candidate) trade(s);
+            (void)repoint();
+            losers.push_back(std::move(s));
             break;
         }
         if (verbose)
@@ -1199,20 +1146,13 @@ static int place_vectors(ec3d_ctx *c, int cand, bool force)
         if (ms < best) {
             best = ms;
             c->vplace_kept = k;
-            losers.emplace_back(best_v, best_p);
-            best_v = nv;
-            best_p = np;
         } else {
-            losers.emplace_back(nv, np);
+            trade(s);
         }
+        losers.push_back(std::move(s));
     }
-    for (auto &l : losers) {
-        (void)hipFree(l.first);
-        if (l.second) (void)hipFree(l.second);
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (!rc) rc = repoint(best_v, best_p);
+    losers.clear(); // every set that lost, together
+    if (!rc) rc = repoint();
     if (rc) return rc;
     // as ec3d_prepare_vectors left them: everything zero, nothing set up
     EC3D_HIP(hipMemsetAsync(c->vec_base, 0, vec_bytes, c->stream));
@@ -1235,7 +1175,7 @@ extern "C" int ec3d_place_vectors(ec3d_handle c, int32_t candidates)
     int rc = ec3d_need_matrix(c, "ec3d_place_vectors");
     if (rc) return rc;
     if ((rc = ec3d_single_rank_only(c, "ec3d_place_vectors"))) return rc;
-    if (!c->own_vectors) {
+    if (!c->own_vectors()) {
         ec3d_set_error("ec3d_place_vectors: this handle works on vectors it does not own");
         return 4;
     }
@@ -1289,9 +1229,8 @@ int ec3d_spare_pair(ec3d_ctx *c)
     // (a z-slab that owns its vectors gets the rings too: whether they are used is the multi-rank driver's decision --
     // ec3d_ctx::slab_xd, slab_fused -- because every rank of the job has to run the same plan)
     if (c->fuse23_ok != c->fuse51_ok || c->dist) D = 1;
-    if ((!c->fuse51_ok && D <= 1) || !c->own_vectors) {
-        if (c->pp_base) (void)hipFree(c->pp_base);
-        c->pp_base = nullptr;
+    if ((!c->fuse51_ok && D <= 1) || !c->own_vectors()) {
+        c->pp_base.reset();
         c->pp_len = 0;
         return 0;
     }
@@ -1324,12 +1263,9 @@ int ec3d_spare_pair(ec3d_ctx *c)
         c->xasync_forced = two_groups && xa == 2;
         c->xinline = D > 1 && xa == 3 && undivided;
         want = len * ((c->pdepth - 1) + 1 + (c->sdepth - 1));
-        if (c->pp_base && c->pp_len != want) {
-            (void)hipFree(c->pp_base);
-            c->pp_base = nullptr;
-        }
+        if (c->pp_base && c->pp_len != want) c->pp_base.reset();
         if (c->pp_base) break;
-        if (hipMalloc(&c->pp_base, (size_t)want * sizeof(double)) == hipSuccess) {
+        if (c->pp_base.alloc((size_t)want) == hipSuccess) {
             EC3D_HIP(hipMemsetAsync(c->pp_base, 0, (size_t)want * sizeof(double), c->stream));
             EC3D_HIP(hipStreamSynchronize(c->stream));
             c->pp_len = want;
@@ -1338,7 +1274,6 @@ int ec3d_spare_pair(ec3d_ctx *c)
         // no room for the rings (2 (D - 1) vectors more): the classic K4 with the spare pair alone, or -- when even that
         // does not fit -- no spare pair: five launches (ec3d_fused51 asks for pp_base)
         (void)hipGetLastError();
-        c->pp_base = nullptr;
         c->pp_len = 0;
         if (two_groups) { // rings of one group: the D-th K4 applies the updates
             two_groups = false;
@@ -1364,9 +1299,9 @@ int ec3d_spare_pair(ec3d_ctx *c)
         int least = 0, greatest = 0;
         EC3D_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
         const bool low = getenv("EC3D_XASYNC_PRIO") && atoi(getenv("EC3D_XASYNC_PRIO")) == 1;
-        EC3D_HIP(hipStreamCreateWithPriority(&c->xstream, hipStreamNonBlocking, low ? least : 0));
-        EC3D_HIP(hipEventCreateWithFlags(&c->ev_xready, hipEventDisableTiming));
-        for (int i = 0; i < 2; ++i) EC3D_HIP(hipEventCreateWithFlags(&c->ev_xdone[i], hipEventDisableTiming));
+        EC3D_HIP(c->xstream.create(hipStreamNonBlocking, low ? least : 0));
+        EC3D_HIP(c->ev_xready.create(hipEventDisableTiming));
+        for (int i = 0; i < 2; ++i) EC3D_HIP(c->ev_xdone[i].create(hipEventDisableTiming));
     }
     double *at = c->pp_base + c->ghost;
     c->apbuf[0] = at;
@@ -1406,8 +1341,7 @@ extern "C" int ec3d_set_workgroups(ec3d_handle c, int32_t nblk)
         }
         c->can_vsplit = false; // the boundary/interior tile sweeps were derived from the old geometry:
                                // ec3d_dist_set_boundary_rows has to be called again
-        if (c->partials) (void)hipFree(c->partials);
-        EC3D_HIP(hipMalloc(&c->partials, (size_t)P_NSLOT * c->sweep.pstride * sizeof(double)));
+        EC3D_HIP(c->partials.alloc((size_t)P_NSLOT * c->sweep.pstride));
         EC3D_HIP(hipMemset(c->partials, 0, (size_t)P_NSLOT * c->sweep.pstride * sizeof(double)));
         return ec3d_spare_pair(c);
     }
@@ -1415,10 +1349,10 @@ extern "C" int ec3d_set_workgroups(ec3d_handle c, int32_t nblk)
 }
 
 template <class T>
-static int up(T *&dst, const std::vector<T> &src, int64_t &bytes, hipStream_t s)
+static int up(DevBuf<T> &dst, const std::vector<T> &src, int64_t &bytes, hipStream_t s)
 {
     const size_t nb = std::max<size_t>(src.size(), 1) * sizeof(T);
-    EC3D_HIP(hipMalloc(&dst, nb));
+    EC3D_HIP(dst.alloc(nb / sizeof(T)));
     if (!src.empty()) EC3D_HIP(hipMemcpyAsync(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, s));
     bytes += (int64_t)nb;
     return 0;
@@ -1428,6 +1362,7 @@ int ec3d_upload_matrix(ec3d_ctx *c, const HostMatrix &M, int64_t halo)
 {
     EC3D_HIP(hipSetDevice(c->device));
     ec3d_free_matrix(c);
+    MatrixBuild build(c);
     c->halo = halo;
     DevMatrix &A = c->A;
     A.n = M.n;
@@ -1445,7 +1380,7 @@ int ec3d_upload_matrix(ec3d_ctx *c, const HostMatrix &M, int64_t halo)
         if ((rc = up(A.table, M.table, A.bytes, c->stream))) return rc;
     } else {
         const size_t nbytes = std::max<size_t>(M.bands.size(), 1) * sizeof(double);
-        if ((rc = ec3d_alloc_bands(c, &A.bands, nbytes))) return rc;
+        if ((rc = ec3d_alloc_bands(c, A.bands, nbytes))) return rc;
         if (!M.bands.empty())
             EC3D_HIP(hipMemcpyAsync(A.bands, M.bands.data(), M.bands.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
         A.bytes += (int64_t)nbytes;
@@ -1457,11 +1392,11 @@ int ec3d_upload_matrix(ec3d_ctx *c, const HostMatrix &M, int64_t halo)
     if ((rc = up(A.tval, M.tval, A.bytes, c->stream))) return rc;
     EC3D_HIP(hipStreamSynchronize(c->stream));
     c->have_matrix = true;
-    return ec3d_prepare_vectors(c);
+    return build.done(ec3d_prepare_vectors(c));
 }
 
 template <class T>
-static int down(std::vector<T> &dst, const T *src, size_t cnt)
+static int down(std::vector<T> &dst, const DevBuf<T> &src, size_t cnt)
 {
     dst.resize(cnt);
     if (cnt) EC3D_HIP(hipMemcpy(dst.data(), src, cnt * sizeof(T), hipMemcpyDeviceToHost));
@@ -1522,6 +1457,7 @@ int ec3d_upload_sav(ec3d_ctx *c, const SavHost &S)
 {
     EC3D_HIP(hipSetDevice(c->device));
     ec3d_free_matrix(c);
+    MatrixBuild build(c);
     DevMatrix &A = c->A;
     A.n = S.n_dev;
     A.n_pad = S.n_pad;
@@ -1538,14 +1474,14 @@ int ec3d_upload_sav(ec3d_ctx *c, const SavHost &S)
     A.ncls = S.ncls;
     c->n_ref = S.n_ref;
     c->plane = S.plane; c->pitch = S.pitch; c->nCd = S.nCd;
-    EC3D_HIP(hipMalloc(&A.tail_id, 8));
-    EC3D_HIP(hipMalloc(&A.chunk_ptr, 8));
-    EC3D_HIP(hipMalloc(&A.tcol, 8));
-    EC3D_HIP(hipMalloc(&A.tval, 8));
-    EC3D_HIP(hipMalloc(&A.cls, S.cls.size()));
-    EC3D_HIP(hipMalloc(&A.tile_flag, S.tile_flag.size() + 4)); // + 4: read by dwords (sav_tile_coupled)
-    EC3D_HIP(hipMalloc(&A.table, S.table.size() * 8));
-    EC3D_HIP(hipMalloc(&A.ulist, std::max<size_t>(S.ulist.size(), 1) * 4));
+    EC3D_HIP(A.tail_id.alloc(2));
+    EC3D_HIP(A.chunk_ptr.alloc(1));
+    EC3D_HIP(A.tcol.alloc(2));
+    EC3D_HIP(A.tval.alloc(1));
+    EC3D_HIP(A.cls.alloc(S.cls.size()));
+    EC3D_HIP(A.tile_flag.alloc(S.tile_flag.size() + 4)); // + 4: read by dwords (sav_tile_coupled)
+    EC3D_HIP(A.table.alloc(S.table.size()));
+    EC3D_HIP(A.ulist.alloc(std::max<size_t>(S.ulist.size(), 1)));
     EC3D_HIP(hipMemcpy(A.cls, S.cls.data(), S.cls.size(), hipMemcpyHostToDevice));
     EC3D_HIP(hipMemcpy(A.tile_flag, S.tile_flag.data(), S.tile_flag.size(), hipMemcpyHostToDevice));
     EC3D_HIP(hipMemcpy(A.table, S.table.data(), S.table.size() * 8, hipMemcpyHostToDevice));
@@ -1555,9 +1491,9 @@ int ec3d_upload_sav(ec3d_ctx *c, const SavHost &S)
     A.bytes = (int64_t)(S.cls.size() + S.tile_flag.size() + S.table.size() * 8 + S.ulist.size() * 4);
     c->n_cond = (int64_t)S.cond_cell.size();
     if (c->n_cond) {
-        EC3D_HIP(hipMalloc(&c->cond_cell, S.cond_cell.size() * 4));
+        EC3D_HIP(c->cond_cell.alloc(S.cond_cell.size()));
         EC3D_HIP(hipMemcpy(c->cond_cell, S.cond_cell.data(), S.cond_cell.size() * 4, hipMemcpyHostToDevice));
-        EC3D_HIP(hipMalloc(&c->io_tmp, S.cond_cell.size() * sizeof(double)));
+        EC3D_HIP(c->io_tmp.alloc(S.cond_cell.size()));
     }
     if (S.nown) { // a z-slab cut out of a recognised system (ec3d_sav_slice)
         c->nown = S.nown;
@@ -1568,7 +1504,7 @@ int ec3d_upload_sav(ec3d_ctx *c, const SavHost &S)
         c->halo = S.halo;
     }
     c->have_matrix = true;
-    return ec3d_prepare_vectors(c);
+    return build.done(ec3d_prepare_vectors(c));
 }
 
 extern "C" int ec3d_probe_csr(int32_t n, const double *valA, const int32_t *irow, const int32_t *jcol,

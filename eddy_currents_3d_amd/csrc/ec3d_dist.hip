@@ -32,10 +32,9 @@ extern "C" int ec3d_adopt_vectors(ec3d_handle c, double *base)
     int rc = ec3d_need_matrix(c, "ec3d_adopt_vectors");
     if (rc) return rc;
     EC3D_HIP(hipStreamSynchronize(c->stream));
-    if (c->vec_base && c->own_vectors) (void)hipFree(c->vec_base);
+    c->vec_own.reset(); // from here on the handle works on the caller's vectors and owns none
     const int64_t len = c->ghost + c->A.n_pad + c->ghost;
     c->vec_base = base;
-    c->own_vectors = false;
     for (int v = 0; v < EC3D_NVEC; ++v) c->vec[v] = base + (size_t)v * len + c->ghost;
     return ec3d_spare_pair(c); // adopted vectors: no spare pair, the kernels of an iteration stay unfused
 }
@@ -83,13 +82,12 @@ extern "C" int ec3d_dist_set_boundary_rows(ec3d_handle c, int32_t nranges, const
         for (int32_t q = 0; q < nranges && !bnd; ++q) bnd = lo[q] < r1 && hi[q] > r0;
         (bnd ? vb : vi).push_back(t);
     }
-    if (c->vb_list) (void)hipFree(c->vb_list);
-    if (c->vi_list) (void)hipFree(c->vi_list);
-    c->vb_list = c->vi_list = nullptr;
+    c->vb_list.reset();
+    c->vi_list.reset();
     c->can_vsplit = false;
     if (vb.empty() || vi.empty()) return 0; // nothing to split (single rank, or a slab that is all boundary)
-    EC3D_HIP(hipMalloc(&c->vb_list, vb.size() * 4));
-    EC3D_HIP(hipMalloc(&c->vi_list, vi.size() * 4));
+    EC3D_HIP(c->vb_list.alloc(vb.size()));
+    EC3D_HIP(c->vi_list.alloc(vi.size()));
     EC3D_HIP(hipMemcpy(c->vb_list, vb.data(), vb.size() * 4, hipMemcpyHostToDevice));
     EC3D_HIP(hipMemcpy(c->vi_list, vi.data(), vi.size() * 4, hipMemcpyHostToDevice));
     auto list_sweep = [&](const int32_t *list, size_t len, int max_blk, int part_off) {
@@ -126,9 +124,8 @@ int ec3d_dist_set_boundary_planes(ec3d_ctx *c, int32_t *enabled)
 {
     if (enabled) *enabled = 0;
     const Sweep &ss = c->sweep_s, &k2 = c->sweep_k2;
-    if (c->vb_list) (void)hipFree(c->vb_list);
-    if (c->vi_list) (void)hipFree(c->vi_list);
-    c->vb_list = c->vi_list = nullptr;
+    c->vb_list.reset();
+    c->vi_list.reset();
     c->can_vsplit = false;
     if (!ec3d_dist_can_split_planes(c)) return 0;
     const int64_t tpp = ss.zm_tpp, total = k2.ntiles;
@@ -305,7 +302,7 @@ extern "C" int ec3d_read_state_async(ec3d_handle c, int32_t *stop_iter_pinned)
 {
     if (!c || !c->state || !stop_iter_pinned) return 2;
     EC3D_HIP(hipSetDevice(c->device));
-    EC3D_HIP(hipMemcpyAsync(stop_iter_pinned, &c->state->stop_iter, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    EC3D_HIP(hipMemcpyAsync(stop_iter_pinned, &c->state.get()->stop_iter, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     return 0;
 }
 

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/ec3d_hip.h"
+#include "ec3d_own.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -250,24 +251,24 @@ struct DevMatrix {
     int64_t n = 0, n_pad = 0, nnz = 0;
     int nb = 0;
     int64_t off[EC3D_MAXB] = {0};
-    double *bands = nullptr;
-    int32_t *tail_id = nullptr;
-    uint8_t *tile_flag = nullptr;
+    DevBuf<double> bands;
+    DevBuf<int32_t> tail_id;
+    DevBuf<uint8_t> tile_flag;
     int64_t ntail = 0, nchunk = 0, tail_entries = 0;
-    int64_t *chunk_ptr = nullptr;
-    int32_t *tcol = nullptr;
-    double *tval = nullptr;
-    uint8_t *cls = nullptr; // dictionary form (ncls > 0): bands == nullptr
-    double *table = nullptr;
+    DevBuf<int64_t> chunk_ptr;
+    DevBuf<int32_t> tcol;
+    DevBuf<double> tval;
+    DevBuf<uint8_t> cls; // dictionary form (ncls > 0): bands is empty
+    DevBuf<double> table;
     int ncls = 0;
     // structured A-V form (see MatView)
     int sav = 0, sav_a0 = 0, sav_u0 = 0, sav_zero = 0;
-    int32_t *ulist = nullptr; // tiles of the U block that hold at least one unknown
+    DevBuf<int32_t> ulist; // tiles of the U block that hold at least one unknown
     int ulist_n = 0;
     std::vector<int32_t> ulist_host; // host copy for the visit-order export
     // the same for runtime-shaped 2-D tiles (Sweep::rp_*), made by choose_sweep for the shape it picked
     int rp_px = 0, rp_py = 0;
-    uint8_t *rp_flag = nullptr;            // per patch tile of the three A blocks: coupled
+    DevBuf<uint8_t> rp_flag;               // per patch tile of the three A blocks: coupled
     std::vector<int32_t> rp_ulist_host;    // patch tiles of the U block that hold an unknown, ascending
     int64_t ntiles_front = 0; // tiles swept unconditionally
     int64_t sav_nC = 0, sav_step[3] = {0, 0, 0};
@@ -298,12 +299,16 @@ struct IterCursor {
 struct ec3d_ctx {
     int device = 0;
     hipStream_t stream = nullptr;         // the stream every launch goes to
-    hipStream_t own_stream_obj = nullptr; // created by ec3d_create; `stream` may point elsewhere
+    Stream own_stream_obj;                // created by ec3d_create; `stream` may point elsewhere (and is never destroyed here)
     DevMatrix A;
     bool have_matrix = false;
     int64_t ghost = 0;     // zero halo (doubles) on both sides of every vector
+    // The work vectors.  vec_own holds them when they are the handle's; it is EMPTY while the handle works on vectors the
+    // caller gave it (ec3d_adopt_vectors).  vec_base / vec[] are what everything else uses: a view, never freed.
+    DevBuf<double> vec_own;
     double *vec_base = nullptr;
     double *vec[8] = {nullptr};
+    bool own_vectors() const { return vec_base == vec_own.get(); } // (also true while there are none)
     Sweep sweep{};   // vector kernels: K4's grid (and the geometry every other sweep is derived from)
     Sweep sweep_k2{}, sweep_k5{}; // K2 (2 reads + 1 write) and K5 (3 + 1) like other workgroup counts than K4 (5 + 2)
     Sweep sweep_s{}; // SpMV kernels (K1, K3, residual, spmv)
@@ -327,7 +332,7 @@ struct ec3d_ctx {
     // pbuf[it & 1], AP(it) in apbuf[it & 1]; index 1 is vec[EC3D_VEC_P] / vec[EC3D_VEC_AP], index 0 the spare pair
     // With the X update deferred over D iterations (k4d_x_r_update; only together with both fusions) P(it) lives in
     // pbuf[it % D] and S(it) in sbuf[it % D] (index 1 = vec[EC3D_VEC_P] / vec[EC3D_VEC_S]); AP keeps its two buffers.
-    double *pp_base = nullptr;
+    DevBuf<double> pp_base;
     int64_t pp_len = 0;    // doubles allocated at pp_base
     double *pbuf[2 * EC3D_XD_MAX] = {nullptr}, *sbuf[2 * EC3D_XD_MAX] = {nullptr}, *apbuf[2] = {nullptr, nullptr};
     int pdepth = 2;        // buffers P cycles through (2, or D; 2 D with the X groups on a stream of their own)
@@ -343,8 +348,8 @@ struct ec3d_ctx {
     // group suffice): the undivided handle's three-launch iteration, where K4 in SpMV form with ten more operand streams in
     // the applying launch ran 18 % over what its bytes allow and a light K4 + one streaming launch per group do not
     bool xinline = false;
-    hipStream_t xstream = nullptr;
-    hipEvent_t ev_xready = nullptr, ev_xdone[2] = {nullptr, nullptr};
+    Stream xstream;
+    Event ev_xready, ev_xdone[2];
     // first failed runtime call of a launcher that cannot return a status (ec3d_launch_x_group_of sits inside the void stage
     // launchers): noted there, turned into an error code by whoever checks the stage's launches (EC3D_ASYNC_CHECK)
     hipError_t async_err = hipSuccess;
@@ -352,22 +357,22 @@ struct ec3d_ctx {
     int xdefer = 1;        // D: iterations between two X updates on this handle (1: every iteration, the classic K4)
     // K2/K5 as boundary + interior launches (ec3d_dist_set_boundary_rows): tile lists on the device
     Sweep sweep_vb{}, sweep_vi{};
-    int32_t *vb_list = nullptr, *vi_list = nullptr;
-    int32_t *us_list = nullptr; // structured form: the U tiles in the order the z-marching SpMV kernels take them (choose_sweep)
-    int32_t *ii_list = nullptr, *ib_list = nullptr; // structured z-slab, K1 / K3 split: the interior launch's U tiles, the boundary launch's tiles
+    DevBuf<int32_t> vb_list, vi_list;
+    DevBuf<int32_t> us_list; // structured form: the U tiles in the order the z-marching SpMV kernels take them (choose_sweep)
+    DevBuf<int32_t> ii_list, ib_list; // structured z-slab, K1 / K3 split: the interior launch's U tiles, the boundary launch's tiles
     std::vector<int32_t> us_host; // host copy (visit-order export)
-    uint32_t *il_umask = nullptr;      // interleaved z-march of the structured form (Sweep::il_*): one bit per (column, plane)
+    DevBuf<uint32_t> il_umask;         // interleaved z-march of the structured form (Sweep::il_*): one bit per (column, plane)
     std::vector<uint32_t> il_umask_host;
-    int32_t *il_seg = nullptr;         // ... and its work list (four int32 per workgroup)
+    DevBuf<int32_t> il_seg;            // ... and its work list (four int32 per workgroup)
     std::vector<int32_t> il_seg_host;
     bool can_vsplit = false;
     int nown = 0;    // ownership ranges of an A-V slab (see Sweep)
     int64_t own_lo[4] = {0}, own_hi[4] = {0};
-    bool own_vectors = true;
     bool dist = false;
     // multi-rank (z-slab) mode: reductions come from the all-gathered per-rank sums
     int nranks = 1;
-    double *lsum = nullptr, *gsum = nullptr; // caller-owned device buffers (P_NSLOT, nranks*P_NSLOT)
+    // BORROWED: the caller's device buffers, never freed here and dropped with the matrix (ec3d_free_matrix)
+    double *lsum = nullptr, *gsum = nullptr; // (P_NSLOT, nranks*P_NSLOT)
     const double *const *lsum_ptrs = nullptr; // device array of nranks pointers: every rank's lsum (ec3d_multi.hip)
     int64_t halo = 0;                        // doubles per halo plane (kdz), 0 when not a slab
     bool use_dict = true;
@@ -380,18 +385,18 @@ struct ec3d_ctx {
     int64_t dev_cell(int64_t q) const { return pitch == plane ? q : (q / plane) * pitch + q % plane; }
     int64_t ref_cell(int64_t p) const { return pitch == plane ? p : (p / pitch) * plane + p % pitch; }
     int64_t planes() const { return pitch ? nCd / pitch : 0; } // xy planes per component block
-    double *io_tmp = nullptr; // sav: staging for the U part of host<->device vector copies
+    DevBuf<double> io_tmp; // sav: staging for the U part of host<->device vector copies
     int nblk_request = 0;
     int nt_request = -1; // -1 auto, 0/1 forced (EC3D_NT)
     int zm_request = 1;  // z-marching SpMV map when the grid allows it (EC3D_ZMARCH)
     int shuffle_request = 1; // +-1 neighbours by lane shuffle (EC3D_SHUFFLE)
-    double *partials = nullptr; // 8 * nblk doubles
-    SolverState *state = nullptr;
-    SolverState *state_pinned = nullptr; // 2 slots
-    double *hist = nullptr;
+    DevBuf<double> partials; // 8 * nblk doubles
+    DevBuf<SolverState> state;
+    PinnedBuf<SolverState> state_pinned; // 2 slots
+    DevBuf<double> hist;
     int64_t hist_cap = 0;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    hipEvent_t t0 = nullptr, t1 = nullptr;
+    Event ev[2];
+    Event t0, t1;
     // assembly by-products (1-based ids, reference order)
     std::vector<int32_t> cel_bnd[6];
     // grid of the last native assembly (0 when the matrix came from CSR)
@@ -403,25 +408,25 @@ struct ec3d_ctx {
     int n_cond_domains = 0;
     int64_t nu_siz_max = 0;        // max over conducting domains of the domain's cell count (PHYS_C%siznod)
     int u_rhs = 0;                 // EC3D_U_RHS_*: which U rows the RHS step gives their A-part (ec3d_set_u_rhs)
-    int32_t *cond_cell = nullptr;  // [n_cond] 0-based DEVICE cell index (dev_cell)
-    double *cond_a = nullptr;      // [n_cond] 2*C/dt of the cell's domain (PHYS_C%valdom)
-    int32_t *bnd_list = nullptr;   // the six cel_bnd* lists, 0-based unknown ids, concatenated
+    DevBuf<int32_t> cond_cell;     // [n_cond] 0-based DEVICE cell index (dev_cell)
+    DevBuf<double> cond_a;         // [n_cond] 2*C/dt of the cell's domain (PHYS_C%valdom)
+    DevBuf<int32_t> bnd_list;      // the six cel_bnd* lists, 0-based unknown ids, concatenated
     int64_t bnd_off[7] = {0};
-    double *rhs_tmp = nullptr;     // [3*n_cond] scratch for the moving-source reset
-    int32_t *src_idx = nullptr;    // per-step source scatter staging
-    double *src_val = nullptr;
+    DevBuf<double> rhs_tmp;        // [3*n_cond] scratch for the moving-source reset
+    DevBuf<int32_t> src_idx;       // per-step source scatter staging
+    DevBuf<double> src_val;
     int64_t src_cap = 0;
     // plain band streams whose placement was probed (place_bands): kept across a change of matrix of the same size, so
     // the probe runs once per handle and size, and what it found (candidate times in us, the one kept)
-    double *placed_bands = nullptr;
+    DevBuf<double> placed_bands;
     size_t placed_bytes = 0;
-    bool bands_placed = false;
+    bool bands_placed = false; // A.bands is an allocation the probe chose (or was taken back from placed_bands)
     std::vector<float> place_us;
     int place_kept = -1;
     // the work vectors' placement (place_vectors): doubles per vector the probe last ran for (0: never), the candidates'
     // iteration times, which one was kept, what the search cost
     int64_t vplace_len = 0;
-    double *parked_vec = nullptr, *parked_pp = nullptr; // the chosen allocation between two matrices (ec3d_free_matrix)
+    DevBuf<double> parked_vec, parked_pp; // the chosen allocation between two matrices (ec3d_free_matrix)
     int64_t parked_pp_len = 0;
     std::vector<float> vplace_us;
     int vplace_kept = -1;
@@ -429,12 +434,12 @@ struct ec3d_ctx {
     std::vector<uint64_t> src_seen; // host: one bit per A unknown, all zero between calls (repeat check of ec3d_rhs_step)
     // field output (ec3d_output.hip): device scratch for the four float32 vectors, the conductor mask, and -- for
     // output overlapped with the next time step -- a side stream with two pinned host buffers
-    float *out_dev = nullptr;
+    DevBuf<float> out_dev;
     int64_t out_cells = 0;
-    int32_t *out_mask = nullptr;
-    float *out_pinned[EC3D_OUT_SLOTS] = {nullptr, nullptr, nullptr};
-    hipStream_t out_stream = nullptr;
-    hipEvent_t out_ev_fields = nullptr, out_ev_free = nullptr, out_ev_copied[EC3D_OUT_SLOTS] = {nullptr, nullptr, nullptr};
+    DevBuf<int32_t> out_mask;
+    PinnedBuf<float> out_pinned[EC3D_OUT_SLOTS];
+    Stream out_stream;
+    Event out_ev_fields, out_ev_free, out_ev_copied[EC3D_OUT_SLOTS];
     int out_next = 0;
     bool out_busy = false;
     unsigned out_started = 0;  // bit i: slot i has had an ec3d_vtk_fields_begin (its event is worth waiting for)
@@ -444,6 +449,8 @@ struct ec3d_ctx {
     double poisson_bnd[6] = {0, 0, 0, 0, 0, 0}, poisson_delta[3] = {0, 0, 0};
     bool in_multi = false;
     ec3d_mg *mg = nullptr; // ec3d_set_preconditioner(EC3D_PRECOND_MG): solves run the preconditioned iteration
+    ec3d_ctx() = default;
+    ~ec3d_ctx(); // ec3d_context.hip: the hierarchy goes (ec3d_mg_free), then every owner above, last declared first
 };
 
 // partial-sum slots inside ctx->partials (each nblk doubles)
@@ -488,17 +495,6 @@ extern thread_local double *ec3d_itmax_print_hold;
         }                                                                                      \
     } while (0)
 
-// scratch device memory released at scope exit, error returns included
-template <class T> struct DevTmp {
-    T *p = nullptr;
-    DevTmp() = default;
-    DevTmp(const DevTmp &) = delete;
-    DevTmp &operator=(const DevTmp &) = delete;
-    ~DevTmp() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t count) { return hipMalloc(&p, count * sizeof(T)); }
-    operator T *() const { return p; }
-};
-
 // ec3d_format.cpp
 int ec3d_csr_to_host_matrix(int64_t n, const double *valA, const int32_t *irow, const int32_t *jcol,
                             HostMatrix &M);
@@ -530,8 +526,22 @@ int ec3d_upload_matrix(ec3d_ctx *c, const HostMatrix &M, int64_t halo = 0);
 int ec3d_download_matrix(ec3d_ctx *c, HostMatrix &M);
 void ec3d_free_matrix(ec3d_ctx *c);
 int ec3d_prepare_vectors(ec3d_ctx *c);
+// A matrix being built into the handle (behind ec3d_free_matrix): unless done(0) is reached -- on every early return --
+// ec3d_free_matrix runs again and the handle is left without a matrix and with none of the failed one's memory.  What a
+// placement search chose on this handle earlier is no part of the failed matrix and stays parked as after any
+// ec3d_free_matrix: band streams taken back from placed_bands, the placed vectors and rings.  The assembly entry points
+// call done(0) in front of ec3d_setup_rhs, so a failure there leaves the matrix in place, as it always did.
+struct MatrixBuild {
+    ec3d_ctx *c;
+    bool kept = false;
+    explicit MatrixBuild(ec3d_ctx *c_) : c(c_) {}
+    MatrixBuild(const MatrixBuild &) = delete;
+    MatrixBuild &operator=(const MatrixBuild &) = delete;
+    ~MatrixBuild() { if (!kept) ec3d_free_matrix(c); }
+    int done(int rc) { kept = rc == 0; return rc; }
+};
 // device memory for the plain band streams: the allocation a placement probe chose earlier, when the size fits
-int ec3d_alloc_bands(ec3d_ctx *c, double **bands, size_t bytes);
+int ec3d_alloc_bands(ec3d_ctx *c, DevBuf<double> &bands, size_t bytes);
 int ec3d_spare_pair(ec3d_ctx *c);
 // host vector (reference numbering, n_ref entries) <-> device vector (device numbering)
 int ec3d_vec_h2d(ec3d_ctx *c, double *dev, const double *host);

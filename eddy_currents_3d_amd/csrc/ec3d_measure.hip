@@ -92,12 +92,12 @@ extern "C" int ec3d_iterate(ec3d_handle c, int32_t first_iter, int32_t count, do
         return 0;
     }
     // per-kernel durations: an event at every kernel boundary of every iteration, on our stream
-    std::vector<hipEvent_t> ev((size_t)count * 6);
-    for (auto &e : ev) EC3D_HIP(hipEventCreate(&e));
+    std::vector<Event> ev((size_t)count * 6);
+    for (auto &e : ev) EC3D_HIP(e.create());
     hipStream_t s = c->stream;
     for (int i = 0; i < count; ++i) {
         const int it = first_iter + i;
-        hipEvent_t *e = &ev[(size_t)i * 6];
+        const Event *e = &ev[(size_t)i * 6];
         EC3D_HIP(hipEventRecord(e[0], s));
         for (int k = 1; k <= 5; ++k) {
             ec3d_launch_stage(c, A, it, k);
@@ -113,7 +113,6 @@ extern "C" int ec3d_iterate(ec3d_handle c, int32_t first_iter, int32_t count, do
             EC3D_HIP(hipEventElapsedTime(&ms, ev[(size_t)i * 6 + k], ev[(size_t)i * 6 + k + 1]));
             kernel_ms[k] += (double)ms / count;
         }
-    for (auto &e : ev) (void)hipEventDestroy(e);
     return 0;
 }
 

@@ -30,6 +30,7 @@
 #include <climits>
 #include <cmath>
 #include <cstring>
+#include <memory>
 
 #define EC3D_MG_COARSE_ROWS 4096 // x of the coarsest level in LDS (32 KiB), b and class bytes in registers
 #define EC3D_MG_COARSE_THREADS 1024
@@ -77,7 +78,7 @@ struct AvOp {
 struct AvLevel {
     AvOp op;
     int f[3] = {1, 1, 1};     // aggregate width towards the next level per axis (1 or 2)
-    double *bands = nullptr;  // coarse levels: owned
+    DevBuf<double> bands;     // coarse levels
     double *x = nullptr, *w = nullptr, *b = nullptr; // coarse levels: inside ec3d_mg::vec_base, 3 blocks each
 };
 
@@ -87,20 +88,20 @@ struct ec3d_mg {
     std::vector<MgLevel> lev;
     std::vector<AvLevel> av;    // EC3D_PRECOND_BLOCK_MG: the A blocks' hierarchy
     AvOp uop{};                 // ... and the U block's rows (class form, no hierarchy)
-    int32_t *ulist = nullptr;   // U-block rows that hold an unknown: the red ones, then the black ones
+    DevBuf<int32_t> ulist;      // U-block rows that hold an unknown: the red ones, then the black ones
     int64_t nu_red = 0, nu_black = 0;
     // Projection of the U right-hand side onto the range of the U block (one null vector per conducting component):
     // ucomp[e] = component of ulist[e]; plist = the U rows ordered by component, pw their weights; chunks = [lo, hi)
     // of each chunk of plist (within one component), cco = first chunk of each component; upart / umean / inv_w
     int32_t *ucomp = nullptr, *plist = nullptr, *chunks = nullptr, *cco = nullptr; // inside uidx
     double *pw = nullptr, *inv_w = nullptr, *upart = nullptr, *umean = nullptr;    // inside ubuf
-    int32_t *uidx = nullptr;
-    double *ubuf = nullptr;
+    DevBuf<int32_t> uidx;
+    DevBuf<double> ubuf;
     int ncomp = 0, nchunk = 0;
-    double *vec_base = nullptr; // coarse x, w, b per level, then the fine w, p^, s^
+    DevBuf<double> vec_base;    // coarse x, w, b per level, then the fine w, p^, s^
     double *w0 = nullptr, *ph = nullptr, *sh = nullptr;
-    double *part = nullptr;     // 2 * EC3D_MG_DOT_BLOCKS
-    MgScalars *scal = nullptr;
+    DevBuf<double> part;        // 2 * EC3D_MG_DOT_BLOCKS
+    DevBuf<MgScalars> scal;
 };
 
 namespace {
@@ -919,34 +920,6 @@ void launch_avcycle(ec3d_mg *m, Gate g, const double *r, double *z, hipStream_t 
     }
 }
 
-void free_level_matrix(DevMatrix &A)
-{
-    if (A.bands) (void)hipFree(A.bands);
-    if (A.tail_id) (void)hipFree(A.tail_id);
-    if (A.tile_flag) (void)hipFree(A.tile_flag);
-    if (A.chunk_ptr) (void)hipFree(A.chunk_ptr);
-    if (A.tcol) (void)hipFree(A.tcol);
-    if (A.tval) (void)hipFree(A.tval);
-    if (A.cls) (void)hipFree(A.cls);
-    if (A.table) (void)hipFree(A.table);
-    A = DevMatrix();
-}
-
-void free_mg(ec3d_mg *m)
-{
-    if (!m) return;
-    for (size_t l = 1; l < m->lev.size(); ++l) free_level_matrix(m->lev[l].A);
-    for (AvLevel &L : m->av)
-        if (L.bands) (void)hipFree(L.bands);
-    if (m->ulist) (void)hipFree(m->ulist);
-    if (m->uidx) (void)hipFree(m->uidx);
-    if (m->ubuf) (void)hipFree(m->ubuf);
-    if (m->vec_base) (void)hipFree(m->vec_base);
-    if (m->part) (void)hipFree(m->part);
-    if (m->scal) (void)hipFree(m->scal);
-    delete m;
-}
-
 } // namespace
 
 // ---- hierarchy rule (host) --------------------------------------------------------------------------------------------
@@ -1096,20 +1069,16 @@ static int set_block_mg(ec3d_ctx *c, int32_t pre, int32_t post, int32_t coarse_s
     const std::vector<std::array<int, 3>> dims = avmg_dims(sdx, sdy, sdz);
     const int L = (int)dims.size();
     // build the new hierarchy completely before the old one is replaced: a failure leaves the handle as it was
-    ec3d_mg *m = new ec3d_mg;
+    std::unique_ptr<ec3d_mg> m(new ec3d_mg);
     m->kind = EC3D_PRECOND_BLOCK_MG;
     m->pre = pre ? pre : 2;
     m->post = post ? post : 2;
     m->coarse = coarse_sweeps ? coarse_sweeps : 16;
     m->av.resize((size_t)L);
-    const auto fail = [&](int code) {
-        free_mg(m);
-        return code;
-    };
     const auto oom = [&](const char *what) {
         (void)hipGetLastError();
         ec3d_set_error(std::string("ec3d_set_preconditioner: ") + what);
-        return fail(100);
+        return 100;
     };
     AvOp &A0 = m->av[0].op;
     A0 = AvOp{};
@@ -1136,7 +1105,7 @@ static int set_block_mg(ec3d_ctx *c, int32_t pre, int32_t post, int32_t coarse_s
         o.n = o.kdz * o.sdz;
         o.n_pad = (o.n + 63) / 64 * 64;
         o.vs = o.n_pad;
-        if (hipMalloc(&Q.bands, (size_t)7 * o.n_pad * sizeof(double)) != hipSuccess)
+        if (Q.bands.alloc((size_t)7 * o.n_pad) != hipSuccess)
             return oom("out of device memory for the hierarchy");
         o.bands = Q.bands;
         coarse_len += 9 * o.n_pad;
@@ -1144,10 +1113,8 @@ static int set_block_mg(ec3d_ctx *c, int32_t pre, int32_t post, int32_t coarse_s
     // p^ and s^ are read by the format's SpMV, which may read the zero halo around a vector (ec3d_prepare_vectors)
     const int64_t nf = c->ghost + (A.n_pad + 63) / 64 * 64 + c->ghost;
     const int64_t total = coarse_len + 3 * nCd + 2 * nf;
-    if (hipMalloc(&m->vec_base, (size_t)total * sizeof(double)) != hipSuccess ||
-        hipMalloc(&m->part, 2 * EC3D_MG_DOT_BLOCKS * sizeof(double)) != hipSuccess ||
-        hipMalloc(&m->scal, sizeof(MgScalars)) != hipSuccess ||
-        hipMalloc(&m->ulist, std::max<size_t>(1, ured.size() + ublack.size()) * sizeof(int32_t)) != hipSuccess)
+    if (m->vec_base.alloc((size_t)total) != hipSuccess || m->part.alloc(2 * EC3D_MG_DOT_BLOCKS) != hipSuccess ||
+        m->scal.alloc(1) != hipSuccess || m->ulist.alloc(std::max<size_t>(1, ured.size() + ublack.size())) != hipSuccess)
         return oom("out of device memory for the hierarchy");
     m->nu_red = (int64_t)ured.size();
     m->nu_black = (int64_t)ublack.size();
@@ -1161,8 +1128,7 @@ static int set_block_mg(ec3d_ctx *c, int32_t pre, int32_t post, int32_t coarse_s
     m->nchunk = (int)(chunks.size() / 2);
     {
         const size_t nu = plist.size(), ni = 2 * nu + chunks.size() + cco.size(), nd = nu + 2 * inv_w.size() + chunks.size() / 2;
-        if (hipMalloc(&m->uidx, std::max<size_t>(1, ni) * sizeof(int32_t)) != hipSuccess ||
-            hipMalloc(&m->ubuf, std::max<size_t>(1, nd) * sizeof(double)) != hipSuccess)
+        if (m->uidx.alloc(std::max<size_t>(1, ni)) != hipSuccess || m->ubuf.alloc(std::max<size_t>(1, nd)) != hipSuccess)
             return oom("out of device memory for the hierarchy");
         m->ucomp = m->uidx;
         m->plist = m->ucomp + nu;
@@ -1204,10 +1170,10 @@ static int set_block_mg(ec3d_ctx *c, int32_t pre, int32_t post, int32_t coarse_s
     }
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
         ec3d_set_error("ec3d_set_preconditioner: building the hierarchy failed");
-        return fail(100);
+        return 100;
     }
     ec3d_mg_free(c);
-    c->mg = m;
+    c->mg = m.release();
     return 0;
 }
 
@@ -1242,7 +1208,7 @@ static void avmg_launch_iteration(ec3d_ctx *c, int it)
 
 void ec3d_mg_free(ec3d_ctx *c)
 {
-    free_mg(c->mg);
+    delete c->mg; // (its levels' matrices and every buffer of the hierarchy with it)
     c->mg = nullptr;
 }
 
@@ -1283,16 +1249,12 @@ extern "C" int ec3d_set_preconditioner(ec3d_handle c, int kind, int32_t pre, int
         return EC3D_PRECOND_E_MATRIX;
     }
     // build the new hierarchy completely before the old one is replaced: a failure leaves the handle as it was
-    ec3d_mg *m = new ec3d_mg;
+    std::unique_ptr<ec3d_mg> m(new ec3d_mg);
     m->pre = pre ? pre : 2;
     m->post = post ? post : 2;
     m->coarse = coarse_sweeps ? coarse_sweeps : 16;
     const int L = (int)dims.size();
     m->lev.resize((size_t)L);
-    const auto fail = [&](int code) {
-        free_mg(m);
-        return code;
-    };
     m->lev[0].op = op_of(c->A, c->sdx, c->sdy, c->sdz);
     for (int a = 0; a < 3; ++a) m->lev[0].delta[a] = c->poisson_delta[a];
     int64_t coarse_len = 0;
@@ -1304,23 +1266,22 @@ extern "C" int ec3d_set_preconditioner(ec3d_handle c, int kind, int32_t pre, int
         }
         rc = ec3d_assemble_poisson_level(c, Q.A, dims[(size_t)l][0], dims[(size_t)l][1], dims[(size_t)l][2],
                                          c->poisson_bnd, Q.delta);
-        if (rc) return fail(rc);
+        if (rc) return rc;
         Q.op = op_of(Q.A, dims[(size_t)l][0], dims[(size_t)l][1], dims[(size_t)l][2]);
         coarse_len += 3 * ((Q.op.n + 63) / 64 * 64);
     }
     const int64_t nf = (c->A.n + 63) / 64 * 64;
     const int64_t total = coarse_len + 3 * nf;
-    if (hipMalloc(&m->vec_base, (size_t)total * sizeof(double)) != hipSuccess ||
-        hipMalloc(&m->part, 2 * EC3D_MG_DOT_BLOCKS * sizeof(double)) != hipSuccess ||
-        hipMalloc(&m->scal, sizeof(MgScalars)) != hipSuccess) {
+    if (m->vec_base.alloc((size_t)total) != hipSuccess || m->part.alloc(2 * EC3D_MG_DOT_BLOCKS) != hipSuccess ||
+        m->scal.alloc(1) != hipSuccess) {
         (void)hipGetLastError();
         ec3d_set_error("ec3d_set_preconditioner: out of device memory for the hierarchy");
-        return fail(100);
+        return 100;
     }
     if (hipMemsetAsync(m->vec_base, 0, (size_t)total * sizeof(double), c->stream) != hipSuccess ||
         hipMemsetAsync(m->scal, 0, sizeof(MgScalars), c->stream) != hipSuccess) {
         ec3d_set_error("ec3d_set_preconditioner: hipMemsetAsync failed");
-        return fail(100);
+        return 100;
     }
     double *q = m->vec_base;
     for (int l = 1; l < L; ++l) {
@@ -1332,10 +1293,10 @@ extern "C" int ec3d_set_preconditioner(ec3d_handle c, int kind, int32_t pre, int
     m->w0 = q; m->ph = q + nf; m->sh = q + 2 * nf;
     if (hipStreamSynchronize(c->stream) != hipSuccess) {
         ec3d_set_error("ec3d_set_preconditioner: building the hierarchy failed");
-        return fail(100);
+        return 100;
     }
     ec3d_mg_free(c);
-    c->mg = m;
+    c->mg = m.release();
     return 0;
 }
 

@@ -110,16 +110,24 @@ const std::vector<Op> kIterFusedOverlap = {{OP_SKIP_IF_AP, 3}, ST(K1), {OP_GATHE
                                            {OP_GATHER, 0}};
 #undef ST
 
-struct Slab {
+// what a slab holds of its device besides its handle; release() lets go of all of it in the order of declaration, on the
+// slab's thread with that device set (ec3d_multi_destroy)
+struct SlabDevice {
+    Stream side;
+    Event ev_ready[NHALO][RING], ev_halo[NHALO][RING], ev_sum[RING], ev_hub[RING];
+    Event ev_stop[2];
+    PinnedBuf<int32_t> stop_pinned;
+    DevBuf<double> lsum;
+    DevBuf<const double *> ptr_table; // device: every rank's lsum
+    void release() { *this = SlabDevice(); }
+};
+
+struct Slab : SlabDevice {
     ec3d_ctx *c = nullptr;
     int rank = 0, device = 0;
     int32_t k0 = 0, k1 = 0, e0 = 0, e1 = 0; // owned planes [k0,k1), held planes [e0,e1)
-    double *lsum = nullptr;
     bool lsum_fine = false;
     uint64_t api_calls = 0, api_iters = 0; // runtime calls / iterations of the last ec3d_multi_iterate (this rank)
-    const double **ptr_table = nullptr; // device: every rank's lsum
-    hipStream_t side = nullptr;
-    hipEvent_t ev_ready[NHALO][RING] = {}, ev_halo[NHALO][RING] = {}, ev_sum[RING] = {}, ev_hub[RING] = {};
     uint64_t seq[NCH] = {0, 0, 0, 0, 0, 0, 0};
     std::atomic<uint64_t> posted[NCH];
     std::vector<Run> send_lo, recv_lo, send_hi, recv_hi; // towards rank-1 / rank+1, same order on both sides
@@ -130,8 +138,6 @@ struct Slab {
     int plan = 0; // 0 plain, 1 overlap (K1/K3 interior + boundary), 2 vsplit (K2/K5 boundary first), 3 three launches
                   // (kIterFused), 4 three launches with the producers of R and AP split around the exchange, 5 = 1 and 2
                   // together (kIterBoth)
-    int32_t *stop_pinned = nullptr;
-    hipEvent_t ev_stop[2] = {};
     // A-V slab: local reference order [Ax_ext | Ay_ext | Az_ext | U_ext] <-> the global vector
     int64_t nC_ext = 0, nU_ext = 0, n_local = 0;
     std::vector<int32_t> u_glob;        // global U index of every held U unknown
@@ -169,8 +175,8 @@ struct ec3d_multi {
     // every neighbour mapped to this process itself (send / recv to self) and the sums gathered over the one real rank.
     // Timing and call counts are those of the real rank; the numbers computed are not a solution of anything.
     bool rehearse = false;
-    double *gsum = nullptr;    // [world * P_NSLOT] the all-gathered sums
-    double *agbuf = nullptr;   // [(world + 1) * kFacts] set-up exchanges between the ranks
+    DevBuf<double> gsum;       // [world * P_NSLOT] the all-gathered sums
+    DevBuf<double> agbuf;      // [(world + 1) * kFacts] set-up exchanges between the ranks
     std::vector<std::unique_ptr<Slab>> slab;
     Pool pool;
     std::atomic<bool> abort{false};
@@ -508,7 +514,7 @@ int kernel_of_stage(int st)
 }
 
 struct StageTimer {
-    std::vector<hipEvent_t> ev; // pairs
+    std::vector<Event> ev;      // pairs
     std::vector<int> kern;      // 0 .. 4: the stage's kernel; T_GATHER / T_HALO_WAIT: a reduction point / a wait for halo planes
     bool sync_points = false;   // bracket the reduction points and the halo waits on the compute stream as well
 };
@@ -518,15 +524,15 @@ enum { T_GATHER = 5, T_HALO_WAIT = 6 };
 template <class F> int timed_sync(StageTimer *tm, Slab &s, int kind, F &&f)
 {
     if (!tm || !tm->sync_points) return f();
-    hipEvent_t a, b;
-    MHIP(hipEventCreate(&a));
-    MHIP(hipEventCreate(&b));
+    Event a, b;
+    MHIP(a.create());
+    MHIP(b.create());
     MHIP(hipEventRecord(a, s.c->stream));
     int rc = f();
     if (rc) return rc;
     MHIP(hipEventRecord(b, s.c->stream));
-    tm->ev.push_back(a);
-    tm->ev.push_back(b);
+    tm->ev.push_back(std::move(a));
+    tm->ev.push_back(std::move(b));
     tm->kern.push_back(kind);
     return 0;
 }
@@ -558,14 +564,14 @@ int run_plan(ec3d_multi *m, Slab &s, const std::vector<Op> &plan, int it, double
             const int k = tm ? kernel_of_stage(st) : -1;
             t_api_calls += (uint64_t)ec3d_dist_launches(s.c, st, it); // the kernel launches of the stage
             if (k >= 0) {
-                hipEvent_t a, b;
-                MHIP(hipEventCreate(&a));
-                MHIP(hipEventCreate(&b));
+                Event a, b;
+                MHIP(a.create());
+                MHIP(b.create());
                 MHIP(hipEventRecord(a, s.c->stream));
                 rc = ec3d_dist_step(s.c, st, it, tol);
                 MHIP(hipEventRecord(b, s.c->stream));
-                tm->ev.push_back(a);
-                tm->ev.push_back(b);
+                tm->ev.push_back(std::move(a));
+                tm->ev.push_back(std::move(b));
                 tm->kern.push_back(k);
             } else {
                 rc = ec3d_dist_step(s.c, st, it, tol);
@@ -637,37 +643,37 @@ int slab_reset(ec3d_multi *m, Slab &s)
         int rc = ec3d_create(&s.c, s.device);
         if (rc == 0) s.c->in_multi = true;
         if (rc) return rc;
-        MHIP(hipStreamCreateWithFlags(&s.side, hipStreamNonBlocking));
+        MHIP(s.side.create(hipStreamNonBlocking));
         for (int v = 0; v < NHALO; ++v)
             for (int i = 0; i < RING; ++i) {
-                MHIP(hipEventCreateWithFlags(&s.ev_ready[v][i], hipEventDisableTiming));
-                MHIP(hipEventCreateWithFlags(&s.ev_halo[v][i], hipEventDisableTiming));
+                MHIP(s.ev_ready[v][i].create(hipEventDisableTiming));
+                MHIP(s.ev_halo[v][i].create(hipEventDisableTiming));
             }
-        for (int i = 0; i < RING; ++i) MHIP(hipEventCreateWithFlags(&s.ev_sum[i], hipEventDisableTiming));
-        for (int i = 0; i < RING; ++i) MHIP(hipEventCreateWithFlags(&s.ev_hub[i], hipEventDisableTiming));
-        for (int i = 0; i < 2; ++i) MHIP(hipEventCreateWithFlags(&s.ev_stop[i], hipEventDisableTiming));
-        MHIP(hipHostMalloc(&s.stop_pinned, 2 * sizeof(int32_t), hipHostMallocDefault));
+        for (int i = 0; i < RING; ++i) MHIP(s.ev_sum[i].create(hipEventDisableTiming));
+        for (int i = 0; i < RING; ++i) MHIP(s.ev_hub[i].create(hipEventDisableTiming));
+        for (int i = 0; i < 2; ++i) MHIP(s.ev_stop[i].create(hipEventDisableTiming));
+        MHIP(s.stop_pinned.alloc(2));
         // The 8 sums every other GPU's kernels read in place, launch after launch: fine-grained (coherent across
         // devices) memory.  Peer access between all the devices involved was enabled BEFORE this allocation
         // (enable_peers, ec3d_multi_create).  Plain hipMalloc memory is only good enough when every slab sits
         // on this same device (rehearsals on a one-GPU box); across devices there is no silent fallback.
         bool several_devices = false;
         for (auto &o : m->slab) several_devices |= o->device != s.device;
-        if (hipExtMallocWithFlags((void **)&s.lsum, P_NSLOT * sizeof(double), hipDeviceMallocFinegrained) == hipSuccess) {
+        if (s.lsum.alloc_fine(P_NSLOT) == hipSuccess) {
             s.lsum_fine = true;
         } else {
             (void)hipGetLastError();
             if (several_devices) {
                 ec3d_set_error("ec3d_multi: device " + std::to_string(s.device) + " cannot allocate fine-grained memory "
-                               "(hipExtMallocWithFlags, hipDeviceMallocFinegrained) for the partial sums the other GPUs "
+                               "(hipDeviceMallocFinegrained) for the partial sums the other GPUs "
                                "read in place; coarse-grained memory is not coherent across devices -- refusing to run "
                                "on several devices without it");
                 return 107;
             }
-            MHIP(hipMalloc(&s.lsum, P_NSLOT * sizeof(double)));
+            MHIP(s.lsum.alloc(P_NSLOT));
         }
         MHIP(hipMemset(s.lsum, 0, P_NSLOT * sizeof(double)));
-        MHIP(hipMalloc(&s.ptr_table, (size_t)m->n * sizeof(double *)));
+        MHIP(s.ptr_table.alloc((size_t)m->n));
     }
     s.send_lo.clear(); s.recv_lo.clear(); s.send_hi.clear(); s.recv_hi.clear();
     s.pull_lo.clear(); s.pull_hi.clear();
@@ -741,9 +747,9 @@ int finish_setup(ec3d_multi *m)
         const ec3d_ctx *c = sl.c;
         auto total = [](const std::vector<Run> &rs) { double t = 0; for (const Run &r : rs) t += (double)r.payload * r.planes; return t; };
         RankFacts f{};
-        f.fused_ok = (c->fuse23_ok && c->fuse51_ok && c->k4s_ok && c->pp_base && c->own_vectors) ? 1.0 : 0.0;
-        f.xd = (c->pp_base && c->own_vectors) ? (double)c->xdefer : 1.0;
-        f.xasync = (c->pp_base && c->own_vectors && c->xasync_cap) ? 1.0 : 0.0;
+        f.fused_ok = (c->fuse23_ok && c->fuse51_ok && c->k4s_ok && c->pp_base && c->own_vectors()) ? 1.0 : 0.0;
+        f.xd = (c->pp_base && c->own_vectors()) ? (double)c->xdefer : 1.0;
+        f.xasync = (c->pp_base && c->own_vectors() && c->xasync_cap) ? 1.0 : 0.0;
         // (an A-V slab splits K2 / K5 by tile lists made from its halo runs: always possible where there is a neighbour)
         f.both_splits = (c->have_matrix && c->can_overlap && (c->A.sav || ec3d_dist_can_split_planes(c))) ? 1.0 : 0.0;
         f.sav = c->A.sav ? 1.0 : 0.0;
@@ -845,7 +851,7 @@ int finish_setup(ec3d_multi *m)
         c->nranks = m->nccl ? m->comm_world : m->world;
         c->lsum = s.lsum;
         c->gsum = m->nccl ? m->gsum : nullptr;          // one process per GPU: the all-gathered copy
-        c->lsum_ptrs = m->nccl ? nullptr : s.ptr_table; // one process: every rank's sums read in place
+        c->lsum_ptrs = m->nccl ? nullptr : s.ptr_table.get(); // one process: every rank's sums read in place
         c->slab_fused = fused;
         c->slab_xd = xd;
         // (three-launch slabs keep the applying K4: measured, the second launch costs them more than it fills)
@@ -1191,9 +1197,9 @@ extern "C" int ec3d_multi_create_rank(ec3d_multi_handle *mh, int32_t rank, int32
         // all-gathers of the sums -- runs the interior launch; every rank issues the calls of each in the same order
         MNCCL(m, api->CommInitRank(&m->comm_halo, nranks, ih, rank));
         MNCCL(m, api->CommInitRank(&m->comm_sum, nranks, is, rank));
-        MHIP(hipMalloc(&m->gsum, (size_t)nranks * P_NSLOT * sizeof(double)));
+        MHIP(m->gsum.alloc((size_t)nranks * P_NSLOT));
         MHIP(hipMemset(m->gsum, 0, (size_t)nranks * P_NSLOT * sizeof(double)));
-        MHIP(hipMalloc(&m->agbuf, (size_t)(nranks + 1) * kFacts * sizeof(double)));
+        MHIP(m->agbuf.alloc((size_t)(nranks + 1) * kFacts));
         return 0;
     });
     if (rc) {
@@ -1215,26 +1221,12 @@ extern "C" int ec3d_multi_destroy(ec3d_multi_handle m)
         (void)hipDeviceSynchronize();
         if (s.c) (void)ec3d_destroy(s.c);
         s.c = nullptr;
-        if (s.side) (void)hipStreamDestroy(s.side);
-        for (int v = 0; v < NHALO; ++v)
-            for (int i = 0; i < RING; ++i) {
-                if (s.ev_ready[v][i]) (void)hipEventDestroy(s.ev_ready[v][i]);
-                if (s.ev_halo[v][i]) (void)hipEventDestroy(s.ev_halo[v][i]);
-            }
-        for (int i = 0; i < RING; ++i) {
-            if (s.ev_sum[i]) (void)hipEventDestroy(s.ev_sum[i]);
-            if (s.ev_hub[i]) (void)hipEventDestroy(s.ev_hub[i]);
-        }
-        for (int i = 0; i < 2; ++i)
-            if (s.ev_stop[i]) (void)hipEventDestroy(s.ev_stop[i]);
-        if (s.stop_pinned) (void)hipHostFree(s.stop_pinned);
-        if (s.lsum) (void)hipFree(s.lsum);
-        if (s.ptr_table) (void)hipFree(s.ptr_table);
+        s.release(); // its side stream, events and buffers
         if (m->nccl) {
             if (m->comm_halo) (void)m->nccl->CommDestroy(m->comm_halo);
             if (m->comm_sum) (void)m->nccl->CommDestroy(m->comm_sum);
-            if (m->gsum) (void)hipFree(m->gsum);
-            if (m->agbuf) (void)hipFree(m->agbuf);
+            m->gsum.reset();
+            m->agbuf.reset();
         }
         return 0;
     });
@@ -1778,7 +1770,6 @@ int multi_iterate(ec3d_multi *m, int32_t first_iter, int32_t count, int timed_ra
             }
             if (sync_n)
                 for (int q = 0; q < 2; ++q) sync_n[q] /= std::max(1, count);
-            for (hipEvent_t e : tm.ev) (void)hipEventDestroy(e);
         }
         return 0;
     }, true);

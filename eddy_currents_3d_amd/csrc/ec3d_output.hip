@@ -86,10 +86,10 @@ int output_prepare(ec3d_ctx *c, bool pinned)
     if (rc) return rc;
     EC3D_HIP(hipSetDevice(c->device));
     if (!c->out_dev) {
-        EC3D_HIP(hipMalloc(&c->out_dev, (size_t)12 * nOwn * sizeof(float)));
+        EC3D_HIP(c->out_dev.alloc((size_t)12 * nOwn));
         c->out_cells = nOwn;
         if (c->n_cond > 0) { // conductor mask per held cell, from the scan-order cell list kept for the RHS build
-            EC3D_HIP(hipMalloc(&c->out_mask, (size_t)c->n_cells * 4));
+            EC3D_HIP(c->out_mask.alloc((size_t)c->n_cells));
             EC3D_HIP(hipMemsetAsync(c->out_mask, 0, (size_t)c->n_cells * 4, c->stream));
             const int64_t plane = c->pitch ? c->plane : 1, pitch = c->pitch ? c->pitch : 1;
             k_mask_from_cells<<<(unsigned)((c->n_cond + 255) / 256), 256, 0, c->stream>>>(c->out_mask, c->cond_cell,
@@ -98,12 +98,12 @@ int output_prepare(ec3d_ctx *c, bool pinned)
         }
     }
     if (pinned && !c->out_stream) {
-        EC3D_HIP(hipStreamCreateWithFlags(&c->out_stream, hipStreamNonBlocking));
-        EC3D_HIP(hipEventCreateWithFlags(&c->out_ev_fields, hipEventDisableTiming));
-        EC3D_HIP(hipEventCreateWithFlags(&c->out_ev_free, hipEventDisableTiming));
+        EC3D_HIP(c->out_stream.create(hipStreamNonBlocking));
+        EC3D_HIP(c->out_ev_fields.create(hipEventDisableTiming));
+        EC3D_HIP(c->out_ev_free.create(hipEventDisableTiming));
         for (int i = 0; i < EC3D_OUT_SLOTS; ++i) {
-            EC3D_HIP(hipEventCreateWithFlags(&c->out_ev_copied[i], hipEventDisableTiming));
-            EC3D_HIP(hipHostMalloc(&c->out_pinned[i], (size_t)12 * nOwn * sizeof(float), hipHostMallocDefault));
+            EC3D_HIP(c->out_ev_copied[i].create(hipEventDisableTiming));
+            EC3D_HIP(c->out_pinned[i].alloc((size_t)12 * nOwn));
         }
     }
     return 0;
@@ -132,22 +132,16 @@ int output_launch(ec3d_ctx *c, const double *delta, bool big_endian)
 void ec3d_free_output(ec3d_ctx *c)
 {
     if (c->out_stream) (void)hipStreamSynchronize(c->out_stream);
-    if (c->out_dev) (void)hipFree(c->out_dev);
-    if (c->out_mask) (void)hipFree(c->out_mask);
-    c->out_dev = nullptr;
-    c->out_mask = nullptr;
+    c->out_dev.reset();
+    c->out_mask.reset();
     c->out_cells = 0;
     for (int i = 0; i < EC3D_OUT_SLOTS; ++i) {
-        if (c->out_pinned[i]) (void)hipHostFree(c->out_pinned[i]);
-        c->out_pinned[i] = nullptr;
-        if (c->out_ev_copied[i]) (void)hipEventDestroy(c->out_ev_copied[i]);
-        c->out_ev_copied[i] = nullptr;
+        c->out_pinned[i].reset();
+        c->out_ev_copied[i].reset();
     }
-    if (c->out_ev_fields) (void)hipEventDestroy(c->out_ev_fields);
-    if (c->out_ev_free) (void)hipEventDestroy(c->out_ev_free);
-    if (c->out_stream) (void)hipStreamDestroy(c->out_stream);
-    c->out_ev_fields = c->out_ev_free = nullptr;
-    c->out_stream = nullptr;
+    c->out_ev_fields.reset();
+    c->out_ev_free.reset();
+    c->out_stream.reset();
     c->out_next = 0;
     c->out_busy = false;
     c->out_started = 0;

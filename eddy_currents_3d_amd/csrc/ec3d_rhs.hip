@@ -105,14 +105,12 @@ inline unsigned blocks(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + 2
 
 void ec3d_free_rhs(ec3d_ctx *c)
 {
-    if (c->cond_cell) (void)hipFree(c->cond_cell);
-    if (c->cond_a) (void)hipFree(c->cond_a);
-    if (c->bnd_list) (void)hipFree(c->bnd_list);
-    if (c->rhs_tmp) (void)hipFree(c->rhs_tmp);
-    if (c->src_idx) (void)hipFree(c->src_idx);
-    if (c->src_val) (void)hipFree(c->src_val);
-    c->cond_cell = nullptr; c->cond_a = nullptr; c->bnd_list = nullptr; c->rhs_tmp = nullptr;
-    c->src_idx = nullptr; c->src_val = nullptr;
+    c->cond_cell.reset();
+    c->cond_a.reset();
+    c->bnd_list.reset();
+    c->rhs_tmp.reset();
+    c->src_idx.reset();
+    c->src_val.reset();
     c->n_cond = 0; c->n_cond_domains = 0; c->nu_siz_max = 0; c->src_cap = 0;
     for (auto &o : c->bnd_off) o = 0;
 }
@@ -148,10 +146,10 @@ int ec3d_setup_rhs(ec3d_ctx *c, int64_t nCells, const int8_t *geoPHYS, const int
     }
     c->bnd_off[6] = (int64_t)lists.size();
     if (c->n_cond == 0) return 0;
-    EC3D_HIP(hipMalloc(&c->cond_cell, cell.size() * 4));
-    EC3D_HIP(hipMalloc(&c->cond_a, a.size() * 8));
-    EC3D_HIP(hipMalloc(&c->rhs_tmp, (size_t)3 * cell.size() * 8));
-    EC3D_HIP(hipMalloc(&c->bnd_list, std::max<size_t>(lists.size(), 1) * 4));
+    EC3D_HIP(c->cond_cell.alloc(cell.size()));
+    EC3D_HIP(c->cond_a.alloc(a.size()));
+    EC3D_HIP(c->rhs_tmp.alloc((size_t)3 * cell.size()));
+    EC3D_HIP(c->bnd_list.alloc(std::max<size_t>(lists.size(), 1)));
     EC3D_HIP(hipMemcpyAsync(c->cond_cell, cell.data(), cell.size() * 4, hipMemcpyHostToDevice, c->stream));
     EC3D_HIP(hipMemcpyAsync(c->cond_a, a.data(), a.size() * 8, hipMemcpyHostToDevice, c->stream));
     if (!lists.empty())
@@ -229,11 +227,11 @@ extern "C" int ec3d_rhs_step(ec3d_handle c, int32_t moving, int32_t nsrc, const 
         }
         const int64_t ns = (int64_t)idx.size();
         if (ns > c->src_cap) {
-            if (c->src_idx) (void)hipFree(c->src_idx);
-            if (c->src_val) (void)hipFree(c->src_val);
+            c->src_idx.reset();
+            c->src_val.reset();
             c->src_cap = ns * 2;
-            EC3D_HIP(hipMalloc(&c->src_idx, (size_t)c->src_cap * 4));
-            EC3D_HIP(hipMalloc(&c->src_val, (size_t)c->src_cap * 8));
+            EC3D_HIP(c->src_idx.alloc((size_t)c->src_cap));
+            EC3D_HIP(c->src_val.alloc((size_t)c->src_cap));
         }
         EC3D_HIP(hipMemcpyAsync(c->src_idx, idx.data(), (size_t)ns * 4, hipMemcpyHostToDevice, s));
         EC3D_HIP(hipMemcpyAsync(c->src_val, val.data(), (size_t)ns * 8, hipMemcpyHostToDevice, s));

@@ -259,9 +259,7 @@ static int ensure_hist(ec3d_ctx *c, int64_t cap)
         c->hist_cap = 0;
         return 0;
     }
-    if (c->hist) (void)hipFree(c->hist);
-    c->hist = nullptr;
-    EC3D_HIP(hipMalloc(&c->hist, (size_t)cap * 2 * sizeof(double)));
+    EC3D_HIP(c->hist.alloc((size_t)cap * 2));
     EC3D_HIP(hipMemsetAsync(c->hist, 0xFF, (size_t)cap * 2 * sizeof(double), c->stream)); // NaN = "not reached"
     c->hist_cap = cap;
     return 0;

@@ -450,7 +450,8 @@ int ec3d_get_vector_placement(ec3d_handle h, int32_t cap, double *candidate_us, 
                               double *search_ms);
 /* The same search on request: at any size, with `candidates` allocations (>= 2), on a handle that has a matrix, owns its
  * vectors and is no z-slab (4 otherwise).  EVERY work vector is zero afterwards (X, B and the warm start included): call it
- * before uploading anything. */
+ * before uploading anything.  The vectors may live in another allocation afterwards: every pointer ec3d_device_vector
+ * returned before this call is invalid, ask again. */
 int ec3d_place_vectors(ec3d_handle h, int32_t candidates);
 
 /* Host-only check (no GPU needed, no handle): would ec3d_set_matrix_csr / sprsbcgstabwr_ store this

@@ -271,3 +271,59 @@ def test_vector_placement_search_leaves_no_trace_and_is_kept(E):
         assert 2 <= len(us) <= 6 and 0 <= kept < len(us) and us[kept] == min(us) and ms < 20000   # (a hipMalloc now and then takes seconds on a box that has just released memory)
         x, it, h = s.solve(b, np.zeros(n), 1e-30, 9, hist_cap=16)
         assert it == it_ref == 10 and np.array_equal(x, x_ref) and np.array_equal(h, h_ref, equal_nan=True)
+
+
+def test_a_handles_life_returns_its_memory(E):
+    """Everything a handle takes from the device -- matrix, work vectors and rings, the tables of the RHS step, the
+    field output's device and pinned buffers with their stream and events, both multigrid hierarchies -- has one owner
+    inside the handle, so a handle's life leaves nothing behind.  Six lives in one process, each: create, assemble a
+    structured A-V model (128^3 cells: 8.4 M device rows, 64 MiB per work vector), attach the block multigrid, an RHS
+    step, a short solve, the post-update and both kinds of field output, replace the matrix by a single-component one of
+    another size with the plain multigrid, solve, destroy.  The device's free memory after the last life equals what
+    it was after the second (the first two pay whatever the runtime keeps for the process) to within ONE work vector,
+    8 n_pad bytes: the smallest allocation whose loss this test is meant to catch -- a bound derived from what is
+    looked for, not measured.  Two readings seconds apart, never an absolute figure: the device is shared."""
+    import torch
+    from eddy_currents_3d_amd import host, vxc
+    g4 = load_golden("g4_ec_src_move_hole")
+    small = vxc.VxcModel(g4["vox"], [str(s) for s in g4["names"]], float(str(g4["lattice_dim"])),
+                         tuple(float(x) for x in g4["adj"]))
+    N = 128
+    model = vxc.resample(small, N, N, N)
+    t = vxc.domain_tables(model)
+    idx, val, moving = host.SourceProgram(model, t).step(0.0)
+    conducting = t["ncells0"] > 0
+    assert conducting
+    pn = (96, 96, 64)
+    b = np.random.Generator(np.random.PCG64(5)).standard_normal(pn[0] * pn[1] * pn[2])
+    lives, first, free, vec_bytes = 6, 2, {}, 0
+    for life in range(1, lives + 1):
+        s = E.EC3DSolver()
+        try:
+            s.assemble(t["geoPHYS"], t["geoPHYS_C"], t["valPHYS"], t["BND"], t["delta"], t["dt"])
+            vec_bytes = 8 * s.vector_layout()["n_pad"]
+            assert vec_bytes >= 64 << 20
+            s.set_preconditioner("block-mg")                 # (only the structured form takes it)
+            assert s.preconditioner()[0] == "block-mg"
+            s.upload("X", np.zeros(s.n))
+            s.upload("B", np.zeros(s.n))
+            s.rhs_step(idx, val, moving=moving)
+            it, _ = s.solve_resident(t["tol"], 3)
+            assert it >= 1
+            s.post_update()
+            f = s.vtk_fields(t["delta"], N ** 3, conducting)
+            assert np.isfinite(f["B"]).all()
+            s.vtk_fields_wait(s.vtk_fields_begin(t["delta"]))
+            s.assemble_poisson(*pn)
+            s.set_preconditioner("mg")
+            assert s.preconditioner()[0] == "mg"
+            _, it, _ = s.solve(b, np.zeros(b.size), 1e-8, 5)
+            assert it >= 1
+        finally:
+            s.close()
+        if life in (first, lives):
+            torch.cuda.synchronize()
+            free[life] = torch.cuda.mem_get_info()[0]
+    print(f"free after life {first}: {free[first]}, after life {lives}: {free[lives]}, difference "
+          f"{free[first] - free[lives]} bytes; one work vector: {vec_bytes} bytes")
+    assert abs(free[first] - free[lives]) < vec_bytes
