@@ -37,7 +37,10 @@ int ec3d_csr_to_host_matrix(int64_t n, const double *valA, const int32_t *irow, 
         std::vector<std::pair<int64_t, int64_t>> cand; // (count, offset)
         for (auto &kv : cnt)
             if (kv.second * 10 >= rows * 4) cand.push_back({kv.second, kv.first});
-        std::sort(cand.begin(), cand.end(), [](auto &a, auto &b) { return a.first > b.first; });
+        // the EC3D_MAXB most frequent; equal counts in favour of the smaller offset, so that the cut does not depend on
+        // the order the hash map hands the candidates out in
+        std::sort(cand.begin(), cand.end(),
+                  [](auto &a, auto &b) { return a.first != b.first ? a.first > b.first : a.second < b.second; });
         if (cand.size() > EC3D_MAXB) cand.resize(EC3D_MAXB);
         M.nb = (int)cand.size();
         std::vector<int64_t> offs;

@@ -48,7 +48,13 @@ const char *ec3d_last_error(void);
  * Converted once on the host to a device format: the structured A-V form (1 class byte per row, U
  * embedded in the grid) when the matrix is recognised, entry by entry, as the one gen_sparse_matrix
  * builds (see ec3d_probe_csr); otherwise 7 bands (class-coded or plain) + a sliced-ELL tail that keeps
- * every row's stored order.  Results do not depend on the format. */
+ * every row's stored order.  Results do not depend on the format.
+ * Bands: the offsets that >= 40 % of a row sample carry, at most 16 (the most frequent; equal counts in favour of
+ * the smaller offset).  Seven bands at (-kdz, -sdx, -1, 0, 1, sdx, kdz) with kdz a whole number of 512-row tiles get
+ * the z-marching and 2-D-tile kernels on the evidence of the offsets alone: the values are not looked at and need
+ * not be a grid operator's.  A nonzero coefficient in a wrap slot (+-1 at the end of an x-row, +-sdx at the end of a
+ * plane) multiplies the LINEAR neighbour x[r +- 1], x[r +- sdx] in every kernel form, as the CSR row says
+ * (tests/test_gpu_generated_csr.py). */
 int ec3d_set_matrix_csr(ec3d_handle h, int32_t n, const double *valA, const int32_t *irow,
                         const int32_t *jcol);
 
@@ -324,7 +330,9 @@ int ec3d_multi_assemble(ec3d_multi_handle mh, int32_t sdx, int32_t sdy, int32_t 
 /* CSR triple of the whole system (src/EC3D.f90:36-38): must be recognisable as the reference's A-V system
  * on a grid (ec3d_probe_csr) or as a single-component 7-point operator on one (seven bands at -kdz, -sdx, -1, 0,
  * 1, sdx, kdz and nothing else: src/EC3D.f90:528-654 without conducting cells), which is then cut into slabs;
- * status 7 otherwise (use one GPU) */
+ * status 7 otherwise (use one GPU).  The seven-band reading goes by the offsets, not the values: wrap slots may hold
+ * nonzero coefficients, they multiply the linear neighbour as on one GPU (a slab's ghost zone is a whole plane, which
+ * covers x[r +- 1] and x[r +- sdx] of its first and last rows) */
 int ec3d_multi_set_matrix_csr(ec3d_multi_handle mh, int32_t n, const double *valA, const int32_t *irow,
                               const int32_t *jcol);
 /* host vectors in the reference's global numbering [Ax | Ay | Az | U], n unknowns (ec3d_multi_size) */
