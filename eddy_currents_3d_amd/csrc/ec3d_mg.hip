@@ -17,6 +17,11 @@
 // runs in place; the prolongation reads w and writes x (another buffer), because its black rows read red neighbours
 // the same launch corrects.
 //
+// EC3D_PRECOND_FP32 (ec3d_set_precond_precision): the same cycle with every level's coefficients narrowed once at set-up,
+// the right-hand side narrowed once per application and every vector and operation of the cycle in fp32 -- the kernels
+// above instantiated with T = float; p^ and s^ are then fp32 vectors the outer kernels widen on load, and the outer
+// iteration stays fp64 (tests/mg_numpy_f32.py restates it).
+//
 // EC3D_PRECOND_BLOCK_MG (the structured A-V form) shares the outer iteration's vector kernels;
 // its own kernels (k_avmg_*) are below, behind the single-component ones.
 //
@@ -37,14 +42,17 @@
 #define EC3D_MG_MAXCLS 32        // dictionary classes a level may have (the single-component operator has 28)
 #define EC3D_MG_DOT_BLOCKS 2048  // workgroups of the reducing kernels (grid-stride)
 
-struct MgOp {
+// T: the precision of the level's coefficients and vectors (double; float for the fp32 V-cycle, EC3D_PRECOND_FP32)
+template <class T> struct MgOpT {
     int sdx, sdy, sdz;
     int64_t n, n_pad, kdz;
     const uint8_t *cls;   // dictionary form: coefficient q of row r = table[cls[r] * 7 + q]
-    const double *table;
+    const T *table;
     int ncls;
-    const double *bands;  // band form (cls == nullptr): bands[q * n_pad + r]
+    const T *bands;       // band form (cls == nullptr): bands[q * n_pad + r]
 };
+using MgOp = MgOpT<double>;
+using MgOp32 = MgOpT<float>;
 
 struct MgLevel {
     DevMatrix A;          // level 0: unused (the handle's matrix)
@@ -52,6 +60,14 @@ struct MgLevel {
     int f[3] = {1, 1, 1}; // coarsening factor towards the next level per axis (1 or 2)
     double delta[3] = {0, 0, 0};
     double *x = nullptr, *w = nullptr, *b = nullptr; // coarse levels: inside ec3d_mg::vec_base
+    // EC3D_PRECOND_FP32: then only level 0's fp64 operator above is still read (by the outer SpMV + dot launch, from the
+    // handle's matrix); a coarse level's A keeps owning its class bytes, which op32 shares, and its fp64 class table
+    // (7 doubles per class, a few hundred bytes) stays allocated unread -- coarse levels are always in dictionary form, so
+    // no fp64 band stream is kept beside an fp32 one.  The level's coefficients narrowed once (the table, or level 0's seven band streams under
+    // ec3d_set_format(h, 0)) and its vectors, inside ec3d_mg::vec32; x, w, b above stay null
+    MgOp32 op32{};
+    DevBuf<float> coef32;
+    float *x32 = nullptr, *w32 = nullptr, *b32 = nullptr;
 };
 
 struct MgScalars {
@@ -100,6 +116,9 @@ struct ec3d_mg {
     int ncomp = 0, nchunk = 0;
     DevBuf<double> vec_base;    // coarse x, w, b per level, then the fine w, p^, s^
     double *w0 = nullptr, *ph = nullptr, *sh = nullptr;
+    int precision = EC3D_PRECOND_FP64; // EC3D_PRECOND_FP32 (kind EC3D_PRECOND_MG only): vec_base stays empty, and
+    DevBuf<float> vec32;        // coarse x, w, b per level, then the fine w, the fine right-hand side's copy, p^, s^
+    float *w0_32 = nullptr, *b0_32 = nullptr, *ph32 = nullptr, *sh32 = nullptr;
     DevBuf<double> part;        // 2 * EC3D_MG_DOT_BLOCKS
     DevBuf<MgScalars> scal;
 };
@@ -125,16 +144,17 @@ __device__ __forceinline__ void mg_stop_publish(SolverState *st, int it, int kin
                        __HIP_MEMORY_SCOPE_AGENT);
 }
 
-__device__ __forceinline__ void load_table(const MgOp &A, double *tbl)
+template <class T> __device__ __forceinline__ void load_table(const MgOpT<T> &A, T *tbl)
 {
     if (!A.cls) return;
     for (int q = threadIdx.x; q < A.ncls * 7; q += blockDim.x) tbl[q] = A.table[q];
     __syncthreads();
 }
-template <bool DICT> __device__ __forceinline__ void row_coefs(const MgOp &A, const double *tbl, int64_t r, double (&c)[7])
+template <bool DICT, class T>
+__device__ __forceinline__ void row_coefs(const MgOpT<T> &A, const T *tbl, int64_t r, T (&c)[7])
 {
     if constexpr (DICT) {
-        const double *t = tbl + 7 * (int)A.cls[r];
+        const T *t = tbl + 7 * (int)A.cls[r];
 #pragma unroll
         for (int q = 0; q < 7; ++q) c[q] = t[q];
     } else {
@@ -152,20 +172,20 @@ template <class OP> __device__ __forceinline__ Pos pos_of(const OP &A, int64_t r
     return Pos{(int)(ij % sx), (int)(ij / sx), (int)(ur / (unsigned)A.kdz)};
 }
 // x at the six neighbours in offset order (-z, -y, -x, +x, +y, +z); 0 beyond the box
-template <class OP, class LD>
-__device__ __forceinline__ void neighbours(const OP &A, const Pos &p, int64_t r, LD ld, double (&v)[6])
+template <class OP, class LD, class T>
+__device__ __forceinline__ void neighbours(const OP &A, const Pos &p, int64_t r, LD ld, T (&v)[6])
 {
-    v[0] = p.k > 0 ? ld(r - A.kdz) : 0.0;
-    v[1] = p.j > 0 ? ld(r - A.sdx) : 0.0;
-    v[2] = p.i > 0 ? ld(r - 1) : 0.0;
-    v[3] = p.i + 1 < A.sdx ? ld(r + 1) : 0.0;
-    v[4] = p.j + 1 < A.sdy ? ld(r + A.sdx) : 0.0;
-    v[5] = p.k + 1 < A.sdz ? ld(r + A.kdz) : 0.0;
+    v[0] = p.k > 0 ? ld(r - A.kdz) : T(0);
+    v[1] = p.j > 0 ? ld(r - A.sdx) : T(0);
+    v[2] = p.i > 0 ? ld(r - 1) : T(0);
+    v[3] = p.i + 1 < A.sdx ? ld(r + 1) : T(0);
+    v[4] = p.j + 1 < A.sdy ? ld(r + A.sdx) : T(0);
+    v[5] = p.k + 1 < A.sdz ? ld(r + A.kdz) : T(0);
 }
 // Gauss-Seidel value of a row: (b - sum of the off-diagonal terms in offset order) / d
-__device__ __forceinline__ double gs_value(const double (&c)[7], const double (&v)[6], double b)
+template <class T> __device__ __forceinline__ T gs_value(const T (&c)[7], const T (&v)[6], T b)
 {
-    double t = b;
+    T t = b;
     t = t - c[0] * v[0];
     t = t - c[1] * v[1];
     t = t - c[2] * v[2];
@@ -178,11 +198,12 @@ __device__ __forceinline__ double gs_value(const double (&c)[7], const double (&
 // Half-sweep of one colour on level A, in place.  init: the first half from x = 0 -- x = b / d on the colour, 0 on
 // the other (b - 0 terms == b).  Bytes per row (fine level, dictionary form): b 8 (the other colour's entries share
 // its lines) + x 8 read (neighbours from L2 / L1) + x 8 written + 1 class byte = 25 B; init: b 8 + x 8 written + 1 = 17 B.
-template <bool DICT>
-__global__ __launch_bounds__(256) void k_mg_smooth(MgOp A, Gate g, int colour, int init, double *__restrict__ x,
-                                                   const double *__restrict__ b)
+// With T = float (13 B, init 9 B on a coarse level): the same operations in fp32.
+template <bool DICT, class T = double>
+__global__ __launch_bounds__(256) void k_mg_smooth(MgOpT<T> A, Gate g, int colour, int init, T *__restrict__ x,
+                                                   const T *__restrict__ b)
 {
-    __shared__ double tbl[EC3D_MG_MAXCLS * 7];
+    __shared__ T tbl[EC3D_MG_MAXCLS * 7];
     if (gated_off(g)) return;
     if (DICT) load_table(A, tbl);
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -190,44 +211,69 @@ __global__ __launch_bounds__(256) void k_mg_smooth(MgOp A, Gate g, int colour, i
     const Pos p = pos_of(A, r);
     const bool mine = ((p.i + p.j + p.k) & 1) == colour;
     if (!mine) {
-        if (init) x[r] = 0.0;
+        if (init) x[r] = T(0);
         return;
     }
-    double c[7];
+    T c[7];
     row_coefs<DICT>(A, tbl, r, c);
     if (init) {
         x[r] = b[r] / c[3];
         return;
     }
-    double v[6];
+    T v[6];
     neighbours(A, p, r, [&](int64_t q) { return x[q]; }, v);
     x[r] = gs_value(c, v, b[r]);
+}
+
+// The init half-sweep (red) of the fp32 cycle's fine level: it visits every row anyway, so it narrows the fp64
+// right-hand side once (round to nearest) into bf, which every later launch of the application reads, and sets
+// x = bf / d on red, 0 on black.  Bytes per row: b 8 + 1 class byte read, bf 4 + x 4 written = 17 B.
+template <bool DICT>
+__global__ __launch_bounds__(256) void k_mg_init_f32(MgOp32 A, Gate g, const double *__restrict__ b,
+                                                     float *__restrict__ bf, float *__restrict__ x)
+{
+    __shared__ float tbl[EC3D_MG_MAXCLS * 7];
+    if (gated_off(g)) return;
+    if (DICT) load_table(A, tbl);
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= A.n) return;
+    const float bv = (float)b[r];
+    bf[r] = bv;
+    const Pos p = pos_of(A, r);
+    if ((p.i + p.j + p.k) & 1) {
+        x[r] = 0.0f;
+        return;
+    }
+    float c[7];
+    row_coefs<DICT>(A, tbl, r, c);
+    x[r] = bv / c[3];
 }
 
 // Residual + restriction: bc[coarse cell] = (sum of its children's b - A w, k outermost, i innermost, from 0) * 1/children.
 // One thread per coarse cell; the fine residual never reaches HBM.  Bytes per FINE row: w 8 + b 8 + 1 class byte read,
 // 8 / children written = 18 B at factor 2 along every axis.
-template <bool DICT>
-__global__ __launch_bounds__(256) void k_mg_restrict(MgOp A, MgOp C, int fx, int fy, int fz, Gate g,
-                                                     const double *__restrict__ w, const double *__restrict__ b,
-                                                     double *__restrict__ bc)
+// T = float: about 9.5 B (1 / children is a power of two, exact in either precision).
+template <bool DICT, class T = double>
+__global__ __launch_bounds__(256) void k_mg_restrict(MgOpT<T> A, MgOpT<T> C, int fx, int fy, int fz, Gate g,
+                                                     const T *__restrict__ w, const T *__restrict__ b,
+                                                     T *__restrict__ bc)
 {
-    __shared__ double tbl[EC3D_MG_MAXCLS * 7];
+    __shared__ T tbl[EC3D_MG_MAXCLS * 7];
     if (gated_off(g)) return;
     if (DICT) load_table(A, tbl);
     const int64_t rc = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (rc >= C.n) return;
     const Pos pc = pos_of(C, rc);
-    double s = 0.0;
+    T s = T(0);
     for (int dk = 0; dk < fz; ++dk)
         for (int dj = 0; dj < fy; ++dj)
             for (int di = 0; di < fx; ++di) {
                 const Pos p{pc.i * fx + di, pc.j * fy + dj, pc.k * fz + dk};
                 const int64_t r = (int64_t)p.k * A.kdz + (int64_t)p.j * A.sdx + p.i;
-                double c[7], v[6];
+                T c[7], v[6];
                 row_coefs<DICT>(A, tbl, r, c);
                 neighbours(A, p, r, [&](int64_t q) { return w[q]; }, v);
-                double t = b[r];
+                T t = b[r];
                 t = t - c[0] * v[0];
                 t = t - c[1] * v[1];
                 t = t - c[2] * v[2];
@@ -237,18 +283,19 @@ __global__ __launch_bounds__(256) void k_mg_restrict(MgOp A, MgOp C, int fx, int
                 t = t - c[6] * v[5];
                 s = s + t;
             }
-    bc[rc] = s * (1.0 / (double)(fx * fy * fz));
+    bc[rc] = s * (T(1) / (T)(fx * fy * fz));
 }
 
 // Prolongation (piecewise-constant injection) + correction fused with the first post-smoothing half-sweep (black):
 // red rows x = w + xc[parent]; black rows the GS value from the corrected red neighbours.  Bytes per fine row: w 8 +
 // b 8 (black rows; the lines hold both colours) + 1 class byte read, x 8 written, xc from the L2 = 25 B.
-template <bool DICT>
-__global__ __launch_bounds__(256) void k_mg_prolong(MgOp A, MgOp C, int fx, int fy, int fz, Gate g,
-                                                    const double *__restrict__ w, const double *__restrict__ xc,
-                                                    const double *__restrict__ b, double *__restrict__ x)
+// T = float: 13 B.
+template <bool DICT, class T = double>
+__global__ __launch_bounds__(256) void k_mg_prolong(MgOpT<T> A, MgOpT<T> C, int fx, int fy, int fz, Gate g,
+                                                    const T *__restrict__ w, const T *__restrict__ xc,
+                                                    const T *__restrict__ b, T *__restrict__ x)
 {
-    __shared__ double tbl[EC3D_MG_MAXCLS * 7];
+    __shared__ T tbl[EC3D_MG_MAXCLS * 7];
     if (gated_off(g)) return;
     if (DICT) load_table(A, tbl);
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -263,7 +310,7 @@ __global__ __launch_bounds__(256) void k_mg_prolong(MgOp A, MgOp C, int fx, int 
         x[r] = corrected(r);
         return;
     }
-    double c[7], v[6];
+    T c[7], v[6];
     row_coefs<DICT>(A, tbl, r, c);
     neighbours(A, p, r, corrected, v);
     x[r] = gs_value(c, v, b[r]);
@@ -271,17 +318,18 @@ __global__ __launch_bounds__(256) void k_mg_prolong(MgOp A, MgOp C, int fx, int 
 
 // Coarsest level: `sweeps` sweeps of (red, black, black, red) from x = 0 by one workgroup, x in LDS, b and the class of
 // a thread's (at most four) rows in registers.  A fixed linear operator of b, so BiCGSTAB stays valid.
-template <bool DICT>
-__global__ __launch_bounds__(EC3D_MG_COARSE_THREADS) void k_mg_coarse(MgOp A, Gate g, int sweeps,
-                                                                      const double *__restrict__ b,
-                                                                      double *__restrict__ x)
+// TB: the precision b arrives in -- T, except on a single-level fp32 hierarchy, whose only launch reads the fp64
+// right-hand side and narrows it on load.
+template <bool DICT, class T = double, class TB = T>
+__global__ __launch_bounds__(EC3D_MG_COARSE_THREADS) void k_mg_coarse(MgOpT<T> A, Gate g, int sweeps,
+                                                                      const TB *__restrict__ b, T *__restrict__ x)
 {
     constexpr int RPT = EC3D_MG_COARSE_ROWS / EC3D_MG_COARSE_THREADS;
-    __shared__ double xs[EC3D_MG_COARSE_ROWS];
-    __shared__ double tbl[EC3D_MG_MAXCLS * 7];
+    __shared__ T xs[EC3D_MG_COARSE_ROWS];
+    __shared__ T tbl[EC3D_MG_MAXCLS * 7];
     if (gated_off(g)) return;
     if (DICT) load_table(A, tbl);
-    double br[RPT];
+    T br[RPT];
     Pos pr[RPT];
     int colr[RPT];
 #pragma unroll
@@ -291,8 +339,8 @@ __global__ __launch_bounds__(EC3D_MG_COARSE_THREADS) void k_mg_coarse(MgOp A, Ga
         if (r < A.n) {
             pr[q] = pos_of(A, r);
             colr[q] = (pr[q].i + pr[q].j + pr[q].k) & 1;
-            br[q] = b[r];
-            xs[r] = 0.0;
+            br[q] = (T)b[r];
+            xs[r] = T(0);
         }
     }
     __syncthreads();
@@ -303,7 +351,7 @@ __global__ __launch_bounds__(EC3D_MG_COARSE_THREADS) void k_mg_coarse(MgOp A, Ga
             for (int q = 0; q < RPT; ++q) {
                 if (colr[q] != colour) continue;
                 const int64_t r = threadIdx.x + (int64_t)q * EC3D_MG_COARSE_THREADS;
-                double c[7], v[6];
+                T c[7], v[6];
                 row_coefs<DICT>(A, tbl, r, c);
                 neighbours(A, pr[q], r, [&](int64_t t) { return xs[t]; }, v);
                 xs[r] = gs_value(c, v, br[q]);
@@ -333,8 +381,9 @@ __device__ __forceinline__ double block_sum(double v, double *lds)
 
 // y = A x (rows summed in offset order from the -z term); partials of a.y (slot 0) and, with two, y.y (slot 1).
 // Bytes per row: x 8 + a 8 + 1 class byte read, y 8 written = 25 B.
-template <bool DICT>
-__global__ __launch_bounds__(256) void k_mg_spmv_dot(MgOp A, Gate g, const double *__restrict__ x,
+// TX = float: x is p^ / s^ of the fp32 V-cycle, widened on load (exact); every product and sum stays fp64 (21 B).
+template <bool DICT, class TX = double>
+__global__ __launch_bounds__(256) void k_mg_spmv_dot(MgOp A, Gate g, const TX *__restrict__ x,
                                                      const double *__restrict__ a, double *__restrict__ y, int two,
                                                      double *__restrict__ part)
 {
@@ -347,11 +396,11 @@ __global__ __launch_bounds__(256) void k_mg_spmv_dot(MgOp A, Gate g, const doubl
         const Pos p = pos_of(A, r);
         double c[7], v[6];
         row_coefs<DICT>(A, tbl, r, c);
-        neighbours(A, p, r, [&](int64_t q) { return x[q]; }, v);
+        neighbours(A, p, r, [&](int64_t q) { return (double)x[q]; }, v);
         double s = c[0] * v[0];
         s = s + c[1] * v[1];
         s = s + c[2] * v[2];
-        s = s + c[3] * x[r];
+        s = s + c[3] * (double)x[r];
         s = s + c[4] * v[3];
         s = s + c[5] * v[4];
         s = s + c[6] * v[5];
@@ -387,8 +436,10 @@ __global__ __launch_bounds__(256) void k_mg_s(int64_t n, Gate g, const SolverSta
 
 // x = x + alpha p^ + omega s^;  r = s - omega t;  partials r.r, r.r0.  After the ||S|| exit of this iteration only
 // x = x + alpha p^ (src/solvers.f90:34-37).  Bytes per row: x, p^, s^, s, t, r0 read 48, x, r written 16 = 64 B.
+// TX = float: p^ and s^ of the fp32 V-cycle, widened on load (56 B).
+template <class TX = double>
 __global__ __launch_bounds__(256) void k_mg_xr(int64_t n, int it, const SolverState *st, double *__restrict__ x,
-                                               const double *__restrict__ ph, const double *__restrict__ sh,
+                                               const TX *__restrict__ ph, const TX *__restrict__ sh,
                                                const double *__restrict__ s, const double *__restrict__ t,
                                                const double *__restrict__ r0, double *__restrict__ r,
                                                double *__restrict__ part)
@@ -401,10 +452,10 @@ __global__ __launch_bounds__(256) void k_mg_xr(int64_t n, int it, const SolverSt
     double d0 = 0.0, d1 = 0.0;
     for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (int64_t)gridDim.x * blockDim.x) {
         if (s_exit) {
-            x[q] = x[q] + alpha * ph[q];
+            x[q] = x[q] + alpha * (double)ph[q];
             continue;
         }
-        x[q] = x[q] + alpha * ph[q] + omega * sh[q];
+        x[q] = x[q] + alpha * (double)ph[q] + omega * (double)sh[q];
         const double rv = s[q] - omega * t[q];
         r[q] = rv;
         d0 = d0 + rv * rv;
@@ -503,43 +554,90 @@ MgOp op_of(const DevMatrix &A, int sdx, int sdy, int sdz)
         else kern<false><<<(grid), (block), 0, s>>>(__VA_ARGS__);                                                 \
     } while (0)
 
-// one V-cycle z = M r (enqueued)
-void launch_vcycle(ec3d_mg *m, Gate g, const double *r, double *z, hipStream_t s)
+// a level's operator and vectors in the precision T of the hierarchy (the kernels' T is deduced from them)
+template <class T> struct LevelOf;
+template <> struct LevelOf<double> {
+    const MgOp &op;
+    double *x, *w, *b;
+    explicit LevelOf(const MgLevel &l) : op(l.op), x(l.x), w(l.w), b(l.b) {}
+};
+template <> struct LevelOf<float> {
+    const MgOp32 &op;
+    float *x, *w, *b;
+    explicit LevelOf(const MgLevel &l) : op(l.op32), x(l.x32), w(l.w32), b(l.b32) {}
+};
+// the fine level's w, and the right-hand side its launches read: fp64 r itself, fp32 the copy the init half-sweep writes
+inline double *fine_w(const ec3d_mg *m, double) { return m->w0; }
+inline float *fine_w(const ec3d_mg *m, float) { return m->w0_32; }
+inline const double *fine_b(const ec3d_mg *, const double *r, double) { return r; }
+inline const float *fine_b(const ec3d_mg *m, const double *, float) { return m->b0_32; }
+// the fine level's first half-sweep (red, from x = 0)
+inline void launch_fine_init(ec3d_mg *m, const MgOp &A, Gate g, const double *r, double *w, hipStream_t s)
+{
+    const bool dict = A.cls != nullptr;
+    MG_LAUNCH(k_mg_smooth, blocks_of(A.n), 256, A, g, 0, 1, w, r);
+}
+inline void launch_fine_init(ec3d_mg *m, const MgOp32 &A, Gate g, const double *r, float *w, hipStream_t s)
+{
+    const bool dict = A.cls != nullptr;
+    MG_LAUNCH(k_mg_init_f32, blocks_of(A.n), 256, A, g, r, m->b0_32, w);
+}
+
+// one V-cycle z = M r (enqueued).  T = float (EC3D_PRECOND_FP32): r stays fp64; the fine level's init half-sweep narrows
+// it into b0_32 (k_mg_init_f32), or the coarse solve does on load when the hierarchy has one level.
+template <class T> void launch_vcycle(ec3d_mg *m, Gate g, const double *r, T *z, hipStream_t s)
 {
     const int L = (int)m->lev.size();
+    const T *B0 = fine_b(m, r, T());
+    T *W0 = fine_w(m, T());
     for (int l = 0; l + 1 < L; ++l) {
-        MgLevel &F = m->lev[(size_t)l];
-        const MgOp &A = F.op;
+        const LevelOf<T> F(m->lev[(size_t)l]), C(m->lev[(size_t)l + 1]);
+        const int *f = m->lev[(size_t)l].f;
+        const auto &A = F.op;
         const bool dict = A.cls != nullptr;
-        const double *B = l == 0 ? r : F.b;
-        double *W = l == 0 ? m->w0 : F.w;
+        const T *B = l == 0 ? B0 : F.b;
+        T *W = l == 0 ? W0 : F.w;
         for (int sw = 0; sw < m->pre; ++sw) {
-            MG_LAUNCH(k_mg_smooth, blocks_of(A.n), 256, A, g, 0, sw == 0, W, B);
+            if (l == 0 && sw == 0) launch_fine_init(m, A, g, r, W, s);
+            else MG_LAUNCH(k_mg_smooth, blocks_of(A.n), 256, A, g, 0, sw == 0, W, B);
             MG_LAUNCH(k_mg_smooth, blocks_of(A.n), 256, A, g, 1, 0, W, B);
         }
-        const MgLevel &C = m->lev[(size_t)l + 1];
-        MG_LAUNCH(k_mg_restrict, blocks_of(C.op.n), 256, A, C.op, F.f[0], F.f[1], F.f[2], g, W, B, C.b);
+        MG_LAUNCH(k_mg_restrict, blocks_of(C.op.n), 256, A, C.op, f[0], f[1], f[2], g, W, B, C.b);
     }
     {
-        MgLevel &K = m->lev[(size_t)L - 1];
+        const LevelOf<T> K(m->lev[(size_t)L - 1]);
         const bool dict = K.op.cls != nullptr;
-        MG_LAUNCH(k_mg_coarse, 1, EC3D_MG_COARSE_THREADS, K.op, g, m->coarse, L == 1 ? r : K.b, L == 1 ? z : K.x);
+        if (L == 1) MG_LAUNCH(k_mg_coarse, 1, EC3D_MG_COARSE_THREADS, K.op, g, m->coarse, r, z);
+        else MG_LAUNCH(k_mg_coarse, 1, EC3D_MG_COARSE_THREADS, K.op, g, m->coarse, K.b, K.x);
     }
     for (int l = L - 2; l >= 0; --l) {
-        MgLevel &F = m->lev[(size_t)l];
-        const MgOp &A = F.op;
+        const LevelOf<T> F(m->lev[(size_t)l]), C(m->lev[(size_t)l + 1]);
+        const int *f = m->lev[(size_t)l].f;
+        const auto &A = F.op;
         const bool dict = A.cls != nullptr;
-        const double *B = l == 0 ? r : F.b;
-        double *W = l == 0 ? m->w0 : F.w;
-        double *X = l == 0 ? z : F.x;
-        const MgLevel &C = m->lev[(size_t)l + 1];
-        MG_LAUNCH(k_mg_prolong, blocks_of(A.n), 256, A, C.op, F.f[0], F.f[1], F.f[2], g, W, C.x, B, X);
+        const T *B = l == 0 ? B0 : F.b;
+        T *W = l == 0 ? W0 : F.w;
+        T *X = l == 0 ? z : F.x;
+        MG_LAUNCH(k_mg_prolong, blocks_of(A.n), 256, A, C.op, f[0], f[1], f[2], g, W, C.x, B, X);
         MG_LAUNCH(k_mg_smooth, blocks_of(A.n), 256, A, g, 0, 0, X, B);
         for (int sw = 1; sw < m->post; ++sw) {
             MG_LAUNCH(k_mg_smooth, blocks_of(A.n), 256, A, g, 1, 0, X, B);
             MG_LAUNCH(k_mg_smooth, blocks_of(A.n), 256, A, g, 0, 0, X, B);
         }
     }
+}
+
+// fp64 -> fp32, round to nearest: a level's coefficients at set-up
+__global__ __launch_bounds__(256) void k_mg_narrow(int64_t n, const double *__restrict__ a, float *__restrict__ o)
+{
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q < n) o[q] = (float)a[q];
+}
+// fp32 -> fp64 (exact): z of ec3d_precond_apply on an fp32 hierarchy
+__global__ __launch_bounds__(256) void k_mg_widen(int64_t n, const float *__restrict__ a, double *__restrict__ o)
+{
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q < n) o[q] = (double)a[q];
 }
 
 // ---- block multigrid of the structured A-V form (EC3D_PRECOND_BLOCK_MG) ----------------------
@@ -1230,6 +1328,12 @@ extern "C" int ec3d_set_preconditioner(ec3d_handle c, int kind, int32_t pre, int
     }
     int rc = ec3d_need_matrix(c, "ec3d_set_preconditioner");
     if (rc) return rc;
+    const bool f32 = c->precond_precision == EC3D_PRECOND_FP32;
+    if (kind == EC3D_PRECOND_BLOCK_MG && f32) {
+        ec3d_set_error("ec3d_set_preconditioner: the fp32 V-cycle (ec3d_set_precond_precision) is available for "
+                       "EC3D_PRECOND_MG only, not for the block multigrid of the A-V form");
+        return EC3D_PRECOND_E_MATRIX;
+    }
     if (kind == EC3D_PRECOND_BLOCK_MG) return set_block_mg(c, pre, post, coarse_sweeps);
     if (!c->poisson_full || c->in_multi || c->halo > 0 || c->nranks > 1 || c->dist) {
         ec3d_set_error("ec3d_set_preconditioner: the multigrid preconditioner needs a matrix from ec3d_assemble_poisson "
@@ -1250,6 +1354,7 @@ extern "C" int ec3d_set_preconditioner(ec3d_handle c, int kind, int32_t pre, int
     }
     // build the new hierarchy completely before the old one is replaced: a failure leaves the handle as it was
     std::unique_ptr<ec3d_mg> m(new ec3d_mg);
+    m->precision = c->precond_precision;
     m->pre = pre ? pre : 2;
     m->post = post ? post : 2;
     m->coarse = coarse_sweeps ? coarse_sweeps : 16;
@@ -1271,26 +1376,62 @@ extern "C" int ec3d_set_preconditioner(ec3d_handle c, int kind, int32_t pre, int
         coarse_len += 3 * ((Q.op.n + 63) / 64 * 64);
     }
     const int64_t nf = (c->A.n + 63) / 64 * 64;
-    const int64_t total = coarse_len + 3 * nf;
-    if (m->vec_base.alloc((size_t)total) != hipSuccess || m->part.alloc(2 * EC3D_MG_DOT_BLOCKS) != hipSuccess ||
-        m->scal.alloc(1) != hipSuccess) {
+    // fp64: the fine w, p^, s^; fp32: those and the fine right-hand side's copy, in floats, and no fp64 vector at all
+    const int64_t total = coarse_len + (f32 ? 4 : 3) * nf;
+    const hipError_t ev = f32 ? m->vec32.alloc((size_t)total) : m->vec_base.alloc((size_t)total);
+    if (ev != hipSuccess || m->part.alloc(2 * EC3D_MG_DOT_BLOCKS) != hipSuccess || m->scal.alloc(1) != hipSuccess) {
         (void)hipGetLastError();
         ec3d_set_error("ec3d_set_preconditioner: out of device memory for the hierarchy");
         return 100;
     }
-    if (hipMemsetAsync(m->vec_base, 0, (size_t)total * sizeof(double), c->stream) != hipSuccess ||
+    void *const vecs = f32 ? (void *)m->vec32.get() : (void *)m->vec_base.get();
+    if (hipMemsetAsync(vecs, 0, (size_t)total * (f32 ? sizeof(float) : sizeof(double)), c->stream) != hipSuccess ||
         hipMemsetAsync(m->scal, 0, sizeof(MgScalars), c->stream) != hipSuccess) {
         ec3d_set_error("ec3d_set_preconditioner: hipMemsetAsync failed");
         return 100;
     }
-    double *q = m->vec_base;
-    for (int l = 1; l < L; ++l) {
-        MgLevel &Q = m->lev[(size_t)l];
-        const int64_t len = (Q.op.n + 63) / 64 * 64;
-        Q.x = q; Q.w = q + len; Q.b = q + 2 * len;
-        q += 3 * len;
+    if (f32) {
+        float *q = m->vec32;
+        for (int l = 1; l < L; ++l) {
+            MgLevel &Q = m->lev[(size_t)l];
+            const int64_t len = (Q.op.n + 63) / 64 * 64;
+            Q.x32 = q; Q.w32 = q + len; Q.b32 = q + 2 * len;
+            q += 3 * len;
+        }
+        m->w0_32 = q; m->b0_32 = q + nf; m->ph32 = q + 2 * nf; m->sh32 = q + 3 * nf;
+        // every level's coefficients, narrowed once: the class table, or (level 0 in band form) the seven streams
+        for (int l = 0; l < L; ++l) {
+            MgLevel &Q = m->lev[(size_t)l];
+            const bool dict = Q.op.cls != nullptr;
+            const int64_t len = dict ? (int64_t)Q.op.ncls * 7 : 7 * Q.op.n_pad;
+            if (Q.coef32.alloc((size_t)len) != hipSuccess) {
+                (void)hipGetLastError();
+                ec3d_set_error("ec3d_set_preconditioner: out of device memory for the hierarchy");
+                return 100;
+            }
+            k_mg_narrow<<<blocks_of(len), 256, 0, c->stream>>>(len, dict ? Q.op.table : Q.op.bands, Q.coef32);
+            MgOp32 &o = Q.op32;
+            o.sdx = Q.op.sdx; o.sdy = Q.op.sdy; o.sdz = Q.op.sdz;
+            o.n = Q.op.n; o.n_pad = Q.op.n_pad; o.kdz = Q.op.kdz;
+            o.cls = Q.op.cls;
+            o.ncls = Q.op.ncls;
+            o.table = dict ? Q.coef32.get() : nullptr;
+            o.bands = dict ? nullptr : Q.coef32.get();
+        }
+        if (hipGetLastError() != hipSuccess) {
+            ec3d_set_error("ec3d_set_preconditioner: building the hierarchy failed");
+            return 100;
+        }
+    } else {
+        double *q = m->vec_base;
+        for (int l = 1; l < L; ++l) {
+            MgLevel &Q = m->lev[(size_t)l];
+            const int64_t len = (Q.op.n + 63) / 64 * 64;
+            Q.x = q; Q.w = q + len; Q.b = q + 2 * len;
+            q += 3 * len;
+        }
+        m->w0 = q; m->ph = q + nf; m->sh = q + 2 * nf;
     }
-    m->w0 = q; m->ph = q + nf; m->sh = q + 2 * nf;
     if (hipStreamSynchronize(c->stream) != hipSuccess) {
         ec3d_set_error("ec3d_set_preconditioner: building the hierarchy failed");
         return 100;
@@ -1328,6 +1469,29 @@ extern "C" int ec3d_get_preconditioner(ec3d_handle c, int *kind, int32_t *levels
     return 0;
 }
 
+extern "C" int ec3d_set_precond_precision(ec3d_handle c, int32_t precision)
+{
+    if (!c || (precision != EC3D_PRECOND_FP64 && precision != EC3D_PRECOND_FP32)) {
+        ec3d_set_error(!c ? std::string("ec3d_set_precond_precision: null handle")
+                          : "ec3d_set_precond_precision: unknown precision " + std::to_string(precision) +
+                                " (EC3D_PRECOND_FP64 = 0, EC3D_PRECOND_FP32 = 1)");
+        return 2;
+    }
+    c->precond_precision = precision;
+    return 0;
+}
+
+extern "C" int ec3d_get_precond_precision(ec3d_handle c, int32_t *setting, int32_t *in_use)
+{
+    if (!c) {
+        ec3d_set_error("ec3d_get_precond_precision: null handle");
+        return 2;
+    }
+    if (setting) *setting = c->precond_precision;
+    if (in_use) *in_use = c->mg ? c->mg->precision : EC3D_PRECOND_FP64;
+    return 0;
+}
+
 extern "C" int ec3d_precond_apply(ec3d_handle c, const double *r, double *z)
 {
     int rc = ec3d_need_matrix(c, "ec3d_precond_apply");
@@ -1337,6 +1501,16 @@ extern "C" int ec3d_precond_apply(ec3d_handle c, const double *r, double *z)
         return 3;
     }
     ec3d_mg *m = c->mg;
+    if (m->precision == EC3D_PRECOND_FP32) {
+        // r and z in fp64 through the work vectors P and AP (as ec3d_spmv); the cycle narrows r, z is widened exactly
+        if ((rc = ec3d_vec_h2d(c, c->vec[EC3D_VEC_P], r))) return rc;
+        launch_vcycle(m, Gate{nullptr, 0, 0}, c->vec[EC3D_VEC_P], m->sh32, c->stream);
+        k_mg_widen<<<blocks_of(c->A.n), 256, 0, c->stream>>>(c->A.n, m->sh32, c->vec[EC3D_VEC_AP]);
+        EC3D_HIP(hipGetLastError());
+        if ((rc = ec3d_vec_d2h(c, z, c->vec[EC3D_VEC_AP]))) return rc;
+        EC3D_HIP(hipStreamSynchronize(c->stream));
+        return 0;
+    }
     if ((rc = ec3d_vec_h2d(c, m->ph, r))) return rc;
     if (m->kind == EC3D_PRECOND_BLOCK_MG) launch_avcycle(m, Gate{nullptr, 0, 0}, m->ph, m->sh, c->stream);
     else launch_vcycle(m, Gate{nullptr, 0, 0}, m->ph, m->sh, c->stream);
@@ -1366,13 +1540,11 @@ int ec3d_mg_chunk(const ec3d_ctx *c)
 //   s^ = M s; t = A s^; omega = (t.s)/(t.t); x += alpha p^ + omega s^; r = s - omega t; [exit on ||r|| / ||b||]
 //   beta = (alpha / omega) (r.r0) / rho; p = r + beta (p - omega v); restart as the reference.
 // The work vectors: v in AP, t in AS.  Sums and exits stay on the device; launches past an exit are no-ops.
-void ec3d_mg_launch_iteration(ec3d_ctx *c, int it)
+// T: the precision of M and of p^, s^ (ph, sh), which the SpMV + dot launch and the x / r update widen on load; every
+// other operand and operation of the outer iteration is fp64 in both.
+template <class T> static void mg_launch_iteration_of(ec3d_ctx *c, int it, T *ph, T *sh)
 {
     ec3d_mg *m = c->mg;
-    if (m->kind == EC3D_PRECOND_BLOCK_MG) {
-        avmg_launch_iteration(c, it);
-        return;
-    }
     double **v = c->vec;
     hipStream_t s = c->stream;
     const MgOp &A = m->lev[0].op;
@@ -1380,16 +1552,24 @@ void ec3d_mg_launch_iteration(ec3d_ctx *c, int it)
     const int64_t n = A.n;
     const unsigned nb = dot_blocks(n);
     const Gate g0{c->state, it, 0}, g1{c->state, it, 1};
-    launch_vcycle(m, g0, v[EC3D_VEC_P], m->ph, s);
-    MG_LAUNCH(k_mg_spmv_dot, nb, 256, A, g0, m->ph, v[EC3D_VEC_R0], v[EC3D_VEC_AP], 0, m->part);
+    launch_vcycle(m, g0, v[EC3D_VEC_P], ph, s);
+    MG_LAUNCH(k_mg_spmv_dot, nb, 256, A, g0, (const T *)ph, v[EC3D_VEC_R0], v[EC3D_VEC_AP], 0, m->part);
     k_mg_scalar<<<1, 256, 0, s>>>(MG_ALPHA, g0, c->state, m->scal, m->part, (int)nb, c->hist, c->hist_cap);
     k_mg_s<<<nb, 256, 0, s>>>(n, g0, c->state, v[EC3D_VEC_R], v[EC3D_VEC_AP], v[EC3D_VEC_S], m->part);
     k_mg_scalar<<<1, 256, 0, s>>>(MG_SEXIT, g0, c->state, m->scal, m->part, (int)nb, c->hist, c->hist_cap);
-    launch_vcycle(m, g1, v[EC3D_VEC_S], m->sh, s);
-    MG_LAUNCH(k_mg_spmv_dot, nb, 256, A, g1, m->sh, v[EC3D_VEC_S], v[EC3D_VEC_AS], 1, m->part);
+    launch_vcycle(m, g1, v[EC3D_VEC_S], sh, s);
+    MG_LAUNCH(k_mg_spmv_dot, nb, 256, A, g1, (const T *)sh, v[EC3D_VEC_S], v[EC3D_VEC_AS], 1, m->part);
     k_mg_scalar<<<1, 256, 0, s>>>(MG_OMEGA, g1, c->state, m->scal, m->part, (int)nb, c->hist, c->hist_cap);
-    k_mg_xr<<<nb, 256, 0, s>>>(n, it, c->state, v[EC3D_VEC_X], m->ph, m->sh, v[EC3D_VEC_S], v[EC3D_VEC_AS],
+    k_mg_xr<<<nb, 256, 0, s>>>(n, it, c->state, v[EC3D_VEC_X], (const T *)ph, (const T *)sh, v[EC3D_VEC_S], v[EC3D_VEC_AS],
                                v[EC3D_VEC_R0], v[EC3D_VEC_R], m->part);
     k_mg_scalar<<<1, 256, 0, s>>>(MG_REXIT, g1, c->state, m->scal, m->part, (int)nb, c->hist, c->hist_cap);
     k_mg_p<<<nb, 256, 0, s>>>(n, g1, c->state, m->scal, v[EC3D_VEC_R], v[EC3D_VEC_AP], v[EC3D_VEC_P], v[EC3D_VEC_R0]);
+}
+
+void ec3d_mg_launch_iteration(ec3d_ctx *c, int it)
+{
+    ec3d_mg *m = c->mg;
+    if (m->kind == EC3D_PRECOND_BLOCK_MG) avmg_launch_iteration(c, it);
+    else if (m->precision == EC3D_PRECOND_FP32) mg_launch_iteration_of(c, it, m->ph32, m->sh32);
+    else mg_launch_iteration_of(c, it, m->ph, m->sh);
 }

@@ -21,12 +21,14 @@ module ec3d_hip
               ec3d_multi_vtk_fields_begin, ec3d_multi_vtk_fields_wait, ec3d_rccl_unique_id, ec3d_multi_create_rank, &
               ec3d_multi_plan, ec3d_set_preconditioner, ec3d_get_preconditioner, ec3d_precond_apply, &
               EC3D_PRECOND_NONE, EC3D_PRECOND_MG, EC3D_PRECOND_BLOCK_MG, &
-              ec3d_set_u_rhs, EC3D_U_RHS_REFERENCE, EC3D_U_RHS_ALL
+              ec3d_set_u_rhs, EC3D_U_RHS_REFERENCE, EC3D_U_RHS_ALL, &
+              ec3d_set_precond_precision, ec3d_get_precond_precision, EC3D_PRECOND_FP64, EC3D_PRECOND_FP32
 
     integer(c_int), parameter :: EC3D_VEC_X = 0, EC3D_VEC_B = 1   ! Uaf, Jaf
     integer(c_int), parameter :: EC3D_PRECOND_NONE = 0, EC3D_PRECOND_MG = 1   ! ec3d_set_preconditioner
     integer(c_int), parameter :: EC3D_PRECOND_BLOCK_MG = 2   ! ... of the structured A-V form (ec3d_assemble)
     integer(c_int), parameter :: EC3D_U_RHS_REFERENCE = 0, EC3D_U_RHS_ALL = 1   ! ec3d_set_u_rhs
+    integer(c_int32_t), parameter :: EC3D_PRECOND_FP64 = 0, EC3D_PRECOND_FP32 = 1   ! ec3d_set_precond_precision
 
     interface
         integer(c_int) function ec3d_create(h, device) bind(C, name="ec3d_create")
@@ -176,6 +178,18 @@ module ec3d_hip
             type(c_ptr), value :: h
             real(c_double), intent(in) :: r(*)
             real(c_double), intent(out) :: z(*)
+        end function
+        ! precision of the V-cycle the next ec3d_set_preconditioner(EC3D_PRECOND_MG) builds (include/ec3d_hip.h)
+        integer(c_int) function ec3d_set_precond_precision(h, precision) bind(C, name="ec3d_set_precond_precision")
+            import :: c_ptr, c_int, c_int32_t
+            type(c_ptr), value :: h
+            integer(c_int32_t), value :: precision
+        end function
+        ! setting: the handle's; in_use: that of the hierarchy now set (EC3D_PRECOND_FP64 when there is none)
+        integer(c_int) function ec3d_get_precond_precision(h, setting, in_use) bind(C, name="ec3d_get_precond_precision")
+            import :: c_ptr, c_int, c_int32_t
+            type(c_ptr), value :: h
+            integer(c_int32_t), intent(out) :: setting, in_use
         end function
         ! U rows ec3d_rhs_step gives their right-hand side with several conducting domains (include/ec3d_hip.h)
         integer(c_int) function ec3d_set_u_rhs(h, rule) bind(C, name="ec3d_set_u_rhs")

@@ -69,10 +69,12 @@ EXPORTS = ["sprsbcgstabwr_", "ec3d_invalidate", "ec3d_create", "ec3d_destroy", "
            "ec3d_multi_rhs_step", "ec3d_multi_post_update", "ec3d_multi_vtk_fields", "ec3d_multi_vtk_fields_begin",
            "ec3d_multi_vtk_fields_wait", "ec3d_multi_iterate_begin",
            "ec3d_multi_iterate", "ec3d_multi_synchronize", "ec3d_true_residual", "ec3d_multi_true_residual", "ec3d_get_visit_order", "ec3d_probe_csr_multi", "ec3d_multi_spmv", "ec3d_multi_api_calls", "ec3d_multi_plan", "ec3d_multi_halo_rows", "ec3d_rccl_unique_id", "ec3d_multi_create_rank", "ec3d_format_real8_gfortran", "ec3d_multi_iterate_timed", "ec3d_multi_rccl_info",
-           "ec3d_set_preconditioner", "ec3d_get_preconditioner", "ec3d_precond_apply", "ec3d_set_u_rhs"]
+           "ec3d_set_preconditioner", "ec3d_get_preconditioner", "ec3d_precond_apply", "ec3d_set_u_rhs",
+           "ec3d_set_precond_precision", "ec3d_get_precond_precision"]
 U_RHS = {"reference": 0, "all": 1}   # EC3D_U_RHS_* of include/ec3d_hip.h
 PRECOND = {"none": 0, "mg": 1, "block-mg": 2}   # EC3D_PRECOND_* of include/ec3d_hip.h
 PRECOND_E_MATRIX, PRECOND_E_COARSE = 20, 21   # ec3d_set_preconditioner's refusals
+PRECOND_PRECISION = {"fp64": 0, "fp32": 1}   # EC3D_PRECOND_FP64 / _FP32 of include/ec3d_hip.h
 
 _f64 = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
 _i32 = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
@@ -151,6 +153,8 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.ec3d_get_preconditioner.argtypes = [hp, C.POINTER(C.c_int), C.POINTER(C.c_int32), hp]
     L.ec3d_precond_apply.argtypes = [hp, _f64, _f64]
     L.ec3d_set_u_rhs.argtypes = [hp, C.c_int32]
+    L.ec3d_set_precond_precision.argtypes = [hp, C.c_int32]
+    L.ec3d_get_precond_precision.argtypes = [hp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.ec3d_export_csr.argtypes = [hp, C.POINTER(C.c_int32), C.POINTER(C.c_int64), hp, hp, hp]
     L.ec3d_get_cel_bnd.argtypes = [hp, C.c_int, C.POINTER(C.c_int32), hp]
     L.ec3d_get_reduction_geometry.argtypes = [hp, C.c_int, C.POINTER(Geom)]
@@ -535,13 +539,42 @@ class EC3DSolver:
         _chk(self.L, self.L.ec3d_set_u_rhs(self.h, U_RHS[rule]), "ec3d_set_u_rhs")
 
     # ---- preconditioner ("mg": a matrix from assemble_poisson; "block-mg": the structured A-V form) -----------
-    def set_preconditioner(self, kind: str = "mg", pre: int = 2, post: int = 2, coarse_sweeps: int = 0):
+    def set_preconditioner(self, kind: str = "mg", pre: int = 2, post: int = 2, coarse_sweeps: int = 0,
+                           precision: str | None = None):
         """"mg": solves run the right-preconditioned iteration with one multigrid V-cycle as M; "block-mg": the same
         iteration on the A-V system of assemble, M one Galerkin V-cycle per A block and Gauss-Seidel sweeps on U;
-        "none": the reference's iteration.  Zeros select the library's defaults.  Refusal: EC3DError with .status
-        PRECOND_E_MATRIX or PRECOND_E_COARSE, the handle unchanged."""
-        _chk(self.L, self.L.ec3d_set_preconditioner(self.h, PRECOND[kind], pre, post, coarse_sweeps),
-             "ec3d_set_preconditioner")
+        "none": the reference's iteration.  Zeros select the library's defaults.  ``precision`` ("fp64" or "fp32"):
+        set_precond_precision(precision) first -- the handle keeps it, unless the call is refused; None leaves the
+        handle's setting as it is.  Refusal: EC3DError with .status PRECOND_E_MATRIX or PRECOND_E_COARSE, the handle unchanged."""
+        if precision is None:
+            _chk(self.L, self.L.ec3d_set_preconditioner(self.h, PRECOND[kind], pre, post, coarse_sweeps),
+                 "ec3d_set_preconditioner")
+            return
+        before = self.precond_precision()[0]
+        self.set_precond_precision(precision)
+        try:
+            _chk(self.L, self.L.ec3d_set_preconditioner(self.h, PRECOND[kind], pre, post, coarse_sweeps),
+                 "ec3d_set_preconditioner")
+        except EC3DError:
+            self.set_precond_precision(before)   # a refusal leaves the handle unchanged, the setting included
+            raise
+
+    def set_precond_precision(self, precision: str = "fp64"):
+        """Precision of the V-cycle the next set_preconditioner("mg") builds: "fp64" (default) or "fp32" (M in single
+        precision, the outer iteration unchanged in fp64; "block-mg" is then refused).  Kept across assemblies and
+        set_preconditioner("none"); a hierarchy already set is not rebuilt."""
+        if precision not in PRECOND_PRECISION:
+            raise ValueError(f"precision must be one of {sorted(PRECOND_PRECISION)}, not {precision!r}")
+        _chk(self.L, self.L.ec3d_set_precond_precision(self.h, PRECOND_PRECISION[precision]),
+             "ec3d_set_precond_precision")
+
+    def precond_precision(self):
+        """(setting, in_use): the handle's setting and the precision of the hierarchy now set ("fp64" without one)."""
+        setting, in_use = C.c_int32(0), C.c_int32(0)
+        _chk(self.L, self.L.ec3d_get_precond_precision(self.h, C.byref(setting), C.byref(in_use)),
+             "ec3d_get_precond_precision")
+        name = {v: k for k, v in PRECOND_PRECISION.items()}
+        return name[setting.value], name[in_use.value]
 
     def preconditioner(self):
         """(kind, [(sdx, sdy, sdz) per level, finest first])"""

@@ -210,8 +210,25 @@ enum { EC3D_PRECOND_E_MATRIX = 20, EC3D_PRECOND_E_COARSE = 21 };
 int ec3d_set_preconditioner(ec3d_handle h, int kind, int32_t pre, int32_t post, int32_t coarse_sweeps);
 /* kind, number of levels, and (dims != NULL) sdx, sdy, sdz of every level, finest first (3*levels entries) */
 int ec3d_get_preconditioner(ec3d_handle h, int *kind, int32_t *levels, int32_t *dims /* 3*levels */);
-/* z = M r, one V-cycle on host vectors (H2D, apply, D2H).  Parity probe, like ec3d_spmv. */
+/* z = M r, one V-cycle on host vectors (H2D, apply, D2H).  Parity probe, like ec3d_spmv.  On an fp32 hierarchy r and z
+ * are doubles all the same: r is narrowed by the cycle, z widened exactly. */
 int ec3d_precond_apply(ec3d_handle h, const double *r, double *z);
+/* Precision of the V-cycle of EC3D_PRECOND_MG.  EC3D_PRECOND_FP64 (default): as above.  EC3D_PRECOND_FP32: M in single
+ * precision.  Every level's coefficients are its own fp64 rediscretisation narrowed once (round to nearest) at
+ * set-up; the right-hand side of an application is narrowed once; every level vector, product, difference and
+ * division of the cycle, the coarse solve included, is fp32 in the fp64 kernels' operation order; p^ and s^ are
+ * stored in fp32 and widened (exactly) where the outer iteration reads them.  The outer iteration -- A p^, the dot
+ * products, the scalars, s, x, r, p, the exits, the restart rule -- stays fp64, and forms v = A p^ and x += alpha p^
+ * from the same p^, so R = b - A x holds as before and the solve reaches the same true residual; only the
+ * iteration count may differ.  The hierarchy then holds fp32 vectors only.  The setting belongs to the handle and
+ * outlives new matrices and EC3D_PRECOND_NONE; it takes effect at the next ec3d_set_preconditioner and does not
+ * rebuild a hierarchy already set.  With EC3D_PRECOND_FP32 set, EC3D_PRECOND_BLOCK_MG is refused
+ * (EC3D_PRECOND_E_MATRIX, the handle unchanged).  An unknown value returns 2 and leaves the handle unchanged.
+ * ec3d_get_precond_precision: *setting = the handle's setting, *in_use = the precision of the hierarchy now set
+ * (EC3D_PRECOND_FP64 when there is none); either may be NULL. */
+enum { EC3D_PRECOND_FP64 = 0, EC3D_PRECOND_FP32 = 1 };
+int ec3d_set_precond_precision(ec3d_handle h, int32_t precision);
+int ec3d_get_precond_precision(ec3d_handle h, int32_t *setting, int32_t *in_use);
 
 /* ------------------------------------------------------------------------------------------
  * 2b. Multi-rank building blocks (z-slab decomposition, one process per GPU).

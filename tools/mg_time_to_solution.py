@@ -1,13 +1,14 @@
 """Time-to-solution of the bar-RHS Poisson solve (BASELINE config 2) with and without the multigrid preconditioner.
 
-    python tools/mg_time_to_solution.py [--sizes 256 512] [--tol 1e-8] [--fixed 200]
+    python tools/mg_time_to_solution.py [--sizes 256 512] [--tol 1e-8] [--fixed 200] [--precision fp64|fp32] [--mg-only]
 
 One JSON line per size: wall time of ec3d_solve_resident to `tol` with MG (after one untimed solve) and its outer
 iterations; the same without a preconditioner -- a full solve where --fixed is 0 or the size is <= 256, otherwise a
 fixed `--fixed` iterations (tol 1e-300) scaled by the reference's iteration count (tests/golden/g5_cube*.npz `iter`,
 or BASELINE.md section 2b's projection of 7 500 at 512^3), which the line says; and us per V-cycle, from
 ec3d_precond_apply minus ec3d_spmv (both move the same two host vectors; the split by level comes from a
-rocprofv3 --kernel-trace --stats run of this tool, profiles/mg_*.txt)."""
+rocprofv3 --kernel-trace --stats run of this tool, profiles/mg_*.txt).  --precision fp32: the V-cycle in single
+precision (ec3d_set_precond_precision); --mg-only leaves the unpreconditioned solve out."""
 from __future__ import annotations
 
 import argparse
@@ -37,11 +38,13 @@ def main():
     ap.add_argument("--sizes", type=int, nargs="+", default=[256, 512])
     ap.add_argument("--tol", type=float, default=1e-8)
     ap.add_argument("--fixed", type=int, default=200)
+    ap.add_argument("--precision", choices=["fp64", "fp32"], default="fp64")
+    ap.add_argument("--mg-only", action="store_true")
     a = ap.parse_args()
     import eddy_currents_3d_amd as E
     from bench import bar_rhs
     for N in a.sizes:
-        out = dict(N=N, tol=a.tol)
+        out = dict(N=N, tol=a.tol, precision=a.precision)
         b = bar_rhs(N)
         x0 = np.zeros(N ** 3)
         with E.EC3DSolver() as s:
@@ -55,6 +58,8 @@ def main():
                 it, _ = s.solve_resident(tol, itmax)
                 return time.perf_counter() - t, it
 
+            if a.precision == "fp32":   # (fp64 is the default: the tool then also runs on a library without the setter)
+                s.set_precond_precision("fp32")
             s.set_preconditioner("mg")
             out["levels"] = s.preconditioner()[1]
             solve()
@@ -65,6 +70,9 @@ def main():
             t_spmv, _ = timed(lambda: s.spmv(r), 3)
             out["us_per_vcycle"] = round(1e6 * (t_apply - t_spmv), 1)
             out["mg_us_per_outer_iteration"] = round(1e6 * out["mg_s"] / max(out["mg_iter"], 1), 1)
+            if a.mg_only:
+                print(json.dumps(out), flush=True)
+                continue
             s.set_preconditioner("none")
             if a.fixed and N > 256:
                 solve(1e-300, a.fixed - 1)
