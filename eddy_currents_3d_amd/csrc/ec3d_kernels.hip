@@ -22,7 +22,7 @@
 //     best for each (choose_sweep in ec3d_context.hip).
 // Built with -ffp-contract=off: products and sums are rounded separately, exactly as the
 // reference's x86-64 object code does; the oracle's "GPU order" twin reproduces every bit.
-#include "ec3d_internal.hpp"
+#include "ec3d_form.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -169,16 +169,7 @@ struct TailDev {
     const int32_t *tcol;
     const double *tval;
 };
-// Matrix formats the row kernel is specialised for (template parameter FMT):
-//   FMT_GENERIC  any number of bands, one fp64 stream per band
-//   FMT_DIA7     7 bands, unrolled (72 B/row: 56 coefficients + x + y)
-//   FMT_DICT7    7 bands whose coefficient 7-tuples take <= 256 distinct values ("stencil classes"):
-//                one class byte per row + a table staged in LDS (17 B/row: 1 + x + y).  The values
-//                multiplied are the same doubles, so results are bit-identical to FMT_DIA7.
-//   FMT_SAV      the structured A-V form (MatView::sav): class byte per row, U on the grid, no tail
-enum { FMT_GENERIC = 0, FMT_DIA7 = 7, FMT_DICT7 = 107, FMT_SAV = 207 };
-#define EC3D_SAV_STRIDE 16
-
+// One view per matrix format the row kernel is specialised for (template parameter FMT: FMT_* in ec3d_form.hpp)
 template <int FMT> struct MatDev;
 template <> struct MatDev<FMT_GENERIC> {
     const double *band[EC3D_MAXB];
@@ -772,8 +763,7 @@ struct ZRegs {
 // LDS staging of operands that would not fit the register budget while in flight: an LDS-DMA load
 // (global_load_lds_dwordx4) has no register destination.  Every thread fetches ITS OWN 16 bytes into its own
 // slot and reads nothing else back, so no barrier is involved -- LDS serves as spill space for loads in
-// flight.  One wave instruction writes 1 KiB at (wave-uniform base) + lane * 16.
-#define EC3D_NSTAGE 4 /* 16-byte slots per thread: 4 x 4 KiB per workgroup */
+// flight.  One wave instruction writes 1 KiB at (wave-uniform base) + lane * 16.  EC3D_NSTAGE (ec3d_form.hpp) slots per thread.
 __device__ __forceinline__ void stage_issue(const double *gp, double *stg, int k)
 {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)gp,
@@ -1225,8 +1215,8 @@ __device__ __forceinline__ void walk_zm_il(const MatDev<FMT_SAV> &A, const Sweep
 // is read (K2 inside K3, K5 inside K1: V is not VecPlain) all of them go through registers.  Same products, same
 // order as sav_pair_zm (bands ascending then U slots for A rows, A slots then bands for U rows = ascending columns =
 // the reference's row sum, src/solvers.f90:59 after src/EC3D.f90:715): A*x is bit-identical; the dot products are
-// summed in this thread -> cell assignment, which ec3d_geom::patch_* tells the oracle's twin.
-#define EC3D_NSTAGE_RT 2
+// summed in this thread -> cell assignment, which ec3d_geom::patch_* tells the oracle's twin.  EC3D_NSTAGE_RT (ec3d_form.hpp)
+// staging slots.
 template <class V>
 __device__ __forceinline__ void sav_patch_step(const MatDev<FMT_SAV> &A, const SweepZ &sw, const double *tbl,
                                                double *lds, int step, const V &x, const PatchPos &pp, bool first,
@@ -2696,16 +2686,17 @@ __global__ __launch_bounds__(EC3D_THREADS) void k5_p_update(SweepV sw, RedSrc sr
 }
 
 // ---------------------------------------------------------------------------------------------
-// launchers
-static inline int fmt_of(const MatView &A)
-{
-    if (A.sav) return FMT_SAV;
-    if (A.nb == 7 && A.ncls > 0) return FMT_DICT7;
-    if (A.nb == 7) return FMT_DIA7;
-    return FMT_GENERIC;
-}
+// launchers.  Which instance of an SpMV-type kernel a launch runs: ec3d_spmv_form (ec3d_form.hpp) says it, launch_form
+// below turns it into template arguments; DESIGN.md section 12 has the rule and the instances of every kernel family.
 // streaming policy: vectors of >= 32 MiB each (n_pad >= 4 Mi rows) cannot live in the caches
 static inline bool nt_of(const Sweep &sw) { return (sw.nt & 1) != 0; }
+// run-time bools as compile-time tags: f(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ...)
+template <bool... Bs, class F> static inline void tag_bools(F &&f) { f(std::bool_constant<Bs>{}...); }
+template <bool... Bs, class F, class... R> static inline void tag_bools(F &&f, bool b, R... rest)
+{
+    if (b) tag_bools<Bs..., true>(f, rest...);
+    else tag_bools<Bs..., false>(f, rest...);
+}
 
 static inline TailDev tail_of(const MatView &A) { return TailDev{A.tail_id, A.tile_flag, A.chunk_ptr, A.tcol, A.tval}; }
 template <int FMT> static MatDev<FMT> mat_dev(const MatView &A);
@@ -2793,57 +2784,65 @@ static inline SweepZ sweep_z(const Sweep &sw)
     z.il_seg = sw.il_seg;
     return z;
 }
-// dynamic LDS: the class table (55 + 9 D classes of the structured form with D conducting domains: 64 classes =
-// 8 KiB for one domain, 253 = 31.6 KiB at D = 22, which with the staging slots caps the CU at 3 workgroups -- a cost
-// not measured) and, for the z-marching structured kernels, the
-// staging slots behind it (16 KiB): 24.6 KiB per workgroup, six of them fit a CU's 160 KiB
-static inline size_t tbl_bytes(const MatView &A, int F, bool zm, bool patch, bool il = false)
+// The instances each kernel family has: launch_form instantiates these and nothing else.
+// a form ec3d_spmv_form can return (15 of them for each cache policy, HS aside)
+static constexpr bool form_possible(const SpmvForm &f)
 {
-    // structured form, interleaved z-march: the table alone (walk_zm_il stages nothing)
-    if (il && F == FMT_SAV) return (size_t)A.ncls * EC3D_SAV_STRIDE * 8;
-    // structured form on runtime-shaped 2-D tiles: table, two exchange buffers, two staging slots (sav_patch_step)
-    if (patch && F == FMT_SAV) return (size_t)A.ncls * EC3D_SAV_STRIDE * 8 + (size_t)(2 + EC3D_NSTAGE_RT) * EC3D_TILE * 8;
-    if (patch) return (size_t)((F == FMT_DICT7 ? A.ncls * 7 + 1 : 0) & ~1) * 8 + (size_t)2 * EC3D_TILE * 8;
-    if (F == FMT_DICT7) return (size_t)A.ncls * 7 * 8;
-    if (F == FMT_SAV) return (size_t)A.ncls * EC3D_SAV_STRIDE * 8 + (zm ? (size_t)EC3D_NSTAGE * EC3D_TILE * 8 : 0);
-    return 0;
+    const bool table = f.fmt == FMT_DICT7 || f.fmt == FMT_SAV;
+    return (!f.tail || f.fmt != FMT_SAV) && (!f.zm || f.fmt != FMT_GENERIC) && (!f.patch || (f.zm && !f.tail && table)) &&
+           (!f.il || (f.zm && !f.patch && f.fmt == FMT_SAV)) && (!f.hs || f.fmt == FMT_DICT7);
 }
-#define EC3D_LAUNCH_ZT(F, NT_, KERNEL, ...)                                                                         \
-    do {                                                                                                            \
-        const bool tail_ = F != FMT_SAV && A.has_tail;                                                              \
-        const bool patch_ = zm_ && !tail_ && ((sw.patch_npx > 0 && F == FMT_DICT7) || (sw.rp_px > 0 && F == FMT_SAV)); /* choose_sweep */ \
-        const size_t lds_ = tbl_bytes(A, F, zm_, patch_, zm_ && !patch_ && sw.il_planes > 0);                       \
-        const MatDev<F> Ad = mat_dev<F>(A);                                                                         \
-        if constexpr (F != FMT_GENERIC) {                                                                           \
-            if (zm_) {                                                                                              \
-                const SweepZ swz = sweep_z(sw);                                                                     \
-                if (patch_) { if constexpr (F == FMT_DICT7 || F == FMT_SAV) KERNEL<F, NT_, true, false, true><<<sw.nblk, EC3D_THREADS, lds_, s>>>(Ad, swz, __VA_ARGS__); } \
-                else if (tail_) { if constexpr (F != FMT_SAV) KERNEL<F, NT_, true, true, false><<<sw.nblk, EC3D_THREADS, lds_, s>>>(Ad, swz, __VA_ARGS__); } \
-                else if (F == FMT_SAV && sw.il_planes > 0) { if constexpr (F == FMT_SAV) KERNEL<F, NT_, true, true, false><<<sw.nblk, EC3D_THREADS, lds_, s>>>(Ad, swz, __VA_ARGS__); } /* interleaved z-march: EC3D_IL */ \
-                else KERNEL<F, NT_, true, false, false><<<sw.nblk, EC3D_THREADS, lds_, s>>>(Ad, swz, __VA_ARGS__);   \
-                break;                                                                                              \
-            }                                                                                                       \
-        }                                                                                                           \
-        if (tail_) { if constexpr (F != FMT_SAV) KERNEL<F, NT_, false, true, false><<<sw.nblk, EC3D_THREADS, lds_, s>>>(Ad, sw, __VA_ARGS__); } \
-        else KERNEL<F, NT_, false, false, false><<<sw.nblk, EC3D_THREADS, lds_, s>>>(Ad, sw, __VA_ARGS__);           \
-    } while (0)
-#define EC3D_LAUNCH_FMT(F, KERNEL, ...)                                                        \
-    do {                                                                                       \
-        const bool zm_ = sw.zm_tpp > 0 && sw.bnd_last < 0 && F != FMT_GENERIC;                 \
-        if (nt_of(sw))                                                                         \
-            EC3D_LAUNCH_ZT(F, true, KERNEL, __VA_ARGS__);                                      \
-        else                                                                                   \
-            EC3D_LAUNCH_ZT(F, false, KERNEL, __VA_ARGS__);                                     \
-    } while (0)
-#define EC3D_DISPATCH(A, KERNEL, ...)                                                          \
-    do {                                                                                       \
-        switch (fmt_of(A)) {                                                                   \
-        case FMT_SAV: EC3D_LAUNCH_FMT(FMT_SAV, KERNEL, __VA_ARGS__); break;                    \
-        case FMT_DICT7: EC3D_LAUNCH_FMT(FMT_DICT7, KERNEL, __VA_ARGS__); break;                \
-        case FMT_DIA7: EC3D_LAUNCH_FMT(FMT_DIA7, KERNEL, __VA_ARGS__); break;                  \
-        default: EC3D_LAUNCH_FMT(FMT_GENERIC, KERNEL, __VA_ARGS__);                            \
-        }                                                                                      \
-    } while (0)
+struct SpmvFamily { // k_spmv, k_residual, k1_spmv_dot, k3_spmv_dots: every form, no HS
+    static constexpr bool hs = false;
+    static constexpr bool has(const SpmvForm &f) { return form_possible(f) && !f.hs; }
+};
+struct FusedFamily { // k23_s_spmv_dots, k51_p_spmv_dot: the 2-D-tile kernels only (ec3d_fused23, ec3d_fused51)
+    static constexpr bool hs = true;
+    static constexpr bool has(const SpmvForm &f) { return form_possible(f) && f.zm && f.patch && !f.tail; }
+};
+struct K4sFamily { // k4s_x_r_spmv: the dictionary cube on 2-D tiles (ec3d_k4s), each with NEMAX = 0 and 4
+    static constexpr bool hs = false;
+    static constexpr bool has(const SpmvForm &f) { return FusedFamily::has(f) && f.fmt == FMT_DICT7 && !f.hs; }
+};
+template <int FMT_, bool NT_, bool ZM_, bool TAIL_, bool PATCH_, bool HS_> struct FormTag { // the kernels' template arguments
+    static constexpr int FMT = FMT_;
+    static constexpr bool NT = NT_, ZM = ZM_, TAIL = TAIL_, PATCH = PATCH_, HS = HS_;
+};
+// launch(FormTag, MatDev, sweep, LDS bytes) for the instance of FAMILY that the matrix and the sweep ask for
+template <class FAMILY, class LAUNCH>
+static void launch_form(const char *kernel, const MatView &A, const Sweep &sw, LAUNCH &&launch)
+{
+    SpmvForm f = ec3d_spmv_form(A, sw);
+    f.hs = f.hs && FAMILY::hs;
+    const size_t lds = ec3d_form_lds(A, f);
+    bool found = false;
+    auto with_fmt = [&](auto FMT) {
+        tag_bools([&](auto NT, auto ZM, auto TAIL, auto PATCH, auto IL, auto HS) {
+            constexpr SpmvForm cf{decltype(FMT)::value,   decltype(NT)::value, decltype(ZM)::value, decltype(TAIL)::value,
+                                  decltype(PATCH)::value, decltype(IL)::value, decltype(HS)::value};
+            if constexpr (FAMILY::has(cf)) {
+                // the kernels have no parameter of their own for the interleaved march: on the structured form, which has
+                // no tail, TAIL = true stands for it (EC3D_IL)
+                using T = FormTag<cf.fmt, cf.nt, cf.zm, cf.tail || cf.il, cf.patch, cf.hs>;
+                found = true;
+                if constexpr (cf.zm) launch(T{}, mat_dev<cf.fmt>(A), sweep_z(sw), lds);
+                else launch(T{}, mat_dev<cf.fmt>(A), sw, lds);
+            }
+        }, f.nt, f.zm, f.tail, f.patch, f.il, f.hs);
+    };
+    switch (f.fmt) {
+    case FMT_SAV: with_fmt(std::integral_constant<int, FMT_SAV>{}); break;
+    case FMT_DICT7: with_fmt(std::integral_constant<int, FMT_DICT7>{}); break;
+    case FMT_DIA7: with_fmt(std::integral_constant<int, FMT_DIA7>{}); break;
+    default: with_fmt(std::integral_constant<int, FMT_GENERIC>{});
+    }
+    if (!found) { // nothing is launched
+        char msg[160];
+        snprintf(msg, sizeof msg, "%s: no kernel instance for the form fmt=%d nt=%d zm=%d tail=%d patch=%d il=%d hs=%d", kernel,
+                 f.fmt, f.nt, f.zm, f.tail, f.patch, f.il, f.hs);
+        ec3d_set_error(msg);
+    }
+}
 static inline SweepV sweep_v(const Sweep &sw)
 {
     SweepV v;
@@ -2867,24 +2866,31 @@ static inline SweepV sweep_v(const Sweep &sw)
     }
     return v;
 }
-#define EC3D_LAUNCH_VEC(KERNEL, ...)                                                           \
-    do {                                                                                       \
-        const SweepV swv = sweep_v(sw);                                                        \
-        if (nt_of(sw))                                                                         \
-            KERNEL<true><<<sw.nblk, EC3D_THREADS, 0, s>>>(swv, __VA_ARGS__);                   \
-        else                                                                                   \
-            KERNEL<false><<<sw.nblk, EC3D_THREADS, 0, s>>>(swv, __VA_ARGS__);                  \
-    } while (0)
+static inline XRing x_ring(const double *const *p, const double *const *sv, int count)
+{
+    XRing ring{};
+    for (int j = 0; j < count; ++j) {
+        ring.p[j] = p[j];
+        ring.s[j] = sv[j];
+    }
+    return ring;
+}
 
 void ec3d_launch_spmv(const MatView &A, const Sweep &sw, const double *x, double *y, hipStream_t s)
 {
-    EC3D_DISPATCH(A, k_spmv, x, y);
+    launch_form<SpmvFamily>("k_spmv", A, sw, [&](auto t, const auto &Ad, const auto &swk, size_t lds) {
+        using T = decltype(t);
+        k_spmv<T::FMT, T::NT, T::ZM, T::TAIL, T::PATCH><<<sw.nblk, EC3D_THREADS, lds, s>>>(Ad, swk, x, y);
+    });
 }
 
 void ec3d_launch_residual(const MatView &A, const Sweep &sw, const double *x, const double *b, double *r,
                           double *r0, double *p, double *part, hipStream_t s)
 {
-    EC3D_DISPATCH(A, k_residual, x, b, r, r0, p, part);
+    launch_form<SpmvFamily>("k_residual", A, sw, [&](auto t, const auto &Ad, const auto &swk, size_t lds) {
+        using T = decltype(t);
+        k_residual<T::FMT, T::NT, T::ZM, T::TAIL, T::PATCH><<<sw.nblk, EC3D_THREADS, lds, s>>>(Ad, swk, x, b, r, r0, p, part);
+    });
 }
 
 void ec3d_launch_finalize(const RedSrc &src, double *lsum, unsigned mask, hipStream_t s)
@@ -2905,84 +2911,60 @@ void ec3d_launch_setup(SolverState *st, const RedSrc &src, double tol, hipStream
 void ec3d_launch_k1(const MatView &A, const Sweep &sw, const SolverState *st, int it, const double *p,
                     const double *r0, double *ap, double *part, hipStream_t s)
 {
-    EC3D_DISPATCH(A, k1_spmv_dot, st, it, p, r0, ap, part);
+    launch_form<SpmvFamily>("k1_spmv_dot", A, sw, [&](auto t, const auto &Ad, const auto &swk, size_t lds) {
+        using T = decltype(t);
+        k1_spmv_dot<T::FMT, T::NT, T::ZM, T::TAIL, T::PATCH><<<sw.nblk, EC3D_THREADS, lds, s>>>(Ad, swk, st, it, p, r0, ap, part);
+    });
 }
 
 void ec3d_launch_k2(const Sweep &sw, const RedSrc &src, SolverState *st, int it, const double *r, const double *ap,
                     double *sv, double *part, hipStream_t s)
 {
-    EC3D_LAUNCH_VEC(k2_s_update, src, st, it, r, ap, sv, part);
+    tag_bools([&](auto NT) {
+        k2_s_update<decltype(NT)::value><<<sw.nblk, EC3D_THREADS, 0, s>>>(sweep_v(sw), src, st, it, r, ap, sv, part);
+    }, nt_of(sw));
 }
 
 void ec3d_launch_k3(const MatView &A, const Sweep &sw, SolverState *st, int it, const double *sv, double *as,
                     double *part, hipStream_t s)
 {
-    EC3D_DISPATCH(A, k3_spmv_dots, st, it, sv, as, part);
+    launch_form<SpmvFamily>("k3_spmv_dots", A, sw, [&](auto t, const auto &Ad, const auto &swk, size_t lds) {
+        using T = decltype(t);
+        k3_spmv_dots<T::FMT, T::NT, T::ZM, T::TAIL, T::PATCH><<<sw.nblk, EC3D_THREADS, lds, s>>>(Ad, swk, st, it, sv, as, part);
+    });
 }
 
+// HS: a z-slab running the three-launch iteration, where S (K2 inside K3) and the new P (K5 inside K1) are also stored on
+// the halo planes
 void ec3d_launch_k23(const MatView &A, const Sweep &sw, const RedSrc &src, SolverState *st, int it, const double *r,
                      const double *ap, double *sv, double *as, double *part, hipStream_t s)
 {
-    // the 2-D-tile kernels only (ec3d_fused23): dictionary cube and structured A-V form, one instance per cache policy
-    const SweepZ swz = sweep_z(sw);
-    if (A.sav) {
-        const MatDev<FMT_SAV> Ad = mat_dev<FMT_SAV>(A);
-        const size_t lds = tbl_bytes(A, FMT_SAV, true, true);
-        if (nt_of(sw))
-            k23_s_spmv_dots<FMT_SAV, true, true, false, true><<<sw.nblk, EC3D_THREADS, lds, s>>>(Ad, swz, src, st, it, r, ap, sv, as, part);
-        else
-            k23_s_spmv_dots<FMT_SAV, false, true, false, true><<<sw.nblk, EC3D_THREADS, lds, s>>>(Ad, swz, src, st, it, r, ap, sv, as, part);
-        return;
-    }
-    const MatDev<FMT_DICT7> Ad = mat_dev<FMT_DICT7>(A);
-    const size_t lds = tbl_bytes(A, FMT_DICT7, true, true);
-    if (sw.halo_store) { // a z-slab running the three-launch iteration: S is also stored on the halo planes
-        if (nt_of(sw))
-            k23_s_spmv_dots<FMT_DICT7, true, true, false, true, true><<<sw.nblk, EC3D_THREADS, lds, s>>>(Ad, swz, src, st, it, r, ap, sv, as, part);
-        else
-            k23_s_spmv_dots<FMT_DICT7, false, true, false, true, true><<<sw.nblk, EC3D_THREADS, lds, s>>>(Ad, swz, src, st, it, r, ap, sv, as, part);
-        return;
-    }
-    if (nt_of(sw))
-        k23_s_spmv_dots<FMT_DICT7, true, true, false, true><<<sw.nblk, EC3D_THREADS, lds, s>>>(Ad, swz, src, st, it, r, ap, sv, as, part);
-    else
-        k23_s_spmv_dots<FMT_DICT7, false, true, false, true><<<sw.nblk, EC3D_THREADS, lds, s>>>(Ad, swz, src, st, it, r, ap, sv, as, part);
+    launch_form<FusedFamily>("k23_s_spmv_dots", A, sw, [&](auto t, const auto &Ad, const auto &swk, size_t lds) {
+        using T = decltype(t);
+        k23_s_spmv_dots<T::FMT, T::NT, T::ZM, T::TAIL, T::PATCH, T::HS><<<sw.nblk, EC3D_THREADS, lds, s>>>(
+            Ad, swk, src, st, it, r, ap, sv, as, part);
+    });
 }
 
 void ec3d_launch_k51(const MatView &A, const Sweep &sw, const RedSrc &src, SolverState *st, int it, const double *r,
                      const double *p_old, const double *ap_old, double *p_new, double *ap_new, double *r0, double *part,
                      double *hist, int64_t hist_cap, hipStream_t s)
 {
-    const SweepZ swz = sweep_z(sw);
-    if (A.sav) {
-        const MatDev<FMT_SAV> Ad = mat_dev<FMT_SAV>(A);
-        const size_t lds = tbl_bytes(A, FMT_SAV, true, true);
-        if (nt_of(sw))
-            k51_p_spmv_dot<FMT_SAV, true, true, false, true><<<sw.nblk, EC3D_THREADS, lds, s>>>(Ad, swz, src, st, it, r, p_old, ap_old, p_new, ap_new, r0, part, hist, hist_cap);
-        else
-            k51_p_spmv_dot<FMT_SAV, false, true, false, true><<<sw.nblk, EC3D_THREADS, lds, s>>>(Ad, swz, src, st, it, r, p_old, ap_old, p_new, ap_new, r0, part, hist, hist_cap);
-        return;
-    }
-    const MatDev<FMT_DICT7> Ad = mat_dev<FMT_DICT7>(A);
-    const size_t lds = tbl_bytes(A, FMT_DICT7, true, true);
-    if (sw.halo_store) { // a z-slab running the three-launch iteration: the new P is also stored on the halo planes
-        if (nt_of(sw))
-            k51_p_spmv_dot<FMT_DICT7, true, true, false, true, true><<<sw.nblk, EC3D_THREADS, lds, s>>>(Ad, swz, src, st, it, r, p_old, ap_old, p_new, ap_new, r0, part, hist, hist_cap);
-        else
-            k51_p_spmv_dot<FMT_DICT7, false, true, false, true, true><<<sw.nblk, EC3D_THREADS, lds, s>>>(Ad, swz, src, st, it, r, p_old, ap_old, p_new, ap_new, r0, part, hist, hist_cap);
-        return;
-    }
-    if (nt_of(sw))
-        k51_p_spmv_dot<FMT_DICT7, true, true, false, true><<<sw.nblk, EC3D_THREADS, lds, s>>>(Ad, swz, src, st, it, r, p_old, ap_old, p_new, ap_new, r0, part, hist, hist_cap);
-    else
-        k51_p_spmv_dot<FMT_DICT7, false, true, false, true><<<sw.nblk, EC3D_THREADS, lds, s>>>(Ad, swz, src, st, it, r, p_old, ap_old, p_new, ap_new, r0, part, hist, hist_cap);
+    launch_form<FusedFamily>("k51_p_spmv_dot", A, sw, [&](auto t, const auto &Ad, const auto &swk, size_t lds) {
+        using T = decltype(t);
+        k51_p_spmv_dot<T::FMT, T::NT, T::ZM, T::TAIL, T::PATCH, T::HS><<<sw.nblk, EC3D_THREADS, lds, s>>>(
+            Ad, swk, src, st, it, r, p_old, ap_old, p_new, ap_new, r0, part, hist, hist_cap);
+    });
 }
 
 void ec3d_launch_k4(const Sweep &sw, const RedSrc &src_ss, const RedSrc &src, SolverState *st, int it,
                     const double *p, const double *sv, const double *as, const double *r0, double *x, double *r,
                     double *part, double *hist, int64_t hist_cap, hipStream_t s)
 {
-    EC3D_LAUNCH_VEC(k4_x_r_update, src_ss, src, st, it, p, sv, as, r0, x, r, part, hist, hist_cap);
+    tag_bools([&](auto NT) {
+        k4_x_r_update<decltype(NT)::value><<<sw.nblk, EC3D_THREADS, 0, s>>>(sweep_v(sw), src_ss, src, st, it, p, sv, as, r0, x, r, part,
+                                                                          hist, hist_cap);
+    }, nt_of(sw));
 }
 
 // K4 of an iteration whose X update is deferred (ne = 0) or which applies ne >= 2 pending updates; p[j], sv[j]: the
@@ -2995,11 +2977,7 @@ void ec3d_launch_k4d(const Sweep &sw, const RedSrc &src_ss, const RedSrc &src, S
         ec3d_launch_k4(sw, src_ss, src, st, it, p[0], sv[0], as, r0, x, r, part, hist, hist_cap, s);
         return;
     }
-    XRing ring{};
-    for (int j = 0; j < (ne > 0 ? std::min(ne, EC3D_XD_MAX) : 1); ++j) {
-        ring.p[j] = p[j];
-        ring.s[j] = sv[j];
-    }
+    const XRing ring = x_ring(p, sv, ne > 0 ? std::min(ne, EC3D_XD_MAX) : 1);
     SweepV swv = sweep_v(sw);
     {   // tiles in flight per wave: the launch without X has 4 streams, the applying one 7 + 4 (ne - 1) -- not K4's 7.
         // Big grids (vector plan of two tiles in flight, nothing cached; 512^3, profiles/r04_deferred_x_512.log): without X
@@ -3011,20 +2989,18 @@ void ec3d_launch_k4d(const Sweep &sw, const RedSrc &src_ss, const RedSrc &src, S
         const int want = ne == 0 ? (off_env > 0 ? off_env : big ? 4 : 1) : (on_env > 0 ? on_env : big ? (ne == 2 ? 2 : 1) : 2);
         if (swv.win_nt == 0) swv.two = (want == 2 || want == 4) ? want : 1;
     }
-#define EC3D_K4D(NE)                                                                                                         \
-    do {                                                                                                                     \
-        if (nt_of(sw))                                                                                                       \
-            k4d_x_r_update<true, NE><<<sw.nblk, EC3D_THREADS, 0, s>>>(swv, src_ss, src, st, it, xm, ring, as, r0, x, r, part, hist, hist_cap); \
-        else                                                                                                                 \
-            k4d_x_r_update<false, NE><<<sw.nblk, EC3D_THREADS, 0, s>>>(swv, src_ss, src, st, it, xm, ring, as, r0, x, r, part, hist, hist_cap); \
-    } while (0)
+    auto launch = [&](auto NE) {
+        tag_bools([&](auto NT) {
+            k4d_x_r_update<decltype(NT)::value, decltype(NE)::value><<<sw.nblk, EC3D_THREADS, 0, s>>>(
+                swv, src_ss, src, st, it, xm, ring, as, r0, x, r, part, hist, hist_cap);
+        }, nt_of(sw));
+    };
     switch (ne) {
-    case 0: EC3D_K4D(0); break;
-    case 2: EC3D_K4D(2); break;
-    case 3: EC3D_K4D(3); break;
-    default: EC3D_K4D(4); break;
+    case 0: launch(std::integral_constant<int, 0>{}); break;
+    case 2: launch(std::integral_constant<int, 2>{}); break;
+    case 3: launch(std::integral_constant<int, 3>{}); break;
+    default: launch(std::integral_constant<int, 4>{}); break;
     }
-#undef EC3D_K4D
 }
 
 // K4 in SpMV form (k4s_x_r_spmv): dictionary cube on 2-D tiles.  ne = 0: X left alone; 1 .. 4: that many updates applied
@@ -3032,24 +3008,14 @@ void ec3d_launch_k4s(const MatView &A, const Sweep &sw, const RedSrc &src_ss, co
                      int ne, int xm, const double *const *p, const double *const *sv, const double *r0, double *x, double *r,
                      double *part, double *hist, int64_t hist_cap, hipStream_t s)
 {
-    XRing ring{};
-    for (int j = 0; j < (ne > 0 ? ne : 1); ++j) {
-        ring.p[j] = p[j];
-        ring.s[j] = sv[j];
-    }
-    const SweepZ swz = sweep_z(sw);
-    const MatDev<FMT_DICT7> Ad = mat_dev<FMT_DICT7>(A);
-    const size_t lds = tbl_bytes(A, FMT_DICT7, true, true);
-#define EC3D_K4S(NT_, NE_) \
-    k4s_x_r_spmv<FMT_DICT7, NT_, NE_><<<sw.nblk, EC3D_THREADS, lds, s>>>(Ad, swz, src_ss, src, st, it, ne, xm, ring, r0, x, r, part, hist, hist_cap)
-    if (nt_of(sw)) {
-        if (ne == 0) EC3D_K4S(true, 0);
-        else EC3D_K4S(true, 4);
-    } else {
-        if (ne == 0) EC3D_K4S(false, 0);
-        else EC3D_K4S(false, 4);
-    }
-#undef EC3D_K4S
+    const XRing ring = x_ring(p, sv, ne > 0 ? ne : 1);
+    launch_form<K4sFamily>("k4s_x_r_spmv", A, sw, [&](auto t, const auto &Ad, const auto &swk, size_t lds) {
+        using T = decltype(t);
+        tag_bools([&](auto APPLY) { // NEMAX: 0 leaves X alone, 4 applies up to four updates
+            k4s_x_r_spmv<T::FMT, T::NT, decltype(APPLY)::value ? 4 : 0><<<sw.nblk, EC3D_THREADS, lds, s>>>(
+                Ad, swk, src_ss, src, st, it, ne, xm, ring, r0, x, r, part, hist, hist_cap);
+        }, ne != 0);
+    });
 }
 
 // A GROUP of X updates -- iterations first .. first + count - 1 -- applied by a launch of its own on a second stream, beside
@@ -3111,11 +3077,7 @@ __global__ __launch_bounds__(EC3D_THREADS) void k_x_group(SweepV sw, const Solve
 void ec3d_launch_x_group(const Sweep &sw, const SolverState *st, const double *const *p, const double *const *sv, int first,
                          int count, int d2, double *x, int nblk, hipStream_t s)
 {
-    XRing ring{};
-    for (int j = 0; j < EC3D_XD_MAX; ++j) {
-        ring.p[j] = p[j];
-        ring.s[j] = sv[j];
-    }
+    const XRing ring = x_ring(p, sv, EC3D_XD_MAX);
     SweepV swv = sweep_v(sw);
     // fewer workgroups than the iteration's kernels when asked for (a smaller share of the bandwidth while they run);
     // the tile walk is a stride over whatever grid it is given
@@ -3130,16 +3092,14 @@ void ec3d_launch_x_group(const Sweep &sw, const SolverState *st, const double *c
 void ec3d_launch_x_flush(const Sweep &sw, const SolverState *st, const double *const *p, const double *const *sv,
                          double *x, hipStream_t s)
 {
-    XRing ring{};
-    for (int j = 0; j < EC3D_XD_MAX; ++j) {
-        ring.p[j] = p[j];
-        ring.s[j] = sv[j];
-    }
+    const XRing ring = x_ring(p, sv, EC3D_XD_MAX);
     k_x_flush<<<sw.nblk, EC3D_THREADS, 0, s>>>(sweep_v(sw), st, ring, x);
 }
 
 void ec3d_launch_k5(const Sweep &sw, const RedSrc &src, SolverState *st, int it, const double *r, const double *ap,
                     const double *p_old, double *p, double *r0, double *hist, int64_t hist_cap, hipStream_t s)
 {
-    EC3D_LAUNCH_VEC(k5_p_update, src, st, it, r, ap, p_old, p, r0, hist, hist_cap);
+    tag_bools([&](auto NT) {
+        k5_p_update<decltype(NT)::value><<<sw.nblk, EC3D_THREADS, 0, s>>>(sweep_v(sw), src, st, it, r, ap, p_old, p, r0, hist, hist_cap);
+    }, nt_of(sw));
 }
