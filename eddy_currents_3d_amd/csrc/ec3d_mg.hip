@@ -25,10 +25,14 @@
 // EC3D_PRECOND_BLOCK_MG (the structured A-V form) shares the outer iteration's vector kernels;
 // its own kernels (k_avmg_*) are below, behind the single-component ones.
 //
+// Host side: a handle's ec3d_mg owns one hierarchy (PoissonMg<double>, PoissonMg<float> or BlockMg), built completely
+// before it replaces the old one; launch_schedule is the cycle's order of launches for all three.
+//
 // A row of a level is read from the level's own device format: class byte + coefficient table in LDS (dictionary form,
 // what every coarse level uses) or the seven band streams (ec3d_set_format(h, 0)).  Bands in offset order
 // (-z, -y, -x, diag, +x, +y, +z); a neighbour beyond the box contributes nothing (its coefficient is 0 there anyway).
 #include "../../include/ec3d_hip.h"
+#include "ec3d_avmg_plan.hpp"
 #include "ec3d_internal.hpp"
 
 #include <array>
@@ -36,6 +40,8 @@
 #include <cmath>
 #include <cstring>
 #include <memory>
+#include <type_traits>
+#include <variant>
 
 #define EC3D_MG_COARSE_ROWS 4096 // x of the coarsest level in LDS (32 KiB), b and class bytes in registers
 #define EC3D_MG_COARSE_THREADS 1024
@@ -53,22 +59,6 @@ template <class T> struct MgOpT {
 };
 using MgOp = MgOpT<double>;
 using MgOp32 = MgOpT<float>;
-
-struct MgLevel {
-    DevMatrix A;          // level 0: unused (the handle's matrix)
-    MgOp op;
-    int f[3] = {1, 1, 1}; // coarsening factor towards the next level per axis (1 or 2)
-    double delta[3] = {0, 0, 0};
-    double *x = nullptr, *w = nullptr, *b = nullptr; // coarse levels: inside ec3d_mg::vec_base
-    // EC3D_PRECOND_FP32: then only level 0's fp64 operator above is still read (by the outer SpMV + dot launch, from the
-    // handle's matrix); a coarse level's A keeps owning its class bytes, which op32 shares, and its fp64 class table
-    // (7 doubles per class, a few hundred bytes) stays allocated unread -- coarse levels are always in dictionary form, so
-    // no fp64 band stream is kept beside an fp32 one.  The level's coefficients narrowed once (the table, or level 0's seven band streams under
-    // ec3d_set_format(h, 0)) and its vectors, inside ec3d_mg::vec32; x, w, b above stay null
-    MgOp32 op32{};
-    DevBuf<float> coef32;
-    float *x32 = nullptr, *w32 = nullptr, *b32 = nullptr;
-};
 
 struct MgScalars {
     double beta;
@@ -95,32 +85,63 @@ struct AvLevel {
     AvOp op;
     int f[3] = {1, 1, 1};     // aggregate width towards the next level per axis (1 or 2)
     DevBuf<double> bands;     // coarse levels
-    double *x = nullptr, *w = nullptr, *b = nullptr; // coarse levels: inside ec3d_mg::vec_base, 3 blocks each
+    double *x = nullptr, *w = nullptr, *b = nullptr; // coarse levels: inside BlockMg::vec, 3 blocks each
 };
 
+// ---- the hierarchies: a handle's ec3d_mg holds exactly one of PoissonMg<double>, PoissonMg<float>, BlockMg ---------------
+
+// A level of the hierarchy of the single-component operator (EC3D_PRECOND_MG): what does not depend on the cycle's precision
+struct MgGrid {
+    DevMatrix A;          // the level's assembled matrix (level 0: unused, the handle's own)
+    int f[3] = {1, 1, 1}; // coarsening factor towards the next level per axis (1 or 2)
+    double delta[3] = {0, 0, 0};
+};
+// ... and what does (the kernels' T is deduced from these)
+template <class T> struct MgLevelT {
+    MgOpT<T> op{};        // double: the level's own device format; float: its class bytes and the narrowed coefficients
+    T *x = nullptr, *w = nullptr, *b = nullptr; // coarse levels: inside PoissonMg::vec
+};
+// float: every level's coefficients narrowed once at set-up -- the class table, or the seven band streams of level 0
+// under ec3d_set_format(h, 0) (coarse levels are always in dictionary form)
+template <class T> struct MgNarrowed {};
+template <> struct MgNarrowed<float> {
+    std::vector<DevBuf<float>> coef;
+};
+// T: the precision of every vector and operation of the cycle.  float (EC3D_PRECOND_FP32): there is no fp64 vector, and
+// of the fp64 operators only op0 is read.
+template <class T> struct PoissonMg : MgNarrowed<T> {
+    std::vector<MgGrid> grid;
+    MgOp op0{};           // level 0 in fp64, from the handle's matrix: what the outer SpMV + dot launch reads
+    std::vector<MgLevelT<T>> lev;
+    DevBuf<T> vec;        // coarse x, w, b per level, then the fine w, [b0,] p^, s^
+    T *w0 = nullptr, *ph = nullptr, *sh = nullptr;
+    T *b0 = nullptr;      // float: the fine right-hand side narrowed; double: null, the cycle reads r itself
+};
+
+// The block hierarchy of the structured A-V form (EC3D_PRECOND_BLOCK_MG): one hierarchy for the three A blocks, and the
+// U block's rows with the projection of their right-hand side onto the U block's range (ec3d_avmg_plan.hpp)
+struct BlockMg {
+    std::vector<AvLevel> lev;
+    AvOp uop{};                 // the U block's rows (class form, no hierarchy)
+    DevBuf<double> vec;         // coarse x, w, b per level, then the fine w (3 blocks each), p^, s^ with their halos
+    double *w0 = nullptr, *ph = nullptr, *sh = nullptr;
+    DevBuf<int32_t> ulist;      // AvmgPlan's ured, then ublack
+    int64_t nu_red = 0, nu_black = 0;
+    DevBuf<int32_t> uidx;       // AvmgPlan's ucomp, plist, chunks, cco
+    const int32_t *ucomp = nullptr, *plist = nullptr, *chunks = nullptr, *cco = nullptr;
+    DevBuf<double> ubuf;        // AvmgPlan's pw, inv_w, then umean (one per component) and upart (one per chunk)
+    double *pw = nullptr, *inv_w = nullptr, *umean = nullptr, *upart = nullptr;
+    int ncomp = 0, nchunk = 0;
+};
+
+// What ec3d_ctx::mg points to: the settings and the outer iteration's scratch, which every kind has, and the hierarchy
 struct ec3d_mg {
     int kind = EC3D_PRECOND_MG;
+    int precision = EC3D_PRECOND_FP64; // EC3D_PRECOND_FP32: kind EC3D_PRECOND_MG only
     int pre = 2, post = 2, coarse = 16;
-    std::vector<MgLevel> lev;
-    std::vector<AvLevel> av;    // EC3D_PRECOND_BLOCK_MG: the A blocks' hierarchy
-    AvOp uop{};                 // ... and the U block's rows (class form, no hierarchy)
-    DevBuf<int32_t> ulist;      // U-block rows that hold an unknown: the red ones, then the black ones
-    int64_t nu_red = 0, nu_black = 0;
-    // Projection of the U right-hand side onto the range of the U block (one null vector per conducting component):
-    // ucomp[e] = component of ulist[e]; plist = the U rows ordered by component, pw their weights; chunks = [lo, hi)
-    // of each chunk of plist (within one component), cco = first chunk of each component; upart / umean / inv_w
-    int32_t *ucomp = nullptr, *plist = nullptr, *chunks = nullptr, *cco = nullptr; // inside uidx
-    double *pw = nullptr, *inv_w = nullptr, *upart = nullptr, *umean = nullptr;    // inside ubuf
-    DevBuf<int32_t> uidx;
-    DevBuf<double> ubuf;
-    int ncomp = 0, nchunk = 0;
-    DevBuf<double> vec_base;    // coarse x, w, b per level, then the fine w, p^, s^
-    double *w0 = nullptr, *ph = nullptr, *sh = nullptr;
-    int precision = EC3D_PRECOND_FP64; // EC3D_PRECOND_FP32 (kind EC3D_PRECOND_MG only): vec_base stays empty, and
-    DevBuf<float> vec32;        // coarse x, w, b per level, then the fine w, the fine right-hand side's copy, p^, s^
-    float *w0_32 = nullptr, *b0_32 = nullptr, *ph32 = nullptr, *sh32 = nullptr;
     DevBuf<double> part;        // 2 * EC3D_MG_DOT_BLOCKS
     DevBuf<MgScalars> scal;
+    std::variant<PoissonMg<double>, PoissonMg<float>, BlockMg> h;
 };
 
 namespace {
@@ -548,83 +569,83 @@ MgOp op_of(const DevMatrix &A, int sdx, int sdy, int sdz)
     return o;
 }
 
-#define MG_LAUNCH(kern, grid, block, ...)                                                                          \
+// kern<DICT> on operator A (the kernel's first argument): the class form when A has class bytes, else the band form
+#define MG_LAUNCH(kern, grid, block, A, ...)                                                                       \
     do {                                                                                                           \
-        if (dict) kern<true><<<(grid), (block), 0, s>>>(__VA_ARGS__);                                             \
-        else kern<false><<<(grid), (block), 0, s>>>(__VA_ARGS__);                                                 \
+        if ((A).cls) kern<true><<<(grid), (block), 0, s>>>(A, __VA_ARGS__);                                       \
+        else kern<false><<<(grid), (block), 0, s>>>(A, __VA_ARGS__);                                              \
     } while (0)
 
-// a level's operator and vectors in the precision T of the hierarchy (the kernels' T is deduced from them)
-template <class T> struct LevelOf;
-template <> struct LevelOf<double> {
-    const MgOp &op;
-    double *x, *w, *b;
-    explicit LevelOf(const MgLevel &l) : op(l.op), x(l.x), w(l.w), b(l.b) {}
-};
-template <> struct LevelOf<float> {
-    const MgOp32 &op;
-    float *x, *w, *b;
-    explicit LevelOf(const MgLevel &l) : op(l.op32), x(l.x32), w(l.w32), b(l.b32) {}
-};
-// the fine level's w, and the right-hand side its launches read: fp64 r itself, fp32 the copy the init half-sweep writes
-inline double *fine_w(const ec3d_mg *m, double) { return m->w0; }
-inline float *fine_w(const ec3d_mg *m, float) { return m->w0_32; }
-inline const double *fine_b(const ec3d_mg *, const double *r, double) { return r; }
-inline const float *fine_b(const ec3d_mg *m, const double *, float) { return m->b0_32; }
-// the fine level's first half-sweep (red, from x = 0)
-inline void launch_fine_init(ec3d_mg *m, const MgOp &A, Gate g, const double *r, double *w, hipStream_t s)
+// the fine level's first half-sweep (red, from x = 0); fp32: it also narrows r into b0
+inline void launch_fine_init(const PoissonMg<double> &h, Gate g, const double *r, hipStream_t s)
 {
-    const bool dict = A.cls != nullptr;
-    MG_LAUNCH(k_mg_smooth, blocks_of(A.n), 256, A, g, 0, 1, w, r);
+    const MgOp &A = h.lev[0].op;
+    MG_LAUNCH(k_mg_smooth, blocks_of(A.n), 256, A, g, 0, 1, h.w0, r);
 }
-inline void launch_fine_init(ec3d_mg *m, const MgOp32 &A, Gate g, const double *r, float *w, hipStream_t s)
+inline void launch_fine_init(const PoissonMg<float> &h, Gate g, const double *r, hipStream_t s)
 {
-    const bool dict = A.cls != nullptr;
-    MG_LAUNCH(k_mg_init_f32, blocks_of(A.n), 256, A, g, r, m->b0_32, w);
+    const MgOp32 &A = h.lev[0].op;
+    MG_LAUNCH(k_mg_init_f32, blocks_of(A.n), 256, A, g, r, h.b0, h.w0);
+}
+
+// The V-cycle's launch schedule from x = 0, for either kernel family (k_mg_* in the hierarchy's precision, k_avmg_*).
+// The family's launches on level l: smooth(l, colour, init, post) a half-sweep, on w before the coarse correction and on
+// x behind it (post); restrict_(l) the right-hand side of level l + 1; coarse() the coarsest level's solve; prolong(l)
+// x = w + the correction, fused with the first post half-sweep (black).
+template <class S, class R, class C, class P>
+void launch_schedule(int L, int pre, int post, const S &smooth, const R &restrict_, const C &coarse, const P &prolong)
+{
+    for (int l = 0; l + 1 < L; ++l) {
+        for (int sw = 0; sw < pre; ++sw) {
+            smooth(l, 0, sw == 0, false);
+            smooth(l, 1, 0, false);
+        }
+        restrict_(l);
+    }
+    coarse();
+    for (int l = L - 2; l >= 0; --l) {
+        prolong(l);
+        smooth(l, 0, 0, true);
+        for (int sw = 1; sw < post; ++sw) {
+            smooth(l, 1, 0, true);
+            smooth(l, 0, 0, true);
+        }
+    }
 }
 
 // one V-cycle z = M r (enqueued).  T = float (EC3D_PRECOND_FP32): r stays fp64; the fine level's init half-sweep narrows
-// it into b0_32 (k_mg_init_f32), or the coarse solve does on load when the hierarchy has one level.
-template <class T> void launch_vcycle(ec3d_mg *m, Gate g, const double *r, T *z, hipStream_t s)
+// it into b0 (k_mg_init_f32), or the coarse solve does on load when the hierarchy has one level.
+template <class T>
+void launch_cycle(const ec3d_mg &m, const PoissonMg<T> &h, Gate g, const double *r, T *z, hipStream_t s)
 {
-    const int L = (int)m->lev.size();
-    const T *B0 = fine_b(m, r, T());
-    T *W0 = fine_w(m, T());
-    for (int l = 0; l + 1 < L; ++l) {
-        const LevelOf<T> F(m->lev[(size_t)l]), C(m->lev[(size_t)l + 1]);
-        const int *f = m->lev[(size_t)l].f;
-        const auto &A = F.op;
-        const bool dict = A.cls != nullptr;
-        const T *B = l == 0 ? B0 : F.b;
-        T *W = l == 0 ? W0 : F.w;
-        for (int sw = 0; sw < m->pre; ++sw) {
-            if (l == 0 && sw == 0) launch_fine_init(m, A, g, r, W, s);
-            else MG_LAUNCH(k_mg_smooth, blocks_of(A.n), 256, A, g, 0, sw == 0, W, B);
-            MG_LAUNCH(k_mg_smooth, blocks_of(A.n), 256, A, g, 1, 0, W, B);
-        }
-        MG_LAUNCH(k_mg_restrict, blocks_of(C.op.n), 256, A, C.op, f[0], f[1], f[2], g, W, B, C.b);
-    }
-    {
-        const LevelOf<T> K(m->lev[(size_t)L - 1]);
-        const bool dict = K.op.cls != nullptr;
-        if (L == 1) MG_LAUNCH(k_mg_coarse, 1, EC3D_MG_COARSE_THREADS, K.op, g, m->coarse, r, z);
-        else MG_LAUNCH(k_mg_coarse, 1, EC3D_MG_COARSE_THREADS, K.op, g, m->coarse, K.b, K.x);
-    }
-    for (int l = L - 2; l >= 0; --l) {
-        const LevelOf<T> F(m->lev[(size_t)l]), C(m->lev[(size_t)l + 1]);
-        const int *f = m->lev[(size_t)l].f;
-        const auto &A = F.op;
-        const bool dict = A.cls != nullptr;
-        const T *B = l == 0 ? B0 : F.b;
-        T *W = l == 0 ? W0 : F.w;
-        T *X = l == 0 ? z : F.x;
-        MG_LAUNCH(k_mg_prolong, blocks_of(A.n), 256, A, C.op, f[0], f[1], f[2], g, W, C.x, B, X);
-        MG_LAUNCH(k_mg_smooth, blocks_of(A.n), 256, A, g, 0, 0, X, B);
-        for (int sw = 1; sw < m->post; ++sw) {
-            MG_LAUNCH(k_mg_smooth, blocks_of(A.n), 256, A, g, 1, 0, X, B);
-            MG_LAUNCH(k_mg_smooth, blocks_of(A.n), 256, A, g, 0, 0, X, B);
-        }
-    }
+    const int L = (int)h.lev.size();
+    const auto &lev = h.lev;
+    const T *b0 = h.b0; // the fine right-hand side: float the narrowed copy, double r itself
+    if constexpr (std::is_same_v<T, double>) b0 = r;
+    const auto B = [&](int l) { return l ? (const T *)lev[l].b : b0; };
+    const auto W = [&](int l, bool post = false) { return post ? (l ? lev[l].x : z) : (l ? lev[l].w : h.w0); };
+    launch_schedule(
+        L, m.pre, m.post,
+        [&](int l, int colour, int init, bool post) {
+            const MgOpT<T> &A = lev[l].op;
+            if (l == 0 && init) launch_fine_init(h, g, r, s);
+            else MG_LAUNCH(k_mg_smooth, blocks_of(A.n), 256, A, g, colour, init, W(l, post), B(l));
+        },
+        [&](int l) {
+            const MgOpT<T> &A = lev[l].op, &C = lev[l + 1].op;
+            const int *f = h.grid[(size_t)l].f;
+            MG_LAUNCH(k_mg_restrict, blocks_of(C.n), 256, A, C, f[0], f[1], f[2], g, W(l), B(l), lev[l + 1].b);
+        },
+        [&] {
+            const MgLevelT<T> &K = lev[L - 1];
+            if (L == 1) MG_LAUNCH(k_mg_coarse, 1, EC3D_MG_COARSE_THREADS, K.op, g, m.coarse, r, z);
+            else MG_LAUNCH(k_mg_coarse, 1, EC3D_MG_COARSE_THREADS, K.op, g, m.coarse, K.b, K.x);
+        },
+        [&](int l) {
+            const MgOpT<T> &A = lev[l].op, &C = lev[l + 1].op;
+            const int *f = h.grid[(size_t)l].f;
+            MG_LAUNCH(k_mg_prolong, blocks_of(A.n), 256, A, C, f[0], f[1], f[2], g, W(l), lev[l + 1].x, B(l), W(l, true));
+        });
 }
 
 // fp64 -> fp32, round to nearest: a level's coefficients at set-up
@@ -919,7 +940,6 @@ __global__ __launch_bounds__(256) void k_avmg_usweep(AvOp U, Gate g, const int32
 // b - (w.b / w.1) on each component, which lies in the U block's range.  The weighted sums run in a fixed order:
 // chunks of EC3D_AVMG_UCHUNK entries of one component (thread t adds entries t, t + 256, ..., then the workgroup
 // tree), then per component the chunks' partials as k_mg_scalar sums them.
-#define EC3D_AVMG_UCHUNK 4096
 __global__ __launch_bounds__(256) void k_avmg_upart(Gate g, const int32_t *__restrict__ plist,
                                                     const double *__restrict__ pw, const int32_t *__restrict__ chunks,
                                                     const double *__restrict__ b, double *__restrict__ upart)
@@ -967,54 +987,43 @@ __global__ __launch_bounds__(256) void k_avmg_dot(int64_t n, Gate g, const doubl
 
 // z = M r of the block multigrid (enqueued): one V-cycle on each A block, the U block's sweeps.  r, z: device vectors
 // of the structured form (4 blocks of nCd rows).
-void launch_avcycle(ec3d_mg *m, Gate g, const double *r, double *z, hipStream_t s)
+void launch_cycle(const ec3d_mg &m, const BlockMg &h, Gate g, const double *r, double *z, hipStream_t s)
 {
-    const int L = (int)m->av.size();
-    for (int l = 0; l + 1 < L; ++l) {
-        AvLevel &F = m->av[(size_t)l];
-        const AvOp &A = F.op;
-        const bool dict = l == 0;
-        const double *B = l == 0 ? r : F.b;
-        double *W = l == 0 ? m->w0 : F.w;
-        for (int sw = 0; sw < m->pre; ++sw) {
-            MG_LAUNCH(k_avmg_smooth, blocks_of(A.n), 256, A, g, 0, sw == 0, W, B);
-            MG_LAUNCH(k_avmg_smooth, blocks_of(A.n), 256, A, g, 1, 0, W, B);
-        }
-        const AvLevel &C = m->av[(size_t)l + 1];
-        MG_LAUNCH(k_avmg_restrict, blocks_of(C.op.n), 256, A, C.op, F.f[0], F.f[1], F.f[2], g, W, B, C.b);
+    const int L = (int)h.lev.size();
+    const auto &lev = h.lev;
+    const auto B = [&](int l) -> const double * { return l ? lev[l].b : r; };
+    const auto W = [&](int l, bool post = false) { return post ? (l ? lev[l].x : z) : (l ? lev[l].w : h.w0); };
+    launch_schedule(
+        L, m.pre, m.post,
+        [&](int l, int colour, int init, bool post) {
+            const AvOp &A = lev[l].op;
+            MG_LAUNCH(k_avmg_smooth, blocks_of(A.n), 256, A, g, colour, init, W(l, post), B(l));
+        },
+        [&](int l) {
+            const AvLevel &F = lev[l], &C = lev[l + 1];
+            MG_LAUNCH(k_avmg_restrict, blocks_of(C.op.n), 256, F.op, C.op, F.f[0], F.f[1], F.f[2], g, W(l), B(l), C.b);
+        },
+        [&] {
+            const AvLevel &K = lev[L - 1];
+            MG_LAUNCH(k_avmg_coarse, 3, EC3D_MG_COARSE_THREADS, K.op, g, m.coarse, L == 1 ? r : K.b, L == 1 ? z : K.x);
+        },
+        [&](int l) {
+            const AvLevel &F = lev[l], &C = lev[l + 1];
+            MG_LAUNCH(k_avmg_prolong, blocks_of(F.op.n), 256, F.op, C.op, F.f[0], F.f[1], F.f[2], g, W(l), C.x, B(l),
+                      W(l, true));
+        });
+    const int64_t ub = 3 * h.lev[0].op.vs; // the U block
+    if (h.ncomp) {
+        k_avmg_upart<<<(unsigned)h.nchunk, 256, 0, s>>>(g, h.plist, h.pw, h.chunks, r + ub, h.upart);
+        k_avmg_umean<<<(unsigned)h.ncomp, 256, 0, s>>>(g, h.cco, h.upart, h.inv_w, h.umean);
     }
-    {
-        AvLevel &K = m->av[(size_t)L - 1];
-        const bool dict = L == 1;
-        MG_LAUNCH(k_avmg_coarse, 3, EC3D_MG_COARSE_THREADS, K.op, g, m->coarse, L == 1 ? r : K.b, L == 1 ? z : K.x);
-    }
-    for (int l = L - 2; l >= 0; --l) {
-        AvLevel &F = m->av[(size_t)l];
-        const AvOp &A = F.op;
-        const bool dict = l == 0;
-        const double *B = l == 0 ? r : F.b;
-        double *W = l == 0 ? m->w0 : F.w;
-        double *X = l == 0 ? z : F.x;
-        const AvLevel &C = m->av[(size_t)l + 1];
-        MG_LAUNCH(k_avmg_prolong, blocks_of(A.n), 256, A, C.op, F.f[0], F.f[1], F.f[2], g, W, C.x, B, X);
-        MG_LAUNCH(k_avmg_smooth, blocks_of(A.n), 256, A, g, 0, 0, X, B);
-        for (int sw = 1; sw < m->post; ++sw) {
-            MG_LAUNCH(k_avmg_smooth, blocks_of(A.n), 256, A, g, 1, 0, X, B);
-            MG_LAUNCH(k_avmg_smooth, blocks_of(A.n), 256, A, g, 0, 0, X, B);
-        }
-    }
-    const int64_t ub = 3 * m->av[0].op.vs; // the U block
-    if (m->ncomp) {
-        k_avmg_upart<<<(unsigned)m->nchunk, 256, 0, s>>>(g, m->plist, m->pw, m->chunks, r + ub, m->upart);
-        k_avmg_umean<<<(unsigned)m->ncomp, 256, 0, s>>>(g, m->cco, m->upart, m->inv_w, m->umean);
-    }
-    for (int sw = 0; sw < m->pre + m->post; ++sw) {
-        if (m->nu_red)
-            k_avmg_usweep<<<blocks_of(m->nu_red), 256, 0, s>>>(m->uop, g, m->ulist, m->ucomp, m->umean, m->nu_red,
-                                                                sw == 0, z + ub, r + ub);
-        if (m->nu_black)
-            k_avmg_usweep<<<blocks_of(m->nu_black), 256, 0, s>>>(m->uop, g, m->ulist + m->nu_red, m->ucomp + m->nu_red,
-                                                                  m->umean, m->nu_black, 0, z + ub, r + ub);
+    for (int sw = 0; sw < m.pre + m.post; ++sw) {
+        if (h.nu_red)
+            k_avmg_usweep<<<blocks_of(h.nu_red), 256, 0, s>>>(h.uop, g, h.ulist, h.ucomp, h.umean, h.nu_red, sw == 0,
+                                                               z + ub, r + ub);
+        if (h.nu_black)
+            k_avmg_usweep<<<blocks_of(h.nu_black), 256, 0, s>>>(h.uop, g, h.ulist + h.nu_red, h.ucomp + h.nu_red, h.umean,
+                                                                 h.nu_black, 0, z + ub, r + ub);
     }
 }
 
@@ -1055,250 +1064,226 @@ static std::vector<std::array<int, 3>> avmg_dims(int sdx, int sdy, int sdz)
     return dims;
 }
 
-static int set_block_mg(ec3d_ctx *c, int32_t pre, int32_t post, int32_t coarse_sweeps)
+static inline int64_t pad64(int64_t n) { return (n + 63) / 64 * 64; }
+
+// a handle of its own: not a slab, a rank or a handle of ec3d_multi
+static bool own_handle(const ec3d_ctx *c) { return !(c->in_multi || c->halo > 0 || c->nranks > 1 || c->dist); }
+
+// a matrix or setting the preconditioner is not built for; a failure of the runtime during set-up.  Either way the new
+// hierarchy is dropped and the handle stays as it was
+static int mg_refuse(const std::string &text, int code = EC3D_PRECOND_E_MATRIX) { ec3d_set_error(text); return code; }
+static int mg_fail(const char *what)
+{
+    (void)hipGetLastError();
+    return mg_refuse(std::string("ec3d_set_preconditioner: ") + what, 100);
+}
+static const char *const MG_OOM = "out of device memory for the hierarchy", *const MG_BUILD = "building the hierarchy failed";
+
+// The coarse vectors of a hierarchy inside its vector block: x, w, b per level in level order, each `blocks` vectors of
+// the level's rows rounded up to 64.  Returns where they end: the fine vectors begin there.
+template <class T, class LEVEL> static T *carve_vectors(T *q, std::vector<LEVEL> &lev, int blocks)
+{
+    for (size_t l = 1; l < lev.size(); ++l) {
+        const int64_t len = blocks * pad64(lev[l].op.n);
+        lev[l].x = q; lev[l].w = q + len; lev[l].b = q + 2 * len;
+        q += 3 * len;
+    }
+    return q;
+}
+
+// Both set-ups fill a new ec3d_mg, which ec3d_set_preconditioner puts in the old one's place when they return 0.
+static int set_block_mg(ec3d_ctx *c, ec3d_mg &m)
 {
     const DevMatrix &A = c->A;
-    if (!A.sav || c->in_multi || c->halo > 0 || c->nranks > 1 || c->dist) {
-        ec3d_set_error("ec3d_set_preconditioner: the block multigrid preconditioner needs the structured A-V form "
-                       "(ec3d_assemble) on a handle of its own (not Poisson, bands + tail, a slab or a handle of "
-                       "ec3d_multi)");
-        return EC3D_PRECOND_E_MATRIX;
-    }
+    if (!A.sav || !own_handle(c))
+        return mg_refuse("ec3d_set_preconditioner: the block multigrid preconditioner needs the structured A-V form "
+                         "(ec3d_assemble) on a handle of its own (not Poisson, bands + tail, a slab or a handle of "
+                         "ec3d_multi)");
     const int sdx = (int)A.sav_step[1], pitch = (int)A.sav_step[2];
     const int sdy = (int)(c->plane / sdx), sdz = (int)(A.sav_nC / pitch);
     const int64_t nCd = A.sav_nC;
     const int a_hi = A.sav_u0, u_lo = A.sav_u0, u_hi = A.sav_zero; // A rows: classes [0, u0); U rows: [u0, zero)
-    if (a_hi > EC3D_AVMG_MAXCLS || u_hi - u_lo > EC3D_AVMG_MAXCLS) {
-        ec3d_set_error("ec3d_set_preconditioner: more classes than the block smoothers' table holds (at most 4 "
-                       "conducting domains)");
-        return EC3D_PRECOND_E_MATRIX;
-    }
-    // the three A blocks must have the same 7 band coefficients in every row (src/EC3D.f90: valY = valX, valZ = valX)
+    if (a_hi > EC3D_AVMG_MAXCLS || u_hi - u_lo > EC3D_AVMG_MAXCLS)
+        return mg_refuse("ec3d_set_preconditioner: more classes than the block smoothers' table holds (at most 4 "
+                         "conducting domains)");
     std::vector<uint8_t> cls((size_t)(4 * nCd));
     std::vector<double> tab((size_t)A.ncls * 16);
     EC3D_HIP(hipMemcpyAsync(cls.data(), A.cls, cls.size(), hipMemcpyDeviceToHost, c->stream));
     EC3D_HIP(hipMemcpyAsync(tab.data(), A.table, tab.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     EC3D_HIP(hipStreamSynchronize(c->stream));
-    const auto bands_of = [&](int k, int lo, int hi, double (&b)[7]) { // what the smoothers read for class k
-        const bool in = k >= lo && k < hi;
-        for (int q = 0; q < 7; ++q) b[q] = in ? tab[(size_t)k * 16 + q] : 0.0;
-        if (in) return true;
-        for (int q = 0; q < 7; ++q) // a class outside the range is only allowed without band coefficients
-            if (tab[(size_t)k * 16 + q] != 0.0) return false;
-        return true;
-    };
-    std::vector<int32_t> ured, ublack;
-    for (int64_t r = 0; r < nCd; ++r) {
-        double b0[7], b1[7], b2[7], bu[7];
-        if (!bands_of(cls[(size_t)r], 0, a_hi, b0) || !bands_of(cls[(size_t)(nCd + r)], 0, a_hi, b1) ||
-            !bands_of(cls[(size_t)(2 * nCd + r)], 0, a_hi, b2) || memcmp(b0, b1, sizeof b0) || memcmp(b0, b2, sizeof b0)) {
-            ec3d_set_error("ec3d_set_preconditioner: the band coefficients of the Ax, Ay, Az rows of device cell " +
-                           std::to_string(r) + " differ: one hierarchy cannot serve the three blocks");
-            return EC3D_PRECOND_E_MATRIX;
-        }
-        const int ku = cls[(size_t)(3 * nCd + r)];
-        if (!bands_of(ku, u_lo, u_hi, bu)) {
-            ec3d_set_error("ec3d_set_preconditioner: a U row outside the U classes has band coefficients");
-            return EC3D_PRECOND_E_MATRIX;
-        }
-        if (ku >= u_lo && ku < u_hi) {
-            const int64_t ij = r % pitch;
-            const int i = (int)(ij % sdx), j = (int)(ij / sdx), k = (int)(r / pitch);
-            (((i + j + k) & 1) ? ublack : ured).push_back((int32_t)r);
-        }
-    }
-    // the U block's conducting components (U rows joined across a face) in order of their first row, and the weights
-    // of the U rows' left null vector (k_avmg_upart)
-    std::vector<int32_t> comp_of((size_t)nCd, -1), plist, chunks, cco, ucomp;
-    std::vector<double> pw, inv_w;
-    {
-        std::vector<char> is_u((size_t)nCd, 0);
-        for (int32_t r : ured) is_u[(size_t)r] = 1;
-        for (int32_t r : ublack) is_u[(size_t)r] = 1;
-        std::vector<int32_t> stack;
-        int nc = 0;
-        for (int64_t r0 = 0; r0 < nCd; ++r0) {
-            if (!is_u[(size_t)r0] || comp_of[(size_t)r0] >= 0) continue;
-            comp_of[(size_t)r0] = nc;
-            stack.assign(1, (int32_t)r0);
-            while (!stack.empty()) {
-                const int64_t r = stack.back();
-                stack.pop_back();
-                const int64_t ij = r % pitch;
-                const int i = (int)(ij % sdx), j = (int)(ij / sdx), k = (int)(r / pitch);
-                const int64_t nb[6] = {k > 0 ? r - pitch : -1, j > 0 ? r - sdx : -1, i > 0 ? r - 1 : -1,
-                                       i + 1 < sdx ? r + 1 : -1, j + 1 < sdy ? r + sdx : -1,
-                                       k + 1 < sdz ? r + pitch : -1};
-                for (int64_t q : nb)
-                    if (q >= 0 && is_u[(size_t)q] && comp_of[(size_t)q] < 0) {
-                        comp_of[(size_t)q] = nc;
-                        stack.push_back((int32_t)q);
-                    }
-            }
-            ++nc;
-        }
-        std::vector<std::vector<int32_t>> rows((size_t)nc);
-        for (int64_t r = 0; r < nCd; ++r)
-            if (comp_of[(size_t)r] >= 0) rows[(size_t)comp_of[(size_t)r]].push_back((int32_t)r);
-        for (int cc = 0; cc < nc; ++cc) {
-            cco.push_back((int32_t)(chunks.size() / 2));
-            const int32_t lo = (int32_t)plist.size();
-            double wsum = 0.0;
-            for (int32_t r : rows[(size_t)cc]) {
-                const double *t = &tab[(size_t)cls[(size_t)(3 * nCd + r)] * 16];
-                double w = 1.0;
-                for (int d = 0; d < 3; ++d)
-                    if (t[2 - d] == 0.0 || t[4 + d] == 0.0) w *= 0.5;
-                plist.push_back(r);
-                pw.push_back(w);
-                wsum += w;
-            }
-            const int32_t hi = (int32_t)plist.size();
-            for (int32_t e = lo; e < hi; e += EC3D_AVMG_UCHUNK) {
-                chunks.push_back(e);
-                chunks.push_back(std::min<int32_t>(hi, e + EC3D_AVMG_UCHUNK));
-            }
-            inv_w.push_back(1.0 / wsum);
-        }
-        cco.push_back((int32_t)(chunks.size() / 2));
-        for (int32_t r : ured) ucomp.push_back(comp_of[(size_t)r]);
-        for (int32_t r : ublack) ucomp.push_back(comp_of[(size_t)r]);
-    }
+    AvmgPlan p;
+    const std::string refusal =
+        ec3d_avmg_plan(sdx, sdy, sdz, pitch, nCd, cls.data(), tab.data(), a_hi, u_lo, u_hi, EC3D_AVMG_UCHUNK, p);
+    if (!refusal.empty()) return mg_refuse(refusal);
     const std::vector<std::array<int, 3>> dims = avmg_dims(sdx, sdy, sdz);
     const int L = (int)dims.size();
-    // build the new hierarchy completely before the old one is replaced: a failure leaves the handle as it was
-    std::unique_ptr<ec3d_mg> m(new ec3d_mg);
-    m->kind = EC3D_PRECOND_BLOCK_MG;
-    m->pre = pre ? pre : 2;
-    m->post = post ? post : 2;
-    m->coarse = coarse_sweeps ? coarse_sweeps : 16;
-    m->av.resize((size_t)L);
-    const auto oom = [&](const char *what) {
-        (void)hipGetLastError();
-        ec3d_set_error(std::string("ec3d_set_preconditioner: ") + what);
-        return 100;
-    };
-    AvOp &A0 = m->av[0].op;
+    BlockMg &h = m.h.emplace<BlockMg>();
+    h.lev.resize((size_t)L);
+    AvOp &A0 = h.lev[0].op;
     A0 = AvOp{};
     A0.sdx = sdx; A0.sdy = sdy; A0.sdz = sdz;
     A0.kdz = pitch;
-    A0.n = nCd;
-    A0.vs = nCd;
-    A0.cls = A.cls; // block 0's classes serve all three blocks (checked above)
+    A0.n = A0.vs = nCd;
+    A0.cls = A.cls; // block 0's classes serve all three blocks (the plan checked it)
     A0.table = A.table;
-    A0.cls0 = 0;
-    A0.ncls = a_hi;
-    m->uop = A0;
-    m->uop.cls = A.cls + 3 * nCd;
-    m->uop.cls0 = u_lo;
-    m->uop.ncls = u_hi - u_lo;
+    A0.cls0 = 0; A0.ncls = a_hi;
+    h.uop = A0;
+    h.uop.cls = A.cls + 3 * nCd;
+    h.uop.cls0 = u_lo; h.uop.ncls = u_hi - u_lo;
     int64_t coarse_len = 0;
     for (int l = 1; l < L; ++l) {
-        AvLevel &P = m->av[(size_t)l - 1], &Q = m->av[(size_t)l];
+        AvLevel &P = h.lev[(size_t)l - 1], &Q = h.lev[(size_t)l];
         for (int a = 0; a < 3; ++a) P.f[a] = dims[(size_t)l - 1][a] > 1 ? 2 : 1;
         AvOp &o = Q.op;
         o = AvOp{};
         o.sdx = dims[(size_t)l][0]; o.sdy = dims[(size_t)l][1]; o.sdz = dims[(size_t)l][2];
         o.kdz = (int64_t)o.sdx * o.sdy;
         o.n = o.kdz * o.sdz;
-        o.n_pad = (o.n + 63) / 64 * 64;
-        o.vs = o.n_pad;
-        if (Q.bands.alloc((size_t)7 * o.n_pad) != hipSuccess)
-            return oom("out of device memory for the hierarchy");
+        o.vs = o.n_pad = pad64(o.n);
+        if (Q.bands.alloc((size_t)7 * o.n_pad) != hipSuccess) return mg_fail(MG_OOM);
         o.bands = Q.bands;
         coarse_len += 9 * o.n_pad;
     }
     // p^ and s^ are read by the format's SpMV, which may read the zero halo around a vector (ec3d_prepare_vectors)
-    const int64_t nf = c->ghost + (A.n_pad + 63) / 64 * 64 + c->ghost;
+    const int64_t nf = c->ghost + pad64(A.n_pad) + c->ghost;
     const int64_t total = coarse_len + 3 * nCd + 2 * nf;
-    if (m->vec_base.alloc((size_t)total) != hipSuccess || m->part.alloc(2 * EC3D_MG_DOT_BLOCKS) != hipSuccess ||
-        m->scal.alloc(1) != hipSuccess || m->ulist.alloc(std::max<size_t>(1, ured.size() + ublack.size())) != hipSuccess)
-        return oom("out of device memory for the hierarchy");
-    m->nu_red = (int64_t)ured.size();
-    m->nu_black = (int64_t)ublack.size();
-    if (hipMemsetAsync(m->vec_base, 0, (size_t)total * sizeof(double), c->stream) != hipSuccess ||
-        hipMemsetAsync(m->scal, 0, sizeof(MgScalars), c->stream) != hipSuccess ||
-        (m->nu_red && hipMemcpyAsync(m->ulist, ured.data(), ured.size() * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess) ||
-        (m->nu_black && hipMemcpyAsync(m->ulist + m->nu_red, ublack.data(), ublack.size() * 4, hipMemcpyHostToDevice,
-                                       c->stream) != hipSuccess))
-        return oom("building the hierarchy failed");
-    m->ncomp = (int)inv_w.size();
-    m->nchunk = (int)(chunks.size() / 2);
+    h.nu_red = (int64_t)p.ured.size(); h.nu_black = (int64_t)p.ublack.size();
+    if (h.vec.alloc((size_t)total) != hipSuccess || m.part.alloc(2 * EC3D_MG_DOT_BLOCKS) != hipSuccess ||
+        m.scal.alloc(1) != hipSuccess || h.ulist.alloc(std::max<size_t>(1, p.ured.size() + p.ublack.size())) != hipSuccess)
+        return mg_fail(MG_OOM);
+    if (hipMemsetAsync(h.vec, 0, (size_t)total * sizeof(double), c->stream) != hipSuccess ||
+        hipMemsetAsync(m.scal, 0, sizeof(MgScalars), c->stream) != hipSuccess ||
+        (h.nu_red && hipMemcpyAsync(h.ulist, p.ured.data(), p.ured.size() * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess) ||
+        (h.nu_black && hipMemcpyAsync(h.ulist + h.nu_red, p.ublack.data(), p.ublack.size() * 4, hipMemcpyHostToDevice,
+                                      c->stream) != hipSuccess))
+        return mg_fail(MG_BUILD);
+    h.ncomp = (int)p.inv_w.size(); h.nchunk = (int)(p.chunks.size() / 2);
     {
-        const size_t nu = plist.size(), ni = 2 * nu + chunks.size() + cco.size(), nd = nu + 2 * inv_w.size() + chunks.size() / 2;
-        if (m->uidx.alloc(std::max<size_t>(1, ni)) != hipSuccess || m->ubuf.alloc(std::max<size_t>(1, nd)) != hipSuccess)
-            return oom("out of device memory for the hierarchy");
-        m->ucomp = m->uidx;
-        m->plist = m->ucomp + nu;
-        m->chunks = m->plist + nu;
-        m->cco = m->chunks + chunks.size();
-        m->pw = m->ubuf;
-        m->inv_w = m->pw + nu;
-        m->umean = m->inv_w + inv_w.size();
-        m->upart = m->umean + inv_w.size();
-        std::vector<int32_t> hi;
-        hi.insert(hi.end(), ucomp.begin(), ucomp.end());
-        hi.insert(hi.end(), plist.begin(), plist.end());
-        hi.insert(hi.end(), chunks.begin(), chunks.end());
-        hi.insert(hi.end(), cco.begin(), cco.end());
-        std::vector<double> hd;
-        hd.insert(hd.end(), pw.begin(), pw.end());
-        hd.insert(hd.end(), inv_w.begin(), inv_w.end());
-        hd.resize(nd, 0.0);
-        if (hipMemcpy(m->uidx, hi.data(), hi.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(m->ubuf, hd.data(), hd.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
-            return oom("building the hierarchy failed");
+        std::vector<int32_t> hi(p.ucomp);
+        hi.insert(hi.end(), p.plist.begin(), p.plist.end());
+        hi.insert(hi.end(), p.chunks.begin(), p.chunks.end());
+        hi.insert(hi.end(), p.cco.begin(), p.cco.end());
+        std::vector<double> hd(p.pw);
+        hd.insert(hd.end(), p.inv_w.begin(), p.inv_w.end());
+        hd.resize(hd.size() + (size_t)h.ncomp + (size_t)h.nchunk, 0.0); // umean, upart
+        if (h.uidx.alloc(std::max<size_t>(1, hi.size())) != hipSuccess || h.ubuf.alloc(std::max<size_t>(1, hd.size())) != hipSuccess)
+            return mg_fail(MG_OOM);
+        const size_t nu = p.plist.size();
+        h.ucomp = h.uidx; h.plist = h.ucomp + nu; h.chunks = h.plist + nu; h.cco = h.chunks + p.chunks.size();
+        h.pw = h.ubuf; h.inv_w = h.pw + nu; h.umean = h.inv_w + h.ncomp; h.upart = h.umean + h.ncomp;
+        if (hipMemcpy(h.uidx, hi.data(), hi.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(h.ubuf, hd.data(), hd.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+            return mg_fail(MG_BUILD);
     }
-    double *q = m->vec_base;
-    for (int l = 1; l < L; ++l) {
-        AvLevel &Q = m->av[(size_t)l];
-        const int64_t len = 3 * Q.op.n_pad;
-        Q.x = q; Q.w = q + len; Q.b = q + 2 * len;
-        q += 3 * len;
-    }
-    m->w0 = q; m->ph = q + 3 * nCd + c->ghost; m->sh = q + 3 * nCd + nf + c->ghost;
+    h.w0 = carve_vectors(h.vec.get(), h.lev, 3);
+    h.ph = h.w0 + 3 * nCd + c->ghost;
+    h.sh = h.ph + nf;
     // the Galerkin levels, finest first, on the device
     for (int l = 1; l < L; ++l) {
-        const AvLevel &P = m->av[(size_t)l - 1];
-        AvLevel &Q = m->av[(size_t)l];
+        const AvLevel &P = h.lev[(size_t)l - 1];
+        AvLevel &Q = h.lev[(size_t)l];
         const double scale = 1.0 / (2.0 * P.f[0] * P.f[1] * P.f[2]);
         hipStream_t s = c->stream;
-        const bool dict = l == 1;
         MG_LAUNCH(k_avmg_galerkin, blocks_of(Q.op.n), 256, P.op, Q.op, P.f[0], P.f[1], P.f[2], scale, Q.bands);
     }
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
-        ec3d_set_error("ec3d_set_preconditioner: building the hierarchy failed");
-        return 100;
-    }
-    ec3d_mg_free(c);
-    c->mg = m.release();
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return mg_fail(MG_BUILD);
     return 0;
 }
 
-// One iteration of the right-preconditioned BiCGSTAB with restart on the structured A-V form: ec3d_mg_launch_iteration's
-// algorithm, with M the block multigrid, v = A p^ and t = A s^ by the format's own SpMV (ec3d_launch_spmv), then their
-// dot partials (k_avmg_dot: the summation order of k_mg_spmv_dot).  The SpMV launches are not gated: past an exit
-// nothing reads what they write.
-static void avmg_launch_iteration(ec3d_ctx *c, int it)
+// T: the precision of the cycle (float: EC3D_PRECOND_FP32)
+template <class T> static int set_poisson_mg(ec3d_ctx *c, ec3d_mg &m)
 {
-    ec3d_mg *m = c->mg;
+    constexpr bool F32 = std::is_same_v<T, float>;
+    if (!c->poisson_full || !own_handle(c))
+        return mg_refuse("ec3d_set_preconditioner: the multigrid preconditioner needs a matrix from ec3d_assemble_poisson "
+                         "on a handle of its own (not A-V, CSR, a slab or a handle of ec3d_multi)");
+    std::vector<std::array<int, 3>> dims;
+    if (!mg_dims(c->sdx, c->sdy, c->sdz, dims)) {
+        const auto d = dims.back();
+        return mg_refuse("ec3d_set_preconditioner: no axis of the " + std::to_string(d[0]) + "x" + std::to_string(d[1]) +
+                         "x" + std::to_string(d[2]) + " level halves (even and >= 8) and it has more than " +
+                         std::to_string(EC3D_MG_COARSE_ROWS) + " rows, the coarse solver's cap", EC3D_PRECOND_E_COARSE);
+    }
+    if (c->A.ncls > EC3D_MG_MAXCLS)
+        return mg_refuse("ec3d_set_preconditioner: more dictionary classes than the smoother's table holds");
+    PoissonMg<T> &h = m.h.emplace<PoissonMg<T>>();
+    const int L = (int)dims.size();
+    h.grid.resize((size_t)L);
+    h.lev.resize((size_t)L);
+    std::vector<MgOp> op((size_t)L); // every level in fp64, as assembled
+    op[0] = h.op0 = op_of(c->A, c->sdx, c->sdy, c->sdz);
+    for (int a = 0; a < 3; ++a) h.grid[0].delta[a] = c->poisson_delta[a];
+    int64_t coarse_len = 0;
+    for (int l = 1; l < L; ++l) {
+        MgGrid &P = h.grid[(size_t)l - 1], &Q = h.grid[(size_t)l];
+        const auto &d = dims[(size_t)l];
+        for (int a = 0; a < 3; ++a) {
+            P.f[a] = dims[(size_t)l - 1][a] / d[a];
+            Q.delta[a] = P.delta[a] * P.f[a];
+        }
+        const int rc = ec3d_assemble_poisson_level(c, Q.A, d[0], d[1], d[2], c->poisson_bnd, Q.delta);
+        if (rc) return rc;
+        op[(size_t)l] = op_of(Q.A, d[0], d[1], d[2]);
+        coarse_len += 3 * pad64(op[(size_t)l].n);
+    }
+    const int64_t nf = pad64(c->A.n);
+    // double: the fine w, p^, s^; float: those and the fine right-hand side's copy
+    const int64_t total = coarse_len + (F32 ? 4 : 3) * nf;
+    if (h.vec.alloc((size_t)total) != hipSuccess || m.part.alloc(2 * EC3D_MG_DOT_BLOCKS) != hipSuccess ||
+        m.scal.alloc(1) != hipSuccess)
+        return mg_fail(MG_OOM);
+    if (hipMemsetAsync(h.vec, 0, (size_t)total * sizeof(T), c->stream) != hipSuccess ||
+        hipMemsetAsync(m.scal, 0, sizeof(MgScalars), c->stream) != hipSuccess)
+        return mg_fail("hipMemsetAsync failed");
+    if constexpr (F32) {
+        // the class table, or (level 0 in band form) the seven streams; a coarse level's A keeps owning the class bytes
+        h.coef.resize((size_t)L);
+        for (int l = 0; l < L; ++l) {
+            const MgOp &D = op[(size_t)l];
+            DevBuf<float> &coef = h.coef[(size_t)l];
+            const bool dict = D.cls != nullptr;
+            const int64_t len = dict ? (int64_t)D.ncls * 7 : 7 * D.n_pad;
+            if (coef.alloc((size_t)len) != hipSuccess) return mg_fail(MG_OOM);
+            k_mg_narrow<<<blocks_of(len), 256, 0, c->stream>>>(len, dict ? D.table : D.bands, coef);
+            h.lev[(size_t)l].op = MgOp32{D.sdx, D.sdy, D.sdz, D.n, D.n_pad, D.kdz, D.cls, dict ? coef.get() : nullptr,
+                                         D.ncls, dict ? nullptr : coef.get()};
+        }
+        if (hipGetLastError() != hipSuccess) return mg_fail(MG_BUILD);
+    } else {
+        for (int l = 0; l < L; ++l) h.lev[(size_t)l].op = op[(size_t)l];
+    }
+    T *q = h.w0 = carve_vectors(h.vec.get(), h.lev, 1);
+    if constexpr (F32) h.b0 = q += nf;
+    h.ph = q + nf;
+    h.sh = q + 2 * nf;
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return mg_fail(MG_BUILD);
+    return 0;
+}
+
+// One iteration of the right-preconditioned BiCGSTAB with restart on the structured A-V form: the Poisson hierarchies'
+// algorithm (below), with M the block multigrid, v = A p^ and t = A s^ by the format's own SpMV (ec3d_launch_spmv), then
+// their dot partials (k_avmg_dot: the summation order of k_mg_spmv_dot).  The SpMV launches are not gated: past an exit
+// nothing reads what they write.
+static void launch_iteration_of(ec3d_ctx *c, int it, const BlockMg &h)
+{
+    const ec3d_mg *m = c->mg;
     double **v = c->vec;
     hipStream_t s = c->stream;
     const MatView V = c->A.view();
     const int64_t n = c->A.n;
     const unsigned nb = dot_blocks(n);
     const Gate g0{c->state, it, 0}, g1{c->state, it, 1};
-    launch_avcycle(m, g0, v[EC3D_VEC_P], m->ph, s);
-    ec3d_launch_spmv(V, c->sweep_s, m->ph, v[EC3D_VEC_AP], s);
+    launch_cycle(*m, h, g0, v[EC3D_VEC_P], h.ph, s);
+    ec3d_launch_spmv(V, c->sweep_s, h.ph, v[EC3D_VEC_AP], s);
     k_avmg_dot<<<nb, 256, 0, s>>>(n, g0, v[EC3D_VEC_R0], v[EC3D_VEC_AP], 0, m->part);
     k_mg_scalar<<<1, 256, 0, s>>>(MG_ALPHA, g0, c->state, m->scal, m->part, (int)nb, c->hist, c->hist_cap);
     k_mg_s<<<nb, 256, 0, s>>>(n, g0, c->state, v[EC3D_VEC_R], v[EC3D_VEC_AP], v[EC3D_VEC_S], m->part);
     k_mg_scalar<<<1, 256, 0, s>>>(MG_SEXIT, g0, c->state, m->scal, m->part, (int)nb, c->hist, c->hist_cap);
-    launch_avcycle(m, g1, v[EC3D_VEC_S], m->sh, s);
-    ec3d_launch_spmv(V, c->sweep_s, m->sh, v[EC3D_VEC_AS], s);
+    launch_cycle(*m, h, g1, v[EC3D_VEC_S], h.sh, s);
+    ec3d_launch_spmv(V, c->sweep_s, h.sh, v[EC3D_VEC_AS], s);
     k_avmg_dot<<<nb, 256, 0, s>>>(n, g1, v[EC3D_VEC_S], v[EC3D_VEC_AS], 1, m->part);
     k_mg_scalar<<<1, 256, 0, s>>>(MG_OMEGA, g1, c->state, m->scal, m->part, (int)nb, c->hist, c->hist_cap);
-    k_mg_xr<<<nb, 256, 0, s>>>(n, it, c->state, v[EC3D_VEC_X], m->ph, m->sh, v[EC3D_VEC_S], v[EC3D_VEC_AS],
+    k_mg_xr<<<nb, 256, 0, s>>>(n, it, c->state, v[EC3D_VEC_X], h.ph, h.sh, v[EC3D_VEC_S], v[EC3D_VEC_AS],
                                v[EC3D_VEC_R0], v[EC3D_VEC_R], m->part);
     k_mg_scalar<<<1, 256, 0, s>>>(MG_REXIT, g1, c->state, m->scal, m->part, (int)nb, c->hist, c->hist_cap);
     k_mg_p<<<nb, 256, 0, s>>>(n, g1, c->state, m->scal, v[EC3D_VEC_R], v[EC3D_VEC_AP], v[EC3D_VEC_P], v[EC3D_VEC_R0]);
@@ -1329,113 +1314,18 @@ extern "C" int ec3d_set_preconditioner(ec3d_handle c, int kind, int32_t pre, int
     int rc = ec3d_need_matrix(c, "ec3d_set_preconditioner");
     if (rc) return rc;
     const bool f32 = c->precond_precision == EC3D_PRECOND_FP32;
-    if (kind == EC3D_PRECOND_BLOCK_MG && f32) {
-        ec3d_set_error("ec3d_set_preconditioner: the fp32 V-cycle (ec3d_set_precond_precision) is available for "
-                       "EC3D_PRECOND_MG only, not for the block multigrid of the A-V form");
-        return EC3D_PRECOND_E_MATRIX;
-    }
-    if (kind == EC3D_PRECOND_BLOCK_MG) return set_block_mg(c, pre, post, coarse_sweeps);
-    if (!c->poisson_full || c->in_multi || c->halo > 0 || c->nranks > 1 || c->dist) {
-        ec3d_set_error("ec3d_set_preconditioner: the multigrid preconditioner needs a matrix from ec3d_assemble_poisson "
-                       "on a handle of its own (not A-V, CSR, a slab or a handle of ec3d_multi)");
-        return EC3D_PRECOND_E_MATRIX;
-    }
-    std::vector<std::array<int, 3>> dims;
-    if (!mg_dims(c->sdx, c->sdy, c->sdz, dims)) {
-        const auto d = dims.back();
-        ec3d_set_error("ec3d_set_preconditioner: no axis of the " + std::to_string(d[0]) + "x" + std::to_string(d[1]) +
-                       "x" + std::to_string(d[2]) + " level halves (even and >= 8) and it has more than " +
-                       std::to_string(EC3D_MG_COARSE_ROWS) + " rows, the coarse solver's cap");
-        return EC3D_PRECOND_E_COARSE;
-    }
-    if (c->A.ncls > EC3D_MG_MAXCLS) {
-        ec3d_set_error("ec3d_set_preconditioner: more dictionary classes than the smoother's table holds");
-        return EC3D_PRECOND_E_MATRIX;
-    }
+    if (kind == EC3D_PRECOND_BLOCK_MG && f32)
+        return mg_refuse("ec3d_set_preconditioner: the fp32 V-cycle (ec3d_set_precond_precision) is available for "
+                         "EC3D_PRECOND_MG only, not for the block multigrid of the A-V form");
     // build the new hierarchy completely before the old one is replaced: a failure leaves the handle as it was
     std::unique_ptr<ec3d_mg> m(new ec3d_mg);
+    m->kind = kind;
     m->precision = c->precond_precision;
-    m->pre = pre ? pre : 2;
+    m->pre = pre ? pre : 2; // 0: the default
     m->post = post ? post : 2;
     m->coarse = coarse_sweeps ? coarse_sweeps : 16;
-    const int L = (int)dims.size();
-    m->lev.resize((size_t)L);
-    m->lev[0].op = op_of(c->A, c->sdx, c->sdy, c->sdz);
-    for (int a = 0; a < 3; ++a) m->lev[0].delta[a] = c->poisson_delta[a];
-    int64_t coarse_len = 0;
-    for (int l = 1; l < L; ++l) {
-        MgLevel &P = m->lev[(size_t)l - 1], &Q = m->lev[(size_t)l];
-        for (int a = 0; a < 3; ++a) {
-            P.f[a] = dims[(size_t)l - 1][a] / dims[(size_t)l][a];
-            Q.delta[a] = P.delta[a] * P.f[a];
-        }
-        rc = ec3d_assemble_poisson_level(c, Q.A, dims[(size_t)l][0], dims[(size_t)l][1], dims[(size_t)l][2],
-                                         c->poisson_bnd, Q.delta);
-        if (rc) return rc;
-        Q.op = op_of(Q.A, dims[(size_t)l][0], dims[(size_t)l][1], dims[(size_t)l][2]);
-        coarse_len += 3 * ((Q.op.n + 63) / 64 * 64);
-    }
-    const int64_t nf = (c->A.n + 63) / 64 * 64;
-    // fp64: the fine w, p^, s^; fp32: those and the fine right-hand side's copy, in floats, and no fp64 vector at all
-    const int64_t total = coarse_len + (f32 ? 4 : 3) * nf;
-    const hipError_t ev = f32 ? m->vec32.alloc((size_t)total) : m->vec_base.alloc((size_t)total);
-    if (ev != hipSuccess || m->part.alloc(2 * EC3D_MG_DOT_BLOCKS) != hipSuccess || m->scal.alloc(1) != hipSuccess) {
-        (void)hipGetLastError();
-        ec3d_set_error("ec3d_set_preconditioner: out of device memory for the hierarchy");
-        return 100;
-    }
-    void *const vecs = f32 ? (void *)m->vec32.get() : (void *)m->vec_base.get();
-    if (hipMemsetAsync(vecs, 0, (size_t)total * (f32 ? sizeof(float) : sizeof(double)), c->stream) != hipSuccess ||
-        hipMemsetAsync(m->scal, 0, sizeof(MgScalars), c->stream) != hipSuccess) {
-        ec3d_set_error("ec3d_set_preconditioner: hipMemsetAsync failed");
-        return 100;
-    }
-    if (f32) {
-        float *q = m->vec32;
-        for (int l = 1; l < L; ++l) {
-            MgLevel &Q = m->lev[(size_t)l];
-            const int64_t len = (Q.op.n + 63) / 64 * 64;
-            Q.x32 = q; Q.w32 = q + len; Q.b32 = q + 2 * len;
-            q += 3 * len;
-        }
-        m->w0_32 = q; m->b0_32 = q + nf; m->ph32 = q + 2 * nf; m->sh32 = q + 3 * nf;
-        // every level's coefficients, narrowed once: the class table, or (level 0 in band form) the seven streams
-        for (int l = 0; l < L; ++l) {
-            MgLevel &Q = m->lev[(size_t)l];
-            const bool dict = Q.op.cls != nullptr;
-            const int64_t len = dict ? (int64_t)Q.op.ncls * 7 : 7 * Q.op.n_pad;
-            if (Q.coef32.alloc((size_t)len) != hipSuccess) {
-                (void)hipGetLastError();
-                ec3d_set_error("ec3d_set_preconditioner: out of device memory for the hierarchy");
-                return 100;
-            }
-            k_mg_narrow<<<blocks_of(len), 256, 0, c->stream>>>(len, dict ? Q.op.table : Q.op.bands, Q.coef32);
-            MgOp32 &o = Q.op32;
-            o.sdx = Q.op.sdx; o.sdy = Q.op.sdy; o.sdz = Q.op.sdz;
-            o.n = Q.op.n; o.n_pad = Q.op.n_pad; o.kdz = Q.op.kdz;
-            o.cls = Q.op.cls;
-            o.ncls = Q.op.ncls;
-            o.table = dict ? Q.coef32.get() : nullptr;
-            o.bands = dict ? nullptr : Q.coef32.get();
-        }
-        if (hipGetLastError() != hipSuccess) {
-            ec3d_set_error("ec3d_set_preconditioner: building the hierarchy failed");
-            return 100;
-        }
-    } else {
-        double *q = m->vec_base;
-        for (int l = 1; l < L; ++l) {
-            MgLevel &Q = m->lev[(size_t)l];
-            const int64_t len = (Q.op.n + 63) / 64 * 64;
-            Q.x = q; Q.w = q + len; Q.b = q + 2 * len;
-            q += 3 * len;
-        }
-        m->w0 = q; m->ph = q + nf; m->sh = q + 2 * nf;
-    }
-    if (hipStreamSynchronize(c->stream) != hipSuccess) {
-        ec3d_set_error("ec3d_set_preconditioner: building the hierarchy failed");
-        return 100;
-    }
+    rc = kind == EC3D_PRECOND_BLOCK_MG ? set_block_mg(c, *m) : f32 ? set_poisson_mg<float>(c, *m) : set_poisson_mg<double>(c, *m);
+    if (rc) return rc;
     ec3d_mg_free(c);
     c->mg = m.release();
     return 0;
@@ -1447,25 +1337,17 @@ extern "C" int ec3d_get_preconditioner(ec3d_handle c, int *kind, int32_t *levels
         ec3d_set_error("ec3d_get_preconditioner: null handle");
         return 2;
     }
-    const ec3d_mg *m = c->mg;
-    if (kind) *kind = m ? m->kind : EC3D_PRECOND_NONE;
-    if (m && m->kind == EC3D_PRECOND_BLOCK_MG) {
-        if (levels) *levels = (int32_t)m->av.size();
-        if (dims)
-            for (size_t l = 0; l < m->av.size(); ++l) {
-                dims[3 * l] = m->av[l].op.sdx;
-                dims[3 * l + 1] = m->av[l].op.sdy;
-                dims[3 * l + 2] = m->av[l].op.sdz;
+    if (kind) *kind = c->mg ? c->mg->kind : EC3D_PRECOND_NONE;
+    if (levels) *levels = 0;
+    if (c->mg)
+        std::visit([&](const auto &h) {
+            if (levels) *levels = (int32_t)h.lev.size();
+            for (size_t l = 0; dims && l < h.lev.size(); ++l) {
+                dims[3 * l] = h.lev[l].op.sdx;
+                dims[3 * l + 1] = h.lev[l].op.sdy;
+                dims[3 * l + 2] = h.lev[l].op.sdz;
             }
-        return 0;
-    }
-    if (levels) *levels = m ? (int32_t)m->lev.size() : 0;
-    if (dims && m)
-        for (size_t l = 0; l < m->lev.size(); ++l) {
-            dims[3 * l] = m->lev[l].op.sdx;
-            dims[3 * l + 1] = m->lev[l].op.sdy;
-            dims[3 * l + 2] = m->lev[l].op.sdz;
-        }
+        }, c->mg->h);
     return 0;
 }
 
@@ -1492,6 +1374,18 @@ extern "C" int ec3d_get_precond_precision(ec3d_handle c, int32_t *setting, int32
     return 0;
 }
 
+// z = M r: r up into `in`, the cycle that `launch` enqueues from `in` into `out`, z down from `out`
+template <class F> static int precond_apply_through(ec3d_ctx *c, double *in, double *out, const double *r, double *z, const F &launch)
+{
+    int rc;
+    if ((rc = ec3d_vec_h2d(c, in, r))) return rc;
+    launch();
+    EC3D_HIP(hipGetLastError());
+    if ((rc = ec3d_vec_d2h(c, z, out))) return rc;
+    EC3D_HIP(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
 extern "C" int ec3d_precond_apply(ec3d_handle c, const double *r, double *z)
 {
     int rc = ec3d_need_matrix(c, "ec3d_precond_apply");
@@ -1500,37 +1394,32 @@ extern "C" int ec3d_precond_apply(ec3d_handle c, const double *r, double *z)
         ec3d_set_error("ec3d_precond_apply: no preconditioner set (ec3d_set_preconditioner)");
         return 3;
     }
-    ec3d_mg *m = c->mg;
-    if (m->precision == EC3D_PRECOND_FP32) {
+    const ec3d_mg &m = *c->mg;
+    const Gate g{nullptr, 0, 0};
+    hipStream_t s = c->stream;
+    if (auto *h = std::get_if<PoissonMg<float>>(&m.h)) {
         // r and z in fp64 through the work vectors P and AP (as ec3d_spmv); the cycle narrows r, z is widened exactly
-        if ((rc = ec3d_vec_h2d(c, c->vec[EC3D_VEC_P], r))) return rc;
-        launch_vcycle(m, Gate{nullptr, 0, 0}, c->vec[EC3D_VEC_P], m->sh32, c->stream);
-        k_mg_widen<<<blocks_of(c->A.n), 256, 0, c->stream>>>(c->A.n, m->sh32, c->vec[EC3D_VEC_AP]);
-        EC3D_HIP(hipGetLastError());
-        if ((rc = ec3d_vec_d2h(c, z, c->vec[EC3D_VEC_AP]))) return rc;
-        EC3D_HIP(hipStreamSynchronize(c->stream));
-        return 0;
+        double *in = c->vec[EC3D_VEC_P], *out = c->vec[EC3D_VEC_AP];
+        return precond_apply_through(c, in, out, r, z, [&] {
+            launch_cycle(m, *h, g, in, h->sh, s);
+            k_mg_widen<<<blocks_of(c->A.n), 256, 0, s>>>(c->A.n, h->sh, out);
+        });
     }
-    if ((rc = ec3d_vec_h2d(c, m->ph, r))) return rc;
-    if (m->kind == EC3D_PRECOND_BLOCK_MG) launch_avcycle(m, Gate{nullptr, 0, 0}, m->ph, m->sh, c->stream);
-    else launch_vcycle(m, Gate{nullptr, 0, 0}, m->ph, m->sh, c->stream);
-    EC3D_HIP(hipGetLastError());
-    if ((rc = ec3d_vec_d2h(c, z, m->sh))) return rc;
-    EC3D_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    if (auto *h = std::get_if<PoissonMg<double>>(&m.h))
+        return precond_apply_through(c, h->ph, h->sh, r, z, [&] { launch_cycle(m, *h, g, h->ph, h->sh, s); });
+    const BlockMg &h = std::get<BlockMg>(m.h);
+    return precond_apply_through(c, h.ph, h.sh, r, z, [&] { launch_cycle(m, h, g, h.ph, h.sh, s); });
 }
 
-// iterations per poll of solve_core: about 1 ms of device work (a V-cycle is ~210 B per fine row, two per iteration)
+// iterations per poll of solve_core: about 1 ms of device work.  Poisson: a V-cycle is ~210 B per fine row, two per
+// iteration.  A-V, per A cell: two applications of M (three V-cycles of ~210 B each) ~1260 B, two SpMVs of the four
+// blocks and the vector kernels ~800 B; the launches of a level cost ~60 us per application on small grids
 int ec3d_mg_chunk(const ec3d_ctx *c)
 {
-    if (c->mg->kind == EC3D_PRECOND_BLOCK_MG) {
-        // per A cell and iteration: two applications of M (three V-cycles of ~210 B each) ~1260 B, two SpMVs of the
-        // four blocks and the vector kernels ~800 B; the launches of a level cost ~60 us per application on small grids
-        const double cells = (double)c->mg->av[0].op.n;
-        const double est_us = cells * 2100.0 / 4.0e6 + 120.0 * (double)c->mg->av.size();
-        return (int)std::min<double>(16.0, std::max<double>(1.0, 1000.0 / est_us));
-    }
-    const double est_us = (double)c->A.n_pad * 600.0 / 4.0e6 + 60.0 * (double)c->mg->lev.size();
+    const auto *av = std::get_if<BlockMg>(&c->mg->h);
+    const double levels = std::visit([](const auto &h) { return (double)h.lev.size(); }, c->mg->h);
+    const double est_us = av ? (double)av->lev[0].op.n * 2100.0 / 4.0e6 + 120.0 * levels
+                             : (double)c->A.n_pad * 600.0 / 4.0e6 + 60.0 * levels;
     return (int)std::min<double>(16.0, std::max<double>(1.0, 1000.0 / est_us));
 }
 
@@ -1542,34 +1431,33 @@ int ec3d_mg_chunk(const ec3d_ctx *c)
 // The work vectors: v in AP, t in AS.  Sums and exits stay on the device; launches past an exit are no-ops.
 // T: the precision of M and of p^, s^ (ph, sh), which the SpMV + dot launch and the x / r update widen on load; every
 // other operand and operation of the outer iteration is fp64 in both.
-template <class T> static void mg_launch_iteration_of(ec3d_ctx *c, int it, T *ph, T *sh)
+template <class T> static void launch_iteration_of(ec3d_ctx *c, int it, const PoissonMg<T> &h)
 {
-    ec3d_mg *m = c->mg;
+    const ec3d_mg *m = c->mg;
     double **v = c->vec;
     hipStream_t s = c->stream;
-    const MgOp &A = m->lev[0].op;
-    const bool dict = A.cls != nullptr;
+    const MgOp &A = h.op0;
     const int64_t n = A.n;
     const unsigned nb = dot_blocks(n);
     const Gate g0{c->state, it, 0}, g1{c->state, it, 1};
-    launch_vcycle(m, g0, v[EC3D_VEC_P], ph, s);
-    MG_LAUNCH(k_mg_spmv_dot, nb, 256, A, g0, (const T *)ph, v[EC3D_VEC_R0], v[EC3D_VEC_AP], 0, m->part);
+    launch_cycle(*m, h, g0, v[EC3D_VEC_P], h.ph, s);
+    MG_LAUNCH(k_mg_spmv_dot, nb, 256, A, g0, (const T *)h.ph, v[EC3D_VEC_R0], v[EC3D_VEC_AP], 0, m->part);
     k_mg_scalar<<<1, 256, 0, s>>>(MG_ALPHA, g0, c->state, m->scal, m->part, (int)nb, c->hist, c->hist_cap);
     k_mg_s<<<nb, 256, 0, s>>>(n, g0, c->state, v[EC3D_VEC_R], v[EC3D_VEC_AP], v[EC3D_VEC_S], m->part);
     k_mg_scalar<<<1, 256, 0, s>>>(MG_SEXIT, g0, c->state, m->scal, m->part, (int)nb, c->hist, c->hist_cap);
-    launch_vcycle(m, g1, v[EC3D_VEC_S], sh, s);
-    MG_LAUNCH(k_mg_spmv_dot, nb, 256, A, g1, (const T *)sh, v[EC3D_VEC_S], v[EC3D_VEC_AS], 1, m->part);
+    launch_cycle(*m, h, g1, v[EC3D_VEC_S], h.sh, s);
+    MG_LAUNCH(k_mg_spmv_dot, nb, 256, A, g1, (const T *)h.sh, v[EC3D_VEC_S], v[EC3D_VEC_AS], 1, m->part);
     k_mg_scalar<<<1, 256, 0, s>>>(MG_OMEGA, g1, c->state, m->scal, m->part, (int)nb, c->hist, c->hist_cap);
-    k_mg_xr<<<nb, 256, 0, s>>>(n, it, c->state, v[EC3D_VEC_X], (const T *)ph, (const T *)sh, v[EC3D_VEC_S], v[EC3D_VEC_AS],
-                               v[EC3D_VEC_R0], v[EC3D_VEC_R], m->part);
+    k_mg_xr<<<nb, 256, 0, s>>>(n, it, c->state, v[EC3D_VEC_X], (const T *)h.ph, (const T *)h.sh, v[EC3D_VEC_S],
+                               v[EC3D_VEC_AS], v[EC3D_VEC_R0], v[EC3D_VEC_R], m->part);
     k_mg_scalar<<<1, 256, 0, s>>>(MG_REXIT, g1, c->state, m->scal, m->part, (int)nb, c->hist, c->hist_cap);
     k_mg_p<<<nb, 256, 0, s>>>(n, g1, c->state, m->scal, v[EC3D_VEC_R], v[EC3D_VEC_AP], v[EC3D_VEC_P], v[EC3D_VEC_R0]);
 }
 
 void ec3d_mg_launch_iteration(ec3d_ctx *c, int it)
 {
-    ec3d_mg *m = c->mg;
-    if (m->kind == EC3D_PRECOND_BLOCK_MG) avmg_launch_iteration(c, it);
-    else if (m->precision == EC3D_PRECOND_FP32) mg_launch_iteration_of(c, it, m->ph32, m->sh32);
-    else mg_launch_iteration_of(c, it, m->ph, m->sh);
+    const ec3d_mg &m = *c->mg;
+    if (auto *h = std::get_if<PoissonMg<float>>(&m.h)) launch_iteration_of(c, it, *h);
+    else if (auto *h = std::get_if<PoissonMg<double>>(&m.h)) launch_iteration_of(c, it, *h);
+    else launch_iteration_of(c, it, std::get<BlockMg>(m.h));
 }

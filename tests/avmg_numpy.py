@@ -204,6 +204,39 @@ def bands_from_csr(valA, irow, jcol, dims, ucell):
     return bands[0], bands[3]
 
 
+def u_components(urows, dims):
+    """Conducting components of the (nC,) mask of U cells (cells joined across a face; cell = (k * sdy + j) * sdx + i),
+    each as its cells in scan order, the components in order of their first cell."""
+    sdx, sdy, sdz = dims
+    comp = np.full(len(urows), -1, np.int64)
+    comps = []
+    for c0 in np.flatnonzero(urows):
+        if comp[c0] >= 0:
+            continue
+        comp[c0] = len(comps)
+        stack, cells = [int(c0)], []
+        while stack:
+            q = stack.pop()
+            cells.append(q)
+            i, j, k = q % sdx, (q // sdx) % sdy, q // (sdx * sdy)
+            for ok, nb in ((k > 0, q - sdx * sdy), (j > 0, q - sdx), (i > 0, q - 1), (i + 1 < sdx, q + 1),
+                           (j + 1 < sdy, q + sdx), (k + 1 < sdz, q + sdx * sdy)):
+                if ok and urows[nb] and comp[nb] < 0:
+                    comp[nb] = comp[c0]
+                    stack.append(nb)
+        comps.append(np.sort(np.array(cells, np.int64)))
+    return comps
+
+
+def u_weights(cu):
+    """Weights of the U rows' left null vector from the U bands (7, nC): 1/2 per axis along which the cell misses a
+    neighbour (a band coefficient of that axis is 0)."""
+    w = np.ones(cu.shape[1])
+    for lo, hi in ((2, 4), (1, 5), (0, 6)):
+        w = np.where((cu[lo] == 0.0) | (cu[hi] == 0.0), w * 0.5, w)
+    return w
+
+
 class AVMG:
     def __init__(self, valA, irow, jcol, dims, ucell, pre=0, post=0, coarse_sweeps=0):
         self.valA, self.irow, self.jcol = valA, irow, jcol
@@ -218,7 +251,8 @@ class AVMG:
         self.ulevel = BandLevel(self.dims, cu)
         self.urows = np.zeros(self.nC, bool)
         self.urows[self.ucell] = True
-        self._u_components()
+        self.ucomps = u_components(self.urows, self.dims)
+        self.uweight = u_weights(cu)
         self.pre = pre or DEFAULT_PRE
         self.post = post or DEFAULT_POST
         self.coarse = coarse_sweeps or DEFAULT_COARSE
@@ -268,33 +302,6 @@ class AVMG:
             x = L.half_sweep(x, b, 1)
             x = L.half_sweep(x, b, 0)
         return x
-
-    def _u_components(self):
-        """Conducting components (U cells joined across a face), each as its cells in scan order, and the weights of
-        the U rows' left null vector: 1/2 per axis along which the cell misses a neighbour."""
-        sdx, sdy, sdz = self.dims
-        comp = np.full(self.nC, -1, np.int64)
-        self.ucomps = []
-        for c0 in np.flatnonzero(self.urows):
-            if comp[c0] >= 0:
-                continue
-            comp[c0] = len(self.ucomps)
-            stack, cells = [int(c0)], []
-            while stack:
-                q = stack.pop()
-                cells.append(q)
-                i, j, k = q % sdx, (q // sdx) % sdy, q // (sdx * sdy)
-                for ok, nb in ((k > 0, q - sdx * sdy), (j > 0, q - sdx), (i > 0, q - 1), (i + 1 < sdx, q + 1),
-                               (j + 1 < sdy, q + sdx), (k + 1 < sdz, q + sdx * sdy)):
-                    if ok and self.urows[nb] and comp[nb] < 0:
-                        comp[nb] = comp[c0]
-                        stack.append(nb)
-            self.ucomps.append(np.sort(np.array(cells, np.int64)))
-        cu = self.ulevel.c
-        w = np.ones(self.nC)
-        for lo, hi in ((2, 4), (1, 5), (0, 6)):
-            w = np.where((cu[lo] == 0.0) | (cu[hi] == 0.0), w * 0.5, w)
-        self.uweight = w
 
     def project_u(self, bu_cells):
         """bu - (w.bu / w.1) on each component (k_avmg_upart / k_avmg_umean: chunks of UCHUNK entries, thread-strided
