@@ -450,6 +450,7 @@ struct ec3d_ctx {
     bool in_multi = false;
     ec3d_mg *mg = nullptr; // ec3d_set_preconditioner(EC3D_PRECOND_MG): solves run the preconditioned iteration
     int precond_precision = 0; // EC3D_PRECOND_FP64 / _FP32: what the next ec3d_set_preconditioner builds (ec3d_set_precond_precision)
+    int precond_coarsening = 0; // EC3D_COARSEN_REDISCRETIZE / _AGGREGATE: likewise (ec3d_set_precond_coarsening)
     ec3d_ctx() = default;
     ~ec3d_ctx(); // ec3d_context.hip: the hierarchy goes (ec3d_mg_free), then every owner above, last declared first
 };

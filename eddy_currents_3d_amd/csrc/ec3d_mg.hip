@@ -5,6 +5,11 @@
 // (ec3d_assemble_poisson_level) at half the cells and twice the spacing on each axis that is even and >= 8, with the
 // same BND -- a rediscretisation, not a Galerkin product.  Coarsening stops when no axis can halve or a level has at
 // most EC3D_MG_COARSE_ROWS rows; that level is solved by one single-workgroup launch in LDS.
+// With EC3D_COARSEN_AGGREGATE (ec3d_set_precond_coarsening; the rule is ec3d_mg_plan.hpp's) every axis of extent > 1 is
+// ceil-halved instead, so every box gets a hierarchy: levels stay rediscretisations while every axis is even and >= 8,
+// and from the first level that is not, every coarser level is the Galerkin product of piecewise-constant aggregation
+// (k_mg_galerkin, fp64, once at set-up), kept as seven band streams; the restriction is then the mean over the
+// aggregate's actual children (an odd axis ends in an aggregate of one cell).  tests/mg_numpy_agg.py restates it.
 //
 // One V-cycle from x = 0 on level l (tests/mg_numpy.py restates it operation by operation; no reduction enters it, so
 // the device result is bit-identical to the restatement):
@@ -33,6 +38,7 @@
 // (-z, -y, -x, diag, +x, +y, +z); a neighbour beyond the box contributes nothing (its coefficient is 0 there anyway).
 #include "../../include/ec3d_hip.h"
 #include "ec3d_avmg_plan.hpp"
+#include "ec3d_mg_plan.hpp"
 #include "ec3d_internal.hpp"
 
 #include <array>
@@ -92,7 +98,9 @@ struct AvLevel {
 
 // A level of the hierarchy of the single-component operator (EC3D_PRECOND_MG): what does not depend on the cycle's precision
 struct MgGrid {
-    DevMatrix A;          // the level's assembled matrix (level 0: unused, the handle's own)
+    int kind = EC3D_MG_LEVEL_MATRIX; // how the level's operator is made (ec3d_mg_plan.hpp)
+    DevMatrix A;          // a rediscretised level's assembled matrix (level 0: unused, the handle's own)
+    DevBuf<double> bands; // a Galerkin level's seven band streams (released once an fp32 hierarchy has narrowed them)
     int f[3] = {1, 1, 1}; // coarsening factor towards the next level per axis (1 or 2)
     double delta[3] = {0, 0, 0};
 };
@@ -102,7 +110,7 @@ template <class T> struct MgLevelT {
     T *x = nullptr, *w = nullptr, *b = nullptr; // coarse levels: inside PoissonMg::vec
 };
 // float: every level's coefficients narrowed once at set-up -- the class table, or the seven band streams of level 0
-// under ec3d_set_format(h, 0) (coarse levels are always in dictionary form)
+// under ec3d_set_format(h, 0) and of a Galerkin level (rediscretised levels are always in dictionary form)
 template <class T> struct MgNarrowed {};
 template <> struct MgNarrowed<float> {
     std::vector<DevBuf<float>> coef;
@@ -138,6 +146,7 @@ struct BlockMg {
 struct ec3d_mg {
     int kind = EC3D_PRECOND_MG;
     int precision = EC3D_PRECOND_FP64; // EC3D_PRECOND_FP32: kind EC3D_PRECOND_MG only
+    int coarsening = EC3D_COARSEN_REDISCRETIZE; // the rule the hierarchy was built by (EC3D_PRECOND_BLOCK_MG: aggregate)
     int pre = 2, post = 2, coarse = 16;
     DevBuf<double> part;        // 2 * EC3D_MG_DOT_BLOCKS
     DevBuf<MgScalars> scal;
@@ -274,7 +283,9 @@ __global__ __launch_bounds__(256) void k_mg_init_f32(MgOp32 A, Gate g, const dou
 // One thread per coarse cell; the fine residual never reaches HBM.  Bytes per FINE row: w 8 + b 8 + 1 class byte read,
 // 8 / children written = 18 B at factor 2 along every axis.
 // T = float: about 9.5 B (1 / children is a power of two, exact in either precision).
-template <bool DICT, class T = double>
+// RAGGED (a level of EC3D_COARSEN_AGGREGATE whose axis is odd): a child beyond the box is skipped and the mean is over
+// the children that exist, 1, 2, 4 or 8 of them; without it the aggregates are full and no bound is tested.
+template <bool DICT, bool RAGGED, class T = double>
 __global__ __launch_bounds__(256) void k_mg_restrict(MgOpT<T> A, MgOpT<T> C, int fx, int fy, int fz, Gate g,
                                                      const T *__restrict__ w, const T *__restrict__ b,
                                                      T *__restrict__ bc)
@@ -286,11 +297,13 @@ __global__ __launch_bounds__(256) void k_mg_restrict(MgOpT<T> A, MgOpT<T> C, int
     if (rc >= C.n) return;
     const Pos pc = pos_of(C, rc);
     T s = T(0);
-    for (int dk = 0; dk < fz; ++dk)
-        for (int dj = 0; dj < fy; ++dj)
-            for (int di = 0; di < fx; ++di) {
+    int children = RAGGED ? 0 : fx * fy * fz;
+    for (int dk = 0; dk < fz && (!RAGGED || pc.k * fz + dk < A.sdz); ++dk)
+        for (int dj = 0; dj < fy && (!RAGGED || pc.j * fy + dj < A.sdy); ++dj)
+            for (int di = 0; di < fx && (!RAGGED || pc.i * fx + di < A.sdx); ++di) {
                 const Pos p{pc.i * fx + di, pc.j * fy + dj, pc.k * fz + dk};
                 const int64_t r = (int64_t)p.k * A.kdz + (int64_t)p.j * A.sdx + p.i;
+                if constexpr (RAGGED) ++children;
                 T c[7], v[6];
                 row_coefs<DICT>(A, tbl, r, c);
                 neighbours(A, p, r, [&](int64_t q) { return w[q]; }, v);
@@ -304,7 +317,7 @@ __global__ __launch_bounds__(256) void k_mg_restrict(MgOpT<T> A, MgOpT<T> C, int
                 t = t - c[6] * v[5];
                 s = s + t;
             }
-    bc[rc] = s * (T(1) / (T)(fx * fy * fz));
+    bc[rc] = s * (T(1) / (T)children);
 }
 
 // Prolongation (piecewise-constant injection) + correction fused with the first post-smoothing half-sweep (black):
@@ -384,6 +397,45 @@ __global__ __launch_bounds__(EC3D_MG_COARSE_THREADS) void k_mg_coarse(MgOpT<T> A
         const int64_t r = threadIdx.x + (int64_t)q * EC3D_MG_COARSE_THREADS;
         if (r < A.n) x[r] = xs[r];
     }
+}
+
+// Galerkin coarse operator of piecewise-constant aggregation (EC3D_COARSEN_AGGREGATE), in the arithmetic and order of
+// k_avmg_galerkin: coarse band q = the sum of the children's couplings that cross the aggregate's face on that side (to
+// a cell inside the box), the diagonal = the children's diagonals plus their couplings inside the aggregate; children k
+// outermost, i innermost, within a child the diagonal first and then the couplings in offset order; times `scale` =
+// 1 / (2 * nominal children).  DICT is the form of the finer level F.  One thread per coarse cell, fp64, once at set-up.
+template <bool DICT>
+__global__ __launch_bounds__(256) void k_mg_galerkin(MgOp F, MgOp C, int fx, int fy, int fz, double scale,
+                                                     double *__restrict__ bands)
+{
+    __shared__ double tbl[EC3D_MG_MAXCLS * 7];
+    if (DICT) load_table(F, tbl);
+    const int64_t rc = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (rc >= C.n) return;
+    const Pos pc = pos_of(C, rc);
+    double D = 0.0, B[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    const int ext[3] = {F.sdx, F.sdy, F.sdz}, f[3] = {fx, fy, fz}, agg[3] = {pc.i, pc.j, pc.k};
+    // offset order: axis and direction of band q (q = 3, the diagonal, is skipped)
+    const int qax[7] = {2, 1, 0, -1, 0, 1, 2}, qdir[7] = {-1, -1, -1, 0, 1, 1, 1};
+    for (int dk = 0; dk < fz && pc.k * fz + dk < F.sdz; ++dk)
+        for (int dj = 0; dj < fy && pc.j * fy + dj < F.sdy; ++dj)
+            for (int di = 0; di < fx && pc.i * fx + di < F.sdx; ++di) {
+                const int pos[3] = {pc.i * fx + di, pc.j * fy + dj, pc.k * fz + dk};
+                const int64_t r = (int64_t)pos[2] * F.kdz + (int64_t)pos[1] * F.sdx + pos[0];
+                double c[7];
+                row_coefs<DICT>(F, tbl, r, c);
+                D = D + c[3];
+#pragma unroll
+                for (int q = 0; q < 7; ++q) {
+                    if (q == 3) continue;
+                    const int a = qax[q], nb = pos[a] + qdir[q];
+                    if (nb < 0 || nb >= ext[a]) continue;
+                    if (nb / f[a] == agg[a]) D = D + c[q];
+                    else B[q] = B[q] + c[q];
+                }
+            }
+#pragma unroll
+    for (int q = 0; q < 7; ++q) bands[(size_t)q * C.n_pad + rc] = (q == 3 ? D : B[q]) * scale;
 }
 
 // ---- outer iteration ------------------------------------------------------------------------------------------------
@@ -576,6 +628,13 @@ MgOp op_of(const DevMatrix &A, int sdx, int sdy, int sdz)
         else kern<false><<<(grid), (block), 0, s>>>(A, __VA_ARGS__);                                              \
     } while (0)
 
+// ... with a second template flag
+#define MG_LAUNCH2(kern, flag, grid, block, A, ...)                                                                \
+    do {                                                                                                           \
+        if ((A).cls) kern<true, flag><<<(grid), (block), 0, s>>>(A, __VA_ARGS__);                                 \
+        else kern<false, flag><<<(grid), (block), 0, s>>>(A, __VA_ARGS__);                                        \
+    } while (0)
+
 // the fine level's first half-sweep (red, from x = 0); fp32: it also narrows r into b0
 inline void launch_fine_init(const PoissonMg<double> &h, Gate g, const double *r, hipStream_t s)
 {
@@ -634,7 +693,11 @@ void launch_cycle(const ec3d_mg &m, const PoissonMg<T> &h, Gate g, const double 
         [&](int l) {
             const MgOpT<T> &A = lev[l].op, &C = lev[l + 1].op;
             const int *f = h.grid[(size_t)l].f;
-            MG_LAUNCH(k_mg_restrict, blocks_of(C.n), 256, A, C, f[0], f[1], f[2], g, W(l), B(l), lev[l + 1].b);
+            // ragged: an axis of A is not f times C's (ceil-halving of an odd extent)
+            if (C.sdx * f[0] != A.sdx || C.sdy * f[1] != A.sdy || C.sdz * f[2] != A.sdz)
+                MG_LAUNCH2(k_mg_restrict, true, blocks_of(C.n), 256, A, C, f[0], f[1], f[2], g, W(l), B(l), lev[l + 1].b);
+            else
+                MG_LAUNCH2(k_mg_restrict, false, blocks_of(C.n), 256, A, C, f[0], f[1], f[2], g, W(l), B(l), lev[l + 1].b);
         },
         [&] {
             const MgLevelT<T> &K = lev[L - 1];
@@ -1029,26 +1092,7 @@ void launch_cycle(const ec3d_mg &m, const BlockMg &h, Gate g, const double *r, d
 
 } // namespace
 
-// ---- hierarchy rule (host) --------------------------------------------------------------------------------------------
-// Level dims: an axis halves while it is even and >= 8; stop when no axis can halve or a level has <= 4096 rows.
-// Returns false when the coarsest level is over the coarse solver's cap.
-static bool mg_dims(int sdx, int sdy, int sdz, std::vector<std::array<int, 3>> &dims)
-{
-    dims.assign(1, {sdx, sdy, sdz});
-    for (;;) {
-        const auto d = dims.back();
-        if ((int64_t)d[0] * d[1] * d[2] <= EC3D_MG_COARSE_ROWS) return true;
-        std::array<int, 3> e = d;
-        bool any = false;
-        for (int a = 0; a < 3; ++a)
-            if (d[a] % 2 == 0 && d[a] >= 8) {
-                e[a] = d[a] / 2;
-                any = true;
-            }
-        if (!any) return false;
-        dims.push_back(e);
-    }
-}
+// ---- hierarchy rule (host): ec3d_mg_plan.hpp for EC3D_PRECOND_MG ----------------------------------------------------
 
 // ---- block multigrid of the structured A-V form: set-up --------------------------------------------------------------
 // Level dims: every axis whose extent is > 1 is ceil-halved, until a level has <= 4096 cells (always reached).
@@ -1197,8 +1241,9 @@ template <class T> static int set_poisson_mg(ec3d_ctx *c, ec3d_mg &m)
     if (!c->poisson_full || !own_handle(c))
         return mg_refuse("ec3d_set_preconditioner: the multigrid preconditioner needs a matrix from ec3d_assemble_poisson "
                          "on a handle of its own (not A-V, CSR, a slab or a handle of ec3d_multi)");
-    std::vector<std::array<int, 3>> dims;
-    if (!mg_dims(c->sdx, c->sdy, c->sdz, dims)) {
+    MgPlan plan;
+    const std::vector<std::array<int, 3>> &dims = plan.dims;
+    if (!ec3d_mg_plan(c->sdx, c->sdy, c->sdz, c->precond_coarsening == EC3D_COARSEN_AGGREGATE, EC3D_MG_COARSE_ROWS, plan)) {
         const auto d = dims.back();
         return mg_refuse("ec3d_set_preconditioner: no axis of the " + std::to_string(d[0]) + "x" + std::to_string(d[1]) +
                          "x" + std::to_string(d[2]) + " level halves (even and >= 8) and it has more than " +
@@ -1218,13 +1263,33 @@ template <class T> static int set_poisson_mg(ec3d_ctx *c, ec3d_mg &m)
         MgGrid &P = h.grid[(size_t)l - 1], &Q = h.grid[(size_t)l];
         const auto &d = dims[(size_t)l];
         for (int a = 0; a < 3; ++a) {
-            P.f[a] = dims[(size_t)l - 1][a] / d[a];
+            P.f[a] = d[a] == dims[(size_t)l - 1][a] ? 1 : 2; // halved, exactly or (aggregate rule) rounding up
             Q.delta[a] = P.delta[a] * P.f[a];
         }
-        const int rc = ec3d_assemble_poisson_level(c, Q.A, d[0], d[1], d[2], c->poisson_bnd, Q.delta);
-        if (rc) return rc;
-        op[(size_t)l] = op_of(Q.A, d[0], d[1], d[2]);
-        coarse_len += 3 * pad64(op[(size_t)l].n);
+        Q.kind = plan.kinds[(size_t)l];
+        MgOp &o = op[(size_t)l];
+        if (Q.kind == EC3D_MG_LEVEL_REDISCRETIZED) {
+            const int rc = ec3d_assemble_poisson_level(c, Q.A, d[0], d[1], d[2], c->poisson_bnd, Q.delta);
+            if (rc) return rc;
+            o = op_of(Q.A, d[0], d[1], d[2]);
+        } else {
+            // the Galerkin product of the level above, which the stream has completed or holds ahead of this launch
+            o = MgOp{};
+            o.sdx = d[0]; o.sdy = d[1]; o.sdz = d[2];
+            o.kdz = (int64_t)d[0] * d[1];
+            o.n = o.kdz * d[2];
+            o.n_pad = pad64(o.n);
+            if (Q.bands.alloc((size_t)7 * o.n_pad) != hipSuccess) return mg_fail(MG_OOM);
+            if (hipMemsetAsync(Q.bands, 0, (size_t)7 * o.n_pad * sizeof(double), c->stream) != hipSuccess)
+                return mg_fail("hipMemsetAsync failed");
+            o.bands = Q.bands;
+            const MgOp &F = op[(size_t)l - 1];
+            const double scale = 1.0 / (2.0 * P.f[0] * P.f[1] * P.f[2]);
+            hipStream_t s = c->stream;
+            MG_LAUNCH(k_mg_galerkin, blocks_of(o.n), 256, F, o, P.f[0], P.f[1], P.f[2], scale, Q.bands);
+            if (hipGetLastError() != hipSuccess) return mg_fail(MG_BUILD);
+        }
+        coarse_len += 3 * pad64(o.n);
     }
     const int64_t nf = pad64(c->A.n);
     // double: the fine w, p^, s^; float: those and the fine right-hand side's copy
@@ -1236,7 +1301,8 @@ template <class T> static int set_poisson_mg(ec3d_ctx *c, ec3d_mg &m)
         hipMemsetAsync(m.scal, 0, sizeof(MgScalars), c->stream) != hipSuccess)
         return mg_fail("hipMemsetAsync failed");
     if constexpr (F32) {
-        // the class table, or (level 0 in band form) the seven streams; a coarse level's A keeps owning the class bytes
+        // the class table, or (level 0 in band form, a Galerkin level) the seven streams; a rediscretised level's A keeps
+        // owning the class bytes
         h.coef.resize((size_t)L);
         for (int l = 0; l < L; ++l) {
             const MgOp &D = op[(size_t)l];
@@ -1257,6 +1323,8 @@ template <class T> static int set_poisson_mg(ec3d_ctx *c, ec3d_mg &m)
     h.ph = q + nf;
     h.sh = q + 2 * nf;
     if (hipStreamSynchronize(c->stream) != hipSuccess) return mg_fail(MG_BUILD);
+    if constexpr (F32)
+        for (MgGrid &G : h.grid) G.bands.reset(); // narrowed: an fp32 hierarchy keeps no fp64 coefficients of its own
     return 0;
 }
 
@@ -1321,6 +1389,7 @@ extern "C" int ec3d_set_preconditioner(ec3d_handle c, int kind, int32_t pre, int
     std::unique_ptr<ec3d_mg> m(new ec3d_mg);
     m->kind = kind;
     m->precision = c->precond_precision;
+    m->coarsening = kind == EC3D_PRECOND_BLOCK_MG ? EC3D_COARSEN_AGGREGATE : c->precond_coarsening;
     m->pre = pre ? pre : 2; // 0: the default
     m->post = post ? post : 2;
     m->coarse = coarse_sweeps ? coarse_sweeps : 16;
@@ -1371,6 +1440,36 @@ extern "C" int ec3d_get_precond_precision(ec3d_handle c, int32_t *setting, int32
     }
     if (setting) *setting = c->precond_precision;
     if (in_use) *in_use = c->mg ? c->mg->precision : EC3D_PRECOND_FP64;
+    return 0;
+}
+
+template <class T> static int level_kind(const PoissonMg<T> &h, size_t l) { return h.grid[l].kind; }
+static int level_kind(const BlockMg &, size_t l) { return l ? EC3D_MG_LEVEL_GALERKIN : EC3D_MG_LEVEL_MATRIX; }
+
+extern "C" int ec3d_set_precond_coarsening(ec3d_handle c, int32_t rule)
+{
+    if (!c || (rule != EC3D_COARSEN_REDISCRETIZE && rule != EC3D_COARSEN_AGGREGATE)) {
+        ec3d_set_error(!c ? std::string("ec3d_set_precond_coarsening: null handle")
+                          : "ec3d_set_precond_coarsening: unknown rule " + std::to_string(rule) +
+                                " (EC3D_COARSEN_REDISCRETIZE = 0, EC3D_COARSEN_AGGREGATE = 1)");
+        return 2;
+    }
+    c->precond_coarsening = rule;
+    return 0;
+}
+
+extern "C" int ec3d_get_precond_coarsening(ec3d_handle c, int32_t *setting, int32_t *in_use, int32_t *level_kinds)
+{
+    if (!c) {
+        ec3d_set_error("ec3d_get_precond_coarsening: null handle");
+        return 2;
+    }
+    if (setting) *setting = c->precond_coarsening;
+    if (in_use) *in_use = c->mg ? c->mg->coarsening : EC3D_COARSEN_REDISCRETIZE;
+    if (c->mg && level_kinds)
+        std::visit([&](const auto &h) {
+            for (size_t l = 0; l < h.lev.size(); ++l) level_kinds[l] = level_kind(h, l);
+        }, c->mg->h);
     return 0;
 }
 

@@ -22,13 +22,15 @@ module ec3d_hip
               ec3d_multi_plan, ec3d_set_preconditioner, ec3d_get_preconditioner, ec3d_precond_apply, &
               EC3D_PRECOND_NONE, EC3D_PRECOND_MG, EC3D_PRECOND_BLOCK_MG, &
               ec3d_set_u_rhs, EC3D_U_RHS_REFERENCE, EC3D_U_RHS_ALL, &
-              ec3d_set_precond_precision, ec3d_get_precond_precision, EC3D_PRECOND_FP64, EC3D_PRECOND_FP32
+              ec3d_set_precond_precision, ec3d_get_precond_precision, EC3D_PRECOND_FP64, EC3D_PRECOND_FP32, &
+              ec3d_set_precond_coarsening, ec3d_get_precond_coarsening, EC3D_COARSEN_REDISCRETIZE, EC3D_COARSEN_AGGREGATE
 
     integer(c_int), parameter :: EC3D_VEC_X = 0, EC3D_VEC_B = 1   ! Uaf, Jaf
     integer(c_int), parameter :: EC3D_PRECOND_NONE = 0, EC3D_PRECOND_MG = 1   ! ec3d_set_preconditioner
     integer(c_int), parameter :: EC3D_PRECOND_BLOCK_MG = 2   ! ... of the structured A-V form (ec3d_assemble)
     integer(c_int), parameter :: EC3D_U_RHS_REFERENCE = 0, EC3D_U_RHS_ALL = 1   ! ec3d_set_u_rhs
     integer(c_int32_t), parameter :: EC3D_PRECOND_FP64 = 0, EC3D_PRECOND_FP32 = 1   ! ec3d_set_precond_precision
+    integer(c_int32_t), parameter :: EC3D_COARSEN_REDISCRETIZE = 0, EC3D_COARSEN_AGGREGATE = 1   ! ec3d_set_precond_coarsening
 
     interface
         integer(c_int) function ec3d_create(h, device) bind(C, name="ec3d_create")
@@ -190,6 +192,21 @@ module ec3d_hip
             import :: c_ptr, c_int, c_int32_t
             type(c_ptr), value :: h
             integer(c_int32_t), intent(out) :: setting, in_use
+        end function
+        ! coarsening rule of the hierarchy the next ec3d_set_preconditioner(EC3D_PRECOND_MG) builds (include/ec3d_hip.h)
+        integer(c_int) function ec3d_set_precond_coarsening(h, rule) bind(C, name="ec3d_set_precond_coarsening")
+            import :: c_ptr, c_int, c_int32_t
+            type(c_ptr), value :: h
+            integer(c_int32_t), value :: rule
+        end function
+        ! setting: the handle's; in_use: that of the hierarchy now set; level_kinds: c_loc of an integer(c_int32_t)
+        ! array with one entry per level of it (0 = the handle's matrix, 1 = rediscretised, 2 = Galerkin), or c_null_ptr
+        integer(c_int) function ec3d_get_precond_coarsening(h, setting, in_use, level_kinds) &
+                bind(C, name="ec3d_get_precond_coarsening")
+            import :: c_ptr, c_int, c_int32_t
+            type(c_ptr), value :: h
+            integer(c_int32_t), intent(out) :: setting, in_use
+            type(c_ptr), value :: level_kinds
         end function
         ! U rows ec3d_rhs_step gives their right-hand side with several conducting domains (include/ec3d_hip.h)
         integer(c_int) function ec3d_set_u_rhs(h, rule) bind(C, name="ec3d_set_u_rhs")

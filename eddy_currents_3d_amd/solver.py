@@ -70,11 +70,13 @@ EXPORTS = ["sprsbcgstabwr_", "ec3d_invalidate", "ec3d_create", "ec3d_destroy", "
            "ec3d_multi_vtk_fields_wait", "ec3d_multi_iterate_begin",
            "ec3d_multi_iterate", "ec3d_multi_synchronize", "ec3d_true_residual", "ec3d_multi_true_residual", "ec3d_get_visit_order", "ec3d_probe_csr_multi", "ec3d_multi_spmv", "ec3d_multi_api_calls", "ec3d_multi_plan", "ec3d_multi_halo_rows", "ec3d_rccl_unique_id", "ec3d_multi_create_rank", "ec3d_format_real8_gfortran", "ec3d_multi_iterate_timed", "ec3d_multi_rccl_info",
            "ec3d_set_preconditioner", "ec3d_get_preconditioner", "ec3d_precond_apply", "ec3d_set_u_rhs",
-           "ec3d_set_precond_precision", "ec3d_get_precond_precision"]
+           "ec3d_set_precond_precision", "ec3d_get_precond_precision", "ec3d_set_precond_coarsening",
+           "ec3d_get_precond_coarsening"]
 U_RHS = {"reference": 0, "all": 1}   # EC3D_U_RHS_* of include/ec3d_hip.h
 PRECOND = {"none": 0, "mg": 1, "block-mg": 2}   # EC3D_PRECOND_* of include/ec3d_hip.h
 PRECOND_E_MATRIX, PRECOND_E_COARSE = 20, 21   # ec3d_set_preconditioner's refusals
 PRECOND_PRECISION = {"fp64": 0, "fp32": 1}   # EC3D_PRECOND_FP64 / _FP32 of include/ec3d_hip.h
+PRECOND_COARSENING = {"rediscretize": 0, "aggregate": 1}   # EC3D_COARSEN_REDISCRETIZE / _AGGREGATE
 
 _f64 = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
 _i32 = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
@@ -155,6 +157,8 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.ec3d_set_u_rhs.argtypes = [hp, C.c_int32]
     L.ec3d_set_precond_precision.argtypes = [hp, C.c_int32]
     L.ec3d_get_precond_precision.argtypes = [hp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.ec3d_set_precond_coarsening.argtypes = [hp, C.c_int32]
+    L.ec3d_get_precond_coarsening.argtypes = [hp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), hp]
     L.ec3d_export_csr.argtypes = [hp, C.POINTER(C.c_int32), C.POINTER(C.c_int64), hp, hp, hp]
     L.ec3d_get_cel_bnd.argtypes = [hp, C.c_int, C.POINTER(C.c_int32), hp]
     L.ec3d_get_reduction_geometry.argtypes = [hp, C.c_int, C.POINTER(Geom)]
@@ -540,23 +544,26 @@ class EC3DSolver:
 
     # ---- preconditioner ("mg": a matrix from assemble_poisson; "block-mg": the structured A-V form) -----------
     def set_preconditioner(self, kind: str = "mg", pre: int = 2, post: int = 2, coarse_sweeps: int = 0,
-                           precision: str | None = None):
+                           precision: str | None = None, coarsening: str | None = None):
         """"mg": solves run the right-preconditioned iteration with one multigrid V-cycle as M; "block-mg": the same
         iteration on the A-V system of assemble, M one Galerkin V-cycle per A block and Gauss-Seidel sweeps on U;
         "none": the reference's iteration.  Zeros select the library's defaults.  ``precision`` ("fp64" or "fp32"):
         set_precond_precision(precision) first -- the handle keeps it, unless the call is refused; None leaves the
-        handle's setting as it is.  Refusal: EC3DError with .status PRECOND_E_MATRIX or PRECOND_E_COARSE, the handle unchanged."""
-        if precision is None:
-            _chk(self.L, self.L.ec3d_set_preconditioner(self.h, PRECOND[kind], pre, post, coarse_sweeps),
-                 "ec3d_set_preconditioner")
-            return
-        before = self.precond_precision()[0]
-        self.set_precond_precision(precision)
+        handle's setting as it is.  ``coarsening`` ("rediscretize" or "aggregate"): set_precond_coarsening likewise.
+        Refusal: EC3DError with .status PRECOND_E_MATRIX or PRECOND_E_COARSE, the handle unchanged."""
+        undo = []   # a refusal leaves the handle unchanged, the settings given here included
         try:
+            if precision is not None:
+                undo.append((self.set_precond_precision, self.precond_precision()[0]))
+                self.set_precond_precision(precision)
+            if coarsening is not None:
+                undo.append((self.set_precond_coarsening, self._coarsening_setting()))
+                self.set_precond_coarsening(coarsening)
             _chk(self.L, self.L.ec3d_set_preconditioner(self.h, PRECOND[kind], pre, post, coarse_sweeps),
                  "ec3d_set_preconditioner")
-        except EC3DError:
-            self.set_precond_precision(before)   # a refusal leaves the handle unchanged, the setting included
+        except (EC3DError, ValueError):
+            for setter, before in undo:
+                setter(before)
             raise
 
     def set_precond_precision(self, precision: str = "fp64"):
@@ -575,6 +582,34 @@ class EC3DSolver:
              "ec3d_get_precond_precision")
         name = {v: k for k, v in PRECOND_PRECISION.items()}
         return name[setting.value], name[in_use.value]
+
+    def set_precond_coarsening(self, rule: str = "rediscretize"):
+        """Coarsening rule of the hierarchy the next set_preconditioner("mg") builds: "rediscretize" (default: an axis
+        halves while it is even and >= 8, other boxes are refused with PRECOND_E_COARSE) or "aggregate" (every axis is
+        ceil-halved, levels below the first odd or short one are Galerkin products in band form: every box gets a
+        hierarchy).  Kept across assemblies and set_preconditioner("none"); a hierarchy already set is not rebuilt;
+        "block-mg" ignores it."""
+        if rule not in PRECOND_COARSENING:
+            raise ValueError(f"coarsening must be one of {sorted(PRECOND_COARSENING)}, not {rule!r}")
+        _chk(self.L, self.L.ec3d_set_precond_coarsening(self.h, PRECOND_COARSENING[rule]),
+             "ec3d_set_precond_coarsening")
+
+    def _coarsening_setting(self):
+        setting = C.c_int32(0)
+        _chk(self.L, self.L.ec3d_get_precond_coarsening(self.h, C.byref(setting), None, None),
+             "ec3d_get_precond_coarsening")
+        return {v: k for k, v in PRECOND_COARSENING.items()}[setting.value]
+
+    def precond_coarsening(self):
+        """(setting, in_use, kinds): the handle's setting, the rule of the hierarchy now set ("rediscretize" without
+        one, "aggregate" for "block-mg") and per level of it 0 = the handle's matrix, 1 = rediscretised, 2 = Galerkin."""
+        setting, in_use = C.c_int32(0), C.c_int32(0)
+        levels = len(self.preconditioner()[1])
+        kinds = np.zeros(max(levels, 1), np.int32)
+        _chk(self.L, self.L.ec3d_get_precond_coarsening(self.h, C.byref(setting), C.byref(in_use), kinds.ctypes.data),
+             "ec3d_get_precond_coarsening")
+        name = {v: k for k, v in PRECOND_COARSENING.items()}
+        return name[setting.value], name[in_use.value], [int(k) for k in kinds[:levels]]
 
     def preconditioner(self):
         """(kind, [(sdx, sdy, sdz) per level, finest first])"""

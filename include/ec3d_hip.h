@@ -229,6 +229,29 @@ int ec3d_precond_apply(ec3d_handle h, const double *r, double *z);
 enum { EC3D_PRECOND_FP64 = 0, EC3D_PRECOND_FP32 = 1 };
 int ec3d_set_precond_precision(ec3d_handle h, int32_t precision);
 int ec3d_get_precond_precision(ec3d_handle h, int32_t *setting, int32_t *in_use);
+/* Coarsening rule of EC3D_PRECOND_MG.  EC3D_COARSEN_REDISCRETIZE (default): as above -- an axis halves only while it is
+ * even and >= 8, and a box whose coarsest level stays above 4096 rows is refused (EC3D_PRECOND_E_COARSE).
+ * EC3D_COARSEN_AGGREGATE (opt-in): every box gets a hierarchy.  Every axis whose extent is > 1 is ceil-halved
+ * (aggregates of 2 cells, the last one 1 cell on an odd axis) until a level has <= 4096 rows.  Level l + 1 is a
+ * rediscretisation (1 class byte per row, as above) while no Galerkin level has appeared and every axis of level l is
+ * even and >= 8; from the first level that fails this, level l + 1 and every coarser one is the Galerkin product of
+ * piecewise-constant aggregation in the arithmetic of EC3D_PRECOND_BLOCK_MG (scaled by 1 / (2 * nominal children)),
+ * built on the device in fp64 and kept as seven band streams (56 B per row, 28 B narrowed once under
+ * EC3D_PRECOND_FP32).  The restriction is the mean over the aggregate's actual cells.  Where the default rule halves
+ * every axis at every level (64^3, 48x40x36) both rules build the same hierarchy and M is the same bits; 100^3 or
+ * 500^3 keep their large levels in the 1-byte form, and only a box whose finest level has an odd or short axis
+ * (255^3) pays the band form on level 1, at one eighth of the rows.  EC3D_PRECOND_E_COARSE cannot occur; the
+ * EC3D_PRECOND_E_MATRIX refusals are unchanged.  The setting belongs to the handle and outlives new matrices and
+ * EC3D_PRECOND_NONE; it takes effect at the next ec3d_set_preconditioner and does not rebuild a hierarchy already
+ * set.  EC3D_PRECOND_BLOCK_MG has always aggregated and ignores it.  An unknown value returns 2 and leaves the handle
+ * unchanged.
+ * ec3d_get_precond_coarsening: *setting = the handle's setting; *in_use = the rule of the hierarchy now set
+ * (EC3D_COARSEN_REDISCRETIZE when there is none, EC3D_COARSEN_AGGREGATE for EC3D_PRECOND_BLOCK_MG); level_kinds: one
+ * entry per level of the hierarchy now set (ec3d_get_preconditioner's count): 0 = the handle's matrix,
+ * 1 = rediscretised, 2 = Galerkin.  Any of the three may be NULL. */
+enum { EC3D_COARSEN_REDISCRETIZE = 0, EC3D_COARSEN_AGGREGATE = 1 };
+int ec3d_set_precond_coarsening(ec3d_handle h, int32_t rule);
+int ec3d_get_precond_coarsening(ec3d_handle h, int32_t *setting, int32_t *in_use, int32_t *level_kinds);
 
 /* ------------------------------------------------------------------------------------------
  * 2b. Multi-rank building blocks (z-slab decomposition, one process per GPU).

@@ -1,6 +1,7 @@
 """Time-to-solution of the bar-RHS Poisson solve (BASELINE config 2) with and without the multigrid preconditioner.
 
-    python tools/mg_time_to_solution.py [--sizes 256 512] [--tol 1e-8] [--fixed 200] [--precision fp64|fp32] [--mg-only]
+    python tools/mg_time_to_solution.py [--sizes 256 512] [--tol 1e-8] [--fixed 200] [--precision fp64|fp32]
+                                        [--coarsening rediscretize|aggregate] [--mg-only | --none-only] [--label TEXT]
 
 One JSON line per size: wall time of ec3d_solve_resident to `tol` with MG (after one untimed solve) and its outer
 iterations; the same without a preconditioner -- a full solve where --fixed is 0 or the size is <= 256, otherwise a
@@ -8,7 +9,10 @@ fixed `--fixed` iterations (tol 1e-300) scaled by the reference's iteration coun
 or BASELINE.md section 2b's projection of 7 500 at 512^3), which the line says; and us per V-cycle, from
 ec3d_precond_apply minus ec3d_spmv (both move the same two host vectors; the split by level comes from a
 rocprofv3 --kernel-trace --stats run of this tool, profiles/mg_*.txt).  --precision fp32: the V-cycle in single
-precision (ec3d_set_precond_precision); --mg-only leaves the unpreconditioned solve out."""
+precision (ec3d_set_precond_precision); --coarsening aggregate: the hierarchy of ec3d_set_precond_coarsening, which every
+size has (the line then names each level's kind); a size without a reference count is scaled by the nearest one's,
+in proportion to N, which the line says.  --mg-only leaves the unpreconditioned solve out, --none-only the
+preconditioned one (it then runs on a library without either setter); --label goes into the line as "build"."""
 from __future__ import annotations
 
 import argparse
@@ -25,6 +29,15 @@ sys.path.insert(0, REPO)
 REF_ITERS = {64: 603, 128: 1439, 256: 4097, 512: 7500}
 
 
+def ref_iters(N):
+    """(the reference's iteration count at N^3, how it was got)"""
+    if N in REF_ITERS:
+        return REF_ITERS[N], f"the reference's {REF_ITERS[N]}"
+    near = min(REF_ITERS, key=lambda m: abs(m - N))
+    it = round(REF_ITERS[near] * N / near)
+    return it, f"{it} = the reference's {REF_ITERS[near]} at {near}^3 times {N}/{near}"
+
+
 def timed(fn, reps=1):
     fn()
     t = time.perf_counter()
@@ -39,12 +52,19 @@ def main():
     ap.add_argument("--tol", type=float, default=1e-8)
     ap.add_argument("--fixed", type=int, default=200)
     ap.add_argument("--precision", choices=["fp64", "fp32"], default="fp64")
+    ap.add_argument("--coarsening", choices=["rediscretize", "aggregate"], default="rediscretize")
     ap.add_argument("--mg-only", action="store_true")
+    ap.add_argument("--none-only", action="store_true")
+    ap.add_argument("--label")
     a = ap.parse_args()
     import eddy_currents_3d_amd as E
     from bench import bar_rhs
     for N in a.sizes:
-        out = dict(N=N, tol=a.tol, precision=a.precision)
+        out = dict(N=N, tol=a.tol, precision=a.precision, coarsening=a.coarsening)
+        if a.label:
+            out = dict(build=a.label, **out)
+        if a.none_only:
+            del out["precision"], out["coarsening"]
         b = bar_rhs(N)
         x0 = np.zeros(N ** 3)
         with E.EC3DSolver() as s:
@@ -58,32 +78,37 @@ def main():
                 it, _ = s.solve_resident(tol, itmax)
                 return time.perf_counter() - t, it
 
-            if a.precision == "fp32":   # (fp64 is the default: the tool then also runs on a library without the setter)
-                s.set_precond_precision("fp32")
-            s.set_preconditioner("mg")
-            out["levels"] = s.preconditioner()[1]
-            solve()
-            out["mg_s"], out["mg_iter"] = solve()
-            out["mg_true_residual"] = s.true_residual()[0]
-            r = np.random.Generator(np.random.PCG64(1)).standard_normal(N ** 3)
-            t_apply, _ = timed(lambda: s.precond_apply(r), 3)
-            t_spmv, _ = timed(lambda: s.spmv(r), 3)
-            out["us_per_vcycle"] = round(1e6 * (t_apply - t_spmv), 1)
-            out["mg_us_per_outer_iteration"] = round(1e6 * out["mg_s"] / max(out["mg_iter"], 1), 1)
-            if a.mg_only:
-                print(json.dumps(out), flush=True)
-                continue
-            s.set_preconditioner("none")
-            if a.fixed and N > 256:
-                solve(1e-300, a.fixed - 1)
-                t, it = solve(1e-300, a.fixed - 1)
-                out["none_fixed_iters"], out["none_fixed_s"] = it, t
-                out["none_iter"] = REF_ITERS.get(N)
-                out["none_s"] = t / it * out["none_iter"]
-                out["none_note"] = f"{it} fixed iterations scaled to the reference's {out['none_iter']}"
-            else:
-                out["none_s"], out["none_iter"] = solve()
-        out["speedup"] = round(out["none_s"] / out["mg_s"], 1)
+            if not a.none_only:
+                if a.precision == "fp32":   # (the defaults set nothing: the tool then also runs on a library without the setters)
+                    s.set_precond_precision("fp32")
+                if a.coarsening == "aggregate":
+                    s.set_precond_coarsening("aggregate")
+                    s.set_preconditioner("mg")
+                    out["level_kinds"] = s.precond_coarsening()[2]
+                else:
+                    s.set_preconditioner("mg")
+                out["levels"] = s.preconditioner()[1]
+                solve()
+                out["mg_s"], out["mg_iter"] = solve()
+                out["mg_true_residual"] = s.true_residual()[0]
+                r = np.random.Generator(np.random.PCG64(1)).standard_normal(N ** 3)
+                t_apply, _ = timed(lambda: s.precond_apply(r), 3)
+                t_spmv, _ = timed(lambda: s.spmv(r), 3)
+                out["us_per_vcycle"] = round(1e6 * (t_apply - t_spmv), 1)
+                out["mg_us_per_outer_iteration"] = round(1e6 * out["mg_s"] / max(out["mg_iter"], 1), 1)
+                s.set_preconditioner("none")
+            if not a.mg_only:
+                if a.fixed and N > 256:
+                    solve(1e-300, a.fixed - 1)
+                    t, it = solve(1e-300, a.fixed - 1)
+                    out["none_fixed_iters"], out["none_fixed_s"] = it, t
+                    out["none_iter"], how = ref_iters(N)
+                    out["none_s"] = t / it * out["none_iter"]
+                    out["none_note"] = f"{it} fixed iterations scaled to {how}"
+                else:
+                    out["none_s"], out["none_iter"] = solve()
+        if "none_s" in out and "mg_s" in out:
+            out["speedup"] = round(out["none_s"] / out["mg_s"], 1)
         print(json.dumps(out), flush=True)
 
 
