@@ -243,6 +243,8 @@ void ec3d_free_matrix(ec3d_ctx *c)
     ec3d_free_output(c);
     ec3d_mg_free(c);
     c->poisson_full = false;
+    c->from_csr = false;
+    c->precond_grid[0] = c->precond_grid[1] = c->precond_grid[2] = 0;
     c->have_matrix = false;
     if (c->vplace_len > 0 && c->vec_own) { // keep the placement the search chose for the next matrix of this size
         c->parked_vec = std::move(c->vec_own);
@@ -1550,15 +1552,20 @@ extern "C" int ec3d_probe_csr_multi(int32_t n, const double *valA, const int32_t
 extern "C" int ec3d_set_matrix_csr(ec3d_handle c, int32_t n, const double *valA, const int32_t *irow,
                                    const int32_t *jcol)
 {
+    int rc;
     if (c->use_sav && c->use_dict) { // the reference's A-V matrix: class-coded stencil form
         SavHost S;
-        if (ec3d_csr_to_sav_host(n, valA, irow, jcol, S) == 0) return ec3d_upload_sav(c, S);
+        if (ec3d_csr_to_sav_host(n, valA, irow, jcol, S) == 0) {
+            if ((rc = ec3d_upload_sav(c, S)) == 0) c->from_csr = true;
+            return rc;
+        }
     }
     HostMatrix M;
-    int rc = ec3d_csr_to_host_matrix(n, valA, irow, jcol, M);
+    rc = ec3d_csr_to_host_matrix(n, valA, irow, jcol, M);
     if (rc) return rc;
     if (c->use_dict) ec3d_build_dictionary_host(M);
-    return ec3d_upload_matrix(c, M);
+    if ((rc = ec3d_upload_matrix(c, M)) == 0) c->from_csr = true; // (what ec3d_set_precond_grid accepts)
+    return rc;
 }
 
 extern "C" int ec3d_assemble(ec3d_handle c, int32_t sdx, int32_t sdy, int32_t sdz, const int8_t *geoPHYS,

@@ -448,6 +448,10 @@ struct ec3d_ctx {
     bool poisson_full = false;
     double poisson_bnd[6] = {0, 0, 0, 0, 0, 0}, poisson_delta[3] = {0, 0, 0};
     bool in_multi = false;
+    // the matrix came from ec3d_set_matrix_csr; precond_grid: the box the caller said it is a 7-point operator on
+    // (ec3d_set_precond_grid; zeros: none).  Both belong to the matrix: ec3d_free_matrix clears them
+    bool from_csr = false;
+    int32_t precond_grid[3] = {0, 0, 0};
     ec3d_mg *mg = nullptr; // ec3d_set_preconditioner(EC3D_PRECOND_MG): solves run the preconditioned iteration
     int precond_precision = 0; // EC3D_PRECOND_FP64 / _FP32: what the next ec3d_set_preconditioner builds (ec3d_set_precond_precision)
     int precond_coarsening = 0; // EC3D_COARSEN_REDISCRETIZE / _AGGREGATE: likewise (ec3d_set_precond_coarsening)

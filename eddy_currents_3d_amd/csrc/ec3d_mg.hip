@@ -11,6 +11,13 @@
 // (k_mg_galerkin, fp64, once at set-up), kept as seven band streams; the restriction is then the mean over the
 // aggregate's actual children (an odd axis ends in an aggregate of one cell).  tests/mg_numpy_agg.py restates it.
 //
+// A 7-point matrix from ec3d_set_matrix_csr whose box the caller named (ec3d_set_precond_grid) gets the same cycle: the
+// matrix is checked on the device (k_mg_check_grid: no tail, the box's offsets only, zero wrap slots, a nonzero finite
+// diagonal), level 0 is the handle's dictionary form itself when it has the seven offsets and at most EC3D_MG_MAXCLS
+// classes, else one gathered copy of seven band streams the hierarchy owns (k_mg_gather; 56 B per row on top of the
+// handle's matrix: variable coefficients with many classes, fewer than seven bands, ec3d_set_format(h, 0)), and every
+// coarse level is a Galerkin product over ceil-halved dims (ec3d_mg_plan_matrix).  tests/mg_numpy_csr.py restates it.
+//
 // One V-cycle from x = 0 on level l (tests/mg_numpy.py restates it operation by operation; no reduction enters it, so
 // the device result is bit-identical to the restatement):
 //   w = pre sweeps of (red, black) on b, the first red half from zero being w = b / d on red, 0 on black (k_mg_smooth);
@@ -120,6 +127,8 @@ template <> struct MgNarrowed<float> {
 template <class T> struct PoissonMg : MgNarrowed<T> {
     std::vector<MgGrid> grid;
     MgOp op0{};           // level 0 in fp64, from the handle's matrix: what the outer SpMV + dot launch reads
+    DevBuf<double> bands0; // a CSR matrix that is no direct view: level 0's gathered band streams, which op0 points to
+                           // (kept by an fp32 hierarchy too: the outer SpMV + dot reads them)
     std::vector<MgLevelT<T>> lev;
     DevBuf<T> vec;        // coarse x, w, b per level, then the fine w, [b0,] p^, s^
     T *w0 = nullptr, *ph = nullptr, *sh = nullptr;
@@ -436,6 +445,67 @@ __global__ __launch_bounds__(256) void k_mg_galerkin(MgOp F, MgOp C, int fx, int
             }
 #pragma unroll
     for (int q = 0; q < 7; ++q) bands[(size_t)q * C.n_pad + rc] = (q == 3 ? D : B[q]) * scale;
+}
+
+// ---- a matrix from ec3d_set_matrix_csr as level 0 (ec3d_set_precond_grid) -------------------------------------------
+// The handle's stored matrix as the checks and the gather read it: band b of row r from the dictionary or the band
+// streams, and the slot q (offset order -z, -y, -x, diag, +x, +y, +z) of every band, -1 for an offset that is not the box's.
+struct MgSrc {
+    const double *bands;      // band form: bands[b * n_pad + r]
+    const uint8_t *cls;       // dictionary form (cls != nullptr): table[cls[r] * nb + b]
+    const double *table;
+    const int32_t *tail_id;   // nullptr: the matrix has no tail
+    int nb;
+    int slot[EC3D_MAXB];      // band b -> q, or -1
+    int band[7];              // q -> band, or -1 (a zero stream)
+    int sdx, sdy;
+    int64_t n, n_pad, kdz;
+};
+__device__ __forceinline__ double src_coef(const MgSrc &S, int b, int64_t r)
+{
+    return S.cls ? S.table[(size_t)S.cls[r] * S.nb + b] : S.bands[(size_t)b * S.n_pad + r];
+}
+// why a row is no row of a 7-point operator on the box, in the order the set-up states them
+enum { MG_BAD_TAIL = 0, MG_BAD_OFFSET = 1, MG_BAD_WRAP = 2, MG_BAD_DIAG = 3 };
+// One thread per row.  out[0]: the kinds found, one bit each (atomic or); out[1]: the smallest row * 4 + kind (atomic
+// min), so the first offending row and the first reason it offends; both untouched by a matrix that passes.  Bytes per
+// row: the stored form once (1 class byte, or 8 nb) + 4 with a tail.
+__global__ __launch_bounds__(256) void k_mg_check_grid(MgSrc S, unsigned long long *__restrict__ out)
+{
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= S.n) return;
+    const int i = (int)(r % S.sdx), j = (int)((r % S.kdz) / S.sdx);
+    int bad = -1;
+    const auto note = [&](int kind) { if (bad < 0 || kind < bad) bad = kind; };
+    if (S.tail_id && S.tail_id[r] >= 0) note(MG_BAD_TAIL);
+    double d = 0.0;
+    for (int b = 0; b < S.nb; ++b) {
+        const double v = src_coef(S, b, r);
+        const int q = S.slot[b];
+        if (q < 0) {
+            if (v != 0.0) note(MG_BAD_OFFSET);
+            continue;
+        }
+        if (q == 3) d = v;
+        // a slot whose neighbour lies beyond the box along x or y is another cell of the numbering (the z slots would be
+        // columns outside the matrix)
+        const bool wrap = (q == 2 && i == 0) || (q == 4 && i == S.sdx - 1) || (q == 1 && j == 0) || (q == 5 && j == S.sdy - 1);
+        if (wrap && v != 0.0) note(MG_BAD_WRAP);
+    }
+    if (d == 0.0 || !isfinite(d)) note(MG_BAD_DIAG);
+    if (bad < 0) return;
+    atomicOr(&out[0], 1ull << bad);
+    atomicMin(&out[1], (unsigned long long)r * 4ull + (unsigned long long)bad);
+}
+
+// Level 0's seven band streams gathered from the stored form, bits unchanged, a band the matrix does not have as zeros;
+// rows [n, n_pad) as stored (zeros).  Bytes per row: the stored form once, 56 written.
+__global__ __launch_bounds__(256) void k_mg_gather(MgSrc S, double *__restrict__ out)
+{
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= S.n_pad) return;
+#pragma unroll
+    for (int q = 0; q < 7; ++q) out[(size_t)q * S.n_pad + r] = S.band[q] >= 0 ? src_coef(S, S.band[q], r) : 0.0;
 }
 
 // ---- outer iteration ------------------------------------------------------------------------------------------------
@@ -1234,29 +1304,117 @@ static int set_block_mg(ec3d_ctx *c, ec3d_mg &m)
     return 0;
 }
 
+// Level 0 over a matrix from ec3d_set_matrix_csr that the caller called a 7-point operator on an sdx x sdy x sdz box
+// (ec3d_set_precond_grid): the matrix is checked where it lies, on the device and in its stored form, and op0 becomes a
+// view of the handle's dictionary form -- as op_of makes it for an assembled matrix -- when that has exactly the seven
+// offsets and a table the smoothers' LDS holds, else seven band streams gathered once into bands0.
+static int csr_level0(ec3d_ctx *c, int sdx, int sdy, int sdz, MgOp &op0, DevBuf<double> &bands0)
+{
+    const DevMatrix &A = c->A;
+    const char *const who = "ec3d_set_preconditioner: ";
+    if (A.sav)
+        return mg_refuse(std::string(who) + "the matrix was recognised as the structured A-V form, which is no "
+                         "single-component operator on the box of ec3d_set_precond_grid");
+    const int64_t kdz = (int64_t)sdx * sdy;
+    const int64_t want[7] = {-kdz, -(int64_t)sdx, -1, 0, 1, sdx, kdz};
+    MgSrc S{};
+    S.bands = A.ncls > 0 ? nullptr : A.bands.get();
+    S.cls = A.ncls > 0 ? A.cls.get() : nullptr;
+    S.table = A.table;
+    S.tail_id = A.ntail > 0 ? A.tail_id.get() : nullptr;
+    S.nb = A.nb;
+    S.sdx = sdx; S.sdy = sdy;
+    S.n = A.n; S.n_pad = A.n_pad; S.kdz = kdz;
+    for (int q = 0; q < 7; ++q) S.band[q] = -1;
+    int stray = -1; // a band whose offset is not the box's
+    for (int b = 0; b < A.nb; ++b) {
+        S.slot[b] = -1;
+        for (int q = 0; q < 7; ++q)
+            if (A.off[b] == want[q]) S.slot[b] = q;
+        if (S.slot[b] >= 0) S.band[S.slot[b]] = b;
+        else if (stray < 0) stray = b;
+    }
+    DevBuf<unsigned long long> found;
+    unsigned long long res[2] = {0ull, ~0ull};
+    if (found.alloc(2) != hipSuccess) return mg_fail(MG_OOM);
+    if (hipMemcpyAsync(found, res, sizeof res, hipMemcpyHostToDevice, c->stream) != hipSuccess) return mg_fail(MG_BUILD);
+    k_mg_check_grid<<<blocks_of(S.n), 256, 0, c->stream>>>(S, found);
+    if (hipGetLastError() != hipSuccess ||
+        hipMemcpyAsync(res, found, sizeof res, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess)
+        return mg_fail(MG_BUILD);
+    const std::string box = std::to_string(sdx) + "x" + std::to_string(sdy) + "x" + std::to_string(sdz);
+    if (res[0]) {
+        const std::string row = "row " + std::to_string(res[1] / 4 + 1) + " (1-based, the first such row) ";
+        switch ((int)(res[1] & 3)) {
+        case MG_BAD_TAIL:
+            return mg_refuse(who + row + "has entries outside the matrix's bands (" + std::to_string(A.ntail) +
+                             " rows with a tail): not a 7-point operator on the " + box + " box");
+        case MG_BAD_OFFSET:
+            return mg_refuse(who + row + "has an entry at a column offset that is none of 0, +-1, +-" + std::to_string(sdx) +
+                             ", +-" + std::to_string(kdz) + ", the offsets of the " + box + " box");
+        case MG_BAD_WRAP:
+            return mg_refuse(who + row + "couples to a cell across an x or y face of the " + box +
+                             " box (a nonzero coefficient where the neighbour lies beyond the box)");
+        default:
+            return mg_refuse(who + row + "has a zero or non-finite diagonal");
+        }
+    }
+    if (stray >= 0) // (every coefficient of it is zero: no row names it)
+        return mg_refuse(std::string(who) + "the matrix has a band at column offset " + std::to_string(A.off[stray]) +
+                         ", none of the offsets of the " + box + " box (row 1 on)");
+    bool seven = A.nb == 7;
+    for (int b = 0; seven && b < 7; ++b) seven = S.slot[b] == b;
+    if (A.ncls > 0 && A.ncls <= EC3D_MG_MAXCLS && seven) {
+        op0 = op_of(A, sdx, sdy, sdz);
+        return 0;
+    }
+    if (bands0.alloc((size_t)7 * A.n_pad) != hipSuccess) return mg_fail(MG_OOM);
+    k_mg_gather<<<blocks_of(A.n_pad), 256, 0, c->stream>>>(S, bands0);
+    if (hipGetLastError() != hipSuccess) return mg_fail(MG_BUILD);
+    op0 = MgOp{};
+    op0.sdx = sdx; op0.sdy = sdy; op0.sdz = sdz;
+    op0.n = A.n; op0.n_pad = A.n_pad; op0.kdz = kdz;
+    op0.bands = bands0;
+    return 0;
+}
+
 // T: the precision of the cycle (float: EC3D_PRECOND_FP32)
 template <class T> static int set_poisson_mg(ec3d_ctx *c, ec3d_mg &m)
 {
     constexpr bool F32 = std::is_same_v<T, float>;
-    if (!c->poisson_full || !own_handle(c))
+    // a matrix from ec3d_set_matrix_csr whose box the caller named: the hierarchy is made from the matrix alone
+    const bool csr = c->from_csr && c->precond_grid[0] > 0;
+    if (!(c->poisson_full || csr) || !own_handle(c))
         return mg_refuse("ec3d_set_preconditioner: the multigrid preconditioner needs a matrix from ec3d_assemble_poisson "
                          "on a handle of its own (not A-V, CSR, a slab or a handle of ec3d_multi)");
+    const int sdx0 = csr ? c->precond_grid[0] : c->sdx, sdy0 = csr ? c->precond_grid[1] : c->sdy,
+              sdz0 = csr ? c->precond_grid[2] : c->sdz;
     MgPlan plan;
     const std::vector<std::array<int, 3>> &dims = plan.dims;
-    if (!ec3d_mg_plan(c->sdx, c->sdy, c->sdz, c->precond_coarsening == EC3D_COARSEN_AGGREGATE, EC3D_MG_COARSE_ROWS, plan)) {
+    if (csr) {
+        ec3d_mg_plan_matrix(sdx0, sdy0, sdz0, EC3D_MG_COARSE_ROWS, plan);
+        m.coarsening = EC3D_COARSEN_AGGREGATE; // whatever the handle's setting says
+    } else if (!ec3d_mg_plan(sdx0, sdy0, sdz0, c->precond_coarsening == EC3D_COARSEN_AGGREGATE, EC3D_MG_COARSE_ROWS, plan)) {
         const auto d = dims.back();
         return mg_refuse("ec3d_set_preconditioner: no axis of the " + std::to_string(d[0]) + "x" + std::to_string(d[1]) +
                          "x" + std::to_string(d[2]) + " level halves (even and >= 8) and it has more than " +
                          std::to_string(EC3D_MG_COARSE_ROWS) + " rows, the coarse solver's cap", EC3D_PRECOND_E_COARSE);
     }
-    if (c->A.ncls > EC3D_MG_MAXCLS)
+    if (!csr && c->A.ncls > EC3D_MG_MAXCLS)
         return mg_refuse("ec3d_set_preconditioner: more dictionary classes than the smoother's table holds");
     PoissonMg<T> &h = m.h.emplace<PoissonMg<T>>();
     const int L = (int)dims.size();
     h.grid.resize((size_t)L);
     h.lev.resize((size_t)L);
     std::vector<MgOp> op((size_t)L); // every level in fp64, as assembled
-    op[0] = h.op0 = op_of(c->A, c->sdx, c->sdy, c->sdz);
+    if (csr) {
+        const int rc = csr_level0(c, sdx0, sdy0, sdz0, h.op0, h.bands0);
+        if (rc) return rc;
+        op[0] = h.op0;
+    } else {
+        op[0] = h.op0 = op_of(c->A, c->sdx, c->sdy, c->sdz);
+    }
     for (int a = 0; a < 3; ++a) h.grid[0].delta[a] = c->poisson_delta[a];
     int64_t coarse_len = 0;
     for (int l = 1; l < L; ++l) {
@@ -1361,6 +1519,36 @@ void ec3d_mg_free(ec3d_ctx *c)
 {
     delete c->mg; // (its levels' matrices and every buffer of the hierarchy with it)
     c->mg = nullptr;
+}
+
+extern "C" int ec3d_set_precond_grid(ec3d_handle c, int32_t sdx, int32_t sdy, int32_t sdz)
+{
+    const char *why = nullptr;
+    if (c && sdx == 0 && sdy == 0 && sdz == 0) { // no grid: what a new matrix leaves, for a caller that takes its word back
+        c->precond_grid[0] = c->precond_grid[1] = c->precond_grid[2] = 0;
+        return 0;
+    }
+    if (!c) why = "null handle";
+    else if (!c->have_matrix || !c->from_csr) why = "the handle holds no matrix from ec3d_set_matrix_csr";
+    else if (!own_handle(c)) why = "not on a slab or a handle of ec3d_multi";
+    else if (sdx < 2 || sdy < 2 || sdz < 2) why = "every extent must be >= 2";
+    else if ((int64_t)sdx * sdy * sdz != c->n_ref) why = "sdx * sdy * sdz is not the matrix's n";
+    if (why) {
+        ec3d_set_error(std::string("ec3d_set_precond_grid: ") + why);
+        return 2;
+    }
+    c->precond_grid[0] = sdx; c->precond_grid[1] = sdy; c->precond_grid[2] = sdz;
+    return 0;
+}
+
+extern "C" int ec3d_get_precond_grid(ec3d_handle c, int32_t *dims)
+{
+    if (!c) {
+        ec3d_set_error("ec3d_get_precond_grid: null handle");
+        return 2;
+    }
+    for (int a = 0; dims && a < 3; ++a) dims[a] = c->precond_grid[a];
+    return 0;
 }
 
 extern "C" int ec3d_set_preconditioner(ec3d_handle c, int kind, int32_t pre, int32_t post, int32_t coarse_sweeps)

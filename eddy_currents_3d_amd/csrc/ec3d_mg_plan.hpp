@@ -13,6 +13,10 @@
 // preconditions hold); from the first level that fails this, level l + 1 and every coarser one is the Galerkin product
 // of piecewise-constant aggregation.  Where the default rule halves every axis at every level the two rules give the
 // same hierarchy.
+//
+// A 7-point matrix supplied as CSR with its box (ec3d_set_precond_grid; ec3d_mg_plan_matrix): there is no BND and no
+// spacing to rediscretise with, so the dims are the aggregate rule's ceil-halving and every coarse level is a Galerkin
+// product, whatever the parity of the axes.  tests/test_mg_csr_host.py checks it against tests/mg_numpy_csr.py.
 #pragma once
 #include <array>
 #include <cstdint>
@@ -49,5 +53,20 @@ inline bool ec3d_mg_plan(int sdx, int sdy, int sdz, bool aggregate, int64_t cap,
         }
         p.dims.push_back(e);
         p.kinds.push_back(galerkin ? EC3D_MG_LEVEL_GALERKIN : EC3D_MG_LEVEL_REDISCRETIZED);
+    }
+}
+
+// The hierarchy over a matrix that is all there is (no assembly to rerun): ceil-halving, every coarse level Galerkin.
+inline void ec3d_mg_plan_matrix(int sdx, int sdy, int sdz, int64_t cap, MgPlan &p)
+{
+    p.dims.assign(1, {sdx, sdy, sdz});
+    p.kinds.assign(1, EC3D_MG_LEVEL_MATRIX);
+    for (;;) {
+        std::array<int, 3> e = p.dims.back();
+        if ((int64_t)e[0] * e[1] * e[2] <= cap) return;
+        for (int a = 0; a < 3; ++a)
+            if (e[a] > 1) e[a] = (e[a] + 1) / 2;
+        p.dims.push_back(e);
+        p.kinds.push_back(EC3D_MG_LEVEL_GALERKIN);
     }
 }

@@ -23,7 +23,8 @@ module ec3d_hip
               EC3D_PRECOND_NONE, EC3D_PRECOND_MG, EC3D_PRECOND_BLOCK_MG, &
               ec3d_set_u_rhs, EC3D_U_RHS_REFERENCE, EC3D_U_RHS_ALL, &
               ec3d_set_precond_precision, ec3d_get_precond_precision, EC3D_PRECOND_FP64, EC3D_PRECOND_FP32, &
-              ec3d_set_precond_coarsening, ec3d_get_precond_coarsening, EC3D_COARSEN_REDISCRETIZE, EC3D_COARSEN_AGGREGATE
+              ec3d_set_precond_coarsening, ec3d_get_precond_coarsening, EC3D_COARSEN_REDISCRETIZE, EC3D_COARSEN_AGGREGATE, &
+              ec3d_set_precond_grid, ec3d_get_precond_grid
 
     integer(c_int), parameter :: EC3D_VEC_X = 0, EC3D_VEC_B = 1   ! Uaf, Jaf
     integer(c_int), parameter :: EC3D_PRECOND_NONE = 0, EC3D_PRECOND_MG = 1   ! ec3d_set_preconditioner
@@ -207,6 +208,19 @@ module ec3d_hip
             type(c_ptr), value :: h
             integer(c_int32_t), intent(out) :: setting, in_use
             type(c_ptr), value :: level_kinds
+        end function
+        ! the matrix of ec3d_set_matrix_csr is a 7-point operator on an sdx x sdy x sdz box, r = i + j sdx + k sdx sdy:
+        ! EC3D_PRECOND_MG then builds its hierarchy from the matrix alone (include/ec3d_hip.h); cleared by a new matrix
+        integer(c_int) function ec3d_set_precond_grid(h, sdx, sdy, sdz) bind(C, name="ec3d_set_precond_grid")
+            import :: c_ptr, c_int, c_int32_t
+            type(c_ptr), value :: h
+            integer(c_int32_t), value :: sdx, sdy, sdz
+        end function
+        ! dims: the grid now set, zeros when none
+        integer(c_int) function ec3d_get_precond_grid(h, dims) bind(C, name="ec3d_get_precond_grid")
+            import :: c_ptr, c_int, c_int32_t
+            type(c_ptr), value :: h
+            integer(c_int32_t), intent(out) :: dims(3)
         end function
         ! U rows ec3d_rhs_step gives their right-hand side with several conducting domains (include/ec3d_hip.h)
         integer(c_int) function ec3d_set_u_rhs(h, rule) bind(C, name="ec3d_set_u_rhs")

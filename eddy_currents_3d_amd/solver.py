@@ -71,7 +71,7 @@ EXPORTS = ["sprsbcgstabwr_", "ec3d_invalidate", "ec3d_create", "ec3d_destroy", "
            "ec3d_multi_iterate", "ec3d_multi_synchronize", "ec3d_true_residual", "ec3d_multi_true_residual", "ec3d_get_visit_order", "ec3d_probe_csr_multi", "ec3d_multi_spmv", "ec3d_multi_api_calls", "ec3d_multi_plan", "ec3d_multi_halo_rows", "ec3d_rccl_unique_id", "ec3d_multi_create_rank", "ec3d_format_real8_gfortran", "ec3d_multi_iterate_timed", "ec3d_multi_rccl_info",
            "ec3d_set_preconditioner", "ec3d_get_preconditioner", "ec3d_precond_apply", "ec3d_set_u_rhs",
            "ec3d_set_precond_precision", "ec3d_get_precond_precision", "ec3d_set_precond_coarsening",
-           "ec3d_get_precond_coarsening"]
+           "ec3d_get_precond_coarsening", "ec3d_set_precond_grid", "ec3d_get_precond_grid"]
 U_RHS = {"reference": 0, "all": 1}   # EC3D_U_RHS_* of include/ec3d_hip.h
 PRECOND = {"none": 0, "mg": 1, "block-mg": 2}   # EC3D_PRECOND_* of include/ec3d_hip.h
 PRECOND_E_MATRIX, PRECOND_E_COARSE = 20, 21   # ec3d_set_preconditioner's refusals
@@ -159,6 +159,8 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.ec3d_get_precond_precision.argtypes = [hp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.ec3d_set_precond_coarsening.argtypes = [hp, C.c_int32]
     L.ec3d_get_precond_coarsening.argtypes = [hp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), hp]
+    L.ec3d_set_precond_grid.argtypes = [hp, C.c_int32, C.c_int32, C.c_int32]
+    L.ec3d_get_precond_grid.argtypes = [hp, hp]
     L.ec3d_export_csr.argtypes = [hp, C.POINTER(C.c_int32), C.POINTER(C.c_int64), hp, hp, hp]
     L.ec3d_get_cel_bnd.argtypes = [hp, C.c_int, C.POINTER(C.c_int32), hp]
     L.ec3d_get_reduction_geometry.argtypes = [hp, C.c_int, C.POINTER(Geom)]
@@ -542,15 +544,19 @@ class EC3DSolver:
             raise ValueError(f"u_rhs must be one of {sorted(U_RHS)}, not {rule!r}")
         _chk(self.L, self.L.ec3d_set_u_rhs(self.h, U_RHS[rule]), "ec3d_set_u_rhs")
 
-    # ---- preconditioner ("mg": a matrix from assemble_poisson; "block-mg": the structured A-V form) -----------
+    # ---- preconditioner ("mg": a matrix from assemble_poisson, or a 7-point matrix from set_matrix_csr with its grid;
+    # "block-mg": the structured A-V form) ------------------------------------------------------------------------
     def set_preconditioner(self, kind: str = "mg", pre: int = 2, post: int = 2, coarse_sweeps: int = 0,
-                           precision: str | None = None, coarsening: str | None = None):
+                           precision: str | None = None, coarsening: str | None = None, grid=None):
         """"mg": solves run the right-preconditioned iteration with one multigrid V-cycle as M; "block-mg": the same
         iteration on the A-V system of assemble, M one Galerkin V-cycle per A block and Gauss-Seidel sweeps on U;
         "none": the reference's iteration.  Zeros select the library's defaults.  ``precision`` ("fp64" or "fp32"):
         set_precond_precision(precision) first -- the handle keeps it, unless the call is refused; None leaves the
         handle's setting as it is.  ``coarsening`` ("rediscretize" or "aggregate"): set_precond_coarsening likewise.
-        Refusal: EC3DError with .status PRECOND_E_MATRIX or PRECOND_E_COARSE, the handle unchanged."""
+        ``grid`` ((sdx, sdy, sdz)): set_precond_grid(*grid) likewise -- the matrix from set_matrix_csr is a 7-point
+        operator on that box, and "mg" builds its hierarchy from the matrix alone.
+        Refusal: EC3DError with .status PRECOND_E_MATRIX or PRECOND_E_COARSE (2 for a grid that does not fit the
+        matrix), the handle unchanged."""
         undo = []   # a refusal leaves the handle unchanged, the settings given here included
         try:
             if precision is not None:
@@ -559,6 +565,10 @@ class EC3DSolver:
             if coarsening is not None:
                 undo.append((self.set_precond_coarsening, self._coarsening_setting()))
                 self.set_precond_coarsening(coarsening)
+            if grid is not None:
+                before = self.precond_grid()
+                self.set_precond_grid(*grid)
+                undo.append((lambda g: self.set_precond_grid(*g), before or (0, 0, 0)))
             _chk(self.L, self.L.ec3d_set_preconditioner(self.h, PRECOND[kind], pre, post, coarse_sweeps),
                  "ec3d_set_preconditioner")
         except (EC3DError, ValueError):
@@ -593,6 +603,19 @@ class EC3DSolver:
             raise ValueError(f"coarsening must be one of {sorted(PRECOND_COARSENING)}, not {rule!r}")
         _chk(self.L, self.L.ec3d_set_precond_coarsening(self.h, PRECOND_COARSENING[rule]),
              "ec3d_set_precond_coarsening")
+
+    def set_precond_grid(self, sdx: int, sdy: int, sdz: int):
+        """The matrix set_matrix_csr put on the handle is a 7-point operator on an sdx x sdy x sdz box, rows numbered
+        r = i + j sdx + k sdx sdy: set_preconditioner("mg") then builds a hierarchy from it (all coarse levels Galerkin)
+        instead of refusing.  Belongs to the matrix: a new matrix or assembly clears it; (0, 0, 0) clears it too.
+        EC3DError with .status 2, nothing changed: no matrix from set_matrix_csr, an extent < 2, sdx sdy sdz != n."""
+        _chk(self.L, self.L.ec3d_set_precond_grid(self.h, int(sdx), int(sdy), int(sdz)), "ec3d_set_precond_grid")
+
+    def precond_grid(self):
+        """(sdx, sdy, sdz) as set_precond_grid left it, or None."""
+        dims = np.zeros(3, np.int32)
+        _chk(self.L, self.L.ec3d_get_precond_grid(self.h, dims.ctypes.data), "ec3d_get_precond_grid")
+        return tuple(int(a) for a in dims) if dims.any() else None
 
     def _coarsening_setting(self):
         setting = C.c_int32(0)

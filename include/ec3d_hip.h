@@ -190,8 +190,9 @@ int ec3d_get_row_map(ec3d_handle h, int32_t *ref_to_dev);
  * own: every coarser level reruns that assembly at half the cells and twice the spacing on each axis that is
  * even and >= 8 (same BND), until no axis halves or a level has <= 4096 rows.  Zeros select the defaults
  * (pre = post = 2, coarse_sweeps = 16).  The hierarchy is built at once and freed by ec3d_destroy, by a new
- * matrix or by EC3D_PRECOND_NONE.  Refused, with the handle left as it was: EC3D_PRECOND_E_MATRIX (A-V, CSR,
- * a slab, a handle of ec3d_multi), EC3D_PRECOND_E_COARSE (the coarsest level has > 4096 rows). */
+ * matrix or by EC3D_PRECOND_NONE.  Refused, with the handle left as it was: EC3D_PRECOND_E_MATRIX (A-V, CSR
+ * without ec3d_set_precond_grid, a slab, a handle of ec3d_multi), EC3D_PRECOND_E_COARSE (the coarsest level has
+ * > 4096 rows). */
 /* EC3D_PRECOND_BLOCK_MG: the same outer iteration on the structured A-V form (ec3d_assemble with the structured
  * form on, an undivided single-GPU handle), v = A p^ and t = A s^ by the full operator.  M is block diagonal over
  * [Ax | Ay | Az | U]; the A-U couplings are left out of M.  The three A blocks have the same band coefficients in every
@@ -252,6 +253,33 @@ int ec3d_get_precond_precision(ec3d_handle h, int32_t *setting, int32_t *in_use)
 enum { EC3D_COARSEN_REDISCRETIZE = 0, EC3D_COARSEN_AGGREGATE = 1 };
 int ec3d_set_precond_coarsening(ec3d_handle h, int32_t rule);
 int ec3d_get_precond_coarsening(ec3d_handle h, int32_t *setting, int32_t *in_use, int32_t *level_kinds);
+/* EC3D_PRECOND_MG for a matrix the caller brings.  ec3d_set_precond_grid says that the matrix ec3d_set_matrix_csr put
+ * on the handle is a 7-point operator on an sdx x sdy x sdz box, rows numbered as the reference numbers cells,
+ * r = i + j * sdx + k * sdx * sdy; its coefficients may vary from cell to cell and it need not be symmetric.  The
+ * statement belongs to the matrix, not to the handle: a new matrix (ec3d_set_matrix_csr, any assembly) clears it.
+ * It returns 2 with a message and changes nothing when the handle holds no matrix from ec3d_set_matrix_csr, is a slab
+ * or a handle of ec3d_multi, an extent is < 2, or sdx * sdy * sdz != n; only sdx = sdy = sdz = 0 is accepted beside
+ * a box, and takes the statement back (no grid, as after a new matrix).  Nothing is checked or built by the call, and
+ * a hierarchy already set stays.
+ * With a grid set, ec3d_set_preconditioner(h, EC3D_PRECOND_MG, ...) builds a hierarchy from the matrix alone instead of
+ * refusing.  First the matrix is checked on the device, in its stored form; EC3D_PRECOND_E_MATRIX, the handle as it
+ * was and a message naming the first offending row (1-based) unless: no row has a tail entry; every band offset is one
+ * of 0, +-1, +-sdx, +-sdx*sdy (fewer than seven bands is fine: a missing band is zeros); the slots whose neighbour
+ * lies beyond an x or y face (-1 at i = 0, +1 at i = sdx - 1, -sdx at j = 0, +sdx at j = sdy - 1) are zero; every
+ * row's diagonal is nonzero and finite.  A matrix recognised as the structured A-V form is refused likewise, and so
+ * is EC3D_PRECOND_BLOCK_MG on any CSR handle, grid or not.  Level 0 is the handle's own dictionary form -- no copy,
+ * 1 class byte per row -- when that has exactly the seven offsets and at most 32 classes; otherwise (variable
+ * coefficients with more classes, fewer than seven bands, ec3d_set_format(h, 0)) the seven band streams are gathered
+ * once into a copy the hierarchy owns: 56 B per row on top of the handle's matrix, released with the hierarchy, and
+ * kept under EC3D_PRECOND_FP32 too (the outer iteration's A p^ reads it) beside the 28 B per row narrowed from it.
+ * Level dims are EC3D_COARSEN_AGGREGATE's ceil-halving until a level has <= 4096 rows, and every coarse level is a
+ * Galerkin product (there is no BND and no spacing to rediscretise with): ec3d_get_precond_coarsening reports
+ * in_use = EC3D_COARSEN_AGGREGATE and level kinds 0, 2, 2, ...  The handle's own coarsening setting is ignored on this
+ * path and left as it is; EC3D_PRECOND_E_COARSE cannot occur; ec3d_set_precond_precision applies as above.  Without
+ * the call everything is as before: EC3D_PRECOND_MG on a CSR handle is refused with EC3D_PRECOND_E_MATRIX.
+ * ec3d_get_precond_grid: dims[0..2] = the grid now set, zeros when none. */
+int ec3d_set_precond_grid(ec3d_handle h, int32_t sdx, int32_t sdy, int32_t sdz);
+int ec3d_get_precond_grid(ec3d_handle h, int32_t *dims /* 3; zeros when none */);
 
 /* ------------------------------------------------------------------------------------------
  * 2b. Multi-rank building blocks (z-slab decomposition, one process per GPU).

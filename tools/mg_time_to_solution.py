@@ -2,6 +2,7 @@
 
     python tools/mg_time_to_solution.py [--sizes 256 512] [--tol 1e-8] [--fixed 200] [--precision fp64|fp32]
                                         [--coarsening rediscretize|aggregate] [--mg-only | --none-only] [--label TEXT]
+                                        [--csr jump|convect]
 
 One JSON line per size: wall time of ec3d_solve_resident to `tol` with MG (after one untimed solve) and its outer
 iterations; the same without a preconditioner -- a full solve where --fixed is 0 or the size is <= 256, otherwise a
@@ -12,7 +13,13 @@ rocprofv3 --kernel-trace --stats run of this tool, profiles/mg_*.txt).  --precis
 precision (ec3d_set_precond_precision); --coarsening aggregate: the hierarchy of ec3d_set_precond_coarsening, which every
 size has (the line then names each level's kind); a size without a reference count is scaled by the nearest one's,
 in proportion to N, which the line says.  --mg-only leaves the unpreconditioned solve out, --none-only the
-preconditioned one (it then runs on a library without either setter); --label goes into the line as "build"."""
+preconditioned one (it then runs on a library without either setter); --label goes into the line as "build".
+--csr jump|convect: instead of ec3d_assemble_poisson, the variable-coefficient operator of that name
+(tests/csr_grid_generate.py: a diffusion coefficient with a jump of 10^3; diffusion + upwind convection) is built on
+the host, uploaded with ec3d_set_matrix_csr and given its box with ec3d_set_precond_grid, so the hierarchy is made from
+the matrix alone (--coarsening is then ignored).  There is no reference count for these: the unpreconditioned figure is
+a full solve capped at --none-itmax iterations, and when the cap is hit the line says so and gives the rate
+(none_ms_per_iteration) instead of a time to solution."""
 from __future__ import annotations
 
 import argparse
@@ -56,6 +63,8 @@ def main():
     ap.add_argument("--mg-only", action="store_true")
     ap.add_argument("--none-only", action="store_true")
     ap.add_argument("--label")
+    ap.add_argument("--csr", choices=["jump", "convect"])
+    ap.add_argument("--none-itmax", type=int, default=20000)
     a = ap.parse_args()
     import eddy_currents_3d_amd as E
     from bench import bar_rhs
@@ -65,10 +74,21 @@ def main():
             out = dict(build=a.label, **out)
         if a.none_only:
             del out["precision"], out["coarsening"]
+        if a.csr:
+            out["operator"] = a.csr
+            out.pop("coarsening", None)
         b = bar_rhs(N)
         x0 = np.zeros(N ** 3)
         with E.EC3DSolver() as s:
-            s.assemble_poisson(N, N, N)
+            if a.csr:
+                sys.path.insert(0, os.path.join(REPO, "tests"))
+                import csr_grid_generate as G
+                s.set_matrix_csr(*G.case(a.csr, (N, N, N))[:3])
+                info = s.info
+                out["dict_classes"] = int(info.dict_classes)
+                G._cache.clear()
+            else:
+                s.assemble_poisson(N, N, N)
 
             def solve(tol=a.tol, itmax=100000):
                 s.upload("B", b)
@@ -81,7 +101,10 @@ def main():
             if not a.none_only:
                 if a.precision == "fp32":   # (the defaults set nothing: the tool then also runs on a library without the setters)
                     s.set_precond_precision("fp32")
-                if a.coarsening == "aggregate":
+                if a.csr:
+                    s.set_preconditioner("mg", grid=(N, N, N))
+                    out["level_kinds"] = s.precond_coarsening()[2]
+                elif a.coarsening == "aggregate":
                     s.set_precond_coarsening("aggregate")
                     s.set_preconditioner("mg")
                     out["level_kinds"] = s.precond_coarsening()[2]
@@ -97,7 +120,14 @@ def main():
                 out["us_per_vcycle"] = round(1e6 * (t_apply - t_spmv), 1)
                 out["mg_us_per_outer_iteration"] = round(1e6 * out["mg_s"] / max(out["mg_iter"], 1), 1)
                 s.set_preconditioner("none")
-            if not a.mg_only:
+            if not a.mg_only and a.csr:
+                out["none_s"], out["none_iter"] = solve(itmax=a.none_itmax)
+                out["none_true_residual"] = s.true_residual()[0]
+                out["none_ms_per_iteration"] = round(1e3 * out["none_s"] / max(out["none_iter"], 1), 4)
+                out["none_capped"] = out["none_iter"] > a.none_itmax
+                if out["none_capped"]:
+                    out["none_note"] = f"stopped at itmax = {a.none_itmax} without reaching tol: a rate, not a time to solution"
+            elif not a.mg_only:
                 if a.fixed and N > 256:
                     solve(1e-300, a.fixed - 1)
                     t, it = solve(1e-300, a.fixed - 1)
@@ -107,7 +137,7 @@ def main():
                     out["none_note"] = f"{it} fixed iterations scaled to {how}"
                 else:
                     out["none_s"], out["none_iter"] = solve()
-        if "none_s" in out and "mg_s" in out:
+        if "none_s" in out and "mg_s" in out and not out.get("none_capped"):
             out["speedup"] = round(out["none_s"] / out["mg_s"], 1)
         print(json.dumps(out), flush=True)
 
