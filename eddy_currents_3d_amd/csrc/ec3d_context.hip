@@ -2,6 +2,7 @@
 // copies, and the option / introspection entry points of the C ABI (include/ec3d_hip.h).
 #include "../../include/ec3d_hip.h"
 #include "ec3d_internal.hpp"
+#include "ec3d_sweep_lists.hpp"
 
 #include <climits>
 #include <algorithm>
@@ -13,6 +14,7 @@
 #include <chrono>
 #include <memory>
 #include <mutex>
+#include <optional>
 
 static thread_local std::string g_err;
 thread_local double *ec3d_itmax_print_hold = nullptr;
@@ -276,32 +278,15 @@ extern "C" int ec3d_destroy(ec3d_handle c)
     return 0;
 }
 
-// Runtime-shaped 2-D tiles for the structured A-V form (sav_patch_step in ec3d_kernels.hip): the patch shape for a
-// grid of sdx x sdy cells per plane.  px must be even (a thread owns two consecutive cells) and divide sdx (no
-// ragged patch columns), px * py <= 512, py >= 2; the last patch ROW may be ragged.  Score = the share of the 512
-// thread-cells of a tile that are real cells; at least 32 cells per patch row (256-byte pieces of a vector) unless
-// the grid itself is narrower; ties go to the px nearest 128 (the shape the cube kernels were tuned on).
-static double pick_patch_shape(int64_t sdx, int64_t sdy, int &px_out, int &py_out)
+// one host list onto the device, in a buffer of max(count, size) elements; an empty list with no count leaves no buffer
+template <class T> static hipError_t upload_list(DevBuf<T> &buf, const std::vector<T> &v, size_t count = 0)
 {
-    double best = 0.0;
-    px_out = py_out = 0;
-    if (sdx % 2) return 0.0;
-    for (int64_t px = 4; px <= std::min<int64_t>(sdx, 256); px += 2) {
-        if (sdx % px) continue;
-        if (px < 32 && px != sdx) continue;
-        const int64_t py = EC3D_TILE / px;
-        if (py < 2) continue;
-        const int64_t npy = (sdy + py - 1) / py;
-        const double eff = (double)(px * py) / EC3D_TILE * (double)sdy / (double)(npy * py);
-        const bool better = eff > best + 1e-9 ||
-                            (eff > best - 1e-9 && std::llabs(px - 128) < std::llabs((int64_t)px_out - 128));
-        if (better) {
-            best = std::max(best, eff);
-            px_out = (int)px;
-            py_out = (int)py;
-        }
-    }
-    return best;
+    buf.reset();
+    count = std::max(count, v.size());
+    if (count == 0) return hipSuccess;
+    hipError_t e = buf.alloc(count);
+    if (e == hipSuccess && !v.empty()) e = hipMemcpy(buf, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+    return e;
 }
 
 // per patch tile of the three A blocks: does it hold a coupled row?  and the patch tiles of the U block that hold an
@@ -312,42 +297,44 @@ static int build_patch_tables(ec3d_ctx *c, int px, int py)
     if (A.rp_px == px && A.rp_py == py && A.rp_flag) return 0;
     A.rp_flag.reset();
     const int64_t sdx = A.sav_step[1], pitch = A.sav_step[2], planes = A.sav_nC / pitch, sdy = c->plane / sdx;
-    const int64_t npx = sdx / px, npy = (sdy + py - 1) / py, tpp = npx * npy;
     std::vector<uint8_t> cls((size_t)A.n_pad);
     EC3D_HIP(hipStreamSynchronize(c->stream));
     EC3D_HIP(hipMemcpy(cls.data(), A.cls, cls.size(), hipMemcpyDeviceToHost));
-    std::vector<uint8_t> flag((size_t)(3 * planes * tpp) + 4, 0); // + 4: read by dwords
-    A.rp_ulist_host.clear();
-    for (int64_t P = 0; P < 4 * planes; ++P)
-        for (int64_t q = 0; q < tpp; ++q) {
-            const int64_t pyi = q / npx, pxi = q % npx;
-            bool any = false;
-            for (int64_t y = pyi * py; y < std::min<int64_t>(sdy, (pyi + 1) * py) && !any; ++y) {
-                const uint8_t *row = &cls[(size_t)(P * pitch + y * sdx + pxi * px)];
-                for (int x = 0; x < px; ++x) {
-                    const int k = row[x];
-                    if (P < 3 * planes ? (k >= A.sav_a0 && k < A.sav_u0) : (k >= A.sav_u0 && k < A.sav_zero)) {
-                        any = true;
-                        break;
-                    }
-                }
-            }
-            if (!any) continue;
-            if (P < 3 * planes) flag[(size_t)(P * tpp + q)] = 1;
-            else A.rp_ulist_host.push_back((int32_t)(P * tpp + q));
-        }
-    EC3D_HIP(A.rp_flag.alloc(flag.size()));
-    EC3D_HIP(hipMemcpy(A.rp_flag, flag.data(), flag.size(), hipMemcpyHostToDevice));
+    std::vector<uint8_t> flag;
+    ec3d_patch_tables(cls.data(), planes, pitch, sdx, sdy, px, py, A.sav_a0, A.sav_u0, A.sav_zero, flag, A.rp_ulist_host);
+    EC3D_HIP(upload_list(A.rp_flag, flag));
     A.rp_px = px;
     A.rp_py = py;
     return 0;
 }
+
+// Every environment knob that steers choose_sweep.  Constructing one reads them all, once; choose_sweep does so on every
+// call, not once per process: tests and tools change the environment between matrices.  An unset knob stays unset: each
+// use keeps its own default, clamping and precedence.
+struct SweepKnobs {
+    static std::optional<int> env(const char *name)
+    {
+        const char *e = getenv(name);
+        return e ? std::optional<int>(atoi(e)) : std::nullopt;
+    }
+    std::optional<int> nt = env("EC3D_NT"), keep = env("EC3D_KEEP");
+    std::optional<int> xcd_map = env("EC3D_XCD_MAP"), vec_depth = env("EC3D_VEC_DEPTH"); // every vector plan ...
+    enum { K2, K4, K5, SPMV_PLAIN, NVEC };                                                // ... and one kernel's
+    std::optional<int> nblk_k[NVEC] = {env("EC3D_NBLK_K2"), env("EC3D_NBLK_K4"), env("EC3D_NBLK_K5"), env("EC3D_NBLK_SPMV_PLAIN")};
+    std::optional<int> map_k[NVEC] = {env("EC3D_MAP_K2"), env("EC3D_MAP_K4"), env("EC3D_MAP_K5"), env("EC3D_MAP_SPMV_PLAIN")};
+    std::optional<int> depth_k[NVEC] = {env("EC3D_DEPTH_K2"), env("EC3D_DEPTH_K4"), env("EC3D_DEPTH_K5"),
+                                        env("EC3D_DEPTH_SPMV_PLAIN")};
+    std::optional<int> zmarch = env("EC3D_ZMARCH"), patch = env("EC3D_PATCH"), nblk_spmv = env("EC3D_NBLK_SPMV");
+    std::optional<int> sav_patch = env("EC3D_SAV_PATCH"), sav_patch_px = env("EC3D_SAV_PATCH_PX"), sav_il = env("EC3D_SAV_IL");
+    std::optional<int> fuse23 = env("EC3D_FUSE23"), fuse51 = env("EC3D_FUSE51"), k4s = env("EC3D_K4S");
+};
 
 // Launch geometry.  Vector kernels (K2, K4, K5): plain XCD-aware grid stride over 512-row tiles.
 // SpMV kernels: the same, or -- when a plane of the grid is a whole number of tiles -- the z-marching
 // map (one xy position per workgroup, consecutive planes per step; ec3d_tile_of in ec3d_kernels.hip).
 static int choose_sweep(ec3d_ctx *c)
 {
+    const SweepKnobs knob;
     Sweep &sw = c->sweep;
     sw = Sweep{};
     sw.bnd_last = -1;
@@ -379,8 +366,7 @@ static int choose_sweep(ec3d_ctx *c)
     // (measured, profiles/r04_keep_and_plans_config5.log: 839 -> 814-819 us per iteration with the mid-size policy).
     const int64_t rows_eff = (c->A.sav && c->A.ulist) ? (c->A.ntiles_front + (int64_t)c->A.ulist_n) * EC3D_TILE : c->A.n_pad;
     {
-        int ntreq = c->nt_request;
-        if (const char *e = getenv("EC3D_NT")) ntreq = atoi(e); // read here too: sweeps of launch knobs in one process
+        const int ntreq = knob.nt.value_or(c->nt_request); // read here too: sweeps of launch knobs in one process
         // nontemporal streams from 4.5 Mi rows (tools/keep_sweep.py: at 4 Mi rows = 32 MiB per vector plain caching is
         // still 8 % faster than any nontemporal policy, at 5.2 M rows it is 1.5 % slower than the policy below)
         sw.nt = (ntreq >= 0 ? ntreq : (rows_eff >= (9 << 19))) & 1;
@@ -394,7 +380,7 @@ static int choose_sweep(ec3d_ctx *c)
         // At 512^3 any of them costs 2-4 %.  EC3D_KEEP=<bits> overrides (1 AP, 2 S, 8 R, 32 P).
         int keep = 0;
         if (rows_eff < ((int64_t)1 << 25)) keep = 1 | 8 | (rows_eff * 8 <= ((int64_t)136 << 20) ? 2 : 0);
-        if (const char *e = getenv("EC3D_KEEP")) keep = atoi(e);
+        keep = knob.keep.value_or(keep);
         if (sw.nt) sw.nt |= keep << 1;
     }
     // Vector kernels (K2, K4, K5): each on a grid, a tile map and a batching depth of its own.
@@ -404,14 +390,13 @@ static int choose_sweep(ec3d_ctx *c)
     // Defaults are the measured optima (tools/vec_sweep.py, profiles/r03_vec_sweep_*); EC3D_NBLK_K*, EC3D_MAP_K*,
     // EC3D_DEPTH_K* override one kernel, EC3D_XCD_MAP / EC3D_VEC_DEPTH all three, ec3d_set_workgroups every grid.
     struct VecPlan { int nblk, map, depth; };
-    auto plan_of = [&](const char *k, VecPlan d) {
+    auto plan_of = [&](int k, VecPlan d) {
         if (c->nblk_request > 0) d.nblk = c->nblk_request;
-        if (const char *e = getenv("EC3D_XCD_MAP")) d.map = atoi(e) != 0;
-        if (const char *e = getenv("EC3D_VEC_DEPTH")) d.depth = atoi(e);
-        if (c->nblk_request <= 0)
-            if (const char *e = getenv((std::string("EC3D_NBLK_") + k).c_str())) d.nblk = std::max(1, atoi(e));
-        if (const char *e = getenv((std::string("EC3D_MAP_") + k).c_str())) d.map = atoi(e) != 0;
-        if (const char *e = getenv((std::string("EC3D_DEPTH_") + k).c_str())) d.depth = atoi(e);
+        if (knob.xcd_map) d.map = *knob.xcd_map != 0;
+        d.depth = knob.vec_depth.value_or(d.depth);
+        if (c->nblk_request <= 0 && knob.nblk_k[k]) d.nblk = std::max(1, *knob.nblk_k[k]);
+        if (knob.map_k[k]) d.map = *knob.map_k[k] != 0;
+        d.depth = knob.depth_k[k].value_or(d.depth);
         if (d.depth != 2 && d.depth != 4) d.depth = 1;
         return d;
     };
@@ -429,12 +414,12 @@ static int choose_sweep(ec3d_ctx *c)
     };
     {
         const bool big = rows_eff >= ((int64_t)1 << 25); // vectors of 256 MiB and more: nothing stays in a cache
-        const VecPlan p2 = plan_of("K2", big ? VecPlan{768, 0, 2} : VecPlan{768, 1, 1});
-        const VecPlan p4 = plan_of("K4", big ? VecPlan{256, 0, 2} : VecPlan{768, 1, 1});
-        const VecPlan p5 = plan_of("K5", big ? VecPlan{256, 0, 2} : VecPlan{768, 1, 1});
+        const VecPlan p2 = plan_of(SweepKnobs::K2, big ? VecPlan{768, 0, 2} : VecPlan{768, 1, 1});
+        const VecPlan p4 = plan_of(SweepKnobs::K4, big ? VecPlan{256, 0, 2} : VecPlan{768, 1, 1});
+        const VecPlan p5 = plan_of(SweepKnobs::K5, big ? VecPlan{256, 0, 2} : VecPlan{768, 1, 1});
         c->sweep_k2 = vec_sweep(p2);
         c->sweep_k5 = vec_sweep(p5);
-        c->sweep_s = vec_sweep(plan_of("SPMV_PLAIN", VecPlan{768, 1, 1})); // SpMV kernels on grids without a z-march
+        c->sweep_s = vec_sweep(plan_of(SweepKnobs::SPMV_PLAIN, VecPlan{768, 1, 1})); // SpMV kernels on grids without a z-march
         sw = vec_sweep(p4);
     }
 
@@ -443,8 +428,7 @@ static int choose_sweep(ec3d_ctx *c)
     c->fuse51_ok = false;
     c->k4s_ok = false;
     const DevMatrix &A = c->A;
-    int zm = c->zm_request;
-    if (const char *e = getenv("EC3D_ZMARCH")) zm = atoi(e);
+    int zm = knob.zmarch.value_or(c->zm_request);
     // the z-marching kernels carry no ownership ranges: a slab whose owned rows are not a window of whole
     // planes (bands + tail A-V slabs) keeps the plain map
     if (sw.nown > 0) zm = 0;
@@ -459,8 +443,7 @@ static int choose_sweep(ec3d_ctx *c)
             // reading them in 1 KiB pieces per patch row instead of 4 KiB runs costs more than the x loads save
             // (512^3: K1/K3 2154/1964 us with patches, 2066/1847 without).
             const int64_t sdx = A.off[5];
-            int patch = 1;
-            if (const char *e = getenv("EC3D_PATCH")) patch = atoi(e);
+            const int patch = knob.patch.value_or(1);
             const bool use_patch = patch && !A.sav && A.ntail == 0 && A.ncls > 0 && sdx % EC3D_PX == 0 && A.off[6] % sdx == 0 &&
                                    (A.off[6] / sdx) % EC3D_PY == 0 && c->A.n == nplanes * A.off[6];
             // The structured A-V form on runtime-shaped 2-D tiles (sav_patch_step): a single-rank handle whose planes are
@@ -473,12 +456,11 @@ static int choose_sweep(ec3d_ctx *c)
                 // (iteration within 1 %), and K2-in-K3 / K5-in-K1 on them LOSE 4 ... 20 % at every size these systems
                 // reach on one GPU (profiles/r04_sav_patch_*.log).  EC3D_SAV_PATCH=1: when a shape
                 // keeps >= 90 % of the threads busy; 2: whenever a shape exists.
-                int want = 0;
-                if (const char *e = getenv("EC3D_SAV_PATCH")) want = atoi(e);
-                const double eff = want ? pick_patch_shape(sdx, c->plane / sdx, rp_px, rp_py) : 0.0;
+                const int want = knob.sav_patch.value_or(0);
+                const double eff = want ? ec3d_pick_patch_shape(sdx, c->plane / sdx, EC3D_TILE, rp_px, rp_py) : 0.0;
                 if (!(rp_px > 0 && (want == 2 || eff >= 0.9))) rp_px = rp_py = 0;
-                if (const char *e = getenv("EC3D_SAV_PATCH_PX")) { // tests: a given shape (px cells per patch row)
-                    const int px = atoi(e);
+                if (knob.sav_patch_px) { // tests: a given shape (px cells per patch row)
+                    const int px = *knob.sav_patch_px;
                     if (want && px >= 4 && px % 2 == 0 && px <= 256 && sdx % px == 0) {
                         rp_px = px;
                         rp_py = EC3D_TILE / px;
@@ -500,7 +482,7 @@ static int choose_sweep(ec3d_ctx *c)
             // 174.9 / 153.1 on 1584, 160.7 / 133.3 on 3024; the 21 M system stays at 1472: 1104 costs it 13 %)
             const bool sav_big = A.sav && rows_eff >= ((int64_t)25 << 20);
             int want_s = c->nblk_request > 0 ? c->nblk_request : A.sav ? (sav_big ? 1024 : 1536) : big ? 1024 : use_patch ? 1536 : 768;
-            if (const char *e = getenv("EC3D_NBLK_SPMV")) want_s = atoi(e);
+            want_s = knob.nblk_spmv.value_or(want_s);
             // tiles per plane and logical tiles of the front sweep as the SpMV kernels count them
             int64_t tpp_s = tpp, ntiles_s = sw.ntiles;
             if (sav_patch) {
@@ -511,12 +493,6 @@ static int choose_sweep(ec3d_ctx *c)
             // columns are dealt to the 8 XCD labels in runs of cpx; with tpp % 8 != 0 the last run is short
             // and 8*cpx - tpp workgroups per segment stay idle
             const int64_t cols = (tpp_s + 7) / 8 * 8;
-            // z segments per column.  6 workgroups per CU are resident (want_s = 6 * 256): a grid just above
-            // that leaves a second, nearly empty round (2048 at 512^3: +5 %, 1600 at 640^3: +30 % on K1), a
-            // grid well below it wastes latency hiding.  So: the fewest segments that fill one round to
-            // >= 5/6 as full as the columns allow, or else >= 1.5 rounds, where the hardware's dynamic dispatch
-            // evens things out (2400 at 640^3, 3072 at 512^3 are as good as an exact fit).
-            int64_t nseg = 1;
             // planes per z segment: at least 2.  (Rounds 1-3 kept 8, so that the two extra loads of a segment's first
             // plane were spread over 8 steps; on a problem that fits the caches that left the shipped 102 x 102 x 24
             // system with 216 workgroups of 8 DEPENDENT steps each, under one workgroup per CU and a memory round trip per
@@ -524,13 +500,12 @@ static int choose_sweep(ec3d_ctx *c)
             // per iteration; no difference from 4 M rows up, where the grid is full either way.)
             const int64_t min_pps = 2;
             const int64_t max_seg = std::max<int64_t>(1, nplanes / min_pps);
-            if (c->nblk_request > 0 || getenv("EC3D_NBLK_SPMV")) {
-                nseg = std::max<int64_t>(1, (want_s + cols / 2) / cols); // explicit request: nearest
-            } else {
-                const int64_t fit = want_s / cols; // most segments that still fit one round
-                nseg = (fit >= 1 && 6 * cols * fit >= 5 * want_s) ? fit : (3 * want_s + 2 * cols - 1) / (2 * cols);
-            }
-            nseg = std::min<int64_t>(nseg, max_seg);
+            // z segments per column.  6 workgroups per CU are resident (want_s = 6 * 256): a grid just above
+            // that leaves a second, nearly empty round (2048 at 512^3: +5 %, 1600 at 640^3: +30 % on K1), a
+            // grid well below it wastes latency hiding.  So: the fewest segments that fill one round to
+            // >= 5/6 as full as the columns allow, or else >= 1.5 rounds, where the hardware's dynamic dispatch
+            // evens things out (2400 at 640^3, 3072 at 512^3 are as good as an exact fit).
+            const int64_t nseg = ec3d_zm_segments(want_s, cols, max_seg, c->nblk_request > 0 || knob.nblk_spmv);
             ss.zm_tpp = (int)tpp_s;
             ss.zm_pps = (int)((nplanes + nseg - 1) / nseg);
             ss.nblk = (int)(cols * nseg);
@@ -547,86 +522,31 @@ static int choose_sweep(ec3d_ctx *c)
             c->il_umask_host.clear();
             c->il_seg_host.clear();
             {
-                int il = 1;
-                if (const char *e = getenv("EC3D_SAV_IL")) il = atoi(e);
+                const int il = knob.sav_il.value_or(1);
                 const int64_t P = nplanes / 3;
                 const bool il_big = rows_eff >= ((int64_t)25 << 20);
                 if (A.sav && !sav_patch && (il == 2 || (il == 1 && il_big)) && c->halo == 0 && c->nown == 0 && sw.win_nt == 0 &&
                     P * 3 == nplanes && P * 3 * tpp == sw.ntiles && (int)c->A.ulist_host.size() == c->A.ulist_n &&
                     c->A.n == 4 * P * tpp * EC3D_TILE /* every row of a visited tile is a row of the system: no masks */) {
-                    const int nw = (int)((P + 31) / 32);
-                    std::vector<uint32_t> um((size_t)(tpp * nw), 0u);
-                    bool ok = true;
-                    for (int32_t t : c->A.ulist_host) {
-                        const int64_t k = (int64_t)t / tpp - 3 * P, col = (int64_t)t % tpp;
-                        if (k < 0 || k >= P) { ok = false; break; }
-                        um[(size_t)(col * nw + k / 32)] |= 1u << (k % 32);
-                    }
-                    // a coupled A tile must lie where a U tile is visited (its rows' cells carry U unknowns): checked, not assumed
-                    if (ok && A.tile_flag) {
-                        std::vector<uint8_t> tf((size_t)sw.ntiles);
+                    int nw = 0;
+                    std::vector<uint32_t> um;
+                    std::vector<uint8_t> tf;
+                    if (A.tile_flag) {
+                        tf.resize((size_t)sw.ntiles);
                         EC3D_HIP(hipMemcpy(tf.data(), A.tile_flag, tf.size(), hipMemcpyDeviceToHost));
-                        for (int64_t t = 0; t < sw.ntiles && ok; ++t)
-                            if (tf[(size_t)t]) {
-                                const int64_t k = (t / tpp) % P, col = t % tpp;
-                                ok = (um[(size_t)(col * nw + k / 32)] >> (k % 32)) & 1u;
-                            }
                     }
-                    if (ok) {
-                        // The work list.  Two workgroups per CU are resident (a step holds the band operands of four tiles), all
-                        // of them from the launch's start to its end, so the launch lasts as long as its heaviest workgroup:
-                        // planes are dealt by weight -- a plane with a U tile (four tiles, the coupling slots of every row) counts
-                        // il_w percent of one without -- column by column, the segments of a column of equal weight, the number of
-                        // segments of a column in proportion to its weight.
+                    if (ec3d_il_umask(c->A.ulist_host, tpp, P, A.tile_flag ? tf.data() : nullptr, sw.ntiles, um, nw)) {
+                        // The work list (ec3d_il_work_list): planes dealt to the workgroups by weight, a plane with a U tile
+                        // counting il_w percent of one without.
                         int64_t want_il = 512;
                         if (c->nblk_request > 0) want_il = c->nblk_request;
-                        if (const char *e = getenv("EC3D_NBLK_SPMV")) want_il = std::max(8, atoi(e));
+                        if (knob.nblk_spmv) want_il = std::max(8, *knob.nblk_spmv);
                         const int il_w = 160; // (100 ... 250 measured at 256^3: 130 ... 180 within 1.5 %, profiles/r06_av256_*)
-                        const int64_t cpx = (tpp + 7) / 8;
-                        auto bit = [&](int64_t col, int64_t k) { return (um[(size_t)(col * nw + k / 32)] >> (k % 32)) & 1u; };
-                        std::vector<int64_t> wcol((size_t)tpp, 0);
-                        int64_t wtot = 0;
-                        for (int64_t col = 0; col < tpp; ++col) {
-                            for (int64_t k = 0; k < P; ++k) wcol[(size_t)col] += bit(col, k) ? il_w : 100;
-                            wtot += wcol[(size_t)col];
-                        }
-                        const double target = (double)wtot / (double)want_il;
-                        std::vector<std::vector<int32_t>> perx(8); // per XCD label: (col, k0, k1) triples in dispatch order
-                        int64_t max_seg = 0;
-                        std::vector<std::vector<std::array<int32_t, 2>>> cuts((size_t)tpp);
-                        for (int64_t col = 0; col < tpp; ++col) {
-                            int64_t ns = std::max<int64_t>(1, (int64_t)std::llround((double)wcol[(size_t)col] / target));
-                            ns = std::min<int64_t>(ns, std::max<int64_t>(1, P / min_pps));
-                            int64_t k0 = 0, acc = 0;
-                            for (int64_t sgi = 0; sgi < ns; ++sgi) {
-                                const int64_t goal = wcol[(size_t)col] * (sgi + 1) / ns;
-                                int64_t k1 = k0;
-                                while (k1 < P && (acc < goal || sgi + 1 == ns)) { acc += bit(col, k1) ? il_w : 100; ++k1; }
-                                cuts[(size_t)col].push_back({(int32_t)k0, (int32_t)k1});
-                                k0 = k1;
-                            }
-                            max_seg = std::max<int64_t>(max_seg, ns);
-                        }
-                        // dispatch order within an XCD: segment index outermost, so that the workgroups that start together work
-                        // on neighbouring columns at about the same planes (their +-sdx lines meet in that XCD's L2)
-                        for (int x = 0; x < 8; ++x)
-                            for (int64_t sgi = 0; sgi < max_seg; ++sgi)
-                                for (int64_t col = x * cpx; col < std::min<int64_t>((x + 1) * cpx, tpp); ++col)
-                                    if (sgi < (int64_t)cuts[(size_t)col].size()) {
-                                        perx[(size_t)x].push_back((int32_t)col);
-                                        perx[(size_t)x].push_back(cuts[(size_t)col][(size_t)sgi][0]);
-                                        perx[(size_t)x].push_back(cuts[(size_t)col][(size_t)sgi][1]);
-                                    }
+                        std::vector<int32_t> seg;
                         size_t per = 0;
-                        for (int x = 0; x < 8; ++x) per = std::max(per, perx[(size_t)x].size() / 3);
-                        std::vector<int32_t> seg(per * 8 * 4, 0);
-                        for (int x = 0; x < 8; ++x)
-                            for (size_t j = 0; j < perx[(size_t)x].size() / 3; ++j)
-                                for (int q = 0; q < 3; ++q) seg[(j * 8 + (size_t)x) * 4 + (size_t)q] = perx[(size_t)x][j * 3 + (size_t)q];
-                        EC3D_HIP(c->il_umask.alloc(std::max<size_t>(um.size(), 1) + 1));
-                        EC3D_HIP(hipMemcpy(c->il_umask, um.data(), um.size() * 4, hipMemcpyHostToDevice));
-                        EC3D_HIP(c->il_seg.alloc(std::max<size_t>(seg.size(), 4)));
-                        EC3D_HIP(hipMemcpy(c->il_seg, seg.data(), seg.size() * 4, hipMemcpyHostToDevice));
+                        ec3d_il_work_list(um, nw, tpp, P, want_il, il_w, min_pps, seg, per);
+                        EC3D_HIP(upload_list(c->il_umask, um, um.size() + 1)); // (+ 1: a word of read-ahead)
+                        EC3D_HIP(upload_list(c->il_seg, seg));
                         c->il_umask_host = um;
                         c->il_seg_host = seg;
                         ss.il_planes = (int)P;
@@ -651,9 +571,7 @@ static int choose_sweep(ec3d_ctx *c)
                 ss.rp_flag = A.rp_flag;
                 // K2 inside K3, K5 inside the next K1 on these tiles as on the cube's (same rule: vectors beyond the
                 // caches; EC3D_FUSE23 / EC3D_FUSE51 = 0 never, 2 always)
-                int fuse = 1, fuse5 = 1;
-                if (const char *e = getenv("EC3D_FUSE23")) fuse = atoi(e);
-                if (const char *e = getenv("EC3D_FUSE51")) fuse5 = atoi(e);
+                const int fuse = knob.fuse23.value_or(1), fuse5 = knob.fuse51.value_or(1);
                 const bool fuse_big = c->A.n_pad >= ((int64_t)1 << 26); // the cube's rule (below)
                 c->fuse23_ok = fuse == 2 || (fuse == 1 && fuse_big);
                 c->fuse51_ok = fuse5 == 2 || (fuse5 == 1 && fuse_big);
@@ -675,17 +593,14 @@ static int choose_sweep(ec3d_ctx *c)
                 // 512 x 512 x 64 388-391 / 381-385, 384 x 384 x 128 449 / 447, 512 x 512 x 72 438-441 / 427-432, 512 x 512 x 80
                 // 494 / 477, 512 x 512 x 96 597-598 / 570-571, 384 x 384 x 192 689-690 / 667, 512 x 512 x 112 705-706 / 658-660:
                 // from 20 Mi rows on an undivided handle (z-slabs keep 32 Mi: their three-launch plans exchange AP and R).
-                int k4s = 1;
-                if (const char *e = getenv("EC3D_K4S")) k4s = atoi(e);
+                const int k4s = knob.k4s.value_or(1);
                 const bool undivided = c->halo == 0 && !c->dist && c->nranks <= 1;
                 const int64_t fuse_rows = !(k4s != 0 && A.ncls > 0) ? (int64_t)1 << 26 : undivided ? (int64_t)20 << 20 : (int64_t)1 << 25;
                 const bool fuse_big = c->A.n_pad >= fuse_rows;
-                int fuse = 1;
-                if (const char *e = getenv("EC3D_FUSE23")) fuse = atoi(e);
+                const int fuse = knob.fuse23.value_or(1);
                 c->fuse23_ok = fuse == 2 || (fuse == 1 && fuse_big);
                 // K5 inside the next iteration's K1 (k51_p_spmv_dot): K1 + K5 593 + 700 us -> 1225 us at 512^3
-                int fuse5 = 1;
-                if (const char *e = getenv("EC3D_FUSE51")) fuse5 = atoi(e);
+                const int fuse5 = knob.fuse51.value_or(1);
                 c->fuse51_ok = fuse5 == 2 || (fuse5 == 1 && fuse_big);
                 // K4 as an SpMV kernel that computes A S again instead of reading the AS that K23 would have written
                 // (k4s_x_r_spmv): 16 B per row and iteration less.  EC3D_K4S=0 never, 2 whenever both fusions run
@@ -704,38 +619,19 @@ static int choose_sweep(ec3d_ctx *c)
     c->us_list.reset();
     c->us_host.clear();
     {
-        const int local = 1;
         // on runtime-shaped 2-D tiles the list holds PATCH tiles of the U block (build_patch_tables); there is no plain
         // form of it on the device, so the XCD-local order is always taken
         const bool rp = ss.rp_px > 0;
         const std::vector<int32_t> &src = rp ? c->A.rp_ulist_host : c->A.ulist_host;
         if (rp) ss.ulist_n = (int)src.size();
-        if ((local || rp) && A.sav && ss.zm_tpp > 0 && ss.ulist_n > 0 && ss.nblk % 8 == 0 &&
+        if (A.sav && ss.zm_tpp > 0 && ss.ulist_n > 0 && ss.nblk % 8 == 0 &&
             (int)src.size() == ss.ulist_n && (rp || ss.ulist == c->A.ulist)) {
-            const int64_t tpp = ss.zm_tpp, G = ss.nblk, Gx = G / 8, L = ss.ulist_n;
-            std::vector<int32_t> byc(src);
-            std::stable_sort(byc.begin(), byc.end(), [&](int32_t a, int32_t b) { return a % tpp < b % tpp; });
-            int64_t K = 0;
-            std::vector<std::vector<int32_t>> share(8);
-            for (int x = 0; x < 8; ++x) {
-                share[x].assign(byc.begin() + L * x / 8, byc.begin() + L * (x + 1) / 8);
-                std::sort(share[x].begin(), share[x].end()); // tile id ascending = plane by plane, column by column
-                K = std::max<int64_t>(K, ((int64_t)share[x].size() + Gx - 1) / Gx);
-            }
-            std::vector<int32_t> perm((size_t)(K * G), -1);
-            for (int x = 0; x < 8; ++x)
-                for (size_t i = 0; i < share[x].size(); ++i)
-                    perm[(size_t)(((int64_t)i / Gx) * G + ((int64_t)i % Gx) * 8 + x)] = share[x][i];
-            EC3D_HIP(c->us_list.alloc(perm.size()));
-            EC3D_HIP(hipMemcpy(c->us_list, perm.data(), perm.size() * 4, hipMemcpyHostToDevice));
+            c->us_host = ec3d_xcd_local_order(src, ss.zm_tpp, ss.nblk);
+            EC3D_HIP(upload_list(c->us_list, c->us_host));
             ss.ulist = c->us_list;
-            ss.ulist_n = (int)perm.size();
-            c->us_host = perm;
+            ss.ulist_n = (int)c->us_host.size();
         } else if (rp) { // (a grid of fewer than 8 workgroups: the list as it is)
-            if (!src.empty()) {
-                EC3D_HIP(c->us_list.alloc(src.size()));
-                EC3D_HIP(hipMemcpy(c->us_list, src.data(), src.size() * 4, hipMemcpyHostToDevice));
-            }
+            EC3D_HIP(upload_list(c->us_list, src));
             ss.ulist = c->us_list;
             c->us_host = src;
         }
@@ -777,18 +673,10 @@ static int choose_sweep(ec3d_ctx *c)
     if (A.sav && c->halo > 0 && sw.win_nt > 0 && ss.zm_tpp > 0 && ss.rp_px == 0 && c->A.ulist &&
         (int)c->A.ulist_host.size() == c->A.ulist_n) {
         const int64_t tpp = ss.zm_tpp, npo = sw.win_nt / tpp, H = 2, blk = sw.win_blk, p0 = sw.win_t0 / tpp;
-        const int split = 1;
-        if (split && npo * tpp == sw.win_nt && p0 * tpp == sw.win_t0 && npo >= 2 * H + 2) {
+        if (npo * tpp == sw.win_nt && p0 * tpp == sw.win_t0 && npo >= 2 * H + 2) {
             const int64_t npi = npo - 2 * H;
-            std::vector<int32_t> ui, ub;
-            bool owned_only = true;
-            for (int32_t t : c->A.ulist_host) {
-                const int64_t pl = ((int64_t)t - 3 * blk) / tpp - p0; // owned plane of the U block this tile lies in
-                if (t < 3 * blk || pl < 0 || pl >= npo) owned_only = false;
-                else if (pl >= H && pl < npo - H) ui.push_back(t);
-                else ub.push_back(t);
-            }
-            if (owned_only) {
+            std::vector<int32_t> ui, ub, bl;
+            if (ec3d_slab_split_lists(c->A.ulist_host, tpp, blk, p0, npo, H, ui, ub, bl)) {
                 Sweep &si = c->sweep_int, &sb = c->sweep_bnd;
                 const int64_t cols = (tpp + 7) / 8 * 8;
                 int64_t nseg = std::max<int64_t>(1, (int64_t)ss.nblk / cols);
@@ -802,33 +690,13 @@ static int choose_sweep(ec3d_ctx *c)
                 // the interior U tiles in the XCD-local order (as us_list above): by column into eight shares, a share plane by plane
                 std::vector<int32_t> perm;
                 if (!ui.empty()) {
-                    const int64_t G = si.nblk, Gx = G / 8, L = (int64_t)ui.size();
-                    std::vector<int32_t> byc(ui);
-                    std::stable_sort(byc.begin(), byc.end(), [&](int32_t a, int32_t b) { return a % tpp < b % tpp; });
-                    int64_t K = 0;
-                    std::vector<std::vector<int32_t>> share(8);
-                    for (int x = 0; x < 8; ++x) {
-                        share[x].assign(byc.begin() + L * x / 8, byc.begin() + L * (x + 1) / 8);
-                        std::sort(share[x].begin(), share[x].end());
-                        K = std::max<int64_t>(K, ((int64_t)share[x].size() + Gx - 1) / Gx);
-                    }
-                    perm.assign((size_t)(K * G), -1);
-                    for (int x = 0; x < 8; ++x)
-                        for (size_t i = 0; i < share[x].size(); ++i)
-                            perm[(size_t)(((int64_t)i / Gx) * G + ((int64_t)i % Gx) * 8 + x)] = share[x][i];
-                    EC3D_HIP(c->ii_list.alloc(perm.size()));
-                    EC3D_HIP(hipMemcpy(c->ii_list, perm.data(), perm.size() * 4, hipMemcpyHostToDevice));
+                    perm = ec3d_xcd_local_order(ui, tpp, si.nblk);
+                    EC3D_HIP(upload_list(c->ii_list, perm));
                 }
                 si.ulist = c->ii_list;
                 si.ulist_n = (int)perm.size();
                 // the boundary list: A tiles of planes 0, 1, npo-2, npo-1 of every block, plane by plane, then the U tiles there
-                std::vector<int32_t> bl;
-                for (int d = 0; d < 3; ++d)
-                    for (int64_t pl : {(int64_t)0, (int64_t)1, npo - 2, npo - 1})
-                        for (int64_t q = 0; q < tpp; ++q) bl.push_back((int32_t)(d * blk + (p0 + pl) * tpp + q));
-                bl.insert(bl.end(), ub.begin(), ub.end());
-                EC3D_HIP(c->ib_list.alloc(bl.size()));
-                EC3D_HIP(hipMemcpy(c->ib_list, bl.data(), bl.size() * 4, hipMemcpyHostToDevice));
+                EC3D_HIP(upload_list(c->ib_list, bl));
                 sb.ntiles = 0; // (no front sweep: ec3d_tile_of / walk_zm find no plane whose tile exists)
                 sb.win_nt = 0;
                 sb.ulist = c->ib_list;
@@ -1809,7 +1677,7 @@ static void visit_of(const ec3d_ctx *c, const Sweep &sw, std::vector<std::vector
             for (int64_t k = c->il_seg_host[(size_t)b * 4 + 1]; k < c->il_seg_host[(size_t)b * 4 + 2]; ++k) {
                 const int64_t t0 = k * tpp + col;
                 for (int d = 0; d < 3; ++d) v.push_back((int32_t)(t0 + d * blk_t));
-                if ((c->il_umask_host[(size_t)(col * sw.il_nw + k / 32)] >> (k % 32)) & 1u) v.push_back((int32_t)(t0 + 3 * blk_t));
+                if (ec3d_il_bit(c->il_umask_host.data(), sw.il_nw, col, k)) v.push_back((int32_t)(t0 + 3 * blk_t));
             }
             out.push_back(std::move(v));
         }

@@ -1,0 +1,210 @@
+// ec3d_sweep_lists.hpp — the tile lists choose_sweep (ec3d_context.hip) builds on the host for the SpMV kernels of the
+// structured A-V form, and the two small rules that go with them (host only: no HIP call, no kernels, no handle): the
+// shape of the runtime-shaped 2-D tiles and their per-tile tables, the z segments of a z-marching grid, the U mask and
+// the work list of the interleaved z-march, the XCD-local order of a list of U tiles, and the interior / boundary lists
+// of a z-slab.  choose_sweep decides WHEN each is used and uploads the result; the arithmetic lives here so that it
+// runs without a GPU.  tests/test_sweep_lists_host.py checks every list against a numpy restatement.
+#pragma once
+#include <algorithm>
+#include <array>
+#include <cmath>
+#include <cstdint>
+#include <cstdlib>
+#include <vector>
+
+// Runtime-shaped 2-D tiles for the structured A-V form (sav_patch_step in ec3d_kernels.hip): the patch shape for a
+// grid of sdx x sdy cells per plane and tiles of `tile` rows (512).  px must be even (a thread owns two consecutive
+// cells) and divide sdx (no ragged patch columns), px * py <= 512, py >= 2; the last patch ROW may be ragged.  Score =
+// the share of the 512 thread-cells of a tile that are real cells; at least 32 cells per patch row (256-byte pieces of
+// a vector) unless the grid itself is narrower; ties go to the px nearest 128 (the shape the cube kernels were tuned on).
+inline double ec3d_pick_patch_shape(int64_t sdx, int64_t sdy, int64_t tile, int &px_out, int &py_out)
+{
+    double best = 0.0;
+    px_out = py_out = 0;
+    if (sdx % 2) return 0.0;
+    for (int64_t px = 4; px <= std::min<int64_t>(sdx, 256); px += 2) {
+        if (sdx % px) continue;
+        if (px < 32 && px != sdx) continue;
+        const int64_t py = tile / px;
+        if (py < 2) continue;
+        const int64_t npy = (sdy + py - 1) / py;
+        const double eff = (double)(px * py) / tile * (double)sdy / (double)(npy * py);
+        const bool better = eff > best + 1e-9 ||
+                            (eff > best - 1e-9 && std::llabs(px - 128) < std::llabs((int64_t)px_out - 128));
+        if (better) {
+            best = std::max(best, eff);
+            px_out = (int)px;
+            py_out = (int)py;
+        }
+    }
+    return best;
+}
+
+// per patch tile of the three A blocks: does it hold a coupled row?  and the patch tiles of the U block that hold an
+// unknown (ascending): from the class bytes `cls` of the 4 * planes stacked planes of `pitch` rows each.  A rows are
+// coupled in classes [sav_a0, sav_u0), U rows hold an unknown in classes [sav_u0, sav_zero).
+inline void ec3d_patch_tables(const uint8_t *cls, int64_t planes, int64_t pitch, int64_t sdx, int64_t sdy, int px, int py,
+                              int sav_a0, int sav_u0, int sav_zero, std::vector<uint8_t> &flag, std::vector<int32_t> &ulist)
+{
+    const int64_t npx = sdx / px, npy = (sdy + py - 1) / py, tpp = npx * npy;
+    flag.assign((size_t)(3 * planes * tpp) + 4, 0); // + 4: read by dwords
+    ulist.clear();
+    for (int64_t P = 0; P < 4 * planes; ++P)
+        for (int64_t q = 0; q < tpp; ++q) {
+            const int64_t pyi = q / npx, pxi = q % npx;
+            bool any = false;
+            for (int64_t y = pyi * py; y < std::min<int64_t>(sdy, (pyi + 1) * py) && !any; ++y) {
+                const uint8_t *row = &cls[(size_t)(P * pitch + y * sdx + pxi * px)];
+                for (int x = 0; x < px; ++x) {
+                    const int k = row[x];
+                    if (P < 3 * planes ? (k >= sav_a0 && k < sav_u0) : (k >= sav_u0 && k < sav_zero)) {
+                        any = true;
+                        break;
+                    }
+                }
+            }
+            if (!any) continue;
+            if (P < 3 * planes) flag[(size_t)(P * tpp + q)] = 1;
+            else ulist.push_back((int32_t)(P * tpp + q));
+        }
+}
+
+// z segments per column of a z-marching grid of `cols` columns that wants want_s workgroups, at most max_seg
+inline int64_t ec3d_zm_segments(int64_t want_s, int64_t cols, int64_t max_seg, bool explicit_request)
+{
+    int64_t nseg = 1;
+    if (explicit_request) {
+        nseg = std::max<int64_t>(1, (want_s + cols / 2) / cols); // explicit request: nearest
+    } else {
+        const int64_t fit = want_s / cols; // most segments that still fit one round
+        nseg = (fit >= 1 && 6 * cols * fit >= 5 * want_s) ? fit : (3 * want_s + 2 * cols - 1) / (2 * cols);
+    }
+    return std::min<int64_t>(nseg, max_seg);
+}
+
+// The U mask of the interleaved z-march (Sweep::il_umask): nw = ceil(P / 32) words per column, bit k of a column's words =
+// a U tile is visited at plane k.  The one place that knows the layout.
+inline uint32_t ec3d_il_bit(const uint32_t *um, int nw, int64_t col, int64_t k)
+{
+    return (um[(size_t)(col * nw + k / 32)] >> (k % 32)) & 1u;
+}
+
+// The mask from the list of U tiles (tile ids of the four stacked blocks of P planes of tpp tiles).  tile_flag (or
+// null): per tile of the three A blocks, ntiles of them, whether it holds a coupled row.  False when a U tile lies
+// outside the U block or a coupled A tile lies where no U tile is visited.
+inline bool ec3d_il_umask(const std::vector<int32_t> &ulist, int64_t tpp, int64_t P, const uint8_t *tile_flag, int64_t ntiles,
+                          std::vector<uint32_t> &um, int &nw)
+{
+    nw = (int)((P + 31) / 32);
+    um.assign((size_t)(tpp * nw), 0u);
+    for (int32_t t : ulist) {
+        const int64_t k = (int64_t)t / tpp - 3 * P, col = (int64_t)t % tpp;
+        if (k < 0 || k >= P) return false;
+        um[(size_t)(col * nw + k / 32)] |= 1u << (k % 32);
+    }
+    // a coupled A tile must lie where a U tile is visited (its rows' cells carry U unknowns): checked, not assumed
+    if (tile_flag)
+        for (int64_t t = 0; t < ntiles; ++t)
+            if (tile_flag[(size_t)t] && !ec3d_il_bit(um.data(), nw, t % tpp, (t / tpp) % P)) return false;
+    return true;
+}
+
+// The work list of the interleaved z-march: four int32 per workgroup (column, first plane, end plane, 0), `per` rows
+// of 8 workgroups (one per XCD label).  Two workgroups per CU are resident (a step holds the band operands of four
+// tiles), all of them from the launch's start to its end, so the launch lasts as long as its heaviest workgroup:
+// planes are dealt by weight -- a plane with a U tile (four tiles, the coupling slots of every row) counts il_w percent
+// of one without -- column by column, the segments of a column of equal weight, the number of segments of a column in
+// proportion to its weight.
+inline void ec3d_il_work_list(const std::vector<uint32_t> &um, int nw, int64_t tpp, int64_t P, int64_t want_il, int il_w,
+                              int64_t min_pps, std::vector<int32_t> &seg, size_t &per)
+{
+    const int64_t cpx = (tpp + 7) / 8;
+    auto bit = [&](int64_t col, int64_t k) { return ec3d_il_bit(um.data(), nw, col, k); };
+    std::vector<int64_t> wcol((size_t)tpp, 0);
+    int64_t wtot = 0;
+    for (int64_t col = 0; col < tpp; ++col) {
+        for (int64_t k = 0; k < P; ++k) wcol[(size_t)col] += bit(col, k) ? il_w : 100;
+        wtot += wcol[(size_t)col];
+    }
+    const double target = (double)wtot / (double)want_il;
+    std::vector<std::vector<int32_t>> perx(8); // per XCD label: (col, k0, k1) triples in dispatch order
+    int64_t max_seg = 0;
+    std::vector<std::vector<std::array<int32_t, 2>>> cuts((size_t)tpp);
+    for (int64_t col = 0; col < tpp; ++col) {
+        int64_t ns = std::max<int64_t>(1, (int64_t)std::llround((double)wcol[(size_t)col] / target));
+        ns = std::min<int64_t>(ns, std::max<int64_t>(1, P / min_pps));
+        int64_t k0 = 0, acc = 0;
+        for (int64_t sgi = 0; sgi < ns; ++sgi) {
+            const int64_t goal = wcol[(size_t)col] * (sgi + 1) / ns;
+            int64_t k1 = k0;
+            while (k1 < P && (acc < goal || sgi + 1 == ns)) { acc += bit(col, k1) ? il_w : 100; ++k1; }
+            cuts[(size_t)col].push_back({(int32_t)k0, (int32_t)k1});
+            k0 = k1;
+        }
+        max_seg = std::max<int64_t>(max_seg, ns);
+    }
+    // dispatch order within an XCD: segment index outermost, so that the workgroups that start together work
+    // on neighbouring columns at about the same planes (their +-sdx lines meet in that XCD's L2)
+    for (int x = 0; x < 8; ++x)
+        for (int64_t sgi = 0; sgi < max_seg; ++sgi)
+            for (int64_t col = x * cpx; col < std::min<int64_t>((x + 1) * cpx, tpp); ++col)
+                if (sgi < (int64_t)cuts[(size_t)col].size()) {
+                    perx[(size_t)x].push_back((int32_t)col);
+                    perx[(size_t)x].push_back(cuts[(size_t)col][(size_t)sgi][0]);
+                    perx[(size_t)x].push_back(cuts[(size_t)col][(size_t)sgi][1]);
+                }
+    per = 0;
+    for (int x = 0; x < 8; ++x) per = std::max(per, perx[(size_t)x].size() / 3);
+    seg.assign(per * 8 * 4, 0);
+    for (int x = 0; x < 8; ++x)
+        for (size_t j = 0; j < perx[(size_t)x].size() / 3; ++j)
+            for (int q = 0; q < 3; ++q) seg[(j * 8 + (size_t)x) * 4 + (size_t)q] = perx[(size_t)x][j * 3 + (size_t)q];
+}
+
+// The XCD-local order of a list of U tiles for a grid of G workgroups (G % 8 == 0): the tiles, sorted by column
+// (tile % tpp), are cut into eight equal shares, one per XCD label; a share is taken plane by plane, consecutive tiles
+// by consecutive workgroups of that XCD at the same time, so in-plane and plane-to-plane neighbours meet in that XCD's
+// L2.  Entry j * G + i * 8 + x is tile j * (G / 8) + i of share x; holes (-1) end a workgroup's list (b, b + G, ...).
+inline std::vector<int32_t> ec3d_xcd_local_order(const std::vector<int32_t> &tiles, int64_t tpp, int64_t G)
+{
+    const int64_t Gx = G / 8, L = (int64_t)tiles.size();
+    std::vector<int32_t> byc(tiles);
+    std::stable_sort(byc.begin(), byc.end(), [&](int32_t a, int32_t b) { return a % tpp < b % tpp; });
+    int64_t K = 0;
+    std::vector<std::vector<int32_t>> share(8);
+    for (int x = 0; x < 8; ++x) {
+        share[x].assign(byc.begin() + L * x / 8, byc.begin() + L * (x + 1) / 8);
+        std::sort(share[x].begin(), share[x].end()); // tile id ascending = plane by plane, column by column
+        K = std::max<int64_t>(K, ((int64_t)share[x].size() + Gx - 1) / Gx);
+    }
+    std::vector<int32_t> perm((size_t)(K * G), -1);
+    for (int x = 0; x < 8; ++x)
+        for (size_t i = 0; i < share[x].size(); ++i)
+            perm[(size_t)(((int64_t)i / Gx) * G + ((int64_t)i % Gx) * 8 + x)] = share[x][i];
+    return perm;
+}
+
+// z-slab of the structured form whose window is the npo owned planes from plane p0 of every block (blk tiles per
+// block, tpp per plane), split H planes from each cut.  ui / ub: the U tiles of the interior / boundary planes, in the
+// list's order.  bl, the boundary launch's list: the A tiles of planes 0, 1, npo-2, npo-1 of every block, plane by
+// plane, then the U tiles there.  False (and no bl) when a U tile lies outside the owned window.
+inline bool ec3d_slab_split_lists(const std::vector<int32_t> &ulist, int64_t tpp, int64_t blk, int64_t p0, int64_t npo, int64_t H,
+                                  std::vector<int32_t> &ui, std::vector<int32_t> &ub, std::vector<int32_t> &bl)
+{
+    ui.clear();
+    ub.clear();
+    bl.clear();
+    bool owned_only = true;
+    for (int32_t t : ulist) {
+        const int64_t pl = ((int64_t)t - 3 * blk) / tpp - p0; // owned plane of the U block this tile lies in
+        if (t < 3 * blk || pl < 0 || pl >= npo) owned_only = false;
+        else if (pl >= H && pl < npo - H) ui.push_back(t);
+        else ub.push_back(t);
+    }
+    if (!owned_only) return false;
+    for (int d = 0; d < 3; ++d)
+        for (int64_t pl : {(int64_t)0, (int64_t)1, npo - 2, npo - 1})
+            for (int64_t q = 0; q < tpp; ++q) bl.push_back((int32_t)(d * blk + (p0 + pl) * tpp + q));
+    bl.insert(bl.end(), ub.begin(), ub.end());
+    return true;
+}
