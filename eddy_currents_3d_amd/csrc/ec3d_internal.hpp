@@ -278,6 +278,23 @@ struct DevMatrix {
 
 struct ec3d_mg; // multigrid hierarchy (ec3d_mg.hip)
 
+// Tables of ec3d_domain_integrals (ec3d_integrals.hip), made with the RHS tables of an undivided A-V handle: the
+// conducting domains in ascending id order and the conductor cell list sorted by (domain id, scan order), cut into
+// chunks that never straddle a domain.
+struct DomIntegrals {
+    int ndom = 0;
+    int64_t nchunk = 0;
+    std::vector<int32_t> id;    // [ndom] geoPHYS id
+    std::vector<int64_t> cells; // [ndom] conductor cells of the domain
+    std::vector<double> C;      // [ndom] valPHYS(id, 2) = mu0 * sigma
+    DevBuf<int32_t> cell;       // [n_cond] 0-based DEVICE cell index (dev_cell)
+    DevBuf<int32_t> chunk;      // [nchunk][3] first entry, entries, domain ordinal
+    DevBuf<int32_t> dom_chunk;  // [ndom + 1] first chunk of every domain
+    DevBuf<double> partial;     // [nchunk][4] sums of q, fx, fy, fz per chunk
+    DevBuf<double> sums;        // [ndom][4]
+    PinnedBuf<double> host;     // [ndom][4] where the call's one copy lands
+};
+
 // The host's cursor of a run of iterations.  The device state is addressed by the iteration number (rr0[it & 1], AP in
 // apbuf[it & 1], P and S in their rings), so the host keeps in step with it here and nowhere else: ec3d_run_reset starts
 // a run, ec3d_run_open says which iterations a call launches, ec3d_after_s / ec3d_after_p advance it behind a launch
@@ -416,6 +433,7 @@ struct ec3d_ctx {
     DevBuf<int32_t> src_idx;       // per-step source scatter staging
     DevBuf<double> src_val;
     int64_t src_cap = 0;
+    DomIntegrals dom;              // per-domain integrals (ec3d_integrals.hip); freed with cond_cell
     // plain band streams whose placement was probed (place_bands): kept across a change of matrix of the same size, so
     // the probe runs once per handle and size, and what it found (candidate times in us, the one kept)
     DevBuf<double> placed_bands;
@@ -676,3 +694,7 @@ void ec3d_free_output(ec3d_ctx *c);
 void ec3d_free_rhs(ec3d_ctx *c);
 int ec3d_setup_rhs(ec3d_ctx *c, int64_t nCells, const int8_t *geoPHYS, const int32_t *geoPHYS_C,
                    const double *valPHYS, int32_t nsub_glob, double dt);
+// ec3d_integrals.hip
+void ec3d_free_integrals(ec3d_ctx *c);
+int ec3d_setup_integrals(ec3d_ctx *c, int64_t nCells, const int8_t *geoPHYS, const int32_t *geoPHYS_C,
+                         const double *valPHYS, int32_t nsub_glob);

@@ -111,6 +111,7 @@ void ec3d_free_rhs(ec3d_ctx *c)
     c->rhs_tmp.reset();
     c->src_idx.reset();
     c->src_val.reset();
+    ec3d_free_integrals(c);
     c->n_cond = 0; c->n_cond_domains = 0; c->nu_siz_max = 0; c->src_cap = 0;
     for (auto &o : c->bnd_off) o = 0;
 }
@@ -155,6 +156,9 @@ int ec3d_setup_rhs(ec3d_ctx *c, int64_t nCells, const int8_t *geoPHYS, const int
     if (!lists.empty())
         EC3D_HIP(hipMemcpyAsync(c->bnd_list, lists.data(), lists.size() * 4, hipMemcpyHostToDevice, c->stream));
     EC3D_HIP(hipStreamSynchronize(c->stream));
+    // the list of ec3d_domain_integrals: undivided handles only (a z-slab holds part of a domain)
+    if (!c->in_multi && nCells == (int64_t)c->sdx * c->sdy * c->sdz)
+        return ec3d_setup_integrals(c, nCells, geoPHYS, geoPHYS_C, valPHYS, nsub_glob);
     return 0;
 }
 

@@ -24,7 +24,7 @@ module ec3d_hip
               ec3d_set_u_rhs, EC3D_U_RHS_REFERENCE, EC3D_U_RHS_ALL, &
               ec3d_set_precond_precision, ec3d_get_precond_precision, EC3D_PRECOND_FP64, EC3D_PRECOND_FP32, &
               ec3d_set_precond_coarsening, ec3d_get_precond_coarsening, EC3D_COARSEN_REDISCRETIZE, EC3D_COARSEN_AGGREGATE, &
-              ec3d_set_precond_grid, ec3d_get_precond_grid
+              ec3d_set_precond_grid, ec3d_get_precond_grid, ec3d_domain_integral, ec3d_domain_integrals
 
     integer(c_int), parameter :: EC3D_VEC_X = 0, EC3D_VEC_B = 1   ! Uaf, Jaf
     integer(c_int), parameter :: EC3D_PRECOND_NONE = 0, EC3D_PRECOND_MG = 1   ! ec3d_set_preconditioner
@@ -32,6 +32,13 @@ module ec3d_hip
     integer(c_int), parameter :: EC3D_U_RHS_REFERENCE = 0, EC3D_U_RHS_ALL = 1   ! ec3d_set_u_rhs
     integer(c_int32_t), parameter :: EC3D_PRECOND_FP64 = 0, EC3D_PRECOND_FP32 = 1   ! ec3d_set_precond_precision
     integer(c_int32_t), parameter :: EC3D_COARSEN_REDISCRETIZE = 0, EC3D_COARSEN_AGGREGATE = 1   ! ec3d_set_precond_coarsening
+
+    ! one record of ec3d_domain_integrals (ec3d_domain_integral of include/ec3d_hip.h)
+    type, bind(C) :: ec3d_domain_integral
+        integer(c_int32_t) :: domain, pad
+        integer(c_int64_t) :: cells
+        real(c_double) :: sigma, joule_w, force_n(3)
+    end type
 
     interface
         integer(c_int) function ec3d_create(h, device) bind(C, name="ec3d_create")
@@ -134,6 +141,17 @@ module ec3d_hip
             type(c_ptr), value :: h
             real(c_double), intent(in) :: delta(*)
             real(c_float), intent(out) :: fA(*), fEddy(*), fSource(*), fB(*)
+        end function
+        ! Joule loss [W] and Lorentz force [N] per conducting domain from the resident Uaf, Jaf: the integrals of the
+        ! fields above before their rounding to REAL(4), ascending domain id; call after ec3d_post_update.  ndomains
+        ! receives the count; cap = room in out (cap = 0 and any out: the count only, status 2 when there are domains)
+        integer(c_int) function ec3d_domain_integrals(h, delta, cap, ndomains, out) bind(C, name="ec3d_domain_integrals")
+            import :: c_ptr, c_int, c_int32_t, c_double, ec3d_domain_integral
+            type(c_ptr), value :: h
+            real(c_double), intent(in) :: delta(*)
+            integer(c_int32_t), value :: cap
+            integer(c_int32_t), intent(out) :: ndomains
+            type(ec3d_domain_integral), intent(out) :: out(*)
         end function
         ! the same beside the next time step: _begin returns at once (field kernel + copy into a pinned buffer are
         ! enqueued), _wait blocks until that buffer has landed and returns C pointers to 3*ncells REAL(4) each

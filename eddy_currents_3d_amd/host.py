@@ -339,7 +339,7 @@ class _SourcesAhead:
 
 def run(model: vxc.VxcModel, solver, steps: int | None = None, out_dir: str | None = None, on_step=None,
         on_rhs=None, on_solved=None, write_output=None, overlap_output: bool = True, on_fields=None, on_written=None,
-        precond: str | None = None, u_rhs: str | None = None):
+        precond: str | None = None, u_rhs: str | None = None, integrals: bool = False):
     """The reference's run of ``model`` on ``solver`` (an EC3DSolver): assemble, then step until T >= stop (or
     ``steps`` steps).  Returns a list of per-step dicts (T, iter).  ``out_dir``: write ``field_N.vtk`` there at
     the reference's output cadence.  Hooks, all ``(k, solver, info)``: ``on_rhs`` when Jaf (B) of step k is
@@ -358,7 +358,12 @@ def run(model: vxc.VxcModel, solver, steps: int | None = None, out_dir: str | No
     to move them away).  ``precond`` (e.g. "block-mg"): solver.set_preconditioner(precond) right after the assembly;
     None leaves the handle's preconditioner as it is.  ``u_rhs`` ("reference" or "all"): solver.set_u_rhs(u_rhs)
     before the assembly -- which U rows get their right-hand side with several conducting domains; None leaves the
-    handle's rule (default "reference", src/EC3D.f90:374-392) as it is."""
+    handle's rule (default "reference", src/EC3D.f90:374-392) as it is.  ``integrals``: ``info["integrals"]`` of every
+    step holds solver.domain_integrals(delta) -- Joule loss and Lorentz force per conducting domain --, taken right
+    after the post-update and before ``on_step``; one handle only (an EC3DMulti raises ValueError)."""
+    if integrals and not hasattr(solver, "domain_integrals"):
+        raise ValueError("integrals=True needs an EC3DSolver: the per-domain integrals are not available on the "
+                         "z-slabs of an EC3DMulti")
     t = vxc.domain_tables(model)
     if t["dt"] is None or t["time"] is None:
         raise ValueError("the model has no 'tran stop=... step=...' line")
@@ -385,7 +390,7 @@ def run(model: vxc.VxcModel, solver, steps: int | None = None, out_dir: str | No
     log = []
     try:
         log = _time_loop(solver, t, prog, (sdx, sdy, sdz), conducting, out_dir, pipe, steps, on_step, on_rhs, on_solved,
-                         write_output, on_fields, on_written, DT, Time, Nout, T, Ntime, Nprint, Npoint)
+                         write_output, on_fields, on_written, DT, Time, Nout, T, Ntime, Nprint, Npoint, integrals)
     finally:
         if pipe is not None:
             pipe.finish()
@@ -393,7 +398,7 @@ def run(model: vxc.VxcModel, solver, steps: int | None = None, out_dir: str | No
 
 
 def _time_loop(solver, t, prog, dims, conducting, out_dir, pipe, steps, on_step, on_rhs, on_solved, write_output,
-               on_fields, on_written, DT, Time, Nout, T, Ntime, Nprint, Npoint):
+               on_fields, on_written, DT, Time, Nout, T, Ntime, Nprint, Npoint, integrals=False):
     sdx, sdy, sdz = dims
     log = []
     ahead = _SourcesAhead(prog, T, DT, Time, steps)
@@ -409,6 +414,8 @@ def _time_loop(solver, t, prog, dims, conducting, out_dir, pipe, steps, on_step,
             if on_solved is not None:
                 on_solved(len(log), solver, info)
             solver.post_update()
+            if integrals:
+                info["integrals"] = solver.domain_integrals(t["delta"])
             if Ntime >= Nprint and Ntime != 0:               # :437-446
                 Nprint = Ntime + Nout
                 Npoint += 1

@@ -1,12 +1,13 @@
 """Run a VoxCad ``.vxc`` model the way the reference program does, on one MI355X.
 
-    python -m eddy_currents_3d_amd.run model.vxc [--steps N] [--out DIR] [--device D]
+    python -m eddy_currents_3d_amd.run model.vxc [--steps N] [--out DIR] [--device D] [--integrals FILE]
     python -m torch.distributed.run --nproc-per-node G -m eddy_currents_3d_amd.run model.vxc ...   (G GPUs)
 
 Reads the file (eddy_currents_3d_amd/vxc.py), assembles the A-V system on the device, and runs the
 reference's time loop (eddy_currents_3d_amd/host.py) with the fields resident in HBM; ``field_N.vtk`` files
 and ``src_N.vtk`` files go to ``--out`` (default: the ``dir=`` name of the model's solver line, as the
-reference does).
+reference does).  ``--integrals FILE``: Joule loss [W] and Lorentz force [N] of every conducting domain after every
+step, as CSV (one GPU only).
 """
 from __future__ import annotations
 
@@ -16,7 +17,16 @@ import sys
 import time
 
 
-def main(argv=None):
+INTEGRALS_HEADER = "step,T,domain,cells,joule_w,force_x,force_y,force_z"
+
+
+def integrals_rows(step, T, records):
+    """CSV lines of one step's EC3DSolver.domain_integrals() records, floats at repr() precision."""
+    return [",".join([str(int(step)), repr(float(T)), str(r["domain"]), str(r["cells"]), repr(float(r["joule_w"]))]
+                     + [repr(float(f)) for f in r["force_n"]]) for r in records]
+
+
+def build_parser():
     ap = argparse.ArgumentParser(prog="python -m eddy_currents_3d_amd.run", description=__doc__.split("\n\n")[0])
     ap.add_argument("model", help="path of the .vxc file")
     ap.add_argument("--steps", type=int, default=None, help="stop after this many time steps (default: the model's stop time)")
@@ -32,7 +42,18 @@ def main(argv=None):
                     help="U rows that get their right-hand side when the model has several conducting domains: "
                          "reference (rows up to the largest domain's cell count, as the reference does; default) or "
                          "all (every U row: the consistent form, a departure from the reference; one GPU only)")
+    ap.add_argument("--integrals", metavar="FILE", default=None,
+                    help="write Joule loss and Lorentz force per conducting domain and time step to this CSV file "
+                         "(" + INTEGRALS_HEADER + "; one GPU only)")
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
     a = ap.parse_args(argv)
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if world > 1 and a.integrals:
+        ap.error("--integrals runs on one GPU only; a z-slab holds only part of a conducting domain")
 
     from . import EC3DSolver, host, vxc
     model = vxc.read_vxc(a.model)
@@ -45,11 +66,18 @@ def main(argv=None):
           f"tol={t['tol']:g} itmax={t['itmax']}", flush=True)
     t0 = time.perf_counter()
 
+    csv = None
+    if a.integrals:   # one line per step and domain, written as the run goes
+        csv = open(a.integrals, "w")
+        csv.write(INTEGRALS_HEADER + "\n")
+
     def on_step(k, s, info):
+        if csv is not None:
+            csv.writelines(line + "\n" for line in integrals_rows(k, info["T"], info["integrals"]))
+            csv.flush()
         print(f"step {k:4d}  T={info['T']:.6g}  iter={info['iter']}"
               + (f"  -> field_{info['output']}.vtk" if "output" in info and out_dir else ""), flush=True)
 
-    world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1 and a.precond != "none":
         ap.error(f"--precond {a.precond} runs on one GPU only; the multi-rank z-slab path has no preconditioner")
     if world > 1 and a.u_rhs != "reference":
@@ -69,10 +97,15 @@ def main(argv=None):
             return 0
         n = 3 * model.vox.size + t["ncells0"]
     else:
-        with EC3DSolver(device=a.device) as s:
-            log = host.run(model, s, steps=a.steps, out_dir=out_dir, on_step=on_step,
-                           precond=None if a.precond == "none" else a.precond, u_rhs=a.u_rhs)
-            n = s.n
+        try:
+            with EC3DSolver(device=a.device) as s:
+                log = host.run(model, s, steps=a.steps, out_dir=out_dir, on_step=on_step,
+                               precond=None if a.precond == "none" else a.precond, u_rhs=a.u_rhs,
+                               integrals=csv is not None)
+                n = s.n
+        finally:
+            if csv is not None:
+                csv.close()
     wall = time.perf_counter() - t0
     its = sum(i["iter"] for i in log)
     print(f"{len(log)} steps, {its} solver iterations, n={n}, {wall:.2f} s wall "

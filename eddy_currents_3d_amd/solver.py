@@ -41,6 +41,12 @@ class MatrixInfo(C.Structure):
                 ("dict_classes", C.c_int32)]
 
 
+class DomainIntegral(C.Structure):
+    """ec3d_domain_integral of include/ec3d_hip.h."""
+    _fields_ = [("domain", C.c_int32), ("pad", C.c_int32), ("cells", C.c_int64), ("sigma", C.c_double),
+                ("joule_w", C.c_double), ("force_n", C.c_double * 3)]
+
+
 class CsrProbe(C.Structure):
     _fields_ = [("structured", C.c_int32), ("sdx", C.c_int32), ("sdy", C.c_int32), ("sdz", C.c_int32),
                 ("n_cond", C.c_int32), ("classes", C.c_int32), ("plane_pitch", C.c_int32)]
@@ -71,7 +77,8 @@ EXPORTS = ["sprsbcgstabwr_", "ec3d_invalidate", "ec3d_create", "ec3d_destroy", "
            "ec3d_multi_iterate", "ec3d_multi_synchronize", "ec3d_true_residual", "ec3d_multi_true_residual", "ec3d_get_visit_order", "ec3d_probe_csr_multi", "ec3d_multi_spmv", "ec3d_multi_api_calls", "ec3d_multi_plan", "ec3d_multi_halo_rows", "ec3d_rccl_unique_id", "ec3d_multi_create_rank", "ec3d_format_real8_gfortran", "ec3d_multi_iterate_timed", "ec3d_multi_rccl_info",
            "ec3d_set_preconditioner", "ec3d_get_preconditioner", "ec3d_precond_apply", "ec3d_set_u_rhs",
            "ec3d_set_precond_precision", "ec3d_get_precond_precision", "ec3d_set_precond_coarsening",
-           "ec3d_get_precond_coarsening", "ec3d_set_precond_grid", "ec3d_get_precond_grid"]
+           "ec3d_get_precond_coarsening", "ec3d_set_precond_grid", "ec3d_get_precond_grid",
+           "ec3d_domain_integrals"]
 U_RHS = {"reference": 0, "all": 1}   # EC3D_U_RHS_* of include/ec3d_hip.h
 PRECOND = {"none": 0, "mg": 1, "block-mg": 2}   # EC3D_PRECOND_* of include/ec3d_hip.h
 PRECOND_E_MATRIX, PRECOND_E_COARSE = 20, 21   # ec3d_set_preconditioner's refusals
@@ -171,6 +178,7 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.ec3d_post_update.argtypes = [hp]
     L.ec3d_vtk_fields.argtypes = [hp, _f64, hp, hp, hp, hp]
     L.ec3d_vtk_fields_begin.argtypes = [hp, _f64, C.c_int32, C.POINTER(C.c_int32)]
+    L.ec3d_domain_integrals.argtypes = [hp, _f64, C.c_int32, C.POINTER(C.c_int32), C.POINTER(DomainIntegral)]
     L.ec3d_vtk_fields_wait.argtypes = [hp, C.c_int32] + [C.POINTER(C.POINTER(C.c_float))] * 4 + [C.POINTER(C.c_int64)]
     L.ec3d_set_workgroups.argtypes = [hp, C.c_int32]
     L.ec3d_get_matrix_info.argtypes = [hp, C.POINTER(MatrixInfo)]
@@ -499,6 +507,21 @@ class EC3DSolver:
                                             fe.ctypes.data if conducting else None, fs.ctypes.data,
                                             fb.ctypes.data), "ec3d_vtk_fields")
         return dict(A=fa, eddy=fe, source=fs, B=fb)
+
+    def domain_integrals(self, delta):
+        """Joule loss and Lorentz force per conducting domain from the resident X, B (ec3d_domain_integrals): the
+        integrals of the fields field_N.vtk shows, in float64, summed on the device.  A list, ascending domain id, of
+        dict(domain, cells, sigma [S/m], joule_w [W], force_n [N], numpy array of 3); empty without conductors.
+        Meaningful after post_update of a step."""
+        d = np.ascontiguousarray(delta, np.float64)
+        n = C.c_int32(0)
+        _chk(self.L, self.L.ec3d_domain_integrals(self.h, d, 0, C.byref(n), None), "ec3d_domain_integrals")
+        if n.value == 0:
+            return []
+        out = (DomainIntegral * n.value)()
+        _chk(self.L, self.L.ec3d_domain_integrals(self.h, d, n.value, C.byref(n), out), "ec3d_domain_integrals")
+        return [dict(domain=int(r.domain), cells=int(r.cells), sigma=float(r.sigma), joule_w=float(r.joule_w),
+                     force_n=np.array(r.force_n[:], np.float64)) for r in out[:n.value]]
 
     def vtk_fields_begin(self, delta, big_endian: bool = True) -> int:
         """Start the field output of this step WITHOUT waiting (ec3d_vtk_fields_begin): the field kernel on the

@@ -141,6 +141,35 @@ int ec3d_vtk_fields_begin(ec3d_handle h, const double *delta, int32_t big_endian
 int ec3d_vtk_fields_wait(ec3d_handle h, int32_t slot, const float **field_A, const float **field_eddy,
                          const float **field_source, const float **field_B, int64_t *ncells);
 
+/* Joule loss and Lorentz force per conducting domain, from the resident Uaf (X) and Jaf (B), summed on the device.
+ * They are the integrals of the very fields field_N.vtk shows, before their rounding to float32 -- not a
+ * Maxwell-stress evaluation.  Per conductor cell (geoPHYS_C != 0), in double precision and without contraction:
+ *   J = s * Jaf, s = -0.07957747154594766788444e7 (Vector_field_eddy, A/m^2: valPHYS(:,2) is mu0 * sigma)
+ *   B = curl A, central differences clamped at the box faces (Vector_field_B)
+ *   q = Jx*Jx + Jy*Jy + Jz*Jz,   f = J x B
+ * and per domain d (the cells' geoPHYS id), with C_d = valPHYS(d, 2):
+ *   cells    conductor cells of the domain
+ *   sigma    C_d * 0.07957747154594766788444e7                S/m
+ *   joule_w  (dx*dy*dz) * sum(q) / sigma                      W
+ *   force_n  (dx*dy*dz) * sum(fx, fy, fz)                     N
+ * Domains come in ascending id order.  *ndomains receives their number; out == NULL: the count only; no conductor:
+ * 0 domains, status 0.  The sums have a fixed order (no atomics): the same X, B and geometry give the same bits,
+ * whichever device form holds them.  X and B are read as they stand -- they mean the above after ec3d_post_update of
+ * a step; nothing is checked about that -- and no work vector is written.  One 32-byte-per-domain copy and one
+ * synchronisation of the handle's stream per call.
+ * Status 3: no A-V system from ec3d_assemble (a Poisson or CSR matrix); 5: a z-slab (ec3d_assemble_slab) or a slab
+ * of ec3d_multi; 2: delta or ndomains NULL, or out != NULL with cap < *ndomains (the count is still written). */
+typedef struct {
+    int32_t domain;
+    int32_t pad;
+    int64_t cells;
+    double sigma;
+    double joule_w;
+    double force_n[3];
+} ec3d_domain_integral;
+int ec3d_domain_integrals(ec3d_handle h, const double *delta, int32_t cap, int32_t *ndomains,
+                          ec3d_domain_integral *out);
+
 /* ||B - A*X|| / ||B|| of the RESIDENT vectors, computed on the device by the solve's own setup kernel
  * (src/solvers.f90:14-21); bnorm (may be NULL) receives ||B||.  The check of a returned x that does not rely
  * on the iteration's recurrence for R.  Overwrites the work vectors R, R0, P (rebuilt by the next solve). */
