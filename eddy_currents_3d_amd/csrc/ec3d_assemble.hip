@@ -791,6 +791,7 @@ int ec3d_assemble_sav_device(ec3d_ctx *c, int32_t sdx, int32_t sdy, int32_t sdz,
     A.off[0] = -g.pitch;
     A.off[6] = g.pitch;
     A.sav = 1;
+    A.sav_box = true;
     A.sav_a0 = id.a0;
     A.sav_u0 = id.u0;
     A.sav_zero = id.zero;

@@ -1544,10 +1544,12 @@ static int sav_to_csr(ec3d_ctx *c, std::vector<int32_t> &irow, std::vector<int32
             const int cc = cls[(size_t)(d * nCd + q)];
             const double *t = &tab[(size_t)cc * 16];
             // a box-position class (tx + 3 ty + 9 tz) keeps every neighbour inside the box, also with coefficient 0.0
-            // (a boundary value of 0: the reference stores that zero, src/EC3D.f90:528-646)
+            // (a boundary value of 0: the reference stores that zero, src/EC3D.f90:528-646).  Only ec3d_assemble numbers
+            // its classes by box position; the recogniser (ec3d_sav_csr.cpp) numbers them as the rows come, and what
+            // it read from CSR comes back without the zeros that were stored
             const int tp[3] = {cc % 3, (cc / 3) % 3, cc / 9};
             for (int b = 0; b < 7; ++b) {
-                const bool inside = cc < 27 && b != 3 && tp[b < 3 ? 2 - b : b - 4] != (b < 3 ? 0 : 2);
+                const bool inside = A.sav_box && cc < 27 && b != 3 && tp[b < 3 ? 2 - b : b - 4] != (b < 3 ? 0 : 2);
                 if (t[b] != 0.0) put(d * nC + c->ref_cell(q + A.off[b]) + 1, t[b]);
                 else if (inside) { jcol.push_back((int32_t)(d * nC + c->ref_cell(q + A.off[b]) + 1)); valA.push_back(t[b]); }
             }

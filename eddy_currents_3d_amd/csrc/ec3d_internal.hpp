@@ -263,6 +263,7 @@ struct DevMatrix {
     int ncls = 0;
     // structured A-V form (see MatView)
     int sav = 0, sav_a0 = 0, sav_u0 = 0, sav_zero = 0;
+    bool sav_box = false; // classes 0 .. 26 are box positions tx + 3 ty + 9 tz (ec3d_assemble; not a form read from CSR)
     DevBuf<int32_t> ulist; // tiles of the U block that hold at least one unknown
     int ulist_n = 0;
     std::vector<int32_t> ulist_host; // host copy for the visit-order export

@@ -178,7 +178,9 @@ int ec3d_true_residual(ec3d_handle h, double *rel, double *bnorm);
 /* y = A*x through the device format (src/solvers.f90:54-61), host vectors.  Parity probe. */
 int ec3d_spmv(ec3d_handle h, const double *x, double *y);
 
-/* Read the device matrix back as the reference's 1-based CSR (two-pass: jcol == NULL -> sizes). */
+/* Read the device matrix back as the reference's 1-based CSR (two-pass: jcol == NULL -> sizes).  A matrix from
+ * ec3d_assemble comes back with the zeros the reference stores (boundary value 0); one from ec3d_set_matrix_csr
+ * without the zeros it stored. */
 int ec3d_export_csr(ec3d_handle h, int32_t *n, int64_t *nnz, int32_t *irow, int32_t *jcol,
                     double *valA);
 
