@@ -11,6 +11,7 @@
 //   * U rows (7 or 13 entries, :766-959): entirely in the tail, sorted ascending (:942);
 //   * U row index = scan-order count (:521, :955); U column ids are geoPHYS_C's (:767).
 #include "ec3d_internal.hpp"
+#include "ec3d_sweep_lists.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -477,6 +478,22 @@ __global__ __launch_bounds__(256) void k_assemble_sav(GridPar g, const int8_t *_
     atomicAdd(nnz, cnt);
 }
 
+// ec3d_class_runs (ec3d_sweep_lists.hpp) on the device: one workgroup of 128 threads per patch tile of the planes
+// 1 .. planes-1, a dword of class bytes per thread against the dword kdz rows below.  (The patch's rows start at
+// multiples of EC3D_PX in a plane whose pitch is a multiple of EC3D_TILE: every dword is aligned.)
+static_assert(EC3D_PX % 4 == 0 && EC3D_TILE / 4 == 128, "k_class_runs: a dword per thread, 128 threads per tile");
+__global__ __launch_bounds__(128) void k_class_runs(const uint8_t *__restrict__ cls, uint8_t *__restrict__ flag, int64_t tpp,
+                                                    int64_t npx, int64_t sdx, int64_t kdz)
+{
+    const int64_t tile = tpp + blockIdx.x; // plane 0 has nothing below it: its flags stay 0
+    const int64_t k = tile / tpp, q = tile % tpp, pyi = q / npx, pxi = q % npx;
+    const int y = threadIdx.x / (EC3D_PX / 4), x4 = threadIdx.x % (EC3D_PX / 4);
+    const int64_t r = k * kdz + (pyi * EC3D_PY + y) * sdx + pxi * EC3D_PX + 4 * x4;
+    const uint32_t a = *reinterpret_cast<const uint32_t *>(cls + r), b = *reinterpret_cast<const uint32_t *>(cls + r - kdz);
+    const int differs = __syncthreads_or(a != b);
+    if (threadIdx.x == 0) flag[tile] = differs ? 0 : 1;
+}
+
 } // namespace
 
 static int64_t round_up64(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
@@ -495,6 +512,27 @@ static int build_device_table(ec3d_ctx *c, DevMatrix &A, GridPar &g, const doubl
     EC3D_HIP(hipMemsetAsync(A.cls, g.zero_cls, (size_t)A.n_pad, c->stream));
     A.bytes += (int64_t)A.n_pad + ncls * 56;
     return ncls;
+}
+
+int ec3d_build_class_runs(ec3d_ctx *c, DevMatrix &A)
+{
+    A.cls_same.reset();
+    A.cls_same_n = 0;
+    int64_t planes = 0, tpp = 0;
+    if (A.ncls <= 0 || !A.cls || !ec3d_class_runs_shape(A.nb, A.off, A.n, EC3D_PX, EC3D_PY, planes, tpp)) return 0;
+    if (planes * A.off[6] > A.n_pad || (planes - 1) * tpp > (int64_t)INT32_MAX) return 0;
+    // the kernels read the flag of the tile a plane above the one they are at, by dwords: a plane of zeros and a dword more
+    const size_t len = (size_t)(planes * tpp + tpp + 4);
+    EC3D_HIP(A.cls_same.alloc(len));
+    EC3D_HIP(hipMemsetAsync(A.cls_same, 0, len, c->stream));
+    if (planes > 1) {
+        k_class_runs<<<(unsigned)((planes - 1) * tpp), 128, 0, c->stream>>>(A.cls, A.cls_same, tpp, A.off[5] / EC3D_PX, A.off[5],
+                                                                           A.off[6]);
+        EC3D_HIP(hipGetLastError());
+    }
+    A.cls_same_n = planes * tpp;
+    A.bytes += (int64_t)len;
+    return 0;
 }
 
 int ec3d_assemble_poisson_device(ec3d_ctx *c, int32_t sdx, int32_t sdy, int32_t sdz, int32_t k0, int32_t k1,
@@ -530,6 +568,8 @@ int ec3d_assemble_poisson_device(ec3d_ctx *c, int32_t sdx, int32_t sdy, int32_t 
             return 100;
         }
         k_assemble_poisson<<<(unsigned)nblk, 256, 0, c->stream>>>(g, nullptr, A.cls);
+        EC3D_HIP(hipGetLastError());
+        if ((rc = ec3d_build_class_runs(c, A))) return rc;
     } else {
         const size_t bb = (size_t)7 * A.n_pad * sizeof(double);
         {
@@ -574,6 +614,7 @@ int ec3d_assemble_poisson_level(ec3d_ctx *c, DevMatrix &A, int32_t sdx, int32_t 
     const int64_t nblk = (g.nCells + 255) / 256;
     k_assemble_poisson<<<(unsigned)nblk, 256, 0, c->stream>>>(g, nullptr, A.cls);
     EC3D_HIP(hipGetLastError());
+    if ((rc = ec3d_build_class_runs(c, A))) return rc;
     EC3D_HIP(hipStreamSynchronize(c->stream));
     A.nnz = 7 * g.nCells - 2 * ((int64_t)sdy * sdz + (int64_t)sdx * sdz) - 2 * (int64_t)sdx * sdy;
     return 0;

@@ -146,6 +146,7 @@ MatView DevMatrix::view() const
         v.off[b] = off[b];
     }
     v.cls = cls;
+    v.cls_same = cls_same;
     v.table = table;
     v.ncls = ncls;
     v.sav = sav;
@@ -1248,6 +1249,7 @@ int ec3d_upload_matrix(ec3d_ctx *c, const HostMatrix &M, int64_t halo)
         A.ncls = M.ncls;
         if ((rc = up(A.cls, M.cls, A.bytes, c->stream))) return rc;
         if ((rc = up(A.table, M.table, A.bytes, c->stream))) return rc;
+        if ((rc = ec3d_build_class_runs(c, A))) return rc;
     } else {
         const size_t nbytes = std::max<size_t>(M.bands.size(), 1) * sizeof(double);
         if ((rc = ec3d_alloc_bands(c, A.bands, nbytes))) return rc;
@@ -1717,6 +1719,21 @@ extern "C" int ec3d_get_visit_order(ec3d_handle c, int which, int32_t *nwg, int6
             o += (int64_t)v[i].size();
         }
         offsets[v.size()] = (int32_t)o;
+    }
+    return 0;
+}
+
+extern "C" int ec3d_get_class_runs(ec3d_handle c, int64_t *count, uint8_t *flags, int64_t cap)
+{
+    int rc = ec3d_need_matrix(c, "ec3d_get_class_runs");
+    if (rc) return rc;
+    if (!count) return 2;
+    const DevMatrix &A = c->A;
+    *count = A.cls_same ? A.cls_same_n : 0;
+    if (flags && *count > 0 && cap > 0) {
+        EC3D_HIP(hipSetDevice(c->device));
+        EC3D_HIP(hipStreamSynchronize(c->stream));
+        EC3D_HIP(hipMemcpy(flags, A.cls_same, (size_t)std::min(cap, *count), hipMemcpyDeviceToHost));
     }
     return 0;
 }

@@ -42,6 +42,7 @@ struct MatView {
     const double *tval;
     // dictionary form of the bands (ncls > 0): band[b][r] == table[cls[r] * nb + b]
     const uint8_t *cls; // [n_pad]
+    const uint8_t *cls_same; // per 2-D tile: its classes equal those of the tile below (DevMatrix::cls_same); or null
     const double *table;
     int ncls;
     int pm1; // bands 2 and 4 of a 7-band operator are the offsets -1 and +1
@@ -259,6 +260,11 @@ struct DevMatrix {
     DevBuf<int32_t> tcol;
     DevBuf<double> tval;
     DevBuf<uint8_t> cls; // dictionary form (ncls > 0): bands is empty
+    // dictionary form on a grid that divides into EC3D_PX x EC3D_PY patches: one byte per patch tile, 1 = every class
+    // byte of the tile equals the one kdz rows below (ec3d_class_runs in ec3d_sweep_lists.hpp; made from `cls` once per
+    // matrix by ec3d_build_class_runs, never a source of its own).  Empty: the kernels load the class bytes every step.
+    DevBuf<uint8_t> cls_same;
+    int64_t cls_same_n = 0; // flags (planes * tiles per plane; the buffer holds a plane of zeros more)
     DevBuf<double> table;
     int ncls = 0;
     // structured A-V form (see MatView)
@@ -681,6 +687,8 @@ int ec3d_assemble_sav_device(ec3d_ctx *c, int32_t sdx, int32_t sdy, int32_t sdz,
 int ec3d_assemble_poisson_device(ec3d_ctx *c, int32_t sdx, int32_t sdy, int32_t sdz, int32_t k0, int32_t k1,
                                  const double *BND, const double *delta);
 // the same assembly (dictionary form) into a matrix of its own: a coarse level of the multigrid hierarchy
+// (re)make A.cls_same from A.cls where the grid divides into 2-D tiles; leaves it empty elsewhere (ec3d_assemble.hip)
+int ec3d_build_class_runs(ec3d_ctx *c, DevMatrix &A);
 int ec3d_assemble_poisson_level(ec3d_ctx *c, DevMatrix &A, int32_t sdx, int32_t sdy, int32_t sdz, const double *BND,
                                 const double *delta);
 // ec3d_mg.hip

@@ -187,6 +187,7 @@ template <> struct MatDev<FMT_DIA7> {
 };
 template <> struct MatDev<FMT_DICT7> {
     const uint8_t *cls;
+    const uint8_t *same; // per 2-D tile: its classes equal those of the tile below (DevMatrix::cls_same); or null
     const double *table;
     int64_t off[7];
     int ncls, pm1;
@@ -757,6 +758,8 @@ struct ZRegs {
     d2 rim; // 2-D tiles: the outer neighbour row of the NEXT step's centre plane (first / last patch row only)
     d2 cr[3]; // ... or its operands as requested at the end of a step, still on their way (patch_pair, request mode 4)
     double edge; // 2-D tiles, request mode 5: the cell beside the patch row's end in the NEXT step's centre plane (edge lanes)
+    unsigned short cc; // 2-D tiles, dictionary form: the thread's class pair, carried while the tiles' classes repeat ...
+    uint32_t same;     // ... which MatDev::same says of the NEXT step's tile: the dword that holds its byte (uniform; asked for a step ahead)
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -1447,12 +1450,40 @@ __device__ __forceinline__ void sav_patch_step(const MatDev<FMT_SAV> &A, const S
 #ifndef EC3D_PP_FUSEDP
 #define EC3D_PP_FUSEDP 5
 #endif
+// The class pair of a step of patch_pair (dictionary form).  The classes barely change along the march -- on the cube
+// only the two face planes differ from their neighbours, on voxel models the material interfaces -- so a tile whose 512
+// class bytes equal those of the tile below (MatDev::same, one byte per tile; ec3d_class_runs in ec3d_sweep_lists.hpp)
+// keeps the pair the thread holds: no request for it, and the table reads no longer wait for one.  The flag is uniform
+// over the workgroup and asked for a step AHEAD, as the aligned dword that holds it through the scalar cache (constant
+// address space: no vector request at all); it lands beside the LDS exchange, behind whose barrier every step waits
+// for its scalar and LDS traffic anyway.  The class load, where a step makes it, goes out with the step's first requests
+// and nothing is formed from it inside the branch (round 6: no wait for everything in flight there).  A matrix without
+// flags (A.same null) and a segment's first step load the pair.  `tile + tpp` of a column's last plane reads the plane
+// of zeros behind the flags (ec3d_build_class_runs).
+template <int FMT>
+__device__ __forceinline__ unsigned short patch_classes(const MatDev<FMT> &A, int64_t r, int64_t tile, bool first, ZRegs &z)
+{
+    unsigned short cc = 0;
+    if constexpr (FMT == FMT_DICT7) {
+        // z.same is the dword as it was asked for: this tile's byte is taken out of it only here, a step later (taken out
+        // at once, the step began with a wait for the scalar load it had just issued)
+        const bool kept = !first && ((z.same >> (8 * (unsigned)(tile & 3))) & 0xFFu) != 0;
+        uint32_t w = 0;
+        if (A.same) w = ((const __attribute__((address_space(4))) uint32_t *)(uintptr_t)A.same)[(tile + A.off[6] / EC3D_TILE) >> 2];
+        if (kept) cc = z.cc;
+        else cc = *reinterpret_cast<const unsigned short *>(A.cls + r);
+        z.cc = cc;
+        z.same = w;
+    }
+    return cc;
+}
 template <class V> struct PatchReq { static constexpr int mode = EC3D_PP_PLAIN; };
 template <> struct PatchReq<VecFused> { static constexpr int mode = EC3D_PP_FUSED; };
 template <> struct PatchReq<VecFusedP> { static constexpr int mode = EC3D_PP_FUSEDP; };
 template <int FMT, bool NTB, class V>
 __device__ __forceinline__ void patch_pair_branchy(const MatDev<FMT> &A, const double *tbl, double *pbuf, int step, const V &x,
-                                           int64_t r, bool first, ZRegs &z, double &s0, double &s1, d2 &ctr)
+                                           int64_t r, int64_t tile, bool first, ZRegs &z, double &s0, double &s1,
+                                           d2 &ctr)
 {
     // (Round 6 measured the plane above requested a step AHEAD here, as the interleaved march of the structured form does:
     // K2-in-K3 680 -> 818 us, K5-in-K1 1227 -> 1275 us at 512^3 -- behind the barrier of the LDS exchange the four waves of a
@@ -1461,8 +1492,7 @@ __device__ __forceinline__ void patch_pair_branchy(const MatDev<FMT> &A, const d
     const int t = threadIdx.x, y = t / HX, q = t % HX;
     const int64_t sdx = A.off[5], kdz = A.off[6];
     double *cur = pbuf + (step & 1) * EC3D_TILE, *nxt = pbuf + ((step + 1) & 1) * EC3D_TILE;
-    unsigned short cc = 0;
-    if constexpr (FMT == FMT_DICT7) cc = *reinterpret_cast<const unsigned short *>(A.cls + r);
+    const unsigned short cc = patch_classes<FMT>(A, r, tile, first, z);
     d2 c[7];
     if constexpr (FMT == FMT_DIA7) {
 #pragma unroll
@@ -1548,22 +1578,22 @@ __device__ __forceinline__ void patch_pair_branchy(const MatDev<FMT> &A, const d
 
 template <int FMT, bool NTB, class V>
 __device__ __forceinline__ void patch_pair(const MatDev<FMT> &A, const double *tbl, double *pbuf, int step, const V &x,
-                                           int64_t r, bool first, ZRegs &z, double &s0, double &s1, d2 &ctr)
+                                           int64_t r, int64_t tile, bool first, ZRegs &z, double &s0, double &s1,
+                                           d2 &ctr)
 {
     // (Round 6 measured the plane above requested a step AHEAD here, as the interleaved march of the structured form does:
     // K2-in-K3 680 -> 818 us, K5-in-K1 1227 -> 1275 us at 512^3 -- behind the barrier of the LDS exchange the four waves of a
     // workgroup wait for the slowest one's request at the end of EVERY step; profiles/r06_patch_plane_ahead_512.log.)
     constexpr int RQ = PatchReq<V>::mode;
     if constexpr (RQ == 2) {
-        patch_pair_branchy<FMT, NTB>(A, tbl, pbuf, step, x, r, first, z, s0, s1, ctr);
+        patch_pair_branchy<FMT, NTB>(A, tbl, pbuf, step, x, r, tile, first, z, s0, s1, ctr);
         return;
     }
     constexpr int HX = EC3D_PX / 2; // lanes per patch row
     const int t = threadIdx.x, y = t / HX, q = t % HX;
     const int64_t sdx = A.off[5], kdz = A.off[6];
     double *cur = pbuf + (step & 1) * EC3D_TILE, *nxt = pbuf + ((step + 1) & 1) * EC3D_TILE;
-    unsigned short cc = 0;
-    if constexpr (FMT == FMT_DICT7) cc = *reinterpret_cast<const unsigned short *>(A.cls + r);
+    const unsigned short cc = patch_classes<FMT>(A, r, tile, first, z);
     d2 c[7];
     if constexpr (FMT == FMT_DIA7) {
 #pragma unroll
@@ -1695,7 +1725,7 @@ __device__ __forceinline__ void spmv_pair(const MatDev<FMT> &A, const SW &sw, co
         return;
     }
     if constexpr (PATCH && (FMT == FMT_DIA7 || FMT == FMT_DICT7)) {
-        patch_pair<FMT, NTB>(A, tbl, stg, step++, x, r, first, z, s0, s1, ctr);
+        patch_pair<FMT, NTB>(A, tbl, stg, step++, x, r, tile, first, z, s0, s1, ctr);
         return;
     }
     uint8_t tflag = 0; // per tile: any tail row (bands + tail) / any coupled row (structured form)
@@ -2726,6 +2756,7 @@ template <> MatDev<FMT_DICT7> mat_dev<FMT_DICT7>(const MatView &A)
 {
     MatDev<FMT_DICT7> m;
     m.cls = A.cls;
+    m.same = A.cls_same;
     m.table = A.table;
     for (int b = 0; b < 7; ++b) m.off[b] = A.off[b];
     m.ncls = A.ncls;

@@ -69,6 +69,41 @@ inline void ec3d_patch_tables(const uint8_t *cls, int64_t planes, int64_t pitch,
         }
 }
 
+// The 2-D tiles of the single-component operator in the dictionary form (patch_pair in ec3d_kernels.hip): does a class
+// array of n rows with the band offsets off[0 .. nb) divide into px x py patches, plane by plane?  planes = n / kdz,
+// tpp = patches per plane (padded rows of a plane included: they carry class bytes like any other row).
+inline bool ec3d_class_runs_shape(int nb, const int64_t *off, int64_t n, int px, int py, int64_t &planes, int64_t &tpp)
+{
+    planes = tpp = 0;
+    if (nb != 7) return false;
+    const int64_t sdx = off[5], kdz = off[6];
+    if (sdx <= 0 || kdz <= 0 || sdx % px || kdz % sdx || (kdz / sdx) % py || n <= 0 || n % kdz) return false;
+    planes = n / kdz;
+    tpp = kdz / ((int64_t)px * py);
+    return true;
+}
+// "Same classes as the tile below", one byte per patch tile (tile = plane * tpp + q, patch q of a plane is
+// (q % npx, q / npx) as in ec3d_row_of): flag = 1 exactly when plane > 0 and all px * py class bytes of the patch equal
+// those kdz rows below.  A z-marching workgroup that steps onto such a tile keeps the class pairs it holds.  The class
+// array stays the only source of truth: the flags say nothing it does not.  Behind the planes * tpp flags come tpp + 4
+// zeros: the kernels read the flag of the tile ABOVE the one they are at (a step ahead), by dwords.
+inline void ec3d_class_runs(const uint8_t *cls, int64_t planes, int64_t kdz, int64_t sdx, int px, int py,
+                            std::vector<uint8_t> &flag)
+{
+    const int64_t npx = sdx / px, tpp = kdz / ((int64_t)px * py);
+    flag.assign((size_t)(planes * tpp + tpp + 4), 0);
+    for (int64_t k = 1; k < planes; ++k)
+        for (int64_t q = 0; q < tpp; ++q) {
+            const int64_t pyi = q / npx, pxi = q % npx;
+            bool same = true;
+            for (int y = 0; y < py && same; ++y) {
+                const uint8_t *row = &cls[(size_t)(k * kdz + (pyi * py + y) * sdx + pxi * px)];
+                same = std::equal(row, row + px, row - kdz);
+            }
+            flag[(size_t)(k * tpp + q)] = same ? 1 : 0;
+        }
+}
+
 // z segments per column of a z-marching grid of `cols` columns that wants want_s workgroups, at most max_seg
 inline int64_t ec3d_zm_segments(int64_t want_s, int64_t cols, int64_t max_seg, bool explicit_request)
 {

@@ -78,7 +78,7 @@ EXPORTS = ["sprsbcgstabwr_", "ec3d_invalidate", "ec3d_create", "ec3d_destroy", "
            "ec3d_set_preconditioner", "ec3d_get_preconditioner", "ec3d_precond_apply", "ec3d_set_u_rhs",
            "ec3d_set_precond_precision", "ec3d_get_precond_precision", "ec3d_set_precond_coarsening",
            "ec3d_get_precond_coarsening", "ec3d_set_precond_grid", "ec3d_get_precond_grid",
-           "ec3d_domain_integrals"]
+           "ec3d_domain_integrals", "ec3d_get_class_runs"]
 U_RHS = {"reference": 0, "all": 1}   # EC3D_U_RHS_* of include/ec3d_hip.h
 PRECOND = {"none": 0, "mg": 1, "block-mg": 2}   # EC3D_PRECOND_* of include/ec3d_hip.h
 PRECOND_E_MATRIX, PRECOND_E_COARSE = 20, 21   # ec3d_set_preconditioner's refusals
@@ -205,6 +205,7 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.ec3d_probe_csr.argtypes = [C.c_int32, _f64, _i32, _i32, C.POINTER(CsrProbe)]
     L.ec3d_probe_csr_multi.argtypes = [C.c_int32, _f64, _i32, _i32, C.c_int32, C.POINTER(C.c_int32)]
     L.ec3d_get_ulist.argtypes = [hp, _i32]
+    L.ec3d_get_class_runs.argtypes = [hp, C.POINTER(C.c_int64), hp, C.c_int64]
     L.ec3d_set_stream.argtypes = [hp, hp]
     L.ec3d_assemble_poisson_slab.argtypes = [hp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f64, _f64]
     L.ec3d_vector_layout.argtypes = [hp] + [C.POINTER(C.c_int64)] * 4
@@ -445,6 +446,16 @@ class EC3DSolver:
         _chk(self.L, self.L.ec3d_get_visit_order(self.h, which, C.byref(nwg), C.byref(tot), off.ctypes.data,
                                                  tiles.ctypes.data), "ec3d_get_visit_order")
         return off, tiles[:tot.value]
+
+    def class_runs(self) -> np.ndarray:
+        """One byte per 2-D tile of a dictionary-form matrix: 1 = the tile's class bytes equal those of the tile a plane
+        below (the z-marching kernels then keep theirs in registers).  Empty: the matrix has no such flags."""
+        cnt = C.c_int64(0)
+        _chk(self.L, self.L.ec3d_get_class_runs(self.h, C.byref(cnt), None, 0), "ec3d_get_class_runs")
+        out = np.zeros(cnt.value, np.uint8)
+        if cnt.value:
+            _chk(self.L, self.L.ec3d_get_class_runs(self.h, C.byref(cnt), out.ctypes.data, out.size), "ec3d_get_class_runs")
+        return out
 
     def set_zmarch(self, on: bool):
         _chk(self.L, self.L.ec3d_set_zmarch(self.h, int(bool(on))), "ec3d_set_zmarch")

@@ -520,6 +520,11 @@ typedef struct {
 /* which = 0: K4 (dots R.R, R.R0); 1: SpMV kernels (B.B, initial R.R, AP.R0, AS.S, AS.AS); 2: K2 (dot S.S) */
 int ec3d_get_reduction_geometry(ec3d_handle h, int which, ec3d_geom *g);
 int ec3d_get_ulist(ec3d_handle h, int32_t *tiles); /* ulist_n entries */
+/* Dictionary-form matrices on a grid that divides into 2-D tiles: one byte per patch tile (tile = plane * tiles per
+ * plane + patch, as ec3d_geom numbers them), 1 = every class byte of the tile equals the one a plane below -- a
+ * z-marching workgroup keeps its class bytes in registers over such a step.  *count = number of flags (0: this matrix
+ * has none and the kernels load the class bytes at every step); flags == NULL: the count only; at most cap are written. */
+int ec3d_get_class_runs(ec3d_handle h, int64_t *count, uint8_t *flags, int64_t cap);
 /* The tiles (512 rows each) every workgroup of a launch visits, in order: workgroup w visits
  * tiles[offsets[w] .. offsets[w+1]).  which as above.
  * Each thread t of a workgroup owns rows tile*512 + 2t, 2t+1 (or the two cells of a patch, ec3d_geom::patch_x) and
