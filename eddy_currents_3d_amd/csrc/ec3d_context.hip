@@ -1772,7 +1772,8 @@ extern "C" int ec3d_get_matrix_info(ec3d_handle c, ec3d_matrix_info *info)
 
 // host vectors are in the reference's numbering [Ax | Ay | Az | U(scan order)].  The structured A-V form
 // keeps the three A blocks as they are and spreads U over a 4th grid-shaped block: U(m) lives at
-// 3*nC + cell(m).  Inactive U slots are never written and stay 0.
+// 3*nC + cell(m).  Inactive U slots hold no unknown: the scatter below never writes them, ec3d_vec_h2d zeroes them with
+// the rest of the vector before it, and the kernels, which compute them like any other row, keep them 0.
 namespace {
 __global__ void k_u_scatter(double *ublock, const int32_t *cell, const double *src, int64_t nu)
 {
@@ -1793,9 +1794,14 @@ int ec3d_vec_h2d(ec3d_ctx *c, double *dev, const double *host)
         return 0;
     }
     const int64_t nA = 3 * c->A.sav_nC, nu = c->n_cond, nAref = 3 * c->plane * c->planes();
+    // Rows below n that hold no unknown -- the padding between pitched planes, the empty slots of the U block -- are
+    // computed by every kernel like any other row and nothing below copies over them: after a solve whose scalars went
+    // NaN or Inf they hold 0 + NaN * 0, which the next solve would read beside a zero coefficient and add into every
+    // dot product.  An uploaded vector starts from zeros, as on a fresh handle (R, P, S ... are produced from X and B).
+    EC3D_HIP(hipMemsetAsync(dev, 0, (size_t)c->A.n * sizeof(double), c->stream));
     if (c->pitch == c->plane)
         EC3D_HIP(hipMemcpyAsync(dev, host, (size_t)nA * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    else // one row per xy plane; the padding between planes stays zero
+    else // one row per xy plane; the padding between planes is zero
         EC3D_HIP(hipMemcpy2DAsync(dev, (size_t)c->pitch * 8, host, (size_t)c->plane * 8, (size_t)c->plane * 8,
                                   (size_t)3 * c->planes(), hipMemcpyHostToDevice, c->stream));
     if (nu) {

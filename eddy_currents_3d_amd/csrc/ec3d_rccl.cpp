@@ -41,7 +41,8 @@ const ec3d_rccl_api *ec3d_rccl_load(std::string &why)
     if (!key.empty()) {
         h = dlopen(key.c_str(), RTLD_NOW | RTLD_LOCAL);
         if (!h) {
-            L.err = "EC3D_RCCL_LIB=" + key + ": " + (dlerror() ? dlerror() : "dlopen failed");
+            const char *de = dlerror(); // once: dlerror() clears the message it returns
+            L.err = "EC3D_RCCL_LIB=" + key + ": " + (de ? de : "dlopen failed");
             why = L.err;
             return nullptr;
         }
@@ -53,7 +54,8 @@ const ec3d_rccl_api *ec3d_rccl_load(std::string &why)
         }
     }
     if (!h) {
-        L.err = std::string("RCCL not found (dlopen librccl.so.1): ") + (dlerror() ? dlerror() : "?");
+        const char *de = dlerror();
+        L.err = std::string("RCCL not found (dlopen librccl.so.1): ") + (de ? de : "?");
         why = L.err;
         return nullptr;
     }

@@ -334,6 +334,9 @@ class HipAVSlabOps(HipSlabOps):
         with self.context():
             src = self.torch.from_numpy(np.ascontiguousarray(host_array, np.float64)).to(self.device)
             b = self._base(name)
+            # rows that hold no unknown (padding between pitched planes, empty U slots) start from zero like the rest:
+            # after a solve that went NaN they hold 0 + NaN * 0 (ec3d_vec_h2d does the same for the library's uploads)
+            self.store[b:b + self.n].zero_()
             self.store[b:b + self.n].index_copy_(0, self._rm, src)
 
     def get_vector(self, name):
