@@ -62,6 +62,24 @@ def _tables(vox, conducting, C, vel, rng_bnd, delta, dt):
             np.asarray(delta, np.float64), float(dt))
 
 
+def from_boxes(dims, domains, bnd, delta, dt):
+    """Conducting domains given as voxels: dims = (sdx, sdy, sdz); domain d = 1 .. D is domains[d - 1], a dict of boxes and
+    holes ([a, b) per axis, 0-based, in the order x, y, z; a hole is carved out of the domain's own boxes), C and vel.
+    Nothing makes the result legal.  Same return value as generate."""
+    sdx, sdy, sdz = dims
+    vox = np.zeros((sdz, sdy, sdx), np.uint8)
+    for d, dom in enumerate(domains, 1):
+        for (x0, x1), (y0, y1), (z0, z1) in dom["boxes"]:
+            part = vox[z0:z1, y0:y1, x0:x1]
+            part[part == 0] = d
+        for (x0, x1), (y0, y1), (z0, z1) in dom.get("holes", ()):
+            part = vox[z0:z1, y0:y1, x0:x1]
+            part[part == d] = 0
+    ids = list(range(1, len(domains) + 1))
+    return _tables(vox, ids, {d: float(domains[d - 1]["C"]) for d in ids},
+                   {d: np.asarray(domains[d - 1]["vel"], np.float64) for d in ids}, bnd, delta, dt)
+
+
 def _box(rng, lo, hi, min_thick=3):
     """A random box [a, b) inside [lo, hi) per axis (z, y, x), at least min_thick thick."""
     out = []

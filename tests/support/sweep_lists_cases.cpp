@@ -2,7 +2,7 @@
 // the smallest shapes at which they can go wrong and prints, per case, what it gave them and what came back:
 //   case KIND NAME
 //   KEY v v v ...        one line per input and per output list, integers (doubles as %a)
-// KIND is xcd, il, slab, patch, shape or zm.  Built with the address and undefined-behaviour sanitizers.
+// KIND is xcd, il, ilgrid, slab, patch, shape or zm.  Built with the address and undefined-behaviour sanitizers.
 #include "../../eddy_currents_3d_amd/csrc/ec3d_sweep_lists.hpp"
 
 #include <cstdio>
@@ -45,23 +45,11 @@ bool masked(Mask m, int tpp, int col, int k)
     return m == ALL || (m == ONE_COLUMN && col == tpp / 2) || (m == CHECKER && ((col + k) & 1));
 }
 
-// flags: 0 no tile_flag; 1 the A_y tile coupled wherever a U tile is; 2 as 1 and one coupled A_z tile where no U tile
-// is; ustray: a tile appended to the list of U tiles (-1: none)
-void il_case(const std::string &name, int tpp, int P, int want_il, Mask m, int flags, int32_t ustray = -1)
+// what ec3d_il_umask and ec3d_il_work_list make of a list of U tiles (tile_flag given to the builder when flags != 0)
+void il_lists(const char *kind, const std::string &name, int tpp, int P, int want_il, int flags, const std::vector<int32_t> &ulist,
+              const std::vector<uint8_t> &tf)
 {
-    std::vector<int32_t> ulist;
-    std::vector<uint8_t> tf((size_t)(3 * P * tpp), 0);
-    for (int k = 0; k < P; ++k)
-        for (int col = 0; col < tpp; ++col)
-            if (masked(m, tpp, col, k)) {
-                ulist.push_back((int32_t)((3 * P + k) * tpp + col));
-                tf[(size_t)((P + k) * tpp + col)] = 1;
-            }
-    if (flags == 2)
-        for (int t = 2 * P * tpp; t < 3 * P * tpp; ++t)
-            if (!tf[(size_t)(t - P * tpp)]) { tf[(size_t)t] = 1; break; }
-    if (ustray >= 0) ulist.push_back(ustray);
-    std::printf("case il %s\n", name.c_str());
+    std::printf("case %s %s\n", kind, name.c_str());
     const int il_w = 160, min_pps = 2;
     line("in", {tpp, P, want_il, il_w, min_pps, flags});
     line("ulist", ulist);
@@ -81,6 +69,54 @@ void il_case(const std::string &name, int tpp, int P, int want_il, Mask m, int f
     ec3d_il_work_list(um, nw, tpp, P, want_il, il_w, min_pps, seg, per);
     line("per", {(long long)per});
     line("seg", seg);
+}
+
+// flags: 0 no tile_flag; 1 the A_y tile coupled wherever a U tile is; 2 as 1 and one coupled A_z tile where no U tile
+// is; ustray: a tile appended to the list of U tiles (-1: none)
+void il_case(const std::string &name, int tpp, int P, int want_il, Mask m, int flags, int32_t ustray = -1)
+{
+    std::vector<int32_t> ulist;
+    std::vector<uint8_t> tf((size_t)(3 * P * tpp), 0);
+    for (int k = 0; k < P; ++k)
+        for (int col = 0; col < tpp; ++col)
+            if (masked(m, tpp, col, k)) {
+                ulist.push_back((int32_t)((3 * P + k) * tpp + col));
+                tf[(size_t)((P + k) * tpp + col)] = 1;
+            }
+    if (flags == 2)
+        for (int t = 2 * P * tpp; t < 3 * P * tpp; ++t)
+            if (!tf[(size_t)(t - P * tpp)]) { tf[(size_t)t] = 1; break; }
+    if (ustray >= 0) ulist.push_back(ustray);
+    il_lists("il", name, tpp, P, want_il, flags, ulist, tf);
+}
+
+// The masks of grids whose plane is SEVERAL tiles (tests/av_grids.py holds the same boxes as voxels): conductor boxes
+// [a, b) per axis in a grid of sdx x sdy x P cells whose planes are `pitch` rows apart; the U tile of (column, plane) is
+// listed when one of its 512 rows is a conducting cell, and the three A tiles there are coupled.
+struct Box { int x0, x1, y0, y1, z0, z1; };
+void il_grid_case(const char *name, int sdx, int sdy, int P, int pitch, int want_il, const std::vector<Box> &boxes,
+                  const std::vector<Box> &holes)
+{
+    const int tpp = pitch / 512;
+    auto in = [](const Box &b, int x, int y, int z) { return x >= b.x0 && x < b.x1 && y >= b.y0 && y < b.y1 && z >= b.z0 && z < b.z1; };
+    std::vector<uint8_t> u((size_t)(P * tpp), 0);
+    for (int z = 0; z < P; ++z)
+        for (int y = 0; y < sdy; ++y)
+            for (int x = 0; x < sdx; ++x) {
+                bool on = false;
+                for (const Box &b : boxes) on = on || in(b, x, y, z);
+                for (const Box &h : holes) on = on && !in(h, x, y, z);
+                if (on) u[(size_t)(z * tpp + (y * sdx + x) / 512)] = 1;
+            }
+    std::vector<int32_t> ulist;
+    std::vector<uint8_t> tf((size_t)(3 * P * tpp), 0);
+    for (int t = 0; t < P * tpp; ++t)
+        if (u[(size_t)t]) {
+            ulist.push_back((int32_t)(3 * P * tpp + t));
+            for (int d = 0; d < 3; ++d) tf[(size_t)(d * P * tpp + t)] = 1;
+        }
+    il_lists("ilgrid", name, tpp, P, want_il, 1, ulist, tf);
+    line("grid", {sdx, sdy, pitch});
 }
 
 // U tiles at (plane, column) pairs of the U block of a slab whose blocks hold p0 + npo + 3 planes of 3 tiles
@@ -141,6 +177,11 @@ int main()
     il_case("coupled_without_u", 5, 33, 40, CHECKER, 2);
     il_case("u_tile_in_az", 5, 33, 40, ONE_COLUMN, 1, (3 * 33 - 1) * 5 + 2);
     il_case("u_tile_behind_the_block", 5, 33, 40, ONE_COLUMN, 1, 4 * 33 * 5);
+    // 64 x 72 x 40: 9 columns, two domains with four planes of air between them, a through hole, nothing in column 0
+    il_grid_case("S1", 64, 72, 40, 4608, 16, {{9, 52, 10, 60, 3, 14}, {20, 60, 18, 66, 18, 37}}, {{28, 36, 30, 38, 3, 14}});
+    il_grid_case("S1_one_block", 64, 72, 40, 4608, 16, {{9, 60, 10, 60, 3, 37}}, {});     // columns 0 and 8 empty
+    il_grid_case("S2", 1024, 8, 34, 8192, 40, {{400, 640, 2, 6, 3, 31}}, {});            // 16 columns of half a grid row
+    il_grid_case("S3", 40, 30, 33, 1536, 8, {{5, 34, 4, 26, 3, 30}}, {});                // 1200 cells in 1536 rows
     for (int p0 : {0, 3})
         for (int npo : {6, 7}) {
             std::vector<std::array<int, 2>> at;

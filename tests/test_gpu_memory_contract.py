@@ -25,6 +25,7 @@ import struct
 import numpy as np
 import pytest
 
+import av_grids as AGR
 import class_runs_numpy as R
 import csr_generate as G
 import guard_zones as Z
@@ -61,6 +62,9 @@ ADOPTED = {
 for _g, _p, _f in itertools.product(AV, PITCH, SAV_FORM):
     if _f != "interleaved" or _p == "pitched":
         ADOPTED[f"{_g}-{_p}-{_f}"] = ("av", _g, {**PITCH[_p], **SAV_FORM[_f]}, {})
+# the interleaved march on three columns: planes of 1200 cells in 1536 rows (tests/av_grids.py S3), tiles that start
+# mid-row, 336 padding rows behind every plane in the third; eight workgroups asked for, so segments start inside the conductor
+ADOPTED["grid-S3-pitched-interleaved"] = ("avgrid", "S3", {**SAV_FORM["interleaved"], "EC3D_NBLK_SPMV": "8"}, {})
 
 # (b): the forms that need the spare pair and the rings
 OWNED_GRIDS = [(256, 8, 9), (128, 12, 10)]
@@ -83,6 +87,8 @@ BAD_SOLVE = {
     "g2-pitched": ("av", "g2", PITCH["pitched"], {}),
     "g8a-pitched": ("av", "g8a", PITCH["pitched"], {}),
     "poisson-256x8x9-three-launch-xd4": ("poisson", (256, 8, 9), THREE_LAUNCH, {}),
+    # 336 rows of padding behind every plane of the third column, which a NaN solve leaves as 0 + NaN * 0
+    "grid-S3-pitched-interleaved": ADOPTED["grid-S3-pitched-interleaved"],
 }
 BAD_KINDS = ("nan", "overflow")
 # (e)
@@ -122,6 +128,11 @@ def system(kind, what):
                                                  float(g["dt"])),
                       n=len(g["irow"]) - 1, itmax=400, plane=sdx * sdy, cells=sdx * sdy * sdz, g=g,
                       b=np.array(g["b0"]), x0=np.array(g["xin0"]))
+        elif kind == "avgrid":
+            args = AGR.system(what)
+            sdx, sdy, sdz = AGR.GRIDS[what]["dims"]
+            sy = dict(build=lambda s: s.assemble(*args), n=3 * sdx * sdy * sdz + int(np.count_nonzero(args[1])), itmax=400,
+                      plane=sdx * sdy, cells=sdx * sdy * sdz)
         else:
             valA, irow, jcol = G.case(what)[:3] if kind == "csr" else R.operator(what, R.DIMS)[:3]
             sy = dict(build=lambda s: s.set_matrix_csr(valA, irow, jcol), n=len(irow) - 1, itmax=5000)
@@ -223,7 +234,7 @@ def check_form(s, kind, what, env):
         patches = marching and env.get("EC3D_PATCH") == "1" and s.info.dict_classes > 0
         assert env.get("EC3D_PATCH") in ("0", "1") or not marching          # every marching case says which tiles it means
         assert (g.patch_x, g.patch_y) == ((128, 4) if patches else (0, 0))
-    if kind == "av":
+    if kind in ("av", "avgrid"):
         pi = Z.pitch_info(s, system(kind, what)["plane"])
         assert pi is not None and len(pi["hidden"]) > 0                      # the structured form
         if env.get("EC3D_PITCH") == "2":
@@ -237,6 +248,9 @@ def check_form(s, kind, what, env):
             assert s.fusion() == (0, 0)
         if env.get("EC3D_SAV_IL") == "2":
             assert g.ulist_n == 0 and len(s.ulist()) > 0                     # the U tiles are inside the march
+        if kind == "avgrid":
+            assert g.zm_tpp == 3 and pi["pitch"] == 1536 and pi["plane"] == 1200 and s.n == system(kind, what)["n"]
+            assert [int(t) for t in s.ulist()] == AGR.u_tiles(what)
 
 
 # ---- (a) ---------------------------------------------------------------------------------------------------------------
@@ -594,6 +608,12 @@ def test_the_lists_hold_what_they_are_meant_to():
             assert (av[f"{g}-{p}-linear"].get("EC3D_PITCH") == "2") == (p == "pitched")
         assert av[f"{g}-pitched-interleaved"]["EC3D_SAV_IL"] == "2"
     assert len(av) == 15
+    grid = {k: c for k, c in ADOPTED.items() if c[0] == "avgrid"}
+    assert set(grid) == {"grid-S3-pitched-interleaved"} and grid["grid-S3-pitched-interleaved"][1] == "S3"
+    assert grid["grid-S3-pitched-interleaved"][2] == {**SAV_FORM["interleaved"], "EC3D_NBLK_SPMV": "8"}
+    assert AGR.GRIDS["S3"]["dims"] == (40, 30, 33) and AGR.pitch_of("S3") == 1536 and AGR.GRIDS["S3"]["pitched"]
+    assert {"spmv x0", "spmv b", "solve 1e-10", "S exit", "R exit", "itmax 4", "true_residual"} <= \
+        {label for label, _ in calls(system("avgrid", "S3"), {"S": 0.0, "R": 0.0})}
     labels = [label for label, _ in calls(system("av", "g2"), {"S": 0.0, "R": 0.0})]
     assert labels[:2] == ["spmv x0", "spmv b"] and {"solve 1e-10", "S exit", "R exit", "itmax 0", "itmax 1", "itmax 4",
                                                     "iterate(1, 5) + iterate(6, 3)", "true_residual", "rhs_step moving=0",
@@ -615,7 +635,8 @@ def test_the_lists_hold_what_they_are_meant_to():
     assert (24 * 24 * 12) % 512 != 0          # a slab of the plain plan whose rows [n, n_pad) overlap the upper halo plane
     # (d), (e)
     assert set(BAD_SOLVE) == {"poisson-17x9x5", "csr-nb3", "g2-auto", "g2-pitched", "g8a-pitched",
-                              "poisson-256x8x9-three-launch-xd4"}
+                              "poisson-256x8x9-three-launch-xd4", "grid-S3-pitched-interleaved"}
+    assert BAD_SOLVE["grid-S3-pitched-interleaved"] is ADOPTED["grid-S3-pitched-interleaved"]
     assert BAD_SOLVE["poisson-256x8x9-three-launch-xd4"][2]["EC3D_XDEFER"] == "4" and BAD_KINDS == ("nan", "overflow")
     assert set(routes(system("av", "g2"))) == {"solve", "upload + solve_resident", "rhs_step -> solve -> post_update"}
     assert [(c[0], c[1]) for c in NEW_MATRIX] == [("poisson", (256, 8, 9)), ("csr", "nb3"), ("av", "g2"),

@@ -140,46 +140,91 @@ def il_work_list(um, nw, tpp, P, want_il, il_w, min_pps):
     return per, seg
 
 
+def check_il_lists(name, c):
+    """One case of ec3d_il_umask + ec3d_il_work_list against the restatement and the properties walk_zm_il relies on.
+    Returns (nw, um), or None where the builder refused the list (as the restatement must)."""
+    tpp, P, want_il, il_w, min_pps, flags = c["in"]
+    assert (il_w, min_pps) == (160, 2)
+    ok, nw, um = il_umask(c["ulist"], tpp, P, c["tile_flag"] if flags else None)
+    assert c["ok"] == [int(ok), nw] and nw == -(-P // 32), name
+    if not ok:
+        assert set(c) == {"in", "ulist", "tile_flag", "ok"}, name
+        return None
+    assert c["um"] == um, name
+    # the accessor reads the bit of (column, plane) the list set
+    visited = {((t // tpp) - 3 * P, t % tpp) for t in c["ulist"]}
+    assert c["bits"] == [int((k, col) in visited) for col in range(tpp) for k in range(P)], name
+    per, seg = il_work_list(um, nw, tpp, P, want_il, il_w, min_pps)
+    assert c["per"] == [per] and c["seg"] == seg, name
+    # per * 8 rows of four; the rows of an XCD label that hold a segment come first, the fourth entry is unused
+    rows = [c["seg"][4 * b:4 * b + 4] for b in range(len(c["seg"]) // 4)]
+    assert len(c["seg"]) == per * 8 * 4 and per >= 1 and all(r[3] == 0 for r in rows), name
+    by_col = {}
+    for x in range(8):
+        mine = rows[x::8]
+        n = sum(1 for r in mine if r[2] > r[1])
+        assert all(r[2] > r[1] for r in mine[:n]) and all(r == [0, 0, 0, 0] for r in mine[n:]), (name, x)
+        for col, k0, k1, _ in mine[:n]:
+            assert col // ((tpp + 7) // 8) == x, (name, x)      # columns are dealt to the labels in runs
+            by_col.setdefault(col, []).append((k0, k1))
+    assert max(sum(1 for r in rows[x::8] if r[2] > r[1]) for x in range(8)) == per, name
+    # the segments of a column tile [0, P) without gap or overlap, each of at least min_pps planes
+    assert sorted(by_col) == list(range(tpp)), name
+    for col, segs in by_col.items():
+        segs.sort()
+        assert segs[0][0] == 0 and segs[-1][1] == P, (name, col)
+        assert all(a[1] == b[0] for a, b in zip(segs, segs[1:])), (name, col)
+        assert P < min_pps or all(k1 - k0 >= min_pps for k0, k1 in segs), (name, col, segs)
+    return nw, um
+
+
 def test_il_umask_and_work_list(cases):
     seen = set()
     for name, c in cases["il"].items():
-        tpp, P, want_il, il_w, min_pps, flags = c["in"]
-        assert (il_w, min_pps) == (160, 2)
-        ok, nw, um = il_umask(c["ulist"], tpp, P, c["tile_flag"] if flags else None)
-        assert c["ok"] == [int(ok), nw] and nw == -(-P // 32), name
-        if not ok:
-            assert set(c) == {"in", "ulist", "tile_flag", "ok"}, name
-            continue
-        seen.add((tpp, P, want_il, len(c["ulist"])))
-        assert c["um"] == um, name
-        # the accessor reads the bit of (column, plane) the list set
-        visited = {((t // tpp) - 3 * P, t % tpp) for t in c["ulist"]}
-        assert c["bits"] == [int((k, col) in visited) for col in range(tpp) for k in range(P)], name
-        per, seg = il_work_list(um, nw, tpp, P, want_il, il_w, min_pps)
-        assert c["per"] == [per] and c["seg"] == seg, name
-        # per * 8 rows of four; the rows of an XCD label that hold a segment come first, the fourth entry is unused
-        rows = [c["seg"][4 * b:4 * b + 4] for b in range(len(c["seg"]) // 4)]
-        assert len(c["seg"]) == per * 8 * 4 and per >= 1 and all(r[3] == 0 for r in rows), name
-        by_col = {}
-        for x in range(8):
-            mine = rows[x::8]
-            n = sum(1 for r in mine if r[2] > r[1])
-            assert all(r[2] > r[1] for r in mine[:n]) and all(r == [0, 0, 0, 0] for r in mine[n:]), (name, x)
-            for col, k0, k1, _ in mine[:n]:
-                assert col // ((tpp + 7) // 8) == x, (name, x)      # columns are dealt to the labels in runs
-                by_col.setdefault(col, []).append((k0, k1))
-        assert max(sum(1 for r in rows[x::8] if r[2] > r[1]) for x in range(8)) == per, name
-        # the segments of a column tile [0, P) without gap or overlap, each of at least min_pps planes
-        assert sorted(by_col) == list(range(tpp)), name
-        for col, segs in by_col.items():
-            segs.sort()
-            assert segs[0][0] == 0 and segs[-1][1] == P, (name, col)
-            assert all(a[1] == b[0] for a, b in zip(segs, segs[1:])), (name, col)
-            assert P < min_pps or all(k1 - k0 >= min_pps for k0, k1 in segs), (name, col, segs)
+        tpp, P, want_il = c["in"][:3]
+        if check_il_lists(name, c) is not None:
+            seen.add((tpp, P, want_il, len(c["ulist"])))
     sizes = {(tpp, P, w) for tpp in (1, 5, 8, 9) for P in (2, 3, 31, 32, 33, 65) for w in (8, 40, 512)}
     assert {s[:3] for s in seen} == sizes
     for tpp, P, w in sizes:                 # masks: none, all, one column, a checkerboard
         assert {s[3] for s in seen if s[:3] == (tpp, P, w)} >= {0, tpp * P, P, (tpp * P) // 2}
+
+
+def test_il_lists_of_grids_of_several_columns(cases):
+    """The masks of tests/av_grids.py -- the systems tests/test_gpu_interleaved_grids.py runs through walk_zm_il -- at the
+    workgroup request quoted for each: the program's list of U tiles is the one the voxels give, the lists are the
+    restatement's, and they hold the features the grids are there for, counted (av_grids.features).
+
+    S1_one_block is one block x[9,60) y[10,60) z[3,37) on S1's grid: seven conductor columns of weight 34 * 160 + 6 * 100 =
+    6040 and columns 0 and 8 of weight 4000 each, target 50280 / 16 = 3142.5: 7 * 2 + 2 * 1 = 16 segments, 16 of the 32
+    entries empty.  S1 itself (two domains, column 8 touched by the second) weighs 4000, 4660, 6 * 5800 and 5140, target
+    3037.5: 1 + 2 + 6 * 2 + 2 = 17 segments, 15 entries empty; cuts and crossings as for the one block."""
+    import av_grids as AGR
+    got = cases["ilgrid"]
+    assert set(got) == set(AGR.GRIDS) | {"S1_one_block"}
+    for name, c in got.items():
+        grid = "S1" if name == "S1_one_block" else name
+        tpp, P, want_il, _, _, flags = c["in"]
+        sdx, sdy, pitch = c["grid"]
+        assert (sdx, sdy, P) == AGR.GRIDS[grid]["dims"] and pitch == AGR.pitch_of(grid) == tpp * 512 and flags == 1
+        assert want_il == AGR.GRIDS[grid]["request"]
+        assert (pitch > sdx * sdy) == AGR.GRIDS[grid]["pitched"]
+        if name in AGR.GRIDS:
+            assert c["ulist"] == AGR.u_tiles(name), name
+        nw, um = check_il_lists(name, c)
+        f = AGR.features(c["seg"], um, nw, P)
+        print(name, f)
+        assert f == AGR.QUOTED[name], name
+        # some column holds no U tile at all exactly where the grid is meant to have one
+        bare = [col for col in range(tpp) if not any(c["bits"][col * P:(col + 1) * P])]
+        assert bool(bare) == (grid in ("S1", "S2")), name
+    # S1: U tiles that stop and start again along z (planes 14 .. 17 of columns 2 .. 7)
+    c = got["S1"]
+    P = c["in"][1]
+    for col in range(2, 8):
+        b = c["bits"][col * P:(col + 1) * P]
+        assert b[13] == 1 and b[14:18] == [0] * 4 and b[18] == 1, col
+    assert not any(c["bits"][:P])               # column 0
 
 
 def test_il_umask_refuses(cases):
