@@ -23,6 +23,7 @@
 // Built with -ffp-contract=off: products and sums are rounded separately, exactly as the
 // reference's x86-64 object code does; the oracle's "GPU order" twin reproduces every bit.
 #include "ec3d_form.hpp"
+#include "ec3d_recurrence.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -525,21 +526,13 @@ __device__ __forceinline__ void walk_spmv(const AD &A, const SW &sw, PatchPos &p
 
 // The vector a row kernel multiplies by, behind a small accessor (pair = two consecutive entries from
 // an 8-byte-aligned address, at = one gathered entry).
-// (rpair / rat + form: the same values in two halves -- the loads, and what is computed from them -- for a caller that
-// wants every request of a step out before the first one is waited for: a fused vector's pair() under `if` keeps its
-// arithmetic, and with it a wait for everything in flight, inside the branch)
+// (the fused vectors' rpair / rat + form: the same values in two halves -- the loads, and what is computed from them --
+// for a caller that wants every request of a step out before the first one is waited for: a fused vector's pair() under
+// `if` keeps its arithmetic, and with it a wait for everything in flight, inside the branch)
 struct VecPlain {
     const double *__restrict__ x;
-    struct Raw2 { d2 v; };
-    struct Raw1 { double v; };
     __device__ __forceinline__ d2 pair(int64_t i) const { return *reinterpret_cast<const d2u *>(x + i); }
     __device__ __forceinline__ double at(int64_t i) const { return x[i]; }
-    __device__ __forceinline__ Raw2 rpair(int64_t i) const { return Raw2{pair(i)}; }
-    __device__ __forceinline__ Raw1 rat(int64_t i) const { return Raw1{x[i]}; }
-    __device__ __forceinline__ d2 form(const Raw2 &w) const { return w.v; }
-    __device__ __forceinline__ double form(const Raw1 &w) const { return w.v; }
-    static __device__ __forceinline__ void to_carry(const Raw2 &w, d2 (&c)[3]) { c[0] = w.v; }
-    static __device__ __forceinline__ Raw2 from_carry(const d2 (&c)[3]) { return Raw2{c[0]}; }
 };
 // S = R - alpha*AP formed where it is read (K2 fused into K3, src/solvers.f90:33 inside :39): every value is the same
 // expression, rounded the same way, whichever thread forms it -- the owner that stores it or a neighbour that needs it
@@ -562,8 +555,8 @@ struct VecFused {
     __device__ __forceinline__ Raw1 rat(int64_t i) const { return Raw1{rv[i], ap[i]}; }
     __device__ __forceinline__ d2 form(const Raw2 &w) const { return d2{w.q.x - alpha * w.a.x, w.q.y - alpha * w.a.y}; }
     __device__ __forceinline__ double form(const Raw1 &w) const { return w.q - alpha * w.a; }
-    static __device__ __forceinline__ void to_carry(const Raw2 &w, d2 (&c)[3]) { c[0] = w.q; c[1] = w.a; }
-    static __device__ __forceinline__ Raw2 from_carry(const d2 (&c)[3]) { return Raw2{c[0], c[1]}; }
+    static __device__ __forceinline__ void to_carry(const Raw2 &w, d2 (&c)[2]) { c[0] = w.q; c[1] = w.a; }
+    static __device__ __forceinline__ Raw2 from_carry(const d2 (&c)[2]) { return Raw2{c[0], c[1]}; }
 };
 // P = R + beta*(P - omega*AP) formed where it is read (K5 fused into the next iteration's K1, src/solvers.f90:46 inside
 // :30), or P = R after a restart (:47-49); reads the PREVIOUS iteration's P and AP, which live in other buffers than
@@ -618,8 +611,6 @@ struct VecFusedP {
         if (restart) return w.q;
         return w.q + beta * (w.pv - omega * w.a);
     }
-    static __device__ __forceinline__ void to_carry(const Raw2 &w, d2 (&c)[3]) { c[0] = w.q; c[1] = w.pv; c[2] = w.a; }
-    static __device__ __forceinline__ Raw2 from_carry(const d2 (&c)[3]) { return Raw2{c[0], c[1], c[2]}; }
 };
 // Tail of one row: s += tval[e] * x[tcol[e]] over the row's slots of its 64-row slice, in stored order.
 // The loads are issued in batches (all values/columns of a batch, then all gathers, then the adds in
@@ -756,8 +747,8 @@ __device__ __forceinline__ void sav_a_post(const MatDev<FMT_SAV> &A, const doubl
 struct ZRegs {
     d2 xm, xc;
     d2 rim; // 2-D tiles: the outer neighbour row of the NEXT step's centre plane (first / last patch row only)
-    d2 cr[3]; // ... or its operands as requested at the end of a step, still on their way (patch_pair, request mode 4)
-    double edge; // 2-D tiles, request mode 5: the cell beside the patch row's end in the NEXT step's centre plane (edge lanes)
+    d2 cr[2]; // ... or its operands (R, AP) as requested at the end of a step, still on their way (patch_pair, PP_RIM_CARRIED)
+    double edge; // 2-D tiles, PP_RIM_EDGE_BEHIND: the cell beside the patch row's end in the NEXT step's centre plane (edge lanes)
     unsigned short cc; // 2-D tiles, dictionary form: the thread's class pair, carried while the tiles' classes repeat ...
     uint32_t same;     // ... which MatDev::same says of the NEXT step's tile: the dword that holds its byte (uniform; asked for a step ahead)
 };
@@ -1435,21 +1426,18 @@ __device__ __forceinline__ void sav_patch_step(const MatDev<FMT_SAV> &A, const S
 // for their outer neighbour.  Global loads per wave and step: 1 full + the rim (two of the four waves) + 2 lanes of edge,
 // where the linear tile issues 3 full + 2 lanes.  Same products in the same order: A*x is bit-identical; the dot
 // products are summed in this thread -> cell assignment, which ec3d_geom::patch_x tells the oracle's twin.
-// How patch_pair makes a step's requests, per operand vector (A/B switches of round 6; the defaults are what was measured
-// best at 512^3): 0 = every request of the step together, forms behind the LDS exchange; 1 = the rim row's requests behind
-// the barrier (the neighbouring patch's requests for the same lines are then out already); 2 = the round-5 step (edge
-// lanes and rim row each formed inside their branch, behind a wait for everything in flight); 3 = the rim row behind the
-// arrival of the plane above; 4 = the rim row at the END of the step, its operands carried into the next step unformed;
-// 5 = as 3, and the edge cells a plane ahead with the rim row (a step's first requests are the plane above and nothing else)
-#ifndef EC3D_PP_PLAIN
-#define EC3D_PP_PLAIN 2
-#endif
-#ifndef EC3D_PP_FUSED
-#define EC3D_PP_FUSED 4
-#endif
-#ifndef EC3D_PP_FUSEDP
-#define EC3D_PP_FUSEDP 5
-#endif
+// How patch_pair makes a step's requests, per operand vector (PatchReq below); each is what was measured best at 512^3:
+//   PP_BRANCHY          (VecPlain)   the round-5 step, patch_pair_branchy: edge lanes and rim row each loaded inside
+//                                    their branch -- a plain vector forms nothing, so no branch waits for anything
+//   PP_RIM_CARRIED      (VecFused)   every request of the step together and the forms behind the LDS exchange; the rim
+//                                    row is requested at the END of the step and its operands are carried into the
+//                                    next step unformed (ZRegs::cr)
+//   PP_RIM_EDGE_BEHIND  (VecFusedP)  the rim row and the edge cells of the NEXT step are requested behind the arrival of
+//                                    the plane above and formed at the end of the step (ZRegs::rim, ZRegs::edge): a
+//                                    step's first requests are the plane above and nothing else
+// Round 6 also measured the rim row with the step's first requests, behind the barrier, and behind the plane above
+// without the edge cells: all three lost (profiles/r06_patch_requests_512.log).
+enum PatchRequests { PP_BRANCHY, PP_RIM_CARRIED, PP_RIM_EDGE_BEHIND };
 // The class pair of a step of patch_pair (dictionary form).  The classes barely change along the march -- on the cube
 // only the two face planes differ from their neighbours, on voxel models the material interfaces -- so a tile whose 512
 // class bytes equal those of the tile below (MatDev::same, one byte per tile; ec3d_class_runs in ec3d_sweep_lists.hpp)
@@ -1477,21 +1465,70 @@ __device__ __forceinline__ unsigned short patch_classes(const MatDev<FMT> &A, in
     }
     return cc;
 }
-template <class V> struct PatchReq { static constexpr int mode = EC3D_PP_PLAIN; };
-template <> struct PatchReq<VecFused> { static constexpr int mode = EC3D_PP_FUSED; };
-template <> struct PatchReq<VecFusedP> { static constexpr int mode = EC3D_PP_FUSEDP; };
+template <class V> struct PatchReq { static constexpr PatchRequests mode = PP_BRANCHY; };
+template <> struct PatchReq<VecFused> { static constexpr PatchRequests mode = PP_RIM_CARRIED; };
+template <> struct PatchReq<VecFusedP> { static constexpr PatchRequests mode = PP_RIM_EDGE_BEHIND; };
+
+// Rows r, r+1 of the 7-point row sum (src/solvers.f90:59): the coefficients of band b (coef.r0(b) for row r, coef.r1(b) for
+// row r+1) times its operand pair xb.  Bands ascending, the first product assigned, the rest added.  Everything by value; a
+// coefficient is taken where it is multiplied (the dictionary's are LDS reads: all fourteen ahead of the sum cost registers).
+struct DiaCoef { // the two entries of each band, loaded with the step's first requests
+    const d2 *c;
+    __device__ __forceinline__ double r0(int b) const { return c[b].x; }
+    __device__ __forceinline__ double r1(int b) const { return c[b].y; }
+};
+struct DictCoef { // entry b of the two rows' classes
+    const double *t0, *t1;
+    __device__ __forceinline__ double r0(int b) const { return t0[b]; }
+    __device__ __forceinline__ double r1(int b) const { return t1[b]; }
+};
+template <class COEF>
+__device__ __forceinline__ d2 sum7(COEF coef, d2 x0, d2 x1, d2 x2, d2 x3, d2 x4, d2 x5, d2 x6)
+{
+    const d2 x[7] = {x0, x1, x2, x3, x4, x5, x6};
+    double s0 = coef.r0(0) * x[0].x;
+    double s1 = coef.r1(0) * x[0].y;
+#pragma unroll
+    for (int b = 1; b < 7; ++b) {
+        s0 = s0 + coef.r0(b) * x[b].x;
+        s1 = s1 + coef.r1(b) * x[b].y;
+    }
+    return d2{s0, s1};
+}
+
+// What both forms of a patch_pair step share, beside patch_classes: the row sums, from the DIA pairs `c` or the class pair
+// `cc` (left, right: x[r - 1], x[r + 2]).  (The thread's place in the patch -- t, y, q, the two buffers -- stays written out
+// in both: from a helper the kernels came out with 2 to 4 more vector registers, k_spmv with a wave per SIMD less.)
+#define EC3D_HX (EC3D_PX / 2) /* lanes per patch row */
+template <int FMT>
+__device__ __forceinline__ d2 patch_sums(const d2 *c, const double *tbl, unsigned short cc, d2 zm, d2 ym, double left, d2 cx,
+                                         double right, d2 yp, d2 zp)
+{
+    const d2 xl = d2{left, cx.x}, xr = d2{cx.y, right};
+    if constexpr (FMT == FMT_DIA7) return sum7(DiaCoef{c}, zm, ym, xl, cx, xr, yp, zp);
+    else return sum7(DictCoef{tbl + (cc & 0xFF) * 7, tbl + (cc >> 8) * 7}, zm, ym, xl, cx, xr, yp, zp);
+}
+// (Round 6 measured the plane above requested a step AHEAD in both forms of the step, as the interleaved march of the
+// structured form does: K2-in-K3 680 -> 818 us, K5-in-K1 1227 -> 1275 us at 512^3 -- behind the barrier of the LDS exchange the
+// four waves of a workgroup wait for the slowest one's request at the end of EVERY step; profiles/r06_patch_plane_ahead_512.log.)
+// The patch's first and last row take their outer neighbour from memory -- one plane AHEAD: the row asked for in a step is
+// the one beside the plane above, i.e. the lines the neighbouring patch is asking for at this very step as ITS plane above,
+// so the two requests meet in the L2.  Asked for a step later (beside the centre plane, as the stencil reads it) the lines
+// had to survive a whole step of every workgroup of the XCD: with the three operand vectors of K5-in-K1 they did not (PMC
+// 56.3 B/row against 49; 52.3 now).  The vectors' ghost zones cover the row beside the plane above the last one
+// (ec3d_prepare_vectors); it is never used.
+// The barrier of a step says that its buffer is complete (written at the end of the previous step, or just now).  It is a
+// raw barrier behind a wait for the LDS writes only: __syncthreads() also drains every global load in flight (vmcnt(0))
+// before the barrier, which would put the LDS exchange BEHIND the arrival of the plane above instead of beside it.
+#define EC3D_PATCH_BARRIER asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 template <int FMT, bool NTB, class V>
 __device__ __forceinline__ void patch_pair_branchy(const MatDev<FMT> &A, const double *tbl, double *pbuf, int step, const V &x,
-                                           int64_t r, int64_t tile, bool first, ZRegs &z, double &s0, double &s1,
-                                           d2 &ctr)
+                                                   int64_t r, int64_t tile, bool first, ZRegs &z, double &s0, double &s1,
+                                                   d2 &ctr)
 {
-    // (Round 6 measured the plane above requested a step AHEAD here, as the interleaved march of the structured form does:
-    // K2-in-K3 680 -> 818 us, K5-in-K1 1227 -> 1275 us at 512^3 -- behind the barrier of the LDS exchange the four waves of a
-    // workgroup wait for the slowest one's request at the end of EVERY step; profiles/r06_patch_plane_ahead_512.log.)
-    constexpr int HX = EC3D_PX / 2; // lanes per patch row
-    const int t = threadIdx.x, y = t / HX, q = t % HX;
-    const int64_t sdx = A.off[5], kdz = A.off[6];
+    const int t = threadIdx.x, y = t / EC3D_HX, q = t % EC3D_HX;
     double *cur = pbuf + (step & 1) * EC3D_TILE, *nxt = pbuf + ((step + 1) & 1) * EC3D_TILE;
+    const int64_t sdx = A.off[5], kdz = A.off[6];
     const unsigned short cc = patch_classes<FMT>(A, r, tile, first, z);
     d2 c[7];
     if constexpr (FMT == FMT_DIA7) {
@@ -1502,13 +1539,7 @@ __device__ __forceinline__ void patch_pair_branchy(const MatDev<FMT> &A, const d
     const d2 zp = x.pair(r + kdz);
     double left = 0.0, right = 0.0;
     if (q == 0) left = x.at(r - 1);
-    if (q == HX - 1) right = x.at(r + 2);
-    // The patch's first and last row take their outer neighbour from memory -- one plane AHEAD: the row asked for now
-    // is the one beside the plane above, i.e. the lines the neighbouring patch is asking for at this very step as ITS
-    // plane above, so the two requests meet in the L2.  Asked for a step later (beside the centre plane, as the stencil
-    // reads it) the lines had to survive a whole step of every workgroup of the XCD: with the three operand vectors of
-    // K5-in-K1 they did not (PMC 56.3 B/row against 49; 52.3 now).  The vectors' ghost zones cover the row beside the plane
-    // above the last one (ec3d_prepare_vectors); it is never used.
+    if (q == EC3D_HX - 1) right = x.at(r + 2);
     const bool rimrow = y == 0 || y == EC3D_PY - 1;
     const int64_t roff = y == 0 ? -sdx : sdx;
     d2 rimc = d2{0.0, 0.0};
@@ -1526,50 +1557,18 @@ __device__ __forceinline__ void patch_pair_branchy(const MatDev<FMT> &A, const d
         zm = z.xm;
         cx = z.xc;
     }
-    // this step's buffer is complete (written at the end of the previous step, or just now).  A raw barrier behind a
-    // wait for the LDS writes only: __syncthreads() also drains every global load in flight (vmcnt(0)) before the
-    // barrier, which would put the LDS exchange BEHIND the arrival of the plane above instead of beside it
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    if (y > 0) ym = *reinterpret_cast<const d2 *>(cur + 2 * (t - HX));
-    if (y < EC3D_PY - 1) yp = *reinterpret_cast<const d2 *>(cur + 2 * (t + HX));
+    EC3D_PATCH_BARRIER;
+    if (y > 0) ym = *reinterpret_cast<const d2 *>(cur + 2 * (t - EC3D_HX));
+    if (y < EC3D_PY - 1) yp = *reinterpret_cast<const d2 *>(cur + 2 * (t + EC3D_HX));
     ctr = cx;
     {
         const double l = __shfl_up(cx.y, 1, 64), rr = __shfl_down(cx.x, 1, 64);
         if (q != 0) left = l;
-        if (q != HX - 1) right = rr;
+        if (q != EC3D_HX - 1) right = rr;
     }
-    if constexpr (FMT == FMT_DIA7) {
-        s0 = c[0].x * zm.x;
-        s1 = c[0].y * zm.y;
-        s0 = s0 + c[1].x * ym.x;
-        s1 = s1 + c[1].y * ym.y;
-        s0 = s0 + c[2].x * left;
-        s1 = s1 + c[2].y * cx.x;
-        s0 = s0 + c[3].x * cx.x;
-        s1 = s1 + c[3].y * cx.y;
-        s0 = s0 + c[4].x * cx.y;
-        s1 = s1 + c[4].y * right;
-        s0 = s0 + c[5].x * yp.x;
-        s1 = s1 + c[5].y * yp.y;
-        s0 = s0 + c[6].x * zp.x;
-        s1 = s1 + c[6].y * zp.y;
-    } else {
-        const double *t0 = tbl + (cc & 0xFF) * 7, *t1 = tbl + (cc >> 8) * 7;
-        s0 = t0[0] * zm.x;
-        s1 = t1[0] * zm.y;
-        s0 = s0 + t0[1] * ym.x;
-        s1 = s1 + t1[1] * ym.y;
-        s0 = s0 + t0[2] * left;
-        s1 = s1 + t1[2] * cx.x;
-        s0 = s0 + t0[3] * cx.x;
-        s1 = s1 + t1[3] * cx.y;
-        s0 = s0 + t0[4] * cx.y;
-        s1 = s1 + t1[4] * right;
-        s0 = s0 + t0[5] * yp.x;
-        s1 = s1 + t1[5] * yp.y;
-        s0 = s0 + t0[6] * zp.x;
-        s1 = s1 + t1[6] * zp.y;
-    }
+    const d2 s = patch_sums<FMT>(c, tbl, cc, zm, ym, left, cx, right, yp, zp);
+    s0 = s.x;
+    s1 = s.y;
     // the plane above is the next step's centre: into the other buffer (nobody reads that one before the next barrier)
     *reinterpret_cast<d2 *>(nxt + 2 * t) = zp;
     z.xm = cx;
@@ -1577,22 +1576,14 @@ __device__ __forceinline__ void patch_pair_branchy(const MatDev<FMT> &A, const d
 }
 
 template <int FMT, bool NTB, class V>
-__device__ __forceinline__ void patch_pair(const MatDev<FMT> &A, const double *tbl, double *pbuf, int step, const V &x,
-                                           int64_t r, int64_t tile, bool first, ZRegs &z, double &s0, double &s1,
-                                           d2 &ctr)
+__device__ __forceinline__ void patch_pair_fused(const MatDev<FMT> &A, const double *tbl, double *pbuf, int step, const V &x,
+                                                 int64_t r, int64_t tile, bool first, ZRegs &z, double &s0, double &s1,
+                                                 d2 &ctr)
 {
-    // (Round 6 measured the plane above requested a step AHEAD here, as the interleaved march of the structured form does:
-    // K2-in-K3 680 -> 818 us, K5-in-K1 1227 -> 1275 us at 512^3 -- behind the barrier of the LDS exchange the four waves of a
-    // workgroup wait for the slowest one's request at the end of EVERY step; profiles/r06_patch_plane_ahead_512.log.)
-    constexpr int RQ = PatchReq<V>::mode;
-    if constexpr (RQ == 2) {
-        patch_pair_branchy<FMT, NTB>(A, tbl, pbuf, step, x, r, tile, first, z, s0, s1, ctr);
-        return;
-    }
-    constexpr int HX = EC3D_PX / 2; // lanes per patch row
-    const int t = threadIdx.x, y = t / HX, q = t % HX;
-    const int64_t sdx = A.off[5], kdz = A.off[6];
+    constexpr PatchRequests RQ = PatchReq<V>::mode;
+    const int t = threadIdx.x, y = t / EC3D_HX, q = t % EC3D_HX;
     double *cur = pbuf + (step & 1) * EC3D_TILE, *nxt = pbuf + ((step + 1) & 1) * EC3D_TILE;
+    const int64_t sdx = A.off[5], kdz = A.off[6];
     const unsigned short cc = patch_classes<FMT>(A, r, tile, first, z);
     d2 c[7];
     if constexpr (FMT == FMT_DIA7) {
@@ -1603,26 +1594,17 @@ __device__ __forceinline__ void patch_pair(const MatDev<FMT> &A, const double *t
     // (S = R - alpha*AP, P = R + beta*(P - omega*AP)) an x.at() / x.pair() under `if` kept its arithmetic inside the branch,
     // and the branch then began with a wait for EVERYTHING in flight -- the plane above included: the edge lanes (every
     // wave has them), then the rim row, each cost the wave a memory round trip of its own before the barrier.  Now: the
-    // raw operands of plane above, edge cell (ONE predicated request for both edge lanes, as sav_band_loads) and rim
-    // row go out together, the LDS exchange runs beside them, and the forms follow behind it, by every lane (a lane
-    // that requested nothing forms zeros).  Same expressions on the same operands: the same bits.
+    // raw operands of plane above, edge cell (ONE predicated request for both edge lanes, as sav_band_loads) and -- in a
+    // segment's first step -- rim row go out together, the LDS exchange runs beside them, and the forms follow behind it,
+    // by every lane (a lane that requested nothing forms zeros).  Same expressions on the same operands: the same bits.
     const typename V::Raw2 zp_r = x.rpair(r + kdz);
-    const bool edge = q == 0 || q == HX - 1;
+    const bool edge = q == 0 || q == EC3D_HX - 1;
     typename V::Raw1 e_r{};
-    if (edge && (RQ != 5 || first)) e_r = x.rat(q == 0 ? r - 1 : r + 2);
-    // The patch's first and last row take their outer neighbour from memory -- one plane AHEAD: the row asked for now
-    // is the one beside the plane above, i.e. the lines the neighbouring patch is asking for at this very step as ITS
-    // plane above, so the two requests meet in the L2.  Asked for a step later (beside the centre plane, as the stencil
-    // reads it) the lines had to survive a whole step of every workgroup of the XCD: with the three operand vectors of
-    // K5-in-K1 they did not (PMC 56.3 B/row against 49; 52.3 now).  The vectors' ghost zones cover the row beside the plane
-    // above the last one (ec3d_prepare_vectors); it is never used.
+    if (edge && (RQ != PP_RIM_EDGE_BEHIND || first)) e_r = x.rat(q == 0 ? r - 1 : r + 2);
     const bool rimrow = y == 0 || y == EC3D_PY - 1;
     const int64_t roff = y == 0 ? -sdx : sdx;
     typename V::Raw2 rimc_r{}, rimn_r{};
-    if (rimrow) {
-        if (first) rimc_r = x.rpair(r + roff);
-        if (RQ == 0 || (RQ == 1 && first)) rimn_r = x.rpair(r + kdz + roff);
-    }
+    if (rimrow && first) rimc_r = x.rpair(r + roff);
     d2 zm, cx;
     if (first) { // nothing carried over: plane below and centre from memory, centre into this step's buffer
         const typename V::Raw2 zm_r = x.rpair(r - kdz), cx_r = x.rpair(r);
@@ -1633,79 +1615,50 @@ __device__ __forceinline__ void patch_pair(const MatDev<FMT> &A, const double *t
         zm = z.xm;
         cx = z.xc;
     }
-    // this step's buffer is complete (written at the end of the previous step, or just now).  A raw barrier behind a
-    // wait for the LDS writes only: __syncthreads() also drains every global load in flight (vmcnt(0)) before the
-    // barrier, which would put the LDS exchange BEHIND the arrival of the plane above instead of beside it
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    if constexpr (RQ == 1) {
-        if (rimrow && !first) rimn_r = x.rpair(r + kdz + roff);
-    }
+    EC3D_PATCH_BARRIER;
     d2 rimc;
-    if constexpr (RQ == 4) rimc = first ? x.form(rimc_r) : x.form(V::from_carry(z.cr));
+    if constexpr (RQ == PP_RIM_CARRIED) rimc = first ? x.form(rimc_r) : x.form(V::from_carry(z.cr));
     else rimc = first ? x.form(rimc_r) : z.rim;
     d2 ym = rimc, yp = rimc;
-    if (y > 0) ym = *reinterpret_cast<const d2 *>(cur + 2 * (t - HX));
-    if (y < EC3D_PY - 1) yp = *reinterpret_cast<const d2 *>(cur + 2 * (t + HX));
+    if (y > 0) ym = *reinterpret_cast<const d2 *>(cur + 2 * (t - EC3D_HX));
+    if (y < EC3D_PY - 1) yp = *reinterpret_cast<const d2 *>(cur + 2 * (t + EC3D_HX));
     ctr = cx;
     double left, right;
     {
         double ev = x.form(e_r);
-        if constexpr (RQ == 5) ev = first ? ev : z.edge;
+        if constexpr (RQ == PP_RIM_EDGE_BEHIND) ev = first ? ev : z.edge;
         const double l = __shfl_up(cx.y, 1, 64), rr = __shfl_down(cx.x, 1, 64);
         left = q != 0 ? l : ev;
-        right = q != HX - 1 ? rr : ev;
+        right = q != EC3D_HX - 1 ? rr : ev;
     }
     const d2 zp = x.form(zp_r);
     typename V::Raw1 en_r{};
-    if constexpr (RQ == 3 || RQ == 5) { // the rim row behind the arrival of the plane above: one more round trip, beside the sums
+    if constexpr (RQ == PP_RIM_EDGE_BEHIND) { // behind the arrival of the plane above: one more round trip, beside the sums
         if (rimrow) rimn_r = x.rpair(r + kdz + roff);
-        if constexpr (RQ == 5) { // ... and the edge cells of the plane above, for the next step
-            if (edge) en_r = x.rat(q == 0 ? r + kdz - 1 : r + kdz + 2);
-        }
+        if (edge) en_r = x.rat(q == 0 ? r + kdz - 1 : r + kdz + 2); // the edge cells of the plane above, for the next step
     }
-    if constexpr (FMT == FMT_DIA7) {
-        s0 = c[0].x * zm.x;
-        s1 = c[0].y * zm.y;
-        s0 = s0 + c[1].x * ym.x;
-        s1 = s1 + c[1].y * ym.y;
-        s0 = s0 + c[2].x * left;
-        s1 = s1 + c[2].y * cx.x;
-        s0 = s0 + c[3].x * cx.x;
-        s1 = s1 + c[3].y * cx.y;
-        s0 = s0 + c[4].x * cx.y;
-        s1 = s1 + c[4].y * right;
-        s0 = s0 + c[5].x * yp.x;
-        s1 = s1 + c[5].y * yp.y;
-        s0 = s0 + c[6].x * zp.x;
-        s1 = s1 + c[6].y * zp.y;
-    } else {
-        const double *t0 = tbl + (cc & 0xFF) * 7, *t1 = tbl + (cc >> 8) * 7;
-        s0 = t0[0] * zm.x;
-        s1 = t1[0] * zm.y;
-        s0 = s0 + t0[1] * ym.x;
-        s1 = s1 + t1[1] * ym.y;
-        s0 = s0 + t0[2] * left;
-        s1 = s1 + t1[2] * cx.x;
-        s0 = s0 + t0[3] * cx.x;
-        s1 = s1 + t1[3] * cx.y;
-        s0 = s0 + t0[4] * cx.y;
-        s1 = s1 + t1[4] * right;
-        s0 = s0 + t0[5] * yp.x;
-        s1 = s1 + t1[5] * yp.y;
-        s0 = s0 + t0[6] * zp.x;
-        s1 = s1 + t1[6] * zp.y;
-    }
+    const d2 s = patch_sums<FMT>(c, tbl, cc, zm, ym, left, cx, right, yp, zp);
+    s0 = s.x;
+    s1 = s.y;
     // the plane above is the next step's centre: into the other buffer (nobody reads that one before the next barrier)
     *reinterpret_cast<d2 *>(nxt + 2 * t) = zp;
     z.xm = cx;
     z.xc = zp;
-    if constexpr (RQ == 4) { // the rim row requested now, waited for behind the next step's barrier
+    if constexpr (RQ == PP_RIM_CARRIED) { // the rim row requested now, waited for behind the next step's barrier
         if (rimrow) rimn_r = x.rpair(r + kdz + roff);
         V::to_carry(rimn_r, z.cr);
     } else {
         z.rim = x.form(rimn_r);
-        if constexpr (RQ == 5) z.edge = x.form(en_r);
+        z.edge = x.form(en_r);
     }
+}
+template <int FMT, bool NTB, class V>
+__device__ __forceinline__ void patch_pair(const MatDev<FMT> &A, const double *tbl, double *pbuf, int step, const V &x,
+                                           int64_t r, int64_t tile, bool first, ZRegs &z, double &s0, double &s1,
+                                           d2 &ctr)
+{
+    if constexpr (PatchReq<V>::mode == PP_BRANCHY) patch_pair_branchy<FMT, NTB>(A, tbl, pbuf, step, x, r, tile, first, z, s0, s1, ctr);
+    else patch_pair_fused<FMT, NTB>(A, tbl, pbuf, step, x, r, tile, first, z, s0, s1, ctr);
 }
 
 // rows r, r+1 of A*x (src/solvers.f90:58-59): bands in ascending column order, then the tail.
@@ -1771,22 +1724,13 @@ __device__ __forceinline__ void spmv_pair(const MatDev<FMT> &A, const SW &sw, co
             d2 c[7];
 #pragma unroll
             for (int b = 0; b < 7; ++b) c[b] = load2<NTB>(A.band[b] + r); // coefficients: touched once per launch
-            s0 = c[0].x * xv[0].x;
-            s1 = c[0].y * xv[0].y;
-#pragma unroll
-            for (int b = 1; b < 7; ++b) {
-                s0 = s0 + c[b].x * xv[b].x;
-                s1 = s1 + c[b].y * xv[b].y;
-            }
+            const d2 s = sum7(DiaCoef{c}, xv[0], xv[1], xv[2], xv[3], xv[4], xv[5], xv[6]);
+            s0 = s.x;
+            s1 = s.y;
         } else if constexpr (FMT == FMT_DICT7) {
-            const double *t0 = tbl + (cc & 0xFF) * 7, *t1 = tbl + (cc >> 8) * 7;
-            s0 = t0[0] * xv[0].x;
-            s1 = t1[0] * xv[0].y;
-#pragma unroll
-            for (int b = 1; b < 7; ++b) {
-                s0 = s0 + t0[b] * xv[b].x;
-                s1 = s1 + t1[b] * xv[b].y;
-            }
+            const d2 s = sum7(DictCoef{tbl + (cc & 0xFF) * 7, tbl + (cc >> 8) * 7}, xv[0], xv[1], xv[2], xv[3], xv[4], xv[5], xv[6]);
+            s0 = s.x;
+            s1 = s.y;
         } else { // FMT_SAV without tile-aligned planes: U rows take their A couplings first, A rows their U couplings last
             const int c0 = cc & 0xFF, c1 = cc >> 8;
             const double *t0 = tbl + c0 * EC3D_SAV_STRIDE, *t1 = tbl + c1 * EC3D_SAV_STRIDE;
@@ -2085,7 +2029,7 @@ __global__ __launch_bounds__(EC3D_THREADS) void k2_s_update(SweepV sw, RedSrc sr
     if (stop_it < it) return;
     double d[1];
     partials_finish<1>(src, slot, pe, d, lds);
-    const double alpha = rr0 / d[0];
+    const double alpha = ec3d_alpha(rr0, d[0]);
     if (blockIdx.x == 0 && threadIdx.x == 0) st->alpha = alpha;
     double acc[1] = {0.0};
     struct Ops { d2 a, q; };
@@ -2182,7 +2126,7 @@ __global__ __launch_bounds__(EC3D_THREADS) __attribute__((amdgpu_waves_per_eu(4)
     if (stop_it < it) return;
     double d[1];
     partials_finish<1>(src, slot, pe, d, lds);
-    const double alpha = rr0 / d[0];
+    const double alpha = ec3d_alpha(rr0, d[0]);
     if (blockIdx.x == 0 && threadIdx.x == 0) st->alpha = alpha;
     table_store<FMT>(A, te, tbl);
     ZRegs zr;
@@ -2253,20 +2197,20 @@ __global__ __launch_bounds__(EC3D_THREADS) __attribute__((amdgpu_waves_per_eu(4)
     }
     double d[2];
     partials_finish<2>(src, slot, pe, d, lds);
-    const double rnorm = sqrt(d[0]);
+    const Ec3dNorm rn = ec3d_rnorm_step(d[0], bnorm, tol);
     // (the second launch of a split K5-in-K1 -- z-slab, interior planes behind the boundary planes -- leaves the state
     // alone: the first one has written it, and the restart counter must count once)
     const bool lead = blockIdx.x == 0 && threadIdx.x == 0 && sw.part_off == 0;
-    if (lead && hist && it <= hist_cap) hist[2 * (int64_t)(it - 1) + 1] = rnorm;
-    if (lead) st->rnorm = rnorm;
-    if (rnorm / bnorm < tol) {
+    if (lead && hist && it <= hist_cap) hist[2 * (int64_t)(it - 1) + 1] = rn.norm;
+    if (lead) st->rnorm = rn.norm;
+    if (rn.exit) {
         if (lead) stop_publish(st, it, 2);
         return;
     }
-    const double rr0_new = d[1];
-    const double beta = (alpha / omega) * rr0_new / rr0;
-    const bool restart = fabs(rr0_new) / bnorm < tol;
-    if (lead) st->rr0[(it + 1) & 1] = restart ? d[0] : rr0_new;
+    const Ec3dBeta bs = ec3d_beta_step(alpha, omega, d[1], rr0, d[0], bnorm, tol);
+    const double beta = bs.beta;
+    const bool restart = bs.restart;
+    if (lead) st->rr0[(it + 1) & 1] = bs.rr0_next;
     if (lead && restart) st->restarts = st->restarts + 1;
     table_store<FMT>(A, te, tbl);
     ZRegs zr;
@@ -2337,10 +2281,10 @@ __global__ __launch_bounds__(EC3D_THREADS) void k4_x_r_update(SweepV sw, RedSrc 
     if (stop_it < it) return; // (this kernel is the one that may publish the exit (it, 1))
     double ss[1];
     partials_finish<1>(src_ss, slot_ss, pss, ss, lds);
-    const double snorm = sqrt(ss[0]);
+    const Ec3dNorm sn = ec3d_snorm_step(ss[0], bnorm, tol);
     const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
-    if (lead && hist && it <= hist_cap) hist[2 * (int64_t)(it - 1)] = snorm;
-    if (snorm / bnorm < tol) {
+    if (lead && hist && it <= hist_cap) hist[2 * (int64_t)(it - 1)] = sn.norm;
+    if (sn.exit) {
         struct OpsX { d2 xv, pv; };
         walk_vec(sw, [&](int64_t tile) {
             EC3D_ROW;
@@ -2357,7 +2301,7 @@ __global__ __launch_bounds__(EC3D_THREADS) void k4_x_r_update(SweepV sw, RedSrc 
     }
     double d[2];
     partials_finish<2>(src, slot, pd, d, lds);
-    const double omega = d[0] / d[1];
+    const double omega = ec3d_omega(d[0], d[1]);
     if (lead) st->omega = omega;
     double acc[2] = {0.0, 0.0};
     struct Ops { d2 xv, pv, s, a, q; };
@@ -2423,10 +2367,10 @@ __global__ __launch_bounds__(EC3D_THREADS) void k4d_x_r_update(SweepV sw, RedSrc
     if (stop_it < it) return;
     double ss[1];
     partials_finish<1>(src_ss, slot_ss, pss, ss, lds);
-    const double snorm = sqrt(ss[0]);
+    const Ec3dNorm sn = ec3d_snorm_step(ss[0], bnorm, tol);
     const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
-    if (lead && hist && it <= hist_cap) hist[2 * (int64_t)(it - 1)] = snorm;
-    if (snorm / bnorm < tol) { // src/solvers.f90:34-38: X = X + alpha*P joins the pending updates as a half one
+    if (lead && hist && it <= hist_cap) hist[2 * (int64_t)(it - 1)] = sn.norm;
+    if (sn.exit) { // src/solvers.f90:34-38: X = X + alpha*P joins the pending updates as a half one
         if (lead) {
             st->pend_alpha[xm] = alpha;
             st->pend_omega[xm] = 0.0;
@@ -2438,7 +2382,7 @@ __global__ __launch_bounds__(EC3D_THREADS) void k4d_x_r_update(SweepV sw, RedSrc
     }
     double d[2];
     partials_finish<2>(src, slot, pd, d, lds);
-    const double omega = d[0] / d[1];
+    const double omega = ec3d_omega(d[0], d[1]);
     if (lead) {
         st->omega = omega;
         if (NE == 0) {
@@ -2527,10 +2471,10 @@ __global__ __launch_bounds__(EC3D_THREADS) __attribute__((amdgpu_waves_per_eu(NE
     if (stop_it < it) return;
     double ss[1];
     partials_finish<1>(src_ss, slot_ss, pss, ss, lds);
-    const double snorm = sqrt(ss[0]);
+    const Ec3dNorm sn = ec3d_snorm_step(ss[0], bnorm, tol);
     const bool lead = blockIdx.x == 0 && threadIdx.x == 0 && sw.part_off == 0; // (split launch: the first one writes the state)
-    if (lead && hist && it <= hist_cap) hist[2 * (int64_t)(it - 1)] = snorm;
-    if (snorm / bnorm < tol) {
+    if (lead && hist && it <= hist_cap) hist[2 * (int64_t)(it - 1)] = sn.norm;
+    if (sn.exit) {
         if (lead) {
             st->pend_alpha[xm] = alpha;
             st->pend_omega[xm] = 0.0;
@@ -2542,7 +2486,7 @@ __global__ __launch_bounds__(EC3D_THREADS) __attribute__((amdgpu_waves_per_eu(NE
     }
     double d[2];
     partials_finish<2>(src, slot, pd, d, lds);
-    const double omega = d[0] / d[1];
+    const double omega = ec3d_omega(d[0], d[1]);
     if (lead) {
         st->omega = omega;
         if (NEMAX == 0) {
@@ -2679,19 +2623,19 @@ __global__ __launch_bounds__(EC3D_THREADS) void k5_p_update(SweepV sw, RedSrc sr
     }
     double d[2];
     partials_finish<2>(src, slot, pe, d, lds);
-    const double rnorm = sqrt(d[0]);
+    const Ec3dNorm rn = ec3d_rnorm_step(d[0], bnorm, tol);
     const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
-    if (lead && hist && it <= hist_cap) hist[2 * (int64_t)(it - 1) + 1] = rnorm;
-    if (lead) st->rnorm = rnorm;
-    if (rnorm / bnorm < tol) {
+    if (lead && hist && it <= hist_cap) hist[2 * (int64_t)(it - 1) + 1] = rn.norm;
+    if (lead) st->rnorm = rn.norm;
+    if (rn.exit) {
         if (lead) stop_publish(st, it, 2);
         return;
     }
-    const double rr0_new = d[1];
-    const double beta = (alpha / omega) * rr0_new / rr0;
-    const bool restart = fabs(rr0_new) / bnorm < tol;
+    const Ec3dBeta bs = ec3d_beta_step(alpha, omega, d[1], rr0, d[0], bnorm, tol);
+    const double beta = bs.beta;
+    const bool restart = bs.restart;
     // next iteration's R·R0: after a restart R0 == R, so it is R·R in the same summation order
-    if (lead) st->rr0[(it + 1) & 1] = restart ? d[0] : rr0_new;
+    if (lead) st->rr0[(it + 1) & 1] = bs.rr0_next;
     if (lead && restart && sw.part_off == 0) st->restarts = st->restarts + 1; // (a split K5 -- boundary + interior launch -- counts once)
     if (restart) {
         walk_vec(sw, [&](int64_t tile) {

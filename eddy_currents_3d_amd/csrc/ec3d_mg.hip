@@ -47,6 +47,7 @@
 #include "ec3d_avmg_plan.hpp"
 #include "ec3d_mg_plan.hpp"
 #include "ec3d_internal.hpp"
+#include "ec3d_recurrence.hpp"
 
 #include <array>
 #include <climits>
@@ -648,27 +649,28 @@ __global__ __launch_bounds__(256) void k_mg_scalar(int stage, Gate g, SolverStat
     const int it = g.it;
     const int64_t h = (int64_t)(it - 1) * 2;
     switch (stage) {
-    case MG_ALPHA: st->alpha = st->rr0[it & 1] / v[0]; break; // (:31-32)
+    // the rules themselves: ec3d_recurrence.hpp
+    case MG_ALPHA: st->alpha = ec3d_alpha(st->rr0[it & 1], v[0]); break; // (:31-32)
     case MG_SEXIT: {
-        const double sn = sqrt(v[0]);
-        if (it - 1 < hist_cap) hist[h] = sn;
-        if (sn / st->bnorm < st->tol) mg_stop_publish(st, it, 1); // (:34-38)
+        const Ec3dNorm s = ec3d_snorm_step(v[0], st->bnorm, st->tol);
+        if (it - 1 < hist_cap) hist[h] = s.norm;
+        if (s.exit) mg_stop_publish(st, it, 1); // (:34-38)
         break;
     }
-    case MG_OMEGA: st->omega = v[0] / v[1]; break; // (:40)
+    case MG_OMEGA: st->omega = ec3d_omega(v[0], v[1]); break; // (:40)
     case MG_REXIT: {
-        const double rn = sqrt(v[0]), rr0_new = v[1];
-        if (it - 1 < hist_cap) hist[h + 1] = rn;
-        st->rnorm = rn;
-        if (rn / st->bnorm < st->tol) { // (:43)
+        const Ec3dNorm rn = ec3d_rnorm_step(v[0], st->bnorm, st->tol);
+        if (it - 1 < hist_cap) hist[h + 1] = rn.norm;
+        st->rnorm = rn.norm;
+        if (rn.exit) { // (:43)
             mg_stop_publish(st, it, 2);
             break;
         }
-        ms->beta = (st->alpha / st->omega) * rr0_new / st->rr0[it & 1]; // (:45)
-        const bool restart = fabs(rr0_new) / st->bnorm < st->tol;   // (:47-49)
-        ms->restart = restart;
-        if (restart) st->restarts = st->restarts + 1;
-        st->rr0[(it + 1) & 1] = restart ? v[0] : rr0_new; // R0 = R: the next rr0 is R.R
+        const Ec3dBeta b = ec3d_beta_step(st->alpha, st->omega, v[1], st->rr0[it & 1], v[0], st->bnorm, st->tol); // (:45-49)
+        ms->beta = b.beta;
+        ms->restart = b.restart;
+        if (b.restart) st->restarts = st->restarts + 1;
+        st->rr0[(it + 1) & 1] = b.rr0_next;
         break;
     }
     }
