@@ -27,9 +27,16 @@
 // launch), the eight sums of every rank are all-gathered (64 B per rank) on the compute stream and added in rank order by
 // the consumer kernels, exactly like the gathered copy of eddy_currents_3d_amd/dist.py.  The whole iteration loop is
 // enqueued from C++: no Python between two launches.
+//
+// What needs no device is NOT here but in ec3d_slab_plan.hpp, where tests/test_slab_plan_host.py reaches it on the CPU: the
+// op tables of the plans and the stage launched for each entry, the slabs' bounds, the halo runs and how neighbours' runs
+// pair up, the refusals of a job whose ranks disagree, the environment knobs, and the job's decision (decide_job,
+// decide_slab).  This file keeps the threads, streams, events, RCCL calls, the watchdog, uploads and downloads, the solve
+// loop and the C entry points; finish_setup applies the decision to the handles.
 #include "../../include/ec3d_hip.h"
 #include "ec3d_internal.hpp"
 #include "ec3d_rccl.hpp"
+#include "ec3d_slab_plan.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -45,70 +52,11 @@
 #include <mutex>
 #include <thread>
 
+using namespace ec3d_slab;
+static_assert(kXdMax == EC3D_XD_MAX, "decide_job starts from the deepest deferral a handle can allocate rings for");
+
 namespace {
 constexpr int RING = 4;
-enum { CH_P = 0, CH_S = 1, CH_X = 2, CH_AP = 3, CH_R = 4, NHALO = 5, CH_SUM = 5, CH_HUB = 6, NCH = 7 };
-const int kVecOf[NHALO] = {EC3D_VEC_P, EC3D_VEC_S, EC3D_VEC_X, EC3D_VEC_AP, EC3D_VEC_R};
-
-// a run of halo planes inside one work vector: `planes` pieces of `payload` doubles, `pitch` apart
-struct Run {
-    int64_t start = 0, pitch = 0, payload = 0;
-    int planes = 0;
-    int64_t lo() const { return start; }
-    int64_t hi() const { return start + (int64_t)(planes - 1) * pitch + std::max(payload, planes > 1 ? pitch : payload); }
-};
-struct Copy {
-    int64_t dst, src, cnt;
-};
-struct Piece {
-    int64_t off, cnt;
-};
-
-enum { OP_HALO = 0, OP_HALO_START, OP_HALO_WAIT, OP_GATHER, OP_STEP, OP_SKIP_IF_AP };
-struct Op {
-    int kind, arg;
-    int dit = 0; // halo ops: the exchanged vector is that of iteration it + dit (P after K5 is the NEXT iteration's)
-};
-#define ST(x) Op{OP_STEP, EC3D_STAGE_##x}
-const std::vector<Op> kBegin = {{OP_HALO, CH_X}, ST(RESID), {OP_GATHER, 0}, ST(SETUP)};
-// (run with it = 0: the first iteration's P)
-const std::vector<Op> kBeginVsplit = {{OP_HALO, CH_X}, ST(RESID), {OP_GATHER, 0}, ST(SETUP), {OP_HALO, CH_P, 1}};
-// three reduction points per iteration (K3 is launched before ||S|| is known)
-const std::vector<Op> kIter = {{OP_HALO, CH_P}, ST(K1), {OP_GATHER, 0}, ST(K2), {OP_HALO, CH_S},
-                               ST(K3), {OP_GATHER, 0}, ST(K4), {OP_GATHER, 0}, ST(K5)};
-// exchange hidden behind the interior planes of K1/K3 (single-component slabs on a z-marching grid)
-const std::vector<Op> kIterOverlap = {{OP_HALO_START, CH_P}, ST(K1_INT), {OP_HALO_WAIT, CH_P}, ST(K1_BND), {OP_GATHER, 0},
-                                      ST(K2), {OP_HALO_START, CH_S}, ST(K3_INT), {OP_HALO_WAIT, CH_S}, ST(K3_BND),
-                                      {OP_GATHER, 0}, ST(K4), {OP_GATHER, 0}, ST(K5)};
-// the same from the producers' side (A-V slabs, any storage): K2/K5 boundary tiles first
-const std::vector<Op> kIterVsplit = {{OP_HALO_WAIT, CH_P}, ST(K1), {OP_GATHER, 0}, ST(K2_BND), {OP_HALO_START, CH_S},
-                                     ST(K2_INT), {OP_HALO_WAIT, CH_S}, ST(K3), {OP_GATHER, 0}, ST(K4), {OP_GATHER, 0},
-                                     ST(K5_BND), {OP_HALO_START, CH_P, 1}, ST(K5_INT)};
-// both at once (plan 5, single-component slabs): the producers K2 / K5 run the boundary planes first and start the
-// exchange, the consumers K1 / K3 run their interior planes before they wait for it -- the planes have the producer's
-// interior launch AND the consumer's to arrive behind, instead of one of the two.  Same exchanges in the same order as
-// kIterVsplit (the first P travels from the begin plan on).
-const std::vector<Op> kBeginBoth = {{OP_HALO, CH_X}, ST(RESID), {OP_GATHER, 0}, ST(SETUP), {OP_HALO_START, CH_P, 1}};
-const std::vector<Op> kIterBoth = {ST(K1_INT), {OP_HALO_WAIT, CH_P}, ST(K1_BND), {OP_GATHER, 0}, ST(K2_BND),
-                                   {OP_HALO_START, CH_S}, ST(K2_INT), ST(K3_INT), {OP_HALO_WAIT, CH_S}, ST(K3_BND),
-                                   {OP_GATHER, 0}, ST(K4), {OP_GATHER, 0}, ST(K5_BND), {OP_HALO_START, CH_P, 1}, ST(K5_INT)};
-// The three-launch iteration on slabs of the single-component operator (every rank >= 32 Mi rows; ec3d_ctx::slab_fused):
-// K2 inside K3, K4 as an SpMV kernel, K5 inside the next iteration's K1.  S and P are formed on the halo planes by the
-// kernels that read them there (and stored into the ghost rows: Sweep::halo_store), so what travels is AP -- after
-// K5-in-K1, for the S = R - alpha*AP of K2-in-K3 and the next P on the halo planes -- and R -- after K4 --: two exchanges
-// and three reduction points per iteration, as before.  P and R are exchanged once before the first iteration; the lone K1
-// (with its reduction point and the exchange of its AP) runs when AP = A P of the iteration does not exist yet.
-const std::vector<Op> kBeginFused = {{OP_HALO, CH_X}, ST(RESID), {OP_GATHER, 0}, ST(SETUP), {OP_HALO, CH_P, 1}, {OP_HALO, CH_R}};
-const std::vector<Op> kIterFused = {{OP_SKIP_IF_AP, 3}, ST(K1), {OP_GATHER, 0}, {OP_HALO, CH_AP}, ST(K3), {OP_GATHER, 0}, ST(K4),
-                                    {OP_GATHER, 0}, {OP_HALO, CH_R}, ST(K5), {OP_GATHER, 0}, {OP_HALO, CH_AP, 1}};
-// the same with the two exchanges hidden: the PRODUCERS of R and AP run planes 0 and np-1 first, the exchange starts, the
-// interior planes follow while the planes travel; the consumer's side waits in front of the launch that reads the halo.
-// Exchanges and reduction points come in the same order as in kIterFused, so ranks may mix the two.
-const std::vector<Op> kIterFusedOverlap = {{OP_SKIP_IF_AP, 3}, ST(K1), {OP_GATHER, 0}, {OP_HALO, CH_AP}, {OP_HALO_WAIT, CH_AP},
-                                           ST(K3), {OP_GATHER, 0}, ST(K4F_BND), {OP_HALO_START, CH_R}, ST(K4F_INT), {OP_GATHER, 0},
-                                           {OP_HALO_WAIT, CH_R}, ST(K5F_BND), {OP_HALO_START, CH_AP, 1}, ST(K5F_INT),
-                                           {OP_GATHER, 0}};
-#undef ST
 
 // what a slab holds of its device besides its handle; release() lets go of all of it in the order of declaration, on the
 // slab's thread with that device set (ec3d_multi_destroy)
@@ -130,14 +78,12 @@ struct Slab : SlabDevice {
     uint64_t api_calls = 0, api_iters = 0; // runtime calls / iterations of the last ec3d_multi_iterate (this rank)
     uint64_t seq[NCH] = {0, 0, 0, 0, 0, 0, 0};
     std::atomic<uint64_t> posted[NCH];
-    std::vector<Run> send_lo, recv_lo, send_hi, recv_hi; // towards rank-1 / rank+1, same order on both sides
+    HaloRuns halo;                                       // the rows I send / receive, DEVICE rows
     std::vector<Copy> pull_lo, pull_hi;                  // my ghost rows <- neighbour's rows
     std::vector<Piece> snd_lo, rcv_lo, snd_hi, rcv_hi;   // RCCL: contiguous pieces of my rows to send / my ghost rows to fill
     bool split_ok = false;   // K2 / K5 can run as boundary + interior launch on this slab
     bool overlap_ok = false; // K1 / K3 can run as interior + boundary launch on this slab
-    int plan = 0; // 0 plain, 1 overlap (K1/K3 interior + boundary), 2 vsplit (K2/K5 boundary first), 3 three launches
-                  // (kIterFused), 4 three launches with the producers of R and AP split around the exchange, 5 = 1 and 2
-                  // together (kIterBoth)
+    int plan = 0;            // begin_plan / iter_plan (ec3d_slab_plan.hpp)
     // A-V slab: local reference order [Ax_ext | Ay_ext | Az_ext | U_ext] <-> the global vector
     int64_t nC_ext = 0, nU_ext = 0, n_local = 0;
     std::vector<int32_t> u_glob;        // global U index of every held U unknown
@@ -350,7 +296,6 @@ int cross_wait(hipStream_t stream, hipEvent_t ev)
     return 0;
 }
 
-constexpr int kFacts = 15;         // doubles every rank tells the others at set-up (finish_setup)
 constexpr int kPlainVec = INT_MIN; // `it` of a caller that means the plain work vector (uploads, probes, the time loop's X)
 // Vector `vec` of iteration `it` in slab `owner`'s memory: the ring position from MY handle's cursor, the pointer from
 // the owner's tables, which do not change while a job runs -- another rank's thread may be iterations ahead or behind
@@ -477,41 +422,6 @@ int gather(ec3d_multi *m, Slab &s)
     return 0;
 }
 
-// a slab too thin for interior + boundary launches of K1 / K3 inside plan 5: the whole kernel where the boundary launch stands
-int unsplit_spmv_stage(int st)
-{
-    switch (st) {
-    case EC3D_STAGE_K1_BND: return EC3D_STAGE_K1;
-    case EC3D_STAGE_K3_BND: return EC3D_STAGE_K3;
-    case EC3D_STAGE_K1_INT:
-    case EC3D_STAGE_K3_INT: return -1;
-    default: return st;
-    }
-}
-
-int unsplit_stage(int st)
-{
-    switch (st) {
-    case EC3D_STAGE_K2_BND: return EC3D_STAGE_K2;
-    case EC3D_STAGE_K5_BND: return EC3D_STAGE_K5;
-    case EC3D_STAGE_K2_INT:
-    case EC3D_STAGE_K5_INT: return -1;
-    default: return st;
-    }
-}
-
-// kernel (0..4 = K1..K5) a stage's time is booked under; -1: none
-int kernel_of_stage(int st)
-{
-    switch (st) {
-    case EC3D_STAGE_K1: case EC3D_STAGE_K1_INT: case EC3D_STAGE_K1_BND: return 0;
-    case EC3D_STAGE_K2: case EC3D_STAGE_K2_INT: case EC3D_STAGE_K2_BND: return 1;
-    case EC3D_STAGE_K3: case EC3D_STAGE_K3_INT: case EC3D_STAGE_K3_BND: return 2;
-    case EC3D_STAGE_K4: case EC3D_STAGE_K4F_BND: case EC3D_STAGE_K4F_INT: return 3;
-    case EC3D_STAGE_K5: case EC3D_STAGE_K5_INT: case EC3D_STAGE_K5_BND: case EC3D_STAGE_K5F_BND: case EC3D_STAGE_K5F_INT: return 4;
-    default: return -1;
-    }
-}
 
 struct StageTimer {
     std::vector<Event> ev;      // pairs
@@ -555,9 +465,7 @@ int run_plan(ec3d_multi *m, Slab &s, const std::vector<Op> &plan, int it, double
             if (it != 1 && s.c->run.ap_valid_for == it) oi += (size_t)op.arg;
             break;
         default: {
-            int st = op.arg;
-            if ((s.plan == 2 || s.plan == 5) && !s.split_ok) st = unsplit_stage(st);
-            if (s.plan == 5 && !s.overlap_ok) st = unsplit_spmv_stage(st);
+            const int st = launched_stage(s.plan, s.split_ok, s.overlap_ok, op.arg);
             if (st < 0) break;
             s.at.store("stage");
             s.at_arg.store(st);
@@ -583,16 +491,6 @@ int run_plan(ec3d_multi *m, Slab &s, const std::vector<Op> &plan, int it, double
     return 0;
 }
 
-const std::vector<Op> &begin_plan(const Slab &s)
-{
-    return s.plan == 5 ? kBeginBoth : s.plan >= 3 ? kBeginFused : s.plan == 2 ? kBeginVsplit : kBegin;
-}
-const std::vector<Op> &iter_plan(const Slab &s)
-{
-    return s.plan == 5 ? kIterBoth : s.plan == 4 ? kIterFusedOverlap : s.plan == 3 ? kIterFused : s.plan == 2 ? kIterVsplit
-           : s.plan == 1 ? kIterOverlap : kIter;
-}
-
 int drain(Slab &s)
 {
     s.at.store("drain:side stream");
@@ -601,13 +499,6 @@ int drain(Slab &s)
     MHIP(hipStreamSynchronize(s.c->stream));
     s.at.store("idle");
     return 0;
-}
-
-void slab_bounds(int sdz, int rank, int world, int32_t &k0, int32_t &k1)
-{
-    const int base = sdz / world, rem = sdz % world;
-    k0 = rank * base + std::min(rank, rem);
-    k1 = k0 + base + (rank < rem ? 1 : 0);
 }
 
 // Peer access from this slab's device to every other device that holds a slab.  Runs on every slab's thread BEFORE
@@ -675,7 +566,7 @@ int slab_reset(ec3d_multi *m, Slab &s)
         MHIP(hipMemset(s.lsum, 0, P_NSLOT * sizeof(double)));
         MHIP(s.ptr_table.alloc((size_t)m->n));
     }
-    s.send_lo.clear(); s.recv_lo.clear(); s.send_hi.clear(); s.recv_hi.clear();
+    s.halo = HaloRuns{};
     s.pull_lo.clear(); s.pull_hi.clear();
     s.u_glob.clear();
     s.split_ok = false;
@@ -683,94 +574,38 @@ int slab_reset(ec3d_multi *m, Slab &s)
     return 0;
 }
 
-// after every slab has its matrix: pointer tables, dist mode, halo copy lists, launch plans
-int finish_setup(ec3d_multi *m)
+// what a rank tells the others of its slab (RankFacts, ec3d_slab_plan.hpp)
+RankFacts facts_of(const Slab &sl)
 {
-    // copy lists: my recv run i towards rank+1 <- rank+1's send run i towards me (and the mirror image)
-    auto pair_up = [&](const std::vector<Run> &recv, const std::vector<Run> &send, std::vector<Copy> &out) -> int {
-        out.clear();
-        if (recv.size() != send.size()) {
-            ec3d_set_error("ec3d_multi: neighbouring slabs disagree on the halo layout");
-            return 105;
-        }
-        for (size_t i = 0; i < recv.size(); ++i) {
-            const Run &r = recv[i], &t = send[i];
-            if (r.planes != t.planes || r.payload != t.payload) {
-                ec3d_set_error("ec3d_multi: neighbouring slabs disagree on the halo size");
-                return 105;
-            }
-            if (r.payload == 0) continue;
-            if (r.pitch == t.pitch || r.planes == 1) { // one contiguous piece (plane padding included)
-                const int64_t cnt = r.planes == 1 ? r.payload : (int64_t)r.planes * r.pitch;
-                out.push_back(Copy{r.start, t.start, cnt});
-            } else {
-                for (int p = 0; p < r.planes; ++p) out.push_back(Copy{r.start + p * r.pitch, t.start + p * t.pitch, r.payload});
-            }
-        }
-        return 0;
-    };
+    const ec3d_ctx *c = sl.c;
+    RankFacts f{};
+    f.fused_ok = (c->fuse23_ok && c->fuse51_ok && c->k4s_ok && c->pp_base && c->own_vectors()) ? 1.0 : 0.0;
+    f.xd = (c->pp_base && c->own_vectors()) ? (double)c->xdefer : 1.0;
+    f.xasync = (c->pp_base && c->own_vectors() && c->xasync_cap) ? 1.0 : 0.0;
+    // (an A-V slab splits K2 / K5 by tile lists made from its halo runs: always possible where there is a neighbour)
+    f.both_splits = (c->have_matrix && c->can_overlap && (c->A.sav || ec3d_dist_can_split_planes(c))) ? 1.0 : 0.0;
+    f.sav = c->A.sav ? 1.0 : 0.0;
+    f.n_pad = (double)c->A.n_pad;
+    f.fsplit = c->can_fsplit ? 1.0 : 0.0;
+    halo_facts(sl.halo, f);
+    return f;
+}
+
+// after every slab has its matrix: the halo copy lists or pieces, every rank's facts, the neighbours' agreement, the job's
+// decision (all four stated in ec3d_slab_plan.hpp) and, on every slab's thread, what it means for that handle
+int finish_setup(ec3d_multi *m, const SlabKnobs &knob)
+{
     int rc = 0;
-    // one process per GPU: contiguous pieces of my own runs (the neighbour's matching lists come out of the same rules on
-    // the same grid and storage format, which the ranks compare below)
-    auto pieces_of = [](const std::vector<Run> &runs, std::vector<Piece> &out) {
-        out.clear();
-        for (const Run &r : runs) {
-            if (r.payload == 0) continue;
-            out.push_back(Piece{r.start, r.planes == 1 ? r.payload : (int64_t)r.planes * r.pitch});
-        }
-    };
-    if (m->nccl) {
-        Slab &s = *m->slab[0];
-        pieces_of(s.send_lo, s.snd_lo);
-        pieces_of(s.recv_lo, s.rcv_lo);
-        pieces_of(s.send_hi, s.snd_hi);
-        pieces_of(s.recv_hi, s.rcv_hi);
-    } else {
-        for (int g = 0; g < m->n; ++g) {
-            Slab &s = *m->slab[(size_t)g];
-            if (g + 1 < m->n && (rc = pair_up(s.recv_hi, m->slab[(size_t)g + 1]->send_lo, s.pull_hi))) return rc;
-            if (g > 0 && (rc = pair_up(s.recv_lo, m->slab[(size_t)g - 1]->send_hi, s.pull_lo))) return rc;
-        }
-    }
-    std::vector<const double *> tab((size_t)m->n);
-    for (int g = 0; g < m->n; ++g) tab[(size_t)g] = m->slab[(size_t)g]->lsum;
-    // What every rank has to know of every other: can it run the three-launch iteration, the depth of its rings, its
-    // storage format, its size, what it sends to its neighbours.  One process: read off the slabs; one process per GPU:
-    // eight doubles per rank, all-gathered once.
-    // (h_*: a digest of the SEQUENCE of piece lengths of that direction -- one process per GPU: the k-th ncclSend of a
-    // rank must meet the k-th ncclRecv of its neighbour with the same count, and a mismatch there is a hang, not an error)
-    struct RankFacts { double fused_ok, xd, sav, n_pad, snd_lo, rcv_lo, snd_hi, rcv_hi, xasync, both_splits, fsplit,
-                       h_snd_lo, h_rcv_lo, h_snd_hi, h_rcv_hi; };
-    static_assert(sizeof(RankFacts) == kFacts * sizeof(double), "kFacts doubles");
+    std::string why;
     std::vector<RankFacts> facts((size_t)(m->nccl ? m->comm_world : m->n));
-    auto facts_of = [&](const Slab &sl) {
-        const ec3d_ctx *c = sl.c;
-        auto total = [](const std::vector<Run> &rs) { double t = 0; for (const Run &r : rs) t += (double)r.payload * r.planes; return t; };
-        RankFacts f{};
-        f.fused_ok = (c->fuse23_ok && c->fuse51_ok && c->k4s_ok && c->pp_base && c->own_vectors()) ? 1.0 : 0.0;
-        f.xd = (c->pp_base && c->own_vectors()) ? (double)c->xdefer : 1.0;
-        f.xasync = (c->pp_base && c->own_vectors() && c->xasync_cap) ? 1.0 : 0.0;
-        // (an A-V slab splits K2 / K5 by tile lists made from its halo runs: always possible where there is a neighbour)
-        f.both_splits = (c->have_matrix && c->can_overlap && (c->A.sav || ec3d_dist_can_split_planes(c))) ? 1.0 : 0.0;
-        f.sav = c->A.sav ? 1.0 : 0.0;
-        f.n_pad = (double)c->A.n_pad;
-        f.snd_lo = total(sl.send_lo); f.rcv_lo = total(sl.recv_lo); f.snd_hi = total(sl.send_hi); f.rcv_hi = total(sl.recv_hi);
-        f.fsplit = c->can_fsplit ? 1.0 : 0.0;
-        // FNV-1a over (count, then every piece's length in order), folded to 52 bits: exact in a double
-        auto digest = [](const std::vector<Piece> &ps) {
-            uint64_t h = 1469598103934665603ull;
-            auto mix = [&](uint64_t v) { for (int b = 0; b < 8; ++b) { h ^= (v >> (8 * b)) & 0xFFu; h *= 1099511628211ull; } };
-            mix((uint64_t)ps.size());
-            for (const Piece &q : ps) mix((uint64_t)q.cnt);
-            return (double)((h ^ (h >> 52)) & ((1ull << 52) - 1));
-        };
-        f.h_snd_lo = digest(sl.snd_lo); f.h_rcv_lo = digest(sl.rcv_lo); f.h_snd_hi = digest(sl.snd_hi); f.h_rcv_hi = digest(sl.rcv_hi);
-        return f;
-    };
-    if (m->nccl) {
-        const RankFacts mine = facts_of(*m->slab[0]);
+    if (m->nccl) { // one process per GPU: my pieces; every rank's facts all-gathered
+        Slab &s = *m->slab[0];
+        s.snd_lo = pieces_of(s.halo.send_lo);
+        s.rcv_lo = pieces_of(s.halo.recv_lo);
+        s.snd_hi = pieces_of(s.halo.send_hi);
+        s.rcv_hi = pieces_of(s.halo.recv_hi);
+        const RankFacts mine = facts_of(s);
         rc = run_all(m, [&](int) -> int {
-            Slab &s = *m->slab[0];
             double *snd = m->agbuf + (size_t)m->comm_world * kFacts;
             MHIP(hipMemcpyAsync(snd, &mine, sizeof mine, hipMemcpyHostToDevice, s.c->stream));
             MNCCL(m, m->nccl->AllGather(snd, m->agbuf, kFacts, ncclDouble, m->comm_sum, s.c->stream));
@@ -779,70 +614,23 @@ int finish_setup(ec3d_multi *m)
             return 0;
         }, true);
         if (rc) return rc;
-    } else {
-        for (int g = 0; g < m->n; ++g) facts[(size_t)g] = facts_of(*m->slab[(size_t)g]);
-    }
-    for (size_t g = 0; g + 1 < facts.size(); ++g) {
-        if (facts[(size_t)g].sav != facts[(size_t)g + 1].sav) {
-            ec3d_set_error("ec3d_multi: slabs chose different storage formats; call ec3d_multi_set_format(h, -1, 0) to use "
-                           "bands + tail everywhere");
-            return 105;
-        }
-        if (facts[(size_t)g].snd_hi != facts[(size_t)g + 1].rcv_lo || facts[(size_t)g].rcv_hi != facts[(size_t)g + 1].snd_lo) {
-            ec3d_set_error("ec3d_multi: neighbouring slabs disagree on the halo size");
-            return 105;
-        }
-        if (m->nccl && (facts[(size_t)g].h_snd_hi != facts[(size_t)g + 1].h_rcv_lo ||
-                        facts[(size_t)g].h_rcv_hi != facts[(size_t)g + 1].h_snd_lo)) {
-            ec3d_set_error("ec3d_multi: ranks " + std::to_string(g) + " and " + std::to_string(g + 1) +
-                           " cut their halo into different pieces (same total): the send / receive pairs would not meet");
-            return 105;
+    } else { // one process: my ghost rows <- the neighbours' rows; the facts read off the slabs
+        for (int g = 0; g < m->n && !rc; ++g) {
+            Slab &s = *m->slab[(size_t)g];
+            if (g + 1 < m->n) rc = pair_up(s.halo.recv_hi, m->slab[(size_t)g + 1]->halo.send_lo, s.pull_hi, why);
+            if (g > 0 && !rc) rc = pair_up(s.halo.recv_lo, m->slab[(size_t)g - 1]->halo.send_hi, s.pull_lo, why);
+            facts[(size_t)g] = facts_of(s);
         }
     }
-    {   // about 0.4 ms of device work between two looks at the stop flag (as ec3d_solve.hip does)
-        double big = 0;
-        for (const RankFacts &f : facts) big = std::max(big, f.n_pad);
-        const double est_us = big * 264.0 / 4.0e6 + 12.0 + 20.0 * (m->world > 1);
-        m->chunk = (int)std::min<double>(32.0, std::max<double>(1.0, 400.0 / est_us));
+    if (!rc) rc = check_neighbours(facts, m->nccl != nullptr, why);
+    if (rc) {
+        ec3d_set_error(why);
+        return rc;
     }
-    // What the whole job can do (the plan is a property of the job: the exchanges of the three-launch iteration differ
-    // from those of the five-launch one, and the rings of the deferred X update decide where an exchanged P or S lives).
-    //   fused: the single-component operator, EVERY slab on 2-D tiles with both fusions, the SpMV-form K4 and the spare
-    //          buffers in place (choose_sweep's size rule per slab: from 32 Mi rows; EC3D_FUSE23 / EC3D_FUSE51 / EC3D_K4S
-    //          force it on small grids).  EC3D_SLAB_FUSE=0 keeps five launches.
-    //   xd:    the smallest depth any slab allocated rings for (ec3d_spare_pair: 4 from 4.5 Mi streamed rows).
-    //          EC3D_SLAB_XDEFER=1 switches it off, 2 .. 4 caps it.
-    //   xasync: the groups of X updates on a stream of their own (ec3d_xasync) when every slab holds rings of two groups
-    //          (ec3d_spare_pair: a z-slab with the X update deferred does; EC3D_XASYNC=0 never) -- the ring depth decides
-    //          where an exchanged P or S lives, so it is the job's, like xd.
-    //   both:  five launches with the exchange behind TWO of them (plan 5: K2 / K5 boundary planes first and K1 / K3 interior
-    //          planes first) when every slab can split both ways and the largest holds fewer than 10 Mi rows.  Measured
-    //          through the rank rehearsal against plan 1 (profiles/r05_plan5_both_splits.log): 2 Mi rows per rank 0.158 ->
-    //          0.149 ms per iteration, 6.75 Mi 0.268 -> 0.261, 16 Mi 0.480 -> 0.493 (there the four extra launches, each
-    //          beside a send / recv kernel, cost more than the waiting they remove).  The START of the P exchange differs
-    //          from plans 0 / 1 (behind K5's boundary launch, an iteration ahead), so the choice is the job's.
-    //          A-V slabs of the structured form (five planes per neighbour travel, one interior launch of a vector kernel
-    //          does not cover them): plan 5 against plan 2 -- config 5 on 8 / 4 / 2 ranks 0.306 -> 0.287 / 0.383 -> 0.343 /
-    //          0.504 -> 0.484 ms per iteration, config 3 on 2 / 4 ranks 0.277 -> 0.259 / 0.255 -> 0.249
-    //          (profiles/r05_plan5_av_slabs.log): at every size.
-    bool fused = m->kind == 1 && m->world > 1;
-    bool xasync = m->world > 1;
-    bool both = m->world > 1;
-    bool fsplit = true; // plans 3 and 4 issue the all-gather and the send / recv group in opposite host order: the job's choice
-    double job_rows = 0;
-    int xd = EC3D_XD_MAX;
-    for (const RankFacts &f : facts) {
-        fused = fused && f.fused_ok != 0.0;
-        xd = std::min(xd, (int)f.xd);
-        xasync = xasync && f.xasync != 0.0;
-        both = both && f.both_splits != 0.0;
-        fsplit = fsplit && f.fsplit != 0.0;
-        job_rows = std::max(job_rows, f.n_pad);
-    }
-    both = both && (m->kind == 2 || job_rows < 10.0 * 1048576.0); // (A-V slabs: measured a gain at every size, below)
-    if (const char *e = getenv("EC3D_SLAB_FUSE")) fused = fused && atoi(e) != 0;
-    if (const char *e = getenv("EC3D_SLAB_XDEFER")) xd = std::min(xd, std::max(1, atoi(e)));
-    // (a one-slab job keeps its slab's own depth: five launches, X every D-th iteration from 4.5 Mi rows, like any slab)
+    const JobPlan job = decide_job(facts, m->kind, m->world, knob);
+    m->chunk = job.chunk;
+    std::vector<const double *> tab((size_t)m->n);
+    for (int g = 0; g < m->n; ++g) tab[(size_t)g] = m->slab[(size_t)g]->lsum;
     return run_all(m, [&](int r) -> int {
         Slab &s = *m->slab[(size_t)r];
         MHIP(hipMemcpy(s.ptr_table, tab.data(), tab.size() * sizeof(double *), hipMemcpyHostToDevice));
@@ -852,118 +640,84 @@ int finish_setup(ec3d_multi *m)
         c->lsum = s.lsum;
         c->gsum = m->nccl ? m->gsum : nullptr;          // one process per GPU: the all-gathered copy
         c->lsum_ptrs = m->nccl ? nullptr : s.ptr_table.get(); // one process: every rank's sums read in place
-        c->slab_fused = fused;
-        c->slab_xd = xd;
-        // (three-launch slabs keep the applying K4: measured, the second launch costs them more than it fills)
-        const bool xa_forced = getenv("EC3D_XASYNC") && atoi(getenv("EC3D_XASYNC")) == 2;
-        c->slab_xasync = xasync && xd > 1 && (!fused || xa_forced);
-        c->sweep_s.halo_store = fused ? ((s.rank > 0 ? 1 : 0) | (s.rank + 1 < m->world ? 2 : 0)) : 0;
+        c->slab_fused = job.fused;
+        c->slab_xd = job.xd;
+        c->slab_xasync = job.xasync;
+        const SlabPlan sp = decide_slab(job, m->kind, m->world, s.rank, knob, ec3d_can_overlap(c) != 0);
+        c->sweep_s.halo_store = sp.halo_store;
         c->sweep_fb.halo_store = c->sweep_fi.halo_store = c->sweep_s.halo_store;
         if (c->pp_base) { // every rank cycles P and S through the same number of buffers
             const int D = ec3d_xdefer(c), depth = ec3d_xasync(c) ? 2 * D : D;
             c->pdepth = std::max(2, depth);
             c->sdepth = std::max(1, depth);
         }
-        s.plan = 0;
-        s.split_ok = false;
-        // EC3D_SLAB_PLAN (the SAME value on every rank: plan 2 orders its exchanges differently) picks the five-launch plan of
-        // a single-component job: 0 exchange in front of K1 / K3, 1 K1 / K3 split around it, 2 K2 / K5 boundary tiles first
-        int want_plan = getenv("EC3D_SLAB_PLAN") ? atoi(getenv("EC3D_SLAB_PLAN")) : -1;
-        // Plan 5 is OPT-IN (EC3D_SLAB_PLAN=5, the same on every rank) until a job of two real devices has verified it
-        // bit for bit: everything measured for it (-3 ... -5 % below 10 Mi rows per rank, -10 % on A-V slabs) was measured
-        // with the "neighbour" on the same card (`both` says where the one-card measurements would have picked it).
-        (void)both;
-        s.overlap_ok = false;
-        if (m->kind == 1 && !((want_plan == 2 || want_plan == 5) && !fused && m->world > 1)) {
-            const bool no_fsplit = getenv("EC3D_SLAB_FSPLIT") && atoi(getenv("EC3D_SLAB_FSPLIT")) == 0;
-            s.plan = fused ? ((fsplit && !no_fsplit) ? 4 : 3) : (ec3d_can_overlap(c) && want_plan != 0) ? 1 : 0;
-        } else if (m->kind == 2 && want_plan == 0) {
-            s.plan = 0; // (measurement: the A-V job with the exchange in front of K1 / K3, no split launches)
-        } else if (m->world > 1) {
-            // the ORDER of exchanges is a property of the job: every A-V rank uses the producer-side
-            // plan; a rank whose slab is all boundary runs the whole kernels in that order
-            s.plan = want_plan == 5 ? 5 : 2;
-            s.overlap_ok = s.plan == 5 && ec3d_can_overlap(c);
+        s.plan = sp.plan;
+        s.overlap_ok = sp.overlap_ok;
+        int32_t en = 0;
+        int rc2 = 0;
+        if (sp.split == SPLIT_PLANES) {
+            rc2 = ec3d_dist_set_boundary_planes(c, &en);
+        } else if (sp.split == SPLIT_ROWS) {
             std::vector<int64_t> lo, hi;
-            for (const std::vector<Run> *rs : {&s.send_lo, &s.recv_lo, &s.send_hi, &s.recv_hi})
-                for (const Run &r : *rs)
-                    if (r.payload > 0) {
-                        lo.push_back(r.lo());
-                        hi.push_back(r.hi());
-                    }
-            int32_t en = 0;
-            if (m->kind == 1) { // the single-component operator: whole planes, window sweeps
-                int rc2 = ec3d_dist_set_boundary_planes(c, &en);
-                if (rc2) return rc2;
-            } else if (!lo.empty()) {
-                int rc2 = ec3d_dist_set_boundary_rows(c, (int32_t)lo.size(), lo.data(), hi.data(), &en);
-                if (rc2) return rc2;
-            }
-            s.split_ok = en != 0;
+            boundary_rows(s.halo, lo, hi);
+            if (!lo.empty()) rc2 = ec3d_dist_set_boundary_rows(c, (int32_t)lo.size(), lo.data(), hi.data(), &en);
         }
-        return 0;
+        s.split_ok = en != 0;
+        return rc2;
     });
 }
 
-// owned ranges (local reference numbering) and halo runs (DEVICE rows) of an A-V slab whose matrix is in place.
-// upl[p] = held conducting cells before held plane p (np + 1 entries).
-void av_layout(ec3d_multi *m, Slab &s, const std::vector<int64_t> &upl)
+// What the four set-up entry points share.  The job's grid is recorded; every slab's thread makes its handle anew, takes
+// its planes [k0, k1) and the ones it holds (an A-V slab, kind 2: two halo planes per interior side) and calls
+// matrix_and_runs(slab) for the slab's matrix, sizes and halo runs; then the job is of `kind` and finish_setup agrees
+// on its plan.  nnz < 0: the sum of the slabs' counts.
+int setup_job(ec3d_multi *m, const SlabKnobs &knob, int kind, int64_t sdx, int64_t sdy, int64_t sdz, int64_t nU_glob,
+              int64_t n_glob, int64_t nnz, const std::function<int(Slab &)> &matrix_and_runs)
 {
-    const int H = 2;
-    ec3d_ctx *c = s.c;
-    const int64_t kdz = m->kdz, nC = s.nC_ext, mloc = s.nU_ext;
-    const int64_t p0 = s.k0 - s.e0, p1 = s.k1 - s.e0;
-    for (int d = 0; d < 3; ++d) {
-        s.own_lo[d] = d * nC + p0 * kdz;
-        s.own_hi[d] = d * nC + p1 * kdz;
-    }
-    s.own_lo[3] = 3 * nC + upl[(size_t)p0];
-    s.own_hi[3] = 3 * nC + upl[(size_t)p1];
-    // The 7-point stencil and the U rows read A one plane away; only the one-sided A-U stencils
-    // (src/EC3D.f90:697-706) reach two planes, and they read U
-    struct Blk { int64_t base, pitch, payload; int h; };
-    std::vector<Blk> blocks;
-    const bool structured = c->A.sav != 0;
-    if (structured) {
-        for (int d = 0; d < 4; ++d) blocks.push_back(Blk{d * c->nCd, c->pitch, kdz, d < 3 ? 1 : H});
-    } else {
-        for (int d = 0; d < 3; ++d) blocks.push_back(Blk{d * nC, kdz, kdz, 1});
-    }
-    // Structured form: the U block is grid-shaped, but only cells of a conductor hold an unknown -- every other row of it
-    // is inert and stays exactly zero in every vector.  Two planes of U that hold no conductor cell therefore need not
-    // travel: the ghost rows they would fill are zero already (most cuts of a real model lie in air: BASELINE config 5 on
-    // 8 ranks has the conductor at ONE of its seven cuts).  Both sides of a cut decide from the same planes' cell counts.
-    // OPT-IN (EC3D_AV_SEND_EMPTY_U=0) until a job of two real devices has run once: by default every U plane travels.
-    const bool u_always = !(getenv("EC3D_AV_SEND_EMPTY_U") && atoi(getenv("EC3D_AV_SEND_EMPTY_U")) == 0);
-    auto u_cells = [&](int64_t a, int64_t b) { return upl[(size_t)std::min<int64_t>(b, (int64_t)upl.size() - 1)] - upl[(size_t)std::max<int64_t>(a, 0)]; };
-    // (a rehearsal sends to itself: what it sends towards a cut must pair with what it receives from there, so a side's U
-    // planes travel when EITHER of the two pairs of planes around the cut holds a conductor cell)
-    auto travels = [&](const Blk &b, int64_t first_plane, int64_t cut) {
-        if (!structured || b.h != H || u_always) return true;
-        return m->rehearse ? u_cells(cut - H, cut + H) > 0 : u_cells(first_plane, first_plane + H) > 0;
-    };
-    if (s.e0 < s.k0) {
-        for (const Blk &b : blocks) {
-            if (travels(b, p0, p0)) s.send_lo.push_back(Run{b.base + p0 * b.pitch, b.pitch, b.payload, b.h});
-            if (travels(b, p0 - b.h, p0)) s.recv_lo.push_back(Run{b.base + (p0 - b.h) * b.pitch, b.pitch, b.payload, b.h});
-        }
-        if (!structured) { // compact U block: the U cells of my first two owned planes / my lower halo planes
-            const int64_t ulo = upl[(size_t)p0], cnt_s = upl[(size_t)(p0 + H)] - ulo;
-            s.send_lo.push_back(Run{3 * nC + ulo, cnt_s, cnt_s, 1});
-            s.recv_lo.push_back(Run{3 * nC, ulo, ulo, 1});
-        }
-    }
-    if (s.k1 < s.e1) {
-        for (const Blk &b : blocks) {
-            if (travels(b, p1 - b.h, p1)) s.send_hi.push_back(Run{b.base + (p1 - b.h) * b.pitch, b.pitch, b.payload, b.h});
-            if (travels(b, p1, p1)) s.recv_hi.push_back(Run{b.base + p1 * b.pitch, b.pitch, b.payload, b.h});
-        }
-        if (!structured) {
-            const int64_t uend = upl[(size_t)p1], cnt_s = uend - upl[(size_t)(p1 - H)], cnt_r = mloc - uend;
-            s.send_hi.push_back(Run{3 * nC + uend - cnt_s, cnt_s, cnt_s, 1});
-            s.recv_hi.push_back(Run{3 * nC + uend, cnt_r, cnt_r, 1});
-        }
-    }
+    m->kind = 0;
+    m->sdx = (int32_t)sdx; m->sdy = (int32_t)sdy; m->sdz = (int32_t)sdz;
+    m->kdz = sdx * sdy;
+    m->nC_glob = m->kdz * sdz;
+    m->nU_glob = nU_glob;
+    m->n_glob = n_glob;
+    int rc = run_all(m, [&](int r) -> int {
+        Slab &s = *m->slab[(size_t)r];
+        int rc2 = slab_reset(m, s);
+        if (rc2) return rc2;
+        slab_bounds((int)sdz, s.rank, m->world, s.k0, s.k1);
+        held_range((int)sdz, s.k0, s.k1, kind == 2 ? 2 : 0, s.e0, s.e1);
+        return matrix_and_runs(s);
+    });
+    if (rc) return rc;
+    m->kind = kind;
+    m->nnz = std::max<int64_t>(nnz, 0);
+    for (auto &s : m->slab)
+        if (nnz < 0) m->nnz += s->c->A.nnz;
+    return finish_setup(m, knob);
+}
+
+// sizes and halo runs of a slab of `rows` rows of the single-component operator
+int cube_slab_layout(const ec3d_multi *m, Slab &s, int64_t rows)
+{
+    std::string why;
+    s.n_local = rows;
+    const int rc = cube_runs(s.rank, m->world, m->kdz, rows, s.c->ghost, s.halo, why);
+    if (rc) ec3d_set_error(why);
+    return rc;
+}
+
+// sizes, owned ranges and halo runs of an A-V slab whose matrix is in place, nU held U unknowns behind three blocks of the
+// held planes' cells; upl[p] = held conducting cells before held plane p
+void av_slab_layout(const ec3d_multi *m, Slab &s, const SlabKnobs &knob, int64_t nU, const std::vector<int64_t> &upl)
+{
+    s.nC_ext = (int64_t)(s.e1 - s.e0) * m->kdz;
+    s.nU_ext = nU;
+    s.n_local = 3 * s.nC_ext + nU;
+    const AvSlab g{s.c->A.sav != 0, s.c->nCd, s.c->pitch, m->kdz, s.nC_ext, s.nU_ext, s.k0, s.k1, s.e0, s.e1};
+    const AvLayout L = av_layout(g, upl, knob.u_always(), m->rehearse);
+    std::copy(L.own_lo, L.own_lo + 4, s.own_lo);
+    std::copy(L.own_hi, L.own_hi + 4, s.own_hi);
+    s.halo = L.runs;
 }
 
 __global__ void k_fill(double *p, int64_t n, double v)
@@ -981,7 +735,7 @@ int poison_recv_rows(Slab &s, int vi)
 {
     double *v = s.c->vec[vi];
     const double nan = std::nan("");
-    for (const std::vector<Run> *rs : {&s.recv_lo, &s.recv_hi})
+    for (const std::vector<Run> *rs : {&s.halo.recv_lo, &s.halo.recv_hi})
         for (const Run &r : *rs)
             for (int p = 0; p < r.planes; ++p) {
                 if (r.payload <= 0) continue;
@@ -1049,7 +803,7 @@ int slab_solve(ec3d_multi *m, Slab &s, double tol, int32_t itmax, int32_t *iter_
 {
     ec3d_ctx *c = s.c;
     const int64_t total = std::max<int64_t>(0, (int64_t)itmax + 1); // src/solvers.f90:25-29
-    int rc = run_plan(m, s, begin_plan(s), 0, tol, nullptr);
+    int rc = run_plan(m, s, begin_plan(s.plan), 0, tol, nullptr);
     if (rc) return rc;
     (void)ec3d_run_open(c, 1, total); // the itmax exit: the last iteration applies the pending X updates
     // every rank must look at the flag after the same iterations, so the chunk is a property of the job
@@ -1063,7 +817,7 @@ int slab_solve(ec3d_multi *m, Slab &s, double tol, int32_t itmax, int32_t *iter_
     while (launched < total && !stopped) {
         const int64_t n = std::min<int64_t>(chunk, total - launched);
         for (int64_t i = 0; i < n; ++i)
-            if ((rc = run_plan(m, s, iter_plan(s), (int)(++launched), 0.0, nullptr))) return rc;
+            if ((rc = run_plan(m, s, iter_plan(s.plan), (int)(++launched), 0.0, nullptr))) return rc;
         if ((rc = ec3d_read_state_async(c, &s.stop_pinned[ci & 1]))) return rc;
         MHIP(hipEventRecord(s.ev_stop[ci & 1], c->stream));
         if (ci > 0) {
@@ -1271,43 +1025,13 @@ extern "C" int ec3d_multi_assemble_poisson(ec3d_multi_handle m, int32_t sdx, int
         ec3d_set_error("ec3d_multi_assemble_poisson: fewer z-planes than ranks");
         return 2;
     }
-    m->kind = 0;
-    m->sdx = sdx; m->sdy = sdy; m->sdz = sdz;
-    m->kdz = (int64_t)sdx * sdy;
-    m->nC_glob = m->kdz * sdz;
-    m->nU_glob = 0;
-    m->n_glob = m->nC_glob;
-    int rc = run_all(m, [&](int r) -> int {
-        Slab &s = *m->slab[(size_t)r];
-        int rc2 = slab_reset(m, s);
-        if (rc2) return rc2;
-        slab_bounds(sdz, s.rank, m->world, s.k0, s.k1);
-        s.e0 = s.k0;
-        s.e1 = s.k1;
-        rc2 = m->world == 1 ? ec3d_assemble_poisson(s.c, sdx, sdy, sdz, BND, delta)
-                            : ec3d_assemble_poisson_slab(s.c, sdx, sdy, sdz, s.k0, s.k1, BND, delta);
-        if (rc2) return rc2;
-        const int64_t kdz = m->kdz, n = (int64_t)(s.k1 - s.k0) * kdz;
-        s.n_local = n;
-        if (s.c->ghost < kdz && m->world > 1) {
-            ec3d_set_error("ec3d_multi: ghost zone smaller than a plane");
-            return 105;
-        }
-        if (s.rank > 0) {
-            s.send_lo.push_back(Run{0, kdz, kdz, 1});
-            s.recv_lo.push_back(Run{-kdz, kdz, kdz, 1});
-        }
-        if (s.rank + 1 < m->world) {
-            s.send_hi.push_back(Run{n - kdz, kdz, kdz, 1});
-            s.recv_hi.push_back(Run{n, kdz, kdz, 1});
-        }
-        return 0;
+    const SlabKnobs knob;
+    const int64_t nC = (int64_t)sdx * sdy * sdz;
+    return setup_job(m, knob, 1, sdx, sdy, sdz, 0, nC, -1, [&](Slab &s) -> int {
+        const int rc = m->world == 1 ? ec3d_assemble_poisson(s.c, sdx, sdy, sdz, BND, delta)
+                                     : ec3d_assemble_poisson_slab(s.c, sdx, sdy, sdz, s.k0, s.k1, BND, delta);
+        return rc ? rc : cube_slab_layout(m, s, (int64_t)(s.k1 - s.k0) * m->kdz);
     });
-    if (rc) return rc;
-    m->kind = 1;
-    m->nnz = 0;
-    for (auto &s : m->slab) m->nnz += s->c->A.nnz;
-    return finish_setup(m);
 }
 
 // ---- the full A-V system (ec3d_assemble, src/EC3D.f90:465-1049) on z-slabs: global tables in, the library
@@ -1323,26 +1047,20 @@ extern "C" int ec3d_multi_assemble(ec3d_multi_handle m, int32_t sdx, int32_t sdy
         return 2;
     }
     m->kind = 0;
-    m->sdx = sdx; m->sdy = sdy; m->sdz = sdz;
-    m->kdz = (int64_t)sdx * sdy;
-    m->nC_glob = m->kdz * sdz;
+    const int64_t kdz = (int64_t)sdx * sdy, nC_glob = kdz * sdz;
     int64_t nU = 0;
-    for (int64_t q = 0; q < m->nC_glob; ++q) nU += geoPHYS_C[q] != 0;
-    m->nU_glob = nU;
-    m->n_glob = 3 * m->nC_glob + nU;
-    for (int64_t q = 0; q < m->nC_glob; ++q)
-        if (geoPHYS_C[q] != 0 && (geoPHYS_C[q] <= 3 * m->nC_glob || geoPHYS_C[q] > m->n_glob)) {
+    for (int64_t q = 0; q < nC_glob; ++q) nU += geoPHYS_C[q] != 0;
+    const int64_t n_glob = 3 * nC_glob + nU;
+    for (int64_t q = 0; q < nC_glob; ++q)
+        if (geoPHYS_C[q] != 0 && (geoPHYS_C[q] <= 3 * nC_glob || geoPHYS_C[q] > n_glob)) {
             ec3d_set_error("ec3d_multi_assemble: geoPHYS_C holds a U column id outside 3*nCells+1 .. n");
             return 2;
         }
-    int rc = run_all(m, [&](int r) -> int {
-        Slab &s = *m->slab[(size_t)r];
-        int rc2 = slab_reset(m, s);
-        if (rc2) return rc2;
-        slab_bounds(sdz, s.rank, m->world, s.k0, s.k1);
-        s.e0 = std::max(0, s.k0 - H);
-        s.e1 = std::min(sdz, s.k1 + H);
-        const int64_t kdz = m->kdz, np = s.e1 - s.e0, nC = np * kdz;
+    const SlabKnobs knob;
+    // (neighbours must agree on the storage -- a slab that fell back to bands + tail next to a structured one would
+    // exchange differently shaped blocks: finish_setup compares; nnz: per-slab counts include inert halo rows, not summed)
+    return setup_job(m, knob, 2, sdx, sdy, sdz, nU, n_glob, 0, [&](Slab &s) -> int {
+        const int64_t np = s.e1 - s.e0, nC = np * kdz;
         const int8_t *geo = geoPHYS + (int64_t)s.e0 * kdz;
         const int32_t *gc = geoPHYS_C + (int64_t)s.e0 * kdz;
         std::vector<int32_t> gc_ext((size_t)nC, 0);
@@ -1353,28 +1071,18 @@ extern "C" int ec3d_multi_assemble(ec3d_multi_handle m, int32_t sdx, int32_t sdy
             for (int64_t q = p * kdz; q < (p + 1) * kdz; ++q)
                 if (gc[q] != 0) {
                     gc_ext[(size_t)q] = (int32_t)(3 * nC + 1 + mloc++);
-                    s.u_glob.push_back((int32_t)(gc[q] - 3 * m->nC_glob - 1));
+                    s.u_glob.push_back((int32_t)(gc[q] - 3 * nC_glob - 1));
                 }
         }
         upl[(size_t)np] = mloc;
-        s.nC_ext = nC;
-        s.nU_ext = mloc;
-        s.n_local = 3 * nC + mloc;
-        if (m->world == 1)
-            rc2 = ec3d_assemble(s.c, sdx, sdy, sdz, geo, gc_ext.data(), valPHYS, nsub_glob, BND, delta, dt);
-        else
-            rc2 = ec3d_assemble_slab(s.c, sdx, sdy, sdz, s.e0, s.e1, s.k0, s.k1, geo, gc_ext.data(), valPHYS, nsub_glob,
-                                     BND, delta, dt);
-        if (rc2) return rc2;
-        av_layout(m, s, upl);
+        const int rc = m->world == 1
+                           ? ec3d_assemble(s.c, sdx, sdy, sdz, geo, gc_ext.data(), valPHYS, nsub_glob, BND, delta, dt)
+                           : ec3d_assemble_slab(s.c, sdx, sdy, sdz, s.e0, s.e1, s.k0, s.k1, geo, gc_ext.data(), valPHYS,
+                                                nsub_glob, BND, delta, dt);
+        if (rc) return rc;
+        av_slab_layout(m, s, knob, mloc, upl);
         return 0;
     });
-    if (rc) return rc;
-    // (neighbours must agree on the storage -- a slab that fell back to bands + tail next to a structured one would
-    // exchange differently shaped blocks: finish_setup compares)
-    m->kind = 2;
-    m->nnz = 0; // per-slab counts include inert halo rows: not summed
-    return finish_setup(m);
 }
 
 // ---- a single-component 7-point operator that arrives as CSR (BASELINE configs 2 and 4 through the drop-in symbol):
@@ -1392,18 +1100,8 @@ static int multi_set_cube_csr(ec3d_multi *m, int32_t n, const double *valA, cons
         ec3d_set_error("ec3d_multi_set_matrix_csr: fewer z-planes than ranks");
         return 2;
     }
-    m->sdx = (int32_t)sdx; m->sdy = (int32_t)(kdz / sdx); m->sdz = (int32_t)sdz;
-    m->kdz = kdz;
-    m->nC_glob = (int64_t)n;
-    m->nU_glob = 0;
-    m->n_glob = (int64_t)n;
-    int rc = run_all(m, [&](int r) -> int {
-        Slab &s = *m->slab[(size_t)r];
-        int rc2 = slab_reset(m, s);
-        if (rc2) return rc2;
-        slab_bounds((int)sdz, s.rank, m->world, s.k0, s.k1);
-        s.e0 = s.k0;
-        s.e1 = s.k1;
+    const SlabKnobs knob;
+    return setup_job(m, knob, 1, sdx, kdz / sdx, sdz, 0, n, M.nnz, [&](Slab &s) -> int {
         const int64_t rows = (int64_t)(s.k1 - s.k0) * kdz, r0 = (int64_t)s.k0 * kdz;
         HostMatrix S;
         S.n = rows;
@@ -1419,26 +1117,9 @@ static int multi_set_cube_csr(ec3d_multi *m, int32_t n, const double *valA, cons
         S.nnz = 0;
         for (int64_t q = r0; q < r0 + rows; ++q) S.nnz += irow[q + 1] - irow[q];
         if (s.c->use_dict) ec3d_build_dictionary_host(S);
-        if ((rc2 = ec3d_upload_matrix(s.c, S, m->world > 1 ? kdz : 0))) return rc2;
-        s.n_local = rows;
-        if (s.c->ghost < kdz && m->world > 1) {
-            ec3d_set_error("ec3d_multi: ghost zone smaller than a plane");
-            return 105;
-        }
-        if (s.rank > 0) {
-            s.send_lo.push_back(Run{0, kdz, kdz, 1});
-            s.recv_lo.push_back(Run{-kdz, kdz, kdz, 1});
-        }
-        if (s.rank + 1 < m->world) {
-            s.send_hi.push_back(Run{rows - kdz, kdz, kdz, 1});
-            s.recv_hi.push_back(Run{rows, kdz, kdz, 1});
-        }
-        return 0;
+        const int rc = ec3d_upload_matrix(s.c, S, m->world > 1 ? kdz : 0);
+        return rc ? rc : cube_slab_layout(m, s, rows);
     });
-    if (rc) return rc;
-    m->kind = 1;
-    m->nnz = M.nnz;
-    return finish_setup(m);
 }
 
 // ---- the reference's CSR triple (what sprsbcgstabwr_ receives): recognised as the A-V system on a grid
@@ -1447,7 +1128,6 @@ extern "C" int ec3d_multi_set_matrix_csr(ec3d_multi_handle m, int32_t n, const d
                                          const int32_t *jcol)
 {
     if (!m) return 2;
-    const int H = 2;
     m->kind = 0;
     SavHost G;
     if (ec3d_csr_to_sav_host(n, valA, irow, jcol, G) != 0) {
@@ -1473,25 +1153,16 @@ extern "C" int ec3d_multi_set_matrix_csr(ec3d_multi_handle m, int32_t n, const d
             return rc0;
         }
     }
-    m->sdx = (int32_t)G.sdx; m->sdy = (int32_t)(G.plane / G.sdx); m->sdz = (int32_t)sdz;
-    m->kdz = G.plane;
-    m->nC_glob = G.plane * sdz;
-    m->nU_glob = (int64_t)G.cond_cell.size();
-    m->n_glob = n;
-    int rc = run_all(m, [&](int r) -> int {
-        Slab &s = *m->slab[(size_t)r];
-        int rc2 = slab_reset(m, s);
-        if (rc2) return rc2;
-        slab_bounds((int)sdz, s.rank, m->world, s.k0, s.k1);
-        s.e0 = std::max(0, s.k0 - H);
-        s.e1 = std::min((int32_t)sdz, s.k1 + H);
+    const SlabKnobs knob;
+    return setup_job(m, knob, 2, G.sdx, G.plane / G.sdx, sdz, (int64_t)G.cond_cell.size(), n, G.nnz, [&](Slab &s) -> int {
+        int rc = 0;
         const int64_t np = s.e1 - s.e0;
         if (m->world == 1) {
-            if ((rc2 = ec3d_upload_sav(s.c, G))) return rc2;
+            if ((rc = ec3d_upload_sav(s.c, G))) return rc;
         } else {
             SavHost L;
             ec3d_sav_slice(G, s.e0, s.e1, s.k0, s.k1, L);
-            if ((rc2 = ec3d_upload_sav(s.c, L))) return rc2;
+            if ((rc = ec3d_upload_sav(s.c, L))) return rc;
         }
         // held conducting cells: one contiguous run of the global scan-order list
         std::vector<int64_t> upl((size_t)np + 1, 0);
@@ -1506,16 +1177,9 @@ extern "C" int ec3d_multi_set_matrix_csr(ec3d_multi_handle m, int32_t n, const d
         for (int64_t p = 0; p < np; ++p) upl[(size_t)p + 1] += upl[(size_t)p];
         s.u_glob.resize((size_t)cnt);
         for (int64_t q = 0; q < cnt; ++q) s.u_glob[(size_t)q] = (int32_t)(first + q);
-        s.nC_ext = np * G.plane;
-        s.nU_ext = cnt;
-        s.n_local = 3 * s.nC_ext + cnt;
-        av_layout(m, s, upl);
+        av_slab_layout(m, s, knob, cnt, upl);
         return 0;
     });
-    if (rc) return rc;
-    m->kind = 2;
-    m->nnz = G.nnz;
-    return finish_setup(m);
 }
 
 extern "C" int ec3d_multi_upload(ec3d_multi_handle m, int which, const double *host)
@@ -1723,7 +1387,7 @@ extern "C" int ec3d_multi_iterate_begin(ec3d_multi_handle m)
     if (rc) return rc;
     return run_all(m, [&](int r) -> int {
         Slab &s = *m->slab[(size_t)r];
-        int rc2 = run_plan(m, s, begin_plan(s), 0, -1.0, nullptr);
+        int rc2 = run_plan(m, s, begin_plan(s.plan), 0, -1.0, nullptr);
         return rc2 ? rc2 : drain(s);
     }, true);
 }
@@ -1748,7 +1412,7 @@ int multi_iterate(ec3d_multi *m, int32_t first_iter, int32_t count, int timed_ra
         int rc2 = 0;
         const uint64_t calls0 = t_api_calls;
         for (int it = first_iter; it < first_iter + count; ++it)
-            if ((rc2 = run_plan(m, s, iter_plan(s), it, 0.0, tp))) return rc2;
+            if ((rc2 = run_plan(m, s, iter_plan(s.plan), it, 0.0, tp))) return rc2;
         s.api_calls = t_api_calls - calls0;
         s.api_iters = (uint64_t)std::max(0, count);
         if (!kernel_ms) return 0; // asynchronous: ec3d_multi_synchronize() joins
@@ -1834,9 +1498,8 @@ extern "C" int ec3d_multi_halo_rows(ec3d_multi_handle m, int32_t rank, int64_t *
     if (rc) return rc;
     if (rank < 0 || rank >= m->n) return 2;
     const Slab &s = *m->slab[(size_t)rank];
-    auto total = [](const std::vector<Run> &rs) { int64_t t = 0; for (const Run &r : rs) t += r.payload * (int64_t)r.planes; return t; };
-    if (sent) *sent = total(s.send_lo) + total(s.send_hi);
-    if (received) *received = total(s.recv_lo) + total(s.recv_hi);
+    if (sent) *sent = rows_of(s.halo.send_lo) + rows_of(s.halo.send_hi);
+    if (received) *received = rows_of(s.halo.recv_lo) + rows_of(s.halo.recv_hi);
     return 0;
 }
 
