@@ -225,20 +225,88 @@ def twin_solve_slabs(slabs, plan, valA, irow, jcol, b, x0, tol, itmax, hist_cap=
     launches, 4 three launches with K4 and K5-in-K1 as boundary + interior launch, 5 = 1 and 2 together (what
     EC3DMulti.plan() reports).
     Returns (x, iter, hist_s, hist_r, restarts)."""
+    return _twin_slabs([(sv, (lambda u, lo=lo, hi=hi: u[lo:hi])) for sv, lo, hi in slabs], plan, valA, irow, jcol, b, x0,
+                       tol, itmax, hist_cap)
+
+
+def av_slab_rows(view, k0, k1, geoPHYS_C):
+    """Where the rows a rank OWNS live: (global rows in the reference's numbering [Ax | Ay | Az | U], their device rows on
+    the rank's handle, length of a device vector) for the z-slab [k0, k1) of the A-V system, held -- as ec3d_multi.hip and
+    dist.HipAVSlabOps hold it -- on the extended slab [max(0, k0 - 2), min(sdz, k1 + 2)) in local reference order, U in
+    scan order of the extended planes, mapped to device rows by the handle's row_map()."""
+    gc = np.asarray(geoPHYS_C)
+    sdz = gc.shape[0]
+    kdz = gc[0].size
+    per = (gc != 0).reshape(sdz, -1).sum(axis=1)
+    e0, e1 = max(0, k0 - 2), min(sdz, k1 + 2)
+    nC, nCg = (e1 - e0) * kdz, sdz * kdz
+    rm = view.row_map().astype(np.int64)
+    assert len(rm) == 3 * nC + int(per[e0:e1].sum())
+    cell = np.arange((k0 - e0) * kdz, (k1 - e0) * kdz)
+    u = np.arange(int(per[e0:k0].sum()), int(per[e0:k1].sum()))
+    local = np.concatenate([d * nC + cell for d in range(3)] + [3 * nC + u])
+    glob = np.concatenate([d * nCg + e0 * kdz + cell for d in range(3)] + [3 * nCg + int(per[:e0].sum()) + u])
+    n_dev = max(int(view.geometry(0).n_pad), int(rm.max()) + 1)
+    return glob, rm[local], n_dev
+
+
+def twin_solve_av_slabs(slabs, geoPHYS_C, plan, valA, irow, jcol, b, x0, tol, itmax, hist_cap=0, swap=(), sums=None):
+    """twin_solve_slabs for z-slabs of the A-V system (one conducting domain, either storage form): the same
+    whole-system iteration with oracle.spmv_csr on the global CSR; every dot product summed per rank over THAT RANK'S
+    DEVICE VECTOR -- the global vector scattered to the device rows of the rows the rank owns (av_slab_rows), exact zeros
+    on every other row: halo rows, which the kernels mask to 0.0 (row_owned, ec3d_kernels.hip) or, on tile-aligned planes,
+    never visit (Sweep::win_*), the padding between pitched planes and empty U slots, which hold 0.0 -- in the order of the
+    launches the rank's view reports, collapsed with tree_sum, the ranks added in rank order with tree_sum.
+    slabs: [(view, k0, k1)] in rank order, as EC3DMulti.slab gives them.  sums: a dict that receives every rank's own sum
+    of the LAST dot product of each kind, by the name of the slot the rank keeps it in (ec3d_internal.hpp P_*: "BB",
+    "RR_INIT", "D1" = AP.R0, "SS", "D2" = AS.S, "D3" = AS.AS, "RR", "RR0N") -- S.S feeds nothing but the stop test, so x
+    cannot tell how it was summed; the slots can.  swap: kinds ("ss", "spmv") whose two launches are strung together in the
+    WRONG order (a deliberately wrong twin, for checking that a comparison can fail).
+    Returns (x, iter, hist_s, hist_r, restarts)."""
+    picks = []
+    for sv, k0, k1 in slabs:
+        glob, dev, n_dev = av_slab_rows(sv, k0, k1, geoPHYS_C)
+
+        def pick(u, glob=glob, dev=dev, n_dev=n_dev):
+            d = np.zeros(n_dev)
+            d[dev] = u[glob]
+            return d
+        picks.append((sv, pick))
+    return _twin_slabs(picks, plan, valA, irow, jcol, b, x0, tol, itmax, hist_cap, swap=swap, per_rank=True, sums=sums)
+
+
+def _twin_slabs(slabs, plan, valA, irow, jcol, b, x0, tol, itmax, hist_cap=0, swap=(), per_rank=False, sums=None):
+    """slabs: [(view, pick)] in rank order; pick(global vector) -> the vector the rank's launches sum over.
+    per_rank: a rank that cannot split a kernel runs it whole inside the job's plan (launched_stage, ec3d_slab_plan.hpp):
+    K1 / K3 where the view says it cannot overlap, K2 where it reports no boundary launch (which 5 holds no tile)."""
     spmv_w = (3, 4) if plan in (1, 5) else (1,)    # (plan 5: both splits at once)
     ss_w = (5, 6) if plan in (2, 5) else (2,)      # who sums S.S (plan 2: K2 as boundary + interior launch)
     k4_w = (7, 8) if plan == 4 else (0,)           # who sums R.R and R.R0
     k51_w = (7, 8) if plan == 4 else spmv_w        # who sums AP.R0 from the second iteration on (K5-in-K1 of the one before)
     geo = []
-    for sv, lo, hi in slabs:
-        g = {w: geoms_of(sv, (w,))[0] for w in set((0, 1) + ss_w + spmv_w + k4_w + k51_w)}
-        geo.append((g, lo, hi))
+    for sv, pick in slabs:
+        who = dict(res=(1,), spmv=spmv_w, ss=ss_w, k4=k4_w, k51=k51_w)
+        if per_rank and spmv_w == (3, 4) and not sv.can_overlap():
+            who["spmv"] = who["k51"] = (1,)
+        if per_rank and ss_w == (5, 6) and len(sv.visit_order(5)[1]) == 0:
+            who["ss"] = (2,)
+        for kind in swap:
+            if len(who[kind]) == 2:
+                who[kind] = who[kind][::-1]
+                if kind == "spmv":
+                    who["k51"] = who["spmv"]
+        g = {w: geoms_of(sv, (w,))[0] for w in set(sum(who.values(), ()))}
+        geo.append((g, pick, who))
 
-    def dot(ws, u, v):
+    def dot(kind, u, v, slot=None):
         vals = []
-        for g, lo, hi in geo:
-            parts = np.concatenate([dot_parts(g[w], u[lo:hi], v[lo:hi]) for w in ws])
+        for g, pick, who in geo:
+            pu = pick(u)
+            pv = pu if v is u else pick(v)
+            parts = np.concatenate([dot_parts(g[w], pu, pv) for w in who[kind]])
             vals.append(tree_sum(parts))
+        if sums is not None and slot:
+            sums[slot] = vals
         return tree_sum(vals)
 
     x = np.array(x0, dtype=np.float64, copy=True)
@@ -248,34 +316,34 @@ def twin_solve_slabs(slabs, plan, valA, irow, jcol, b, x0, tol, itmax, hist_cap=
     P = R.copy()
     it = 0
     restarts = 0
-    bnorm = np.sqrt(dot((1,), b, b))                         # k_residual
+    bnorm = np.sqrt(dot("res", b, b, "BB"))                  # k_residual
     if bnorm == 0.0:
         return x, 0, hs, hr, 0
-    rr0 = dot((1,), R, R0)                                   # k_residual: R.R
+    rr0 = dot("res", R, R0, "RR_INIT")                       # k_residual: R.R
     while True:
         if it > itmax:
             break
         it += 1
         AP = spmv_csr(valA, irow, jcol, P)
-        alpha = rr0 / dot(spmv_w if it == 1 else k51_w, AP, R0)   # K1 (or K5-in-K1 of the previous iteration)
+        alpha = rr0 / dot("spmv" if it == 1 else "k51", AP, R0, "D1")   # K1 (or K5-in-K1 of the previous iteration)
         S = R - alpha * AP
-        nrm = np.sqrt(dot(ss_w, S, S))                       # K2 (or K2-in-K3)
+        nrm = np.sqrt(dot("ss", S, S, "SS"))                 # K2 (or K2-in-K3)
         if it <= hist_cap:
             hs[it - 1] = nrm
         if nrm / bnorm < tol:
             x = x + alpha * P
             break
         AS = spmv_csr(valA, irow, jcol, S)
-        omega = dot(spmv_w, AS, S) / dot(spmv_w, AS, AS)     # K3
+        omega = dot("spmv", AS, S, "D2") / dot("spmv", AS, AS, "D3")   # K3
         x = (x + alpha * P) + omega * S
         R = S - omega * AS
-        rr = dot(k4_w, R, R)                                 # K4
+        rr = dot("k4", R, R, "RR")                           # K4
         nrm = np.sqrt(rr)
         if it <= hist_cap:
             hr[it - 1] = nrm
         if nrm / bnorm < tol:
             break
-        rr0_new = dot(k4_w, R, R0)                           # K4
+        rr0_new = dot("k4", R, R0, "RR0N")                   # K4
         beta = (alpha / omega) * rr0_new / rr0
         P = R + beta * (P - omega * AP)
         if abs(rr0_new) / bnorm < tol:                       # src/solvers.f90:47-49
