@@ -245,6 +245,7 @@ void ec3d_free_matrix(ec3d_ctx *c)
     ec3d_free_rhs(c);
     ec3d_free_output(c);
     ec3d_mg_free(c);
+    ec3d_guess_free(c); // the pairs are a statement about this matrix; the depth stays
     c->poisson_full = false;
     c->from_csr = false;
     c->precond_grid[0] = c->precond_grid[1] = c->precond_grid[2] = 0;
@@ -1052,6 +1053,7 @@ extern "C" int ec3d_place_vectors(ec3d_handle c, int32_t candidates)
     }
     EC3D_HIP(hipSetDevice(c->device));
     EC3D_HIP(hipStreamSynchronize(c->stream));
+    if ((rc = ec3d_guess_clear(c))) return rc;
     return place_vectors(c, candidates, true);
 }
 

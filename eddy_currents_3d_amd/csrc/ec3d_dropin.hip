@@ -23,6 +23,9 @@ struct DropIn {
     ec3d_multi_handle multi = nullptr;
     bool multi_has_matrix = false;
     int ngpu = -1;
+    // EC3D_GUESS_HISTORY=N (read once, beside EC3D_NGPU): ec3d_set_guess_history(N) on the single-GPU handle -- every call
+    // starts from the projection onto up to N earlier solutions of the cached matrix; ignored with EC3D_NGPU > 1
+    int guess = 0;
     const void *valA = nullptr, *irow = nullptr, *jcol = nullptr;
     int64_t n = 0, nnz = 0;
     uint64_t sig = 0, quick = 0;
@@ -106,6 +109,7 @@ extern "C" void sprsbcgstabwr_(double *valA, int32_t *irow, int32_t *jcol, int32
     if (g_drop.ngpu < 0) {
         g_drop.ngpu = 1;
         if (const char *e = getenv("EC3D_NGPU")) g_drop.ngpu = std::max(1, atoi(e));
+        if (const char *e = getenv("EC3D_GUESS_HISTORY")) g_drop.guess = atoi(e);
     }
     if (g_drop.ngpu > 1 && !g_drop.multi) {
         std::vector<int32_t> devs;
@@ -131,6 +135,7 @@ extern "C" void sprsbcgstabwr_(double *valA, int32_t *irow, int32_t *jcol, int32
         int dev = 0;
         if (const char *e = getenv("EC3D_DEVICE")) dev = atoi(e);
         if (ec3d_create(&g_drop.ctx, dev)) die("ec3d_create");
+        if (g_drop.guess && ec3d_set_guess_history(g_drop.ctx, g_drop.guess)) die("EC3D_GUESS_HISTORY");
     }
     const int64_t nn = *n, nnz = (int64_t)irow[nn] - 1;
     const uint64_t quick = sample_signature(valA, jcol, nnz);
@@ -145,6 +150,7 @@ extern "C" void sprsbcgstabwr_(double *valA, int32_t *irow, int32_t *jcol, int32
             int dev = 0;
             if (const char *e = getenv("EC3D_DEVICE")) dev = atoi(e);
             if (ec3d_create(&g_drop.ctx, dev)) die("ec3d_create");
+            if (g_drop.guess && ec3d_set_guess_history(g_drop.ctx, g_drop.guess)) die("EC3D_GUESS_HISTORY");
         }
     };
     // The solve on whatever device matrix is in place: b and x go up, the iteration runs, x comes back ONLY if

@@ -320,6 +320,22 @@ struct IterCursor {
     void forget_ap() { ap_valid_for = 0; } // the next stage 1 launches K1 on its own (ec3d_time_kernel)
 };
 
+// ec3d_set_guess_history (ec3d_guess.hip): the pairs (Q_i, A Q_i) a solve is started from.  Library-owned vectors of n_pad
+// doubles -- no ghosts: no stencil reads them -- outside the work vectors' block, allocated by the first solve after the depth
+// was set; pair i (oldest first) lives in slot (head + i) % depth.  The depth belongs to the handle, the pairs to the matrix.
+struct GuessHistory {
+    int depth = 0;       // m: 0 = off
+    int k = 0, head = 0; // pairs stored, slot of the oldest
+    std::vector<DevBuf<double>> q, aq;
+    DevBuf<double> xs;   // X as the solve found it
+    DevBuf<double> part; // per-workgroup partials, (EC3D_GUESS_MAX_DEPTH + 1) slots of wgs
+    DevBuf<double> scal; // the solve's scalars (GS_* in ec3d_guess.hip) ...
+    PinnedBuf<double> host; // ... and where the one copy per solve lands
+    int64_t len = 0;     // doubles per vector (0: nothing allocated)
+    int wgs = 0;         // workgroups of the streaming launches
+    ec3d_guess_info last{}; // what ec3d_get_guess_history reports
+};
+
 struct ec3d_ctx {
     int device = 0;
     hipStream_t stream = nullptr;         // the stream every launch goes to
@@ -480,6 +496,7 @@ struct ec3d_ctx {
     ec3d_mg *mg = nullptr; // ec3d_set_preconditioner(EC3D_PRECOND_MG): solves run the preconditioned iteration
     int precond_precision = 0; // EC3D_PRECOND_FP64 / _FP32: what the next ec3d_set_preconditioner builds (ec3d_set_precond_precision)
     int precond_coarsening = 0; // EC3D_COARSEN_REDISCRETIZE / _AGGREGATE: likewise (ec3d_set_precond_coarsening)
+    GuessHistory guess;
     ec3d_ctx() = default;
     ~ec3d_ctx(); // ec3d_context.hip: the hierarchy goes (ec3d_mg_free), then every owner above, last declared first
 };
@@ -697,6 +714,12 @@ int ec3d_mg_chunk(const ec3d_ctx *c);             // iterations per poll of the 
 void ec3d_mg_launch_iteration(ec3d_ctx *c, int it); // one preconditioned iteration (after ec3d_launch_begin)
 // ec3d_format.cpp / ec3d_context.hip: dictionary compression of the bands
 int ec3d_build_dictionary_host(HostMatrix &M);
+// ec3d_guess.hip: the history of earlier solutions around a solve (solve_core, when guess.depth > 0)
+void ec3d_guess_free(ec3d_ctx *c);  // the pairs and their memory go (a new matrix, a new depth); the depth stays
+int ec3d_guess_clear(ec3d_ctx *c);  // no pair stored, the vectors zero again
+int ec3d_guess_project(ec3d_ctx *c, const MatView &A);            // in front of ec3d_launch_begin
+int ec3d_guess_note_setup(ec3d_ctx *c);                           // behind it
+int ec3d_guess_update(ec3d_ctx *c, const MatView &A, bool store); // behind the solve and ec3d_flush_x; one read-back
 // ec3d_output.hip
 void ec3d_free_output(ec3d_ctx *c);
 // ec3d_rhs.hip

@@ -272,7 +272,10 @@ static int solve_core(ec3d_ctx *c, double tol, int32_t itmax, int32_t *iter, dou
     const int64_t total = std::max<int64_t>(0, (int64_t)itmax + 1); // src/solvers.f90:25-29
     int rc = ensure_hist(c, hist_host ? std::min<int64_t>(hist_cap, total) : 0);
     if (rc) return rc;
+    const bool guess = c->guess.depth > 0; // ec3d_set_guess_history: X moved along earlier solutions first (ec3d_guess.hip)
+    if (guess && (rc = ec3d_guess_project(c, A))) return rc;
     if ((rc = ec3d_launch_begin(c, A, tol))) return rc;
+    if (guess && (rc = ec3d_guess_note_setup(c))) return rc;
     (void)ec3d_run_open(c, 1, total); // the itmax exit: the last iteration applies what is pending
 
     // iterations per poll: about 0.4 ms of device work, so an exit is noticed within ~1 ms
@@ -316,6 +319,8 @@ static int solve_core(ec3d_ctx *c, double tol, int32_t itmax, int32_t *iter, dou
             else ec3d_print_rnorm(fin.rnorm);
         }
     }
+    // whichever exit it took: the step this solve made joins the history (not after ||b|| = 0, which moved nothing)
+    if (guess && (rc = ec3d_guess_update(c, A, fin.stop_iter != 0))) return rc;
     if (hist_host && c->hist_cap > 0)
         EC3D_HIP(hipMemcpy(hist_host, c->hist, (size_t)c->hist_cap * 2 * sizeof(double), hipMemcpyDeviceToHost));
     return 0;

@@ -24,7 +24,8 @@ module ec3d_hip
               ec3d_set_u_rhs, EC3D_U_RHS_REFERENCE, EC3D_U_RHS_ALL, &
               ec3d_set_precond_precision, ec3d_get_precond_precision, EC3D_PRECOND_FP64, EC3D_PRECOND_FP32, &
               ec3d_set_precond_coarsening, ec3d_get_precond_coarsening, EC3D_COARSEN_REDISCRETIZE, EC3D_COARSEN_AGGREGATE, &
-              ec3d_set_precond_grid, ec3d_get_precond_grid, ec3d_domain_integral, ec3d_domain_integrals
+              ec3d_set_precond_grid, ec3d_get_precond_grid, ec3d_domain_integral, ec3d_domain_integrals, &
+              ec3d_set_guess_history, ec3d_get_guess_history, ec3d_guess_info, EC3D_GUESS_MAX_DEPTH
 
     integer(c_int), parameter :: EC3D_VEC_X = 0, EC3D_VEC_B = 1   ! Uaf, Jaf
     integer(c_int), parameter :: EC3D_PRECOND_NONE = 0, EC3D_PRECOND_MG = 1   ! ec3d_set_preconditioner
@@ -32,6 +33,14 @@ module ec3d_hip
     integer(c_int), parameter :: EC3D_U_RHS_REFERENCE = 0, EC3D_U_RHS_ALL = 1   ! ec3d_set_u_rhs
     integer(c_int32_t), parameter :: EC3D_PRECOND_FP64 = 0, EC3D_PRECOND_FP32 = 1   ! ec3d_set_precond_precision
     integer(c_int32_t), parameter :: EC3D_COARSEN_REDISCRETIZE = 0, EC3D_COARSEN_AGGREGATE = 1   ! ec3d_set_precond_coarsening
+
+    integer(c_int32_t), parameter :: EC3D_GUESS_MAX_DEPTH = 8   ! ec3d_set_guess_history
+
+    ! what ec3d_get_guess_history reports of the last solve (ec3d_guess_info of include/ec3d_hip.h)
+    type, bind(C) :: ec3d_guess_info
+        integer(c_int32_t) :: depth, stored, used, kept
+        real(c_double) :: res_before, res_after, coef(EC3D_GUESS_MAX_DEPTH)
+    end type
 
     ! one record of ec3d_domain_integrals (ec3d_domain_integral of include/ec3d_hip.h)
     type, bind(C) :: ec3d_domain_integral
@@ -239,6 +248,19 @@ module ec3d_hip
             import :: c_ptr, c_int, c_int32_t
             type(c_ptr), value :: h
             integer(c_int32_t), intent(out) :: dims(3)
+        end function
+        ! start every solve from the projection onto up to `depth` earlier solutions of the matrix (0 = off, the default;
+        ! include/ec3d_hip.h): 2 for a depth outside 0 .. EC3D_GUESS_MAX_DEPTH, 4 on a z-slab
+        integer(c_int) function ec3d_set_guess_history(h, depth) bind(C, name="ec3d_set_guess_history")
+            import :: c_ptr, c_int, c_int32_t
+            type(c_ptr), value :: h
+            integer(c_int32_t), value :: depth
+        end function
+        ! of the last solve: pairs projected on, the new pair stored / discarded / the history cleared, the residuals
+        integer(c_int) function ec3d_get_guess_history(h, info) bind(C, name="ec3d_get_guess_history")
+            import :: c_ptr, c_int, ec3d_guess_info
+            type(c_ptr), value :: h
+            type(ec3d_guess_info), intent(out) :: info
         end function
         ! U rows ec3d_rhs_step gives their right-hand side with several conducting domains (include/ec3d_hip.h)
         integer(c_int) function ec3d_set_u_rhs(h, rule) bind(C, name="ec3d_set_u_rhs")

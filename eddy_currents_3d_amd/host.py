@@ -339,7 +339,7 @@ class _SourcesAhead:
 
 def run(model: vxc.VxcModel, solver, steps: int | None = None, out_dir: str | None = None, on_step=None,
         on_rhs=None, on_solved=None, write_output=None, overlap_output: bool = True, on_fields=None, on_written=None,
-        precond: str | None = None, u_rhs: str | None = None, integrals: bool = False):
+        precond: str | None = None, u_rhs: str | None = None, integrals: bool = False, guess_history: int | None = None):
     """The reference's run of ``model`` on ``solver`` (an EC3DSolver): assemble, then step until T >= stop (or
     ``steps`` steps).  Returns a list of per-step dicts (T, iter).  ``out_dir``: write ``field_N.vtk`` there at
     the reference's output cadence.  Hooks, all ``(k, solver, info)``: ``on_rhs`` when Jaf (B) of step k is
@@ -360,7 +360,15 @@ def run(model: vxc.VxcModel, solver, steps: int | None = None, out_dir: str | No
     before the assembly -- which U rows get their right-hand side with several conducting domains; None leaves the
     handle's rule (default "reference", src/EC3D.f90:374-392) as it is.  ``integrals``: ``info["integrals"]`` of every
     step holds solver.domain_integrals(delta) -- Joule loss and Lorentz force per conducting domain --, taken right
-    after the post-update and before ``on_step``; one handle only (an EC3DMulti raises ValueError)."""
+    after the post-update and before ``on_step``; one handle only (an EC3DMulti raises ValueError).
+    ``guess_history`` (0 .. 8): solver.set_guess_history(N) before the assembly -- every step's solve starts from the
+    projection onto up to N earlier steps' solutions; ``info["guess"]`` of every step then holds
+    solver.guess_history().  None leaves the handle's depth as it is; one handle only (an EC3DMulti raises ValueError)."""
+    if guess_history is not None and not hasattr(solver, "set_guess_history"):
+        raise ValueError("guess_history needs an EC3DSolver: the history's sums are not available on the z-slabs of an "
+                         "EC3DMulti")
+    if guess_history is not None:
+        solver.set_guess_history(guess_history)
     if integrals and not hasattr(solver, "domain_integrals"):
         raise ValueError("integrals=True needs an EC3DSolver: the per-domain integrals are not available on the "
                          "z-slabs of an EC3DMulti")
@@ -390,7 +398,7 @@ def run(model: vxc.VxcModel, solver, steps: int | None = None, out_dir: str | No
     log = []
     try:
         log = _time_loop(solver, t, prog, (sdx, sdy, sdz), conducting, out_dir, pipe, steps, on_step, on_rhs, on_solved,
-                         write_output, on_fields, on_written, DT, Time, Nout, T, Ntime, Nprint, Npoint, integrals)
+                         write_output, on_fields, on_written, DT, Time, Nout, T, Ntime, Nprint, Npoint, integrals, guess=bool(guess_history))
     finally:
         if pipe is not None:
             pipe.finish()
@@ -398,7 +406,7 @@ def run(model: vxc.VxcModel, solver, steps: int | None = None, out_dir: str | No
 
 
 def _time_loop(solver, t, prog, dims, conducting, out_dir, pipe, steps, on_step, on_rhs, on_solved, write_output,
-               on_fields, on_written, DT, Time, Nout, T, Ntime, Nprint, Npoint, integrals=False):
+               on_fields, on_written, DT, Time, Nout, T, Ntime, Nprint, Npoint, integrals=False, guess=False):
     sdx, sdy, sdz = dims
     log = []
     ahead = _SourcesAhead(prog, T, DT, Time, steps)
@@ -411,6 +419,8 @@ def _time_loop(solver, t, prog, dims, conducting, out_dir, pipe, steps, on_step,
                 on_rhs(len(log), solver, info)
             it, _ = solver.solve_resident(t["tol"], t["itmax"])
             info["iter"] = it
+            if guess:
+                info["guess"] = solver.guess_history()
             if on_solved is not None:
                 on_solved(len(log), solver, info)
             solver.post_update()

@@ -1,13 +1,14 @@
 """Run a VoxCad ``.vxc`` model the way the reference program does, on one MI355X.
 
-    python -m eddy_currents_3d_amd.run model.vxc [--steps N] [--out DIR] [--device D] [--integrals FILE]
+    python -m eddy_currents_3d_amd.run model.vxc [--steps N] [--out DIR] [--device D] [--integrals FILE] [--guess-history N]
     python -m torch.distributed.run --nproc-per-node G -m eddy_currents_3d_amd.run model.vxc ...   (G GPUs)
 
 Reads the file (eddy_currents_3d_amd/vxc.py), assembles the A-V system on the device, and runs the
 reference's time loop (eddy_currents_3d_amd/host.py) with the fields resident in HBM; ``field_N.vtk`` files
 and ``src_N.vtk`` files go to ``--out`` (default: the ``dir=`` name of the model's solver line, as the
 reference does).  ``--integrals FILE``: Joule loss [W] and Lorentz force [N] of every conducting domain after every
-step, as CSV (one GPU only).
+step, as CSV (one GPU only).  ``--guess-history N``: start every step's solve from the projection onto up to N earlier
+steps' solutions (EC3DSolver.set_guess_history; default 0 = off, one GPU only).
 """
 from __future__ import annotations
 
@@ -45,6 +46,9 @@ def build_parser():
     ap.add_argument("--integrals", metavar="FILE", default=None,
                     help="write Joule loss and Lorentz force per conducting domain and time step to this CSV file "
                          "(" + INTEGRALS_HEADER + "; one GPU only)")
+    ap.add_argument("--guess-history", type=int, default=0, metavar="N", choices=range(0, 9),
+                    help="start every step's solve from the projection onto up to N (0 .. 8) earlier steps' solutions; "
+                         "0 (default): off, the reference's warm start from the previous step alone (one GPU only)")
     return ap
 
 
@@ -80,6 +84,8 @@ def main(argv=None):
 
     if world > 1 and a.precond != "none":
         ap.error(f"--precond {a.precond} runs on one GPU only; the multi-rank z-slab path has no preconditioner")
+    if world > 1 and a.guess_history:
+        ap.error("--guess-history runs on one GPU only; the history's sums would need every rank's")
     if world > 1 and a.u_rhs != "reference":
         ap.error(f"--u-rhs {a.u_rhs} runs on one GPU only; z-slabs take one conducting domain")
     if world > 1:   # one process per GPU: z-slabs, halo exchange and reductions over RCCL
@@ -101,7 +107,7 @@ def main(argv=None):
             with EC3DSolver(device=a.device) as s:
                 log = host.run(model, s, steps=a.steps, out_dir=out_dir, on_step=on_step,
                                precond=None if a.precond == "none" else a.precond, u_rhs=a.u_rhs,
-                               integrals=csv is not None)
+                               integrals=csv is not None, guess_history=a.guess_history or None)
                 n = s.n
         finally:
             if csv is not None:

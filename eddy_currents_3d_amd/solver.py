@@ -47,6 +47,12 @@ class DomainIntegral(C.Structure):
                 ("joule_w", C.c_double), ("force_n", C.c_double * 3)]
 
 
+class GuessInfo(C.Structure):
+    """ec3d_guess_info of include/ec3d_hip.h."""
+    _fields_ = [("depth", C.c_int32), ("stored", C.c_int32), ("used", C.c_int32), ("kept", C.c_int32),
+                ("res_before", C.c_double), ("res_after", C.c_double), ("coef", C.c_double * 8)]
+
+
 class CsrProbe(C.Structure):
     _fields_ = [("structured", C.c_int32), ("sdx", C.c_int32), ("sdy", C.c_int32), ("sdz", C.c_int32),
                 ("n_cond", C.c_int32), ("classes", C.c_int32), ("plane_pitch", C.c_int32)]
@@ -78,7 +84,7 @@ EXPORTS = ["sprsbcgstabwr_", "ec3d_invalidate", "ec3d_create", "ec3d_destroy", "
            "ec3d_set_preconditioner", "ec3d_get_preconditioner", "ec3d_precond_apply", "ec3d_set_u_rhs",
            "ec3d_set_precond_precision", "ec3d_get_precond_precision", "ec3d_set_precond_coarsening",
            "ec3d_get_precond_coarsening", "ec3d_set_precond_grid", "ec3d_get_precond_grid",
-           "ec3d_domain_integrals", "ec3d_get_class_runs"]
+           "ec3d_domain_integrals", "ec3d_get_class_runs", "ec3d_set_guess_history", "ec3d_get_guess_history"]
 U_RHS = {"reference": 0, "all": 1}   # EC3D_U_RHS_* of include/ec3d_hip.h
 PRECOND = {"none": 0, "mg": 1, "block-mg": 2}   # EC3D_PRECOND_* of include/ec3d_hip.h
 PRECOND_E_MATRIX, PRECOND_E_COARSE = 20, 21   # ec3d_set_preconditioner's refusals
@@ -174,6 +180,8 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.ec3d_get_precond_coarsening.argtypes = [hp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), hp]
     L.ec3d_set_precond_grid.argtypes = [hp, C.c_int32, C.c_int32, C.c_int32]
     L.ec3d_get_precond_grid.argtypes = [hp, hp]
+    L.ec3d_set_guess_history.argtypes = [hp, C.c_int32]
+    L.ec3d_get_guess_history.argtypes = [hp, C.POINTER(GuessInfo)]
     L.ec3d_export_csr.argtypes = [hp, C.POINTER(C.c_int32), C.POINTER(C.c_int64), hp, hp, hp]
     L.ec3d_get_cel_bnd.argtypes = [hp, C.c_int, C.POINTER(C.c_int32), hp]
     L.ec3d_get_reduction_geometry.argtypes = [hp, C.c_int, C.POINTER(Geom)]
@@ -656,6 +664,23 @@ class EC3DSolver:
         dims = np.zeros(3, np.int32)
         _chk(self.L, self.L.ec3d_get_precond_grid(self.h, dims.ctypes.data), "ec3d_get_precond_grid")
         return tuple(int(a) for a in dims) if dims.any() else None
+
+    def set_guess_history(self, depth: int):
+        """Start every solve from the projection onto up to `depth` (0 .. 8; 0 = off, the default) earlier solutions of
+        this matrix (ec3d_set_guess_history of include/ec3d_hip.h).  The depth stays with the handle; a new matrix,
+        place_vectors and a change of the depth drop the stored pairs.  EC3DError with .status 2 for a depth out of
+        range, 4 on a z-slab."""
+        _chk(self.L, self.L.ec3d_set_guess_history(self.h, int(depth)), "ec3d_set_guess_history")
+
+    def guess_history(self):
+        """Of the last solve: dict(depth, stored, used, kept, res_before, res_after, coef) -- pairs held now, pairs the
+        projection ran on, 1 / 0 / -1 = the new pair was stored / discarded / the history cleared, ||b - A x|| / ||b||
+        in front of and behind the projection, and its `used` coefficients."""
+        g = GuessInfo()
+        _chk(self.L, self.L.ec3d_get_guess_history(self.h, C.byref(g)), "ec3d_get_guess_history")
+        return dict(depth=int(g.depth), stored=int(g.stored), used=int(g.used), kept=int(g.kept),
+                    res_before=float(g.res_before), res_after=float(g.res_after),
+                    coef=np.array(g.coef[:max(int(g.used), 0)], dtype=np.float64))
 
     def _coarsening_setting(self):
         setting = C.c_int32(0)

@@ -311,6 +311,38 @@ int ec3d_get_precond_coarsening(ec3d_handle h, int32_t *setting, int32_t *in_use
  * ec3d_get_precond_grid: dims[0..2] = the grid now set, zeros when none. */
 int ec3d_set_precond_grid(ec3d_handle h, int32_t sdx, int32_t sdy, int32_t sdz);
 int ec3d_get_precond_grid(ec3d_handle h, int32_t *dims /* 3; zeros when none */);
+/* A solve started from the projection onto earlier solutions (opt-in; no reference counterpart: the reference starts
+ * from the previous x and nothing else).  With depth m in 1 .. EC3D_GUESS_MAX_DEPTH the handle keeps k <= m pairs
+ * (Q_i, A Q_i), oldest first, the A Q_i orthonormal.  In front of every ec3d_solve / ec3d_solve_resident:
+ * R = B - A X, c_i = (A Q_i).R, X = X + c_1 Q_1 + ... + c_k Q_k, in that order, every term a rounded product and a
+ * rounded sum (Fischer's projection in GCR form: A need not be symmetric); with ||B|| = 0 every c_i is 0, X keeps its
+ * bits, iter = 0 and nothing is stored.  Then the solve runs as without a history -- iteration, exits, restart rule and
+ * kernels unchanged -- from the new X.  Behind it, whichever exit it took: Q_new = X - X_start (the X the call found),
+ * A Q_new by the handle's own SpMV, two passes of classical Gram-Schmidt of A Q_new against the stored A Q_i (Q_new gets
+ * the same combination of the Q_i), both scaled by 1 / ||A Q_new||, the oldest pair dropped when k = m.  The new pair is
+ * discarded when ||A Q_new|| behind the passes is <= EC3D_GUESS_MIN_NEW times its value before them (noise of the
+ * inexact solve, or a null direction of A), and the whole history is cleared when any of these numbers is not finite:
+ * a solve that went NaN leaves no trace.  The pairs belong to the matrix: ec3d_set_matrix_csr, every ec3d_assemble*,
+ * ec3d_place_vectors and a call that changes the depth clear them; ec3d_upload, ec3d_rhs_step, ec3d_post_update and
+ * ec3d_set_preconditioner do not (a preconditioned solve uses them unchanged).  The depth belongs to the handle and
+ * outlives new matrices.  Memory: 2 m + 1 library-owned vectors of n_pad doubles (the pairs and X_start), allocated by
+ * the first solve after the depth was set, never part of the work vectors (ec3d_adopt_vectors handles work); one host
+ * read-back of the deciding scalars per solve.  depth = 0 (default): a solve launches and allocates nothing more and
+ * returns the same bits as before.  A depth outside 0 .. EC3D_GUESS_MAX_DEPTH returns 2, a z-slab or a slab of
+ * ec3d_multi 4 (the sums would need every rank's), the handle unchanged either way.
+ * ec3d_get_guess_history, of the last solve: used = pairs the projection ran on; kept = 1 the new pair was stored,
+ * 0 discarded (or ||B|| = 0), -1 the history was cleared; stored = pairs held now; coef[i] = c_i (i < used);
+ * res_before / res_after = ||B - A X|| / ||B|| in front of and behind the projection, the latter from the solve's own
+ * set-up. */
+#define EC3D_GUESS_MAX_DEPTH 8
+#define EC3D_GUESS_MIN_NEW 1e-6
+int ec3d_set_guess_history(ec3d_handle h, int32_t depth);
+typedef struct {
+    int32_t depth, stored, used, kept;
+    double res_before, res_after;
+    double coef[EC3D_GUESS_MAX_DEPTH];
+} ec3d_guess_info;
+int ec3d_get_guess_history(ec3d_handle h, ec3d_guess_info *info);
 
 /* ------------------------------------------------------------------------------------------
  * 2b. Multi-rank building blocks (z-slab decomposition, one process per GPU).
