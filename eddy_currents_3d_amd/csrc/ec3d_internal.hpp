@@ -302,6 +302,31 @@ struct DomIntegrals {
     PinnedBuf<double> host;     // [ndom][4] where the call's one copy lands
 };
 
+// Tables of ec3d_domain_linkage: the same for the domains that hold cells outside the conductors (the coils, the plain
+// bodies and the air).  Built on the host at assembly; the device buffers are made by the first call, which frees the
+// host lists.
+struct DomLinkage {
+    bool built = false;
+    int ndom = 0;
+    int64_t nchunk = 0;
+    std::vector<int32_t> id;    // [ndom] geoPHYS id
+    std::vector<int64_t> cells; // [ndom] non-conducting cells of the domain
+    std::vector<int32_t> cell_host, chunk_host, dom_chunk_host; // until the first call
+    DevBuf<int32_t> cell, chunk, dom_chunk;
+    DevBuf<double> partial;     // [nchunk][4] sums of A.J, Jx, Jy, Jz per chunk
+    DevBuf<double> sums;        // [ndom][4]
+    PinnedBuf<double> host;
+};
+
+// What ec3d_field_energy keeps, made by its first call: one byte per device cell (1 inside a conductor; none without
+// conductors), the workgroups' partials and the five sums.
+struct FieldEnergy {
+    int wgs = 0;
+    DevBuf<uint8_t> cond;
+    DevBuf<double> part, sums;
+    PinnedBuf<double> host;
+};
+
 // The host's cursor of a run of iterations.  The device state is addressed by the iteration number (rr0[it & 1], AP in
 // apbuf[it & 1], P and S in their rings), so the host keeps in step with it here and nowhere else: ec3d_run_reset starts
 // a run, ec3d_run_open says which iterations a call launches, ec3d_after_s / ec3d_after_p advance it behind a launch
@@ -457,6 +482,8 @@ struct ec3d_ctx {
     DevBuf<double> src_val;
     int64_t src_cap = 0;
     DomIntegrals dom;              // per-domain integrals (ec3d_integrals.hip); freed with cond_cell
+    DomLinkage link;               // ... of the non-conducting domains (ec3d_domain_linkage)
+    FieldEnergy energy;            // ec3d_field_energy's buffers
     // plain band streams whose placement was probed (place_bands): kept across a change of matrix of the same size, so
     // the probe runs once per handle and size, and what it found (candidate times in us, the one kept)
     DevBuf<double> placed_bands;

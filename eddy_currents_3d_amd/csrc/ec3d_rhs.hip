@@ -146,7 +146,9 @@ int ec3d_setup_rhs(ec3d_ctx *c, int64_t nCells, const int8_t *geoPHYS, const int
         }
     }
     c->bnd_off[6] = (int64_t)lists.size();
-    if (c->n_cond == 0) return 0;
+    // the lists of ec3d_domain_integrals and ec3d_domain_linkage: undivided handles only (a z-slab holds part of a domain)
+    const bool undivided = !c->in_multi && nCells == (int64_t)c->sdx * c->sdy * c->sdz;
+    if (c->n_cond == 0) return undivided ? ec3d_setup_integrals(c, nCells, geoPHYS, geoPHYS_C, valPHYS, nsub_glob) : 0;
     EC3D_HIP(c->cond_cell.alloc(cell.size()));
     EC3D_HIP(c->cond_a.alloc(a.size()));
     EC3D_HIP(c->rhs_tmp.alloc((size_t)3 * cell.size()));
@@ -156,10 +158,7 @@ int ec3d_setup_rhs(ec3d_ctx *c, int64_t nCells, const int8_t *geoPHYS, const int
     if (!lists.empty())
         EC3D_HIP(hipMemcpyAsync(c->bnd_list, lists.data(), lists.size() * 4, hipMemcpyHostToDevice, c->stream));
     EC3D_HIP(hipStreamSynchronize(c->stream));
-    // the list of ec3d_domain_integrals: undivided handles only (a z-slab holds part of a domain)
-    if (!c->in_multi && nCells == (int64_t)c->sdx * c->sdy * c->sdz)
-        return ec3d_setup_integrals(c, nCells, geoPHYS, geoPHYS_C, valPHYS, nsub_glob);
-    return 0;
+    return undivided ? ec3d_setup_integrals(c, nCells, geoPHYS, geoPHYS_C, valPHYS, nsub_glob) : 0;
 }
 
 static int need_grid(ec3d_ctx *c, const char *who)

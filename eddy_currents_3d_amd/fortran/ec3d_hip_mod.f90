@@ -25,6 +25,7 @@ module ec3d_hip
               ec3d_set_precond_precision, ec3d_get_precond_precision, EC3D_PRECOND_FP64, EC3D_PRECOND_FP32, &
               ec3d_set_precond_coarsening, ec3d_get_precond_coarsening, EC3D_COARSEN_REDISCRETIZE, EC3D_COARSEN_AGGREGATE, &
               ec3d_set_precond_grid, ec3d_get_precond_grid, ec3d_domain_integral, ec3d_domain_integrals, &
+              ec3d_field_energy_info, ec3d_field_energy, ec3d_domain_link, ec3d_domain_linkage, &
               ec3d_set_guess_history, ec3d_get_guess_history, ec3d_guess_info, EC3D_GUESS_MAX_DEPTH
 
     integer(c_int), parameter :: EC3D_VEC_X = 0, EC3D_VEC_B = 1   ! Uaf, Jaf
@@ -47,6 +48,19 @@ module ec3d_hip
         integer(c_int32_t) :: domain, pad
         integer(c_int64_t) :: cells
         real(c_double) :: sigma, joule_w, force_n(3)
+    end type
+
+    ! what ec3d_field_energy returns (ec3d_field_energy_info of include/ec3d_hip.h)
+    type, bind(C) :: ec3d_field_energy_info
+        integer(c_int64_t) :: cells
+        real(c_double) :: energy_b, energy_axis(3), aj_source, aj_eddy
+    end type
+
+    ! one record of ec3d_domain_linkage (ec3d_domain_link of include/ec3d_hip.h)
+    type, bind(C) :: ec3d_domain_link
+        integer(c_int32_t) :: domain, pad
+        integer(c_int64_t) :: cells
+        real(c_double) :: linkage, jsum(3)
     end type
 
     interface
@@ -161,6 +175,24 @@ module ec3d_hip
             integer(c_int32_t), value :: cap
             integer(c_int32_t), intent(out) :: ndomains
             type(ec3d_domain_integral), intent(out) :: out(*)
+        end function
+        ! magnetic energy of the box [J] and the integral of A.J outside / inside the conductors [J] from the resident Uaf,
+        ! Jaf, one streaming pass on the device; call after ec3d_post_update
+        integer(c_int) function ec3d_field_energy(h, delta, out) bind(C, name="ec3d_field_energy")
+            import :: c_ptr, c_int, c_double, ec3d_field_energy_info
+            type(c_ptr), value :: h
+            real(c_double), intent(in) :: delta(*)
+            type(ec3d_field_energy_info), intent(out) :: out
+        end function
+        ! flux linkage psi*I [J] and the integral of J [A m] of every non-conducting domain (the air among them), ascending
+        ! domain id; cap and ndomains as in ec3d_domain_integrals
+        integer(c_int) function ec3d_domain_linkage(h, delta, cap, ndomains, out) bind(C, name="ec3d_domain_linkage")
+            import :: c_ptr, c_int, c_int32_t, c_double, ec3d_domain_link
+            type(c_ptr), value :: h
+            real(c_double), intent(in) :: delta(*)
+            integer(c_int32_t), value :: cap
+            integer(c_int32_t), intent(out) :: ndomains
+            type(ec3d_domain_link), intent(out) :: out(*)
         end function
         ! the same beside the next time step: _begin returns at once (field kernel + copy into a pinned buffer are
         ! enqueued), _wait blocks until that buffer has landed and returns C pointers to 3*ncells REAL(4) each

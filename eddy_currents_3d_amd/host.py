@@ -339,7 +339,8 @@ class _SourcesAhead:
 
 def run(model: vxc.VxcModel, solver, steps: int | None = None, out_dir: str | None = None, on_step=None,
         on_rhs=None, on_solved=None, write_output=None, overlap_output: bool = True, on_fields=None, on_written=None,
-        precond: str | None = None, u_rhs: str | None = None, integrals: bool = False, guess_history: int | None = None):
+        precond: str | None = None, u_rhs: str | None = None, integrals: bool = False, guess_history: int | None = None,
+        energy: bool = False):
     """The reference's run of ``model`` on ``solver`` (an EC3DSolver): assemble, then step until T >= stop (or
     ``steps`` steps).  Returns a list of per-step dicts (T, iter).  ``out_dir``: write ``field_N.vtk`` there at
     the reference's output cadence.  Hooks, all ``(k, solver, info)``: ``on_rhs`` when Jaf (B) of step k is
@@ -363,7 +364,13 @@ def run(model: vxc.VxcModel, solver, steps: int | None = None, out_dir: str | No
     after the post-update and before ``on_step``; one handle only (an EC3DMulti raises ValueError).
     ``guess_history`` (0 .. 8): solver.set_guess_history(N) before the assembly -- every step's solve starts from the
     projection onto up to N earlier steps' solutions; ``info["guess"]`` of every step then holds
-    solver.guess_history().  None leaves the handle's depth as it is; one handle only (an EC3DMulti raises ValueError)."""
+    solver.guess_history().  None leaves the handle's depth as it is; one handle only (an EC3DMulti raises ValueError).
+    ``energy``: ``info["energy"]`` of every step holds solver.field_energy(delta) -- the magnetic energy of the box and
+    the integral of A.J -- and ``info["linkage"]`` solver.domain_linkage(delta) -- the flux linkage of every
+    non-conducting domain --, taken where ``integrals`` is taken; one handle only (an EC3DMulti raises ValueError)."""
+    if energy and not hasattr(solver, "field_energy"):
+        raise ValueError("energy=True needs an EC3DSolver: the field energy and the flux linkages are not available on "
+                         "the z-slabs of an EC3DMulti")
     if guess_history is not None and not hasattr(solver, "set_guess_history"):
         raise ValueError("guess_history needs an EC3DSolver: the history's sums are not available on the z-slabs of an "
                          "EC3DMulti")
@@ -398,7 +405,8 @@ def run(model: vxc.VxcModel, solver, steps: int | None = None, out_dir: str | No
     log = []
     try:
         log = _time_loop(solver, t, prog, (sdx, sdy, sdz), conducting, out_dir, pipe, steps, on_step, on_rhs, on_solved,
-                         write_output, on_fields, on_written, DT, Time, Nout, T, Ntime, Nprint, Npoint, integrals, guess=bool(guess_history))
+                         write_output, on_fields, on_written, DT, Time, Nout, T, Ntime, Nprint, Npoint, integrals, guess=bool(guess_history),
+                         energy=energy)
     finally:
         if pipe is not None:
             pipe.finish()
@@ -406,7 +414,8 @@ def run(model: vxc.VxcModel, solver, steps: int | None = None, out_dir: str | No
 
 
 def _time_loop(solver, t, prog, dims, conducting, out_dir, pipe, steps, on_step, on_rhs, on_solved, write_output,
-               on_fields, on_written, DT, Time, Nout, T, Ntime, Nprint, Npoint, integrals=False, guess=False):
+               on_fields, on_written, DT, Time, Nout, T, Ntime, Nprint, Npoint, integrals=False, guess=False,
+               energy=False):
     sdx, sdy, sdz = dims
     log = []
     ahead = _SourcesAhead(prog, T, DT, Time, steps)
@@ -426,6 +435,9 @@ def _time_loop(solver, t, prog, dims, conducting, out_dir, pipe, steps, on_step,
             solver.post_update()
             if integrals:
                 info["integrals"] = solver.domain_integrals(t["delta"])
+            if energy:
+                info["energy"] = solver.field_energy(t["delta"])
+                info["linkage"] = solver.domain_linkage(t["delta"])
             if Ntime >= Nprint and Ntime != 0:               # :437-446
                 Nprint = Ntime + Nout
                 Npoint += 1
@@ -545,13 +557,16 @@ def _pwrite_all(fd, data, offset):
 
 
 def run_slabs(model: vxc.VxcModel, rank: int, world: int, device: int = 0, steps: int | None = None,
-              out_dir: str | None = None, on_step=None, overlap_output: bool = True):
+              out_dir: str | None = None, on_step=None, overlap_output: bool = True, energy: bool = False):
     """The same run on ``world`` GPUs, one process per GPU (torch.distributed initialised by the caller):
     z-slabs of the A-V system (eddy_currents_3d_amd/dist.py), every rank evaluates the (tiny) source program
     itself and keeps its part of the fields resident.  Output: every rank writes its own cells into field_N.vtk
     beside the next step's solve (_SlabOutputPipeline; the files are complete when this function returns, after a
     barrier); ``overlap_output=False``: the fields gathered on rank 0, which writes them inside the loop.  Returns the
-    per-step log (identical on all ranks)."""
+    per-step log (identical on all ranks).  ``energy=True`` raises ValueError before anything is assembled: a z-slab
+    holds only part of the box and of every domain (ec3d_field_energy, ec3d_domain_linkage)."""
+    if energy:
+        raise ValueError("energy=True runs on one GPU only: a z-slab holds only part of the box and of every domain")
     from .dist import HipAVSlabOps, SlabSolver, slab_bounds
     t = vxc.domain_tables(model)
     if t["dt"] is None or t["time"] is None:

@@ -1,6 +1,7 @@
 """Run a VoxCad ``.vxc`` model the way the reference program does, on one MI355X.
 
     python -m eddy_currents_3d_amd.run model.vxc [--steps N] [--out DIR] [--device D] [--integrals FILE] [--guess-history N]
+                                                 [--energy FILE]
     python -m torch.distributed.run --nproc-per-node G -m eddy_currents_3d_amd.run model.vxc ...   (G GPUs)
 
 Reads the file (eddy_currents_3d_amd/vxc.py), assembles the A-V system on the device, and runs the
@@ -8,7 +9,9 @@ reference's time loop (eddy_currents_3d_amd/host.py) with the fields resident in
 and ``src_N.vtk`` files go to ``--out`` (default: the ``dir=`` name of the model's solver line, as the
 reference does).  ``--integrals FILE``: Joule loss [W] and Lorentz force [N] of every conducting domain after every
 step, as CSV (one GPU only).  ``--guess-history N``: start every step's solve from the projection onto up to N earlier
-steps' solutions (EC3DSolver.set_guess_history; default 0 = off, one GPU only).
+steps' solutions (EC3DSolver.set_guess_history; default 0 = off, one GPU only).  ``--energy FILE``: magnetic energy of
+the box [J], the integral of A.J outside and inside the conductors [J] and the flux linkage psi*I [J] of every
+non-conducting domain after every step, as CSV, one line per step (one GPU only).
 """
 from __future__ import annotations
 
@@ -25,6 +28,19 @@ def integrals_rows(step, T, records):
     """CSV lines of one step's EC3DSolver.domain_integrals() records, floats at repr() precision."""
     return [",".join([str(int(step)), repr(float(T)), str(r["domain"]), str(r["cells"]), repr(float(r["joule_w"]))]
                      + [repr(float(f)) for f in r["force_n"]]) for r in records]
+
+
+ENERGY_HEADER = "step,T,energy_b,aj_source,aj_eddy"   # then linkage_<id> per domain of EC3DSolver.domain_linkage()
+
+
+def energy_header(linkage):
+    return ",".join([ENERGY_HEADER] + [f"linkage_{r['domain']}" for r in linkage])
+
+
+def energy_row(step, T, energy, linkage):
+    """The CSV line of one step's EC3DSolver.field_energy() and domain_linkage(), floats at repr() precision."""
+    return ",".join([str(int(step)), repr(float(T))] + [repr(float(energy[k])) for k in ("energy_b", "aj_source", "aj_eddy")]
+                    + [repr(float(r["linkage"])) for r in linkage])
 
 
 def build_parser():
@@ -46,6 +62,9 @@ def build_parser():
     ap.add_argument("--integrals", metavar="FILE", default=None,
                     help="write Joule loss and Lorentz force per conducting domain and time step to this CSV file "
                          "(" + INTEGRALS_HEADER + "; one GPU only)")
+    ap.add_argument("--energy", metavar="FILE", default=None,
+                    help="write the magnetic energy, the integral of A.J and the flux linkage of every non-conducting "
+                         "domain per time step to this CSV file (" + ENERGY_HEADER + ",linkage_<id>...; one GPU only)")
     ap.add_argument("--guess-history", type=int, default=0, metavar="N", choices=range(0, 9),
                     help="start every step's solve from the projection onto up to N (0 .. 8) earlier steps' solutions; "
                          "0 (default): off, the reference's warm start from the previous step alone (one GPU only)")
@@ -58,6 +77,8 @@ def main(argv=None):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1 and a.integrals:
         ap.error("--integrals runs on one GPU only; a z-slab holds only part of a conducting domain")
+    if world > 1 and a.energy:
+        ap.error("--energy runs on one GPU only; a z-slab holds only part of the box and of every domain")
 
     from . import EC3DSolver, host, vxc
     model = vxc.read_vxc(a.model)
@@ -75,10 +96,17 @@ def main(argv=None):
         csv = open(a.integrals, "w")
         csv.write(INTEGRALS_HEADER + "\n")
 
+    ecsv = open(a.energy, "w") if a.energy else None   # one line per step; the header goes out with the first
+
     def on_step(k, s, info):
         if csv is not None:
             csv.writelines(line + "\n" for line in integrals_rows(k, info["T"], info["integrals"]))
             csv.flush()
+        if ecsv is not None:
+            if k == 0:
+                ecsv.write(energy_header(info["linkage"]) + "\n")
+            ecsv.write(energy_row(k, info["T"], info["energy"], info["linkage"]) + "\n")
+            ecsv.flush()
         print(f"step {k:4d}  T={info['T']:.6g}  iter={info['iter']}"
               + (f"  -> field_{info['output']}.vtk" if "output" in info and out_dir else ""), flush=True)
 
@@ -107,11 +135,14 @@ def main(argv=None):
             with EC3DSolver(device=a.device) as s:
                 log = host.run(model, s, steps=a.steps, out_dir=out_dir, on_step=on_step,
                                precond=None if a.precond == "none" else a.precond, u_rhs=a.u_rhs,
-                               integrals=csv is not None, guess_history=a.guess_history or None)
+                               integrals=csv is not None, guess_history=a.guess_history or None,
+                               energy=ecsv is not None)
                 n = s.n
         finally:
             if csv is not None:
                 csv.close()
+            if ecsv is not None:
+                ecsv.close()
     wall = time.perf_counter() - t0
     its = sum(i["iter"] for i in log)
     print(f"{len(log)} steps, {its} solver iterations, n={n}, {wall:.2f} s wall "

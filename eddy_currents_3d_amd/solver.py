@@ -47,6 +47,18 @@ class DomainIntegral(C.Structure):
                 ("joule_w", C.c_double), ("force_n", C.c_double * 3)]
 
 
+class FieldEnergy(C.Structure):
+    """ec3d_field_energy_info of include/ec3d_hip.h."""
+    _fields_ = [("cells", C.c_int64), ("energy_b", C.c_double), ("energy_axis", C.c_double * 3),
+                ("aj_source", C.c_double), ("aj_eddy", C.c_double)]
+
+
+class DomainLink(C.Structure):
+    """ec3d_domain_link of include/ec3d_hip.h."""
+    _fields_ = [("domain", C.c_int32), ("pad", C.c_int32), ("cells", C.c_int64), ("linkage", C.c_double),
+                ("jsum", C.c_double * 3)]
+
+
 class GuessInfo(C.Structure):
     """ec3d_guess_info of include/ec3d_hip.h."""
     _fields_ = [("depth", C.c_int32), ("stored", C.c_int32), ("used", C.c_int32), ("kept", C.c_int32),
@@ -84,7 +96,7 @@ EXPORTS = ["sprsbcgstabwr_", "ec3d_invalidate", "ec3d_create", "ec3d_destroy", "
            "ec3d_set_preconditioner", "ec3d_get_preconditioner", "ec3d_precond_apply", "ec3d_set_u_rhs",
            "ec3d_set_precond_precision", "ec3d_get_precond_precision", "ec3d_set_precond_coarsening",
            "ec3d_get_precond_coarsening", "ec3d_set_precond_grid", "ec3d_get_precond_grid",
-           "ec3d_domain_integrals", "ec3d_get_class_runs", "ec3d_set_guess_history", "ec3d_get_guess_history"]
+           "ec3d_domain_integrals", "ec3d_field_energy", "ec3d_domain_linkage", "ec3d_get_class_runs", "ec3d_set_guess_history", "ec3d_get_guess_history"]
 U_RHS = {"reference": 0, "all": 1}   # EC3D_U_RHS_* of include/ec3d_hip.h
 PRECOND = {"none": 0, "mg": 1, "block-mg": 2}   # EC3D_PRECOND_* of include/ec3d_hip.h
 PRECOND_E_MATRIX, PRECOND_E_COARSE = 20, 21   # ec3d_set_preconditioner's refusals
@@ -193,6 +205,8 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.ec3d_vtk_fields.argtypes = [hp, _f64, hp, hp, hp, hp]
     L.ec3d_vtk_fields_begin.argtypes = [hp, _f64, C.c_int32, C.POINTER(C.c_int32)]
     L.ec3d_domain_integrals.argtypes = [hp, _f64, C.c_int32, C.POINTER(C.c_int32), C.POINTER(DomainIntegral)]
+    L.ec3d_field_energy.argtypes = [hp, _f64, C.POINTER(FieldEnergy)]
+    L.ec3d_domain_linkage.argtypes = [hp, _f64, C.c_int32, C.POINTER(C.c_int32), C.POINTER(DomainLink)]
     L.ec3d_vtk_fields_wait.argtypes = [hp, C.c_int32] + [C.POINTER(C.POINTER(C.c_float))] * 4 + [C.POINTER(C.c_int64)]
     L.ec3d_set_workgroups.argtypes = [hp, C.c_int32]
     L.ec3d_get_matrix_info.argtypes = [hp, C.POINTER(MatrixInfo)]
@@ -547,6 +561,31 @@ class EC3DSolver:
         _chk(self.L, self.L.ec3d_domain_integrals(self.h, d, n.value, C.byref(n), out), "ec3d_domain_integrals")
         return [dict(domain=int(r.domain), cells=int(r.cells), sigma=float(r.sigma), joule_w=float(r.joule_w),
                      force_n=np.array(r.force_n[:], np.float64)) for r in out[:n.value]]
+
+    def field_energy(self, delta):
+        """Magnetic energy of the box and the integral of A.J from the resident X, B (ec3d_field_energy), in float64,
+        summed on the device in a fixed order: dict(cells, energy_b [J], energy_axis (numpy array of 3: the x, y, z
+        parts of energy_b), aj_source [J] (outside the conductors), aj_eddy [J] (inside)).  Meaningful after
+        post_update of a step."""
+        r = FieldEnergy()
+        _chk(self.L, self.L.ec3d_field_energy(self.h, np.ascontiguousarray(delta, np.float64), C.byref(r)),
+             "ec3d_field_energy")
+        return dict(cells=int(r.cells), energy_b=float(r.energy_b), energy_axis=np.array(r.energy_axis[:], np.float64),
+                    aj_source=float(r.aj_source), aj_eddy=float(r.aj_eddy))
+
+    def domain_linkage(self, delta):
+        """Flux linkage of every non-conducting domain (the coils, the plain bodies and the air) from the resident X, B
+        (ec3d_domain_linkage).  A list, ascending domain id, of dict(domain, cells, linkage [J] (psi * I), jsum [A m],
+        numpy array of 3).  Meaningful after post_update of a step."""
+        d = np.ascontiguousarray(delta, np.float64)
+        n = C.c_int32(0)
+        _chk(self.L, self.L.ec3d_domain_linkage(self.h, d, 0, C.byref(n), None), "ec3d_domain_linkage")
+        if n.value == 0:
+            return []
+        out = (DomainLink * n.value)()
+        _chk(self.L, self.L.ec3d_domain_linkage(self.h, d, n.value, C.byref(n), out), "ec3d_domain_linkage")
+        return [dict(domain=int(r.domain), cells=int(r.cells), linkage=float(r.linkage),
+                     jsum=np.array(r.jsum[:], np.float64)) for r in out[:n.value]]
 
     def vtk_fields_begin(self, delta, big_endian: bool = True) -> int:
         """Start the field output of this step WITHOUT waiting (ec3d_vtk_fields_begin): the field kernel on the

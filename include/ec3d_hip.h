@@ -170,6 +170,54 @@ typedef struct {
 int ec3d_domain_integrals(ec3d_handle h, const double *delta, int32_t cap, int32_t *ndomains,
                           ec3d_domain_integral *out);
 
+/* Magnetic energy of the box and the integral of A.J, from the resident Uaf (X) and Jaf (B), in one streaming pass over
+ * every cell on the device.  Per cell, in double precision and without contraction, the B and s of
+ * ec3d_domain_integrals:
+ *   B = curl A (Vector_field_B),   J = s * Jaf in EVERY cell,   a = (Ax*Jx + Ay*Jy) + Az*Jz
+ * and over the box, with 1/mu0 = 0.07957747154594766788444e7 (the literal behind s):
+ *   cells        cells of the box
+ *   energy_axis  (dx*dy*dz) * (0.5 / mu0) * sum(Bx*Bx), sum(By*By), sum(Bz*Bz)      J
+ *   energy_b     (dx*dy*dz) * (0.5 / mu0) * ((sum Bx*Bx + sum By*By) + sum Bz*Bz)   J   (L = 2 W / I^2)
+ *   aj_source    (dx*dy*dz) * sum(a) over the cells outside the conductors          J
+ *   aj_eddy      (dx*dy*dz) * sum(a) over the conductor cells (geoPHYS_C != 0)       J
+ * The sums have a fixed order (no atomics): the same X, B and geometry give the same bits, whichever
+ * device form and plane pitch hold them.  X and B are read as they stand -- they mean the above after
+ * ec3d_post_update of a step -- and no work vector is written.  The first call allocates one byte per cell (none
+ * without conductors) and 40 KB; every call is two launches, one 40-byte copy and one synchronisation of the handle's
+ * stream.  Status 3, 5 as ec3d_domain_integrals; 2: delta or out NULL. */
+typedef struct {
+    int64_t cells;
+    double energy_b;
+    double energy_axis[3];
+    double aj_source;
+    double aj_eddy;
+} ec3d_field_energy_info;
+int ec3d_field_energy(ec3d_handle h, const double *delta, ec3d_field_energy_info *out);
+
+/* Flux linkage of every domain that holds cells outside the conductors, from the resident Uaf (X) and Jaf (B), summed on
+ * the device.  Per such cell (geoPHYS_C == 0), J and a as in ec3d_field_energy; per domain d (the cells' geoPHYS id):
+ *   cells    cells of the domain
+ *   linkage  (dx*dy*dz) * sum(a)              J    (the reference stores +mu0 * J in source cells, so s * Jaf is minus the
+ *                                                   source current density: psi * I of a coil is -linkage)
+ *   jsum     (dx*dy*dz) * sum(Jx, Jy, Jz)     A m  (divides the current out of a straight conductor segment)
+ * The library is given ids, not roles: it cannot tell the environment (air) from a coil that carries no current at the
+ * moment, so EVERY non-conducting domain is listed, the air among them with its own cell list -- where Jaf is 0 the
+ * sums are exactly 0.  Conducting domains are not listed (ec3d_domain_integrals covers them).  Domains come in
+ * ascending id order; *ndomains receives their number; out == NULL: the count only.  The cell lists are built on the
+ * host by ec3d_assemble (4 B per non-conducting cell) and moved to the device by the first call with out != NULL; a
+ * handle that never calls holds nothing on the device.  Fixed summation order as in ec3d_domain_integrals; X and B are
+ * read as they stand and no work vector is written; one 32-byte-per-domain copy and one synchronisation per call.
+ * Status 3, 5 as ec3d_domain_integrals; 2: delta or ndomains NULL, or out != NULL with cap < *ndomains (the count is
+ * still written). */
+typedef struct {
+    int32_t domain;
+    int32_t pad;
+    int64_t cells;
+    double linkage;
+    double jsum[3];
+} ec3d_domain_link;
+int ec3d_domain_linkage(ec3d_handle h, const double *delta, int32_t cap, int32_t *ndomains, ec3d_domain_link *out);
+
 /* ||B - A*X|| / ||B|| of the RESIDENT vectors, computed on the device by the solve's own setup kernel
  * (src/solvers.f90:14-21); bnorm (may be NULL) receives ||B||.  The check of a returned x that does not rely
  * on the iteration's recurrence for R.  Overwrites the work vectors R, R0, P (rebuilt by the next solve). */
