@@ -607,6 +607,14 @@ static int choose_sweep(ec3d_ctx *c)
                 // K4 as an SpMV kernel that computes A S again instead of reading the AS that K23 would have written
                 // (k4s_x_r_spmv): 16 B per row and iteration less.  EC3D_K4S=0 never, 2 whenever both fusions run
                 c->k4s_ok = A.ncls > 0 && !A.sav && c->fuse23_ok && c->fuse51_ok && (k4s == 2 || (k4s == 1 && fuse_big));
+                // Paired patch columns: y-adjacent columns marched by one workgroup of 512 threads, their common boundary
+                // through LDS (ec3d_patch_pairs_ok has the rule).  EC3D_PATCH=2: every launch kind, wherever the rule allows;
+                // EC3D_PATCH=1: never; unset: the kinds in EC3D_PAIR_DEFAULT_BIG on vectors beyond the caches (docs/rounds/r08.md).
+                {
+                    const int kinds = patch == 2 ? EC3D_PAIR_ALL : knob.patch ? 0 : big ? EC3D_PAIR_DEFAULT_BIG : 0;
+                    const bool slab = c->halo > 0 || c->nranks > 1;
+                    ss.pair = ec3d_patch_pairs_ok(tpp, ss.patch_npx, nplanes, ss.zm_pps, ss.nblk, slab, c->dist) ? kinds : 0;
+                }
             }
         }
     }

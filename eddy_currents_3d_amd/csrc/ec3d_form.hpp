@@ -28,6 +28,7 @@ struct SpmvForm {
     bool il;    // interleaved z-march of the structured form
     bool hs;    // z-slab of the three-launch iteration: the formed vector is also stored on the halo planes
                 // (only k23_s_spmv_dots and k51_p_spmv_dot have such instances)
+    bool pair;  // paired patch columns (Sweep::pair holds the launch's kind): set by the launcher, see ec3d_form_pair
 };
 
 inline SpmvForm ec3d_spmv_form(const MatView &A, const Sweep &sw)
@@ -44,6 +45,13 @@ inline SpmvForm ec3d_spmv_form(const MatView &A, const Sweep &sw)
     return f;
 }
 
+// Does a launch of kind `kind` (one EC3D_PAIR_* bit) of this form run paired patch columns?  Dictionary cube on 2-D tiles,
+// no z-slab instance, and the sweep's plan (choose_sweep, ec3d_patch_pairs_ok) says so for the kind.
+inline bool ec3d_form_pair(const SpmvForm &f, const Sweep &sw, int kind)
+{
+    return f.patch && f.fmt == FMT_DICT7 && !f.hs && (sw.pair & kind) != 0;
+}
+
 // Dynamic LDS bytes of the launch; EC3D_TBL_DECL (ec3d_kernels.hip) lays the same LDS out on the device.
 // The class table (55 + 9 D classes of the structured form with D conducting domains: 64 classes =
 // 8 KiB for one domain, 253 = 31.6 KiB at D = 22, which with the staging slots caps the CU at 3 workgroups -- a cost
@@ -57,7 +65,8 @@ inline size_t ec3d_form_lds(const MatView &A, const SpmvForm &f)
     // structured form on runtime-shaped 2-D tiles: table, two exchange buffers, two staging slots (sav_patch_step)
     if (f.patch && f.fmt == FMT_SAV) return sav_tbl + (size_t)(2 + EC3D_NSTAGE_RT) * EC3D_TILE * 8;
     // 2-D tiles of the single-component kernels: table (an even number of doubles), two centre-plane buffers (patch_pair)
-    if (f.patch) return (size_t)((f.fmt == FMT_DICT7 ? A.ncls * 7 + 1 : 0) & ~1) * 8 + (size_t)2 * EC3D_TILE * 8;
+    // (paired patch columns: the two buffers hold eight patch rows)
+    if (f.patch) return (size_t)((f.fmt == FMT_DICT7 ? A.ncls * 7 + 1 : 0) & ~1) * 8 + (size_t)(f.pair ? 4 : 2) * EC3D_TILE * 8;
     if (f.fmt == FMT_DICT7) return (size_t)A.ncls * 7 * 8;
     if (f.fmt == FMT_SAV) return sav_tbl + (f.zm ? (size_t)EC3D_NSTAGE * EC3D_TILE * 8 : 0);
     return 0;

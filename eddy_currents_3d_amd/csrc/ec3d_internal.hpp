@@ -141,6 +141,10 @@ struct Sweep {
     // nothing).  Cut by WEIGHT (a plane with a U tile costs more than one without), per column, the columns of XCD label x =
     // b % 8 being its cpx adjacent ones, so that every workgroup of the launch ends at about the same time.
     const int32_t *il_seg = nullptr;
+    // Paired patch columns (2-D tiles; ec3d_patch_pairs_ok in ec3d_sweep_lists.hpp): the launch kinds (EC3D_PAIR_* bits)
+    // that run nblk / 2 workgroups of 512 threads, each hosting two y-adjacent workgroups of the nblk this sweep counts.
+    // nblk, the partials, the visit order and the tile lists keep speaking of those nblk "virtual" workgroups.
+    int pair = 0;
 };
 
 // first of the two consecutive rows thread t of a workgroup owns in `tile`

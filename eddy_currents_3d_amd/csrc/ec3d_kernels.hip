@@ -24,6 +24,7 @@
 // reference's x86-64 object code does; the oracle's "GPU order" twin reproduces every bit.
 #include "ec3d_form.hpp"
 #include "ec3d_recurrence.hpp"
+#include "ec3d_sweep_lists.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -40,11 +41,33 @@ __device__ __forceinline__ double wave_sum(double v)
     return v; // lane 0
 }
 
-// sums NV values over the workgroup; result valid in every thread.  lds: NV*4 doubles.
-template <int NV>
+// Paired patch columns (PAIR; patch_pair below, ec3d_patch_pairs_ok in ec3d_sweep_lists.hpp): a workgroup of 512 threads
+// hosts two VIRTUAL workgroups of 256 -- half 0 and half 1 -- each of which is exactly a workgroup of the unpaired launch:
+// its thread index, its workgroup index (column, z segment, XCD label, partial slot), its own four-wave sums.  The two
+// halves share the class table, the step's barrier and one LDS exchange buffer of eight patch rows.  Without PAIR these
+// are threadIdx.x and blockIdx.x and nothing else.  (The half is wave uniform: read through the first lane, it and the
+// workgroup index stay in scalar registers.)
+template <bool PAIR> __device__ __forceinline__ int vw_tid()
+{
+    return PAIR ? (int)(threadIdx.x & (EC3D_THREADS - 1)) : (int)threadIdx.x;
+}
+template <bool PAIR> __device__ __forceinline__ int vw_half()
+{
+    if constexpr (PAIR) return __builtin_amdgcn_readfirstlane((int)(threadIdx.x / EC3D_THREADS));
+    else return 0;
+}
+template <bool PAIR, class SW> __device__ __forceinline__ int vw_bid(const SW &sw)
+{
+    if constexpr (PAIR) return ec3d_patch_pair_virtual(sw.tpp, sw.patch_npx, (int)blockIdx.x, vw_half<PAIR>());
+    else return (int)blockIdx.x;
+}
+
+// sums NV values over the (virtual) workgroup; result valid in every thread.  lds: NV*4 doubles per half.
+template <int NV, bool PAIR = false>
 __device__ __forceinline__ void block_sum(double (&v)[NV], double *lds)
 {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, w = vw_tid<PAIR>() >> 6;
+    if constexpr (PAIR) lds += vw_half<PAIR>() * (NV * 4);
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
         double t = wave_sum(v[k]);
@@ -85,15 +108,16 @@ __device__ __forceinline__ void reduce_partials(const RedSrc &src, const int (&s
 // partials_finish adds them in the order of reduce_partials -- the same sums -- and loads what is left, if anything.
 #define EC3D_PMAX 6
 template <int NV> struct PartialsEarly { double v[NV][EC3D_PMAX]; };
-template <int NV>
+template <int NV, bool PAIR = false>
 __device__ __forceinline__ void partials_request(const RedSrc &src, const int (&slot)[NV], PartialsEarly<NV> &e)
 {
+    const int tid = vw_tid<PAIR>(); // (a virtual workgroup adds what a workgroup of 256 adds, in its order)
     // branch free: an index beyond the count reads entry 0 (always there) and its value is dropped -- a load behind a
     // branch of its own is waited for at the end of that branch, and the requests would go out one by one again
     if (src.ptrs) { // one value per rank, each in that rank's own memory
 #pragma unroll
         for (int j = 0; j < EC3D_PMAX; ++j) {
-            const int i = (int)threadIdx.x + j * EC3D_THREADS;
+            const int i = tid + j * EC3D_THREADS;
             const double *q = src.ptrs[i < src.count ? i : 0];
 #pragma unroll
             for (int k = 0; k < NV; ++k) e.v[k][j] = q[slot[k]];
@@ -104,29 +128,30 @@ __device__ __forceinline__ void partials_request(const RedSrc &src, const int (&
             const double *p = src.base + (int64_t)slot[k] * src.slot_mul;
 #pragma unroll
             for (int j = 0; j < EC3D_PMAX; ++j) {
-                const int i = (int)threadIdx.x + j * EC3D_THREADS;
+                const int i = tid + j * EC3D_THREADS;
                 e.v[k][j] = p[(int64_t)(i < src.count ? i : 0) * src.stride];
             }
         }
     }
 }
-template <int NV>
+template <int NV, bool PAIR = false>
 __device__ __forceinline__ void partials_finish(const RedSrc &src, const int (&slot)[NV], const PartialsEarly<NV> &e,
                                                 double (&out)[NV], double *lds)
 {
+    const int tid = vw_tid<PAIR>();
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
         double a = 0.0;
 #pragma unroll
         for (int j = 0; j < EC3D_PMAX; ++j) // (a value beyond the count enters as +0.0, which changes no sum)
-            a = a + ((int)threadIdx.x + j * EC3D_THREADS < src.count ? e.v[k][j] : 0.0);
-        for (int i = (int)threadIdx.x + EC3D_PMAX * EC3D_THREADS; i < src.count; i += EC3D_THREADS) {
+            a = a + (tid + j * EC3D_THREADS < src.count ? e.v[k][j] : 0.0);
+        for (int i = tid + EC3D_PMAX * EC3D_THREADS; i < src.count; i += EC3D_THREADS) {
             if (src.ptrs) a = a + src.ptrs[i][slot[k]];
             else a = a + src.base[(int64_t)slot[k] * src.slot_mul + (int64_t)i * src.stride];
         }
         out[k] = a;
     }
-    block_sum<NV>(out, lds);
+    block_sum<NV, PAIR>(out, lds);
 }
 
 // A producer's workgroup leaves its partial sums: one per slot, at the launch's offset within the slot.  The consumer kernel
@@ -136,13 +161,14 @@ __device__ __forceinline__ void partials_finish(const RedSrc &src, const int (&s
 // bit-identical and no faster than the four small launches it replaced: the serial tail behind the last workgroup costs what a
 // launch costs.  Removed; profiles/r05_partial_sum_collapse_in_kernel_vs_launch.log, commit "Experiment: partial sums
 // collapsed by the producers' last workgroup".)
-template <int NV, class SW>
+template <int NV, bool PAIR = false, class SW>
 __device__ __forceinline__ void publish_partials(const SW &sw, double *part, const int (&slot)[NV], const double (&acc)[NV],
                                                  double *)
 {
-    if (threadIdx.x == 0) {
+    if (vw_tid<PAIR>() == 0) { // (paired columns: each half into its own virtual workgroup's slot)
+        const int b = vw_bid<PAIR>(sw);
 #pragma unroll
-        for (int k = 0; k < NV; ++k) part[slot[k] * sw.pstride + sw.part_off + blockIdx.x] = acc[k];
+        for (int k = 0; k < NV; ++k) part[slot[k] * sw.pstride + sw.part_off + b] = acc[k];
     }
 }
 
@@ -379,10 +405,12 @@ __device__ __forceinline__ void walk_vec(const SweepV &sw, LOAD &&load, FIN &&fi
 // ec3d_tile_of<1> walked incrementally: one column, runs of consecutive planes.  A run ends where the segment
 // ends or -- in a windowed slab -- where the owned planes of a block end: the physical plane then jumps over the
 // halo planes and the march starts afresh in the next block.
-template <bool SPEC, class BODY>
+// (PAIR: the walk of this half's virtual workgroup; both halves take the same number of steps, ec3d_patch_pairs_ok)
+template <bool SPEC, bool PAIR = false, class BODY>
 __device__ __forceinline__ void walk_zm(const SweepZ &sw, BODY &&body)
 {
-    const int cpx = (sw.tpp + 7) >> 3, c = blockIdx.x & 7, sg = blockIdx.x >> 3;
+    const int vb = vw_bid<PAIR>(sw);
+    const int cpx = (sw.tpp + 7) >> 3, c = vb & 7, sg = vb >> 3;
     const int col = c * cpx + sg % cpx;
     int64_t lp = (int64_t)(sg / cpx) * sw.pps; // logical plane, relative to pl0
     int64_t lend = lp + sw.pps;
@@ -412,7 +440,8 @@ __device__ __forceinline__ void walk_zm(const SweepZ &sw, BODY &&body)
             pl += run + (sw.win_npb - sw.win_npo); // next block's first owned plane (windowed slab only)
             rem = 0;
         }
-        for (int64_t lst = blockIdx.x; lst < sw.ulist_n; lst += gridDim.x) body((int64_t)sw.ulist[lst], TrueC());
+        if constexpr (!PAIR) // (a paired launch has no tile list)
+            for (int64_t lst = blockIdx.x; lst < sw.ulist_n; lst += gridDim.x) body((int64_t)sw.ulist[lst], TrueC());
     } else {
         // a body too large to have three times (structured form: two copies already cost 25-45 spilled
         // registers): ONE loop over the front sweep and the list, `first` a run-time flag
@@ -504,11 +533,11 @@ __device__ __forceinline__ void walk_zm_rt(const SweepZ &sw, int64_t pitch, int6
         body(pp.P * sw.tpp + pp.q, first);
     }
 }
-template <int FMT, bool ZM, bool SPEC, bool PATCH, class SW, class AD, class BODY>
+template <int FMT, bool ZM, bool SPEC, bool PATCH, bool PAIR = false, class SW, class AD, class BODY>
 __device__ __forceinline__ void walk_spmv(const AD &A, const SW &sw, PatchPos &pp, BODY &&body)
 {
     if constexpr (FMT == 207 /* FMT_SAV */ && ZM && PATCH) walk_zm_rt(sw, A.pitch, A.sdx, pp, body);
-    else if constexpr (ZM) walk_zm<SPEC>(sw, body);
+    else if constexpr (ZM) walk_zm<SPEC, PAIR>(sw, body);
     else walk_plain<0>(sw, body);
 }
 #define EC3D_ROW const int64_t r = tile * EC3D_TILE + 2 * (int64_t)threadIdx.x
@@ -516,7 +545,7 @@ __device__ __forceinline__ void walk_spmv(const AD &A, const SW &sw, PatchPos &p
 // threads), and the row count its stores compare with (0 for an idle thread: nothing is stored)
 #define EC3D_ROW_S                                                                                                     \
     const int64_t r = (FMT == FMT_SAV && PATCH) ? pp.r                                                                 \
-                      : PATCH ? ec3d_row_of(sw, tile, (int)threadIdx.x) : tile * EC3D_TILE + 2 * (int64_t)threadIdx.x; \
+                      : PATCH ? ec3d_row_of(sw, tile, vw_tid<PAIR>()) : tile * EC3D_TILE + 2 * (int64_t)threadIdx.x; \
     const bool live_ = (FMT == FMT_SAV && PATCH) ? pp.live : true;                                                     \
     const int64_t nst = live_ ? sw.n : 0
 #define EC3D_IDLE2(a, b)                                                                                               \
@@ -1435,6 +1464,12 @@ __device__ __forceinline__ void sav_patch_step(const MatDev<FMT_SAV> &A, const S
 //   PP_RIM_EDGE_BEHIND  (VecFusedP)  the rim row and the edge cells of the NEXT step are requested behind the arrival of
 //                                    the plane above and formed at the end of the step (ZRegs::rim, ZRegs::edge): a
 //                                    step's first requests are the plane above and nothing else
+// PAIR (round 8): the same step on a patch of 128 x 8 -- two y-adjacent patches of 128 x 4, each marched by one half of a
+// workgroup of 512 threads (vw_tid / vw_half / vw_bid above: every half is a workgroup of the unpaired launch).  `t` below is the
+// PHYSICAL thread, so y runs over the eight rows of the common exchange buffer: rows 3 and 4 find their +-sdx neighbour -- the
+// other half's centre values, formed by their owners -- in LDS like any inner row, and only rows 0 and 7 are rim rows.  Row
+// addresses (r), tiles and class pairs are the half's own.  Which launches pair: ec3d_patch_pairs_ok (ec3d_sweep_lists.hpp)
+// and, per kind of launch, the A/B of docs/rounds/r08.md.
 // Round 6 also measured the rim row with the step's first requests, behind the barrier, and behind the plane above
 // without the edge cells: all three lost (profiles/r06_patch_requests_512.log).
 enum PatchRequests { PP_BRANCHY, PP_RIM_CARRIED, PP_RIM_EDGE_BEHIND };
@@ -1521,13 +1556,14 @@ __device__ __forceinline__ d2 patch_sums(const d2 *c, const double *tbl, unsigne
 // raw barrier behind a wait for the LDS writes only: __syncthreads() also drains every global load in flight (vmcnt(0))
 // before the barrier, which would put the LDS exchange BEHIND the arrival of the plane above instead of beside it.
 #define EC3D_PATCH_BARRIER asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-template <int FMT, bool NTB, class V>
+template <int FMT, bool NTB, bool PAIR, class V>
 __device__ __forceinline__ void patch_pair_branchy(const MatDev<FMT> &A, const double *tbl, double *pbuf, int step, const V &x,
                                                    int64_t r, int64_t tile, bool first, ZRegs &z, double &s0, double &s1,
                                                    d2 &ctr)
 {
+    constexpr int PY = PAIR ? 2 * EC3D_PY : EC3D_PY, BUF = PY * EC3D_PX; // patch rows and cells of the (paired) workgroup
     const int t = threadIdx.x, y = t / EC3D_HX, q = t % EC3D_HX;
-    double *cur = pbuf + (step & 1) * EC3D_TILE, *nxt = pbuf + ((step + 1) & 1) * EC3D_TILE;
+    double *cur = pbuf + (step & 1) * BUF, *nxt = pbuf + ((step + 1) & 1) * BUF;
     const int64_t sdx = A.off[5], kdz = A.off[6];
     const unsigned short cc = patch_classes<FMT>(A, r, tile, first, z);
     d2 c[7];
@@ -1540,7 +1576,7 @@ __device__ __forceinline__ void patch_pair_branchy(const MatDev<FMT> &A, const d
     double left = 0.0, right = 0.0;
     if (q == 0) left = x.at(r - 1);
     if (q == EC3D_HX - 1) right = x.at(r + 2);
-    const bool rimrow = y == 0 || y == EC3D_PY - 1;
+    const bool rimrow = y == 0 || y == PY - 1;
     const int64_t roff = y == 0 ? -sdx : sdx;
     d2 rimc = d2{0.0, 0.0};
     if (rimrow) {
@@ -1559,7 +1595,7 @@ __device__ __forceinline__ void patch_pair_branchy(const MatDev<FMT> &A, const d
     }
     EC3D_PATCH_BARRIER;
     if (y > 0) ym = *reinterpret_cast<const d2 *>(cur + 2 * (t - EC3D_HX));
-    if (y < EC3D_PY - 1) yp = *reinterpret_cast<const d2 *>(cur + 2 * (t + EC3D_HX));
+    if (y < PY - 1) yp = *reinterpret_cast<const d2 *>(cur + 2 * (t + EC3D_HX));
     ctr = cx;
     {
         const double l = __shfl_up(cx.y, 1, 64), rr = __shfl_down(cx.x, 1, 64);
@@ -1575,14 +1611,15 @@ __device__ __forceinline__ void patch_pair_branchy(const MatDev<FMT> &A, const d
     z.xc = zp;
 }
 
-template <int FMT, bool NTB, class V>
+template <int FMT, bool NTB, bool PAIR, class V>
 __device__ __forceinline__ void patch_pair_fused(const MatDev<FMT> &A, const double *tbl, double *pbuf, int step, const V &x,
                                                  int64_t r, int64_t tile, bool first, ZRegs &z, double &s0, double &s1,
                                                  d2 &ctr)
 {
     constexpr PatchRequests RQ = PatchReq<V>::mode;
+    constexpr int PY = PAIR ? 2 * EC3D_PY : EC3D_PY, BUF = PY * EC3D_PX; // patch rows and cells of the (paired) workgroup
     const int t = threadIdx.x, y = t / EC3D_HX, q = t % EC3D_HX;
-    double *cur = pbuf + (step & 1) * EC3D_TILE, *nxt = pbuf + ((step + 1) & 1) * EC3D_TILE;
+    double *cur = pbuf + (step & 1) * BUF, *nxt = pbuf + ((step + 1) & 1) * BUF;
     const int64_t sdx = A.off[5], kdz = A.off[6];
     const unsigned short cc = patch_classes<FMT>(A, r, tile, first, z);
     d2 c[7];
@@ -1601,7 +1638,7 @@ __device__ __forceinline__ void patch_pair_fused(const MatDev<FMT> &A, const dou
     const bool edge = q == 0 || q == EC3D_HX - 1;
     typename V::Raw1 e_r{};
     if (edge && (RQ != PP_RIM_EDGE_BEHIND || first)) e_r = x.rat(q == 0 ? r - 1 : r + 2);
-    const bool rimrow = y == 0 || y == EC3D_PY - 1;
+    const bool rimrow = y == 0 || y == PY - 1;
     const int64_t roff = y == 0 ? -sdx : sdx;
     typename V::Raw2 rimc_r{}, rimn_r{};
     if (rimrow && first) rimc_r = x.rpair(r + roff);
@@ -1621,7 +1658,7 @@ __device__ __forceinline__ void patch_pair_fused(const MatDev<FMT> &A, const dou
     else rimc = first ? x.form(rimc_r) : z.rim;
     d2 ym = rimc, yp = rimc;
     if (y > 0) ym = *reinterpret_cast<const d2 *>(cur + 2 * (t - EC3D_HX));
-    if (y < EC3D_PY - 1) yp = *reinterpret_cast<const d2 *>(cur + 2 * (t + EC3D_HX));
+    if (y < PY - 1) yp = *reinterpret_cast<const d2 *>(cur + 2 * (t + EC3D_HX));
     ctr = cx;
     double left, right;
     {
@@ -1652,19 +1689,19 @@ __device__ __forceinline__ void patch_pair_fused(const MatDev<FMT> &A, const dou
         z.edge = x.form(en_r);
     }
 }
-template <int FMT, bool NTB, class V>
+template <int FMT, bool NTB, bool PAIR, class V>
 __device__ __forceinline__ void patch_pair(const MatDev<FMT> &A, const double *tbl, double *pbuf, int step, const V &x,
                                            int64_t r, int64_t tile, bool first, ZRegs &z, double &s0, double &s1,
                                            d2 &ctr)
 {
-    if constexpr (PatchReq<V>::mode == PP_BRANCHY) patch_pair_branchy<FMT, NTB>(A, tbl, pbuf, step, x, r, tile, first, z, s0, s1, ctr);
-    else patch_pair_fused<FMT, NTB>(A, tbl, pbuf, step, x, r, tile, first, z, s0, s1, ctr);
+    if constexpr (PatchReq<V>::mode == PP_BRANCHY) patch_pair_branchy<FMT, NTB, PAIR>(A, tbl, pbuf, step, x, r, tile, first, z, s0, s1, ctr);
+    else patch_pair_fused<FMT, NTB, PAIR>(A, tbl, pbuf, step, x, r, tile, first, z, s0, s1, ctr);
 }
 
 // rows r, r+1 of A*x (src/solvers.f90:58-59): bands in ascending column order, then the tail.
 // ZM: band 0 / 3 / 6 (offsets -kdz, 0, +kdz) come from / go to the registers `z`.
 // `ctr` returns x[r], x[r+1] (the centre band's operand).
-template <int FMT, bool ZM, bool TAIL, bool NTB, bool PATCH, class V, class SW>
+template <int FMT, bool ZM, bool TAIL, bool NTB, bool PATCH, bool PAIR = false, class V, class SW>
 __device__ __forceinline__ void spmv_pair(const MatDev<FMT> &A, const SW &sw, const PatchPos &pp, const double *tbl,
                                           double *stg, int &step, const V &x, int64_t r, int64_t tile, bool first,
                                           ZRegs &z, double &s0, double &s1, d2 &ctr)
@@ -1678,7 +1715,7 @@ __device__ __forceinline__ void spmv_pair(const MatDev<FMT> &A, const SW &sw, co
         return;
     }
     if constexpr (PATCH && (FMT == FMT_DIA7 || FMT == FMT_DICT7)) {
-        patch_pair<FMT, NTB>(A, tbl, stg, step++, x, r, tile, first, z, s0, s1, ctr);
+        patch_pair<FMT, NTB, PAIR>(A, tbl, stg, step++, x, r, tile, first, z, s0, s1, ctr);
         return;
     }
     uint8_t tflag = 0; // per tile: any tail row (bands + tail) / any coupled row (structured form)
@@ -1789,7 +1826,8 @@ __device__ __forceinline__ void spmv_pair(const MatDev<FMT> &A, const SW &sw, co
 // four blocks at once: two workgroups per CU)
 #define EC3D_IL (FMT == FMT_SAV && ZM && TAIL && !PATCH)
 #define EC3D_SPMV_OCC __attribute__((amdgpu_waves_per_eu(EC3D_IL ? 2 : (FMT == FMT_SAV && !ZM) ? 5 : 6)))
-#define EC3D_SPMV_T template <int FMT, bool NT, bool ZM, bool TAIL, bool PATCH>
+#define EC3D_SPMV_T template <int FMT, bool NT, bool ZM, bool TAIL, bool PATCH, bool PAIR = false>
+#define EC3D_WG_THREADS (PAIR ? 2 * EC3D_THREADS : EC3D_THREADS) /* paired patch columns: two virtual workgroups */
 #define EC3D_SWEEP_OF(ZM_) typename SweepSel<ZM_>::type
 // classes in the LDS table (0 for the formats without one)
 template <int FMT> __device__ __forceinline__ int ncls_of(const MatDev<FMT> &A)
@@ -1803,7 +1841,7 @@ template <int FMT> __device__ __forceinline__ int ncls_of(const MatDev<FMT> &A)
 
 // ---------------------------------------------------------------------------------------------
 // plain y = A x  (src/solvers.f90:54-61)
-EC3D_SPMV_T __global__ __launch_bounds__(EC3D_THREADS) EC3D_SPMV_OCC void k_spmv(MatDev<FMT> A, EC3D_SWEEP_OF(ZM) sw,
+EC3D_SPMV_T __global__ __launch_bounds__(EC3D_WG_THREADS) EC3D_SPMV_OCC void k_spmv(MatDev<FMT> A, EC3D_SWEEP_OF(ZM) sw,
                                                                                    const double *__restrict__ x,
                                                                                    double *__restrict__ y)
 {
@@ -1816,22 +1854,22 @@ EC3D_SPMV_T __global__ __launch_bounds__(EC3D_THREADS) EC3D_SPMV_OCC void k_spmv
         walk_zm_il(A, sw, tbl, VecPlain{x}, [](int64_t) { return d2{0.0, 0.0}; },
                    [&](int64_t r, double s0, double s1, d2, d2) { store2<NT>(y, r, INT64_MAX, s0, s1); });
     } else {
-        walk_spmv<FMT, ZM, FMT != FMT_SAV, PATCH>(A, sw, pp, [&](int64_t tile, auto fc) {
+        walk_spmv<FMT, ZM, FMT != FMT_SAV, PATCH, PAIR>(A, sw, pp, [&](int64_t tile, auto fc) {
             EC3D_ROW_S;
             double s0, s1;
             d2 ctr;
-            spmv_pair<FMT, ZM, TAIL, NT, PATCH>(A, sw, pp, tbl, stg, pstep, VecPlain{x}, r, tile, (bool)fc, zr, s0, s1, ctr);
+            spmv_pair<FMT, ZM, TAIL, NT, PATCH, PAIR>(A, sw, pp, tbl, stg, pstep, VecPlain{x}, r, tile, (bool)fc, zr, s0, s1, ctr);
             store2<NT>(y, r, nst, s0, s1);
         });
     }
 }
 
 // setup: R = B - A X ; R0 = R ; P = R ; partials of B·B and R·R   (src/solvers.f90:14-21)
-EC3D_SPMV_T __global__ __launch_bounds__(EC3D_THREADS) EC3D_SPMV_OCC void k_residual(
+EC3D_SPMV_T __global__ __launch_bounds__(EC3D_WG_THREADS) EC3D_SPMV_OCC void k_residual(
     MatDev<FMT> A, EC3D_SWEEP_OF(ZM) sw, const double *__restrict__ x, const double *__restrict__ b,
     double *__restrict__ rv, double *__restrict__ r0, double *__restrict__ p, double *__restrict__ part)
 {
-    __shared__ double lds[8];
+    __shared__ double lds[(PAIR ? 2 : 1) * 8];
     EC3D_TBL_DECL;
     stage_table<FMT>(A, tbl);
     ZRegs zr;
@@ -1851,11 +1889,11 @@ EC3D_SPMV_T __global__ __launch_bounds__(EC3D_THREADS) EC3D_SPMV_OCC void k_resi
                        acc[1] = acc[1] + e1 * e1;
                    });
     } else {
-        walk_spmv<FMT, ZM, FMT != FMT_SAV, PATCH>(A, sw, pp, [&](int64_t tile, auto fc) {
+        walk_spmv<FMT, ZM, FMT != FMT_SAV, PATCH, PAIR>(A, sw, pp, [&](int64_t tile, auto fc) {
             EC3D_ROW_S;
             double s0, s1;
             d2 ctr;
-            spmv_pair<FMT, ZM, TAIL, NT, PATCH>(A, sw, pp, tbl, stg, pstep, VecPlain{x}, r, tile, (bool)fc, zr, s0, s1, ctr);
+            spmv_pair<FMT, ZM, TAIL, NT, PATCH, PAIR>(A, sw, pp, tbl, stg, pstep, VecPlain{x}, r, tile, (bool)fc, zr, s0, s1, ctr);
             d2 bv = load2<NT>(b + r);
             double e0 = bv.x - s0, e1 = bv.y - s1, b0 = bv.x, b1 = bv.y;
             store2<NT>(rv, r, nst, e0, e1);
@@ -1871,10 +1909,10 @@ EC3D_SPMV_T __global__ __launch_bounds__(EC3D_THREADS) EC3D_SPMV_OCC void k_resi
             acc[1] = acc[1] + e1 * e1;
         });
     }
-    block_sum<2>(acc, lds);
+    block_sum<2, PAIR>(acc, lds);
     {
         const int pslot_[2] = {P_BB, P_RR_INIT};
-        publish_partials<2>(sw, part, pslot_, acc, lds);
+        publish_partials<2, PAIR>(sw, part, pslot_, acc, lds);
     }
 }
 
@@ -1964,11 +2002,11 @@ __global__ __launch_bounds__(EC3D_THREADS) void k_setup(SolverState *st, RedSrc 
 }
 
 // K1: AP = A P ; partial AP·R0    (src/solvers.f90:30, :32 denominator)
-EC3D_SPMV_T __global__ __launch_bounds__(EC3D_THREADS) EC3D_SPMV_OCC void k1_spmv_dot(
+EC3D_SPMV_T __global__ __launch_bounds__(EC3D_WG_THREADS) EC3D_SPMV_OCC void k1_spmv_dot(
     MatDev<FMT> A, EC3D_SWEEP_OF(ZM) sw, const SolverState *st, int it, const double *__restrict__ p,
     const double *__restrict__ r0, double *__restrict__ ap, double *__restrict__ part)
 {
-    __shared__ double lds[4];
+    __shared__ double lds[(PAIR ? 2 : 1) * 4];
     EC3D_TBL_DECL;
     TableEarly te;
     table_request<FMT>(A, te); // with the exit word: one round trip before the first tile instead of two
@@ -1988,7 +2026,7 @@ EC3D_SPMV_T __global__ __launch_bounds__(EC3D_THREADS) EC3D_SPMV_OCC void k1_spm
                        acc[0] = acc[0] + s1 * q.y;
                    });
     } else {
-        walk_spmv<FMT, ZM, FMT != FMT_SAV, PATCH>(A, sw, pp, [&](int64_t tile, auto fc) {
+        walk_spmv<FMT, ZM, FMT != FMT_SAV, PATCH, PAIR>(A, sw, pp, [&](int64_t tile, auto fc) {
             EC3D_ROW_S;
             double s0, s1;
             d2 ctr;
@@ -1996,7 +2034,7 @@ EC3D_SPMV_T __global__ __launch_bounds__(EC3D_THREADS) EC3D_SPMV_OCC void k1_spm
             // steps wait on LDS-DMA slots), after them elsewhere (2-D tiles: 593 vs 603 us at 512^3, 76 vs 80 at 256^3)
             d2 q;
             if constexpr (FMT == FMT_SAV && !PATCH) q = load2<NT>(r0 + r);
-            spmv_pair<FMT, ZM, TAIL, NT, PATCH>(A, sw, pp, tbl, stg, pstep, VecPlain{p}, r, tile, (bool)fc, zr, s0, s1, ctr);
+            spmv_pair<FMT, ZM, TAIL, NT, PATCH, PAIR>(A, sw, pp, tbl, stg, pstep, VecPlain{p}, r, tile, (bool)fc, zr, s0, s1, ctr);
             if constexpr (FMT != FMT_SAV || PATCH) q = load2<NT>(r0 + r);
             store2k<NT>(ap, r, nst, s0, s1, keep_of(sw) & EC3D_KEEP_AP);
             EC3D_MASK2(r, sw, s0, s1);
@@ -2005,10 +2043,10 @@ EC3D_SPMV_T __global__ __launch_bounds__(EC3D_THREADS) EC3D_SPMV_OCC void k1_spm
             acc[0] = acc[0] + s1 * q.y;
         });
     }
-    block_sum<1>(acc, lds);
+    block_sum<1, PAIR>(acc, lds);
     {
         const int pslot_[1] = {P_D1};
-        publish_partials<1>(sw, part, pslot_, acc, lds);
+        publish_partials<1, PAIR>(sw, part, pslot_, acc, lds);
     }
 }
 
@@ -2055,11 +2093,11 @@ __global__ __launch_bounds__(EC3D_THREADS) void k2_s_update(SweepV sw, RedSrc sr
 // K3: AS = A S ; partials AS·S and AS·AS (src/solvers.f90:39-40).  Launched before ‖S‖ is known
 // (one global reduction point less per iteration): when the ‖S‖ exit of :34-38 is then
 // taken by K4, AS is simply never used -- results are unchanged.
-EC3D_SPMV_T __global__ __launch_bounds__(EC3D_THREADS) EC3D_SPMV_OCC void k3_spmv_dots(
+EC3D_SPMV_T __global__ __launch_bounds__(EC3D_WG_THREADS) EC3D_SPMV_OCC void k3_spmv_dots(
     MatDev<FMT> A, EC3D_SWEEP_OF(ZM) sw, SolverState *st, int it, const double *__restrict__ sv,
     double *__restrict__ as, double *__restrict__ part)
 {
-    __shared__ double lds[8];
+    __shared__ double lds[(PAIR ? 2 : 1) * 8];
     EC3D_TBL_DECL;
     TableEarly te;
     table_request<FMT>(A, te);
@@ -2081,11 +2119,11 @@ EC3D_SPMV_T __global__ __launch_bounds__(EC3D_THREADS) EC3D_SPMV_OCC void k3_spm
                        acc[1] = acc[1] + s1 * s1;
                    });
     } else {
-        walk_spmv<FMT, ZM, FMT != FMT_SAV, PATCH>(A, sw, pp, [&](int64_t tile, auto fc) {
+        walk_spmv<FMT, ZM, FMT != FMT_SAV, PATCH, PAIR>(A, sw, pp, [&](int64_t tile, auto fc) {
             EC3D_ROW_S;
             double s0, s1;
             d2 q;
-            spmv_pair<FMT, ZM, TAIL, NT, PATCH>(A, sw, pp, tbl, stg, pstep, VecPlain{sv}, r, tile, (bool)fc, zr, s0, s1, q);
+            spmv_pair<FMT, ZM, TAIL, NT, PATCH, PAIR>(A, sw, pp, tbl, stg, pstep, VecPlain{sv}, r, tile, (bool)fc, zr, s0, s1, q);
             store2<NT>(as, r, nst, s0, s1);
             EC3D_MASK2(r, sw, s0, s1);
             EC3D_IDLE2(s0, s1);
@@ -2095,10 +2133,10 @@ EC3D_SPMV_T __global__ __launch_bounds__(EC3D_THREADS) EC3D_SPMV_OCC void k3_spm
             acc[1] = acc[1] + s1 * s1;
         });
     }
-    block_sum<2>(acc, lds);
+    block_sum<2, PAIR>(acc, lds);
     {
         const int pslot_[2] = {P_D2, P_D3};
-        publish_partials<2>(sw, part, pslot_, acc, lds);
+        publish_partials<2, PAIR>(sw, part, pslot_, acc, lds);
     }
 }
 
@@ -2108,16 +2146,16 @@ EC3D_SPMV_T __global__ __launch_bounds__(EC3D_THREADS) EC3D_SPMV_OCC void k3_spm
 // AS.AS -- all three in the SpMV kernels' thread -> cell assignment.  Saves the 8 B per row S costs to re-read and one
 // launch; the products, their order and every stored value are those of K2 followed by K3 (src/solvers.f90:31-40).
 // HS (z-slab, Sweep::halo_store): an instance of its own, so that the single-GPU kernel carries nothing for it
-template <int FMT, bool NT, bool ZM, bool TAIL, bool PATCH, bool HS = false>
-__global__ __launch_bounds__(EC3D_THREADS) __attribute__((amdgpu_waves_per_eu(4))) void k23_s_spmv_dots(
+template <int FMT, bool NT, bool ZM, bool TAIL, bool PATCH, bool HS = false, bool PAIR = false>
+__global__ __launch_bounds__(EC3D_WG_THREADS) __attribute__((amdgpu_waves_per_eu(4))) void k23_s_spmv_dots(
     MatDev<FMT> A, EC3D_SWEEP_OF(ZM) sw, RedSrc src, SolverState *st, int it, const double *__restrict__ rv,
     const double *__restrict__ ap, double *__restrict__ sv, double *__restrict__ as, double *__restrict__ part)
 {
-    __shared__ double lds[12];
+    __shared__ double lds[(PAIR ? 2 : 1) * 12];
     EC3D_TBL_DECL;
     const int slot[1] = {P_D1};
     PartialsEarly<1> pe;
-    partials_request<1>(src, slot, pe);
+    partials_request<1, PAIR>(src, slot, pe);
     const double rr0 = st->rr0[it & 1];
     TableEarly te;
     table_request<FMT>(A, te);
@@ -2125,7 +2163,7 @@ __global__ __launch_bounds__(EC3D_THREADS) __attribute__((amdgpu_waves_per_eu(4)
     EC3D_REQUESTS_OUT;
     if (stop_it < it) return;
     double d[1];
-    partials_finish<1>(src, slot, pe, d, lds);
+    partials_finish<1, PAIR>(src, slot, pe, d, lds);
     const double alpha = ec3d_alpha(rr0, d[0]);
     if (blockIdx.x == 0 && threadIdx.x == 0) st->alpha = alpha;
     table_store<FMT>(A, te, tbl);
@@ -2133,11 +2171,11 @@ __global__ __launch_bounds__(EC3D_THREADS) __attribute__((amdgpu_waves_per_eu(4)
     PatchPos pp{};
     int pstep = 0;
     double acc[3] = {0.0, 0.0, 0.0};
-    walk_spmv<FMT, ZM, FMT != FMT_SAV, PATCH>(A, sw, pp, [&](int64_t tile, auto fc) {
+    walk_spmv<FMT, ZM, FMT != FMT_SAV, PATCH, PAIR>(A, sw, pp, [&](int64_t tile, auto fc) {
         EC3D_ROW_S;
         double s0, s1;
         d2 q; // S[r], S[r+1]
-        spmv_pair<FMT, ZM, TAIL, NT, PATCH>(A, sw, pp, tbl, stg, pstep, VecFused{rv, ap, alpha}, r, tile, (bool)fc, zr, s0, s1, q);
+        spmv_pair<FMT, ZM, TAIL, NT, PATCH, PAIR>(A, sw, pp, tbl, stg, pstep, VecFused{rv, ap, alpha}, r, tile, (bool)fc, zr, s0, s1, q);
         store2<NT>(sv, r, nst, q.x, q.y);
         if (as) store2<NT>(as, r, nst, s0, s1); // (nullptr: K4 runs in SpMV form and computes A S again, k4s_x_r_spmv)
         if constexpr (HS && FMT == FMT_DICT7 && ZM && PATCH) {
@@ -2162,10 +2200,10 @@ __global__ __launch_bounds__(EC3D_THREADS) __attribute__((amdgpu_waves_per_eu(4)
         acc[2] = acc[2] + s0 * s0;
         acc[2] = acc[2] + s1 * s1;
     });
-    block_sum<3>(acc, lds);
+    block_sum<3, PAIR>(acc, lds);
     {
         const int pslot_[3] = {P_SS, P_D2, P_D3};
-        publish_partials<3>(sw, part, pslot_, acc, lds);
+        publish_partials<3, PAIR>(sw, part, pslot_, acc, lds);
     }
 }
 
@@ -2175,17 +2213,17 @@ __global__ __launch_bounds__(EC3D_THREADS) __attribute__((amdgpu_waves_per_eu(4)
 // (p_old, ap_old) and those of it + 1 written to (p_new, ap_new): other workgroups read the old values of cells this
 // one owns (rim, edge, the planes at a segment's ends), so the update cannot be in place.  Saves the 8 B per row P
 // costs to re-read and one launch; every stored value and every product is K5's followed by K1's.
-template <int FMT, bool NT, bool ZM, bool TAIL, bool PATCH, bool HS = false>
-__global__ __launch_bounds__(EC3D_THREADS) __attribute__((amdgpu_waves_per_eu(4))) void k51_p_spmv_dot(
+template <int FMT, bool NT, bool ZM, bool TAIL, bool PATCH, bool HS = false, bool PAIR = false>
+__global__ __launch_bounds__(EC3D_WG_THREADS) __attribute__((amdgpu_waves_per_eu(4))) void k51_p_spmv_dot(
     MatDev<FMT> A, EC3D_SWEEP_OF(ZM) sw, RedSrc src, SolverState *st, int it, const double *__restrict__ rv,
     const double *__restrict__ p_old, const double *__restrict__ ap_old, double *__restrict__ p_new,
     double *__restrict__ ap_new, double *__restrict__ r0, double *__restrict__ part, double *hist, int64_t hist_cap)
 {
-    __shared__ double lds[8];
+    __shared__ double lds[(PAIR ? 2 : 1) * 8];
     EC3D_TBL_DECL;
     const int slot[2] = {P_RR, P_RR0N};
     PartialsEarly<2> pe;
-    partials_request<2>(src, slot, pe);
+    partials_request<2, PAIR>(src, slot, pe);
     const double bnorm = st->bnorm, tol = st->tol, alpha = st->alpha, omega = st->omega, rr0 = st->rr0[it & 1];
     TableEarly te;
     table_request<FMT>(A, te);
@@ -2196,7 +2234,7 @@ __global__ __launch_bounds__(EC3D_THREADS) __attribute__((amdgpu_waves_per_eu(4)
         if (si < it || (si == it && kind == 1)) return;
     }
     double d[2];
-    partials_finish<2>(src, slot, pe, d, lds);
+    partials_finish<2, PAIR>(src, slot, pe, d, lds);
     const Ec3dNorm rn = ec3d_rnorm_step(d[0], bnorm, tol);
     // (the second launch of a split K5-in-K1 -- z-slab, interior planes behind the boundary planes -- leaves the state
     // alone: the first one has written it, and the restart counter must count once)
@@ -2219,11 +2257,11 @@ __global__ __launch_bounds__(EC3D_THREADS) __attribute__((amdgpu_waves_per_eu(4)
     double acc[1] = {0.0};
     // (Round 6 measured AP.R0's products a step LATER -- R0's pair still requested behind the step, but waited for behind the
     // next step's plane above: 1185-1190 us either way at 512^3, profiles/r06_patch_requests_512.log; not kept.)
-    walk_spmv<FMT, ZM, FMT != FMT_SAV, PATCH>(A, sw, pp, [&](int64_t tile, auto fc) {
+    walk_spmv<FMT, ZM, FMT != FMT_SAV, PATCH, PAIR>(A, sw, pp, [&](int64_t tile, auto fc) {
         EC3D_ROW_S;
         double s0, s1;
         d2 pc; // the new P[r], P[r+1]
-        spmv_pair<FMT, ZM, TAIL, NT, PATCH>(A, sw, pp, tbl, stg, pstep, VecFusedP{rv, p_old, ap_old, beta, omega, restart}, r, tile,
+        spmv_pair<FMT, ZM, TAIL, NT, PATCH, PAIR>(A, sw, pp, tbl, stg, pstep, VecFusedP{rv, p_old, ap_old, beta, omega, restart}, r, tile,
                                             (bool)fc, zr, s0, s1, pc);
         // R0's pair BEHIND the step, a memory round trip of its own.  Requested with the step's first requests it loses
         // (round 3: 1176 -> 1206 us), and so it does behind the arrival of the plane above, with the rim row (round 6:
@@ -2248,10 +2286,10 @@ __global__ __launch_bounds__(EC3D_THREADS) __attribute__((amdgpu_waves_per_eu(4)
         acc[0] = acc[0] + s0 * q.x;
         acc[0] = acc[0] + s1 * q.y;
     });
-    block_sum<1>(acc, lds);
+    block_sum<1, PAIR>(acc, lds);
     {
         const int pslot_[1] = {P_D1};
-        publish_partials<1>(sw, part, pslot_, acc, lds);
+        publish_partials<1, PAIR>(sw, part, pslot_, acc, lds);
     }
 }
 
@@ -2442,21 +2480,21 @@ __global__ __launch_bounds__(EC3D_THREADS) void k4d_x_r_update(SweepV sw, RedSrc
 // kernels' thread -> cell assignment (the library reports it as geometry 0, the twin follows).  The X update is the
 // deferred one of k4d_x_r_update: NEMAX = 0 leaves X alone, NEMAX = 4 applies ne (1 .. 4) pending updates, oldest first.
 // Both exits leave pending updates to k_x_flush (the ||S|| exit's X = X + alpha*P as a half update).
-template <int FMT, bool NT, int NEMAX>
-__global__ __launch_bounds__(EC3D_THREADS) __attribute__((amdgpu_waves_per_eu(NEMAX > 0 ? 2 : 4))) void k4s_x_r_spmv(
+template <int FMT, bool NT, int NEMAX, bool PAIR = false>
+__global__ __launch_bounds__(EC3D_WG_THREADS) __attribute__((amdgpu_waves_per_eu(NEMAX > 0 ? 2 : 4))) void k4s_x_r_spmv(
     MatDev<FMT> A, SweepZ sw, RedSrc src_ss, RedSrc src, SolverState *st, int it, int ne, int xm, XRing ring,
     const double *__restrict__ r0, double *__restrict__ x, double *__restrict__ rv, double *__restrict__ part, double *hist,
     int64_t hist_cap)
 {
     constexpr bool ZM = true, TAIL = false, PATCH = true;
-    __shared__ double lds[8];
+    __shared__ double lds[(PAIR ? 2 : 1) * 8];
     EC3D_TBL_DECL;
     const int slot_ss[1] = {P_SS};
     const int slot[2] = {P_D2, P_D3};
     PartialsEarly<1> pss;
     PartialsEarly<2> pd;
-    partials_request<1>(src_ss, slot_ss, pss);
-    partials_request<2>(src, slot, pd);
+    partials_request<1, PAIR>(src_ss, slot_ss, pss);
+    partials_request<2, PAIR>(src, slot, pd);
     const double alpha = st->alpha, bnorm = st->bnorm, tol = st->tol;
     double pa[EC3D_XD_MAX], po[EC3D_XD_MAX];
 #pragma unroll
@@ -2470,7 +2508,7 @@ __global__ __launch_bounds__(EC3D_THREADS) __attribute__((amdgpu_waves_per_eu(NE
     EC3D_REQUESTS_OUT;
     if (stop_it < it) return;
     double ss[1];
-    partials_finish<1>(src_ss, slot_ss, pss, ss, lds);
+    partials_finish<1, PAIR>(src_ss, slot_ss, pss, ss, lds);
     const Ec3dNorm sn = ec3d_snorm_step(ss[0], bnorm, tol);
     const bool lead = blockIdx.x == 0 && threadIdx.x == 0 && sw.part_off == 0; // (split launch: the first one writes the state)
     if (lead && hist && it <= hist_cap) hist[2 * (int64_t)(it - 1)] = sn.norm;
@@ -2485,7 +2523,7 @@ __global__ __launch_bounds__(EC3D_THREADS) __attribute__((amdgpu_waves_per_eu(NE
         return;
     }
     double d[2];
-    partials_finish<2>(src, slot, pd, d, lds);
+    partials_finish<2, PAIR>(src, slot, pd, d, lds);
     const double omega = ec3d_omega(d[0], d[1]);
     if (lead) {
         st->omega = omega;
@@ -2510,7 +2548,7 @@ __global__ __launch_bounds__(EC3D_THREADS) __attribute__((amdgpu_waves_per_eu(NE
     int pstep = 0;
     double acc[2] = {0.0, 0.0};
     const double *scur = ring.s[NEMAX > 0 ? ne - 1 : 0];
-    walk_spmv<FMT, ZM, FMT != FMT_SAV, PATCH>(A, sw, pp, [&](int64_t tile, auto fc) {
+    walk_spmv<FMT, ZM, FMT != FMT_SAV, PATCH, PAIR>(A, sw, pp, [&](int64_t tile, auto fc) {
         EC3D_ROW_S;
         // the operands that do not go through the stencil first: they are in flight while it runs
         const d2 q = load2<NT>(r0 + r);
@@ -2526,7 +2564,7 @@ __global__ __launch_bounds__(EC3D_THREADS) __attribute__((amdgpu_waves_per_eu(NE
         }
         double a0, a1;
         d2 sc; // S[r], S[r+1]
-        spmv_pair<FMT, ZM, TAIL, NT, PATCH>(A, sw, pp, tbl, stg, pstep, VecPlain{scur}, r, tile, (bool)fc, zr, a0, a1, sc);
+        spmv_pair<FMT, ZM, TAIL, NT, PATCH, PAIR>(A, sw, pp, tbl, stg, pstep, VecPlain{scur}, r, tile, (bool)fc, zr, a0, a1, sc);
         if (NEMAX > 0) {
 #pragma unroll
             for (int j = 0; j < NEMAX; ++j)
@@ -2546,10 +2584,10 @@ __global__ __launch_bounds__(EC3D_THREADS) __attribute__((amdgpu_waves_per_eu(NE
         acc[1] = acc[1] + e0 * q.x;
         acc[1] = acc[1] + e1 * q.y;
     });
-    block_sum<2>(acc, lds);
+    block_sum<2, PAIR>(acc, lds);
     {
         const int pslot_[2] = {P_RR, P_RR0N};
-        publish_partials<2>(sw, part, pslot_, acc, lds);
+        publish_partials<2, PAIR>(sw, part, pslot_, acc, lds);
     }
 }
 
@@ -2767,43 +2805,54 @@ static constexpr bool form_possible(const SpmvForm &f)
     return (!f.tail || f.fmt != FMT_SAV) && (!f.zm || f.fmt != FMT_GENERIC) && (!f.patch || (f.zm && !f.tail && table)) &&
            (!f.il || (f.zm && !f.patch && f.fmt == FMT_SAV)) && (!f.hs || f.fmt == FMT_DICT7);
 }
+// (pair_kind: the bit of Sweep::pair that lets the family's launches run paired patch columns, ec3d_form_pair)
 struct SpmvFamily { // k_spmv, k_residual, k1_spmv_dot, k3_spmv_dots: every form, no HS
     static constexpr bool hs = false;
+    static constexpr int pair_kind = EC3D_PAIR_K13; // (k_spmv: EC3D_PAIR_SPMV, a kind of its own)
     static constexpr bool has(const SpmvForm &f) { return form_possible(f) && !f.hs; }
 };
 struct FusedFamily { // k23_s_spmv_dots, k51_p_spmv_dot: the 2-D-tile kernels only (ec3d_fused23, ec3d_fused51)
     static constexpr bool hs = true;
     static constexpr bool has(const SpmvForm &f) { return form_possible(f) && f.zm && f.patch && !f.tail; }
 };
+struct Fused23Family : FusedFamily { static constexpr int pair_kind = EC3D_PAIR_K23; };
+struct Fused51Family : FusedFamily { static constexpr int pair_kind = EC3D_PAIR_K51; };
 struct K4sFamily { // k4s_x_r_spmv: the dictionary cube on 2-D tiles (ec3d_k4s), each with NEMAX = 0 and 4
     static constexpr bool hs = false;
+    static constexpr int pair_kind = EC3D_PAIR_K4S;
     static constexpr bool has(const SpmvForm &f) { return FusedFamily::has(f) && f.fmt == FMT_DICT7 && !f.hs; }
 };
-template <int FMT_, bool NT_, bool ZM_, bool TAIL_, bool PATCH_, bool HS_> struct FormTag { // the kernels' template arguments
+template <int FMT_, bool NT_, bool ZM_, bool TAIL_, bool PATCH_, bool HS_, bool PAIR_> struct FormTag { // the kernels' template arguments
     static constexpr int FMT = FMT_;
-    static constexpr bool NT = NT_, ZM = ZM_, TAIL = TAIL_, PATCH = PATCH_, HS = HS_;
+    static constexpr bool NT = NT_, ZM = ZM_, TAIL = TAIL_, PATCH = PATCH_, HS = HS_, PAIR = PAIR_;
+    // the launch: a paired instance runs half as many workgroups of twice the threads
+    static constexpr int threads = PAIR_ ? 2 * EC3D_THREADS : EC3D_THREADS;
+    static int grid(const Sweep &sw) { return PAIR_ ? sw.nblk / 2 : sw.nblk; }
 };
 // launch(FormTag, MatDev, sweep, LDS bytes) for the instance of FAMILY that the matrix and the sweep ask for
+// (pair_kind 0: this launch never pairs)
 template <class FAMILY, class LAUNCH>
-static void launch_form(const char *kernel, const MatView &A, const Sweep &sw, LAUNCH &&launch)
+static void launch_form(const char *kernel, const MatView &A, const Sweep &sw, LAUNCH &&launch, int pair_kind = FAMILY::pair_kind)
 {
     SpmvForm f = ec3d_spmv_form(A, sw);
     f.hs = f.hs && FAMILY::hs;
+    f.pair = ec3d_form_pair(f, sw, pair_kind);
     const size_t lds = ec3d_form_lds(A, f);
     bool found = false;
     auto with_fmt = [&](auto FMT) {
-        tag_bools([&](auto NT, auto ZM, auto TAIL, auto PATCH, auto IL, auto HS) {
+        tag_bools([&](auto NT, auto ZM, auto TAIL, auto PATCH, auto IL, auto HS, auto PAIR) {
             constexpr SpmvForm cf{decltype(FMT)::value,   decltype(NT)::value, decltype(ZM)::value, decltype(TAIL)::value,
-                                  decltype(PATCH)::value, decltype(IL)::value, decltype(HS)::value};
-            if constexpr (FAMILY::has(cf)) {
+                                  decltype(PATCH)::value, decltype(IL)::value, decltype(HS)::value, decltype(PAIR)::value};
+            // (paired instances: the dictionary cube's 2-D tiles only, what ec3d_form_pair can ask for)
+            if constexpr (FAMILY::has(cf) && (!cf.pair || (cf.patch && cf.fmt == FMT_DICT7 && !cf.hs))) {
                 // the kernels have no parameter of their own for the interleaved march: on the structured form, which has
                 // no tail, TAIL = true stands for it (EC3D_IL)
-                using T = FormTag<cf.fmt, cf.nt, cf.zm, cf.tail || cf.il, cf.patch, cf.hs>;
+                using T = FormTag<cf.fmt, cf.nt, cf.zm, cf.tail || cf.il, cf.patch, cf.hs, cf.pair>;
                 found = true;
                 if constexpr (cf.zm) launch(T{}, mat_dev<cf.fmt>(A), sweep_z(sw), lds);
                 else launch(T{}, mat_dev<cf.fmt>(A), sw, lds);
             }
-        }, f.nt, f.zm, f.tail, f.patch, f.il, f.hs);
+        }, f.nt, f.zm, f.tail, f.patch, f.il, f.hs, f.pair);
     };
     switch (f.fmt) {
     case FMT_SAV: with_fmt(std::integral_constant<int, FMT_SAV>{}); break;
@@ -2855,8 +2904,8 @@ void ec3d_launch_spmv(const MatView &A, const Sweep &sw, const double *x, double
 {
     launch_form<SpmvFamily>("k_spmv", A, sw, [&](auto t, const auto &Ad, const auto &swk, size_t lds) {
         using T = decltype(t);
-        k_spmv<T::FMT, T::NT, T::ZM, T::TAIL, T::PATCH><<<sw.nblk, EC3D_THREADS, lds, s>>>(Ad, swk, x, y);
-    });
+        k_spmv<T::FMT, T::NT, T::ZM, T::TAIL, T::PATCH, T::PAIR><<<T::grid(sw), T::threads, lds, s>>>(Ad, swk, x, y);
+    }, EC3D_PAIR_SPMV);
 }
 
 void ec3d_launch_residual(const MatView &A, const Sweep &sw, const double *x, const double *b, double *r,
@@ -2864,7 +2913,7 @@ void ec3d_launch_residual(const MatView &A, const Sweep &sw, const double *x, co
 {
     launch_form<SpmvFamily>("k_residual", A, sw, [&](auto t, const auto &Ad, const auto &swk, size_t lds) {
         using T = decltype(t);
-        k_residual<T::FMT, T::NT, T::ZM, T::TAIL, T::PATCH><<<sw.nblk, EC3D_THREADS, lds, s>>>(Ad, swk, x, b, r, r0, p, part);
+        k_residual<T::FMT, T::NT, T::ZM, T::TAIL, T::PATCH, T::PAIR><<<T::grid(sw), T::threads, lds, s>>>(Ad, swk, x, b, r, r0, p, part);
     });
 }
 
@@ -2888,7 +2937,7 @@ void ec3d_launch_k1(const MatView &A, const Sweep &sw, const SolverState *st, in
 {
     launch_form<SpmvFamily>("k1_spmv_dot", A, sw, [&](auto t, const auto &Ad, const auto &swk, size_t lds) {
         using T = decltype(t);
-        k1_spmv_dot<T::FMT, T::NT, T::ZM, T::TAIL, T::PATCH><<<sw.nblk, EC3D_THREADS, lds, s>>>(Ad, swk, st, it, p, r0, ap, part);
+        k1_spmv_dot<T::FMT, T::NT, T::ZM, T::TAIL, T::PATCH, T::PAIR><<<T::grid(sw), T::threads, lds, s>>>(Ad, swk, st, it, p, r0, ap, part);
     });
 }
 
@@ -2905,7 +2954,7 @@ void ec3d_launch_k3(const MatView &A, const Sweep &sw, SolverState *st, int it, 
 {
     launch_form<SpmvFamily>("k3_spmv_dots", A, sw, [&](auto t, const auto &Ad, const auto &swk, size_t lds) {
         using T = decltype(t);
-        k3_spmv_dots<T::FMT, T::NT, T::ZM, T::TAIL, T::PATCH><<<sw.nblk, EC3D_THREADS, lds, s>>>(Ad, swk, st, it, sv, as, part);
+        k3_spmv_dots<T::FMT, T::NT, T::ZM, T::TAIL, T::PATCH, T::PAIR><<<T::grid(sw), T::threads, lds, s>>>(Ad, swk, st, it, sv, as, part);
     });
 }
 
@@ -2914,9 +2963,9 @@ void ec3d_launch_k3(const MatView &A, const Sweep &sw, SolverState *st, int it, 
 void ec3d_launch_k23(const MatView &A, const Sweep &sw, const RedSrc &src, SolverState *st, int it, const double *r,
                      const double *ap, double *sv, double *as, double *part, hipStream_t s)
 {
-    launch_form<FusedFamily>("k23_s_spmv_dots", A, sw, [&](auto t, const auto &Ad, const auto &swk, size_t lds) {
+    launch_form<Fused23Family>("k23_s_spmv_dots", A, sw, [&](auto t, const auto &Ad, const auto &swk, size_t lds) {
         using T = decltype(t);
-        k23_s_spmv_dots<T::FMT, T::NT, T::ZM, T::TAIL, T::PATCH, T::HS><<<sw.nblk, EC3D_THREADS, lds, s>>>(
+        k23_s_spmv_dots<T::FMT, T::NT, T::ZM, T::TAIL, T::PATCH, T::HS, T::PAIR><<<T::grid(sw), T::threads, lds, s>>>(
             Ad, swk, src, st, it, r, ap, sv, as, part);
     });
 }
@@ -2925,9 +2974,9 @@ void ec3d_launch_k51(const MatView &A, const Sweep &sw, const RedSrc &src, Solve
                      const double *p_old, const double *ap_old, double *p_new, double *ap_new, double *r0, double *part,
                      double *hist, int64_t hist_cap, hipStream_t s)
 {
-    launch_form<FusedFamily>("k51_p_spmv_dot", A, sw, [&](auto t, const auto &Ad, const auto &swk, size_t lds) {
+    launch_form<Fused51Family>("k51_p_spmv_dot", A, sw, [&](auto t, const auto &Ad, const auto &swk, size_t lds) {
         using T = decltype(t);
-        k51_p_spmv_dot<T::FMT, T::NT, T::ZM, T::TAIL, T::PATCH, T::HS><<<sw.nblk, EC3D_THREADS, lds, s>>>(
+        k51_p_spmv_dot<T::FMT, T::NT, T::ZM, T::TAIL, T::PATCH, T::HS, T::PAIR><<<T::grid(sw), T::threads, lds, s>>>(
             Ad, swk, src, st, it, r, p_old, ap_old, p_new, ap_new, r0, part, hist, hist_cap);
     });
 }
@@ -2987,10 +3036,12 @@ void ec3d_launch_k4s(const MatView &A, const Sweep &sw, const RedSrc &src_ss, co
     launch_form<K4sFamily>("k4s_x_r_spmv", A, sw, [&](auto t, const auto &Ad, const auto &swk, size_t lds) {
         using T = decltype(t);
         tag_bools([&](auto APPLY) { // NEMAX: 0 leaves X alone, 4 applies up to four updates
-            k4s_x_r_spmv<T::FMT, T::NT, decltype(APPLY)::value ? 4 : 0><<<sw.nblk, EC3D_THREADS, lds, s>>>(
-                Ad, swk, src_ss, src, st, it, ne, xm, ring, r0, x, r, part, hist, hist_cap);
+            // (the applying form holds 148 registers, three waves per SIMD: not a whole number of paired workgroups)
+            if constexpr (!(decltype(APPLY)::value && T::PAIR))
+                k4s_x_r_spmv<T::FMT, T::NT, decltype(APPLY)::value ? 4 : 0, T::PAIR><<<T::grid(sw), T::threads, lds, s>>>(
+                    Ad, swk, src_ss, src, st, it, ne, xm, ring, r0, x, r, part, hist, hist_cap);
         }, ne != 0);
-    });
+    }, ne != 0 ? 0 : (int)K4sFamily::pair_kind);
 }
 
 // A GROUP of X updates -- iterations first .. first + count - 1 -- applied by a launch of its own on a second stream, beside

@@ -53,6 +53,18 @@ extern "C" int ec3d_get_fusion(ec3d_handle c, int32_t *k2_in_k3, int32_t *k5_in_
     return 0;
 }
 
+// patch rows per workgroup of a launch kind on this handle: 8 = paired patch columns, 4 = plain 2-D tiles, 0 = no 2-D tiles
+extern "C" int ec3d_get_patch_rows(ec3d_handle c, int kind, int32_t *rows)
+{
+    int rc = ec3d_need_matrix(c, "ec3d_get_patch_rows");
+    if (rc) return rc;
+    if (kind < 0 || kind > 4 || !rows) return 2;
+    const Sweep &ss = c->sweep_s;
+    const bool dict = c->A.ncls > 0 && !c->A.sav;
+    *rows = !(ss.patch_npx > 0 && dict) ? 0 : (ss.pair & (1 << kind)) ? 2 * EC3D_PY : EC3D_PY;
+    return 0;
+}
+
 extern "C" int ec3d_get_x_interval(ec3d_handle c, int32_t *iterations)
 {
     int rc = ec3d_need_matrix(c, "ec3d_get_x_interval");

@@ -2,8 +2,9 @@
 // structured A-V form, and the two small rules that go with them (host only: no HIP call, no kernels, no handle): the
 // shape of the runtime-shaped 2-D tiles and their per-tile tables, the z segments of a z-marching grid, the U mask and
 // the work list of the interleaved z-march, the XCD-local order of a list of U tiles, and the interior / boundary lists
-// of a z-slab.  choose_sweep decides WHEN each is used and uploads the result; the arithmetic lives here so that it
-// runs without a GPU.  tests/test_sweep_lists_host.py checks every list against a numpy restatement.
+// of a z-slab; and which launches of the 2-D tiles run paired patch columns (ec3d_patch_pair_virtual is the one function
+// here that the kernels call too).  choose_sweep decides WHEN each is used and uploads the result; the arithmetic lives
+// here so that it runs without a GPU.  tests/test_sweep_lists_host.py checks every list against a numpy restatement.
 #pragma once
 #include <algorithm>
 #include <array>
@@ -103,6 +104,47 @@ inline void ec3d_class_runs(const uint8_t *cls, int64_t planes, int64_t kdz, int
             flag[(size_t)(k * tpp + q)] = same ? 1 : 0;
         }
 }
+
+// Paired patch columns (patch_pair with eight patch rows, ec3d_kernels.hip): one 512-thread workgroup hosts two of the
+// z-marching launch's workgroups -- "virtual" workgroups from here on -- whose patches are y-neighbours, so that the rows
+// on either side of their common boundary travel through the LDS exchange instead of being requested as rim rows.
+// Virtual workgroup v is what workgroup v of the unpaired launch is (walk_zm): XCD label v % 8, column
+// (v % 8) * cpx + (v / 8) % cpx with cpx = tpp / 8, z segment (v / 8) / cpx; patch q of a plane lies at (q % npx, q / npx).
+// The rule: 2-D tiles, an undivided handle (no z-slab, no rank driver), every XCD label's run of cpx columns made of
+// whole patch rows and an even number of them (so no pair straddles two runs), nseg segments of pps planes each that
+// cover the nplanes planes exactly (both halves of a pair march the same planes, and so do all pairs of a segment).
+// A launch the rule refuses runs unpaired.
+#if defined(__HIPCC__)
+#define EC3D_PAIR_HD __host__ __device__
+#else
+#define EC3D_PAIR_HD
+#endif
+inline bool ec3d_patch_pairs_ok(int64_t tpp, int64_t npx, int64_t nplanes, int64_t pps, int64_t nblk, bool slab, bool dist)
+{
+    if (slab || dist || tpp <= 0 || npx <= 0 || pps <= 0 || nblk <= 0) return false;
+    if (tpp % 8) return false; // the last XCD run would be short
+    const int64_t cpx = tpp / 8;
+    if (cpx % (2 * npx)) return false; // an odd number of patch rows in an XCD run, or a run that starts inside one
+    if (nblk % tpp) return false;
+    const int64_t nseg = nblk / tpp;
+    return nseg * pps == nplanes; // segments of equal length, none empty
+}
+// The virtual workgroup that half `half` (0, 1) of physical workgroup `phys` hosts.  Physical workgroup phys keeps the XCD
+// label phys % 8; within the label the pairs are numbered as their lower halves are among the unpaired workgroups
+// (segment outermost, then patch row pair, then patch column), the upper half lying npx columns further on.
+EC3D_PAIR_HD inline int ec3d_patch_pair_virtual(int tpp, int npx, int phys, int half)
+{
+    const int cpx = tpp >> 3, hc = cpx >> 1;
+    const int c = phys & 7, sgp = phys >> 3;
+    const int seg = sgp / hc, jj = sgp - seg * hc;
+    const int pr = jj / npx, px = jj - pr * npx;
+    return 8 * (seg * cpx + (2 * pr + half) * npx + px) + c;
+}
+// launch kinds that can pair (bits of Sweep::pair; bit k = kind k of ec3d_get_patch_rows): the bare SpMV, K2-in-K3 (S
+// formed), K5-in-K1 (P formed), K4 in SpMV form without the X update, and the setup residual, K1 and K3
+enum { EC3D_PAIR_SPMV = 1, EC3D_PAIR_K23 = 2, EC3D_PAIR_K51 = 4, EC3D_PAIR_K4S = 8, EC3D_PAIR_K13 = 16, EC3D_PAIR_ALL = 31 };
+// the kinds that pair when nobody asks (vectors beyond the caches): those that won their A/B at 512^3, docs/rounds/r08.md
+enum { EC3D_PAIR_DEFAULT_BIG = EC3D_PAIR_SPMV | EC3D_PAIR_K23 };
 
 // z segments per column of a z-marching grid of `cols` columns that wants want_s workgroups, at most max_seg
 inline int64_t ec3d_zm_segments(int64_t want_s, int64_t cols, int64_t max_seg, bool explicit_request)

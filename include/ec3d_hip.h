@@ -605,6 +605,11 @@ int ec3d_get_ulist(ec3d_handle h, int32_t *tiles); /* ulist_n entries */
  * z-marching workgroup keeps its class bytes in registers over such a step.  *count = number of flags (0: this matrix
  * has none and the kernels load the class bytes at every step); flags == NULL: the count only; at most cap are written. */
 int ec3d_get_class_runs(ec3d_handle h, int64_t *count, uint8_t *flags, int64_t cap);
+/* Patch rows per workgroup of one kind of launch on the 2-D tiles: 4, or 8 where two y-adjacent patch columns are marched
+ * by one workgroup of 512 threads ("paired": their common boundary travels through LDS; results are the same bits).
+ * kind 0: the bare SpMV (k_spmv); 1: K2 inside K3; 2: K5 inside K1; 3: K4 in SpMV form (its launches that leave X alone);
+ * 4: the setup residual, K1 and K3.  *rows = 0 on a handle without 2-D tiles.  EC3D_PATCH=2 pairs wherever the grid allows, EC3D_PATCH=1 never. */
+int ec3d_get_patch_rows(ec3d_handle h, int kind, int32_t *rows);
 /* The tiles (512 rows each) every workgroup of a launch visits, in order: workgroup w visits
  * tiles[offsets[w] .. offsets[w+1]).  which as above.
  * Each thread t of a workgroup owns rows tile*512 + 2t, 2t+1 (or the two cells of a patch, ec3d_geom::patch_x) and
