@@ -2,6 +2,7 @@
 // copies, and the option / introspection entry points of the C ABI (include/ec3d_hip.h).
 #include "../../include/ec3d_hip.h"
 #include "ec3d_internal.hpp"
+#include "ec3d_split_sweeps.hpp"
 #include "ec3d_sweep_lists.hpp"
 
 #include <climits>
@@ -230,7 +231,7 @@ void ec3d_free_matrix(ec3d_ctx *c)
     c->ii_list.reset();
     c->ib_list.reset();
     c->us_host.clear();
-    c->can_vsplit = false;
+    c->split_v.ok = false;
     c->n_ref = 0;
     c->plane = c->pitch = c->nCd = 0;
     c->halo = 0;
@@ -331,6 +332,15 @@ struct SweepKnobs {
     std::optional<int> fuse23 = env("EC3D_FUSE23"), fuse51 = env("EC3D_FUSE51"), k4s = env("EC3D_K4S");
 };
 
+// Rows the kernels actually stream.  The structured form's device numbering holds a whole grid-shaped block for U, of
+// which only the tiles with an unknown are ever touched: BASELINE config 5 (LIM at 384 x 192 x 128) has 37.7 M device
+// rows but streams 29.8 M, and belongs with the sizes where a vector or two still find room in the Infinity Cache
+// (measured, profiles/r04_keep_and_plans_config5.log: 839 -> 814-819 us per iteration with the mid-size policy).
+static inline int64_t rows_streamed(const ec3d_ctx *c)
+{
+    return (c->A.sav && c->A.ulist) ? (c->A.ntiles_front + (int64_t)c->A.ulist_n) * EC3D_TILE : c->A.n_pad;
+}
+
 // Launch geometry.  Vector kernels (K2, K4, K5): plain XCD-aware grid stride over 512-row tiles.
 // SpMV kernels: the same, or -- when a plane of the grid is a whole number of tiles -- the z-marching
 // map (one xy position per workgroup, consecutive planes per step; ec3d_tile_of in ec3d_kernels.hip).
@@ -362,11 +372,7 @@ static int choose_sweep(ec3d_ctx *c)
         sw.ntiles = 3 * sw.win_nt;
         sw.nown = 0;
     }
-    // Rows the kernels actually stream.  The structured form's device numbering holds a whole grid-shaped block for U, of
-    // which only the tiles with an unknown are ever touched: BASELINE config 5 (LIM at 384 x 192 x 128) has 37.7 M device
-    // rows but streams 29.8 M, and belongs with the sizes where a vector or two still find room in the Infinity Cache
-    // (measured, profiles/r04_keep_and_plans_config5.log: 839 -> 814-819 us per iteration with the mid-size policy).
-    const int64_t rows_eff = (c->A.sav && c->A.ulist) ? (c->A.ntiles_front + (int64_t)c->A.ulist_n) * EC3D_TILE : c->A.n_pad;
+    const int64_t rows_eff = rows_streamed(c);
     {
         const int ntreq = knob.nt.value_or(c->nt_request); // read here too: sweeps of launch knobs in one process
         // nontemporal streams from 4.5 Mi rows (tools/keep_sweep.py: at 4 Mi rows = 32 MiB per vector plain caching is
@@ -646,111 +652,25 @@ static int choose_sweep(ec3d_ctx *c)
             c->us_host = src;
         }
     }
-    // z-slab of the single-component operator on a z-marching grid: K1/K3 can be split into an interior
-    // launch (planes 1 .. np-2, independent of the halo) and a boundary launch (planes 0 and np-1)
-    c->can_overlap = false;
-    c->sweep_int = c->sweep_bnd = ss;
-    int parts = ss.nblk;
-    if (c->halo > 0 && c->nown == 0 && ss.zm_tpp > 0) {
-        const int64_t np = sw.ntiles / ss.zm_tpp; // planes held (n is a whole number of planes here)
-        if (np * ss.zm_tpp == sw.ntiles && np >= 10) {
-            Sweep &si = c->sweep_int, &sb = c->sweep_bnd;
-            const int64_t tpp = ss.zm_tpp, npl = np - 2, cols = (tpp + 7) / 8 * 8;
-            int64_t nseg = std::max<int64_t>(1, ((int64_t)ss.nblk + cols / 2) / cols);
-            nseg = std::min<int64_t>(nseg, std::max<int64_t>(1, npl / 8));
-            si.zm_pl0 = 1;
-            si.zm_npl = (int)npl;
-            si.zm_pps = (int)((npl + nseg - 1) / nseg);
-            si.nblk = (int)(cols * nseg);
-            si.part_off = 0;
-            sb.bnd_last = (int)(np - 1);
-            sb.patch_npx = 0; // the boundary planes go through the plain kernels: 512 consecutive cells per tile
-            sb.nblk = (int)std::min<int64_t>(2 * tpp, 768);
-            sb.part_off = si.nblk;
-            parts = si.nblk + sb.nblk;
-            c->can_overlap = true;
-        }
-    }
-    // z-slab of the STRUCTURED A-V form with tile-aligned planes (the windowed sweep above): K1 / K3 as interior + boundary
-    // launch too.  The A rows and the U rows read A one plane away, the one-sided A-U stencils (src/EC3D.f90:697-706) read
-    // U two planes away, so the two owned planes next to each cut are "boundary" in all four blocks.  Interior launch: the
-    // z-march over the window narrowed by two planes at both ends in every A block, then the U tiles of those planes (in
-    // the XCD-local order of the whole list).  Boundary launch: no front sweep at all -- the tiles of the four outer planes
-    // of the three A blocks and the U tiles there, as ONE list (a listed tile starts its march afresh, which is what a
-    // tile of a lone plane needs anyway).  Every owned tile is visited by exactly one of the two (ec3d_get_visit_order 3 / 4).
+    // z-slab: K1 / K3 (single-component operator, or the structured A-V form on a plane window) and the 2-D-tile kernels of
+    // the three-launch iteration as boundary + interior launch.  ec3d_split_sweeps.hpp has the rules; the lists go up here.
     c->ib_list.reset();
     c->ii_list.reset();
-    if (A.sav && c->halo > 0 && sw.win_nt > 0 && ss.zm_tpp > 0 && ss.rp_px == 0 && c->A.ulist &&
-        (int)c->A.ulist_host.size() == c->A.ulist_n) {
-        const int64_t tpp = ss.zm_tpp, npo = sw.win_nt / tpp, H = 2, blk = sw.win_blk, p0 = sw.win_t0 / tpp;
-        if (npo * tpp == sw.win_nt && p0 * tpp == sw.win_t0 && npo >= 2 * H + 2) {
-            const int64_t npi = npo - 2 * H;
-            std::vector<int32_t> ui, ub, bl;
-            if (ec3d_slab_split_lists(c->A.ulist_host, tpp, blk, p0, npo, H, ui, ub, bl)) {
-                Sweep &si = c->sweep_int, &sb = c->sweep_bnd;
-                const int64_t cols = (tpp + 7) / 8 * 8;
-                int64_t nseg = std::max<int64_t>(1, (int64_t)ss.nblk / cols);
-                nseg = std::min<int64_t>(nseg, std::max<int64_t>(1, 3 * npi / 2));
-                si.win_t0 = sw.win_t0 + H * tpp;
-                si.win_nt = npi * tpp;
-                si.ntiles = 3 * si.win_nt;
-                si.zm_pps = (int)((3 * npi + nseg - 1) / nseg);
-                si.nblk = (int)(cols * nseg);
-                si.part_off = 0;
-                // the interior U tiles in the XCD-local order (as us_list above): by column into eight shares, a share plane by plane
-                std::vector<int32_t> perm;
-                if (!ui.empty()) {
-                    perm = ec3d_xcd_local_order(ui, tpp, si.nblk);
-                    EC3D_HIP(upload_list(c->ii_list, perm));
-                }
-                si.ulist = c->ii_list;
-                si.ulist_n = (int)perm.size();
-                // the boundary list: A tiles of planes 0, 1, npo-2, npo-1 of every block, plane by plane, then the U tiles there
-                EC3D_HIP(upload_list(c->ib_list, bl));
-                sb.ntiles = 0; // (no front sweep: ec3d_tile_of / walk_zm find no plane whose tile exists)
-                sb.win_nt = 0;
-                sb.ulist = c->ib_list;
-                sb.ulist_n = (int)bl.size();
-                sb.nblk = (int)std::max<int64_t>(8, std::min<int64_t>((int64_t)bl.size(), 768) / 8 * 8);
-                sb.part_off = si.nblk;
-                parts = std::max(parts, si.nblk + sb.nblk);
-                c->can_overlap = true;
-            }
+    c->split_s = ec3d_split_spmv_planes(sw, ss, c->halo, c->nown);
+    if (!c->split_s.ok && A.sav && c->A.ulist && (int)c->A.ulist_host.size() == c->A.ulist_n) {
+        std::vector<int32_t> ii, ib;
+        c->split_s = ec3d_split_spmv_av(sw, ss, c->halo, c->A.ulist_host, ii, ib);
+        if (c->split_s.ok) {
+            EC3D_HIP(upload_list(c->ii_list, ii));
+            EC3D_HIP(upload_list(c->ib_list, ib));
+            c->split_s.inte.ulist = c->ii_list;
+            c->split_s.bnd.ulist = c->ib_list;
         }
     }
-    // z-slab of the single-component operator on 2-D tiles: the 2-D-tile kernels in two launches too -- planes 0 and np-1
-    // (one plane per workgroup: zm_plstep), then planes 1 .. np-2 -- for the producers of the exchanged vectors in the
-    // three-launch iteration (K4 in SpMV form makes R, K5-in-K1 the next AP; ec3d_multi.hip plan 4)
-    c->can_fsplit = false;
-    c->sweep_fb = c->sweep_fi = ss;
-    if (c->halo > 0 && c->nown == 0 && ss.zm_tpp > 0 && ss.patch_npx > 0) {
-        const int64_t np = sw.ntiles / ss.zm_tpp;
-        if (np * ss.zm_tpp == sw.ntiles && np >= 3) {
-            Sweep &fb = c->sweep_fb, &fi = c->sweep_fi;
-            const int64_t tpp = ss.zm_tpp, npl = np - 2, cols = (tpp + 7) / 8 * 8;
-            fb.zm_pl0 = 0;
-            fb.zm_plstep = (int)(np - 1);
-            fb.zm_npl = 2;
-            fb.zm_pps = 1;
-            fb.nblk = (int)(cols * 2);
-            fb.part_off = 0;
-            int64_t nseg = std::max<int64_t>(1, ((int64_t)ss.nblk + cols / 2) / cols);
-            nseg = std::min<int64_t>(nseg, std::max<int64_t>(1, npl / 2));
-            fi.zm_pl0 = 1;
-            fi.zm_npl = (int)npl;
-            fi.zm_pps = (int)((npl + nseg - 1) / nseg);
-            fi.nblk = (int)(cols * nseg);
-            fi.part_off = fb.nblk;
-            parts = std::max(parts, fb.nblk + fi.nblk);
-            c->can_fsplit = true;
-        }
-    }
-    // room for a vector kernel in two launches as well (boundary list <= 256 workgroups)
-    const int vmax = std::max(sw.nblk, std::max(c->sweep_k2.nblk, c->sweep_k5.nblk));
-    const int ps = std::max(vmax + 256, std::max(ss.nblk, parts));
-    sw.pstride = ss.pstride = c->sweep_int.pstride = c->sweep_bnd.pstride = ps;
-    c->sweep_fb.pstride = c->sweep_fi.pstride = ps;
-    c->sweep_k2.pstride = c->sweep_k5.pstride = ps;
+    c->split_f = ec3d_split_tiles2d(sw, ss, c->halo, c->nown);
+    const int ps = ec3d_partial_stride(sw, c->sweep_k2, c->sweep_k5, ss, c->split_s, c->split_f, c->split_v);
+    for (Sweep *s : {&sw, &ss, &c->sweep_k2, &c->sweep_k5, &c->split_s.bnd, &c->split_s.inte, &c->split_f.bnd, &c->split_f.inte})
+        s->pstride = ps;
     return 0;
 }
 
@@ -1104,8 +1024,7 @@ int ec3d_spare_pair(ec3d_ctx *c)
     // (profiles/r04_deferred_x_mid_sizes.log): 256 x 256 x 80 -2.7 %, A-V 8 M rows -2.2 %, 256^3 -1.9 %, A-V 21 M rows and
     // config 5 -1.4 %, config 3 +0.2 % -- with ONE tile in flight in the launch without X and two in the applying one
     // (ec3d_launch_k4d picks by the vector plan), not the four / one of the big grids.
-    const int64_t rows_eff = (c->A.sav && c->A.ulist) ? (c->A.ntiles_front + (int64_t)c->A.ulist_n) * EC3D_TILE : c->A.n_pad;
-    int D = rows_eff >= (9 << 19) ? 4 : 1;
+    int D = rows_streamed(c) >= (9 << 19) ? 4 : 1;
     if (const char *e = getenv("EC3D_XDEFER")) D = std::max(1, std::min(EC3D_XD_MAX, atoi(e)));
     // (a z-slab that owns its vectors gets the rings too: whether they are used is the multi-rank driver's decision --
     // ec3d_ctx::slab_xd, slab_fused -- because every rank of the job has to run the same plan)
@@ -1216,12 +1135,12 @@ extern "C" int ec3d_set_workgroups(ec3d_handle c, int32_t nblk)
     if (c->have_matrix) {
         EC3D_HIP(hipSetDevice(c->device));
         // partial buffer depends on nblk; vectors are kept
+        c->split_v.ok = false; // the boundary/interior launches of K2 / K5 were derived from the old geometry:
+                               // ec3d_dist_set_boundary_rows has to be called again
         {
             int rc = choose_sweep(c);
             if (rc) return rc;
         }
-        c->can_vsplit = false; // the boundary/interior tile sweeps were derived from the old geometry:
-                               // ec3d_dist_set_boundary_rows has to be called again
         EC3D_HIP(c->partials.alloc((size_t)P_NSLOT * c->sweep.pstride));
         EC3D_HIP(hipMemset(c->partials, 0, (size_t)P_NSLOT * c->sweep.pstride * sizeof(double)));
         return ec3d_spare_pair(c);
@@ -1629,12 +1548,12 @@ static const Sweep &sweep_for(const ec3d_ctx *c, int which)
     switch (which) {
     case 1: return c->sweep_s;
     case 2: return ec3d_fused23(c) ? c->sweep_s : c->sweep_k2;
-    case 3: return c->sweep_int;
-    case 4: return c->sweep_bnd;
-    case 5: return c->sweep_vb;
-    case 6: return c->sweep_vi;
-    case 7: return c->sweep_fb; // boundary / interior launch of K4 in SpMV form and of K5-in-K1 (three-launch iteration)
-    case 8: return c->sweep_fi;
+    case 3: return c->split_s.inte;
+    case 4: return c->split_s.bnd;
+    case 5: return c->split_v.bnd;
+    case 6: return c->split_v.inte;
+    case 7: return c->split_f.bnd; // boundary / interior launch of K4 in SpMV form and of K5-in-K1 (three-launch iteration)
+    case 8: return c->split_f.inte;
     default: return ec3d_k4s(c) ? c->sweep_s : c->sweep;
     }
 }
@@ -1669,45 +1588,16 @@ extern "C" int ec3d_get_reduction_geometry(ec3d_handle c, int which, ec3d_geom *
     return 0;
 }
 
-// The tiles every workgroup visits, in order -- exactly what EC3D_SWEEP_BEGIN_ does on the device (same
-// ec3d_tile_of, same list rules).  The oracle's "GPU order" twin takes this as data.
-static void visit_of(const ec3d_ctx *c, const Sweep &sw, std::vector<std::vector<int32_t>> &out)
+// host copy of the tile list a sweep of this handle reads behind its front sweep (for ec3d_visit_of)
+static std::vector<int32_t> host_list_of(const ec3d_ctx *c, const Sweep &sw)
 {
-    const DevMatrix &A = c->A;
     std::vector<int32_t> ul;
-    if (sw.ulist_n > 0) {
-        if (sw.ulist == A.ulist) ul = A.ulist_host;
-        else if (sw.ulist == c->us_list && !c->us_host.empty()) ul = c->us_host; // the SpMV kernels' own order of the U tiles
-        else { // a tile list made elsewhere (K2/K5 split sweeps)
-            ul.resize((size_t)sw.ulist_n);
-            (void)hipMemcpy(ul.data(), sw.ulist, ul.size() * 4, hipMemcpyDeviceToHost);
-        }
-    }
-    if (sw.il_planes > 0) { // the interleaved z-march of the structured form: walk_zm_il, step by step
-        const int64_t tpp = sw.zm_tpp, P = sw.il_planes, blk_t = P * tpp;
-        for (int b = 0; b < sw.nblk; ++b) {
-            std::vector<int32_t> v;
-            const int64_t col = c->il_seg_host[(size_t)b * 4];
-            for (int64_t k = c->il_seg_host[(size_t)b * 4 + 1]; k < c->il_seg_host[(size_t)b * 4 + 2]; ++k) {
-                const int64_t t0 = k * tpp + col;
-                for (int d = 0; d < 3; ++d) v.push_back((int32_t)(t0 + d * blk_t));
-                if (ec3d_il_bit(c->il_umask_host.data(), sw.il_nw, col, k)) v.push_back((int32_t)(t0 + 3 * blk_t));
-            }
-            out.push_back(std::move(v));
-        }
-        return;
-    }
-    for (int b = 0; b < sw.nblk; ++b) {
-        std::vector<int32_t> v;
-        for (int64_t it = 0;; ++it) {
-            const int64_t tile = ec3d_tile_of(sw, b, it);
-            if (tile < 0) break;
-            v.push_back((int32_t)tile);
-        }
-        // a hole (-1) of the XCD-local list ends the workgroup's share
-        for (int64_t l = b; l < sw.ulist_n && ul[(size_t)l] >= 0; l += sw.nblk) v.push_back(ul[(size_t)l]);
-        out.push_back(std::move(v));
-    }
+    if (sw.ulist_n <= 0) return ul;
+    if (sw.ulist == c->A.ulist) return c->A.ulist_host;
+    if (sw.ulist == c->us_list && !c->us_host.empty()) return c->us_host; // the SpMV kernels' own order of the U tiles
+    ul.resize((size_t)sw.ulist_n); // a list made elsewhere (the split sweeps)
+    (void)hipMemcpy(ul.data(), sw.ulist, ul.size() * 4, hipMemcpyDeviceToHost);
+    return ul;
 }
 
 extern "C" int ec3d_get_visit_order(ec3d_handle c, int which, int32_t *nwg, int64_t *total, int32_t *offsets,
@@ -1716,7 +1606,8 @@ extern "C" int ec3d_get_visit_order(ec3d_handle c, int which, int32_t *nwg, int6
     int rc = ec3d_need_matrix(c, "ec3d_get_visit_order");
     if (rc) return rc;
     std::vector<std::vector<int32_t>> v;
-    visit_of(c, sweep_for(c, which), v);
+    const Sweep &sw = sweep_for(c, which);
+    ec3d_visit_of(sw, host_list_of(c, sw), c->il_seg_host, c->il_umask_host, v);
     int64_t tot = 0;
     for (auto &w : v) tot += (int64_t)w.size();
     *nwg = (int32_t)v.size();

@@ -2,6 +2,7 @@
 // eddy_currents_3d_amd/dist.py: the library launches, the host moves halos and sums between the stages.
 #include "../../include/ec3d_hip.h"
 #include "ec3d_internal.hpp"
+#include "ec3d_split_sweeps.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -66,88 +67,43 @@ extern "C" int ec3d_dist_set_boundary_rows(ec3d_handle c, int32_t nranges, const
     if (rc) return rc;
     if (nranges < 0 || (nranges > 0 && (!lo || !hi))) return 2;
     if (enabled) *enabled = 0;
-    // tiles the vector kernels visit: the front sweep and the occupied U tiles of the structured form
+    // (rule: ec3d_split_vec_rows; its tiles are the vector kernels' front sweep and the occupied U tiles of the structured form)
     const Sweep &sw = c->sweep;
-    std::vector<int32_t> visit((size_t)sw.ntiles);
-    for (int64_t t = 0; t < sw.ntiles; ++t) visit[(size_t)t] = (int32_t)ec3d_phys_tile(sw, t);
-    if (sw.ulist_n) {
-        std::vector<int32_t> ul((size_t)sw.ulist_n);
-        EC3D_HIP(hipMemcpy(ul.data(), sw.ulist, ul.size() * 4, hipMemcpyDeviceToHost));
-        visit.insert(visit.end(), ul.begin(), ul.end());
-    }
-    std::vector<int32_t> vb, vi;
-    for (int32_t t : visit) {
-        const int64_t r0 = (int64_t)t * EC3D_TILE, r1 = r0 + EC3D_TILE;
-        bool bnd = false;
-        for (int32_t q = 0; q < nranges && !bnd; ++q) bnd = lo[q] < r1 && hi[q] > r0;
-        (bnd ? vb : vi).push_back(t);
-    }
+    std::vector<int32_t> ul((size_t)sw.ulist_n), vb, vi;
+    if (sw.ulist_n) EC3D_HIP(hipMemcpy(ul.data(), sw.ulist, ul.size() * 4, hipMemcpyDeviceToHost));
+    SplitSweep k = ec3d_split_vec_rows(sw, ul, nranges, lo, hi, vb, vi);
     c->vb_list.reset();
     c->vi_list.reset();
-    c->can_vsplit = false;
-    if (vb.empty() || vi.empty()) return 0; // nothing to split (single rank, or a slab that is all boundary)
+    c->split_v.ok = false;
+    if (!k.ok) return 0; // nothing to split (single rank, or a slab that is all boundary)
     EC3D_HIP(c->vb_list.alloc(vb.size()));
     EC3D_HIP(c->vi_list.alloc(vi.size()));
     EC3D_HIP(hipMemcpy(c->vb_list, vb.data(), vb.size() * 4, hipMemcpyHostToDevice));
     EC3D_HIP(hipMemcpy(c->vi_list, vi.data(), vi.size() * 4, hipMemcpyHostToDevice));
-    auto list_sweep = [&](const int32_t *list, size_t len, int max_blk, int part_off) {
-        Sweep s = sw;
-        s.ntiles = 0; // list only
-        s.ulist = list;
-        s.ulist_n = (int)len;
-        s.nblk = (int)std::min<size_t>(len, (size_t)max_blk);
-        s.S = 0;
-        s.part_off = part_off;
-        return s;
-    };
-    c->sweep_vb = list_sweep(c->vb_list, vb.size(), 256, 0);
-    c->sweep_vi = list_sweep(c->vi_list, vi.size(), sw.nblk, c->sweep_vb.nblk);
-    c->can_vsplit = true;
+    k.bnd.ulist = c->vb_list;
+    k.inte.ulist = c->vi_list;
+    c->split_v = k;
     if (enabled) *enabled = 1;
     return 0;
 }
 
-// The same split for a z-slab of the SINGLE-COMPONENT operator whose planes are whole tiles, without tile lists: the boundary
-// launch takes the first and the last owned plane, the interior launch the planes between, both as windows of the ordinary
-// strided sweep (Sweep::win_*: logical tile t of the boundary launch is tile t of plane 0 for t < tpp, of plane np-1 after;
-// the interior launch starts at plane 1) -- a list-driven K2 / K5 costs 15-30 us more at 16 Mi rows than the strided one.
-// can K2 / K5 of this slab run as a launch over planes 0 and np-1 followed by one over the planes between?
+// The same split for a z-slab of the SINGLE-COMPONENT operator whose planes are whole tiles, without tile lists
+// (ec3d_split_vec_planes): can K2 / K5 of this slab run as a launch over planes 0 and np-1 followed by one over the planes
+// between?
 bool ec3d_dist_can_split_planes(const ec3d_ctx *c)
 {
-    const Sweep &ss = c->sweep_s, &k2 = c->sweep_k2;
-    if (c->A.sav || c->halo <= 0 || c->nown != 0 || k2.ulist_n != 0 || ss.zm_tpp <= 0 || k2.win_nt != 0) return false;
-    const int64_t tpp = ss.zm_tpp, total = k2.ntiles, np = total / tpp;
-    return np * tpp == total && np >= 3;
+    return ec3d_vec_planes_splittable(c->sweep_k2, c->sweep_s, c->A.sav, c->halo, c->nown);
 }
 
 int ec3d_dist_set_boundary_planes(ec3d_ctx *c, int32_t *enabled)
 {
     if (enabled) *enabled = 0;
-    const Sweep &ss = c->sweep_s, &k2 = c->sweep_k2;
     c->vb_list.reset();
     c->vi_list.reset();
-    c->can_vsplit = false;
-    if (!ec3d_dist_can_split_planes(c)) return 0;
-    const int64_t tpp = ss.zm_tpp, total = k2.ntiles;
-    Sweep vb = k2, vi = k2;
-    vb.ntiles = 2 * tpp;
-    vb.win_nt = tpp;
-    vb.win_blk = total - tpp;
-    vb.win_t0 = 0;
-    vb.S = 0;
-    vb.vec_depth = 1;
-    vb.nblk = (int)std::max<int64_t>(8, std::min<int64_t>(2 * tpp, 256) / 8 * 8);
-    vb.part_off = 0;
-    vi.ntiles = total - 2 * tpp;
-    vi.win_nt = vi.ntiles;
-    vi.win_blk = total;
-    vi.win_t0 = tpp;
-    vi.nblk = (int)std::min<int64_t>(k2.nblk, std::max<int64_t>(8, vi.ntiles / 8 * 8));
-    vi.S = k2.S > 0 ? vi.nblk / 8 : 0;
-    vi.part_off = vb.nblk;
-    c->sweep_vb = vb;
-    c->sweep_vi = vi;
-    c->can_vsplit = true;
+    c->split_v.ok = false;
+    const SplitSweep k = ec3d_split_vec_planes(c->sweep_k2, c->sweep_s, c->A.sav, c->halo, c->nown);
+    if (!k.ok) return 0;
+    c->split_v = k;
     if (enabled) *enabled = 1;
     return 0;
 }
@@ -178,8 +134,8 @@ extern "C" int ec3d_dist_step(ec3d_handle c, int32_t stage, int32_t it, double t
         c->run.ss_parts = 0;
     };
     auto need_split = [&]() {
-        if (!c->can_overlap) ec3d_set_error("ec3d_dist_step: this slab cannot split K1/K3 (see ec3d_can_overlap)");
-        return c->can_overlap;
+        if (!c->split_s.ok) ec3d_set_error("ec3d_dist_step: this slab cannot split K1/K3 (see ec3d_can_overlap)");
+        return c->split_s.ok;
     };
     switch (stage) {
     case EC3D_STAGE_RESID:
@@ -214,45 +170,45 @@ extern "C" int ec3d_dist_step(ec3d_handle c, int32_t stage, int32_t it, double t
         break;
     case EC3D_STAGE_K1_INT:
         if (!need_split()) return 3;
-        ec3d_launch_k1(A, c->sweep_int, c->state, it, ec3d_vec_at(c, EC3D_VEC_P, it), v[EC3D_VEC_R0], v[EC3D_VEC_AP],
+        ec3d_launch_k1(A, c->split_s.inte, c->state, it, ec3d_vec_at(c, EC3D_VEC_P, it), v[EC3D_VEC_R0], v[EC3D_VEC_AP],
                        c->partials, c->stream);
         break;
     case EC3D_STAGE_K1_BND:
         if (!need_split()) return 3;
-        ec3d_launch_k1(A, c->sweep_bnd, c->state, it, ec3d_vec_at(c, EC3D_VEC_P, it), v[EC3D_VEC_R0], v[EC3D_VEC_AP],
+        ec3d_launch_k1(A, c->split_s.bnd, c->state, it, ec3d_vec_at(c, EC3D_VEC_P, it), v[EC3D_VEC_R0], v[EC3D_VEC_AP],
                        c->partials, c->stream);
         fin(EC3D_BY_SPMV, 1u << P_D1, true);
         break;
     case EC3D_STAGE_K3_INT:
         if (!need_split()) return 3;
-        ec3d_launch_k3(A, c->sweep_int, c->state, it, ec3d_vec_at(c, EC3D_VEC_S, it), v[EC3D_VEC_AS], c->partials, c->stream);
+        ec3d_launch_k3(A, c->split_s.inte, c->state, it, ec3d_vec_at(c, EC3D_VEC_S, it), v[EC3D_VEC_AS], c->partials, c->stream);
         break;
     case EC3D_STAGE_K3_BND:
         if (!need_split()) return 3;
-        ec3d_launch_k3(A, c->sweep_bnd, c->state, it, ec3d_vec_at(c, EC3D_VEC_S, it), v[EC3D_VEC_AS], c->partials, c->stream);
+        ec3d_launch_k3(A, c->split_s.bnd, c->state, it, ec3d_vec_at(c, EC3D_VEC_S, it), v[EC3D_VEC_AS], c->partials, c->stream);
         fin_k3(true);
         break;
     case EC3D_STAGE_K2_BND:
     case EC3D_STAGE_K2_INT: {
-        if (!c->can_vsplit) {
+        if (!c->split_v.ok) {
             ec3d_set_error("ec3d_dist_step: call ec3d_dist_set_boundary_rows first");
             return 3;
         }
         const bool bnd = stage == EC3D_STAGE_K2_BND;
-        ec3d_launch_k2(bnd ? c->sweep_vb : c->sweep_vi, ec3d_src_of(c, EC3D_BY_SPMV), c->state, it, v[EC3D_VEC_R], v[EC3D_VEC_AP],
+        ec3d_launch_k2(bnd ? c->split_v.bnd : c->split_v.inte, ec3d_src_of(c, EC3D_BY_SPMV), c->state, it, v[EC3D_VEC_R], v[EC3D_VEC_AP],
                        ec3d_vec_at(c, EC3D_VEC_S, it), c->partials, c->stream);
         ec3d_after_s(c, it);
-        if (!bnd) c->run.ss_parts = c->sweep_vb.nblk + c->sweep_vi.nblk; // (both launches' partials, folded by K3's collapse launch)
+        if (!bnd) c->run.ss_parts = c->split_v.parts(); // (both launches' partials, folded by K3's collapse launch)
         break;
     }
     case EC3D_STAGE_K5_BND:
     case EC3D_STAGE_K5_INT:
-        if (!c->can_vsplit) {
+        if (!c->split_v.ok) {
             ec3d_set_error("ec3d_dist_step: call ec3d_dist_set_boundary_rows first");
             return 3;
         }
         // (deferred X update: the new P goes to the next buffer of the ring)
-        ec3d_launch_k5(stage == EC3D_STAGE_K5_BND ? c->sweep_vb : c->sweep_vi, ec3d_src_of(c, EC3D_BY_K4), c->state, it,
+        ec3d_launch_k5(stage == EC3D_STAGE_K5_BND ? c->split_v.bnd : c->split_v.inte, ec3d_src_of(c, EC3D_BY_K4), c->state, it,
                        v[EC3D_VEC_R], v[EC3D_VEC_AP], ec3d_vec_at(c, EC3D_VEC_P, it), ec3d_vec_at(c, EC3D_VEC_P, it + 1),
                        v[EC3D_VEC_R0], c->hist, c->hist_cap, c->stream);
         ec3d_after_p(c, it);
@@ -261,7 +217,7 @@ extern "C" int ec3d_dist_step(ec3d_handle c, int32_t stage, int32_t it, double t
     case EC3D_STAGE_K4F_INT:
     case EC3D_STAGE_K5F_BND:
     case EC3D_STAGE_K5F_INT: {
-        if (!c->can_fsplit || !c->slab_fused || !ec3d_k4s(c)) {
+        if (!c->split_f.ok || !c->slab_fused || !ec3d_k4s(c)) {
             ec3d_set_error("ec3d_dist_step: this slab does not run the three-launch iteration in split launches");
             return 3;
         }
@@ -296,7 +252,7 @@ int ec3d_dist_launches(const ec3d_ctx *c, int stage, int it)
     }
 }
 
-extern "C" int ec3d_can_overlap(ec3d_handle c) { return c && c->have_matrix && c->can_overlap ? 1 : 0; }
+extern "C" int ec3d_can_overlap(ec3d_handle c) { return c && c->have_matrix && c->split_s.ok ? 1 : 0; }
 
 extern "C" int ec3d_read_state_async(ec3d_handle c, int32_t *stop_iter_pinned)
 {

@@ -199,6 +199,16 @@ __host__ __device__ inline int64_t ec3d_tile_of(const SW &sw, int b, int64_t i)
     }
     return t < sw.ntiles ? ec3d_phys_tile(sw, t) : -1;
 }
+
+// A kernel of a z-slab as two launches, so that the halo exchange overlaps the interior: `bnd` visits the tiles next to a
+// cut, `inte` all others, each tile in exactly one of them.  Every pair is derived in ec3d_split_sweeps.hpp (host only; the
+// record lives here because ec3d_ctx holds three).  !ok: the kernel runs unsplit.
+struct SplitSweep {
+    Sweep bnd{}, inte{};
+    bool ok = false;
+    // partial sums per slot the two launches leave: one's, from its part_off = 0, followed by the other's
+    int parts() const { return bnd.nblk + inte.nblk; }
+};
 #define EC3D_XD_MAX 4 // deepest deferral of the X update (iterations whose P and S are kept)
 struct SolverState {
     double rr0[2]; // R·R0 entering iteration it is rr0[it & 1]
@@ -381,12 +391,15 @@ struct ec3d_ctx {
     Sweep sweep{};   // vector kernels: K4's grid (and the geometry every other sweep is derived from)
     Sweep sweep_k2{}, sweep_k5{}; // K2 (2 reads + 1 write) and K5 (3 + 1) like other workgroup counts than K4 (5 + 2)
     Sweep sweep_s{}; // SpMV kernels (K1, K3, residual, spmv)
-    Sweep sweep_int{}, sweep_bnd{}; // z-slab: interior / boundary-plane launches of K1 and K3
-    bool can_overlap = false;
-    // z-slab on 2-D tiles: planes {0, np-1} / 1 .. np-2 as two launches of the 2-D-tile kernels (K4 in SpMV form and
-    // K5-in-K1 of the three-launch iteration: the producers of the exchanged R and AP); can_fsplit: np >= 3
-    Sweep sweep_fb{}, sweep_fi{};
-    bool can_fsplit = false;
+    // z-slab: the kernels that run as boundary + interior launch (SplitSweep; ec3d_split_sweeps.hpp derives all three).
+    // While a split is refused, split_s and split_f hold the unsplit sweep_s twice.
+    SplitSweep split_s; // K1 and K3 (ec3d_can_overlap): the planes next to a cut / those between
+    // on 2-D tiles: planes {0, np-1} / 1 .. np-2 as two launches of the 2-D-tile kernels (K4 in SpMV form and K5-in-K1 of
+    // the three-launch iteration: the producers of the exchanged R and AP)
+    SplitSweep split_f;
+    // K2 and K5, made by ec3d_dist_set_boundary_rows (tile lists: vb_list, vi_list) or ec3d_dist_set_boundary_planes
+    // (windows) after the matrix is set, and dropped (ok = false, the sweeps left as they were) whenever the geometry changes
+    SplitSweep split_v;
     bool fuse23_ok = false; // 2-D tiles: K2 may run inside K3 (single rank only, see ec3d_fused23)
     bool fuse51_ok = false; // 2-D tiles: K5 may run inside the next iteration's K1 (ec3d_fused51)
     bool k4s_ok = false;    // dictionary cube on 2-D tiles: K4 may run as an SpMV kernel that computes A S again (ec3d_k4s)
@@ -424,9 +437,7 @@ struct ec3d_ctx {
     hipError_t async_err = hipSuccess;
     const char *async_what = nullptr;
     int xdefer = 1;        // D: iterations between two X updates on this handle (1: every iteration, the classic K4)
-    // K2/K5 as boundary + interior launches (ec3d_dist_set_boundary_rows): tile lists on the device
-    Sweep sweep_vb{}, sweep_vi{};
-    DevBuf<int32_t> vb_list, vi_list;
+    DevBuf<int32_t> vb_list, vi_list; // split_v from tile lists (ec3d_dist_set_boundary_rows): the lists on the device
     DevBuf<int32_t> us_list; // structured form: the U tiles in the order the z-marching SpMV kernels take them (choose_sweep)
     DevBuf<int32_t> ii_list, ib_list; // structured z-slab, K1 / K3 split: the interior launch's U tiles, the boundary launch's tiles
     std::vector<int32_t> us_host; // host copy (visit-order export)
@@ -434,7 +445,6 @@ struct ec3d_ctx {
     std::vector<uint32_t> il_umask_host;
     DevBuf<int32_t> il_seg;            // ... and its work list (four int32 per workgroup)
     std::vector<int32_t> il_seg_host;
-    bool can_vsplit = false;
     int nown = 0;    // ownership ranges of an A-V slab (see Sweep)
     int64_t own_lo[4] = {0}, own_hi[4] = {0};
     bool dist = false;
@@ -635,7 +645,7 @@ enum { EC3D_BY_K4 = 0, EC3D_BY_SPMV = 1, EC3D_BY_K2 = 2 };
 RedSrc ec3d_src_of(const ec3d_ctx *c, int producer);
 RedSrc ec3d_part_of(const ec3d_ctx *c, int producer, bool split = false);
 // k = 1..5, 0 = all five; part: 0 the whole launch, 1 / 2 the boundary / interior launch of stage 4 or 5 on a slab that runs
-// the three-launch iteration (sweep_fb / sweep_fi)
+// the three-launch iteration (split_f.bnd / split_f.inte)
 void ec3d_launch_stage(ec3d_ctx *c, const MatView &A, int it, int k, int part = 0);
 inline bool ec3d_fused23(const ec3d_ctx *c) { return c->fuse23_ok && ((!c->dist && c->halo == 0) || c->slab_fused); }
 inline bool ec3d_fused51(const ec3d_ctx *c)

@@ -583,10 +583,10 @@ RankFacts facts_of(const Slab &sl)
     f.xd = (c->pp_base && c->own_vectors()) ? (double)c->xdefer : 1.0;
     f.xasync = (c->pp_base && c->own_vectors() && c->xasync_cap) ? 1.0 : 0.0;
     // (an A-V slab splits K2 / K5 by tile lists made from its halo runs: always possible where there is a neighbour)
-    f.both_splits = (c->have_matrix && c->can_overlap && (c->A.sav || ec3d_dist_can_split_planes(c))) ? 1.0 : 0.0;
+    f.both_splits = (c->have_matrix && c->split_s.ok && (c->A.sav || ec3d_dist_can_split_planes(c))) ? 1.0 : 0.0;
     f.sav = c->A.sav ? 1.0 : 0.0;
     f.n_pad = (double)c->A.n_pad;
-    f.fsplit = c->can_fsplit ? 1.0 : 0.0;
+    f.fsplit = c->split_f.ok ? 1.0 : 0.0;
     halo_facts(sl.halo, f);
     return f;
 }
@@ -645,7 +645,7 @@ int finish_setup(ec3d_multi *m, const SlabKnobs &knob)
         c->slab_xasync = job.xasync;
         const SlabPlan sp = decide_slab(job, m->kind, m->world, s.rank, knob, ec3d_can_overlap(c) != 0);
         c->sweep_s.halo_store = sp.halo_store;
-        c->sweep_fb.halo_store = c->sweep_fi.halo_store = c->sweep_s.halo_store;
+        c->split_f.bnd.halo_store = c->split_f.inte.halo_store = c->sweep_s.halo_store;
         if (c->pp_base) { // every rank cycles P and S through the same number of buffers
             const int D = ec3d_xdefer(c), depth = ec3d_xasync(c) ? 2 * D : D;
             c->pdepth = std::max(2, depth);

@@ -21,13 +21,13 @@
 // vector kernels (sweep) -- every consumer reads slots of one producer class only.
 static int parts_of(const ec3d_ctx *c, int producer, bool split)
 {
-    // (a split launch of the three-launch iteration -- K4 in SpMV form or K5-in-K1 as boundary + interior launch -- leaves
-    // the boundary launch's partials followed by the interior launch's)
-    const int fsplit = c->sweep_fb.nblk + c->sweep_fi.nblk;
     if (producer == EC3D_BY_K2) return ec3d_fused23(c) ? c->sweep_s.nblk : c->sweep_k2.nblk; // fused: S.S comes from K23
-    if (producer == EC3D_BY_K4) return ec3d_k4s(c) ? (split ? fsplit : c->sweep_s.nblk) : c->sweep.nblk; // K4 in SpMV form sums on that grid
-    if (split && ec3d_fused51(c) && c->slab_fused) return fsplit;
-    return split ? c->sweep_int.nblk + c->sweep_bnd.nblk : c->sweep_s.nblk;
+    if (producer == EC3D_BY_K4 && !ec3d_k4s(c)) return c->sweep.nblk; // (K4 in SpMV form sums on that grid)
+    if (!split) return c->sweep_s.nblk;
+    // a split producer leaves both launches' partials (SplitSweep::parts): K4 in SpMV form and K5-in-K1 of the three-launch
+    // iteration on the 2-D tiles, K1 and K3 otherwise
+    const bool f = producer == EC3D_BY_K4 || (ec3d_fused51(c) && c->slab_fused);
+    return (f ? c->split_f : c->split_s).parts();
 }
 RedSrc ec3d_src_of(const ec3d_ctx *c, int producer)
 {
@@ -95,7 +95,7 @@ void ec3d_after_p(ec3d_ctx *c, int it)
 void ec3d_launch_stage(ec3d_ctx *c, const MatView &A, int it, int k, int part)
 {
     double **v = c->vec;
-    const Sweep &sw = c->sweep, &ss = part == 1 ? c->sweep_fb : part == 2 ? c->sweep_fi : c->sweep_s;
+    const Sweep &sw = c->sweep, &ss = part == 1 ? c->split_f.bnd : part == 2 ? c->split_f.inte : c->sweep_s;
     hipStream_t s = c->stream;
     const bool fused = ec3d_fused23(c); // K2 inside K3 (2-D tiles, single rank): stage 2 is empty, stage 3 is K23
     const bool f51 = ec3d_fused51(c);
