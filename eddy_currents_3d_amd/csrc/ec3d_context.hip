@@ -330,6 +330,7 @@ struct SweepKnobs {
     std::optional<int> zmarch = env("EC3D_ZMARCH"), patch = env("EC3D_PATCH"), nblk_spmv = env("EC3D_NBLK_SPMV");
     std::optional<int> sav_patch = env("EC3D_SAV_PATCH"), sav_patch_px = env("EC3D_SAV_PATCH_PX"), sav_il = env("EC3D_SAV_IL");
     std::optional<int> fuse23 = env("EC3D_FUSE23"), fuse51 = env("EC3D_FUSE51"), k4s = env("EC3D_K4S");
+    std::optional<int> k51_ap = env("EC3D_K51_AP");
 };
 
 // Rows the kernels actually stream.  The structured form's device numbering holds a whole grid-shaped block for U, of
@@ -616,10 +617,23 @@ static int choose_sweep(ec3d_ctx *c)
                 // Paired patch columns: y-adjacent columns marched by one workgroup of 512 threads, their common boundary
                 // through LDS (ec3d_patch_pairs_ok has the rule).  EC3D_PATCH=2: every launch kind, wherever the rule allows;
                 // EC3D_PATCH=1: never; unset: the kinds in EC3D_PAIR_DEFAULT_BIG on vectors beyond the caches (docs/rounds/r08.md).
+                // K5-in-K1 with AP_old formed inside the patch from P_old (patch_pair_apc): the undivided dictionary cube
+                // only.  EC3D_K51_AP=0: AP_old always loaded; 1: formed wherever the instance exists; unset:
+                // EC3D_K51_AP_DEFAULT_BIG on vectors beyond the caches (docs/rounds/r09.md).
                 {
-                    const int kinds = patch == 2 ? EC3D_PAIR_ALL : knob.patch ? 0 : big ? EC3D_PAIR_DEFAULT_BIG : 0;
-                    const bool slab = c->halo > 0 || c->nranks > 1;
-                    ss.pair = ec3d_patch_pairs_ok(tpp, ss.patch_npx, nplanes, ss.zm_pps, ss.nblk, slab, c->dist) ? kinds : 0;
+                    const bool inst = undivided && A.ncls > 0 && !A.sav;
+                    ss.k51_ap = inst && knob.k51_ap.value_or(big && EC3D_K51_AP_DEFAULT_BIG) != 0 ? 1 : 0;
+                }
+                const bool slab = c->halo > 0 || c->nranks > 1;
+                const bool pairs_ok = ec3d_patch_pairs_ok(tpp, ss.patch_npx, nplanes, ss.zm_pps, ss.nblk, slab, c->dist);
+                // (unset: only as the form that passed the A/B, i.e. on paired columns -- a big grid whose pairing is refused,
+                // or EC3D_PATCH=1, keeps loading: unpaired the gain stayed inside the margin)
+                if (!knob.k51_ap && !(pairs_ok && !(knob.patch && patch != 2))) ss.k51_ap = 0;
+                // (K5-in-K1 pairs by default only in that form: the rim fraction then decides how much of AP_old is still
+                // fetched, 1084 -> 1008 us at 512^3, where the loading form loses by pairing, 1084 -> 1098 us)
+                {
+                    const int kinds = patch == 2 ? EC3D_PAIR_ALL : knob.patch ? 0 : !big ? 0 : EC3D_PAIR_DEFAULT_BIG | (ss.k51_ap ? EC3D_PAIR_K51 : 0);
+                    ss.pair = pairs_ok ? kinds : 0;
                 }
             }
         }

@@ -6,6 +6,7 @@
 // instances per kernel family.
 #pragma once
 #include "ec3d_internal.hpp"
+#include "ec3d_sweep_lists.hpp"
 
 // Matrix formats the row kernel is specialised for (template parameter FMT):
 //   FMT_GENERIC  any number of bands, one fp64 stream per band
@@ -29,6 +30,8 @@ struct SpmvForm {
     bool hs;    // z-slab of the three-launch iteration: the formed vector is also stored on the halo planes
                 // (only k23_s_spmv_dots and k51_p_spmv_dot have such instances)
     bool pair;  // paired patch columns (Sweep::pair holds the launch's kind): set by the launcher, see ec3d_form_pair
+    bool apc;   // k51_p_spmv_dot: AP_old of the patch's own cells formed from P_old, not loaded (Sweep::k51_ap): set by the
+                // launcher, see ec3d_form_apc
 };
 
 inline SpmvForm ec3d_spmv_form(const MatView &A, const Sweep &sw)
@@ -52,6 +55,28 @@ inline bool ec3d_form_pair(const SpmvForm &f, const Sweep &sw, int kind)
     return f.patch && f.fmt == FMT_DICT7 && !f.hs && (sw.pair & kind) != 0;
 }
 
+// Does K5-in-K1 of this form compute AP_old inside the patch (patch_pair_apc in ec3d_kernels.hip)?  The same instances as
+// pairing: dictionary cube on 2-D tiles, no z-slab instance; and choose_sweep's policy for the handle (Sweep::k51_ap).
+inline bool ec3d_form_apc(const SpmvForm &f, const Sweep &sw)
+{
+    return f.patch && f.fmt == FMT_DICT7 && !f.hs && sw.k51_ap != 0;
+}
+
+// The form a launch of a kernel family runs: ec3d_spmv_form narrowed by what the family has instances for (fam_hs: z-slab
+// instances; pair_kind: the EC3D_PAIR_* bit of its launches, 0 = never paired; fam_apc: instances that form AP_old on the
+// patch).  launch_form (ec3d_kernels.hip) dispatches on exactly this, and what a handle reports of its launches
+// (ec3d_get_k51_ap_form) is read off the same function.
+inline SpmvForm ec3d_family_form(const MatView &A, const Sweep &sw, bool fam_hs, int pair_kind, bool fam_apc)
+{
+    SpmvForm f = ec3d_spmv_form(A, sw);
+    f.hs = f.hs && fam_hs;
+    f.pair = ec3d_form_pair(f, sw, pair_kind);
+    f.apc = fam_apc && ec3d_form_apc(f, sw);
+    return f;
+}
+// k51_p_spmv_dot's launch (Fused51Family: z-slab instances, pairs as EC3D_PAIR_K51, has the APC instances)
+inline SpmvForm ec3d_k51_form(const MatView &A, const Sweep &sw) { return ec3d_family_form(A, sw, true, EC3D_PAIR_K51, true); }
+
 // Dynamic LDS bytes of the launch; EC3D_TBL_DECL (ec3d_kernels.hip) lays the same LDS out on the device.
 // The class table (55 + 9 D classes of the structured form with D conducting domains: 64 classes =
 // 8 KiB for one domain, 253 = 31.6 KiB at D = 22, which with the staging slots caps the CU at 3 workgroups -- a cost
@@ -66,7 +91,11 @@ inline size_t ec3d_form_lds(const MatView &A, const SpmvForm &f)
     if (f.patch && f.fmt == FMT_SAV) return sav_tbl + (size_t)(2 + EC3D_NSTAGE_RT) * EC3D_TILE * 8;
     // 2-D tiles of the single-component kernels: table (an even number of doubles), two centre-plane buffers (patch_pair)
     // (paired patch columns: the two buffers hold eight patch rows)
-    if (f.patch) return (size_t)((f.fmt == FMT_DICT7 ? A.ncls * 7 + 1 : 0) & ~1) * 8 + (size_t)(f.pair ? 4 : 2) * EC3D_TILE * 8;
+    // (AP_old formed on the patch, patch_pair_apc: two more buffers, of raw P_old, and all four with the two rim rows beside the
+    // patch rows)
+    if (f.patch)
+        return (size_t)((f.fmt == FMT_DICT7 ? A.ncls * 7 + 1 : 0) & ~1) * 8 +
+               (f.apc ? (size_t)4 * ((f.pair ? 2 : 1) * EC3D_PY + 2) * EC3D_PX * 8 : (size_t)(f.pair ? 4 : 2) * EC3D_TILE * 8);
     if (f.fmt == FMT_DICT7) return (size_t)A.ncls * 7 * 8;
     if (f.fmt == FMT_SAV) return sav_tbl + (f.zm ? (size_t)EC3D_NSTAGE * EC3D_TILE * 8 : 0);
     return 0;

@@ -145,6 +145,9 @@ struct Sweep {
     // that run nblk / 2 workgroups of 512 threads, each hosting two y-adjacent workgroups of the nblk this sweep counts.
     // nblk, the partials, the visit order and the tile lists keep speaking of those nblk "virtual" workgroups.
     int pair = 0;
+    // K5-in-K1 forms AP_old inside the patch instead of loading it (undivided dictionary cube on 2-D tiles; choose_sweep's
+    // policy, EC3D_K51_AP; ec3d_form_apc in ec3d_form.hpp)
+    int k51_ap = 0;
 };
 
 // first of the two consecutive rows thread t of a workgroup owns in `tile`

@@ -40,6 +40,21 @@ __device__ __forceinline__ double wave_sum(double v)
     for (int off = 32; off > 0; off >>= 1) v = v + __shfl_down(v, off, 64);
     return v; // lane 0
 }
+// The same tree with the lane number taken afresh, through an asm the compiler cannot look into: a kernel that reduces both
+// before and behind its sweep otherwise keeps the shuffle addresses of the first reduction in registers across the whole
+// sweep for the second one (six of them; k51_p_spmv_dot's APC instances spilled three to scratch for it).
+__device__ __forceinline__ double wave_sum_fresh(double v)
+{
+    int lane;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const int src = (lane + off < 64 ? lane + off : lane) << 2; // __shfl_down's source lane, as a byte address
+        const int lo = __builtin_amdgcn_ds_bpermute(src, __double2loint(v)), hi = __builtin_amdgcn_ds_bpermute(src, __double2hiint(v));
+        v = v + __hiloint2double(hi, lo);
+    }
+    return v; // lane 0
+}
 
 // Paired patch columns (PAIR; patch_pair below, ec3d_patch_pairs_ok in ec3d_sweep_lists.hpp): a workgroup of 512 threads
 // hosts two VIRTUAL workgroups of 256 -- half 0 and half 1 -- each of which is exactly a workgroup of the unpaired launch:
@@ -63,14 +78,14 @@ template <bool PAIR, class SW> __device__ __forceinline__ int vw_bid(const SW &s
 }
 
 // sums NV values over the (virtual) workgroup; result valid in every thread.  lds: NV*4 doubles per half.
-template <int NV, bool PAIR = false>
+template <int NV, bool PAIR = false, bool FRESH = false>
 __device__ __forceinline__ void block_sum(double (&v)[NV], double *lds)
 {
     const int lane = threadIdx.x & 63, w = vw_tid<PAIR>() >> 6;
     if constexpr (PAIR) lds += vw_half<PAIR>() * (NV * 4);
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
-        double t = wave_sum(v[k]);
+        double t = FRESH ? wave_sum_fresh(v[k]) : wave_sum(v[k]);
         if (lane == 0) lds[k * 4 + w] = t;
     }
     __syncthreads();
@@ -780,6 +795,10 @@ struct ZRegs {
     double edge; // 2-D tiles, PP_RIM_EDGE_BEHIND: the cell beside the patch row's end in the NEXT step's centre plane (edge lanes)
     unsigned short cc; // 2-D tiles, dictionary form: the thread's class pair, carried while the tiles' classes repeat ...
     uint32_t same;     // ... which MatDev::same says of the NEXT step's tile: the dword that holds its byte (uniform; asked for a step ahead)
+    // 2-D tiles, K5-in-K1 with AP_old formed on the patch (patch_pair_apc): the raw P_old pair of the plane
+    // above and the raw P_old edge cell beside the plane above (`same` then runs a plane further ahead)
+    d2 pc;
+    double pedge;
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -1689,6 +1708,157 @@ __device__ __forceinline__ void patch_pair_fused(const MatDev<FMT> &A, const dou
         z.edge = x.form(en_r);
     }
 }
+// K5-in-K1 with AP_old FORMED on the patch (round 9; Fused51Family's APC instances, dictionary form, no z-slab).  The step
+// above forms the plane above, P_new(k+1) = R + beta*(P_old - omega*AP_old), from three loaded pairs.  But AP_old IS A*P_old:
+// the previous launch of this kernel (or K1) stored patch_sums over the very values that are P_old now, so the same
+// patch_sums over the stored P_old gives the stored AP_old bit for bit (as k4s_x_r_spmv gives AS again).  For the thread's own
+// two cells of the plane above it is therefore summed instead of loaded; its operands are
+//   P_old(k+1)             the thread's pair, carried (ZRegs::pc)
+//   P_old(k+2)             the step's one new request: the P_old stream runs a plane ahead of R
+//   P_old(k)               read back from the thread's own slot of the exchange buffer it overwrites at the end of the step,
+//                          where it lies since the step before last (so does P_new(k-1) in the centre-plane buffer: the
+//                          register budget of four waves per SIMD has no room to carry the two)
+//   +-1 in the row         lane shuffles of P_old(k+1); the edge lanes' cell was requested a step earlier (ZRegs::pedge)
+//   +-sdx                  a second LDS exchange of RAW P_old, PY + 2 rows: every thread stores its P_old(k+2) pair at the end of
+//                          the step, the rim waves the rim row of that plane into row -1 / PY, requested a step earlier too
+//   classes of plane k+1   the class pair runs a plane ahead as well (z.cc is carried into the next step as ITS pair)
+// AP_old is still LOADED where the cell lies outside the patch (rim row and edge cells, which form P_new there) and for all
+// three planes of a segment's first step, which carries nothing yet.  The plane above the grid's last one is ghost: its
+// AP_old is the zero a load gives (`up` false: no stencil there, no class byte, and P_old two planes up -- beyond the ghost
+// zone -- is not requested).  After a restart nothing of P_old or AP_old is read.  Requests keep the order of the step above:
+// raw operands first, forms behind the LDS exchange, selects instead of branches around arithmetic.
+// Holds only where AP_old is the product of P_old -- which is how the iteration produces the two (ec3d_launch_stage).
+template <int FMT, bool PAIR>
+__device__ __forceinline__ void patch_pair_apc(const MatDev<FMT> &A, const double *tbl, double *pbuf, int step, const VecFusedP &x,
+                                               int64_t r, int64_t tile, bool first, bool up, ZRegs &z, double &s0, double &s1,
+                                               d2 &ctr)
+{
+    static_assert(FMT == FMT_DICT7, "patch_pair_apc: the dictionary form only");
+    typedef VecFusedP V;
+    constexpr int PY = PAIR ? 2 * EC3D_PY : EC3D_PY, BUF = (PY + 2) * EC3D_PX; // patch rows and the rim row on either side
+    const int t = threadIdx.x, y = t / EC3D_HX, q = t % EC3D_HX;
+    // two centre-plane buffers, the two of raw P_old behind them; the pointers stand at patch row 0 (rows -1 and PY: the rim
+    // rows, formed and stored by the rim waves: held in registers like ZRegs::rim they did not fit four waves per SIMD)
+    double *cur = pbuf + (step & 1) * BUF + EC3D_PX, *nxt = pbuf + ((step + 1) & 1) * BUF + EC3D_PX;
+    double *pcur = cur + 2 * BUF, *pnxt = nxt + 2 * BUF;
+    const int trim = y == 0 ? t - EC3D_HX : t + EC3D_HX; // a rim wave's slot in the rim row
+    const int64_t sdx = A.off[5], kdz = A.off[6], tpp = kdz / EC3D_TILE;
+    const bool calc = up && !x.restart;
+    // P_old a plane up: its requests then share their row index with those of R and AP_old beside the plane above (a 64-bit
+    // index of their own for each of them did not fit the registers)
+    const double *__restrict__ pup = x.p + kdz;
+    // class pairs of this plane (carried, or loaded in a first step) and of the plane above (kept or loaded: patch_classes)
+    unsigned short cc, cn = 0;
+    {
+        const bool kept = !first && ((z.same >> (8 * (unsigned)((tile + tpp) & 3))) & 0xFFu) != 0;
+        uint32_t w = 0;
+        if (A.same && up) w = ((const __attribute__((address_space(4))) uint32_t *)(uintptr_t)A.same)[(tile + 2 * tpp) >> 2];
+        if (first) cc = *reinterpret_cast<const unsigned short *>(A.cls + r);
+        else cc = z.cc;
+        if (up) {
+            if (kept) cn = cc;
+            else cn = *reinterpret_cast<const unsigned short *>(A.cls + r + kdz);
+        }
+        z.same = w;
+    }
+    // the step's first requests: R of the plane above and P_old two planes up (a first step: the plane above in full)
+    V::Raw2 zp_r{};
+    if (first) zp_r = x.rpair(r + kdz);
+    else zp_r.q = *reinterpret_cast<const d2u *>(x.rv + r + kdz);
+    d2 p2 = d2{0.0, 0.0};
+    if (!first && calc) p2 = *reinterpret_cast<const d2u *>(pup + r + kdz);
+    const bool edge = q == 0 || q == EC3D_HX - 1;
+    const int64_t eoff = q == 0 ? -1 : 2;
+    V::Raw1 e_r{};
+    if (edge && first) e_r = x.rat(r + eoff);
+    const bool rimrow = y == 0 || y == PY - 1;
+    const int64_t roff = y == 0 ? -sdx : sdx;
+    V::Raw2 rimc_r{};
+    if (rimrow && first) rimc_r = x.rpair(r + roff);
+    d2 zm, cx;
+    if (first) { // nothing carried over: plane below and centre from memory, centre into this step's buffer
+        const V::Raw2 zm_r = x.rpair(r - kdz), cx_r = x.rpair(r);
+        zm = x.form(zm_r);
+        cx = x.form(cx_r);
+        *reinterpret_cast<d2 *>(cur + 2 * t) = cx;
+        const d2 rimc = x.form(rimc_r);
+        if (rimrow) *reinterpret_cast<d2 *>(cur + 2 * trim) = rimc;
+    } else {
+        cx = z.xc;
+    }
+    EC3D_PATCH_BARRIER;
+    if (!first) zm = *reinterpret_cast<const d2 *>(nxt + 2 * t); // the plane below: this thread's own store of the step before last
+    const d2 ym = *reinterpret_cast<const d2 *>(cur + 2 * (t - EC3D_HX));
+    const d2 yp = *reinterpret_cast<const d2 *>(cur + 2 * (t + EC3D_HX));
+    ctr = cx;
+    double left, right;
+    {
+        const double ev = first ? x.form(e_r) : z.edge;
+        const double l = __shfl_up(cx.y, 1, 64), rr = __shfl_down(cx.x, 1, 64);
+        left = q != 0 ? l : ev;
+        right = q != EC3D_HX - 1 ? rr : ev;
+    }
+    // AP_old of the plane above, the thread's own pair: the row sums over P_old (zero above the grid's last plane)
+    d2 prim = d2{0.0, 0.0}; // the rim row of P_old beside the plane above (rim waves), as it lies in the exchange buffer
+    if (!first) {
+        const d2 pym = *reinterpret_cast<const d2 *>(pcur + 2 * (t - EC3D_HX));
+        const d2 pyp = *reinterpret_cast<const d2 *>(pcur + 2 * (t + EC3D_HX));
+        const double pl = __shfl_up(z.pc.y, 1, 64), pr = __shfl_down(z.pc.x, 1, 64);
+        const double pleft = q != 0 ? pl : z.pedge, pright = q != EC3D_HX - 1 ? pr : z.pedge;
+        const d2 pm = *reinterpret_cast<const d2 *>(pnxt + 2 * t); // (its own store of the step before last, as zm)
+        const d2 a = patch_sums<FMT>(nullptr, tbl, cn, pm, pym, pleft, z.pc, pright, pyp, p2);
+        zp_r.pv = z.pc;
+        zp_r.a = d2{calc ? a.x : 0.0, calc ? a.y : 0.0};
+        prim = y == 0 ? pym : pyp;
+    }
+    const d2 zp = x.form(zp_r);
+    // behind the arrival of the plane above (PP_RIM_EDGE_BEHIND): the rim row and the edge cells beside it -- R and AP_old
+    // there, P_old a plane further up (a first step: both planes of P_old)
+    V::Raw2 rimn_r{};
+    V::Raw1 en_r{};
+    d2 prim2 = d2{0.0, 0.0};
+    double pe2 = 0.0;
+    if (first && calc) p2 = *reinterpret_cast<const d2u *>(pup + r + kdz); // (a first step has requests enough in front)
+    if (rimrow) {
+        if (first) {
+            rimn_r = x.rpair(r + kdz + roff);
+        } else {
+            rimn_r.q = *reinterpret_cast<const d2u *>(x.rv + r + kdz + roff);
+            if (!x.restart) rimn_r.a = *reinterpret_cast<const d2u *>(x.ap + r + kdz + roff);
+        }
+        if (calc) prim2 = *reinterpret_cast<const d2u *>(pup + r + kdz + roff);
+    }
+    if (edge) {
+        if (first) {
+            en_r = x.rat(r + kdz + eoff);
+        } else {
+            en_r.q = x.rv[r + kdz + eoff];
+            if (!x.restart) en_r.a = x.ap[r + kdz + eoff];
+        }
+        if (calc) pe2 = pup[r + kdz + eoff];
+    }
+    if (!first) {
+        rimn_r.pv = prim;
+        en_r.pv = z.pedge;
+    }
+    const d2 s = patch_sums<FMT>(nullptr, tbl, cc, zm, ym, left, cx, right, yp, zp);
+    s0 = s.x;
+    s1 = s.y;
+    // the plane above is the next step's centre, P_old two planes up the next step's plane above: into the other buffers
+    *reinterpret_cast<d2 *>(nxt + 2 * t) = zp;
+    *reinterpret_cast<d2 *>(pnxt + 2 * t) = p2;
+    if (first) *reinterpret_cast<d2 *>(pcur + 2 * t) = zp_r.pv; // P_old of the plane above, where the next step reads its plane below
+    z.xc = zp;
+    z.pc = p2;
+    z.cc = cn;
+    z.edge = x.form(en_r);
+    z.pedge = pe2;
+    const d2 rimn = x.form(rimn_r);
+    if (rimrow) {
+        *reinterpret_cast<d2 *>(nxt + 2 * trim) = rimn;
+        *reinterpret_cast<d2 *>(pnxt + 2 * trim) = prim2;
+    }
+}
 template <int FMT, bool NTB, bool PAIR, class V>
 __device__ __forceinline__ void patch_pair(const MatDev<FMT> &A, const double *tbl, double *pbuf, int step, const V &x,
                                            int64_t r, int64_t tile, bool first, ZRegs &z, double &s0, double &s1,
@@ -2213,7 +2383,8 @@ __global__ __launch_bounds__(EC3D_WG_THREADS) __attribute__((amdgpu_waves_per_eu
 // (p_old, ap_old) and those of it + 1 written to (p_new, ap_new): other workgroups read the old values of cells this
 // one owns (rim, edge, the planes at a segment's ends), so the update cannot be in place.  Saves the 8 B per row P
 // costs to re-read and one launch; every stored value and every product is K5's followed by K1's.
-template <int FMT, bool NT, bool ZM, bool TAIL, bool PATCH, bool HS = false, bool PAIR = false>
+// APC: AP_old of the patch's own cells is formed from P_old instead of loaded (patch_pair_apc)
+template <int FMT, bool NT, bool ZM, bool TAIL, bool PATCH, bool HS = false, bool PAIR = false, bool APC = false>
 __global__ __launch_bounds__(EC3D_WG_THREADS) __attribute__((amdgpu_waves_per_eu(4))) void k51_p_spmv_dot(
     MatDev<FMT> A, EC3D_SWEEP_OF(ZM) sw, RedSrc src, SolverState *st, int it, const double *__restrict__ rv,
     const double *__restrict__ p_old, const double *__restrict__ ap_old, double *__restrict__ p_new,
@@ -2261,8 +2432,12 @@ __global__ __launch_bounds__(EC3D_WG_THREADS) __attribute__((amdgpu_waves_per_eu
         EC3D_ROW_S;
         double s0, s1;
         d2 pc; // the new P[r], P[r+1]
-        spmv_pair<FMT, ZM, TAIL, NT, PATCH, PAIR>(A, sw, pp, tbl, stg, pstep, VecFusedP{rv, p_old, ap_old, beta, omega, restart}, r, tile,
-                                            (bool)fc, zr, s0, s1, pc);
+        if constexpr (APC)
+            patch_pair_apc<FMT, PAIR>(A, tbl, stg, pstep++, VecFusedP{rv, p_old, ap_old, beta, omega, restart}, r, tile, (bool)fc,
+                                      tile + sw.tpp < sw.ntiles, zr, s0, s1, pc);
+        else
+            spmv_pair<FMT, ZM, TAIL, NT, PATCH, PAIR>(A, sw, pp, tbl, stg, pstep, VecFusedP{rv, p_old, ap_old, beta, omega, restart}, r, tile,
+                                                (bool)fc, zr, s0, s1, pc);
         // R0's pair BEHIND the step, a memory round trip of its own.  Requested with the step's first requests it loses
         // (round 3: 1176 -> 1206 us), and so it does behind the arrival of the plane above, with the rim row (round 6:
         // 1120-1185 -> 1215-1218 us; AP.R0 summed before the step's stores instead of behind them: no difference) --
@@ -2286,7 +2461,7 @@ __global__ __launch_bounds__(EC3D_WG_THREADS) __attribute__((amdgpu_waves_per_eu
         acc[0] = acc[0] + s0 * q.x;
         acc[0] = acc[0] + s1 * q.y;
     });
-    block_sum<1, PAIR>(acc, lds);
+    block_sum<1, PAIR, APC>(acc, lds);
     {
         const int pslot_[1] = {P_D1};
         publish_partials<1, PAIR>(sw, part, pslot_, acc, lds);
@@ -2807,24 +2982,28 @@ static constexpr bool form_possible(const SpmvForm &f)
 }
 // (pair_kind: the bit of Sweep::pair that lets the family's launches run paired patch columns, ec3d_form_pair)
 struct SpmvFamily { // k_spmv, k_residual, k1_spmv_dot, k3_spmv_dots: every form, no HS
-    static constexpr bool hs = false;
+    static constexpr bool hs = false, apc = false;
     static constexpr int pair_kind = EC3D_PAIR_K13; // (k_spmv: EC3D_PAIR_SPMV, a kind of its own)
     static constexpr bool has(const SpmvForm &f) { return form_possible(f) && !f.hs; }
 };
 struct FusedFamily { // k23_s_spmv_dots, k51_p_spmv_dot: the 2-D-tile kernels only (ec3d_fused23, ec3d_fused51)
-    static constexpr bool hs = true;
+    static constexpr bool hs = true, apc = false;
     static constexpr bool has(const SpmvForm &f) { return form_possible(f) && f.zm && f.patch && !f.tail; }
 };
 struct Fused23Family : FusedFamily { static constexpr int pair_kind = EC3D_PAIR_K23; };
-struct Fused51Family : FusedFamily { static constexpr int pair_kind = EC3D_PAIR_K51; };
+struct Fused51Family : FusedFamily { // (apc: the family has instances that form AP_old on the patch; ec3d_k51_form states the same)
+    static constexpr int pair_kind = EC3D_PAIR_K51;
+    static constexpr bool apc = true;
+};
+static_assert(Fused51Family::hs && Fused51Family::apc && Fused51Family::pair_kind == EC3D_PAIR_K51, "ec3d_k51_form (ec3d_form.hpp)");
 struct K4sFamily { // k4s_x_r_spmv: the dictionary cube on 2-D tiles (ec3d_k4s), each with NEMAX = 0 and 4
-    static constexpr bool hs = false;
+    static constexpr bool hs = false, apc = false;
     static constexpr int pair_kind = EC3D_PAIR_K4S;
     static constexpr bool has(const SpmvForm &f) { return FusedFamily::has(f) && f.fmt == FMT_DICT7 && !f.hs; }
 };
-template <int FMT_, bool NT_, bool ZM_, bool TAIL_, bool PATCH_, bool HS_, bool PAIR_> struct FormTag { // the kernels' template arguments
+template <int FMT_, bool NT_, bool ZM_, bool TAIL_, bool PATCH_, bool HS_, bool PAIR_, bool APC_> struct FormTag { // the kernels' template arguments
     static constexpr int FMT = FMT_;
-    static constexpr bool NT = NT_, ZM = ZM_, TAIL = TAIL_, PATCH = PATCH_, HS = HS_, PAIR = PAIR_;
+    static constexpr bool NT = NT_, ZM = ZM_, TAIL = TAIL_, PATCH = PATCH_, HS = HS_, PAIR = PAIR_, APC = APC_;
     // the launch: a paired instance runs half as many workgroups of twice the threads
     static constexpr int threads = PAIR_ ? 2 * EC3D_THREADS : EC3D_THREADS;
     static int grid(const Sweep &sw) { return PAIR_ ? sw.nblk / 2 : sw.nblk; }
@@ -2834,25 +3013,26 @@ template <int FMT_, bool NT_, bool ZM_, bool TAIL_, bool PATCH_, bool HS_, bool 
 template <class FAMILY, class LAUNCH>
 static void launch_form(const char *kernel, const MatView &A, const Sweep &sw, LAUNCH &&launch, int pair_kind = FAMILY::pair_kind)
 {
-    SpmvForm f = ec3d_spmv_form(A, sw);
-    f.hs = f.hs && FAMILY::hs;
-    f.pair = ec3d_form_pair(f, sw, pair_kind);
+    const SpmvForm f = ec3d_family_form(A, sw, FAMILY::hs, pair_kind, FAMILY::apc);
     const size_t lds = ec3d_form_lds(A, f);
     bool found = false;
     auto with_fmt = [&](auto FMT) {
-        tag_bools([&](auto NT, auto ZM, auto TAIL, auto PATCH, auto IL, auto HS, auto PAIR) {
-            constexpr SpmvForm cf{decltype(FMT)::value,   decltype(NT)::value, decltype(ZM)::value, decltype(TAIL)::value,
-                                  decltype(PATCH)::value, decltype(IL)::value, decltype(HS)::value, decltype(PAIR)::value};
-            // (paired instances: the dictionary cube's 2-D tiles only, what ec3d_form_pair can ask for)
-            if constexpr (FAMILY::has(cf) && (!cf.pair || (cf.patch && cf.fmt == FMT_DICT7 && !cf.hs))) {
+        tag_bools([&](auto NT, auto ZM, auto TAIL, auto PATCH, auto IL, auto HS, auto PAIR, auto APC) {
+            constexpr SpmvForm cf{decltype(FMT)::value,   decltype(NT)::value, decltype(ZM)::value,   decltype(TAIL)::value,
+                                  decltype(PATCH)::value, decltype(IL)::value, decltype(HS)::value,   decltype(PAIR)::value,
+                                  decltype(APC)::value};
+            // (paired instances: the dictionary cube's 2-D tiles only, what ec3d_form_pair can ask for; the same for the
+            // instances that form AP_old on the patch, in the one family that has them: ec3d_form_apc)
+            constexpr bool cube2d = cf.patch && cf.fmt == FMT_DICT7 && !cf.hs;
+            if constexpr (FAMILY::has(cf) && (!cf.pair || cube2d) && (!cf.apc || (cube2d && FAMILY::apc))) {
                 // the kernels have no parameter of their own for the interleaved march: on the structured form, which has
                 // no tail, TAIL = true stands for it (EC3D_IL)
-                using T = FormTag<cf.fmt, cf.nt, cf.zm, cf.tail || cf.il, cf.patch, cf.hs, cf.pair>;
+                using T = FormTag<cf.fmt, cf.nt, cf.zm, cf.tail || cf.il, cf.patch, cf.hs, cf.pair, cf.apc>;
                 found = true;
                 if constexpr (cf.zm) launch(T{}, mat_dev<cf.fmt>(A), sweep_z(sw), lds);
                 else launch(T{}, mat_dev<cf.fmt>(A), sw, lds);
             }
-        }, f.nt, f.zm, f.tail, f.patch, f.il, f.hs, f.pair);
+        }, f.nt, f.zm, f.tail, f.patch, f.il, f.hs, f.pair, f.apc);
     };
     switch (f.fmt) {
     case FMT_SAV: with_fmt(std::integral_constant<int, FMT_SAV>{}); break;
@@ -2976,7 +3156,7 @@ void ec3d_launch_k51(const MatView &A, const Sweep &sw, const RedSrc &src, Solve
 {
     launch_form<Fused51Family>("k51_p_spmv_dot", A, sw, [&](auto t, const auto &Ad, const auto &swk, size_t lds) {
         using T = decltype(t);
-        k51_p_spmv_dot<T::FMT, T::NT, T::ZM, T::TAIL, T::PATCH, T::HS, T::PAIR><<<T::grid(sw), T::threads, lds, s>>>(
+        k51_p_spmv_dot<T::FMT, T::NT, T::ZM, T::TAIL, T::PATCH, T::HS, T::PAIR, T::APC><<<T::grid(sw), T::threads, lds, s>>>(
             Ad, swk, src, st, it, r, p_old, ap_old, p_new, ap_new, r0, part, hist, hist_cap);
     });
 }

@@ -1,6 +1,7 @@
 // ec3d_measure.hip — timing entry points used by bench.py and the tools (hipEvents on the handle's stream).
 #include "../../include/ec3d_hip.h"
 #include "ec3d_internal.hpp"
+#include "ec3d_form.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -62,6 +63,18 @@ extern "C" int ec3d_get_patch_rows(ec3d_handle c, int kind, int32_t *rows)
     const Sweep &ss = c->sweep_s;
     const bool dict = c->A.ncls > 0 && !c->A.sav;
     *rows = !(ss.patch_npx > 0 && dict) ? 0 : (ss.pair & (1 << kind)) ? 2 * EC3D_PY : EC3D_PY;
+    return 0;
+}
+
+// 1: K5 inside K1 forms AP_old of the patch's own cells from P_old (k51_p_spmv_dot's APC instances), 0: it loads AP_old
+// everywhere (also: no K5 inside K1 on this handle)
+extern "C" int ec3d_get_k51_ap_form(ec3d_handle c, int32_t *computed)
+{
+    int rc = ec3d_need_matrix(c, "ec3d_get_k51_ap_form");
+    if (rc) return rc;
+    if (!computed) return 2;
+    // the form the launcher dispatches on (launch_form in ec3d_kernels.hip reads the same function), where K5 runs inside K1
+    *computed = ec3d_fused51(c) && ec3d_k51_form(c->A.view(), c->sweep_s).apc ? 1 : 0;
     return 0;
 }
 
@@ -154,7 +167,10 @@ extern "C" int ec3d_time_kernel(ec3d_handle c, int kernel, int32_t reps, double 
             ec3d_launch_spmv(A, c->sweep_s, v[EC3D_VEC_P], v[EC3D_VEC_AP], s);
         else {
             // K5-in-K1 handles: EC3D_K1 times the plain K1 of iteration 2 (on the AP buffer the fused launch filled),
-            // EC3D_K5 the fused K5 + K1 launch
+            // EC3D_K5 the fused K5 + K1 launch -- repeated on the P and AP buffers of iteration 2 as they stand, which from
+            // the second repetition on are no longer a vector and its product: an instance that forms AP_old on the patch
+            // (ec3d_get_k51_ap_form) then stores other values than the loading one would.  The time is the same; nothing
+            // reads those vectors afterwards (every solve and ec3d_iterate_begin start from X and B)
             if (kernel == EC3D_K1) c->run.forget_ap();
             ec3d_launch_stage(c, A, 2, kernel);
         }

@@ -145,6 +145,8 @@ EC3D_PAIR_HD inline int ec3d_patch_pair_virtual(int tpp, int npx, int phys, int 
 enum { EC3D_PAIR_SPMV = 1, EC3D_PAIR_K23 = 2, EC3D_PAIR_K51 = 4, EC3D_PAIR_K4S = 8, EC3D_PAIR_K13 = 16, EC3D_PAIR_ALL = 31 };
 // the kinds that pair when nobody asks (vectors beyond the caches): those that won their A/B at 512^3, docs/rounds/r08.md
 enum { EC3D_PAIR_DEFAULT_BIG = EC3D_PAIR_SPMV | EC3D_PAIR_K23 };
+// K5-in-K1 forming AP_old inside the patch (Sweep::k51_ap): what an unset EC3D_K51_AP means from 32 Mi rows (docs/rounds/r09.md)
+enum { EC3D_K51_AP_DEFAULT_BIG = 1 };
 
 // z segments per column of a z-marching grid of `cols` columns that wants want_s workgroups, at most max_seg
 inline int64_t ec3d_zm_segments(int64_t want_s, int64_t cols, int64_t max_seg, bool explicit_request)

@@ -96,7 +96,7 @@ EXPORTS = ["sprsbcgstabwr_", "ec3d_invalidate", "ec3d_create", "ec3d_destroy", "
            "ec3d_set_preconditioner", "ec3d_get_preconditioner", "ec3d_precond_apply", "ec3d_set_u_rhs",
            "ec3d_set_precond_precision", "ec3d_get_precond_precision", "ec3d_set_precond_coarsening",
            "ec3d_get_precond_coarsening", "ec3d_set_precond_grid", "ec3d_get_precond_grid",
-           "ec3d_domain_integrals", "ec3d_field_energy", "ec3d_domain_linkage", "ec3d_get_class_runs", "ec3d_get_patch_rows", "ec3d_set_guess_history", "ec3d_get_guess_history"]
+           "ec3d_domain_integrals", "ec3d_field_energy", "ec3d_domain_linkage", "ec3d_get_class_runs", "ec3d_get_patch_rows", "ec3d_get_k51_ap_form", "ec3d_set_guess_history", "ec3d_get_guess_history"]
 U_RHS = {"reference": 0, "all": 1}   # EC3D_U_RHS_* of include/ec3d_hip.h
 PRECOND = {"none": 0, "mg": 1, "block-mg": 2}   # EC3D_PRECOND_* of include/ec3d_hip.h
 PRECOND_E_MATRIX, PRECOND_E_COARSE = 20, 21   # ec3d_set_preconditioner's refusals
@@ -235,6 +235,7 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.ec3d_get_ulist.argtypes = [hp, _i32]
     L.ec3d_get_class_runs.argtypes = [hp, C.POINTER(C.c_int64), hp, C.c_int64]
     L.ec3d_get_patch_rows.argtypes = [hp, C.c_int, C.POINTER(C.c_int32)]
+    L.ec3d_get_k51_ap_form.argtypes = [hp, C.POINTER(C.c_int32)]
     L.ec3d_set_stream.argtypes = [hp, hp]
     L.ec3d_assemble_poisson_slab.argtypes = [hp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f64, _f64]
     L.ec3d_vector_layout.argtypes = [hp] + [C.POINTER(C.c_int64)] * 4
@@ -493,6 +494,13 @@ class EC3DSolver:
         rows = C.c_int32(0)
         _chk(self.L, self.L.ec3d_get_patch_rows(self.h, int(kind), C.byref(rows)), "ec3d_get_patch_rows")
         return rows.value
+
+    def k51_ap_form(self) -> int:
+        """1 where K5 inside K1 sums the old A*P of a workgroup's own patch again from the old P instead of loading the stored
+        AP there (EC3D_K51_AP; the undivided dictionary cube on 2-D tiles only), 0 where it loads AP everywhere."""
+        v = C.c_int32(0)
+        _chk(self.L, self.L.ec3d_get_k51_ap_form(self.h, C.byref(v)), "ec3d_get_k51_ap_form")
+        return v.value
 
     def set_zmarch(self, on: bool):
         _chk(self.L, self.L.ec3d_set_zmarch(self.h, int(bool(on))), "ec3d_set_zmarch")

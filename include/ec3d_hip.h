@@ -610,6 +610,12 @@ int ec3d_get_class_runs(ec3d_handle h, int64_t *count, uint8_t *flags, int64_t c
  * kind 0: the bare SpMV (k_spmv); 1: K2 inside K3; 2: K5 inside K1; 3: K4 in SpMV form (its launches that leave X alone);
  * 4: the setup residual, K1 and K3.  *rows = 0 on a handle without 2-D tiles.  EC3D_PATCH=2 pairs wherever the grid allows, EC3D_PATCH=1 never. */
 int ec3d_get_patch_rows(ec3d_handle h, int kind, int32_t *rows);
+/* How K5 inside K1 (three-launch iteration on the 2-D tiles) gets the old AP it forms the new P from: *computed = 1: for the
+ * cells of a workgroup's own patch it sums A*P_old again from the old P it holds anyway, and loads AP only on the rim rows,
+ * the edge cells and at a segment's first step (8 B per row less to fetch, the same bits: the stored AP is that very sum);
+ * 0: AP is loaded everywhere.  Only the undivided single-GPU dictionary cube has the computing form; z-slabs, the
+ * five-launch iteration, plain DIA and the structured A-V kernels report 0.  EC3D_K51_AP=0/1 forces either. */
+int ec3d_get_k51_ap_form(ec3d_handle h, int32_t *computed);
 /* The tiles (512 rows each) every workgroup of a launch visits, in order: workgroup w visits
  * tiles[offsets[w] .. offsets[w+1]).  which as above.
  * Each thread t of a workgroup owns rows tile*512 + 2t, 2t+1 (or the two cells of a patch, ec3d_geom::patch_x) and
