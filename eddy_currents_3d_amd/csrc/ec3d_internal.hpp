@@ -301,6 +301,12 @@ struct DevMatrix {
 };
 
 struct ec3d_mg; // multigrid hierarchy (ec3d_mg.hip)
+// beta and the restart decision of the outer iteration of ec3d_mg.hip, left on the device by k_mg_scalar
+struct MgScalars {
+    double beta;
+    int restart;
+    int pad_;
+};
 
 // Tables of ec3d_domain_integrals (ec3d_integrals.hip), made with the RHS tables of an undivided A-V handle: the
 // conducting domains in ascending id order and the conductor cell list sorted by (domain id, scan order), cut into
@@ -376,6 +382,23 @@ struct GuessHistory {
     int64_t len = 0;     // doubles per vector (0: nothing allocated)
     int wgs = 0;         // workgroups of the streaming launches
     ec3d_guess_info last{}; // what ec3d_get_guess_history reports
+};
+
+// ec3d_set_null_projection (ec3d_null.hip): the orthonormal left null vectors Q of the structured A-V matrix, one per
+// conducting component kept.  Library-owned vectors of n_pad doubles, no ghosts (the transposed kernel tests its
+// source rows instead of reading zeros), vector i at q + i * len.  The setting belongs to the handle, Q to the matrix.
+struct NullProjection {
+    int on = 0;
+    double null_tol = 1e-10;
+    bool built = false;
+    int kept = 0;
+    int64_t len = 0;
+    DevBuf<double> q;
+    DevBuf<double> part, coef; // per-workgroup partials (kept slots of wgs), the collapsed sums
+    DevBuf<double> kpart;      // the adjoint iteration's partials (ec3d_plain_begin)
+    DevBuf<MgScalars> kscal;
+    int wgs = 0;
+    ec3d_null_info last{};
 };
 
 struct ec3d_ctx {
@@ -541,6 +564,7 @@ struct ec3d_ctx {
     int precond_precision = 0; // EC3D_PRECOND_FP64 / _FP32: what the next ec3d_set_preconditioner builds (ec3d_set_precond_precision)
     int precond_coarsening = 0; // EC3D_COARSEN_REDISCRETIZE / _AGGREGATE: likewise (ec3d_set_precond_coarsening)
     GuessHistory guess;
+    NullProjection nullp;
     ec3d_ctx() = default;
     ~ec3d_ctx(); // ec3d_context.hip: the hierarchy goes (ec3d_mg_free), then every owner above, last declared first
 };
@@ -695,7 +719,7 @@ int ec3d_run_open(ec3d_ctx *c, int first, int64_t last, const char *who = nullpt
 void ec3d_after_s(ec3d_ctx *c, int it); // behind K2 / K2-in-K3 of iteration it
 void ec3d_after_p(ec3d_ctx *c, int it); // behind K5 / K5-in-K1 of iteration it
 void ec3d_launch_iteration(ec3d_ctx *c, const MatView &A, int it);
-int ec3d_launch_begin(ec3d_ctx *c, const MatView &A, double tol);
+int ec3d_launch_begin(ec3d_ctx *c, const MatView &A, double tol, bool null_project = false);
 int ec3d_single_rank_only(ec3d_ctx *c, const char *who);
 // K2 / K5 of a single-component z-slab as boundary-plane + interior launch (window sweeps, no tile lists); ec3d_dist.hip
 int ec3d_dist_set_boundary_planes(ec3d_ctx *c, int32_t *enabled);
@@ -764,6 +788,34 @@ int ec3d_guess_clear(ec3d_ctx *c);  // no pair stored, the vectors zero again
 int ec3d_guess_project(ec3d_ctx *c, const MatView &A);            // in front of ec3d_launch_begin
 int ec3d_guess_note_setup(ec3d_ctx *c);                           // behind it
 int ec3d_guess_update(ec3d_ctx *c, const MatView &A, bool store); // behind the solve and ec3d_flush_x; one read-back
+// ec3d_mg.hip: the outer iteration with M = I and an operator the caller launches (apply(x, y) enqueues y = Op x on
+// c->stream): the adjoint solves of ec3d_null.hip.  Rows [0, n) of every vector; k.r holds the right-hand side (the
+// solve starts from x = 0).  State, exits and restart rule are the solve's own (c->state, ec3d_recurrence.hpp).
+struct PlainKrylov {
+    int64_t n;
+    double *x, *r, *r0, *p, *v, *s, *t;
+    double *part;     // 2 * ec3d_plain_parts(n) doubles
+    MgScalars *scal;
+};
+int ec3d_plain_parts(int64_t n);
+int ec3d_plain_begin(ec3d_ctx *c, const PlainKrylov &k, double tol);
+template <class Apply> void ec3d_plain_iteration(ec3d_ctx *c, const PlainKrylov &k, int it, const Apply &apply);
+void ec3d_plain_stage(ec3d_ctx *c, const PlainKrylov &k, int it, int stage); // 0: behind v = Op p, 1: behind t = Op s
+template <class Apply> void ec3d_plain_iteration(ec3d_ctx *c, const PlainKrylov &k, int it, const Apply &apply)
+{
+    apply(k.p, k.v);
+    ec3d_plain_stage(c, k, it, 0);
+    apply(k.s, k.t);
+    ec3d_plain_stage(c, k, it, 1);
+}
+// ec3d_transpose.hip: y = A^T x on rows [0, A.n) of the structured form (x, y: device vectors, no ghosts needed)
+void ec3d_launch_spmv_t(const MatView &A, int64_t n, const double *x, double *y, hipStream_t s);
+// ec3d_null.hip: the left null vectors around a solve (solve_core, when nullp.on)
+void ec3d_null_free(ec3d_ctx *c);                 // Q and its memory go (a new matrix); the setting stays
+int ec3d_null_eligible(const ec3d_ctx *c, const char *who, bool set_text); // 0, EC3D_NULL_E_MATRIX or 4
+int ec3d_null_prepare(ec3d_ctx *c);               // in front of the solve: builds Q when there is none
+int ec3d_null_project(ec3d_ctx *c);               // behind the residual launch of ec3d_launch_begin, before its set-up
+int ec3d_null_note(ec3d_ctx *c, double bnorm);    // behind the solve: `removed` of ec3d_get_null_projection
 // ec3d_output.hip
 void ec3d_free_output(ec3d_ctx *c);
 // ec3d_rhs.hip

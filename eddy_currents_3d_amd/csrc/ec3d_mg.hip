@@ -74,12 +74,6 @@ template <class T> struct MgOpT {
 using MgOp = MgOpT<double>;
 using MgOp32 = MgOpT<float>;
 
-struct MgScalars {
-    double beta;
-    int restart;
-    int pad_;
-};
-
 // A level of the block multigrid of the structured A-V form (EC3D_PRECOND_BLOCK_MG).  One operator serves the three
 // A blocks, whose vectors lie vs doubles apart.  Level 0 reads block 0's class bytes of the handle's matrix, with the
 // plane pitch of the structured form (kdz) and its zero-class padding rows; coarse levels are 7 plain band streams.
@@ -1515,6 +1509,45 @@ static void launch_iteration_of(ec3d_ctx *c, int it, const BlockMg &h)
                                v[EC3D_VEC_R0], v[EC3D_VEC_R], m->part);
     k_mg_scalar<<<1, 256, 0, s>>>(MG_REXIT, g1, c->state, m->scal, m->part, (int)nb, c->hist, c->hist_cap);
     k_mg_p<<<nb, 256, 0, s>>>(n, g1, c->state, m->scal, v[EC3D_VEC_R], v[EC3D_VEC_AP], v[EC3D_VEC_P], v[EC3D_VEC_R0]);
+}
+
+// The same iteration with M = I (p^ = p, s^ = s) around an operator the caller launches: ec3d_plain_iteration of
+// ec3d_internal.hpp calls stage 0 behind v = Op p and stage 1 behind t = Op s.
+int ec3d_plain_parts(int64_t n) { return (int)dot_blocks(n); }
+
+int ec3d_plain_begin(ec3d_ctx *c, const PlainKrylov &k, double tol)
+{
+    hipStream_t s = c->stream;
+    const unsigned nb = dot_blocks(k.n);
+    const size_t bytes = (size_t)k.n * sizeof(double);
+    EC3D_HIP(hipMemsetAsync(k.x, 0, bytes, s));
+    EC3D_HIP(hipMemcpyAsync(k.r0, k.r, bytes, hipMemcpyDeviceToDevice, s));
+    EC3D_HIP(hipMemcpyAsync(k.p, k.r, bytes, hipMemcpyDeviceToDevice, s));
+    // b.b and r.r of the set-up (slots P_BB, P_RR_INIT) are the same sum: r = b
+    k_avmg_dot<<<nb, 256, 0, s>>>(k.n, Gate{nullptr, 0, 0}, k.r, k.r, 1, k.part);
+    ec3d_launch_setup(c->state, RedSrc{k.part, (int)nb, 1, (int)nb, nullptr}, tol, s);
+    EC3D_HIP(hipGetLastError());
+    return 0;
+}
+
+void ec3d_plain_stage(ec3d_ctx *c, const PlainKrylov &k, int it, int stage)
+{
+    hipStream_t s = c->stream;
+    const int64_t n = k.n;
+    const unsigned nb = dot_blocks(n);
+    const Gate g0{c->state, it, 0}, g1{c->state, it, 1};
+    if (stage == 0) {
+        k_avmg_dot<<<nb, 256, 0, s>>>(n, g0, k.r0, k.v, 0, k.part);
+        k_mg_scalar<<<1, 256, 0, s>>>(MG_ALPHA, g0, c->state, k.scal, k.part, (int)nb, nullptr, 0);
+        k_mg_s<<<nb, 256, 0, s>>>(n, g0, c->state, k.r, k.v, k.s, k.part);
+        k_mg_scalar<<<1, 256, 0, s>>>(MG_SEXIT, g0, c->state, k.scal, k.part, (int)nb, nullptr, 0);
+        return;
+    }
+    k_avmg_dot<<<nb, 256, 0, s>>>(n, g1, k.s, k.t, 1, k.part);
+    k_mg_scalar<<<1, 256, 0, s>>>(MG_OMEGA, g1, c->state, k.scal, k.part, (int)nb, nullptr, 0);
+    k_mg_xr<<<nb, 256, 0, s>>>(n, it, c->state, k.x, (const double *)k.p, (const double *)k.s, k.s, k.t, k.r0, k.r, k.part);
+    k_mg_scalar<<<1, 256, 0, s>>>(MG_REXIT, g1, c->state, k.scal, k.part, (int)nb, nullptr, 0);
+    k_mg_p<<<nb, 256, 0, s>>>(n, g1, c->state, k.scal, k.r, k.v, k.p, k.r0);
 }
 
 void ec3d_mg_free(ec3d_ctx *c)

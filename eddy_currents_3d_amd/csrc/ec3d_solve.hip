@@ -230,11 +230,16 @@ int ec3d_flush_x(ec3d_ctx *c, int stop_iter)
 
 void ec3d_launch_iteration(ec3d_ctx *c, const MatView &A, int it) { ec3d_launch_stage(c, A, it, 0); }
 
-int ec3d_launch_begin(ec3d_ctx *c, const MatView &A, double tol)
+int ec3d_launch_begin(ec3d_ctx *c, const MatView &A, double tol, bool null_project)
 {
     double **v = c->vec;
     ec3d_launch_residual(A, c->sweep_s, v[EC3D_VEC_X], v[EC3D_VEC_B], v[EC3D_VEC_R], v[EC3D_VEC_R0], v[EC3D_VEC_P],
                          c->partials, c->stream);
+    // ec3d_set_null_projection: R = R - Q (Q^T R) before R0, P and R.R are what the iteration starts from (ec3d_null.hip)
+    if (null_project) {
+        const int rc = ec3d_null_project(c);
+        if (rc) return rc;
+    }
     ec3d_launch_setup(c->state, ec3d_src_of(c, EC3D_BY_SPMV), tol, c->stream);
     ec3d_run_reset(c);
     EC3D_HIP(hipGetLastError());
@@ -273,8 +278,10 @@ static int solve_core(ec3d_ctx *c, double tol, int32_t itmax, int32_t *iter, dou
     int rc = ensure_hist(c, hist_host ? std::min<int64_t>(hist_cap, total) : 0);
     if (rc) return rc;
     const bool guess = c->guess.depth > 0; // ec3d_set_guess_history: X moved along earlier solutions first (ec3d_guess.hip)
+    const bool nullp = c->nullp.on != 0;   // ec3d_set_null_projection: the left null vectors leave the initial residual
+    if (nullp && (rc = ec3d_null_prepare(c))) return rc; // (the first solve on a matrix builds them, in the work vectors)
     if (guess && (rc = ec3d_guess_project(c, A))) return rc;
-    if ((rc = ec3d_launch_begin(c, A, tol))) return rc;
+    if ((rc = ec3d_launch_begin(c, A, tol, nullp))) return rc;
     if (guess && (rc = ec3d_guess_note_setup(c))) return rc;
     (void)ec3d_run_open(c, 1, total); // the itmax exit: the last iteration applies what is pending
 
@@ -321,6 +328,7 @@ static int solve_core(ec3d_ctx *c, double tol, int32_t itmax, int32_t *iter, dou
     }
     // whichever exit it took: the step this solve made joins the history (not after ||b|| = 0, which moved nothing)
     if (guess && (rc = ec3d_guess_update(c, A, fin.stop_iter != 0))) return rc;
+    if (nullp && (rc = ec3d_null_note(c, fin.bnorm))) return rc;
     if (hist_host && c->hist_cap > 0)
         EC3D_HIP(hipMemcpy(hist_host, c->hist, (size_t)c->hist_cap * 2 * sizeof(double), hipMemcpyDeviceToHost));
     return 0;

@@ -26,7 +26,9 @@ module ec3d_hip
               ec3d_set_precond_coarsening, ec3d_get_precond_coarsening, EC3D_COARSEN_REDISCRETIZE, EC3D_COARSEN_AGGREGATE, &
               ec3d_set_precond_grid, ec3d_get_precond_grid, ec3d_domain_integral, ec3d_domain_integrals, &
               ec3d_field_energy_info, ec3d_field_energy, ec3d_domain_link, ec3d_domain_linkage, &
-              ec3d_set_guess_history, ec3d_get_guess_history, ec3d_guess_info, EC3D_GUESS_MAX_DEPTH
+              ec3d_set_guess_history, ec3d_get_guess_history, ec3d_guess_info, EC3D_GUESS_MAX_DEPTH, &
+              ec3d_spmv_t, ec3d_set_null_projection, ec3d_get_null_projection, ec3d_left_null_vector, ec3d_null_info, &
+              EC3D_NULL_MAX_REPORT, EC3D_NULL_E_MATRIX, EC3D_NULL_E_SETUP
 
     integer(c_int), parameter :: EC3D_VEC_X = 0, EC3D_VEC_B = 1   ! Uaf, Jaf
     integer(c_int), parameter :: EC3D_PRECOND_NONE = 0, EC3D_PRECOND_MG = 1   ! ec3d_set_preconditioner
@@ -41,6 +43,18 @@ module ec3d_hip
     type, bind(C) :: ec3d_guess_info
         integer(c_int32_t) :: depth, stored, used, kept
         real(c_double) :: res_before, res_after, coef(EC3D_GUESS_MAX_DEPTH)
+    end type
+
+    integer(c_int32_t), parameter :: EC3D_NULL_MAX_REPORT = 32   ! ec3d_get_null_projection
+    integer(c_int), parameter :: EC3D_NULL_E_MATRIX = 22, EC3D_NULL_E_SETUP = 23   ! ec3d_set_null_projection, a solve's set-up
+
+    ! what ec3d_get_null_projection reports (ec3d_null_info of include/ec3d_hip.h)
+    type, bind(C) :: ec3d_null_info
+        integer(c_int32_t) :: on, built, found, kept, dropped, reported
+        real(c_double) :: null_tol, removed, setup_ms
+        integer(c_int64_t) :: seed_row(EC3D_NULL_MAX_REPORT)
+        integer(c_int32_t) :: iterations(EC3D_NULL_MAX_REPORT), was_kept(EC3D_NULL_MAX_REPORT)
+        real(c_double) :: residual(EC3D_NULL_MAX_REPORT)
     end type
 
     ! one record of ec3d_domain_integrals (ec3d_domain_integral of include/ec3d_hip.h)
@@ -293,6 +307,34 @@ module ec3d_hip
             import :: c_ptr, c_int, ec3d_guess_info
             type(c_ptr), value :: h
             type(ec3d_guess_info), intent(out) :: info
+        end function
+        ! y = A^T x on the structured A-V form of ec3d_assemble (parity probe; include/ec3d_hip.h)
+        integer(c_int) function ec3d_spmv_t(h, x, y) bind(C, name="ec3d_spmv_t")
+            import :: c_ptr, c_int, c_double
+            type(c_ptr), value :: h
+            real(c_double), intent(in) :: x(*)
+            real(c_double), intent(out) :: y(*)
+        end function
+        ! take the left null vectors of the A-V system out of every solve's initial residual (on = 0: off, the default;
+        ! null_tol <= 0: 1e-10; include/ec3d_hip.h): EC3D_NULL_E_MATRIX on a Poisson, CSR or bands + tail matrix, 4 on a z-slab
+        integer(c_int) function ec3d_set_null_projection(h, on, null_tol) bind(C, name="ec3d_set_null_projection")
+            import :: c_ptr, c_int, c_int32_t, c_double
+            type(c_ptr), value :: h
+            integer(c_int32_t), value :: on
+            real(c_double), value :: null_tol
+        end function
+        ! the setting, the components found / kept / dropped, per component seed row, adjoint iterations and residual
+        integer(c_int) function ec3d_get_null_projection(h, info) bind(C, name="ec3d_get_null_projection")
+            import :: c_ptr, c_int, ec3d_null_info
+            type(c_ptr), value :: h
+            type(ec3d_null_info), intent(out) :: info
+        end function
+        ! kept left null vector `index` (0-based; n doubles, the reference's numbering)
+        integer(c_int) function ec3d_left_null_vector(h, index, w) bind(C, name="ec3d_left_null_vector")
+            import :: c_ptr, c_int, c_int32_t, c_double
+            type(c_ptr), value :: h
+            integer(c_int32_t), value :: index
+            real(c_double), intent(out) :: w(*)
         end function
         ! U rows ec3d_rhs_step gives their right-hand side with several conducting domains (include/ec3d_hip.h)
         integer(c_int) function ec3d_set_u_rhs(h, rule) bind(C, name="ec3d_set_u_rhs")

@@ -340,7 +340,8 @@ class _SourcesAhead:
 def run(model: vxc.VxcModel, solver, steps: int | None = None, out_dir: str | None = None, on_step=None,
         on_rhs=None, on_solved=None, write_output=None, overlap_output: bool = True, on_fields=None, on_written=None,
         precond: str | None = None, u_rhs: str | None = None, integrals: bool = False, guess_history: int | None = None,
-        energy: bool = False):
+        energy: bool = False, null_projection: bool | None = None, tol: float | None = None,
+        null_tol: float | None = None):
     """The reference's run of ``model`` on ``solver`` (an EC3DSolver): assemble, then step until T >= stop (or
     ``steps`` steps).  Returns a list of per-step dicts (T, iter).  ``out_dir``: write ``field_N.vtk`` there at
     the reference's output cadence.  Hooks, all ``(k, solver, info)``: ``on_rhs`` when Jaf (B) of step k is
@@ -367,7 +368,15 @@ def run(model: vxc.VxcModel, solver, steps: int | None = None, out_dir: str | No
     solver.guess_history().  None leaves the handle's depth as it is; one handle only (an EC3DMulti raises ValueError).
     ``energy``: ``info["energy"]`` of every step holds solver.field_energy(delta) -- the magnetic energy of the box and
     the integral of A.J -- and ``info["linkage"]`` solver.domain_linkage(delta) -- the flux linkage of every
-    non-conducting domain --, taken where ``integrals`` is taken; one handle only (an EC3DMulti raises ValueError)."""
+    non-conducting domain --, taken where ``integrals`` is taken; one handle only (an EC3DMulti raises ValueError).
+    ``null_projection``: solver.set_null_projection(flag) after the assembly -- the left null vectors of the A-V system
+    leave every step's initial residual, so tolerances below the reference's can be reached; ``info["null"]`` of every
+    step then holds solver.null_projection().  None leaves the handle's setting as it is; one handle only (an EC3DMulti
+    raises ValueError); ``null_tol``: the accuracy of the adjoint solves instead of 1e-10.  ``tol``: the solves' tolerance
+    instead of the model's."""
+    if null_projection is not None and not hasattr(solver, "set_null_projection"):
+        raise ValueError("null_projection needs an EC3DSolver: the left null vectors are not available on the z-slabs of "
+                         "an EC3DMulti")
     if energy and not hasattr(solver, "field_energy"):
         raise ValueError("energy=True needs an EC3DSolver: the field energy and the flux linkages are not available on "
                          "the z-slabs of an EC3DMulti")
@@ -387,6 +396,10 @@ def run(model: vxc.VxcModel, solver, steps: int | None = None, out_dir: str | No
     solver.assemble(t["geoPHYS"], t["geoPHYS_C"], t["valPHYS"], t["BND"], t["delta"], t["dt"])
     if precond is not None:
         solver.set_preconditioner(precond)
+    if null_projection is not None:
+        solver.set_null_projection(bool(null_projection), **({} if null_tol is None else {"null_tol": float(null_tol)}))
+    if tol is not None:
+        t = dict(t, tol=float(tol))
     n = solver.n
     solver.upload("X", np.zeros(n))
     solver.upload("B", np.zeros(n))
@@ -406,7 +419,7 @@ def run(model: vxc.VxcModel, solver, steps: int | None = None, out_dir: str | No
     try:
         log = _time_loop(solver, t, prog, (sdx, sdy, sdz), conducting, out_dir, pipe, steps, on_step, on_rhs, on_solved,
                          write_output, on_fields, on_written, DT, Time, Nout, T, Ntime, Nprint, Npoint, integrals, guess=bool(guess_history),
-                         energy=energy)
+                         energy=energy, null=bool(null_projection))
     finally:
         if pipe is not None:
             pipe.finish()
@@ -415,7 +428,7 @@ def run(model: vxc.VxcModel, solver, steps: int | None = None, out_dir: str | No
 
 def _time_loop(solver, t, prog, dims, conducting, out_dir, pipe, steps, on_step, on_rhs, on_solved, write_output,
                on_fields, on_written, DT, Time, Nout, T, Ntime, Nprint, Npoint, integrals=False, guess=False,
-               energy=False):
+               energy=False, null=False):
     sdx, sdy, sdz = dims
     log = []
     ahead = _SourcesAhead(prog, T, DT, Time, steps)
@@ -430,6 +443,8 @@ def _time_loop(solver, t, prog, dims, conducting, out_dir, pipe, steps, on_step,
             info["iter"] = it
             if guess:
                 info["guess"] = solver.guess_history()
+            if null:
+                info["null"] = solver.null_projection()
             if on_solved is not None:
                 on_solved(len(log), solver, info)
             solver.post_update()

@@ -1,7 +1,7 @@
 """Run a VoxCad ``.vxc`` model the way the reference program does, on one MI355X.
 
     python -m eddy_currents_3d_amd.run model.vxc [--steps N] [--out DIR] [--device D] [--integrals FILE] [--guess-history N]
-                                                 [--energy FILE]
+                                                 [--energy FILE] [--null-projection [--null-tol Y]] [--tol X]
     python -m torch.distributed.run --nproc-per-node G -m eddy_currents_3d_amd.run model.vxc ...   (G GPUs)
 
 Reads the file (eddy_currents_3d_amd/vxc.py), assembles the A-V system on the device, and runs the
@@ -11,7 +11,9 @@ reference does).  ``--integrals FILE``: Joule loss [W] and Lorentz force [N] of 
 step, as CSV (one GPU only).  ``--guess-history N``: start every step's solve from the projection onto up to N earlier
 steps' solutions (EC3DSolver.set_guess_history; default 0 = off, one GPU only).  ``--energy FILE``: magnetic energy of
 the box [J], the integral of A.J outside and inside the conductors [J] and the flux linkage psi*I [J] of every
-non-conducting domain after every step, as CSV, one line per step (one GPU only).
+non-conducting domain after every step, as CSV, one line per step (one GPU only).  ``--null-projection``: take the left
+null vectors of the A-V system out of every solve's initial residual (EC3DSolver.set_null_projection; one GPU only), which
+lets ``--tol X`` -- the solves' tolerance instead of the model's -- go below the reference's.
 """
 from __future__ import annotations
 
@@ -68,6 +70,15 @@ def build_parser():
     ap.add_argument("--guess-history", type=int, default=0, metavar="N", choices=range(0, 9),
                     help="start every step's solve from the projection onto up to N (0 .. 8) earlier steps' solutions; "
                          "0 (default): off, the reference's warm start from the previous step alone (one GPU only)")
+    ap.add_argument("--null-projection", action="store_true",
+                    help="take the left null vectors of the A-V system (one per connected conductor, found by an adjoint "
+                         "solve after the assembly) out of every solve's initial residual, so that tolerances below the "
+                         "reference's can be reached (one GPU only)")
+    ap.add_argument("--null-tol", type=float, default=None, metavar="Y",
+                    help="accuracy the adjoint solves of --null-projection are run to (default 1e-10); a solve fails when "
+                         "one of them does not get there within its cap")
+    ap.add_argument("--tol", type=float, default=None, metavar="X",
+                    help="tolerance of the time step's solve instead of the model's (one GPU only)")
     return ap
 
 
@@ -114,6 +125,8 @@ def main(argv=None):
         ap.error(f"--precond {a.precond} runs on one GPU only; the multi-rank z-slab path has no preconditioner")
     if world > 1 and a.guess_history:
         ap.error("--guess-history runs on one GPU only; the history's sums would need every rank's")
+    if world > 1 and (a.null_projection or a.tol is not None):
+        ap.error("--null-projection and --tol run on one GPU only; the left null vectors' sums would need every rank's")
     if world > 1 and a.u_rhs != "reference":
         ap.error(f"--u-rhs {a.u_rhs} runs on one GPU only; z-slabs take one conducting domain")
     if world > 1:   # one process per GPU: z-slabs, halo exchange and reductions over RCCL
@@ -136,7 +149,12 @@ def main(argv=None):
                 log = host.run(model, s, steps=a.steps, out_dir=out_dir, on_step=on_step,
                                precond=None if a.precond == "none" else a.precond, u_rhs=a.u_rhs,
                                integrals=csv is not None, guess_history=a.guess_history or None,
-                               energy=ecsv is not None)
+                               energy=ecsv is not None, null_projection=True if a.null_projection else None,
+                               tol=a.tol, null_tol=a.null_tol)
+                if a.null_projection:
+                    q = s.null_projection()
+                    print(f"null projection: {q['kept']} of {q['found']} components kept, set-up {q['setup_ms']:.1f} ms, "
+                          + ", ".join(f"{c['iterations']} it / {c['residual']:.2e}" for c in q["components"]), flush=True)
                 n = s.n
         finally:
             if csv is not None:

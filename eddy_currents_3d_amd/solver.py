@@ -65,6 +65,14 @@ class GuessInfo(C.Structure):
                 ("res_before", C.c_double), ("res_after", C.c_double), ("coef", C.c_double * 8)]
 
 
+class NullInfo(C.Structure):
+    """ec3d_null_info of include/ec3d_hip.h."""
+    _fields_ = [("on", C.c_int32), ("built", C.c_int32), ("found", C.c_int32), ("kept", C.c_int32),
+                ("dropped", C.c_int32), ("reported", C.c_int32), ("null_tol", C.c_double), ("removed", C.c_double),
+                ("setup_ms", C.c_double), ("seed_row", C.c_int64 * 32), ("iterations", C.c_int32 * 32),
+                ("was_kept", C.c_int32 * 32), ("residual", C.c_double * 32)]
+
+
 class CsrProbe(C.Structure):
     _fields_ = [("structured", C.c_int32), ("sdx", C.c_int32), ("sdy", C.c_int32), ("sdz", C.c_int32),
                 ("n_cond", C.c_int32), ("classes", C.c_int32), ("plane_pitch", C.c_int32)]
@@ -96,10 +104,12 @@ EXPORTS = ["sprsbcgstabwr_", "ec3d_invalidate", "ec3d_create", "ec3d_destroy", "
            "ec3d_set_preconditioner", "ec3d_get_preconditioner", "ec3d_precond_apply", "ec3d_set_u_rhs",
            "ec3d_set_precond_precision", "ec3d_get_precond_precision", "ec3d_set_precond_coarsening",
            "ec3d_get_precond_coarsening", "ec3d_set_precond_grid", "ec3d_get_precond_grid",
-           "ec3d_domain_integrals", "ec3d_field_energy", "ec3d_domain_linkage", "ec3d_get_class_runs", "ec3d_get_patch_rows", "ec3d_get_k51_ap_form", "ec3d_set_guess_history", "ec3d_get_guess_history"]
+           "ec3d_domain_integrals", "ec3d_field_energy", "ec3d_domain_linkage", "ec3d_get_class_runs", "ec3d_get_patch_rows", "ec3d_get_k51_ap_form", "ec3d_set_guess_history", "ec3d_get_guess_history",
+           "ec3d_spmv_t", "ec3d_set_null_projection", "ec3d_get_null_projection", "ec3d_left_null_vector"]
 U_RHS = {"reference": 0, "all": 1}   # EC3D_U_RHS_* of include/ec3d_hip.h
 PRECOND = {"none": 0, "mg": 1, "block-mg": 2}   # EC3D_PRECOND_* of include/ec3d_hip.h
 PRECOND_E_MATRIX, PRECOND_E_COARSE = 20, 21   # ec3d_set_preconditioner's refusals
+NULL_E_MATRIX, NULL_E_SETUP = 22, 23   # ec3d_set_null_projection's refusal, a set-up that did not reach null_tol
 PRECOND_PRECISION = {"fp64": 0, "fp32": 1}   # EC3D_PRECOND_FP64 / _FP32 of include/ec3d_hip.h
 PRECOND_COARSENING = {"rediscretize": 0, "aggregate": 1}   # EC3D_COARSEN_REDISCRETIZE / _AGGREGATE
 
@@ -194,6 +204,10 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.ec3d_get_precond_grid.argtypes = [hp, hp]
     L.ec3d_set_guess_history.argtypes = [hp, C.c_int32]
     L.ec3d_get_guess_history.argtypes = [hp, C.POINTER(GuessInfo)]
+    L.ec3d_spmv_t.argtypes = [hp, _f64, _f64]
+    L.ec3d_set_null_projection.argtypes = [hp, C.c_int32, C.c_double]
+    L.ec3d_get_null_projection.argtypes = [hp, C.POINTER(NullInfo)]
+    L.ec3d_left_null_vector.argtypes = [hp, C.c_int32, _f64]
     L.ec3d_export_csr.argtypes = [hp, C.POINTER(C.c_int32), C.POINTER(C.c_int64), hp, hp, hp]
     L.ec3d_get_cel_bnd.argtypes = [hp, C.c_int, C.POINTER(C.c_int32), hp]
     L.ec3d_get_reduction_geometry.argtypes = [hp, C.c_int, C.POINTER(Geom)]
@@ -640,6 +654,13 @@ class EC3DSolver:
         _chk(self.L, self.L.ec3d_spmv(self.h, np.ascontiguousarray(x, np.float64), y), "ec3d_spmv")
         return y
 
+    def spmv_t(self, x):
+        """y = A^T x through the transposed kernel of the structured A-V form (ec3d_spmv_t): a row's terms in ascending
+        source row.  EC3DError with .status NULL_E_MATRIX on any other matrix form, 4 on a z-slab."""
+        y = np.empty(self.n)
+        _chk(self.L, self.L.ec3d_spmv_t(self.h, np.ascontiguousarray(x, np.float64), y), "ec3d_spmv_t")
+        return y
+
     def set_u_rhs(self, rule: str = "reference"):
         """Which U rows rhs_step gives their right-hand side with several conducting domains: "reference" (default)
         only the rows n <= max siznod, as src/EC3D.f90:374-392 does; "all" every U row, the consistent form and a
@@ -737,6 +758,34 @@ class EC3DSolver:
         return dict(depth=int(g.depth), stored=int(g.stored), used=int(g.used), kept=int(g.kept),
                     res_before=float(g.res_before), res_after=float(g.res_after),
                     coef=np.array(g.coef[:max(int(g.used), 0)], dtype=np.float64))
+
+    def set_null_projection(self, on: bool = True, null_tol: float = 1e-10):
+        """Take the left null vectors of the A-V system out of every solve's initial residual, so that tolerances
+        below |w.b| / ||w|| ||b|| can be reached (ec3d_set_null_projection of include/ec3d_hip.h).  The first solve on
+        a matrix finds one vector per connected conducting component by an adjoint solve to ``null_tol``.  The setting
+        stays with the handle, the vectors with the matrix.  EC3DError with .status NULL_E_MATRIX on a Poisson, CSR or
+        bands + tail matrix, 4 on a z-slab; the setting is then off.  A solve whose set-up misses ``null_tol`` raises
+        with .status NULL_E_SETUP."""
+        _chk(self.L, self.L.ec3d_set_null_projection(self.h, 1 if on else 0, float(null_tol)), "ec3d_set_null_projection")
+
+    def null_projection(self):
+        """dict(on, built, found, kept, dropped, null_tol, removed, setup_ms, components): components = per conducting
+        component (the first 32) dict(seed_row, iterations, residual, kept) -- the U row the adjoint solve was seeded
+        with (0-based, the reference's numbering), its iterations, ||A^T w|| / ||w||; removed = ||Q^T R|| / ||b|| of
+        the last solve."""
+        g = NullInfo()
+        _chk(self.L, self.L.ec3d_get_null_projection(self.h, C.byref(g)), "ec3d_get_null_projection")
+        comps = [dict(seed_row=int(g.seed_row[i]), iterations=int(g.iterations[i]), residual=float(g.residual[i]),
+                      kept=bool(g.was_kept[i])) for i in range(int(g.reported))]
+        return dict(on=bool(g.on), built=bool(g.built), found=int(g.found), kept=int(g.kept), dropped=int(g.dropped),
+                    null_tol=float(g.null_tol), removed=float(g.removed), setup_ms=float(g.setup_ms), components=comps)
+
+    def left_null_vector(self, index: int = 0):
+        """Kept left null vector ``index`` (unit norm, the reference's numbering); builds the vectors when the
+        projection is on and they do not exist yet."""
+        w = np.empty(self.n)
+        _chk(self.L, self.L.ec3d_left_null_vector(self.h, int(index), w), "ec3d_left_null_vector")
+        return w
 
     def _coarsening_setting(self):
         setting = C.c_int32(0)

@@ -225,6 +225,11 @@ int ec3d_true_residual(ec3d_handle h, double *rel, double *bnorm);
 
 /* y = A*x through the device format (src/solvers.f90:54-61), host vectors.  Parity probe. */
 int ec3d_spmv(ec3d_handle h, const double *x, double *y);
+/* y = A^T*x on the structured A-V form of ec3d_assemble (undivided handle), host vectors.  Row j adds
+ * table[class(i)][slot] * x[i] over the rows i that hold an entry in column j, in ascending i (the reference's
+ * numbering), from +0.0, every product and sum rounded on its own, zero coefficients left out.  Any other matrix
+ * form, a z-slab or a slab of ec3d_multi: EC3D_NULL_E_MATRIX / 4, nothing computed.  Uses P and AP as scratch. */
+int ec3d_spmv_t(ec3d_handle h, const double *x, double *y);
 
 /* Read the device matrix back as the reference's 1-based CSR (two-pass: jcol == NULL -> sizes).  A matrix from
  * ec3d_assemble comes back with the zeros the reference stores (boundary value 0); one from ec3d_set_matrix_csr
@@ -391,6 +396,47 @@ typedef struct {
     double coef[EC3D_GUESS_MAX_DEPTH];
 } ec3d_guess_info;
 int ec3d_get_guess_history(ec3d_handle h, ec3d_guess_info *info);
+/* Left null vectors of the A-V system taken out of every solve's initial residual (opt-in; no reference counterpart;
+ * DESIGN.md section 16).  A constant U on one connected conducting component is a right null vector of A, so A has a
+ * left null vector w per component, every residual keeps w.r = w.b, and no iterate gets below |w.b| / ||w||: the
+ * floor the reference's tolerances sit just above.  With the setting on, the first solve on a matrix finds the
+ * connected components of the conducting cells (6-neighbourhood, scan order of their first cell) and for each the
+ * U row m of its middle cell, solves A^T y = -A^T e_m from y = 0 by the reference's BiCGSTAB with restart (operator
+ * ec3d_spmv_t's kernel) to null_tol, at most 20 n^(1/3) + 2000 iterations, and sets w = y + e_m.  The w are
+ * orthonormalised by classical Gram-Schmidt in component order (fixed-order sums); one that keeps less than
+ * EC3D_NULL_MIN_KEEP of its norm is dropped and counted.  Every solve then replaces R = B - A X by R - Q (Q^T R)
+ * before R0, P and R.R are taken: since (I - Q Q^T) A = A this is the solve of A x = (I - Q Q^T) b.  B itself, ||b||,
+ * the exits, the restart rule and the iteration's kernels are untouched; the tolerance then reachable is about the
+ * adjoint residual times what was removed.  A w that did not reach null_tol is never used: the solve returns
+ * EC3D_NULL_E_SETUP with the component named in the error text.  Q belongs to the matrix (a new matrix clears it, the
+ * next solve rebuilds it); the setting belongs to the handle.  Applies to the structured form of ec3d_assemble on an
+ * undivided handle; on a Poisson, CSR or bands + tail matrix ec3d_set_null_projection(h, 1, ..) returns
+ * EC3D_NULL_E_MATRIX, on a z-slab or a slab of ec3d_multi 4, and the setting stays off; a solve that finds such a
+ * matrix under a setting made earlier returns the same status.  on = 0 (default): a solve launches and allocates
+ * nothing more and returns the same bits as before.  null_tol <= 0: the default 1e-10.
+ * ec3d_get_null_projection: built = Q exists for the present matrix; found / kept / dropped components; of the first
+ * EC3D_NULL_MAX_REPORT components the seed row (0-based, the reference's numbering), the adjoint solve's iterations,
+ * ||A^T w|| / ||w|| and whether it was kept; removed = ||Q^T R|| / ||b|| of the last solve; setup_ms = wall time of the
+ * set-up.  ec3d_left_null_vector: kept vector `index` of Q (n doubles, the reference's numbering); builds Q when the
+ * setting is on and it does not exist yet. */
+#define EC3D_NULL_MAX_REPORT 32
+#define EC3D_NULL_MIN_KEEP 1e-6
+#define EC3D_NULL_E_MATRIX 22
+#define EC3D_NULL_E_SETUP 23
+int ec3d_set_null_projection(ec3d_handle h, int32_t on, double null_tol);
+typedef struct {
+    int32_t on, built;
+    int32_t found, kept, dropped, reported;
+    double null_tol;
+    double removed;
+    double setup_ms;
+    int64_t seed_row[EC3D_NULL_MAX_REPORT];
+    int32_t iterations[EC3D_NULL_MAX_REPORT];
+    int32_t was_kept[EC3D_NULL_MAX_REPORT];
+    double residual[EC3D_NULL_MAX_REPORT];
+} ec3d_null_info;
+int ec3d_get_null_projection(ec3d_handle h, ec3d_null_info *info);
+int ec3d_left_null_vector(ec3d_handle h, int32_t index, double *w_host);
 
 /* ------------------------------------------------------------------------------------------
  * 2b. Multi-rank building blocks (z-slab decomposition, one process per GPU).
