@@ -27,7 +27,7 @@ HEADERS = [os.path.join(CSRC, "ec3d_internal.hpp"), os.path.join(CSRC, "ec3d_for
            os.path.join(CSRC, "ec3d_rccl.hpp"), os.path.join(CSRC, "ec3d_avmg_plan.hpp"),
            os.path.join(CSRC, "ec3d_mg_plan.hpp"), os.path.join(CSRC, "ec3d_sweep_lists.hpp"),
            os.path.join(CSRC, "ec3d_recurrence.hpp"), os.path.join(CSRC, "ec3d_slab_plan.hpp"),
-           os.path.join(CSRC, "ec3d_split_sweeps.hpp"), os.path.join(os.path.dirname(PKG), "include", "ec3d_hip.h")]
+           os.path.join(CSRC, "ec3d_split_sweeps.hpp"), os.path.join(CSRC, "ec3d_stream.hpp"), os.path.join(os.path.dirname(PKG), "include", "ec3d_hip.h")]
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 LDFLAGS = ["--offload-arch=gfx950", "-shared", "-fPIC", "-ldl"]
 

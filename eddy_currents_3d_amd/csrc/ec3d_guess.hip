@@ -7,26 +7,17 @@
 // classical Gram-Schmidt, scaled to ||A Q_new|| = 1 and stored, the oldest pair giving way when k = m.  The iteration
 // in between is untouched.
 //
-// Kernels.  Streaming launches of G = min(chunks, EC3D_GUESS_WGS) workgroups; workgroup b takes the chunks b, b + G, ...
-// of EC3D_TILE rows, thread t rows 2t and 2t + 1 of a chunk (one 16-byte access per stream).  Rows r >= n -- the
-// padding up to n_pad, which a bad solve may have left as 0 + NaN * 0 in the work vectors -- enter every sum as +0.0 and are
-// never stored (row_owned of ec3d_kernels.hip on a handle that is no slab: r < n; slabs are refused); the history vectors
-// are zero filled when they are allocated and written on rows < n only.
-//
-// Summation chain of a dot product (no float atomics; tests/guess_history_numpy.py restates it):
-//   a thread adds its products chunk after chunk, row 2t before row 2t + 1;
-//   the workgroup: six levels of the wave's shuffle tree (lane l takes lane l + 32, + 16, ... + 1), then the four waves'
-//   sums in order from 0.0; one partial per workgroup and sum;
-//   k_guess_collapse, one workgroup: thread t adds the partials t, t + 256, ... in order, then the same tree.
+// Kernels.  Streaming launches, sums and the rows that count (r < n: row_owned of ec3d_kernels.hip on a handle that is no
+// slab; slabs are refused): ec3d_stream.hpp.  The history vectors are zero filled when they are allocated and written on
+// rows < n only.  One partial per workgroup and sum; k_guess_collapse, one workgroup, collapses them
+// (tests/guess_history_numpy.py restates the whole).
 //
 // The host reads EC3D_GS_N scalars back once per solve (ec3d_guess_update); the decisions that kernels depend on -- a zero
 // right-hand side, a sum that is not finite, a new pair too small to keep -- are taken on the device from the same scalars.
-#include "ec3d_internal.hpp"
+#include "ec3d_stream.hpp"
 
 #include <cmath>
 #include <cstring>
-
-#define EC3D_GUESS_WGS 1024
 
 // the scalars of a solve (doubles in GuessHistory::scal)
 enum {
@@ -45,45 +36,12 @@ enum {
 
 namespace {
 
-typedef double gd2 __attribute__((ext_vector_type(2)));
 struct GPtrs {
     const double *p[EC3D_GUESS_MAX_DEPTH];
 };
 struct GIdx {
     int at[EC3D_GUESS_MAX_DEPTH + 1]; // where a collapsed sum goes in the scalars; -1: nowhere
 };
-
-__device__ __forceinline__ gd2 gload(const double *p, int64_t r) { return *reinterpret_cast<const gd2 *>(p + r); }
-// rows that count: r < n (see above)
-__device__ __forceinline__ gd2 gmask(gd2 v, int64_t r, int64_t n)
-{
-    if (r >= n) v.x = 0.0;
-    if (r + 1 >= n) v.y = 0.0;
-    return v;
-}
-__device__ __forceinline__ void gstore(double *p, int64_t r, int64_t n, gd2 v)
-{
-    if (r + 1 < n) *reinterpret_cast<gd2 *>(p + r) = v;
-    else if (r < n) p[r] = v.x;
-}
-
-// NV sums over the workgroup, valid in thread 0.  lds: NV * 4 doubles.
-template <int NV> __device__ __forceinline__ void gblock_sum(double (&v)[NV], double *lds)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        double t = v[k];
-        for (int o = 32; o > 0; o >>= 1) t = t + __shfl_down(t, o, 64);
-        if (lane == 0) lds[k * 4 + w] = t;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < NV; ++k) v[k] = (((0.0 + lds[k * 4 + 0]) + lds[k * 4 + 1]) + lds[k * 4 + 2]) + lds[k * 4 + 3];
-    }
-    __syncthreads();
-}
 
 // partials of a_i . v (i < K) and of v . v: slot j of workgroup b at part[j * gridDim.x + b]
 template <int K>
@@ -95,21 +53,21 @@ __global__ __launch_bounds__(EC3D_THREADS) void k_guess_dots(GPtrs a, const doub
 #pragma unroll
     for (int i = 0; i <= K; ++i) acc[i] = 0.0;
     for (int64_t ch = blockIdx.x; ch < nchunk; ch += gridDim.x) {
-        const int64_t r = ch * EC3D_TILE + 2 * (int64_t)threadIdx.x;
-        gd2 s[K > 0 ? K : 1];
+        const int64_t r = stream_chunk_row(ch);
+        stream_d2 s[K > 0 ? K : 1];
 #pragma unroll
-        for (int i = 0; i < K; ++i) s[i] = gload(a.p[i], r);
-        const gd2 x = gmask(gload(v, r), r, n);
+        for (int i = 0; i < K; ++i) s[i] = stream_load(a.p[i], r);
+        const stream_d2 x = stream_mask(stream_load(v, r), r, n);
 #pragma unroll
         for (int i = 0; i < K; ++i) {
-            const gd2 q = gmask(s[i], r, n);
+            const stream_d2 q = stream_mask(s[i], r, n);
             acc[i] = acc[i] + q.x * x.x;
             acc[i] = acc[i] + q.y * x.y;
         }
         acc[K] = acc[K] + x.x * x.x;
         acc[K] = acc[K] + x.y * x.y;
     }
-    gblock_sum<K + 1>(acc, lds);
+    stream_block_sum<K + 1>(acc, lds);
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int i = 0; i <= K; ++i) part[(int64_t)i * gridDim.x + blockIdx.x] = acc[i];
@@ -129,23 +87,18 @@ __global__ __launch_bounds__(EC3D_THREADS) void k_guess_collapse(const double *_
     __shared__ double lds[4];
     bool skip = false;
     for (int j = 0; j < nv; ++j) {
-        double a[1] = {0.0};
-        for (int i = threadIdx.x; i < count; i += EC3D_THREADS) a[0] = a[0] + part[(int64_t)j * count + i];
-        gblock_sum<1>(a, lds);
+        const double a = stream_block_sum(stream_strided_sum(part + (int64_t)j * count, count), lds);
         if (threadIdx.x == 0 && idx.at[j] >= 0) {
-            scal[idx.at[j]] = a[0];
-            skip |= !gfinite(a[0]);
+            scal[idx.at[j]] = a;
+            skip |= !gfinite(a);
         }
     }
-    double bb[1] = {0.0};
-    if (mode == 1) {
-        for (int i = threadIdx.x; i < bb_count; i += EC3D_THREADS) bb[0] = bb[0] + bb_part[i];
-        gblock_sum<1>(bb, lds);
-    }
+    double bb = 0.0;
+    if (mode == 1) bb = stream_block_sum(stream_strided_sum(bb_part, bb_count), lds);
     if (threadIdx.x != 0) return;
     if (mode == 1) {
-        scal[GS_BB] = bb[0];
-        if (bb[0] == 0.0) { // src/solvers.f90:23: the solve returns at once, X keeps its bits
+        scal[GS_BB] = bb;
+        if (bb == 0.0) { // src/solvers.f90:23: the solve returns at once, X keeps its bits
             for (int j = 0; j < EC3D_GUESS_MAX_DEPTH; ++j) scal[GS_COEF + j] = 0.0;
             skip = true;
         }
@@ -169,17 +122,17 @@ __global__ __launch_bounds__(EC3D_THREADS) void k_guess_axpy_x(GPtrs q, const do
 #pragma unroll
     for (int i = 0; i < K; ++i) c[i] = scal[GS_COEF + i];
     for (int64_t ch = blockIdx.x; ch < nchunk; ch += gridDim.x) {
-        const int64_t r = ch * EC3D_TILE + 2 * (int64_t)threadIdx.x;
-        gd2 s[K];
+        const int64_t r = stream_chunk_row(ch);
+        stream_d2 s[K];
 #pragma unroll
-        for (int i = 0; i < K; ++i) s[i] = gload(q.p[i], r);
-        gd2 v = gload(x, r);
+        for (int i = 0; i < K; ++i) s[i] = stream_load(q.p[i], r);
+        stream_d2 v = stream_load(x, r);
 #pragma unroll
         for (int i = 0; i < K; ++i) {
             v.x = v.x + c[i] * s[i].x;
             v.y = v.y + c[i] * s[i].y;
         }
-        gstore(x, r, n, v);
+        stream_store(x, r, n, v);
     }
 }
 
@@ -188,9 +141,9 @@ __global__ __launch_bounds__(EC3D_THREADS) void k_guess_diff(const double *__res
                                                             double *__restrict__ s, int64_t n, int64_t nchunk)
 {
     for (int64_t ch = blockIdx.x; ch < nchunk; ch += gridDim.x) {
-        const int64_t r = ch * EC3D_TILE + 2 * (int64_t)threadIdx.x;
-        const gd2 a = gload(x, r), b = gload(xs, r);
-        gstore(s, r, n, gd2{a.x - b.x, a.y - b.y});
+        const int64_t r = stream_chunk_row(ch);
+        const stream_d2 a = stream_load(x, r), b = stream_load(xs, r);
+        stream_store(s, r, n, stream_d2{a.x - b.x, a.y - b.y});
     }
 }
 
@@ -206,16 +159,16 @@ __global__ __launch_bounds__(EC3D_THREADS) void k_guess_gs(GPtrs q, GPtrs aq, co
     double h[K];
 #pragma unroll
     for (int i = 0; i < K; ++i) h[i] = scal[GS_H + i];
-    double acc[1] = {0.0};
+    double acc = 0.0;
     for (int64_t ch = blockIdx.x; ch < nchunk; ch += gridDim.x) {
-        const int64_t r = ch * EC3D_TILE + 2 * (int64_t)threadIdx.x;
-        gd2 a[K], b[K];
+        const int64_t r = stream_chunk_row(ch);
+        stream_d2 a[K], b[K];
 #pragma unroll
         for (int i = 0; i < K; ++i) {
-            a[i] = gload(aq.p[i], r);
-            b[i] = gload(q.p[i], r);
+            a[i] = stream_load(aq.p[i], r);
+            b[i] = stream_load(q.p[i], r);
         }
-        gd2 va = gload(as, r), vs = gload(s, r);
+        stream_d2 va = stream_load(as, r), vs = stream_load(s, r);
 #pragma unroll
         for (int i = 0; i < K; ++i) {
             va.x = va.x - h[i] * a[i].x;
@@ -223,14 +176,14 @@ __global__ __launch_bounds__(EC3D_THREADS) void k_guess_gs(GPtrs q, GPtrs aq, co
             vs.x = vs.x - h[i] * b[i].x;
             vs.y = vs.y - h[i] * b[i].y;
         }
-        gstore(as, r, n, va);
-        gstore(s, r, n, vs);
-        va = gmask(va, r, n);
-        acc[0] = acc[0] + va.x * va.x;
-        acc[0] = acc[0] + va.y * va.y;
+        stream_store(as, r, n, va);
+        stream_store(s, r, n, vs);
+        va = stream_mask(va, r, n);
+        acc = acc + va.x * va.x;
+        acc = acc + va.y * va.y;
     }
-    gblock_sum<1>(acc, lds);
-    if (threadIdx.x == 0) part[blockIdx.x] = acc[0];
+    acc = stream_block_sum(acc, lds);
+    if (threadIdx.x == 0) part[blockIdx.x] = acc;
 }
 
 // the new pair, scaled, into its slot -- when it is kept
@@ -241,10 +194,10 @@ __global__ __launch_bounds__(EC3D_THREADS) void k_guess_scale(const double *__re
     if (scal[GS_KEEP] == 0.0) return;
     const double inv = scal[GS_INV];
     for (int64_t ch = blockIdx.x; ch < nchunk; ch += gridDim.x) {
-        const int64_t r = ch * EC3D_TILE + 2 * (int64_t)threadIdx.x;
-        const gd2 a = gload(s, r), b = gload(as, r);
-        gstore(q, r, n, gd2{a.x * inv, a.y * inv});
-        gstore(aq, r, n, gd2{b.x * inv, b.y * inv});
+        const int64_t r = stream_chunk_row(ch);
+        const stream_d2 a = stream_load(s, r), b = stream_load(as, r);
+        stream_store(q, r, n, stream_d2{a.x * inv, a.y * inv});
+        stream_store(aq, r, n, stream_d2{b.x * inv, b.y * inv});
     }
 }
 
@@ -333,7 +286,7 @@ static int guess_alloc(ec3d_ctx *c)
     for (auto &v : g.q) EC3D_HIP(v.alloc(len));
     for (auto &v : g.aq) EC3D_HIP(v.alloc(len));
     EC3D_HIP(g.xs.alloc(len));
-    g.wgs = (int)std::min<int64_t>(c->A.n_pad / EC3D_TILE, EC3D_GUESS_WGS);
+    g.wgs = ec3d_stream_wgs(c->A.n_pad);
     EC3D_HIP(g.part.alloc((size_t)(EC3D_GUESS_MAX_DEPTH + 1) * g.wgs));
     EC3D_HIP(g.scal.alloc(EC3D_GS_N));
     EC3D_HIP(g.host.alloc(EC3D_GS_N));

@@ -18,50 +18,28 @@
 // domains' lists go to the device at assembly; the non-conducting domains' stay on the host until the first
 // ec3d_domain_linkage.
 //
-// Summation chain of a list (no float atomics: the result is a pure function of X, B and the geometry).  A value of sums[d]
-// is reached through, at most,
+// Summation chain of a list (ec3d_stream.hpp's: the result is a pure function of X, B and the geometry).  A value of
+// sums[d] is reached through, at most,
 //   k_dom_partials   3 additions of a thread's own 4 entries (stride 256), 6 levels of the wave's shuffle tree, 4 wave sums
 //   k_dom_final      ceil(chunks_d / 256) - 1 additions of a thread's own partials (stride 256), 6 levels, 4 wave sums
 // i.e. 13 + ceil(n_d / 262144) + 9 dependent additions for a domain of n_d cells: 61 at 10 M cells, and below 2100 for any
 // list whose device rows fit the library's int32 row index (4 nCd < 2^31).
 //
-// The streaming pass (ec3d_field_energy; the geometry of ec3d_guess.hip's launches).  Every xy plane is cut into
-// ceil(sdx*sdy / EC3D_TILE) chunks of EC3D_TILE cells -- of the plane, not of the device rows, so both storage forms and
-// every plane pitch cut alike --; G = min(chunks, EC3D_ENERGY_WGS) workgroups, workgroup b takes the chunks b, b + G, ...,
-// thread t the cells 2t and 2t + 1 of a chunk.  Cells past the plane's end are never loaded and add nothing.  Chain:
-//   a thread adds its terms chunk after chunk, cell 2t before cell 2t + 1;
-//   the workgroup: six levels of the wave's shuffle tree, then the four waves' sums in order from 0.0;
-//   k_energy_collapse, one workgroup: thread t adds the partials t, t + 256, ... in order, then the same tree.
+// The streaming pass (ec3d_field_energy; a streaming launch of ec3d_stream.hpp over cells instead of rows).  Every xy
+// plane is cut into ceil(sdx*sdy / EC3D_TILE) chunks of EC3D_TILE cells -- of the plane, not of the device rows, so both
+// storage forms and every plane pitch cut alike --; thread t takes the cells 2t and 2t + 1 of a chunk, cell 2t first.  Cells
+// past the plane's end are never loaded and add nothing.  k_energy_collapse, one workgroup, collapses the partials.
 // tests/field_integrals_numpy.py restates both chains.
-#include "ec3d_internal.hpp"
+#include "ec3d_stream.hpp"
 
 #include <algorithm>
 
 #define EC3D_DOM_CHUNK 1024 /* list entries per workgroup of k_dom_partials: 4 per thread */
-#define EC3D_ENERGY_WGS 1024 /* workgroups of the streaming pass, at most (EC3D_GUESS_WGS of ec3d_guess.hip) */
-#define EC3D_ENERGY_NV 5     /* its sums: Bx^2, By^2, Bz^2, A.J outside the conductors, A.J inside */
+#define EC3D_ENERGY_NV 5     /* sums of the streaming pass: Bx^2, By^2, Bz^2, A.J outside the conductors, A.J inside */
 
 namespace {
 
-typedef double d2 __attribute__((ext_vector_type(2)));
-
-// the NV sums of a 256-thread workgroup: 64-lane shuffle tree, then the waves' values through the LDS (block_sum of
-// ec3d_mg.hip, NV values at once).  Valid in thread 0.
-template <int NV> __device__ __forceinline__ void block_sum(double (&v)[NV], double (*lds)[NV])
-{
-    for (int c = 0; c < NV; ++c)
-        for (int o = 32; o > 0; o >>= 1) v[c] += __shfl_down(v[c], o, 64);
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    if (lane == 0)
-        for (int c = 0; c < NV; ++c) lds[wid][c] = v[c];
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int c = 0; c < NV; ++c) {
-            double s = 0.0;
-            for (int q = 0; q < (int)(blockDim.x >> 6); ++q) s += lds[q][c];
-            v[c] = s;
-        }
-}
+typedef stream_d2 d2;
 
 struct Grid {
     int sdx, sdy, sdz;
@@ -113,13 +91,13 @@ __global__ __launch_bounds__(256) void k_dom_partials(Grid g, const int32_t *__r
                                                       const int32_t *__restrict__ chunk, const double *__restrict__ U,
                                                       const double *__restrict__ J, double *__restrict__ partial)
 {
-    __shared__ double lds[4][4];
+    __shared__ double lds[4 * 4];
     const int64_t first = chunk[3 * (int64_t)blockIdx.x];
     const int cnt = chunk[3 * (int64_t)blockIdx.x + 1];
     double v[4] = {0.0, 0.0, 0.0, 0.0};
     for (int e = threadIdx.x; e < cnt; e += 256) // entries past the domain's end: no address formed, no load
         Term::add(v, g, cell[first + e], U, J);
-    block_sum<4>(v, lds);
+    stream_block_sum<4>(v, lds);
     if (threadIdx.x == 0)
         for (int c = 0; c < 4; ++c) partial[4 * (int64_t)blockIdx.x + c] = v[c];
 }
@@ -128,12 +106,11 @@ __global__ __launch_bounds__(256) void k_dom_partials(Grid g, const int32_t *__r
 __global__ __launch_bounds__(256) void k_dom_final(const int32_t *__restrict__ dom_chunk,
                                                    const double *__restrict__ partial, double *__restrict__ sums)
 {
-    __shared__ double lds[4][4];
+    __shared__ double lds[4 * 4];
     const int64_t c0 = dom_chunk[blockIdx.x], c1 = dom_chunk[blockIdx.x + 1];
-    double v[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int64_t ch = c0 + threadIdx.x; ch < c1; ch += 256)
-        for (int c = 0; c < 4; ++c) v[c] = v[c] + partial[4 * ch + c];
-    block_sum<4>(v, lds);
+    double v[4];
+    stream_strided_sum<4>(v, partial + 4 * c0, c1 - c0, 1, 4);
+    stream_block_sum<4>(v, lds);
     if (threadIdx.x == 0)
         for (int c = 0; c < 4; ++c) sums[4 * (int64_t)blockIdx.x + c] = v[c];
 }
@@ -144,7 +121,7 @@ __global__ __launch_bounds__(256) void k_dom_final(const int32_t *__restrict__ d
 // it is a cell.
 template <bool V> __device__ __forceinline__ d2 load2(const double *__restrict__ p, int64_t a, bool second)
 {
-    if (V) return *reinterpret_cast<const d2 *>(p + a);
+    if (V) return stream_load(p, a);
     d2 v;
     v.x = p[a];
     v.y = second ? p[a + 1] : 0.0;
@@ -159,7 +136,7 @@ __global__ __launch_bounds__(256) void k_field_energy(Grid g, int cpp, int nchun
                                                       const double *__restrict__ U, const double *__restrict__ J,
                                                       double *__restrict__ part)
 {
-    __shared__ double lds[4][EC3D_ENERGY_NV];
+    __shared__ double lds[4 * EC3D_ENERGY_NV];
     const double s = -0.07957747154594766788444e7;
     const int kdz = g.sdx * g.sdy;
     const int64_t nCd = g.nCd;
@@ -225,7 +202,7 @@ __global__ __launch_bounds__(256) void k_field_energy(Grid g, int cpp, int nchun
             acc[4] = acc[4] + (c1 ? a : 0.0);
         }
     }
-    block_sum<EC3D_ENERGY_NV>(acc, lds);
+    stream_block_sum<EC3D_ENERGY_NV>(acc, lds);
     if (threadIdx.x == 0)
         for (int c = 0; c < EC3D_ENERGY_NV; ++c) part[(int64_t)c * gridDim.x + blockIdx.x] = acc[c];
 }
@@ -233,11 +210,10 @@ __global__ __launch_bounds__(256) void k_field_energy(Grid g, int cpp, int nchun
 // One workgroup: thread t adds the partials t, t + 256, ... of every sum in order.
 __global__ __launch_bounds__(256) void k_energy_collapse(const double *__restrict__ part, int count, double *__restrict__ sums)
 {
-    __shared__ double lds[4][EC3D_ENERGY_NV];
-    double v[EC3D_ENERGY_NV] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int i = threadIdx.x; i < count; i += 256)
-        for (int c = 0; c < EC3D_ENERGY_NV; ++c) v[c] = v[c] + part[(int64_t)c * count + i];
-    block_sum<EC3D_ENERGY_NV>(v, lds);
+    __shared__ double lds[4 * EC3D_ENERGY_NV];
+    double v[EC3D_ENERGY_NV];
+    stream_strided_sum<EC3D_ENERGY_NV>(v, part, count, count);
+    stream_block_sum<EC3D_ENERGY_NV>(v, lds);
     if (threadIdx.x == 0)
         for (int c = 0; c < EC3D_ENERGY_NV; ++c) sums[c] = v[c];
 }
@@ -475,7 +451,7 @@ extern "C" int ec3d_field_energy(ec3d_handle c, const double *delta, ec3d_field_
             k_cond_bytes<<<(unsigned)((c->n_cond + 255) / 256), 256, 0, c->stream>>>(cond, c->cond_cell, c->n_cond);
             EC3D_HIP(hipGetLastError());
         }
-        e.wgs = std::min(nchunk, EC3D_ENERGY_WGS);
+        e.wgs = ec3d_stream_wgs((int64_t)nchunk * EC3D_TILE);
         EC3D_HIP(e.sums.alloc(EC3D_ENERGY_NV));
         EC3D_HIP(e.host.alloc(EC3D_ENERGY_NV));
         EC3D_HIP(e.part.alloc((size_t)EC3D_ENERGY_NV * e.wgs));

@@ -721,6 +721,8 @@ void ec3d_after_p(ec3d_ctx *c, int it); // behind K5 / K5-in-K1 of iteration it
 void ec3d_launch_iteration(ec3d_ctx *c, const MatView &A, int it);
 int ec3d_launch_begin(ec3d_ctx *c, const MatView &A, double tol, bool null_project = false);
 int ec3d_single_rank_only(ec3d_ctx *c, const char *who);
+// a handle of its own: not a slab, a rank or a handle of ec3d_multi (the caller words its own refusal)
+inline bool ec3d_own_handle(const ec3d_ctx *c) { return !(c->in_multi || c->halo > 0 || c->nranks > 1 || c->dist); }
 // K2 / K5 of a single-component z-slab as boundary-plane + interior launch (window sweeps, no tile lists); ec3d_dist.hip
 int ec3d_dist_set_boundary_planes(ec3d_ctx *c, int32_t *enabled);
 int ec3d_dist_launches(const ec3d_ctx *c, int stage, int it); // ec3d_dist.hip (call BEFORE the stage is launched)

@@ -46,7 +46,7 @@
 #include "../../include/ec3d_hip.h"
 #include "ec3d_avmg_plan.hpp"
 #include "ec3d_mg_plan.hpp"
-#include "ec3d_internal.hpp"
+#include "ec3d_stream.hpp"
 #include "ec3d_recurrence.hpp"
 
 #include <array>
@@ -504,19 +504,8 @@ __global__ __launch_bounds__(256) void k_mg_gather(MgSrc S, double *__restrict__
 }
 
 // ---- outer iteration ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double block_sum(double v, double *lds)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) lds[wid] = v;
-    __syncthreads();
-    double s = 0.0;
-    if (threadIdx.x == 0)
-        for (int q = 0; q < (int)(blockDim.x >> 6); ++q) s += lds[q];
-    return s; // valid in thread 0
-}
-
+// The reducing kernels are grid-strided over rows (thread t of workgroup b takes the rows b * 256 + t + m * 256 * gridDim.x
+// in increasing m); their workgroup sums and the scalar launch's collapse are ec3d_stream.hpp's.
 // y = A x (rows summed in offset order from the -z term); partials of a.y (slot 0) and, with two, y.y (slot 1).
 // Bytes per row: x 8 + a 8 + 1 class byte read, y 8 written = 25 B.
 // TX = float: x is p^ / s^ of the fp32 V-cycle, widened on load (exact); every product and sum stays fp64 (21 B).
@@ -526,7 +515,7 @@ __global__ __launch_bounds__(256) void k_mg_spmv_dot(MgOp A, Gate g, const TX *_
                                                      double *__restrict__ part)
 {
     __shared__ double tbl[EC3D_MG_MAXCLS * 7];
-    __shared__ double lds[8];
+    __shared__ double lds[4];
     if (gated_off(g)) return;
     if (DICT) load_table(A, tbl);
     double d0 = 0.0, d1 = 0.0;
@@ -546,10 +535,10 @@ __global__ __launch_bounds__(256) void k_mg_spmv_dot(MgOp A, Gate g, const TX *_
         d0 = d0 + a[r] * s;
         d1 = d1 + s * s;
     }
-    d0 = block_sum(d0, lds);
+    d0 = stream_block_sum(d0, lds);
     if (threadIdx.x == 0) part[blockIdx.x] = d0;
     if (two) {
-        d1 = block_sum(d1, lds);
+        d1 = stream_block_sum(d1, lds);
         if (threadIdx.x == 0) part[gridDim.x + blockIdx.x] = d1;
     }
 }
@@ -559,7 +548,7 @@ __global__ __launch_bounds__(256) void k_mg_s(int64_t n, Gate g, const SolverSta
                                               const double *__restrict__ v, double *__restrict__ s,
                                               double *__restrict__ part)
 {
-    __shared__ double lds[8];
+    __shared__ double lds[4];
     if (gated_off(g)) return;
     const double alpha = st->alpha;
     double d = 0.0;
@@ -568,7 +557,7 @@ __global__ __launch_bounds__(256) void k_mg_s(int64_t n, Gate g, const SolverSta
         s[q] = sv;
         d = d + sv * sv;
     }
-    d = block_sum(d, lds);
+    d = stream_block_sum(d, lds);
     if (threadIdx.x == 0) part[blockIdx.x] = d;
 }
 
@@ -582,7 +571,7 @@ __global__ __launch_bounds__(256) void k_mg_xr(int64_t n, int it, const SolverSt
                                                const double *__restrict__ r0, double *__restrict__ r,
                                                double *__restrict__ part)
 {
-    __shared__ double lds[8];
+    __shared__ double lds[4];
     const int stop = st->stop_iter;
     if (stop < it) return;
     const double alpha = st->alpha, omega = st->omega;
@@ -600,9 +589,9 @@ __global__ __launch_bounds__(256) void k_mg_xr(int64_t n, int it, const SolverSt
         d1 = d1 + rv * r0[q];
     }
     if (s_exit) return;
-    d0 = block_sum(d0, lds);
+    d0 = stream_block_sum(d0, lds);
     if (threadIdx.x == 0) part[blockIdx.x] = d0;
-    d1 = block_sum(d1, lds);
+    d1 = stream_block_sum(d1, lds);
     if (threadIdx.x == 0) part[gridDim.x + blockIdx.x] = d1;
 }
 
@@ -630,14 +619,12 @@ __global__ __launch_bounds__(256) void k_mg_scalar(int stage, Gate g, SolverStat
                                                    const double *__restrict__ part, int nparts, double *hist,
                                                    int64_t hist_cap)
 {
-    __shared__ double lds[8];
+    __shared__ double lds[4];
     if (gated_off(g)) return;
     const int nslot = (stage == MG_OMEGA || stage == MG_REXIT) ? 2 : 1;
     double v[2] = {0.0, 0.0};
     for (int sl = 0; sl < nslot; ++sl) {
-        double a = 0.0;
-        for (int q = threadIdx.x; q < nparts; q += blockDim.x) a += part[(int64_t)sl * nparts + q];
-        v[sl] = block_sum(a, lds);
+        v[sl] = stream_block_sum(stream_strided_sum(part + (int64_t)sl * nparts, nparts), lds);
     }
     if (threadIdx.x != 0) return;
     const int it = g.it;
@@ -1073,24 +1060,22 @@ __global__ __launch_bounds__(256) void k_avmg_upart(Gate g, const int32_t *__res
                                                     const double *__restrict__ pw, const int32_t *__restrict__ chunks,
                                                     const double *__restrict__ b, double *__restrict__ upart)
 {
-    __shared__ double lds[8];
+    __shared__ double lds[4];
     if (gated_off(g)) return;
     const int lo = chunks[2 * blockIdx.x], hi = chunks[2 * blockIdx.x + 1];
     double a = 0.0;
     for (int e = lo + (int)threadIdx.x; e < hi; e += (int)blockDim.x) a = a + pw[e] * b[plist[e]];
-    a = block_sum(a, lds);
+    a = stream_block_sum(a, lds);
     if (threadIdx.x == 0) upart[blockIdx.x] = a;
 }
 __global__ __launch_bounds__(256) void k_avmg_umean(Gate g, const int32_t *__restrict__ cco,
                                                     const double *__restrict__ upart, const double *__restrict__ inv_w,
                                                     double *__restrict__ umean)
 {
-    __shared__ double lds[8];
+    __shared__ double lds[4];
     if (gated_off(g)) return;
     const int lo = cco[blockIdx.x], hi = cco[blockIdx.x + 1];
-    double a = 0.0;
-    for (int q = lo + (int)threadIdx.x; q < hi; q += (int)blockDim.x) a += upart[q];
-    a = block_sum(a, lds);
+    const double a = stream_block_sum(stream_strided_sum(upart + lo, hi - lo), lds);
     if (threadIdx.x == 0) umean[blockIdx.x] = a * inv_w[blockIdx.x];
 }
 
@@ -1098,7 +1083,7 @@ __global__ __launch_bounds__(256) void k_avmg_umean(Gate g, const int32_t *__res
 __global__ __launch_bounds__(256) void k_avmg_dot(int64_t n, Gate g, const double *__restrict__ a,
                                                   const double *__restrict__ y, int two, double *__restrict__ part)
 {
-    __shared__ double lds[8];
+    __shared__ double lds[4];
     if (gated_off(g)) return;
     double d0 = 0.0, d1 = 0.0;
     for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x) {
@@ -1106,10 +1091,10 @@ __global__ __launch_bounds__(256) void k_avmg_dot(int64_t n, Gate g, const doubl
         d0 = d0 + a[r] * s;
         d1 = d1 + s * s;
     }
-    d0 = block_sum(d0, lds);
+    d0 = stream_block_sum(d0, lds);
     if (threadIdx.x == 0) part[blockIdx.x] = d0;
     if (two) {
-        d1 = block_sum(d1, lds);
+        d1 = stream_block_sum(d1, lds);
         if (threadIdx.x == 0) part[gridDim.x + blockIdx.x] = d1;
     }
 }
@@ -1176,9 +1161,6 @@ static std::vector<std::array<int, 3>> avmg_dims(int sdx, int sdy, int sdz)
 
 static inline int64_t pad64(int64_t n) { return (n + 63) / 64 * 64; }
 
-// a handle of its own: not a slab, a rank or a handle of ec3d_multi
-static bool own_handle(const ec3d_ctx *c) { return !(c->in_multi || c->halo > 0 || c->nranks > 1 || c->dist); }
-
 // a matrix or setting the preconditioner is not built for; a failure of the runtime during set-up.  Either way the new
 // hierarchy is dropped and the handle stays as it was
 static int mg_refuse(const std::string &text, int code = EC3D_PRECOND_E_MATRIX) { ec3d_set_error(text); return code; }
@@ -1205,7 +1187,7 @@ template <class T, class LEVEL> static T *carve_vectors(T *q, std::vector<LEVEL>
 static int set_block_mg(ec3d_ctx *c, ec3d_mg &m)
 {
     const DevMatrix &A = c->A;
-    if (!A.sav || !own_handle(c))
+    if (!A.sav || !ec3d_own_handle(c))
         return mg_refuse("ec3d_set_preconditioner: the block multigrid preconditioner needs the structured A-V form "
                          "(ec3d_assemble) on a handle of its own (not Poisson, bands + tail, a slab or a handle of "
                          "ec3d_multi)");
@@ -1381,7 +1363,7 @@ template <class T> static int set_poisson_mg(ec3d_ctx *c, ec3d_mg &m)
     constexpr bool F32 = std::is_same_v<T, float>;
     // a matrix from ec3d_set_matrix_csr whose box the caller named: the hierarchy is made from the matrix alone
     const bool csr = c->from_csr && c->precond_grid[0] > 0;
-    if (!(c->poisson_full || csr) || !own_handle(c))
+    if (!(c->poisson_full || csr) || !ec3d_own_handle(c))
         return mg_refuse("ec3d_set_preconditioner: the multigrid preconditioner needs a matrix from ec3d_assemble_poisson "
                          "on a handle of its own (not A-V, CSR, a slab or a handle of ec3d_multi)");
     const int sdx0 = csr ? c->precond_grid[0] : c->sdx, sdy0 = csr ? c->precond_grid[1] : c->sdy,
@@ -1565,7 +1547,7 @@ extern "C" int ec3d_set_precond_grid(ec3d_handle c, int32_t sdx, int32_t sdy, in
     }
     if (!c) why = "null handle";
     else if (!c->have_matrix || !c->from_csr) why = "the handle holds no matrix from ec3d_set_matrix_csr";
-    else if (!own_handle(c)) why = "not on a slab or a handle of ec3d_multi";
+    else if (!ec3d_own_handle(c)) why = "not on a slab or a handle of ec3d_multi";
     else if (sdx < 2 || sdy < 2 || sdz < 2) why = "every extent must be >= 2";
     else if ((int64_t)sdx * sdy * sdz != c->n_ref) why = "sdx * sdy * sdz is not the matrix's n";
     if (why) {

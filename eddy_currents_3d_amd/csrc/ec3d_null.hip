@@ -8,44 +8,16 @@
 // vectors kept so far.  In front of a solve (ec3d_null_project): c_i = Q_i.R, R = R - c_1 Q_1 - ... - c_k Q_k, R0 = R,
 // P = R, and the partials of R.R where the solve's set-up kernel looks for them.
 //
-// Sums.  The launch geometry of ec3d_guess.hip: G = min(chunks, EC3D_NULL_WGS) workgroups, workgroup b takes the chunks
-// b, b + G, ... of EC3D_TILE rows, thread t rows 2t and 2t + 1 of a chunk; a thread adds its products chunk after chunk,
-// the workgroup by six levels of the wave's shuffle tree and then the four waves in order; one workgroup per sum
-// collapses the partials (thread t adds partials t, t + 256, ..., then the same tree).  No float atomics: a solve is a
-// pure function of its inputs.  Rows r >= n enter every sum as +0.0 and are never stored.
-#include "ec3d_internal.hpp"
+// Sums and streaming launches: ec3d_stream.hpp.  One partial per workgroup and vector; k_null_collapse, one workgroup per
+// vector, collapses them.
+#include "ec3d_stream.hpp"
 
 #include <chrono>
 #include <cmath>
 
-#define EC3D_NULL_WGS 1024
-
 namespace {
 
-typedef double nd2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ nd2 nload(const double *p, int64_t r, int64_t n)
-{
-    nd2 v = *reinterpret_cast<const nd2 *>(p + r); // (r even, r + 1 < n_pad: inside every vector)
-    if (r >= n) v.x = 0.0;
-    if (r + 1 >= n) v.y = 0.0;
-    return v;
-}
-__device__ __forceinline__ void nstore(double *p, int64_t r, int64_t n, nd2 v)
-{
-    if (r + 1 < n) *reinterpret_cast<nd2 *>(p + r) = v;
-    else if (r < n) p[r] = v.x;
-}
-// the workgroup's sum, valid in thread 0
-__device__ __forceinline__ double nblock_sum(double t, double *lds)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    for (int o = 32; o > 0; o >>= 1) t = t + __shfl_down(t, o, 64);
-    if (lane == 0) lds[w] = t;
-    __syncthreads();
-    const double s = (((0.0 + lds[0]) + lds[1]) + lds[2]) + lds[3];
-    __syncthreads();
-    return s;
-}
+__device__ __forceinline__ stream_d2 nload(const double *p, int64_t r, int64_t n) { return stream_mask(stream_load(p, r), r, n); }
 
 // partials of (qbase + i * qstride) . v for i = blockIdx.y: part[i * gridDim.x + b]
 __global__ __launch_bounds__(EC3D_THREADS) void k_null_dots(const double *__restrict__ qbase, int64_t qstride,
@@ -56,12 +28,12 @@ __global__ __launch_bounds__(EC3D_THREADS) void k_null_dots(const double *__rest
     const double *q = qbase + (int64_t)blockIdx.y * qstride;
     double acc = 0.0;
     for (int64_t ch = blockIdx.x; ch < nchunk; ch += gridDim.x) {
-        const int64_t r = ch * EC3D_TILE + 2 * (int64_t)threadIdx.x;
-        const nd2 a = nload(q, r, n), x = nload(v, r, n);
+        const int64_t r = stream_chunk_row(ch);
+        const stream_d2 a = nload(q, r, n), x = nload(v, r, n);
         acc = acc + a.x * x.x;
         acc = acc + a.y * x.y;
     }
-    acc = nblock_sum(acc, lds);
+    acc = stream_block_sum(acc, lds);
     if (threadIdx.x == 0) part[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = acc;
 }
 
@@ -70,9 +42,7 @@ __global__ __launch_bounds__(EC3D_THREADS) void k_null_collapse(const double *__
                                                                double *__restrict__ out)
 {
     __shared__ double lds[4];
-    double a = 0.0;
-    for (int i = threadIdx.x; i < count; i += EC3D_THREADS) a = a + part[(int64_t)blockIdx.x * count + i];
-    a = nblock_sum(a, lds);
+    const double a = stream_block_sum(stream_strided_sum(part + (int64_t)blockIdx.x * count, count), lds);
     if (threadIdx.x == 0) out[blockIdx.x] = a;
 }
 
@@ -87,22 +57,22 @@ __global__ __launch_bounds__(EC3D_THREADS) void k_null_sub(const double *__restr
     __shared__ double lds[4];
     double acc = 0.0;
     for (int64_t ch = blockIdx.x; ch < nchunk; ch += gridDim.x) {
-        const int64_t r = ch * EC3D_TILE + 2 * (int64_t)threadIdx.x;
-        nd2 x = nload(v, r, n);
+        const int64_t r = stream_chunk_row(ch);
+        stream_d2 x = nload(v, r, n);
         for (int i = 0; i < k; ++i) {
             const double ci = coef[i];
-            const nd2 a = nload(qbase + (int64_t)i * qstride, r, n);
+            const stream_d2 a = nload(qbase + (int64_t)i * qstride, r, n);
             x.x = x.x - ci * a.x;
             x.y = x.y - ci * a.y;
         }
-        nstore(v, r, n, x);
-        if (r0) nstore(r0, r, n, x);
-        if (p) nstore(p, r, n, x);
+        stream_store(v, r, n, x);
+        if (r0) stream_store(r0, r, n, x);
+        if (p) stream_store(p, r, n, x);
         acc = acc + x.x * x.x;
         acc = acc + x.y * x.y;
     }
     if (!rr) return;
-    acc = nblock_sum(acc, lds);
+    acc = stream_block_sum(acc, lds);
     if (threadIdx.x == 0) rr[blockIdx.x] = acc;
 }
 
@@ -111,16 +81,14 @@ __global__ __launch_bounds__(EC3D_THREADS) void k_null_scale(const double *__res
                                                             int64_t n, int64_t nchunk)
 {
     for (int64_t ch = blockIdx.x; ch < nchunk; ch += gridDim.x) {
-        const int64_t r = ch * EC3D_TILE + 2 * (int64_t)threadIdx.x;
-        const nd2 a = nload(x, r, n);
-        nstore(y, r, n, nd2{f * a.x, f * a.y});
+        const int64_t r = stream_chunk_row(ch);
+        const stream_d2 a = nload(x, r, n);
+        stream_store(y, r, n, stream_d2{f * a.x, f * a.y});
     }
 }
 
 // v[row] = v[row] + 1 (w = y + e_m)
 __global__ void k_null_add_one(double *v, int64_t row) { v[row] = v[row] + 1.0; }
-
-bool own_handle(const ec3d_ctx *c) { return !(c->in_multi || c->halo > 0 || c->nranks > 1 || c->dist); }
 
 // connected components (6-neighbourhood) of the conducting cells, in scan order of their first cell; cells: the
 // conducting cells' REFERENCE cell indices in scan order.  Returns per component its cells in scan order.
@@ -201,7 +169,7 @@ int build(ec3d_ctx *c)
     N.last.found = ncomp;
     N.last.reported = std::min(ncomp, EC3D_NULL_MAX_REPORT);
     N.len = len;
-    N.wgs = (int)std::min<int64_t>(nc, EC3D_NULL_WGS);
+    N.wgs = ec3d_stream_wgs(len);
     if (ncomp == 0) { // no conductor: A has no such null vector, the projection is the identity
         N.built = true;
         N.last.built = 1;
@@ -317,7 +285,7 @@ void ec3d_null_free(ec3d_ctx *c)
 
 int ec3d_null_eligible(const ec3d_ctx *c, const char *who, bool set_text)
 {
-    if (!own_handle(c)) {
+    if (!ec3d_own_handle(c)) {
         if (set_text)
             ec3d_set_error(std::string(who) + ": this handle holds a z-slab (or is a slab of ec3d_multi); the left null "
                                               "vectors and their sums would need every rank's");

@@ -18,9 +18,10 @@ from __future__ import annotations
 
 import numpy as np
 
+from device_sums_numpy import THREADS, TILE, WGS, block_sum, stream_partials, strided  # noqa: F401  (re-exported)
 from fields_numpy import EDDY_SCALE, _clamped
 
-TILE, THREADS, WGS, DOM_CHUNK = 512, 256, 1024, 1024   # EC3D_TILE, threads, EC3D_ENERGY_WGS, EC3D_DOM_CHUNK
+DOM_CHUNK = 1024                                       # EC3D_DOM_CHUNK
 INV_MU0 = 0.07957747154594766788444e7                  # the literal behind s = -1 / mu0
 
 
@@ -47,25 +48,6 @@ def cell_terms(geoPHYS_C, delta, x, b):
                 cond=gc.reshape(-1) != 0)
 
 
-def block_sum(acc):
-    """[G, 256] thread values -> [G]: six levels of the wave's shuffle tree (lane l takes lane l + 32, + 16, ... + 1), then
-    the four waves in order from 0.0."""
-    w = acc.reshape(len(acc), 4, 64)
-    for o in (32, 16, 8, 4, 2, 1):
-        w = w[:, :, :o] + w[:, :, o:2 * o]
-    w = w[:, :, 0]
-    return (((0.0 + w[:, 0]) + w[:, 1]) + w[:, 2]) + w[:, 3]
-
-
-def strided(part):
-    """One workgroup over `part`: thread t adds the entries t, t + 256, ... in order, then the tree."""
-    t = np.zeros(THREADS)
-    for j in range(0, len(part), THREADS):
-        seg = part[j:j + THREADS]
-        t[:len(seg)] = t[:len(seg)] + seg
-    return float(block_sum(t[None, :])[0])
-
-
 def stream_sum(v, shape):
     """k_field_energy + k_energy_collapse: every xy plane cut into ceil(sdx*sdy / 512) chunks (cells past the plane's end
     add +0.0), workgroup w of G = min(chunks, 1024) takes chunks w, w + G, ..., thread t cell 2t, then cell 2t + 1."""
@@ -73,16 +55,7 @@ def stream_sum(v, shape):
     cpp = -(-kdz // TILE)
     p = np.zeros((sdz, cpp * TILE))
     p[:, :kdz] = np.asarray(v, np.float64).reshape(sdz, kdz)
-    p = p.reshape(sdz * cpp, THREADS, 2)
-    nchunk = len(p)
-    G = min(nchunk, WGS)
-    acc = np.zeros((G, THREADS))
-    with np.errstate(invalid="ignore"):
-        for j in range(0, nchunk, G):
-            blk = p[j:j + G]
-            acc[:len(blk)] = acc[:len(blk)] + blk[:, :, 0]
-            acc[:len(blk)] = acc[:len(blk)] + blk[:, :, 1]
-        return strided(block_sum(acc))
+    return strided(stream_partials(p.reshape(sdz * cpp, THREADS, 2)))
 
 
 def list_sum(v):

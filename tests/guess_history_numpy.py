@@ -13,36 +13,10 @@ and the update of the stored pairs behind it, every sum in the device's order.
 No test lives here (the name does not start with test_)."""
 import numpy as np
 
-TILE, THREADS, WGS = 512, 256, 1024     # EC3D_TILE, EC3D_THREADS, EC3D_GUESS_WGS
+from device_sums_numpy import THREADS, TILE, WGS, stream_dot as dot_device  # noqa: F401  (k_guess_dots + k_guess_collapse)
+
 MIN_NEW = 1e-6                          # EC3D_GUESS_MIN_NEW
 MAX_DEPTH = 8
-
-
-def block_sum(acc):
-    """[G, 256] thread values -> [G]: six levels of the wave's shuffle tree, then the four waves in order from 0.0."""
-    w = acc.reshape(len(acc), 4, 64)
-    for o in (32, 16, 8, 4, 2, 1):
-        w = w[:, :, :o] + w[:, :, o:2 * o]
-    w = w[:, :, 0]
-    return (((0.0 + w[:, 0]) + w[:, 1]) + w[:, 2]) + w[:, 3]
-
-
-def dot_device(a, b):
-    assert len(a) == len(b) and len(a) % TILE == 0
-    nchunk = len(a) // TILE
-    G = min(nchunk, WGS)
-    prod = (a * b).reshape(nchunk, THREADS, 2)
-    acc = np.zeros((G, THREADS))
-    for j in range(0, nchunk, G):               # workgroup w takes chunks w, w + G, ...: row 2t, then row 2t + 1
-        blk = prod[j:j + G]
-        acc[:len(blk)] = acc[:len(blk)] + blk[:, :, 0]
-        acc[:len(blk)] = acc[:len(blk)] + blk[:, :, 1]
-    part = block_sum(acc)
-    t = np.zeros(THREADS)                       # k_guess_collapse: thread t adds partials t, t + 256, ...
-    for j in range(0, G, THREADS):
-        seg = part[j:j + THREADS]
-        t[:len(seg)] = t[:len(seg)] + seg
-    return float(block_sum(t[None, :])[0])
 
 
 class History:

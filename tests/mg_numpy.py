@@ -27,6 +27,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from device_sums_numpy import block_sum as _block_sums, strided as mg_scalar_sum   # the workgroup tree, k_mg_scalar's collapse
+
 MAX_COARSE_ROWS = 4096
 DEFAULT_PRE, DEFAULT_POST, DEFAULT_COARSE = 2, 2, 16
 
@@ -221,20 +223,6 @@ MG_DOT_BLOCKS = 2048  # EC3D_MG_DOT_BLOCKS
 EXIT_NONE, EXIT_S, EXIT_R = 0, 1, 2  # SolverState::stop_kind: 0 for the itmax exit and ||b|| = 0
 
 
-def _block_sums(v):
-    """block_sum of every 256-value row of v: a 64-lane __shfl_down tree per wave (o = 32 ... 1), then the four wave
-    sums added in order from 0.0."""
-    w = v.reshape(-1, 4, 64)
-    o = 32
-    while o >= 1:
-        w = w[..., :o] + w[..., o:2 * o]
-        o //= 2
-    s = np.zeros(w.shape[0])
-    for q in range(4):
-        s = s + w[:, q, 0]
-    return s
-
-
 def mg_partials(prod):
     """The per-workgroup partials of one reducing MG kernel (k_mg_spmv_dot, k_mg_s, k_mg_xr) over the row products
     `prod`: nb = min(2048, ceil(n / 256)) workgroups of 256 threads, thread t of workgroup k adding rows
@@ -250,18 +238,6 @@ def mg_partials(prod):
     for m in range(M):
         acc = acc + P[m]
     return _block_sums(acc)
-
-
-def mg_scalar_sum(part):
-    """k_mg_scalar: thread t adds part[t], part[t + 256], ... from 0.0, then block_sum."""
-    nr = -(-len(part) // 256)
-    P = np.zeros(nr * 256)
-    P[:len(part)] = part
-    P = P.reshape(nr, 256)
-    acc = np.zeros(256)
-    for m in range(nr):
-        acc = acc + P[m]
-    return float(_block_sums(acc)[0])
 
 
 def mg_dot(a, b):

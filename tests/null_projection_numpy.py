@@ -18,11 +18,16 @@ The system's CSR comes in the reference's numbering ([Ax | Ay | Az | U], 1-based
               per component: A^T y = -A^T e_m from y = 0 to null_tol, w = y + e_m; then Gram-Schmidt in component
               order, a vector that keeps less than MIN_KEEP of its norm being dropped.
   project     v - Q (Q^T v), all coefficients taken first, then subtracted in component order.
+  project_device
+              the same on vectors in device numbering with every sum in the device's order (k_null_dots, k_null_collapse,
+              k_null_sub through tests/device_sums_numpy.py): expected to equal ec3d_null_project bit for bit.
 
 No test lives here (the name does not start with test_)."""
 from __future__ import annotations
 
 import numpy as np
+
+from device_sums_numpy import THREADS, TILE, stream_dot, stream_partials
 
 MIN_KEEP = 1e-6          # EC3D_NULL_MIN_KEEP of include/ec3d_hip.h
 DEFAULT_NULL_TOL = 1e-10
@@ -121,6 +126,23 @@ def project(Q, v):
     for ci, q in zip(c, Q):
         v = v - ci * q
     return v, c
+
+
+def project_device(Q_dev, r_dev, n, launched=None):
+    """(r, c, rr_part): ec3d_null_project on vectors in device numbering, zero padded to n_pad (oracle.device_system).
+    c_i = stream_dot(Q_i, r), all taken first; r = r - c_i Q_i in component order, every term a rounded product and a
+    rounded difference; rr_part: the per-workgroup partials of r.r as k_null_sub leaves them -- one per workgroup of its
+    launch (`launched`: the residual launch's count, where that is not the streaming launch's own).  Rows >= n enter
+    every sum as +0.0 and come back as they went in."""
+    r = np.array(r_dev, np.float64)
+    assert len(r) % TILE == 0 and all(len(q) == len(r) for q in Q_dev)
+    live = np.arange(len(r)) < n
+    c = np.array([stream_dot(np.where(live, q, 0.0), np.where(live, r, 0.0)) for q in Q_dev])
+    x = np.where(live, r, 0.0)
+    for ci, q in zip(c, Q_dev):
+        x = x - ci * np.where(live, q, 0.0)
+    r[:n] = x[:n]
+    return r, c, stream_partials((x * x).reshape(-1, THREADS, 2), launched=launched)
 
 
 def bicgstab(op, b, x0, tol, itmax, Q=None):

@@ -30,6 +30,7 @@ pytestmark = pytest.mark.gpu
 
 AV = {"g2": "g2_conducting_hole_16x15x14", "g8a": "g8a_two_plates_18x16x16"}
 SCALES = (1.0, -0.5, 2.0, 1.0, 0.25)
+BIG_ITMAX = 12     # 97 x 81 x 77 needs 494 iterations to 1e-5, 23 ms each in the CPU twin: five solves of 13 iterations instead
 
 
 @pytest.fixture(scope="module")
@@ -76,21 +77,30 @@ def check_sequence(s, twin, rhs, x0, tol, itmax, cap, where):
 
 
 # ---- the twin, bit for bit ---------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("dims, dictionary", [((17, 9, 5), True), ((16, 16, 16), True), ((16, 16, 16), False)],
-                         ids=["17x9x5", "16x16x16", "16x16x16-bands"])
-def test_poisson_equals_twin(E, oracle, dims, dictionary):
+# 97 x 81 x 77: 604 989 rows, an odd count (the last pair of rows is half masked) in 1182 chunks of 512 -- more than the 1024
+# workgroups of a streaming launch, so workgroups 0 ... 157 take a second chunk.  Its itmax keeps the twin's CPU solves short;
+# the comparison is the same.
+PADDING = {(17, 9, 5): 259, (97, 81, 77): 195}
+
+
+@pytest.mark.parametrize("dims, dictionary, itmax", [((17, 9, 5), True, 2000), ((16, 16, 16), True, 2000),
+                                                     ((16, 16, 16), False, 2000), ((97, 81, 77), True, BIG_ITMAX)],
+                         ids=["17x9x5", "16x16x16", "16x16x16-bands", "97x81x77"])
+def test_poisson_equals_twin(E, oracle, dims, dictionary, itmax):
     valA, irow, jcol = oracle.poisson_csr(*dims)
     b0 = oracle.bar_rhs(dims[0]) if dims[0] == dims[1] == dims[2] else bar_rhs_box(dims)
-    tol, itmax, cap = 1e-5, 2000, 48
+    tol, cap = 1e-5, 48
     with E.EC3DSolver(dictionary=dictionary) as s:
         s.assemble_poisson(*dims)
         lay = s.vector_layout()
-        assert lay["n_pad"] - lay["n"] == (259 if dims == (17, 9, 5) else 0)
+        assert lay["n_pad"] - lay["n"] == PADDING.get(dims, 0)
+        assert (lay["n_pad"] // 512 > 1024) == (dims == (97, 81, 77))
         s.set_guess_history(2)
         twin = GH.for_handle(oracle, s, valA, irow, jcol, 2, tol, itmax, cap)
         seen = check_sequence(s, twin, [a * b0 for a in SCALES], np.zeros(len(b0)), tol, itmax, cap, f"poisson {dims}")
     assert seen[0]["used"] == 0 and seen[0]["kept"] == 1 and seen[1]["used"] == 1
-    assert seen[1]["res_after"] <= 10 * tol         # the second right-hand side is a multiple of the first
+    if itmax == 2000:                               # (a solve cut short leaves less than the whole direction)
+        assert seen[1]["res_after"] <= 10 * tol     # the second right-hand side is a multiple of the first
 
 
 def test_bands_and_tail_equals_twin(E, oracle):

@@ -9,6 +9,9 @@ csrc/ec3d_transpose.hip, csrc/ec3d_null.hip).
   the cap, ec3d_left_null_vector within 1e-6 of the twin's w up to the sign;
 * THE TEST THAT FAILS WITHOUT THE FEATURE: tol = 1e-8, itmax = 2000 on every captured step -- with the projection
   iter <= 2000 and ||P (b - A x)|| / ||b|| <= 2e-8, without it iter = itmax + 1;
+* ec3d_null_project == the twin's project_device BIT FOR BIT -- R, R0 and P of a solve with itmax = -1 (the residual launch,
+  the projection and the set-up, no iteration) against the projection of the same call's R with the projection off -- on g2,
+  pitched and not, and on a 96 x 96 x 64 box whose device rows exceed 1024 chunks: the second trip of the kernels' chunk loop;
 * at the fixtures' own tolerance x is within 10 tol of the captured xout on the A blocks (U printed, not asserted);
 * off is a fresh handle's bits; B keeps its bytes; guess history on top; refusals; host.run."""
 import numpy as np
@@ -27,6 +30,7 @@ SIX = ["g2_conducting_hole_16x15x14", "g2v_conducting_moving_16x15x14", "g3_movi
 # (tests/test_gpu_multidomain.py, STRUCTURED): there the transposed product is refused, as for every bands + tail matrix,
 # and that is what its case asserts.  g8d -- two touching domains in the structured form -- stands beside it.
 CASES = SIX + ["g8d_g3_split_18x16x12"]
+BIG_NULL_TOL = 1e-10
 BANDS_AND_TAIL = {"g8c_side_by_side_20x18x14"}
 
 
@@ -154,6 +158,72 @@ def test_reaches_1e_8_on_every_captured_step(E, oracle, setups, name):
             assert ito == itmax + 1
             wb = np.sqrt(sum((w @ (b - A(x0))) ** 2 for w in W)) / np.linalg.norm(b)
             assert abs(info["removed"] - wb) <= 1e-6 * wb + 1e-12
+
+
+def _g2_args():
+    g = load_golden("g2_conducting_hole_16x15x14")
+    return (g["geoPHYS"], g["geoPHYS_C"], g["valPHYS"], g["BND"], g["delta"], float(g["dt"]))
+
+
+def _big_args():
+    from test_gpu_field_integrals import big_box
+    return big_box()
+
+
+# null_tol of the big box: the bits of a projection do not depend on how accurate Q is (docs/rounds/r10.md has the adjoint
+# solve's iterations at this value)
+@pytest.mark.parametrize("args_of, pitched, null_tol", [(_g2_args, False, 1e-10), (_g2_args, True, 1e-10),
+                                                        (_big_args, False, BIG_NULL_TOL)],
+                         ids=["g2-auto", "g2-pitched", "big"])
+def test_projection_equals_the_twin_bit_for_bit(E, monkeypatch, args_of, pitched, null_tol):
+    monkeypatch.delenv("EC3D_PITCH", raising=False)
+    if pitched:
+        monkeypatch.setenv("EC3D_PITCH", "2")
+    args = args_of()
+    n_ref = 3 * args[0].size + int(np.count_nonzero(args[1]))
+    rng = np.random.default_rng(16)
+    x, b = rng.standard_normal(n_ref), rng.standard_normal(n_ref)
+    tol = 1e-8
+
+    def set_up_only(s):
+        s.upload("X", x)
+        s.upload("B", b)
+        it, _ = s.solve_resident(tol, -1)
+        assert it == 0
+        return [s.download(w) for w in ("R", "R0", "P")]
+
+    with E.EC3DSolver() as s:
+        s.assemble(*args)
+        plain = set_up_only(s)
+        assert all(np.array_equal(v.view(np.uint64), plain[0].view(np.uint64)) for v in plain)
+        s.set_null_projection(True, null_tol)
+        s.upload("B", b)
+        s.upload("X", np.zeros(n_ref))
+        s.solve_resident(tol, 0)                      # any solve: the vectors are built in front of it
+        info = s.null_projection()
+        print(f"null_tol {null_tol:g}: {info['kept']} kept, adjoint iterations "
+              f"{[c['iterations'] for c in info['components']]}, set-up {info['setup_ms']:.0f} ms")
+        assert info["built"] and info["kept"] >= 1
+        W = [s.left_null_vector(i) for i in range(info["kept"])]
+        got = set_up_only(s)
+        removed = s.null_projection()["removed"]
+        lay, rm = s.vector_layout(), s.row_map().astype(np.int64)
+    n, n_pad = int(lay["n"]), int(lay["n_pad"])
+    assert (n_pad // 512 > 1024) == (args_of is _big_args)      # the big box: workgroups 0 ... take a second chunk
+
+    def to_dev(v):
+        d = np.zeros(n_pad)
+        d[rm] = v
+        return d
+    want, c, _ = NP.project_device([to_dev(w) for w in W], to_dev(plain[0]), n)
+    want = want[rm]
+    for name, v in zip(("R", "R0", "P"), got):
+        assert np.array_equal(v.view(np.uint64), want.view(np.uint64)), \
+            f"{name}: {np.count_nonzero(v != want)} rows differ, max {np.abs(v - want).max():.3e}"
+    assert not np.array_equal(want, plain[0])         # (it did something)
+    wb = float(np.sqrt(c @ c) / np.linalg.norm(b))
+    print(f"removed {removed:.6e}, twin {wb:.6e}")
+    assert abs(removed - wb) <= 1e-6 * wb + 1e-12
 
 
 @pytest.mark.parametrize("name", FOUR)
