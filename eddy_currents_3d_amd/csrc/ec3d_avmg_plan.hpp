@@ -107,3 +107,15 @@ inline std::string ec3d_avmg_plan(int sdx, int sdy, int sdz, int pitch, int64_t 
     for (int32_t r : p.ublack) p.ucomp.push_back(comp_of[(size_t)r]);
     return std::string();
 }
+
+// The plan of N, the preconditioner of the null projection's adjoint solves (ec3d_set_null_precond): U^T has the
+// constants as LEFT null vector, so the projections take the plain mean of a component -- every weight 1 (1.0 * b is b,
+// and the sums keep k_avmg_upart / k_avmg_umean's order), inv_w = 1 / cells.  Lists, chunks and components stay.
+inline void ec3d_avmg_plain_means(AvmgPlan &p)
+{
+    std::fill(p.pw.begin(), p.pw.end(), 1.0);
+    for (size_t cc = 0; cc < p.inv_w.size(); ++cc) {
+        const int32_t lo = p.chunks[2 * (size_t)p.cco[cc]], hi = p.chunks[2 * (size_t)p.cco[cc + 1] - 1];
+        p.inv_w[cc] = 1.0 / (double)(hi - lo);
+    }
+}

@@ -399,6 +399,11 @@ struct NullProjection {
     DevBuf<MgScalars> kscal;
     int wgs = 0;
     ec3d_null_info last{};
+    // ec3d_set_null_precond: N of the adjoint solves.  The setting stays with the handle; the hierarchy lives inside one
+    // set-up only, what it looked like is kept for ec3d_get_null_precond
+    int precond = EC3D_NULL_PRECOND_NONE, pre = 0, post = 0, coarse = 0;
+    int32_t levels = 0, dims[3 * EC3D_NULL_PRECOND_MAX_LEVELS] = {0};
+    double hierarchy_ms = 0.0;
 };
 
 struct ec3d_ctx {
@@ -810,6 +815,13 @@ template <class Apply> void ec3d_plain_iteration(ec3d_ctx *c, const PlainKrylov 
     apply(k.s, k.t);
     ec3d_plain_stage(c, k, it, 1);
 }
+// ec3d_mg.hip: N ~ (A^T)^-1 of ec3d_set_null_precond -- a block hierarchy of its own (kind: EC3D_NULL_PRECOND_BLOCK_MG
+// or _A; 0 sweeps: the defaults), which the caller deletes; one right-preconditioned iteration with A^T and N in k's
+// vectors (p^ and s^ are the hierarchy's); levels and 3 dims per level of the hierarchy
+int ec3d_null_mg_build(ec3d_ctx *c, int kind, int pre, int post, int coarse, ec3d_mg **out);
+void ec3d_null_mg_delete(ec3d_mg *m);
+void ec3d_null_mg_dims(const ec3d_mg *m, int32_t *levels, int32_t *dims);
+void ec3d_null_mg_iteration(ec3d_ctx *c, const ec3d_mg *m, const PlainKrylov &k, int it);
 // ec3d_transpose.hip: y = A^T x on rows [0, A.n) of the structured form (x, y: device vectors, no ghosts needed)
 void ec3d_launch_spmv_t(const MatView &A, int64_t n, const double *x, double *y, hipStream_t s);
 // ec3d_null.hip: the left null vectors around a solve (solve_core, when nullp.on)

@@ -35,7 +35,8 @@
 // iteration stays fp64 (tests/mg_numpy_f32.py restates it).
 //
 // EC3D_PRECOND_BLOCK_MG (the structured A-V form) shares the outer iteration's vector kernels;
-// its own kernels (k_avmg_*) are below, behind the single-component ones.
+// its own kernels (k_avmg_*) are below, behind the single-component ones.  N of ec3d_set_null_precond (section 16a) is
+// the same hierarchy on the transposed blocks, a BlockMg of the null set-up's own around the same outer iteration.
 //
 // Host side: a handle's ec3d_mg owns one hierarchy (PoissonMg<double>, PoissonMg<float> or BlockMg), built completely
 // before it replaces the old one; launch_schedule is the cycle's order of launches for all three.
@@ -144,6 +145,9 @@ struct BlockMg {
     DevBuf<double> ubuf;        // AvmgPlan's pw, inv_w, then umean (one per component) and upart (one per chunk)
     double *pw = nullptr, *inv_w = nullptr, *umean = nullptr, *upart = nullptr;
     int ncomp = 0, nchunk = 0;
+    // N of the null projection's adjoint solves (ec3d_set_null_precond)
+    bool adjoint = false;       // the U sweeps run on U^T between two plain-mean projections (pw = 1, inv_w = 1 / cells)
+    DevBuf<double> bands0;      // EC3D_NULL_PRECOND_BLOCK_MG: the transposed A block gathered once, level 0's band streams
 };
 
 // What ec3d_ctx::mg points to: the settings and the outer iteration's scratch, which every kind has, and the hierarchy
@@ -1048,6 +1052,81 @@ __global__ __launch_bounds__(256) void k_avmg_usweep(AvOp U, Gate g, const int32
     x[r] = val;
 }
 
+// The same half-sweep on U^T (N of the adjoint solves): the coefficient towards neighbour q is the NEIGHBOUR's row's
+// coefficient 6 - q, looked up under the neighbour's U class once the neighbour is known to lie inside the box; a
+// neighbour without a U unknown gives 0.  The diagonal is the row's own.
+__global__ __launch_bounds__(256) void k_avmg_usweep_t(AvOp U, Gate g, const int32_t *__restrict__ list,
+                                                       const int32_t *__restrict__ comp, const double *__restrict__ umean,
+                                                       int64_t count, int init, double *__restrict__ x,
+                                                       const double *__restrict__ b)
+{
+    __shared__ double tbl[EC3D_AVMG_MAXCLS * 7];
+    if (gated_off(g)) return;
+    av_load_table(U, tbl);
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= count) return;
+    const int64_t r = list[e];
+    const double d = av_diag<true>(U, tbl, r);
+    const double bb = b[r] - umean[comp[e]];
+    double val = 0.0;
+    if (d != 0.0 && init) {
+        val = bb / d;
+    } else if (d != 0.0) {
+        const Pos p = pos_of(U, r);
+        const int64_t off[7] = {-U.kdz, -(int64_t)U.sdx, -1, 0, 1, U.sdx, U.kdz};
+        const bool in[7] = {p.k > 0, p.j > 0, p.i > 0, false, p.i + 1 < U.sdx, p.j + 1 < U.sdy, p.k + 1 < U.sdz};
+        double c[7], v[6];
+#pragma unroll
+        for (int q = 0; q < 7; ++q) {
+            c[q] = 0.0;
+            if (!in[q]) continue;
+            const unsigned kn = (unsigned)((int)U.cls[r + off[q]] - U.cls0);
+            if (kn < (unsigned)U.ncls) c[q] = tbl[7 * kn + 6 - q];
+        }
+        c[3] = d;
+        neighbours(U, p, r, [&](int64_t q) { return x[q]; }, v);
+        val = gs_value(c, v, bb);
+    }
+    x[r] = val;
+}
+
+// x = x - umean[its component] on the U unknowns' rows: the output projection of N
+__global__ __launch_bounds__(256) void k_avmg_usub(Gate g, const int32_t *__restrict__ list,
+                                                   const int32_t *__restrict__ comp, const double *__restrict__ umean,
+                                                   int64_t count, double *__restrict__ x)
+{
+    if (gated_off(g)) return;
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= count) return;
+    const int64_t r = list[e];
+    x[r] = x[r] - umean[comp[e]];
+}
+
+// Level 0 of the TRANSPOSED A block as seven band streams (set-up of N, once): band q of row r is band 6 - q of row
+// r + off[q], looked up under that row's class byte once the neighbour is known to lie inside the box and to have a
+// class in [cls0, cls0 + ncls) -- else 0 --; the diagonal is the row's own.  A row without coefficients stays one.
+__global__ __launch_bounds__(256) void k_avmg_gather_t(AvOp A, double *__restrict__ bands, int64_t n_pad)
+{
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= A.n) return;
+    const Pos p = pos_of(A, r);
+    const unsigned k = (unsigned)((int)A.cls[r] - A.cls0);
+    double c[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (k < (unsigned)A.ncls && p.j < A.sdy) {
+        const int64_t off[7] = {-A.kdz, -(int64_t)A.sdx, -1, 0, 1, A.sdx, A.kdz};
+        const bool in[7] = {p.k > 0, p.j > 0, p.i > 0, false, p.i + 1 < A.sdx, p.j + 1 < A.sdy, p.k + 1 < A.sdz};
+        c[3] = A.table[(size_t)(A.cls0 + (int)k) * 16 + 3];
+#pragma unroll
+        for (int q = 0; q < 7; ++q) {
+            if (!in[q]) continue;
+            const unsigned kn = (unsigned)((int)A.cls[r + off[q]] - A.cls0);
+            if (kn < (unsigned)A.ncls) c[q] = A.table[(size_t)(A.cls0 + (int)kn) * 16 + 6 - q];
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 7; ++q) bands[(size_t)q * n_pad + r] = c[q];
+}
+
 // The U block of the A-V system is singular: a constant on one conducting component (A = 0) is a null vector of the
 // whole operator, and the U rows' left null vector is w = the product over the axes of 1/2 where the cell misses a
 // neighbour along that axis, 1 elsewhere (the one-sided rows carry the factor 2; exact where a missing neighbour is
@@ -1131,13 +1210,19 @@ void launch_cycle(const ec3d_mg &m, const BlockMg &h, Gate g, const double *r, d
         k_avmg_upart<<<(unsigned)h.nchunk, 256, 0, s>>>(g, h.plist, h.pw, h.chunks, r + ub, h.upart);
         k_avmg_umean<<<(unsigned)h.ncomp, 256, 0, s>>>(g, h.cco, h.upart, h.inv_w, h.umean);
     }
+    const auto usweep = h.adjoint ? k_avmg_usweep_t : k_avmg_usweep;
     for (int sw = 0; sw < m.pre + m.post; ++sw) {
         if (h.nu_red)
-            k_avmg_usweep<<<blocks_of(h.nu_red), 256, 0, s>>>(h.uop, g, h.ulist, h.ucomp, h.umean, h.nu_red, sw == 0,
-                                                               z + ub, r + ub);
+            usweep<<<blocks_of(h.nu_red), 256, 0, s>>>(h.uop, g, h.ulist, h.ucomp, h.umean, h.nu_red, sw == 0, z + ub, r + ub);
         if (h.nu_black)
-            k_avmg_usweep<<<blocks_of(h.nu_black), 256, 0, s>>>(h.uop, g, h.ulist + h.nu_red, h.ucomp + h.nu_red, h.umean,
-                                                                 h.nu_black, 0, z + ub, r + ub);
+            usweep<<<blocks_of(h.nu_black), 256, 0, s>>>(h.uop, g, h.ulist + h.nu_red, h.ucomp + h.nu_red, h.umean,
+                                                        h.nu_black, 0, z + ub, r + ub);
+    }
+    if (h.adjoint && h.ncomp) { // N: the plain mean of every component leaves the swept z too
+        const int64_t nu = h.nu_red + h.nu_black;
+        k_avmg_upart<<<(unsigned)h.nchunk, 256, 0, s>>>(g, h.plist, h.pw, h.chunks, z + ub, h.upart);
+        k_avmg_umean<<<(unsigned)h.ncomp, 256, 0, s>>>(g, h.cco, h.upart, h.inv_w, h.umean);
+        k_avmg_usub<<<blocks_of(nu), 256, 0, s>>>(g, h.ulist, h.ucomp, h.umean, nu, z + ub);
     }
 }
 
@@ -1184,7 +1269,9 @@ template <class T, class LEVEL> static T *carve_vectors(T *q, std::vector<LEVEL>
 }
 
 // Both set-ups fill a new ec3d_mg, which ec3d_set_preconditioner puts in the old one's place when they return 0.
-static int set_block_mg(ec3d_ctx *c, ec3d_mg &m)
+// null_kind: EC3D_NULL_PRECOND_NONE for M of section 10; EC3D_NULL_PRECOND_BLOCK_MG / _A for N of the adjoint solves
+// (the U block transposed and projected with plain means on both sides; BLOCK_MG: level 0 of the A blocks transposed too).
+static int set_block_mg(ec3d_ctx *c, ec3d_mg &m, int null_kind = EC3D_NULL_PRECOND_NONE)
 {
     const DevMatrix &A = c->A;
     if (!A.sav || !ec3d_own_handle(c))
@@ -1207,9 +1294,11 @@ static int set_block_mg(ec3d_ctx *c, ec3d_mg &m)
     const std::string refusal =
         ec3d_avmg_plan(sdx, sdy, sdz, pitch, nCd, cls.data(), tab.data(), a_hi, u_lo, u_hi, EC3D_AVMG_UCHUNK, p);
     if (!refusal.empty()) return mg_refuse(refusal);
+    if (null_kind != EC3D_NULL_PRECOND_NONE) ec3d_avmg_plain_means(p);
     const std::vector<std::array<int, 3>> dims = avmg_dims(sdx, sdy, sdz);
     const int L = (int)dims.size();
     BlockMg &h = m.h.emplace<BlockMg>();
+    h.adjoint = null_kind != EC3D_NULL_PRECOND_NONE;
     h.lev.resize((size_t)L);
     AvOp &A0 = h.lev[0].op;
     A0 = AvOp{};
@@ -1222,6 +1311,13 @@ static int set_block_mg(ec3d_ctx *c, ec3d_mg &m)
     h.uop = A0;
     h.uop.cls = A.cls + 3 * nCd;
     h.uop.cls0 = u_lo; h.uop.ncls = u_hi - u_lo;
+    if (null_kind == EC3D_NULL_PRECOND_BLOCK_MG) { // level 0 of the transposed A block: gathered once, read as band streams
+        if (h.bands0.alloc((size_t)7 * nCd) != hipSuccess) return mg_fail(MG_OOM);
+        k_avmg_gather_t<<<blocks_of(nCd), 256, 0, c->stream>>>(A0, h.bands0, nCd);
+        A0.cls = nullptr;
+        A0.bands = h.bands0;
+        A0.n_pad = nCd;
+    }
     int64_t coarse_len = 0;
     for (int l = 1; l < L; ++l) {
         AvLevel &P = h.lev[(size_t)l - 1], &Q = h.lev[(size_t)l];
@@ -1468,29 +1564,50 @@ template <class T> static int set_poisson_mg(ec3d_ctx *c, ec3d_mg &m)
 // algorithm (below), with M the block multigrid, v = A p^ and t = A s^ by the format's own SpMV (ec3d_launch_spmv), then
 // their dot partials (k_avmg_dot: the summation order of k_mg_spmv_dot).  The SpMV launches are not gated: past an exit
 // nothing reads what they write.
+// The vectors, the operator (op(x, y) enqueues y = Op x) and the cycle (cycle(g, r, z) enqueues z = M r) are parameters:
+// the solve runs it in the handle's work vectors with A and M, the null projection's set-up in a PlainKrylov's with A^T
+// and N (ec3d_null_mg_iteration).
+struct OuterVecs {
+    int64_t n;
+    double *x, *r, *r0, *p, *v, *s, *t; // v = Op p^, t = Op s^
+    double *ph, *sh;
+    double *part;
+    MgScalars *scal;
+    double *hist;
+    int64_t hist_cap;
+};
+template <class Cycle, class Op>
+static void launch_block_iteration(ec3d_ctx *c, int it, const OuterVecs &k, const Cycle &cycle, const Op &op)
+{
+    hipStream_t s = c->stream;
+    const int64_t n = k.n;
+    const unsigned nb = dot_blocks(n);
+    const Gate g0{c->state, it, 0}, g1{c->state, it, 1};
+    cycle(g0, k.p, k.ph);
+    op(k.ph, k.v);
+    k_avmg_dot<<<nb, 256, 0, s>>>(n, g0, k.r0, k.v, 0, k.part);
+    k_mg_scalar<<<1, 256, 0, s>>>(MG_ALPHA, g0, c->state, k.scal, k.part, (int)nb, k.hist, k.hist_cap);
+    k_mg_s<<<nb, 256, 0, s>>>(n, g0, c->state, k.r, k.v, k.s, k.part);
+    k_mg_scalar<<<1, 256, 0, s>>>(MG_SEXIT, g0, c->state, k.scal, k.part, (int)nb, k.hist, k.hist_cap);
+    cycle(g1, k.s, k.sh);
+    op(k.sh, k.t);
+    k_avmg_dot<<<nb, 256, 0, s>>>(n, g1, k.s, k.t, 1, k.part);
+    k_mg_scalar<<<1, 256, 0, s>>>(MG_OMEGA, g1, c->state, k.scal, k.part, (int)nb, k.hist, k.hist_cap);
+    k_mg_xr<<<nb, 256, 0, s>>>(n, it, c->state, k.x, (const double *)k.ph, (const double *)k.sh, k.s, k.t, k.r0, k.r, k.part);
+    k_mg_scalar<<<1, 256, 0, s>>>(MG_REXIT, g1, c->state, k.scal, k.part, (int)nb, k.hist, k.hist_cap);
+    k_mg_p<<<nb, 256, 0, s>>>(n, g1, c->state, k.scal, k.r, k.v, k.p, k.r0);
+}
+
 static void launch_iteration_of(ec3d_ctx *c, int it, const BlockMg &h)
 {
     const ec3d_mg *m = c->mg;
     double **v = c->vec;
     hipStream_t s = c->stream;
     const MatView V = c->A.view();
-    const int64_t n = c->A.n;
-    const unsigned nb = dot_blocks(n);
-    const Gate g0{c->state, it, 0}, g1{c->state, it, 1};
-    launch_cycle(*m, h, g0, v[EC3D_VEC_P], h.ph, s);
-    ec3d_launch_spmv(V, c->sweep_s, h.ph, v[EC3D_VEC_AP], s);
-    k_avmg_dot<<<nb, 256, 0, s>>>(n, g0, v[EC3D_VEC_R0], v[EC3D_VEC_AP], 0, m->part);
-    k_mg_scalar<<<1, 256, 0, s>>>(MG_ALPHA, g0, c->state, m->scal, m->part, (int)nb, c->hist, c->hist_cap);
-    k_mg_s<<<nb, 256, 0, s>>>(n, g0, c->state, v[EC3D_VEC_R], v[EC3D_VEC_AP], v[EC3D_VEC_S], m->part);
-    k_mg_scalar<<<1, 256, 0, s>>>(MG_SEXIT, g0, c->state, m->scal, m->part, (int)nb, c->hist, c->hist_cap);
-    launch_cycle(*m, h, g1, v[EC3D_VEC_S], h.sh, s);
-    ec3d_launch_spmv(V, c->sweep_s, h.sh, v[EC3D_VEC_AS], s);
-    k_avmg_dot<<<nb, 256, 0, s>>>(n, g1, v[EC3D_VEC_S], v[EC3D_VEC_AS], 1, m->part);
-    k_mg_scalar<<<1, 256, 0, s>>>(MG_OMEGA, g1, c->state, m->scal, m->part, (int)nb, c->hist, c->hist_cap);
-    k_mg_xr<<<nb, 256, 0, s>>>(n, it, c->state, v[EC3D_VEC_X], h.ph, h.sh, v[EC3D_VEC_S], v[EC3D_VEC_AS],
-                               v[EC3D_VEC_R0], v[EC3D_VEC_R], m->part);
-    k_mg_scalar<<<1, 256, 0, s>>>(MG_REXIT, g1, c->state, m->scal, m->part, (int)nb, c->hist, c->hist_cap);
-    k_mg_p<<<nb, 256, 0, s>>>(n, g1, c->state, m->scal, v[EC3D_VEC_R], v[EC3D_VEC_AP], v[EC3D_VEC_P], v[EC3D_VEC_R0]);
+    const OuterVecs k{c->A.n, v[EC3D_VEC_X], v[EC3D_VEC_R], v[EC3D_VEC_R0], v[EC3D_VEC_P], v[EC3D_VEC_AP], v[EC3D_VEC_S],
+                      v[EC3D_VEC_AS], h.ph, h.sh, m->part, m->scal, c->hist, c->hist_cap};
+    launch_block_iteration(c, it, k, [&](Gate g, const double *r, double *z) { launch_cycle(*m, h, g, r, z, s); },
+                           [&](const double *x, double *y) { ec3d_launch_spmv(V, c->sweep_s, x, y, s); });
 }
 
 // The same iteration with M = I (p^ = p, s^ = s) around an operator the caller launches: ec3d_plain_iteration of
@@ -1530,6 +1647,50 @@ void ec3d_plain_stage(ec3d_ctx *c, const PlainKrylov &k, int it, int stage)
     k_mg_xr<<<nb, 256, 0, s>>>(n, it, c->state, k.x, (const double *)k.p, (const double *)k.s, k.s, k.t, k.r0, k.r, k.part);
     k_mg_scalar<<<1, 256, 0, s>>>(MG_REXIT, g1, c->state, k.scal, k.part, (int)nb, nullptr, 0);
     k_mg_p<<<nb, 256, 0, s>>>(n, g1, c->state, k.scal, k.r, k.v, k.p, k.r0);
+}
+
+// ---- N, the preconditioner of the null projection's adjoint solves (ec3d_set_null_precond) -------
+// A hierarchy of its own, built inside the null set-up (or for one ec3d_null_precond_apply) and released by the caller
+// before it returns: c->mg, the caller's preconditioner, is neither read nor written.
+int ec3d_null_mg_build(ec3d_ctx *c, int kind, int pre, int post, int coarse, ec3d_mg **out)
+{
+    *out = nullptr;
+    std::unique_ptr<ec3d_mg> m(new ec3d_mg);
+    m->kind = EC3D_PRECOND_BLOCK_MG;
+    m->coarsening = EC3D_COARSEN_AGGREGATE;
+    m->pre = pre ? pre : 2;
+    m->post = post ? post : 2;
+    m->coarse = coarse ? coarse : 16;
+    const int rc = set_block_mg(c, *m, kind);
+    if (rc == EC3D_PRECOND_E_MATRIX) // the block hierarchy's refusal, under the name of the setting that asked for it
+        ec3d_set_error(std::string("ec3d_set_null_precond: the block hierarchy refuses this matrix -- ") + ec3d_last_error());
+    if (rc) return rc;
+    *out = m.release();
+    return 0;
+}
+
+void ec3d_null_mg_delete(ec3d_mg *m) { delete m; }
+
+void ec3d_null_mg_dims(const ec3d_mg *m, int32_t *levels, int32_t *dims)
+{
+    const BlockMg &h = std::get<BlockMg>(m->h);
+    const size_t L = std::min<size_t>(h.lev.size(), EC3D_NULL_PRECOND_MAX_LEVELS);
+    *levels = (int32_t)L;
+    for (size_t l = 0; l < L; ++l) {
+        dims[3 * l] = h.lev[l].op.sdx;
+        dims[3 * l + 1] = h.lev[l].op.sdy;
+        dims[3 * l + 2] = h.lev[l].op.sdz;
+    }
+}
+
+void ec3d_null_mg_iteration(ec3d_ctx *c, const ec3d_mg *m, const PlainKrylov &k, int it)
+{
+    const BlockMg &h = std::get<BlockMg>(m->h);
+    hipStream_t s = c->stream;
+    const MatView V = c->A.view();
+    const OuterVecs o{k.n, k.x, k.r, k.r0, k.p, k.v, k.s, k.t, h.ph, h.sh, k.part, k.scal, nullptr, 0};
+    launch_block_iteration(c, it, o, [&](Gate g, const double *r, double *z) { launch_cycle(*m, h, g, r, z, s); },
+                           [&](const double *x, double *y) { ec3d_launch_spmv_t(V, k.n, x, y, s); });
 }
 
 void ec3d_mg_free(ec3d_ctx *c)
@@ -1713,6 +1874,27 @@ extern "C" int ec3d_precond_apply(ec3d_handle c, const double *r, double *z)
         return precond_apply_through(c, h->ph, h->sh, r, z, [&] { launch_cycle(m, *h, g, h->ph, h->sh, s); });
     const BlockMg &h = std::get<BlockMg>(m.h);
     return precond_apply_through(c, h.ph, h.sh, r, z, [&] { launch_cycle(m, h, g, h.ph, h.sh, s); });
+}
+
+extern "C" int ec3d_null_precond_apply(ec3d_handle c, const double *r, double *z)
+{
+    int rc = ec3d_need_matrix(c, "ec3d_null_precond_apply");
+    if (rc) return rc;
+    if ((rc = ec3d_null_eligible(c, "ec3d_null_precond_apply", true))) return rc;
+    const NullProjection &N = c->nullp;
+    if (N.precond == EC3D_NULL_PRECOND_NONE || !r || !z) {
+        ec3d_set_error("ec3d_null_precond_apply: no preconditioner of the adjoint solve set (ec3d_set_null_precond), or a "
+                       "null vector");
+        return N.precond == EC3D_NULL_PRECOND_NONE ? 3 : 2;
+    }
+    EC3D_HIP(hipSetDevice(c->device));
+    EC3D_HIP(hipStreamSynchronize(c->stream));
+    ec3d_mg *built = nullptr;
+    if ((rc = ec3d_null_mg_build(c, N.precond, N.pre, N.post, N.coarse, &built))) return rc;
+    const std::unique_ptr<ec3d_mg> m(built); // N lives for this call only
+    const BlockMg &h = std::get<BlockMg>(m->h);
+    hipStream_t s = c->stream;
+    return precond_apply_through(c, h.ph, h.sh, r, z, [&] { launch_cycle(*m, h, Gate{nullptr, 0, 0}, h.ph, h.sh, s); });
 }
 
 // iterations per poll of solve_core: about 1 ms of device work.  Poisson: a V-cycle is ~210 B per fine row, two per

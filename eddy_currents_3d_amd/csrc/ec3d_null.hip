@@ -4,7 +4,8 @@
 // Set-up, once per matrix (ec3d_null_prepare): the connected components of the conducting cells on the host; per
 // component the adjoint solve A^T y = -A^T e_m from y = 0 -- the outer iteration of ec3d_mg.hip with M = I
 // (ec3d_plain_iteration) around ec3d_launch_spmv_t, in the work vectors R, R0, P, AP, S, AS, which are free between two
-// solves (X and B are the caller's and stay) -- then w = y + e_m, its residual, and classical Gram-Schmidt against the
+// solves (X and B are the caller's and stay), or with ec3d_set_null_precond the right-preconditioned one around N, a
+// block hierarchy this set-up builds and releases (ec3d_null_mg_*, section 16a) -- then w = y + e_m, its residual, and classical Gram-Schmidt against the
 // vectors kept so far.  In front of a solve (ec3d_null_project): c_i = Q_i.R, R = R - c_1 Q_1 - ... - c_k Q_k, R0 = R,
 // P = R, and the partials of R.R where the solve's set-up kernel looks for them.
 //
@@ -187,6 +188,21 @@ int build(ec3d_ctx *c)
     const int64_t cap = (int64_t)(20.0 * std::cbrt((double)c->n_ref)) + 2000;
     const int64_t total = cap + 1; // src/solvers.f90:25-29: itmax + 1 iterations
     const auto apply = [&](const double *x, double *y) { ec3d_launch_spmv_t(A, n, x, y, c->stream); };
+    // N of ec3d_set_null_precond: a hierarchy of this set-up's own, gone when build returns
+    struct OwnedMg {
+        ec3d_mg *m = nullptr;
+        ~OwnedMg() { ec3d_null_mg_delete(m); }
+    } nmg;
+    if (N.precond != EC3D_NULL_PRECOND_NONE) {
+        const auto t_h = std::chrono::steady_clock::now();
+        const int rc = ec3d_null_mg_build(c, N.precond, N.pre, N.post, N.coarse, &nmg.m);
+        if (rc) {
+            ec3d_null_free(c);
+            return rc;
+        }
+        ec3d_null_mg_dims(nmg.m, &N.levels, N.dims);
+        N.hierarchy_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_h).count();
+    }
     std::vector<double> h((size_t)ncomp + 2);
     int kept = 0;
     for (int ci = 0; ci < ncomp; ++ci) {
@@ -210,7 +226,10 @@ int build(ec3d_ctx *c)
         bool stopped = false;
         while (launched < total && !stopped) {
             const int64_t m = std::min<int64_t>(16, total - launched);
-            for (int64_t i = 0; i < m; ++i) ec3d_plain_iteration(c, K, (int)(++launched), apply);
+            for (int64_t i = 0; i < m; ++i) {
+                if (nmg.m) ec3d_null_mg_iteration(c, nmg.m, K, (int)(++launched));
+                else ec3d_plain_iteration(c, K, (int)(++launched), apply);
+            }
             EC3D_HIP(hipGetLastError());
             EC3D_HIP(hipMemcpyAsync(&st, c->state, sizeof st, hipMemcpyDeviceToHost, c->stream));
             EC3D_HIP(hipStreamSynchronize(c->stream));
@@ -222,6 +241,7 @@ int build(ec3d_ctx *c)
                      "null_tol = %.3g within %lld iterations (||r|| / ||A^T e_m|| = %.3g); its left null vector is not used",
                      ci, (long long)seed_ref, null_tol, (long long)cap, st.bnorm > 0.0 ? st.rnorm / st.bnorm : 0.0);
             ec3d_null_free(c);
+            EC3D_HIP(hipStreamSynchronize(c->stream)); // (N goes with this return: nothing of it may still run)
             if ((rc = scrub(c))) return rc;
             ec3d_set_error(msg);
             return EC3D_NULL_E_SETUP;
@@ -281,6 +301,8 @@ void ec3d_null_free(ec3d_ctx *c)
     N.len = 0;
     N.wgs = 0;
     N.last = ec3d_null_info{};
+    N.levels = 0;
+    N.hierarchy_ms = 0.0;
 }
 
 int ec3d_null_eligible(const ec3d_ctx *c, const char *who, bool set_text)
@@ -362,6 +384,46 @@ extern "C" int ec3d_set_null_projection(ec3d_handle c, int32_t on, double null_t
     }
     c->nullp.on = 1;
     c->nullp.null_tol = tol;
+    return 0;
+}
+
+extern "C" int ec3d_set_null_precond(ec3d_handle c, int32_t kind, int32_t pre, int32_t post, int32_t coarse_sweeps)
+{
+    if (!c || kind < EC3D_NULL_PRECOND_NONE || kind > EC3D_NULL_PRECOND_BLOCK_MG_A || pre < 0 || post < 0 || coarse_sweeps < 0) {
+        ec3d_set_error(!c ? "ec3d_set_null_precond: null handle"
+                          : "ec3d_set_null_precond: unknown kind or negative sweep count");
+        return 2;
+    }
+    int rc = ec3d_null_eligible(c, "ec3d_set_null_precond", true);
+    if (rc) return rc;
+    NullProjection &N = c->nullp;
+    if (kind == N.precond && pre == N.pre && post == N.post && coarse_sweeps == N.coarse) return 0;
+    EC3D_HIP(hipSetDevice(c->device));
+    EC3D_HIP(hipStreamSynchronize(c->stream));
+    if (kind != EC3D_NULL_PRECOND_NONE && c->have_matrix) { // what the block hierarchy refuses is known now: build it once
+        ec3d_mg *m = nullptr;
+        if ((rc = ec3d_null_mg_build(c, kind, pre, post, coarse_sweeps, &m))) return rc;
+        ec3d_null_mg_delete(m);
+    }
+    if (N.built) ec3d_null_free(c); // another set-up: the vectors are made again
+    N.precond = kind;
+    N.pre = pre;
+    N.post = post;
+    N.coarse = coarse_sweeps;
+    return 0;
+}
+
+extern "C" int ec3d_get_null_precond(ec3d_handle c, int32_t *kind, int32_t *levels, int32_t *dims, double *hierarchy_ms)
+{
+    if (!c) {
+        ec3d_set_error("ec3d_get_null_precond: null handle");
+        return 2;
+    }
+    const NullProjection &N = c->nullp;
+    if (kind) *kind = N.precond;
+    if (levels) *levels = N.levels;
+    for (int q = 0; dims && q < 3 * N.levels; ++q) dims[q] = N.dims[q];
+    if (hierarchy_ms) *hierarchy_ms = N.hierarchy_ms;
     return 0;
 }
 

@@ -341,7 +341,7 @@ def run(model: vxc.VxcModel, solver, steps: int | None = None, out_dir: str | No
         on_rhs=None, on_solved=None, write_output=None, overlap_output: bool = True, on_fields=None, on_written=None,
         precond: str | None = None, u_rhs: str | None = None, integrals: bool = False, guess_history: int | None = None,
         energy: bool = False, null_projection: bool | None = None, tol: float | None = None,
-        null_tol: float | None = None):
+        null_tol: float | None = None, null_precond: str | None = None):
     """The reference's run of ``model`` on ``solver`` (an EC3DSolver): assemble, then step until T >= stop (or
     ``steps`` steps).  Returns a list of per-step dicts (T, iter).  ``out_dir``: write ``field_N.vtk`` there at
     the reference's output cadence.  Hooks, all ``(k, solver, info)``: ``on_rhs`` when Jaf (B) of step k is
@@ -372,7 +372,9 @@ def run(model: vxc.VxcModel, solver, steps: int | None = None, out_dir: str | No
     ``null_projection``: solver.set_null_projection(flag) after the assembly -- the left null vectors of the A-V system
     leave every step's initial residual, so tolerances below the reference's can be reached; ``info["null"]`` of every
     step then holds solver.null_projection().  None leaves the handle's setting as it is; one handle only (an EC3DMulti
-    raises ValueError); ``null_tol``: the accuracy of the adjoint solves instead of 1e-10.  ``tol``: the solves' tolerance
+    raises ValueError); ``null_tol``: the accuracy of the adjoint solves instead of 1e-10;
+    ``null_precond`` ("none", "block-mg", "block-mg-a"): their preconditioner (set_null_projection's ``precond``; None
+    leaves the handle's setting as it is).  ``tol``: the solves' tolerance
     instead of the model's."""
     if null_projection is not None and not hasattr(solver, "set_null_projection"):
         raise ValueError("null_projection needs an EC3DSolver: the left null vectors are not available on the z-slabs of "
@@ -397,7 +399,8 @@ def run(model: vxc.VxcModel, solver, steps: int | None = None, out_dir: str | No
     if precond is not None:
         solver.set_preconditioner(precond)
     if null_projection is not None:
-        solver.set_null_projection(bool(null_projection), **({} if null_tol is None else {"null_tol": float(null_tol)}))
+        solver.set_null_projection(bool(null_projection), **({} if null_tol is None else {"null_tol": float(null_tol)}),
+                                   **({} if null_precond is None else {"precond": null_precond}))
     if tol is not None:
         t = dict(t, tol=float(tol))
     n = solver.n

@@ -77,6 +77,10 @@ def build_parser():
     ap.add_argument("--null-tol", type=float, default=None, metavar="Y",
                     help="accuracy the adjoint solves of --null-projection are run to (default 1e-10); a solve fails when "
                          "one of them does not get there within its cap")
+    ap.add_argument("--null-precond", choices=("none", "block-mg", "block-mg-a"), default=None,
+                    help="preconditioner of the adjoint solves of --null-projection: the transposed block multigrid "
+                         "(block-mg), the same with the A blocks' hierarchy of A as it stands (block-mg-a), or none "
+                         "(default: the handle's setting, which starts as none)")
     ap.add_argument("--tol", type=float, default=None, metavar="X",
                     help="tolerance of the time step's solve instead of the model's (one GPU only)")
     return ap
@@ -150,10 +154,13 @@ def main(argv=None):
                                precond=None if a.precond == "none" else a.precond, u_rhs=a.u_rhs,
                                integrals=csv is not None, guess_history=a.guess_history or None,
                                energy=ecsv is not None, null_projection=True if a.null_projection else None,
-                               tol=a.tol, null_tol=a.null_tol)
+                               tol=a.tol, null_tol=a.null_tol,
+                               null_precond=a.null_precond if a.null_projection else None)
                 if a.null_projection:
                     q = s.null_projection()
-                    print(f"null projection: {q['kept']} of {q['found']} components kept, set-up {q['setup_ms']:.1f} ms, "
+                    kind, levels, hms = s.null_precond()
+                    print(f"null projection: {q['kept']} of {q['found']} components kept, set-up {q['setup_ms']:.1f} ms "
+                          f"(preconditioner {kind}, {len(levels)} levels, {hms:.1f} ms), "
                           + ", ".join(f"{c['iterations']} it / {c['residual']:.2e}" for c in q["components"]), flush=True)
                 n = s.n
         finally:

@@ -105,10 +105,13 @@ EXPORTS = ["sprsbcgstabwr_", "ec3d_invalidate", "ec3d_create", "ec3d_destroy", "
            "ec3d_set_precond_precision", "ec3d_get_precond_precision", "ec3d_set_precond_coarsening",
            "ec3d_get_precond_coarsening", "ec3d_set_precond_grid", "ec3d_get_precond_grid",
            "ec3d_domain_integrals", "ec3d_field_energy", "ec3d_domain_linkage", "ec3d_get_class_runs", "ec3d_get_patch_rows", "ec3d_get_k51_ap_form", "ec3d_set_guess_history", "ec3d_get_guess_history",
-           "ec3d_spmv_t", "ec3d_set_null_projection", "ec3d_get_null_projection", "ec3d_left_null_vector"]
+           "ec3d_spmv_t", "ec3d_set_null_projection", "ec3d_get_null_projection", "ec3d_left_null_vector",
+           "ec3d_set_null_precond", "ec3d_get_null_precond", "ec3d_null_precond_apply"]
 U_RHS = {"reference": 0, "all": 1}   # EC3D_U_RHS_* of include/ec3d_hip.h
 PRECOND = {"none": 0, "mg": 1, "block-mg": 2}   # EC3D_PRECOND_* of include/ec3d_hip.h
 PRECOND_E_MATRIX, PRECOND_E_COARSE = 20, 21   # ec3d_set_preconditioner's refusals
+NULL_PRECOND = {"none": 0, "block-mg": 1, "block-mg-a": 2}   # EC3D_NULL_PRECOND_* of include/ec3d_hip.h
+NULL_PRECOND_MAX_LEVELS = 16
 NULL_E_MATRIX, NULL_E_SETUP = 22, 23   # ec3d_set_null_projection's refusal, a set-up that did not reach null_tol
 PRECOND_PRECISION = {"fp64": 0, "fp32": 1}   # EC3D_PRECOND_FP64 / _FP32 of include/ec3d_hip.h
 PRECOND_COARSENING = {"rediscretize": 0, "aggregate": 1}   # EC3D_COARSEN_REDISCRETIZE / _AGGREGATE
@@ -208,6 +211,9 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.ec3d_set_null_projection.argtypes = [hp, C.c_int32, C.c_double]
     L.ec3d_get_null_projection.argtypes = [hp, C.POINTER(NullInfo)]
     L.ec3d_left_null_vector.argtypes = [hp, C.c_int32, _f64]
+    L.ec3d_set_null_precond.argtypes = [hp, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    L.ec3d_get_null_precond.argtypes = [hp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_double)]
+    L.ec3d_null_precond_apply.argtypes = [hp, _f64, _f64]
     L.ec3d_export_csr.argtypes = [hp, C.POINTER(C.c_int32), C.POINTER(C.c_int64), hp, hp, hp]
     L.ec3d_get_cel_bnd.argtypes = [hp, C.c_int, C.POINTER(C.c_int32), hp]
     L.ec3d_get_reduction_geometry.argtypes = [hp, C.c_int, C.POINTER(Geom)]
@@ -759,13 +765,21 @@ class EC3DSolver:
                     res_before=float(g.res_before), res_after=float(g.res_after),
                     coef=np.array(g.coef[:max(int(g.used), 0)], dtype=np.float64))
 
-    def set_null_projection(self, on: bool = True, null_tol: float = 1e-10):
+    def set_null_projection(self, on: bool = True, null_tol: float = 1e-10, precond: str | None = None, pre: int = 0,
+                            post: int = 0, coarse_sweeps: int = 0):
         """Take the left null vectors of the A-V system out of every solve's initial residual, so that tolerances
         below |w.b| / ||w|| ||b|| can be reached (ec3d_set_null_projection of include/ec3d_hip.h).  The first solve on
         a matrix finds one vector per connected conducting component by an adjoint solve to ``null_tol``.  The setting
         stays with the handle, the vectors with the matrix.  EC3DError with .status NULL_E_MATRIX on a Poisson, CSR or
         bands + tail matrix, 4 on a z-slab; the setting is then off.  A solve whose set-up misses ``null_tol`` raises
-        with .status NULL_E_SETUP."""
+        with .status NULL_E_SETUP.  ``precond`` ("none", "block-mg" or "block-mg-a"; None leaves the setting as it is):
+        the preconditioner of the adjoint solves (ec3d_set_null_precond) -- the transposed block multigrid, or with
+        "block-mg-a" the A blocks' hierarchy of A as it stands --, with ``pre`` / ``post`` / ``coarse_sweeps`` sweeps
+        (0: the defaults of set_preconditioner).  EC3DError with .status PRECOND_E_MATRIX when the block hierarchy
+        refuses the matrix; the setting then stays as it was."""
+        if precond is not None:
+            _chk(self.L, self.L.ec3d_set_null_precond(self.h, NULL_PRECOND[precond], int(pre), int(post), int(coarse_sweeps)),
+                 "ec3d_set_null_precond")
         _chk(self.L, self.L.ec3d_set_null_projection(self.h, 1 if on else 0, float(null_tol)), "ec3d_set_null_projection")
 
     def null_projection(self):
@@ -779,6 +793,23 @@ class EC3DSolver:
                       kept=bool(g.was_kept[i])) for i in range(int(g.reported))]
         return dict(on=bool(g.on), built=bool(g.built), found=int(g.found), kept=int(g.kept), dropped=int(g.dropped),
                     null_tol=float(g.null_tol), removed=float(g.removed), setup_ms=float(g.setup_ms), components=comps)
+
+    def null_precond(self):
+        """(kind, [(sdx, sdy, sdz) per level, finest first], hierarchy_ms): the preconditioner of the adjoint solves that
+        is set, and the hierarchy the last set-up built (no level when none was built) with the time spent building it."""
+        kind, levels, ms = C.c_int32(0), C.c_int32(0), C.c_double(0.0)
+        dims = np.zeros(3 * NULL_PRECOND_MAX_LEVELS, np.int32)
+        _chk(self.L, self.L.ec3d_get_null_precond(self.h, C.byref(kind), C.byref(levels), dims.ctypes.data, C.byref(ms)),
+             "ec3d_get_null_precond")
+        name = {v: k for k, v in NULL_PRECOND.items()}[kind.value]
+        return name, [tuple(int(a) for a in dims[3 * l:3 * l + 3]) for l in range(levels.value)], float(ms.value)
+
+    def null_precond_apply(self, r):
+        """z = N r on host vectors (the reference's numbering), N the preconditioner of the adjoint solves that is set;
+        N is built for the call and released."""
+        z = np.empty(self.n)
+        _chk(self.L, self.L.ec3d_null_precond_apply(self.h, np.ascontiguousarray(r, np.float64), z), "ec3d_null_precond_apply")
+        return z
 
     def left_null_vector(self, index: int = 0):
         """Kept left null vector ``index`` (unit norm, the reference's numbering); builds the vectors when the

@@ -437,6 +437,31 @@ typedef struct {
 } ec3d_null_info;
 int ec3d_get_null_projection(ec3d_handle h, ec3d_null_info *info);
 int ec3d_left_null_vector(ec3d_handle h, int32_t index, double *w_host);
+/* A preconditioner N ~ (A^T)^-1 for the adjoint solves of that set-up (opt-in): the block
+ * multigrid of EC3D_PRECOND_BLOCK_MG, transposed.  N is block diagonal over [Ax | Ay | Az | U].  A blocks: the
+ * hierarchy and V-cycle of EC3D_PRECOND_BLOCK_MG on the transposed block (EC3D_NULL_PRECOND_BLOCK_MG: level 0 is the
+ * transposed block, gathered once into seven band streams; coarse levels its Galerkin products) or on the block of A as
+ * it stands (EC3D_NULL_PRECOND_BLOCK_MG_A).  U block, both kinds: the plain mean of every conducting component leaves
+ * the right-hand side, pre + post red-black sweeps from zero run on U^T, and the plain mean leaves the result.  The
+ * adjoint iteration is then the right-preconditioned BiCGSTAB of ec3d_set_preconditioner around ec3d_spmv_t's kernel:
+ * the residual tested is the true one, so null_tol, the cap, EC3D_NULL_E_SETUP and ec3d_null_info mean what they meant.
+ * The hierarchy is built inside the set-up and released before it returns; the handle's own preconditioner is not
+ * touched.  pre / post / coarse_sweeps = 0: the defaults of ec3d_set_preconditioner.  The setting stays with the
+ * handle across matrices; changing it clears vectors already built.  Status: as ec3d_set_null_projection
+ * (EC3D_NULL_E_MATRIX, 4); an unknown kind or a negative count 2; with a matrix on the handle, what the block
+ * hierarchy refuses (A blocks that differ, more than 4 conducting domains) EC3D_PRECOND_E_MATRIX, the setting as it
+ * was.  EC3D_NULL_PRECOND_NONE (default): the set-up launches what it launched before and returns the same bits.
+ * ec3d_get_null_precond: the kind set; levels and dims (3 per level, at most EC3D_NULL_PRECOND_MAX_LEVELS levels) of
+ * the hierarchy the last set-up built (0 levels when none was built) and the wall time spent building it.
+ * ec3d_null_precond_apply: z = N r on host vectors in the reference's numbering; builds N for the call and releases
+ * it (status 3 when the kind is EC3D_NULL_PRECOND_NONE). */
+#define EC3D_NULL_PRECOND_NONE 0
+#define EC3D_NULL_PRECOND_BLOCK_MG 1
+#define EC3D_NULL_PRECOND_BLOCK_MG_A 2
+#define EC3D_NULL_PRECOND_MAX_LEVELS 16
+int ec3d_set_null_precond(ec3d_handle h, int32_t kind, int32_t pre, int32_t post, int32_t coarse_sweeps);
+int ec3d_get_null_precond(ec3d_handle h, int32_t *kind, int32_t *levels, int32_t *dims, double *hierarchy_ms);
+int ec3d_null_precond_apply(ec3d_handle h, const double *r, double *z);
 
 /* ------------------------------------------------------------------------------------------
  * 2b. Multi-rank building blocks (z-slab decomposition, one process per GPU).

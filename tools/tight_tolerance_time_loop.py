@@ -3,9 +3,10 @@
 
     python tools/tight_tolerance_time_loop.py [--cases LIM ec_src_move_hole] [--tols model 1e-6 1e-8] [--modes off on]
                                               [--steps N] [--runs R] [--itmax M] [--null-tol Y] [--precond block-mg]
-                                              [--label TEXT]
+                                              [--null-precond none|block-mg|block-mg-a] [--label TEXT]
                                               [--out profiles/null_projection.jsonl]
     python tools/tight_tolerance_time_loop.py --config3 [--label TEXT]
+    python tools/tight_tolerance_time_loop.py --setup-only [--cases ..] [--null-tol Y ..] [--null-precond KIND ..]
 
 One JSON line per case, tolerance, mode and run, appended to --out and printed: iterations of every step, the wall time
 of the loop (host.run without output, the assembly and -- with the projection -- its set-up included) and of the solves
@@ -18,6 +19,12 @@ iterations (default: the model's): without the projection a tolerance below the 
 --precond block-mg: the preconditioned iteration around the same projection.
 Mode off never calls ec3d_set_null_projection, so the tool also runs on a build that has no such call (EC3D_LIB names
 its library, --label the build): that is how the default loop is compared with the parent commit.
+
+--null-precond: the preconditioner of the adjoint solves (ec3d_set_null_precond); the set-up record then also holds its
+kind, the hierarchy's levels and hierarchy_ms.  A set-up that misses null_tol (EC3D_NULL_E_SETUP) is recorded as
+setup_failed with the library's text, not raised.
+--setup-only: no time loop -- per case, null_tol and preconditioner one line with the assembly, the set-up (adjoint
+iterations per component, whether null_tol was reached, ||A^T w|| / ||w||, setup_ms, hierarchy_ms) and nothing else.
 
 --config3: one solve of BASELINE config 3 at 256^3 (tests/test_gpu_av256.py's model) at tol 5e-4, projection off and
 on, each compared with the reference's converged step in tests/golden/g7x_*: the fixture holds a count-sketch and probes
@@ -58,7 +65,35 @@ def projected_residual(s, W):
     return float(np.linalg.norm(r) / np.linalg.norm(b))
 
 
-def one_run(E, host, model, tol, itmax, on, steps, null_tol=None, precond=None):
+def setup_record(s, setup):
+    kind, levels, hms = s.null_precond() if hasattr(s, "null_precond") else ("none", [], 0.0)
+    return dict(found=setup["found"], kept=setup["kept"], dropped=setup["dropped"], ms=round(setup["setup_ms"], 3),
+                null_tol=setup["null_tol"], components=setup["components"], null_precond=kind, levels=len(levels),
+                hierarchy_ms=round(hms, 3))
+
+
+def setup_only(E, model, null_tol, null_precond):
+    """Assembly and the null set-up alone: what the adjoint solves cost and whether they reach null_tol."""
+    from eddy_currents_3d_amd import vxc
+    t = vxc.domain_tables(model)
+    with E.EC3DSolver() as s:
+        s.assemble(t["geoPHYS"], t["geoPHYS_C"], t["valPHYS"], t["BND"], t["delta"], t["dt"])
+        s.set_null_projection(True, **({} if null_tol is None else {"null_tol": null_tol}),
+                              **({} if null_precond is None else {"precond": null_precond}))
+        t0 = time.perf_counter()
+        try:
+            s.left_null_vector(0)
+        except E.EC3DError as e:
+            if getattr(e, "status", None) != E.solver.NULL_E_SETUP:
+                raise
+            kind, levels, hms = s.null_precond()
+            return dict(n=int(s.n), reached=False, setup_failed=str(e), wall_s=round(time.perf_counter() - t0, 4),
+                        null_precond=kind)
+        return dict(n=int(s.n), reached=True, wall_s=round(time.perf_counter() - t0, 4),
+                    setup=setup_record(s, s.null_projection()))
+
+
+def one_run(E, host, model, tol, itmax, on, steps, null_tol=None, precond=None, null_precond=None):
     res, pres, removed, solve_s, W = [], [], [], [0.0], []
     with E.EC3DSolver() as s:
         inner = s.solve_resident
@@ -81,11 +116,18 @@ def one_run(E, host, model, tol, itmax, on, steps, null_tol=None, precond=None):
         extra = dict(null_projection=True, tol=tol, null_tol=null_tol) if on else dict(tol=tol) if tol is not None else {}
         if precond:
             extra["precond"] = precond
-        log = host.run(model, s, steps=steps, on_solved=on_solved, **extra)
+        if on and null_precond:
+            extra["null_precond"] = null_precond
+        try:
+            log = host.run(model, s, steps=steps, on_solved=on_solved, **extra)
+        except E.EC3DError as e:
+            if getattr(e, "status", None) != E.solver.NULL_E_SETUP:
+                raise
+            return dict(n=int(s.n), setup_failed=str(e), wall_s=round(time.perf_counter() - t0, 4))
         s.synchronize()
         wall = time.perf_counter() - t0
         n = int(s.n)
-        setup = s.null_projection() if on else None
+        setup_rec = setup_record(s, s.null_projection()) if on else None
     out = dict(n=n, steps=len(log), iters=[int(i["iter"]) for i in log], wall_s=round(wall, 4), solve_s=round(solve_s[0], 4),
                true_residual_max=max(res), true_residual=[float(f"{r:.4e}") for r in res])
     out["iters_total"] = sum(out["iters"])
@@ -93,8 +135,7 @@ def one_run(E, host, model, tol, itmax, on, steps, null_tol=None, precond=None):
         out["projected_residual_max"] = max(pres)
         out["projected_residual"] = [float(f"{r:.4e}") for r in pres]
         out["removed"] = [float(f"{r:.4e}") for r in removed]
-        out["setup"] = dict(found=setup["found"], kept=setup["kept"], dropped=setup["dropped"], ms=round(setup["setup_ms"], 3),
-                            null_tol=setup["null_tol"], components=setup["components"])
+        out["setup"] = setup_rec
         out["wall_s_note"] = "includes the host-side projected residual of every step"
     return out
 
@@ -145,7 +186,11 @@ def main():
     ap.add_argument("--modes", nargs="+", default=["off", "on"], choices=["off", "on"])
     ap.add_argument("--steps", type=int, default=None, help="instead of the case's own count")
     ap.add_argument("--itmax", type=int, default=None, help="cap of a solve's iterations instead of the model's")
-    ap.add_argument("--null-tol", type=float, default=None, help="accuracy of the adjoint solves instead of 1e-10")
+    ap.add_argument("--null-tol", type=float, nargs="+", default=[None],
+                    help="accuracy of the adjoint solves instead of 1e-10 (--setup-only: one line per value)")
+    ap.add_argument("--null-precond", nargs="+", default=[None], choices=["none", "block-mg", "block-mg-a"],
+                    help="preconditioner of the adjoint solves (--setup-only: one line per value)")
+    ap.add_argument("--setup-only", action="store_true")
     ap.add_argument("--precond", default=None, choices=["block-mg"], help="host.run(..., precond=...) on top")
     ap.add_argument("--runs", type=int, default=1)
     ap.add_argument("--label", default=None)
@@ -155,18 +200,29 @@ def main():
     import eddy_currents_3d_amd as E
     from eddy_currents_3d_amd import host
     if a.config3:
-        return config3(E, host, a.label, a.out, a.null_tol)
+        return config3(E, host, a.label, a.out, a.null_tol[0])
     for case in a.cases:
         model, model_tol, model_itmax = model_of(case)
+        if a.setup_only:
+            for null_tol in a.null_tol:
+                for kind in a.null_precond:
+                    line = dict(case=case, setup_only=True, null_tol=null_tol or 1e-10, null_precond=kind or "none")
+                    if a.label:
+                        line = dict(build=a.label, **line)
+                    line.update(setup_only(E, model, null_tol, kind))
+                    emit(line, a.out)
+            continue
         for tol_text in a.tols:
             tol = None if tol_text == "model" else float(tol_text)
             for mode in a.modes:
                 for run in range(a.runs):
                     line = dict(case=case, tol=model_tol if tol is None else tol, mode=mode, run=run,
-                                itmax=a.itmax or model_itmax, **({"precond": a.precond} if a.precond else {}))
+                                itmax=a.itmax or model_itmax, **({"precond": a.precond} if a.precond else {}),
+                                **({"null_precond": a.null_precond[0]} if a.null_precond[0] else {}))
                     if a.label:
                         line = dict(build=a.label, **line)
-                    line.update(one_run(E, host, model, tol, a.itmax, mode == "on", a.steps or CASES[case][1], a.null_tol, a.precond))
+                    line.update(one_run(E, host, model, tol, a.itmax, mode == "on", a.steps or CASES[case][1], a.null_tol[0], a.precond,
+                                        a.null_precond[0]))
                     emit(line, a.out)
 
 
