@@ -245,6 +245,7 @@ void ec3d_free_matrix(ec3d_ctx *c)
     c->slab_xd = 0;
     ec3d_free_rhs(c);
     ec3d_free_output(c);
+    ec3d_free_probes(c);
     ec3d_mg_free(c);
     ec3d_guess_free(c); // the pairs are a statement about this matrix; the depth stays
     ec3d_null_free(c);  // ... and so are the left null vectors; the setting stays

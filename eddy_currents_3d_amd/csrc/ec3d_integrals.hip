@@ -224,20 +224,6 @@ __global__ void k_cond_bytes(uint8_t *cond, const int32_t *__restrict__ cell, in
     if (m < ncond) cond[cell[m]] = 1;
 }
 
-// what the three calls refuse first, in this order (status 3, 5)
-int need_undivided(ec3d_ctx *c, const char *who)
-{
-    if (!c || !c->have_matrix || c->sdx == 0 || c->n_cells == 0 || c->A.n < 3 * c->n_cells) { // as ec3d_vtk_fields
-        ec3d_set_error(std::string(who) + ": needs the A-V system [Ax|Ay|Az|U] from ec3d_assemble");
-        return 3;
-    }
-    if (c->in_multi || c->n_cells != (int64_t)c->sdx * c->sdy * c->sdz) {
-        ec3d_set_error(std::string(who) + ": a z-slab holds only part of a domain; undivided handles (ec3d_assemble) only");
-        return 5;
-    }
-    return 0;
-}
-
 Grid grid_of(const ec3d_ctx *c, const double *delta)
 {
     const int64_t kdz = (int64_t)c->sdx * c->sdy;
@@ -291,6 +277,19 @@ int list_sums(ec3d_ctx *c, const double *delta, int ndom, int64_t nchunk, const 
 
 } // namespace
 
+int ec3d_need_undivided(ec3d_ctx *c, const char *who)
+{
+    if (!c || !c->have_matrix || c->sdx == 0 || c->n_cells == 0 || c->A.n < 3 * c->n_cells) { // as ec3d_vtk_fields
+        ec3d_set_error(std::string(who) + ": needs the A-V system [Ax|Ay|Az|U] from ec3d_assemble");
+        return 3;
+    }
+    if (c->in_multi || c->n_cells != (int64_t)c->sdx * c->sdy * c->sdz) {
+        ec3d_set_error(std::string(who) + ": a z-slab holds only part of a domain; undivided handles (ec3d_assemble) only");
+        return 5;
+    }
+    return 0;
+}
+
 void ec3d_free_integrals(ec3d_ctx *c)
 {
     c->dom = DomIntegrals();
@@ -337,7 +336,7 @@ int ec3d_setup_integrals(ec3d_ctx *c, int64_t nCells, const int8_t *geoPHYS, con
 extern "C" int ec3d_domain_integrals(ec3d_handle c, const double *delta, int32_t cap, int32_t *ndomains,
                                      ec3d_domain_integral *out)
 {
-    int rc = need_undivided(c, "ec3d_domain_integrals");
+    int rc = ec3d_need_undivided(c, "ec3d_domain_integrals");
     if (rc) return rc;
     if (!delta || !ndomains) {
         ec3d_set_error("ec3d_domain_integrals: delta and ndomains are required");
@@ -374,7 +373,7 @@ extern "C" int ec3d_domain_integrals(ec3d_handle c, const double *delta, int32_t
 
 extern "C" int ec3d_domain_linkage(ec3d_handle c, const double *delta, int32_t cap, int32_t *ndomains, ec3d_domain_link *out)
 {
-    int rc = need_undivided(c, "ec3d_domain_linkage");
+    int rc = ec3d_need_undivided(c, "ec3d_domain_linkage");
     if (rc) return rc;
     if (!delta || !ndomains) {
         ec3d_set_error("ec3d_domain_linkage: delta and ndomains are required");
@@ -430,7 +429,7 @@ extern "C" int ec3d_domain_linkage(ec3d_handle c, const double *delta, int32_t c
 
 extern "C" int ec3d_field_energy(ec3d_handle c, const double *delta, ec3d_field_energy_info *out)
 {
-    int rc = need_undivided(c, "ec3d_field_energy");
+    int rc = ec3d_need_undivided(c, "ec3d_field_energy");
     if (rc) return rc;
     if (!delta || !out) {
         ec3d_set_error("ec3d_field_energy: delta and out are required");

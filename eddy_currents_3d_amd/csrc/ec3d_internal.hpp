@@ -350,6 +350,17 @@ struct FieldEnergy {
     PinnedBuf<double> host;
 };
 
+// The probe set of ec3d_set_probes (ec3d_probes.hip): the cells resolved to device cells and U rows, the buffer of the
+// immediate sample and the record that stays on the device.  Belongs to the matrix (ec3d_free_matrix).
+struct Probes {
+    int64_t n = 0, capacity = 0, recorded = 0;
+    DevBuf<int32_t> cell;   // [n] 0-based DEVICE cell index (dev_cell)
+    DevBuf<int32_t> urow;   // [n] device row of the cell's U unknown (ec3d_get_row_map's), -1 outside the conductors
+    DevBuf<double> sample;  // [13][n] what ec3d_probe_sample copies out
+    DevBuf<double> record;  // [capacity][13][n]
+    std::vector<double> T;  // [recorded] the caller's time of every record
+};
+
 // The host's cursor of a run of iterations.  The device state is addressed by the iteration number (rr0[it & 1], AP in
 // apbuf[it & 1], P and S in their rings), so the host keeps in step with it here and nowhere else: ec3d_run_reset starts
 // a run, ec3d_run_open says which iterations a call launches, ec3d_after_s / ec3d_after_p advance it behind a launch
@@ -529,6 +540,7 @@ struct ec3d_ctx {
     DomIntegrals dom;              // per-domain integrals (ec3d_integrals.hip); freed with cond_cell
     DomLinkage link;               // ... of the non-conducting domains (ec3d_domain_linkage)
     FieldEnergy energy;            // ec3d_field_energy's buffers
+    Probes probes;                 // ec3d_set_probes' cells and records (ec3d_probes.hip)
     // plain band streams whose placement was probed (place_bands): kept across a change of matrix of the same size, so
     // the probe runs once per handle and size, and what it found (candidate times in us, the one kept)
     DevBuf<double> placed_bands;
@@ -840,3 +852,8 @@ int ec3d_setup_rhs(ec3d_ctx *c, int64_t nCells, const int8_t *geoPHYS, const int
 void ec3d_free_integrals(ec3d_ctx *c);
 int ec3d_setup_integrals(ec3d_ctx *c, int64_t nCells, const int8_t *geoPHYS, const int32_t *geoPHYS_C,
                          const double *valPHYS, int32_t nsub_glob);
+// what the calls on the resident fields of an undivided A-V handle refuse first, in this order: 3 (no A-V system from
+// ec3d_assemble), 5 (a z-slab or a slab of ec3d_multi), with the error text; 0 otherwise
+int ec3d_need_undivided(ec3d_ctx *c, const char *who);
+// ec3d_probes.hip
+void ec3d_free_probes(ec3d_ctx *c);

@@ -28,7 +28,9 @@ module ec3d_hip
               ec3d_field_energy_info, ec3d_field_energy, ec3d_domain_link, ec3d_domain_linkage, &
               ec3d_set_guess_history, ec3d_get_guess_history, ec3d_guess_info, EC3D_GUESS_MAX_DEPTH, &
               ec3d_spmv_t, ec3d_set_null_projection, ec3d_get_null_projection, ec3d_left_null_vector, ec3d_null_info, &
-              EC3D_NULL_MAX_REPORT, EC3D_NULL_E_MATRIX, EC3D_NULL_E_SETUP
+              EC3D_NULL_MAX_REPORT, EC3D_NULL_E_MATRIX, EC3D_NULL_E_SETUP, &
+              ec3d_set_probes, ec3d_probe_sample, ec3d_probe_record, ec3d_probe_read, ec3d_probe_reset, ec3d_get_probes, &
+              ec3d_probe_info, EC3D_PROBE_NCOMP, EC3D_PROBE_E_FULL
 
     integer(c_int), parameter :: EC3D_VEC_X = 0, EC3D_VEC_B = 1   ! Uaf, Jaf
     integer(c_int), parameter :: EC3D_PRECOND_NONE = 0, EC3D_PRECOND_MG = 1   ! ec3d_set_preconditioner
@@ -75,6 +77,14 @@ module ec3d_hip
         integer(c_int32_t) :: domain, pad
         integer(c_int64_t) :: cells
         real(c_double) :: linkage, jsum(3)
+    end type
+
+    integer(c_int32_t), parameter :: EC3D_PROBE_NCOMP = 13   ! values per probe: a(3), eddy(3), source(3), b(3), u
+    integer(c_int), parameter :: EC3D_PROBE_E_FULL = 24      ! ec3d_probe_record on a full buffer
+
+    ! what ec3d_get_probes reports (ec3d_probe_info of include/ec3d_hip.h)
+    type, bind(C) :: ec3d_probe_info
+        integer(c_int64_t) :: nprobes, capacity, recorded, device_bytes
     end type
 
     interface
@@ -208,7 +218,46 @@ module ec3d_hip
             integer(c_int32_t), intent(out) :: ndomains
             type(ec3d_domain_link), intent(out) :: out(*)
         end function
-        ! the same beside the next time step: _begin returns at once (field kernel + copy into a pinned buffer are
+        ! probes: the fields at chosen cells from the resident Uaf, Jaf -- what field_N.vtk shows there before its rounding
+        ! to REAL(4), and U.  cells: 0-based cell numbers i + j*sdx + k*sdx*sdy (i, j, k from 0); capacity: records the
+        ! device buffer holds (0: ec3d_probe_sample only); nprobes = 0 clears the set
+        integer(c_int) function ec3d_set_probes(h, nprobes, cells, capacity) bind(C, name="ec3d_set_probes")
+            import :: c_ptr, c_int, c_int64_t
+            type(c_ptr), value :: h
+            integer(c_int64_t), value :: nprobes, capacity
+            integer(c_int64_t), intent(in) :: cells(*)
+        end function
+        ! out(nprobes, EC3D_PROBE_NCOMP): ax ay az, eddy x y z, source x y z, bx by bz, u; call after ec3d_post_update
+        integer(c_int) function ec3d_probe_sample(h, delta, out) bind(C, name="ec3d_probe_sample")
+            import :: c_ptr, c_int, c_double
+            type(c_ptr), value :: h
+            real(c_double), intent(in) :: delta(*)
+            real(c_double), intent(out) :: out(*)
+        end function
+        ! the same sample appended to the record on the device, nothing waits; EC3D_PROBE_E_FULL when the buffer is full
+        integer(c_int) function ec3d_probe_record(h, delta, T) bind(C, name="ec3d_probe_record")
+            import :: c_ptr, c_int, c_double
+            type(c_ptr), value :: h
+            real(c_double), intent(in) :: delta(*)
+            real(c_double), value :: T
+        end function
+        ! records first .. first + count - 1 (from 0): out(nprobes, EC3D_PROBE_NCOMP, count) and T_out(count)
+        integer(c_int) function ec3d_probe_read(h, first, count, T_out, out) bind(C, name="ec3d_probe_read")
+            import :: c_ptr, c_int, c_int64_t, c_double
+            type(c_ptr), value :: h
+            integer(c_int64_t), value :: first, count
+            real(c_double), intent(out) :: T_out(*), out(*)
+        end function
+        integer(c_int) function ec3d_probe_reset(h) bind(C, name="ec3d_probe_reset")
+            import :: c_ptr, c_int
+            type(c_ptr), value :: h
+        end function
+        integer(c_int) function ec3d_get_probes(h, info) bind(C, name="ec3d_get_probes")
+            import :: c_ptr, c_int, ec3d_probe_info
+            type(c_ptr), value :: h
+            type(ec3d_probe_info), intent(out) :: info
+        end function
+        ! ec3d_vtk_fields beside the next time step: _begin returns at once (field kernel + copy into a pinned buffer are
         ! enqueued), _wait blocks until that buffer has landed and returns C pointers to 3*ncells REAL(4) each
         ! (c_f_pointer them); big_endian /= 0: already in the byte order of the BINARY legacy-VTK file
         integer(c_int) function ec3d_vtk_fields_begin(h, delta, big_endian, slot) bind(C, name="ec3d_vtk_fields_begin")

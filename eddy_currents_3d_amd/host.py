@@ -341,7 +341,7 @@ def run(model: vxc.VxcModel, solver, steps: int | None = None, out_dir: str | No
         on_rhs=None, on_solved=None, write_output=None, overlap_output: bool = True, on_fields=None, on_written=None,
         precond: str | None = None, u_rhs: str | None = None, integrals: bool = False, guess_history: int | None = None,
         energy: bool = False, null_projection: bool | None = None, tol: float | None = None,
-        null_tol: float | None = None, null_precond: str | None = None):
+        null_tol: float | None = None, null_precond: str | None = None, probes=None, probe_capacity: int | None = None):
     """The reference's run of ``model`` on ``solver`` (an EC3DSolver): assemble, then step until T >= stop (or
     ``steps`` steps).  Returns a list of per-step dicts (T, iter).  ``out_dir``: write ``field_N.vtk`` there at
     the reference's output cadence.  Hooks, all ``(k, solver, info)``: ``on_rhs`` when Jaf (B) of step k is
@@ -375,7 +375,16 @@ def run(model: vxc.VxcModel, solver, steps: int | None = None, out_dir: str | No
     raises ValueError); ``null_tol``: the accuracy of the adjoint solves instead of 1e-10;
     ``null_precond`` ("none", "block-mg", "block-mg-a"): their preconditioner (set_null_projection's ``precond``; None
     leaves the handle's setting as it is).  ``tol``: the solves' tolerance
-    instead of the model's."""
+    instead of the model's.
+    ``probes`` (cell numbers, eddy_currents_3d_amd.probes): solver.set_probes(probes, probe_capacity) after the
+    assembly and solver.probe_record(delta, T) after every post-update, where ``integrals`` is taken -- one launch and no
+    wait per step; the record stays on the device and is read when its ``probe_capacity`` records are full (default: the
+    whole run, or what fits 64 MiB) and at the end.  AFTER the loop ``info["probes"]`` of every step holds that step's
+    (nprobes, 13) float64 array (a, eddy, source, b, u: probes.COMPONENTS); the hooks do NOT see it during the loop --
+    ``on_step`` runs before the record is read.  One handle only (an EC3DMulti raises ValueError)."""
+    if probes is not None and not hasattr(solver, "set_probes"):
+        raise ValueError("probes need an EC3DSolver: a probe's cell and its neighbours are not available on the z-slabs "
+                         "of an EC3DMulti")
     if null_projection is not None and not hasattr(solver, "set_null_projection"):
         raise ValueError("null_projection needs an EC3DSolver: the left null vectors are not available on the z-slabs of "
                          "an EC3DMulti")
@@ -403,6 +412,10 @@ def run(model: vxc.VxcModel, solver, steps: int | None = None, out_dir: str | No
                                    **({} if null_precond is None else {"precond": null_precond}))
     if tol is not None:
         t = dict(t, tol=float(tol))
+    plog = None
+    if probes is not None:
+        plog = _ProbeLog(solver, t["delta"], probes, probe_capacity,
+                         steps if steps is not None else int(float(t["time"]) / float(t["dt"])) + 1)
     n = solver.n
     solver.upload("X", np.zeros(n))
     solver.upload("B", np.zeros(n))
@@ -422,16 +435,48 @@ def run(model: vxc.VxcModel, solver, steps: int | None = None, out_dir: str | No
     try:
         log = _time_loop(solver, t, prog, (sdx, sdy, sdz), conducting, out_dir, pipe, steps, on_step, on_rhs, on_solved,
                          write_output, on_fields, on_written, DT, Time, Nout, T, Ntime, Nprint, Npoint, integrals, guess=bool(guess_history),
-                         energy=energy, null=bool(null_projection))
+                         energy=energy, null=bool(null_projection), plog=plog)
+        if plog is not None:
+            plog.drain()
     finally:
         if pipe is not None:
             pipe.finish()
     return log
 
 
+class _ProbeLog:
+    """The probes of a run: one ec3d_probe_record per step, the record read (one copy) whenever it is full and at the
+    end; every step's (nprobes, 13) array goes into that step's info then."""
+    DEFAULT_BYTES = 64 << 20
+
+    def __init__(self, solver, delta, cells, capacity, steps):
+        cells = np.ascontiguousarray(cells, np.int64).reshape(-1)
+        if capacity is None:
+            capacity = min(max(1, int(steps)), max(1, self.DEFAULT_BYTES // (104 * max(1, len(cells)))))
+        if len(cells) == 0 or int(capacity) < 1:
+            raise ValueError("probes: at least one cell and a probe_capacity of at least 1 are needed")
+        self.solver, self.delta, self.capacity, self.pending = solver, delta, int(capacity), []
+        solver.set_probes(cells, self.capacity)
+
+    def record(self, T, info):
+        if len(self.pending) == self.capacity:
+            self.drain()
+        self.solver.probe_record(self.delta, T)
+        self.pending.append(info)
+
+    def drain(self):
+        from .probes import stack
+        if self.pending:
+            _, rec = self.solver.probe_read(0, len(self.pending))
+            for info, v in zip(self.pending, stack(rec)):
+                info["probes"] = v
+            self.solver.probe_reset()
+            self.pending = []
+
+
 def _time_loop(solver, t, prog, dims, conducting, out_dir, pipe, steps, on_step, on_rhs, on_solved, write_output,
                on_fields, on_written, DT, Time, Nout, T, Ntime, Nprint, Npoint, integrals=False, guess=False,
-               energy=False, null=False):
+               energy=False, null=False, plog=None):
     sdx, sdy, sdz = dims
     log = []
     ahead = _SourcesAhead(prog, T, DT, Time, steps)
@@ -456,6 +501,8 @@ def _time_loop(solver, t, prog, dims, conducting, out_dir, pipe, steps, on_step,
             if energy:
                 info["energy"] = solver.field_energy(t["delta"])
                 info["linkage"] = solver.domain_linkage(t["delta"])
+            if plog is not None:
+                plog.record(T, info)
             if Ntime >= Nprint and Ntime != 0:               # :437-446
                 Nprint = Ntime + Nout
                 Npoint += 1
@@ -575,16 +622,19 @@ def _pwrite_all(fd, data, offset):
 
 
 def run_slabs(model: vxc.VxcModel, rank: int, world: int, device: int = 0, steps: int | None = None,
-              out_dir: str | None = None, on_step=None, overlap_output: bool = True, energy: bool = False):
+              out_dir: str | None = None, on_step=None, overlap_output: bool = True, energy: bool = False, probes=None):
     """The same run on ``world`` GPUs, one process per GPU (torch.distributed initialised by the caller):
     z-slabs of the A-V system (eddy_currents_3d_amd/dist.py), every rank evaluates the (tiny) source program
     itself and keeps its part of the fields resident.  Output: every rank writes its own cells into field_N.vtk
     beside the next step's solve (_SlabOutputPipeline; the files are complete when this function returns, after a
     barrier); ``overlap_output=False``: the fields gathered on rank 0, which writes them inside the loop.  Returns the
     per-step log (identical on all ranks).  ``energy=True`` raises ValueError before anything is assembled: a z-slab
-    holds only part of the box and of every domain (ec3d_field_energy, ec3d_domain_linkage)."""
+    holds only part of the box and of every domain (ec3d_field_energy, ec3d_domain_linkage); so does ``probes`` (a
+    probe's neighbours may lie on another rank)."""
     if energy:
         raise ValueError("energy=True runs on one GPU only: a z-slab holds only part of the box and of every domain")
+    if probes is not None:
+        raise ValueError("probes run on one GPU only: a z-slab holds only part of the box")
     from .dist import HipAVSlabOps, SlabSolver, slab_bounds
     t = vxc.domain_tables(model)
     if t["dt"] is None or t["time"] is None:

@@ -2,6 +2,8 @@
 
     python -m eddy_currents_3d_amd.run model.vxc [--steps N] [--out DIR] [--device D] [--integrals FILE] [--guess-history N]
                                                  [--energy FILE] [--null-projection [--null-tol Y]] [--tol X]
+                                                 [--probes FILE [--probe I,J,K]... [--probe-line I0,J0,K0:I1,J1,K1]...
+                                                  [--probe-box I0,J0,K0:I1,J1,K1]...]
     python -m torch.distributed.run --nproc-per-node G -m eddy_currents_3d_amd.run model.vxc ...   (G GPUs)
 
 Reads the file (eddy_currents_3d_amd/vxc.py), assembles the A-V system on the device, and runs the
@@ -13,7 +15,10 @@ steps' solutions (EC3DSolver.set_guess_history; default 0 = off, one GPU only). 
 the box [J], the integral of A.J outside and inside the conductors [J] and the flux linkage psi*I [J] of every
 non-conducting domain after every step, as CSV, one line per step (one GPU only).  ``--null-projection``: take the left
 null vectors of the A-V system out of every solve's initial residual (EC3DSolver.set_null_projection; one GPU only), which
-lets ``--tol X`` -- the solves' tolerance instead of the model's -- go below the reference's.
+lets ``--tol X`` -- the solves' tolerance instead of the model's -- go below the reference's.  ``--probes FILE``: A, the
+eddy and source current densities, B and U at chosen cells (0-based I,J,K: points, lines, boxes; a plane is a box one cell
+thick) after every step, in float64, as CSV, one line per step and probe; they are recorded on the device and written
+after the run (one GPU only).
 """
 from __future__ import annotations
 
@@ -81,15 +86,35 @@ def build_parser():
                     help="preconditioner of the adjoint solves of --null-projection: the transposed block multigrid "
                          "(block-mg), the same with the A blocks' hierarchy of A as it stands (block-mg-a), or none "
                          "(default: the handle's setting, which starts as none)")
+    ap.add_argument("--probes", metavar="FILE", default=None,
+                    help="write the fields at the cells of --probe, --probe-line and --probe-box per time step to this "
+                         "CSV file, from the record kept on the device (step,T,probe,i,j,k,ax,...,bz,u; one GPU only)")
+    ap.add_argument("--probe", action="append", default=[], metavar="I,J,K", help="a probe at this cell (0-based; repeatable)")
+    ap.add_argument("--probe-line", action="append", default=[], metavar="I0,J0,K0:I1,J1,K1",
+                    help="probes along the line between the two cells, both included (repeatable)")
+    ap.add_argument("--probe-box", action="append", default=[], metavar="I0,J0,K0:I1,J1,K1",
+                    help="probes at every cell of the box with these inclusive corners, in scan order (repeatable)")
     ap.add_argument("--tol", type=float, default=None, metavar="X",
                     help="tolerance of the time step's solve instead of the model's (one GPU only)")
     return ap
+
+
+def check_probe_options(ap, a, world):
+    """The refusals of --probes that need no model: several ranks, no probe option, a probe option without --probes."""
+    given = bool(a.probe or a.probe_line or a.probe_box)
+    if a.probes and world > 1:
+        ap.error("--probes runs on one GPU only; a z-slab holds only part of the box")
+    if a.probes and not given:
+        ap.error("--probes needs at least one of --probe, --probe-line, --probe-box")
+    if given and not a.probes:
+        ap.error("--probe, --probe-line and --probe-box need --probes FILE")
 
 
 def main(argv=None):
     ap = build_parser()
     a = ap.parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    check_probe_options(ap, a, world)
     if world > 1 and a.integrals:
         ap.error("--integrals runs on one GPU only; a z-slab holds only part of a conducting domain")
     if world > 1 and a.energy:
@@ -104,6 +129,13 @@ def main(argv=None):
     out_dir = None if a.no_output else (a.out or str(t["directory"]).upper())
     print(f"{a.model}: grid {sdx}x{sdy}x{sdz}, {t['ncells0']} conducting cells, dt={t['dt']:g} stop={t['time']:g} "
           f"tol={t['tol']:g} itmax={t['itmax']}", flush=True)
+    pcells = None
+    if a.probes:
+        from . import probes as P
+        try:
+            pcells = P.cells_from_options(a.probe, a.probe_line, a.probe_box, (sdx, sdy, sdz))
+        except ValueError as e:
+            ap.error(str(e))
     t0 = time.perf_counter()
 
     csv = None
@@ -155,7 +187,12 @@ def main(argv=None):
                                integrals=csv is not None, guess_history=a.guess_history or None,
                                energy=ecsv is not None, null_projection=True if a.null_projection else None,
                                tol=a.tol, null_tol=a.null_tol,
-                               null_precond=a.null_precond if a.null_projection else None)
+                               null_precond=a.null_precond if a.null_projection else None, probes=pcells)
+                if pcells is not None:   # the record has been read: one line per step and probe
+                    with open(a.probes, "w") as f:
+                        f.write(P.CSV_HEADER + "\n")
+                        for k, info in enumerate(log):
+                            f.writelines(line + "\n" for line in P.csv_rows(k, info["T"], pcells, (sdx, sdy, sdz), info["probes"]))
                 if a.null_projection:
                     q = s.null_projection()
                     kind, levels, hms = s.null_precond()

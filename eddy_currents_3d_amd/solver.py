@@ -59,6 +59,11 @@ class DomainLink(C.Structure):
                 ("jsum", C.c_double * 3)]
 
 
+class ProbeInfo(C.Structure):
+    """ec3d_probe_info of include/ec3d_hip.h."""
+    _fields_ = [("nprobes", C.c_int64), ("capacity", C.c_int64), ("recorded", C.c_int64), ("device_bytes", C.c_int64)]
+
+
 class GuessInfo(C.Structure):
     """ec3d_guess_info of include/ec3d_hip.h."""
     _fields_ = [("depth", C.c_int32), ("stored", C.c_int32), ("used", C.c_int32), ("kept", C.c_int32),
@@ -106,7 +111,11 @@ EXPORTS = ["sprsbcgstabwr_", "ec3d_invalidate", "ec3d_create", "ec3d_destroy", "
            "ec3d_get_precond_coarsening", "ec3d_set_precond_grid", "ec3d_get_precond_grid",
            "ec3d_domain_integrals", "ec3d_field_energy", "ec3d_domain_linkage", "ec3d_get_class_runs", "ec3d_get_patch_rows", "ec3d_get_k51_ap_form", "ec3d_set_guess_history", "ec3d_get_guess_history",
            "ec3d_spmv_t", "ec3d_set_null_projection", "ec3d_get_null_projection", "ec3d_left_null_vector",
-           "ec3d_set_null_precond", "ec3d_get_null_precond", "ec3d_null_precond_apply"]
+           "ec3d_set_null_precond", "ec3d_get_null_precond", "ec3d_null_precond_apply",
+           "ec3d_set_probes", "ec3d_probe_sample", "ec3d_probe_record", "ec3d_probe_read", "ec3d_probe_reset",
+           "ec3d_get_probes"]
+PROBE_NCOMP = 13     # EC3D_PROBE_NCOMP of include/ec3d_hip.h: a[3], eddy[3], source[3], b[3], u
+PROBE_E_FULL = 24    # EC3D_PROBE_E_FULL: ec3d_probe_record on a full buffer
 U_RHS = {"reference": 0, "all": 1}   # EC3D_U_RHS_* of include/ec3d_hip.h
 PRECOND = {"none": 0, "mg": 1, "block-mg": 2}   # EC3D_PRECOND_* of include/ec3d_hip.h
 PRECOND_E_MATRIX, PRECOND_E_COARSE = 20, 21   # ec3d_set_preconditioner's refusals
@@ -227,6 +236,12 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.ec3d_domain_integrals.argtypes = [hp, _f64, C.c_int32, C.POINTER(C.c_int32), C.POINTER(DomainIntegral)]
     L.ec3d_field_energy.argtypes = [hp, _f64, C.POINTER(FieldEnergy)]
     L.ec3d_domain_linkage.argtypes = [hp, _f64, C.c_int32, C.POINTER(C.c_int32), C.POINTER(DomainLink)]
+    L.ec3d_set_probes.argtypes = [hp, C.c_int64, C.c_void_p, C.c_int64]
+    L.ec3d_probe_sample.argtypes = [hp, _f64, C.c_void_p]
+    L.ec3d_probe_record.argtypes = [hp, _f64, C.c_double]
+    L.ec3d_probe_read.argtypes = [hp, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
+    L.ec3d_probe_reset.argtypes = [hp]
+    L.ec3d_get_probes.argtypes = [hp, C.POINTER(ProbeInfo)]
     L.ec3d_vtk_fields_wait.argtypes = [hp, C.c_int32] + [C.POINTER(C.POINTER(C.c_float))] * 4 + [C.POINTER(C.c_int64)]
     L.ec3d_set_workgroups.argtypes = [hp, C.c_int32]
     L.ec3d_get_matrix_info.argtypes = [hp, C.POINTER(MatrixInfo)]
@@ -623,6 +638,62 @@ class EC3DSolver:
         _chk(self.L, self.L.ec3d_domain_linkage(self.h, d, n.value, C.byref(n), out), "ec3d_domain_linkage")
         return [dict(domain=int(r.domain), cells=int(r.cells), linkage=float(r.linkage),
                      jsum=np.array(r.jsum[:], np.float64)) for r in out[:n.value]]
+
+    # ---- probes: the fields at chosen cells (ec3d_set_probes ... ec3d_get_probes) --------------
+    def set_probes(self, cells, capacity: int = 0):
+        """The probe set: 0-based cell numbers i + j*sdx + k*sdx*sdy in any order, duplicates allowed
+        (eddy_currents_3d_amd.probes builds lines and boxes); ``capacity``: records the device buffer holds (0:
+        probe_sample only).  An empty list clears the set.  A new assemble clears it too."""
+        cells = np.ascontiguousarray(cells, np.int64).reshape(-1)
+        _chk(self.L, self.L.ec3d_set_probes(self.h, len(cells), cells.ctypes.data if len(cells) else None, int(capacity)),
+             "ec3d_set_probes")
+
+    def probes(self):
+        """dict(nprobes, capacity, recorded, device_bytes) of the probe set (ec3d_get_probes)."""
+        r = ProbeInfo()
+        _chk(self.L, self.L.ec3d_get_probes(self.h, C.byref(r)), "ec3d_get_probes")
+        return dict(nprobes=int(r.nprobes), capacity=int(r.capacity), recorded=int(r.recorded),
+                    device_bytes=int(r.device_bytes))
+
+    @staticmethod
+    def _probe_dict(v):
+        """(..., 13, nprobes) as the library lays it out -> dict of a, eddy, source, b (..., nprobes, 3), u (..., nprobes)."""
+        m = np.moveaxis(v, -2, -1)
+        return dict(a=np.ascontiguousarray(m[..., 0:3]), eddy=np.ascontiguousarray(m[..., 3:6]),
+                    source=np.ascontiguousarray(m[..., 6:9]), b=np.ascontiguousarray(m[..., 9:12]),
+                    u=np.ascontiguousarray(m[..., 12]))
+
+    def probe_sample(self, delta):
+        """The fields at the probes from the resident X, B (ec3d_probe_sample), in float64: dict of a, eddy, source, b
+        of shape (nprobes, 3) and u of shape (nprobes,) -- what field_N.vtk shows at those cells before its rounding to
+        float32, and the scalar potential.  Meaningful after post_update of a step."""
+        n = self.probes()["nprobes"]
+        out = np.empty((PROBE_NCOMP, n), np.float64)
+        _chk(self.L, self.L.ec3d_probe_sample(self.h, np.ascontiguousarray(delta, np.float64), out.ctypes.data),
+             "ec3d_probe_sample")
+        return self._probe_dict(out)
+
+    def probe_record(self, delta, T: float):
+        """Append the same sample to the record on the device WITHOUT waiting (ec3d_probe_record); ``T`` is kept with
+        it.  Raises EC3DError with status PROBE_E_FULL when the buffer is full."""
+        _chk(self.L, self.L.ec3d_probe_record(self.h, np.ascontiguousarray(delta, np.float64), float(T)),
+             "ec3d_probe_record")
+
+    def probe_read(self, first: int = 0, count: int | None = None):
+        """Records [first, first + count) (default: all from ``first``) with one copy (ec3d_probe_read): (T, dict) with
+        T of shape (count,) and the arrays of probe_sample with a leading step axis."""
+        q = self.probes()
+        if count is None:
+            count = max(q["recorded"] - int(first), 0)
+        T = np.empty(max(int(count), 0), np.float64)
+        out = np.empty((max(int(count), 0), PROBE_NCOMP, q["nprobes"]), np.float64)
+        _chk(self.L, self.L.ec3d_probe_read(self.h, int(first), int(count), T.ctypes.data, out.ctypes.data),
+             "ec3d_probe_read")
+        return T, self._probe_dict(out)
+
+    def probe_reset(self):
+        """recorded = 0; the set and the buffer stay (ec3d_probe_reset)."""
+        _chk(self.L, self.L.ec3d_probe_reset(self.h), "ec3d_probe_reset")
 
     def vtk_fields_begin(self, delta, big_endian: bool = True) -> int:
         """Start the field output of this step WITHOUT waiting (ec3d_vtk_fields_begin): the field kernel on the

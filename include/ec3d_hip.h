@@ -218,6 +218,50 @@ typedef struct {
 } ec3d_domain_link;
 int ec3d_domain_linkage(ec3d_handle h, const double *delta, int32_t cap, int32_t *ndomains, ec3d_domain_link *out);
 
+/* The resident fields at chosen cells (probes): points, lines, planes or any sub-box, sampled from the resident Uaf (X)
+ * and Jaf (B) by one small launch, returned at once (ec3d_probe_sample) or appended to a record that stays on the device
+ * and is read once at the end of a run (ec3d_probe_record, ec3d_probe_read).  The EC3D_PROBE_NCOMP = 13 values of the
+ * probe at cell (i, j, k), in double precision and without contraction, the s and the B of ec3d_domain_integrals:
+ *    0 ..  2  a       A                                               (Field_A)
+ *    3 ..  5  eddy    s * Jaf in a conductor cell (geoPHYS_C != 0), else 0.0   (Vector_field_eddy)
+ *    6 ..  8  source  Jaf outside the conductors, else 0.0           (Vector_field_SOURCE)
+ *    9 .. 11  b       curl A, central differences clamped at the box faces     (Vector_field_B)
+ *   12        u       the cell's U, 0.0 outside the conductors
+ * (float) of the first twelve is bit for bit what ec3d_vtk_fields returns at that cell.  X and B are read as they stand
+ * -- they mean the above after ec3d_post_update of a step -- and no work vector is written.  Nothing is summed: the
+ * same X, B and geometry give the same bits, whichever device form and plane pitch hold them.
+ *
+ * ec3d_set_probes    cells: nprobes 0-based cell numbers i + j*sdx + k*sdx*sdy, in the caller's order, duplicates
+ *                    allowed.  capacity: records the device buffer holds (13 * nprobes doubles each); 0: no buffer,
+ *                    ec3d_probe_sample only.  nprobes = 0 clears the set and frees everything.  The set replaces the
+ *                    previous one and its records; it belongs to the assembled matrix: a new assembly or matrix clears
+ *                    it.  Device memory: 8 B per probe and 104 B per probe and record (one more for the sample).
+ * ec3d_probe_sample  one launch, one copy, one synchronisation of the handle's stream: out receives 13 * nprobes
+ *                    doubles by component, then by probe: out[c * nprobes + p].
+ * ec3d_probe_record  enqueues the same launch on the handle's stream into record number `recorded`, keeps T beside
+ *                    it on the host and returns without waiting.  A full buffer (recorded == capacity; always with
+ *                    capacity 0): nothing is written, status EC3D_PROBE_E_FULL.
+ * ec3d_probe_read    records [first, first + count) with one copy and one synchronisation:
+ *                    out[(s * 13 + c) * nprobes + p] and T_out[s], s counted from `first`.
+ * ec3d_probe_reset   recorded = 0; the set and the buffer stay.
+ * ec3d_get_probes    nprobes, capacity, recorded and the device bytes held (all 0 without a set); any handle.
+ * Status 3, 5 as ec3d_domain_integrals; 2: a NULL argument, a negative count, no probes set, first + count > recorded,
+ * or a cell outside the box -- ec3d_last_error() then names the first offending entry and the previous set stays. */
+#define EC3D_PROBE_NCOMP 13
+#define EC3D_PROBE_E_FULL 24
+typedef struct {
+    int64_t nprobes;
+    int64_t capacity;
+    int64_t recorded;
+    int64_t device_bytes;
+} ec3d_probe_info;
+int ec3d_set_probes(ec3d_handle h, int64_t nprobes, const int64_t *cells, int64_t capacity);
+int ec3d_probe_sample(ec3d_handle h, const double *delta, double *out);
+int ec3d_probe_record(ec3d_handle h, const double *delta, double T);
+int ec3d_probe_read(ec3d_handle h, int64_t first, int64_t count, double *T_out, double *out);
+int ec3d_probe_reset(ec3d_handle h);
+int ec3d_get_probes(ec3d_handle h, ec3d_probe_info *info);
+
 /* ||B - A*X|| / ||B|| of the RESIDENT vectors, computed on the device by the solve's own setup kernel
  * (src/solvers.f90:14-21); bnorm (may be NULL) receives ||B||.  The check of a returned x that does not rely
  * on the iteration's recurrence for R.  Overwrites the work vectors R, R0, P (rebuilt by the next solve). */
