@@ -412,6 +412,78 @@ __global__ void k_build_table_sav(GridPar g, const double *__restrict__ valPHYS,
     for (int j = 0; j < 16; ++j) table[q * 16 + j] = t[j];
 }
 
+// The time-harmonic operator's two tables on the same classes (ec3d_harmonic.hip): re = what
+// k_build_table_sav writes with every dt term left out (the conductor's velocity terms stay), m = the unit imaginary
+// part -- C on the diagonal of a conducting A row (the trapezoidal 2 C / dt is C * 2 / dt), in a U row the A_d slots
+// with 0.5 in the place of h = 0.5 / dt and 2 / delta_d in the place of av = 2 / (dt delta_d) -- so that the transient
+// table is re + (omega m) * 2 / (omega dt) in A rows and re + (omega m) / (omega dt) in U rows.
+__global__ void k_build_table_harmonic(GridPar g, const double *__restrict__ valPHYS, double *re, double *mm)
+{
+    const SavIds id = sav_ids(g.ndom_c);
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= id.ncls) return;
+    double t[16], m[16];
+    for (int j = 0; j < 16; ++j) t[j] = m[j] = 0.0;
+    double c[7] = {0, 0, 0, 0, 0, 0, 0};
+    bool on_box;
+    if (q < 27) {
+        const int tt[3] = {q % 3, (q / 3) % 3, q / 9}, sd[3] = {g.sdx, g.sdy, g.sdz};
+        int p[3];
+        for (int d = 0; d < 3; ++d) p[d] = tt[d] == 0 ? 1 : (tt[d] == 2 ? sd[d] : 2);
+        a_row_bands(g, p[0], p[1], p[2], c, on_box);
+        for (int b = 0; b < 7; ++b) t[b] = c[b];
+    } else if (q < id.u0) {
+        const int e = q - 27, pat = e % 3 + 1, d = (e / 3) % 3, dom = g.cond_dom_of[e / 9];
+        a_row_bands(g, 2, 2, 2, c, on_box);
+        const double C = valPHYS[1 * (int64_t)g.nsub_glob + dom - 1];
+        for (int dd = 0; dd < 3; ++dd) { // conductor_terms without its last line
+            const double h = valPHYS[(2 + dd) * (int64_t)g.nsub_glob + dom - 1] / (2.0 * g.delta[dd]);
+            c[2 - dd] = c[2 - dd] - h;
+            c[4 + dd] = c[4 + dd] + h;
+        }
+        for (int b = 0; b < 7; ++b) t[b] = c[b];
+        m[3] = C;
+        double *u = t + 7 + 2;
+        if (pat == 1) {
+            u[+1] = -C * g.ds[d];
+            u[-1] = +C * g.ds[d];
+        } else if (pat == 2) {
+            u[0] = -3.0 * C * g.ds[d];
+            u[-1] = +4.0 * C * g.ds[d];
+            u[-2] = -1.0 * C * g.ds[d];
+        } else {
+            u[0] = +3.0 * C * g.ds[d];
+            u[+1] = -4.0 * C * g.ds[d];
+            u[+2] = +1.0 * C * g.ds[d];
+        }
+    } else if (q < id.zero) {
+        const int p = q - id.u0, st[3] = {p % 3, (p / 3) % 3, p / 9};
+        const int nmiss = (st[0] != 0) + (st[1] != 0) + (st[2] != 0);
+        const bool quirk = st[0] == 1 && st[1] == 2 && st[2] == 2; // :803-804
+        for (int d = 0; d < 3; ++d) {
+            double &cm = t[2 - d], &cp = t[4 + d];
+            if (st[d] == 0) { cm = -g.s[d]; cp = -g.s[d]; }
+            else if (st[d] == 1) { cm = 0.0; cp = -2.0 * g.s[d]; }
+            else { cm = -2.0 * g.s[d]; cp = 0.0; }
+            double *a = m + 7 + 3 * d;
+            if (nmiss == 0) {
+                a[0] = 0.5 * (1.0 / g.delta[d]);
+                a[2] = 0.5 * (-1.0 / g.delta[d]);
+            } else if (st[d] != 0) {
+                const double av = 2.0 / g.delta[d];
+                bool neg = st[d] == 1;
+                if (quirk && d < 2) neg = !neg;
+                a[1] = neg ? -av : av;
+            }
+        }
+        t[3] = 2.0 * ((g.s[0] + g.s[1]) + g.s[2]);
+    }
+    for (int j = 0; j < 16; ++j) {
+        re[q * 16 + j] = t[j];
+        mm[q * 16 + j] = m[j];
+    }
+}
+
 __global__ __launch_bounds__(256) void k_assemble_sav(GridPar g, const int8_t *__restrict__ geo,
                                                       const int32_t *__restrict__ geoC, uint8_t *cls,
                                                       uint8_t *tile_flag, uint8_t *flags, int *err,
@@ -870,6 +942,9 @@ int ec3d_assemble_sav_device(ec3d_ctx *c, int32_t sdx, int32_t sdy, int32_t sdz,
     EC3D_HIP(hipMemsetAsync(d_err, 0, sizeof(int), c->stream));
     EC3D_HIP(hipMemsetAsync(d_nnz, 0, sizeof(unsigned long long), c->stream));
     k_build_table_sav<<<(id.ncls + 63) / 64, 64, 0, c->stream>>>(g, d_val, A.table);
+    EC3D_HIP(c->harm.re.alloc((size_t)id.ncls * 16));
+    EC3D_HIP(c->harm.m.alloc((size_t)id.ncls * 16));
+    k_build_table_harmonic<<<(id.ncls + 63) / 64, 64, 0, c->stream>>>(g, d_val, c->harm.re, c->harm.m);
     k_assemble_sav<<<(unsigned)((g.nCells + 255) / 256), 256, 0, c->stream>>>(g, d_geo, d_geoC, A.cls, A.tile_flag,
                                                                               d_flags, d_err, d_nnz);
     EC3D_HIP(hipGetLastError());

@@ -249,6 +249,7 @@ void ec3d_free_matrix(ec3d_ctx *c)
     ec3d_mg_free(c);
     ec3d_guess_free(c); // the pairs are a statement about this matrix; the depth stays
     ec3d_null_free(c);  // ... and so are the left null vectors; the setting stays
+    ec3d_harmonic_free(c); // ... and the harmonic operator's tables and vectors
     c->poisson_full = false;
     c->from_csr = false;
     c->precond_grid[0] = c->precond_grid[1] = c->precond_grid[2] = 0;

@@ -1,0 +1,679 @@
+// ec3d_harmonic.hip — the time-harmonic A-V solve (K + j omega M) x^ = b^: complex BiCGSTAB with restart on the
+// structured form (ec3d_harmonic_*).
+//
+// Operator.  The class bytes of the real matrix with two tables of their own, made at ec3d_assemble
+// (k_build_table_harmonic): re, the transient table without its dt terms, and m, the unit imaginary part;
+// ec3d_harmonic_setup interleaves (re, omega * m) into one table of 16 pairs per class, which k_h_spmv holds in LDS.
+//
+// Vectors.  Eight complex vectors of n_pad interleaved (re, im) pairs in device numbering, no ghosts: a row's class is
+// tested before a neighbour is read, as in ec3d_transpose.hip.  A row is one 16-byte access.
+//
+// Arithmetic (-ffp-contract=off; tests/harmonic_numpy.py restates every line).  a x = (ar xr - ai xi, ar xi + ai xr),
+// every product and sum rounded on its own.  A row adds its terms from +0.0 in ascending column -- an A row its bands,
+// then its U couplings; a U row its A couplings, then its bands -- and a term whose two coefficients are 0 is neither
+// formed nor added.  <a, b> = sum conj(a) b, row term (ar br + ai bi, ar bi - ai br); a / b with d = br br + bi bi.
+//
+// Sums and launches: the streaming idiom of ec3d_stream.hpp on chunks of EC3D_TILE rows, G = ec3d_stream_wgs(n_pad)
+// workgroups, workgroup w the chunks w, w + G, ...; thread t owns rows t and t + 256 of a chunk (consecutive lanes,
+// consecutive 16-byte pairs) and adds row t's term, then row t + 256's.  Rows >= n enter every sum as +0.0 and are never
+// stored.  Every workgroup leaves one partial per sum; the NEXT kernel's workgroups each collapse them
+// (stream_strided_sum, stream_block_sum) and compute the scalars redundantly -- identical bits in every workgroup --
+// and workgroup 0 records them.  No float atomics.
+//
+// Iteration `it` (src/solvers.f90:29-49), five launches:
+//   k_h_spmv<1>   AP = A P, <R0, AP>
+//   k_h_s         alpha = rr0 / <R0, AP>;  S = R - alpha AP, ||S||^2
+//   k_h_spmv<2>   AS = A S, <AS, S>, <AS, AS>
+//   k_h_xr        ||S|| exit: X = X + alpha P.  Else omega = <AS, S> / <AS, AS>; X = (X + alpha P) + omega S;
+//                 R = S - omega AS, ||R||^2, <R0, R>
+//   k_h_p         ||R|| exit.  Else beta = (alpha / omega) rr0_new / rr0; restart (R0 = R, P = R, rr0 = ||R||^2) when
+//                 |rr0_new| / ||b^|| < tol, else P = R + beta (P - omega AP), rr0 = rr0_new
+// The exit words stay on the device: stop_s is written by k_h_xr only, stop_r by k_h_p (and the set-up) only, and a
+// kernel never tests at its entry a word that its own launch may write with a value that would change the test --
+// k_h_xr of iteration it asks stop_s < it, k_h_p stop_r < it -- so a workgroup that starts late takes the same path as
+// workgroup 0.  rr0 alternates between two slots for the same reason.  The host enqueues 16 iterations and polls once.
+#include "ec3d_stream.hpp"
+
+#include <chrono>
+#include <cmath>
+
+enum { HP_BB = 0, HP_RR, HP_RR0R, HP_RR0I, HP_D1R, HP_D1I, HP_SS, HP_D2R, HP_D2I, HP_D3, HP_NSLOT };
+
+struct HarmonicState {
+    double rr0[2][2]; // <R0, R> entering iteration it: rr0[it & 1]
+    double alpha[2], omega[2];
+    double bnorm, tol;
+    double rnorm, snorm; // of the last k_h_p / k_h_xr that got that far
+    int stop_s, stop_r;  // INT_MAX while running; the iteration of the ||S|| / ||R|| exit (stop_r = 0: ||b^|| = 0)
+    int restarts, pad_;
+};
+
+namespace {
+
+typedef stream_d2 cplx; // .x = re, .y = im
+static_assert((55 + 9 * EC3D_SAV_MAXDOM) * 16 * sizeof(cplx) + 256 <= 65536, "k_h_spmv: the table of pairs fits 64 KB of LDS");
+
+__device__ __forceinline__ cplx cmul(cplx a, cplx b) { return cplx{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
+__device__ __forceinline__ cplx cdiv(cplx a, cplx b)
+{
+    const double d = b.x * b.x + b.y * b.y;
+    return cplx{(a.x * b.x + a.y * b.y) / d, (a.y * b.x - a.x * b.y) / d};
+}
+// the row term of <a, b> and of a norm
+__device__ __forceinline__ cplx cdot(cplx a, cplx b) { return cplx{a.x * b.x + a.y * b.y, a.x * b.y - a.y * b.x}; }
+__device__ __forceinline__ double cabs2(cplx a) { return a.x * a.x + a.y * a.y; }
+
+__device__ __forceinline__ int64_t h_row(int64_t ch, int half) { return ch * EC3D_TILE + half * EC3D_THREADS + threadIdx.x; }
+__device__ __forceinline__ cplx h_load(const cplx *p, int64_t r, int64_t n) { return r < n ? p[r] : cplx{0.0, 0.0}; }
+
+// NV sums, slot0 .. slot0 + NV - 1 of `part` (G partials each), in every thread
+template <int NV> __device__ __forceinline__ void h_collapse(double (&v)[NV], const double *part, int slot0, int G, double *lds)
+{
+    stream_strided_sum<NV>(v, part + (int64_t)slot0 * G, G, G);
+    stream_block_sum<NV>(v, lds);
+    if (threadIdx.x == 0)
+        for (int k = 0; k < NV; ++k) lds[k] = v[k];
+    __syncthreads();
+    for (int k = 0; k < NV; ++k) v[k] = lds[k];
+    __syncthreads();
+}
+template <int NV> __device__ __forceinline__ void h_leave(double (&v)[NV], double *part, int slot0, double *lds)
+{
+    stream_block_sum<NV>(v, lds);
+    if (threadIdx.x == 0)
+        for (int k = 0; k < NV; ++k) part[(int64_t)(slot0 + k) * gridDim.x + blockIdx.x] = v[k];
+}
+
+struct HSav {
+    const uint8_t *cls;
+    const cplx *table;
+    int ncls, a0, u0, zero;
+    int64_t n, nC, off[7], step[3];
+};
+
+__device__ __forceinline__ void h_term(cplx &s, cplx t, const cplx *__restrict__ x, int64_t j, int64_t n)
+{
+    if (t.x == 0.0 && t.y == 0.0) return;
+    if (j < 0 || j >= n) return; // (no table of ec3d_assemble points outside the box)
+    const cplx p = cmul(t, x[j]);
+    s.x = s.x + p.x;
+    s.y = s.y + p.y;
+}
+
+__device__ __forceinline__ cplx h_row_product(const HSav &A, const cplx *tbl, const cplx *__restrict__ x, int64_t i)
+{
+    cplx s = {0.0, 0.0};
+    const int cc = A.cls[i];
+    if (cc >= A.zero) return s;
+    const cplx *t = tbl + cc * 16;
+    const int blk = (int)(i / A.nC);
+    const int64_t q = i - blk * A.nC;
+    if (cc < A.u0) {
+        for (int b = 0; b < 7; ++b) h_term(s, t[b], x, i + A.off[b], A.n);
+        if (cc >= A.a0) {
+            const int64_t step = blk == 0 ? A.step[0] : (blk == 1 ? A.step[1] : A.step[2]);
+            for (int m = -2; m <= 2; ++m) h_term(s, t[7 + m + 2], x, 3 * A.nC + q + m * step, A.n);
+        }
+    } else {
+        for (int d = 0; d < 3; ++d)
+            for (int j = 0; j < 3; ++j) h_term(s, t[7 + 3 * d + j], x, d * A.nC + q + (j - 1) * A.step[d], A.n);
+        for (int b = 0; b < 7; ++b) h_term(s, t[b], x, i + A.off[b], A.n);
+    }
+    return s;
+}
+
+// MODE 0: y = A x.  1: and <o, y> (o = R0).  2: and <y, x>, <y, y> (x = S).  3: r = o - y (o = B^), r0 = p = r,
+// ||o||^2 and ||r||^2: y, r0, p are the three outputs
+template <int MODE>
+__global__ __launch_bounds__(EC3D_THREADS) void k_h_spmv(HSav A, const HarmonicState *st, const cplx *__restrict__ x,
+                                                        const cplx *__restrict__ o, cplx *__restrict__ y,
+                                                        cplx *__restrict__ r0, cplx *__restrict__ p, int64_t nchunk,
+                                                        double *__restrict__ part)
+{
+    extern __shared__ cplx tbl[];
+    __shared__ double lds[12];
+    if ((MODE == 1 || MODE == 2) && (st->stop_s != INT_MAX || st->stop_r != INT_MAX)) return;
+    for (int q = threadIdx.x; q < A.ncls * 16; q += EC3D_THREADS) tbl[q] = A.table[q];
+    __syncthreads();
+    double acc[3] = {0.0, 0.0, 0.0};
+    for (int64_t ch = blockIdx.x; ch < nchunk; ch += gridDim.x)
+        for (int half = 0; half < 2; ++half) {
+            const int64_t i = h_row(ch, half);
+            if (i >= A.n) continue;
+            const cplx s = h_row_product(A, tbl, x, i);
+            if (MODE == 0) y[i] = s;
+            if (MODE == 1) {
+                y[i] = s;
+                const cplx d = cdot(o[i], s);
+                acc[0] = acc[0] + d.x;
+                acc[1] = acc[1] + d.y;
+            }
+            if (MODE == 2) {
+                y[i] = s;
+                const cplx d = cdot(s, x[i]);
+                acc[0] = acc[0] + d.x;
+                acc[1] = acc[1] + d.y;
+                acc[2] = acc[2] + cabs2(s);
+            }
+            if (MODE == 3) {
+                const cplx b = o[i], r = cplx{b.x - s.x, b.y - s.y};
+                y[i] = r;
+                r0[i] = r;
+                p[i] = r;
+                acc[0] = acc[0] + cabs2(b);
+                acc[1] = acc[1] + cabs2(r);
+            }
+        }
+    if (MODE == 1) {
+        double v[2] = {acc[0], acc[1]};
+        h_leave<2>(v, part, HP_D1R, lds);
+    }
+    if (MODE == 2) h_leave<3>(acc, part, HP_D2R, lds);
+    if (MODE == 3) {
+        double v[2] = {acc[0], acc[1]};
+        h_leave<2>(v, part, HP_BB, lds);
+    }
+}
+
+// behind k_h_spmv<3>, one workgroup: ||b^||, rr0 = <R0, R> = (||R||^2, 0), the exit words
+__global__ __launch_bounds__(EC3D_THREADS) void k_h_setup(HarmonicState *st, const double *part, int G, double tol)
+{
+    __shared__ double lds[8];
+    double v[2];
+    h_collapse<2>(v, part, HP_BB, G, lds);
+    if (threadIdx.x != 0) return;
+    const double bnorm = sqrt(v[0]);
+    st->rr0[0][0] = st->rr0[0][1] = 0.0;
+    st->rr0[1][0] = v[1];
+    st->rr0[1][1] = 0.0;
+    st->alpha[0] = st->alpha[1] = st->omega[0] = st->omega[1] = 0.0;
+    st->bnorm = bnorm;
+    st->tol = tol;
+    st->rnorm = sqrt(v[1]);
+    st->snorm = 0.0;
+    st->stop_s = INT_MAX;
+    st->stop_r = bnorm == 0.0 ? 0 : INT_MAX; // src/solvers.f90:23
+    st->restarts = 0;
+    st->pad_ = 0;
+}
+
+__global__ __launch_bounds__(EC3D_THREADS) void k_h_s(HarmonicState *st, int it, const cplx *__restrict__ r,
+                                                     const cplx *__restrict__ ap, cplx *__restrict__ sv, int64_t n,
+                                                     int64_t nchunk, double *__restrict__ part)
+{
+    __shared__ double lds[8];
+    if (st->stop_s != INT_MAX || st->stop_r != INT_MAX) return;
+    double d[2];
+    h_collapse<2>(d, part, HP_D1R, gridDim.x, lds);
+    const cplx alpha = cdiv(cplx{st->rr0[it & 1][0], st->rr0[it & 1][1]}, cplx{d[0], d[1]});
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        st->alpha[0] = alpha.x;
+        st->alpha[1] = alpha.y;
+    }
+    double acc[1] = {0.0};
+    for (int64_t ch = blockIdx.x; ch < nchunk; ch += gridDim.x)
+        for (int half = 0; half < 2; ++half) {
+            const int64_t i = h_row(ch, half);
+            if (i >= n) continue;
+            const cplx t = cmul(alpha, ap[i]), a = r[i], s = cplx{a.x - t.x, a.y - t.y};
+            sv[i] = s;
+            acc[0] = acc[0] + cabs2(s);
+        }
+    h_leave<1>(acc, part, HP_SS, lds);
+}
+
+__global__ __launch_bounds__(EC3D_THREADS) void k_h_xr(HarmonicState *st, int it, const cplx *__restrict__ p,
+                                                      const cplx *__restrict__ sv, const cplx *__restrict__ as,
+                                                      const cplx *__restrict__ r0, cplx *__restrict__ x,
+                                                      cplx *__restrict__ r, int64_t n, int64_t nchunk,
+                                                      double *__restrict__ part)
+{
+    __shared__ double lds[16];
+    if (st->stop_s < it || st->stop_r != INT_MAX) return;
+    double v[4]; // ||S||^2, <AS, S>, <AS, AS>
+    h_collapse<4>(v, part, HP_SS, gridDim.x, lds);
+    const double snorm = sqrt(v[0]);
+    const bool exit_s = snorm / st->bnorm < st->tol; // src/solvers.f90:34
+    const cplx alpha = {st->alpha[0], st->alpha[1]};
+    const bool first = blockIdx.x == 0 && threadIdx.x == 0;
+    if (exit_s) {
+        if (first) {
+            st->snorm = snorm;
+            st->stop_s = it;
+        }
+        for (int64_t ch = blockIdx.x; ch < nchunk; ch += gridDim.x)
+            for (int half = 0; half < 2; ++half) {
+                const int64_t i = h_row(ch, half);
+                if (i >= n) continue;
+                const cplx t = cmul(alpha, p[i]), a = x[i];
+                x[i] = cplx{a.x + t.x, a.y + t.y};
+            }
+        return;
+    }
+    const cplx omega = cdiv(cplx{v[1], v[2]}, cplx{v[3], 0.0});
+    if (first) {
+        st->snorm = snorm;
+        st->omega[0] = omega.x;
+        st->omega[1] = omega.y;
+    }
+    double acc[3] = {0.0, 0.0, 0.0};
+    for (int64_t ch = blockIdx.x; ch < nchunk; ch += gridDim.x)
+        for (int half = 0; half < 2; ++half) {
+            const int64_t i = h_row(ch, half);
+            if (i >= n) continue;
+            const cplx s = sv[i], t = cmul(alpha, p[i]), u = cmul(omega, s), w = cmul(omega, as[i]), a = x[i];
+            x[i] = cplx{(a.x + t.x) + u.x, (a.y + t.y) + u.y};
+            const cplx rn = {s.x - w.x, s.y - w.y};
+            r[i] = rn;
+            const cplx d = cdot(r0[i], rn);
+            acc[0] = acc[0] + cabs2(rn);
+            acc[1] = acc[1] + d.x;
+            acc[2] = acc[2] + d.y;
+        }
+    h_leave<3>(acc, part, HP_RR, lds);
+}
+
+__global__ __launch_bounds__(EC3D_THREADS) void k_h_p(HarmonicState *st, int it, const cplx *__restrict__ r,
+                                                     const cplx *__restrict__ ap, cplx *__restrict__ p,
+                                                     cplx *__restrict__ r0, int64_t n, int64_t nchunk,
+                                                     const double *__restrict__ part)
+{
+    __shared__ double lds[12];
+    if (st->stop_s != INT_MAX || st->stop_r < it) return;
+    double v[3]; // ||R||^2, <R0, R>
+    h_collapse<3>(v, part, HP_RR, gridDim.x, lds);
+    const double rnorm = sqrt(v[0]), bnorm = st->bnorm, tol = st->tol;
+    const bool first = blockIdx.x == 0 && threadIdx.x == 0;
+    if (rnorm / bnorm < tol) { // src/solvers.f90:43
+        if (first) {
+            st->rnorm = rnorm;
+            st->stop_r = it;
+        }
+        return;
+    }
+    const cplx alpha = {st->alpha[0], st->alpha[1]}, omega = {st->omega[0], st->omega[1]};
+    const cplx rr0n = {v[1], v[2]}, rr0 = {st->rr0[it & 1][0], st->rr0[it & 1][1]};
+    const cplx beta = cdiv(cmul(cdiv(alpha, omega), rr0n), rr0);              // :45
+    const bool restart = sqrt(rr0n.x * rr0n.x + rr0n.y * rr0n.y) / bnorm < tol; // :47
+    if (first) {
+        st->rnorm = rnorm;
+        st->rr0[(it + 1) & 1][0] = restart ? v[0] : rr0n.x; // after R0 = R the next <R0, R> is ||R||^2
+        st->rr0[(it + 1) & 1][1] = restart ? 0.0 : rr0n.y;
+        if (restart) st->restarts = st->restarts + 1;
+    }
+    for (int64_t ch = blockIdx.x; ch < nchunk; ch += gridDim.x)
+        for (int half = 0; half < 2; ++half) {
+            const int64_t i = h_row(ch, half);
+            if (i >= n) continue;
+            const cplx a = r[i];
+            if (restart) {
+                r0[i] = a;
+                p[i] = a;
+            } else {
+                const cplx w = cmul(omega, ap[i]), po = p[i], t = cmul(beta, cplx{po.x - w.x, po.y - w.y});
+                p[i] = cplx{a.x + t.x, a.y + t.y};
+            }
+        }
+}
+
+// host copies: (re plane, im plane) in device numbering <-> interleaved pairs; rows >= n of an uploaded vector are zero
+__global__ void k_h_pack(const double *__restrict__ re, const double *__restrict__ im, cplx *__restrict__ v, int64_t n, int64_t n_pad)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_pad) v[i] = i < n ? cplx{re[i], im[i]} : cplx{0.0, 0.0};
+}
+__global__ void k_h_unpack(const cplx *__restrict__ v, double *__restrict__ re, double *__restrict__ im, int64_t n)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) {
+        const cplx a = v[i];
+        re[i] = a.x;
+        im[i] = a.y;
+    }
+}
+
+// ec3d_harmonic_load: the part of x^ and b^ into the real X and B ...
+__global__ void k_h_load(const cplx *__restrict__ xh, const cplx *__restrict__ bh, int part, double *__restrict__ x,
+                         double *__restrict__ b, int64_t n)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const cplx a = xh[i], c = bh[i];
+    x[i] = part ? a.y : a.x;
+    b[i] = part ? c.y : c.x;
+}
+// ... B on the A rows of a conductor cell = the part of j (omega C) A^, omega C being the diagonal entry of the row's
+// class in the im table ...
+__global__ void k_h_load_eddy(const cplx *__restrict__ xh, const uint8_t *__restrict__ cls, const cplx *__restrict__ table,
+                              const int32_t *__restrict__ cond_cell, int64_t nc, int64_t nCd, int part, double *__restrict__ b)
+{
+    const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= nc) return;
+    const int64_t L = cond_cell[m];
+    for (int d = 0; d < 3; ++d) {
+        const int64_t q = d * nCd + L;
+        const double w = table[(int64_t)cls[q] * 16 + 3].y;
+        const cplx a = xh[q];
+        b[q] = part ? w * a.x : -(w * a.y);
+    }
+}
+// ... and both zeroed on the cel_bndX/Y/Z lists (src/EC3D.f90:426-432)
+__global__ void k_h_zero_list(const int32_t *list, int64_t cnt, double *x, double *b)
+{
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= cnt) return;
+    x[list[q]] = 0.0;
+    b[list[q]] = 0.0;
+}
+
+inline unsigned blocks(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + 255) / 256); }
+
+HSav view_of(const ec3d_ctx *c)
+{
+    const DevMatrix &A = c->A;
+    HSav T;
+    T.cls = A.cls;
+    T.table = reinterpret_cast<const cplx *>(c->harm.tab.get());
+    T.ncls = A.ncls;
+    T.a0 = A.sav_a0;
+    T.u0 = A.sav_u0;
+    T.zero = A.sav_zero;
+    T.n = A.n;
+    T.nC = A.sav_nC;
+    for (int b = 0; b < 7; ++b) T.off[b] = A.off[b];
+    for (int d = 0; d < 3; ++d) T.step[d] = A.sav_step[d];
+    return T;
+}
+
+cplx *hv(const ec3d_ctx *c, int w) { return reinterpret_cast<cplx *>(c->harm.vec[w]); }
+
+template <int MODE> void launch_spmv(ec3d_ctx *c, const cplx *x, const cplx *o, cplx *y, cplx *r0, cplx *p)
+{
+    const Harmonic &H = c->harm;
+    k_h_spmv<MODE><<<(unsigned)H.wgs, EC3D_THREADS, (size_t)c->A.ncls * 16 * sizeof(cplx), c->stream>>>(
+        view_of(c), H.state, x, o, y, r0, p, c->A.n_pad / EC3D_TILE, H.part);
+}
+
+// R = B^ - A X^, R0 = R, P = R and the state of a solve that has just begun
+void launch_begin(ec3d_ctx *c, double tol)
+{
+    const Harmonic &H = c->harm;
+    launch_spmv<3>(c, hv(c, HV_X), hv(c, HV_B), hv(c, HV_R), hv(c, HV_R0), hv(c, HV_P));
+    k_h_setup<<<1, EC3D_THREADS, 0, c->stream>>>(H.state, H.part, H.wgs, tol);
+}
+
+void launch_iteration(ec3d_ctx *c, int it)
+{
+    const Harmonic &H = c->harm;
+    const int64_t n = c->A.n, nc = c->A.n_pad / EC3D_TILE;
+    const unsigned G = (unsigned)H.wgs;
+    hipStream_t s = c->stream;
+    launch_spmv<1>(c, hv(c, HV_P), hv(c, HV_R0), hv(c, HV_AP), nullptr, nullptr);
+    k_h_s<<<G, EC3D_THREADS, 0, s>>>(H.state, it, hv(c, HV_R), hv(c, HV_AP), hv(c, HV_S), n, nc, H.part);
+    launch_spmv<2>(c, hv(c, HV_S), nullptr, hv(c, HV_AS), nullptr, nullptr);
+    k_h_xr<<<G, EC3D_THREADS, 0, s>>>(H.state, it, hv(c, HV_P), hv(c, HV_S), hv(c, HV_AS), hv(c, HV_R0), hv(c, HV_X),
+                                     hv(c, HV_R), n, nc, H.part);
+    k_h_p<<<G, EC3D_THREADS, 0, s>>>(H.state, it, hv(c, HV_R), hv(c, HV_AP), hv(c, HV_P), hv(c, HV_R0), n, nc, H.part);
+}
+
+// what every entry point refuses first; ready: ec3d_harmonic_setup must have run
+int h_need(ec3d_ctx *c, const char *who, bool ready)
+{
+    if (!c) {
+        ec3d_set_error(std::string(who) + ": null handle");
+        return 2;
+    }
+    int rc = ec3d_need_undivided(c, who);
+    if (rc) return rc;
+    if ((rc = ec3d_null_eligible(c, who, true))) return rc;
+    if (!c->harm.re || !c->harm.m) {
+        ec3d_set_error(std::string(who) + ": needs the A-V system [Ax|Ay|Az|U] from ec3d_assemble");
+        return 3;
+    }
+    if (ready && !c->harm.ready) {
+        ec3d_set_error(std::string(who) + ": call ec3d_harmonic_setup first");
+        return 2;
+    }
+    EC3D_HIP(hipSetDevice(c->device));
+    return 0;
+}
+
+int h_which(int which, const char *who)
+{
+    if (which == EC3D_VEC_X || which == EC3D_VEC_B) return 0;
+    ec3d_set_error(std::string(who) + ": which must be EC3D_VEC_X or EC3D_VEC_B");
+    return 2;
+}
+
+int h_to_device(ec3d_ctx *c, cplx *dst, const double *re, const double *im)
+{
+    Harmonic &H = c->harm;
+    const int64_t len = c->A.n_pad;
+    double *sre = H.stage, *sim = H.stage.get() + len;
+    int rc;
+    if ((rc = ec3d_vec_h2d(c, sre, re))) return rc;
+    if (im) {
+        if ((rc = ec3d_vec_h2d(c, sim, im))) return rc;
+    } else {
+        EC3D_HIP(hipMemsetAsync(sim, 0, (size_t)c->A.n * sizeof(double), c->stream));
+    }
+    k_h_pack<<<blocks(len), 256, 0, c->stream>>>(sre, sim, dst, c->A.n, len);
+    EC3D_HIP(hipGetLastError());
+    return 0;
+}
+
+int h_to_host(ec3d_ctx *c, const cplx *src, double *re, double *im)
+{
+    Harmonic &H = c->harm;
+    double *sre = H.stage, *sim = H.stage.get() + c->A.n_pad;
+    k_h_unpack<<<blocks(c->A.n), 256, 0, c->stream>>>(src, sre, sim, c->A.n);
+    EC3D_HIP(hipGetLastError());
+    int rc;
+    if (re && (rc = ec3d_vec_d2h(c, re, sre))) return rc;
+    if (im && (rc = ec3d_vec_d2h(c, im, sim))) return rc;
+    EC3D_HIP(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+} // namespace
+
+void ec3d_harmonic_free(ec3d_ctx *c)
+{
+    Harmonic &H = c->harm;
+    H.re.reset();
+    H.m.reset();
+    H.tab.reset();
+    H.vec_own.reset();
+    for (auto &v : H.vec) v = nullptr;
+    H.stage.reset();
+    H.part.reset();
+    H.state.reset();
+    H.ready = false;
+    H.omega = 0.0;
+    H.wgs = 0;
+    H.last = ec3d_harmonic_info{};
+}
+
+extern "C" int ec3d_harmonic_setup(ec3d_handle c, double omega)
+{
+    int rc = h_need(c, "ec3d_harmonic_setup", false);
+    if (rc) return rc;
+    if (!(omega >= 0.0) || !std::isfinite(omega)) {
+        ec3d_set_error("ec3d_harmonic_setup: omega must be finite and not negative");
+        return 2;
+    }
+    Harmonic &H = c->harm;
+    EC3D_HIP(hipStreamSynchronize(c->stream));
+    const size_t nt = (size_t)c->A.ncls * 16, len = (size_t)c->A.n_pad;
+    std::vector<double> re(nt), m(nt), tab(2 * nt);
+    EC3D_HIP(hipMemcpy(re.data(), H.re, nt * sizeof(double), hipMemcpyDeviceToHost));
+    EC3D_HIP(hipMemcpy(m.data(), H.m, nt * sizeof(double), hipMemcpyDeviceToHost));
+    for (size_t q = 0; q < nt; ++q) {
+        tab[2 * q] = re[q];
+        tab[2 * q + 1] = omega * m[q]; // one rounding per entry
+    }
+    if (!H.tab) EC3D_HIP(H.tab.alloc(2 * nt));
+    EC3D_HIP(hipMemcpy(H.tab, tab.data(), 2 * nt * sizeof(double), hipMemcpyHostToDevice));
+    if (!H.vec_own) { // the first set-up on this matrix: vectors (zero), staging, partials, state
+        H.wgs = ec3d_stream_wgs((int64_t)len);
+        EC3D_HIP(H.vec_own.alloc((size_t)HV_N * 2 * len));
+        EC3D_HIP(hipMemsetAsync(H.vec_own, 0, (size_t)HV_N * 2 * len * sizeof(double), c->stream));
+        for (int w = 0; w < HV_N; ++w) H.vec[w] = H.vec_own.get() + (size_t)w * 2 * len;
+        EC3D_HIP(H.stage.alloc(2 * len));
+        EC3D_HIP(hipMemsetAsync(H.stage, 0, 2 * len * sizeof(double), c->stream));
+        EC3D_HIP(H.part.alloc((size_t)HP_NSLOT * H.wgs));
+        EC3D_HIP(hipMemsetAsync(H.part, 0, (size_t)HP_NSLOT * H.wgs * sizeof(double), c->stream));
+        EC3D_HIP(H.state.alloc(1));
+        EC3D_HIP(hipMemsetAsync(H.state, 0, sizeof(HarmonicState), c->stream));
+        EC3D_HIP(hipStreamSynchronize(c->stream));
+    }
+    H.omega = omega;
+    H.ready = true;
+    H.last = ec3d_harmonic_info{};
+    H.last.ready = 1;
+    H.last.omega = omega;
+    H.last.device_bytes = (int64_t)(((size_t)HV_N * 2 * len + 2 * len + (size_t)HP_NSLOT * H.wgs + 2 * nt) * sizeof(double) +
+                                    sizeof(HarmonicState));
+    return 0;
+}
+
+extern "C" int ec3d_harmonic_upload(ec3d_handle c, int which, const double *re, const double *im)
+{
+    int rc = h_need(c, "ec3d_harmonic_upload", true);
+    if (rc) return rc;
+    if ((rc = h_which(which, "ec3d_harmonic_upload"))) return rc;
+    if (!re) {
+        ec3d_set_error("ec3d_harmonic_upload: re is NULL");
+        return 2;
+    }
+    if ((rc = h_to_device(c, hv(c, which == EC3D_VEC_X ? HV_X : HV_B), re, im))) return rc;
+    EC3D_HIP(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+extern "C" int ec3d_harmonic_download(ec3d_handle c, int which, double *re, double *im)
+{
+    int rc = h_need(c, "ec3d_harmonic_download", true);
+    if (rc) return rc;
+    if ((rc = h_which(which, "ec3d_harmonic_download"))) return rc;
+    if (!re || !im) {
+        ec3d_set_error("ec3d_harmonic_download: re or im is NULL");
+        return 2;
+    }
+    return h_to_host(c, hv(c, which == EC3D_VEC_X ? HV_X : HV_B), re, im);
+}
+
+extern "C" int ec3d_harmonic_spmv(ec3d_handle c, const double *xre, const double *xim, double *yre, double *yim)
+{
+    int rc = h_need(c, "ec3d_harmonic_spmv", true);
+    if (rc) return rc;
+    if (!yre || !yim || (xre && !xim)) {
+        ec3d_set_error("ec3d_harmonic_spmv: NULL argument");
+        return 2;
+    }
+    const cplx *x = hv(c, HV_X);
+    if (xre) {
+        if ((rc = h_to_device(c, hv(c, HV_P), xre, xim))) return rc;
+        x = hv(c, HV_P);
+    }
+    launch_spmv<0>(c, x, nullptr, hv(c, HV_AP), nullptr, nullptr);
+    EC3D_HIP(hipGetLastError());
+    return h_to_host(c, hv(c, HV_AP), yre, yim);
+}
+
+extern "C" int ec3d_harmonic_solve(ec3d_handle c, double tol, int32_t itmax, int32_t *iter, double *relres)
+{
+    int rc = h_need(c, "ec3d_harmonic_solve", true);
+    if (rc) return rc;
+    Harmonic &H = c->harm;
+    const auto t_start = std::chrono::steady_clock::now();
+    launch_begin(c, tol);
+    EC3D_HIP(hipGetLastError());
+    HarmonicState st;
+    const int64_t total = (int64_t)itmax + 1; // src/solvers.f90:25-29: itmax + 1 iterations
+    int64_t launched = 0;
+    bool stopped = false;
+    do {
+        const int64_t m = std::min<int64_t>(16, total - launched);
+        for (int64_t i = 0; i < m; ++i) launch_iteration(c, (int)(++launched));
+        EC3D_HIP(hipGetLastError());
+        EC3D_HIP(hipMemcpyAsync(&st, H.state, sizeof st, hipMemcpyDeviceToHost, c->stream));
+        EC3D_HIP(hipStreamSynchronize(c->stream));
+        stopped = st.stop_s != INT_MAX || st.stop_r != INT_MAX;
+    } while (launched < total && !stopped);
+    H.last.iter = stopped ? std::min(st.stop_s, st.stop_r) : (int32_t)std::max<int64_t>(total, 0);
+    H.last.restarts = st.restarts;
+    H.last.stop_kind = st.stop_s != INT_MAX ? 1 : (st.stop_r != INT_MAX && st.stop_r > 0 ? 2 : 0);
+    const double last_norm = H.last.stop_kind == 1 ? st.snorm : st.rnorm;
+    H.last.relres = st.bnorm > 0.0 ? last_norm / st.bnorm : 0.0;
+    H.last.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    if (iter) *iter = H.last.iter;
+    if (relres) *relres = H.last.relres;
+    return 0;
+}
+
+extern "C" int ec3d_harmonic_true_residual(ec3d_handle c, double *rel, double *bnorm)
+{
+    int rc = h_need(c, "ec3d_harmonic_true_residual", true);
+    if (rc) return rc;
+    if (!rel) {
+        ec3d_set_error("ec3d_harmonic_true_residual: rel is NULL");
+        return 2;
+    }
+    launch_begin(c, 0.0);
+    EC3D_HIP(hipGetLastError());
+    HarmonicState st;
+    EC3D_HIP(hipMemcpyAsync(&st, c->harm.state, sizeof st, hipMemcpyDeviceToHost, c->stream));
+    EC3D_HIP(hipStreamSynchronize(c->stream));
+    if (bnorm) *bnorm = st.bnorm;
+    *rel = st.bnorm > 0.0 ? st.rnorm / st.bnorm : st.rnorm;
+    return 0;
+}
+
+extern "C" int ec3d_harmonic_load(ec3d_handle c, int32_t part)
+{
+    int rc = h_need(c, "ec3d_harmonic_load", true);
+    if (rc) return rc;
+    if (part != 0 && part != 1) {
+        ec3d_set_error("ec3d_harmonic_load: part must be 0 (Re) or 1 (Im)");
+        return 2;
+    }
+    const Harmonic &H = c->harm;
+    double *x = c->vec[EC3D_VEC_X], *b = c->vec[EC3D_VEC_B];
+    hipStream_t s = c->stream;
+    k_h_load<<<blocks(c->A.n), 256, 0, s>>>(hv(c, HV_X), hv(c, HV_B), part, x, b, c->A.n);
+    if (c->n_cond) {
+        k_h_load_eddy<<<blocks(c->n_cond), 256, 0, s>>>(hv(c, HV_X), c->A.cls, reinterpret_cast<const cplx *>(H.tab.get()),
+                                                       c->cond_cell, c->n_cond, c->nCd, part, b);
+        const int64_t cnt = c->bnd_off[3];
+        if (cnt) k_h_zero_list<<<blocks(cnt), 256, 0, s>>>(c->bnd_list, cnt, x, b);
+    }
+    EC3D_HIP(hipGetLastError());
+    EC3D_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
+extern "C" int ec3d_get_harmonic(ec3d_handle c, ec3d_harmonic_info *out)
+{
+    if (!c || !out) {
+        ec3d_set_error("ec3d_get_harmonic: null handle or info");
+        return 2;
+    }
+    *out = c->harm.last;
+    out->ready = c->harm.ready ? 1 : 0;
+    out->omega = c->harm.omega;
+    return 0;
+}
+
+extern "C" int ec3d_harmonic_device_vector(ec3d_handle c, int which, double **device_ptr, int64_t *pairs)
+{
+    int rc = h_need(c, "ec3d_harmonic_device_vector", true);
+    if (rc) return rc;
+    if (which < 0 || which >= HV_N || !device_ptr || !pairs) {
+        ec3d_set_error("ec3d_harmonic_device_vector: unknown vector or NULL argument");
+        return 2;
+    }
+    *device_ptr = c->harm.vec[which];
+    *pairs = c->A.n_pad;
+    return 0;
+}

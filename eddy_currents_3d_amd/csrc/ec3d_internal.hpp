@@ -417,6 +417,26 @@ struct NullProjection {
     double hierarchy_ms = 0.0;
 };
 
+// ec3d_harmonic_* (ec3d_harmonic.hip): the time-harmonic operator K + j omega M on the class bytes
+// of the structured A-V form.  re and m are made by every ec3d_assemble (k_build_table_harmonic beside
+// k_build_table_sav: the transient table without its dt terms, and the unit imaginary table); everything else by
+// ec3d_harmonic_setup only.  Belongs to the matrix (ec3d_free_matrix).
+enum { HV_X = 0, HV_B, HV_R, HV_R0, HV_P, HV_AP, HV_S, HV_AS, HV_N };
+struct HarmonicState; // the solve's scalars and exit words on the device (ec3d_harmonic.hip)
+struct Harmonic {
+    DevBuf<double> re, m;   // [ncls * 16] each
+    bool ready = false;     // ec3d_harmonic_setup ran on this matrix
+    double omega = 0.0;
+    DevBuf<double> tab;     // [ncls * 16] (re, omega * m) pairs: what k_h_spmv holds in LDS
+    DevBuf<double> vec_own; // HV_N vectors of n_pad (re, im) pairs, device numbering, no ghosts
+    double *vec[HV_N] = {nullptr};
+    DevBuf<double> stage;   // [2 * n_pad] a real and an imaginary part in device numbering (host copies)
+    DevBuf<double> part;    // [HP_NSLOT * wgs] per-workgroup partial sums
+    DevBuf<HarmonicState> state;
+    int wgs = 0;
+    ec3d_harmonic_info last{};
+};
+
 struct ec3d_ctx {
     int device = 0;
     hipStream_t stream = nullptr;         // the stream every launch goes to
@@ -582,6 +602,7 @@ struct ec3d_ctx {
     int precond_coarsening = 0; // EC3D_COARSEN_REDISCRETIZE / _AGGREGATE: likewise (ec3d_set_precond_coarsening)
     GuessHistory guess;
     NullProjection nullp;
+    Harmonic harm;
     ec3d_ctx() = default;
     ~ec3d_ctx(); // ec3d_context.hip: the hierarchy goes (ec3d_mg_free), then every owner above, last declared first
 };
@@ -842,6 +863,8 @@ int ec3d_null_eligible(const ec3d_ctx *c, const char *who, bool set_text); // 0,
 int ec3d_null_prepare(ec3d_ctx *c);               // in front of the solve: builds Q when there is none
 int ec3d_null_project(ec3d_ctx *c);               // behind the residual launch of ec3d_launch_begin, before its set-up
 int ec3d_null_note(ec3d_ctx *c, double bnorm);    // behind the solve: `removed` of ec3d_get_null_projection
+// ec3d_harmonic.hip
+void ec3d_harmonic_free(ec3d_ctx *c); // the tables, vectors and setting of ec3d_harmonic_setup go (a new matrix)
 // ec3d_output.hip
 void ec3d_free_output(ec3d_ctx *c);
 // ec3d_rhs.hip

@@ -30,7 +30,9 @@ module ec3d_hip
               ec3d_spmv_t, ec3d_set_null_projection, ec3d_get_null_projection, ec3d_left_null_vector, ec3d_null_info, &
               EC3D_NULL_MAX_REPORT, EC3D_NULL_E_MATRIX, EC3D_NULL_E_SETUP, &
               ec3d_set_probes, ec3d_probe_sample, ec3d_probe_record, ec3d_probe_read, ec3d_probe_reset, ec3d_get_probes, &
-              ec3d_probe_info, EC3D_PROBE_NCOMP, EC3D_PROBE_E_FULL
+              ec3d_probe_info, EC3D_PROBE_NCOMP, EC3D_PROBE_E_FULL, &
+              ec3d_harmonic_setup, ec3d_harmonic_upload, ec3d_harmonic_download, ec3d_harmonic_spmv, ec3d_harmonic_solve, &
+              ec3d_harmonic_true_residual, ec3d_harmonic_load, ec3d_get_harmonic, ec3d_harmonic_info
 
     integer(c_int), parameter :: EC3D_VEC_X = 0, EC3D_VEC_B = 1   ! Uaf, Jaf
     integer(c_int), parameter :: EC3D_PRECOND_NONE = 0, EC3D_PRECOND_MG = 1   ! ec3d_set_preconditioner
@@ -85,6 +87,13 @@ module ec3d_hip
     ! what ec3d_get_probes reports (ec3d_probe_info of include/ec3d_hip.h)
     type, bind(C) :: ec3d_probe_info
         integer(c_int64_t) :: nprobes, capacity, recorded, device_bytes
+    end type
+
+    ! what ec3d_get_harmonic reports (ec3d_harmonic_info of include/ec3d_hip.h)
+    type, bind(C) :: ec3d_harmonic_info
+        integer(c_int32_t) :: ready, iter, restarts, stop_kind
+        real(c_double) :: omega, relres, ms
+        integer(c_int64_t) :: device_bytes
     end type
 
     interface
@@ -384,6 +393,57 @@ module ec3d_hip
             type(c_ptr), value :: h
             integer(c_int32_t), value :: index
             real(c_double), intent(out) :: w(*)
+        end function
+        ! Time-harmonic solve (K + j omega M) x^ = b^ on the A-V system of ec3d_assemble (include/ec3d_hip.h; opt-in):
+        ! set-up at omega [rad/s]; host vectors as separate real and imaginary parts, n doubles each, the reference's numbering
+        integer(c_int) function ec3d_harmonic_setup(h, omega) bind(C, name="ec3d_harmonic_setup")
+            import :: c_ptr, c_int, c_double
+            type(c_ptr), value :: h
+            real(c_double), value :: omega
+        end function
+        ! which: EC3D_VEC_X or EC3D_VEC_B
+        integer(c_int) function ec3d_harmonic_upload(h, which, re, im) bind(C, name="ec3d_harmonic_upload")
+            import :: c_ptr, c_int, c_double
+            type(c_ptr), value :: h
+            integer(c_int), value :: which
+            real(c_double), intent(in) :: re(*), im(*)
+        end function
+        integer(c_int) function ec3d_harmonic_download(h, which, re, im) bind(C, name="ec3d_harmonic_download")
+            import :: c_ptr, c_int, c_double
+            type(c_ptr), value :: h
+            integer(c_int), value :: which
+            real(c_double), intent(out) :: re(*), im(*)
+        end function
+        integer(c_int) function ec3d_harmonic_spmv(h, xre, xim, yre, yim) bind(C, name="ec3d_harmonic_spmv")
+            import :: c_ptr, c_int, c_double
+            type(c_ptr), value :: h
+            real(c_double), intent(in) :: xre(*), xim(*)
+            real(c_double), intent(out) :: yre(*), yim(*)
+        end function
+        ! complex BiCGSTAB with restart from the resident x^; iter as ec3d_solve reports it
+        integer(c_int) function ec3d_harmonic_solve(h, tol, itmax, iter, relres) bind(C, name="ec3d_harmonic_solve")
+            import :: c_ptr, c_int, c_int32_t, c_double
+            type(c_ptr), value :: h
+            real(c_double), value :: tol
+            integer(c_int32_t), value :: itmax
+            integer(c_int32_t), intent(out) :: iter
+            real(c_double), intent(out) :: relres
+        end function
+        integer(c_int) function ec3d_harmonic_true_residual(h, rel, bnorm) bind(C, name="ec3d_harmonic_true_residual")
+            import :: c_ptr, c_int, c_double
+            type(c_ptr), value :: h
+            real(c_double), intent(out) :: rel, bnorm
+        end function
+        ! part 0 / 1: Re / Im of the phasor into the real X and B; the observables of the resident fields then return it
+        integer(c_int) function ec3d_harmonic_load(h, part) bind(C, name="ec3d_harmonic_load")
+            import :: c_ptr, c_int, c_int32_t
+            type(c_ptr), value :: h
+            integer(c_int32_t), value :: part
+        end function
+        integer(c_int) function ec3d_get_harmonic(h, info) bind(C, name="ec3d_get_harmonic")
+            import :: c_ptr, c_int, ec3d_harmonic_info
+            type(c_ptr), value :: h
+            type(ec3d_harmonic_info), intent(out) :: info
         end function
         ! U rows ec3d_rhs_step gives their right-hand side with several conducting domains (include/ec3d_hip.h)
         integer(c_int) function ec3d_set_u_rhs(h, rule) bind(C, name="ec3d_set_u_rhs")

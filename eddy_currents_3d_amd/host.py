@@ -444,6 +444,85 @@ def run(model: vxc.VxcModel, solver, steps: int | None = None, out_dir: str | No
     return log
 
 
+HARMONIC_SAMPLES = 64
+
+
+def source_phasor(f, freq: float) -> complex:
+    """The phasor of one source function at ``freq``: (2 / 64) sum f(T_n) exp(-j omega T_n) over T_n = n / (64 freq),
+    n = 0 .. 63 -- a for a cos(omega t), -j a for a sin(omega t) (convention x(t) = Re(x^ exp(j omega t)))."""
+    N = HARMONIC_SAMPLES
+    T = np.arange(N) / (N * float(freq))
+    v = np.array([f.value(float(t)) for t in T], np.float64)
+    return complex((2.0 / N) * np.sum(v * np.exp(-2j * np.pi * float(freq) * T)))
+
+
+def harmonic_rhs(prog: SourceProgram, freq: float, n: int) -> np.ndarray:
+    """b^ of the model's sources at ``freq`` (complex, reference numbering): every function's phasor times MU0 at the
+    function's cells, a repeated cell keeping its last value as in the time loop.  ValueError on moving sources."""
+    if prog.moving:
+        raise ValueError("the model's sources move (Vsx / Vsy / Vsz): there is no periodic steady state at one frequency "
+                         "for the harmonic solve to find; run the time loop")
+    b = np.zeros(n, np.complex128)
+    for f in prog.funs:
+        b[f["nodes"] + f["axis"] * prog.ncells - 1] = source_phasor(f["f"], freq) * MU0
+    return b
+
+
+def run_harmonic(model: vxc.VxcModel, solver, freq: float, tol: float | None = None, itmax: int | None = None,
+                 out_dir: str | None = None, integrals: bool = False, probes=None):
+    """The periodic steady state of ``model`` at ``freq`` [Hz] by one complex solve (K + j omega M) x^ = b^ on ``solver``
+    (an EC3DSolver) instead of a time loop run until its start-up transient has died away:
+    assemble, harmonic_setup(2 pi freq), b^ from the model's sources (harmonic_rhs), harmonic_solve from x^ = 0 at the
+    model's tolerance and iteration limit (or ``tol`` / ``itmax``).  Returns dict(freq, omega, iter, relres,
+    true_residual, bnorm, x (complex, reference numbering), b, parts): parts[0] / parts[1] belong to Re / Im of the phasor,
+    each loaded into the resident real X and B (harmonic_load) for the observables asked for -- ``integrals``:
+    parts[p]["integrals"] = solver.domain_integrals(delta) and, in the result, "integrals": per conducting domain
+    half the sum of the two parts' Joule loss and force, the averages over a period; ``probes`` (cell numbers): "probes",
+    the complex (nprobes, 13) sample; ``out_dir``: harmonic_re.vtk and harmonic_im.vtk in the layout of field_N.vtk.
+    The fields at time t are Re(part0 + j part1) exp(j omega t) = part0 cos(omega t) - part1 sin(omega t)."""
+    if not hasattr(solver, "harmonic_setup"):
+        raise ValueError("run_harmonic needs an EC3DSolver: the harmonic solve runs on one undivided handle")
+    t = vxc.domain_tables(model)
+    if t["dt"] is None:
+        raise ValueError("the model has no 'tran stop=... step=...' line")
+    prog = SourceProgram(model, t)
+    n_ref = 3 * model.vox.size + t["ncells0"]
+    b = harmonic_rhs(prog, freq, n_ref)       # (refuses moving sources before anything is assembled)
+    omega = 2.0 * math.pi * float(freq)
+    solver.assemble(t["geoPHYS"], t["geoPHYS_C"], t["valPHYS"], t["BND"], t["delta"], t["dt"])
+    solver.harmonic_setup(omega)
+    solver.harmonic_upload("B", b)
+    solver.harmonic_upload("X", np.zeros(n_ref))
+    it, relres = solver.harmonic_solve(float(t["tol"] if tol is None else tol), int(t["itmax"] if itmax is None else itmax))
+    true_res, bnorm = solver.harmonic_true_residual()
+    out = dict(freq=float(freq), omega=omega, iter=it, relres=relres, true_residual=true_res, bnorm=bnorm,
+               x=solver.harmonic_download("X"), b=b, parts=[{}, {}], info=solver.harmonic_info())
+    sdz, sdy, sdx = model.vox.shape
+    if probes is not None:
+        from .probes import stack
+        solver.set_probes(probes, 0)
+    if out_dir:
+        os.makedirs(out_dir, exist_ok=True)
+    for part, name in enumerate(("re", "im")):
+        solver.harmonic_load(part)
+        rec = out["parts"][part]
+        if integrals:
+            rec["integrals"] = solver.domain_integrals(t["delta"])
+        if probes is not None:
+            rec["probes"] = stack(solver.probe_sample(t["delta"]))
+        if out_dir:
+            f = solver.vtk_fields(t["delta"], sdx * sdy * sdz, t["ncells0"] > 0)
+            rec["vtk"] = os.path.join(out_dir, f"harmonic_{name}.vtk")
+            write_field_vtk(rec["vtk"], sdx, sdy, sdz, t["delta"], f)
+    if integrals:
+        out["integrals"] = [dict(domain=a["domain"], cells=a["cells"], sigma=a["sigma"],
+                                 joule_w=0.5 * (a["joule_w"] + c["joule_w"]), force_n=0.5 * (a["force_n"] + c["force_n"]))
+                            for a, c in zip(out["parts"][0]["integrals"], out["parts"][1]["integrals"])]
+    if probes is not None:
+        out["probes"] = out["parts"][0]["probes"] + 1j * out["parts"][1]["probes"]
+    return out
+
+
 class _ProbeLog:
     """The probes of a run: one ec3d_probe_record per step, the record read (one copy) whenever it is full and at the
     end; every step's (nprobes, 13) array goes into that step's info then."""

@@ -4,6 +4,7 @@
                                                  [--energy FILE] [--null-projection [--null-tol Y]] [--tol X]
                                                  [--probes FILE [--probe I,J,K]... [--probe-line I0,J0,K0:I1,J1,K1]...
                                                   [--probe-box I0,J0,K0:I1,J1,K1]...]
+    python -m eddy_currents_3d_amd.run model.vxc --harmonic FREQ [--out DIR] [--integrals FILE] [--tol X]
     python -m torch.distributed.run --nproc-per-node G -m eddy_currents_3d_amd.run model.vxc ...   (G GPUs)
 
 Reads the file (eddy_currents_3d_amd/vxc.py), assembles the A-V system on the device, and runs the
@@ -18,7 +19,9 @@ null vectors of the A-V system out of every solve's initial residual (EC3DSolver
 lets ``--tol X`` -- the solves' tolerance instead of the model's -- go below the reference's.  ``--probes FILE``: A, the
 eddy and source current densities, B and U at chosen cells (0-based I,J,K: points, lines, boxes; a plane is a box one cell
 thick) after every step, in float64, as CSV, one line per step and probe; they are recorded on the device and written
-after the run (one GPU only).
+after the run (one GPU only).  ``--harmonic FREQ``: no time loop -- the periodic steady state at FREQ [Hz] by one complex
+solve (host.run_harmonic): ``harmonic_re.vtk`` and ``harmonic_im.vtk`` go to ``--out``, ``--integrals FILE`` gets the Joule
+loss and force of every conducting domain averaged over a period (one GPU only; moving sources are refused).
 """
 from __future__ import annotations
 
@@ -96,7 +99,37 @@ def build_parser():
                     help="probes at every cell of the box with these inclusive corners, in scan order (repeatable)")
     ap.add_argument("--tol", type=float, default=None, metavar="X",
                     help="tolerance of the time step's solve instead of the model's (one GPU only)")
+    ap.add_argument("--harmonic", type=float, default=None, metavar="FREQ",
+                    help="instead of the time loop: one complex solve for the periodic steady state at FREQ Hz; writes "
+                         "harmonic_re.vtk / harmonic_im.vtk to --out and the period averages to --integrals (one GPU only)")
     return ap
+
+
+HARMONIC_INTEGRALS_HEADER = "freq,domain,cells,joule_w_avg,force_x_avg,force_y_avg,force_z_avg"
+
+
+def run_harmonic_cli(ap, a, model, t, out_dir):
+    """--harmonic FREQ: host.run_harmonic and its report."""
+    from . import EC3DSolver, host
+    if not a.harmonic > 0.0:
+        ap.error("--harmonic needs a frequency above 0")
+    t0 = time.perf_counter()
+    with EC3DSolver(device=a.device) as s:
+        try:
+            r = host.run_harmonic(model, s, a.harmonic, tol=a.tol, out_dir=out_dir, integrals=bool(a.integrals))
+        except ValueError as e:
+            ap.error(str(e))
+    if a.integrals:
+        with open(a.integrals, "w") as f:
+            f.write(HARMONIC_INTEGRALS_HEADER + "\n")
+            for q in r["integrals"]:
+                f.write(",".join([repr(float(a.harmonic)), str(q["domain"]), str(q["cells"]), repr(float(q["joule_w"]))]
+                                 + [repr(float(v)) for v in q["force_n"]]) + "\n")
+    print(f"harmonic solve at {a.harmonic:g} Hz: iter={r['iter']} relres={r['relres']:.3e} "
+          f"true residual={r['true_residual']:.3e} restarts={r['info']['restarts']} "
+          f"({r['info']['ms']:.1f} ms in the solve, {time.perf_counter() - t0:.2f} s wall)"
+          + (f"  -> {out_dir}/harmonic_re.vtk, harmonic_im.vtk" if out_dir else ""), flush=True)
+    return 0
 
 
 def check_probe_options(ap, a, world):
@@ -129,6 +162,10 @@ def main(argv=None):
     out_dir = None if a.no_output else (a.out or str(t["directory"]).upper())
     print(f"{a.model}: grid {sdx}x{sdy}x{sdz}, {t['ncells0']} conducting cells, dt={t['dt']:g} stop={t['time']:g} "
           f"tol={t['tol']:g} itmax={t['itmax']}", flush=True)
+    if a.harmonic is not None:
+        if world > 1:
+            ap.error("--harmonic runs on one GPU only; the complex solve has no z-slab form")
+        return run_harmonic_cli(ap, a, model, t, out_dir)
     pcells = None
     if a.probes:
         from . import probes as P

@@ -78,6 +78,12 @@ class NullInfo(C.Structure):
                 ("was_kept", C.c_int32 * 32), ("residual", C.c_double * 32)]
 
 
+class HarmonicInfo(C.Structure):
+    """ec3d_harmonic_info of include/ec3d_hip.h."""
+    _fields_ = [("ready", C.c_int32), ("iter", C.c_int32), ("restarts", C.c_int32), ("stop_kind", C.c_int32),
+                ("omega", C.c_double), ("relres", C.c_double), ("ms", C.c_double), ("device_bytes", C.c_int64)]
+
+
 class CsrProbe(C.Structure):
     _fields_ = [("structured", C.c_int32), ("sdx", C.c_int32), ("sdy", C.c_int32), ("sdz", C.c_int32),
                 ("n_cond", C.c_int32), ("classes", C.c_int32), ("plane_pitch", C.c_int32)]
@@ -113,7 +119,10 @@ EXPORTS = ["sprsbcgstabwr_", "ec3d_invalidate", "ec3d_create", "ec3d_destroy", "
            "ec3d_spmv_t", "ec3d_set_null_projection", "ec3d_get_null_projection", "ec3d_left_null_vector",
            "ec3d_set_null_precond", "ec3d_get_null_precond", "ec3d_null_precond_apply",
            "ec3d_set_probes", "ec3d_probe_sample", "ec3d_probe_record", "ec3d_probe_read", "ec3d_probe_reset",
-           "ec3d_get_probes"]
+           "ec3d_get_probes",
+           "ec3d_harmonic_setup", "ec3d_harmonic_upload", "ec3d_harmonic_download", "ec3d_harmonic_spmv",
+           "ec3d_harmonic_solve", "ec3d_harmonic_true_residual", "ec3d_harmonic_load", "ec3d_get_harmonic",
+           "ec3d_harmonic_device_vector"]
 PROBE_NCOMP = 13     # EC3D_PROBE_NCOMP of include/ec3d_hip.h: a[3], eddy[3], source[3], b[3], u
 PROBE_E_FULL = 24    # EC3D_PROBE_E_FULL: ec3d_probe_record on a full buffer
 U_RHS = {"reference": 0, "all": 1}   # EC3D_U_RHS_* of include/ec3d_hip.h
@@ -242,6 +251,15 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.ec3d_probe_read.argtypes = [hp, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
     L.ec3d_probe_reset.argtypes = [hp]
     L.ec3d_get_probes.argtypes = [hp, C.POINTER(ProbeInfo)]
+    L.ec3d_harmonic_setup.argtypes = [hp, C.c_double]
+    L.ec3d_harmonic_upload.argtypes = [hp, C.c_int, C.c_void_p, C.c_void_p]
+    L.ec3d_harmonic_download.argtypes = [hp, C.c_int, _f64, _f64]
+    L.ec3d_harmonic_spmv.argtypes = [hp, C.c_void_p, C.c_void_p, _f64, _f64]
+    L.ec3d_harmonic_solve.argtypes = [hp, C.c_double, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double)]
+    L.ec3d_harmonic_true_residual.argtypes = [hp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.ec3d_harmonic_load.argtypes = [hp, C.c_int32]
+    L.ec3d_get_harmonic.argtypes = [hp, C.POINTER(HarmonicInfo)]
+    L.ec3d_harmonic_device_vector.argtypes = [hp, C.c_int, C.POINTER(hp), C.POINTER(C.c_int64)]
     L.ec3d_vtk_fields_wait.argtypes = [hp, C.c_int32] + [C.POINTER(C.POINTER(C.c_float))] * 4 + [C.POINTER(C.c_int64)]
     L.ec3d_set_workgroups.argtypes = [hp, C.c_int32]
     L.ec3d_get_matrix_info.argtypes = [hp, C.POINTER(MatrixInfo)]
@@ -737,6 +755,79 @@ class EC3DSolver:
         y = np.empty(self.n)
         _chk(self.L, self.L.ec3d_spmv_t(self.h, np.ascontiguousarray(x, np.float64), y), "ec3d_spmv_t")
         return y
+
+    # ---- time-harmonic solve (ec3d_harmonic_*) ---------------------------
+    @staticmethod
+    def _parts(z, n):
+        z = np.asarray(z)
+        if z.shape != (n,):
+            raise ValueError(f"expected a vector of {n} entries, got shape {z.shape}")
+        return np.ascontiguousarray(z.real, np.float64), np.ascontiguousarray(z.imag, np.float64)
+
+    @staticmethod
+    def _complex(re, im):
+        z = np.empty(len(re), np.complex128)     # (re + 1j * im would turn a -0.0 into +0.0)
+        z.real, z.imag = re, im
+        return z
+
+    def harmonic_setup(self, omega: float):
+        """The operator K + j omega M on this handle's A-V system and, on the first call, the complex work vectors
+        (ec3d_harmonic_setup).  EC3DError with .status 3 / 5 / NULL_E_MATRIX on a handle that has no undivided
+        structured A-V system, 2 for a negative or non-finite omega."""
+        _chk(self.L, self.L.ec3d_harmonic_setup(self.h, float(omega)), "ec3d_harmonic_setup")
+
+    def harmonic_upload(self, which: str, z):
+        """X^ or B^ from a complex (or real) vector in the reference numbering."""
+        re, im = self._parts(z, self.n)
+        _chk(self.L, self.L.ec3d_harmonic_upload(self.h, VEC[which], re.ctypes.data, im.ctypes.data), "ec3d_harmonic_upload")
+
+    def harmonic_download(self, which: str):
+        re, im = np.empty(self.n), np.empty(self.n)
+        _chk(self.L, self.L.ec3d_harmonic_download(self.h, VEC[which], re, im), "ec3d_harmonic_download")
+        return self._complex(re, im)
+
+    def harmonic_spmv(self, x=None):
+        """(K + j omega M) x; x = None: the resident X^."""
+        yre, yim = np.empty(self.n), np.empty(self.n)
+        if x is None:
+            rc = self.L.ec3d_harmonic_spmv(self.h, None, None, yre, yim)
+        else:
+            re, im = self._parts(x, self.n)
+            rc = self.L.ec3d_harmonic_spmv(self.h, re.ctypes.data, im.ctypes.data, yre, yim)
+        _chk(self.L, rc, "ec3d_harmonic_spmv")
+        return self._complex(yre, yim)
+
+    def harmonic_solve(self, tolerance: float, itmax: int):
+        """Complex BiCGSTAB with restart from the resident X^ (src/solvers.f90:3-50).  Returns (iter, relres)."""
+        it, rr = C.c_int32(0), C.c_double(0)
+        _chk(self.L, self.L.ec3d_harmonic_solve(self.h, float(tolerance), int(itmax), C.byref(it), C.byref(rr)),
+             "ec3d_harmonic_solve")
+        return it.value, rr.value
+
+    def harmonic_true_residual(self):
+        """(||b^ - A x^|| / ||b^||, ||b^||) of the resident complex vectors."""
+        rel, bn = C.c_double(0), C.c_double(0)
+        _chk(self.L, self.L.ec3d_harmonic_true_residual(self.h, C.byref(rel), C.byref(bn)), "ec3d_harmonic_true_residual")
+        return rel.value, bn.value
+
+    def harmonic_load(self, part: int):
+        """Re (0) or Im (1) of the phasor into the real X and B: every observable of the resident fields then returns
+        that part's (ec3d_harmonic_load)."""
+        _chk(self.L, self.L.ec3d_harmonic_load(self.h, int(part)), "ec3d_harmonic_load")
+
+    def harmonic_info(self):
+        """dict(ready, omega, iter, restarts, stop_kind, relres, ms, device_bytes) (ec3d_get_harmonic)."""
+        r = HarmonicInfo()
+        _chk(self.L, self.L.ec3d_get_harmonic(self.h, C.byref(r)), "ec3d_get_harmonic")
+        return dict(ready=bool(r.ready), omega=float(r.omega), iter=int(r.iter), restarts=int(r.restarts),
+                    stop_kind=int(r.stop_kind), relres=float(r.relres), ms=float(r.ms), device_bytes=int(r.device_bytes))
+
+    def harmonic_device_vector(self, which: str):
+        """(device address, n_pad) of a complex work vector: interleaved (re, im) pairs in device numbering."""
+        p, n = C.c_void_p(), C.c_int64(0)
+        _chk(self.L, self.L.ec3d_harmonic_device_vector(self.h, VEC[which], C.byref(p), C.byref(n)),
+             "ec3d_harmonic_device_vector")
+        return p.value, n.value
 
     def set_u_rhs(self, rule: str = "reference"):
         """Which U rows rhs_step gives their right-hand side with several conducting domains: "reference" (default)

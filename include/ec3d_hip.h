@@ -853,6 +853,56 @@ void ec3d_format_real8(double v, char *buf);
  * library print the itmax line that way (default: flang's, above); this is the formatter.  buf >= 40 bytes. */
 void ec3d_format_real8_gfortran(double v, char *buf);
 
+/* ---- Time-harmonic A-V solve (opt-in) ------------------------------------------------------
+ * One complex solve (K + j omega M) x^ = b^ per frequency gives the periodic steady state that the time loop reaches
+ * after its start-up transient; convention x(t) = Re(x^ e^{j omega t}).  The operator lives on the class bytes of the
+ * structured A-V form: re[cls][slot] is the table of ec3d_assemble with every dt term left out (conductor velocity
+ * terms stay), m[cls][slot] the unit imaginary table -- C = mu0 sigma on the diagonal of a conducting A row,
+ * 0.5 (+-1 / delta_d) or +-2 / delta_d in the A_d slots of a U row -- and im = omega * m, one rounding per entry; the
+ * transient table is re + im * 2 / (omega dt) in A rows and re + im / (omega dt) in U rows.  Both tables are made by
+ * every ec3d_assemble; the eight complex work vectors (X^, B^, R, R0, P, AP, S, AS: n_pad interleaved (re, im) pairs each,
+ * plus one of staging) by ec3d_harmonic_setup only.  Nothing of the real solve -- its vectors, kernels, defaults, bits --
+ * is touched before ec3d_harmonic_load.
+ * Arithmetic (no contraction, no float atomics; tests/harmonic_numpy.py restates it bit for bit): a product a x is
+ * (ar xr - ai xi, ar xi + ai xr), every product and sum rounded on its own; a row adds its terms from +0.0 in ascending
+ * column and skips a term whose two coefficients are 0; <a, b> = sum conj(a) b with the row term (ar br + ai bi,
+ * ar bi - ai br), each part a fixed-order sum; a / b = ((ar br + ai bi) / d, (ai br - ar bi) / d), d = br br + bi bi.
+ * The iteration is src/solvers.f90:3-50 in this arithmetic: the ||b^|| = 0 return, the ||S|| and ||R|| exits, itmax + 1
+ * iterations at most, the restart R0 = R, P = R when |rr0_new| / ||b^|| < tol.
+ * Refusals: 3 without an A-V system of ec3d_assemble, 5 on a z-slab or a slab of ec3d_multi, EC3D_NULL_E_MATRIX on a
+ * bands + tail or CSR handle, 2 for a negative or non-finite omega, a NULL argument, or a call before
+ * ec3d_harmonic_setup.  Host vectors are in the reference numbering, length n. */
+typedef struct {
+    int32_t ready;      /* ec3d_harmonic_setup ran on this matrix                                   */
+    int32_t iter;       /* of the last ec3d_harmonic_solve (itmax + 1: no exit)                     */
+    int32_t restarts;   /* times R0 = R, P = R fired in it                                          */
+    int32_t stop_kind;  /* 1: the ||S|| exit, 2: the ||R|| exit, 0: none, or ||b^|| = 0             */
+    double omega;
+    double relres;      /* ||R|| / ||b^|| of the recurrence at the exit (||S|| / ||b^|| at an ||S|| exit) */
+    double ms;          /* wall time of the last solve                                              */
+    int64_t device_bytes; /* what ec3d_harmonic_setup allocated                                     */
+} ec3d_harmonic_info;
+int ec3d_harmonic_setup(ec3d_handle h, double omega);
+/* which: EC3D_VEC_X or EC3D_VEC_B; im == NULL on upload: a real phasor */
+int ec3d_harmonic_upload(ec3d_handle h, int which, const double *re, const double *im);
+int ec3d_harmonic_download(ec3d_handle h, int which, double *re, double *im);
+/* y = (K + j omega M) x.  Uses P and AP of the complex vectors as scratch; xre == NULL: x is the resident X^ */
+int ec3d_harmonic_spmv(ec3d_handle h, const double *xre, const double *xim, double *yre, double *yim);
+/* from the resident X^; *iter as ec3d_solve reports it, *relres as in ec3d_harmonic_info (either may be NULL) */
+int ec3d_harmonic_solve(ec3d_handle h, double tol, int32_t itmax, int32_t *iter, double *relres);
+/* ||b^ - A x^|| / ||b^|| of the resident vectors (the absolute norm when ||b^|| = 0); overwrites R, R0, P */
+int ec3d_harmonic_true_residual(ec3d_handle h, double *rel, double *bnorm);
+/* part 0: Re, 1: Im of the phasor into the handle's REAL X and B, after which every observable of the resident
+ * fields (ec3d_vtk_fields, probes, ec3d_domain_integrals, ec3d_field_energy, ec3d_domain_linkage) returns that part's:
+ * X = the part of x^; B = the part of j omega C A^ on the A rows of conductor cells (-omega C Im A^ / omega C Re A^,
+ * omega C being the im table's diagonal entry), the part of b^ elsewhere; both zeroed on the cel_bndX/Y/Z lists as
+ * ec3d_post_update zeroes them.  x^ and b^ stay resident. */
+int ec3d_harmonic_load(ec3d_handle h, int32_t part);
+int ec3d_get_harmonic(ec3d_handle h, ec3d_harmonic_info *out); /* (a function cannot share the struct's name in C) */
+/* tests and device-side callers: complex vector `which` (EC3D_VEC_X ... EC3D_VEC_AS) as the kernels hold it, *pairs =
+ * n_pad interleaved (re, im) pairs in device numbering */
+int ec3d_harmonic_device_vector(ec3d_handle h, int which, double **device_ptr, int64_t *pairs);
+
 #ifdef __cplusplus
 }
 #endif
