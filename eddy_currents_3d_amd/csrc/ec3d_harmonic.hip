@@ -32,6 +32,12 @@
 // kernel never tests at its entry a word that its own launch may write with a value that would change the test --
 // k_h_xr of iteration it asks stop_s < it, k_h_p stop_r < it -- so a workgroup that starts late takes the same path as
 // workgroup 0.  rr0 alternates between two slots for the same reason.  The host enqueues 16 iterations and polls once.
+//
+// Left null vectors (opt-in, ec3d_harmonic_set_null_projection).  K + j omega M is singular as the
+// transient matrix is: one left null vector per connected conducting component, and every residual keeps w^H r = w^H b^.
+// The set-up (null_build) finds them by adjoint solves -- the iteration above around k_h_spmv_h, y = A^H x -- and a solve
+// with the setting on takes them out of its initial residual between k_h_spmv<3> and k_h_setup (k_hn_dots,
+// k_hn_collapse, k_hn_sub).  tests/harmonic_null_numpy.py restates every line.
 #include "ec3d_stream.hpp"
 
 #include <chrono>
@@ -122,16 +128,71 @@ __device__ __forceinline__ cplx h_row_product(const HSav &A, const cplx *tbl, co
     return s;
 }
 
-// MODE 0: y = A x.  1: and <o, y> (o = R0).  2: and <y, x>, <y, y> (x = S).  3: r = o - y (o = B^), r0 = p = r,
-// ||o||^2 and ||r||^2: y, r0, p are the three outputs
-template <int MODE>
-__global__ __launch_bounds__(EC3D_THREADS) void k_h_spmv(HSav A, const HarmonicState *st, const cplx *__restrict__ x,
-                                                        const cplx *__restrict__ o, cplx *__restrict__ y,
-                                                        cplx *__restrict__ r0, cplx *__restrict__ p, int64_t nchunk,
-                                                        double *__restrict__ part)
+// Row j of A^H x: the gather of k_sav_spmv_t (ec3d_transpose.hip) in complex pairs.  Column j of A
+// holds band b of row j - off[b]; for an A_d column of cell q the U rows of the cells q - (jj - 1) step_d, slot
+// 7 + 3 d + jj; for a U column the A_d rows of the cells q - m step_d, slot 7 + m + 2.  The coefficient stands under the
+// SOURCE row's class and is conjugated: conj(a) x = (ar xr + ai xi, ar xi - ai xr).  Terms are added from +0.0 in
+// ascending source row -- bands from the largest offset down, shifts from the largest down, the A blocks before the U
+// block.  A source row is tested before anything of it is read: inside its block (so inside [0, n)), of a class that
+// owns the slot; x is read only where both tests passed and a coefficient is not zero.
+__device__ __forceinline__ void h_term_h(cplx &s, cplx t, const cplx *__restrict__ x, int64_t i)
 {
-    extern __shared__ cplx tbl[];
-    __shared__ double lds[12];
+    if (t.x == 0.0 && t.y == 0.0) return;
+    const cplx v = x[i];
+    const cplx p = cplx{t.x * v.x + t.y * v.y, t.x * v.y - t.y * v.x};
+    s.x = s.x + p.x;
+    s.y = s.y + p.y;
+}
+
+__device__ __forceinline__ cplx h_row_product_h(const HSav &A, const cplx *tbl, const cplx *__restrict__ x, int64_t j)
+{
+    cplx s = {0.0, 0.0};
+    if (A.cls[j] >= A.zero) return s; // a row of no unknown: no column of A either
+    const int blk = (int)(j / A.nC);
+    const int64_t q = j - blk * A.nC;
+    const int64_t lo = blk * A.nC, hi = blk < 3 ? lo + A.nC : A.n;
+    auto bands = [&]() {
+        for (int b = 6; b >= 0; --b) {
+            const int64_t i = j - A.off[b];
+            if (i < lo || i >= hi) continue;
+            const int cc = A.cls[i];
+            if (cc >= A.zero) continue;
+            h_term_h(s, tbl[cc * 16 + b], x, i);
+        }
+    };
+    if (blk < 3) {
+        bands();
+        for (int jj = 2; jj >= 0; --jj) { // the U rows that reach this A_d column
+            const int64_t cu = q - (jj - 1) * A.step[blk];
+            if (cu < 0 || 3 * A.nC + cu >= A.n) continue;
+            const int64_t i = 3 * A.nC + cu;
+            const int cc = A.cls[i];
+            if (cc < A.u0 || cc >= A.zero) continue;
+            h_term_h(s, tbl[cc * 16 + 7 + 3 * blk + jj], x, i);
+        }
+    } else {
+        for (int d = 0; d < 3; ++d)
+            for (int m = 2; m >= -2; --m) { // the coupled A_d rows that reach this U column
+                const int64_t ca = q - m * A.step[d];
+                if (ca < 0 || ca >= A.nC) continue;
+                const int64_t i = d * A.nC + ca;
+                const int cc = A.cls[i];
+                if (cc < A.a0 || cc >= A.u0) continue;
+                h_term_h(s, tbl[cc * 16 + 7 + m + 2], x, i);
+            }
+        bands();
+    }
+    return s;
+}
+
+// MODE 0: y = A x.  1: and <o, y> (o = R0).  2: and <y, x>, <y, y> (x = S).  3: r = o - y (o = B^), r0 = p = r,
+// ||o||^2 and ||r||^2: y, r0, p are the three outputs.  ADJ: A^H in place of A
+template <int MODE, bool ADJ>
+__device__ __forceinline__ void h_spmv_modes(const HSav &A, const HarmonicState *st, const cplx *__restrict__ x,
+                                             const cplx *__restrict__ o, cplx *__restrict__ y, cplx *__restrict__ r0,
+                                             cplx *__restrict__ p, int64_t nchunk, double *__restrict__ part, cplx *tbl,
+                                             double *lds)
+{
     if ((MODE == 1 || MODE == 2) && (st->stop_s != INT_MAX || st->stop_r != INT_MAX)) return;
     for (int q = threadIdx.x; q < A.ncls * 16; q += EC3D_THREADS) tbl[q] = A.table[q];
     __syncthreads();
@@ -140,7 +201,7 @@ __global__ __launch_bounds__(EC3D_THREADS) void k_h_spmv(HSav A, const HarmonicS
         for (int half = 0; half < 2; ++half) {
             const int64_t i = h_row(ch, half);
             if (i >= A.n) continue;
-            const cplx s = h_row_product(A, tbl, x, i);
+            const cplx s = ADJ ? h_row_product_h(A, tbl, x, i) : h_row_product(A, tbl, x, i);
             if (MODE == 0) y[i] = s;
             if (MODE == 1) {
                 y[i] = s;
@@ -173,6 +234,30 @@ __global__ __launch_bounds__(EC3D_THREADS) void k_h_spmv(HSav A, const HarmonicS
         double v[2] = {acc[0], acc[1]};
         h_leave<2>(v, part, HP_BB, lds);
     }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(EC3D_THREADS) void k_h_spmv(HSav A, const HarmonicState *st, const cplx *__restrict__ x,
+                                                        const cplx *__restrict__ o, cplx *__restrict__ y,
+                                                        cplx *__restrict__ r0, cplx *__restrict__ p, int64_t nchunk,
+                                                        double *__restrict__ part)
+{
+    extern __shared__ cplx tbl[];
+    __shared__ double lds[12];
+    h_spmv_modes<MODE, false>(A, st, x, o, y, r0, p, nchunk, part, tbl, lds);
+}
+
+// y = A^H x in the layout, the modes and the partial slots of k_h_spmv: the adjoint solves of the left null vectors run
+// k_h_s, k_h_xr, k_h_p and k_h_setup around it unchanged
+template <int MODE>
+__global__ __launch_bounds__(EC3D_THREADS) void k_h_spmv_h(HSav A, const HarmonicState *st, const cplx *__restrict__ x,
+                                                          const cplx *__restrict__ o, cplx *__restrict__ y,
+                                                          cplx *__restrict__ r0, cplx *__restrict__ p, int64_t nchunk,
+                                                          double *__restrict__ part)
+{
+    extern __shared__ cplx tbl[];
+    __shared__ double lds[12];
+    h_spmv_modes<MODE, true>(A, st, x, o, y, r0, p, nchunk, part, tbl, lds);
 }
 
 // behind k_h_spmv<3>, one workgroup: ||b^||, rr0 = <R0, R> = (||R||^2, 0), the exit words
@@ -316,6 +401,79 @@ __global__ __launch_bounds__(EC3D_THREADS) void k_h_p(HarmonicState *st, int it,
         }
 }
 
+// ---- left null vectors: the streaming kernels of the set-up and of the projection -------------
+// partials of c_i = <Q_i, v>, Q_i = qbase + i * qstride, i = blockIdx.y: the two parts at part[(2 i + {0, 1}) * G + b]
+__global__ __launch_bounds__(EC3D_THREADS) void k_hn_dots(const cplx *__restrict__ qbase, int64_t qstride,
+                                                         const cplx *__restrict__ v, int64_t n, int64_t nchunk,
+                                                         double *__restrict__ part)
+{
+    __shared__ double lds[8];
+    const cplx *q = qbase + (int64_t)blockIdx.y * qstride;
+    double acc[2] = {0.0, 0.0};
+    for (int64_t ch = blockIdx.x; ch < nchunk; ch += gridDim.x)
+        for (int half = 0; half < 2; ++half) {
+            const int64_t i = h_row(ch, half);
+            if (i >= n) continue;
+            const cplx d = cdot(q[i], v[i]);
+            acc[0] = acc[0] + d.x;
+            acc[1] = acc[1] + d.y;
+        }
+    h_leave<2>(acc, part, 2 * (int)blockIdx.y, lds);
+}
+
+// workgroup i: coef[i] = the two parts of c_i, from `count` partials each
+__global__ __launch_bounds__(EC3D_THREADS) void k_hn_collapse(const double *__restrict__ part, int count, cplx *__restrict__ coef)
+{
+    __shared__ double lds[8];
+    double v[2];
+    stream_strided_sum<2>(v, part + (int64_t)2 * blockIdx.x * count, count, count);
+    stream_block_sum<2>(v, lds);
+    if (threadIdx.x == 0) coef[blockIdx.x] = cplx{v[0], v[1]};
+}
+
+// v = v - c_0 Q_0 - ... - c_{k-1} Q_{k-1}, every term a rounded cmul and a rounded difference per part; r0, p (or null):
+// copies of the new v; rr (or null): workgroup b's partial of ||v||^2 at rr[b], written by EVERY workgroup of the launch
+__global__ __launch_bounds__(EC3D_THREADS) void k_hn_sub(const cplx *__restrict__ qbase, int64_t qstride, int k,
+                                                        const cplx *__restrict__ coef, cplx *__restrict__ v,
+                                                        cplx *__restrict__ r0, cplx *__restrict__ p, int64_t n,
+                                                        int64_t nchunk, double *__restrict__ rr)
+{
+    __shared__ double lds[4];
+    double acc[1] = {0.0};
+    for (int64_t ch = blockIdx.x; ch < nchunk; ch += gridDim.x)
+        for (int half = 0; half < 2; ++half) {
+            const int64_t i = h_row(ch, half);
+            if (i >= n) continue;
+            cplx x = v[i];
+            for (int m = 0; m < k; ++m) {
+                const cplx t = cmul(coef[m], qbase[(int64_t)m * qstride + i]);
+                x = cplx{x.x - t.x, x.y - t.y};
+            }
+            v[i] = x;
+            if (r0) r0[i] = x;
+            if (p) p[i] = x;
+            acc[0] = acc[0] + cabs2(x);
+        }
+    if (!rr) return;
+    stream_block_sum<1>(acc, lds);
+    if (threadIdx.x == 0) rr[blockIdx.x] = acc[0];
+}
+
+// v = v / d on rows < n, each part divided on its own
+__global__ __launch_bounds__(EC3D_THREADS) void k_hn_div(cplx *__restrict__ v, double d, int64_t n, int64_t nchunk)
+{
+    for (int64_t ch = blockIdx.x; ch < nchunk; ch += gridDim.x)
+        for (int half = 0; half < 2; ++half) {
+            const int64_t i = h_row(ch, half);
+            if (i >= n) continue;
+            const cplx a = v[i];
+            v[i] = cplx{a.x / d, a.y / d};
+        }
+}
+
+// Re v[row] = Re v[row] + a (e_m and -e_m)
+__global__ void k_hn_add_re(cplx *v, int64_t row, double a) { v[row].x = v[row].x + a; }
+
 // host copies: (re plane, im plane) in device numbering <-> interleaved pairs; rows >= n of an uploaded vector are zero
 __global__ void k_h_pack(const double *__restrict__ re, const double *__restrict__ im, cplx *__restrict__ v, int64_t n, int64_t n_pad)
 {
@@ -387,33 +545,75 @@ HSav view_of(const ec3d_ctx *c)
 
 cplx *hv(const ec3d_ctx *c, int w) { return reinterpret_cast<cplx *>(c->harm.vec[w]); }
 
-template <int MODE> void launch_spmv(ec3d_ctx *c, const cplx *x, const cplx *o, cplx *y, cplx *r0, cplx *p)
+// the operator of a solve: K + j omega M or its conjugate transpose (the adjoint solves of the left null vectors)
+enum HOp { H_A = 0, H_AH };
+
+template <int MODE> void launch_spmv(ec3d_ctx *c, HOp op, const cplx *x, const cplx *o, cplx *y, cplx *r0, cplx *p)
 {
     const Harmonic &H = c->harm;
-    k_h_spmv<MODE><<<(unsigned)H.wgs, EC3D_THREADS, (size_t)c->A.ncls * 16 * sizeof(cplx), c->stream>>>(
-        view_of(c), H.state, x, o, y, r0, p, c->A.n_pad / EC3D_TILE, H.part);
+    const size_t lds = (size_t)c->A.ncls * 16 * sizeof(cplx);
+    if (op == H_A)
+        k_h_spmv<MODE><<<(unsigned)H.wgs, EC3D_THREADS, lds, c->stream>>>(view_of(c), H.state, x, o, y, r0, p,
+                                                                         c->A.n_pad / EC3D_TILE, H.part);
+    else
+        k_h_spmv_h<MODE><<<(unsigned)H.wgs, EC3D_THREADS, lds, c->stream>>>(view_of(c), H.state, x, o, y, r0, p,
+                                                                           c->A.n_pad / EC3D_TILE, H.part);
 }
 
-// R = B^ - A X^, R0 = R, P = R and the state of a solve that has just begun
-void launch_begin(ec3d_ctx *c, double tol)
+// c_i = <Q_i, R>; R = R - c_1 Q_1 - ... - c_k Q_k, R0 = R, P = R; the partials of ||R||^2 where k_h_spmv<3> left them
+// (HP_RR, one per workgroup of that launch), so k_h_setup reads them unchanged
+void launch_project(ec3d_ctx *c)
 {
     const Harmonic &H = c->harm;
-    launch_spmv<3>(c, hv(c, HV_X), hv(c, HV_B), hv(c, HV_R), hv(c, HV_R0), hv(c, HV_P));
+    if (H.null_kept == 0) return;
+    const int64_t n = c->A.n, len = c->A.n_pad, nc = len / EC3D_TILE;
+    const cplx *q = reinterpret_cast<const cplx *>(H.nq.get());
+    cplx *coef = reinterpret_cast<cplx *>(H.ncoef.get());
+    k_hn_dots<<<dim3((unsigned)H.wgs, (unsigned)H.null_kept), EC3D_THREADS, 0, c->stream>>>(q, len, hv(c, HV_R), n, nc, H.npart);
+    k_hn_collapse<<<(unsigned)H.null_kept, EC3D_THREADS, 0, c->stream>>>(H.npart, H.wgs, coef);
+    k_hn_sub<<<(unsigned)H.wgs, EC3D_THREADS, 0, c->stream>>>(q, len, H.null_kept, coef, hv(c, HV_R), hv(c, HV_R0), hv(c, HV_P), n,
+                                                             nc, H.part.get() + (int64_t)HP_RR * H.wgs);
+}
+
+// R = b - op x, R0 = R, P = R and the state of a solve that has just begun; project: the left null vectors leave R first
+void launch_begin(ec3d_ctx *c, HOp op, const cplx *x, const cplx *b, double tol, bool project)
+{
+    const Harmonic &H = c->harm;
+    launch_spmv<3>(c, op, x, b, hv(c, HV_R), hv(c, HV_R0), hv(c, HV_P));
+    if (project) launch_project(c);
     k_h_setup<<<1, EC3D_THREADS, 0, c->stream>>>(H.state, H.part, H.wgs, tol);
 }
 
-void launch_iteration(ec3d_ctx *c, int it)
+void launch_iteration(ec3d_ctx *c, HOp op, cplx *x, int it)
 {
     const Harmonic &H = c->harm;
     const int64_t n = c->A.n, nc = c->A.n_pad / EC3D_TILE;
     const unsigned G = (unsigned)H.wgs;
     hipStream_t s = c->stream;
-    launch_spmv<1>(c, hv(c, HV_P), hv(c, HV_R0), hv(c, HV_AP), nullptr, nullptr);
+    launch_spmv<1>(c, op, hv(c, HV_P), hv(c, HV_R0), hv(c, HV_AP), nullptr, nullptr);
     k_h_s<<<G, EC3D_THREADS, 0, s>>>(H.state, it, hv(c, HV_R), hv(c, HV_AP), hv(c, HV_S), n, nc, H.part);
-    launch_spmv<2>(c, hv(c, HV_S), nullptr, hv(c, HV_AS), nullptr, nullptr);
-    k_h_xr<<<G, EC3D_THREADS, 0, s>>>(H.state, it, hv(c, HV_P), hv(c, HV_S), hv(c, HV_AS), hv(c, HV_R0), hv(c, HV_X),
-                                     hv(c, HV_R), n, nc, H.part);
+    launch_spmv<2>(c, op, hv(c, HV_S), nullptr, hv(c, HV_AS), nullptr, nullptr);
+    k_h_xr<<<G, EC3D_THREADS, 0, s>>>(H.state, it, hv(c, HV_P), hv(c, HV_S), hv(c, HV_AS), hv(c, HV_R0), x, hv(c, HV_R), n, nc,
+                                     H.part);
     k_h_p<<<G, EC3D_THREADS, 0, s>>>(H.state, it, hv(c, HV_R), hv(c, HV_AP), hv(c, HV_P), hv(c, HV_R0), n, nc, H.part);
+}
+
+// itmax + 1 iterations at most (src/solvers.f90:25-29) behind a launch_begin, 16 enqueued per poll; st: the state at the
+// last poll.  *stopped: an exit was taken
+int run_iterations(ec3d_ctx *c, HOp op, cplx *x, int64_t itmax, HarmonicState &st, bool *stopped)
+{
+    const int64_t total = itmax + 1;
+    int64_t launched = 0;
+    *stopped = false;
+    do {
+        const int64_t m = std::min<int64_t>(16, total - launched);
+        for (int64_t i = 0; i < m; ++i) launch_iteration(c, op, x, (int)(++launched));
+        EC3D_HIP(hipGetLastError());
+        EC3D_HIP(hipMemcpyAsync(&st, c->harm.state, sizeof st, hipMemcpyDeviceToHost, c->stream));
+        EC3D_HIP(hipStreamSynchronize(c->stream));
+        *stopped = st.stop_s != INT_MAX || st.stop_r != INT_MAX;
+    } while (launched < total && !*stopped);
+    return 0;
 }
 
 // what every entry point refuses first; ready: ec3d_harmonic_setup must have run
@@ -475,11 +675,152 @@ int h_to_host(ec3d_ctx *c, const cplx *src, double *re, double *im)
     return 0;
 }
 
+// sum over the rows of <a, v>'s terms (a == v: ||v||^2 in the real part), read back: one k_hn_dots and one collapse
+int dot_to_host(ec3d_ctx *c, const cplx *a, const cplx *v, double *re)
+{
+    Harmonic &H = c->harm;
+    cplx *coef = reinterpret_cast<cplx *>(H.ncoef.get());
+    k_hn_dots<<<dim3((unsigned)H.wgs, 1), EC3D_THREADS, 0, c->stream>>>(a, 0, v, c->A.n, c->A.n_pad / EC3D_TILE, H.npart);
+    k_hn_collapse<<<1, EC3D_THREADS, 0, c->stream>>>(H.npart, H.wgs, coef);
+    EC3D_HIP(hipGetLastError());
+    double h[2];
+    EC3D_HIP(hipMemcpyAsync(h, coef, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    EC3D_HIP(hipStreamSynchronize(c->stream));
+    *re = h[0];
+    return 0;
+}
+
+// The set-up of ec3d_harmonic_set_null_projection, once per matrix and omega.  Per connected conducting component
+// (ec3d_null_seeds): c = A^H (-e_m) into AS by one launch (-e_m in S); the adjoint solve A^H y = c from y = 0 -- this
+// file's iteration around k_h_spmv_h, y in the next free slot of Q, in the work vectors R, R0, P, AP, S, AS and the
+// state, which nothing reads between two solves; X^ and B^ are not touched -- then w = y + e_m, ||A^H w|| / ||w||, and
+// classical Gram-Schmidt against the vectors kept.
+int null_build(ec3d_ctx *c)
+{
+    Harmonic &H = c->harm;
+    const auto t_start = std::chrono::steady_clock::now();
+    ec3d_harmonic_null_free(c);
+    EC3D_HIP(hipStreamSynchronize(c->stream));
+    const int64_t n = c->A.n, len = c->A.n_pad, nc = len / EC3D_TILE;
+    std::vector<NullSeed> seeds;
+    int rc = ec3d_null_seeds(c, seeds);
+    if (rc) return rc;
+    const int ncomp = (int)seeds.size();
+    ec3d_null_info &L = H.null_last;
+    L.found = ncomp;
+    L.reported = std::min(ncomp, EC3D_NULL_MAX_REPORT);
+    if (ncomp == 0) { // no conductor: the operator has no such null vector, the projection is the identity
+        H.null_built = true;
+        return 0;
+    }
+    EC3D_HIP(H.nq.alloc((size_t)ncomp * 2 * len));
+    EC3D_HIP(hipMemsetAsync(H.nq, 0, (size_t)ncomp * 2 * len * sizeof(double), c->stream));
+    EC3D_HIP(H.npart.alloc((size_t)2 * ncomp * H.wgs));
+    EC3D_HIP(H.ncoef.alloc((size_t)2 * ncomp));
+    H.null_bytes = (int64_t)(((size_t)ncomp * 2 * len + (size_t)2 * ncomp * H.wgs + (size_t)2 * ncomp) * sizeof(double));
+    cplx *Q = reinterpret_cast<cplx *>(H.nq.get()), *coef = reinterpret_cast<cplx *>(H.ncoef.get());
+    const int64_t cap = (int64_t)(20.0 * std::cbrt((double)c->n_ref)) + 2000;
+    const unsigned G = (unsigned)H.wgs;
+    int kept = 0;
+    for (int ci = 0; ci < ncomp; ++ci) {
+        const int64_t row = seeds[(size_t)ci].row;
+        cplx *w = Q + (size_t)kept * len; // the next free slot: y, then w, then Q_kept
+        EC3D_HIP(hipMemsetAsync(hv(c, HV_S), 0, (size_t)n * sizeof(cplx), c->stream));
+        k_hn_add_re<<<1, 1, 0, c->stream>>>(hv(c, HV_S), row, -1.0);
+        launch_spmv<0>(c, H_AH, hv(c, HV_S), nullptr, hv(c, HV_AS), nullptr, nullptr);
+        launch_begin(c, H_AH, w, hv(c, HV_AS), H.null_tol, false);
+        EC3D_HIP(hipGetLastError());
+        HarmonicState st;
+        bool stopped = false;
+        if ((rc = run_iterations(c, H_AH, w, cap, st, &stopped))) return rc;
+        k_hn_add_re<<<1, 1, 0, c->stream>>>(w, row, 1.0);
+        // c - A^H y = -A^H w: ||A^H w|| is the adjoint system's TRUE residual, and the figure of the report
+        double aw2 = 0.0, w2 = 0.0;
+        launch_spmv<0>(c, H_AH, w, nullptr, hv(c, HV_AS), nullptr, nullptr);
+        if ((rc = dot_to_host(c, hv(c, HV_AS), hv(c, HV_AS), &aw2))) return rc;
+        if ((rc = dot_to_host(c, w, w, &w2))) return rc;
+        // A w that missed null_tol is never used.  Missed: no exit within the cap, or an exit of the recurrence that the
+        // true residual does not bear out.  The exits bound the recurrence's residual by null_tol ||c||; the true one
+        // differs from it by the rounding gathered along the solve, some 1e-14 ||c|| and far below any null_tol the
+        // arithmetic can deliver, so twice the bound tells a solve that delivered from a recurrence that ran away.
+        const double true_rel = std::sqrt(aw2) / st.bnorm;
+        if (!stopped || !(true_rel <= 2.0 * H.null_tol)) {
+            char msg[400];
+            snprintf(msg, sizeof msg, "harmonic null projection: the adjoint solve of conducting component %d (seed row %lld) did "
+                     "not reach null_tol = %.3g: %s after %lld iterations (cap %lld), true residual ||A^H w|| / ||A^H e_m|| = %.3g; "
+                     "its left null vector is not used", ci, (long long)seeds[(size_t)ci].seed_ref, H.null_tol,
+                     stopped ? "the recurrence took an exit" : "no exit",
+                     (long long)(stopped ? std::min(st.stop_s, st.stop_r) : cap + 1), (long long)cap, true_rel);
+            ec3d_harmonic_null_free(c);
+            ec3d_set_error(msg);
+            return EC3D_NULL_E_SETUP;
+        }
+        const double n0 = std::sqrt(w2), res = std::sqrt(aw2) / n0;
+        if (kept > 0) {
+            k_hn_dots<<<dim3(G, (unsigned)kept), EC3D_THREADS, 0, c->stream>>>(Q, len, w, n, nc, H.npart);
+            k_hn_collapse<<<(unsigned)kept, EC3D_THREADS, 0, c->stream>>>(H.npart, H.wgs, coef);
+            k_hn_sub<<<G, EC3D_THREADS, 0, c->stream>>>(Q, len, kept, coef, w, nullptr, nullptr, n, nc, nullptr);
+            if ((rc = dot_to_host(c, w, w, &w2))) return rc;
+        }
+        const double n1 = std::sqrt(w2);
+        const bool keep = std::isfinite(n0) && std::isfinite(n1) && n1 > EC3D_NULL_MIN_KEEP * n0;
+        if (keep) {
+            k_hn_div<<<G, EC3D_THREADS, 0, c->stream>>>(w, n1, n, nc);
+            ++kept;
+        } else {
+            EC3D_HIP(hipMemsetAsync(w, 0, (size_t)len * sizeof(cplx), c->stream)); // the slot is free again
+        }
+        if (ci < EC3D_NULL_MAX_REPORT) {
+            L.seed_row[ci] = seeds[(size_t)ci].seed_ref;
+            L.iterations[ci] = std::min(st.stop_s, st.stop_r);
+            L.was_kept[ci] = keep ? 1 : 0;
+            L.residual[ci] = res;
+            H.null_restarts[ci] = st.restarts;
+        }
+    }
+    EC3D_HIP(hipGetLastError());
+    EC3D_HIP(hipStreamSynchronize(c->stream));
+    H.null_kept = kept;
+    H.null_built = true;
+    L.kept = kept;
+    L.dropped = ncomp - kept;
+    L.setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    return 0;
+}
+
+// removed = sqrt(sum |c_i|^2) / ||b^|| of the projection that has just run: one copy of the coefficients
+int null_note(ec3d_ctx *c, double bnorm)
+{
+    Harmonic &H = c->harm;
+    H.null_last.removed = 0.0;
+    if (H.null_kept == 0 || bnorm == 0.0) return 0;
+    std::vector<double> h((size_t)2 * H.null_kept);
+    EC3D_HIP(hipMemcpy(h.data(), H.ncoef, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+    double s = 0.0;
+    for (size_t i = 0; i < h.size(); i += 2) s += h[i] * h[i] + h[i + 1] * h[i + 1];
+    H.null_last.removed = std::sqrt(s) / bnorm;
+    return 0;
+}
+
 } // namespace
+
+void ec3d_harmonic_null_free(ec3d_ctx *c)
+{
+    Harmonic &H = c->harm;
+    H.nq.reset();
+    H.npart.reset();
+    H.ncoef.reset();
+    H.null_built = false;
+    H.null_kept = 0;
+    H.null_bytes = 0;
+    H.null_last = ec3d_null_info{};
+    for (auto &r : H.null_restarts) r = 0;
+}
 
 void ec3d_harmonic_free(ec3d_ctx *c)
 {
     Harmonic &H = c->harm;
+    ec3d_harmonic_null_free(c); // (the setting stays with the handle)
     H.re.reset();
     H.m.reset();
     H.tab.reset();
@@ -504,6 +845,7 @@ extern "C" int ec3d_harmonic_setup(ec3d_handle c, double omega)
     }
     Harmonic &H = c->harm;
     EC3D_HIP(hipStreamSynchronize(c->stream));
+    if (!(H.ready && omega == H.omega)) ec3d_harmonic_null_free(c); // Q belongs to the matrix and to omega
     const size_t nt = (size_t)c->A.ncls * 16, len = (size_t)c->A.n_pad;
     std::vector<double> re(nt), m(nt), tab(2 * nt);
     EC3D_HIP(hipMemcpy(re.data(), H.re, nt * sizeof(double), hipMemcpyDeviceToHost));
@@ -576,7 +918,7 @@ extern "C" int ec3d_harmonic_spmv(ec3d_handle c, const double *xre, const double
         if ((rc = h_to_device(c, hv(c, HV_P), xre, xim))) return rc;
         x = hv(c, HV_P);
     }
-    launch_spmv<0>(c, x, nullptr, hv(c, HV_AP), nullptr, nullptr);
+    launch_spmv<0>(c, H_A, x, nullptr, hv(c, HV_AP), nullptr, nullptr);
     EC3D_HIP(hipGetLastError());
     return h_to_host(c, hv(c, HV_AP), yre, yim);
 }
@@ -586,21 +928,14 @@ extern "C" int ec3d_harmonic_solve(ec3d_handle c, double tol, int32_t itmax, int
     int rc = h_need(c, "ec3d_harmonic_solve", true);
     if (rc) return rc;
     Harmonic &H = c->harm;
+    if (H.null_on && !H.null_built && (rc = null_build(c))) return rc;
     const auto t_start = std::chrono::steady_clock::now();
-    launch_begin(c, tol);
+    launch_begin(c, H_A, hv(c, HV_X), hv(c, HV_B), tol, H.null_on != 0);
     EC3D_HIP(hipGetLastError());
     HarmonicState st;
     const int64_t total = (int64_t)itmax + 1; // src/solvers.f90:25-29: itmax + 1 iterations
-    int64_t launched = 0;
     bool stopped = false;
-    do {
-        const int64_t m = std::min<int64_t>(16, total - launched);
-        for (int64_t i = 0; i < m; ++i) launch_iteration(c, (int)(++launched));
-        EC3D_HIP(hipGetLastError());
-        EC3D_HIP(hipMemcpyAsync(&st, H.state, sizeof st, hipMemcpyDeviceToHost, c->stream));
-        EC3D_HIP(hipStreamSynchronize(c->stream));
-        stopped = st.stop_s != INT_MAX || st.stop_r != INT_MAX;
-    } while (launched < total && !stopped);
+    if ((rc = run_iterations(c, H_A, hv(c, HV_X), itmax, st, &stopped))) return rc;
     H.last.iter = stopped ? std::min(st.stop_s, st.stop_r) : (int32_t)std::max<int64_t>(total, 0);
     H.last.restarts = st.restarts;
     H.last.stop_kind = st.stop_s != INT_MAX ? 1 : (st.stop_r != INT_MAX && st.stop_r > 0 ? 2 : 0);
@@ -609,6 +944,7 @@ extern "C" int ec3d_harmonic_solve(ec3d_handle c, double tol, int32_t itmax, int
     H.last.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
     if (iter) *iter = H.last.iter;
     if (relres) *relres = H.last.relres;
+    if (H.null_on) return null_note(c, st.bnorm);
     return 0;
 }
 
@@ -620,7 +956,7 @@ extern "C" int ec3d_harmonic_true_residual(ec3d_handle c, double *rel, double *b
         ec3d_set_error("ec3d_harmonic_true_residual: rel is NULL");
         return 2;
     }
-    launch_begin(c, 0.0);
+    launch_begin(c, H_A, hv(c, HV_X), hv(c, HV_B), 0.0, false);
     EC3D_HIP(hipGetLastError());
     HarmonicState st;
     EC3D_HIP(hipMemcpyAsync(&st, c->harm.state, sizeof st, hipMemcpyDeviceToHost, c->stream));
@@ -662,6 +998,7 @@ extern "C" int ec3d_get_harmonic(ec3d_handle c, ec3d_harmonic_info *out)
     *out = c->harm.last;
     out->ready = c->harm.ready ? 1 : 0;
     out->omega = c->harm.omega;
+    out->device_bytes += c->harm.null_bytes; // Q, its partials and coefficients, while they exist
     return 0;
 }
 
@@ -675,5 +1012,113 @@ extern "C" int ec3d_harmonic_device_vector(ec3d_handle c, int which, double **de
     }
     *device_ptr = c->harm.vec[which];
     *pairs = c->A.n_pad;
+    return 0;
+}
+
+// ---- left null vectors of K + j omega M -------------------------------------------------------
+extern "C" int ec3d_harmonic_set_null_projection(ec3d_handle c, int32_t on, double null_tol)
+{
+    if (!c) {
+        ec3d_set_error("ec3d_harmonic_set_null_projection: null handle");
+        return 2;
+    }
+    if (!on) {
+        c->harm.null_on = 0; // Q stays with the matrix and omega: switching on again costs nothing
+        return 0;
+    }
+    int rc = h_need(c, "ec3d_harmonic_set_null_projection", true);
+    if (rc) return rc; // (the setting as it was)
+    Harmonic &H = c->harm;
+    const double tol = null_tol > 0.0 ? null_tol : 1e-10;
+    if (tol != H.null_tol && H.null_built) {
+        EC3D_HIP(hipStreamSynchronize(c->stream));
+        ec3d_harmonic_null_free(c); // another accuracy: the vectors are made again
+    }
+    H.null_on = 1;
+    H.null_tol = tol;
+    return 0;
+}
+
+extern "C" int ec3d_get_harmonic_null(ec3d_handle c, ec3d_null_info *info)
+{
+    if (!c || !info) {
+        ec3d_set_error("ec3d_get_harmonic_null: null handle or info");
+        return 2;
+    }
+    *info = c->harm.null_last;
+    info->on = c->harm.null_on;
+    info->null_tol = c->harm.null_tol;
+    info->built = c->harm.null_built ? 1 : 0;
+    return 0;
+}
+
+extern "C" int ec3d_harmonic_left_null_vector(ec3d_handle c, int32_t index, double *re, double *im)
+{
+    int rc = h_need(c, "ec3d_harmonic_left_null_vector", true);
+    if (rc) return rc;
+    Harmonic &H = c->harm;
+    if (!H.null_built) {
+        if (!H.null_on) {
+            ec3d_set_error("ec3d_harmonic_left_null_vector: no vectors yet and the projection is off "
+                           "(ec3d_harmonic_set_null_projection)");
+            return 2;
+        }
+        if ((rc = null_build(c))) return rc;
+    }
+    if (index < 0 || index >= H.null_kept || !re || !im) {
+        ec3d_set_error("ec3d_harmonic_left_null_vector: index " + std::to_string(index) + " is outside the " +
+                       std::to_string(H.null_kept) + " vectors kept, or a NULL argument");
+        return 2;
+    }
+    return h_to_host(c, reinterpret_cast<const cplx *>(H.nq.get()) + (size_t)index * c->A.n_pad, re, im);
+}
+
+extern "C" int ec3d_harmonic_spmv_h(ec3d_handle c, const double *xre, const double *xim, double *yre, double *yim)
+{
+    int rc = h_need(c, "ec3d_harmonic_spmv_h", true);
+    if (rc) return rc;
+    if (!yre || !yim || (xre && !xim)) {
+        ec3d_set_error("ec3d_harmonic_spmv_h: NULL argument");
+        return 2;
+    }
+    const cplx *x = hv(c, HV_X);
+    if (xre) {
+        if ((rc = h_to_device(c, hv(c, HV_P), xre, xim))) return rc;
+        x = hv(c, HV_P);
+    }
+    launch_spmv<0>(c, H_AH, x, nullptr, hv(c, HV_AP), nullptr, nullptr);
+    EC3D_HIP(hipGetLastError());
+    return h_to_host(c, hv(c, HV_AP), yre, yim);
+}
+
+extern "C" int ec3d_harmonic_projected_residual(ec3d_handle c, double *rel, double *removed)
+{
+    int rc = h_need(c, "ec3d_harmonic_projected_residual", true);
+    if (rc) return rc;
+    Harmonic &H = c->harm;
+    if (!H.null_on || !rel) {
+        ec3d_set_error(!rel ? "ec3d_harmonic_projected_residual: rel is NULL"
+                            : "ec3d_harmonic_projected_residual: the projection is off (ec3d_harmonic_set_null_projection)");
+        return 2;
+    }
+    if (!H.null_built && (rc = null_build(c))) return rc;
+    launch_begin(c, H_A, hv(c, HV_X), hv(c, HV_B), 0.0, true);
+    EC3D_HIP(hipGetLastError());
+    HarmonicState st;
+    EC3D_HIP(hipMemcpyAsync(&st, H.state, sizeof st, hipMemcpyDeviceToHost, c->stream));
+    EC3D_HIP(hipStreamSynchronize(c->stream));
+    *rel = st.bnorm > 0.0 ? st.rnorm / st.bnorm : st.rnorm;
+    if ((rc = null_note(c, st.bnorm))) return rc;
+    if (removed) *removed = H.null_last.removed;
+    return 0;
+}
+
+extern "C" int ec3d_harmonic_null_restarts(ec3d_handle c, int32_t *restarts)
+{
+    if (!c || !restarts) {
+        ec3d_set_error("ec3d_harmonic_null_restarts: null handle or array");
+        return 2;
+    }
+    for (int i = 0; i < EC3D_NULL_MAX_REPORT; ++i) restarts[i] = c->harm.null_restarts[i];
     return 0;
 }

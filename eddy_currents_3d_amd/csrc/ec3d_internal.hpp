@@ -435,6 +435,18 @@ struct Harmonic {
     DevBuf<HarmonicState> state;
     int wgs = 0;
     ec3d_harmonic_info last{};
+    // ec3d_harmonic_set_null_projection: the orthonormal left null vectors of K + j omega M, vector
+    // i the n_pad pairs at nq + i * 2 * n_pad.  The setting (null_on, null_tol) belongs to the handle, Q to the matrix
+    // AND to omega.
+    int null_on = 0;
+    double null_tol = 1e-10;
+    bool null_built = false;
+    int null_kept = 0;
+    DevBuf<double> nq;
+    DevBuf<double> npart, ncoef; // [2 * kept * wgs] partials of the coefficients' parts, [2 * kept] the coefficients
+    int64_t null_bytes = 0;
+    ec3d_null_info null_last{};
+    int32_t null_restarts[EC3D_NULL_MAX_REPORT] = {0}; // of the adjoint solves (tests; ec3d_null_info has no room)
 };
 
 struct ec3d_ctx {
@@ -860,11 +872,18 @@ void ec3d_launch_spmv_t(const MatView &A, int64_t n, const double *x, double *y,
 // ec3d_null.hip: the left null vectors around a solve (solve_core, when nullp.on)
 void ec3d_null_free(ec3d_ctx *c);                 // Q and its memory go (a new matrix); the setting stays
 int ec3d_null_eligible(const ec3d_ctx *c, const char *who, bool set_text); // 0, EC3D_NULL_E_MATRIX or 4
+// per connected component of the conducting cells (6-neighbourhood, scan order of the first cell): the U row of its
+// middle cell, in device numbering and 0-based in the reference's -- the seeds of the real and the harmonic set-up
+struct NullSeed {
+    int64_t row, seed_ref;
+};
+int ec3d_null_seeds(ec3d_ctx *c, std::vector<NullSeed> &seeds);
 int ec3d_null_prepare(ec3d_ctx *c);               // in front of the solve: builds Q when there is none
 int ec3d_null_project(ec3d_ctx *c);               // behind the residual launch of ec3d_launch_begin, before its set-up
 int ec3d_null_note(ec3d_ctx *c, double bnorm);    // behind the solve: `removed` of ec3d_get_null_projection
 // ec3d_harmonic.hip
 void ec3d_harmonic_free(ec3d_ctx *c); // the tables, vectors and setting of ec3d_harmonic_setup go (a new matrix)
+void ec3d_harmonic_null_free(ec3d_ctx *c); // Q of the harmonic operator goes (a new matrix or omega); the setting stays
 // ec3d_output.hip
 void ec3d_free_output(ec3d_ctx *c);
 // ec3d_rhs.hip

@@ -159,14 +159,13 @@ int build(ec3d_ctx *c)
     EC3D_HIP(hipSetDevice(c->device));
     EC3D_HIP(hipStreamSynchronize(c->stream));
     const MatView A = c->A.view();
-    const int64_t n = c->A.n, len = c->A.n_pad, nc = len / EC3D_TILE, nCd = c->A.sav_nC;
-    // the conducting cells: device cell of U unknown m, scan order (ec3d_setup_rhs)
-    std::vector<int32_t> dcell((size_t)c->n_cond);
-    if (c->n_cond) EC3D_HIP(hipMemcpy(dcell.data(), c->cond_cell, dcell.size() * 4, hipMemcpyDeviceToHost));
-    std::vector<int64_t> cells(dcell.size());
-    for (size_t m = 0; m < dcell.size(); ++m) cells[m] = c->ref_cell(dcell[m]);
-    const auto comps = components(cells, c->sdx, c->sdy, c->sdz);
-    const int ncomp = (int)comps.size();
+    const int64_t n = c->A.n, len = c->A.n_pad, nc = len / EC3D_TILE;
+    std::vector<NullSeed> seeds;
+    {
+        const int rc = ec3d_null_seeds(c, seeds);
+        if (rc) return rc;
+    }
+    const int ncomp = (int)seeds.size();
     N.last.found = ncomp;
     N.last.reported = std::min(ncomp, EC3D_NULL_MAX_REPORT);
     N.len = len;
@@ -206,11 +205,7 @@ int build(ec3d_ctx *c)
     std::vector<double> h((size_t)ncomp + 2);
     int kept = 0;
     for (int ci = 0; ci < ncomp; ++ci) {
-        const auto &cc = comps[(size_t)ci];
-        const int64_t mid = cc[cc.size() / 2];
-        const int64_t row = 3 * nCd + c->dev_cell(mid);
-        const int64_t um = std::lower_bound(cells.begin(), cells.end(), mid) - cells.begin();
-        const int64_t seed_ref = 3 * (int64_t)c->plane * c->planes() + um;
+        const int64_t row = seeds[(size_t)ci].row, seed_ref = seeds[(size_t)ci].seed_ref;
         double *w = N.q.get() + (size_t)kept * len; // the next free slot: y, then w, then Q_kept
         // right-hand side -A^T e_m into R (e_m in S, A^T e_m in AS)
         EC3D_HIP(hipMemsetAsync(v[EC3D_VEC_S], 0, (size_t)n * sizeof(double), c->stream));
@@ -303,6 +298,23 @@ void ec3d_null_free(ec3d_ctx *c)
     N.last = ec3d_null_info{};
     N.levels = 0;
     N.hierarchy_ms = 0.0;
+}
+
+int ec3d_null_seeds(ec3d_ctx *c, std::vector<NullSeed> &seeds)
+{
+    // the conducting cells: device cell of U unknown m, scan order (ec3d_setup_rhs)
+    std::vector<int32_t> dcell((size_t)c->n_cond);
+    if (c->n_cond) EC3D_HIP(hipMemcpy(dcell.data(), c->cond_cell, dcell.size() * 4, hipMemcpyDeviceToHost));
+    std::vector<int64_t> cells(dcell.size());
+    for (size_t m = 0; m < dcell.size(); ++m) cells[m] = c->ref_cell(dcell[m]);
+    const auto comps = components(cells, c->sdx, c->sdy, c->sdz);
+    seeds.clear();
+    for (const auto &cc : comps) {
+        const int64_t mid = cc[cc.size() / 2];
+        const int64_t um = std::lower_bound(cells.begin(), cells.end(), mid) - cells.begin();
+        seeds.push_back(NullSeed{3 * c->A.sav_nC + c->dev_cell(mid), 3 * (int64_t)c->plane * c->planes() + um});
+    }
+    return 0;
 }
 
 int ec3d_null_eligible(const ec3d_ctx *c, const char *who, bool set_text)

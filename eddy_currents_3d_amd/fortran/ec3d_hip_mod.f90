@@ -32,7 +32,9 @@ module ec3d_hip
               ec3d_set_probes, ec3d_probe_sample, ec3d_probe_record, ec3d_probe_read, ec3d_probe_reset, ec3d_get_probes, &
               ec3d_probe_info, EC3D_PROBE_NCOMP, EC3D_PROBE_E_FULL, &
               ec3d_harmonic_setup, ec3d_harmonic_upload, ec3d_harmonic_download, ec3d_harmonic_spmv, ec3d_harmonic_solve, &
-              ec3d_harmonic_true_residual, ec3d_harmonic_load, ec3d_get_harmonic, ec3d_harmonic_info
+              ec3d_harmonic_true_residual, ec3d_harmonic_load, ec3d_get_harmonic, ec3d_harmonic_info, &
+              ec3d_harmonic_set_null_projection, ec3d_get_harmonic_null, ec3d_harmonic_left_null_vector, &
+              ec3d_harmonic_spmv_h, ec3d_harmonic_projected_residual, ec3d_harmonic_null_restarts
 
     integer(c_int), parameter :: EC3D_VEC_X = 0, EC3D_VEC_B = 1   ! Uaf, Jaf
     integer(c_int), parameter :: EC3D_PRECOND_NONE = 0, EC3D_PRECOND_MG = 1   ! ec3d_set_preconditioner
@@ -444,6 +446,47 @@ module ec3d_hip
             import :: c_ptr, c_int, ec3d_harmonic_info
             type(c_ptr), value :: h
             type(ec3d_harmonic_info), intent(out) :: info
+        end function
+        ! Left null vectors of K + j omega M out of every harmonic solve's initial residual (include/ec3d_hip.h; opt-in):
+        ! on = 1 / 0, null_tol <= 0: 1e-10.  The first ec3d_harmonic_solve on a matrix and omega builds them
+        integer(c_int) function ec3d_harmonic_set_null_projection(h, on, null_tol) &
+                bind(C, name="ec3d_harmonic_set_null_projection")
+            import :: c_ptr, c_int, c_int32_t, c_double
+            type(c_ptr), value :: h
+            integer(c_int32_t), value :: on
+            real(c_double), value :: null_tol
+        end function
+        integer(c_int) function ec3d_get_harmonic_null(h, info) bind(C, name="ec3d_get_harmonic_null")
+            import :: c_ptr, c_int, ec3d_null_info
+            type(c_ptr), value :: h
+            type(ec3d_null_info), intent(out) :: info
+        end function
+        ! kept vector `index` (0-based), n doubles per part, the reference's numbering
+        integer(c_int) function ec3d_harmonic_left_null_vector(h, index, re, im) bind(C, name="ec3d_harmonic_left_null_vector")
+            import :: c_ptr, c_int, c_int32_t, c_double
+            type(c_ptr), value :: h
+            integer(c_int32_t), value :: index
+            real(c_double), intent(out) :: re(*), im(*)
+        end function
+        ! y = (K + j omega M)^H x
+        integer(c_int) function ec3d_harmonic_spmv_h(h, xre, xim, yre, yim) bind(C, name="ec3d_harmonic_spmv_h")
+            import :: c_ptr, c_int, c_double
+            type(c_ptr), value :: h
+            real(c_double), intent(in) :: xre(*), xim(*)
+            real(c_double), intent(out) :: yre(*), yim(*)
+        end function
+        ! ||P (b^ - A x^)|| / ||b^|| with the handle's vectors; removed = sqrt(sum |c_i|^2) / ||b^||
+        integer(c_int) function ec3d_harmonic_projected_residual(h, rel, removed) &
+                bind(C, name="ec3d_harmonic_projected_residual")
+            import :: c_ptr, c_int, c_double
+            type(c_ptr), value :: h
+            real(c_double), intent(out) :: rel, removed
+        end function
+        ! the adjoint solves' restart counts, EC3D_NULL_MAX_REPORT entries
+        integer(c_int) function ec3d_harmonic_null_restarts(h, restarts) bind(C, name="ec3d_harmonic_null_restarts")
+            import :: c_ptr, c_int, c_int32_t
+            type(c_ptr), value :: h
+            integer(c_int32_t), intent(out) :: restarts(*)
         end function
         ! U rows ec3d_rhs_step gives their right-hand side with several conducting domains (include/ec3d_hip.h)
         integer(c_int) function ec3d_set_u_rhs(h, rule) bind(C, name="ec3d_set_u_rhs")

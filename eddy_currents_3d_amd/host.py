@@ -469,7 +469,8 @@ def harmonic_rhs(prog: SourceProgram, freq: float, n: int) -> np.ndarray:
 
 
 def run_harmonic(model: vxc.VxcModel, solver, freq: float, tol: float | None = None, itmax: int | None = None,
-                 out_dir: str | None = None, integrals: bool = False, probes=None):
+                 out_dir: str | None = None, integrals: bool = False, probes=None, null_projection: bool = False,
+                 null_tol: float | None = None):
     """The periodic steady state of ``model`` at ``freq`` [Hz] by one complex solve (K + j omega M) x^ = b^ on ``solver``
     (an EC3DSolver) instead of a time loop run until its start-up transient has died away:
     assemble, harmonic_setup(2 pi freq), b^ from the model's sources (harmonic_rhs), harmonic_solve from x^ = 0 at the
@@ -479,7 +480,11 @@ def run_harmonic(model: vxc.VxcModel, solver, freq: float, tol: float | None = N
     parts[p]["integrals"] = solver.domain_integrals(delta) and, in the result, "integrals": per conducting domain
     half the sum of the two parts' Joule loss and force, the averages over a period; ``probes`` (cell numbers): "probes",
     the complex (nprobes, 13) sample; ``out_dir``: harmonic_re.vtk and harmonic_im.vtk in the layout of field_N.vtk.
-    The fields at time t are Re(part0 + j part1) exp(j omega t) = part0 cos(omega t) - part1 sin(omega t)."""
+    The fields at time t are Re(part0 + j part1) exp(j omega t) = part0 cos(omega t) - part1 sin(omega t).
+    ``null_projection``: the left null vectors of the operator leave the initial residual (section 18a), found to
+    ``null_tol`` (None: 1e-10), so that a ``tol`` below the floor can be reached; the result then also holds
+    "projected_residual" -- what the solve converged to, where "true_residual" shows the floor --, "removed" and "null"
+    (solver.harmonic_null_projection()).  The setting is left as it was found."""
     if not hasattr(solver, "harmonic_setup"):
         raise ValueError("run_harmonic needs an EC3DSolver: the harmonic solve runs on one undivided handle")
     t = vxc.domain_tables(model)
@@ -493,10 +498,22 @@ def run_harmonic(model: vxc.VxcModel, solver, freq: float, tol: float | None = N
     solver.harmonic_setup(omega)
     solver.harmonic_upload("B", b)
     solver.harmonic_upload("X", np.zeros(n_ref))
-    it, relres = solver.harmonic_solve(float(t["tol"] if tol is None else tol), int(t["itmax"] if itmax is None else itmax))
+    was = solver.harmonic_null_projection() if null_projection else None
+    if null_projection:
+        solver.harmonic_set_null_projection(True, 1e-10 if null_tol is None else float(null_tol))
+    try:
+        it, relres = solver.harmonic_solve(float(t["tol"] if tol is None else tol), int(t["itmax"] if itmax is None else itmax))
+        info = solver.harmonic_info()
+        extra = {}
+        if null_projection:
+            pres, removed = solver.harmonic_projected_residual()
+            extra = dict(projected_residual=pres, removed=removed, null=solver.harmonic_null_projection())
+    finally:
+        if null_projection:
+            solver.harmonic_set_null_projection(was["on"], was["null_tol"])
     true_res, bnorm = solver.harmonic_true_residual()
     out = dict(freq=float(freq), omega=omega, iter=it, relres=relres, true_residual=true_res, bnorm=bnorm,
-               x=solver.harmonic_download("X"), b=b, parts=[{}, {}], info=solver.harmonic_info())
+               x=solver.harmonic_download("X"), b=b, parts=[{}, {}], info=info, **extra)
     sdz, sdy, sdx = model.vox.shape
     if probes is not None:
         from .probes import stack

@@ -5,6 +5,7 @@
                                                  [--probes FILE [--probe I,J,K]... [--probe-line I0,J0,K0:I1,J1,K1]...
                                                   [--probe-box I0,J0,K0:I1,J1,K1]...]
     python -m eddy_currents_3d_amd.run model.vxc --harmonic FREQ [--out DIR] [--integrals FILE] [--tol X]
+                                                 [--null-projection [--null-tol Y]]
     python -m torch.distributed.run --nproc-per-node G -m eddy_currents_3d_amd.run model.vxc ...   (G GPUs)
 
 Reads the file (eddy_currents_3d_amd/vxc.py), assembles the A-V system on the device, and runs the
@@ -21,7 +22,9 @@ eddy and source current densities, B and U at chosen cells (0-based I,J,K: point
 thick) after every step, in float64, as CSV, one line per step and probe; they are recorded on the device and written
 after the run (one GPU only).  ``--harmonic FREQ``: no time loop -- the periodic steady state at FREQ [Hz] by one complex
 solve (host.run_harmonic): ``harmonic_re.vtk`` and ``harmonic_im.vtk`` go to ``--out``, ``--integrals FILE`` gets the Joule
-loss and force of every conducting domain averaged over a period (one GPU only; moving sources are refused).
+loss and force of every conducting domain averaged over a period (one GPU only; moving sources are refused); with
+``--null-projection`` the complex operator's left null vectors leave the initial residual, the
+report line gains the projected residual and the adjoint solves' iterations, and ``--null-precond`` is refused.
 """
 from __future__ import annotations
 
@@ -113,10 +116,15 @@ def run_harmonic_cli(ap, a, model, t, out_dir):
     from . import EC3DSolver, host
     if not a.harmonic > 0.0:
         ap.error("--harmonic needs a frequency above 0")
+    if a.null_precond is not None:
+        ap.error("--null-precond does not go with --harmonic: there is no preconditioner for the complex adjoint solves")
+    if a.null_tol is not None and not a.null_projection:
+        ap.error("--null-tol needs --null-projection")
     t0 = time.perf_counter()
     with EC3DSolver(device=a.device) as s:
         try:
-            r = host.run_harmonic(model, s, a.harmonic, tol=a.tol, out_dir=out_dir, integrals=bool(a.integrals))
+            r = host.run_harmonic(model, s, a.harmonic, tol=a.tol, out_dir=out_dir, integrals=bool(a.integrals),
+                                  null_projection=a.null_projection, null_tol=a.null_tol)
         except ValueError as e:
             ap.error(str(e))
     if a.integrals:
@@ -125,8 +133,10 @@ def run_harmonic_cli(ap, a, model, t, out_dir):
             for q in r["integrals"]:
                 f.write(",".join([repr(float(a.harmonic)), str(q["domain"]), str(q["cells"]), repr(float(q["joule_w"]))]
                                  + [repr(float(v)) for v in q["force_n"]]) + "\n")
+    null = (f"projected residual={r['projected_residual']:.3e} adjoint iterations="
+            f"{'+'.join(str(q['iterations']) for q in r['null']['components'])} " if a.null_projection else "")
     print(f"harmonic solve at {a.harmonic:g} Hz: iter={r['iter']} relres={r['relres']:.3e} "
-          f"true residual={r['true_residual']:.3e} restarts={r['info']['restarts']} "
+          f"true residual={r['true_residual']:.3e} restarts={r['info']['restarts']} {null}"
           f"({r['info']['ms']:.1f} ms in the solve, {time.perf_counter() - t0:.2f} s wall)"
           + (f"  -> {out_dir}/harmonic_re.vtk, harmonic_im.vtk" if out_dir else ""), flush=True)
     return 0

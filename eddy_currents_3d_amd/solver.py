@@ -122,7 +122,9 @@ EXPORTS = ["sprsbcgstabwr_", "ec3d_invalidate", "ec3d_create", "ec3d_destroy", "
            "ec3d_get_probes",
            "ec3d_harmonic_setup", "ec3d_harmonic_upload", "ec3d_harmonic_download", "ec3d_harmonic_spmv",
            "ec3d_harmonic_solve", "ec3d_harmonic_true_residual", "ec3d_harmonic_load", "ec3d_get_harmonic",
-           "ec3d_harmonic_device_vector"]
+           "ec3d_harmonic_device_vector",
+           "ec3d_harmonic_set_null_projection", "ec3d_get_harmonic_null", "ec3d_harmonic_left_null_vector",
+           "ec3d_harmonic_spmv_h", "ec3d_harmonic_projected_residual", "ec3d_harmonic_null_restarts"]
 PROBE_NCOMP = 13     # EC3D_PROBE_NCOMP of include/ec3d_hip.h: a[3], eddy[3], source[3], b[3], u
 PROBE_E_FULL = 24    # EC3D_PROBE_E_FULL: ec3d_probe_record on a full buffer
 U_RHS = {"reference": 0, "all": 1}   # EC3D_U_RHS_* of include/ec3d_hip.h
@@ -260,6 +262,12 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.ec3d_harmonic_load.argtypes = [hp, C.c_int32]
     L.ec3d_get_harmonic.argtypes = [hp, C.POINTER(HarmonicInfo)]
     L.ec3d_harmonic_device_vector.argtypes = [hp, C.c_int, C.POINTER(hp), C.POINTER(C.c_int64)]
+    L.ec3d_harmonic_set_null_projection.argtypes = [hp, C.c_int32, C.c_double]
+    L.ec3d_get_harmonic_null.argtypes = [hp, C.POINTER(NullInfo)]
+    L.ec3d_harmonic_left_null_vector.argtypes = [hp, C.c_int32, _f64, _f64]
+    L.ec3d_harmonic_spmv_h.argtypes = [hp, C.c_void_p, C.c_void_p, _f64, _f64]
+    L.ec3d_harmonic_projected_residual.argtypes = [hp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.ec3d_harmonic_null_restarts.argtypes = [hp, _i32]
     L.ec3d_vtk_fields_wait.argtypes = [hp, C.c_int32] + [C.POINTER(C.POINTER(C.c_float))] * 4 + [C.POINTER(C.c_int64)]
     L.ec3d_set_workgroups.argtypes = [hp, C.c_int32]
     L.ec3d_get_matrix_info.argtypes = [hp, C.POINTER(MatrixInfo)]
@@ -828,6 +836,55 @@ class EC3DSolver:
         _chk(self.L, self.L.ec3d_harmonic_device_vector(self.h, VEC[which], C.byref(p), C.byref(n)),
              "ec3d_harmonic_device_vector")
         return p.value, n.value
+
+    def harmonic_set_null_projection(self, on: bool = True, null_tol: float = 1e-10):
+        """Take the left null vectors of K + j omega M out of every harmonic solve's initial residual, so that
+        tolerances below |q^H b^| / ||b^|| can be reached (ec3d_harmonic_set_null_projection).
+        The first harmonic_solve on a matrix and omega finds one complex vector per connected conducting component by
+        an adjoint solve to ``null_tol``.  The setting stays with the handle; the vectors go with the matrix and with
+        omega.  EC3DError with the .status of the other harmonic calls on a refusal, the setting then as it was; a
+        solve whose set-up misses ``null_tol`` raises with .status NULL_E_SETUP."""
+        _chk(self.L, self.L.ec3d_harmonic_set_null_projection(self.h, 1 if on else 0, float(null_tol)),
+             "ec3d_harmonic_set_null_projection")
+
+    def harmonic_null_projection(self):
+        """The dict of null_projection() for the harmonic operator's vectors (ec3d_get_harmonic_null): residual =
+        ||A^H w|| / ||w||, removed = sqrt(sum |c_i|^2) / ||b^|| of the last projected solve; every component also has
+        ``restarts``, its adjoint solve's restart count."""
+        g = NullInfo()
+        _chk(self.L, self.L.ec3d_get_harmonic_null(self.h, C.byref(g)), "ec3d_get_harmonic_null")
+        rs = np.zeros(32, np.int32)
+        _chk(self.L, self.L.ec3d_harmonic_null_restarts(self.h, rs), "ec3d_harmonic_null_restarts")
+        comps = [dict(seed_row=int(g.seed_row[i]), iterations=int(g.iterations[i]), residual=float(g.residual[i]),
+                      kept=bool(g.was_kept[i]), restarts=int(rs[i])) for i in range(int(g.reported))]
+        return dict(on=bool(g.on), built=bool(g.built), found=int(g.found), kept=int(g.kept), dropped=int(g.dropped),
+                    null_tol=float(g.null_tol), removed=float(g.removed), setup_ms=float(g.setup_ms), components=comps)
+
+    def harmonic_left_null_vector(self, index: int = 0):
+        """Kept left null vector ``index`` of K + j omega M (complex, unit norm, the reference numbering); builds the
+        vectors when the projection is on and they do not exist yet."""
+        re, im = np.empty(self.n), np.empty(self.n)
+        _chk(self.L, self.L.ec3d_harmonic_left_null_vector(self.h, int(index), re, im), "ec3d_harmonic_left_null_vector")
+        return self._complex(re, im)
+
+    def harmonic_spmv_h(self, x=None):
+        """(K + j omega M)^H x; x = None: the resident X^."""
+        yre, yim = np.empty(self.n), np.empty(self.n)
+        if x is None:
+            rc = self.L.ec3d_harmonic_spmv_h(self.h, None, None, yre, yim)
+        else:
+            re, im = self._parts(x, self.n)
+            rc = self.L.ec3d_harmonic_spmv_h(self.h, re.ctypes.data, im.ctypes.data, yre, yim)
+        _chk(self.L, rc, "ec3d_harmonic_spmv_h")
+        return self._complex(yre, yim)
+
+    def harmonic_projected_residual(self):
+        """(||P (b^ - A x^)|| / ||b^||, removed) with the handle's left null vectors: what a projected solve converges
+        to, where harmonic_true_residual shows the floor."""
+        rel, rem = C.c_double(0), C.c_double(0)
+        _chk(self.L, self.L.ec3d_harmonic_projected_residual(self.h, C.byref(rel), C.byref(rem)),
+             "ec3d_harmonic_projected_residual")
+        return rel.value, rem.value
 
     def set_u_rhs(self, rule: str = "reference"):
         """Which U rows rhs_step gives their right-hand side with several conducting domains: "reference" (default)

@@ -890,7 +890,9 @@ int ec3d_harmonic_download(ec3d_handle h, int which, double *re, double *im);
 int ec3d_harmonic_spmv(ec3d_handle h, const double *xre, const double *xim, double *yre, double *yim);
 /* from the resident X^; *iter as ec3d_solve reports it, *relres as in ec3d_harmonic_info (either may be NULL) */
 int ec3d_harmonic_solve(ec3d_handle h, double tol, int32_t itmax, int32_t *iter, double *relres);
-/* ||b^ - A x^|| / ||b^|| of the resident vectors (the absolute norm when ||b^|| = 0); overwrites R, R0, P */
+/* ||b^ - A x^|| / ||b^|| of the resident vectors (the absolute norm when ||b^|| = 0); overwrites R, R0, P.  Always the
+ * unprojected residual: with ec3d_harmonic_set_null_projection on it shows the floor |q^H b^| / ||b^|| that the solve
+ * left in place, not what the solve converged to (ec3d_harmonic_projected_residual) */
 int ec3d_harmonic_true_residual(ec3d_handle h, double *rel, double *bnorm);
 /* part 0: Re, 1: Im of the phasor into the handle's REAL X and B, after which every observable of the resident
  * fields (ec3d_vtk_fields, probes, ec3d_domain_integrals, ec3d_field_energy, ec3d_domain_linkage) returns that part's:
@@ -902,6 +904,43 @@ int ec3d_get_harmonic(ec3d_handle h, ec3d_harmonic_info *out); /* (a function ca
 /* tests and device-side callers: complex vector `which` (EC3D_VEC_X ... EC3D_VEC_AS) as the kernels hold it, *pairs =
  * n_pad interleaved (re, im) pairs in device numbering */
 int ec3d_harmonic_device_vector(ec3d_handle h, int which, double **device_ptr, int64_t *pairs);
+/* Left null vectors of K + j omega M taken out of every harmonic solve's initial residual (opt-in; DESIGN.md section
+ * 18a).  The complex operator is singular for the reason the transient one is (section 16): a constant U on a connected
+ * conducting component is a right null vector, so there is a left null vector w per component, every residual keeps
+ * w^H r = w^H b^, and no iterate gets below |w^H b^| / ||w||.  w is complex, so the Q of ec3d_set_null_projection does
+ * not serve.  With the setting on, the first ec3d_harmonic_solve on a matrix and omega (or
+ * ec3d_harmonic_left_null_vector) takes the components and seed rows m as section 16 does, forms c = A^H (-e_m) by one
+ * launch, solves A^H y = c from y = 0 with the complex iteration above around y = A^H x (k_h_spmv_h: row j adds the
+ * entries of column j from +0.0 in ascending source row, a term conj(a) x = (ar xr + ai xi, ar xi - ai xr), zero
+ * coefficients skipped) to null_tol within 20 n^(1/3) + 2000 iterations, in the work vectors R ... AS, and sets
+ * w = y + e_m.  The w are orthonormalised by classical Gram-Schmidt in component order -- c_i = <Q_i, w> with the
+ * conjugate on Q_i, all taken first, then subtracted in order; each part divided by sqrt(sum(re^2 + im^2)) -- and one
+ * that keeps less than EC3D_NULL_MIN_KEEP of its norm is dropped and counted.  Every solve then replaces R = b^ - A x^
+ * by R - sum c_i Q_i, c_i = <Q_i, R>, before R0, P and ||R||^2 are taken; b^, ||b^||, the exits, the restart rule and
+ * the iteration's kernels are untouched, and X^ and B^ keep their bytes through the set-up.  A w that did not reach
+ * null_tol is never used: the call returns EC3D_NULL_E_SETUP with component and seed row in the error text.  Not
+ * reached means no exit within the cap, or an exit of the recurrence that the adjoint system's true residual
+ * ||A^H w|| > 2 null_tol ||A^H e_m|| does not bear out (a recurrence residual keeps falling long after the true one has
+ * stopped near 1e-14).  Q belongs
+ * to the matrix and to omega: a new matrix or ec3d_harmonic_setup with another omega clears it, the same omega keeps
+ * it; the setting belongs to the handle.  on = 0 (default): a solve launches and allocates nothing more and returns the
+ * same bits as before.  null_tol <= 0: the default 1e-10.  There is no preconditioner for the adjoint solves.
+ * Refusals as the other harmonic entry points (3, 5, EC3D_NULL_E_MATRIX, 2 before ec3d_harmonic_setup); a refusal
+ * leaves the setting as it was.
+ * ec3d_get_harmonic_null: ec3d_null_info as ec3d_get_null_projection fills it (residual = ||A^H w|| / ||w||, removed =
+ * sqrt(sum |c_i|^2) / ||b^|| of the last projected solve or projected residual); while Q exists, device_bytes of
+ * ec3d_get_harmonic counts it.  ec3d_harmonic_left_null_vector: kept vector `index`, n doubles per part in the
+ * reference numbering; builds Q when the setting is on and there is none; an index outside [0, kept) 2.
+ * ec3d_harmonic_spmv_h: y = A^H x, P and AP as scratch.  ec3d_harmonic_projected_residual: ||P (b^ - A x^)|| / ||b^||
+ * with the handle's Q (2 with the setting off); overwrites R, R0, P; removed may be NULL.
+ * ec3d_harmonic_null_restarts: the restart counts of the adjoint solves, EC3D_NULL_MAX_REPORT entries (tests:
+ * ec3d_null_info has no field for them). */
+int ec3d_harmonic_set_null_projection(ec3d_handle h, int32_t on, double null_tol);
+int ec3d_get_harmonic_null(ec3d_handle h, ec3d_null_info *info);
+int ec3d_harmonic_left_null_vector(ec3d_handle h, int32_t index, double *re, double *im);
+int ec3d_harmonic_spmv_h(ec3d_handle h, const double *xre, const double *xim, double *yre, double *yim);
+int ec3d_harmonic_projected_residual(ec3d_handle h, double *rel, double *removed);
+int ec3d_harmonic_null_restarts(ec3d_handle h, int32_t *restarts);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,6 @@
 """One harmonic solve against the time loop's periodic steady state on compare_to_Elmer (TEAM 7, 50 Hz), one MI355X.
 
-    python tools/harmonic_vs_transient.py [--periods 5] [--out profiles/harmonic.jsonl]
+    python tools/harmonic_vs_transient.py [--periods 5] [--harmonic-tol X [--null-projection]] [--out profiles/harmonic.jsonl]
 
 * the harmonic solve at 50 Hz at the model's tolerance: iterations, seconds (assembly excluded and included), the true
   residual; and the true residual reached at tol = 1e-6 and 1e-8 (itmax 20000);
@@ -8,6 +8,8 @@
   along x through the plate's centre in the plate's top plane -- after every step; the 50 Hz Fourier fit of the last period,
   a^ = (2 / N) sum A(T_n) exp(-j omega T_n), against the harmonic A^ there: |fit - A^| / |A^| over the line's three
   components; beside it the loop's own period-to-period change |fit(last) - fit(last - 1)| / |fit(last)|.
+--harmonic-tol X: the harmonic side at tolerance X (itmax 20000) instead of the model's, with --null-projection below
+the floor; the time loop keeps the model's tolerance.
 Exact agreement is not expected: the U rows are backward-differenced, the A rows trapezoidal, and the reference zeroes Uaf
 on cel_bnd* after every step.  One JSON line appended to --out and printed."""
 from __future__ import annotations
@@ -75,6 +77,8 @@ def transient(model, cells, periods):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--periods", type=int, default=5)
+    ap.add_argument("--harmonic-tol", type=float, default=None)
+    ap.add_argument("--null-projection", action="store_true")
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "harmonic.jsonl"))
     a = ap.parse_args()
     assert a.periods >= 3
@@ -87,7 +91,13 @@ def main():
                 tol=float(t["tol"]))
     with E.EC3DSolver() as s:
         t0 = time.perf_counter()
-        r = host.run_harmonic(model, s, FREQ, probes=cells)
+        r = host.run_harmonic(model, s, FREQ, probes=cells, tol=a.harmonic_tol, itmax=20000 if a.harmonic_tol else None,
+                              null_projection=a.null_projection)
+        if a.harmonic_tol:
+            line.update(harmonic_tol=a.harmonic_tol, null_projection=a.null_projection)
+        if a.null_projection:
+            line.update(harmonic_projected_residual=r["projected_residual"], removed=r["removed"],
+                        adjoint_iterations=[c["iterations"] for c in r["null"]["components"]])
         line.update(harmonic_iter=r["iter"], harmonic_restarts=r["info"]["restarts"], harmonic_solve_s=r["info"]["ms"] * 1e-3,
                     harmonic_wall_s=time.perf_counter() - t0, harmonic_relres=r["relres"], harmonic_true_residual=r["true_residual"])
         ah = r["probes"][:, 0:3]
