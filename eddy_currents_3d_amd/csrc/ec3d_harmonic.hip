@@ -38,6 +38,11 @@
 // The set-up (null_build) finds them by adjoint solves -- the iteration above around k_h_spmv_h, y = A^H x -- and a solve
 // with the setting on takes them out of its initial residual between k_h_spmv<3> and k_h_setup (k_hn_dots,
 // k_hn_collapse, k_hn_sub).  tests/harmonic_null_numpy.py restates every line.
+//
+// Batch (opt-in, ec3d_harmonic_batch_*).  Up to EC3D_HARMONIC_MAX_BATCH systems (omega_s, b^_s, x^_s)
+// on the one matrix ride in the five launches of an iteration on a grid of (G, S): the bodies of k_h_s, k_h_xr, k_h_p
+// and k_h_setup are __device__ functions, as h_spmv_modes is, and k_hb_* run them on the system blockIdx.y names.  Every
+// system keeps the bits of its own single solve; the host copies the S states back once per 16 lock-step iterations.
 #include "ec3d_stream.hpp"
 
 #include <chrono>
@@ -186,15 +191,16 @@ __device__ __forceinline__ cplx h_row_product_h(const HSav &A, const cplx *tbl, 
 }
 
 // MODE 0: y = A x.  1: and <o, y> (o = R0).  2: and <y, x>, <y, y> (x = S).  3: r = o - y (o = B^), r0 = p = r,
-// ||o||^2 and ||r||^2: y, r0, p are the three outputs.  ADJ: A^H in place of A
+// ||o||^2 and ||r||^2: y, r0, p are the three outputs.  ADJ: A^H in place of A.  table: the operator's pairs (A.table of
+// a single solve, the system's own in a batch)
 template <int MODE, bool ADJ>
-__device__ __forceinline__ void h_spmv_modes(const HSav &A, const HarmonicState *st, const cplx *__restrict__ x,
-                                             const cplx *__restrict__ o, cplx *__restrict__ y, cplx *__restrict__ r0,
-                                             cplx *__restrict__ p, int64_t nchunk, double *__restrict__ part, cplx *tbl,
-                                             double *lds)
+__device__ __forceinline__ void h_spmv_modes(const HSav &A, const cplx *__restrict__ table, const HarmonicState *st,
+                                             const cplx *__restrict__ x, const cplx *__restrict__ o,
+                                             cplx *__restrict__ y, cplx *__restrict__ r0, cplx *__restrict__ p,
+                                             int64_t nchunk, double *__restrict__ part, cplx *tbl, double *lds)
 {
     if ((MODE == 1 || MODE == 2) && (st->stop_s != INT_MAX || st->stop_r != INT_MAX)) return;
-    for (int q = threadIdx.x; q < A.ncls * 16; q += EC3D_THREADS) tbl[q] = A.table[q];
+    for (int q = threadIdx.x; q < A.ncls * 16; q += EC3D_THREADS) tbl[q] = table[q];
     __syncthreads();
     double acc[3] = {0.0, 0.0, 0.0};
     for (int64_t ch = blockIdx.x; ch < nchunk; ch += gridDim.x)
@@ -244,7 +250,7 @@ __global__ __launch_bounds__(EC3D_THREADS) void k_h_spmv(HSav A, const HarmonicS
 {
     extern __shared__ cplx tbl[];
     __shared__ double lds[12];
-    h_spmv_modes<MODE, false>(A, st, x, o, y, r0, p, nchunk, part, tbl, lds);
+    h_spmv_modes<MODE, false>(A, A.table, st, x, o, y, r0, p, nchunk, part, tbl, lds);
 }
 
 // y = A^H x in the layout, the modes and the partial slots of k_h_spmv: the adjoint solves of the left null vectors run
@@ -257,13 +263,12 @@ __global__ __launch_bounds__(EC3D_THREADS) void k_h_spmv_h(HSav A, const Harmoni
 {
     extern __shared__ cplx tbl[];
     __shared__ double lds[12];
-    h_spmv_modes<MODE, true>(A, st, x, o, y, r0, p, nchunk, part, tbl, lds);
+    h_spmv_modes<MODE, true>(A, A.table, st, x, o, y, r0, p, nchunk, part, tbl, lds);
 }
 
 // behind k_h_spmv<3>, one workgroup: ||b^||, rr0 = <R0, R> = (||R||^2, 0), the exit words
-__global__ __launch_bounds__(EC3D_THREADS) void k_h_setup(HarmonicState *st, const double *part, int G, double tol)
+__device__ __forceinline__ void h_setup_body(HarmonicState *st, const double *part, int G, double tol, double *lds)
 {
-    __shared__ double lds[8];
     double v[2];
     h_collapse<2>(v, part, HP_BB, G, lds);
     if (threadIdx.x != 0) return;
@@ -282,11 +287,16 @@ __global__ __launch_bounds__(EC3D_THREADS) void k_h_setup(HarmonicState *st, con
     st->pad_ = 0;
 }
 
-__global__ __launch_bounds__(EC3D_THREADS) void k_h_s(HarmonicState *st, int it, const cplx *__restrict__ r,
-                                                     const cplx *__restrict__ ap, cplx *__restrict__ sv, int64_t n,
-                                                     int64_t nchunk, double *__restrict__ part)
+__global__ __launch_bounds__(EC3D_THREADS) void k_h_setup(HarmonicState *st, const double *part, int G, double tol)
 {
     __shared__ double lds[8];
+    h_setup_body(st, part, G, tol, lds);
+}
+
+__device__ __forceinline__ void h_s_body(HarmonicState *st, int it, const cplx *__restrict__ r,
+                                         const cplx *__restrict__ ap, cplx *__restrict__ sv, int64_t n, int64_t nchunk,
+                                         double *__restrict__ part, double *lds)
+{
     if (st->stop_s != INT_MAX || st->stop_r != INT_MAX) return;
     double d[2];
     h_collapse<2>(d, part, HP_D1R, gridDim.x, lds);
@@ -307,13 +317,19 @@ __global__ __launch_bounds__(EC3D_THREADS) void k_h_s(HarmonicState *st, int it,
     h_leave<1>(acc, part, HP_SS, lds);
 }
 
-__global__ __launch_bounds__(EC3D_THREADS) void k_h_xr(HarmonicState *st, int it, const cplx *__restrict__ p,
-                                                      const cplx *__restrict__ sv, const cplx *__restrict__ as,
-                                                      const cplx *__restrict__ r0, cplx *__restrict__ x,
-                                                      cplx *__restrict__ r, int64_t n, int64_t nchunk,
-                                                      double *__restrict__ part)
+__global__ __launch_bounds__(EC3D_THREADS) void k_h_s(HarmonicState *st, int it, const cplx *__restrict__ r,
+                                                     const cplx *__restrict__ ap, cplx *__restrict__ sv, int64_t n,
+                                                     int64_t nchunk, double *__restrict__ part)
 {
-    __shared__ double lds[16];
+    __shared__ double lds[8];
+    h_s_body(st, it, r, ap, sv, n, nchunk, part, lds);
+}
+
+__device__ __forceinline__ void h_xr_body(HarmonicState *st, int it, const cplx *__restrict__ p,
+                                          const cplx *__restrict__ sv, const cplx *__restrict__ as,
+                                          const cplx *__restrict__ r0, cplx *__restrict__ x, cplx *__restrict__ r,
+                                          int64_t n, int64_t nchunk, double *__restrict__ part, double *lds)
+{
     if (st->stop_s < it || st->stop_r != INT_MAX) return;
     double v[4]; // ||S||^2, <AS, S>, <AS, AS>
     h_collapse<4>(v, part, HP_SS, gridDim.x, lds);
@@ -358,12 +374,20 @@ __global__ __launch_bounds__(EC3D_THREADS) void k_h_xr(HarmonicState *st, int it
     h_leave<3>(acc, part, HP_RR, lds);
 }
 
-__global__ __launch_bounds__(EC3D_THREADS) void k_h_p(HarmonicState *st, int it, const cplx *__restrict__ r,
-                                                     const cplx *__restrict__ ap, cplx *__restrict__ p,
-                                                     cplx *__restrict__ r0, int64_t n, int64_t nchunk,
-                                                     const double *__restrict__ part)
+__global__ __launch_bounds__(EC3D_THREADS) void k_h_xr(HarmonicState *st, int it, const cplx *__restrict__ p,
+                                                      const cplx *__restrict__ sv, const cplx *__restrict__ as,
+                                                      const cplx *__restrict__ r0, cplx *__restrict__ x,
+                                                      cplx *__restrict__ r, int64_t n, int64_t nchunk,
+                                                      double *__restrict__ part)
 {
-    __shared__ double lds[12];
+    __shared__ double lds[16];
+    h_xr_body(st, it, p, sv, as, r0, x, r, n, nchunk, part, lds);
+}
+
+__device__ __forceinline__ void h_p_body(HarmonicState *st, int it, const cplx *__restrict__ r,
+                                         const cplx *__restrict__ ap, cplx *__restrict__ p, cplx *__restrict__ r0,
+                                         int64_t n, int64_t nchunk, const double *__restrict__ part, double *lds)
+{
     if (st->stop_s != INT_MAX || st->stop_r < it) return;
     double v[3]; // ||R||^2, <R0, R>
     h_collapse<3>(v, part, HP_RR, gridDim.x, lds);
@@ -399,6 +423,73 @@ __global__ __launch_bounds__(EC3D_THREADS) void k_h_p(HarmonicState *st, int it,
                 p[i] = cplx{a.x + t.x, a.y + t.y};
             }
         }
+}
+
+__global__ __launch_bounds__(EC3D_THREADS) void k_h_p(HarmonicState *st, int it, const cplx *__restrict__ r,
+                                                     const cplx *__restrict__ ap, cplx *__restrict__ p,
+                                                     cplx *__restrict__ r0, int64_t n, int64_t nchunk,
+                                                     const double *__restrict__ part)
+{
+    __shared__ double lds[12];
+    h_p_body(st, it, r, ap, p, r0, n, nchunk, part, lds);
+}
+
+// ---- a batch of systems in lock step (ec3d_harmonic_batch_*) -----------------------------------
+// blockIdx.y is the system: its state, partials, table and vectors stand `sys` strides further, and the workgroup then
+// runs the body of the single kernel.  h_leave and h_collapse index with gridDim.x and blockIdx.x only, so the sums of
+// system s are the sums of its own single solve; a stopped system's workgroups return at their first load.
+struct HBatch {
+    cplx *vec;            // system s, vector w: vec + (s * HV_N + w) * len
+    double *part;         // system s: part + s * HP_NSLOT * gridDim.x
+    HarmonicState *state; // system s: state + s
+    int64_t len;
+};
+__device__ __forceinline__ cplx *hb_vec(const HBatch &B, int w) { return B.vec + ((int64_t)blockIdx.y * HV_N + w) * B.len; }
+__device__ __forceinline__ double *hb_part(const HBatch &B) { return B.part + (int64_t)blockIdx.y * HP_NSLOT * gridDim.x; }
+
+// k_h_spmv<MODE> on system blockIdx.y: st, part and the vectors are system 0's, the next system's stand 1 state,
+// HP_NSLOT * gridDim.x partials and `vstride` pairs further; A.table is system 0's table.  The vectors come as arguments
+// of their own, __restrict__ as k_h_spmv's: behind one base pointer the same body takes 98 VGPRs instead of 72
+template <int MODE>
+__global__ __launch_bounds__(EC3D_THREADS) void k_hb_spmv(HSav A, const HarmonicState *st, const cplx *__restrict__ x,
+                                                         const cplx *__restrict__ o, cplx *__restrict__ y,
+                                                         cplx *__restrict__ r0, cplx *__restrict__ p, int64_t nchunk,
+                                                         double *__restrict__ part, int64_t vstride)
+{
+    static_assert(MODE >= 1 && MODE <= 3, "the batch has the begin launch and the two products of an iteration");
+    extern __shared__ cplx tbl[];
+    __shared__ double lds[12];
+    const int64_t sys = blockIdx.y, v = sys * vstride;
+    h_spmv_modes<MODE, false>(A, A.table + sys * A.ncls * 16, st + sys, x + v, MODE == 2 ? nullptr : o + v, y + v,
+                              MODE == 3 ? r0 + v : nullptr, MODE == 3 ? p + v : nullptr, nchunk,
+                              part + sys * HP_NSLOT * gridDim.x, tbl, lds);
+}
+
+// one workgroup per system (grid (1, S)) behind k_hb_spmv<3> on (G, S)
+__global__ __launch_bounds__(EC3D_THREADS) void k_hb_setup(HBatch B, int G, double tol)
+{
+    __shared__ double lds[8];
+    h_setup_body(B.state + blockIdx.y, B.part + (int64_t)blockIdx.y * HP_NSLOT * G, G, tol, lds);
+}
+
+__global__ __launch_bounds__(EC3D_THREADS) void k_hb_s(HBatch B, int it, int64_t n, int64_t nchunk)
+{
+    __shared__ double lds[8];
+    h_s_body(B.state + blockIdx.y, it, hb_vec(B, HV_R), hb_vec(B, HV_AP), hb_vec(B, HV_S), n, nchunk, hb_part(B), lds);
+}
+
+__global__ __launch_bounds__(EC3D_THREADS) void k_hb_xr(HBatch B, int it, int64_t n, int64_t nchunk)
+{
+    __shared__ double lds[16];
+    h_xr_body(B.state + blockIdx.y, it, hb_vec(B, HV_P), hb_vec(B, HV_S), hb_vec(B, HV_AS), hb_vec(B, HV_R0), hb_vec(B, HV_X),
+              hb_vec(B, HV_R), n, nchunk, hb_part(B), lds);
+}
+
+__global__ __launch_bounds__(EC3D_THREADS) void k_hb_p(HBatch B, int it, int64_t n, int64_t nchunk)
+{
+    __shared__ double lds[12];
+    h_p_body(B.state + blockIdx.y, it, hb_vec(B, HV_R), hb_vec(B, HV_AP), hb_vec(B, HV_P), hb_vec(B, HV_R0), n, nchunk, hb_part(B),
+             lds);
 }
 
 // ---- left null vectors: the streaming kernels of the set-up and of the projection -------------
@@ -616,6 +707,16 @@ int run_iterations(ec3d_ctx *c, HOp op, cplx *x, int64_t itmax, HarmonicState &s
     return 0;
 }
 
+// iter, restarts, stop_kind and relres of a solve from its last state; total = itmax + 1 iterations were allowed
+void h_report(ec3d_harmonic_info &o, const HarmonicState &st, bool stopped, int64_t total)
+{
+    o.iter = stopped ? std::min(st.stop_s, st.stop_r) : (int32_t)std::max<int64_t>(total, 0);
+    o.restarts = st.restarts;
+    o.stop_kind = st.stop_s != INT_MAX ? 1 : (st.stop_r != INT_MAX && st.stop_r > 0 ? 2 : 0);
+    const double last_norm = o.stop_kind == 1 ? st.snorm : st.rnorm;
+    o.relres = st.bnorm > 0.0 ? last_norm / st.bnorm : 0.0;
+}
+
 // what every entry point refuses first; ready: ec3d_harmonic_setup must have run
 int h_need(ec3d_ctx *c, const char *who, bool ready)
 {
@@ -638,6 +739,17 @@ int h_need(ec3d_ctx *c, const char *who, bool ready)
     return 0;
 }
 
+// the (re, omega m) pairs of one operator from the two tables of ec3d_assemble
+std::vector<double> h_table(const std::vector<double> &re, const std::vector<double> &m, double omega)
+{
+    std::vector<double> tab(2 * re.size());
+    for (size_t q = 0; q < re.size(); ++q) {
+        tab[2 * q] = re[q];
+        tab[2 * q + 1] = omega * m[q]; // one rounding per entry
+    }
+    return tab;
+}
+
 int h_which(int which, const char *who)
 {
     if (which == EC3D_VEC_X || which == EC3D_VEC_B) return 0;
@@ -645,11 +757,11 @@ int h_which(int which, const char *who)
     return 2;
 }
 
-int h_to_device(ec3d_ctx *c, cplx *dst, const double *re, const double *im)
+// stage: 2 * n_pad doubles of staging, the single solve's (H.stage) or the batch's (H.bstage)
+int h_to_device(ec3d_ctx *c, double *stage, cplx *dst, const double *re, const double *im)
 {
-    Harmonic &H = c->harm;
     const int64_t len = c->A.n_pad;
-    double *sre = H.stage, *sim = H.stage.get() + len;
+    double *sre = stage, *sim = stage + len;
     int rc;
     if ((rc = ec3d_vec_h2d(c, sre, re))) return rc;
     if (im) {
@@ -662,10 +774,9 @@ int h_to_device(ec3d_ctx *c, cplx *dst, const double *re, const double *im)
     return 0;
 }
 
-int h_to_host(ec3d_ctx *c, const cplx *src, double *re, double *im)
+int h_to_host(ec3d_ctx *c, double *stage, const cplx *src, double *re, double *im)
 {
-    Harmonic &H = c->harm;
-    double *sre = H.stage, *sim = H.stage.get() + c->A.n_pad;
+    double *sre = stage, *sim = stage + c->A.n_pad;
     k_h_unpack<<<blocks(c->A.n), 256, 0, c->stream>>>(src, sre, sim, c->A.n);
     EC3D_HIP(hipGetLastError());
     int rc;
@@ -802,6 +913,137 @@ int null_note(ec3d_ctx *c, double bnorm)
     return 0;
 }
 
+// ---- the batch ---------------------------------------------------------------------------------
+HBatch batch_of(const ec3d_ctx *c)
+{
+    const Harmonic &H = c->harm;
+    HBatch B;
+    B.vec = reinterpret_cast<cplx *>(H.bvec.get());
+    B.part = H.bpart.get();
+    B.state = H.bstate.get();
+    B.len = c->A.n_pad;
+    return B;
+}
+
+// the matrix with system 0's table of the batch
+HSav batch_view_of(const ec3d_ctx *c)
+{
+    HSav T = view_of(c);
+    T.table = reinterpret_cast<const cplx *>(c->harm.btab.get());
+    return T;
+}
+
+cplx *hbv(const ec3d_ctx *c, int sys, int w)
+{
+    return reinterpret_cast<cplx *>(c->harm.bvec.get()) + ((size_t)sys * HV_N + (size_t)w) * (size_t)c->A.n_pad;
+}
+
+void batch_free(ec3d_ctx *c)
+{
+    Harmonic &H = c->harm;
+    H.bvec.reset();
+    H.btab.reset();
+    H.bpart.reset();
+    H.bstage.reset();
+    H.bstate.reset();
+    H.bn = 0;
+    H.bwgs = 0;
+    H.bbytes = 0;
+    for (auto &o : H.bomega) o = 0.0;
+    for (auto &l : H.blast) l = ec3d_harmonic_info{};
+}
+
+// everything of a batch of S systems; the caller frees the batch when this fails
+int batch_alloc(ec3d_ctx *c, int S, const std::vector<double> &tabs)
+{
+    Harmonic &H = c->harm;
+    const size_t nt = (size_t)c->A.ncls * 16, len = (size_t)c->A.n_pad;
+    const int G = ec3d_stream_wgs((int64_t)len);
+    EC3D_HIP(H.bvec.alloc((size_t)S * HV_N * 2 * len));
+    EC3D_HIP(H.btab.alloc((size_t)S * 2 * nt));
+    EC3D_HIP(H.bpart.alloc((size_t)S * HP_NSLOT * G));
+    EC3D_HIP(H.bstage.alloc(2 * len));
+    EC3D_HIP(H.bstate.alloc((size_t)S));
+    EC3D_HIP(hipMemsetAsync(H.bvec, 0, (size_t)S * HV_N * 2 * len * sizeof(double), c->stream));
+    EC3D_HIP(hipMemsetAsync(H.bpart, 0, (size_t)S * HP_NSLOT * G * sizeof(double), c->stream));
+    EC3D_HIP(hipMemsetAsync(H.bstage, 0, 2 * len * sizeof(double), c->stream));
+    EC3D_HIP(hipMemsetAsync(H.bstate, 0, (size_t)S * sizeof(HarmonicState), c->stream));
+    EC3D_HIP(hipMemcpy(H.btab, tabs.data(), (size_t)S * 2 * nt * sizeof(double), hipMemcpyHostToDevice));
+    EC3D_HIP(hipStreamSynchronize(c->stream));
+    H.bwgs = G;
+    H.bbytes = (int64_t)(((size_t)S * HV_N * 2 * len + (size_t)S * 2 * nt + (size_t)S * HP_NSLOT * G + 2 * len) * sizeof(double) +
+                         (size_t)S * sizeof(HarmonicState));
+    return 0;
+}
+
+// h_need and: a batch exists, sys is one of its systems (sys < 0: not asked)
+int hb_need(ec3d_ctx *c, const char *who, int32_t sys, bool any_sys)
+{
+    int rc = h_need(c, who, false);
+    if (rc) return rc;
+    const Harmonic &H = c->harm;
+    if (H.bn == 0) {
+        ec3d_set_error(std::string(who) + ": call ec3d_harmonic_batch_setup first");
+        return 2;
+    }
+    if (!any_sys && (sys < 0 || sys >= H.bn)) {
+        ec3d_set_error(std::string(who) + ": system " + std::to_string(sys) + " is outside the batch of " + std::to_string(H.bn));
+        return 2;
+    }
+    return 0;
+}
+
+void batch_launch_begin(ec3d_ctx *c, double tol)
+{
+    const Harmonic &H = c->harm;
+    const dim3 grid((unsigned)H.bwgs, (unsigned)H.bn);
+    const size_t lds = (size_t)c->A.ncls * 16 * sizeof(cplx);
+    const HBatch B = batch_of(c);
+    k_hb_spmv<3><<<grid, EC3D_THREADS, lds, c->stream>>>(batch_view_of(c), B.state, hbv(c, 0, HV_X), hbv(c, 0, HV_B), hbv(c, 0, HV_R),
+                                                         hbv(c, 0, HV_R0), hbv(c, 0, HV_P), c->A.n_pad / EC3D_TILE, B.part,
+                                                         (int64_t)HV_N * B.len);
+    k_hb_setup<<<dim3(1, (unsigned)H.bn), EC3D_THREADS, 0, c->stream>>>(B, H.bwgs, tol);
+}
+
+// one lock-step iteration: the five launches of launch_iteration, every system in each
+void batch_launch_iteration(ec3d_ctx *c, int it)
+{
+    const Harmonic &H = c->harm;
+    const dim3 grid((unsigned)H.bwgs, (unsigned)H.bn);
+    const size_t lds = (size_t)c->A.ncls * 16 * sizeof(cplx);
+    const int64_t n = c->A.n, nc = c->A.n_pad / EC3D_TILE;
+    const HBatch B = batch_of(c);
+    const HSav A = batch_view_of(c);
+    const int64_t vs = (int64_t)HV_N * B.len;
+    hipStream_t s = c->stream;
+    k_hb_spmv<1><<<grid, EC3D_THREADS, lds, s>>>(A, B.state, hbv(c, 0, HV_P), hbv(c, 0, HV_R0), hbv(c, 0, HV_AP), nullptr, nullptr, nc,
+                                                 B.part, vs);
+    k_hb_s<<<grid, EC3D_THREADS, 0, s>>>(B, it, n, nc);
+    k_hb_spmv<2><<<grid, EC3D_THREADS, lds, s>>>(A, B.state, hbv(c, 0, HV_S), nullptr, hbv(c, 0, HV_AS), nullptr, nullptr, nc, B.part, vs);
+    k_hb_xr<<<grid, EC3D_THREADS, 0, s>>>(B, it, n, nc);
+    k_hb_p<<<grid, EC3D_THREADS, 0, s>>>(B, it, n, nc);
+}
+
+// run_iterations for a batch: 16 lock-step iterations per poll, all the states in one copy, on while any system runs
+int batch_run_iterations(ec3d_ctx *c, int64_t itmax, std::vector<HarmonicState> &st)
+{
+    const Harmonic &H = c->harm;
+    const int64_t total = itmax + 1;
+    int64_t launched = 0;
+    bool running;
+    st.resize((size_t)H.bn);
+    do {
+        const int64_t m = std::min<int64_t>(16, total - launched);
+        for (int64_t i = 0; i < m; ++i) batch_launch_iteration(c, (int)(++launched));
+        EC3D_HIP(hipGetLastError());
+        EC3D_HIP(hipMemcpyAsync(st.data(), H.bstate, st.size() * sizeof(HarmonicState), hipMemcpyDeviceToHost, c->stream));
+        EC3D_HIP(hipStreamSynchronize(c->stream));
+        running = false;
+        for (const HarmonicState &q : st) running = running || (q.stop_s == INT_MAX && q.stop_r == INT_MAX);
+    } while (launched < total && running);
+    return 0;
+}
+
 } // namespace
 
 void ec3d_harmonic_null_free(ec3d_ctx *c)
@@ -821,6 +1063,7 @@ void ec3d_harmonic_free(ec3d_ctx *c)
 {
     Harmonic &H = c->harm;
     ec3d_harmonic_null_free(c); // (the setting stays with the handle)
+    batch_free(c);
     H.re.reset();
     H.m.reset();
     H.tab.reset();
@@ -847,13 +1090,10 @@ extern "C" int ec3d_harmonic_setup(ec3d_handle c, double omega)
     EC3D_HIP(hipStreamSynchronize(c->stream));
     if (!(H.ready && omega == H.omega)) ec3d_harmonic_null_free(c); // Q belongs to the matrix and to omega
     const size_t nt = (size_t)c->A.ncls * 16, len = (size_t)c->A.n_pad;
-    std::vector<double> re(nt), m(nt), tab(2 * nt);
+    std::vector<double> re(nt), m(nt);
     EC3D_HIP(hipMemcpy(re.data(), H.re, nt * sizeof(double), hipMemcpyDeviceToHost));
     EC3D_HIP(hipMemcpy(m.data(), H.m, nt * sizeof(double), hipMemcpyDeviceToHost));
-    for (size_t q = 0; q < nt; ++q) {
-        tab[2 * q] = re[q];
-        tab[2 * q + 1] = omega * m[q]; // one rounding per entry
-    }
+    const std::vector<double> tab = h_table(re, m, omega);
     if (!H.tab) EC3D_HIP(H.tab.alloc(2 * nt));
     EC3D_HIP(hipMemcpy(H.tab, tab.data(), 2 * nt * sizeof(double), hipMemcpyHostToDevice));
     if (!H.vec_own) { // the first set-up on this matrix: vectors (zero), staging, partials, state
@@ -888,7 +1128,7 @@ extern "C" int ec3d_harmonic_upload(ec3d_handle c, int which, const double *re, 
         ec3d_set_error("ec3d_harmonic_upload: re is NULL");
         return 2;
     }
-    if ((rc = h_to_device(c, hv(c, which == EC3D_VEC_X ? HV_X : HV_B), re, im))) return rc;
+    if ((rc = h_to_device(c, c->harm.stage, hv(c, which == EC3D_VEC_X ? HV_X : HV_B), re, im))) return rc;
     EC3D_HIP(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -902,7 +1142,7 @@ extern "C" int ec3d_harmonic_download(ec3d_handle c, int which, double *re, doub
         ec3d_set_error("ec3d_harmonic_download: re or im is NULL");
         return 2;
     }
-    return h_to_host(c, hv(c, which == EC3D_VEC_X ? HV_X : HV_B), re, im);
+    return h_to_host(c, c->harm.stage, hv(c, which == EC3D_VEC_X ? HV_X : HV_B), re, im);
 }
 
 extern "C" int ec3d_harmonic_spmv(ec3d_handle c, const double *xre, const double *xim, double *yre, double *yim)
@@ -915,12 +1155,12 @@ extern "C" int ec3d_harmonic_spmv(ec3d_handle c, const double *xre, const double
     }
     const cplx *x = hv(c, HV_X);
     if (xre) {
-        if ((rc = h_to_device(c, hv(c, HV_P), xre, xim))) return rc;
+        if ((rc = h_to_device(c, c->harm.stage, hv(c, HV_P), xre, xim))) return rc;
         x = hv(c, HV_P);
     }
     launch_spmv<0>(c, H_A, x, nullptr, hv(c, HV_AP), nullptr, nullptr);
     EC3D_HIP(hipGetLastError());
-    return h_to_host(c, hv(c, HV_AP), yre, yim);
+    return h_to_host(c, c->harm.stage, hv(c, HV_AP), yre, yim);
 }
 
 extern "C" int ec3d_harmonic_solve(ec3d_handle c, double tol, int32_t itmax, int32_t *iter, double *relres)
@@ -936,11 +1176,7 @@ extern "C" int ec3d_harmonic_solve(ec3d_handle c, double tol, int32_t itmax, int
     const int64_t total = (int64_t)itmax + 1; // src/solvers.f90:25-29: itmax + 1 iterations
     bool stopped = false;
     if ((rc = run_iterations(c, H_A, hv(c, HV_X), itmax, st, &stopped))) return rc;
-    H.last.iter = stopped ? std::min(st.stop_s, st.stop_r) : (int32_t)std::max<int64_t>(total, 0);
-    H.last.restarts = st.restarts;
-    H.last.stop_kind = st.stop_s != INT_MAX ? 1 : (st.stop_r != INT_MAX && st.stop_r > 0 ? 2 : 0);
-    const double last_norm = H.last.stop_kind == 1 ? st.snorm : st.rnorm;
-    H.last.relres = st.bnorm > 0.0 ? last_norm / st.bnorm : 0.0;
+    h_report(H.last, st, stopped, total);
     H.last.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
     if (iter) *iter = H.last.iter;
     if (relres) *relres = H.last.relres;
@@ -1070,7 +1306,7 @@ extern "C" int ec3d_harmonic_left_null_vector(ec3d_handle c, int32_t index, doub
                        std::to_string(H.null_kept) + " vectors kept, or a NULL argument");
         return 2;
     }
-    return h_to_host(c, reinterpret_cast<const cplx *>(H.nq.get()) + (size_t)index * c->A.n_pad, re, im);
+    return h_to_host(c, H.stage, reinterpret_cast<const cplx *>(H.nq.get()) + (size_t)index * c->A.n_pad, re, im);
 }
 
 extern "C" int ec3d_harmonic_spmv_h(ec3d_handle c, const double *xre, const double *xim, double *yre, double *yim)
@@ -1083,12 +1319,12 @@ extern "C" int ec3d_harmonic_spmv_h(ec3d_handle c, const double *xre, const doub
     }
     const cplx *x = hv(c, HV_X);
     if (xre) {
-        if ((rc = h_to_device(c, hv(c, HV_P), xre, xim))) return rc;
+        if ((rc = h_to_device(c, c->harm.stage, hv(c, HV_P), xre, xim))) return rc;
         x = hv(c, HV_P);
     }
     launch_spmv<0>(c, H_AH, x, nullptr, hv(c, HV_AP), nullptr, nullptr);
     EC3D_HIP(hipGetLastError());
-    return h_to_host(c, hv(c, HV_AP), yre, yim);
+    return h_to_host(c, c->harm.stage, hv(c, HV_AP), yre, yim);
 }
 
 extern "C" int ec3d_harmonic_projected_residual(ec3d_handle c, double *rel, double *removed)
@@ -1120,5 +1356,142 @@ extern "C" int ec3d_harmonic_null_restarts(ec3d_handle c, int32_t *restarts)
         return 2;
     }
     for (int i = 0; i < EC3D_NULL_MAX_REPORT; ++i) restarts[i] = c->harm.null_restarts[i];
+    return 0;
+}
+
+// ---- a batch of systems in lock step ----------------------------------------------------------
+extern "C" int ec3d_harmonic_batch_setup(ec3d_handle c, int32_t nsys, const double *omega)
+{
+    int rc = h_need(c, "ec3d_harmonic_batch_setup", false);
+    if (rc) return rc;
+    if (nsys < 0 || nsys > EC3D_HARMONIC_MAX_BATCH) {
+        ec3d_set_error("ec3d_harmonic_batch_setup: nsys must be in [0, " + std::to_string(EC3D_HARMONIC_MAX_BATCH) + "]");
+        return 2;
+    }
+    Harmonic &H = c->harm;
+    if (nsys == 0) {
+        EC3D_HIP(hipStreamSynchronize(c->stream));
+        batch_free(c);
+        return 0;
+    }
+    if (!omega) {
+        ec3d_set_error("ec3d_harmonic_batch_setup: omega is NULL");
+        return 2;
+    }
+    for (int32_t s = 0; s < nsys; ++s)
+        if (!(omega[s] >= 0.0) || !std::isfinite(omega[s])) {
+            ec3d_set_error("ec3d_harmonic_batch_setup: omega[" + std::to_string(s) + "] must be finite and not negative");
+            return 2;
+        }
+    EC3D_HIP(hipStreamSynchronize(c->stream));
+    const size_t nt = (size_t)c->A.ncls * 16;
+    std::vector<double> re(nt), m(nt), tabs;
+    EC3D_HIP(hipMemcpy(re.data(), H.re, nt * sizeof(double), hipMemcpyDeviceToHost));
+    EC3D_HIP(hipMemcpy(m.data(), H.m, nt * sizeof(double), hipMemcpyDeviceToHost));
+    tabs.reserve((size_t)nsys * 2 * nt);
+    for (int32_t s = 0; s < nsys; ++s) {
+        const std::vector<double> t = h_table(re, m, omega[s]);
+        tabs.insert(tabs.end(), t.begin(), t.end());
+    }
+    batch_free(c); // nothing is refused from here on: the batch before goes, whatever its size
+    if ((rc = batch_alloc(c, nsys, tabs))) {
+        batch_free(c);
+        return rc;
+    }
+    H.bn = nsys;
+    for (int32_t s = 0; s < nsys; ++s) {
+        H.bomega[s] = omega[s];
+        H.blast[s].ready = 1;
+        H.blast[s].omega = omega[s];
+        H.blast[s].device_bytes = H.bbytes;
+    }
+    return 0;
+}
+
+extern "C" int ec3d_harmonic_batch_upload(ec3d_handle c, int32_t sys, int which, const double *re, const double *im)
+{
+    int rc = hb_need(c, "ec3d_harmonic_batch_upload", sys, false);
+    if (rc) return rc;
+    if ((rc = h_which(which, "ec3d_harmonic_batch_upload"))) return rc;
+    if (!re) {
+        ec3d_set_error("ec3d_harmonic_batch_upload: re is NULL");
+        return 2;
+    }
+    if ((rc = h_to_device(c, c->harm.bstage, hbv(c, sys, which == EC3D_VEC_X ? HV_X : HV_B), re, im))) return rc;
+    EC3D_HIP(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+extern "C" int ec3d_harmonic_batch_download(ec3d_handle c, int32_t sys, int which, double *re, double *im)
+{
+    int rc = hb_need(c, "ec3d_harmonic_batch_download", sys, false);
+    if (rc) return rc;
+    if ((rc = h_which(which, "ec3d_harmonic_batch_download"))) return rc;
+    if (!re || !im) {
+        ec3d_set_error("ec3d_harmonic_batch_download: re or im is NULL");
+        return 2;
+    }
+    return h_to_host(c, c->harm.bstage, hbv(c, sys, which == EC3D_VEC_X ? HV_X : HV_B), re, im);
+}
+
+extern "C" int ec3d_harmonic_batch_solve(ec3d_handle c, double tol, int32_t itmax, int32_t *iter)
+{
+    int rc = hb_need(c, "ec3d_harmonic_batch_solve", 0, true);
+    if (rc) return rc;
+    Harmonic &H = c->harm;
+    if (H.null_on) {
+        ec3d_set_error("ec3d_harmonic_batch_solve: ec3d_harmonic_set_null_projection is on, and its vectors belong to one omega; "
+                       "switch it off, or solve the systems one by one (ec3d_harmonic_batch_select)");
+        return 2;
+    }
+    const auto t_start = std::chrono::steady_clock::now();
+    batch_launch_begin(c, tol);
+    EC3D_HIP(hipGetLastError());
+    std::vector<HarmonicState> st;
+    if ((rc = batch_run_iterations(c, itmax, st))) return rc;
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    for (int s = 0; s < H.bn; ++s) {
+        const HarmonicState &q = st[(size_t)s];
+        h_report(H.blast[s], q, q.stop_s != INT_MAX || q.stop_r != INT_MAX, (int64_t)itmax + 1);
+        H.blast[s].ms = ms;
+        if (iter) iter[s] = H.blast[s].iter;
+    }
+    return 0;
+}
+
+extern "C" int ec3d_get_harmonic_batch(ec3d_handle c, int32_t sys, ec3d_harmonic_info *out)
+{
+    int rc = hb_need(c, "ec3d_get_harmonic_batch", sys, false);
+    if (rc) return rc;
+    if (!out) {
+        ec3d_set_error("ec3d_get_harmonic_batch: info is NULL");
+        return 2;
+    }
+    *out = c->harm.blast[sys];
+    return 0;
+}
+
+extern "C" int ec3d_harmonic_batch_select(ec3d_handle c, int32_t sys)
+{
+    int rc = hb_need(c, "ec3d_harmonic_batch_select", sys, false);
+    if (rc) return rc;
+    if ((rc = ec3d_harmonic_setup(c, c->harm.bomega[sys]))) return rc;
+    const size_t bytes = (size_t)c->A.n_pad * sizeof(cplx);
+    EC3D_HIP(hipMemcpyAsync(hv(c, HV_X), hbv(c, sys, HV_X), bytes, hipMemcpyDeviceToDevice, c->stream));
+    EC3D_HIP(hipMemcpyAsync(hv(c, HV_B), hbv(c, sys, HV_B), bytes, hipMemcpyDeviceToDevice, c->stream));
+    EC3D_HIP(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+extern "C" int ec3d_harmonic_batch_device_vector(ec3d_handle c, int32_t sys, int which, double **device_ptr, int64_t *pairs)
+{
+    int rc = hb_need(c, "ec3d_harmonic_batch_device_vector", sys, false);
+    if (rc) return rc;
+    if (which < 0 || which >= HV_N || !device_ptr || !pairs) {
+        ec3d_set_error("ec3d_harmonic_batch_device_vector: unknown vector or NULL argument");
+        return 2;
+    }
+    *device_ptr = reinterpret_cast<double *>(hbv(c, sys, which));
+    *pairs = c->A.n_pad;
     return 0;
 }

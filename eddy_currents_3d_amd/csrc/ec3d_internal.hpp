@@ -447,6 +447,17 @@ struct Harmonic {
     int64_t null_bytes = 0;
     ec3d_null_info null_last{};
     int32_t null_restarts[EC3D_NULL_MAX_REPORT] = {0}; // of the adjoint solves (tests; ec3d_null_info has no room)
+    // ec3d_harmonic_batch_* (DESIGN section 18b): nsys systems (omega_s, b^_s, x^_s) solved in lock step on this matrix.
+    // Storage of its own, made by ec3d_harmonic_batch_setup only: system s has its HV_N vectors at
+    // bvec + s * HV_N * 2 * n_pad, its table at btab + s * 2 * ncls * 16, its partials at bpart + s * HP_NSLOT * bwgs
+    // and bstate[s].  Belongs to the matrix; ec3d_harmonic_setup leaves it alone.
+    int bn = 0;
+    double bomega[EC3D_HARMONIC_MAX_BATCH] = {0.0};
+    DevBuf<double> bvec, btab, bpart, bstage; // bstage: [2 * n_pad], the host copies of the batch
+    DevBuf<HarmonicState> bstate;
+    int bwgs = 0;
+    int64_t bbytes = 0;
+    ec3d_harmonic_info blast[EC3D_HARMONIC_MAX_BATCH] = {};
 };
 
 struct ec3d_ctx {

@@ -34,7 +34,10 @@ module ec3d_hip
               ec3d_harmonic_setup, ec3d_harmonic_upload, ec3d_harmonic_download, ec3d_harmonic_spmv, ec3d_harmonic_solve, &
               ec3d_harmonic_true_residual, ec3d_harmonic_load, ec3d_get_harmonic, ec3d_harmonic_info, &
               ec3d_harmonic_set_null_projection, ec3d_get_harmonic_null, ec3d_harmonic_left_null_vector, &
-              ec3d_harmonic_spmv_h, ec3d_harmonic_projected_residual, ec3d_harmonic_null_restarts
+              ec3d_harmonic_spmv_h, ec3d_harmonic_projected_residual, ec3d_harmonic_null_restarts, &
+              EC3D_HARMONIC_MAX_BATCH, ec3d_harmonic_batch_setup, ec3d_harmonic_batch_upload, &
+              ec3d_harmonic_batch_download, ec3d_harmonic_batch_solve, ec3d_get_harmonic_batch, &
+              ec3d_harmonic_batch_select, ec3d_harmonic_batch_device_vector
 
     integer(c_int), parameter :: EC3D_VEC_X = 0, EC3D_VEC_B = 1   ! Uaf, Jaf
     integer(c_int), parameter :: EC3D_PRECOND_NONE = 0, EC3D_PRECOND_MG = 1   ! ec3d_set_preconditioner
@@ -85,6 +88,7 @@ module ec3d_hip
 
     integer(c_int32_t), parameter :: EC3D_PROBE_NCOMP = 13   ! values per probe: a(3), eddy(3), source(3), b(3), u
     integer(c_int), parameter :: EC3D_PROBE_E_FULL = 24      ! ec3d_probe_record on a full buffer
+    integer(c_int), parameter :: EC3D_HARMONIC_MAX_BATCH = 16   ! systems of one ec3d_harmonic_batch_setup
 
     ! what ec3d_get_probes reports (ec3d_probe_info of include/ec3d_hip.h)
     type, bind(C) :: ec3d_probe_info
@@ -487,6 +491,60 @@ module ec3d_hip
             import :: c_ptr, c_int, c_int32_t
             type(c_ptr), value :: h
             integer(c_int32_t), intent(out) :: restarts(*)
+        end function
+        ! A batch of harmonic systems (omega_s, b^_s, x^_s) solved in lock step on the one matrix (include/ec3d_hip.h;
+        ! opt-in): nsys in [1, EC3D_HARMONIC_MAX_BATCH], nsys = 0 frees the batch; sys is 0-based
+        integer(c_int) function ec3d_harmonic_batch_setup(h, nsys, omega) bind(C, name="ec3d_harmonic_batch_setup")
+            import :: c_ptr, c_int, c_int32_t, c_double
+            type(c_ptr), value :: h
+            integer(c_int32_t), value :: nsys
+            real(c_double), intent(in) :: omega(*)
+        end function
+        integer(c_int) function ec3d_harmonic_batch_upload(h, sys, which, re, im) bind(C, name="ec3d_harmonic_batch_upload")
+            import :: c_ptr, c_int, c_int32_t, c_double
+            type(c_ptr), value :: h
+            integer(c_int32_t), value :: sys
+            integer(c_int), value :: which
+            real(c_double), intent(in) :: re(*), im(*)
+        end function
+        integer(c_int) function ec3d_harmonic_batch_download(h, sys, which, re, im) &
+                bind(C, name="ec3d_harmonic_batch_download")
+            import :: c_ptr, c_int, c_int32_t, c_double
+            type(c_ptr), value :: h
+            integer(c_int32_t), value :: sys
+            integer(c_int), value :: which
+            real(c_double), intent(out) :: re(*), im(*)
+        end function
+        ! every system from its resident x^; iter: nsys entries
+        integer(c_int) function ec3d_harmonic_batch_solve(h, tol, itmax, iter) bind(C, name="ec3d_harmonic_batch_solve")
+            import :: c_ptr, c_int, c_int32_t, c_double
+            type(c_ptr), value :: h
+            real(c_double), value :: tol
+            integer(c_int32_t), value :: itmax
+            integer(c_int32_t), intent(out) :: iter(*)
+        end function
+        ! the report of system sys; ms and device_bytes are the whole batch's
+        integer(c_int) function ec3d_get_harmonic_batch(h, sys, info) bind(C, name="ec3d_get_harmonic_batch")
+            import :: c_ptr, c_int, c_int32_t, ec3d_harmonic_info
+            type(c_ptr), value :: h
+            integer(c_int32_t), value :: sys
+            type(ec3d_harmonic_info), intent(out) :: info
+        end function
+        ! ec3d_harmonic_setup(omega_sys), then x^_sys and b^_sys into the resident single X^ and B^
+        integer(c_int) function ec3d_harmonic_batch_select(h, sys) bind(C, name="ec3d_harmonic_batch_select")
+            import :: c_ptr, c_int, c_int32_t
+            type(c_ptr), value :: h
+            integer(c_int32_t), value :: sys
+        end function
+        ! complex vector `which` (EC3D_VEC_X ... 7) of system sys on the device: pairs = n_pad interleaved (re, im) pairs
+        integer(c_int) function ec3d_harmonic_batch_device_vector(h, sys, which, device_ptr, pairs) &
+                bind(C, name="ec3d_harmonic_batch_device_vector")
+            import :: c_ptr, c_int, c_int32_t, c_int64_t
+            type(c_ptr), value :: h
+            integer(c_int32_t), value :: sys
+            integer(c_int), value :: which
+            type(c_ptr), intent(out) :: device_ptr
+            integer(c_int64_t), intent(out) :: pairs
         end function
         ! U rows ec3d_rhs_step gives their right-hand side with several conducting domains (include/ec3d_hip.h)
         integer(c_int) function ec3d_set_u_rhs(h, rule) bind(C, name="ec3d_set_u_rhs")

@@ -514,6 +514,13 @@ def run_harmonic(model: vxc.VxcModel, solver, freq: float, tol: float | None = N
     true_res, bnorm = solver.harmonic_true_residual()
     out = dict(freq=float(freq), omega=omega, iter=it, relres=relres, true_residual=true_res, bnorm=bnorm,
                x=solver.harmonic_download("X"), b=b, parts=[{}, {}], info=info, **extra)
+    _harmonic_observables(model, solver, t, out, out_dir, integrals, probes, "harmonic")
+    return out
+
+
+def _harmonic_observables(model, solver, t, out, out_dir, integrals, probes, stem):
+    """The per-part observables of the resident single x^ and b^ into ``out`` (run_harmonic, run_harmonic_sweep): each
+    part loaded (harmonic_load), then the integrals, probes and <stem>_re.vtk / <stem>_im.vtk asked for."""
     sdz, sdy, sdx = model.vox.shape
     if probes is not None:
         from .probes import stack
@@ -529,7 +536,7 @@ def run_harmonic(model: vxc.VxcModel, solver, freq: float, tol: float | None = N
             rec["probes"] = stack(solver.probe_sample(t["delta"]))
         if out_dir:
             f = solver.vtk_fields(t["delta"], sdx * sdy * sdz, t["ncells0"] > 0)
-            rec["vtk"] = os.path.join(out_dir, f"harmonic_{name}.vtk")
+            rec["vtk"] = os.path.join(out_dir, f"{stem}_{name}.vtk")
             write_field_vtk(rec["vtk"], sdx, sdy, sdz, t["delta"], f)
     if integrals:
         out["integrals"] = [dict(domain=a["domain"], cells=a["cells"], sigma=a["sigma"],
@@ -537,7 +544,61 @@ def run_harmonic(model: vxc.VxcModel, solver, freq: float, tol: float | None = N
                             for a, c in zip(out["parts"][0]["integrals"], out["parts"][1]["integrals"])]
     if probes is not None:
         out["probes"] = out["parts"][0]["probes"] + 1j * out["parts"][1]["probes"]
-    return out
+
+
+HARMONIC_MAX_BATCH = 16     # EC3D_HARMONIC_MAX_BATCH of include/ec3d_hip.h
+
+
+def run_harmonic_sweep(model: vxc.VxcModel, solver, drive_freq: float, freqs, tol: float | None = None,
+                       itmax: int | None = None, out_dir: str | None = None, integrals: bool = False, probes=None,
+                       batch: int = HARMONIC_MAX_BATCH):
+    """A constant-current frequency sweep of ``model`` on ``solver`` (an EC3DSolver): b^ is built
+    ONCE from the source phasors the model's functions have at ``drive_freq`` (harmonic_rhs) and applied at every
+    frequency of ``freqs`` [Hz]; the systems (K + j 2 pi f M) x^ = b^ go through the solver's batch in groups of at most
+    ``batch`` (1 .. 16), in lock step and every x^ from 0, at the model's tolerance and iteration limit (or ``tol`` /
+    ``itmax``).  Per frequency the system is then selected (harmonic_batch_select) and gets run_harmonic's observables.
+    Returns a list, in the order of ``freqs``, of dicts with run_harmonic's keys; ``out_dir`` gets harmonic_<k>_re.vtk and
+    harmonic_<k>_im.vtk, k the position in ``freqs``.  There is no null projection inside a batch.  ValueError, before
+    anything is assembled, on moving sources, an empty list, a frequency that is not above 0 or a ``batch`` outside
+    [1, 16]."""
+    if not hasattr(solver, "harmonic_batch_setup"):
+        raise ValueError("run_harmonic_sweep needs an EC3DSolver: the harmonic solve runs on one undivided handle")
+    freqs = [float(f) for f in freqs]
+    if not freqs or not all(f > 0.0 and math.isfinite(f) for f in freqs):
+        raise ValueError("run_harmonic_sweep needs at least one frequency, every one finite and above 0")
+    if int(batch) != batch or not 1 <= int(batch) <= HARMONIC_MAX_BATCH:
+        raise ValueError(f"batch must be in [1, {HARMONIC_MAX_BATCH}], not {batch!r}")
+    batch = int(batch)
+    t = vxc.domain_tables(model)
+    if t["dt"] is None:
+        raise ValueError("the model has no 'tran stop=... step=...' line")
+    prog = SourceProgram(model, t)
+    n_ref = 3 * model.vox.size + t["ncells0"]
+    b = harmonic_rhs(prog, drive_freq, n_ref)       # (refuses moving sources before anything is assembled)
+    solver.assemble(t["geoPHYS"], t["geoPHYS_C"], t["valPHYS"], t["BND"], t["delta"], t["dt"])
+    tol = float(t["tol"] if tol is None else tol)
+    itmax = int(t["itmax"] if itmax is None else itmax)
+    zero = np.zeros(n_ref)
+    results = []
+    for k0 in range(0, len(freqs), batch):
+        group = freqs[k0:k0 + batch]
+        omegas = [2.0 * math.pi * f for f in group]
+        solver.harmonic_batch_setup(omegas)
+        for s in range(len(group)):
+            solver.harmonic_batch_upload(s, "B", b)
+            solver.harmonic_batch_upload(s, "X", zero)
+        solved = solver.harmonic_batch_solve(tol, itmax)
+        for s, (f, omega) in enumerate(zip(group, omegas)):
+            it, relres = solved[s]
+            info = solver.harmonic_batch_info(s)
+            solver.harmonic_batch_select(s)
+            true_res, bnorm = solver.harmonic_true_residual()
+            out = dict(freq=f, omega=omega, iter=it, relres=relres, true_residual=true_res, bnorm=bnorm,
+                       x=solver.harmonic_download("X"), b=b, parts=[{}, {}], info=info)
+            _harmonic_observables(model, solver, t, out, out_dir, integrals, probes, f"harmonic_{k0 + s}")
+            results.append(out)
+    solver.harmonic_batch_setup([])                  # the batch's memory goes; the last system stays selected
+    return results
 
 
 class _ProbeLog:

@@ -6,6 +6,8 @@
                                                   [--probe-box I0,J0,K0:I1,J1,K1]...]
     python -m eddy_currents_3d_amd.run model.vxc --harmonic FREQ [--out DIR] [--integrals FILE] [--tol X]
                                                  [--null-projection [--null-tol Y]]
+    python -m eddy_currents_3d_amd.run model.vxc --harmonic F0 --sweep F1,F2,... [--sweep-batch N] [--out DIR]
+                                                 [--integrals FILE] [--tol X]
     python -m torch.distributed.run --nproc-per-node G -m eddy_currents_3d_amd.run model.vxc ...   (G GPUs)
 
 Reads the file (eddy_currents_3d_amd/vxc.py), assembles the A-V system on the device, and runs the
@@ -25,6 +27,11 @@ solve (host.run_harmonic): ``harmonic_re.vtk`` and ``harmonic_im.vtk`` go to ``-
 loss and force of every conducting domain averaged over a period (one GPU only; moving sources are refused); with
 ``--null-projection`` the complex operator's left null vectors leave the initial residual, the
 report line gains the projected residual and the adjoint solves' iterations, and ``--null-precond`` is refused.
+``--harmonic F0 --sweep F1,F2,...``: a constant-current frequency sweep (host.run_harmonic_sweep) --
+the source phasors are read at F0 and the same b^ is solved at every frequency of the list, up to ``--sweep-batch N``
+(default and most: 16) of them in lock step in the launches of one iteration; ``harmonic_<k>_re.vtk`` and
+``harmonic_<k>_im.vtk``, k the position in the list, go to ``--out``, ``--integrals FILE`` gets one line per frequency and
+domain, and there is one report line per frequency; ``--null-projection`` is refused.
 """
 from __future__ import annotations
 
@@ -105,7 +112,64 @@ def build_parser():
     ap.add_argument("--harmonic", type=float, default=None, metavar="FREQ",
                     help="instead of the time loop: one complex solve for the periodic steady state at FREQ Hz; writes "
                          "harmonic_re.vtk / harmonic_im.vtk to --out and the period averages to --integrals (one GPU only)")
+    ap.add_argument("--sweep", default=None, metavar="F1,F2,...",
+                    help="with --harmonic F0: solve the right-hand side of F0's source phasors at each of these "
+                         "frequencies [Hz], batches of them in lock step; harmonic_<k>_re.vtk / harmonic_<k>_im.vtk per "
+                         "frequency to --out, one line per frequency and domain to --integrals")
+    ap.add_argument("--sweep-batch", type=int, default=16, metavar="N", choices=range(1, 17),
+                    help="systems of --sweep solved in one batch (1 .. 16, default 16)")
     return ap
+
+
+def check_sweep_options(ap, a):
+    """The refusals of --sweep that need no model; returns the frequencies (None without --sweep)."""
+    if a.sweep is None:
+        return None
+    if a.harmonic is None:
+        ap.error("--sweep needs --harmonic F0, the frequency at which the sources' phasors are read")
+    if a.null_projection:
+        ap.error("--sweep does not go with --null-projection: the left null vectors belong to one frequency")
+    try:
+        freqs = [float(w) for w in a.sweep.split(",") if w.strip()]
+    except ValueError:
+        ap.error(f"--sweep needs a list of frequencies F1,F2,..., not {a.sweep!r}")
+    if not freqs:
+        ap.error("--sweep needs at least one frequency")
+    if not all(f > 0.0 and f < float("inf") for f in freqs):
+        ap.error("--sweep needs frequencies above 0")
+    return freqs
+
+
+def _write_harmonic_integrals(f, freq, records):
+    for q in records:
+        f.write(",".join([repr(float(freq)), str(q["domain"]), str(q["cells"]), repr(float(q["joule_w"]))]
+                         + [repr(float(v)) for v in q["force_n"]]) + "\n")
+
+
+def run_sweep_cli(ap, a, model, t, out_dir, freqs):
+    """--harmonic F0 --sweep F1,F2,...: host.run_harmonic_sweep and one report line per frequency."""
+    from . import EC3DSolver, host
+    if not a.harmonic > 0.0:
+        ap.error("--harmonic needs a frequency above 0")
+    t0 = time.perf_counter()
+    with EC3DSolver(device=a.device) as s:
+        try:
+            rs = host.run_harmonic_sweep(model, s, a.harmonic, freqs, tol=a.tol, out_dir=out_dir,
+                                         integrals=bool(a.integrals), batch=a.sweep_batch)
+        except ValueError as e:
+            ap.error(str(e))
+    if a.integrals:
+        with open(a.integrals, "w") as f:
+            f.write(HARMONIC_INTEGRALS_HEADER + "\n")
+            for r in rs:
+                _write_harmonic_integrals(f, r["freq"], r["integrals"])
+    for k, r in enumerate(rs):
+        print(f"harmonic sweep {k} at {r['freq']:g} Hz (phasors of {a.harmonic:g} Hz): iter={r['iter']} "
+              f"relres={r['relres']:.3e} true residual={r['true_residual']:.3e} restarts={r['info']['restarts']} "
+              f"({r['info']['ms']:.1f} ms in its batch's solve)"
+              + (f"  -> {out_dir}/harmonic_{k}_re.vtk, harmonic_{k}_im.vtk" if out_dir else ""), flush=True)
+    print(f"{len(rs)} frequencies in {time.perf_counter() - t0:.2f} s wall", flush=True)
+    return 0
 
 
 HARMONIC_INTEGRALS_HEADER = "freq,domain,cells,joule_w_avg,force_x_avg,force_y_avg,force_z_avg"
@@ -130,9 +194,7 @@ def run_harmonic_cli(ap, a, model, t, out_dir):
     if a.integrals:
         with open(a.integrals, "w") as f:
             f.write(HARMONIC_INTEGRALS_HEADER + "\n")
-            for q in r["integrals"]:
-                f.write(",".join([repr(float(a.harmonic)), str(q["domain"]), str(q["cells"]), repr(float(q["joule_w"]))]
-                                 + [repr(float(v)) for v in q["force_n"]]) + "\n")
+            _write_harmonic_integrals(f, a.harmonic, r["integrals"])
     null = (f"projected residual={r['projected_residual']:.3e} adjoint iterations="
             f"{'+'.join(str(q['iterations']) for q in r['null']['components'])} " if a.null_projection else "")
     print(f"harmonic solve at {a.harmonic:g} Hz: iter={r['iter']} relres={r['relres']:.3e} "
@@ -158,6 +220,7 @@ def main(argv=None):
     a = ap.parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     check_probe_options(ap, a, world)
+    sweep = check_sweep_options(ap, a)
     if world > 1 and a.integrals:
         ap.error("--integrals runs on one GPU only; a z-slab holds only part of a conducting domain")
     if world > 1 and a.energy:
@@ -175,6 +238,8 @@ def main(argv=None):
     if a.harmonic is not None:
         if world > 1:
             ap.error("--harmonic runs on one GPU only; the complex solve has no z-slab form")
+        if sweep is not None:
+            return run_sweep_cli(ap, a, model, t, out_dir, sweep)
         return run_harmonic_cli(ap, a, model, t, out_dir)
     pcells = None
     if a.probes:

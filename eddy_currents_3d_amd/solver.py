@@ -124,7 +124,11 @@ EXPORTS = ["sprsbcgstabwr_", "ec3d_invalidate", "ec3d_create", "ec3d_destroy", "
            "ec3d_harmonic_solve", "ec3d_harmonic_true_residual", "ec3d_harmonic_load", "ec3d_get_harmonic",
            "ec3d_harmonic_device_vector",
            "ec3d_harmonic_set_null_projection", "ec3d_get_harmonic_null", "ec3d_harmonic_left_null_vector",
-           "ec3d_harmonic_spmv_h", "ec3d_harmonic_projected_residual", "ec3d_harmonic_null_restarts"]
+           "ec3d_harmonic_spmv_h", "ec3d_harmonic_projected_residual", "ec3d_harmonic_null_restarts",
+           "ec3d_harmonic_batch_setup", "ec3d_harmonic_batch_upload", "ec3d_harmonic_batch_download",
+           "ec3d_harmonic_batch_solve", "ec3d_get_harmonic_batch", "ec3d_harmonic_batch_select",
+           "ec3d_harmonic_batch_device_vector"]
+HARMONIC_MAX_BATCH = 16   # EC3D_HARMONIC_MAX_BATCH of include/ec3d_hip.h
 PROBE_NCOMP = 13     # EC3D_PROBE_NCOMP of include/ec3d_hip.h: a[3], eddy[3], source[3], b[3], u
 PROBE_E_FULL = 24    # EC3D_PROBE_E_FULL: ec3d_probe_record on a full buffer
 U_RHS = {"reference": 0, "all": 1}   # EC3D_U_RHS_* of include/ec3d_hip.h
@@ -268,6 +272,13 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.ec3d_harmonic_spmv_h.argtypes = [hp, C.c_void_p, C.c_void_p, _f64, _f64]
     L.ec3d_harmonic_projected_residual.argtypes = [hp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.ec3d_harmonic_null_restarts.argtypes = [hp, _i32]
+    L.ec3d_harmonic_batch_setup.argtypes = [hp, C.c_int32, C.c_void_p]
+    L.ec3d_harmonic_batch_upload.argtypes = [hp, C.c_int32, C.c_int, C.c_void_p, C.c_void_p]
+    L.ec3d_harmonic_batch_download.argtypes = [hp, C.c_int32, C.c_int, _f64, _f64]
+    L.ec3d_harmonic_batch_solve.argtypes = [hp, C.c_double, C.c_int32, C.c_void_p]
+    L.ec3d_get_harmonic_batch.argtypes = [hp, C.c_int32, C.POINTER(HarmonicInfo)]
+    L.ec3d_harmonic_batch_select.argtypes = [hp, C.c_int32]
+    L.ec3d_harmonic_batch_device_vector.argtypes = [hp, C.c_int32, C.c_int, C.POINTER(hp), C.POINTER(C.c_int64)]
     L.ec3d_vtk_fields_wait.argtypes = [hp, C.c_int32] + [C.POINTER(C.POINTER(C.c_float))] * 4 + [C.POINTER(C.c_int64)]
     L.ec3d_set_workgroups.argtypes = [hp, C.c_int32]
     L.ec3d_get_matrix_info.argtypes = [hp, C.POINTER(MatrixInfo)]
@@ -885,6 +896,60 @@ class EC3DSolver:
         _chk(self.L, self.L.ec3d_harmonic_projected_residual(self.h, C.byref(rel), C.byref(rem)),
              "ec3d_harmonic_projected_residual")
         return rel.value, rem.value
+
+    # ---- a batch of harmonic systems in lock step (ec3d_harmonic_batch_*) ----
+    def harmonic_batch_setup(self, omegas):
+        """A batch of len(omegas) systems (omega_s, b^_s, x^_s), at most HARMONIC_MAX_BATCH, on this handle's A-V system,
+        with storage of its own (ec3d_harmonic_batch_setup); equal omegas are allowed; an empty list frees the batch.
+        EC3DError with .status 3 / 5 / NULL_E_MATRIX as harmonic_setup, 2 for too many systems or a negative or
+        non-finite omega; the batch is then as it was."""
+        w = np.ascontiguousarray(omegas, np.float64).reshape(-1)
+        _chk(self.L, self.L.ec3d_harmonic_batch_setup(self.h, len(w), w.ctypes.data if len(w) else None),
+             "ec3d_harmonic_batch_setup")
+
+    def harmonic_batch_upload(self, sys: int, which: str, z):
+        """X^ or B^ of system ``sys`` from a complex (or real) vector in the reference numbering."""
+        re, im = self._parts(z, self.n)
+        _chk(self.L, self.L.ec3d_harmonic_batch_upload(self.h, int(sys), VEC[which], re.ctypes.data, im.ctypes.data),
+             "ec3d_harmonic_batch_upload")
+
+    def harmonic_batch_download(self, sys: int, which: str):
+        re, im = np.empty(self.n), np.empty(self.n)
+        _chk(self.L, self.L.ec3d_harmonic_batch_download(self.h, int(sys), VEC[which], re, im), "ec3d_harmonic_batch_download")
+        return self._complex(re, im)
+
+    def harmonic_batch_solve(self, tolerance: float, itmax: int):
+        """Every system of the batch from its resident X^, in lock step: each gets the bits of its own harmonic_solve.
+        Returns [(iter, relres), ...], one per system.  EC3DError with .status 2 while harmonic_set_null_projection
+        is on."""
+        it = np.zeros(HARMONIC_MAX_BATCH, np.int32)
+        _chk(self.L, self.L.ec3d_harmonic_batch_solve(self.h, float(tolerance), int(itmax), it.ctypes.data),
+             "ec3d_harmonic_batch_solve")
+        out, r = [], HarmonicInfo()
+        while len(out) < HARMONIC_MAX_BATCH and self.L.ec3d_get_harmonic_batch(self.h, len(out), C.byref(r)) == 0:
+            out.append((int(it[len(out)]), float(r.relres)))     # (the first system outside the batch ends the list)
+        return out
+
+    def harmonic_batch_info(self, sys: int):
+        """The dict of harmonic_info() for system ``sys``; ms and device_bytes are the whole batch's
+        (ec3d_get_harmonic_batch)."""
+        r = HarmonicInfo()
+        _chk(self.L, self.L.ec3d_get_harmonic_batch(self.h, int(sys), C.byref(r)), "ec3d_get_harmonic_batch")
+        return dict(ready=bool(r.ready), omega=float(r.omega), iter=int(r.iter), restarts=int(r.restarts),
+                    stop_kind=int(r.stop_kind), relres=float(r.relres), ms=float(r.ms), device_bytes=int(r.device_bytes))
+
+    def harmonic_batch_select(self, sys: int):
+        """harmonic_setup(omega_sys) and device copies of system ``sys``'s x^ and b^ into the resident single X^ and B^:
+        harmonic_true_residual, harmonic_load and every observable behind it, and a further harmonic_solve then work on
+        that system.  The batch keeps its vectors."""
+        _chk(self.L, self.L.ec3d_harmonic_batch_select(self.h, int(sys)), "ec3d_harmonic_batch_select")
+
+    def harmonic_batch_device_vector(self, sys: int, which: str):
+        """(device address, n_pad) of a complex work vector of system ``sys``."""
+        p, n = C.c_void_p(), C.c_int64(0)
+        _chk(self.L, self.L.ec3d_harmonic_batch_device_vector(self.h, int(sys), VEC[which], C.byref(p), C.byref(n)),
+             "ec3d_harmonic_batch_device_vector")
+        return p.value, n.value
 
     def set_u_rhs(self, rule: str = "reference"):
         """Which U rows rhs_step gives their right-hand side with several conducting domains: "reference" (default)

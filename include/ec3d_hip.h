@@ -941,6 +941,38 @@ int ec3d_harmonic_left_null_vector(ec3d_handle h, int32_t index, double *re, dou
 int ec3d_harmonic_spmv_h(ec3d_handle h, const double *xre, const double *xim, double *yre, double *yim);
 int ec3d_harmonic_projected_residual(ec3d_handle h, double *rel, double *removed);
 int ec3d_harmonic_null_restarts(ec3d_handle h, int32_t *restarts);
+/* A batch of harmonic systems solved in lock step (opt-in): nsys systems (omega_s, b^_s, x^_s),
+ * 1 <= nsys <= EC3D_HARMONIC_MAX_BATCH, on the handle's one matrix -- a frequency sweep, one frequency with several
+ * right-hand sides (equal omega in several systems is allowed), or any mixture.  The systems ride in the launches of
+ * ONE iteration, on a grid of (workgroups, nsys): a workgroup takes its system's state, partial sums, table and vectors
+ * and runs the body of the single solve's kernel, so every system gets the bits of its own ec3d_harmonic_solve -- x^,
+ * iter, restarts, stop_kind, relres -- whatever the others do.  A system that has taken an exit launches workgroups that
+ * return at their first load; the batch ends when every system has stopped or itmax + 1 iterations are launched; the
+ * host copies all the states back once per 16 iterations.  One tol and one itmax serve the batch.
+ * Storage of its own, made by ec3d_harmonic_batch_setup only and freed by nsys = 0, a new matrix or ec3d_destroy: per
+ * system the eight complex vectors (zeroed), the (re, omega_s m) table -- built as ec3d_harmonic_setup builds its one --,
+ * the partial sums and the state; plus one staging vector.  ec3d_harmonic_setup is not needed and leaves the batch
+ * alone; the batch touches nothing of the single solve.
+ * ec3d_harmonic_batch_upload / _download: which = EC3D_VEC_X or EC3D_VEC_B of system sys, as ec3d_harmonic_upload.
+ * ec3d_harmonic_batch_solve: from the resident x^_s; iter: nsys entries or NULL.  ec3d_get_harmonic_batch: the info of
+ * system sys as ec3d_get_harmonic fills it for a single solve; ms and device_bytes are the whole batch's.
+ * ec3d_harmonic_batch_select: ec3d_harmonic_setup(h, omega_s), then device copies of x^_s and b^_s into the resident
+ * single X^ and B^: every observable of the single solve (ec3d_harmonic_true_residual, ec3d_harmonic_load and what
+ * follows it, a further ec3d_harmonic_solve, with the null projection if wanted) then works on system sys.  The batch
+ * keeps its vectors.  ec3d_harmonic_batch_device_vector: vector `which` (EC3D_VEC_X ... EC3D_VEC_AS) of system sys, as
+ * ec3d_harmonic_device_vector.
+ * Refusals: 3, 5 and EC3D_NULL_E_MATRIX as ec3d_harmonic_setup; 2 for nsys outside [0, EC3D_HARMONIC_MAX_BATCH], a NULL,
+ * negative or non-finite omega, a sys outside the batch, any call before a batch set-up, and ec3d_harmonic_batch_solve
+ * while ec3d_harmonic_set_null_projection is on (Q belongs to ONE omega: the setting is refused, never ignored).  A
+ * refusal leaves the batch as it was; a failed allocation frees the whole batch and returns the HIP status. */
+#define EC3D_HARMONIC_MAX_BATCH 16
+int ec3d_harmonic_batch_setup(ec3d_handle h, int32_t nsys, const double *omega);
+int ec3d_harmonic_batch_upload(ec3d_handle h, int32_t sys, int which, const double *re, const double *im);
+int ec3d_harmonic_batch_download(ec3d_handle h, int32_t sys, int which, double *re, double *im);
+int ec3d_harmonic_batch_solve(ec3d_handle h, double tol, int32_t itmax, int32_t *iter);
+int ec3d_get_harmonic_batch(ec3d_handle h, int32_t sys, ec3d_harmonic_info *out);
+int ec3d_harmonic_batch_select(ec3d_handle h, int32_t sys);
+int ec3d_harmonic_batch_device_vector(ec3d_handle h, int32_t sys, int which, double **device_ptr, int64_t *pairs);
 
 #ifdef __cplusplus
 }
