@@ -43,10 +43,18 @@
 // on the one matrix ride in the five launches of an iteration on a grid of (G, S): the bodies of k_h_s, k_h_xr, k_h_p
 // and k_h_setup are __device__ functions, as h_spmv_modes is, and k_hb_* run them on the system blockIdx.y names.  Every
 // system keeps the bits of its own single solve; the host copies the S states back once per 16 lock-step iterations.
+//
+// Left null vectors inside a batch (opt-in, ec3d_harmonic_batch_set_null_projection).  One set of
+// vectors per distinct omega of the batch: batch_null_build runs the adjoint solves of all the sets in lock step --
+// k_hb_spmv_h and k_hb_xr_at around the batch's own k_hb_s, k_hb_p, k_hb_setup, in the work vectors of the first systems,
+// the unknown in a staging vector per set -- and null_build's every step per set; k_hbn_* are k_hn_* with the system as
+// one more grid dimension, and batch_launch_project takes every system's own vectors out of its R between k_hb_spmv<3>
+// and k_hb_setup.  Every system keeps the bits of its own single projected solve.
 #include "ec3d_stream.hpp"
 
 #include <chrono>
 #include <cmath>
+#include <cstring>
 
 enum { HP_BB = 0, HP_RR, HP_RR0R, HP_RR0I, HP_D1R, HP_D1I, HP_SS, HP_D2R, HP_D2I, HP_D3, HP_NSLOT };
 
@@ -565,6 +573,137 @@ __global__ __launch_bounds__(EC3D_THREADS) void k_hn_div(cplx *__restrict__ v, d
 // Re v[row] = Re v[row] + a (e_m and -e_m)
 __global__ void k_hn_add_re(cplx *v, int64_t row, double a) { v[row].x = v[row].x + a; }
 
+// ---- left null vectors inside a batch ----------------------------------------------------------
+// The adjoint solves of the batch's distinct omegas in lock step: `sys` below is a SET of vectors (one per distinct
+// omega), which borrows the work vectors, the partials and the state of system `sys` of the batch.
+// k_h_spmv_h<MODE> on set blockIdx.y: A.table is set 0's table; st, part, o, y, r0, p are system 0's, `vstride` pairs
+// apart; x stands `xstride` pairs apart -- the unknown of the adjoint solves has a vector of its own per set (MODE 3,
+// and MODE 0 on w), the work vectors have the batch's stride.  __restrict__ arguments of system 0 plus strides, as
+// k_hb_spmv has them.
+template <int MODE>
+__global__ __launch_bounds__(EC3D_THREADS) void k_hb_spmv_h(HSav A, const HarmonicState *st, const cplx *__restrict__ x,
+                                                           const cplx *__restrict__ o, cplx *__restrict__ y,
+                                                           cplx *__restrict__ r0, cplx *__restrict__ p, int64_t nchunk,
+                                                           double *__restrict__ part, int64_t vstride, int64_t xstride)
+{
+    extern __shared__ cplx tbl[];
+    __shared__ double lds[12];
+    const int64_t sys = blockIdx.y, v = sys * vstride;
+    h_spmv_modes<MODE, true>(A, A.table + sys * A.ncls * 16, st + sys, x + sys * xstride,
+                             MODE == 1 || MODE == 3 ? o + v : nullptr, y + v, MODE == 3 ? r0 + v : nullptr,
+                             MODE == 3 ? p + v : nullptr, nchunk, part + sys * HP_NSLOT * gridDim.x, tbl, lds);
+}
+
+// k_hb_xr with the unknown at x + blockIdx.y * xstride in place of the system's HV_X
+__global__ __launch_bounds__(EC3D_THREADS) void k_hb_xr_at(HBatch B, int it, cplx *__restrict__ x, int64_t xstride, int64_t n,
+                                                          int64_t nchunk)
+{
+    __shared__ double lds[16];
+    h_xr_body(B.state + blockIdx.y, it, hb_vec(B, HV_P), hb_vec(B, HV_S), hb_vec(B, HV_AS), hb_vec(B, HV_R0),
+              x + (int64_t)blockIdx.y * xstride, hb_vec(B, HV_R), n, nchunk, hb_part(B), lds);
+}
+
+// The streaming kernels above with the system as one more grid dimension.  System s projects with the vectors of set
+// set[s], of which kept[s] exist; a workgroup of a vector past kept[s] returns before it reads or writes anything.
+struct HNSys {
+    int32_t set[EC3D_HARMONIC_MAX_BATCH], kept[EC3D_HARMONIC_MAX_BATCH];
+};
+struct HNDiv {
+    double d[EC3D_HARMONIC_MAX_BATCH]; // 0: the system is skipped
+};
+
+// k_hn_dots on system blockIdx.z: Q_i = qbase + set[s] * qset + i * qstride, v = vbase + s * vstride, the partials at
+// part + s * pstride.  h_leave indexes with gridDim.x and blockIdx.x only: the sums are k_hn_dots' own
+__global__ __launch_bounds__(EC3D_THREADS) void k_hbn_dots(HNSys M, const cplx *__restrict__ qbase, int64_t qset, int64_t qstride,
+                                                          const cplx *__restrict__ vbase, int64_t vstride, int64_t n,
+                                                          int64_t nchunk, double *__restrict__ part, int64_t pstride)
+{
+    __shared__ double lds[8];
+    const int s = blockIdx.z;
+    if ((int)blockIdx.y >= M.kept[s]) return;
+    const cplx *q = qbase + (int64_t)M.set[s] * qset + (int64_t)blockIdx.y * qstride;
+    const cplx *v = vbase + (int64_t)s * vstride;
+    double acc[2] = {0.0, 0.0};
+    for (int64_t ch = blockIdx.x; ch < nchunk; ch += gridDim.x)
+        for (int half = 0; half < 2; ++half) {
+            const int64_t i = h_row(ch, half);
+            if (i >= n) continue;
+            const cplx d = cdot(q[i], v[i]);
+            acc[0] = acc[0] + d.x;
+            acc[1] = acc[1] + d.y;
+        }
+    h_leave<2>(acc, part + (int64_t)s * pstride, 2 * (int)blockIdx.y, lds);
+}
+
+// k_hn_collapse on system blockIdx.y: coef[s * cstride + i]
+__global__ __launch_bounds__(EC3D_THREADS) void k_hbn_collapse(HNSys M, const double *__restrict__ part, int64_t pstride, int count,
+                                                              cplx *__restrict__ coef, int64_t cstride)
+{
+    __shared__ double lds[8];
+    const int s = blockIdx.y;
+    if ((int)blockIdx.x >= M.kept[s]) return;
+    double v[2];
+    stream_strided_sum<2>(v, part + (int64_t)s * pstride + (int64_t)2 * blockIdx.x * count, count, count);
+    stream_block_sum<2>(v, lds);
+    if (threadIdx.x == 0) coef[(int64_t)s * cstride + blockIdx.x] = cplx{v[0], v[1]};
+}
+
+// k_hn_sub on system blockIdx.y with its own kept[s] vectors; r0, p, rr (or null) are system 0's, vstride pairs and
+// rrstride doubles apart.  A system that kept nothing is left as it is, partials included
+__global__ __launch_bounds__(EC3D_THREADS) void k_hbn_sub(HNSys M, const cplx *__restrict__ qbase, int64_t qset, int64_t qstride,
+                                                         const cplx *__restrict__ coef, int64_t cstride, cplx *__restrict__ vbase,
+                                                         cplx *__restrict__ r0base, cplx *__restrict__ pbase, int64_t vstride,
+                                                         int64_t n, int64_t nchunk, double *__restrict__ rrbase, int64_t rrstride)
+{
+    __shared__ double lds[4];
+    const int s = blockIdx.y, k = M.kept[s];
+    if (k == 0) return;
+    const cplx *q = qbase + (int64_t)M.set[s] * qset;
+    const cplx *c = coef + (int64_t)s * cstride;
+    cplx *v = vbase + (int64_t)s * vstride;
+    cplx *r0 = r0base ? r0base + (int64_t)s * vstride : nullptr, *p = pbase ? pbase + (int64_t)s * vstride : nullptr;
+    double acc[1] = {0.0};
+    for (int64_t ch = blockIdx.x; ch < nchunk; ch += gridDim.x)
+        for (int half = 0; half < 2; ++half) {
+            const int64_t i = h_row(ch, half);
+            if (i >= n) continue;
+            cplx x = v[i];
+            for (int m = 0; m < k; ++m) {
+                const cplx t = cmul(c[m], q[(int64_t)m * qstride + i]);
+                x = cplx{x.x - t.x, x.y - t.y};
+            }
+            v[i] = x;
+            if (r0) r0[i] = x;
+            if (p) p[i] = x;
+            acc[0] = acc[0] + cabs2(x);
+        }
+    if (!rrbase) return;
+    stream_block_sum<1>(acc, lds);
+    if (threadIdx.x == 0) rrbase[(int64_t)s * rrstride + blockIdx.x] = acc[0];
+}
+
+// k_hn_div on system blockIdx.y by D.d[s]
+__global__ __launch_bounds__(EC3D_THREADS) void k_hbn_div(HNDiv D, cplx *__restrict__ vbase, int64_t vstride, int64_t n, int64_t nchunk)
+{
+    const double d = D.d[blockIdx.y];
+    if (d == 0.0) return;
+    cplx *v = vbase + (int64_t)blockIdx.y * vstride;
+    for (int64_t ch = blockIdx.x; ch < nchunk; ch += gridDim.x)
+        for (int half = 0; half < 2; ++half) {
+            const int64_t i = h_row(ch, half);
+            if (i >= n) continue;
+            const cplx a = v[i];
+            v[i] = cplx{a.x / d, a.y / d};
+        }
+}
+
+// k_hn_add_re on system blockIdx.x
+__global__ void k_hbn_add_re(cplx *vbase, int64_t vstride, int64_t row, double a)
+{
+    cplx *v = vbase + (int64_t)blockIdx.x * vstride;
+    v[row].x = v[row].x + a;
+}
+
 // host copies: (re plane, im plane) in device numbering <-> interleaved pairs; rows >= n of an uploaded vector are zero
 __global__ void k_h_pack(const double *__restrict__ re, const double *__restrict__ im, cplx *__restrict__ v, int64_t n, int64_t n_pad)
 {
@@ -938,9 +1077,32 @@ cplx *hbv(const ec3d_ctx *c, int sys, int w)
     return reinterpret_cast<cplx *>(c->harm.bvec.get()) + ((size_t)sys * HV_N + (size_t)w) * (size_t)c->A.n_pad;
 }
 
+// the vectors of ec3d_harmonic_batch_set_null_projection and what was reported of them; the setting stays
+void batch_null_free(ec3d_ctx *c)
+{
+    Harmonic &H = c->harm;
+    H.bnq.reset();
+    H.bny.reset();
+    H.bntab.reset();
+    H.bnpart.reset();
+    H.bncoef.reset();
+    H.bnull_built = false;
+    H.bnsets = 0;
+    H.bncomp = 0;
+    H.bnull_bytes = 0;
+    H.bnull_setup_ms = 0.0;
+    for (int s = 0; s < EC3D_HARMONIC_MAX_BATCH; ++s) {
+        H.bnset_of[s] = H.bnfirst[s] = H.bnkept[s] = 0;
+        H.bnremoved[s] = 0.0;
+        H.bnull_last[s] = ec3d_null_info{};
+        for (auto &r : H.bnull_restarts[s]) r = 0;
+    }
+}
+
 void batch_free(ec3d_ctx *c)
 {
     Harmonic &H = c->harm;
+    batch_null_free(c);
     H.bvec.reset();
     H.btab.reset();
     H.bpart.reset();
@@ -993,7 +1155,34 @@ int hb_need(ec3d_ctx *c, const char *who, int32_t sys, bool any_sys)
     return 0;
 }
 
-void batch_launch_begin(ec3d_ctx *c, double tol)
+// launch_project for every system of the batch: c_{s,i} = <Q_{s,i}, R_s>; R_s = R_s - sum_i c_{s,i} Q_{s,i}, R0 = P = R; the
+// partials of ||R_s||^2 in system s's HP_RR slots, where k_hb_spmv<3> left them and k_hb_setup reads them
+void batch_launch_project(ec3d_ctx *c)
+{
+    const Harmonic &H = c->harm;
+    HNSys M{};
+    int kmax = 0;
+    for (int s = 0; s < H.bn; ++s) {
+        M.set[s] = H.bnset_of[s];
+        M.kept[s] = H.bnkept[H.bnset_of[s]];
+        kmax = std::max(kmax, M.kept[s]);
+    }
+    if (kmax == 0) return;
+    const int64_t n = c->A.n, len = c->A.n_pad, nc = len / EC3D_TILE, vs = (int64_t)HV_N * len;
+    const unsigned G = (unsigned)H.bwgs, S = (unsigned)H.bn;
+    const int64_t pstride = (int64_t)2 * H.bncomp * H.bwgs, cstride = H.bncomp;
+    const cplx *q = reinterpret_cast<const cplx *>(H.bnq.get());
+    cplx *coef = reinterpret_cast<cplx *>(H.bncoef.get());
+    k_hbn_dots<<<dim3(G, (unsigned)kmax, S), EC3D_THREADS, 0, c->stream>>>(M, q, (int64_t)H.bncomp * len, len, hbv(c, 0, HV_R), vs, n,
+                                                                          nc, H.bnpart, pstride);
+    k_hbn_collapse<<<dim3((unsigned)kmax, S), EC3D_THREADS, 0, c->stream>>>(M, H.bnpart, pstride, H.bwgs, coef, cstride);
+    k_hbn_sub<<<dim3(G, S), EC3D_THREADS, 0, c->stream>>>(M, q, (int64_t)H.bncomp * len, len, coef, cstride, hbv(c, 0, HV_R),
+                                                         hbv(c, 0, HV_R0), hbv(c, 0, HV_P), vs, n, nc,
+                                                         H.bpart.get() + (int64_t)HP_RR * H.bwgs, (int64_t)HP_NSLOT * H.bwgs);
+}
+
+// project: every system's left null vectors leave its R first
+void batch_launch_begin(ec3d_ctx *c, double tol, bool project)
 {
     const Harmonic &H = c->harm;
     const dim3 grid((unsigned)H.bwgs, (unsigned)H.bn);
@@ -1002,6 +1191,7 @@ void batch_launch_begin(ec3d_ctx *c, double tol)
     k_hb_spmv<3><<<grid, EC3D_THREADS, lds, c->stream>>>(batch_view_of(c), B.state, hbv(c, 0, HV_X), hbv(c, 0, HV_B), hbv(c, 0, HV_R),
                                                          hbv(c, 0, HV_R0), hbv(c, 0, HV_P), c->A.n_pad / EC3D_TILE, B.part,
                                                          (int64_t)HV_N * B.len);
+    if (project) batch_launch_project(c);
     k_hb_setup<<<dim3(1, (unsigned)H.bn), EC3D_THREADS, 0, c->stream>>>(B, H.bwgs, tol);
 }
 
@@ -1041,6 +1231,234 @@ int batch_run_iterations(ec3d_ctx *c, int64_t itmax, std::vector<HarmonicState> 
         running = false;
         for (const HarmonicState &q : st) running = running || (q.stop_s == INT_MAX && q.stop_r == INT_MAX);
     } while (launched < total && running);
+    return 0;
+}
+
+// ---- left null vectors inside a batch ----------------------------------------------------------
+// the lowest system whose omega has the bits of system s's
+int batch_shares_with(const Harmonic &H, int s)
+{
+    for (int t = 0; t < s; ++t)
+        if (std::memcmp(&H.bomega[t], &H.bomega[s], sizeof(double)) == 0) return t;
+    return s;
+}
+
+// out[d] = the real part of sum <a_d, v_d> over the rows, d < D: a_d = a + d * astride, v_d = v + d * vstride
+int batch_dots_to_host(ec3d_ctx *c, int D, const cplx *a, int64_t astride, const cplx *v, int64_t vstride, double *out)
+{
+    Harmonic &H = c->harm;
+    HNSys M{};
+    for (int d = 0; d < D; ++d) {
+        M.set[d] = d;
+        M.kept[d] = 1;
+    }
+    const int64_t pstride = (int64_t)2 * H.bncomp * H.bwgs, cstride = H.bncomp;
+    cplx *coef = reinterpret_cast<cplx *>(H.bncoef.get());
+    k_hbn_dots<<<dim3((unsigned)H.bwgs, 1, (unsigned)D), EC3D_THREADS, 0, c->stream>>>(M, a, astride, 0, v, vstride, c->A.n,
+                                                                                     c->A.n_pad / EC3D_TILE, H.bnpart, pstride);
+    k_hbn_collapse<<<dim3(1, (unsigned)D), EC3D_THREADS, 0, c->stream>>>(M, H.bnpart, pstride, H.bwgs, coef, cstride);
+    EC3D_HIP(hipGetLastError());
+    std::vector<double> h((size_t)2 * cstride * D);
+    EC3D_HIP(hipMemcpyAsync(h.data(), coef, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    EC3D_HIP(hipStreamSynchronize(c->stream));
+    for (int d = 0; d < D; ++d) out[d] = h[(size_t)2 * cstride * d];
+    return 0;
+}
+
+// null_build for the batch: per conducting component the adjoint solves of the D distinct omegas in lock step -- set d
+// in the work vectors R, R0, P, AP, S, AS, the partials and the state of system d, its unknown in bny + d * n_pad; X^
+// and B^ of no system are touched -- then every step of null_build per set, the decisions on the host from one copy of
+// D figures.  A kept vector is copied from the staging vector into its slot of Q: a copy keeps the bits.
+int batch_null_build(ec3d_ctx *c)
+{
+    Harmonic &H = c->harm;
+    const auto t_start = std::chrono::steady_clock::now();
+    batch_null_free(c);
+    EC3D_HIP(hipStreamSynchronize(c->stream));
+    const int64_t n = c->A.n, len = c->A.n_pad, nc = len / EC3D_TILE, vs = (int64_t)HV_N * len;
+    int D = 0;
+    for (int s = 0; s < H.bn; ++s) {
+        const int f = batch_shares_with(H, s);
+        if (f == s) {
+            H.bnfirst[D] = s;
+            H.bnset_of[s] = D++;
+        } else {
+            H.bnset_of[s] = H.bnset_of[f];
+        }
+    }
+    H.bnsets = D;
+    std::vector<NullSeed> seeds;
+    int rc = ec3d_null_seeds(c, seeds);
+    if (rc) return rc;
+    const int ncomp = (int)seeds.size();
+    for (int d = 0; d < D; ++d) {
+        H.bnull_last[d].found = ncomp;
+        H.bnull_last[d].reported = std::min(ncomp, EC3D_NULL_MAX_REPORT);
+    }
+    if (ncomp == 0) { // no conductor: the projection is the identity
+        H.bnull_built = true;
+        return 0;
+    }
+    const size_t nt = (size_t)c->A.ncls * 16;
+    const int G = H.bwgs;
+    EC3D_HIP(H.bnq.alloc((size_t)D * ncomp * 2 * len));
+    EC3D_HIP(H.bny.alloc((size_t)D * 2 * len));
+    EC3D_HIP(H.bntab.alloc((size_t)D * 2 * nt));
+    EC3D_HIP(H.bnpart.alloc((size_t)H.bn * 2 * ncomp * G));
+    EC3D_HIP(H.bncoef.alloc((size_t)H.bn * 2 * ncomp));
+    EC3D_HIP(hipMemsetAsync(H.bnq, 0, (size_t)D * ncomp * 2 * len * sizeof(double), c->stream));
+    EC3D_HIP(hipMemsetAsync(H.bnpart, 0, (size_t)H.bn * 2 * ncomp * G * sizeof(double), c->stream));
+    EC3D_HIP(hipMemsetAsync(H.bncoef, 0, (size_t)H.bn * 2 * ncomp * sizeof(double), c->stream));
+    {
+        std::vector<double> re(nt), m(nt), tabs;
+        EC3D_HIP(hipMemcpy(re.data(), H.re, nt * sizeof(double), hipMemcpyDeviceToHost));
+        EC3D_HIP(hipMemcpy(m.data(), H.m, nt * sizeof(double), hipMemcpyDeviceToHost));
+        for (int d = 0; d < D; ++d) {
+            const std::vector<double> t = h_table(re, m, H.bomega[H.bnfirst[d]]);
+            tabs.insert(tabs.end(), t.begin(), t.end());
+        }
+        EC3D_HIP(hipMemcpy(H.bntab, tabs.data(), tabs.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
+    H.bncomp = ncomp;
+    const int64_t nbytes = (int64_t)(((size_t)D * ncomp * 2 * len + (size_t)D * 2 * len + (size_t)D * 2 * nt +
+                                      (size_t)H.bn * 2 * ncomp * G + (size_t)H.bn * 2 * ncomp) * sizeof(double));
+    cplx *Q = reinterpret_cast<cplx *>(H.bnq.get()), *Y = reinterpret_cast<cplx *>(H.bny.get());
+    cplx *coef = reinterpret_cast<cplx *>(H.bncoef.get());
+    const int64_t cap = (int64_t)(20.0 * std::cbrt((double)c->n_ref)) + 2000, total = cap + 1;
+    const int64_t pstride = (int64_t)2 * ncomp * G, cstride = ncomp, qset = (int64_t)ncomp * len;
+    const dim3 grid((unsigned)G, (unsigned)D);
+    const size_t lds = nt * sizeof(cplx);
+    const HBatch B = batch_of(c);
+    HSav A = view_of(c);
+    A.table = reinterpret_cast<const cplx *>(H.bntab.get());
+    hipStream_t s = c->stream;
+    std::vector<HarmonicState> st((size_t)D);
+    std::vector<double> aw2((size_t)D), w2((size_t)D), w2b((size_t)D);
+    for (int ci = 0; ci < ncomp; ++ci) {
+        const int64_t row = seeds[(size_t)ci].row;
+        for (int d = 0; d < D; ++d) EC3D_HIP(hipMemsetAsync(hbv(c, d, HV_S), 0, (size_t)n * sizeof(cplx), s));
+        k_hbn_add_re<<<(unsigned)D, 1, 0, s>>>(hbv(c, 0, HV_S), vs, row, -1.0);
+        k_hb_spmv_h<0><<<grid, EC3D_THREADS, lds, s>>>(A, B.state, hbv(c, 0, HV_S), nullptr, hbv(c, 0, HV_AS), nullptr, nullptr, nc,
+                                                       B.part, vs, vs);
+        EC3D_HIP(hipMemsetAsync(Y, 0, (size_t)D * len * sizeof(cplx), s));
+        k_hb_spmv_h<3><<<grid, EC3D_THREADS, lds, s>>>(A, B.state, Y, hbv(c, 0, HV_AS), hbv(c, 0, HV_R), hbv(c, 0, HV_R0),
+                                                       hbv(c, 0, HV_P), nc, B.part, vs, len);
+        k_hb_setup<<<dim3(1, (unsigned)D), EC3D_THREADS, 0, s>>>(B, G, H.bnull_tol);
+        EC3D_HIP(hipGetLastError());
+        int64_t launched = 0;
+        bool running;
+        do { // run_iterations, D adjoint solves in each launch
+            const int64_t m = std::min<int64_t>(16, total - launched);
+            for (int64_t i = 0; i < m; ++i) {
+                const int it = (int)(++launched);
+                k_hb_spmv_h<1><<<grid, EC3D_THREADS, lds, s>>>(A, B.state, hbv(c, 0, HV_P), hbv(c, 0, HV_R0), hbv(c, 0, HV_AP), nullptr,
+                                                               nullptr, nc, B.part, vs, vs);
+                k_hb_s<<<grid, EC3D_THREADS, 0, s>>>(B, it, n, nc);
+                k_hb_spmv_h<2><<<grid, EC3D_THREADS, lds, s>>>(A, B.state, hbv(c, 0, HV_S), nullptr, hbv(c, 0, HV_AS), nullptr, nullptr,
+                                                               nc, B.part, vs, vs);
+                k_hb_xr_at<<<grid, EC3D_THREADS, 0, s>>>(B, it, Y, len, n, nc);
+                k_hb_p<<<grid, EC3D_THREADS, 0, s>>>(B, it, n, nc);
+            }
+            EC3D_HIP(hipGetLastError());
+            EC3D_HIP(hipMemcpyAsync(st.data(), H.bstate, st.size() * sizeof(HarmonicState), hipMemcpyDeviceToHost, s));
+            EC3D_HIP(hipStreamSynchronize(s));
+            running = false;
+            for (const HarmonicState &q : st) running = running || (q.stop_s == INT_MAX && q.stop_r == INT_MAX);
+        } while (launched < total && running);
+        k_hbn_add_re<<<(unsigned)D, 1, 0, s>>>(Y, len, row, 1.0);
+        // ||A^H w||, the adjoint system's true residual, and ||w||, per set
+        k_hb_spmv_h<0><<<grid, EC3D_THREADS, lds, s>>>(A, B.state, Y, nullptr, hbv(c, 0, HV_AS), nullptr, nullptr, nc, B.part, vs, len);
+        if ((rc = batch_dots_to_host(c, D, hbv(c, 0, HV_AS), vs, hbv(c, 0, HV_AS), vs, aw2.data()))) return rc;
+        if ((rc = batch_dots_to_host(c, D, Y, len, Y, len, w2.data()))) return rc;
+        for (int d = 0; d < D; ++d) { // the rule of null_build, per set
+            const HarmonicState &q = st[(size_t)d];
+            const bool stopped = q.stop_s != INT_MAX || q.stop_r != INT_MAX;
+            const double true_rel = std::sqrt(aw2[(size_t)d]) / q.bnorm;
+            if (stopped && true_rel <= 2.0 * H.bnull_tol) continue;
+            char msg[480];
+            snprintf(msg, sizeof msg, "harmonic batch null projection: the adjoint solve of system %d (omega = %.17g), conducting "
+                     "component %d (seed row %lld) did not reach null_tol = %.3g: %s after %lld iterations (cap %lld), true residual "
+                     "||A^H w|| / ||A^H e_m|| = %.3g; no left null vector of the batch is used", H.bnfirst[d],
+                     H.bomega[H.bnfirst[d]], ci, (long long)seeds[(size_t)ci].seed_ref, H.bnull_tol,
+                     stopped ? "the recurrence took an exit" : "no exit",
+                     (long long)(stopped ? std::min(q.stop_s, q.stop_r) : cap + 1), (long long)cap, true_rel);
+            batch_null_free(c);
+            ec3d_set_error(msg);
+            return EC3D_NULL_E_SETUP;
+        }
+        HNSys K{};
+        int kmax = 0;
+        for (int d = 0; d < D; ++d) {
+            K.set[d] = d;
+            K.kept[d] = H.bnkept[d];
+            kmax = std::max(kmax, K.kept[d]);
+        }
+        w2b = w2;
+        if (kmax > 0) {
+            k_hbn_dots<<<dim3((unsigned)G, (unsigned)kmax, (unsigned)D), EC3D_THREADS, 0, s>>>(K, Q, qset, len, Y, len, n, nc, H.bnpart,
+                                                                                             pstride);
+            k_hbn_collapse<<<dim3((unsigned)kmax, (unsigned)D), EC3D_THREADS, 0, s>>>(K, H.bnpart, pstride, G, coef, cstride);
+            k_hbn_sub<<<grid, EC3D_THREADS, 0, s>>>(K, Q, qset, len, coef, cstride, Y, nullptr, nullptr, len, n, nc, nullptr, 0);
+            std::vector<double> after((size_t)D);
+            if ((rc = batch_dots_to_host(c, D, Y, len, Y, len, after.data()))) return rc;
+            for (int d = 0; d < D; ++d)
+                if (K.kept[d] > 0) w2b[(size_t)d] = after[(size_t)d];
+        }
+        HNDiv dv{};
+        bool keep[EC3D_HARMONIC_MAX_BATCH] = {false};
+        for (int d = 0; d < D; ++d) {
+            const double n0 = std::sqrt(w2[(size_t)d]), n1 = std::sqrt(w2b[(size_t)d]);
+            keep[d] = std::isfinite(n0) && std::isfinite(n1) && n1 > EC3D_NULL_MIN_KEEP * n0;
+            dv.d[d] = keep[d] ? n1 : 0.0;
+        }
+        k_hbn_div<<<grid, EC3D_THREADS, 0, s>>>(dv, Y, len, n, nc);
+        for (int d = 0; d < D; ++d) {
+            if (keep[d]) {
+                EC3D_HIP(hipMemcpyAsync(Q + (size_t)d * qset + (size_t)H.bnkept[d] * len, Y + (size_t)d * len, (size_t)len * sizeof(cplx),
+                                        hipMemcpyDeviceToDevice, s));
+                ++H.bnkept[d];
+            }
+            if (ci < EC3D_NULL_MAX_REPORT) {
+                ec3d_null_info &L = H.bnull_last[d];
+                const HarmonicState &q = st[(size_t)d];
+                L.seed_row[ci] = seeds[(size_t)ci].seed_ref;
+                L.iterations[ci] = std::min(q.stop_s, q.stop_r);
+                L.was_kept[ci] = keep[d] ? 1 : 0;
+                L.residual[ci] = std::sqrt(aw2[(size_t)d]) / std::sqrt(w2[(size_t)d]);
+                H.bnull_restarts[d][ci] = q.restarts;
+            }
+        }
+    }
+    EC3D_HIP(hipGetLastError());
+    EC3D_HIP(hipStreamSynchronize(s));
+    H.bnull_built = true;
+    H.bnull_bytes = nbytes;
+    H.bnull_setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    for (int d = 0; d < D; ++d) {
+        H.bnull_last[d].kept = H.bnkept[d];
+        H.bnull_last[d].dropped = ncomp - H.bnkept[d];
+        H.bnull_last[d].setup_ms = H.bnull_setup_ms;
+    }
+    return 0;
+}
+
+// null_note per system: removed_s = sqrt(sum_i |c_{s,i}|^2) / ||b^_s|| of the projection that has just run
+int batch_null_note(ec3d_ctx *c, const std::vector<HarmonicState> &st)
+{
+    Harmonic &H = c->harm;
+    for (int s = 0; s < H.bn; ++s) H.bnremoved[s] = 0.0;
+    if (H.bncomp == 0) return 0;
+    std::vector<double> h((size_t)H.bn * 2 * H.bncomp);
+    EC3D_HIP(hipMemcpy(h.data(), H.bncoef, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int s = 0; s < H.bn; ++s) {
+        const int kept = H.bnkept[H.bnset_of[s]];
+        const double bnorm = st[(size_t)s].bnorm;
+        if (kept == 0 || bnorm == 0.0) continue;
+        const double *q = h.data() + (size_t)s * 2 * H.bncomp;
+        double sum = 0.0;
+        for (int i = 0; i < 2 * kept; i += 2) sum += q[i] * q[i] + q[i + 1] * q[i + 1];
+        H.bnremoved[s] = std::sqrt(sum) / bnorm;
+    }
     return 0;
 }
 
@@ -1444,8 +1862,9 @@ extern "C" int ec3d_harmonic_batch_solve(ec3d_handle c, double tol, int32_t itma
                        "switch it off, or solve the systems one by one (ec3d_harmonic_batch_select)");
         return 2;
     }
+    if (H.bnull_on && !H.bnull_built && (rc = batch_null_build(c))) return rc;
     const auto t_start = std::chrono::steady_clock::now();
-    batch_launch_begin(c, tol);
+    batch_launch_begin(c, tol, H.bnull_on != 0);
     EC3D_HIP(hipGetLastError());
     std::vector<HarmonicState> st;
     if ((rc = batch_run_iterations(c, itmax, st))) return rc;
@@ -1456,6 +1875,7 @@ extern "C" int ec3d_harmonic_batch_solve(ec3d_handle c, double tol, int32_t itma
         H.blast[s].ms = ms;
         if (iter) iter[s] = H.blast[s].iter;
     }
+    if (H.bnull_on) return batch_null_note(c, st);
     return 0;
 }
 
@@ -1468,6 +1888,7 @@ extern "C" int ec3d_get_harmonic_batch(ec3d_handle c, int32_t sys, ec3d_harmonic
         return 2;
     }
     *out = c->harm.blast[sys];
+    out->device_bytes += c->harm.bnull_bytes; // the left null vectors of the batch, while they exist
     return 0;
 }
 
@@ -1493,5 +1914,111 @@ extern "C" int ec3d_harmonic_batch_device_vector(ec3d_handle c, int32_t sys, int
     }
     *device_ptr = reinterpret_cast<double *>(hbv(c, sys, which));
     *pairs = c->A.n_pad;
+    return 0;
+}
+
+// ---- left null vectors inside a batch ----------------------------------------------------------
+extern "C" int ec3d_harmonic_batch_set_null_projection(ec3d_handle c, int32_t on, double null_tol)
+{
+    if (!c) {
+        ec3d_set_error("ec3d_harmonic_batch_set_null_projection: null handle");
+        return 2;
+    }
+    if (!on) { // the handle is checked as everywhere; only the batch is not asked for.  The vectors stay with the batch
+        const int rc = h_need(c, "ec3d_harmonic_batch_set_null_projection", false);
+        if (rc) return rc;
+        c->harm.bnull_on = 0;
+        return 0;
+    }
+    int rc = hb_need(c, "ec3d_harmonic_batch_set_null_projection", 0, true);
+    if (rc) return rc; // (the setting as it was)
+    Harmonic &H = c->harm;
+    const double tol = null_tol > 0.0 ? null_tol : 1e-10;
+    if (tol != H.bnull_tol && H.bnull_built) {
+        EC3D_HIP(hipStreamSynchronize(c->stream));
+        batch_null_free(c); // another accuracy: the vectors are made again
+    }
+    H.bnull_on = 1;
+    H.bnull_tol = tol;
+    return 0;
+}
+
+extern "C" int ec3d_get_harmonic_batch_null(ec3d_handle c, int32_t sys, ec3d_null_info *info, int32_t *shares_with)
+{
+    int rc = hb_need(c, "ec3d_get_harmonic_batch_null", sys, false);
+    if (rc) return rc;
+    if (!info) {
+        ec3d_set_error("ec3d_get_harmonic_batch_null: info is NULL");
+        return 2;
+    }
+    const Harmonic &H = c->harm;
+    *info = H.bnull_built ? H.bnull_last[H.bnset_of[sys]] : ec3d_null_info{};
+    info->on = H.bnull_on;
+    info->null_tol = H.bnull_tol;
+    info->built = H.bnull_built ? 1 : 0;
+    info->removed = H.bnremoved[sys];
+    if (shares_with) *shares_with = batch_shares_with(H, sys);
+    return 0;
+}
+
+extern "C" int ec3d_harmonic_batch_left_null_vector(ec3d_handle c, int32_t sys, int32_t index, double *re, double *im)
+{
+    int rc = hb_need(c, "ec3d_harmonic_batch_left_null_vector", sys, false);
+    if (rc) return rc;
+    Harmonic &H = c->harm;
+    if (!H.bnull_built) {
+        if (!H.bnull_on) {
+            ec3d_set_error("ec3d_harmonic_batch_left_null_vector: no vectors yet and the projection is off "
+                           "(ec3d_harmonic_batch_set_null_projection)");
+            return 2;
+        }
+        if ((rc = batch_null_build(c))) return rc;
+    }
+    const int d = H.bnset_of[sys], kept = H.bnkept[d];
+    if (index < 0 || index >= kept || !re || !im) {
+        ec3d_set_error("ec3d_harmonic_batch_left_null_vector: index " + std::to_string(index) + " is outside the " +
+                       std::to_string(kept) + " vectors kept for system " + std::to_string(sys) + ", or a NULL argument");
+        return 2;
+    }
+    return h_to_host(c, H.bstage, reinterpret_cast<const cplx *>(H.bnq.get()) + ((size_t)d * H.bncomp + (size_t)index) * c->A.n_pad,
+                     re, im);
+}
+
+extern "C" int ec3d_harmonic_batch_null_restarts(ec3d_handle c, int32_t sys, int32_t *restarts)
+{
+    int rc = hb_need(c, "ec3d_harmonic_batch_null_restarts", sys, false);
+    if (rc) return rc;
+    if (!restarts) {
+        ec3d_set_error("ec3d_harmonic_batch_null_restarts: restarts is NULL");
+        return 2;
+    }
+    const Harmonic &H = c->harm;
+    for (int i = 0; i < EC3D_NULL_MAX_REPORT; ++i) restarts[i] = H.bnull_built ? H.bnull_restarts[H.bnset_of[sys]][i] : 0;
+    return 0;
+}
+
+extern "C" int ec3d_harmonic_batch_projected_residual(ec3d_handle c, double *rel, double *removed)
+{
+    int rc = hb_need(c, "ec3d_harmonic_batch_projected_residual", 0, true);
+    if (rc) return rc;
+    Harmonic &H = c->harm;
+    if (!H.bnull_on || !rel) {
+        ec3d_set_error(!rel ? "ec3d_harmonic_batch_projected_residual: rel is NULL"
+                            : "ec3d_harmonic_batch_projected_residual: the projection is off "
+                              "(ec3d_harmonic_batch_set_null_projection)");
+        return 2;
+    }
+    if (!H.bnull_built && (rc = batch_null_build(c))) return rc;
+    batch_launch_begin(c, 0.0, true);
+    EC3D_HIP(hipGetLastError());
+    std::vector<HarmonicState> st((size_t)H.bn);
+    EC3D_HIP(hipMemcpyAsync(st.data(), H.bstate, st.size() * sizeof(HarmonicState), hipMemcpyDeviceToHost, c->stream));
+    EC3D_HIP(hipStreamSynchronize(c->stream));
+    if ((rc = batch_null_note(c, st))) return rc;
+    for (int s = 0; s < H.bn; ++s) {
+        const HarmonicState &q = st[(size_t)s];
+        rel[s] = q.bnorm > 0.0 ? q.rnorm / q.bnorm : q.rnorm;
+        if (removed) removed[s] = H.bnremoved[s];
+    }
     return 0;
 }

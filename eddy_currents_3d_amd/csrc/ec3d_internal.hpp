@@ -458,6 +458,25 @@ struct Harmonic {
     int bwgs = 0;
     int64_t bbytes = 0;
     ec3d_harmonic_info blast[EC3D_HARMONIC_MAX_BATCH] = {};
+    // ec3d_harmonic_batch_set_null_projection: one set of left null vectors per DISTINCT omega of
+    // the batch, found by adjoint solves that run in lock step in the work vectors, partials and states of the systems
+    // 0 .. bnsets - 1.  Vector i of set d: the n_pad pairs at bnq + (d * bncomp + i) * 2 * n_pad; bny: one staging
+    // vector per set, the unknown of its adjoint solve; bntab: the table of set d's omega; bnpart, bncoef: per SYSTEM
+    // the partials and the coefficients of its projection.  The setting (bnull_on, bnull_tol) belongs to the handle, the
+    // rest to the batch (batch_free).
+    int bnull_on = 0;
+    double bnull_tol = 1e-10;
+    bool bnull_built = false;
+    int bnsets = 0, bncomp = 0;
+    int bnset_of[EC3D_HARMONIC_MAX_BATCH] = {0};   // system -> set
+    int bnfirst[EC3D_HARMONIC_MAX_BATCH] = {0};    // set -> its lowest system
+    int bnkept[EC3D_HARMONIC_MAX_BATCH] = {0};     // per set
+    DevBuf<double> bnq, bny, bntab, bnpart, bncoef;
+    int64_t bnull_bytes = 0;
+    double bnull_setup_ms = 0.0;
+    double bnremoved[EC3D_HARMONIC_MAX_BATCH] = {0.0};  // per system, of its last projection
+    ec3d_null_info bnull_last[EC3D_HARMONIC_MAX_BATCH] = {}; // per set
+    int32_t bnull_restarts[EC3D_HARMONIC_MAX_BATCH][EC3D_NULL_MAX_REPORT] = {{0}};
 };
 
 struct ec3d_ctx {

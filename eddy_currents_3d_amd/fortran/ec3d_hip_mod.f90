@@ -37,7 +37,10 @@ module ec3d_hip
               ec3d_harmonic_spmv_h, ec3d_harmonic_projected_residual, ec3d_harmonic_null_restarts, &
               EC3D_HARMONIC_MAX_BATCH, ec3d_harmonic_batch_setup, ec3d_harmonic_batch_upload, &
               ec3d_harmonic_batch_download, ec3d_harmonic_batch_solve, ec3d_get_harmonic_batch, &
-              ec3d_harmonic_batch_select, ec3d_harmonic_batch_device_vector
+              ec3d_harmonic_batch_select, ec3d_harmonic_batch_device_vector, &
+              ec3d_harmonic_batch_set_null_projection, ec3d_get_harmonic_batch_null, &
+              ec3d_harmonic_batch_left_null_vector, ec3d_harmonic_batch_null_restarts, &
+              ec3d_harmonic_batch_projected_residual
 
     integer(c_int), parameter :: EC3D_VEC_X = 0, EC3D_VEC_B = 1   ! Uaf, Jaf
     integer(c_int), parameter :: EC3D_PRECOND_NONE = 0, EC3D_PRECOND_MG = 1   ! ec3d_set_preconditioner
@@ -545,6 +548,46 @@ module ec3d_hip
             integer(c_int), value :: which
             type(c_ptr), intent(out) :: device_ptr
             integer(c_int64_t), intent(out) :: pairs
+        end function
+        ! The left null vectors inside a batch (include/ec3d_hip.h; opt-in): every system projects with the vectors of
+        ! its own omega; null_tol <= 0: 1e-10
+        integer(c_int) function ec3d_harmonic_batch_set_null_projection(h, on, null_tol) &
+                bind(C, name="ec3d_harmonic_batch_set_null_projection")
+            import :: c_ptr, c_int, c_int32_t, c_double
+            type(c_ptr), value :: h
+            integer(c_int32_t), value :: on
+            real(c_double), value :: null_tol
+        end function
+        ! the report of system sys; shares_with: the lowest system with the same omega (C callers may pass NULL for it,
+        ! a caller of this interface always receives it)
+        integer(c_int) function ec3d_get_harmonic_batch_null(h, sys, info, shares_with) &
+                bind(C, name="ec3d_get_harmonic_batch_null")
+            import :: c_ptr, c_int, c_int32_t, ec3d_null_info
+            type(c_ptr), value :: h
+            integer(c_int32_t), value :: sys
+            type(ec3d_null_info), intent(out) :: info
+            integer(c_int32_t), intent(out) :: shares_with
+        end function
+        integer(c_int) function ec3d_harmonic_batch_left_null_vector(h, sys, index, re, im) &
+                bind(C, name="ec3d_harmonic_batch_left_null_vector")
+            import :: c_ptr, c_int, c_int32_t, c_double
+            type(c_ptr), value :: h
+            integer(c_int32_t), value :: sys, index
+            real(c_double), intent(out) :: re(*), im(*)
+        end function
+        integer(c_int) function ec3d_harmonic_batch_null_restarts(h, sys, restarts) &
+                bind(C, name="ec3d_harmonic_batch_null_restarts")
+            import :: c_ptr, c_int, c_int32_t
+            type(c_ptr), value :: h
+            integer(c_int32_t), value :: sys
+            integer(c_int32_t), intent(out) :: restarts(*)
+        end function
+        ! nsys entries each (C callers may pass NULL for removed; this interface always takes the array)
+        integer(c_int) function ec3d_harmonic_batch_projected_residual(h, rel, removed) &
+                bind(C, name="ec3d_harmonic_batch_projected_residual")
+            import :: c_ptr, c_int, c_double
+            type(c_ptr), value :: h
+            real(c_double), intent(out) :: rel(*), removed(*)
         end function
         ! U rows ec3d_rhs_step gives their right-hand side with several conducting domains (include/ec3d_hip.h)
         integer(c_int) function ec3d_set_u_rhs(h, rule) bind(C, name="ec3d_set_u_rhs")

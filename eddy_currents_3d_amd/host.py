@@ -551,16 +551,19 @@ HARMONIC_MAX_BATCH = 16     # EC3D_HARMONIC_MAX_BATCH of include/ec3d_hip.h
 
 def run_harmonic_sweep(model: vxc.VxcModel, solver, drive_freq: float, freqs, tol: float | None = None,
                        itmax: int | None = None, out_dir: str | None = None, integrals: bool = False, probes=None,
-                       batch: int = HARMONIC_MAX_BATCH):
+                       batch: int = HARMONIC_MAX_BATCH, null_projection: bool = False, null_tol: float | None = None):
     """A constant-current frequency sweep of ``model`` on ``solver`` (an EC3DSolver): b^ is built
     ONCE from the source phasors the model's functions have at ``drive_freq`` (harmonic_rhs) and applied at every
     frequency of ``freqs`` [Hz]; the systems (K + j 2 pi f M) x^ = b^ go through the solver's batch in groups of at most
     ``batch`` (1 .. 16), in lock step and every x^ from 0, at the model's tolerance and iteration limit (or ``tol`` /
     ``itmax``).  Per frequency the system is then selected (harmonic_batch_select) and gets run_harmonic's observables.
     Returns a list, in the order of ``freqs``, of dicts with run_harmonic's keys; ``out_dir`` gets harmonic_<k>_re.vtk and
-    harmonic_<k>_im.vtk, k the position in ``freqs``.  There is no null projection inside a batch.  ValueError, before
-    anything is assembled, on moving sources, an empty list, a frequency that is not above 0 or a ``batch`` outside
-    [1, 16]."""
+    harmonic_<k>_im.vtk, k the position in ``freqs``.  ``null_projection``: every system of a batch projects with the left
+    null vectors of its own frequency (harmonic_batch_set_null_projection; section 18c), found to ``null_tol`` (None:
+    1e-10) by adjoint solves in lock step, so that a ``tol`` below the floor can be reached over the whole sweep; every
+    result then also holds "projected_residual", "removed" and "null" (solver.harmonic_batch_null_projection(s)), as
+    run_harmonic's do, and the handle's setting is left as it was found.  ValueError, before anything is assembled, on
+    moving sources, an empty list, a frequency that is not above 0 or a ``batch`` outside [1, 16]."""
     if not hasattr(solver, "harmonic_batch_setup"):
         raise ValueError("run_harmonic_sweep needs an EC3DSolver: the harmonic solve runs on one undivided handle")
     freqs = [float(f) for f in freqs]
@@ -580,23 +583,43 @@ def run_harmonic_sweep(model: vxc.VxcModel, solver, drive_freq: float, freqs, to
     itmax = int(t["itmax"] if itmax is None else itmax)
     zero = np.zeros(n_ref)
     results = []
-    for k0 in range(0, len(freqs), batch):
-        group = freqs[k0:k0 + batch]
-        omegas = [2.0 * math.pi * f for f in group]
-        solver.harmonic_batch_setup(omegas)
-        for s in range(len(group)):
-            solver.harmonic_batch_upload(s, "B", b)
-            solver.harmonic_batch_upload(s, "X", zero)
-        solved = solver.harmonic_batch_solve(tol, itmax)
-        for s, (f, omega) in enumerate(zip(group, omegas)):
-            it, relres = solved[s]
-            info = solver.harmonic_batch_info(s)
-            solver.harmonic_batch_select(s)
-            true_res, bnorm = solver.harmonic_true_residual()
-            out = dict(freq=f, omega=omega, iter=it, relres=relres, true_residual=true_res, bnorm=bnorm,
-                       x=solver.harmonic_download("X"), b=b, parts=[{}, {}], info=info)
-            _harmonic_observables(model, solver, t, out, out_dir, integrals, probes, f"harmonic_{k0 + s}")
-            results.append(out)
+    was = None                                       # the batch's null-projection setting as it was found
+    try:
+        for k0 in range(0, len(freqs), batch):
+            group = freqs[k0:k0 + batch]
+            omegas = [2.0 * math.pi * f for f in group]
+            solver.harmonic_batch_setup(omegas)
+            if null_projection:                      # (the setting can be read and set while a batch exists)
+                if was is None:
+                    was = solver.harmonic_batch_null_projection(0)
+                solver.harmonic_batch_set_null_projection(True, 1e-10 if null_tol is None else float(null_tol))
+            for s in range(len(group)):
+                solver.harmonic_batch_upload(s, "B", b)
+                solver.harmonic_batch_upload(s, "X", zero)
+            solved = solver.harmonic_batch_solve(tol, itmax)
+            projected = solver.harmonic_batch_projected_residual() if null_projection else None
+            for s, (f, omega) in enumerate(zip(group, omegas)):
+                it, relres = solved[s]
+                info = solver.harmonic_batch_info(s)
+                extra = {}
+                if null_projection:
+                    extra = dict(projected_residual=projected[s][0], removed=projected[s][1],
+                                 null=solver.harmonic_batch_null_projection(s))
+                solver.harmonic_batch_select(s)
+                true_res, bnorm = solver.harmonic_true_residual()
+                out = dict(freq=f, omega=omega, iter=it, relres=relres, true_residual=true_res, bnorm=bnorm,
+                           x=solver.harmonic_download("X"), b=b, parts=[{}, {}], info=info, **extra)
+                _harmonic_observables(model, solver, t, out, out_dir, integrals, probes, f"harmonic_{k0 + s}")
+                results.append(out)
+    except BaseException:
+        if was is not None:                          # put back what can be put back; the error above is the one to report
+            try:
+                solver.harmonic_batch_set_null_projection(was["on"], was["null_tol"])
+            except Exception:
+                pass
+        raise
+    if was is not None:
+        solver.harmonic_batch_set_null_projection(was["on"], was["null_tol"])
     solver.harmonic_batch_setup([])                  # the batch's memory goes; the last system stays selected
     return results
 

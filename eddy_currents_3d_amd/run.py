@@ -8,6 +8,7 @@
                                                  [--null-projection [--null-tol Y]]
     python -m eddy_currents_3d_amd.run model.vxc --harmonic F0 --sweep F1,F2,... [--sweep-batch N] [--out DIR]
                                                  [--integrals FILE] [--tol X]
+                                                 [--sweep-null-projection [--sweep-null-tol Y]]
     python -m torch.distributed.run --nproc-per-node G -m eddy_currents_3d_amd.run model.vxc ...   (G GPUs)
 
 Reads the file (eddy_currents_3d_amd/vxc.py), assembles the A-V system on the device, and runs the
@@ -31,7 +32,10 @@ report line gains the projected residual and the adjoint solves' iterations, and
 the source phasors are read at F0 and the same b^ is solved at every frequency of the list, up to ``--sweep-batch N``
 (default and most: 16) of them in lock step in the launches of one iteration; ``harmonic_<k>_re.vtk`` and
 ``harmonic_<k>_im.vtk``, k the position in the list, go to ``--out``, ``--integrals FILE`` gets one line per frequency and
-domain, and there is one report line per frequency; ``--null-projection`` is refused.
+domain, and there is one report line per frequency; ``--null-projection`` is refused.  ``--sweep-null-projection``: every
+frequency of a batch projects with the left null vectors of its own operator, found by adjoint
+solves in lock step to ``--sweep-null-tol Y`` (default 1e-10), so that ``--tol X`` can go below the floor over the whole
+sweep; the report lines gain the projected residual and the adjoint solves' iterations.
 """
 from __future__ import annotations
 
@@ -118,17 +122,27 @@ def build_parser():
                          "frequency to --out, one line per frequency and domain to --integrals")
     ap.add_argument("--sweep-batch", type=int, default=16, metavar="N", choices=range(1, 17),
                     help="systems of --sweep solved in one batch (1 .. 16, default 16)")
+    ap.add_argument("--sweep-null-projection", action="store_true",
+                    help="with --sweep: take the left null vectors of every frequency's own operator out of its initial "
+                         "residual, so that --tol can go below the floor at every frequency")
+    ap.add_argument("--sweep-null-tol", type=float, default=None, metavar="Y",
+                    help="accuracy the adjoint solves of --sweep-null-projection are run to (default 1e-10)")
     return ap
 
 
 def check_sweep_options(ap, a):
     """The refusals of --sweep that need no model; returns the frequencies (None without --sweep)."""
+    if a.sweep_null_tol is not None and not a.sweep_null_projection:
+        ap.error("--sweep-null-tol needs --sweep-null-projection")
     if a.sweep is None:
+        if a.sweep_null_projection:
+            ap.error("--sweep-null-projection needs --sweep F1,F2,...")
         return None
     if a.harmonic is None:
         ap.error("--sweep needs --harmonic F0, the frequency at which the sources' phasors are read")
     if a.null_projection:
-        ap.error("--sweep does not go with --null-projection: the left null vectors belong to one frequency")
+        ap.error("--sweep does not go with --null-projection: the left null vectors belong to one frequency "
+                 "(--sweep-null-projection gives every frequency of the sweep its own)")
     try:
         freqs = [float(w) for w in a.sweep.split(",") if w.strip()]
     except ValueError:
@@ -155,7 +169,9 @@ def run_sweep_cli(ap, a, model, t, out_dir, freqs):
     with EC3DSolver(device=a.device) as s:
         try:
             rs = host.run_harmonic_sweep(model, s, a.harmonic, freqs, tol=a.tol, out_dir=out_dir,
-                                         integrals=bool(a.integrals), batch=a.sweep_batch)
+                                         integrals=bool(a.integrals), batch=a.sweep_batch,
+                                         **(dict(null_projection=True, null_tol=a.sweep_null_tol)
+                                            if a.sweep_null_projection else {}))
         except ValueError as e:
             ap.error(str(e))
     if a.integrals:
@@ -164,8 +180,10 @@ def run_sweep_cli(ap, a, model, t, out_dir, freqs):
             for r in rs:
                 _write_harmonic_integrals(f, r["freq"], r["integrals"])
     for k, r in enumerate(rs):
+        null = (f"projected residual={r['projected_residual']:.3e} adjoint iterations="
+                f"{'+'.join(str(q['iterations']) for q in r['null']['components'])} " if a.sweep_null_projection else "")
         print(f"harmonic sweep {k} at {r['freq']:g} Hz (phasors of {a.harmonic:g} Hz): iter={r['iter']} "
-              f"relres={r['relres']:.3e} true residual={r['true_residual']:.3e} restarts={r['info']['restarts']} "
+              f"relres={r['relres']:.3e} true residual={r['true_residual']:.3e} restarts={r['info']['restarts']} {null}"
               f"({r['info']['ms']:.1f} ms in its batch's solve)"
               + (f"  -> {out_dir}/harmonic_{k}_re.vtk, harmonic_{k}_im.vtk" if out_dir else ""), flush=True)
     print(f"{len(rs)} frequencies in {time.perf_counter() - t0:.2f} s wall", flush=True)

@@ -127,7 +127,10 @@ EXPORTS = ["sprsbcgstabwr_", "ec3d_invalidate", "ec3d_create", "ec3d_destroy", "
            "ec3d_harmonic_spmv_h", "ec3d_harmonic_projected_residual", "ec3d_harmonic_null_restarts",
            "ec3d_harmonic_batch_setup", "ec3d_harmonic_batch_upload", "ec3d_harmonic_batch_download",
            "ec3d_harmonic_batch_solve", "ec3d_get_harmonic_batch", "ec3d_harmonic_batch_select",
-           "ec3d_harmonic_batch_device_vector"]
+           "ec3d_harmonic_batch_device_vector",
+           "ec3d_harmonic_batch_set_null_projection", "ec3d_get_harmonic_batch_null",
+           "ec3d_harmonic_batch_left_null_vector", "ec3d_harmonic_batch_null_restarts",
+           "ec3d_harmonic_batch_projected_residual"]
 HARMONIC_MAX_BATCH = 16   # EC3D_HARMONIC_MAX_BATCH of include/ec3d_hip.h
 PROBE_NCOMP = 13     # EC3D_PROBE_NCOMP of include/ec3d_hip.h: a[3], eddy[3], source[3], b[3], u
 PROBE_E_FULL = 24    # EC3D_PROBE_E_FULL: ec3d_probe_record on a full buffer
@@ -279,6 +282,11 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.ec3d_get_harmonic_batch.argtypes = [hp, C.c_int32, C.POINTER(HarmonicInfo)]
     L.ec3d_harmonic_batch_select.argtypes = [hp, C.c_int32]
     L.ec3d_harmonic_batch_device_vector.argtypes = [hp, C.c_int32, C.c_int, C.POINTER(hp), C.POINTER(C.c_int64)]
+    L.ec3d_harmonic_batch_set_null_projection.argtypes = [hp, C.c_int32, C.c_double]
+    L.ec3d_get_harmonic_batch_null.argtypes = [hp, C.c_int32, C.POINTER(NullInfo), C.POINTER(C.c_int32)]
+    L.ec3d_harmonic_batch_left_null_vector.argtypes = [hp, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    L.ec3d_harmonic_batch_null_restarts.argtypes = [hp, C.c_int32, C.c_void_p]
+    L.ec3d_harmonic_batch_projected_residual.argtypes = [hp, C.c_void_p, C.c_void_p]
     L.ec3d_vtk_fields_wait.argtypes = [hp, C.c_int32] + [C.POINTER(C.POINTER(C.c_float))] * 4 + [C.POINTER(C.c_int64)]
     L.ec3d_set_workgroups.argtypes = [hp, C.c_int32]
     L.ec3d_get_matrix_info.argtypes = [hp, C.POINTER(MatrixInfo)]
@@ -906,6 +914,7 @@ class EC3DSolver:
         w = np.ascontiguousarray(omegas, np.float64).reshape(-1)
         _chk(self.L, self.L.ec3d_harmonic_batch_setup(self.h, len(w), w.ctypes.data if len(w) else None),
              "ec3d_harmonic_batch_setup")
+        self._harmonic_batch_nsys = len(w)
 
     def harmonic_batch_upload(self, sys: int, which: str, z):
         """X^ or B^ of system ``sys`` from a complex (or real) vector in the reference numbering."""
@@ -950,6 +959,45 @@ class EC3DSolver:
         _chk(self.L, self.L.ec3d_harmonic_batch_device_vector(self.h, int(sys), VEC[which], C.byref(p), C.byref(n)),
              "ec3d_harmonic_batch_device_vector")
         return p.value, n.value
+
+    # ---- the left null vectors inside a batch ----
+    def harmonic_batch_set_null_projection(self, on: bool = True, null_tol: float = 1e-10):
+        """Take the left null vectors of every system's own K + j omega_s M out of its initial residual in
+        harmonic_batch_solve (ec3d_harmonic_batch_set_null_projection): each system then gets the bits of its own
+        harmonic_solve with harmonic_set_null_projection on.  A setting of the batch, separate from the single solve's;
+        needs a batch (switching off does not).  The first solve of a batch builds the vectors, the adjoint solves of
+        the batch's distinct omegas in lock step; a set-up that misses ``null_tol`` raises with .status NULL_E_SETUP."""
+        _chk(self.L, self.L.ec3d_harmonic_batch_set_null_projection(self.h, 1 if on else 0, float(null_tol)),
+             "ec3d_harmonic_batch_set_null_projection")
+
+    def harmonic_batch_null_projection(self, sys: int):
+        """The dict of harmonic_null_projection() for system ``sys`` (ec3d_get_harmonic_batch_null): setup_ms is the
+        whole set-up's, removed that of the system's last projection; ``shares_with``: the lowest system with the same
+        omega, whose vectors this system uses."""
+        g, sw = NullInfo(), C.c_int32(-1)
+        _chk(self.L, self.L.ec3d_get_harmonic_batch_null(self.h, int(sys), C.byref(g), C.byref(sw)), "ec3d_get_harmonic_batch_null")
+        rs = np.zeros(32, np.int32)
+        _chk(self.L, self.L.ec3d_harmonic_batch_null_restarts(self.h, int(sys), rs.ctypes.data), "ec3d_harmonic_batch_null_restarts")
+        comps = [dict(seed_row=int(g.seed_row[i]), iterations=int(g.iterations[i]), residual=float(g.residual[i]),
+                      kept=bool(g.was_kept[i]), restarts=int(rs[i])) for i in range(int(g.reported))]
+        return dict(on=bool(g.on), built=bool(g.built), found=int(g.found), kept=int(g.kept), dropped=int(g.dropped),
+                    null_tol=float(g.null_tol), removed=float(g.removed), setup_ms=float(g.setup_ms), components=comps,
+                    shares_with=int(sw.value))
+
+    def harmonic_batch_left_null_vector(self, sys: int, index: int = 0):
+        """Kept left null vector ``index`` of system ``sys``'s operator (complex, unit norm, the reference numbering);
+        builds the batch's vectors when the projection is on and they do not exist yet."""
+        re, im = np.empty(self.n), np.empty(self.n)
+        _chk(self.L, self.L.ec3d_harmonic_batch_left_null_vector(self.h, int(sys), int(index), re.ctypes.data, im.ctypes.data),
+             "ec3d_harmonic_batch_left_null_vector")
+        return self._complex(re, im)
+
+    def harmonic_batch_projected_residual(self):
+        """[(||P_s (b^_s - A_s x^_s)|| / ||b^_s||, removed_s), ...], one per system, with each system's own vectors."""
+        rel, rem = np.zeros(HARMONIC_MAX_BATCH), np.zeros(HARMONIC_MAX_BATCH)
+        _chk(self.L, self.L.ec3d_harmonic_batch_projected_residual(self.h, rel.ctypes.data, rem.ctypes.data),
+             "ec3d_harmonic_batch_projected_residual")
+        return [(float(rel[k]), float(rem[k])) for k in range(getattr(self, "_harmonic_batch_nsys", 0))]
 
     def set_u_rhs(self, rule: str = "reference"):
         """Which U rows rhs_step gives their right-hand side with several conducting domains: "reference" (default)

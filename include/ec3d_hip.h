@@ -973,6 +973,36 @@ int ec3d_harmonic_batch_solve(ec3d_handle h, double tol, int32_t itmax, int32_t 
 int ec3d_get_harmonic_batch(ec3d_handle h, int32_t sys, ec3d_harmonic_info *out);
 int ec3d_harmonic_batch_select(ec3d_handle h, int32_t sys);
 int ec3d_harmonic_batch_device_vector(ec3d_handle h, int32_t sys, int which, double **device_ptr, int64_t *pairs);
+/* The left null vectors inside a batch (opt-in): every system s gets the Q_s of its own omega_s
+ * and is solved as ec3d_harmonic_solve solves it with ec3d_harmonic_set_null_projection on -- x^_s, iter, restarts,
+ * stop_kind, relres and removed bit for bit.  A setting of the batch, separate from the single solve's (while THAT one is
+ * on, ec3d_harmonic_batch_solve is refused as before).  With it on, the first ec3d_harmonic_batch_solve of a batch (or
+ * ec3d_harmonic_batch_left_null_vector, ec3d_harmonic_batch_projected_residual) builds the vectors: per conducting
+ * component, the adjoint solves of the DISTINCT omegas of the batch run in lock step -- in the work vectors, partials
+ * and states of the first systems, the unknown in a staging vector per omega; x^_s and b^_s keep their bytes -- and
+ * every step of the single set-up (seed rows, c = A^H (-e_m), the cap, w = y + e_m, the 2 null_tol check of the true
+ * residual, classical Gram-Schmidt, EC3D_NULL_MIN_KEEP) follows per omega, so the number of vectors kept is per omega.
+ * Systems with bit-equal omega share one set of vectors.  Every solve then takes Q_s out of system s's initial residual
+ * between the batch's begin launch and its set-up launch.  A set-up that misses null_tol returns EC3D_NULL_E_SETUP with
+ * system, component and seed row in the error text, and no vector is kept.  null_tol <= 0: the default 1e-10.  Another
+ * null_tol, a new ec3d_harmonic_batch_setup, nsys = 0, a new matrix or ec3d_destroy frees the vectors; the setting
+ * stays with the handle.  on = 0 (default): nothing more is allocated or launched.
+ * ec3d_get_harmonic_batch_null: ec3d_null_info as ec3d_get_harmonic_null fills it, for system sys (setup_ms: the whole
+ * set-up's; removed: of system sys's last projection); *shares_with (may be NULL): the lowest system with the same omega.
+ * ec3d_harmonic_batch_left_null_vector: kept vector `index` of system sys.  ec3d_harmonic_batch_null_restarts: the
+ * restart counts of system sys's adjoint solves, EC3D_NULL_MAX_REPORT entries.  ec3d_harmonic_batch_projected_residual:
+ * per system ||P_s (b^_s - A_s x^_s)|| / ||b^_s|| and removed (nsys entries each; removed may be NULL); overwrites R,
+ * R0, P of every system; 2 with the setting off.  While the vectors exist, device_bytes of ec3d_get_harmonic_batch
+ * counts them.
+ * ec3d_harmonic_batch_projected_residual runs a projection of its own: behind it `removed` of
+ * ec3d_get_harmonic_batch_null is that projection's figure, no longer the last solve's.
+ * Refusals: 3, 5 and EC3D_NULL_E_MATRIX as the other batch entry points -- switching off included --; 2 before a batch
+ * set-up (only switching OFF needs no batch), for a sys or an index outside, or a NULL. */
+int ec3d_harmonic_batch_set_null_projection(ec3d_handle h, int32_t on, double null_tol);
+int ec3d_get_harmonic_batch_null(ec3d_handle h, int32_t sys, ec3d_null_info *info, int32_t *shares_with);
+int ec3d_harmonic_batch_left_null_vector(ec3d_handle h, int32_t sys, int32_t index, double *re, double *im);
+int ec3d_harmonic_batch_null_restarts(ec3d_handle h, int32_t sys, int32_t *restarts);
+int ec3d_harmonic_batch_projected_residual(ec3d_handle h, double *rel, double *removed);
 
 #ifdef __cplusplus
 }
