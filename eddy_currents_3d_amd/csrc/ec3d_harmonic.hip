@@ -3,7 +3,7 @@
 //
 // Operator.  The class bytes of the real matrix with two tables of their own, made at ec3d_assemble
 // (k_build_table_harmonic): re, the transient table without its dt terms, and m, the unit imaginary part;
-// ec3d_harmonic_setup interleaves (re, omega * m) into one table of 16 pairs per class, which k_h_spmv holds in LDS.
+// a set-up interleaves (re, omega * m) into one table of 16 pairs per class, which k_hb_spmv holds in LDS.
 //
 // Vectors.  Eight complex vectors of n_pad interleaved (re, im) pairs in device numbering, no ghosts: a row's class is
 // tested before a neighbour is read, as in ec3d_transpose.hip.  A row is one 16-byte access.
@@ -20,36 +20,33 @@
 // (stream_strided_sum, stream_block_sum) and compute the scalars redundantly -- identical bits in every workgroup --
 // and workgroup 0 records them.  No float atomics.
 //
+// Systems.  Everything below is written once, for S systems (omega_s, b^_s, x^_s) on the one matrix
+// in lock step: the kernels of the iteration run on a grid of (G, S) and blockIdx.y names the system, whose state,
+// partials, table and vectors stand s strides behind system 0's.  h_leave and h_collapse index with gridDim.x and
+// blockIdx.x only, so a system's bits depend on neither S nor s.  The single solve (ec3d_harmonic_setup) is S = 1 in
+// storage of its own; a batch (ec3d_harmonic_batch_*) holds up to EC3D_HARMONIC_MAX_BATCH.  The host describes the
+// systems of a run in an HRun, which every launch_* takes.
+//
 // Iteration `it` (src/solvers.f90:29-49), five launches:
-//   k_h_spmv<1>   AP = A P, <R0, AP>
-//   k_h_s         alpha = rr0 / <R0, AP>;  S = R - alpha AP, ||S||^2
-//   k_h_spmv<2>   AS = A S, <AS, S>, <AS, AS>
-//   k_h_xr        ||S|| exit: X = X + alpha P.  Else omega = <AS, S> / <AS, AS>; X = (X + alpha P) + omega S;
+//   k_hb_spmv<1>  AP = A P, <R0, AP>
+//   k_hb_s        alpha = rr0 / <R0, AP>;  S = R - alpha AP, ||S||^2
+//   k_hb_spmv<2>  AS = A S, <AS, S>, <AS, AS>
+//   k_hb_xr       ||S|| exit: X = X + alpha P.  Else omega = <AS, S> / <AS, AS>; X = (X + alpha P) + omega S;
 //                 R = S - omega AS, ||R||^2, <R0, R>
-//   k_h_p         ||R|| exit.  Else beta = (alpha / omega) rr0_new / rr0; restart (R0 = R, P = R, rr0 = ||R||^2) when
+//   k_hb_p        ||R|| exit.  Else beta = (alpha / omega) rr0_new / rr0; restart (R0 = R, P = R, rr0 = ||R||^2) when
 //                 |rr0_new| / ||b^|| < tol, else P = R + beta (P - omega AP), rr0 = rr0_new
-// The exit words stay on the device: stop_s is written by k_h_xr only, stop_r by k_h_p (and the set-up) only, and a
+// The exit words stay on the device: stop_s is written by k_hb_xr only, stop_r by k_hb_p (and k_hb_setup) only, and a
 // kernel never tests at its entry a word that its own launch may write with a value that would change the test --
-// k_h_xr of iteration it asks stop_s < it, k_h_p stop_r < it -- so a workgroup that starts late takes the same path as
-// workgroup 0.  rr0 alternates between two slots for the same reason.  The host enqueues 16 iterations and polls once.
+// k_hb_xr of iteration it asks stop_s < it, k_hb_p stop_r < it -- so a workgroup that starts late takes the same path as
+// workgroup 0.  rr0 alternates between two slots for the same reason.  The host enqueues 16 iterations and copies the S
+// states back once (run_iterations), on while any system runs; a stopped system's workgroups return at their first load.
 //
-// Left null vectors (opt-in, ec3d_harmonic_set_null_projection).  K + j omega M is singular as the
-// transient matrix is: one left null vector per connected conducting component, and every residual keeps w^H r = w^H b^.
-// The set-up (null_build) finds them by adjoint solves -- the iteration above around k_h_spmv_h, y = A^H x -- and a solve
-// with the setting on takes them out of its initial residual between k_h_spmv<3> and k_h_setup (k_hn_dots,
-// k_hn_collapse, k_hn_sub).  tests/harmonic_null_numpy.py restates every line.
-//
-// Batch (opt-in, ec3d_harmonic_batch_*).  Up to EC3D_HARMONIC_MAX_BATCH systems (omega_s, b^_s, x^_s)
-// on the one matrix ride in the five launches of an iteration on a grid of (G, S): the bodies of k_h_s, k_h_xr, k_h_p
-// and k_h_setup are __device__ functions, as h_spmv_modes is, and k_hb_* run them on the system blockIdx.y names.  Every
-// system keeps the bits of its own single solve; the host copies the S states back once per 16 lock-step iterations.
-//
-// Left null vectors inside a batch (opt-in, ec3d_harmonic_batch_set_null_projection).  One set of
-// vectors per distinct omega of the batch: batch_null_build runs the adjoint solves of all the sets in lock step --
-// k_hb_spmv_h and k_hb_xr_at around the batch's own k_hb_s, k_hb_p, k_hb_setup, in the work vectors of the first systems,
-// the unknown in a staging vector per set -- and null_build's every step per set; k_hbn_* are k_hn_* with the system as
-// one more grid dimension, and batch_launch_project takes every system's own vectors out of its R between k_hb_spmv<3>
-// and k_hb_setup.  Every system keeps the bits of its own single projected solve.
+// Left null vectors (opt-in, ec3d_harmonic_set_null_projection and ec3d_harmonic_batch_set_null_projection; DESIGN
+// sections 18a, 18c).  K + j omega M is singular as the transient matrix is: one left null vector per connected
+// conducting component, and every residual keeps w^H r = w^H b^.  The set-up (null_build) finds one set of vectors per
+// distinct omega by adjoint solves in lock step -- the iteration above around k_hb_spmv_h, y = A^H x, and k_hb_xr_at --
+// and a solve with the setting on takes every system's own vectors out of its initial residual between k_hb_spmv<3> and
+// k_hb_setup (launch_project: k_hbn_dots, k_hbn_collapse, k_hbn_sub).  tests/harmonic_null_numpy.py restates every line.
 #include "ec3d_stream.hpp"
 
 #include <chrono>
@@ -62,7 +59,7 @@ struct HarmonicState {
     double rr0[2][2]; // <R0, R> entering iteration it: rr0[it & 1]
     double alpha[2], omega[2];
     double bnorm, tol;
-    double rnorm, snorm; // of the last k_h_p / k_h_xr that got that far
+    double rnorm, snorm; // of the last k_hb_p / k_hb_xr that got that far
     int stop_s, stop_r;  // INT_MAX while running; the iteration of the ||S|| / ||R|| exit (stop_r = 0: ||b^|| = 0)
     int restarts, pad_;
 };
@@ -70,7 +67,7 @@ struct HarmonicState {
 namespace {
 
 typedef stream_d2 cplx; // .x = re, .y = im
-static_assert((55 + 9 * EC3D_SAV_MAXDOM) * 16 * sizeof(cplx) + 256 <= 65536, "k_h_spmv: the table of pairs fits 64 KB of LDS");
+static_assert((55 + 9 * EC3D_SAV_MAXDOM) * 16 * sizeof(cplx) + 256 <= 65536, "k_hb_spmv: the table of pairs fits 64 KB of LDS");
 
 __device__ __forceinline__ cplx cmul(cplx a, cplx b) { return cplx{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
 __device__ __forceinline__ cplx cdiv(cplx a, cplx b)
@@ -250,31 +247,7 @@ __device__ __forceinline__ void h_spmv_modes(const HSav &A, const cplx *__restri
     }
 }
 
-template <int MODE>
-__global__ __launch_bounds__(EC3D_THREADS) void k_h_spmv(HSav A, const HarmonicState *st, const cplx *__restrict__ x,
-                                                        const cplx *__restrict__ o, cplx *__restrict__ y,
-                                                        cplx *__restrict__ r0, cplx *__restrict__ p, int64_t nchunk,
-                                                        double *__restrict__ part)
-{
-    extern __shared__ cplx tbl[];
-    __shared__ double lds[12];
-    h_spmv_modes<MODE, false>(A, A.table, st, x, o, y, r0, p, nchunk, part, tbl, lds);
-}
-
-// y = A^H x in the layout, the modes and the partial slots of k_h_spmv: the adjoint solves of the left null vectors run
-// k_h_s, k_h_xr, k_h_p and k_h_setup around it unchanged
-template <int MODE>
-__global__ __launch_bounds__(EC3D_THREADS) void k_h_spmv_h(HSav A, const HarmonicState *st, const cplx *__restrict__ x,
-                                                          const cplx *__restrict__ o, cplx *__restrict__ y,
-                                                          cplx *__restrict__ r0, cplx *__restrict__ p, int64_t nchunk,
-                                                          double *__restrict__ part)
-{
-    extern __shared__ cplx tbl[];
-    __shared__ double lds[12];
-    h_spmv_modes<MODE, true>(A, A.table, st, x, o, y, r0, p, nchunk, part, tbl, lds);
-}
-
-// behind k_h_spmv<3>, one workgroup: ||b^||, rr0 = <R0, R> = (||R||^2, 0), the exit words
+// behind k_hb_spmv<3>, one workgroup: ||b^||, rr0 = <R0, R> = (||R||^2, 0), the exit words
 __device__ __forceinline__ void h_setup_body(HarmonicState *st, const double *part, int G, double tol, double *lds)
 {
     double v[2];
@@ -293,12 +266,6 @@ __device__ __forceinline__ void h_setup_body(HarmonicState *st, const double *pa
     st->stop_r = bnorm == 0.0 ? 0 : INT_MAX; // src/solvers.f90:23
     st->restarts = 0;
     st->pad_ = 0;
-}
-
-__global__ __launch_bounds__(EC3D_THREADS) void k_h_setup(HarmonicState *st, const double *part, int G, double tol)
-{
-    __shared__ double lds[8];
-    h_setup_body(st, part, G, tol, lds);
 }
 
 __device__ __forceinline__ void h_s_body(HarmonicState *st, int it, const cplx *__restrict__ r,
@@ -323,14 +290,6 @@ __device__ __forceinline__ void h_s_body(HarmonicState *st, int it, const cplx *
             acc[0] = acc[0] + cabs2(s);
         }
     h_leave<1>(acc, part, HP_SS, lds);
-}
-
-__global__ __launch_bounds__(EC3D_THREADS) void k_h_s(HarmonicState *st, int it, const cplx *__restrict__ r,
-                                                     const cplx *__restrict__ ap, cplx *__restrict__ sv, int64_t n,
-                                                     int64_t nchunk, double *__restrict__ part)
-{
-    __shared__ double lds[8];
-    h_s_body(st, it, r, ap, sv, n, nchunk, part, lds);
 }
 
 __device__ __forceinline__ void h_xr_body(HarmonicState *st, int it, const cplx *__restrict__ p,
@@ -382,16 +341,6 @@ __device__ __forceinline__ void h_xr_body(HarmonicState *st, int it, const cplx 
     h_leave<3>(acc, part, HP_RR, lds);
 }
 
-__global__ __launch_bounds__(EC3D_THREADS) void k_h_xr(HarmonicState *st, int it, const cplx *__restrict__ p,
-                                                      const cplx *__restrict__ sv, const cplx *__restrict__ as,
-                                                      const cplx *__restrict__ r0, cplx *__restrict__ x,
-                                                      cplx *__restrict__ r, int64_t n, int64_t nchunk,
-                                                      double *__restrict__ part)
-{
-    __shared__ double lds[16];
-    h_xr_body(st, it, p, sv, as, r0, x, r, n, nchunk, part, lds);
-}
-
 __device__ __forceinline__ void h_p_body(HarmonicState *st, int it, const cplx *__restrict__ r,
                                          const cplx *__restrict__ ap, cplx *__restrict__ p, cplx *__restrict__ r0,
                                          int64_t n, int64_t nchunk, const double *__restrict__ part, double *lds)
@@ -433,19 +382,9 @@ __device__ __forceinline__ void h_p_body(HarmonicState *st, int it, const cplx *
         }
 }
 
-__global__ __launch_bounds__(EC3D_THREADS) void k_h_p(HarmonicState *st, int it, const cplx *__restrict__ r,
-                                                     const cplx *__restrict__ ap, cplx *__restrict__ p,
-                                                     cplx *__restrict__ r0, int64_t n, int64_t nchunk,
-                                                     const double *__restrict__ part)
-{
-    __shared__ double lds[12];
-    h_p_body(st, it, r, ap, p, r0, n, nchunk, part, lds);
-}
-
-// ---- a batch of systems in lock step (ec3d_harmonic_batch_*) -----------------------------------
+// ---- the kernels of the iteration: S systems in lock step on a grid of (G, S) (DESIGN sections 18, 18b) -------------
 // blockIdx.y is the system: its state, partials, table and vectors stand `sys` strides further, and the workgroup then
-// runs the body of the single kernel.  h_leave and h_collapse index with gridDim.x and blockIdx.x only, so the sums of
-// system s are the sums of its own single solve; a stopped system's workgroups return at their first load.
+// runs one of the bodies above.  The single solve is the grid (G, 1).
 struct HBatch {
     cplx *vec;            // system s, vector w: vec + (s * HV_N + w) * len
     double *part;         // system s: part + s * HP_NSLOT * gridDim.x
@@ -455,22 +394,39 @@ struct HBatch {
 __device__ __forceinline__ cplx *hb_vec(const HBatch &B, int w) { return B.vec + ((int64_t)blockIdx.y * HV_N + w) * B.len; }
 __device__ __forceinline__ double *hb_part(const HBatch &B) { return B.part + (int64_t)blockIdx.y * HP_NSLOT * gridDim.x; }
 
-// k_h_spmv<MODE> on system blockIdx.y: st, part and the vectors are system 0's, the next system's stand 1 state,
-// HP_NSLOT * gridDim.x partials and `vstride` pairs further; A.table is system 0's table.  The vectors come as arguments
-// of their own, __restrict__ as k_h_spmv's: behind one base pointer the same body takes 98 VGPRs instead of 72
+// h_spmv_modes<MODE> on system blockIdx.y: st, part and the vectors are system 0's, the next system's stand 1 state,
+// HP_NSLOT * gridDim.x partials and `vstride` pairs further; A.table is system 0's table.  The vectors come as
+// __restrict__ arguments of their own: behind one base pointer the same body takes 98 VGPRs instead of 72
 template <int MODE>
 __global__ __launch_bounds__(EC3D_THREADS) void k_hb_spmv(HSav A, const HarmonicState *st, const cplx *__restrict__ x,
                                                          const cplx *__restrict__ o, cplx *__restrict__ y,
                                                          cplx *__restrict__ r0, cplx *__restrict__ p, int64_t nchunk,
                                                          double *__restrict__ part, int64_t vstride)
 {
-    static_assert(MODE >= 1 && MODE <= 3, "the batch has the begin launch and the two products of an iteration");
     extern __shared__ cplx tbl[];
     __shared__ double lds[12];
     const int64_t sys = blockIdx.y, v = sys * vstride;
-    h_spmv_modes<MODE, false>(A, A.table + sys * A.ncls * 16, st + sys, x + v, MODE == 2 ? nullptr : o + v, y + v,
-                              MODE == 3 ? r0 + v : nullptr, MODE == 3 ? p + v : nullptr, nchunk,
+    h_spmv_modes<MODE, false>(A, A.table + sys * A.ncls * 16, st + sys, x + v, MODE == 1 || MODE == 3 ? o + v : nullptr,
+                              y + v, MODE == 3 ? r0 + v : nullptr, MODE == 3 ? p + v : nullptr, nchunk,
                               part + sys * HP_NSLOT * gridDim.x, tbl, lds);
+}
+
+// y = A^H x in the layout, the modes and the partial slots of k_hb_spmv: the adjoint solves of the left null vectors
+// (DESIGN sections 18a, 18c) run the other four kernels around it unchanged.  There blockIdx.y is a SET of vectors, one
+// per distinct omega, which borrows the work vectors, the partials and the state of system blockIdx.y; x stands
+// `xstride` pairs apart -- the unknown of an adjoint solve is no work vector (MODE 3, and MODE 0 on w)
+template <int MODE>
+__global__ __launch_bounds__(EC3D_THREADS) void k_hb_spmv_h(HSav A, const HarmonicState *st, const cplx *__restrict__ x,
+                                                           const cplx *__restrict__ o, cplx *__restrict__ y,
+                                                           cplx *__restrict__ r0, cplx *__restrict__ p, int64_t nchunk,
+                                                           double *__restrict__ part, int64_t vstride, int64_t xstride)
+{
+    extern __shared__ cplx tbl[];
+    __shared__ double lds[12];
+    const int64_t sys = blockIdx.y, v = sys * vstride;
+    h_spmv_modes<MODE, true>(A, A.table + sys * A.ncls * 16, st + sys, x + sys * xstride,
+                             MODE == 1 || MODE == 3 ? o + v : nullptr, y + v, MODE == 3 ? r0 + v : nullptr,
+                             MODE == 3 ? p + v : nullptr, nchunk, part + sys * HP_NSLOT * gridDim.x, tbl, lds);
 }
 
 // one workgroup per system (grid (1, S)) behind k_hb_spmv<3> on (G, S)
@@ -493,108 +449,8 @@ __global__ __launch_bounds__(EC3D_THREADS) void k_hb_xr(HBatch B, int it, int64_
               hb_vec(B, HV_R), n, nchunk, hb_part(B), lds);
 }
 
-__global__ __launch_bounds__(EC3D_THREADS) void k_hb_p(HBatch B, int it, int64_t n, int64_t nchunk)
-{
-    __shared__ double lds[12];
-    h_p_body(B.state + blockIdx.y, it, hb_vec(B, HV_R), hb_vec(B, HV_AP), hb_vec(B, HV_P), hb_vec(B, HV_R0), n, nchunk, hb_part(B),
-             lds);
-}
-
-// ---- left null vectors: the streaming kernels of the set-up and of the projection -------------
-// partials of c_i = <Q_i, v>, Q_i = qbase + i * qstride, i = blockIdx.y: the two parts at part[(2 i + {0, 1}) * G + b]
-__global__ __launch_bounds__(EC3D_THREADS) void k_hn_dots(const cplx *__restrict__ qbase, int64_t qstride,
-                                                         const cplx *__restrict__ v, int64_t n, int64_t nchunk,
-                                                         double *__restrict__ part)
-{
-    __shared__ double lds[8];
-    const cplx *q = qbase + (int64_t)blockIdx.y * qstride;
-    double acc[2] = {0.0, 0.0};
-    for (int64_t ch = blockIdx.x; ch < nchunk; ch += gridDim.x)
-        for (int half = 0; half < 2; ++half) {
-            const int64_t i = h_row(ch, half);
-            if (i >= n) continue;
-            const cplx d = cdot(q[i], v[i]);
-            acc[0] = acc[0] + d.x;
-            acc[1] = acc[1] + d.y;
-        }
-    h_leave<2>(acc, part, 2 * (int)blockIdx.y, lds);
-}
-
-// workgroup i: coef[i] = the two parts of c_i, from `count` partials each
-__global__ __launch_bounds__(EC3D_THREADS) void k_hn_collapse(const double *__restrict__ part, int count, cplx *__restrict__ coef)
-{
-    __shared__ double lds[8];
-    double v[2];
-    stream_strided_sum<2>(v, part + (int64_t)2 * blockIdx.x * count, count, count);
-    stream_block_sum<2>(v, lds);
-    if (threadIdx.x == 0) coef[blockIdx.x] = cplx{v[0], v[1]};
-}
-
-// v = v - c_0 Q_0 - ... - c_{k-1} Q_{k-1}, every term a rounded cmul and a rounded difference per part; r0, p (or null):
-// copies of the new v; rr (or null): workgroup b's partial of ||v||^2 at rr[b], written by EVERY workgroup of the launch
-__global__ __launch_bounds__(EC3D_THREADS) void k_hn_sub(const cplx *__restrict__ qbase, int64_t qstride, int k,
-                                                        const cplx *__restrict__ coef, cplx *__restrict__ v,
-                                                        cplx *__restrict__ r0, cplx *__restrict__ p, int64_t n,
-                                                        int64_t nchunk, double *__restrict__ rr)
-{
-    __shared__ double lds[4];
-    double acc[1] = {0.0};
-    for (int64_t ch = blockIdx.x; ch < nchunk; ch += gridDim.x)
-        for (int half = 0; half < 2; ++half) {
-            const int64_t i = h_row(ch, half);
-            if (i >= n) continue;
-            cplx x = v[i];
-            for (int m = 0; m < k; ++m) {
-                const cplx t = cmul(coef[m], qbase[(int64_t)m * qstride + i]);
-                x = cplx{x.x - t.x, x.y - t.y};
-            }
-            v[i] = x;
-            if (r0) r0[i] = x;
-            if (p) p[i] = x;
-            acc[0] = acc[0] + cabs2(x);
-        }
-    if (!rr) return;
-    stream_block_sum<1>(acc, lds);
-    if (threadIdx.x == 0) rr[blockIdx.x] = acc[0];
-}
-
-// v = v / d on rows < n, each part divided on its own
-__global__ __launch_bounds__(EC3D_THREADS) void k_hn_div(cplx *__restrict__ v, double d, int64_t n, int64_t nchunk)
-{
-    for (int64_t ch = blockIdx.x; ch < nchunk; ch += gridDim.x)
-        for (int half = 0; half < 2; ++half) {
-            const int64_t i = h_row(ch, half);
-            if (i >= n) continue;
-            const cplx a = v[i];
-            v[i] = cplx{a.x / d, a.y / d};
-        }
-}
-
-// Re v[row] = Re v[row] + a (e_m and -e_m)
-__global__ void k_hn_add_re(cplx *v, int64_t row, double a) { v[row].x = v[row].x + a; }
-
-// ---- left null vectors inside a batch ----------------------------------------------------------
-// The adjoint solves of the batch's distinct omegas in lock step: `sys` below is a SET of vectors (one per distinct
-// omega), which borrows the work vectors, the partials and the state of system `sys` of the batch.
-// k_h_spmv_h<MODE> on set blockIdx.y: A.table is set 0's table; st, part, o, y, r0, p are system 0's, `vstride` pairs
-// apart; x stands `xstride` pairs apart -- the unknown of the adjoint solves has a vector of its own per set (MODE 3,
-// and MODE 0 on w), the work vectors have the batch's stride.  __restrict__ arguments of system 0 plus strides, as
-// k_hb_spmv has them.
-template <int MODE>
-__global__ __launch_bounds__(EC3D_THREADS) void k_hb_spmv_h(HSav A, const HarmonicState *st, const cplx *__restrict__ x,
-                                                           const cplx *__restrict__ o, cplx *__restrict__ y,
-                                                           cplx *__restrict__ r0, cplx *__restrict__ p, int64_t nchunk,
-                                                           double *__restrict__ part, int64_t vstride, int64_t xstride)
-{
-    extern __shared__ cplx tbl[];
-    __shared__ double lds[12];
-    const int64_t sys = blockIdx.y, v = sys * vstride;
-    h_spmv_modes<MODE, true>(A, A.table + sys * A.ncls * 16, st + sys, x + sys * xstride,
-                             MODE == 1 || MODE == 3 ? o + v : nullptr, y + v, MODE == 3 ? r0 + v : nullptr,
-                             MODE == 3 ? p + v : nullptr, nchunk, part + sys * HP_NSLOT * gridDim.x, tbl, lds);
-}
-
-// k_hb_xr with the unknown at x + blockIdx.y * xstride in place of the system's HV_X
+// k_hb_xr with the unknown at x + blockIdx.y * xstride in place of the system's HV_X (the adjoint solves).  A kernel of
+// its own: the pointer beside the HBatch costs 10 VGPRs and a wave of occupancy (70 and 7 against 60 and 8)
 __global__ __launch_bounds__(EC3D_THREADS) void k_hb_xr_at(HBatch B, int it, cplx *__restrict__ x, int64_t xstride, int64_t n,
                                                           int64_t nchunk)
 {
@@ -603,8 +459,16 @@ __global__ __launch_bounds__(EC3D_THREADS) void k_hb_xr_at(HBatch B, int it, cpl
               x + (int64_t)blockIdx.y * xstride, hb_vec(B, HV_R), n, nchunk, hb_part(B), lds);
 }
 
-// The streaming kernels above with the system as one more grid dimension.  System s projects with the vectors of set
-// set[s], of which kept[s] exist; a workgroup of a vector past kept[s] returns before it reads or writes anything.
+__global__ __launch_bounds__(EC3D_THREADS) void k_hb_p(HBatch B, int it, int64_t n, int64_t nchunk)
+{
+    __shared__ double lds[12];
+    h_p_body(B.state + blockIdx.y, it, hb_vec(B, HV_R), hb_vec(B, HV_AP), hb_vec(B, HV_P), hb_vec(B, HV_R0), n, nchunk, hb_part(B),
+             lds);
+}
+
+// ---- left null vectors (DESIGN sections 18a, 18c): the streaming kernels of the set-up and of the projection --------
+// The system is a grid dimension here too.  System s projects with the vectors of set set[s], of which kept[s] exist; a
+// workgroup of a vector past kept[s] returns before it reads or writes anything.
 struct HNSys {
     int32_t set[EC3D_HARMONIC_MAX_BATCH], kept[EC3D_HARMONIC_MAX_BATCH];
 };
@@ -612,8 +476,9 @@ struct HNDiv {
     double d[EC3D_HARMONIC_MAX_BATCH]; // 0: the system is skipped
 };
 
-// k_hn_dots on system blockIdx.z: Q_i = qbase + set[s] * qset + i * qstride, v = vbase + s * vstride, the partials at
-// part + s * pstride.  h_leave indexes with gridDim.x and blockIdx.x only: the sums are k_hn_dots' own
+// partials of c_i = <Q_i, v> of system s = blockIdx.z, i = blockIdx.y: Q_i = qbase + set[s] * qset + i * qstride,
+// v = vbase + s * vstride, the two parts at part[s * pstride + (2 i + {0, 1}) * G + b].  h_leave indexes with gridDim.x
+// and blockIdx.x only: the sums do not depend on the other two grid dimensions
 __global__ __launch_bounds__(EC3D_THREADS) void k_hbn_dots(HNSys M, const cplx *__restrict__ qbase, int64_t qset, int64_t qstride,
                                                           const cplx *__restrict__ vbase, int64_t vstride, int64_t n,
                                                           int64_t nchunk, double *__restrict__ part, int64_t pstride)
@@ -635,7 +500,7 @@ __global__ __launch_bounds__(EC3D_THREADS) void k_hbn_dots(HNSys M, const cplx *
     h_leave<2>(acc, part + (int64_t)s * pstride, 2 * (int)blockIdx.y, lds);
 }
 
-// k_hn_collapse on system blockIdx.y: coef[s * cstride + i]
+// workgroup (i, s): coef[s * cstride + i] = the two parts of c_i of system s, from `count` partials each
 __global__ __launch_bounds__(EC3D_THREADS) void k_hbn_collapse(HNSys M, const double *__restrict__ part, int64_t pstride, int count,
                                                               cplx *__restrict__ coef, int64_t cstride)
 {
@@ -648,8 +513,10 @@ __global__ __launch_bounds__(EC3D_THREADS) void k_hbn_collapse(HNSys M, const do
     if (threadIdx.x == 0) coef[(int64_t)s * cstride + blockIdx.x] = cplx{v[0], v[1]};
 }
 
-// k_hn_sub on system blockIdx.y with its own kept[s] vectors; r0, p, rr (or null) are system 0's, vstride pairs and
-// rrstride doubles apart.  A system that kept nothing is left as it is, partials included
+// v = v - c_0 Q_0 - ... - c_{k-1} Q_{k-1} on system s = blockIdx.y with its own k = kept[s] vectors, every term a rounded
+// cmul and a rounded difference per part; r0, p (or null): copies of the new v; rr (or null): workgroup b's partial of
+// ||v||^2 at rr[b], written by EVERY workgroup of the system.  r0, p, rr are system 0's, vstride pairs and rrstride
+// doubles apart.  A system that kept nothing is left as it is, partials included
 __global__ __launch_bounds__(EC3D_THREADS) void k_hbn_sub(HNSys M, const cplx *__restrict__ qbase, int64_t qset, int64_t qstride,
                                                          const cplx *__restrict__ coef, int64_t cstride, cplx *__restrict__ vbase,
                                                          cplx *__restrict__ r0base, cplx *__restrict__ pbase, int64_t vstride,
@@ -682,7 +549,7 @@ __global__ __launch_bounds__(EC3D_THREADS) void k_hbn_sub(HNSys M, const cplx *_
     if (threadIdx.x == 0) rrbase[(int64_t)s * rrstride + blockIdx.x] = acc[0];
 }
 
-// k_hn_div on system blockIdx.y by D.d[s]
+// v = v / D.d[s] on rows < n of system s = blockIdx.y, each part divided on its own
 __global__ __launch_bounds__(EC3D_THREADS) void k_hbn_div(HNDiv D, cplx *__restrict__ vbase, int64_t vstride, int64_t n, int64_t nchunk)
 {
     const double d = D.d[blockIdx.y];
@@ -697,7 +564,7 @@ __global__ __launch_bounds__(EC3D_THREADS) void k_hbn_div(HNDiv D, cplx *__restr
         }
 }
 
-// k_hn_add_re on system blockIdx.x
+// Re v[row] = Re v[row] + a (e_m and -e_m) on system blockIdx.x
 __global__ void k_hbn_add_re(cplx *vbase, int64_t vstride, int64_t row, double a)
 {
     cplx *v = vbase + (int64_t)blockIdx.x * vstride;
@@ -756,12 +623,13 @@ __global__ void k_h_zero_list(const int32_t *list, int64_t cnt, double *x, doubl
 
 inline unsigned blocks(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + 255) / 256); }
 
-HSav view_of(const ec3d_ctx *c)
+// the matrix with the table of system (or set) 0
+HSav view_of(const ec3d_ctx *c, const cplx *table)
 {
     const DevMatrix &A = c->A;
     HSav T;
     T.cls = A.cls;
-    T.table = reinterpret_cast<const cplx *>(c->harm.tab.get());
+    T.table = table;
     T.ncls = A.ncls;
     T.a0 = A.sav_a0;
     T.u0 = A.sav_u0;
@@ -773,83 +641,135 @@ HSav view_of(const ec3d_ctx *c)
     return T;
 }
 
-cplx *hv(const ec3d_ctx *c, int w) { return reinterpret_cast<cplx *>(c->harm.vec[w]); }
+// vector w of system sys
+cplx *sysv(const ec3d_ctx *c, const HarmonicSystems &T, int sys, int w)
+{
+    return reinterpret_cast<cplx *>(T.vec.get()) + ((size_t)sys * HV_N + (size_t)w) * (size_t)c->A.n_pad;
+}
+cplx *hv(const ec3d_ctx *c, int w) { return sysv(c, c->harm.one, 0, w); }
+bool is_batch(const ec3d_ctx *c, const HarmonicSystems &T) { return &T == &c->harm.batch; }
 
 // the operator of a solve: K + j omega M or its conjugate transpose (the adjoint solves of the left null vectors)
 enum HOp { H_A = 0, H_AH };
 
-template <int MODE> void launch_spmv(ec3d_ctx *c, HOp op, const cplx *x, const cplx *o, cplx *y, cplx *r0, cplx *p)
+// S systems in lock step, as every launch of the iteration takes them: system s works in the state, partials and
+// vectors `s` strides behind B's, under the table tab + s * ncls * 16, on the unknown x + s * xstride
+struct HRun {
+    int S, G;
+    HBatch B;
+    const cplx *tab;
+    HOp op;
+    cplx *x;
+    int64_t xstride;
+};
+cplx *runv(const HRun &R, int w) { return R.B.vec + (int64_t)w * R.B.len; } // vector w of system 0
+
+// the systems of T, each solving A x = b for its own HV_X
+HRun run_of(const ec3d_ctx *c, const HarmonicSystems &T)
 {
-    const Harmonic &H = c->harm;
+    const HBatch B = {sysv(c, T, 0, 0), T.part.get(), T.state.get(), c->A.n_pad};
+    return HRun{T.n, T.wgs, B, reinterpret_cast<const cplx *>(T.tab.get()), H_A, sysv(c, T, 0, HV_X), (int64_t)HV_N * B.len};
+}
+
+// x: system 0's, xstride pairs apart (the adjoint only: under H_A x is a work vector); o, y, r0, p: work vectors of system 0
+template <int MODE>
+void launch_spmv(ec3d_ctx *c, const HRun &R, const cplx *x, int64_t xstride, const cplx *o, cplx *y, cplx *r0, cplx *p)
+{
+    const dim3 grid((unsigned)R.G, (unsigned)R.S);
     const size_t lds = (size_t)c->A.ncls * 16 * sizeof(cplx);
-    if (op == H_A)
-        k_h_spmv<MODE><<<(unsigned)H.wgs, EC3D_THREADS, lds, c->stream>>>(view_of(c), H.state, x, o, y, r0, p,
-                                                                         c->A.n_pad / EC3D_TILE, H.part);
+    const int64_t nc = c->A.n_pad / EC3D_TILE, vs = (int64_t)HV_N * R.B.len;
+    if (R.op == H_A)
+        k_hb_spmv<MODE><<<grid, EC3D_THREADS, lds, c->stream>>>(view_of(c, R.tab), R.B.state, x, o, y, r0, p, nc, R.B.part, vs);
     else
-        k_h_spmv_h<MODE><<<(unsigned)H.wgs, EC3D_THREADS, lds, c->stream>>>(view_of(c), H.state, x, o, y, r0, p,
-                                                                           c->A.n_pad / EC3D_TILE, H.part);
+        k_hb_spmv_h<MODE><<<grid, EC3D_THREADS, lds, c->stream>>>(view_of(c, R.tab), R.B.state, x, o, y, r0, p, nc, R.B.part, vs,
+                                                                  xstride);
 }
 
-// c_i = <Q_i, R>; R = R - c_1 Q_1 - ... - c_k Q_k, R0 = R, P = R; the partials of ||R||^2 where k_h_spmv<3> left them
-// (HP_RR, one per workgroup of that launch), so k_h_setup reads them unchanged
-void launch_project(ec3d_ctx *c)
+// For every system s of T: c_{s,i} = <Q_{s,i}, R_s>; R_s = R_s - sum_i c_{s,i} Q_{s,i}, R0 = P = R; the partials of
+// ||R_s||^2 in system s's HP_RR slots (one per workgroup), where k_hb_spmv<3> left them and k_hb_setup reads them
+void launch_project(ec3d_ctx *c, const HarmonicSystems &T)
 {
-    const Harmonic &H = c->harm;
-    if (H.null_kept == 0) return;
-    const int64_t n = c->A.n, len = c->A.n_pad, nc = len / EC3D_TILE;
-    const cplx *q = reinterpret_cast<const cplx *>(H.nq.get());
-    cplx *coef = reinterpret_cast<cplx *>(H.ncoef.get());
-    k_hn_dots<<<dim3((unsigned)H.wgs, (unsigned)H.null_kept), EC3D_THREADS, 0, c->stream>>>(q, len, hv(c, HV_R), n, nc, H.npart);
-    k_hn_collapse<<<(unsigned)H.null_kept, EC3D_THREADS, 0, c->stream>>>(H.npart, H.wgs, coef);
-    k_hn_sub<<<(unsigned)H.wgs, EC3D_THREADS, 0, c->stream>>>(q, len, H.null_kept, coef, hv(c, HV_R), hv(c, HV_R0), hv(c, HV_P), n,
-                                                             nc, H.part.get() + (int64_t)HP_RR * H.wgs);
+    const HarmonicNull &N = T.null;
+    HNSys M{};
+    int kmax = 0;
+    for (int s = 0; s < T.n; ++s) {
+        M.set[s] = N.set_of[s];
+        M.kept[s] = N.kept[N.set_of[s]];
+        kmax = std::max(kmax, M.kept[s]);
+    }
+    if (kmax == 0) return;
+    const int64_t n = c->A.n, len = c->A.n_pad, nc = len / EC3D_TILE, vs = (int64_t)HV_N * len;
+    const unsigned G = (unsigned)T.wgs, S = (unsigned)T.n;
+    const int64_t pstride = (int64_t)2 * N.ncomp * T.wgs, cstride = N.ncomp, qset = (int64_t)N.ncomp * len;
+    const cplx *q = reinterpret_cast<const cplx *>(N.q.get());
+    cplx *coef = reinterpret_cast<cplx *>(N.coef.get());
+    k_hbn_dots<<<dim3(G, (unsigned)kmax, S), EC3D_THREADS, 0, c->stream>>>(M, q, qset, len, sysv(c, T, 0, HV_R), vs, n, nc, N.part,
+                                                                          pstride);
+    k_hbn_collapse<<<dim3((unsigned)kmax, S), EC3D_THREADS, 0, c->stream>>>(M, N.part, pstride, T.wgs, coef, cstride);
+    k_hbn_sub<<<dim3(G, S), EC3D_THREADS, 0, c->stream>>>(M, q, qset, len, coef, cstride, sysv(c, T, 0, HV_R), sysv(c, T, 0, HV_R0),
+                                                         sysv(c, T, 0, HV_P), vs, n, nc, T.part.get() + (int64_t)HP_RR * T.wgs,
+                                                         (int64_t)HP_NSLOT * T.wgs);
 }
 
-// R = b - op x, R0 = R, P = R and the state of a solve that has just begun; project: the left null vectors leave R first
-void launch_begin(ec3d_ctx *c, HOp op, const cplx *x, const cplx *b, double tol, bool project)
+// R = b - op x, R0 = R, P = R and the state of a solve that has just begun; b: a work vector of system 0; project (or
+// null): the systems whose left null vectors leave R first
+void launch_begin(ec3d_ctx *c, const HRun &R, const cplx *b, double tol, const HarmonicSystems *project)
 {
-    const Harmonic &H = c->harm;
-    launch_spmv<3>(c, op, x, b, hv(c, HV_R), hv(c, HV_R0), hv(c, HV_P));
-    if (project) launch_project(c);
-    k_h_setup<<<1, EC3D_THREADS, 0, c->stream>>>(H.state, H.part, H.wgs, tol);
+    launch_spmv<3>(c, R, R.x, R.xstride, b, runv(R, HV_R), runv(R, HV_R0), runv(R, HV_P));
+    if (project) launch_project(c, *project);
+    k_hb_setup<<<dim3(1, (unsigned)R.S), EC3D_THREADS, 0, c->stream>>>(R.B, R.G, tol);
 }
 
-void launch_iteration(ec3d_ctx *c, HOp op, cplx *x, int it)
+// one lock-step iteration: five launches, every system in each
+void launch_iteration(ec3d_ctx *c, const HRun &R, int it)
 {
-    const Harmonic &H = c->harm;
-    const int64_t n = c->A.n, nc = c->A.n_pad / EC3D_TILE;
-    const unsigned G = (unsigned)H.wgs;
+    const dim3 grid((unsigned)R.G, (unsigned)R.S);
+    const int64_t n = c->A.n, nc = c->A.n_pad / EC3D_TILE, vs = (int64_t)HV_N * R.B.len;
     hipStream_t s = c->stream;
-    launch_spmv<1>(c, op, hv(c, HV_P), hv(c, HV_R0), hv(c, HV_AP), nullptr, nullptr);
-    k_h_s<<<G, EC3D_THREADS, 0, s>>>(H.state, it, hv(c, HV_R), hv(c, HV_AP), hv(c, HV_S), n, nc, H.part);
-    launch_spmv<2>(c, op, hv(c, HV_S), nullptr, hv(c, HV_AS), nullptr, nullptr);
-    k_h_xr<<<G, EC3D_THREADS, 0, s>>>(H.state, it, hv(c, HV_P), hv(c, HV_S), hv(c, HV_AS), hv(c, HV_R0), x, hv(c, HV_R), n, nc,
-                                     H.part);
-    k_h_p<<<G, EC3D_THREADS, 0, s>>>(H.state, it, hv(c, HV_R), hv(c, HV_AP), hv(c, HV_P), hv(c, HV_R0), n, nc, H.part);
+    launch_spmv<1>(c, R, runv(R, HV_P), vs, runv(R, HV_R0), runv(R, HV_AP), nullptr, nullptr);
+    k_hb_s<<<grid, EC3D_THREADS, 0, s>>>(R.B, it, n, nc);
+    launch_spmv<2>(c, R, runv(R, HV_S), vs, nullptr, runv(R, HV_AS), nullptr, nullptr);
+    if (R.x == runv(R, HV_X))
+        k_hb_xr<<<grid, EC3D_THREADS, 0, s>>>(R.B, it, n, nc);
+    else
+        k_hb_xr_at<<<grid, EC3D_THREADS, 0, s>>>(R.B, it, R.x, R.xstride, n, nc);
+    k_hb_p<<<grid, EC3D_THREADS, 0, s>>>(R.B, it, n, nc);
 }
 
-// itmax + 1 iterations at most (src/solvers.f90:25-29) behind a launch_begin, 16 enqueued per poll; st: the state at the
-// last poll.  *stopped: an exit was taken
-int run_iterations(ec3d_ctx *c, HOp op, cplx *x, int64_t itmax, HarmonicState &st, bool *stopped)
+inline bool h_stopped(const HarmonicState &q) { return q.stop_s != INT_MAX || q.stop_r != INT_MAX; }
+
+// the S states in one copy
+int states_to_host(ec3d_ctx *c, const HRun &R, std::vector<HarmonicState> &st)
+{
+    st.resize((size_t)R.S);
+    EC3D_HIP(hipMemcpyAsync(st.data(), R.B.state, st.size() * sizeof(HarmonicState), hipMemcpyDeviceToHost, c->stream));
+    EC3D_HIP(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// itmax + 1 iterations at most (src/solvers.f90:25-29) behind a launch_begin, 16 enqueued per poll, on while any system
+// runs; st: the states at the last poll
+int run_iterations(ec3d_ctx *c, const HRun &R, int64_t itmax, std::vector<HarmonicState> &st)
 {
     const int64_t total = itmax + 1;
     int64_t launched = 0;
-    *stopped = false;
+    bool running;
     do {
         const int64_t m = std::min<int64_t>(16, total - launched);
-        for (int64_t i = 0; i < m; ++i) launch_iteration(c, op, x, (int)(++launched));
+        for (int64_t i = 0; i < m; ++i) launch_iteration(c, R, (int)(++launched));
         EC3D_HIP(hipGetLastError());
-        EC3D_HIP(hipMemcpyAsync(&st, c->harm.state, sizeof st, hipMemcpyDeviceToHost, c->stream));
-        EC3D_HIP(hipStreamSynchronize(c->stream));
-        *stopped = st.stop_s != INT_MAX || st.stop_r != INT_MAX;
-    } while (launched < total && !*stopped);
+        int rc = states_to_host(c, R, st);
+        if (rc) return rc;
+        running = false;
+        for (const HarmonicState &q : st) running = running || !h_stopped(q);
+    } while (launched < total && running);
     return 0;
 }
 
 // iter, restarts, stop_kind and relres of a solve from its last state; total = itmax + 1 iterations were allowed
-void h_report(ec3d_harmonic_info &o, const HarmonicState &st, bool stopped, int64_t total)
+void h_report(ec3d_harmonic_info &o, const HarmonicState &st, int64_t total)
 {
-    o.iter = stopped ? std::min(st.stop_s, st.stop_r) : (int32_t)std::max<int64_t>(total, 0);
+    o.iter = h_stopped(st) ? std::min(st.stop_s, st.stop_r) : (int32_t)std::max<int64_t>(total, 0);
     o.restarts = st.restarts;
     o.stop_kind = st.stop_s != INT_MAX ? 1 : (st.stop_r != INT_MAX && st.stop_r > 0 ? 2 : 0);
     const double last_norm = o.stop_kind == 1 ? st.snorm : st.rnorm;
@@ -870,7 +790,7 @@ int h_need(ec3d_ctx *c, const char *who, bool ready)
         ec3d_set_error(std::string(who) + ": needs the A-V system [Ax|Ay|Az|U] from ec3d_assemble");
         return 3;
     }
-    if (ready && !c->harm.ready) {
+    if (ready && c->harm.one.n == 0) {
         ec3d_set_error(std::string(who) + ": call ec3d_harmonic_setup first");
         return 2;
     }
@@ -878,15 +798,46 @@ int h_need(ec3d_ctx *c, const char *who, bool ready)
     return 0;
 }
 
-// the (re, omega m) pairs of one operator from the two tables of ec3d_assemble
-std::vector<double> h_table(const std::vector<double> &re, const std::vector<double> &m, double omega)
+// h_need and: a batch exists, sys is one of its systems (any_sys: not asked)
+int hb_need(ec3d_ctx *c, const char *who, int32_t sys, bool any_sys)
 {
-    std::vector<double> tab(2 * re.size());
-    for (size_t q = 0; q < re.size(); ++q) {
-        tab[2 * q] = re[q];
-        tab[2 * q + 1] = omega * m[q]; // one rounding per entry
+    int rc = h_need(c, who, false);
+    if (rc) return rc;
+    const int bn = c->harm.batch.n;
+    if (bn == 0) {
+        ec3d_set_error(std::string(who) + ": call ec3d_harmonic_batch_setup first");
+        return 2;
     }
-    return tab;
+    if (!any_sys && (sys < 0 || sys >= bn)) {
+        ec3d_set_error(std::string(who) + ": system " + std::to_string(sys) + " is outside the batch of " + std::to_string(bn));
+        return 2;
+    }
+    return 0;
+}
+
+// the entry points that exist for the single system and for system sys of the batch: what they refuse first, and *T
+int h_enter(ec3d_ctx *c, const char *who, bool batch, int32_t sys, HarmonicSystems **T)
+{
+    const int rc = batch ? hb_need(c, who, sys, false) : h_need(c, who, true);
+    if (rc) return rc;
+    *T = batch ? &c->harm.batch : &c->harm.one;
+    return 0;
+}
+
+// the (re, omega m) pairs of the operators omega[0 .. S - 1], one after another, from the two tables of ec3d_assemble
+int h_tables(ec3d_ctx *c, int S, const double *omega, std::vector<double> &tabs)
+{
+    const size_t nt = (size_t)c->A.ncls * 16;
+    std::vector<double> re(nt), m(nt);
+    EC3D_HIP(hipMemcpy(re.data(), c->harm.re, nt * sizeof(double), hipMemcpyDeviceToHost));
+    EC3D_HIP(hipMemcpy(m.data(), c->harm.m, nt * sizeof(double), hipMemcpyDeviceToHost));
+    tabs.resize((size_t)S * 2 * nt);
+    for (int s = 0; s < S; ++s)
+        for (size_t q = 0; q < nt; ++q) {
+            tabs[((size_t)s * nt + q) * 2] = re[q];
+            tabs[((size_t)s * nt + q) * 2 + 1] = omega[s] * m[q]; // one rounding per entry
+        }
+    return 0;
 }
 
 int h_which(int which, const char *who)
@@ -896,7 +847,7 @@ int h_which(int which, const char *who)
     return 2;
 }
 
-// stage: 2 * n_pad doubles of staging, the single solve's (H.stage) or the batch's (H.bstage)
+// stage: the 2 * n_pad doubles of staging of the systems that own dst
 int h_to_device(ec3d_ctx *c, double *stage, cplx *dst, const double *re, const double *im)
 {
     const int64_t len = c->A.n_pad;
@@ -925,338 +876,71 @@ int h_to_host(ec3d_ctx *c, double *stage, const cplx *src, double *re, double *i
     return 0;
 }
 
-// sum over the rows of <a, v>'s terms (a == v: ||v||^2 in the real part), read back: one k_hn_dots and one collapse
-int dot_to_host(ec3d_ctx *c, const cplx *a, const cplx *v, double *re)
+// ---- storage ---------------------------------------------------------------------------------------------------------
+// the vectors of a null projection and what was reported of them; the setting stays
+void null_free(HarmonicNull &N)
 {
-    Harmonic &H = c->harm;
-    cplx *coef = reinterpret_cast<cplx *>(H.ncoef.get());
-    k_hn_dots<<<dim3((unsigned)H.wgs, 1), EC3D_THREADS, 0, c->stream>>>(a, 0, v, c->A.n, c->A.n_pad / EC3D_TILE, H.npart);
-    k_hn_collapse<<<1, EC3D_THREADS, 0, c->stream>>>(H.npart, H.wgs, coef);
-    EC3D_HIP(hipGetLastError());
-    double h[2];
-    EC3D_HIP(hipMemcpyAsync(h, coef, sizeof h, hipMemcpyDeviceToHost, c->stream));
-    EC3D_HIP(hipStreamSynchronize(c->stream));
-    *re = h[0];
-    return 0;
+    HarmonicNull fresh;
+    fresh.on = N.on;
+    fresh.tol = N.tol;
+    N = std::move(fresh); // (a buffer that is moved onto is freed)
 }
 
-// The set-up of ec3d_harmonic_set_null_projection, once per matrix and omega.  Per connected conducting component
-// (ec3d_null_seeds): c = A^H (-e_m) into AS by one launch (-e_m in S); the adjoint solve A^H y = c from y = 0 -- this
-// file's iteration around k_h_spmv_h, y in the next free slot of Q, in the work vectors R, R0, P, AP, S, AS and the
-// state, which nothing reads between two solves; X^ and B^ are not touched -- then w = y + e_m, ||A^H w|| / ||w||, and
-// classical Gram-Schmidt against the vectors kept.
-int null_build(ec3d_ctx *c)
+// the systems and their null projection; its setting stays with the handle
+void systems_free(HarmonicSystems &T)
 {
-    Harmonic &H = c->harm;
-    const auto t_start = std::chrono::steady_clock::now();
-    ec3d_harmonic_null_free(c);
-    EC3D_HIP(hipStreamSynchronize(c->stream));
-    const int64_t n = c->A.n, len = c->A.n_pad, nc = len / EC3D_TILE;
-    std::vector<NullSeed> seeds;
-    int rc = ec3d_null_seeds(c, seeds);
-    if (rc) return rc;
-    const int ncomp = (int)seeds.size();
-    ec3d_null_info &L = H.null_last;
-    L.found = ncomp;
-    L.reported = std::min(ncomp, EC3D_NULL_MAX_REPORT);
-    if (ncomp == 0) { // no conductor: the operator has no such null vector, the projection is the identity
-        H.null_built = true;
-        return 0;
-    }
-    EC3D_HIP(H.nq.alloc((size_t)ncomp * 2 * len));
-    EC3D_HIP(hipMemsetAsync(H.nq, 0, (size_t)ncomp * 2 * len * sizeof(double), c->stream));
-    EC3D_HIP(H.npart.alloc((size_t)2 * ncomp * H.wgs));
-    EC3D_HIP(H.ncoef.alloc((size_t)2 * ncomp));
-    H.null_bytes = (int64_t)(((size_t)ncomp * 2 * len + (size_t)2 * ncomp * H.wgs + (size_t)2 * ncomp) * sizeof(double));
-    cplx *Q = reinterpret_cast<cplx *>(H.nq.get()), *coef = reinterpret_cast<cplx *>(H.ncoef.get());
-    const int64_t cap = (int64_t)(20.0 * std::cbrt((double)c->n_ref)) + 2000;
-    const unsigned G = (unsigned)H.wgs;
-    int kept = 0;
-    for (int ci = 0; ci < ncomp; ++ci) {
-        const int64_t row = seeds[(size_t)ci].row;
-        cplx *w = Q + (size_t)kept * len; // the next free slot: y, then w, then Q_kept
-        EC3D_HIP(hipMemsetAsync(hv(c, HV_S), 0, (size_t)n * sizeof(cplx), c->stream));
-        k_hn_add_re<<<1, 1, 0, c->stream>>>(hv(c, HV_S), row, -1.0);
-        launch_spmv<0>(c, H_AH, hv(c, HV_S), nullptr, hv(c, HV_AS), nullptr, nullptr);
-        launch_begin(c, H_AH, w, hv(c, HV_AS), H.null_tol, false);
-        EC3D_HIP(hipGetLastError());
-        HarmonicState st;
-        bool stopped = false;
-        if ((rc = run_iterations(c, H_AH, w, cap, st, &stopped))) return rc;
-        k_hn_add_re<<<1, 1, 0, c->stream>>>(w, row, 1.0);
-        // c - A^H y = -A^H w: ||A^H w|| is the adjoint system's TRUE residual, and the figure of the report
-        double aw2 = 0.0, w2 = 0.0;
-        launch_spmv<0>(c, H_AH, w, nullptr, hv(c, HV_AS), nullptr, nullptr);
-        if ((rc = dot_to_host(c, hv(c, HV_AS), hv(c, HV_AS), &aw2))) return rc;
-        if ((rc = dot_to_host(c, w, w, &w2))) return rc;
-        // A w that missed null_tol is never used.  Missed: no exit within the cap, or an exit of the recurrence that the
-        // true residual does not bear out.  The exits bound the recurrence's residual by null_tol ||c||; the true one
-        // differs from it by the rounding gathered along the solve, some 1e-14 ||c|| and far below any null_tol the
-        // arithmetic can deliver, so twice the bound tells a solve that delivered from a recurrence that ran away.
-        const double true_rel = std::sqrt(aw2) / st.bnorm;
-        if (!stopped || !(true_rel <= 2.0 * H.null_tol)) {
-            char msg[400];
-            snprintf(msg, sizeof msg, "harmonic null projection: the adjoint solve of conducting component %d (seed row %lld) did "
-                     "not reach null_tol = %.3g: %s after %lld iterations (cap %lld), true residual ||A^H w|| / ||A^H e_m|| = %.3g; "
-                     "its left null vector is not used", ci, (long long)seeds[(size_t)ci].seed_ref, H.null_tol,
-                     stopped ? "the recurrence took an exit" : "no exit",
-                     (long long)(stopped ? std::min(st.stop_s, st.stop_r) : cap + 1), (long long)cap, true_rel);
-            ec3d_harmonic_null_free(c);
-            ec3d_set_error(msg);
-            return EC3D_NULL_E_SETUP;
-        }
-        const double n0 = std::sqrt(w2), res = std::sqrt(aw2) / n0;
-        if (kept > 0) {
-            k_hn_dots<<<dim3(G, (unsigned)kept), EC3D_THREADS, 0, c->stream>>>(Q, len, w, n, nc, H.npart);
-            k_hn_collapse<<<(unsigned)kept, EC3D_THREADS, 0, c->stream>>>(H.npart, H.wgs, coef);
-            k_hn_sub<<<G, EC3D_THREADS, 0, c->stream>>>(Q, len, kept, coef, w, nullptr, nullptr, n, nc, nullptr);
-            if ((rc = dot_to_host(c, w, w, &w2))) return rc;
-        }
-        const double n1 = std::sqrt(w2);
-        const bool keep = std::isfinite(n0) && std::isfinite(n1) && n1 > EC3D_NULL_MIN_KEEP * n0;
-        if (keep) {
-            k_hn_div<<<G, EC3D_THREADS, 0, c->stream>>>(w, n1, n, nc);
-            ++kept;
-        } else {
-            EC3D_HIP(hipMemsetAsync(w, 0, (size_t)len * sizeof(cplx), c->stream)); // the slot is free again
-        }
-        if (ci < EC3D_NULL_MAX_REPORT) {
-            L.seed_row[ci] = seeds[(size_t)ci].seed_ref;
-            L.iterations[ci] = std::min(st.stop_s, st.stop_r);
-            L.was_kept[ci] = keep ? 1 : 0;
-            L.residual[ci] = res;
-            H.null_restarts[ci] = st.restarts;
-        }
-    }
-    EC3D_HIP(hipGetLastError());
-    EC3D_HIP(hipStreamSynchronize(c->stream));
-    H.null_kept = kept;
-    H.null_built = true;
-    L.kept = kept;
-    L.dropped = ncomp - kept;
-    L.setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
-    return 0;
+    null_free(T.null);
+    HarmonicSystems fresh;
+    fresh.null = std::move(T.null);
+    T = std::move(fresh);
 }
 
-// removed = sqrt(sum |c_i|^2) / ||b^|| of the projection that has just run: one copy of the coefficients
-int null_note(ec3d_ctx *c, double bnorm)
+// everything of S systems but the tables' contents: vectors, partials, staging and states, all zero
+int systems_alloc(ec3d_ctx *c, HarmonicSystems &T, int S)
 {
-    Harmonic &H = c->harm;
-    H.null_last.removed = 0.0;
-    if (H.null_kept == 0 || bnorm == 0.0) return 0;
-    std::vector<double> h((size_t)2 * H.null_kept);
-    EC3D_HIP(hipMemcpy(h.data(), H.ncoef, h.size() * sizeof(double), hipMemcpyDeviceToHost));
-    double s = 0.0;
-    for (size_t i = 0; i < h.size(); i += 2) s += h[i] * h[i] + h[i + 1] * h[i + 1];
-    H.null_last.removed = std::sqrt(s) / bnorm;
-    return 0;
-}
-
-// ---- the batch ---------------------------------------------------------------------------------
-HBatch batch_of(const ec3d_ctx *c)
-{
-    const Harmonic &H = c->harm;
-    HBatch B;
-    B.vec = reinterpret_cast<cplx *>(H.bvec.get());
-    B.part = H.bpart.get();
-    B.state = H.bstate.get();
-    B.len = c->A.n_pad;
-    return B;
-}
-
-// the matrix with system 0's table of the batch
-HSav batch_view_of(const ec3d_ctx *c)
-{
-    HSav T = view_of(c);
-    T.table = reinterpret_cast<const cplx *>(c->harm.btab.get());
-    return T;
-}
-
-cplx *hbv(const ec3d_ctx *c, int sys, int w)
-{
-    return reinterpret_cast<cplx *>(c->harm.bvec.get()) + ((size_t)sys * HV_N + (size_t)w) * (size_t)c->A.n_pad;
-}
-
-// the vectors of ec3d_harmonic_batch_set_null_projection and what was reported of them; the setting stays
-void batch_null_free(ec3d_ctx *c)
-{
-    Harmonic &H = c->harm;
-    H.bnq.reset();
-    H.bny.reset();
-    H.bntab.reset();
-    H.bnpart.reset();
-    H.bncoef.reset();
-    H.bnull_built = false;
-    H.bnsets = 0;
-    H.bncomp = 0;
-    H.bnull_bytes = 0;
-    H.bnull_setup_ms = 0.0;
-    for (int s = 0; s < EC3D_HARMONIC_MAX_BATCH; ++s) {
-        H.bnset_of[s] = H.bnfirst[s] = H.bnkept[s] = 0;
-        H.bnremoved[s] = 0.0;
-        H.bnull_last[s] = ec3d_null_info{};
-        for (auto &r : H.bnull_restarts[s]) r = 0;
-    }
-}
-
-void batch_free(ec3d_ctx *c)
-{
-    Harmonic &H = c->harm;
-    batch_null_free(c);
-    H.bvec.reset();
-    H.btab.reset();
-    H.bpart.reset();
-    H.bstage.reset();
-    H.bstate.reset();
-    H.bn = 0;
-    H.bwgs = 0;
-    H.bbytes = 0;
-    for (auto &o : H.bomega) o = 0.0;
-    for (auto &l : H.blast) l = ec3d_harmonic_info{};
-}
-
-// everything of a batch of S systems; the caller frees the batch when this fails
-int batch_alloc(ec3d_ctx *c, int S, const std::vector<double> &tabs)
-{
-    Harmonic &H = c->harm;
     const size_t nt = (size_t)c->A.ncls * 16, len = (size_t)c->A.n_pad;
     const int G = ec3d_stream_wgs((int64_t)len);
-    EC3D_HIP(H.bvec.alloc((size_t)S * HV_N * 2 * len));
-    EC3D_HIP(H.btab.alloc((size_t)S * 2 * nt));
-    EC3D_HIP(H.bpart.alloc((size_t)S * HP_NSLOT * G));
-    EC3D_HIP(H.bstage.alloc(2 * len));
-    EC3D_HIP(H.bstate.alloc((size_t)S));
-    EC3D_HIP(hipMemsetAsync(H.bvec, 0, (size_t)S * HV_N * 2 * len * sizeof(double), c->stream));
-    EC3D_HIP(hipMemsetAsync(H.bpart, 0, (size_t)S * HP_NSLOT * G * sizeof(double), c->stream));
-    EC3D_HIP(hipMemsetAsync(H.bstage, 0, 2 * len * sizeof(double), c->stream));
-    EC3D_HIP(hipMemsetAsync(H.bstate, 0, (size_t)S * sizeof(HarmonicState), c->stream));
-    EC3D_HIP(hipMemcpy(H.btab, tabs.data(), (size_t)S * 2 * nt * sizeof(double), hipMemcpyHostToDevice));
+    EC3D_HIP(T.vec.alloc((size_t)S * HV_N * 2 * len));
+    EC3D_HIP(T.tab.alloc((size_t)S * 2 * nt));
+    EC3D_HIP(T.part.alloc((size_t)S * HP_NSLOT * G));
+    EC3D_HIP(T.stage.alloc(2 * len));
+    EC3D_HIP(T.state.alloc((size_t)S));
+    EC3D_HIP(hipMemsetAsync(T.vec, 0, (size_t)S * HV_N * 2 * len * sizeof(double), c->stream));
+    EC3D_HIP(hipMemsetAsync(T.part, 0, (size_t)S * HP_NSLOT * G * sizeof(double), c->stream));
+    EC3D_HIP(hipMemsetAsync(T.stage, 0, 2 * len * sizeof(double), c->stream));
+    EC3D_HIP(hipMemsetAsync(T.state, 0, (size_t)S * sizeof(HarmonicState), c->stream));
     EC3D_HIP(hipStreamSynchronize(c->stream));
-    H.bwgs = G;
-    H.bbytes = (int64_t)(((size_t)S * HV_N * 2 * len + (size_t)S * 2 * nt + (size_t)S * HP_NSLOT * G + 2 * len) * sizeof(double) +
-                         (size_t)S * sizeof(HarmonicState));
+    T.wgs = G;
+    T.bytes = (int64_t)(((size_t)S * HV_N * 2 * len + (size_t)S * 2 * nt + (size_t)S * HP_NSLOT * G + 2 * len) * sizeof(double) +
+                        (size_t)S * sizeof(HarmonicState));
     return 0;
 }
 
-// h_need and: a batch exists, sys is one of its systems (sys < 0: not asked)
-int hb_need(ec3d_ctx *c, const char *who, int32_t sys, bool any_sys)
-{
-    int rc = h_need(c, who, false);
-    if (rc) return rc;
-    const Harmonic &H = c->harm;
-    if (H.bn == 0) {
-        ec3d_set_error(std::string(who) + ": call ec3d_harmonic_batch_setup first");
-        return 2;
-    }
-    if (!any_sys && (sys < 0 || sys >= H.bn)) {
-        ec3d_set_error(std::string(who) + ": system " + std::to_string(sys) + " is outside the batch of " + std::to_string(H.bn));
-        return 2;
-    }
-    return 0;
-}
-
-// launch_project for every system of the batch: c_{s,i} = <Q_{s,i}, R_s>; R_s = R_s - sum_i c_{s,i} Q_{s,i}, R0 = P = R; the
-// partials of ||R_s||^2 in system s's HP_RR slots, where k_hb_spmv<3> left them and k_hb_setup reads them
-void batch_launch_project(ec3d_ctx *c)
-{
-    const Harmonic &H = c->harm;
-    HNSys M{};
-    int kmax = 0;
-    for (int s = 0; s < H.bn; ++s) {
-        M.set[s] = H.bnset_of[s];
-        M.kept[s] = H.bnkept[H.bnset_of[s]];
-        kmax = std::max(kmax, M.kept[s]);
-    }
-    if (kmax == 0) return;
-    const int64_t n = c->A.n, len = c->A.n_pad, nc = len / EC3D_TILE, vs = (int64_t)HV_N * len;
-    const unsigned G = (unsigned)H.bwgs, S = (unsigned)H.bn;
-    const int64_t pstride = (int64_t)2 * H.bncomp * H.bwgs, cstride = H.bncomp;
-    const cplx *q = reinterpret_cast<const cplx *>(H.bnq.get());
-    cplx *coef = reinterpret_cast<cplx *>(H.bncoef.get());
-    k_hbn_dots<<<dim3(G, (unsigned)kmax, S), EC3D_THREADS, 0, c->stream>>>(M, q, (int64_t)H.bncomp * len, len, hbv(c, 0, HV_R), vs, n,
-                                                                          nc, H.bnpart, pstride);
-    k_hbn_collapse<<<dim3((unsigned)kmax, S), EC3D_THREADS, 0, c->stream>>>(M, H.bnpart, pstride, H.bwgs, coef, cstride);
-    k_hbn_sub<<<dim3(G, S), EC3D_THREADS, 0, c->stream>>>(M, q, (int64_t)H.bncomp * len, len, coef, cstride, hbv(c, 0, HV_R),
-                                                         hbv(c, 0, HV_R0), hbv(c, 0, HV_P), vs, n, nc,
-                                                         H.bpart.get() + (int64_t)HP_RR * H.bwgs, (int64_t)HP_NSLOT * H.bwgs);
-}
-
-// project: every system's left null vectors leave its R first
-void batch_launch_begin(ec3d_ctx *c, double tol, bool project)
-{
-    const Harmonic &H = c->harm;
-    const dim3 grid((unsigned)H.bwgs, (unsigned)H.bn);
-    const size_t lds = (size_t)c->A.ncls * 16 * sizeof(cplx);
-    const HBatch B = batch_of(c);
-    k_hb_spmv<3><<<grid, EC3D_THREADS, lds, c->stream>>>(batch_view_of(c), B.state, hbv(c, 0, HV_X), hbv(c, 0, HV_B), hbv(c, 0, HV_R),
-                                                         hbv(c, 0, HV_R0), hbv(c, 0, HV_P), c->A.n_pad / EC3D_TILE, B.part,
-                                                         (int64_t)HV_N * B.len);
-    if (project) batch_launch_project(c);
-    k_hb_setup<<<dim3(1, (unsigned)H.bn), EC3D_THREADS, 0, c->stream>>>(B, H.bwgs, tol);
-}
-
-// one lock-step iteration: the five launches of launch_iteration, every system in each
-void batch_launch_iteration(ec3d_ctx *c, int it)
-{
-    const Harmonic &H = c->harm;
-    const dim3 grid((unsigned)H.bwgs, (unsigned)H.bn);
-    const size_t lds = (size_t)c->A.ncls * 16 * sizeof(cplx);
-    const int64_t n = c->A.n, nc = c->A.n_pad / EC3D_TILE;
-    const HBatch B = batch_of(c);
-    const HSav A = batch_view_of(c);
-    const int64_t vs = (int64_t)HV_N * B.len;
-    hipStream_t s = c->stream;
-    k_hb_spmv<1><<<grid, EC3D_THREADS, lds, s>>>(A, B.state, hbv(c, 0, HV_P), hbv(c, 0, HV_R0), hbv(c, 0, HV_AP), nullptr, nullptr, nc,
-                                                 B.part, vs);
-    k_hb_s<<<grid, EC3D_THREADS, 0, s>>>(B, it, n, nc);
-    k_hb_spmv<2><<<grid, EC3D_THREADS, lds, s>>>(A, B.state, hbv(c, 0, HV_S), nullptr, hbv(c, 0, HV_AS), nullptr, nullptr, nc, B.part, vs);
-    k_hb_xr<<<grid, EC3D_THREADS, 0, s>>>(B, it, n, nc);
-    k_hb_p<<<grid, EC3D_THREADS, 0, s>>>(B, it, n, nc);
-}
-
-// run_iterations for a batch: 16 lock-step iterations per poll, all the states in one copy, on while any system runs
-int batch_run_iterations(ec3d_ctx *c, int64_t itmax, std::vector<HarmonicState> &st)
-{
-    const Harmonic &H = c->harm;
-    const int64_t total = itmax + 1;
-    int64_t launched = 0;
-    bool running;
-    st.resize((size_t)H.bn);
-    do {
-        const int64_t m = std::min<int64_t>(16, total - launched);
-        for (int64_t i = 0; i < m; ++i) batch_launch_iteration(c, (int)(++launched));
-        EC3D_HIP(hipGetLastError());
-        EC3D_HIP(hipMemcpyAsync(st.data(), H.bstate, st.size() * sizeof(HarmonicState), hipMemcpyDeviceToHost, c->stream));
-        EC3D_HIP(hipStreamSynchronize(c->stream));
-        running = false;
-        for (const HarmonicState &q : st) running = running || (q.stop_s == INT_MAX && q.stop_r == INT_MAX);
-    } while (launched < total && running);
-    return 0;
-}
-
-// ---- left null vectors inside a batch ----------------------------------------------------------
+// ---- left null vectors (DESIGN sections 18a, 18c) --------------------------------------------------------------------
 // the lowest system whose omega has the bits of system s's
-int batch_shares_with(const Harmonic &H, int s)
+int shares_with(const HarmonicSystems &T, int s)
 {
     for (int t = 0; t < s; ++t)
-        if (std::memcmp(&H.bomega[t], &H.bomega[s], sizeof(double)) == 0) return t;
+        if (std::memcmp(&T.omega[t], &T.omega[s], sizeof(double)) == 0) return t;
     return s;
 }
 
-// out[d] = the real part of sum <a_d, v_d> over the rows, d < D: a_d = a + d * astride, v_d = v + d * vstride
-int batch_dots_to_host(ec3d_ctx *c, int D, const cplx *a, int64_t astride, const cplx *v, int64_t vstride, double *out)
+// out[d] = the real part of sum <a_d, v_d> over the rows (a == v: ||v_d||^2), d < D: a_d = a + d * astride,
+// v_d = v + d * vstride; one k_hbn_dots, one collapse and one copy, in the partials and coefficients of the projection
+int dots_to_host(ec3d_ctx *c, const HarmonicSystems &T, int D, const cplx *a, int64_t astride, const cplx *v, int64_t vstride,
+                 double *out)
 {
-    Harmonic &H = c->harm;
+    const HarmonicNull &N = T.null;
     HNSys M{};
     for (int d = 0; d < D; ++d) {
         M.set[d] = d;
         M.kept[d] = 1;
     }
-    const int64_t pstride = (int64_t)2 * H.bncomp * H.bwgs, cstride = H.bncomp;
-    cplx *coef = reinterpret_cast<cplx *>(H.bncoef.get());
-    k_hbn_dots<<<dim3((unsigned)H.bwgs, 1, (unsigned)D), EC3D_THREADS, 0, c->stream>>>(M, a, astride, 0, v, vstride, c->A.n,
-                                                                                     c->A.n_pad / EC3D_TILE, H.bnpart, pstride);
-    k_hbn_collapse<<<dim3(1, (unsigned)D), EC3D_THREADS, 0, c->stream>>>(M, H.bnpart, pstride, H.bwgs, coef, cstride);
+    const int64_t pstride = (int64_t)2 * N.ncomp * T.wgs, cstride = N.ncomp;
+    cplx *coef = reinterpret_cast<cplx *>(N.coef.get());
+    k_hbn_dots<<<dim3((unsigned)T.wgs, 1, (unsigned)D), EC3D_THREADS, 0, c->stream>>>(M, a, astride, 0, v, vstride, c->A.n,
+                                                                                    c->A.n_pad / EC3D_TILE, N.part, pstride);
+    k_hbn_collapse<<<dim3(1, (unsigned)D), EC3D_THREADS, 0, c->stream>>>(M, N.part, pstride, T.wgs, coef, cstride);
     EC3D_HIP(hipGetLastError());
     std::vector<double> h((size_t)2 * cstride * D);
     EC3D_HIP(hipMemcpyAsync(h.data(), coef, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -1265,124 +949,125 @@ int batch_dots_to_host(ec3d_ctx *c, int D, const cplx *a, int64_t astride, const
     return 0;
 }
 
-// null_build for the batch: per conducting component the adjoint solves of the D distinct omegas in lock step -- set d
-// in the work vectors R, R0, P, AP, S, AS, the partials and the state of system d, its unknown in bny + d * n_pad; X^
-// and B^ of no system are touched -- then every step of null_build per set, the decisions on the host from one copy of
-// D figures.  A kept vector is copied from the staging vector into its slot of Q: a copy keeps the bits.
-int batch_null_build(ec3d_ctx *c)
+// A w that missed null_tol is never used.  Missed: no exit within the cap, or an exit of the recurrence that the true
+// residual ||A^H w|| / ||c|| does not bear out.  The exits bound the recurrence's residual by null_tol ||c||; the true
+// one differs from it by the rounding gathered along the solve, some 1e-14 ||c|| and far below any null_tol the
+// arithmetic can deliver, so twice the bound tells a solve that delivered from a recurrence that ran away.
+bool null_solve_missed(const HarmonicState &q, double true_rel, double null_tol)
 {
-    Harmonic &H = c->harm;
+    return !h_stopped(q) || !(true_rel <= 2.0 * null_tol);
+}
+
+// the error of a set-up whose adjoint solve of set d, component ci missed; the batch's names the system and its omega
+std::string null_missed_text(const HarmonicSystems &T, bool batch, int d, int ci, const NullSeed &seed, const HarmonicState &q,
+                             int64_t cap, double true_rel)
+{
+    char who[120] = "harmonic null projection: the adjoint solve of";
+    if (batch)
+        snprintf(who, sizeof who, "harmonic batch null projection: the adjoint solve of system %d (omega = %.17g),",
+                 T.null.first[d], T.omega[T.null.first[d]]);
+    const bool stopped = h_stopped(q);
+    char msg[480];
+    snprintf(msg, sizeof msg, "%s conducting component %d (seed row %lld) did not reach null_tol = %.3g: %s after %lld iterations "
+             "(cap %lld), true residual ||A^H w|| / ||A^H e_m|| = %.3g; %s", who, ci, (long long)seed.seed_ref, T.null.tol,
+             stopped ? "the recurrence took an exit" : "no exit", (long long)(stopped ? std::min(q.stop_s, q.stop_r) : cap + 1),
+             (long long)cap, true_rel, batch ? "no left null vector of the batch is used" : "its left null vector is not used");
+    return msg;
+}
+
+// w of norm n0 left Gram-Schmidt against the vectors kept with norm n1: kept unless (nearly) nothing of it is new
+bool null_keeps(double n0, double n1) { return std::isfinite(n0) && std::isfinite(n1) && n1 > EC3D_NULL_MIN_KEEP * n0; }
+
+// The set-up of a null projection, once per matrix and set of omegas.  Per connected conducting component
+// (ec3d_null_seeds), for the D distinct omegas of T in lock step: c = A^H (-e_m) into AS by one launch (-e_m in S); the
+// adjoint solve A^H y = c from y = 0 -- this file's iteration around k_hb_spmv_h, set d in the work vectors R, R0, P, AP,
+// S, AS, the partials and the state of system d, which nothing reads between two solves; X^ and B^ of no system are
+// touched -- then w = y + e_m, ||A^H w|| / ||w||, and classical Gram-Schmidt against the vectors kept, the decisions on
+// the host from one copy of D figures.  The unknown: the single system solves in the next free slot of its Q, where a
+// kept vector stays; the sets of a batch keep different numbers of vectors, so set d solves in the staging vector
+// y + d * n_pad under the table of its omega, and a kept vector is copied into its slot: a copy keeps the bits.
+int null_build(ec3d_ctx *c, HarmonicSystems &T)
+{
+    HarmonicNull &N = T.null;
+    const bool staged = is_batch(c, T);
     const auto t_start = std::chrono::steady_clock::now();
-    batch_null_free(c);
+    null_free(N);
     EC3D_HIP(hipStreamSynchronize(c->stream));
     const int64_t n = c->A.n, len = c->A.n_pad, nc = len / EC3D_TILE, vs = (int64_t)HV_N * len;
     int D = 0;
-    for (int s = 0; s < H.bn; ++s) {
-        const int f = batch_shares_with(H, s);
+    for (int s = 0; s < T.n; ++s) {
+        const int f = shares_with(T, s);
         if (f == s) {
-            H.bnfirst[D] = s;
-            H.bnset_of[s] = D++;
+            N.first[D] = s;
+            N.set_of[s] = D++;
         } else {
-            H.bnset_of[s] = H.bnset_of[f];
+            N.set_of[s] = N.set_of[f];
         }
     }
-    H.bnsets = D;
+    N.sets = D;
     std::vector<NullSeed> seeds;
     int rc = ec3d_null_seeds(c, seeds);
     if (rc) return rc;
     const int ncomp = (int)seeds.size();
     for (int d = 0; d < D; ++d) {
-        H.bnull_last[d].found = ncomp;
-        H.bnull_last[d].reported = std::min(ncomp, EC3D_NULL_MAX_REPORT);
+        N.last[d].found = ncomp;
+        N.last[d].reported = std::min(ncomp, EC3D_NULL_MAX_REPORT);
     }
-    if (ncomp == 0) { // no conductor: the projection is the identity
-        H.bnull_built = true;
+    if (ncomp == 0) { // no conductor: the operator has no such null vector, the projection is the identity
+        N.built = true;
         return 0;
     }
-    const size_t nt = (size_t)c->A.ncls * 16;
-    const int G = H.bwgs;
-    EC3D_HIP(H.bnq.alloc((size_t)D * ncomp * 2 * len));
-    EC3D_HIP(H.bny.alloc((size_t)D * 2 * len));
-    EC3D_HIP(H.bntab.alloc((size_t)D * 2 * nt));
-    EC3D_HIP(H.bnpart.alloc((size_t)H.bn * 2 * ncomp * G));
-    EC3D_HIP(H.bncoef.alloc((size_t)H.bn * 2 * ncomp));
-    EC3D_HIP(hipMemsetAsync(H.bnq, 0, (size_t)D * ncomp * 2 * len * sizeof(double), c->stream));
-    EC3D_HIP(hipMemsetAsync(H.bnpart, 0, (size_t)H.bn * 2 * ncomp * G * sizeof(double), c->stream));
-    EC3D_HIP(hipMemsetAsync(H.bncoef, 0, (size_t)H.bn * 2 * ncomp * sizeof(double), c->stream));
-    {
-        std::vector<double> re(nt), m(nt), tabs;
-        EC3D_HIP(hipMemcpy(re.data(), H.re, nt * sizeof(double), hipMemcpyDeviceToHost));
-        EC3D_HIP(hipMemcpy(m.data(), H.m, nt * sizeof(double), hipMemcpyDeviceToHost));
-        for (int d = 0; d < D; ++d) {
-            const std::vector<double> t = h_table(re, m, H.bomega[H.bnfirst[d]]);
-            tabs.insert(tabs.end(), t.begin(), t.end());
-        }
-        EC3D_HIP(hipMemcpy(H.bntab, tabs.data(), tabs.size() * sizeof(double), hipMemcpyHostToDevice));
+    const size_t nt = (size_t)c->A.ncls * 16, nq = (size_t)D * ncomp * 2 * len;
+    const size_t npart = (size_t)T.n * 2 * ncomp * T.wgs, ncoef = (size_t)T.n * 2 * ncomp;
+    EC3D_HIP(N.q.alloc(nq));
+    EC3D_HIP(hipMemsetAsync(N.q, 0, nq * sizeof(double), c->stream));
+    EC3D_HIP(N.part.alloc(npart));
+    EC3D_HIP(N.coef.alloc(ncoef));
+    N.bytes = (int64_t)((nq + npart + ncoef) * sizeof(double));
+    if (staged) {
+        EC3D_HIP(N.y.alloc((size_t)D * 2 * len));
+        EC3D_HIP(N.tab.alloc((size_t)D * 2 * nt));
+        N.bytes += (int64_t)(((size_t)D * 2 * len + (size_t)D * 2 * nt) * sizeof(double));
+        EC3D_HIP(hipMemsetAsync(N.part, 0, npart * sizeof(double), c->stream));
+        EC3D_HIP(hipMemsetAsync(N.coef, 0, ncoef * sizeof(double), c->stream));
+        std::vector<double> omega((size_t)D), tabs;
+        for (int d = 0; d < D; ++d) omega[(size_t)d] = T.omega[N.first[d]];
+        if ((rc = h_tables(c, D, omega.data(), tabs))) return rc;
+        EC3D_HIP(hipMemcpy(N.tab, tabs.data(), tabs.size() * sizeof(double), hipMemcpyHostToDevice));
     }
-    H.bncomp = ncomp;
-    const int64_t nbytes = (int64_t)(((size_t)D * ncomp * 2 * len + (size_t)D * 2 * len + (size_t)D * 2 * nt +
-                                      (size_t)H.bn * 2 * ncomp * G + (size_t)H.bn * 2 * ncomp) * sizeof(double));
-    cplx *Q = reinterpret_cast<cplx *>(H.bnq.get()), *Y = reinterpret_cast<cplx *>(H.bny.get());
-    cplx *coef = reinterpret_cast<cplx *>(H.bncoef.get());
-    const int64_t cap = (int64_t)(20.0 * std::cbrt((double)c->n_ref)) + 2000, total = cap + 1;
-    const int64_t pstride = (int64_t)2 * ncomp * G, cstride = ncomp, qset = (int64_t)ncomp * len;
-    const dim3 grid((unsigned)G, (unsigned)D);
-    const size_t lds = nt * sizeof(cplx);
-    const HBatch B = batch_of(c);
-    HSav A = view_of(c);
-    A.table = reinterpret_cast<const cplx *>(H.bntab.get());
+    N.ncomp = ncomp;
+    cplx *Q = reinterpret_cast<cplx *>(N.q.get()), *coef = reinterpret_cast<cplx *>(N.coef.get());
+    const int64_t cap = (int64_t)(20.0 * std::cbrt((double)c->n_ref)) + 2000;
+    const int64_t pstride = (int64_t)2 * ncomp * T.wgs, cstride = ncomp, qset = (int64_t)ncomp * len;
+    const dim3 grid((unsigned)T.wgs, (unsigned)D);
+    HRun R = run_of(c, T);
+    R.S = D;
+    R.op = H_AH;
+    if (staged) R.tab = reinterpret_cast<const cplx *>(N.tab.get());
     hipStream_t s = c->stream;
-    std::vector<HarmonicState> st((size_t)D);
+    std::vector<HarmonicState> st;
     std::vector<double> aw2((size_t)D), w2((size_t)D), w2b((size_t)D);
     for (int ci = 0; ci < ncomp; ++ci) {
         const int64_t row = seeds[(size_t)ci].row;
-        for (int d = 0; d < D; ++d) EC3D_HIP(hipMemsetAsync(hbv(c, d, HV_S), 0, (size_t)n * sizeof(cplx), s));
-        k_hbn_add_re<<<(unsigned)D, 1, 0, s>>>(hbv(c, 0, HV_S), vs, row, -1.0);
-        k_hb_spmv_h<0><<<grid, EC3D_THREADS, lds, s>>>(A, B.state, hbv(c, 0, HV_S), nullptr, hbv(c, 0, HV_AS), nullptr, nullptr, nc,
-                                                       B.part, vs, vs);
-        EC3D_HIP(hipMemsetAsync(Y, 0, (size_t)D * len * sizeof(cplx), s));
-        k_hb_spmv_h<3><<<grid, EC3D_THREADS, lds, s>>>(A, B.state, Y, hbv(c, 0, HV_AS), hbv(c, 0, HV_R), hbv(c, 0, HV_R0),
-                                                       hbv(c, 0, HV_P), nc, B.part, vs, len);
-        k_hb_setup<<<dim3(1, (unsigned)D), EC3D_THREADS, 0, s>>>(B, G, H.bnull_tol);
+        R.x = staged ? reinterpret_cast<cplx *>(N.y.get()) : Q + (size_t)N.kept[0] * len; // y, then w, then (divided) Q_kept
+        R.xstride = staged ? len : qset;
+        for (int d = 0; d < D; ++d) EC3D_HIP(hipMemsetAsync(sysv(c, T, d, HV_S), 0, (size_t)n * sizeof(cplx), s));
+        k_hbn_add_re<<<(unsigned)D, 1, 0, s>>>(runv(R, HV_S), vs, row, -1.0);
+        launch_spmv<0>(c, R, runv(R, HV_S), vs, nullptr, runv(R, HV_AS), nullptr, nullptr);
+        if (staged) EC3D_HIP(hipMemsetAsync(R.x, 0, (size_t)D * len * sizeof(cplx), s)); // (a free slot of Q is zero)
+        launch_begin(c, R, runv(R, HV_AS), N.tol, nullptr);
         EC3D_HIP(hipGetLastError());
-        int64_t launched = 0;
-        bool running;
-        do { // run_iterations, D adjoint solves in each launch
-            const int64_t m = std::min<int64_t>(16, total - launched);
-            for (int64_t i = 0; i < m; ++i) {
-                const int it = (int)(++launched);
-                k_hb_spmv_h<1><<<grid, EC3D_THREADS, lds, s>>>(A, B.state, hbv(c, 0, HV_P), hbv(c, 0, HV_R0), hbv(c, 0, HV_AP), nullptr,
-                                                               nullptr, nc, B.part, vs, vs);
-                k_hb_s<<<grid, EC3D_THREADS, 0, s>>>(B, it, n, nc);
-                k_hb_spmv_h<2><<<grid, EC3D_THREADS, lds, s>>>(A, B.state, hbv(c, 0, HV_S), nullptr, hbv(c, 0, HV_AS), nullptr, nullptr,
-                                                               nc, B.part, vs, vs);
-                k_hb_xr_at<<<grid, EC3D_THREADS, 0, s>>>(B, it, Y, len, n, nc);
-                k_hb_p<<<grid, EC3D_THREADS, 0, s>>>(B, it, n, nc);
-            }
-            EC3D_HIP(hipGetLastError());
-            EC3D_HIP(hipMemcpyAsync(st.data(), H.bstate, st.size() * sizeof(HarmonicState), hipMemcpyDeviceToHost, s));
-            EC3D_HIP(hipStreamSynchronize(s));
-            running = false;
-            for (const HarmonicState &q : st) running = running || (q.stop_s == INT_MAX && q.stop_r == INT_MAX);
-        } while (launched < total && running);
-        k_hbn_add_re<<<(unsigned)D, 1, 0, s>>>(Y, len, row, 1.0);
-        // ||A^H w||, the adjoint system's true residual, and ||w||, per set
-        k_hb_spmv_h<0><<<grid, EC3D_THREADS, lds, s>>>(A, B.state, Y, nullptr, hbv(c, 0, HV_AS), nullptr, nullptr, nc, B.part, vs, len);
-        if ((rc = batch_dots_to_host(c, D, hbv(c, 0, HV_AS), vs, hbv(c, 0, HV_AS), vs, aw2.data()))) return rc;
-        if ((rc = batch_dots_to_host(c, D, Y, len, Y, len, w2.data()))) return rc;
-        for (int d = 0; d < D; ++d) { // the rule of null_build, per set
-            const HarmonicState &q = st[(size_t)d];
-            const bool stopped = q.stop_s != INT_MAX || q.stop_r != INT_MAX;
-            const double true_rel = std::sqrt(aw2[(size_t)d]) / q.bnorm;
-            if (stopped && true_rel <= 2.0 * H.bnull_tol) continue;
-            char msg[480];
-            snprintf(msg, sizeof msg, "harmonic batch null projection: the adjoint solve of system %d (omega = %.17g), conducting "
-                     "component %d (seed row %lld) did not reach null_tol = %.3g: %s after %lld iterations (cap %lld), true residual "
-                     "||A^H w|| / ||A^H e_m|| = %.3g; no left null vector of the batch is used", H.bnfirst[d],
-                     H.bomega[H.bnfirst[d]], ci, (long long)seeds[(size_t)ci].seed_ref, H.bnull_tol,
-                     stopped ? "the recurrence took an exit" : "no exit",
-                     (long long)(stopped ? std::min(q.stop_s, q.stop_r) : cap + 1), (long long)cap, true_rel);
-            batch_null_free(c);
+        if ((rc = run_iterations(c, R, cap, st))) return rc;
+        k_hbn_add_re<<<(unsigned)D, 1, 0, s>>>(R.x, R.xstride, row, 1.0);
+        // c - A^H y = -A^H w: ||A^H w|| is the adjoint system's TRUE residual, and the figure of the report
+        launch_spmv<0>(c, R, R.x, R.xstride, nullptr, runv(R, HV_AS), nullptr, nullptr);
+        if ((rc = dots_to_host(c, T, D, runv(R, HV_AS), vs, runv(R, HV_AS), vs, aw2.data()))) return rc;
+        if ((rc = dots_to_host(c, T, D, R.x, R.xstride, R.x, R.xstride, w2.data()))) return rc;
+        for (int d = 0; d < D; ++d) {
+            const double true_rel = std::sqrt(aw2[(size_t)d]) / st[(size_t)d].bnorm;
+            if (!null_solve_missed(st[(size_t)d], true_rel, N.tol)) continue;
+            const std::string msg = null_missed_text(T, staged, d, ci, seeds[(size_t)ci], st[(size_t)d], cap, true_rel);
+            null_free(N);
             ec3d_set_error(msg);
             return EC3D_NULL_E_SETUP;
         }
@@ -1390,110 +1075,241 @@ int batch_null_build(ec3d_ctx *c)
         int kmax = 0;
         for (int d = 0; d < D; ++d) {
             K.set[d] = d;
-            K.kept[d] = H.bnkept[d];
+            K.kept[d] = N.kept[d];
             kmax = std::max(kmax, K.kept[d]);
         }
         w2b = w2;
         if (kmax > 0) {
-            k_hbn_dots<<<dim3((unsigned)G, (unsigned)kmax, (unsigned)D), EC3D_THREADS, 0, s>>>(K, Q, qset, len, Y, len, n, nc, H.bnpart,
-                                                                                             pstride);
-            k_hbn_collapse<<<dim3((unsigned)kmax, (unsigned)D), EC3D_THREADS, 0, s>>>(K, H.bnpart, pstride, G, coef, cstride);
-            k_hbn_sub<<<grid, EC3D_THREADS, 0, s>>>(K, Q, qset, len, coef, cstride, Y, nullptr, nullptr, len, n, nc, nullptr, 0);
+            k_hbn_dots<<<dim3(grid.x, (unsigned)kmax, grid.y), EC3D_THREADS, 0, s>>>(K, Q, qset, len, R.x, R.xstride, n, nc, N.part,
+                                                                                   pstride);
+            k_hbn_collapse<<<dim3((unsigned)kmax, grid.y), EC3D_THREADS, 0, s>>>(K, N.part, pstride, T.wgs, coef, cstride);
+            k_hbn_sub<<<grid, EC3D_THREADS, 0, s>>>(K, Q, qset, len, coef, cstride, R.x, nullptr, nullptr, R.xstride, n, nc, nullptr, 0);
             std::vector<double> after((size_t)D);
-            if ((rc = batch_dots_to_host(c, D, Y, len, Y, len, after.data()))) return rc;
+            if ((rc = dots_to_host(c, T, D, R.x, R.xstride, R.x, R.xstride, after.data()))) return rc;
             for (int d = 0; d < D; ++d)
                 if (K.kept[d] > 0) w2b[(size_t)d] = after[(size_t)d];
         }
         HNDiv dv{};
-        bool keep[EC3D_HARMONIC_MAX_BATCH] = {false};
+        bool keep[EC3D_HARMONIC_MAX_BATCH] = {false}, any = false;
         for (int d = 0; d < D; ++d) {
-            const double n0 = std::sqrt(w2[(size_t)d]), n1 = std::sqrt(w2b[(size_t)d]);
-            keep[d] = std::isfinite(n0) && std::isfinite(n1) && n1 > EC3D_NULL_MIN_KEEP * n0;
+            const double n1 = std::sqrt(w2b[(size_t)d]);
+            keep[d] = null_keeps(std::sqrt(w2[(size_t)d]), n1);
             dv.d[d] = keep[d] ? n1 : 0.0;
+            any = any || keep[d];
         }
-        k_hbn_div<<<grid, EC3D_THREADS, 0, s>>>(dv, Y, len, n, nc);
+        if (any) k_hbn_div<<<grid, EC3D_THREADS, 0, s>>>(dv, R.x, R.xstride, n, nc);
         for (int d = 0; d < D; ++d) {
-            if (keep[d]) {
-                EC3D_HIP(hipMemcpyAsync(Q + (size_t)d * qset + (size_t)H.bnkept[d] * len, Y + (size_t)d * len, (size_t)len * sizeof(cplx),
+            cplx *w = R.x + (size_t)d * R.xstride;
+            if (keep[d] && staged)
+                EC3D_HIP(hipMemcpyAsync(Q + (size_t)d * qset + (size_t)N.kept[d] * len, w, (size_t)len * sizeof(cplx),
                                         hipMemcpyDeviceToDevice, s));
-                ++H.bnkept[d];
-            }
+            if (!keep[d] && !staged) EC3D_HIP(hipMemsetAsync(w, 0, (size_t)len * sizeof(cplx), s)); // the slot is free again
+            if (keep[d]) ++N.kept[d];
             if (ci < EC3D_NULL_MAX_REPORT) {
-                ec3d_null_info &L = H.bnull_last[d];
+                ec3d_null_info &L = N.last[d];
                 const HarmonicState &q = st[(size_t)d];
                 L.seed_row[ci] = seeds[(size_t)ci].seed_ref;
                 L.iterations[ci] = std::min(q.stop_s, q.stop_r);
                 L.was_kept[ci] = keep[d] ? 1 : 0;
                 L.residual[ci] = std::sqrt(aw2[(size_t)d]) / std::sqrt(w2[(size_t)d]);
-                H.bnull_restarts[d][ci] = q.restarts;
+                N.restarts[d][ci] = q.restarts;
             }
         }
     }
     EC3D_HIP(hipGetLastError());
     EC3D_HIP(hipStreamSynchronize(s));
-    H.bnull_built = true;
-    H.bnull_bytes = nbytes;
-    H.bnull_setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    N.built = true;
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
     for (int d = 0; d < D; ++d) {
-        H.bnull_last[d].kept = H.bnkept[d];
-        H.bnull_last[d].dropped = ncomp - H.bnkept[d];
-        H.bnull_last[d].setup_ms = H.bnull_setup_ms;
+        N.last[d].kept = N.kept[d];
+        N.last[d].dropped = ncomp - N.kept[d];
+        N.last[d].setup_ms = ms;
     }
     return 0;
 }
 
-// null_note per system: removed_s = sqrt(sum_i |c_{s,i}|^2) / ||b^_s|| of the projection that has just run
-int batch_null_note(ec3d_ctx *c, const std::vector<HarmonicState> &st)
+// removed_s = sqrt(sum_i |c_{s,i}|^2) / ||b^_s|| of the projection that has just run, per system: one copy of the
+// coefficients
+int null_note(ec3d_ctx *c, HarmonicSystems &T, const std::vector<HarmonicState> &st)
 {
-    Harmonic &H = c->harm;
-    for (int s = 0; s < H.bn; ++s) H.bnremoved[s] = 0.0;
-    if (H.bncomp == 0) return 0;
-    std::vector<double> h((size_t)H.bn * 2 * H.bncomp);
-    EC3D_HIP(hipMemcpy(h.data(), H.bncoef, h.size() * sizeof(double), hipMemcpyDeviceToHost));
-    for (int s = 0; s < H.bn; ++s) {
-        const int kept = H.bnkept[H.bnset_of[s]];
+    HarmonicNull &N = T.null;
+    bool any = false;
+    for (int s = 0; s < T.n; ++s) {
+        N.removed[s] = 0.0;
+        any = any || (N.kept[N.set_of[s]] > 0 && st[(size_t)s].bnorm != 0.0);
+    }
+    if (!any) return 0;
+    std::vector<double> h((size_t)T.n * 2 * N.ncomp);
+    EC3D_HIP(hipMemcpy(h.data(), N.coef, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int s = 0; s < T.n; ++s) {
+        const int kept = N.kept[N.set_of[s]];
         const double bnorm = st[(size_t)s].bnorm;
         if (kept == 0 || bnorm == 0.0) continue;
-        const double *q = h.data() + (size_t)s * 2 * H.bncomp;
+        const double *q = h.data() + (size_t)s * 2 * N.ncomp;
         double sum = 0.0;
         for (int i = 0; i < 2 * kept; i += 2) sum += q[i] * q[i] + q[i + 1] * q[i + 1];
-        H.bnremoved[s] = std::sqrt(sum) / bnorm;
+        N.removed[s] = std::sqrt(sum) / bnorm;
     }
     return 0;
+}
+
+// ---- what the entry points of the single system and of the batch share ----------------------------------------------
+// the solve of every system of T; the report in T.last
+int h_solve(ec3d_ctx *c, HarmonicSystems &T, double tol, int32_t itmax)
+{
+    HarmonicNull &N = T.null;
+    int rc;
+    if (N.on && !N.built && (rc = null_build(c, T))) return rc;
+    const auto t_start = std::chrono::steady_clock::now();
+    const HRun R = run_of(c, T);
+    launch_begin(c, R, runv(R, HV_B), tol, N.on ? &T : nullptr);
+    EC3D_HIP(hipGetLastError());
+    std::vector<HarmonicState> st;
+    if ((rc = run_iterations(c, R, itmax, st))) return rc;
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    for (int s = 0; s < T.n; ++s) {
+        h_report(T.last[s], st[(size_t)s], (int64_t)itmax + 1); // src/solvers.f90:25-29: itmax + 1 iterations
+        T.last[s].ms = ms;
+    }
+    if (N.on) return null_note(c, T, st);
+    return 0;
+}
+
+// b^ - A x^ of every system as a solve would begin with it, the left null vectors taken out if `project`: the states
+int h_residual(ec3d_ctx *c, HarmonicSystems &T, bool project, std::vector<HarmonicState> &st)
+{
+    int rc;
+    if (project && !T.null.built && (rc = null_build(c, T))) return rc;
+    const HRun R = run_of(c, T);
+    launch_begin(c, R, runv(R, HV_B), 0.0, project ? &T : nullptr);
+    EC3D_HIP(hipGetLastError());
+    if ((rc = states_to_host(c, R, st))) return rc;
+    return project ? null_note(c, T, st) : 0;
+}
+
+int h_upload(ec3d_ctx *c, const char *who, bool batch, int32_t sys, int which, const double *re, const double *im)
+{
+    HarmonicSystems *T;
+    int rc = h_enter(c, who, batch, sys, &T);
+    if (rc) return rc;
+    if ((rc = h_which(which, who))) return rc;
+    if (!re) {
+        ec3d_set_error(std::string(who) + ": re is NULL");
+        return 2;
+    }
+    if ((rc = h_to_device(c, T->stage, sysv(c, *T, sys, which == EC3D_VEC_X ? HV_X : HV_B), re, im))) return rc;
+    EC3D_HIP(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int h_download(ec3d_ctx *c, const char *who, bool batch, int32_t sys, int which, double *re, double *im)
+{
+    HarmonicSystems *T;
+    int rc = h_enter(c, who, batch, sys, &T);
+    if (rc) return rc;
+    if ((rc = h_which(which, who))) return rc;
+    if (!re || !im) {
+        ec3d_set_error(std::string(who) + ": re or im is NULL");
+        return 2;
+    }
+    return h_to_host(c, T->stage, sysv(c, *T, sys, which == EC3D_VEC_X ? HV_X : HV_B), re, im);
+}
+
+int h_device_vector(ec3d_ctx *c, const char *who, bool batch, int32_t sys, int which, double **device_ptr, int64_t *pairs)
+{
+    HarmonicSystems *T;
+    const int rc = h_enter(c, who, batch, sys, &T);
+    if (rc) return rc;
+    if (which < 0 || which >= HV_N || !device_ptr || !pairs) {
+        ec3d_set_error(std::string(who) + ": unknown vector or NULL argument");
+        return 2;
+    }
+    *device_ptr = reinterpret_cast<double *>(sysv(c, *T, sys, which));
+    *pairs = c->A.n_pad;
+    return 0;
+}
+
+// on: a tolerance other than the vectors' own has them made again
+int h_null_switch_on(ec3d_ctx *c, HarmonicNull &N, double null_tol)
+{
+    const double tol = null_tol > 0.0 ? null_tol : 1e-10;
+    if (tol != N.tol && N.built) {
+        EC3D_HIP(hipStreamSynchronize(c->stream));
+        null_free(N); // another accuracy: the vectors are made again
+    }
+    N.on = 1;
+    N.tol = tol;
+    return 0;
+}
+
+void h_null_info(const HarmonicNull &N, int sys, ec3d_null_info *info)
+{
+    *info = N.built ? N.last[N.set_of[sys]] : ec3d_null_info{};
+    info->on = N.on;
+    info->null_tol = N.tol;
+    info->built = N.built ? 1 : 0;
+    info->removed = N.removed[sys];
+}
+
+int h_left_null_vector(ec3d_ctx *c, const char *who, bool batch, int32_t sys, int32_t index, double *re, double *im)
+{
+    HarmonicSystems *T;
+    int rc = h_enter(c, who, batch, sys, &T);
+    if (rc) return rc;
+    HarmonicNull &N = T->null;
+    if (!N.built) {
+        if (!N.on) {
+            ec3d_set_error(std::string(who) + ": no vectors yet and the projection is off (" +
+                           (batch ? "ec3d_harmonic_batch_set_null_projection" : "ec3d_harmonic_set_null_projection") + ")");
+            return 2;
+        }
+        if ((rc = null_build(c, *T))) return rc;
+    }
+    const int d = N.set_of[sys], kept = N.kept[d];
+    if (index < 0 || index >= kept || !re || !im) {
+        ec3d_set_error(std::string(who) + ": index " + std::to_string(index) + " is outside the " + std::to_string(kept) +
+                       " vectors kept" + (batch ? " for system " + std::to_string(sys) : std::string()) + ", or a NULL argument");
+        return 2;
+    }
+    return h_to_host(c, T->stage, reinterpret_cast<const cplx *>(N.q.get()) + ((size_t)d * N.ncomp + (size_t)index) * c->A.n_pad, re,
+                     im);
+}
+
+void h_null_restarts(const HarmonicNull &N, int sys, int32_t *restarts)
+{
+    for (int i = 0; i < EC3D_NULL_MAX_REPORT; ++i) restarts[i] = N.built ? N.restarts[N.set_of[sys]][i] : 0;
+}
+
+// y = op x: x^ of the handle, or the caller's (through P); y through AP
+int h_spmv_entry(ec3d_ctx *c, const char *who, HOp op, const double *xre, const double *xim, double *yre, double *yim)
+{
+    int rc = h_need(c, who, true);
+    if (rc) return rc;
+    if (!yre || !yim || (xre && !xim)) {
+        ec3d_set_error(std::string(who) + ": NULL argument");
+        return 2;
+    }
+    HRun R = run_of(c, c->harm.one);
+    R.op = op;
+    const cplx *x = hv(c, HV_X);
+    if (xre) {
+        if ((rc = h_to_device(c, c->harm.one.stage, hv(c, HV_P), xre, xim))) return rc;
+        x = hv(c, HV_P);
+    }
+    launch_spmv<0>(c, R, x, R.xstride, nullptr, hv(c, HV_AP), nullptr, nullptr);
+    EC3D_HIP(hipGetLastError());
+    return h_to_host(c, c->harm.one.stage, hv(c, HV_AP), yre, yim);
 }
 
 } // namespace
 
-void ec3d_harmonic_null_free(ec3d_ctx *c)
-{
-    Harmonic &H = c->harm;
-    H.nq.reset();
-    H.npart.reset();
-    H.ncoef.reset();
-    H.null_built = false;
-    H.null_kept = 0;
-    H.null_bytes = 0;
-    H.null_last = ec3d_null_info{};
-    for (auto &r : H.null_restarts) r = 0;
-}
-
 void ec3d_harmonic_free(ec3d_ctx *c)
 {
     Harmonic &H = c->harm;
-    ec3d_harmonic_null_free(c); // (the setting stays with the handle)
-    batch_free(c);
+    systems_free(H.one);
+    systems_free(H.batch);
     H.re.reset();
     H.m.reset();
-    H.tab.reset();
-    H.vec_own.reset();
-    for (auto &v : H.vec) v = nullptr;
-    H.stage.reset();
-    H.part.reset();
-    H.state.reset();
-    H.ready = false;
-    H.omega = 0.0;
-    H.wgs = 0;
-    H.last = ec3d_harmonic_info{};
 }
 
 extern "C" int ec3d_harmonic_setup(ec3d_handle c, double omega)
@@ -1504,101 +1320,45 @@ extern "C" int ec3d_harmonic_setup(ec3d_handle c, double omega)
         ec3d_set_error("ec3d_harmonic_setup: omega must be finite and not negative");
         return 2;
     }
-    Harmonic &H = c->harm;
+    HarmonicSystems &T = c->harm.one;
     EC3D_HIP(hipStreamSynchronize(c->stream));
-    if (!(H.ready && omega == H.omega)) ec3d_harmonic_null_free(c); // Q belongs to the matrix and to omega
-    const size_t nt = (size_t)c->A.ncls * 16, len = (size_t)c->A.n_pad;
-    std::vector<double> re(nt), m(nt);
-    EC3D_HIP(hipMemcpy(re.data(), H.re, nt * sizeof(double), hipMemcpyDeviceToHost));
-    EC3D_HIP(hipMemcpy(m.data(), H.m, nt * sizeof(double), hipMemcpyDeviceToHost));
-    const std::vector<double> tab = h_table(re, m, omega);
-    if (!H.tab) EC3D_HIP(H.tab.alloc(2 * nt));
-    EC3D_HIP(hipMemcpy(H.tab, tab.data(), 2 * nt * sizeof(double), hipMemcpyHostToDevice));
-    if (!H.vec_own) { // the first set-up on this matrix: vectors (zero), staging, partials, state
-        H.wgs = ec3d_stream_wgs((int64_t)len);
-        EC3D_HIP(H.vec_own.alloc((size_t)HV_N * 2 * len));
-        EC3D_HIP(hipMemsetAsync(H.vec_own, 0, (size_t)HV_N * 2 * len * sizeof(double), c->stream));
-        for (int w = 0; w < HV_N; ++w) H.vec[w] = H.vec_own.get() + (size_t)w * 2 * len;
-        EC3D_HIP(H.stage.alloc(2 * len));
-        EC3D_HIP(hipMemsetAsync(H.stage, 0, 2 * len * sizeof(double), c->stream));
-        EC3D_HIP(H.part.alloc((size_t)HP_NSLOT * H.wgs));
-        EC3D_HIP(hipMemsetAsync(H.part, 0, (size_t)HP_NSLOT * H.wgs * sizeof(double), c->stream));
-        EC3D_HIP(H.state.alloc(1));
-        EC3D_HIP(hipMemsetAsync(H.state, 0, sizeof(HarmonicState), c->stream));
-        EC3D_HIP(hipStreamSynchronize(c->stream));
-    }
-    H.omega = omega;
-    H.ready = true;
-    H.last = ec3d_harmonic_info{};
-    H.last.ready = 1;
-    H.last.omega = omega;
-    H.last.device_bytes = (int64_t)(((size_t)HV_N * 2 * len + 2 * len + (size_t)HP_NSLOT * H.wgs + 2 * nt) * sizeof(double) +
-                                    sizeof(HarmonicState));
+    if (!(T.n && omega == T.omega[0])) null_free(T.null); // Q belongs to the matrix and to omega
+    std::vector<double> tab;
+    if ((rc = h_tables(c, 1, &omega, tab))) return rc;
+    if (!T.vec && (rc = systems_alloc(c, T, 1))) return rc; // the first set-up on this matrix; the vectors stay across omegas
+    EC3D_HIP(hipMemcpy(T.tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
+    T.n = 1;
+    T.omega[0] = omega;
+    T.last[0] = ec3d_harmonic_info{};
+    T.last[0].ready = 1;
+    T.last[0].omega = omega;
+    T.last[0].device_bytes = T.bytes;
     return 0;
 }
 
 extern "C" int ec3d_harmonic_upload(ec3d_handle c, int which, const double *re, const double *im)
 {
-    int rc = h_need(c, "ec3d_harmonic_upload", true);
-    if (rc) return rc;
-    if ((rc = h_which(which, "ec3d_harmonic_upload"))) return rc;
-    if (!re) {
-        ec3d_set_error("ec3d_harmonic_upload: re is NULL");
-        return 2;
-    }
-    if ((rc = h_to_device(c, c->harm.stage, hv(c, which == EC3D_VEC_X ? HV_X : HV_B), re, im))) return rc;
-    EC3D_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    return h_upload(c, "ec3d_harmonic_upload", false, 0, which, re, im);
 }
 
 extern "C" int ec3d_harmonic_download(ec3d_handle c, int which, double *re, double *im)
 {
-    int rc = h_need(c, "ec3d_harmonic_download", true);
-    if (rc) return rc;
-    if ((rc = h_which(which, "ec3d_harmonic_download"))) return rc;
-    if (!re || !im) {
-        ec3d_set_error("ec3d_harmonic_download: re or im is NULL");
-        return 2;
-    }
-    return h_to_host(c, c->harm.stage, hv(c, which == EC3D_VEC_X ? HV_X : HV_B), re, im);
+    return h_download(c, "ec3d_harmonic_download", false, 0, which, re, im);
 }
 
 extern "C" int ec3d_harmonic_spmv(ec3d_handle c, const double *xre, const double *xim, double *yre, double *yim)
 {
-    int rc = h_need(c, "ec3d_harmonic_spmv", true);
-    if (rc) return rc;
-    if (!yre || !yim || (xre && !xim)) {
-        ec3d_set_error("ec3d_harmonic_spmv: NULL argument");
-        return 2;
-    }
-    const cplx *x = hv(c, HV_X);
-    if (xre) {
-        if ((rc = h_to_device(c, c->harm.stage, hv(c, HV_P), xre, xim))) return rc;
-        x = hv(c, HV_P);
-    }
-    launch_spmv<0>(c, H_A, x, nullptr, hv(c, HV_AP), nullptr, nullptr);
-    EC3D_HIP(hipGetLastError());
-    return h_to_host(c, c->harm.stage, hv(c, HV_AP), yre, yim);
+    return h_spmv_entry(c, "ec3d_harmonic_spmv", H_A, xre, xim, yre, yim);
 }
 
 extern "C" int ec3d_harmonic_solve(ec3d_handle c, double tol, int32_t itmax, int32_t *iter, double *relres)
 {
     int rc = h_need(c, "ec3d_harmonic_solve", true);
     if (rc) return rc;
-    Harmonic &H = c->harm;
-    if (H.null_on && !H.null_built && (rc = null_build(c))) return rc;
-    const auto t_start = std::chrono::steady_clock::now();
-    launch_begin(c, H_A, hv(c, HV_X), hv(c, HV_B), tol, H.null_on != 0);
-    EC3D_HIP(hipGetLastError());
-    HarmonicState st;
-    const int64_t total = (int64_t)itmax + 1; // src/solvers.f90:25-29: itmax + 1 iterations
-    bool stopped = false;
-    if ((rc = run_iterations(c, H_A, hv(c, HV_X), itmax, st, &stopped))) return rc;
-    h_report(H.last, st, stopped, total);
-    H.last.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
-    if (iter) *iter = H.last.iter;
-    if (relres) *relres = H.last.relres;
-    if (H.null_on) return null_note(c, st.bnorm);
+    HarmonicSystems &T = c->harm.one;
+    if ((rc = h_solve(c, T, tol, itmax))) return rc;
+    if (iter) *iter = T.last[0].iter;
+    if (relres) *relres = T.last[0].relres;
     return 0;
 }
 
@@ -1610,13 +1370,10 @@ extern "C" int ec3d_harmonic_true_residual(ec3d_handle c, double *rel, double *b
         ec3d_set_error("ec3d_harmonic_true_residual: rel is NULL");
         return 2;
     }
-    launch_begin(c, H_A, hv(c, HV_X), hv(c, HV_B), 0.0, false);
-    EC3D_HIP(hipGetLastError());
-    HarmonicState st;
-    EC3D_HIP(hipMemcpyAsync(&st, c->harm.state, sizeof st, hipMemcpyDeviceToHost, c->stream));
-    EC3D_HIP(hipStreamSynchronize(c->stream));
-    if (bnorm) *bnorm = st.bnorm;
-    *rel = st.bnorm > 0.0 ? st.rnorm / st.bnorm : st.rnorm;
+    std::vector<HarmonicState> st;
+    if ((rc = h_residual(c, c->harm.one, false, st))) return rc;
+    if (bnorm) *bnorm = st[0].bnorm;
+    *rel = st[0].bnorm > 0.0 ? st[0].rnorm / st[0].bnorm : st[0].rnorm;
     return 0;
 }
 
@@ -1628,12 +1385,11 @@ extern "C" int ec3d_harmonic_load(ec3d_handle c, int32_t part)
         ec3d_set_error("ec3d_harmonic_load: part must be 0 (Re) or 1 (Im)");
         return 2;
     }
-    const Harmonic &H = c->harm;
     double *x = c->vec[EC3D_VEC_X], *b = c->vec[EC3D_VEC_B];
     hipStream_t s = c->stream;
     k_h_load<<<blocks(c->A.n), 256, 0, s>>>(hv(c, HV_X), hv(c, HV_B), part, x, b, c->A.n);
     if (c->n_cond) {
-        k_h_load_eddy<<<blocks(c->n_cond), 256, 0, s>>>(hv(c, HV_X), c->A.cls, reinterpret_cast<const cplx *>(H.tab.get()),
+        k_h_load_eddy<<<blocks(c->n_cond), 256, 0, s>>>(hv(c, HV_X), c->A.cls, reinterpret_cast<const cplx *>(c->harm.one.tab.get()),
                                                        c->cond_cell, c->n_cond, c->nCd, part, b);
         const int64_t cnt = c->bnd_off[3];
         if (cnt) k_h_zero_list<<<blocks(cnt), 256, 0, s>>>(c->bnd_list, cnt, x, b);
@@ -1649,24 +1405,17 @@ extern "C" int ec3d_get_harmonic(ec3d_handle c, ec3d_harmonic_info *out)
         ec3d_set_error("ec3d_get_harmonic: null handle or info");
         return 2;
     }
-    *out = c->harm.last;
-    out->ready = c->harm.ready ? 1 : 0;
-    out->omega = c->harm.omega;
-    out->device_bytes += c->harm.null_bytes; // Q, its partials and coefficients, while they exist
+    const HarmonicSystems &T = c->harm.one;
+    *out = T.last[0];
+    out->ready = T.n ? 1 : 0;
+    out->omega = T.omega[0];
+    out->device_bytes += T.null.bytes; // Q, its partials and coefficients, while they exist
     return 0;
 }
 
 extern "C" int ec3d_harmonic_device_vector(ec3d_handle c, int which, double **device_ptr, int64_t *pairs)
 {
-    int rc = h_need(c, "ec3d_harmonic_device_vector", true);
-    if (rc) return rc;
-    if (which < 0 || which >= HV_N || !device_ptr || !pairs) {
-        ec3d_set_error("ec3d_harmonic_device_vector: unknown vector or NULL argument");
-        return 2;
-    }
-    *device_ptr = c->harm.vec[which];
-    *pairs = c->A.n_pad;
-    return 0;
+    return h_device_vector(c, "ec3d_harmonic_device_vector", false, 0, which, device_ptr, pairs);
 }
 
 // ---- left null vectors of K + j omega M -------------------------------------------------------
@@ -1677,20 +1426,12 @@ extern "C" int ec3d_harmonic_set_null_projection(ec3d_handle c, int32_t on, doub
         return 2;
     }
     if (!on) {
-        c->harm.null_on = 0; // Q stays with the matrix and omega: switching on again costs nothing
+        c->harm.one.null.on = 0; // Q stays with the matrix and omega: switching on again costs nothing
         return 0;
     }
-    int rc = h_need(c, "ec3d_harmonic_set_null_projection", true);
+    const int rc = h_need(c, "ec3d_harmonic_set_null_projection", true);
     if (rc) return rc; // (the setting as it was)
-    Harmonic &H = c->harm;
-    const double tol = null_tol > 0.0 ? null_tol : 1e-10;
-    if (tol != H.null_tol && H.null_built) {
-        EC3D_HIP(hipStreamSynchronize(c->stream));
-        ec3d_harmonic_null_free(c); // another accuracy: the vectors are made again
-    }
-    H.null_on = 1;
-    H.null_tol = tol;
-    return 0;
+    return h_null_switch_on(c, c->harm.one.null, null_tol);
 }
 
 extern "C" int ec3d_get_harmonic_null(ec3d_handle c, ec3d_null_info *info)
@@ -1699,71 +1440,34 @@ extern "C" int ec3d_get_harmonic_null(ec3d_handle c, ec3d_null_info *info)
         ec3d_set_error("ec3d_get_harmonic_null: null handle or info");
         return 2;
     }
-    *info = c->harm.null_last;
-    info->on = c->harm.null_on;
-    info->null_tol = c->harm.null_tol;
-    info->built = c->harm.null_built ? 1 : 0;
+    h_null_info(c->harm.one.null, 0, info);
     return 0;
 }
 
 extern "C" int ec3d_harmonic_left_null_vector(ec3d_handle c, int32_t index, double *re, double *im)
 {
-    int rc = h_need(c, "ec3d_harmonic_left_null_vector", true);
-    if (rc) return rc;
-    Harmonic &H = c->harm;
-    if (!H.null_built) {
-        if (!H.null_on) {
-            ec3d_set_error("ec3d_harmonic_left_null_vector: no vectors yet and the projection is off "
-                           "(ec3d_harmonic_set_null_projection)");
-            return 2;
-        }
-        if ((rc = null_build(c))) return rc;
-    }
-    if (index < 0 || index >= H.null_kept || !re || !im) {
-        ec3d_set_error("ec3d_harmonic_left_null_vector: index " + std::to_string(index) + " is outside the " +
-                       std::to_string(H.null_kept) + " vectors kept, or a NULL argument");
-        return 2;
-    }
-    return h_to_host(c, H.stage, reinterpret_cast<const cplx *>(H.nq.get()) + (size_t)index * c->A.n_pad, re, im);
+    return h_left_null_vector(c, "ec3d_harmonic_left_null_vector", false, 0, index, re, im);
 }
 
 extern "C" int ec3d_harmonic_spmv_h(ec3d_handle c, const double *xre, const double *xim, double *yre, double *yim)
 {
-    int rc = h_need(c, "ec3d_harmonic_spmv_h", true);
-    if (rc) return rc;
-    if (!yre || !yim || (xre && !xim)) {
-        ec3d_set_error("ec3d_harmonic_spmv_h: NULL argument");
-        return 2;
-    }
-    const cplx *x = hv(c, HV_X);
-    if (xre) {
-        if ((rc = h_to_device(c, c->harm.stage, hv(c, HV_P), xre, xim))) return rc;
-        x = hv(c, HV_P);
-    }
-    launch_spmv<0>(c, H_AH, x, nullptr, hv(c, HV_AP), nullptr, nullptr);
-    EC3D_HIP(hipGetLastError());
-    return h_to_host(c, c->harm.stage, hv(c, HV_AP), yre, yim);
+    return h_spmv_entry(c, "ec3d_harmonic_spmv_h", H_AH, xre, xim, yre, yim);
 }
 
 extern "C" int ec3d_harmonic_projected_residual(ec3d_handle c, double *rel, double *removed)
 {
     int rc = h_need(c, "ec3d_harmonic_projected_residual", true);
     if (rc) return rc;
-    Harmonic &H = c->harm;
-    if (!H.null_on || !rel) {
+    HarmonicSystems &T = c->harm.one;
+    if (!T.null.on || !rel) {
         ec3d_set_error(!rel ? "ec3d_harmonic_projected_residual: rel is NULL"
                             : "ec3d_harmonic_projected_residual: the projection is off (ec3d_harmonic_set_null_projection)");
         return 2;
     }
-    if (!H.null_built && (rc = null_build(c))) return rc;
-    launch_begin(c, H_A, hv(c, HV_X), hv(c, HV_B), 0.0, true);
-    EC3D_HIP(hipGetLastError());
-    HarmonicState st;
-    EC3D_HIP(hipMemcpyAsync(&st, H.state, sizeof st, hipMemcpyDeviceToHost, c->stream));
-    EC3D_HIP(hipStreamSynchronize(c->stream));
-    *rel = st.bnorm > 0.0 ? st.rnorm / st.bnorm : st.rnorm;
-    if ((rc = null_note(c, st.bnorm))) return rc;
-    if (removed) *removed = H.null_last.removed;
+    std::vector<HarmonicState> st;
+    if ((rc = h_residual(c, T, true, st))) return rc;
+    *rel = st[0].bnorm > 0.0 ? st[0].rnorm / st[0].bnorm : st[0].rnorm;
+    if (removed) *removed = T.null.removed[0];
     return 0;
 }
 
@@ -1773,7 +1477,7 @@ extern "C" int ec3d_harmonic_null_restarts(ec3d_handle c, int32_t *restarts)
         ec3d_set_error("ec3d_harmonic_null_restarts: null handle or array");
         return 2;
     }
-    for (int i = 0; i < EC3D_NULL_MAX_REPORT; ++i) restarts[i] = c->harm.null_restarts[i];
+    h_null_restarts(c->harm.one.null, 0, restarts);
     return 0;
 }
 
@@ -1786,10 +1490,10 @@ extern "C" int ec3d_harmonic_batch_setup(ec3d_handle c, int32_t nsys, const doub
         ec3d_set_error("ec3d_harmonic_batch_setup: nsys must be in [0, " + std::to_string(EC3D_HARMONIC_MAX_BATCH) + "]");
         return 2;
     }
-    Harmonic &H = c->harm;
+    HarmonicSystems &T = c->harm.batch;
     if (nsys == 0) {
         EC3D_HIP(hipStreamSynchronize(c->stream));
-        batch_free(c);
+        systems_free(T);
         return 0;
     }
     if (!omega) {
@@ -1802,80 +1506,46 @@ extern "C" int ec3d_harmonic_batch_setup(ec3d_handle c, int32_t nsys, const doub
             return 2;
         }
     EC3D_HIP(hipStreamSynchronize(c->stream));
-    const size_t nt = (size_t)c->A.ncls * 16;
-    std::vector<double> re(nt), m(nt), tabs;
-    EC3D_HIP(hipMemcpy(re.data(), H.re, nt * sizeof(double), hipMemcpyDeviceToHost));
-    EC3D_HIP(hipMemcpy(m.data(), H.m, nt * sizeof(double), hipMemcpyDeviceToHost));
-    tabs.reserve((size_t)nsys * 2 * nt);
-    for (int32_t s = 0; s < nsys; ++s) {
-        const std::vector<double> t = h_table(re, m, omega[s]);
-        tabs.insert(tabs.end(), t.begin(), t.end());
-    }
-    batch_free(c); // nothing is refused from here on: the batch before goes, whatever its size
-    if ((rc = batch_alloc(c, nsys, tabs))) {
-        batch_free(c);
+    std::vector<double> tabs;
+    if ((rc = h_tables(c, nsys, omega, tabs))) return rc;
+    systems_free(T); // nothing is refused from here on: the batch before goes, whatever its size
+    if ((rc = systems_alloc(c, T, nsys))) {
+        systems_free(T);
         return rc;
     }
-    H.bn = nsys;
+    EC3D_HIP(hipMemcpy(T.tab, tabs.data(), tabs.size() * sizeof(double), hipMemcpyHostToDevice));
+    T.n = nsys;
     for (int32_t s = 0; s < nsys; ++s) {
-        H.bomega[s] = omega[s];
-        H.blast[s].ready = 1;
-        H.blast[s].omega = omega[s];
-        H.blast[s].device_bytes = H.bbytes;
+        T.omega[s] = omega[s];
+        T.last[s].ready = 1;
+        T.last[s].omega = omega[s];
+        T.last[s].device_bytes = T.bytes;
     }
     return 0;
 }
 
 extern "C" int ec3d_harmonic_batch_upload(ec3d_handle c, int32_t sys, int which, const double *re, const double *im)
 {
-    int rc = hb_need(c, "ec3d_harmonic_batch_upload", sys, false);
-    if (rc) return rc;
-    if ((rc = h_which(which, "ec3d_harmonic_batch_upload"))) return rc;
-    if (!re) {
-        ec3d_set_error("ec3d_harmonic_batch_upload: re is NULL");
-        return 2;
-    }
-    if ((rc = h_to_device(c, c->harm.bstage, hbv(c, sys, which == EC3D_VEC_X ? HV_X : HV_B), re, im))) return rc;
-    EC3D_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    return h_upload(c, "ec3d_harmonic_batch_upload", true, sys, which, re, im);
 }
 
 extern "C" int ec3d_harmonic_batch_download(ec3d_handle c, int32_t sys, int which, double *re, double *im)
 {
-    int rc = hb_need(c, "ec3d_harmonic_batch_download", sys, false);
-    if (rc) return rc;
-    if ((rc = h_which(which, "ec3d_harmonic_batch_download"))) return rc;
-    if (!re || !im) {
-        ec3d_set_error("ec3d_harmonic_batch_download: re or im is NULL");
-        return 2;
-    }
-    return h_to_host(c, c->harm.bstage, hbv(c, sys, which == EC3D_VEC_X ? HV_X : HV_B), re, im);
+    return h_download(c, "ec3d_harmonic_batch_download", true, sys, which, re, im);
 }
 
 extern "C" int ec3d_harmonic_batch_solve(ec3d_handle c, double tol, int32_t itmax, int32_t *iter)
 {
     int rc = hb_need(c, "ec3d_harmonic_batch_solve", 0, true);
     if (rc) return rc;
-    Harmonic &H = c->harm;
-    if (H.null_on) {
+    if (c->harm.one.null.on) {
         ec3d_set_error("ec3d_harmonic_batch_solve: ec3d_harmonic_set_null_projection is on, and its vectors belong to one omega; "
                        "switch it off, or solve the systems one by one (ec3d_harmonic_batch_select)");
         return 2;
     }
-    if (H.bnull_on && !H.bnull_built && (rc = batch_null_build(c))) return rc;
-    const auto t_start = std::chrono::steady_clock::now();
-    batch_launch_begin(c, tol, H.bnull_on != 0);
-    EC3D_HIP(hipGetLastError());
-    std::vector<HarmonicState> st;
-    if ((rc = batch_run_iterations(c, itmax, st))) return rc;
-    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
-    for (int s = 0; s < H.bn; ++s) {
-        const HarmonicState &q = st[(size_t)s];
-        h_report(H.blast[s], q, q.stop_s != INT_MAX || q.stop_r != INT_MAX, (int64_t)itmax + 1);
-        H.blast[s].ms = ms;
-        if (iter) iter[s] = H.blast[s].iter;
-    }
-    if (H.bnull_on) return batch_null_note(c, st);
+    HarmonicSystems &T = c->harm.batch;
+    if ((rc = h_solve(c, T, tol, itmax))) return rc;
+    for (int s = 0; iter && s < T.n; ++s) iter[s] = T.last[s].iter;
     return 0;
 }
 
@@ -1887,8 +1557,8 @@ extern "C" int ec3d_get_harmonic_batch(ec3d_handle c, int32_t sys, ec3d_harmonic
         ec3d_set_error("ec3d_get_harmonic_batch: info is NULL");
         return 2;
     }
-    *out = c->harm.blast[sys];
-    out->device_bytes += c->harm.bnull_bytes; // the left null vectors of the batch, while they exist
+    *out = c->harm.batch.last[sys];
+    out->device_bytes += c->harm.batch.null.bytes; // the left null vectors of the batch, while they exist
     return 0;
 }
 
@@ -1896,25 +1566,18 @@ extern "C" int ec3d_harmonic_batch_select(ec3d_handle c, int32_t sys)
 {
     int rc = hb_need(c, "ec3d_harmonic_batch_select", sys, false);
     if (rc) return rc;
-    if ((rc = ec3d_harmonic_setup(c, c->harm.bomega[sys]))) return rc;
+    const HarmonicSystems &T = c->harm.batch;
+    if ((rc = ec3d_harmonic_setup(c, T.omega[sys]))) return rc;
     const size_t bytes = (size_t)c->A.n_pad * sizeof(cplx);
-    EC3D_HIP(hipMemcpyAsync(hv(c, HV_X), hbv(c, sys, HV_X), bytes, hipMemcpyDeviceToDevice, c->stream));
-    EC3D_HIP(hipMemcpyAsync(hv(c, HV_B), hbv(c, sys, HV_B), bytes, hipMemcpyDeviceToDevice, c->stream));
+    EC3D_HIP(hipMemcpyAsync(hv(c, HV_X), sysv(c, T, sys, HV_X), bytes, hipMemcpyDeviceToDevice, c->stream));
+    EC3D_HIP(hipMemcpyAsync(hv(c, HV_B), sysv(c, T, sys, HV_B), bytes, hipMemcpyDeviceToDevice, c->stream));
     EC3D_HIP(hipStreamSynchronize(c->stream));
     return 0;
 }
 
 extern "C" int ec3d_harmonic_batch_device_vector(ec3d_handle c, int32_t sys, int which, double **device_ptr, int64_t *pairs)
 {
-    int rc = hb_need(c, "ec3d_harmonic_batch_device_vector", sys, false);
-    if (rc) return rc;
-    if (which < 0 || which >= HV_N || !device_ptr || !pairs) {
-        ec3d_set_error("ec3d_harmonic_batch_device_vector: unknown vector or NULL argument");
-        return 2;
-    }
-    *device_ptr = reinterpret_cast<double *>(hbv(c, sys, which));
-    *pairs = c->A.n_pad;
-    return 0;
+    return h_device_vector(c, "ec3d_harmonic_batch_device_vector", true, sys, which, device_ptr, pairs);
 }
 
 // ---- left null vectors inside a batch ----------------------------------------------------------
@@ -1927,23 +1590,15 @@ extern "C" int ec3d_harmonic_batch_set_null_projection(ec3d_handle c, int32_t on
     if (!on) { // the handle is checked as everywhere; only the batch is not asked for.  The vectors stay with the batch
         const int rc = h_need(c, "ec3d_harmonic_batch_set_null_projection", false);
         if (rc) return rc;
-        c->harm.bnull_on = 0;
+        c->harm.batch.null.on = 0;
         return 0;
     }
-    int rc = hb_need(c, "ec3d_harmonic_batch_set_null_projection", 0, true);
+    const int rc = hb_need(c, "ec3d_harmonic_batch_set_null_projection", 0, true);
     if (rc) return rc; // (the setting as it was)
-    Harmonic &H = c->harm;
-    const double tol = null_tol > 0.0 ? null_tol : 1e-10;
-    if (tol != H.bnull_tol && H.bnull_built) {
-        EC3D_HIP(hipStreamSynchronize(c->stream));
-        batch_null_free(c); // another accuracy: the vectors are made again
-    }
-    H.bnull_on = 1;
-    H.bnull_tol = tol;
-    return 0;
+    return h_null_switch_on(c, c->harm.batch.null, null_tol);
 }
 
-extern "C" int ec3d_get_harmonic_batch_null(ec3d_handle c, int32_t sys, ec3d_null_info *info, int32_t *shares_with)
+extern "C" int ec3d_get_harmonic_batch_null(ec3d_handle c, int32_t sys, ec3d_null_info *info, int32_t *shares)
 {
     int rc = hb_need(c, "ec3d_get_harmonic_batch_null", sys, false);
     if (rc) return rc;
@@ -1951,37 +1606,14 @@ extern "C" int ec3d_get_harmonic_batch_null(ec3d_handle c, int32_t sys, ec3d_nul
         ec3d_set_error("ec3d_get_harmonic_batch_null: info is NULL");
         return 2;
     }
-    const Harmonic &H = c->harm;
-    *info = H.bnull_built ? H.bnull_last[H.bnset_of[sys]] : ec3d_null_info{};
-    info->on = H.bnull_on;
-    info->null_tol = H.bnull_tol;
-    info->built = H.bnull_built ? 1 : 0;
-    info->removed = H.bnremoved[sys];
-    if (shares_with) *shares_with = batch_shares_with(H, sys);
+    h_null_info(c->harm.batch.null, sys, info);
+    if (shares) *shares = shares_with(c->harm.batch, sys);
     return 0;
 }
 
 extern "C" int ec3d_harmonic_batch_left_null_vector(ec3d_handle c, int32_t sys, int32_t index, double *re, double *im)
 {
-    int rc = hb_need(c, "ec3d_harmonic_batch_left_null_vector", sys, false);
-    if (rc) return rc;
-    Harmonic &H = c->harm;
-    if (!H.bnull_built) {
-        if (!H.bnull_on) {
-            ec3d_set_error("ec3d_harmonic_batch_left_null_vector: no vectors yet and the projection is off "
-                           "(ec3d_harmonic_batch_set_null_projection)");
-            return 2;
-        }
-        if ((rc = batch_null_build(c))) return rc;
-    }
-    const int d = H.bnset_of[sys], kept = H.bnkept[d];
-    if (index < 0 || index >= kept || !re || !im) {
-        ec3d_set_error("ec3d_harmonic_batch_left_null_vector: index " + std::to_string(index) + " is outside the " +
-                       std::to_string(kept) + " vectors kept for system " + std::to_string(sys) + ", or a NULL argument");
-        return 2;
-    }
-    return h_to_host(c, H.bstage, reinterpret_cast<const cplx *>(H.bnq.get()) + ((size_t)d * H.bncomp + (size_t)index) * c->A.n_pad,
-                     re, im);
+    return h_left_null_vector(c, "ec3d_harmonic_batch_left_null_vector", true, sys, index, re, im);
 }
 
 extern "C" int ec3d_harmonic_batch_null_restarts(ec3d_handle c, int32_t sys, int32_t *restarts)
@@ -1992,8 +1624,7 @@ extern "C" int ec3d_harmonic_batch_null_restarts(ec3d_handle c, int32_t sys, int
         ec3d_set_error("ec3d_harmonic_batch_null_restarts: restarts is NULL");
         return 2;
     }
-    const Harmonic &H = c->harm;
-    for (int i = 0; i < EC3D_NULL_MAX_REPORT; ++i) restarts[i] = H.bnull_built ? H.bnull_restarts[H.bnset_of[sys]][i] : 0;
+    h_null_restarts(c->harm.batch.null, sys, restarts);
     return 0;
 }
 
@@ -2001,24 +1632,20 @@ extern "C" int ec3d_harmonic_batch_projected_residual(ec3d_handle c, double *rel
 {
     int rc = hb_need(c, "ec3d_harmonic_batch_projected_residual", 0, true);
     if (rc) return rc;
-    Harmonic &H = c->harm;
-    if (!H.bnull_on || !rel) {
+    HarmonicSystems &T = c->harm.batch;
+    if (!T.null.on || !rel) {
         ec3d_set_error(!rel ? "ec3d_harmonic_batch_projected_residual: rel is NULL"
                             : "ec3d_harmonic_batch_projected_residual: the projection is off "
                               "(ec3d_harmonic_batch_set_null_projection)");
         return 2;
     }
-    if (!H.bnull_built && (rc = batch_null_build(c))) return rc;
-    batch_launch_begin(c, 0.0, true);
-    EC3D_HIP(hipGetLastError());
-    std::vector<HarmonicState> st((size_t)H.bn);
-    EC3D_HIP(hipMemcpyAsync(st.data(), H.bstate, st.size() * sizeof(HarmonicState), hipMemcpyDeviceToHost, c->stream));
-    EC3D_HIP(hipStreamSynchronize(c->stream));
-    if ((rc = batch_null_note(c, st))) return rc;
-    for (int s = 0; s < H.bn; ++s) {
+    std::vector<HarmonicState> st;
+    if ((rc = h_residual(c, T, true, st))) return rc;
+    for (int s = 0; s < T.n; ++s) {
         const HarmonicState &q = st[(size_t)s];
         rel[s] = q.bnorm > 0.0 ? q.rnorm / q.bnorm : q.rnorm;
-        if (removed) removed[s] = H.bnremoved[s];
+        if (removed) removed[s] = T.null.removed[s];
     }
     return 0;
 }
+

@@ -420,63 +420,51 @@ struct NullProjection {
 // ec3d_harmonic_* (ec3d_harmonic.hip): the time-harmonic operator K + j omega M on the class bytes
 // of the structured A-V form.  re and m are made by every ec3d_assemble (k_build_table_harmonic beside
 // k_build_table_sav: the transient table without its dt terms, and the unit imaginary table); everything else by
-// ec3d_harmonic_setup only.  Belongs to the matrix (ec3d_free_matrix).
+// ec3d_harmonic_setup and ec3d_harmonic_batch_setup only.  Belongs to the matrix (ec3d_free_matrix).
 enum { HV_X = 0, HV_B, HV_R, HV_R0, HV_P, HV_AP, HV_S, HV_AS, HV_N };
 struct HarmonicState; // the solve's scalars and exit words on the device (ec3d_harmonic.hip)
-struct Harmonic {
-    DevBuf<double> re, m;   // [ncls * 16] each
-    bool ready = false;     // ec3d_harmonic_setup ran on this matrix
-    double omega = 0.0;
-    DevBuf<double> tab;     // [ncls * 16] (re, omega * m) pairs: what k_h_spmv holds in LDS
-    DevBuf<double> vec_own; // HV_N vectors of n_pad (re, im) pairs, device numbering, no ghosts
-    double *vec[HV_N] = {nullptr};
-    DevBuf<double> stage;   // [2 * n_pad] a real and an imaginary part in device numbering (host copies)
-    DevBuf<double> part;    // [HP_NSLOT * wgs] per-workgroup partial sums
+
+// The left null vectors of a HarmonicSystems (DESIGN sections 18a, 18c): one orthonormal set per DISTINCT omega, found by
+// adjoint solves that run in lock step in the work vectors, partials and states of the systems 0 .. sets - 1.  The
+// setting (on, tol) belongs to the handle, everything else to the systems AND their omegas.
+struct HarmonicNull {
+    int on = 0;
+    double tol = 1e-10;
+    bool built = false;
+    int sets = 0, ncomp = 0;                     // ncomp: the conducting components, the room of a set
+    int set_of[EC3D_HARMONIC_MAX_BATCH] = {0};   // system -> set
+    int first[EC3D_HARMONIC_MAX_BATCH] = {0};    // set -> its lowest system
+    int kept[EC3D_HARMONIC_MAX_BATCH] = {0};     // per set
+    DevBuf<double> q;          // vector i of set d: the n_pad pairs at q + (d * ncomp + i) * 2 * n_pad
+    DevBuf<double> y, tab;     // the batch only: per set the unknown of its adjoint solve and the table of its omega
+    DevBuf<double> part, coef; // per SYSTEM [2 * ncomp * wgs] partials of its coefficients' parts, [2 * ncomp] coefficients
+    int64_t bytes = 0;
+    double removed[EC3D_HARMONIC_MAX_BATCH] = {0.0};     // per system, of its last projection
+    ec3d_null_info last[EC3D_HARMONIC_MAX_BATCH] = {};   // per set
+    int32_t restarts[EC3D_HARMONIC_MAX_BATCH][EC3D_NULL_MAX_REPORT] = {{0}}; // of the adjoint solves, per set (tests)
+};
+
+// n systems (omega_s, b^_s, x^_s) solved in lock step: system s has its HV_N vectors of n_pad (re, im) pairs (device
+// numbering, no ghosts) at vec + s * HV_N * 2 * n_pad, its table of [ncls * 16] (re, omega_s * m) pairs at
+// tab + s * 2 * ncls * 16, its per-workgroup partial sums at part + s * HP_NSLOT * wgs, and state[s].
+struct HarmonicSystems {
+    int n = 0;
+    double omega[EC3D_HARMONIC_MAX_BATCH] = {0.0};
+    DevBuf<double> vec, tab, part;
+    DevBuf<double> stage; // [2 * n_pad] a real and an imaginary part in device numbering (host copies)
     DevBuf<HarmonicState> state;
     int wgs = 0;
-    ec3d_harmonic_info last{};
-    // ec3d_harmonic_set_null_projection: the orthonormal left null vectors of K + j omega M, vector
-    // i the n_pad pairs at nq + i * 2 * n_pad.  The setting (null_on, null_tol) belongs to the handle, Q to the matrix
-    // AND to omega.
-    int null_on = 0;
-    double null_tol = 1e-10;
-    bool null_built = false;
-    int null_kept = 0;
-    DevBuf<double> nq;
-    DevBuf<double> npart, ncoef; // [2 * kept * wgs] partials of the coefficients' parts, [2 * kept] the coefficients
-    int64_t null_bytes = 0;
-    ec3d_null_info null_last{};
-    int32_t null_restarts[EC3D_NULL_MAX_REPORT] = {0}; // of the adjoint solves (tests; ec3d_null_info has no room)
-    // ec3d_harmonic_batch_* (DESIGN section 18b): nsys systems (omega_s, b^_s, x^_s) solved in lock step on this matrix.
-    // Storage of its own, made by ec3d_harmonic_batch_setup only: system s has its HV_N vectors at
-    // bvec + s * HV_N * 2 * n_pad, its table at btab + s * 2 * ncls * 16, its partials at bpart + s * HP_NSLOT * bwgs
-    // and bstate[s].  Belongs to the matrix; ec3d_harmonic_setup leaves it alone.
-    int bn = 0;
-    double bomega[EC3D_HARMONIC_MAX_BATCH] = {0.0};
-    DevBuf<double> bvec, btab, bpart, bstage; // bstage: [2 * n_pad], the host copies of the batch
-    DevBuf<HarmonicState> bstate;
-    int bwgs = 0;
-    int64_t bbytes = 0;
-    ec3d_harmonic_info blast[EC3D_HARMONIC_MAX_BATCH] = {};
-    // ec3d_harmonic_batch_set_null_projection: one set of left null vectors per DISTINCT omega of
-    // the batch, found by adjoint solves that run in lock step in the work vectors, partials and states of the systems
-    // 0 .. bnsets - 1.  Vector i of set d: the n_pad pairs at bnq + (d * bncomp + i) * 2 * n_pad; bny: one staging
-    // vector per set, the unknown of its adjoint solve; bntab: the table of set d's omega; bnpart, bncoef: per SYSTEM
-    // the partials and the coefficients of its projection.  The setting (bnull_on, bnull_tol) belongs to the handle, the
-    // rest to the batch (batch_free).
-    int bnull_on = 0;
-    double bnull_tol = 1e-10;
-    bool bnull_built = false;
-    int bnsets = 0, bncomp = 0;
-    int bnset_of[EC3D_HARMONIC_MAX_BATCH] = {0};   // system -> set
-    int bnfirst[EC3D_HARMONIC_MAX_BATCH] = {0};    // set -> its lowest system
-    int bnkept[EC3D_HARMONIC_MAX_BATCH] = {0};     // per set
-    DevBuf<double> bnq, bny, bntab, bnpart, bncoef;
-    int64_t bnull_bytes = 0;
-    double bnull_setup_ms = 0.0;
-    double bnremoved[EC3D_HARMONIC_MAX_BATCH] = {0.0};  // per system, of its last projection
-    ec3d_null_info bnull_last[EC3D_HARMONIC_MAX_BATCH] = {}; // per set
-    int32_t bnull_restarts[EC3D_HARMONIC_MAX_BATCH][EC3D_NULL_MAX_REPORT] = {{0}};
+    int64_t bytes = 0;
+    ec3d_harmonic_info last[EC3D_HARMONIC_MAX_BATCH] = {};
+    HarmonicNull null;
+};
+
+// one: the system of ec3d_harmonic_setup (n = 1 once it ran), which keeps its vectors across omegas.  batch: the
+// systems of ec3d_harmonic_batch_setup, storage of their own that every set-up makes anew;
+// ec3d_harmonic_setup leaves it alone.
+struct Harmonic {
+    DevBuf<double> re, m; // [ncls * 16] each
+    HarmonicSystems one, batch;
 };
 
 struct ec3d_ctx {
@@ -912,8 +900,7 @@ int ec3d_null_prepare(ec3d_ctx *c);               // in front of the solve: buil
 int ec3d_null_project(ec3d_ctx *c);               // behind the residual launch of ec3d_launch_begin, before its set-up
 int ec3d_null_note(ec3d_ctx *c, double bnorm);    // behind the solve: `removed` of ec3d_get_null_projection
 // ec3d_harmonic.hip
-void ec3d_harmonic_free(ec3d_ctx *c); // the tables, vectors and setting of ec3d_harmonic_setup go (a new matrix)
-void ec3d_harmonic_null_free(ec3d_ctx *c); // Q of the harmonic operator goes (a new matrix or omega); the setting stays
+void ec3d_harmonic_free(ec3d_ctx *c); // the tables, the single system and the batch go (a new matrix); the settings stay
 // ec3d_output.hip
 void ec3d_free_output(ec3d_ctx *c);
 // ec3d_rhs.hip

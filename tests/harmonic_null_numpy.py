@@ -1,5 +1,5 @@
-"""Numpy restatement of the left null vectors of the time-harmonic operator and their projection (k_h_spmv_h, the
-set-up and the k_hn_* kernels of csrc/ec3d_harmonic.hip), bit for bit.
+"""Numpy restatement of the left null vectors of the time-harmonic operator and their projection (k_hb_spmv_h, the
+set-up and the k_hbn_* kernels of csrc/ec3d_harmonic.hip), bit for bit.
 
     OperatorH            y = A^H x, A = K + j omega M of harmonic_numpy.Operator: row j adds the entries of column j of
                          A in ascending SOURCE row from +0.0, a term conj(a) x = (ar xr + ai xi, ar xi - ai xr), every

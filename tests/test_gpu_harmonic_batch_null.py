@@ -11,6 +11,8 @@ Every test here fails on a library without the entry points.
   call's R with the setting off, bit for bit, on g2 and on g3 with padded planes;
 * whole solves: itmax = 1, 5, 20 and tol 1e-6 on g2 and g8a, per system, against the twin and the single projected solve;
 * systems with bit-equal omega share one set of vectors; no cross-talk from a zero and a NaN right-hand side;
+* a batch of one system == the single set-up and the single projected solve, bit for bit, and three systems of one omega
+  (one set for S = 3): device_bytes by the formula, so the single projection has no staging vector and the batch has one;
 * a null_tol no solve reaches; the contract (off again is a fresh handle; what clears the vectors; the real vectors, the
   rings and the single solve's own Q and setting are untouched); refusals; host.run_harmonic_sweep and the command line."""
 import ctypes as C
@@ -312,6 +314,90 @@ def test_systems_with_equal_omega_share_one_set_of_vectors(E):
         assert rep[k] == (it_t, rs_t, kind_t, rel_t) and solved[k] == (it_t, rel_t) and kind_t != 0
         assert info[k]["removed"] == removed_t
         _same(x[k], xt, f"system {k} against its twin")
+
+
+def _stream_wgs(n_pad):
+    return min(n_pad // DS.TILE, DS.WGS)        # ec3d_stream_wgs
+
+
+def test_a_batch_of_one_is_the_single_projected_solve(E):
+    """The single solve and the batch are one code path at S = 1 and S > 1: a batch of one system with the projection on
+    against the single set-up and the single projected solve on the same handle, bit for bit; the single projection's
+    memory is Q, its partials and its coefficients, with no staging vector and no table of its own."""
+    g = golden(G8A)
+    b = _rhs(g)
+    n, w = len(b), _w(50.0)
+    x0 = 1e-3 * _random_complex(n, 95)
+    runs = ((0.0, 5, x0), (1e-6, 2000, np.zeros(n)))      # (from zero every g8a system exits below 1e-6)
+    with E.EC3DSolver() as s:
+        _assemble(s, g)
+        n_pad = s.vector_layout()["n_pad"]
+        _batch(s, [w], [b], [x0])
+        s.harmonic_batch_set_null_projection(True, NULL_TOL)
+        W = _vectors(s, 0)
+        info = s.harmonic_batch_null_projection(0)
+        got = []
+        for tol, itmax, xin in runs:
+            s.harmonic_batch_upload(0, "X", xin)
+            solved = s.harmonic_batch_solve(tol, itmax)
+            got.append((s.harmonic_batch_download(0, "X"), _report(s, 0), s.harmonic_batch_null_projection(0)["removed"], solved))
+        s.harmonic_setup(w)
+        base = s.harmonic_info()["device_bytes"]
+        s.harmonic_set_null_projection(True, NULL_TOL)
+        V = [s.harmonic_left_null_vector(0)]
+        info1 = s.harmonic_null_projection()
+        V += [s.harmonic_left_null_vector(i) for i in range(1, info1["kept"])]
+        grew = s.harmonic_info()["device_bytes"] - base
+        s.harmonic_set_null_projection(False)
+        single = [_single_projected(s, w, b, xin, tol, itmax) for tol, itmax, xin in runs]
+    ncomp = 2
+    print(f"batch of one {info['components']}, single {info1['components']}; reports {[q[1] for q in got]}, single "
+          f"{[q[1] for q in single]}; device_bytes of the single projection {grew}")
+    assert info["built"] and info1["built"] and info["shares_with"] == 0
+    assert info["found"] == info1["found"] == info["kept"] == info1["kept"] == len(W) == len(V) == ncomp
+    assert info["components"] == info1["components"]          # seed_row, iterations, residual, kept, restarts
+    for i in range(ncomp):
+        _same(W[i], V[i], f"kept vector {i}: the batch of one against the single set-up")
+    for (tol, itmax, _), (x, rep, removed, solved), (x1, rep1, removed1, _) in zip(runs, got, single):
+        assert rep == rep1 and removed == removed1 and solved == [(rep1[0], rep1[3])]
+        _same(x, x1, f"X^ behind tol = {tol:g}, itmax = {itmax}: the batch of one against the single projected solve")
+    assert got[0][1][0] == 6 and got[0][1][2] == 0 and got[1][1][2] in (1, 2) and got[1][1][3] < 1e-6
+    assert grew == (ncomp * 2 * n_pad + 2 * ncomp * _stream_wgs(n_pad) + 2 * ncomp) * 8
+
+
+def test_three_systems_of_one_omega_share_one_set(E):
+    """D = 1 < S: one set of vectors, one staging vector and one table for three systems, partials and coefficients per
+    system; equal right-hand sides give equal bits."""
+    g = golden(G2)
+    b = _rhs(g)
+    n, w, S = len(b), _w(50.0), 3
+    x0 = 1e-3 * _random_complex(n, 96)
+    with E.EC3DSolver() as s:
+        _assemble(s, g)
+        n_pad = s.vector_layout()["n_pad"]
+        _batch(s, [w] * S, [b] * S, [x0] * S)
+        base = s.harmonic_batch_info(0)["device_bytes"]
+        s.harmonic_batch_set_null_projection(True, NULL_TOL)
+        solved = s.harmonic_batch_solve(0.0, 5)
+        grew = s.harmonic_batch_info(0)["device_bytes"] - base
+        info = [s.harmonic_batch_null_projection(k) for k in range(S)]
+        rep = [_report(s, k) for k in range(S)]
+        x = [s.harmonic_batch_download(k, "X") for k in range(S)]
+    assert [q["shares_with"] for q in info] == [0] * S and info[0]["built"]
+    D, ncomp, G = 1, info[0]["found"], _stream_wgs(n_pad)
+    assert ncomp == info[0]["kept"] == 1
+    # the batch itself: S * (8 vectors of 2 n_pad + a table of 2 nt + 10 * G partials) + 2 n_pad of staging doubles and S
+    # states of 112 bytes; nt = 16 pairs per class, which no report shows, from there
+    words, odd = divmod(base - 112 * S, 8)
+    per_system, odd2 = divmod(words - 2 * n_pad, S)
+    two_nt = per_system - 16 * n_pad - 10 * G
+    assert odd == 0 and odd2 == 0 and two_nt > 0 and two_nt % 32 == 0
+    print(f"device_bytes: batch {base}, its projection {grew}; n_pad {n_pad}, G {G}, classes {two_nt // 32}")
+    assert grew == (D * ncomp * 2 * n_pad + D * 2 * n_pad + D * two_nt + S * 2 * ncomp * G + S * 2 * ncomp) * 8
+    assert [it for it, _ in solved] == [6] * S and rep[1] == rep[0] and rep[2] == rep[0]
+    assert info[1]["removed"] == info[0]["removed"] == info[2]["removed"] > 0.0
+    for k in (1, 2):
+        _same(x[k], x[0], f"X^ of system {k} against system 0's")
 
 
 def test_no_cross_talk(E):

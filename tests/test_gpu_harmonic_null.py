@@ -1,5 +1,5 @@
-"""The left null vectors of the time-harmonic operator on the device (ec3d_harmonic_set_null_projection, k_h_spmv_h and
-the k_hn_* kernels of csrc/ec3d_harmonic.hip) against the twin (tests/harmonic_null_numpy.py).
+"""The left null vectors of the time-harmonic operator on the device (ec3d_harmonic_set_null_projection, k_hb_spmv_h and
+the k_hbn_* kernels of csrc/ec3d_harmonic.hip) against the twin (tests/harmonic_null_numpy.py).
 Every test here fails on a library without the entry points.
 
 * harmonic_spmv_h == the twin's OperatorH BIT FOR BIT on g2, g2v, g8a, g9b, g3 with padded planes and the 96 x 96 x 64 box
@@ -8,7 +8,7 @@ Every test here fails on a library without the entry points.
 * the set-up on g2, g8a, g9b: iterations, restarts and every kept vector equal left_null_vectors bit for bit, the
   report's residual to 1e-12 relative; X^ and B^ keep their bytes;
 * the projection: R, R0, P behind harmonic_solve(tol, -1) == project_device of the device's own Q and of the same call's
-  R with the projection off, bit for bit, on g2, g2 with padded planes and the box; ||R|| as k_h_setup took it from the
+  R with the projection off, bit for bit, on g2, g2 with padded planes and the box; ||R|| as k_hb_setup took it from the
   partials the subtraction left;
 * whole solves: itmax = 1, 5, 20 on g2 and g8a equal bicgstab_projected bit for bit; tol 1e-6 on five fixtures and 1e-8
   on g3, g8a, g9b converge within 2000 iterations to a projected residual <= 10 tol that equals the twin's, where the
@@ -187,7 +187,7 @@ def test_the_projection_equals_the_twin_bit_for_bit(E, monkeypatch, case):
     for nm, v in zip(("R", "R0", "P"), got):
         assert np.array_equal(_bits(v[rm]), _bits(want[rm])), f"{nm}: {np.count_nonzero(v[rm] != want[rm])} rows differ"
     assert not np.array_equal(_bits(want[rm]), _bits(plain[0][rm]))        # (it did something)
-    assert relres == np.sqrt(DS.strided(rr)) / bnorm                     # the HP_RR partials, as k_h_setup read them
+    assert relres == np.sqrt(DS.strided(rr)) / bnorm                     # the HP_RR partials, as k_hb_setup read them
     wb = float(np.sqrt(np.sum(np.abs(c) ** 2)) / bnorm)
     assert abs(info["removed"] - wb) <= 1e-6 * wb
 
