@@ -21,13 +21,14 @@ OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(PKG, "libec3d_hip.so")
 SOURCES = ["ec3d_kernels.hip", "ec3d_context.hip", "ec3d_solve.hip", "ec3d_measure.hip", "ec3d_dist.hip", "ec3d_multi.hip",
            "ec3d_rccl.cpp", "ec3d_dropin.hip", "ec3d_assemble.hip", "ec3d_rhs.hip", "ec3d_output.hip", "ec3d_format.cpp",
-           "ec3d_sav_csr.cpp", "ec3d_mg.hip", "ec3d_integrals.hip", "ec3d_guess.hip", "ec3d_transpose.hip",
+           "ec3d_sav_csr.cpp", "ec3d_mg.hip", "ec3d_outer.hip", "ec3d_integrals.hip", "ec3d_guess.hip", "ec3d_transpose.hip",
            "ec3d_null.hip", "ec3d_probes.hip", "ec3d_harmonic.hip"]
 HEADERS = [os.path.join(CSRC, "ec3d_internal.hpp"), os.path.join(CSRC, "ec3d_form.hpp"), os.path.join(CSRC, "ec3d_own.hpp"),
            os.path.join(CSRC, "ec3d_rccl.hpp"), os.path.join(CSRC, "ec3d_avmg_plan.hpp"),
            os.path.join(CSRC, "ec3d_mg_plan.hpp"), os.path.join(CSRC, "ec3d_sweep_lists.hpp"),
            os.path.join(CSRC, "ec3d_recurrence.hpp"), os.path.join(CSRC, "ec3d_slab_plan.hpp"),
-           os.path.join(CSRC, "ec3d_split_sweeps.hpp"), os.path.join(CSRC, "ec3d_stream.hpp"), os.path.join(os.path.dirname(PKG), "include", "ec3d_hip.h")]
+           os.path.join(CSRC, "ec3d_split_sweeps.hpp"), os.path.join(CSRC, "ec3d_stream.hpp"), os.path.join(CSRC, "ec3d_outer.hpp"),
+           os.path.join(os.path.dirname(PKG), "include", "ec3d_hip.h")]
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 LDFLAGS = ["--offload-arch=gfx950", "-shared", "-fPIC", "-ldl"]
 

@@ -301,7 +301,7 @@ struct DevMatrix {
 };
 
 struct ec3d_mg; // multigrid hierarchy (ec3d_mg.hip)
-// beta and the restart decision of the outer iteration of ec3d_mg.hip, left on the device by k_mg_scalar
+// beta and the restart decision of the outer iteration (ec3d_outer.hip), left on the device by k_mg_scalar
 struct MgScalars {
     double beta;
     int restart;
@@ -406,7 +406,7 @@ struct NullProjection {
     int64_t len = 0;
     DevBuf<double> q;
     DevBuf<double> part, coef; // per-workgroup partials (kept slots of wgs), the collapsed sums
-    DevBuf<double> kpart;      // the adjoint iteration's partials (ec3d_plain_begin)
+    DevBuf<double> kpart;      // the adjoint iteration's partials (ec3d_outer_begin)
     DevBuf<MgScalars> kscal;
     int wgs = 0;
     ec3d_null_info last{};
@@ -858,33 +858,12 @@ int ec3d_guess_clear(ec3d_ctx *c);  // no pair stored, the vectors zero again
 int ec3d_guess_project(ec3d_ctx *c, const MatView &A);            // in front of ec3d_launch_begin
 int ec3d_guess_note_setup(ec3d_ctx *c);                           // behind it
 int ec3d_guess_update(ec3d_ctx *c, const MatView &A, bool store); // behind the solve and ec3d_flush_x; one read-back
-// ec3d_mg.hip: the outer iteration with M = I and an operator the caller launches (apply(x, y) enqueues y = Op x on
-// c->stream): the adjoint solves of ec3d_null.hip.  Rows [0, n) of every vector; k.r holds the right-hand side (the
-// solve starts from x = 0).  State, exits and restart rule are the solve's own (c->state, ec3d_recurrence.hpp).
-struct PlainKrylov {
-    int64_t n;
-    double *x, *r, *r0, *p, *v, *s, *t;
-    double *part;     // 2 * ec3d_plain_parts(n) doubles
-    MgScalars *scal;
-};
-int ec3d_plain_parts(int64_t n);
-int ec3d_plain_begin(ec3d_ctx *c, const PlainKrylov &k, double tol);
-template <class Apply> void ec3d_plain_iteration(ec3d_ctx *c, const PlainKrylov &k, int it, const Apply &apply);
-void ec3d_plain_stage(ec3d_ctx *c, const PlainKrylov &k, int it, int stage); // 0: behind v = Op p, 1: behind t = Op s
-template <class Apply> void ec3d_plain_iteration(ec3d_ctx *c, const PlainKrylov &k, int it, const Apply &apply)
-{
-    apply(k.p, k.v);
-    ec3d_plain_stage(c, k, it, 0);
-    apply(k.s, k.t);
-    ec3d_plain_stage(c, k, it, 1);
-}
 // ec3d_mg.hip: N ~ (A^T)^-1 of ec3d_set_null_precond -- a block hierarchy of its own (kind: EC3D_NULL_PRECOND_BLOCK_MG
-// or _A; 0 sweeps: the defaults), which the caller deletes; one right-preconditioned iteration with A^T and N in k's
-// vectors (p^ and s^ are the hierarchy's); levels and 3 dims per level of the hierarchy
+// or _A; 0 sweeps: the defaults), which the caller deletes; levels and 3 dims per level of the hierarchy.  The adjoint
+// solves that use it: ec3d_outer.hpp
 int ec3d_null_mg_build(ec3d_ctx *c, int kind, int pre, int post, int coarse, ec3d_mg **out);
 void ec3d_null_mg_delete(ec3d_mg *m);
 void ec3d_null_mg_dims(const ec3d_mg *m, int32_t *levels, int32_t *dims);
-void ec3d_null_mg_iteration(ec3d_ctx *c, const ec3d_mg *m, const PlainKrylov &k, int it);
 // ec3d_transpose.hip: y = A^T x on rows [0, A.n) of the structured form (x, y: device vectors, no ghosts needed)
 void ec3d_launch_spmv_t(const MatView &A, int64_t n, const double *x, double *y, hipStream_t s);
 // ec3d_null.hip: the left null vectors around a solve (solve_core, when nullp.on)

@@ -1,5 +1,6 @@
-// ec3d_mg.hip — geometric multigrid preconditioner of the single-component operator (ec3d_assemble_poisson) and the
-// right-preconditioned BiCGSTAB-with-restart that uses it (ec3d_set_preconditioner).
+// ec3d_mg.hip — geometric multigrid preconditioner of the single-component operator (ec3d_assemble_poisson), the block
+// multigrid of the structured A-V form, and what each hands to the outer iteration of ec3d_outer.hip: its cycle and its
+// operator (ec3d_set_preconditioner; DESIGN.md sections 9, 10).
 //
 // Hierarchy: level 0 is the handle's own matrix; every coarser level is the same device assembly
 // (ec3d_assemble_poisson_level) at half the cells and twice the spacing on each axis that is even and >= 8, with the
@@ -34,9 +35,9 @@
 // above instantiated with T = float; p^ and s^ are then fp32 vectors the outer kernels widen on load, and the outer
 // iteration stays fp64 (tests/mg_numpy_f32.py restates it).
 //
-// EC3D_PRECOND_BLOCK_MG (the structured A-V form) shares the outer iteration's vector kernels;
-// its own kernels (k_avmg_*) are below, behind the single-component ones.  N of ec3d_set_null_precond (section 16a) is
-// the same hierarchy on the transposed blocks, a BlockMg of the null set-up's own around the same outer iteration.
+// EC3D_PRECOND_BLOCK_MG (the structured A-V form): its kernels (k_avmg_*) are below, behind the
+// single-component ones.  N of ec3d_set_null_precond (section 16a) is the same hierarchy on the transposed blocks, a
+// BlockMg of the null set-up's own; ec3d_adjoint_iteration runs the outer iteration around it, or around M = I.
 //
 // Host side: a handle's ec3d_mg owns one hierarchy (PoissonMg<double>, PoissonMg<float> or BlockMg), built completely
 // before it replaces the old one; launch_schedule is the cycle's order of launches for all three.
@@ -47,8 +48,7 @@
 #include "../../include/ec3d_hip.h"
 #include "ec3d_avmg_plan.hpp"
 #include "ec3d_mg_plan.hpp"
-#include "ec3d_stream.hpp"
-#include "ec3d_recurrence.hpp"
+#include "ec3d_outer.hpp"
 
 #include <array>
 #include <climits>
@@ -61,7 +61,6 @@
 #define EC3D_MG_COARSE_ROWS 4096 // x of the coarsest level in LDS (32 KiB), b and class bytes in registers
 #define EC3D_MG_COARSE_THREADS 1024
 #define EC3D_MG_MAXCLS 32        // dictionary classes a level may have (the single-component operator has 28)
-#define EC3D_MG_DOT_BLOCKS 2048  // workgroups of the reducing kernels (grid-stride)
 
 // T: the precision of the level's coefficients and vectors (double; float for the fp32 V-cycle, EC3D_PRECOND_FP32)
 template <class T> struct MgOpT {
@@ -162,25 +161,6 @@ struct ec3d_mg {
 };
 
 namespace {
-
-// ---- gating: every launch of iteration `it` is a no-op once the solve has stopped before it (strict = 0) or at it
-// (strict = 1: the launches behind the ||S|| exit's check).  st == nullptr: not inside a solve (ec3d_precond_apply).
-struct Gate {
-    const SolverState *st;
-    int it, strict;
-};
-__device__ __forceinline__ bool gated_off(const Gate &g)
-{
-    if (!g.st) return false;
-    const int s = g.st->stop_iter; // written by an earlier launch on the stream: an ordinary load sees it
-    return g.strict ? s <= g.it : s < g.it;
-}
-__device__ __forceinline__ void mg_stop_publish(SolverState *st, int it, int kind)
-{
-    __hip_atomic_store(reinterpret_cast<unsigned long long *>(&st->stop_iter),
-                       (unsigned long long)(unsigned)it | ((unsigned long long)(unsigned)kind << 32), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-}
 
 template <class T> __device__ __forceinline__ void load_table(const MgOpT<T> &A, T *tbl)
 {
@@ -507,9 +487,9 @@ __global__ __launch_bounds__(256) void k_mg_gather(MgSrc S, double *__restrict__
     for (int q = 0; q < 7; ++q) out[(size_t)q * S.n_pad + r] = S.band[q] >= 0 ? src_coef(S, S.band[q], r) : 0.0;
 }
 
-// ---- outer iteration ------------------------------------------------------------------------------------------------
-// The reducing kernels are grid-strided over rows (thread t of workgroup b takes the rows b * 256 + t + m * 256 * gridDim.x
-// in increasing m); their workgroup sums and the scalar launch's collapse are ec3d_stream.hpp's.
+// ---- the outer iteration's operator on level 0 (its other kernels: ec3d_outer.hip) ----------------------------------
+// Grid-strided over rows like them (thread t of workgroup b takes the rows b * 256 + t + m * 256 * gridDim.x in
+// increasing m); the workgroup sums are ec3d_stream.hpp's.
 // y = A x (rows summed in offset order from the -z term); partials of a.y (slot 0) and, with two, y.y (slot 1).
 // Bytes per row: x 8 + a 8 + 1 class byte read, y 8 written = 25 B.
 // TX = float: x is p^ / s^ of the fp32 V-cycle, widened on load (exact); every product and sum stays fp64 (21 B).
@@ -546,123 +526,6 @@ __global__ __launch_bounds__(256) void k_mg_spmv_dot(MgOp A, Gate g, const TX *_
         if (threadIdx.x == 0) part[gridDim.x + blockIdx.x] = d1;
     }
 }
-
-// s = r - alpha v; partial s.s.  Bytes per row: 16 read, 8 written.
-__global__ __launch_bounds__(256) void k_mg_s(int64_t n, Gate g, const SolverState *st, const double *__restrict__ r,
-                                              const double *__restrict__ v, double *__restrict__ s,
-                                              double *__restrict__ part)
-{
-    __shared__ double lds[4];
-    if (gated_off(g)) return;
-    const double alpha = st->alpha;
-    double d = 0.0;
-    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (int64_t)gridDim.x * blockDim.x) {
-        const double sv = r[q] - alpha * v[q];
-        s[q] = sv;
-        d = d + sv * sv;
-    }
-    d = stream_block_sum(d, lds);
-    if (threadIdx.x == 0) part[blockIdx.x] = d;
-}
-
-// x = x + alpha p^ + omega s^;  r = s - omega t;  partials r.r, r.r0.  After the ||S|| exit of this iteration only
-// x = x + alpha p^ (src/solvers.f90:34-37).  Bytes per row: x, p^, s^, s, t, r0 read 48, x, r written 16 = 64 B.
-// TX = float: p^ and s^ of the fp32 V-cycle, widened on load (56 B).
-template <class TX = double>
-__global__ __launch_bounds__(256) void k_mg_xr(int64_t n, int it, const SolverState *st, double *__restrict__ x,
-                                               const TX *__restrict__ ph, const TX *__restrict__ sh,
-                                               const double *__restrict__ s, const double *__restrict__ t,
-                                               const double *__restrict__ r0, double *__restrict__ r,
-                                               double *__restrict__ part)
-{
-    __shared__ double lds[4];
-    const int stop = st->stop_iter;
-    if (stop < it) return;
-    const double alpha = st->alpha, omega = st->omega;
-    const bool s_exit = stop == it;
-    double d0 = 0.0, d1 = 0.0;
-    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (int64_t)gridDim.x * blockDim.x) {
-        if (s_exit) {
-            x[q] = x[q] + alpha * (double)ph[q];
-            continue;
-        }
-        x[q] = x[q] + alpha * (double)ph[q] + omega * (double)sh[q];
-        const double rv = s[q] - omega * t[q];
-        r[q] = rv;
-        d0 = d0 + rv * rv;
-        d1 = d1 + rv * r0[q];
-    }
-    if (s_exit) return;
-    d0 = stream_block_sum(d0, lds);
-    if (threadIdx.x == 0) part[blockIdx.x] = d0;
-    d1 = stream_block_sum(d1, lds);
-    if (threadIdx.x == 0) part[gridDim.x + blockIdx.x] = d1;
-}
-
-// p = r + beta (p - omega v), or the restart r0 = r, p = r (src/solvers.f90:46-49).  Bytes per row: 24 read, 8 (16) written.
-__global__ __launch_bounds__(256) void k_mg_p(int64_t n, Gate g, const SolverState *st, const MgScalars *ms,
-                                              const double *__restrict__ r, const double *__restrict__ v,
-                                              double *__restrict__ p, double *__restrict__ r0)
-{
-    if (gated_off(g)) return;
-    const double beta = ms->beta, omega = st->omega;
-    const bool restart = ms->restart != 0;
-    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (int64_t)gridDim.x * blockDim.x) {
-        if (restart) {
-            p[q] = r[q];
-            r0[q] = r[q];
-        } else {
-            p[q] = r[q] + beta * (p[q] - omega * v[q]);
-        }
-    }
-}
-
-// The scalar steps, one workgroup; partials summed in a fixed order (thread-strided, then the workgroup tree).
-enum { MG_ALPHA = 0, MG_SEXIT = 1, MG_OMEGA = 2, MG_REXIT = 3 };
-__global__ __launch_bounds__(256) void k_mg_scalar(int stage, Gate g, SolverState *st, MgScalars *ms,
-                                                   const double *__restrict__ part, int nparts, double *hist,
-                                                   int64_t hist_cap)
-{
-    __shared__ double lds[4];
-    if (gated_off(g)) return;
-    const int nslot = (stage == MG_OMEGA || stage == MG_REXIT) ? 2 : 1;
-    double v[2] = {0.0, 0.0};
-    for (int sl = 0; sl < nslot; ++sl) {
-        v[sl] = stream_block_sum(stream_strided_sum(part + (int64_t)sl * nparts, nparts), lds);
-    }
-    if (threadIdx.x != 0) return;
-    const int it = g.it;
-    const int64_t h = (int64_t)(it - 1) * 2;
-    switch (stage) {
-    // the rules themselves: ec3d_recurrence.hpp
-    case MG_ALPHA: st->alpha = ec3d_alpha(st->rr0[it & 1], v[0]); break; // (:31-32)
-    case MG_SEXIT: {
-        const Ec3dNorm s = ec3d_snorm_step(v[0], st->bnorm, st->tol);
-        if (it - 1 < hist_cap) hist[h] = s.norm;
-        if (s.exit) mg_stop_publish(st, it, 1); // (:34-38)
-        break;
-    }
-    case MG_OMEGA: st->omega = ec3d_omega(v[0], v[1]); break; // (:40)
-    case MG_REXIT: {
-        const Ec3dNorm rn = ec3d_rnorm_step(v[0], st->bnorm, st->tol);
-        if (it - 1 < hist_cap) hist[h + 1] = rn.norm;
-        st->rnorm = rn.norm;
-        if (rn.exit) { // (:43)
-            mg_stop_publish(st, it, 2);
-            break;
-        }
-        const Ec3dBeta b = ec3d_beta_step(st->alpha, st->omega, v[1], st->rr0[it & 1], v[0], st->bnorm, st->tol); // (:45-49)
-        ms->beta = b.beta;
-        ms->restart = b.restart;
-        if (b.restart) st->restarts = st->restarts + 1;
-        st->rr0[(it + 1) & 1] = b.rr0_next;
-        break;
-    }
-    }
-}
-
-inline unsigned blocks_of(int64_t n, int t = 256) { return (unsigned)((n + t - 1) / t); }
-inline unsigned dot_blocks(int64_t n) { return (unsigned)std::min<int64_t>(EC3D_MG_DOT_BLOCKS, std::max<int64_t>(1, blocks_of(n))); }
 
 MgOp op_of(const DevMatrix &A, int sdx, int sdy, int sdz)
 {
@@ -1158,26 +1021,6 @@ __global__ __launch_bounds__(256) void k_avmg_umean(Gate g, const int32_t *__res
     if (threadIdx.x == 0) umean[blockIdx.x] = a * inv_w[blockIdx.x];
 }
 
-// partials of a.y (slot 0) and, with two, y.y (slot 1), the products summed as k_mg_spmv_dot sums them
-__global__ __launch_bounds__(256) void k_avmg_dot(int64_t n, Gate g, const double *__restrict__ a,
-                                                  const double *__restrict__ y, int two, double *__restrict__ part)
-{
-    __shared__ double lds[4];
-    if (gated_off(g)) return;
-    double d0 = 0.0, d1 = 0.0;
-    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x) {
-        const double s = y[r];
-        d0 = d0 + a[r] * s;
-        d1 = d1 + s * s;
-    }
-    d0 = stream_block_sum(d0, lds);
-    if (threadIdx.x == 0) part[blockIdx.x] = d0;
-    if (two) {
-        d1 = stream_block_sum(d1, lds);
-        if (threadIdx.x == 0) part[gridDim.x + blockIdx.x] = d1;
-    }
-}
-
 // z = M r of the block multigrid (enqueued): one V-cycle on each A block, the U block's sweeps.  r, z: device vectors
 // of the structured form (4 blocks of nCd rows).
 void launch_cycle(const ec3d_mg &m, const BlockMg &h, Gate g, const double *r, double *z, hipStream_t s)
@@ -1560,95 +1403,6 @@ template <class T> static int set_poisson_mg(ec3d_ctx *c, ec3d_mg &m)
     return 0;
 }
 
-// One iteration of the right-preconditioned BiCGSTAB with restart on the structured A-V form: the Poisson hierarchies'
-// algorithm (below), with M the block multigrid, v = A p^ and t = A s^ by the format's own SpMV (ec3d_launch_spmv), then
-// their dot partials (k_avmg_dot: the summation order of k_mg_spmv_dot).  The SpMV launches are not gated: past an exit
-// nothing reads what they write.
-// The vectors, the operator (op(x, y) enqueues y = Op x) and the cycle (cycle(g, r, z) enqueues z = M r) are parameters:
-// the solve runs it in the handle's work vectors with A and M, the null projection's set-up in a PlainKrylov's with A^T
-// and N (ec3d_null_mg_iteration).
-struct OuterVecs {
-    int64_t n;
-    double *x, *r, *r0, *p, *v, *s, *t; // v = Op p^, t = Op s^
-    double *ph, *sh;
-    double *part;
-    MgScalars *scal;
-    double *hist;
-    int64_t hist_cap;
-};
-template <class Cycle, class Op>
-static void launch_block_iteration(ec3d_ctx *c, int it, const OuterVecs &k, const Cycle &cycle, const Op &op)
-{
-    hipStream_t s = c->stream;
-    const int64_t n = k.n;
-    const unsigned nb = dot_blocks(n);
-    const Gate g0{c->state, it, 0}, g1{c->state, it, 1};
-    cycle(g0, k.p, k.ph);
-    op(k.ph, k.v);
-    k_avmg_dot<<<nb, 256, 0, s>>>(n, g0, k.r0, k.v, 0, k.part);
-    k_mg_scalar<<<1, 256, 0, s>>>(MG_ALPHA, g0, c->state, k.scal, k.part, (int)nb, k.hist, k.hist_cap);
-    k_mg_s<<<nb, 256, 0, s>>>(n, g0, c->state, k.r, k.v, k.s, k.part);
-    k_mg_scalar<<<1, 256, 0, s>>>(MG_SEXIT, g0, c->state, k.scal, k.part, (int)nb, k.hist, k.hist_cap);
-    cycle(g1, k.s, k.sh);
-    op(k.sh, k.t);
-    k_avmg_dot<<<nb, 256, 0, s>>>(n, g1, k.s, k.t, 1, k.part);
-    k_mg_scalar<<<1, 256, 0, s>>>(MG_OMEGA, g1, c->state, k.scal, k.part, (int)nb, k.hist, k.hist_cap);
-    k_mg_xr<<<nb, 256, 0, s>>>(n, it, c->state, k.x, (const double *)k.ph, (const double *)k.sh, k.s, k.t, k.r0, k.r, k.part);
-    k_mg_scalar<<<1, 256, 0, s>>>(MG_REXIT, g1, c->state, k.scal, k.part, (int)nb, k.hist, k.hist_cap);
-    k_mg_p<<<nb, 256, 0, s>>>(n, g1, c->state, k.scal, k.r, k.v, k.p, k.r0);
-}
-
-static void launch_iteration_of(ec3d_ctx *c, int it, const BlockMg &h)
-{
-    const ec3d_mg *m = c->mg;
-    double **v = c->vec;
-    hipStream_t s = c->stream;
-    const MatView V = c->A.view();
-    const OuterVecs k{c->A.n, v[EC3D_VEC_X], v[EC3D_VEC_R], v[EC3D_VEC_R0], v[EC3D_VEC_P], v[EC3D_VEC_AP], v[EC3D_VEC_S],
-                      v[EC3D_VEC_AS], h.ph, h.sh, m->part, m->scal, c->hist, c->hist_cap};
-    launch_block_iteration(c, it, k, [&](Gate g, const double *r, double *z) { launch_cycle(*m, h, g, r, z, s); },
-                           [&](const double *x, double *y) { ec3d_launch_spmv(V, c->sweep_s, x, y, s); });
-}
-
-// The same iteration with M = I (p^ = p, s^ = s) around an operator the caller launches: ec3d_plain_iteration of
-// ec3d_internal.hpp calls stage 0 behind v = Op p and stage 1 behind t = Op s.
-int ec3d_plain_parts(int64_t n) { return (int)dot_blocks(n); }
-
-int ec3d_plain_begin(ec3d_ctx *c, const PlainKrylov &k, double tol)
-{
-    hipStream_t s = c->stream;
-    const unsigned nb = dot_blocks(k.n);
-    const size_t bytes = (size_t)k.n * sizeof(double);
-    EC3D_HIP(hipMemsetAsync(k.x, 0, bytes, s));
-    EC3D_HIP(hipMemcpyAsync(k.r0, k.r, bytes, hipMemcpyDeviceToDevice, s));
-    EC3D_HIP(hipMemcpyAsync(k.p, k.r, bytes, hipMemcpyDeviceToDevice, s));
-    // b.b and r.r of the set-up (slots P_BB, P_RR_INIT) are the same sum: r = b
-    k_avmg_dot<<<nb, 256, 0, s>>>(k.n, Gate{nullptr, 0, 0}, k.r, k.r, 1, k.part);
-    ec3d_launch_setup(c->state, RedSrc{k.part, (int)nb, 1, (int)nb, nullptr}, tol, s);
-    EC3D_HIP(hipGetLastError());
-    return 0;
-}
-
-void ec3d_plain_stage(ec3d_ctx *c, const PlainKrylov &k, int it, int stage)
-{
-    hipStream_t s = c->stream;
-    const int64_t n = k.n;
-    const unsigned nb = dot_blocks(n);
-    const Gate g0{c->state, it, 0}, g1{c->state, it, 1};
-    if (stage == 0) {
-        k_avmg_dot<<<nb, 256, 0, s>>>(n, g0, k.r0, k.v, 0, k.part);
-        k_mg_scalar<<<1, 256, 0, s>>>(MG_ALPHA, g0, c->state, k.scal, k.part, (int)nb, nullptr, 0);
-        k_mg_s<<<nb, 256, 0, s>>>(n, g0, c->state, k.r, k.v, k.s, k.part);
-        k_mg_scalar<<<1, 256, 0, s>>>(MG_SEXIT, g0, c->state, k.scal, k.part, (int)nb, nullptr, 0);
-        return;
-    }
-    k_avmg_dot<<<nb, 256, 0, s>>>(n, g1, k.s, k.t, 1, k.part);
-    k_mg_scalar<<<1, 256, 0, s>>>(MG_OMEGA, g1, c->state, k.scal, k.part, (int)nb, nullptr, 0);
-    k_mg_xr<<<nb, 256, 0, s>>>(n, it, c->state, k.x, (const double *)k.p, (const double *)k.s, k.s, k.t, k.r0, k.r, k.part);
-    k_mg_scalar<<<1, 256, 0, s>>>(MG_REXIT, g1, c->state, k.scal, k.part, (int)nb, nullptr, 0);
-    k_mg_p<<<nb, 256, 0, s>>>(n, g1, c->state, k.scal, k.r, k.v, k.p, k.r0);
-}
-
 // ---- N, the preconditioner of the null projection's adjoint solves (ec3d_set_null_precond) -------
 // A hierarchy of its own, built inside the null set-up (or for one ec3d_null_precond_apply) and released by the caller
 // before it returns: c->mg, the caller's preconditioner, is neither read nor written.
@@ -1683,14 +1437,16 @@ void ec3d_null_mg_dims(const ec3d_mg *m, int32_t *levels, int32_t *dims)
     }
 }
 
-void ec3d_null_mg_iteration(ec3d_ctx *c, const ec3d_mg *m, const PlainKrylov &k, int it)
+void ec3d_adjoint_iteration(ec3d_ctx *c, const ec3d_mg *m, const OuterRun &k, int it)
 {
-    const BlockMg &h = std::get<BlockMg>(m->h);
+    const BlockMg *h = m ? &std::get<BlockMg>(m->h) : nullptr;
     hipStream_t s = c->stream;
     const MatView V = c->A.view();
-    const OuterVecs o{k.n, k.x, k.r, k.r0, k.p, k.v, k.s, k.t, h.ph, h.sh, k.part, k.scal, nullptr, 0};
-    launch_block_iteration(c, it, o, [&](Gate g, const double *r, double *z) { launch_cycle(*m, h, g, r, z, s); },
-                           [&](const double *x, double *y) { ec3d_launch_spmv_t(V, k.n, x, y, s); });
+    OuterRun o = k;
+    if (h) o.ph = h->ph, o.sh = h->sh;
+    ec3d_outer_iteration(
+        c, o, it, false, [&](Gate g, const double *r, void *z) { if (h) launch_cycle(*m, *h, g, r, (double *)z, s); },
+        [&](Gate, const void *x, const double *, double *y, int) { ec3d_launch_spmv_t(V, k.n, (const double *)x, y, s); });
 }
 
 void ec3d_mg_free(ec3d_ctx *c)
@@ -1909,35 +1665,40 @@ int ec3d_mg_chunk(const ec3d_ctx *c)
     return (int)std::min<double>(16.0, std::max<double>(1.0, 1000.0 / est_us));
 }
 
-// One iteration of the right-preconditioned BiCGSTAB with restart (src/solvers.f90:24-50 with P, S replaced by their
-// preconditioned images in the products with A and the X update):
-//   p^ = M p; v = A p^; alpha = rho / (r0.v); s = r - alpha v; [exit on ||s|| / ||b||: x += alpha p^]
-//   s^ = M s; t = A s^; omega = (t.s)/(t.t); x += alpha p^ + omega s^; r = s - omega t; [exit on ||r|| / ||b||]
-//   beta = (alpha / omega) (r.r0) / rho; p = r + beta (p - omega v); restart as the reference.
-// The work vectors: v in AP, t in AS.  Sums and exits stay on the device; launches past an exit are no-ops.
-// T: the precision of M and of p^, s^ (ph, sh), which the SpMV + dot launch and the x / r update widen on load; every
-// other operand and operation of the outer iteration is fp64 in both.
+// The run of a solve (ec3d_outer.hpp): the handle's work vectors, v in AP and t in AS, with the hierarchy's p^ and s^
+// and the history the caller asked for.
+static OuterRun solve_run(ec3d_ctx *c, int64_t n, void *ph, void *sh, bool f32)
+{
+    double **v = c->vec;
+    return OuterRun{n, v[EC3D_VEC_X], v[EC3D_VEC_R], v[EC3D_VEC_R0], v[EC3D_VEC_P], v[EC3D_VEC_AP], v[EC3D_VEC_S],
+                    v[EC3D_VEC_AS], ph, sh, f32, c->mg->part, c->mg->scal, c->hist, c->hist_cap};
+}
+
+// The single-component operator.  T: the precision of M and of p^, s^, which the SpMV + dot launch and the x / r update
+// widen on load.  The product's launch sums its dot partials itself.
 template <class T> static void launch_iteration_of(ec3d_ctx *c, int it, const PoissonMg<T> &h)
 {
     const ec3d_mg *m = c->mg;
-    double **v = c->vec;
     hipStream_t s = c->stream;
     const MgOp &A = h.op0;
-    const int64_t n = A.n;
-    const unsigned nb = dot_blocks(n);
-    const Gate g0{c->state, it, 0}, g1{c->state, it, 1};
-    launch_cycle(*m, h, g0, v[EC3D_VEC_P], h.ph, s);
-    MG_LAUNCH(k_mg_spmv_dot, nb, 256, A, g0, (const T *)h.ph, v[EC3D_VEC_R0], v[EC3D_VEC_AP], 0, m->part);
-    k_mg_scalar<<<1, 256, 0, s>>>(MG_ALPHA, g0, c->state, m->scal, m->part, (int)nb, c->hist, c->hist_cap);
-    k_mg_s<<<nb, 256, 0, s>>>(n, g0, c->state, v[EC3D_VEC_R], v[EC3D_VEC_AP], v[EC3D_VEC_S], m->part);
-    k_mg_scalar<<<1, 256, 0, s>>>(MG_SEXIT, g0, c->state, m->scal, m->part, (int)nb, c->hist, c->hist_cap);
-    launch_cycle(*m, h, g1, v[EC3D_VEC_S], h.sh, s);
-    MG_LAUNCH(k_mg_spmv_dot, nb, 256, A, g1, (const T *)h.sh, v[EC3D_VEC_S], v[EC3D_VEC_AS], 1, m->part);
-    k_mg_scalar<<<1, 256, 0, s>>>(MG_OMEGA, g1, c->state, m->scal, m->part, (int)nb, c->hist, c->hist_cap);
-    k_mg_xr<<<nb, 256, 0, s>>>(n, it, c->state, v[EC3D_VEC_X], (const T *)h.ph, (const T *)h.sh, v[EC3D_VEC_S],
-                               v[EC3D_VEC_AS], v[EC3D_VEC_R0], v[EC3D_VEC_R], m->part);
-    k_mg_scalar<<<1, 256, 0, s>>>(MG_REXIT, g1, c->state, m->scal, m->part, (int)nb, c->hist, c->hist_cap);
-    k_mg_p<<<nb, 256, 0, s>>>(n, g1, c->state, m->scal, v[EC3D_VEC_R], v[EC3D_VEC_AP], v[EC3D_VEC_P], v[EC3D_VEC_R0]);
+    const OuterRun k = solve_run(c, A.n, h.ph, h.sh, std::is_same_v<T, float>);
+    ec3d_outer_iteration(
+        c, k, it, true, [&](Gate g, const double *r, void *z) { launch_cycle(*m, h, g, r, (T *)z, s); },
+        [&](Gate g, const void *x, const double *a, double *y, int two) {
+            MG_LAUNCH(k_mg_spmv_dot, dot_blocks(A.n), 256, A, g, (const T *)x, a, y, two, k.part);
+        });
+}
+
+// The structured A-V form: M the block multigrid, v = A p^ and t = A s^ by the format's own SpMV (ec3d_launch_spmv)
+static void launch_iteration_of(ec3d_ctx *c, int it, const BlockMg &h)
+{
+    const ec3d_mg *m = c->mg;
+    hipStream_t s = c->stream;
+    const MatView V = c->A.view();
+    ec3d_outer_iteration(
+        c, solve_run(c, c->A.n, h.ph, h.sh, false), it, false,
+        [&](Gate g, const double *r, void *z) { launch_cycle(*m, h, g, r, (double *)z, s); },
+        [&](Gate, const void *x, const double *, double *y, int) { ec3d_launch_spmv(V, c->sweep_s, (const double *)x, y, s); });
 }
 
 void ec3d_mg_launch_iteration(ec3d_ctx *c, int it)

@@ -2,16 +2,16 @@
 // (ec3d_set_null_projection).
 //
 // Set-up, once per matrix (ec3d_null_prepare): the connected components of the conducting cells on the host; per
-// component the adjoint solve A^T y = -A^T e_m from y = 0 -- the outer iteration of ec3d_mg.hip with M = I
-// (ec3d_plain_iteration) around ec3d_launch_spmv_t, in the work vectors R, R0, P, AP, S, AS, which are free between two
-// solves (X and B are the caller's and stay), or with ec3d_set_null_precond the right-preconditioned one around N, a
-// block hierarchy this set-up builds and releases (ec3d_null_mg_*, section 16a) -- then w = y + e_m, its residual, and classical Gram-Schmidt against the
-// vectors kept so far.  In front of a solve (ec3d_null_project): c_i = Q_i.R, R = R - c_1 Q_1 - ... - c_k Q_k, R0 = R,
-// P = R, and the partials of R.R where the solve's set-up kernel looks for them.
+// component the adjoint solve A^T y = -A^T e_m from y = 0 -- the outer iteration of ec3d_outer.hip around
+// ec3d_launch_spmv_t (ec3d_outer_begin, ec3d_adjoint_iteration), in the work vectors R, R0, P, AP, S, AS, which are free
+// between two solves (X and B are the caller's and stay); M = I, or with ec3d_set_null_precond M = N, a block hierarchy
+// this set-up builds and releases (ec3d_null_mg_*, section 16a) -- then w = y + e_m, its residual, and classical
+// Gram-Schmidt against the vectors kept so far.  In front of a solve (ec3d_null_project): c_i = Q_i.R,
+// R = R - c_1 Q_1 - ... - c_k Q_k, R0 = R, P = R, and the partials of R.R where the solve's set-up kernel looks for them.
 //
 // Sums and streaming launches: ec3d_stream.hpp.  One partial per workgroup and vector; k_null_collapse, one workgroup per
 // vector, collapses them.
-#include "ec3d_stream.hpp"
+#include "ec3d_outer.hpp"
 
 #include <chrono>
 #include <cmath>
@@ -179,8 +179,7 @@ int build(ec3d_ctx *c)
     EC3D_HIP(hipMemsetAsync(N.q, 0, (size_t)ncomp * len * sizeof(double), c->stream));
     EC3D_HIP(N.part.alloc((size_t)ncomp * N.wgs));
     EC3D_HIP(N.coef.alloc((size_t)ncomp + 2));
-    const int kparts = ec3d_plain_parts(n);
-    EC3D_HIP(N.kpart.alloc((size_t)2 * kparts));
+    EC3D_HIP(N.kpart.alloc((size_t)2 * dot_blocks(n)));
     EC3D_HIP(N.kscal.alloc(1));
     EC3D_HIP(hipMemsetAsync(N.kscal, 0, sizeof(MgScalars), c->stream));
     double **v = c->vec;
@@ -212,19 +211,16 @@ int build(ec3d_ctx *c)
         k_null_add_one<<<1, 1, 0, c->stream>>>(v[EC3D_VEC_S], row);
         apply(v[EC3D_VEC_S], v[EC3D_VEC_AS]);
         k_null_scale<<<(unsigned)N.wgs, EC3D_THREADS, 0, c->stream>>>(v[EC3D_VEC_AS], -1.0, v[EC3D_VEC_R], n, nc);
-        const PlainKrylov K{n, w, v[EC3D_VEC_R], v[EC3D_VEC_R0], v[EC3D_VEC_P], v[EC3D_VEC_AP], v[EC3D_VEC_S], v[EC3D_VEC_AS],
-                            N.kpart, N.kscal};
-        int rc = ec3d_plain_begin(c, K, null_tol);
+        const OuterRun K{n, w, v[EC3D_VEC_R], v[EC3D_VEC_R0], v[EC3D_VEC_P], v[EC3D_VEC_AP], v[EC3D_VEC_S], v[EC3D_VEC_AS],
+                         v[EC3D_VEC_P], v[EC3D_VEC_S], false, N.kpart, N.kscal, nullptr, 0}; // p^ = p, s^ = s; no history
+        int rc = ec3d_outer_begin(c, K, null_tol);
         if (rc) return rc;
         SolverState st;
         int64_t launched = 0;
         bool stopped = false;
         while (launched < total && !stopped) {
             const int64_t m = std::min<int64_t>(16, total - launched);
-            for (int64_t i = 0; i < m; ++i) {
-                if (nmg.m) ec3d_null_mg_iteration(c, nmg.m, K, (int)(++launched));
-                else ec3d_plain_iteration(c, K, (int)(++launched), apply);
-            }
+            for (int64_t i = 0; i < m; ++i) ec3d_adjoint_iteration(c, nmg.m, K, (int)(++launched));
             EC3D_HIP(hipGetLastError());
             EC3D_HIP(hipMemcpyAsync(&st, c->state, sizeof st, hipMemcpyDeviceToHost, c->stream));
             EC3D_HIP(hipStreamSynchronize(c->stream));

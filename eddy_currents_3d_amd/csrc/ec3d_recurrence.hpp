@@ -1,7 +1,7 @@
 // ec3d_recurrence.hpp — the scalar steps of BiCGSTAB with restart (src/solvers.f90:31-49), each stated ONCE.
 //
 // Pure functions of doubles: no device state, no pointers, no HIP types, so the kernels (ec3d_kernels.hip,
-// k_mg_scalar in ec3d_mg.hip) and a plain C++ program (tests/support/recurrence_cases.cpp) compile the same
+// k_mg_scalar in ec3d_outer.hip) and a plain C++ program (tests/support/recurrence_cases.cpp) compile the same
 // text.  Every operation is one rounded IEEE operation, in the operand order written here (the library is built
 // with -ffp-contract=off); a zero divisor gives inf or NaN as the expression gives it -- nothing is caught.
 // The oracle does not include this header: it is the checker.

@@ -1,5 +1,5 @@
 // ec3d_stream.hpp — the fixed-order sums and the streaming idiom of every kernel outside the iteration's hot path
-// (ec3d_guess.hip, ec3d_null.hip, ec3d_integrals.hip, the outer iteration of ec3d_mg.hip; DESIGN.md "Fixed-order sums").
+// (ec3d_guess.hip, ec3d_null.hip, ec3d_integrals.hip, ec3d_mg.hip, ec3d_outer.hip; DESIGN.md "Fixed-order sums").
 // The hot path's own block_sum (ec3d_kernels.hip) is another function: no leading 0.0, valid in every thread.
 //
 // Summation chain (no float atomics: a result is a pure function of its inputs; tests/device_sums_numpy.py restates it):
